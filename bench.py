@@ -7,10 +7,13 @@ OILMM, Orthogonal(U,S) 64x32, 32 Matern52 latents, n = 16384, Float64.  It fits 
 run at every N with the 32 latents sharded over the ranks (strong scaling; one scalar all-reduce per step).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c1dense|c0|small|notebook|c3]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the field definitions).
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the field definitions).  A plain run sets up, warms up, times the K
+steps and prints it; `--full` adds the secondary figures after the timed steps (the instrumented roofline pass and what hangs on
+it, the CPU baseline).  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -52,6 +55,20 @@ FP64_MFMA_PEAK_TFLOPS = 78.6      # AMD MI355X datasheet FP64 matrix (= vector) 
                                   # rate.  Measured here: v_mfma_f64_16x16x4_f64 with VGPR accumulators issues at 77.7 TFLOP/s
                                   # (tools/mfma_probe4, profiles/r02) = 98.9 % of it, so 78.6 is the denominator.
 HBM_PEAK_GBS = 8000.0             # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # --dump-outputs: the .npy files, headers included, stay under 64 MB
+
+
+def dump_outputs(outdir, arrays):
+    """Write each output as outdir/<name>.npy in float64.  Above DUMP_LIMIT_BYTES in all, every array is cut to the same share of
+    its entries at positions drawn by a fixed seed, so that two runs with the same arguments write the same positions."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(v.cpu() if hasattr(v, "cpu") else v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, a.size * DUMP_LIMIT_BYTES // total, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def build_model(lmm, P):
@@ -149,9 +166,16 @@ def main():
                     help="compute dtype of the per-latent matrices (lmm_set_compute_dtype); f64 is the parity mode")
     ap.add_argument("--proj", default="native", choices=["native", "bf16", "bf16x2"],
                     help="dtype of the H unprojection of predictive marginals (lmm_set_projection_dtype); bf16 = BASELINE configs[3] as named")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the instrumented roofline pass (per-kernel rates, measured write and MFMA "
+                         "ceilings, the 8-GPU share) and the CPU baseline; a plain run reports the timed steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline pass")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; a fixed seeded sample above 64 MB)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU) through
@@ -228,6 +252,7 @@ def main():
     red = torch.zeros(1, dtype=torch.float64, device=rdev)
     red_host = np.zeros(1)
     stats = {"allreduce_s": 0.0, "nonfinite_partials": 0, "last_partial": None}      # this rank's diagnostics (per_rank in the JSON line)
+    last = {}            # the arrays the last step returned to its caller (--dump-outputs)
 
     predictive = (args.workload == "c3")
     sampling = (args.workload == "c4")
@@ -246,6 +271,7 @@ def main():
             else:
                 pc = part.cpu(); dist.all_reduce(pc); part = pc
             stats["allreduce_s"] += time.perf_counter() - ta
+        last["sample"] = part
         return float(part[0])
 
     if predictive:
@@ -254,6 +280,7 @@ def main():
     def step_predictive():
         post = lmm_amd.posterior(fx, yd)                                            # this rank's latents only
         mean, var = lmm_amd.sharded_mean_and_var(post(xs_in, s2))                   # one all-reduce of 2 x p x n* doubles
+        last["mean"], last["var"] = mean, var
         return float(mean[0])
 
     def step():
@@ -301,15 +328,17 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt[0])
     steps = max(args.steps, 1)
-    # --steps 0: roofline leg only (used for the rocprofv3 summary of the serial-stream pass); value is then null
+    # --full --steps 0: roofline leg only (used for the rocprofv3 summary of the serial-stream pass); value is then null
     evals_per_s = (steps * (world if not orth else 1)) / dt if args.steps > 0 else None   # replicas: every rank runs the job
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last if (predictive or sampling) else {"logpdf": val})
 
     roof = None
     extra = {}
     peak_tf = FP32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else FP64_MFMA_PEAK_TFLOPS
     prof = None
     nprof = min(16, shard[1] - shard[0]) if orth else m     # one production-sized batch of latents (LMM_BATCH default 16)
-    if (rank == 0 or world > 1) and not args.no_roofline and nprof > 0:
+    if (rank == 0 or world > 1) and args.full and not args.no_roofline and nprof > 0:
         # Instrumented pass: one more evaluation of one batch of this rank's latents with every launch of the hot kernels
         # bracketed by HIP events on its stream; the batch runs on ONE stream so that an event pair times its kernel alone (the
         # timed region above runs several batches on concurrent streams).  Rank 0's pass is the roofline leg (DESIGN.md
@@ -442,7 +471,7 @@ def main():
     bad = sum(r["nonfinite_partials"] for r in per_rank)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_predictive(P) if predictive else (cpu_baseline_sampling(P) if sampling else cpu_baseline(P, orth))
 
     if rank == 0:
