@@ -13,7 +13,8 @@
  *           reference src/ilmm.jl:43 `reshape_y`).
  *   - x, y, xs, z, eps and every OUTPUT array may be HOST or DEVICE (HIP) pointers; the library
  *     detects which (hipPointerGetAttributes).  Small model arrays (U, S, H, gps) are host.
- *   - latents are described by lmm_gp_t (ConstMean + variance * kernel(|x-x'| / lengthscale)).
+ *   - latents are described by lmm_gp_t (ConstMean + variance * kernel(|x-x'| / lengthscale)), or with per-dimension lengthscales
+ *     (kernel(|(x-x') ./ l|), l = lengthscale * ard) through an ARD tag in the kind word (lmm_ard_create below).
  *   - `latent_begin, latent_end` select the shard [begin, end) of latent processes this process
  *     (one process per GPU) evaluates; partial results are summed by the caller (RCCL all-reduce
  *     in the Python/Julia host layer).  Use 0, m for the whole model.
@@ -70,9 +71,12 @@ typedef enum {
 
 typedef enum { LMM_KERNEL_SE = 0, LMM_KERNEL_MATERN32 = 1, LMM_KERNEL_MATERN52 = 2 } lmm_kernel_kind;
 
-/* One latent GP: GP(mean, variance * Kernel o ScaleTransform(1/lengthscale)). */
+/* One latent GP: GP(mean, variance * Kernel o ScaleTransform(1/lengthscale)).
+ * kind = base | (tag << 8): the low byte is the lmm_kernel_kind; a non-zero tag (lmm_ard_create) gives the latent per-dimension
+ * lengthscales (KernelFunctions' Kernel o ARDTransform(1 ./ l)): the effective lengthscale of input dimension k is then
+ * lengthscale * ard[k], so `lengthscale` becomes a common multiplier.  A tag may be shared by several latents (tied parameters). */
 typedef struct {
-  int kind;            /* lmm_kernel_kind */
+  int kind;            /* lmm_kernel_kind | (ARD tag << 8) */
   double variance;
   double lengthscale;
   double mean;         /* ConstMean / ZeroMean */
@@ -87,6 +91,25 @@ typedef struct {
 } lmm_jitters_t;
 
 typedef struct lmm_post lmm_post_t;   /* opaque posterior state (device resident) */
+
+/* ---- per-dimension (ARD) lengthscales -------------------------------------------------------
+ * Host-only registry: no device or lmm_init needed, safe from any thread (own mutex, never the context lock).
+ *   lmm_ard_create : registers d > 0 positive finite factors ard[0..d-1]; *tag > 0.  At most 4096 live tags
+ *                    (LMM_ERR_UNSUPPORTED beyond).  Use kind = base_kind | (tag << 8) in lmm_gp_t.
+ *   lmm_ard_destroy: unknown or destroyed tag -> LMM_ERR_ARG.  Posterior handles keep their own copy of the effective
+ *                    lengthscales, so destroying a tag never affects a handle built with it.
+ *   lmm_ard_grad   : d values d logpdf / d ard[k] = lengthscale * d logpdf / d l_k from the most recent gradient entry point that
+ *                    named the tag: summed over that call's latents carrying the tag, partial over its latent shard like grad_gps,
+ *                    zeros if its grad_gps was NULL.  (grad_gps[l].lengthscale of such a latent is the derivative with respect to
+ *                    the multiplier lengthscale.)
+ * Validation in every entry point: the base kind must be 0..2 and the tag live (LMM_ERR_ARG otherwise); the tag's d must equal the
+ * call's d (LMM_ERR_DIM, naming the latent).  With d == 1, or when all ard[k] are equal, the latent is folded into the isotropic
+ * descriptor (lengthscale * ard[0]) before anything runs: its values are then exactly those of the isotropic latent.  The gradient
+ * entry points serve d <= 32 for latents with d > 1 tags (LMM_ERR_UNSUPPORTED beyond). */
+#define LMM_KERNEL_BASE_MASK 0xff
+int lmm_ard_create(int d, const double* lengthscale, int* tag);
+int lmm_ard_destroy(int tag);
+int lmm_ard_grad(int tag, double* out);
 
 /* ---- lifetime -------------------------------------------------------------------------- */
 int lmm_init(int device);                 /* bind this process to HIP device `device`, create streams */

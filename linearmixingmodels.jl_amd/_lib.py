@@ -19,7 +19,7 @@ KERNEL_KINDS = {"se": 0, "matern32": 1, "matern52": 2}
 # Every symbol include/lmm_hip.h declares (tests/test_abi.py checks the library exports each one).
 SYMBOLS = [
     "lmm_init", "lmm_shutdown", "lmm_last_error_string", "lmm_last_error_detail", "lmm_device_synchronize", "lmm_release_cached_memory",
-    "lmm_stream_wait_caller", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
+    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
     "lmm_comm_destroy",
     "lmm_set_strict_progress", "lmm_get_strict_progress", "lmm_dev_claim_scramble", "lmm_orthogonal_validate", "lmm_oilmm_logpdf", "lmm_oilmm_logpdf_grad", "lmm_oilmm_post_logpdf_grad", "lmm_oilmm_post_logpdf_grad_seq", "lmm_ilmm_logpdf_grad", "lmm_ilmm_post_logpdf_grad", "lmm_ilmm_post_logpdf_grad_seq", "lmm_ilmm_post_latent_logpdf_grad_seq", "lmm_oilmm_logpdf_multi", "lmm_reorder", "lmm_ilmm_logpdf", "lmm_ilmm_logpdf_ex", "lmm_ilmm_logpdf_multi", "lmm_mogp_logpdf", "lmm_mogp_logpdf_diag",
     "lmm_oilmm_posterior_create", "lmm_mogp_posterior_create", "lmm_post_condition", "lmm_ilmm_posterior_create", "lmm_post_destroy", "lmm_ilmm_post_latent_view", "lmm_ilmm_post_mean_and_var", "lmm_ilmm_post_mean_and_cov", "lmm_ilmm_post_condition", "lmm_ilmm_post_logpdf", "lmm_ilmm_post_rand",
@@ -305,13 +305,59 @@ def allreduce_sum(a, op: str = "sum"):
     return a
 
 
+KERNEL_BASE_MASK = 0xFF
+
+
+class ArdTags:
+    """Owner of the ARD tags (lmm_ard_create) of one lmm_gp_t array: destroyed with the array (gps_array attaches it as `.ard`).
+    tags[l] is latent l's tag, 0 for an isotropic latent."""
+
+    def __init__(self, m: int):
+        self.tags = [0] * m
+        self._lib = None
+
+    def create(self, l: int, ls: np.ndarray) -> int:
+        self._lib = self._lib or load()
+        t = C.c_int()
+        check(self._lib.lmm_ard_create(int(ls.size), ls.ctypes.data_as(C.POINTER(C.c_double)), C.byref(t)))
+        self.tags[l] = t.value
+        return t.value
+
+    def grad(self, l: int, d: int) -> np.ndarray:
+        """d logpdf / d ard of latent l's tag after a gradient call (its own tag: d / d lengthscale_k, the multiplier being 1)."""
+        out = np.zeros(d)
+        check(self._lib.lmm_ard_grad(self.tags[l], out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def close(self) -> None:
+        if self._lib is not None:
+            for t in self.tags:
+                if t:
+                    self._lib.lmm_ard_destroy(t)
+        self.tags = [0] * len(self.tags)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def gps_array(gps: Sequence[dict]):
+    """lmm_gp_t array of latent descriptors.  A vector "lengthscale" (length d) becomes an ARD latent: a tag holding the vector, kind
+    = base | tag << 8 and lengthscale (the common multiplier) 1.  The tags live as long as the returned array (its `.ard`)."""
     arr = (GpT * max(len(gps), 1))()
+    arr.ard = ArdTags(len(gps))
     for l, g in enumerate(gps):
         a = arr[l]
         a.kind = KERNEL_KINDS[g["kind"]]
         a.variance = float(g.get("variance", 1.0))
-        a.lengthscale = float(g.get("lengthscale", 1.0))
+        ls = g.get("lengthscale", 1.0)
+        if np.ndim(ls) == 0:
+            a.lengthscale = float(ls)
+        else:
+            a.kind |= arr.ard.create(l, np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)) << 8
+            a.lengthscale = 1.0
         a.mean = float(g.get("mean", 0.0))
     return arr
 

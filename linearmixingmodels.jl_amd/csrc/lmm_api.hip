@@ -21,6 +21,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -288,19 +289,194 @@ struct Dims {
   size_t elems() const { return (size_t)ld * NC; }
 };
 
+// ---- per-dimension (ARD) lengthscales ----------------------------------------------------------------------------------------
+// The user-facing registry (lmm_ard_create / _destroy / _grad) maps a tag to d factors and keeps the tag's latest gradient; it has
+// its own mutex and never takes the context lock for longer than a try-lock on an error message.  An entry point RESOLVES the tags of
+// its latents once (resolve_gps, under the context lock): a latent whose factors are all equal (or d == 1) is folded into the
+// isotropic descriptor; every other ARD latent gets its effective inverse lengthscales 1 / (lengthscale * ard[k]) uploaded to the
+// device, and its kind word is rewritten to  base | (slot + 1) << 8  with `slot` an index of g_ils_slot, the table of the device
+// vectors that live calls and posterior handles hold.  Everything downstream reads the base kind (kind & 0xff) and the vector through
+// ils_of(); the slot table is process state guarded by the context lock like the rest of the context.
+#define LMM_ARD_MAX_TAGS 4096
+struct ArdTag { int d; std::vector<double> ard, grad; };
+std::mutex g_ard_mu;
+std::map<int, ArdTag> g_ard_tags;
+int g_ard_next = 1;
+
+std::vector<const double*> g_ils_slot;
+std::vector<int> g_ils_free;
+
+// The resolved ARD state of one call, shared with the posterior handles it builds (and their conditioned successors and views).
+struct ArdSet {
+  int d = 0;
+  std::vector<double> host;                 // effective inverse lengthscales, d per entry
+  Buf<double> dev;                          // the same on the device
+  std::vector<int> slots;                   // g_ils_slot entries this set holds
+  // per latent of the call: user tag (0: none), the caller's lengthscale (the common multiplier), the factor a folded latent's
+  // lengthscale was multiplied by (1 otherwise), and the vector the gradient reduction uses (nullptr: the isotropic reduction)
+  std::vector<int> tag;
+  std::vector<double> mult, fold;
+  std::vector<const double*> gils;
+  ArdSet() = default;
+  ArdSet(const ArdSet&) = delete;
+  ArdSet& operator=(const ArdSet&) = delete;
+  ~ArdSet() { for (int sl : slots) { g_ils_slot[sl] = nullptr; g_ils_free.push_back(sl); } }
+};
+// The ArdSet of the entry point that is running (set by resolve_gps, cleared when the call returns): read by the gradient cores.
+const ArdSet* g_call_ard = nullptr;
+
+inline int base_kind(const lmm_gp_t& gp) { return gp.kind & LMM_KERNEL_BASE_MASK; }
+inline const double* ils_of(const lmm_gp_t& gp) { const int sl = gp.kind >> 8; return sl > 0 ? g_ils_slot[sl - 1] : nullptr; }
+
 LatentDev to_dev(const lmm_gp_t& gp) {
   LatentDev d;
-  d.kind = gp.kind; d.var = gp.variance; d.inv_ls = 1.0 / gp.lengthscale; d.mean = gp.mean;
+  d.kind = base_kind(gp); d.var = gp.variance; d.inv_ls = 1.0 / gp.lengthscale; d.mean = gp.mean; d.ils = ils_of(gp);
   return d;
+}
+// kernel fields of a Gram assembly from a (resolved) latent descriptor
+void set_kernel(GramArgs& a, const lmm_gp_t& gp) {
+  a.kind = base_kind(gp); a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale; a.ils = ils_of(gp);
 }
 
 int check_gps(const lmm_gp_t* gps, int m) {
   if (!gps) return fail(LMM_ERR_ARG, "gps is NULL");
   for (int l = 0; l < m; ++l) {
-    if (gps[l].kind < 0 || gps[l].kind > 2) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
+    const int base = gps[l].kind & LMM_KERNEL_BASE_MASK;
+    if (gps[l].kind < 0 || base > 2) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
     if (!(gps[l].variance > 0.0) || !(gps[l].lengthscale > 0.0)) return fail(LMM_ERR_ARG, "latent %d: variance and lengthscale must be > 0", l);
   }
   return LMM_OK;
+}
+
+// The resolved latents of one call: `v` replaces the caller's array when any latent carries a tag (`ard` then holds the state).
+struct CallGps {
+  std::vector<lmm_gp_t> v;
+  std::shared_ptr<ArdSet> ard;
+  CallGps() = default;
+  CallGps(const CallGps&) = delete;
+  CallGps& operator=(const CallGps&) = delete;
+  ~CallGps() { if (ard && g_call_ard == ard.get()) g_call_ard = nullptr; }
+};
+
+int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
+  if (int rc = check_gps(gps, m)) return rc;
+  bool any = false;
+  for (int l = 0; l < m; ++l) any = any || (gps[l].kind >> 8) != 0;
+  if (!any) return LMM_OK;
+  auto A = std::make_shared<ArdSet>();
+  A->d = d;
+  A->tag.assign(m, 0); A->mult.assign(m, 1.0); A->fold.assign(m, 1.0); A->gils.assign(m, nullptr);
+  out.v.assign(gps, gps + m);
+  std::map<std::pair<int, double>, int> entry_of;     // (tag, multiplier) -> entry: latents sharing both share the vector (and kind word)
+  std::vector<int> ent(m, -1);
+  std::vector<char> folded(m, 0);
+  for (int l = 0; l < m; ++l) {
+    const int tag = gps[l].kind >> 8;
+    if (tag == 0) continue;
+    std::vector<double> ard;
+    {
+      std::lock_guard<std::mutex> lk(g_ard_mu);
+      auto it = g_ard_tags.find(tag);
+      if (it == g_ard_tags.end()) return fail(LMM_ERR_ARG, "latent %d: unknown or destroyed ARD tag %d", l, tag);
+      if (it->second.d != d)
+        return fail(LMM_ERR_DIM, "latent %d: ARD tag %d has %d dimensions, the inputs have %d", l, tag, it->second.d, d);
+      ard = it->second.ard;
+    }
+    const double ls = gps[l].lengthscale;
+    A->tag[l] = tag; A->mult[l] = ls;
+    bool equal = true;
+    for (int k = 1; k < d; ++k) equal = equal && ard[k] == ard[0];
+    out.v[l].kind = base_kind(gps[l]);
+    if (equal) {                       // folded: exactly the isotropic latent of lengthscale ls * ard[0]
+      folded[l] = 1;
+      A->fold[l] = ard[0];
+      out.v[l].lengthscale = ls * ard[0];
+      if (d == 1) continue;            // d == 1: the isotropic reduction gives the one derivative
+    }
+    auto key = std::make_pair(tag, ls);
+    auto it = entry_of.find(key);
+    if (it == entry_of.end()) {
+      it = entry_of.emplace(key, (int)(A->host.size() / d)).first;
+      for (int k = 0; k < d; ++k) A->host.push_back(1.0 / (ls * ard[k]));
+    }
+    ent[l] = it->second;
+  }
+  const int ne = (int)(A->host.size() / std::max(d, 1));
+  if (ne > 0) {
+    A->dev = Buf<double>(A->host.size());
+    // (A->host lives as long as the set, so the copy may complete asynchronously; every launch that reads it is ordered behind st0)
+    HIPCHK(hipMemcpyAsync(A->dev.p, A->host.data(), A->host.size() * sizeof(double), hipMemcpyHostToDevice, g.streams[0]));
+    for (int e = 0; e < ne; ++e) {
+      int sl;
+      if (!g_ils_free.empty()) { sl = g_ils_free.back(); g_ils_free.pop_back(); }
+      else { sl = (int)g_ils_slot.size(); g_ils_slot.push_back(nullptr); }
+      g_ils_slot[sl] = A->dev.p + (size_t)e * d;
+      A->slots.push_back(sl);
+    }
+    for (int l = 0; l < m; ++l) {
+      if (ent[l] < 0) continue;
+      A->gils[l] = A->dev.p + (size_t)ent[l] * d;
+      if (!folded[l]) out.v[l].kind = base_kind(gps[l]) | ((A->slots[ent[l]] + 1) << 8);
+    }
+  }
+  out.ard = A;
+  g_call_ard = A.get();
+  return LMM_OK;
+}
+// Invariant: resolve_gps reads the high 24 bits of `kind` as a USER tag, so it is only ever given a caller's array.  A resolved array
+// (cg_.v, lmm_post.gps) carries slot indices of g_ils_slot there instead and must never be resolved again: internal code passes it
+// straight to the launch helpers (to_dev / set_kernel / ils_of), which read the slot.
+#define RESOLVE_GPS(gps, m, d)                                  \
+  CallGps cg_;                                                  \
+  if (int rc_ = resolve_gps(gps, m, d, cg_)) return rc_;        \
+  if (cg_.ard) gps = cg_.v.data()
+
+// Gradient entry points: the per-dimension reduction keeps d sums in registers (LMM_ARD_GRAD_DMAX).
+int ard_grad_check(int d) {
+  if (!g_call_ard || d <= LMM_ARD_GRAD_DMAX) return LMM_OK;
+  for (const double* p : g_call_ard->gils)
+    if (p) return fail(LMM_ERR_UNSUPPORTED, "gradients of ARD latents are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
+  return LMM_OK;
+}
+// d of the ARD gradient reduction in this call (0: every latent takes the isotropic one)
+int ard_grad_d() {
+  if (!g_call_ard) return 0;
+  for (const double* p : g_call_ard->gils) if (p) return g_call_ard->d;
+  return 0;
+}
+// The latent's descriptor for the gradient reduction: an ARD latent (folded ones included, d > 1) takes the per-dimension variant
+// with inv_ls = 1 / its multiplier.
+LatentDev grad_dev(const lmm_gp_t& gp, int l) {
+  LatentDev gd = to_dev(gp);
+  if (g_call_ard && g_call_ard->gils[l]) { gd.ils = g_call_ard->gils[l]; gd.inv_ls = 1.0 / g_call_ard->mult[l]; }
+  return gd;
+}
+// After the reduction: red = the LMM_NGRAD sums of latent l, ard = its d per-dimension sums (d/d l_k; unused unless gils[l]).
+// Writes d/d multiplier into *dl and d/d l_k into gard[0..d).
+void ard_grad_finish(int l, int d, const double* red, const double* ard, double* dl, double* gard) {
+  *dl = red[0];
+  if (!g_call_ard || g_call_ard->tag[l] == 0) return;
+  if (g_call_ard->gils[l]) { for (int k = 0; k < d; ++k) gard[k] = ard[k]; return; }
+  gard[0] = red[0];                           // d == 1, folded: red[0] = d/d l_eff, l_eff = multiplier * fold
+  *dl = red[0] * g_call_ard->fold[l];
+}
+// Publishes the call's per-dimension gradients to the registry: every tag the call named gets d/d ard[k] = multiplier * d/d l_k summed
+// over the call's latents [l0, l1) carrying it; gard == nullptr (grad_gps NULL): zeros.
+void ard_publish(const std::vector<double>* gard, int l0, int l1) {
+  if (!g_call_ard) return;
+  const ArdSet& A = *g_call_ard;
+  const int d = A.d, m = (int)A.tag.size();
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  for (int l = 0; l < m; ++l) {
+    auto it = g_ard_tags.find(A.tag[l]);
+    if (A.tag[l] != 0 && it != g_ard_tags.end()) it->second.grad.assign(d, 0.0);
+  }
+  if (!gard) return;
+  for (int l = l0; l < l1; ++l) {
+    auto it = g_ard_tags.find(A.tag[l]);
+    if (A.tag[l] == 0 || it == g_ard_tags.end()) continue;
+    for (int k = 0; k < d; ++k) it->second.grad[k] += A.mult[l] * (*gard)[(size_t)l * d + k];
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -856,7 +1032,7 @@ int latent_lmls(const double* xd, int d, int n, const lmm_gp_t* gps, const doubl
       const lmm_gp_t& gp = gps[l0 + k];
       GramArgs a{};
       a.A = s.A[j].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.row_tile0 = 0; a.row_shift = 0; a.full = 0;
-      a.x = xd; a.d = d; a.n = n; a.kind = gp.kind; a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale;
+      a.x = xd; a.d = d; a.n = n; set_kernel(a, gp);
       a.diag_add = noisevec ? 0.0 : noise[l0 + k]; a.pad_diag = 1.0;
       a.diag_vec = noisevec ? noisevec + (size_t)k * n : nullptr;      // per-point noise of latent k (device, n values)
       a.rider = delta + (size_t)k * nrhs * n; a.rider_ld = n; a.nrider = nrhs; a.xs = nullptr; a.ns = 0;
@@ -901,7 +1077,8 @@ struct lmm_post {
   int kind = 0;               // 0: per-latent (OILMM / MOGP), 1: dense ILMM
   int n = 0, d = 0, l0 = 0, l1 = 0, m = 0;
   int NC = 0, NR = 0, ld = 0;
-  std::vector<lmm_gp_t> gps;  // all m latents (host)
+  std::vector<lmm_gp_t> gps;  // all m latents (host; ARD latents resolved: their kind words name slots of `ard`)
+  std::shared_ptr<ArdSet> ard;  // the effective per-dimension lengthscales the handle was built with (own copy: tags may go)
   Buf<double> x;              // d x n
   std::vector<Buf<double>> L; // per latent of the shard: factor matrix (NR x NC, ld)
   std::vector<Buf<double>> W; // inverse diagonal blocks
@@ -1004,6 +1181,43 @@ int lmm_shutdown(void) {
 }
 
 const char* lmm_last_error_string(void) { return g.err.c_str(); }
+
+// ---- ARD registry (host only): the message of a refusal is recorded only when the context lock is free at that moment ----------
+static int ard_fail(int code, const char* msg) {
+  std::unique_lock<std::mutex> lk(g_mu, std::try_to_lock);
+  if (lk.owns_lock()) fail(code, "%s", msg);
+  return code;
+}
+
+int lmm_ard_create(int d, const double* lengthscale, int* tag) {
+  if (d <= 0 || !lengthscale || !tag) return ard_fail(LMM_ERR_ARG, "lmm_ard_create: bad arguments");
+  for (int k = 0; k < d; ++k)
+    if (!(lengthscale[k] > 0.0) || !std::isfinite(lengthscale[k])) return ard_fail(LMM_ERR_ARG, "lmm_ard_create: lengthscales must be finite and > 0");
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_ard_create: too many live ARD tags");
+  while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;     // tag << 8 stays a positive int
+  const int t = g_ard_next;
+  g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
+  ArdTag& a = g_ard_tags[t];
+  a.d = d; a.ard.assign(lengthscale, lengthscale + d); a.grad.assign(d, 0.0);
+  *tag = t;
+  return LMM_OK;
+}
+
+int lmm_ard_destroy(int tag) {
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  if (g_ard_tags.erase(tag) == 0) return ard_fail(LMM_ERR_ARG, "lmm_ard_destroy: unknown ARD tag");
+  return LMM_OK;
+}
+
+int lmm_ard_grad(int tag, double* out) {
+  if (!out) return ard_fail(LMM_ERR_ARG, "lmm_ard_grad: out is NULL");
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  auto it = g_ard_tags.find(tag);
+  if (it == g_ard_tags.end()) return ard_fail(LMM_ERR_ARG, "lmm_ard_grad: unknown ARD tag");
+  std::copy(it->second.grad.begin(), it->second.grad.end(), out);
+  return LMM_OK;
+}
 
 int lmm_last_error_detail(int* latent, int* info) {
   if (latent) *latent = g.err_latent;
@@ -1180,7 +1394,7 @@ int lmm_oilmm_logpdf(const double* x, int d, int n, const double* y, int p, cons
   if (!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST, H;
@@ -1270,6 +1484,7 @@ struct OilmmGrad {          // host results of oilmm_grad_core (partial sums ove
   std::vector<double> gs2;    // one per noise block
   std::vector<double> gS, gU;
   std::vector<lmm_gp_grad_t> ggps;
+  std::vector<double> gard;   // m x d: d logpdf / d l_k of the ARD latents (ard_grad_finish), zeros elsewhere
 };
 
 // Value and gradient of the OILMM logpdf (reference src/oilmm.jl:79-113 differentiated) over N points in NB.nblk consecutive
@@ -1311,10 +1526,11 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
       Am[s].emplace_back(mat_count(D.elems())); Wm[s].emplace_back(mat_count((size_t)(D.NC / 64) * 4096));
       Rm[s].emplace_back(mat_count((size_t)D.ld * D.NC));
     }
-    part.emplace_back((size_t)grad_partials(n));
+    part.emplace_back((size_t)grad_partials(n, ard_grad_d()));
   }
   const int NGR = LMM_NGRAD;
   Buf<double> alpha((size_t)D.NC * std::max(ms, 1)), lmld(std::max(ms, 1)), red((size_t)NGR * std::max(ms, 1));
+  Buf<double> ardred((size_t)d * std::max(ms, 1));             // per-dimension sums of the ARD latents (d/d l_k)
   // more than two noise blocks: [tr Kinv, alpha.alpha] per (latent, block) from the small per-range kernels
   Buf<double> blksum(nblk > 2 ? (size_t)2 * nblk * std::max(ms, 1) : 1);
   Buf<int> info(std::max(ms, 1));
@@ -1333,7 +1549,7 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
       const lmm_gp_t& gp = gps[l0 + k];
       GramArgs a{};
       a.A = Am[s][j].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n;
-      a.kind = gp.kind; a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale; a.pad_diag = 1.0;
+      set_kernel(a, gp); a.pad_diag = 1.0;
       a.diag_add = two ? 0.0 : STa[l0 + k];
       a.diag_vec = two ? nv.p + (size_t)k * n : nullptr;
       a.rider = delta.p + (size_t)k * n; a.rider_ld = n; a.nrider = 1;
@@ -1353,8 +1569,8 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     launch_syrk_upper_set(B.A, D.ld, Rb, D.ld, D.NC, nb, st);                // lower(A) = L^-T L^-1 = Kt^-1
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      launch_grad_reduce(Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, to_dev(gps[l0 + k]), part[s].p,
-                         red.p + (size_t)NGR * k, st);
+      launch_grad_reduce(Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, grad_dev(gps[l0 + k], l0 + k), part[s].p,
+                         red.p + (size_t)NGR * k, st, ardred.p + (size_t)d * k);
       if (nblk > 2)
         for (int b = 0; b < nblk; ++b) {
           double* o = blksum.p + ((size_t)k * nblk + b) * 2;
@@ -1369,6 +1585,8 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   std::vector<double> hblk(nblk > 2 ? (size_t)2 * nblk * std::max(ms, 1) : 0, 0.0);
   HIPCHK(hipMemcpyAsync(lml.data(), lmld.p, std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hred.data(), red.p, (size_t)NGR * std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
+  std::vector<double> hard(ard_grad_d() ? (size_t)d * std::max(ms, 1) : 0, 0.0);
+  if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   if (!hblk.empty() && ms > 0) HIPCHK(hipMemcpyAsync(hblk.data(), blksum.p, hblk.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, st0));
   // small dense products needed by the chain rule: YA = Y' alpha (p x ms), aTy = alpha_l . (T y)_l, M2 = Y Y' (p x p) per noise block
@@ -1393,11 +1611,14 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   G.gs2.assign(nblk, 0.0);
   G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
   G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
+  G.gard.assign((size_t)m * d, 0.0);
   for (int k = 0; k < ms; ++k) {
     const int l = l0 + k;
     total += lml[k];
     const double* r = &hred[(size_t)NGR * k];
-    const double cl = r[0], ad = r[3], sa = r[4], v = gps[l].variance;
+    double cl;
+    ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * k], &cl, &G.gard[(size_t)l * d]);
+    const double ad = r[3], sa = r[4], v = gps[l].variance;
     double D_aa = 0.0, D_tr = 0.0, g_s2 = 0.0;       // a'Da, tr(Kt^-1 D) with D the projected noise; sum_b s2[b] dlml/dnoise_b
     for (int b = 0; b < nblk; ++b) {
       // tr Kinv and alpha.alpha over the block's rows
@@ -1500,16 +1721,18 @@ int lmm_oilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p,
   if (!x || !y || !U || !S || !out_logpdf || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   DevOut gy(grad_y, (size_t)n * p);
+  if (int rc = ard_grad_check(d)) return rc;
   OilmmGrad G;
   if (int rc = oilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, U, S, m, gps, latent_begin, latent_end, with_regulariser,
                                G, gy.p))
     return rc;
   write_oilmm_grad(G, m, p, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
+  ard_publish(grad_gps ? &G.gard : nullptr, latent_begin, latent_end);
   if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
   return LMM_OK;
   LMM_CATCH
@@ -1538,7 +1761,7 @@ int lmm_oilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* bat
     return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   if (int rc = check_batches(batch_n, batch_sigma2, nbatch, n)) return rc;
   if (!(sigma2_s > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
@@ -1549,6 +1772,7 @@ int lmm_oilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* bat
   HIPCHK(hipMemcpyAsync(xj.p + (size_t)d * n, xsd.p, (size_t)d * ns * sizeof(double), hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpy2DAsync(yj.p, (size_t)N * sizeof(double), yd.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpy2DAsync(yj.p + n, (size_t)N * sizeof(double), ysd.p, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
+  if (int rc = ard_grad_check(d)) return rc;
   const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
   OilmmGrad GJ, GM;
   if (int rc = oilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, U, S, m, gps,
@@ -1567,6 +1791,8 @@ int lmm_oilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* bat
     }
   }
   if (grad_U) for (size_t q = 0; q < (size_t)p * m; ++q) grad_U[q] = GJ.gU[q] - GM.gU[q];
+  for (size_t q = 0; q < GJ.gard.size(); ++q) GJ.gard[q] -= GM.gard[q];
+  ard_publish(grad_gps ? &GJ.gard : nullptr, latent_begin, latent_end);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);
@@ -1606,7 +1832,7 @@ int lmm_oilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p
   if (!x || !Y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0 || ncol <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST, H;
   project_orthogonal(U, S, p, m, sigma2, T, ST, H);
@@ -1667,7 +1893,7 @@ int lmm_mogp_logpdf(const double* x, int d, int n, const double* y, int m, doubl
   LMM_TRY
   if (!x || !y || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   hipStream_t st0 = g.streams[0];
   const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0);
@@ -1693,7 +1919,7 @@ int lmm_mogp_logpdf_diag(const double* x, int d, int n, const double* y, int m, 
   LMM_TRY
   if (!x || !y || !noise_diag || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   hipStream_t st0 = g.streams[0];
   const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0), nd(noise_diag, (size_t)n * m, st0);
@@ -1717,7 +1943,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !y || !H || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   if (!jit) jit = &kDefaultJit;
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
   hipStream_t st0 = g.streams[0];
@@ -1811,7 +2037,7 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !Y || !H || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0 || ncol <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   if (!jit) jit = &kDefaultJit;
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
@@ -1866,6 +2092,7 @@ struct IlmmGrad {            // host results of ilmm_grad_core
   double value = 0.0, gs2[LMM_MAX_NOISE_BLOCKS] = {};
   std::vector<double> gH;    // p x m
   std::vector<lmm_gp_grad_t> ggps;
+  std::vector<double> gard;  // m x d: d logpdf / d l_k of the ARD latents (ard_grad_finish), zeros elsewhere
 };
 
 // Value and gradient of the dense-H ILMM prior logpdf over n points in NB.nblk consecutive blocks, block b carrying observation
@@ -1947,10 +2174,11 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   launch_syrk_upper_set(A.p, D.ld, R.p, D.ld, D.NC, st0);                         // lower(A) = Sigma^-1
   const int NGR = LMM_NGRAD;
   const size_t mm = (size_t)m * m, mp = (size_t)m * p;
-  Buf<double> red((size_t)NGR * m), gpart((size_t)grad_partials(n)), Btr(KB * mm), AAt(KB * mm), AY(KB * mp);
+  Buf<double> red((size_t)NGR * m), gpart((size_t)grad_partials(n, ard_grad_d())), Btr(KB * mm), AAt(KB * mm), AY(KB * mp);
+  Buf<double> ardred((size_t)d * m);
   for (int l = 0; l < m; ++l)
     launch_grad_reduce(mat_at(A.p, (size_t)l * n * D.ld + (size_t)l * n), D.ld, n, n, alpha.p + (size_t)l * n, delta.p + (size_t)l * n, xd, d,
-                       lat[l], gpart.p, red.p + (size_t)NGR * l, st0);
+                       grad_dev(gps[l], l), gpart.p, red.p + (size_t)NGR * l, st0, ardred.p + (size_t)d * l);
   // regulariser pieces: Rm = Y - (T Y)' H' (n x p), RH = Rm H (n x m), per block Rm' Ty (p x m), RH' Y (m x p)
   Buf<double> HTY((size_t)n * p), Rm((size_t)n * p), RH((size_t)N), RtTy(KB * mp), RHtY(KB * mp);
   for (int b = 0; b < nblk; ++b)
@@ -1973,6 +2201,8 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   HIPCHK(hipMemcpyAsync(resid, resid_dev.p, nblk * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  std::vector<double> hard(ard_grad_d() ? (size_t)d * m : 0, 0.0);
+  if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hB.data(), Btr.p, nblk * mm * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hAAt.data(), AAt.p, nblk * mm * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hAY.data(), AY.p, nblk * mp * sizeof(double), hipMemcpyDeviceToHost, st0));
@@ -1986,9 +2216,10 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
     G.value -= ((double)bn[b] * ((double)(p - m) * kLog2Pi + ((double)p * std::log(s2[b]) - logdetST[b])) + resid[b] / s2[b]) / 2.0;
   // ---- kernel-parameter gradients: 1/2 tr((aa' - Sigma^-1) dSigma/dtheta_l), dSigma = E_ll (x) dK_l ----
   G.ggps.assign(m, lmm_gp_grad_t{});
+  G.gard.assign((size_t)m * d, 0.0);
   for (int l = 0; l < m; ++l) {
     const double* r = &hred[(size_t)NGR * l];
-    G.ggps[l].lengthscale = r[0];
+    ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * l], &G.ggps[l].lengthscale, &G.gard[(size_t)l * d]);
     G.ggps[l].variance = (r[7] + 0.5 * gps[l].variance * (r[2] - r[1])) / gps[l].variance;     // K_ii = variance
     G.ggps[l].mean = r[4];
   }
@@ -2103,14 +2334,16 @@ int lmm_ilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p, 
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !y || !H || !out_logpdf || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   if (!jit) jit = &kDefaultJit;
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   DevOut gy(grad_y, (size_t)n * p);
+  if (int rc = ard_grad_check(d)) return rc;
   IlmmGrad G;
   if (int rc = ilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, H, m, gps, jit, G, gy.p)) return rc;
+  ard_publish(grad_gps ? &G.gard : nullptr, 0, m);
   *out_logpdf = G.value;
   if (grad_sigma2) *grad_sigma2 = G.gs2[0];
   if (grad_H) std::copy(G.gH.begin(), G.gH.end(), grad_H);
@@ -2135,7 +2368,7 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
                                lmm_gp_grad_t* grad_gps) {
   if (!x || !y || !xs || !ys || !H || !out_logpdf || d <= 0 || n <= 0 || ns <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_test && m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   if (int rc = check_batches(batch_n, batch_sigma2, nbatch, n)) return rc;
   if (!(sigma2_s > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   if (!jit) jit = &kDefaultJit;
@@ -2158,6 +2391,7 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
     for (int l = 0; l < m; ++l) Hlat[l + (size_t)l * p] = 1.0;
     Hblk[nbatch] = Hlat.data();
   }
+  if (int rc = ard_grad_check(d)) return rc;
   const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
   IlmmGrad GJ, GM;
   if (int rc = ilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, H, m, gps, jit, GJ,
@@ -2175,6 +2409,8 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
       grad_gps[l].lengthscale = GJ.ggps[l].lengthscale - GM.ggps[l].lengthscale;
       grad_gps[l].mean = GJ.ggps[l].mean - GM.ggps[l].mean;
     }
+  for (size_t q = 0; q < GJ.gard.size(); ++q) GJ.gard[q] -= GM.gard[q];
+  ard_publish(grad_gps ? &GJ.gard : nullptr, 0, m);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);
@@ -2238,7 +2474,7 @@ int lmm_ilmm_post_logpdf_grad(const double* x, int d, int n, const double* y, co
 // ------------------------------------------------------------------------------------------------
 // noise: per-latent scalar (host, indexed by latent) used when noisevec == NULL; noisevec: device [k][n] per-point noise.
 static int posterior_create_common(const double* xd, int d, int n, const lmm_gp_t* gps, int m, const double* noise,
-                                   int l0, int l1, const double* delta, lmm_post_t** out,
+                                   int l0, int l1, const double* delta, lmm_post_t** out, std::shared_ptr<ArdSet> ard,
                                    const double* noisevec = nullptr) {
   const int ms = l1 - l0;
   lmm_post* P = new lmm_post();
@@ -2247,6 +2483,7 @@ static int posterior_create_common(const double* xd, int d, int n, const lmm_gp_
     P->kind = 0; P->f32 = g_f32; P->n = n; P->d = d; P->l0 = l0; P->l1 = l1; P->m = m;
     P->NC = D.NC; P->NR = D.NR; P->ld = D.ld;
     P->gps.assign(gps, gps + m);
+    P->ard = std::move(ard);
     P->x = Buf<double>((size_t)d * n);
     HIPCHK(hipMemcpyAsync(P->x.p, xd, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, g.streams[0]));
     Buf<int> info(std::max(ms, 1));
@@ -2279,7 +2516,7 @@ static int posterior_create_common(const double* xd, int d, int n, const lmm_gp_
         const lmm_gp_t& gp = gps[l0 + k];
         GramArgs a{};
         a.A = P->L[k].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = P->x.p; a.d = d; a.n = n;
-        a.kind = gp.kind; a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale; a.pad_diag = 1.0;
+        set_kernel(a, gp); a.pad_diag = 1.0;
         a.diag_add = noisevec ? 0.0 : noise[l0 + k];
         a.diag_vec = noisevec ? P->noise_all.p + (size_t)k * n : nullptr;
         a.rider = delta + (size_t)k * n; a.rider_ld = n; a.nrider = 1;
@@ -2317,7 +2554,7 @@ int lmm_oilmm_posterior_create(const double* x, int d, int n, const double* y, i
   if (!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST, H;
   project_orthogonal(U, S, p, m, sigma2, T, ST, H);
@@ -2329,7 +2566,7 @@ int lmm_oilmm_posterior_create(const double* x, int d, int n, const double* y, i
   const int ms = latent_end - latent_begin;
   Buf<double> delta((size_t)n * std::max(ms, 1));
   if (ms > 0) project_on_device(yd.p, n, p, Td.buf, m, latent_begin, ms, meansd.buf.p + latent_begin, delta.p, st0);
-  return posterior_create_common(xd.p, d, n, gps, m, ST.data(), latent_begin, latent_end, delta.p, out);
+  return posterior_create_common(xd.p, d, n, gps, m, ST.data(), latent_begin, latent_end, delta.p, out, cg_.ard);
   LMM_CATCH
 }
 
@@ -2371,7 +2608,7 @@ int lmm_post_condition(const lmm_post_t* post, const double* U, const double* S,
     else launch_fill(nv.p + (size_t)k * n, n1, P->noise_scalar[k], st0);
     launch_fill(nv.p + (size_t)k * n + n1, n2, ST[l0 + k], st0);
   }
-  return posterior_create_common(xall.p, d, n, P->gps.data(), m, ST.data(), l0, l1, delta.p, out, nv.p);
+  return posterior_create_common(xall.p, d, n, P->gps.data(), m, ST.data(), l0, l1, delta.p, out, P->ard, nv.p);
   LMM_CATCH
 }
 
@@ -2382,7 +2619,7 @@ int lmm_mogp_posterior_create(const double* x, int d, int n, const double* y, in
   LMM_TRY
   if (!x || !y || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0);
   std::vector<double> T((size_t)m * m, 0.0), means(m), noise(m, sigma2);
@@ -2391,7 +2628,7 @@ int lmm_mogp_posterior_create(const double* x, int d, int n, const double* y, in
   const int ms = latent_end - latent_begin;
   Buf<double> delta((size_t)n * std::max(ms, 1));
   if (ms > 0) project_on_device(yd.p, n, m, Td.buf, m, latent_begin, ms, meansd.buf.p + latent_begin, delta.p, st0);
-  return posterior_create_common(xd.p, d, n, gps, m, noise.data(), latent_begin, latent_end, delta.p, out);
+  return posterior_create_common(xd.p, d, n, gps, m, noise.data(), latent_begin, latent_end, delta.p, out, cg_.ard);
   LMM_CATCH
 }
 
@@ -2399,7 +2636,7 @@ int lmm_mogp_posterior_create(const double* x, int d, int n, const double* y, in
 // device) and the per-batch SigmaT list: assemble blockdiag(K_l) + SigmaT_{batch(i)} (x) e_i e_i', factor, alpha = C \ delta.
 static int dense_posterior_build(const double* xd, int d, int n, const double* H, int p, int m, const lmm_gp_t* gps,
                                  const double* delta, const std::vector<double>& sigs, const std::vector<int>& sigidx,
-                                 lmm_post_t** out) {
+                                 lmm_post_t** out, std::shared_ptr<ArdSet> ard) {
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
   hipStream_t st0 = g.streams[0];
   std::vector<LatentDev> lat(m);
@@ -2411,6 +2648,7 @@ static int dense_posterior_build(const double* xd, int d, int n, const double* H
     P->kind = 1; P->f32 = g_f32; P->n = n; P->d = d; P->l0 = 0; P->l1 = m; P->m = m; P->p = p;
     P->NC = D.NC; P->NR = D.NR; P->ld = D.ld;
     P->gps.assign(gps, gps + m);
+    P->ard = std::move(ard);
     P->H.assign(H, H + (size_t)p * m);
     P->sigs = sigs; P->sigidx = sigidx;
     P->x = Buf<double>((size_t)d * n);
@@ -2454,7 +2692,7 @@ int lmm_ilmm_posterior_create(const double* x, int d, int n, const double* y, in
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !y || !H || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (int rc = check_gps(gps, m)) return rc;
+  RESOLVE_GPS(gps, m, d);
   if (!jit) jit = &kDefaultJit;
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST;
@@ -2466,7 +2704,7 @@ int lmm_ilmm_posterior_create(const double* x, int d, int n, const double* y, in
   Uploaded meansd(means, st0);
   Buf<double> delta((size_t)n * m);
   project_on_device(yd.p, n, p, Td.buf, m, 0, m, meansd.buf.p, delta.p, st0);
-  return dense_posterior_build(xd.p, d, n, H, p, m, gps, delta.p, ST, std::vector<int>(n, 0), out);
+  return dense_posterior_build(xd.p, d, n, H, p, m, gps, delta.p, ST, std::vector<int>(n, 0), out, cg_.ard);
   LMM_CATCH
 }
 
@@ -2506,7 +2744,7 @@ int lmm_ilmm_post_condition(const lmm_post_t* post, double sigma2, const double*
   sigs.insert(sigs.end(), ST.begin(), ST.end());
   std::vector<int> idx = P->sigidx;
   idx.resize(n, (int)(P->sigs.size() / ((size_t)m * m)));
-  return dense_posterior_build(xall.p, d, n, P->H.data(), p, m, P->gps.data(), delta.p, sigs, idx, out);
+  return dense_posterior_build(xall.p, d, n, P->H.data(), p, m, P->gps.data(), delta.p, sigs, idx, out, P->ard);
   LMM_CATCH
 }
 
@@ -2727,7 +2965,7 @@ int lmm_ilmm_post_latent_view(const lmm_post_t* post, lmm_post_t** out) {
   lmm_post* V = new lmm_post();
   V->f32 = B->f32; V->kind = 1; V->n = B->n; V->d = B->d; V->l0 = 0; V->l1 = B->m; V->m = B->m; V->p = B->m;
   V->NC = B->NC; V->NR = B->NR; V->ld = B->ld;
-  V->gps = B->gps; V->sigs = B->sigs; V->sigidx = B->sigidx;
+  V->gps = B->gps; V->ard = B->ard; V->sigs = B->sigs; V->sigidx = B->sigidx;
   V->H.assign((size_t)B->m * B->m, 0.0);
   for (int l = 0; l < B->m; ++l) V->H[l + (size_t)l * B->m] = 1.0;
   V->base = B;
@@ -2759,7 +2997,7 @@ static GramArgs cross_gram_args(const lmm_post* P, const lmm_gp_t& gp, const dou
                                 int nsr) {
   GramArgs r{};
   r.A = Rk; r.ld = ldr; r.nrows = P->NC + nsr; r.ncols = P->NC; r.row_tile0 = P->NC / 64; r.row_shift = P->NC; r.full = 1;
-  r.x = P->x.p; r.d = d; r.n = P->n; r.kind = gp.kind; r.var = gp.variance; r.inv_ls = 1.0 / gp.lengthscale;
+  r.x = P->x.p; r.d = d; r.n = P->n; set_kernel(r, gp);
   r.xs = xsd; r.ns = ns;
   return r;
 }
@@ -2836,7 +3074,8 @@ int lmm_latent_marginals(const lmm_post_t* post, const lmm_gp_t* gps, int m_shar
   if (!xs || !mean_lat || !var_lat || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (post && post->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "per-latent marginals of the dense-H posterior (coupled latents): use lmm_ilmm_post_mean_and_var");
   const int ms = post ? (post->l1 - post->l0) : m_shard;
-  if (!post) { if (int rc = check_gps(gps, m_shard)) return rc; }
+  CallGps cg_;
+  if (!post) { if (int rc = resolve_gps(gps, m_shard, d, cg_)) return rc; if (cg_.ard) gps = cg_.v.data(); }
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)d * ns, st0);
   DevOut mo(mean_lat, (size_t)ns * ms), vo(var_lat, (size_t)ns * ms);
@@ -2858,8 +3097,10 @@ int lmm_oilmm_mean_and_var(const lmm_post_t* post, const lmm_gp_t* gps, const do
   if (post && post->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "dense-H posterior handle: use lmm_ilmm_post_mean_and_var");
   if (!jit) jit = &kDefaultJit;
   int l0 = latent_begin, l1 = latent_end;
+  CallGps cg_;
   if (post) { l0 = post->l0; l1 = post->l1; if (post->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", post->m, m); }
-  else if (int rc = check_gps(gps, m)) return rc;
+  else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
+  if (cg_.ard) gps = cg_.v.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   const int ms = l1 - l0;
   hipStream_t st0 = g.streams[0];
@@ -2914,7 +3155,7 @@ static GramArgs cov_args(const lmm_gp_t& gp, const double* xsd, int d, int ns, d
                          const Dims& Ds, double* B) {
   GramArgs a{};
   a.A = B; a.ld = Ds.ld; a.nrows = Ds.NR; a.ncols = Ds.NC; a.x = xsd; a.d = d; a.n = ns;
-  a.kind = gp.kind; a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale; a.diag_add = diag_add; a.pad_diag = 1.0;
+  set_kernel(a, gp); a.diag_add = diag_add; a.pad_diag = 1.0;
   a.rider = rider_vec; a.rider_ld = ns; a.nrider = rider_vec ? 1 : 0;
   return a;
 }
@@ -2979,12 +3220,14 @@ extern "C" int lmm_lmm_mean_and_cov(const lmm_post_t* post, const lmm_gp_t* gps,
   if (!jit) jit = &kDefaultJit;
   const lmm_post* P = post;
   int l0 = latent_begin, l1 = latent_end;
+  CallGps cg_;
   if (P) {
     if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "full covariance of the dense-H posterior is not built");
     l0 = P->l0; l1 = P->l1;
     if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", P->m, m);
     if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  } else if (int rc = check_gps(gps, m)) return rc;
+  } else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
+  if (cg_.ard) gps = cg_.v.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   const int ms = l1 - l0;
   hipStream_t st0 = g.streams[0];
@@ -3043,12 +3286,14 @@ extern "C" int lmm_mogp_cross_cov(const lmm_post_t* post, const lmm_gp_t* gps, i
   if ((double)m * n * (double)m * n2 > 4e8) return fail(LMM_ERR_UNSUPPORTED, "cross-covariance (m n) x (m n2) too large");
   const lmm_post* P = post;
   int l0 = latent_begin, l1 = latent_end;
+  CallGps cg_;
   if (P) {
     if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "cross-covariance of the coupled latents of a dense-H posterior is not built");
     l0 = P->l0; l1 = P->l1;
     if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, m = %d", P->m, m);
     if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, x has d=%d", P->d, d);
-  } else if (int rc = check_gps(gps, m)) return rc;
+  } else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
+  if (cg_.ard) gps = cg_.v.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)d * n2, st0);
@@ -3066,7 +3311,7 @@ extern "C" int lmm_mogp_cross_cov(const lmm_post_t* post, const lmm_gp_t* gps, i
     const lmm_gp_t& gp = P ? P->gps[l] : gps[l];
     GramArgs a{};
     a.A = Kb.p; a.ld = ldk; a.nrows = NCy + nxr; a.ncols = NCy; a.row_tile0 = NCy / 64; a.row_shift = NCy; a.full = 1;
-    a.x = yd.p; a.d = d; a.n = n2; a.kind = gp.kind; a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale;
+    a.x = yd.p; a.d = d; a.n = n2; set_kernel(a, gp);
     a.xs = xd.p; a.ns = n;
     gram_g(a, st0, "cross-covariance K(x, y)");
     if (P) {
@@ -3173,12 +3418,14 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps, const double
   if (!jit) jit = &kDefaultJit;
   const lmm_post* P = post;
   int l0 = latent_begin, l1 = latent_end;
+  CallGps cg_;
   if (P) {
     if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "dense-H posterior handle: use lmm_ilmm_post_rand");
     l0 = P->l0; l1 = P->l1;
     if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", P->m, m);
     if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  } else if (int rc = check_gps(gps, m)) return rc;
+  } else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
+  if (cg_.ard) gps = cg_.v.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   const int ms = l1 - l0;
   // OILMM: f(x) default jitter 1e-18 (reference src/oilmm.jl:47); dense-H ILMM: 1e-12 (src/ilmm.jl:84)
@@ -3346,7 +3593,12 @@ int lmm_dev_gram(double* A, int ld, int nrows, int ncols, const double* x, int d
   if (!A || !x || !gp || nrows % 64 || ncols % 64 || (ld & 1) || ld < nrows) return fail(LMM_ERR_ARG, "bad arguments");
   GramArgs a{};
   a.A = A; a.ld = ld; a.nrows = nrows; a.ncols = ncols; a.x = x; a.d = d; a.n = n;
-  a.kind = gp->kind; a.var = gp->variance; a.inv_ls = 1.0 / gp->lengthscale; a.diag_add = diag_add; a.pad_diag = 1.0;
+  CallGps cg_;
+  if (gp->kind >> 8) {                  // an ARD latent: resolve its tag like the entry points do
+    if (int rc = resolve_gps(gp, 1, d, cg_)) return rc;
+    gp = cg_.v.data();
+  }
+  set_kernel(a, *gp); a.diag_add = diag_add; a.pad_diag = 1.0;
   gram_g(a, g.streams[0]);
   HIPCHK(hipStreamSynchronize(g.streams[0]));
   return LMM_OK;

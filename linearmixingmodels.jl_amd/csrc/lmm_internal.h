@@ -8,9 +8,12 @@ extern int g_f32;              // compute dtype of the matrices: 0 = Float64, 1 
 struct BatchPtr { double* p[LMM_MAX_BATCH]; };   // base pointers of the matrices of one batch (kernel argument, by value)
 struct BatchInfo { int* p[LMM_MAX_BATCH]; };
 
+// kind: the BASE kernel kind (lmm_kernel_kind); ils: nullptr (isotropic, inv_ls) or the latent's d per-dimension inverse lengthscales
+// (device; an ARD latent, d > 1).  An ARD latent keeps inv_ls = 1 / its common multiplier (the gradient reduction's d/d multiplier).
 struct LatentDev {
   int kind;
   double var, inv_ls, mean;
+  const double* ils;
 };
 
 // Gram / factor-matrix assembly arguments (see gram_kernel).
@@ -22,6 +25,7 @@ struct GramArgs {
   int full;             // 1: no lower-triangle skip (rectangular rider matrix)
   const double* x; int d, n;
   int kind; double var, inv_ls, diag_add, pad_diag;
+  const double* ils;                           // per-dimension inverse lengthscales (device, d of them; nullptr: isotropic inv_ls)
   const double* diag_vec;                      // optional per-point diagonal term (length n), added to diag_add
   const double* rider; int rider_ld, nrider;   // rows ncols + r  <- rider[r*rider_ld + j] - rider_sub
   double rider_sub;                            // constant subtracted from the rider rows (latent mean: delta = T y - mean)
@@ -36,6 +40,7 @@ struct GramBatchArgs {
   GramArgs base;
   double* A[LMM_MAX_BATCH];
   double var[LMM_MAX_BATCH], inv_ls[LMM_MAX_BATCH], diag_add[LMM_MAX_BATCH];
+  const double* ils[LMM_MAX_BATCH];
   const double* diag_vec[LMM_MAX_BATCH];
   const double* rider[LMM_MAX_BATCH];
   double rider_sub[LMM_MAX_BATCH];
@@ -52,7 +57,7 @@ struct DenseArgs {
 };
 
 void launch_gram(const GramArgs& a, hipStream_t st);
-// nb same-shaped assemblies (differing only in A, kind, var, inv_ls, diag_add, diag_vec, rider): one launch per run of equal kinds
+// nb same-shaped assemblies (differing only in A, kind, var, inv_ls, ils, diag_add, diag_vec, rider): one launch per run of equal kinds
 void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st);
 void launch_dense_assemble(const DenseArgs& a, hipStream_t st);
 void launch_dense_cov(const double* S, int lds, int ns, int m, const double* Hm, int p, double jitter, double sigma2, double* T,
@@ -169,10 +174,12 @@ void launch_trmv_lower(const double* L, int ld, int n, const double* z, double m
 void launch_syrk_upper_set(double* C, int ldc, const double* X, int ldx, int N, hipStream_t st);
 void launch_syrk_upper_set(const BatchPtr& C, int ldc, const BatchPtr& X, int ldx, int N, int nb, hipStream_t st);
 void launch_set_identity(double* R, int ld, int nc, hipStream_t st);
-int grad_partials(int n);
+int grad_partials(int n, int d_ard = 0);      // partial-buffer elements of launch_grad_reduce (d_ard: the d of an ARD latent, else 0)
 #define LMM_NGRAD 8
+#define LMM_ARD_GRAD_DMAX 32                  // widest ARD latent the gradient reduction serves (per-dimension sums in registers)
+// g.ils != nullptr (an ARD latent, d <= LMM_ARD_GRAD_DMAX): out8[0] is d/d multiplier and out_ard[k] = d/d l_k (d values)
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,
-                        LatentDev g, double* partial, double* out7, hipStream_t st);
+                        LatentDev g, double* partial, double* out7, hipStream_t st, double* out_ard = nullptr);
 void launch_vec_axpby(const double* a, double sa, const double* b, double sb, size_t n, double* out, hipStream_t st);
 void launch_block_trace(const double* Minv, int ld, int n, int m, int i0, int i1, double* out, hipStream_t st);   // points i0..i1-1
 // Consecutive point ranges [off[b], off[b + 1]) that carry the observation-noise variance s2[b]: the conditioning batches of a

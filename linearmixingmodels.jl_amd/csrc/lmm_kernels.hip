@@ -130,12 +130,20 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh4) {
 // K1: Gram assembly (lower triangle of K + diag_add*I, identity pad, rider rows).  HBM-write bound:
 // each thread produces two consecutive rows (one 16-byte store) for 8 columns of a 64x64 tile.
 // ---------------------------------------------------------------------------------------------------
+// ils != nullptr: per-dimension inverse lengthscales (an ARD latent) in place of the scalar inv_ls
 __device__ __forceinline__ double scaled_dist2(const double* __restrict__ a, const double* __restrict__ b,
-                                               int d, double inv_ls) {
+                                               int d, double inv_ls, const double* __restrict__ ils) {
   double s = 0.0;
-  for (int k = 0; k < d; ++k) {
-    const double t = (a[k] - b[k]) * inv_ls;
-    s = __builtin_fma(t, t, s);
+  if (ils == nullptr) {
+    for (int k = 0; k < d; ++k) {
+      const double t = (a[k] - b[k]) * inv_ls;
+      s = __builtin_fma(t, t, s);
+    }
+  } else {
+    for (int k = 0; k < d; ++k) {
+      const double t = (a[k] - b[k]) * ils[k];
+      s = __builtin_fma(t, t, s);
+    }
   }
   return s;
 }
@@ -207,7 +215,7 @@ __device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int
         if (rtype[e] == 0 || rtype[e] == 3) {
           double r, r2;
           if (a.d == 1) { r = fabs(rx[e] - xj) * a.inv_ls; r2 = r * r; }
-          else { r2 = scaled_dist2(rpt[e], a.x + (size_t)j * a.d, a.d, a.inv_ls); r = sqrt(r2); }
+          else { r2 = scaled_dist2(rpt[e], a.x + (size_t)j * a.d, a.d, a.inv_ls, a.ils); r = sqrt(r2); }
           val = kappa(a.kind, a.var, r, r2);
           if (rtype[e] == 0 && i0 + e == j) val += a.diag_add + (a.diag_vec ? a.diag_vec[j] : 0.0);
         } else if (rtype[e] == 2) {
@@ -269,11 +277,12 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
   const bool rows_interior = (a.d == 1) && rsrc != nullptr;
   const bool rows_nd = ND && (a.d > 1) && (a.d <= DMAX) && rsrc != nullptr;
   double xr0[DMAX], xr1[DMAX];                                // d > 1: this thread's two row points, pre-scaled by 1/lengthscale
-  if (ND && rows_nd) {
+  if (ND && rows_nd) {                                        // (per dimension for an ARD latent: a.ils)
 #pragma unroll
     for (int k = 0; k < DMAX; ++k) {
-      xr0[k] = (k < a.d) ? rsrc[(size_t)(i0 - rbase) * a.d + k] * a.inv_ls : 0.0;
-      xr1[k] = (k < a.d) ? rsrc[(size_t)(i0 + 1 - rbase) * a.d + k] * a.inv_ls : 0.0;
+      const double sk = (k < a.d) ? (a.ils ? a.ils[k] : a.inv_ls) : 0.0;
+      xr0[k] = (k < a.d) ? rsrc[(size_t)(i0 - rbase) * a.d + k] * sk : 0.0;
+      xr1[k] = (k < a.d) ? rsrc[(size_t)(i0 + 1 - rbase) * a.d + k] * sk : 0.0;
     }
   }
   constexpr bool SEP = (KIND != LMM_KERNEL_SE);
@@ -296,7 +305,8 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
     const size_t out = (size_t)(tj * 64 + cg) * a.ld + (i0 - a.row_shift);      // element index of this thread's first store
     if (ND && rows_nd && cols_in) {                         // d > 1 interior tile: column points staged (pre-scaled) in LDS
       __syncthreads();
-      for (int e = t; e < 64 * a.d; e += 256) colP[e] = a.x[(size_t)tj * 64 * a.d + e] * a.inv_ls;
+      if (a.ils == nullptr) { for (int e = t; e < 64 * a.d; e += 256) colP[e] = a.x[(size_t)tj * 64 * a.d + e] * a.inv_ls; }
+      else { for (int e = t; e < 64 * a.d; e += 256) colP[e] = a.x[(size_t)tj * 64 * a.d + e] * a.ils[e % a.d]; }
       __syncthreads();
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
@@ -396,7 +406,7 @@ template <int KIND, bool ND, typename TS>
 __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
   GramArgs a = b.base;
   const int z = blockIdx.z;
-  a.A = b.A[z]; a.var = b.var[z]; a.inv_ls = b.inv_ls[z]; a.diag_add = b.diag_add[z]; a.diag_vec = b.diag_vec[z]; a.rider = b.rider[z]; a.rider_sub = b.rider_sub[z];
+  a.A = b.A[z]; a.var = b.var[z]; a.inv_ls = b.inv_ls[z]; a.ils = b.ils[z]; a.diag_add = b.diag_add[z]; a.diag_vec = b.diag_vec[z]; a.rider = b.rider[z]; a.rider_sub = b.rider_sub[z];
   if (b.info_zero[z] && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *b.info_zero[z] = 0;
   gram_body<KIND, ND, TS>(a);
 }
@@ -433,7 +443,7 @@ __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
             const LatentDev g = a.lat[lj];
             double r, r2;
             if (a.d == 1) { r = fabs(a.x[ii[e]] - a.x[jj]) * g.inv_ls; r2 = r * r; }
-            else { r2 = scaled_dist2(a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d, g.inv_ls); r = sqrt(r2); }
+            else { r2 = scaled_dist2(a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d, g.inv_ls, g.ils); r = sqrt(r2); }
             val = kappa(g.kind, g.var, r, r2);
           }
           if (ii[e] == jj) val += a.sigmaT[(size_t)(a.sig_idx ? a.sig_idx[jj] : 0) * a.m * a.m + li[e] + lj * a.m];
@@ -467,7 +477,7 @@ __global__ __launch_bounds__(256) void dense_cross_kernel(void* __restrict__ R, 
       const LatentDev g = lat[l];
       double rr, r2;
       if (d == 1) { rr = fabs(xs[s] - x[jj]) * g.inv_ls; r2 = rr * rr; }
-      else { r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)jj * d, d, g.inv_ls); rr = sqrt(r2); }
+      else { r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)jj * d, d, g.inv_ls, g.ils); rr = sqrt(r2); }
       val = kappa(g.kind, g.var, rr, r2);
     }
   }
@@ -3200,7 +3210,7 @@ __global__ __launch_bounds__(256) void post_mean_kernel(const double* __restrict
     }
   } else if (s < ns) {
     for (int i = ibeg; i < iend; ++i) {
-      const double r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)i * d, d, g.inv_ls);
+      const double r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)i * d, d, g.inv_ls, g.ils);
       acc = __builtin_fma(kappa(g.kind, g.var, sqrt(r2), r2), alpha[i], acc);
     }
   }
@@ -3403,7 +3413,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
       if (j < i0 && j < n) {
         double r, r2;
         if (d == 1) { r = fabs(x[i0] - x[j]) * g.inv_ls; r2 = r * r; }
-        else { r2 = scaled_dist2(x + (size_t)i0 * d, x + (size_t)j * d, d, g.inv_ls); r = sqrt(r2); }
+        else { r2 = scaled_dist2(x + (size_t)i0 * d, x + (size_t)j * d, d, g.inv_ls, nullptr); r = sqrt(r2); }
         const double w = ai * alpha[j] - MatIO<TS>::ld1(Kinv, (size_t)j * ld + i0);
         acc = __builtin_fma(w, dkappa_dell(g.kind, g.var, g.inv_ls, r, r2), acc);
         acck = __builtin_fma(w, kappa(g.kind, g.var, r, r2), acck);
@@ -3427,17 +3437,116 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
   }
 }
 
-// out[c] = sum over the nt*nt tile partials of component c (c < LMM_NG); upper tiles were never written -> skip them.
-__global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restrict__ partial, int nt, double* __restrict__ out) {
+// ARD variant of grad_reduce_kernel (an ARD latent: g.ils holds its d <= DK inverse lengthscales l_k^-1, g.inv_ls = 1 / the common
+// multiplier).  Per pair, with t_k = (x_ik - x_jk) / l_k, r^2 = sum_k t_k^2 and
+//     h(r) = v e^{-r^2/2} (SE),  3 v e^{-sqrt3 r} (Matern32),  (5/3) v (1 + sqrt5 r) e^{-sqrt5 r} (Matern52)   (finite at r = 0),
+//     d kappa / d l_k = h t_k^2 / l_k,    d kappa / d multiplier = h r^2 / multiplier  (= sum_k (l_k / multiplier) d kappa / d l_k).
+// The tile partials hold LMM_NG + d entries: the LMM_NG of grad_reduce_kernel ([0] = d/d multiplier) followed by the d sums
+// sum_{i>j in tile} w_ij d kappa_ij / d l_k.  Kinv is read once per tile, as in the isotropic kernel; the d extra FMAs per pair (and,
+// for DK <= 8, the t_k^2 kept in registers) leave the kernel bound by that read.  All sums of a tile are reduced with ONE barrier.
+template <int DK>
+__device__ __forceinline__ void ard_pair(int kind, double var, double r2, double w, double& acc0, double& acck, double& wh) {
+  double e, kap, h;
+  if (kind == LMM_KERNEL_SE) { e = exp_nonpos(-0.5 * r2); kap = var * e; h = kap; }
+  else {
+    const double r = sqrt(r2);
+    if (kind == LMM_KERNEL_MATERN32) {
+      const double s = 1.7320508075688772 * r;
+      e = exp_nonpos(-s); kap = var * (1.0 + s) * e; h = 3.0 * var * e;
+    } else {
+      const double s = 2.23606797749979 * r;
+      e = exp_nonpos(-s); kap = var * (1.0 + s + (5.0 / 3.0) * r2) * e; h = (5.0 / 3.0) * var * (1.0 + s) * e;
+    }
+  }
+  wh = w * h;
+  acc0 = __builtin_fma(wh, r2, acc0);
+  acck = __builtin_fma(w, kap, acck);
+}
+
+template <typename TS, int DK>
+__global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __restrict__ Kinv, int ld, int n, int nsplit,
+                                                              const double* __restrict__ alpha, const double* __restrict__ delta,
+                                                              const double* __restrict__ x, int d, LatentDev g, int nt,
+                                                              double* __restrict__ partial) {
+  constexpr int NV = LMM_NG + DK;
+  constexpr bool KEEP = DK <= 8;                  // keep t_k^2 in registers between the distance and the accumulation
+  __shared__ double sils[DK];
+  __shared__ double red[4][NV];
+  const int ti = blockIdx.x, tj = blockIdx.y;
+  if (ti < tj) return;
+  const int t = threadIdx.x;
+  if (t < DK) sils[t] = (t < d) ? g.ils[t] : 0.0;
+  __syncthreads();
+  const int i0 = ti * 64 + (t & 63);
+  const int cg = t >> 6;
+  double acc0 = 0.0, acck = 0.0, acc[DK], xi[DK];
+#pragma unroll
+  for (int k = 0; k < DK; ++k) { acc[k] = 0.0; xi[k] = 0.0; }
+  if (i0 < n) {
+#pragma unroll
+    for (int k = 0; k < DK; ++k) if (k < d) xi[k] = x[(size_t)i0 * d + k] * sils[k];
+    const double ai = alpha[i0];
+    for (int q = 0; q < 16; ++q) {
+      const int j = tj * 64 + cg + 4 * q;
+      if (j < i0 && j < n) {
+        const double* xj = x + (size_t)j * d;
+        double t2[KEEP ? DK : 1];
+        double r2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < DK; ++k)
+          if (k < d) {
+            const double tk = xi[k] - xj[k] * sils[k];
+            if (KEEP) t2[k] = tk * tk;
+            r2 = __builtin_fma(tk, tk, r2);
+          }
+        const double w = ai * alpha[j] - MatIO<TS>::ld1(Kinv, (size_t)j * ld + i0);
+        double wh;
+        ard_pair<DK>(g.kind, g.var, r2, w, acc0, acck, wh);
+#pragma unroll
+        for (int k = 0; k < DK; ++k)
+          if (k < d) {
+            double tk2;
+            if (KEEP) tk2 = t2[k];
+            else { const double tk = xi[k] - xj[k] * sils[k]; tk2 = tk * tk; }
+            acc[k] = __builtin_fma(wh, tk2, acc[k]);
+          }
+      }
+    }
+  }
+  double tra = 0.0, aaa = 0.0, trb = 0.0, aab = 0.0, ad = 0.0, sa = 0.0;
+  if (ti == tj && t < 64 && i0 < n) {
+    const double ai = alpha[i0], kii = MatIO<TS>::ld1(Kinv, (size_t)i0 * ld + i0);
+    if (i0 < nsplit) { tra = kii; aaa = ai * ai; } else { trb = kii; aab = ai * ai; }
+    ad = ai * delta[i0]; sa = ai;
+  }
+  const int lane = t & 63, wv = t >> 6;
+  double v[NV];
+  v[0] = acc0 * g.inv_ls; v[1] = tra; v[2] = aaa; v[3] = ad; v[4] = sa; v[5] = trb; v[6] = aab; v[7] = acck;
+#pragma unroll
+  for (int k = 0; k < DK; ++k) v[LMM_NG + k] = acc[k] * sils[k];
+#pragma unroll
+  for (int c = 0; c < NV; ++c) {
+    const double sc = wave_sum(v[c]);
+    if (lane == 0) red[wv][c] = sc;
+  }
+  __syncthreads();
+  const int ngs = LMM_NG + d;
+  if (t < ngs) partial[(size_t)ngs * (ti * nt + tj) + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+}
+
+// out[c] = sum over the nt*nt tile partials of component c (c < LMM_NG; the partials hold ngs >= LMM_NG components per tile, the
+// ones from LMM_NG on go to out_ard); upper tiles were never written -> skip them.
+__global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restrict__ partial, int nt, double* __restrict__ out, int ngs,
+                                                          double* __restrict__ out_ard) {
   __shared__ double sh[4];
-  for (int c = 0; c < LMM_NG; ++c) {
+  for (int c = 0; c < ngs; ++c) {
     double s = 0.0;
     for (int k = threadIdx.x; k < nt * nt; k += 256) {
       const int ti = k / nt, tj = k - ti * nt;
-      if (ti >= tj) s += partial[(size_t)LMM_NG * k + c];
+      if (ti >= tj) s += partial[(size_t)ngs * k + c];
     }
     const double tot = block_sum_256(s, sh);
-    if (threadIdx.x == 0) out[c] = tot;
+    if (threadIdx.x == 0) { if (c < LMM_NG) out[c] = tot; else out_ard[c - LMM_NG] = tot; }
   }
 }
 
@@ -3605,7 +3714,7 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     b.base = args[j0];
     for (int j = j0; j < j1; ++j) {
       const GramArgs& a = args[j];
-      b.A[j - j0] = a.A; b.var[j - j0] = a.var; b.inv_ls[j - j0] = a.inv_ls; b.diag_add[j - j0] = a.diag_add;
+      b.A[j - j0] = a.A; b.var[j - j0] = a.var; b.inv_ls[j - j0] = a.inv_ls; b.ils[j - j0] = a.ils; b.diag_add[j - j0] = a.diag_add;
       b.diag_vec[j - j0] = a.diag_vec; b.rider[j - j0] = a.rider; b.rider_sub[j - j0] = a.rider_sub; b.info_zero[j - j0] = a.info_zero;
     }
     b.base.cpw = gram_cpw(b.base.nrows / 64 - b.base.row_tile0, b.base.ncols / 64, j1 - j0);
@@ -4187,15 +4296,22 @@ void launch_set_identity(double* R, int ld, int nc, hipStream_t st) {
   LMM_TS_LAUNCH((set_identity_kernel<TS>), dim3((nc + 255) / 256, nc), dim3(256), 0, st, (void*)R, ld, nc);
 }
 
-int grad_partials(int n) { const int nt = (n + 63) / 64; return LMM_NG * nt * nt; }
+int grad_partials(int n, int d_ard) { const int nt = (n + 63) / 64; return (LMM_NG + d_ard) * nt * nt; }
 
 // out8: [dl/d ell, tr Kinv (rows < nsplit), a.a (rows < nsplit), a.delta, sum a, tr Kinv (rows >= nsplit), a.a (rows >= nsplit),
 //        sum_{i>j} (a_i a_j - Kinv_ij) K_ij]
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,
-                        LatentDev g, double* partial, double* out7, hipStream_t st) {
+                        LatentDev g, double* partial, double* out7, hipStream_t st, double* out_ard) {
   const int nt = (n + 63) / 64;
+  if (g.ils != nullptr) {          // ARD latent (the caller guarantees 1 < d <= LMM_ARD_GRAD_DMAX and out_ard != nullptr)
+    if (d <= 4) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, 4>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+    else if (d <= 8) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, 8>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+    else LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, LMM_ARD_GRAD_DMAX>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+    hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG + d, out_ard);
+    return;
+  }
   LMM_TS_LAUNCH((grad_reduce_kernel<TS>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
-  hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7);
+  hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG, (double*)nullptr);
 }
 
 void launch_vec_axpby(const double* a, double sa, const double* b, double sb, size_t n, double* out, hipStream_t st) {

@@ -93,9 +93,48 @@ _kind(::Matern52Kernel) = Cint(2)
 _desc(k::Kernel) = (_kind(k), 1.0, 1.0)
 _desc(k::ScaledKernel) = ((kd, v, l) = _desc(k.kernel); (kd, v * only(k.σ²), l))
 _desc(k::TransformedKernel{<:Kernel,<:ScaleTransform}) = ((kd, v, l) = _desc(k.kernel); (kd, v, l / only(k.transform.s)))
+# per-dimension lengthscales (KernelFunctions' with_lengthscale(k, ℓ::AbstractVector) = k ∘ ARDTransform(1 ./ ℓ)): the common
+# multiplier stays in `lengthscale`, the factors ard[k] (effective ℓ_k = lengthscale * ard[k]) travel as a tag (lmm_ard_create)
+_desc(k::TransformedKernel{<:Kernel,<:ARDTransform}) = _desc(k.kernel)
+_ard(k::Kernel) = nothing                                       # isotropic
+_ard(k::ScaledKernel) = _ard(k.kernel)
+_ard(k::TransformedKernel{<:Kernel,<:ScaleTransform}) = _ard(k.kernel)
+function _ard(k::TransformedKernel{<:Kernel,<:ARDTransform})   # the inner kernel sees v .* x: its lengthscales divide by v
+    a = _ard(k.kernel); v = Vector{Float64}(k.transform.v)
+    return a === nothing ? 1.0 ./ v : a ./ v
+end
 _mean(::AbstractGPs.ZeroMean) = 0.0
 _mean(m::AbstractGPs.ConstMean) = Float64(m.c)
-_gps(fs::Vector{<:AbstractGP}) = [begin (kd, v, l) = _desc(f.kernel); LmmGp(kd, v, l, _mean(f.mean)) end for f in fs]
+# `_gps(fs) do gps, tags ... end`: the lmm_gp_t array of the latents fs (nothing: none, for calls on a posterior handle) for the
+# duration of ONE library call.  Each ARD latent's factors are registered as a tag (kind = base | tag << 8) before the body runs and
+# destroyed after it, whatever happens; tags[l] is latent l's tag, 0 for an isotropic latent (a handle keeps its own copy of the
+# lengthscales, so destroying the tags after a posterior call is safe).
+function _gps(body, fs)
+    gps = LmmGp[]; tags = Cint[]
+    try
+        for f in (fs === nothing ? () : fs)
+            (kd, v, l) = _desc(f.kernel); a = _ard(f.kernel); t = Cint(0)
+            if a !== nothing
+                tr = Ref{Cint}(0)
+                GC.@preserve a check(ccall((:lmm_ard_create, liblmm), Cint, (Cint, Ptr{Cdouble}, Ref{Cint}), length(a), a, tr))
+                t = tr[]
+            end
+            push!(tags, t)
+            push!(gps, LmmGp(t == 0 ? kd : kd | (t << 8), v, l, _mean(f.mean)))
+        end
+        return body(gps, tags)
+    finally
+        for t in tags
+            t == 0 || ccall((:lmm_ard_destroy, liblmm), Cint, (Cint,), t)
+        end
+    end
+end
+# after a gradient call inside _gps: d logpdf / d ard[k] of each latent (its tag's lmm_ard_grad), nothing for an isotropic one
+function _ard_grads(tags::Vector{Cint}, d::Integer)
+    return [t == 0 ? nothing :
+            (g = Vector{Float64}(undef, d); GC.@preserve g check(ccall((:lmm_ard_grad, liblmm), Cint, (Cint, Ptr{Cdouble}), t, g)); g)
+            for t in tags]
+end
 
 # x as a d x n column-major matrix: Vector{Float64} => 1 x n; ColVecs => its X; RowVecs => transposed copy.
 _xmat(x::AbstractVector{<:Real}) = reshape(collect(Float64, x), 1, :)
@@ -120,10 +159,11 @@ function AbstractGPs.logpdf(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Rea
             (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ref{Cdouble}),
             fs.handle, U, S, p, m, σ², X, d, n, yv, 1, out))
     else
-        gps = _gps(fs.fs)
-        GC.@preserve X yv U S gps check(ccall((:lmm_oilmm_logpdf, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}),
-            X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, out))
+        _gps(fs.fs) do gps, tags
+            GC.@preserve X yv U S gps check(ccall((:lmm_oilmm_logpdf, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}),
+                X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, out))
+        end
     end
     return out[]
 end
@@ -132,11 +172,13 @@ end
 function AbstractGPs.logpdf(fx::ByOutputsFill{HIPOILMM}, Y::AbstractMatrix{<:Real})
     fs, H, σ², x = unpack(fx)
     isposterior(fs) && return [logpdf(fx, Y[:, c]) for c in axes(Y, 2)]
-    X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); Ym = Matrix{Float64}(Y); gps = _gps(fs.fs)
+    X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); Ym = Matrix{Float64}(Y)
     out = Vector{Float64}(undef, size(Ym, 2))
-    GC.@preserve X Ym U S gps out check(ccall((:lmm_oilmm_logpdf_multi, liblmm), Cint,
-        (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ptr{Cdouble}),
-        X, d, n, Ym, p, size(Ym, 2), U, S, m, σ², gps, 0, m, 1, out))
+    _gps(fs.fs) do gps, tags
+        GC.@preserve X Ym U S gps out check(ccall((:lmm_oilmm_logpdf_multi, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ptr{Cdouble}),
+            X, d, n, Ym, p, size(Ym, 2), U, S, m, σ², gps, 0, m, 1, out))
+    end
     return out
 end
 
@@ -145,22 +187,26 @@ end
 function AbstractGPs.logpdf(fx::ByOutputsFill{HIPDenseILMM}, Y::AbstractMatrix{<:Real})
     f, H, σ², x = unpack(fx)
     isposterior(f) && return [logpdf(fx, Y[:, c]) for c in axes(Y, 2)]
-    X = _xmat(x); d, n = size(X); p, m = size(H); Ym = Matrix{Float64}(Y); gps = _gps(f.fs); Hm = Matrix{Float64}(H)
+    X = _xmat(x); d, n = size(X); p, m = size(H); Ym = Matrix{Float64}(Y); Hm = Matrix{Float64}(H)
     out = Vector{Float64}(undef, size(Ym, 2))
-    GC.@preserve X Ym Hm gps out check(ccall((:lmm_ilmm_logpdf_multi, liblmm), Cint,
-        (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ptr{Cdouble}),
-        X, d, n, Ym, p, size(Ym, 2), Hm, m, σ², gps, C_NULL, out))
+    _gps(f.fs) do gps, tags
+        GC.@preserve X Ym Hm gps out check(ccall((:lmm_ilmm_logpdf_multi, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ptr{Cdouble}),
+            X, d, n, Ym, p, size(Ym, 2), Hm, m, σ², gps, C_NULL, out))
+    end
     return out
 end
 function AbstractGPs.logpdf(ft::ByOutputsFill{HIPMOGP}, Y::AbstractMatrix{<:Real})
     isposterior(ft.f) && return [logpdf(ft, Y[:, c]) for c in axes(Y, 2)]
     X = _xmat(ft.x.x); d, n = size(X); m = length(ft.f.fs); σ² = noise_var(ft.Σy)
     ft.x.out_dim == m || throw(ErrorException("out dim of x != out dim of f."))
-    U = Matrix{Float64}(I, m, m); S = ones(m); Ym = Matrix{Float64}(Y); gps = _gps(ft.f.fs)
+    U = Matrix{Float64}(I, m, m); S = ones(m); Ym = Matrix{Float64}(Y)
     out = Vector{Float64}(undef, size(Ym, 2))
-    GC.@preserve X Ym U S gps out check(ccall((:lmm_oilmm_logpdf_multi, liblmm), Cint,
-        (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ptr{Cdouble}),
-        X, d, n, Ym, m, size(Ym, 2), U, S, m, σ², gps, 0, m, 0, out))
+    _gps(ft.f.fs) do gps, tags
+        GC.@preserve X Ym U S gps out check(ccall((:lmm_oilmm_logpdf_multi, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ptr{Cdouble}),
+            X, d, n, Ym, m, size(Ym, 2), U, S, m, σ², gps, 0, m, 0, out))
+    end
     return out
 end
 
@@ -174,10 +220,12 @@ function AbstractGPs.logpdf(fx::ByOutputsFill{HIPDenseILMM}, y::AbstractVector{<
             (Ptr{Cvoid}, Cdouble, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{LmmJitters}, Ref{Cdouble}),
             f.handle, σ², X, d, n, yv, C_NULL, out))
     else
-        gps = _gps(f.fs); Hm = Matrix{Float64}(H)
-        GC.@preserve X yv Hm gps check(ccall((:lmm_ilmm_logpdf, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}),
-            X, d, n, yv, p, Hm, m, σ², gps, C_NULL, out))
+        Hm = Matrix{Float64}(H)
+        _gps(f.fs) do gps, tags
+            GC.@preserve X yv Hm gps check(ccall((:lmm_ilmm_logpdf, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}),
+                X, d, n, yv, p, Hm, m, σ², gps, C_NULL, out))
+        end
     end
     return out[]
 end
@@ -193,10 +241,11 @@ function AbstractGPs.logpdf(ft::ByOutputsFill{HIPMOGP}, y::AbstractVector{<:Real
             (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cdouble, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ref{Cdouble}),
             ft.f.handle, U, S, m, m, σ², X, d, n, yv, 0, out))
     else
-        gps = _gps(ft.f.fs)
-        GC.@preserve X yv gps check(ccall((:lmm_mogp_logpdf, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Ref{Cdouble}),
-            X, d, n, yv, m, σ², gps, 0, m, out))
+        _gps(ft.f.fs) do gps, tags
+            GC.@preserve X yv gps check(ccall((:lmm_mogp_logpdf, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Ref{Cdouble}),
+                X, d, n, yv, m, σ², gps, 0, m, out))
+        end
     end
     return out[]
 end
@@ -207,11 +256,13 @@ function AbstractGPs.logpdf(ft::FiniteGP{<:HIPMOGP,<:MOInputIsotopicByOutputs,<:
     isposterior(ft.f) && error("logpdf with a general Diagonal noise is served for the prior IndependentMOGP only")
     X = _xmat(ft.x.x); d, n = size(X); m = length(ft.f.fs)
     ft.x.out_dim == m || throw(ErrorException("out dim of x != out dim of f."))
-    gps = _gps(ft.f.fs); yv = Vector{Float64}(y); nv = Vector{Float64}(ft.Σy.diag)
+    yv = Vector{Float64}(y); nv = Vector{Float64}(ft.Σy.diag)
     out = Ref{Cdouble}(0.0)
-    GC.@preserve X yv nv gps check(ccall((:lmm_mogp_logpdf_diag, liblmm), Cint,
-        (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{LmmGp}, Cint, Cint, Ref{Cdouble}),
-        X, d, n, yv, m, nv, gps, 0, m, out))
+    _gps(ft.f.fs) do gps, tags
+        GC.@preserve X yv nv gps check(ccall((:lmm_mogp_logpdf_diag, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{LmmGp}, Cint, Cint, Ref{Cdouble}),
+            X, d, n, yv, m, nv, gps, 0, m, out))
+    end
     return out[]
 end
 
@@ -242,10 +293,11 @@ function AbstractGPs.posterior(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:
             fs.handle, U, S, p, m, σ², X, d, n, yv, h))
         return ILMM(HIPMOGP(fs.fs, h[], _push_train(fs.train, X, σ², yv)), H)
     end
-    gps = _gps(fs.fs)
-    GC.@preserve X yv U S gps check(ccall((:lmm_oilmm_posterior_create, liblmm), Cint,
-        (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Ref{Ptr{Cvoid}}),
-        X, d, n, yv, p, U, S, m, σ², gps, 0, m, h))
+    _gps(fs.fs) do gps, tags
+        GC.@preserve X yv U S gps check(ccall((:lmm_oilmm_posterior_create, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Ref{Ptr{Cvoid}}),
+            X, d, n, yv, p, U, S, m, σ², gps, 0, m, h))
+    end
     return ILMM(HIPMOGP(fs.fs, h[], [(X, Float64(σ²), yv)]), H)    # again an ILMM with the same H (src/oilmm.jl:133)
 end
 
@@ -260,10 +312,11 @@ function AbstractGPs.posterior(ft::ByOutputsFill{HIPMOGP}, y::AbstractVector{<:R
             ft.f.handle, U, S, m, m, σ², X, d, n, yv, h))
         return HIPMOGP(ft.f.fs, h[], _push_train(ft.f.train, X, σ², yv))
     end
-    gps = _gps(ft.f.fs)
-    GC.@preserve X yv gps check(ccall((:lmm_mogp_posterior_create, liblmm), Cint,
-        (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Ref{Ptr{Cvoid}}),
-        X, d, n, yv, m, σ², gps, 0, m, h))
+    _gps(ft.f.fs) do gps, tags
+        GC.@preserve X yv gps check(ccall((:lmm_mogp_posterior_create, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Ref{Ptr{Cvoid}}),
+            X, d, n, yv, m, σ², gps, 0, m, h))
+    end
     return HIPMOGP(ft.f.fs, h[], [(X, Float64(σ²), yv)])
 end
 
@@ -279,10 +332,12 @@ function AbstractGPs.posterior(fx::ByOutputsFill{HIPDenseILMM}, y::AbstractVecto
         # (a latent view conditioned ON latent observations keeps no training record: its batches were observed through different H's)
         return ILMM(HIPMOGP(f.fs, h[], f.mix === nothing ? _push_train(f.train, X, σ², yv) : nothing), H)
     end
-    gps = _gps(f.fs); Hm = Matrix{Float64}(H)
-    GC.@preserve X yv Hm gps check(ccall((:lmm_ilmm_posterior_create, liblmm), Cint,
-        (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Ptr{Cvoid}}),
-        X, d, n, yv, p, Hm, m, σ², gps, C_NULL, h))
+    Hm = Matrix{Float64}(H)
+    _gps(f.fs) do gps, tags
+        GC.@preserve X yv Hm gps check(ccall((:lmm_ilmm_posterior_create, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Ptr{Cvoid}}),
+            X, d, n, yv, p, Hm, m, σ², gps, C_NULL, h))
+    end
     return ILMM(HIPMOGP(f.fs, h[], [(X, Float64(σ²), yv)]), H)
 end
 
@@ -293,13 +348,14 @@ end
 function _mean_var(fx, want_var::Bool)
     f, H, σ², x = unpack(fx)
     X = _xmat(x); d, ns = size(X); U, S, p, m = _hargs(H)
-    gps = isposterior(f) ? LmmGp[] : _gps(f.fs)
     M = Vector{Float64}(undef, ns * p); V = want_var ? similar(M) : Float64[]
-    GC.@preserve X U S gps M V check(ccall((:lmm_oilmm_mean_and_var, liblmm), Cint,
-        (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint,
-         Ptr{LmmJitters}, Ptr{Cdouble}, Ptr{Cdouble}),
-        f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, _ptr(S), p, m, 0, m, σ², 1, X, d, ns, C_NULL,
-        M, want_var ? pointer(V) : Ptr{Cdouble}(C_NULL)))
+    _gps(isposterior(f) ? nothing : f.fs) do gps, tags
+        GC.@preserve X U S gps M V check(ccall((:lmm_oilmm_mean_and_var, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint,
+             Ptr{LmmJitters}, Ptr{Cdouble}, Ptr{Cdouble}),
+            f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, _ptr(S), p, m, 0, m, σ², 1, X, d, ns, C_NULL,
+            M, want_var ? pointer(V) : Ptr{Cdouble}(C_NULL)))
+    end
     return M, V
 end
 AbstractGPs.mean_and_var(fx::ByOutputsFill{HIPOILMM}) = _mean_var(fx, true)
@@ -323,11 +379,12 @@ AbstractGPs.var(fx::ByOutputsFill{HIPDenseILMM}) = mean_and_var(fx)[2]
 # reference src/independent_mogp.jl:50,55: vcat of the latent marginals (+ Σy on the variances)
 function AbstractGPs.mean_and_var(ft::ByOutputsFill{HIPMOGP})
     X = _xmat(ft.x.x); d, ns = size(X); m = length(ft.f.fs)
-    gps = isposterior(ft.f) ? LmmGp[] : _gps(ft.f.fs)
     M = Vector{Float64}(undef, ns * m); V = similar(M)
-    GC.@preserve X gps M V check(ccall((:lmm_latent_marginals, liblmm), Cint,
-        (Ptr{Cvoid}, Ptr{LmmGp}, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
-        ft.f.handle, isposterior(ft.f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), m, X, d, ns, M, V))
+    _gps(isposterior(ft.f) ? nothing : ft.f.fs) do gps, tags
+        GC.@preserve X gps M V check(ccall((:lmm_latent_marginals, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+            ft.f.handle, isposterior(ft.f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), m, X, d, ns, M, V))
+    end
     return M, V .+ noise_var(ft.Σy)
 end
 AbstractGPs.mean(ft::ByOutputsFill{HIPMOGP}) = mean_and_var(ft)[1]
@@ -344,11 +401,12 @@ function AbstractGPs.mean_and_cov(fx::Union{ByOutputsFill{HIPOILMM},ByOutputsFil
             f.handle, σ², X, d, ns, C_NULL, M, Cm))
         return M, Cm
     end
-    gps = isposterior(f) ? LmmGp[] : _gps(f.fs)
-    GC.@preserve X U S gps M Cm check(ccall((:lmm_lmm_mean_and_cov, liblmm), Cint,
-        (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint,
-         Ptr{LmmJitters}, Ptr{Cdouble}, Ptr{Cdouble}),
-        f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, _ptr(S), p, m, 0, m, σ², 1, X, d, ns, C_NULL, M, Cm))
+    _gps(isposterior(f) ? nothing : f.fs) do gps, tags
+        GC.@preserve X U S gps M Cm check(ccall((:lmm_lmm_mean_and_cov, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint,
+             Ptr{LmmJitters}, Ptr{Cdouble}, Ptr{Cdouble}),
+            f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, _ptr(S), p, m, 0, m, σ², 1, X, d, ns, C_NULL, M, Cm))
+    end
     return M, Cm
 end
 AbstractGPs.cov(fx::Union{ByOutputsFill{HIPOILMM},ByOutputsFill{HIPDenseILMM}}) = mean_and_cov(fx)[2]
@@ -374,11 +432,12 @@ function _rand(rng::AbstractRNG, fx, N::Int)
         end
         return out
     end
-    gps = isposterior(f) ? LmmGp[] : _gps(f.fs)
-    GC.@preserve X U S gps z ε out check(ccall((:lmm_lmm_rand_multi, liblmm), Cint,
-        (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint, Cint,
-         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmJitters}, Ptr{Cdouble}),
-        f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, _ptr(S), p, m, 0, m, σ², 1, X, d, ns, N, z, ε, C_NULL, out))
+    _gps(isposterior(f) ? nothing : f.fs) do gps, tags
+        GC.@preserve X U S gps z ε out check(ccall((:lmm_lmm_rand_multi, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint, Cint,
+             Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmJitters}, Ptr{Cdouble}),
+            f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, _ptr(S), p, m, 0, m, σ², 1, X, d, ns, N, z, ε, C_NULL, out))
+    end
     return out
 end
 const HIPLMMFinite = Union{ByOutputsFill{HIPOILMM},ByOutputsFill{HIPDenseILMM}}
@@ -395,11 +454,12 @@ function _rand_mogp(rng::AbstractRNG, ft, N::Int)
     end
     out = Matrix{Float64}(undef, ns * m, N)
     jit = Ref(LmmJitters(1e-9, σ², σ²))
-    gps = isposterior(ft.f) ? LmmGp[] : _gps(ft.f.fs)
-    GC.@preserve X U gps z out check(ccall((:lmm_lmm_rand_multi, liblmm), Cint,
-        (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint, Cint,
-         Ptr{Cdouble}, Ptr{Cdouble}, Ref{LmmJitters}, Ptr{Cdouble}),
-        ft.f.handle, isposterior(ft.f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, C_NULL, m, m, 0, m, σ², 0, X, d, ns, N, z, C_NULL, jit, out))
+    _gps(isposterior(ft.f) ? nothing : ft.f.fs) do gps, tags
+        GC.@preserve X U gps z out check(ccall((:lmm_lmm_rand_multi, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint, Cint,
+             Ptr{Cdouble}, Ptr{Cdouble}, Ref{LmmJitters}, Ptr{Cdouble}),
+            ft.f.handle, isposterior(ft.f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, C_NULL, m, m, 0, m, σ², 0, X, d, ns, N, z, C_NULL, jit, out))
+    end
     return out
 end
 AbstractGPs.rand(rng::AbstractRNG, ft::ByOutputsFill{HIPMOGP}) = vec(_rand_mogp(rng, ft, 1))
@@ -457,13 +517,14 @@ AbstractGPs.var(ft::ByFeaturesFill{HIPMOGP}) = mean_and_var(ft)[2]
 function AbstractGPs.mean_and_cov(ft::ByOutputsFill{HIPMOGP})
     X = _xmat(ft.x.x); d, ns = size(X); m = length(ft.f.fs); σ² = noise_var(ft.Σy)
     U = Matrix{Float64}(I, m, m)
-    gps = isposterior(ft.f) ? LmmGp[] : _gps(ft.f.fs)
     M = Vector{Float64}(undef, ns * m); Cm = Matrix{Float64}(undef, ns * m, ns * m)
     jit = Ref(LmmJitters(1e-9, 0.0, 0.0))                   # cov(f, x) + Σy of a bare MOGP: no latent jitter (src/independent_mogp.jl:60-63)
-    GC.@preserve X U gps M Cm check(ccall((:lmm_lmm_mean_and_cov, liblmm), Cint,
-        (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint,
-         Ref{LmmJitters}, Ptr{Cdouble}, Ptr{Cdouble}),
-        ft.f.handle, isposterior(ft.f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, Ptr{Cdouble}(C_NULL), m, m, 0, m, σ², 1, X, d, ns, jit, M, Cm))
+    _gps(isposterior(ft.f) ? nothing : ft.f.fs) do gps, tags
+        GC.@preserve X U gps M Cm check(ccall((:lmm_lmm_mean_and_cov, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Cdouble, Cint, Ptr{Cdouble}, Cint, Cint,
+             Ref{LmmJitters}, Ptr{Cdouble}, Ptr{Cdouble}),
+            ft.f.handle, isposterior(ft.f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, Ptr{Cdouble}(C_NULL), m, m, 0, m, σ², 1, X, d, ns, jit, M, Cm))
+    end
     return M, Cm
 end
 AbstractGPs.cov(ft::ByOutputsFill{HIPMOGP}) = mean_and_cov(ft)[2]
@@ -497,11 +558,12 @@ function AbstractGPs.cov(f::HIPMOGP, x::MOIsotopic, y::MOIsotopic)
     m = length(f.fs)
     (x.out_dim == m && y.out_dim == m) || throw(ErrorException("out dim of x != out dim of f."))
     X = _xmat(x.x); Y = _xmat(y.x); d, n = size(X); n2 = size(Y, 2)
-    gps = isposterior(f) ? LmmGp[] : _gps(f.fs)
     Cm = Matrix{Float64}(undef, m * n, m * n2)
-    GC.@preserve X Y gps Cm check(ccall((:lmm_mogp_cross_cov, liblmm), Cint,
-        (Ptr{Cvoid}, Ptr{LmmGp}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}),
-        f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), m, 0, m, X, d, n, _byfeat(x), Y, n2, _byfeat(y), Cm))
+    _gps(isposterior(f) ? nothing : f.fs) do gps, tags
+        GC.@preserve X Y gps Cm check(ccall((:lmm_mogp_cross_cov, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}),
+            f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), m, 0, m, X, d, n, _byfeat(x), Y, n2, _byfeat(y), Cm))
+    end
     return Cm
 end
 AbstractGPs.cov(f::HIPMOGP, x::MOIsotopic) = cov(f, x, x)
@@ -510,11 +572,12 @@ function _mean_var(f::HIPMOGP, x::MOIsotopic)
     m = length(f.fs)
     x.out_dim == m || throw(ErrorException("out dim of x != out dim of f."))
     X = _xmat(x.x); d, ns = size(X)
-    gps = isposterior(f) ? LmmGp[] : _gps(f.fs)
     M = Vector{Float64}(undef, ns * m); V = similar(M)
-    GC.@preserve X gps M V check(ccall((:lmm_latent_marginals, liblmm), Cint,
-        (Ptr{Cvoid}, Ptr{LmmGp}, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
-        f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), m, X, d, ns, M, V))
+    _gps(isposterior(f) ? nothing : f.fs) do gps, tags
+        GC.@preserve X gps M V check(ccall((:lmm_latent_marginals, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+            f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), m, X, d, ns, M, V))
+    end
     x isa MOInputIsotopicByFeatures && return _to_features(M, x), _to_features(V, x)
     return M, V
 end
@@ -528,36 +591,52 @@ AbstractGPs.var(f::HIPMOGP, x::MOIsotopic) = _mean_var(f, x)[2]
 
 # kernel cotangent: the library differentiates w.r.t. the EFFECTIVE (variance, lengthscale); the chain rule through the
 # kernel's construction: ScaledKernel: v = v_inner σ² -> d/dσ² = gv v_inner; ScaleTransform: ℓ = ℓ_inner / s -> d/ds = -gl ℓ_inner / s².
-_ktangent(k::Kernel, gv, gl) = NoTangent()                                    # SEKernel() etc. carry no parameters
-function _ktangent(k::ScaledKernel, gv, gl)
+# ga: d/d ard[k] of an ARD latent (lmm_ard_grad; gl is then d/d the common multiplier).  ARDTransform(v): ard = ard_inner ./ v
+# -> d/dv_k = -ga_k ard_inner_k / v_k^2 (with no inner factors, ℓ_k = multiplier / v_k: d/dv_k = -ℓ_k^2 d/dℓ_k), d/d ard_inner = ga ./ v.
+_ktangent(k::Kernel, gv, gl, ga=nothing) = NoTangent()                        # SEKernel() etc. carry no parameters
+function _ktangent(k::ScaledKernel, gv, gl, ga=nothing)
     (_, vin, _) = _desc(k.kernel)
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv * only(k.σ²), gl), σ²=[gv * vin])
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv * only(k.σ²), gl, ga), σ²=[gv * vin])
 end
-function _ktangent(k::TransformedKernel{<:Kernel,<:ScaleTransform}, gv, gl)
+function _ktangent(k::TransformedKernel{<:Kernel,<:ScaleTransform}, gv, gl, ga=nothing)
     (_, _, lin) = _desc(k.kernel); s = only(k.transform.s)
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl / s), transform=Tangent{typeof(k.transform)}(; s=[-gl * lin / s^2]))
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl / s, ga), transform=Tangent{typeof(k.transform)}(; s=[-gl * lin / s^2]))
+end
+function _ktangent(k::TransformedKernel{<:Kernel,<:ARDTransform}, gv, gl, ga=nothing)
+    v = Vector{Float64}(k.transform.v); ain = _ard(k.kernel)
+    ga === nothing && return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl), transform=NoTangent())
+    a0 = ain === nothing ? ones(length(v)) : ain
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl, ain === nothing ? nothing : ga ./ v),
+                              transform=Tangent{typeof(k.transform)}(; v=-ga .* a0 ./ v .^ 2))
 end
 _mtangent(::AbstractGPs.ZeroMean, g) = NoTangent()
 _mtangent(m::AbstractGPs.ConstMean, g) = Tangent{typeof(m)}(; c=g)
-_fstangent(fs::Vector{<:AbstractGP}, gg::Vector{LmmGpGrad}, Δ) =
-    [Tangent{typeof(f)}(; mean=_mtangent(f.mean, Δ * g.mean), kernel=_ktangent(f.kernel, Δ * g.variance, Δ * g.lengthscale)) for (f, g) in zip(fs, gg)]
+# gard: nothing, or per latent d/d ard (nothing for an isotropic latent) from _ard_grads
+_fstangent(fs::Vector{<:AbstractGP}, gg::Vector{LmmGpGrad}, Δ, gard=nothing) =
+    [Tangent{typeof(f)}(; mean=_mtangent(f.mean, Δ * g.mean),
+                          kernel=_ktangent(f.kernel, Δ * g.variance, Δ * g.lengthscale,
+                                           (gard === nothing || gard[l] === nothing) ? nothing : Δ .* gard[l]))
+     for (l, (f, g)) in enumerate(zip(fs, gg))]
 _noise_tangent(fx, g) = Tangent{typeof(fx.Σy)}(; diag=Tangent{typeof(fx.Σy.diag)}(; value=g))     # Fill(σ², n p): one parameter
 _htangent(H::Orthogonal, gU, gS) = Tangent{typeof(H)}(; U=gU, S=Tangent{typeof(H.S)}(; diag=gS))
 
 function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real})
     fs, H, σ², x = unpack(fx)
-    X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); gps = _gps(fs.fs); yv = Vector{Float64}(y)
+    X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); gard = nothing; yv = Vector{Float64}(y)
     val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
     gy = Vector{Float64}(undef, n * p); gS = Vector{Float64}(undef, m); gU = Matrix{Float64}(undef, p, m)
     gg = Vector{LmmGpGrad}(undef, m)
     if isposterior(fs)
         fs.train === nothing && error("this posterior does not carry its training data")
         X0, bn, bs, y0 = _merged_train(fs.train, p); n0 = size(X0, 2); gy0 = Vector{Float64}(undef, n0 * p); gb = similar(bs)
-        GC.@preserve X0 bn bs y0 X yv U S gps gy0 gy gb gS gU gg check(ccall((:lmm_oilmm_post_logpdf_grad_seq, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
-             Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
-             Ptr{Cdouble}, Ptr{LmmGpGrad}),
-            X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy0, gy, gb, gσ, gS, gU, gg))
+        _gps(fs.fs) do gps, tags
+            GC.@preserve X0 bn bs y0 X yv U S gps gy0 gy gb gS gU gg check(ccall((:lmm_oilmm_post_logpdf_grad_seq, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                 Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
+                 Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy0, gy, gb, gσ, gS, gU, gg))
+            gard = _ard_grads(tags, d)
+        end
         # The library returns TOTAL derivatives through the posterior, including those w.r.t. the training data (gy0) and the
         # training noise (gb, one per conditioning batch).  The posterior model object has no differentiable slot for (x, σ², y) -- they entered through
         # `posterior`, whose own rrule would be the place to receive them -- so THIS pullback propagates the cotangents of the
@@ -565,13 +644,16 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
         # θ -> logpdf(posterior(f_θ(x, σ²), y)(x*, σ²*), y*) end to end use `predictive_logpdf_and_gradient` below, which returns them.
         fs.last_train_cotangents[] = _split_train(gy0, gb, bn, p)      # one entry per conditioning batch when there are several
     else
-        GC.@preserve X yv U S gps gy gS gU gg check(ccall((:lmm_oilmm_logpdf_grad, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
-             Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-            X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy, gσ, gS, gU, gg))
+        _gps(fs.fs) do gps, tags
+            GC.@preserve X yv U S gps gy gS gU gg check(ccall((:lmm_oilmm_logpdf_grad, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
+                 Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy, gσ, gS, gU, gg))
+            gard = _ard_grads(tags, d)
+        end
     end
     function logpdf_pullback(Δ)
-        dlat = Tangent{typeof(fs)}(; fs=_fstangent(fs.fs, gg, Δ))
+        dlat = Tangent{typeof(fs)}(; fs=_fstangent(fs.fs, gg, Δ, gard))
         dfx = Tangent{typeof(fx)}(; f=Tangent{typeof(fx.f)}(; f=dlat, H=_htangent(H, Δ .* gU, Δ .* gS)), Σy=_noise_tangent(fx, Δ * gσ[]))
         return NoTangent(), dfx, Δ .* gy
     end
@@ -590,25 +672,31 @@ end
 # IndependentMOGP (reference test/independent_mogp.jl:65-66): the OILMM with U = I, S = 1 and no regulariser
 function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), ft::ByOutputsFill{HIPMOGP}, y::AbstractVector{<:Real})
     f = ft.f; X = _xmat(ft.x.x); d, n = size(X); m = length(f.fs); σ² = noise_var(ft.Σy)
-    U = Matrix{Float64}(I, m, m); S = ones(m); gps = _gps(f.fs); yv = Vector{Float64}(y)
+    U = Matrix{Float64}(I, m, m); S = ones(m); gard = nothing; yv = Vector{Float64}(y)
     val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
     gy = Vector{Float64}(undef, n * m); gg = Vector{LmmGpGrad}(undef, m)
     if isposterior(f)
         f.train === nothing && error("this posterior does not carry its training data")
         X0, bn, bs, y0 = _merged_train(f.train, m); n0 = size(X0, 2)
-        GC.@preserve X0 bn bs y0 X yv U S gps gy gg check(ccall((:lmm_oilmm_post_logpdf_grad_seq, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
-             Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
-             Ptr{Cdouble}, Ptr{LmmGpGrad}),
-            X0, d, n0, bn, bs, length(bn), y0, X, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, C_NULL, gy, C_NULL, gσ, C_NULL, C_NULL, gg))
+        _gps(f.fs) do gps, tags
+            GC.@preserve X0 bn bs y0 X yv U S gps gy gg check(ccall((:lmm_oilmm_post_logpdf_grad_seq, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                 Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
+                 Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                X0, d, n0, bn, bs, length(bn), y0, X, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, C_NULL, gy, C_NULL, gσ, C_NULL, C_NULL, gg))
+            gard = _ard_grads(tags, d)
+        end
     else
-        GC.@preserve X yv U S gps gy gg check(ccall((:lmm_oilmm_logpdf_grad, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
-             Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-            X, d, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, gy, gσ, C_NULL, C_NULL, gg))
+        _gps(f.fs) do gps, tags
+            GC.@preserve X yv U S gps gy gg check(ccall((:lmm_oilmm_logpdf_grad, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
+                 Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                X, d, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, gy, gσ, C_NULL, C_NULL, gg))
+            gard = _ard_grads(tags, d)
+        end
     end
     function logpdf_pullback(Δ)
-        dft = Tangent{typeof(ft)}(; f=Tangent{typeof(f)}(; fs=_fstangent(f.fs, gg, Δ)), Σy=_noise_tangent(ft, Δ * gσ[]))
+        dft = Tangent{typeof(ft)}(; f=Tangent{typeof(f)}(; fs=_fstangent(f.fs, gg, Δ, gard)), Σy=_noise_tangent(ft, Δ * gσ[]))
         return NoTangent(), dft, Δ .* gy
     end
     return val[], logpdf_pullback
@@ -618,7 +706,7 @@ end
 # the posterior's predictive logpdf as the joint density of (y, y*) under two-block noise minus the density of y
 function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HIPDenseILMM}, y::AbstractVector{<:Real})
     f, H, σ², x = unpack(fx)
-    X = _xmat(x); d, n = size(X); p, m = size(H); gps = _gps(f.fs); Hm = Matrix{Float64}(H); yv = Vector{Float64}(y)
+    X = _xmat(x); d, n = size(X); p, m = size(H); gard = nothing; Hm = Matrix{Float64}(H); yv = Vector{Float64}(y)
     val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
     gy = Vector{Float64}(undef, n * p); gH = Matrix{Float64}(undef, p, m); gg = Vector{LmmGpGrad}(undef, m)
     if isposterior(f) && f.mix !== nothing
@@ -629,28 +717,37 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
         Hp = f.mix::Matrix{Float64}; pp = size(Hp, 1)
         X0, bn, bs, y0 = _merged_train(f.train, pp); n0 = size(X0, 2); gy0 = Vector{Float64}(undef, n0 * pp); gb = similar(bs)
         gHp = Matrix{Float64}(undef, pp, m)
-        GC.@preserve X0 bn bs y0 X yv Hp gps gy0 gy gb gHp gg check(ccall((:lmm_ilmm_post_latent_logpdf_grad_seq, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
-             Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-            X0, d, n0, bn, bs, length(bn), y0, X, n, yv, pp, Hp, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gHp, gg))
+        _gps(f.fs) do gps, tags
+            GC.@preserve X0 bn bs y0 X yv Hp gps gy0 gy gb gHp gg check(ccall((:lmm_ilmm_post_latent_logpdf_grad_seq, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
+                 Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                X0, d, n0, bn, bs, length(bn), y0, X, n, yv, pp, Hp, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gHp, gg))
+            gard = _ard_grads(tags, d)
+        end
         f.last_train_cotangents[] = merge(_split_train(gy0, gb, bn, pp), (H_train=gHp,))
         fill!(gH, 0.0)
     elseif isposterior(f)
         f.train === nothing && error("this posterior does not carry its training data")
         X0, bn, bs, y0 = _merged_train(f.train, p); n0 = size(X0, 2); gy0 = Vector{Float64}(undef, n0 * p); gb = similar(bs)
-        GC.@preserve X0 bn bs y0 X yv Hm gps gy0 gy gb gH gg check(ccall((:lmm_ilmm_post_logpdf_grad_seq, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
-             Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-            X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gH, gg))
+        _gps(f.fs) do gps, tags
+            GC.@preserve X0 bn bs y0 X yv Hm gps gy0 gy gb gH gg check(ccall((:lmm_ilmm_post_logpdf_grad_seq, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
+                 Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gH, gg))
+            gard = _ard_grads(tags, d)
+        end
         f.last_train_cotangents[] = _split_train(gy0, gb, bn, p)
     else
-        GC.@preserve X yv Hm gps gy gH gg check(ccall((:lmm_ilmm_logpdf_grad, liblmm), Cint,
-            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble},
-             Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-            X, d, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy, gσ, gH, gg))
+        _gps(f.fs) do gps, tags
+            GC.@preserve X yv Hm gps gy gH gg check(ccall((:lmm_ilmm_logpdf_grad, liblmm), Cint,
+                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble},
+                 Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                X, d, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy, gσ, gH, gg))
+            gard = _ard_grads(tags, d)
+        end
     end
     function logpdf_pullback(Δ)
-        dfx = Tangent{typeof(fx)}(; f=Tangent{typeof(fx.f)}(; f=Tangent{typeof(f)}(; fs=_fstangent(f.fs, gg, Δ)), H=Δ .* gH),
+        dfx = Tangent{typeof(fx)}(; f=Tangent{typeof(fx.f)}(; f=Tangent{typeof(f)}(; fs=_fstangent(f.fs, gg, Δ, gard)), H=Δ .* gH),
                                   Σy=_noise_tangent(fx, Δ * gσ[]))
         return NoTangent(), dfx, Δ .* gy
     end
@@ -697,12 +794,14 @@ end
 # adds the regulariser, ONE 8-byte all-reduce finishes it (SURVEY.md section 8e)
 function sharded_logpdf(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real}, rank::Integer, world::Integer)
     fs, H, σ², x = unpack(fx)
-    X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); gps = _gps(fs.fs); yv = Vector{Float64}(y)
+    X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); yv = Vector{Float64}(y)
     l0, l1 = latent_shard(m, rank, world)
     out = Ref{Cdouble}(0.0)
-    GC.@preserve X yv U S gps check(ccall((:lmm_oilmm_logpdf, liblmm), Cint,
-        (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}),
-        X, d, n, yv, p, U, S, m, σ², gps, l0, l1, rank == 0 ? 1 : 0, out))
+    _gps(fs.fs) do gps, tags
+        GC.@preserve X yv U S gps check(ccall((:lmm_oilmm_logpdf, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}),
+            X, d, n, yv, p, U, S, m, σ², gps, l0, l1, rank == 0 ? 1 : 0, out))
+    end
     return allreduce_sum!([out[]])[1]
 end
 

@@ -23,17 +23,32 @@ from . import _lib as L
 
 
 # ---- kernels / GPs (KernelFunctions.jl + AbstractGPs.jl names) ------------------------------------
+def _ls_key(ls):
+    """Hashable, comparable form of a lengthscale: the float, or the tuple of a per-dimension (ARD) vector."""
+    return ls if isinstance(ls, float) else tuple(ls.tolist())
+
+
 class _Kernel:
+    """variance * kernel(|x - x'| / lengthscale).  A length-d vector lengthscale gives per-dimension lengthscales: KernelFunctions'
+    with_lengthscale(k, l::AbstractVector) = k o ARDTransform(1 ./ l)."""
     kind = ""
 
-    def __init__(self, variance: float = 1.0, lengthscale: float = 1.0):
-        self.variance, self.lengthscale = float(variance), float(lengthscale)
+    def __init__(self, variance: float = 1.0, lengthscale=1.0):
+        self.variance = float(variance)
+        if np.ndim(lengthscale) == 0:
+            self.lengthscale = float(lengthscale)
+        else:
+            ls = np.array(lengthscale, dtype=np.float64).reshape(-1)
+            if ls.size == 0:
+                raise ValueError("lengthscale vector is empty")
+            self.lengthscale = ls
 
     def __eq__(self, o):
-        return type(self) is type(o) and (self.variance, self.lengthscale) == (o.variance, o.lengthscale)
+        return type(self) is type(o) and (self.variance, _ls_key(self.lengthscale)) == (o.variance, _ls_key(o.lengthscale))
 
     def __repr__(self):
-        return f"{type(self).__name__}(variance={self.variance}, lengthscale={self.lengthscale})"
+        ls = self.lengthscale if isinstance(self.lengthscale, float) else list(self.lengthscale.tolist())
+        return f"{type(self).__name__}(variance={self.variance}, lengthscale={ls})"
 
 
 class SEKernel(_Kernel):
@@ -349,7 +364,7 @@ def _split_train_grad(gy, sizes, p: int):
 def _gps_arg(mogp):
     """(descs, lmm_gp_t array) of an IndependentMOGP's latents.  The ctypes array is rebuilt only when a hyperparameter changed (the key
     is the tuple of current values: building it costs a third of filling the array, which at m = 20 is 25 us of a 380-us call)."""
-    key = tuple((g.kernel.kind, g.kernel.variance, g.kernel.lengthscale, g.mean) for g in mogp.fs)
+    key = tuple((g.kernel.kind, g.kernel.variance, _ls_key(g.kernel.lengthscale), g.mean) for g in mogp.fs)
     hit = getattr(mogp, "_gps_cache", None)
     if hit is not None and hit[0] == key:
         return hit[1], hit[2]
@@ -451,6 +466,16 @@ def logpdf(fx: FiniteGP, y, with_regulariser: bool = True) -> float:
     return out.value
 
 
+def _gps_grads(gg, ga, m: int, d: int) -> list:
+    """The latents' kernel-parameter gradients: "lengthscale" is a float for an isotropic latent and, for a per-dimension (ARD) one,
+    the length-d array d logpdf / d lengthscale_k (its tag's lmm_ard_grad: the array passes multiplier 1)."""
+    out = []
+    for l in range(m):
+        ls = ga.ard.grad(l, d) if ga.ard.tags[l] else gg[l].lengthscale
+        out.append({"variance": gg[l].variance, "lengthscale": ls, "mean": gg[l].mean})
+    return out
+
+
 def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True) -> dict:
     """Value and gradient of logpdf(fx, y) -- what `Zygote.gradient(logpdf, fx, y)` differentiates in the reference's tests
     (test/oilmm.jl:31-32, test/ilmm.jl:31-32, test/independent_mogp.jl:65-66).
@@ -487,38 +512,38 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True) -> dict:
         val, gs2 = C.c_double(), C.c_double()
         gy, gH = _alloc_like(y if L._is_torch(y) else x.x, n * m), np.empty(p * m)
         gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
-        gg = (L.GpGradT * m)()
+        gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.fs])
         L.check(lib.lmm_ilmm_post_latent_logpdf_grad_seq(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
-                                                         L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), L.gps_array([g.desc() for g in f.fs]),
+                                                         L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
                                                          None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
                                                          L.Arr(gH, True).ptr, gg))
         return {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
                 "sigma2_train": _train_noise_grad(gb, s2b), "H": gH.reshape(m, p).T.copy(),
-                "gps": [{"variance": gg[l].variance, "lengthscale": gg[l].lengthscale, "mean": gg[l].mean} for l in range(m)]}
+                "gps": _gps_grads(gg, ga, m, x.dim)}
     if not mogp and not f.is_oilmm:
         unpack(fx)
         Ha, _, p, m = _H_args(f.H)
         n = x.n
         val, gs2 = C.c_double(), C.c_double()
         gy, gH = _alloc_like(y if L._is_torch(y) else x.x, n * p), np.empty(p * m)
-        gg = (L.GpGradT * m)()
+        gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.f.fs])
         if post is not None:          # reference test/ilmm.jl:32: gradient(logpdf, pi, y_test) on the dense-H posterior
             x0, s2b, y0, sizes = _merged_train(post.train, p)
             bn, bs, gb = _batch_args(s2b, sizes)
             gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
             L.check(lib.lmm_ilmm_post_logpdf_grad_seq(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
-                                                      L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), L.gps_array([g.desc() for g in f.f.fs]),
+                                                      L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
                                                       None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
                                                       L.Arr(gH, True).ptr, gg))
             return {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
                     "sigma2_train": _train_noise_grad(gb, s2b),
                     "H": gH.reshape(m, p).T.copy(),
-                    "gps": [{"variance": gg[l].variance, "lengthscale": gg[l].lengthscale, "mean": gg[l].mean} for l in range(m)]}
+                    "gps": _gps_grads(gg, ga, m, x.dim)}
         L.check(lib.lmm_ilmm_logpdf_grad(x.carr().ptr, x.dim, n, L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2),
-                                         L.gps_array([g.desc() for g in f.f.fs]), None, C.byref(val), L.Arr(gy, True).ptr,
+                                         ga, None, C.byref(val), L.Arr(gy, True).ptr,
                                          C.byref(gs2), L.Arr(gH, True).ptr, gg))
         return {"value": val.value, "y": gy, "sigma2": gs2.value, "H": gH.reshape(m, p).T.copy(),
-                "gps": [{"variance": gg[l].variance, "lengthscale": gg[l].lengthscale, "mean": gg[l].mean} for l in range(m)]}
+                "gps": _gps_grads(gg, ga, m, x.dim)}
     if mogp:                      # gradient(logpdf, fx, y) on an IndependentMOGP (reference test/independent_mogp.jl:65-66):
         m = p = len(f.fs)         # the OILMM with U = I, S = 1 (regulariser identically 0, so it is skipped)
         if x.out_dim != m:
@@ -531,23 +556,23 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True) -> dict:
     n = x.n
     val, gs2 = C.c_double(), C.c_double()
     gy, gS, gU = _alloc_like(y if L._is_torch(y) else x.x, n * p), np.empty(m), np.empty(p * m)
-    gg = (L.GpGradT * m)()
+    gg, ga = (L.GpGradT * m)(), L.gps_array(descs)
     out = {}
     if post is None:
         L.check(lib.lmm_oilmm_logpdf_grad(x.carr().ptr, x.dim, n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(s2),
-                                          L.gps_array(descs), shard[0], shard[1], int(with_regulariser), C.byref(val),
+                                          ga, shard[0], shard[1], int(with_regulariser), C.byref(val),
                                           L.Arr(gy, True).ptr, C.byref(gs2), L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg))
     else:
         x0, s2b, y0, sizes = _merged_train(post.train, p)
         bn, bs, gb = _batch_args(s2b, sizes)
         gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
         L.check(lib.lmm_oilmm_post_logpdf_grad_seq(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
-                                                   L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(s2), L.gps_array(descs), shard[0],
+                                                   L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(s2), ga, shard[0],
                                                    shard[1], int(with_regulariser), C.byref(val), L.Arr(gy0, True).ptr,
                                                    L.Arr(gy, True).ptr, gb, C.byref(gs2), L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg))
         out.update(y_train=_split_train_grad(gy0, sizes, p), sigma2_train=_train_noise_grad(gb, s2b))
     out.update({"value": val.value, "y": gy, "sigma2": gs2.value,
-                "gps": [{"variance": gg[l].variance, "lengthscale": gg[l].lengthscale, "mean": gg[l].mean} for l in range(m)]})
+                "gps": _gps_grads(gg, ga, m, x.dim)})
     if not mogp:
         out["S"], out["U"] = gS, gU.reshape(m, p).T.copy()
     return out
