@@ -69,14 +69,20 @@ typedef enum {
   LMM_ERR_RCCL = 7             /* a collective failed (lmm_last_error_string carries ncclGetErrorString)             */
 } lmm_status;
 
-typedef enum { LMM_KERNEL_SE = 0, LMM_KERNEL_MATERN32 = 1, LMM_KERNEL_MATERN52 = 2 } lmm_kernel_kind;
+/* kappa(r), r = |x - x'| / lengthscale:  SE v e^{-r^2/2};  Matern32 v (1 + sqrt3 r) e^{-sqrt3 r};  Matern52 v (1 + sqrt5 r + 5 r^2/3)
+ * e^{-sqrt5 r};  Matern12 (= KernelFunctions' ExponentialKernel) v e^{-r};  RQ (RationalQuadraticKernel) v (1 + r^2 / (2 alpha))^{-alpha},
+ * alpha from the latent's tag (lmm_kernel_tag_create below), 2 without one. */
+typedef enum {
+  LMM_KERNEL_SE = 0, LMM_KERNEL_MATERN32 = 1, LMM_KERNEL_MATERN52 = 2, LMM_KERNEL_MATERN12 = 3, LMM_KERNEL_RQ = 4
+} lmm_kernel_kind;
 
 /* One latent GP: GP(mean, variance * Kernel o ScaleTransform(1/lengthscale)).
  * kind = base | (tag << 8): the low byte is the lmm_kernel_kind; a non-zero tag (lmm_ard_create) gives the latent per-dimension
  * lengthscales (KernelFunctions' Kernel o ARDTransform(1 ./ l)): the effective lengthscale of input dimension k is then
- * lengthscale * ard[k], so `lengthscale` becomes a common multiplier.  A tag may be shared by several latents (tied parameters). */
+ * lengthscale * ard[k], so `lengthscale` becomes a common multiplier.  A tag may be shared by several latents (tied parameters).
+ * A tag may also (or instead) carry the shape alpha of an RQ latent (lmm_kernel_tag_create). */
 typedef struct {
-  int kind;            /* lmm_kernel_kind | (ARD tag << 8) */
+  int kind;            /* lmm_kernel_kind | (tag << 8) */
   double variance;
   double lengthscale;
   double mean;         /* ConstMean / ZeroMean */
@@ -102,14 +108,26 @@ typedef struct lmm_post lmm_post_t;   /* opaque posterior state (device resident
  *                    named the tag: summed over that call's latents carrying the tag, partial over its latent shard like grad_gps,
  *                    zeros if its grad_gps was NULL.  (grad_gps[l].lengthscale of such a latent is the derivative with respect to
  *                    the multiplier lengthscale.)
- * Validation in every entry point: the base kind must be 0..2 and the tag live (LMM_ERR_ARG otherwise); the tag's d must equal the
+ *   lmm_kernel_tag_create : the general form of lmm_ard_create.  d > 0 with ard != NULL: per-dimension factors as above; d = 0 with
+ *                    ard = NULL: none.  alpha > 0 and finite: the shape of an RQ latent; alpha = 0: none.  Anything else, or a tag
+ *                    with neither, is LMM_ERR_ARG.  lmm_ard_create(d, ard, tag) == lmm_kernel_tag_create(d, ard, 0, tag).
+ *   lmm_kernel_tag_alpha_grad : d logpdf / d alpha from the most recent gradient entry point that named the tag, with the semantics
+ *                    of lmm_ard_grad (summed over that call's RQ latents carrying the tag, partial over its shard, 0 if grad_gps
+ *                    was NULL).
+ * Validation in every entry point: the base kind must be 0..4 (LMM_ERR_UNSUPPORTED otherwise) and the tag live (LMM_ERR_ARG
+ * otherwise); a tag with an alpha on a latent whose base kind is not LMM_KERNEL_RQ is LMM_ERR_ARG; a tag with factors must have the
  * call's d (LMM_ERR_DIM, naming the latent).  With d == 1, or when all ard[k] are equal, the latent is folded into the isotropic
- * descriptor (lengthscale * ard[0]) before anything runs: its values are then exactly those of the isotropic latent.  The gradient
- * entry points serve d <= 32 for latents with d > 1 tags (LMM_ERR_UNSUPPORTED beyond). */
+ * descriptor (lengthscale * ard[0]) before anything runs: its values are then exactly those of the isotropic latent, and it keeps
+ * its alpha.  An RQ latent without a tag, or whose tag has no alpha, uses alpha = 2 (KernelFunctions' default) and reports no alpha
+ * gradient.  lmm_ard_destroy frees any tag; lmm_ard_grad on a tag without factors writes nothing.  The 4096-tag limit counts every
+ * tag.  Posterior handles keep their own copy of alpha, as of the lengthscales.  The gradient entry points serve d <= 32 for
+ * latents with d > 1 factors (LMM_ERR_UNSUPPORTED beyond). */
 #define LMM_KERNEL_BASE_MASK 0xff
 int lmm_ard_create(int d, const double* lengthscale, int* tag);
 int lmm_ard_destroy(int tag);
 int lmm_ard_grad(int tag, double* out);
+int lmm_kernel_tag_create(int d, const double* ard, double alpha, int* tag);
+int lmm_kernel_tag_alpha_grad(int tag, double* out);
 
 /* ---- lifetime -------------------------------------------------------------------------- */
 int lmm_init(int device);                 /* bind this process to HIP device `device`, create streams */

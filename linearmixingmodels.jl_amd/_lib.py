@@ -14,12 +14,12 @@ LIB_PATH = os.environ.get("LMM_HIP_LIB") or os.path.join(_HERE, "liblmm_hip.so")
 
 LMM_OK, LMM_ERR_DIM, LMM_ERR_NOT_ORTHOGONAL, LMM_ERR_NOT_PD, LMM_ERR_HIP, LMM_ERR_ARG, LMM_ERR_UNSUPPORTED, LMM_ERR_RCCL = range(8)
 UNIQUE_ID_BYTES = 128
-KERNEL_KINDS = {"se": 0, "matern32": 1, "matern52": 2}
+KERNEL_KINDS = {"se": 0, "matern32": 1, "matern52": 2, "matern12": 3, "rq": 4}
 
 # Every symbol include/lmm_hip.h declares (tests/test_abi.py checks the library exports each one).
 SYMBOLS = [
     "lmm_init", "lmm_shutdown", "lmm_last_error_string", "lmm_last_error_detail", "lmm_device_synchronize", "lmm_release_cached_memory",
-    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
+    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
     "lmm_comm_destroy",
     "lmm_set_strict_progress", "lmm_get_strict_progress", "lmm_dev_claim_scramble", "lmm_orthogonal_validate", "lmm_oilmm_logpdf", "lmm_oilmm_logpdf_grad", "lmm_oilmm_post_logpdf_grad", "lmm_oilmm_post_logpdf_grad_seq", "lmm_ilmm_logpdf_grad", "lmm_ilmm_post_logpdf_grad", "lmm_ilmm_post_logpdf_grad_seq", "lmm_ilmm_post_latent_logpdf_grad_seq", "lmm_oilmm_logpdf_multi", "lmm_reorder", "lmm_ilmm_logpdf", "lmm_ilmm_logpdf_ex", "lmm_ilmm_logpdf_multi", "lmm_mogp_logpdf", "lmm_mogp_logpdf_diag",
     "lmm_oilmm_posterior_create", "lmm_mogp_posterior_create", "lmm_post_condition", "lmm_ilmm_posterior_create", "lmm_post_destroy", "lmm_ilmm_post_latent_view", "lmm_ilmm_post_mean_and_var", "lmm_ilmm_post_mean_and_cov", "lmm_ilmm_post_condition", "lmm_ilmm_post_logpdf", "lmm_ilmm_post_rand",
@@ -309,19 +309,35 @@ KERNEL_BASE_MASK = 0xFF
 
 
 class ArdTags:
-    """Owner of the ARD tags (lmm_ard_create) of one lmm_gp_t array: destroyed with the array (gps_array attaches it as `.ard`).
-    tags[l] is latent l's tag, 0 for an isotropic latent."""
+    """Owner of the kernel tags (lmm_ard_create / lmm_kernel_tag_create) of one lmm_gp_t array: destroyed with the array (gps_array
+    attaches it as `.ard`).  tags[l] is latent l's tag, 0 for an isotropic latent without an RQ shape; has_ard[l] tells whether the
+    tag holds per-dimension factors, has_alpha[l] whether it holds an RQ shape."""
 
     def __init__(self, m: int):
         self.tags = [0] * m
+        self.has_ard = [False] * m
+        self.has_alpha = [False] * m
         self._lib = None
 
-    def create(self, l: int, ls: np.ndarray) -> int:
+    def create(self, l: int, ls: Optional[np.ndarray], alpha: Optional[float] = None) -> int:
+        """One tag for latent l: the factors `ls` (None: none) and / or the RQ shape `alpha` (None: none)."""
         self._lib = self._lib or load()
         t = C.c_int()
-        check(self._lib.lmm_ard_create(int(ls.size), ls.ctypes.data_as(C.POINTER(C.c_double)), C.byref(t)))
+        if alpha is None:
+            check(self._lib.lmm_ard_create(int(ls.size), ls.ctypes.data_as(C.POINTER(C.c_double)), C.byref(t)))
+        else:
+            d, p = (0, None) if ls is None else (int(ls.size), ls.ctypes.data_as(C.POINTER(C.c_double)))
+            check(self._lib.lmm_kernel_tag_create(d, p, C.c_double(alpha), C.byref(t)))
         self.tags[l] = t.value
+        self.has_ard[l] = ls is not None
+        self.has_alpha[l] = alpha is not None
         return t.value
+
+    def alpha_grad(self, l: int) -> float:
+        """d logpdf / d alpha of latent l's tag after a gradient call."""
+        out = C.c_double(0.0)
+        check(self._lib.lmm_kernel_tag_alpha_grad(self.tags[l], C.byref(out)))
+        return out.value
 
     def grad(self, l: int, d: int) -> np.ndarray:
         """d logpdf / d ard of latent l's tag after a gradient call (its own tag: d / d lengthscale_k, the multiplier being 1)."""
@@ -335,6 +351,8 @@ class ArdTags:
                 if t:
                     self._lib.lmm_ard_destroy(t)
         self.tags = [0] * len(self.tags)
+        self.has_ard = [False] * len(self.tags)
+        self.has_alpha = [False] * len(self.tags)
 
     def __del__(self):
         try:
@@ -345,7 +363,8 @@ class ArdTags:
 
 def gps_array(gps: Sequence[dict]):
     """lmm_gp_t array of latent descriptors.  A vector "lengthscale" (length d) becomes an ARD latent: a tag holding the vector, kind
-    = base | tag << 8 and lengthscale (the common multiplier) 1.  The tags live as long as the returned array (its `.ard`)."""
+    = base | tag << 8 and lengthscale (the common multiplier) 1.  An "rq" latent's "alpha" (default 2.0) goes into its tag too (one
+    tag holds both).  The tags live as long as the returned array (its `.ard`)."""
     arr = (GpT * max(len(gps), 1))()
     arr.ard = ArdTags(len(gps))
     for l, g in enumerate(gps):
@@ -353,11 +372,15 @@ def gps_array(gps: Sequence[dict]):
         a.kind = KERNEL_KINDS[g["kind"]]
         a.variance = float(g.get("variance", 1.0))
         ls = g.get("lengthscale", 1.0)
+        alpha = float(g.get("alpha", 2.0)) if g["kind"] == "rq" else None
+        vec = None
         if np.ndim(ls) == 0:
             a.lengthscale = float(ls)
         else:
-            a.kind |= arr.ard.create(l, np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)) << 8
+            vec = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
             a.lengthscale = 1.0
+        if vec is not None or alpha is not None:
+            a.kind |= arr.ard.create(l, vec, alpha) << 8
         a.mean = float(g.get("mean", 0.0))
     return arr
 

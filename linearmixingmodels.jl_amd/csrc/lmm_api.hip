@@ -294,55 +294,66 @@ struct Dims {
 // its own mutex and never takes the context lock for longer than a try-lock on an error message.  An entry point RESOLVES the tags of
 // its latents once (resolve_gps, under the context lock): a latent whose factors are all equal (or d == 1) is folded into the
 // isotropic descriptor; every other ARD latent gets its effective inverse lengthscales 1 / (lengthscale * ard[k]) uploaded to the
-// device, and its kind word is rewritten to  base | (slot + 1) << 8  with `slot` an index of g_ils_slot, the table of the device
-// vectors that live calls and posterior handles hold.  Everything downstream reads the base kind (kind & 0xff) and the vector through
-// ils_of(); the slot table is process state guarded by the context lock like the rest of the context.
+// device, and its kind word is rewritten to  base | (slot + 1) << 8  with `slot` an index of g_slot, the table of the device
+// vectors (and RQ shapes) that live calls and posterior handles hold.  Everything downstream reads the base kind (kind & 0xff), the
+// vector through ils_of() and the RQ shape through alpha_of(); the slot table is process state guarded by the context lock like the
+// rest of the context.  A tag may carry an RQ shape alpha instead of, or besides, factors (lmm_kernel_tag_create): an RQ latent
+// naming it gets a slot holding its alpha (ils nullptr when it has no factors or was folded).
 #define LMM_ARD_MAX_TAGS 4096
-struct ArdTag { int d; std::vector<double> ard, grad; };
+struct ArdTag { int d; std::vector<double> ard, grad; double alpha = 0.0, galpha = 0.0; };   // d = 0: no factors; alpha = 0: no shape
 std::mutex g_ard_mu;
 std::map<int, ArdTag> g_ard_tags;
 int g_ard_next = 1;
 
-std::vector<const double*> g_ils_slot;
-std::vector<int> g_ils_free;
+#define LMM_RQ_DEFAULT_ALPHA 2.0          // KernelFunctions' RationalQuadraticKernel(; alpha = 2.0)
+struct KernelSlot { const double* ils; double alpha; };
+std::vector<KernelSlot> g_slot;
+std::vector<int> g_slot_free;
 
 // The resolved ARD state of one call, shared with the posterior handles it builds (and their conditioned successors and views).
 struct ArdSet {
   int d = 0;
   std::vector<double> host;                 // effective inverse lengthscales, d per entry
   Buf<double> dev;                          // the same on the device
-  std::vector<int> slots;                   // g_ils_slot entries this set holds
-  // per latent of the call: user tag (0: none), the caller's lengthscale (the common multiplier), the factor a folded latent's
-  // lengthscale was multiplied by (1 otherwise), and the vector the gradient reduction uses (nullptr: the isotropic reduction)
+  std::vector<int> slots;                   // g_slot entries this set holds
+  // per latent of the call: user tag (0: none), whether the tag has factors, the caller's lengthscale (the common multiplier), the
+  // factor a folded latent's lengthscale was multiplied by (1 otherwise), the vector the gradient reduction uses (nullptr: the
+  // isotropic reduction), and the RQ shape taken from the tag (0: none; the latent then reports no alpha gradient)
   std::vector<int> tag;
-  std::vector<double> mult, fold;
+  std::vector<char> has_ard;
+  std::vector<double> mult, fold, alpha;
   std::vector<const double*> gils;
   ArdSet() = default;
   ArdSet(const ArdSet&) = delete;
   ArdSet& operator=(const ArdSet&) = delete;
-  ~ArdSet() { for (int sl : slots) { g_ils_slot[sl] = nullptr; g_ils_free.push_back(sl); } }
+  ~ArdSet() { for (int sl : slots) { g_slot[sl] = KernelSlot{nullptr, 0.0}; g_slot_free.push_back(sl); } }
 };
 // The ArdSet of the entry point that is running (set by resolve_gps, cleared when the call returns): read by the gradient cores.
 const ArdSet* g_call_ard = nullptr;
 
 inline int base_kind(const lmm_gp_t& gp) { return gp.kind & LMM_KERNEL_BASE_MASK; }
-inline const double* ils_of(const lmm_gp_t& gp) { const int sl = gp.kind >> 8; return sl > 0 ? g_ils_slot[sl - 1] : nullptr; }
+inline const double* ils_of(const lmm_gp_t& gp) { const int sl = gp.kind >> 8; return sl > 0 ? g_slot[sl - 1].ils : nullptr; }
+inline double alpha_of(const lmm_gp_t& gp) {
+  const int sl = gp.kind >> 8;
+  return (sl > 0 && g_slot[sl - 1].alpha > 0.0) ? g_slot[sl - 1].alpha : LMM_RQ_DEFAULT_ALPHA;
+}
 
 LatentDev to_dev(const lmm_gp_t& gp) {
   LatentDev d;
   d.kind = base_kind(gp); d.var = gp.variance; d.inv_ls = 1.0 / gp.lengthscale; d.mean = gp.mean; d.ils = ils_of(gp);
+  d.alpha = alpha_of(gp);
   return d;
 }
 // kernel fields of a Gram assembly from a (resolved) latent descriptor
 void set_kernel(GramArgs& a, const lmm_gp_t& gp) {
-  a.kind = base_kind(gp); a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale; a.ils = ils_of(gp);
+  a.kind = base_kind(gp); a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale; a.ils = ils_of(gp); a.alpha = alpha_of(gp);
 }
 
 int check_gps(const lmm_gp_t* gps, int m) {
   if (!gps) return fail(LMM_ERR_ARG, "gps is NULL");
   for (int l = 0; l < m; ++l) {
     const int base = gps[l].kind & LMM_KERNEL_BASE_MASK;
-    if (gps[l].kind < 0 || base > 2) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
+    if (gps[l].kind < 0 || base > LMM_KERNEL_RQ) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
     if (!(gps[l].variance > 0.0) || !(gps[l].lengthscale > 0.0)) return fail(LMM_ERR_ARG, "latent %d: variance and lengthscale must be > 0", l);
   }
   return LMM_OK;
@@ -365,7 +376,8 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
   if (!any) return LMM_OK;
   auto A = std::make_shared<ArdSet>();
   A->d = d;
-  A->tag.assign(m, 0); A->mult.assign(m, 1.0); A->fold.assign(m, 1.0); A->gils.assign(m, nullptr);
+  A->tag.assign(m, 0); A->has_ard.assign(m, 0); A->mult.assign(m, 1.0); A->fold.assign(m, 1.0); A->alpha.assign(m, 0.0);
+  A->gils.assign(m, nullptr);
   out.v.assign(gps, gps + m);
   std::map<std::pair<int, double>, int> entry_of;     // (tag, multiplier) -> entry: latents sharing both share the vector (and kind word)
   std::vector<int> ent(m, -1);
@@ -374,19 +386,25 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
     const int tag = gps[l].kind >> 8;
     if (tag == 0) continue;
     std::vector<double> ard;
+    double alpha;
     {
       std::lock_guard<std::mutex> lk(g_ard_mu);
       auto it = g_ard_tags.find(tag);
       if (it == g_ard_tags.end()) return fail(LMM_ERR_ARG, "latent %d: unknown or destroyed ARD tag %d", l, tag);
-      if (it->second.d != d)
+      if (it->second.d != 0 && it->second.d != d)
         return fail(LMM_ERR_DIM, "latent %d: ARD tag %d has %d dimensions, the inputs have %d", l, tag, it->second.d, d);
       ard = it->second.ard;
+      alpha = it->second.alpha;
     }
+    if (alpha > 0.0 && base_kind(gps[l]) != LMM_KERNEL_RQ)
+      return fail(LMM_ERR_ARG, "latent %d: tag %d carries an RQ shape but the kernel kind is %d", l, tag, base_kind(gps[l]));
     const double ls = gps[l].lengthscale;
-    A->tag[l] = tag; A->mult[l] = ls;
+    A->tag[l] = tag; A->mult[l] = ls; A->alpha[l] = alpha;
+    out.v[l].kind = base_kind(gps[l]);
+    if (ard.empty()) continue;         // an RQ shape alone: isotropic, its slot is assigned below
+    A->has_ard[l] = 1;
     bool equal = true;
     for (int k = 1; k < d; ++k) equal = equal && ard[k] == ard[0];
-    out.v[l].kind = base_kind(gps[l]);
     if (equal) {                       // folded: exactly the isotropic latent of lengthscale ls * ard[0]
       folded[l] = 1;
       A->fold[l] = ard[0];
@@ -406,25 +424,33 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
     A->dev = Buf<double>(A->host.size());
     // (A->host lives as long as the set, so the copy may complete asynchronously; every launch that reads it is ordered behind st0)
     HIPCHK(hipMemcpyAsync(A->dev.p, A->host.data(), A->host.size() * sizeof(double), hipMemcpyHostToDevice, g.streams[0]));
-    for (int e = 0; e < ne; ++e) {
+    for (int l = 0; l < m; ++l)
+      if (ent[l] >= 0) A->gils[l] = A->dev.p + (size_t)ent[l] * d;
+  }
+  // Slots: one per (tag, multiplier) among the latents that need one (a per-dimension vector, or an RQ shape); latents sharing both
+  // share the slot and so the kind word.
+  std::map<std::pair<int, double>, int> slot_of;
+  for (int l = 0; l < m; ++l) {
+    const bool vec = ent[l] >= 0 && !folded[l];
+    if (!vec && !(A->alpha[l] > 0.0)) continue;
+    auto key = std::make_pair(A->tag[l], A->mult[l]);
+    auto it = slot_of.find(key);
+    if (it == slot_of.end()) {
       int sl;
-      if (!g_ils_free.empty()) { sl = g_ils_free.back(); g_ils_free.pop_back(); }
-      else { sl = (int)g_ils_slot.size(); g_ils_slot.push_back(nullptr); }
-      g_ils_slot[sl] = A->dev.p + (size_t)e * d;
+      if (!g_slot_free.empty()) { sl = g_slot_free.back(); g_slot_free.pop_back(); }
+      else { sl = (int)g_slot.size(); g_slot.push_back(KernelSlot{nullptr, 0.0}); }
+      g_slot[sl] = KernelSlot{vec ? A->gils[l] : nullptr, A->alpha[l]};
       A->slots.push_back(sl);
+      it = slot_of.emplace(key, sl).first;
     }
-    for (int l = 0; l < m; ++l) {
-      if (ent[l] < 0) continue;
-      A->gils[l] = A->dev.p + (size_t)ent[l] * d;
-      if (!folded[l]) out.v[l].kind = base_kind(gps[l]) | ((A->slots[ent[l]] + 1) << 8);
-    }
+    out.v[l].kind = base_kind(gps[l]) | ((it->second + 1) << 8);
   }
   out.ard = A;
   g_call_ard = A.get();
   return LMM_OK;
 }
 // Invariant: resolve_gps reads the high 24 bits of `kind` as a USER tag, so it is only ever given a caller's array.  A resolved array
-// (cg_.v, lmm_post.gps) carries slot indices of g_ils_slot there instead and must never be resolved again: internal code passes it
+// (cg_.v, lmm_post.gps) carries slot indices of g_slot there instead and must never be resolved again: internal code passes it
 // straight to the launch helpers (to_dev / set_kernel / ils_of), which read the slot.
 #define RESOLVE_GPS(gps, m, d)                                  \
   CallGps cg_;                                                  \
@@ -455,27 +481,30 @@ LatentDev grad_dev(const lmm_gp_t& gp, int l) {
 // Writes d/d multiplier into *dl and d/d l_k into gard[0..d).
 void ard_grad_finish(int l, int d, const double* red, const double* ard, double* dl, double* gard) {
   *dl = red[0];
-  if (!g_call_ard || g_call_ard->tag[l] == 0) return;
+  if (!g_call_ard || !g_call_ard->has_ard[l]) return;
   if (g_call_ard->gils[l]) { for (int k = 0; k < d; ++k) gard[k] = ard[k]; return; }
   gard[0] = red[0];                           // d == 1, folded: red[0] = d/d l_eff, l_eff = multiplier * fold
   *dl = red[0] * g_call_ard->fold[l];
 }
 // Publishes the call's per-dimension gradients to the registry: every tag the call named gets d/d ard[k] = multiplier * d/d l_k summed
-// over the call's latents [l0, l1) carrying it; gard == nullptr (grad_gps NULL): zeros.
-void ard_publish(const std::vector<double>* gard, int l0, int l1) {
+// over the call's latents [l0, l1) carrying it, and a tag with an RQ shape gets d/d alpha summed over those latents (galpha: one per
+// latent); gard == nullptr (grad_gps NULL): zeros.
+void ard_publish(const std::vector<double>* gard, const std::vector<double>* galpha, int l0, int l1) {
   if (!g_call_ard) return;
   const ArdSet& A = *g_call_ard;
   const int d = A.d, m = (int)A.tag.size();
   std::lock_guard<std::mutex> lk(g_ard_mu);
   for (int l = 0; l < m; ++l) {
     auto it = g_ard_tags.find(A.tag[l]);
-    if (A.tag[l] != 0 && it != g_ard_tags.end()) it->second.grad.assign(d, 0.0);
+    if (A.tag[l] != 0 && it != g_ard_tags.end()) { it->second.grad.assign(it->second.d, 0.0); it->second.galpha = 0.0; }
   }
   if (!gard) return;
   for (int l = l0; l < l1; ++l) {
     auto it = g_ard_tags.find(A.tag[l]);
     if (A.tag[l] == 0 || it == g_ard_tags.end()) continue;
-    for (int k = 0; k < d; ++k) it->second.grad[k] += A.mult[l] * (*gard)[(size_t)l * d + k];
+    if (A.has_ard[l])
+      for (int k = 0; k < d; ++k) it->second.grad[k] += A.mult[l] * (*gard)[(size_t)l * d + k];
+    if (A.alpha[l] > 0.0) it->second.galpha += (*galpha)[l];
   }
 }
 
@@ -1189,18 +1218,42 @@ static int ard_fail(int code, const char* msg) {
   return code;
 }
 
-int lmm_ard_create(int d, const double* lengthscale, int* tag) {
-  if (d <= 0 || !lengthscale || !tag) return ard_fail(LMM_ERR_ARG, "lmm_ard_create: bad arguments");
-  for (int k = 0; k < d; ++k)
-    if (!(lengthscale[k] > 0.0) || !std::isfinite(lengthscale[k])) return ard_fail(LMM_ERR_ARG, "lmm_ard_create: lengthscales must be finite and > 0");
+// Registers a validated tag (d = 0, ard unused: no factors; alpha = 0: no RQ shape).
+static int tag_register(int d, const double* ard, double alpha, int* tag, const char* full_msg) {
   std::lock_guard<std::mutex> lk(g_ard_mu);
-  if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_ard_create: too many live ARD tags");
+  if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, full_msg);
   while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;     // tag << 8 stays a positive int
   const int t = g_ard_next;
   g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
   ArdTag& a = g_ard_tags[t];
-  a.d = d; a.ard.assign(lengthscale, lengthscale + d); a.grad.assign(d, 0.0);
+  a.d = d; a.ard.assign(ard, ard + d); a.grad.assign(d, 0.0); a.alpha = alpha;
   *tag = t;
+  return LMM_OK;
+}
+
+int lmm_ard_create(int d, const double* lengthscale, int* tag) {
+  if (d <= 0 || !lengthscale || !tag) return ard_fail(LMM_ERR_ARG, "lmm_ard_create: bad arguments");
+  for (int k = 0; k < d; ++k)
+    if (!(lengthscale[k] > 0.0) || !std::isfinite(lengthscale[k])) return ard_fail(LMM_ERR_ARG, "lmm_ard_create: lengthscales must be finite and > 0");
+  return tag_register(d, lengthscale, 0.0, tag, "lmm_ard_create: too many live ARD tags");
+}
+
+int lmm_kernel_tag_create(int d, const double* ard, double alpha, int* tag) {
+  if (d < 0 || !tag || (d == 0) != (ard == nullptr)) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create: bad arguments");
+  if (!(alpha == 0.0 || (alpha > 0.0 && std::isfinite(alpha))))
+    return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create: alpha must be 0 (none) or finite and > 0");
+  if (d == 0 && alpha == 0.0) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create: a tag needs factors or an alpha");
+  for (int k = 0; k < d; ++k)
+    if (!(ard[k] > 0.0) || !std::isfinite(ard[k])) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create: factors must be finite and > 0");
+  return tag_register(d, ard, alpha, tag, "lmm_kernel_tag_create: too many live tags");
+}
+
+int lmm_kernel_tag_alpha_grad(int tag, double* out) {
+  if (!out) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_alpha_grad: out is NULL");
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  auto it = g_ard_tags.find(tag);
+  if (it == g_ard_tags.end()) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_alpha_grad: unknown tag");
+  *out = it->second.galpha;
   return LMM_OK;
 }
 
@@ -1485,6 +1538,7 @@ struct OilmmGrad {          // host results of oilmm_grad_core (partial sums ove
   std::vector<double> gS, gU;
   std::vector<lmm_gp_grad_t> ggps;
   std::vector<double> gard;   // m x d: d logpdf / d l_k of the ARD latents (ard_grad_finish), zeros elsewhere
+  std::vector<double> galpha; // m: d logpdf / d alpha of the RQ latents, zeros elsewhere
 };
 
 // Value and gradient of the OILMM logpdf (reference src/oilmm.jl:79-113 differentiated) over N points in NB.nblk consecutive
@@ -1612,10 +1666,12 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
   G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
   G.gard.assign((size_t)m * d, 0.0);
+  G.galpha.assign(m, 0.0);
   for (int k = 0; k < ms; ++k) {
     const int l = l0 + k;
     total += lml[k];
     const double* r = &hred[(size_t)NGR * k];
+    G.galpha[l] = r[8];
     double cl;
     ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * k], &cl, &G.gard[(size_t)l * d]);
     const double ad = r[3], sa = r[4], v = gps[l].variance;
@@ -1732,7 +1788,7 @@ int lmm_oilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p,
                                G, gy.p))
     return rc;
   write_oilmm_grad(G, m, p, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
-  ard_publish(grad_gps ? &G.gard : nullptr, latent_begin, latent_end);
+  ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, latent_begin, latent_end);
   if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
   return LMM_OK;
   LMM_CATCH
@@ -1792,7 +1848,8 @@ int lmm_oilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* bat
   }
   if (grad_U) for (size_t q = 0; q < (size_t)p * m; ++q) grad_U[q] = GJ.gU[q] - GM.gU[q];
   for (size_t q = 0; q < GJ.gard.size(); ++q) GJ.gard[q] -= GM.gard[q];
-  ard_publish(grad_gps ? &GJ.gard : nullptr, latent_begin, latent_end);
+  for (size_t q = 0; q < GJ.galpha.size(); ++q) GJ.galpha[q] -= GM.galpha[q];
+  ard_publish(grad_gps ? &GJ.gard : nullptr, &GJ.galpha, latent_begin, latent_end);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);
@@ -1968,7 +2025,8 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   };
   bool identical = allow_decoupled != 0;
   for (int l = 1; l < m && identical; ++l)
-    identical = gps[l].kind == gps[0].kind && gps[l].variance == gps[0].variance && gps[l].lengthscale == gps[0].lengthscale;
+    identical = base_kind(gps[l]) == base_kind(gps[0]) && ils_of(gps[l]) == ils_of(gps[0]) && alpha_of(gps[l]) == alpha_of(gps[0]) &&
+                gps[l].variance == gps[0].variance && gps[l].lengthscale == gps[0].lengthscale;   // two tags with one alpha: one kernel
   if (path_used) *path_used = identical ? 1 : 0;
   if (identical) {
     // Decoupled shortcut: with one shared latent kernel the covariance is I (x) K + SigmaT (x) I;
@@ -2093,6 +2151,7 @@ struct IlmmGrad {            // host results of ilmm_grad_core
   std::vector<double> gH;    // p x m
   std::vector<lmm_gp_grad_t> ggps;
   std::vector<double> gard;  // m x d: d logpdf / d l_k of the ARD latents (ard_grad_finish), zeros elsewhere
+  std::vector<double> galpha;  // m: d logpdf / d alpha of the RQ latents, zeros elsewhere
 };
 
 // Value and gradient of the dense-H ILMM prior logpdf over n points in NB.nblk consecutive blocks, block b carrying observation
@@ -2217,8 +2276,10 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   // ---- kernel-parameter gradients: 1/2 tr((aa' - Sigma^-1) dSigma/dtheta_l), dSigma = E_ll (x) dK_l ----
   G.ggps.assign(m, lmm_gp_grad_t{});
   G.gard.assign((size_t)m * d, 0.0);
+  G.galpha.assign(m, 0.0);
   for (int l = 0; l < m; ++l) {
     const double* r = &hred[(size_t)NGR * l];
+    G.galpha[l] = r[8];
     ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * l], &G.ggps[l].lengthscale, &G.gard[(size_t)l * d]);
     G.ggps[l].variance = (r[7] + 0.5 * gps[l].variance * (r[2] - r[1])) / gps[l].variance;     // K_ii = variance
     G.ggps[l].mean = r[4];
@@ -2343,7 +2404,7 @@ int lmm_ilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p, 
   if (int rc = ard_grad_check(d)) return rc;
   IlmmGrad G;
   if (int rc = ilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, H, m, gps, jit, G, gy.p)) return rc;
-  ard_publish(grad_gps ? &G.gard : nullptr, 0, m);
+  ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, 0, m);
   *out_logpdf = G.value;
   if (grad_sigma2) *grad_sigma2 = G.gs2[0];
   if (grad_H) std::copy(G.gH.begin(), G.gH.end(), grad_H);
@@ -2410,7 +2471,8 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
       grad_gps[l].mean = GJ.ggps[l].mean - GM.ggps[l].mean;
     }
   for (size_t q = 0; q < GJ.gard.size(); ++q) GJ.gard[q] -= GM.gard[q];
-  ard_publish(grad_gps ? &GJ.gard : nullptr, 0, m);
+  for (size_t q = 0; q < GJ.galpha.size(); ++q) GJ.galpha[q] -= GM.galpha[q];
+  ard_publish(grad_gps ? &GJ.gard : nullptr, &GJ.galpha, 0, m);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);

@@ -10,10 +10,12 @@ struct BatchInfo { int* p[LMM_MAX_BATCH]; };
 
 // kind: the BASE kernel kind (lmm_kernel_kind); ils: nullptr (isotropic, inv_ls) or the latent's d per-dimension inverse lengthscales
 // (device; an ARD latent, d > 1).  An ARD latent keeps inv_ls = 1 / its common multiplier (the gradient reduction's d/d multiplier).
+// alpha: the RQ shape (unused by the other kinds).
 struct LatentDev {
   int kind;
   double var, inv_ls, mean;
   const double* ils;
+  double alpha;
 };
 
 // Gram / factor-matrix assembly arguments (see gram_kernel).
@@ -32,6 +34,7 @@ struct GramArgs {
   const double* xs; int ns;                    // rows ncols + r  <- kappa(xs_r, x_j)
   int* info_zero;                              // optional: the matrix's pivot-info word, zeroed by the launch (saves a memset per call)
   int cpw;                                     // column tiles per workgroup (set by the launcher: 4, or 1 when the grid would be small)
+  double alpha;                                // RQ shape (unused by the other kinds)
 };
 
 // The same assembly for up to LMM_MAX_BATCH same-shaped matrices in ONE launch (blockIdx.z = matrix): everything in `base`
@@ -45,6 +48,7 @@ struct GramBatchArgs {
   const double* rider[LMM_MAX_BATCH];
   double rider_sub[LMM_MAX_BATCH];
   int* info_zero[LMM_MAX_BATCH];
+  double alpha[LMM_MAX_BATCH];
 };
 
 struct DenseArgs {
@@ -57,7 +61,7 @@ struct DenseArgs {
 };
 
 void launch_gram(const GramArgs& a, hipStream_t st);
-// nb same-shaped assemblies (differing only in A, kind, var, inv_ls, ils, diag_add, diag_vec, rider): one launch per run of equal kinds
+// nb same-shaped assemblies (differing only in A, kind, var, inv_ls, ils, alpha, diag_add, diag_vec, rider): one launch per run of equal kinds
 void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st);
 void launch_dense_assemble(const DenseArgs& a, hipStream_t st);
 void launch_dense_cov(const double* S, int lds, int ns, int m, const double* Hm, int p, double jitter, double sigma2, double* T,
@@ -175,7 +179,7 @@ void launch_syrk_upper_set(double* C, int ldc, const double* X, int ldx, int N, 
 void launch_syrk_upper_set(const BatchPtr& C, int ldc, const BatchPtr& X, int ldx, int N, int nb, hipStream_t st);
 void launch_set_identity(double* R, int ld, int nc, hipStream_t st);
 int grad_partials(int n, int d_ard = 0);      // partial-buffer elements of launch_grad_reduce (d_ard: the d of an ARD latent, else 0)
-#define LMM_NGRAD 8
+#define LMM_NGRAD 9
 #define LMM_ARD_GRAD_DMAX 32                  // widest ARD latent the gradient reduction serves (per-dimension sums in registers)
 // g.ils != nullptr (an ARD latent, d <= LMM_ARD_GRAD_DMAX): out8[0] is d/d multiplier and out_ard[k] = d/d l_k (d values)
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,

@@ -108,6 +108,22 @@ __device__ __forceinline__ double kappa(int kind, double var, double r, double r
   return var * (1.0 + s + (5.0 / 3.0) * r2) * exp_nonpos(-s);
 }
 
+// log(1 + u) for u >= 0 (the RQ kernel): the device library's log1p, documented within 1 ulp in Float64 (no cancellation near u = 0,
+// unlike log(1 + u)).
+__device__ __forceinline__ double log1p_nonneg(double u) { return log1p(u); }
+
+// RationalQuadraticKernel: v (1 + u)^{-alpha}, u = r^2 / (2 alpha), evaluated as exp(-alpha log1p(u)).
+__device__ __forceinline__ double kappa_rq(double var, double r2, double alpha) {
+  return var * exp_nonpos(-alpha * log1p_nonneg(r2 * (0.5 / alpha)));
+}
+
+// All five kinds: Matern12 (KernelFunctions' ExponentialKernel) v e^{-r}, RQ with shape alpha, the others as kappa above.
+__device__ __forceinline__ double kappa(int kind, double var, double r, double r2, double alpha) {
+  if (kind == LMM_KERNEL_MATERN12) return var * exp_nonpos(-r);
+  if (kind == LMM_KERNEL_RQ) return kappa_rq(var, r2, alpha);
+  return kappa(kind, var, r, r2);
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -166,17 +182,19 @@ template <typename TS>
 __device__ __forceinline__ void gram_store(void* base, size_t idx, d2 v) { MatIO<TS>::st2(base, idx, v); }
 
 template <int KIND>
-__device__ __forceinline__ double kappa_t(double var, double r, double r2) {
+__device__ __forceinline__ double kappa_t(double var, double r, double r2, double alpha) {
   if (KIND == LMM_KERNEL_SE) return var * exp_nonpos(-0.5 * r2);
   if (KIND == LMM_KERNEL_MATERN32) {
     const double s = 1.7320508075688772 * r;
     return var * (1.0 + s) * exp_nonpos(-s);
   }
+  if (KIND == LMM_KERNEL_MATERN12) return var * exp_nonpos(-r);
+  if (KIND == LMM_KERNEL_RQ) return kappa_rq(var, r2, alpha);
   const double s = 2.23606797749979 * r;
   return var * __builtin_fma(5.0 / 3.0, r2, 1.0 + s) * exp_nonpos(-s);
 }
 
-template <typename TS>
+template <int KIND, typename TS>      // the three original kinds evaluate kappa on a.kind at run time, as they always have
 __device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int tj) {
   const int t = threadIdx.x;
   const int i0 = ti * 64 + 2 * (t & 31);
@@ -216,7 +234,8 @@ __device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int
           double r, r2;
           if (a.d == 1) { r = fabs(rx[e] - xj) * a.inv_ls; r2 = r * r; }
           else { r2 = scaled_dist2(rpt[e], a.x + (size_t)j * a.d, a.d, a.inv_ls, a.ils); r = sqrt(r2); }
-          val = kappa(a.kind, a.var, r, r2);
+          if (KIND <= LMM_KERNEL_MATERN52) val = kappa(a.kind, a.var, r, r2);
+          else val = kappa_t<KIND>(a.var, r, r2, a.alpha);
           if (rtype[e] == 0 && i0 + e == j) val += a.diag_add + (a.diag_vec ? a.diag_vec[j] : 0.0);
         } else if (rtype[e] == 2) {
           val = rpt[e][j] - a.rider_sub;
@@ -258,7 +277,8 @@ __device__ __forceinline__ double exp_any(double x) {
 // with per-strip reference points c (rows: c_r, each column tile: c_c, and the scalar exp(+-a (c_r - c_c)) folded into the
 // column factors), so the per-element cost drops from a full exp (~20 f64 ops) to 2 multiplies and a min; the 4 row and
 // 2 x 64 column exponentials are amortised over 64 elements per thread.  Guard: |a (x - c)| <= 40 inside the strip (else
-// the direct per-element exp is used, e.g. for unsorted inputs).  Relative error of the product form <= ~1e-14.
+// the direct per-element exp is used, e.g. for unsorted inputs).  Relative error of the product form <= ~1e-14.  Matern12 takes the
+// same path with a = 1 / lengthscale and polynomial factor 1; RQ, like SE, is not separable and evaluates every element.
 template <int KIND, bool ND, typename TS>      // ND: the 1 < d <= 8 fast path is compiled in (kept out of the d == 1 kernel's register budget)
 __device__ __forceinline__ void gram_body(const GramArgs& a) {
   constexpr int DMAX = 8;                                     // input dimensions with a fast path (d > DMAX: generic tiles)
@@ -285,8 +305,8 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
       xr1[k] = (k < a.d) ? rsrc[(size_t)(i0 + 1 - rbase) * a.d + k] * sk : 0.0;
     }
   }
-  constexpr bool SEP = (KIND != LMM_KERNEL_SE);
-  const double aS = (KIND == LMM_KERNEL_MATERN32 ? 1.7320508075688772 : 2.23606797749979) * a.inv_ls;
+  constexpr bool SEP = (KIND != LMM_KERNEL_SE && KIND != LMM_KERNEL_RQ);
+  const double aS = KIND == LMM_KERNEL_MATERN12 ? a.inv_ls : (KIND == LMM_KERNEL_MATERN32 ? 1.7320508075688772 : 2.23606797749979) * a.inv_ls;
   double x0 = 0.0, x1 = 0.0, cr = 0.0, E0 = 0.0, F0 = 0.0, E1 = 0.0, F1 = 0.0;
   bool rows_ok = false;
   if (rows_interior) {
@@ -322,8 +342,9 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
           }
         }
         d2 v;
-        v.x = kappa_t<KIND>(a.var, KIND == LMM_KERNEL_SE ? 0.0 : sqrt_dist(s0), s0);
-        v.y = kappa_t<KIND>(a.var, KIND == LMM_KERNEL_SE ? 0.0 : sqrt_dist(s1), s1);
+        constexpr bool NOR = (KIND == LMM_KERNEL_SE || KIND == LMM_KERNEL_RQ);     // functions of r^2 alone
+        v.x = kappa_t<KIND>(a.var, NOR ? 0.0 : sqrt_dist(s0), s0, a.alpha);
+        v.y = kappa_t<KIND>(a.var, NOR ? 0.0 : sqrt_dist(s1), s1, a.alpha);
         if (ti == tj) {
           const int j = tj * 64 + jl;
           const double da = a.diag_add + (a.diag_vec ? a.diag_vec[j] : 0.0);
@@ -335,7 +356,7 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
       continue;
     }
     const bool interior = rows_interior && cols_in;
-    if (!interior) { gram_tile_generic<TS>(a, ti, tj); continue; }
+    if (!interior) { gram_tile_generic<KIND, TS>(a, ti, tj); continue; }
     bool sep = false;
     if (SEP) {
       __syncthreads();                                      // previous tile's readers are done with colE/colF/colX
@@ -362,7 +383,8 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
         const double s0 = aS * fabs(x0 - xj), s1 = aS * fabs(x1 - xj);
         const double e0 = fmin(E0 * cF, F0 * cE), e1 = fmin(E1 * cF, F1 * cE);
         d2 v;
-        if (KIND == LMM_KERNEL_MATERN32) { v.x = a.var * (1.0 + s0) * e0; v.y = a.var * (1.0 + s1) * e1; }
+        if (KIND == LMM_KERNEL_MATERN12) { v.x = a.var * e0; v.y = a.var * e1; }
+        else if (KIND == LMM_KERNEL_MATERN32) { v.x = a.var * (1.0 + s0) * e0; v.y = a.var * (1.0 + s1) * e1; }
         else {
           v.x = a.var * __builtin_fma(s0 * s0, 1.0 / 3.0, 1.0 + s0) * e0;
           v.y = a.var * __builtin_fma(s1 * s1, 1.0 / 3.0, 1.0 + s1) * e1;
@@ -382,8 +404,8 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
         const double xj = xc[8 * q];
         const double r0 = fabs(x0 - xj) * a.inv_ls, r1 = fabs(x1 - xj) * a.inv_ls;
         d2 v;
-        v.x = kappa_t<KIND>(a.var, r0, r0 * r0);
-        v.y = kappa_t<KIND>(a.var, r1, r1 * r1);
+        v.x = kappa_t<KIND>(a.var, r0, r0 * r0, a.alpha);
+        v.y = kappa_t<KIND>(a.var, r1, r1 * r1, a.alpha);
         if (ti == tj) {
           const int j = tj * 64 + cg + 8 * q;
           const double da = a.diag_add + (a.diag_vec ? a.diag_vec[j] : 0.0);
@@ -406,7 +428,7 @@ template <int KIND, bool ND, typename TS>
 __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
   GramArgs a = b.base;
   const int z = blockIdx.z;
-  a.A = b.A[z]; a.var = b.var[z]; a.inv_ls = b.inv_ls[z]; a.ils = b.ils[z]; a.diag_add = b.diag_add[z]; a.diag_vec = b.diag_vec[z]; a.rider = b.rider[z]; a.rider_sub = b.rider_sub[z];
+  a.A = b.A[z]; a.var = b.var[z]; a.inv_ls = b.inv_ls[z]; a.ils = b.ils[z]; a.alpha = b.alpha[z]; a.diag_add = b.diag_add[z]; a.diag_vec = b.diag_vec[z]; a.rider = b.rider[z]; a.rider_sub = b.rider_sub[z];
   if (b.info_zero[z] && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *b.info_zero[z] = 0;
   gram_body<KIND, ND, TS>(a);
 }
@@ -444,7 +466,7 @@ __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
             double r, r2;
             if (a.d == 1) { r = fabs(a.x[ii[e]] - a.x[jj]) * g.inv_ls; r2 = r * r; }
             else { r2 = scaled_dist2(a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d, g.inv_ls, g.ils); r = sqrt(r2); }
-            val = kappa(g.kind, g.var, r, r2);
+            val = kappa(g.kind, g.var, r, r2, g.alpha);
           }
           if (ii[e] == jj) val += a.sigmaT[(size_t)(a.sig_idx ? a.sig_idx[jj] : 0) * a.m * a.m + li[e] + lj * a.m];
         } else if (i >= a.ncols) {
@@ -478,7 +500,7 @@ __global__ __launch_bounds__(256) void dense_cross_kernel(void* __restrict__ R, 
       double rr, r2;
       if (d == 1) { rr = fabs(xs[s] - x[jj]) * g.inv_ls; r2 = rr * rr; }
       else { r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)jj * d, d, g.inv_ls, g.ils); rr = sqrt(r2); }
-      val = kappa(g.kind, g.var, rr, r2);
+      val = kappa(g.kind, g.var, rr, r2, g.alpha);
     }
   }
   MatIO<TS>::st1(R, (size_t)j * ldr + r, val);
@@ -3183,7 +3205,9 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restr
 // ---------------------------------------------------------------------------------------------------
 // Latent mean at xs from the weights:  mean[s] = mu + sum_i kappa(xs_s, x_i) alpha_i   (cross-Gram fused with the GEMV;
 // never materialised).  The i range is cut into chunks of ichunk (blockIdx.y) whose partial sums strip_finish_kernel adds.
+// EXT: a Matern12 / RQ latent (the three original kinds keep the instantiation they always had).
 // ---------------------------------------------------------------------------------------------------
+template <bool EXT>
 __global__ __launch_bounds__(256) void post_mean_kernel(const double* __restrict__ xs, int ns,
                                                         const double* __restrict__ x, int n, int d, int ichunk,
                                                         const double* __restrict__ alpha, LatentDev g,
@@ -3205,13 +3229,14 @@ __global__ __launch_bounds__(256) void post_mean_kernel(const double* __restrict
 #pragma unroll 4
       for (int k = 0; k < lim; ++k) {
         const double r = fabs(xv - xa[k]) * g.inv_ls;
-        acc = __builtin_fma(kappa(g.kind, g.var, r, r * r), xa[256 + k], acc);
+        acc = __builtin_fma(EXT ? kappa(g.kind, g.var, r, r * r, g.alpha) : kappa(g.kind, g.var, r, r * r), xa[256 + k], acc);
       }
     }
   } else if (s < ns) {
     for (int i = ibeg; i < iend; ++i) {
       const double r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)i * d, d, g.inv_ls, g.ils);
-      acc = __builtin_fma(kappa(g.kind, g.var, sqrt(r2), r2), alpha[i], acc);
+      const double rr = sqrt(r2);
+      acc = __builtin_fma(EXT ? kappa(g.kind, g.var, rr, r2, g.alpha) : kappa(g.kind, g.var, rr, r2), alpha[i], acc);
     }
   }
   partial[(size_t)blockIdx.y * ((size_t)gridDim.x * 256) + s] = acc;
@@ -3385,6 +3410,28 @@ __device__ __forceinline__ double dkappa_dell(int kind, double var, double inv_l
   const double s = 2.23606797749979 * r;
   return var * exp_nonpos(-s) * (s * s / 3.0) * (1.0 + s) * inv_ls;
 }
+// Matern12 (ext_pair below): v e^{-r} r / ell;  RQ: v (1 + u)^{-alpha-1} r2 / ell.
+
+// RQ at squared scaled distance r2, u = r2 / (2 alpha):  kap = v (1 + u)^{-alpha};  h = v (1 + u)^{-alpha-1} = kap / (1 + u), so that
+// d kap / d ell = h r2 / ell and d kap / d l_k = h t_k^2 / l_k;  d kap / d alpha = kap (u / (1 + u) - log1p(u)).
+__device__ __forceinline__ void rq_pair(double var, double alpha, double r2, double& kap, double& h, double& dal) {
+  const double u = r2 * (0.5 / alpha), lg = log1p_nonneg(u), q = 1.0 / (1.0 + u);
+  kap = var * exp_nonpos(-alpha * lg);
+  h = kap * q;
+  dal = kap * (u * q - lg);
+}
+// kappa, d kappa / d ell and (RQ) d kappa / d alpha of a Matern12 or RQ pair
+__device__ __forceinline__ void ext_pair(const LatentDev& g, double r, double r2, double& kap, double& dell, double& dal) {
+  if (g.kind == LMM_KERNEL_RQ) {
+    double h;
+    rq_pair(g.var, g.alpha, r2, kap, h, dal);
+    dell = h * r2 * g.inv_ls;
+  } else {
+    kap = g.var * exp_nonpos(-r);
+    dell = kap * r * g.inv_ls;
+    dal = 0.0;
+  }
+}
 
 // Gradient contractions of one latent: per 64x64 lower tile (ti >= tj) of Kinv
 //   partial[NG*tile + 0] = sum_{i>j in tile} (alpha_i alpha_j - Kinv_ij) dK_ij/d ell        (lengthscale)
@@ -3392,9 +3439,12 @@ __device__ __forceinline__ double dkappa_dell(int kind, double var, double inv_l
 //   partial[NG*tile + 2], [6] = alpha.alpha over the same two row ranges
 //   partial[NG*tile + 3..4]   = alpha.delta, sum alpha over the tile's rows                   (diagonal tiles only)
 //   partial[NG*tile + 7]      = sum_{i>j in tile} (alpha_i alpha_j - Kinv_ij) K_ij            (variance, when Kinv is a block of a larger inverse)
+//   partial[NG*tile + 8]      = sum_{i>j in tile} (alpha_i alpha_j - Kinv_ij) dK_ij/d alpha   (the RQ shape; 0 for the other kinds)
 // The split at nsplit serves the predictive logpdf (joint of training and test points, each block with its own noise).
-#define LMM_NG 8
-template <typename TS>      // storage type of the inverse Kinv (a MATRIX: Float32 in the fp32 compute mode); all sums in Float64
+#define LMM_NG 9
+// TS: storage type of the inverse Kinv (a MATRIX: Float32 in the fp32 compute mode); all sums in Float64.  EXT: a Matern12 / RQ latent
+// (the three original kinds keep the instantiation, and the register budget, they always had).
+template <typename TS, bool EXT>
 __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict__ Kinv, int ld, int n, int nsplit,
                                                           const double* __restrict__ alpha, const double* __restrict__ delta,
                                                           const double* __restrict__ x, int d, LatentDev g, int nt,
@@ -3405,7 +3455,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
   const int t = threadIdx.x;
   const int i0 = ti * 64 + (t & 63);
   const int cg = t >> 6;
-  double acc = 0.0, acck = 0.0;
+  double acc = 0.0, acck = 0.0, acca = 0.0;
   if (i0 < n) {
     const double ai = alpha[i0];
     for (int q = 0; q < 16; ++q) {
@@ -3415,14 +3465,23 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
         if (d == 1) { r = fabs(x[i0] - x[j]) * g.inv_ls; r2 = r * r; }
         else { r2 = scaled_dist2(x + (size_t)i0 * d, x + (size_t)j * d, d, g.inv_ls, nullptr); r = sqrt(r2); }
         const double w = ai * alpha[j] - MatIO<TS>::ld1(Kinv, (size_t)j * ld + i0);
-        acc = __builtin_fma(w, dkappa_dell(g.kind, g.var, g.inv_ls, r, r2), acc);
-        acck = __builtin_fma(w, kappa(g.kind, g.var, r, r2), acck);
+        if (EXT) {
+          double kap, dell, dal;
+          ext_pair(g, r, r2, kap, dell, dal);
+          acc = __builtin_fma(w, dell, acc);
+          acck = __builtin_fma(w, kap, acck);
+          acca = __builtin_fma(w, dal, acca);
+        } else {
+          acc = __builtin_fma(w, dkappa_dell(g.kind, g.var, g.inv_ls, r, r2), acc);
+          acck = __builtin_fma(w, kappa(g.kind, g.var, r, r2), acck);
+        }
       }
     }
   }
   const int tile = ti * nt + tj;
   const double tl = block_sum_256(acc, sh);
   const double tk = block_sum_256(acck, sh);
+  const double ta = (EXT && g.kind == LMM_KERNEL_RQ) ? block_sum_256(acca, sh) : 0.0;     // (g.kind is uniform: the barrier is too)
   double tra = 0.0, aaa = 0.0, trb = 0.0, aab = 0.0, ad = 0.0, sa = 0.0;
   if (ti == tj && t < 64 && i0 < n) {
     const double ai = alpha[i0], kii = MatIO<TS>::ld1(Kinv, (size_t)i0 * ld + i0);
@@ -3433,21 +3492,33 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
   const double s5 = block_sum_256(trb, sh), s6 = block_sum_256(aab, sh);
   if (t == 0) {
     double* o = partial + (size_t)LMM_NG * tile;
-    o[0] = tl; o[1] = s1; o[2] = s2; o[3] = s3; o[4] = s4; o[5] = s5; o[6] = s6; o[7] = tk;
+    o[0] = tl; o[1] = s1; o[2] = s2; o[3] = s3; o[4] = s4; o[5] = s5; o[6] = s6; o[7] = tk; o[8] = ta;
   }
 }
 
 // ARD variant of grad_reduce_kernel (an ARD latent: g.ils holds its d <= DK inverse lengthscales l_k^-1, g.inv_ls = 1 / the common
 // multiplier).  Per pair, with t_k = (x_ik - x_jk) / l_k, r^2 = sum_k t_k^2 and
 //     h(r) = v e^{-r^2/2} (SE),  3 v e^{-sqrt3 r} (Matern32),  (5/3) v (1 + sqrt5 r) e^{-sqrt5 r} (Matern52)   (finite at r = 0),
+//            v e^{-r} / r (Matern12: every t_k = 0 at r = 0, where the pair contributes 0),  v (1 + u)^{-alpha-1} (RQ, rq_pair),
 //     d kappa / d l_k = h t_k^2 / l_k,    d kappa / d multiplier = h r^2 / multiplier  (= sum_k (l_k / multiplier) d kappa / d l_k).
 // The tile partials hold LMM_NG + d entries: the LMM_NG of grad_reduce_kernel ([0] = d/d multiplier) followed by the d sums
 // sum_{i>j in tile} w_ij d kappa_ij / d l_k.  Kinv is read once per tile, as in the isotropic kernel; the d extra FMAs per pair (and,
 // for DK <= 8, the t_k^2 kept in registers) leave the kernel bound by that read.  All sums of a tile are reduced with ONE barrier.
-template <int DK>
-__device__ __forceinline__ void ard_pair(int kind, double var, double r2, double w, double& acc0, double& acck, double& wh) {
+template <int DK, bool EXT>
+__device__ __forceinline__ void ard_pair(int kind, double var, double alpha, double r2, double w, double& acc0, double& acck,
+                                         double& acca, double& wh) {
   double e, kap, h;
-  if (kind == LMM_KERNEL_SE) { e = exp_nonpos(-0.5 * r2); kap = var * e; h = kap; }
+  if (EXT) {
+    if (kind == LMM_KERNEL_RQ) {
+      double dal;
+      rq_pair(var, alpha, r2, kap, h, dal);
+      acca = __builtin_fma(w, dal, acca);
+    } else {                                     // Matern12
+      const double r = sqrt(r2);
+      kap = var * exp_nonpos(-r);
+      h = (r2 > 0.0) ? kap / r : 0.0;            // r >= 2e-162 when r2 > 0: no overflow; r = 0 -> no inf * 0
+    }
+  } else if (kind == LMM_KERNEL_SE) { e = exp_nonpos(-0.5 * r2); kap = var * e; h = kap; }
   else {
     const double r = sqrt(r2);
     if (kind == LMM_KERNEL_MATERN32) {
@@ -3463,7 +3534,7 @@ __device__ __forceinline__ void ard_pair(int kind, double var, double r2, double
   acck = __builtin_fma(w, kap, acck);
 }
 
-template <typename TS, int DK>
+template <typename TS, int DK, bool EXT>
 __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __restrict__ Kinv, int ld, int n, int nsplit,
                                                               const double* __restrict__ alpha, const double* __restrict__ delta,
                                                               const double* __restrict__ x, int d, LatentDev g, int nt,
@@ -3479,7 +3550,7 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
   __syncthreads();
   const int i0 = ti * 64 + (t & 63);
   const int cg = t >> 6;
-  double acc0 = 0.0, acck = 0.0, acc[DK], xi[DK];
+  double acc0 = 0.0, acck = 0.0, acca = 0.0, acc[DK], xi[DK];
 #pragma unroll
   for (int k = 0; k < DK; ++k) { acc[k] = 0.0; xi[k] = 0.0; }
   if (i0 < n) {
@@ -3501,7 +3572,7 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
           }
         const double w = ai * alpha[j] - MatIO<TS>::ld1(Kinv, (size_t)j * ld + i0);
         double wh;
-        ard_pair<DK>(g.kind, g.var, r2, w, acc0, acck, wh);
+        ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, acc0, acck, acca, wh);
 #pragma unroll
         for (int k = 0; k < DK; ++k)
           if (k < d) {
@@ -3521,7 +3592,7 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
   }
   const int lane = t & 63, wv = t >> 6;
   double v[NV];
-  v[0] = acc0 * g.inv_ls; v[1] = tra; v[2] = aaa; v[3] = ad; v[4] = sa; v[5] = trb; v[6] = aab; v[7] = acck;
+  v[0] = acc0 * g.inv_ls; v[1] = tra; v[2] = aaa; v[3] = ad; v[4] = sa; v[5] = trb; v[6] = aab; v[7] = acck; v[8] = acca;
 #pragma unroll
   for (int k = 0; k < DK; ++k) v[LMM_NG + k] = acc[k] * sils[k];
 #pragma unroll
@@ -3700,6 +3771,8 @@ void launch_gram(const GramArgs& a0, hipStream_t st) {
   } while (0)
   if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
   else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
+  else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
+  else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
   else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
 #undef LMM_GRAM_LAUNCH
 }
@@ -3714,7 +3787,7 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     b.base = args[j0];
     for (int j = j0; j < j1; ++j) {
       const GramArgs& a = args[j];
-      b.A[j - j0] = a.A; b.var[j - j0] = a.var; b.inv_ls[j - j0] = a.inv_ls; b.ils[j - j0] = a.ils; b.diag_add[j - j0] = a.diag_add;
+      b.A[j - j0] = a.A; b.var[j - j0] = a.var; b.inv_ls[j - j0] = a.inv_ls; b.ils[j - j0] = a.ils; b.alpha[j - j0] = a.alpha; b.diag_add[j - j0] = a.diag_add;
       b.diag_vec[j - j0] = a.diag_vec; b.rider[j - j0] = a.rider; b.rider_sub[j - j0] = a.rider_sub; b.info_zero[j - j0] = a.info_zero;
     }
     b.base.cpw = gram_cpw(b.base.nrows / 64 - b.base.row_tile0, b.base.ncols / 64, j1 - j0);
@@ -3728,6 +3801,8 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     } while (0)
     if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
     else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
+    else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
+    else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
     else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
 #undef LMM_GRAM_LAUNCH
     j0 = j1;
@@ -4258,7 +4333,8 @@ void launch_post_mean(const double* xs, int ns, const double* x, int n, int d, c
     return;
   }
   const int ic = post_mean_ichunk(n), nch = (n + ic - 1) / ic, nsp = (ns + 255) / 256 * 256;
-  hipLaunchKernelGGL(post_mean_kernel, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  if (g.kind >= LMM_KERNEL_MATERN12) hipLaunchKernelGGL(post_mean_kernel<true>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  else hipLaunchKernelGGL(post_mean_kernel<false>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
   hipLaunchKernelGGL(strip_finish_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, partial, nsp, nch, 1, ns, 0, g.mean, 0.0,
                      out, (double*)nullptr);
 }
@@ -4298,19 +4374,27 @@ void launch_set_identity(double* R, int ld, int nc, hipStream_t st) {
 
 int grad_partials(int n, int d_ard) { const int nt = (n + 63) / 64; return (LMM_NG + d_ard) * nt * nt; }
 
-// out8: [dl/d ell, tr Kinv (rows < nsplit), a.a (rows < nsplit), a.delta, sum a, tr Kinv (rows >= nsplit), a.a (rows >= nsplit),
-//        sum_{i>j} (a_i a_j - Kinv_ij) K_ij]
+// out (LMM_NGRAD values): [dl/d ell, tr Kinv (rows < nsplit), a.a (rows < nsplit), a.delta, sum a, tr Kinv (rows >= nsplit),
+//        a.a (rows >= nsplit), sum_{i>j} (a_i a_j - Kinv_ij) K_ij, dl/d alpha (RQ; 0 otherwise)]
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,
                         LatentDev g, double* partial, double* out7, hipStream_t st, double* out_ard) {
   const int nt = (n + 63) / 64;
+  const bool ext = g.kind >= LMM_KERNEL_MATERN12;      // Matern12 / RQ: the EXT instantiations
   if (g.ils != nullptr) {          // ARD latent (the caller guarantees 1 < d <= LMM_ARD_GRAD_DMAX and out_ard != nullptr)
-    if (d <= 4) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, 4>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
-    else if (d <= 8) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, 8>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
-    else LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, LMM_ARD_GRAD_DMAX>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+#define LMM_ARD_LAUNCH(DK)                                                                                                      \
+    do {                                                                                                                        \
+      if (ext) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, true>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
+      else LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, false>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
+    } while (0)
+    if (d <= 4) LMM_ARD_LAUNCH(4);
+    else if (d <= 8) LMM_ARD_LAUNCH(8);
+    else LMM_ARD_LAUNCH(LMM_ARD_GRAD_DMAX);
+#undef LMM_ARD_LAUNCH
     hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG + d, out_ard);
     return;
   }
-  LMM_TS_LAUNCH((grad_reduce_kernel<TS>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  if (ext) LMM_TS_LAUNCH((grad_reduce_kernel<TS, true>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  else LMM_TS_LAUNCH((grad_reduce_kernel<TS, false>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
   hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG, (double*)nullptr);
 }
 

@@ -90,6 +90,11 @@ isposterior(f::HIPMOGP) = f.handle != C_NULL
 _kind(::SEKernel) = Cint(0)
 _kind(::Matern32Kernel) = Cint(1)
 _kind(::Matern52Kernel) = Cint(2)
+# Matern12Kernel is an alias of ExponentialKernel.  Only the Euclidean metric is served (the library computes |x - x'| itself).
+_euclidean(k) = nameof(typeof(k.metric)) === :Euclidean ||
+    error("LinearMixingModelsHIP: $(nameof(typeof(k))) with metric $(k.metric) is not served (Euclidean only)")
+_kind(k::ExponentialKernel) = (_euclidean(k); Cint(3))
+_kind(k::RationalQuadraticKernel) = (_euclidean(k); Cint(4))
 _desc(k::Kernel) = (_kind(k), 1.0, 1.0)
 _desc(k::ScaledKernel) = ((kd, v, l) = _desc(k.kernel); (kd, v * only(k.σ²), l))
 _desc(k::TransformedKernel{<:Kernel,<:ScaleTransform}) = ((kd, v, l) = _desc(k.kernel); (kd, v, l / only(k.transform.s)))
@@ -103,36 +108,55 @@ function _ard(k::TransformedKernel{<:Kernel,<:ARDTransform})   # the inner kerne
     a = _ard(k.kernel); v = Vector{Float64}(k.transform.v)
     return a === nothing ? 1.0 ./ v : a ./ v
 end
+# the RQ shape alpha (it travels in the latent's tag, lmm_kernel_tag_create); nothing for the other kernels
+_alpha(k::Kernel) = nothing
+_alpha(k::RationalQuadraticKernel) = Float64(only(k.α))
+_alpha(k::ScaledKernel) = _alpha(k.kernel)
+_alpha(k::TransformedKernel) = _alpha(k.kernel)
 _mean(::AbstractGPs.ZeroMean) = 0.0
 _mean(m::AbstractGPs.ConstMean) = Float64(m.c)
 # `_gps(fs) do gps, tags ... end`: the lmm_gp_t array of the latents fs (nothing: none, for calls on a posterior handle) for the
-# duration of ONE library call.  Each ARD latent's factors are registered as a tag (kind = base | tag << 8) before the body runs and
-# destroyed after it, whatever happens; tags[l] is latent l's tag, 0 for an isotropic latent (a handle keeps its own copy of the
-# lengthscales, so destroying the tags after a posterior call is safe).
+# duration of ONE library call.  Each ARD latent's factors and each RQ latent's alpha are registered as one tag (kind = base | tag << 8)
+# before the body runs and destroyed after it, whatever happens; tags[l] is latent l's tag (id 0 for an isotropic latent without
+# alpha; a handle keeps its own copy of the lengthscales and alpha, so destroying the tags after a posterior call is safe).
+struct KTag
+    id::Cint
+    ard::Bool      # the tag holds per-dimension factors
+    alpha::Bool    # the tag holds an RQ shape
+end
 function _gps(body, fs)
-    gps = LmmGp[]; tags = Cint[]
+    gps = LmmGp[]; tags = KTag[]
     try
         for f in (fs === nothing ? () : fs)
-            (kd, v, l) = _desc(f.kernel); a = _ard(f.kernel); t = Cint(0)
-            if a !== nothing
+            (kd, v, l) = _desc(f.kernel); a = _ard(f.kernel); α = _alpha(f.kernel); t = Cint(0)
+            if a !== nothing && α === nothing
                 tr = Ref{Cint}(0)
                 GC.@preserve a check(ccall((:lmm_ard_create, liblmm), Cint, (Cint, Ptr{Cdouble}, Ref{Cint}), length(a), a, tr))
                 t = tr[]
+            elseif α !== nothing
+                tr = Ref{Cint}(0); av = a === nothing ? Float64[] : a
+                GC.@preserve av check(ccall((:lmm_kernel_tag_create, liblmm), Cint, (Cint, Ptr{Cdouble}, Cdouble, Ref{Cint}),
+                                            length(av), a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(av), α, tr))
+                t = tr[]
             end
-            push!(tags, t)
+            push!(tags, KTag(t, a !== nothing, α !== nothing))
             push!(gps, LmmGp(t == 0 ? kd : kd | (t << 8), v, l, _mean(f.mean)))
         end
         return body(gps, tags)
     finally
         for t in tags
-            t == 0 || ccall((:lmm_ard_destroy, liblmm), Cint, (Cint,), t)
+            t.id == 0 || ccall((:lmm_ard_destroy, liblmm), Cint, (Cint,), t.id)
         end
     end
 end
-# after a gradient call inside _gps: d logpdf / d ard[k] of each latent (its tag's lmm_ard_grad), nothing for an isotropic one
-function _ard_grads(tags::Vector{Cint}, d::Integer)
-    return [t == 0 ? nothing :
-            (g = Vector{Float64}(undef, d); GC.@preserve g check(ccall((:lmm_ard_grad, liblmm), Cint, (Cint, Ptr{Cdouble}), t, g)); g)
+# after a gradient call inside _gps, per latent: nothing (no tag) or (ard = d logpdf / d ard[k] (lmm_ard_grad) or nothing,
+# alpha = d logpdf / d alpha (lmm_kernel_tag_alpha_grad) or nothing)
+function _ard_grads(tags::Vector{KTag}, d::Integer)
+    return [t.id == 0 ? nothing :
+            (ard = t.ard ? (g = Vector{Float64}(undef, d);
+                            GC.@preserve g check(ccall((:lmm_ard_grad, liblmm), Cint, (Cint, Ptr{Cdouble}), t.id, g)); g) : nothing,
+             alpha = t.alpha ? (r = Ref{Cdouble}(0.0);
+                                check(ccall((:lmm_kernel_tag_alpha_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) : nothing)
             for t in tags]
 end
 
@@ -593,29 +617,34 @@ AbstractGPs.var(f::HIPMOGP, x::MOIsotopic) = _mean_var(f, x)[2]
 # kernel's construction: ScaledKernel: v = v_inner σ² -> d/dσ² = gv v_inner; ScaleTransform: ℓ = ℓ_inner / s -> d/ds = -gl ℓ_inner / s².
 # ga: d/d ard[k] of an ARD latent (lmm_ard_grad; gl is then d/d the common multiplier).  ARDTransform(v): ard = ard_inner ./ v
 # -> d/dv_k = -ga_k ard_inner_k / v_k^2 (with no inner factors, ℓ_k = multiplier / v_k: d/dv_k = -ℓ_k^2 d/dℓ_k), d/d ard_inner = ga ./ v.
-_ktangent(k::Kernel, gv, gl, ga=nothing) = NoTangent()                        # SEKernel() etc. carry no parameters
-function _ktangent(k::ScaledKernel, gv, gl, ga=nothing)
+# gα: d/d alpha of an RQ latent (lmm_kernel_tag_alpha_grad), nothing otherwise
+_ktangent(k::Kernel, gv, gl, ga=nothing, gα=nothing) = NoTangent()            # SEKernel() etc. carry no parameters
+_ktangent(k::RationalQuadraticKernel, gv, gl, ga=nothing, gα=nothing) =
+    gα === nothing ? NoTangent() : Tangent{typeof(k)}(; α=[gα], metric=NoTangent())
+function _ktangent(k::ScaledKernel, gv, gl, ga=nothing, gα=nothing)
     (_, vin, _) = _desc(k.kernel)
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv * only(k.σ²), gl, ga), σ²=[gv * vin])
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv * only(k.σ²), gl, ga, gα), σ²=[gv * vin])
 end
-function _ktangent(k::TransformedKernel{<:Kernel,<:ScaleTransform}, gv, gl, ga=nothing)
+function _ktangent(k::TransformedKernel{<:Kernel,<:ScaleTransform}, gv, gl, ga=nothing, gα=nothing)
     (_, _, lin) = _desc(k.kernel); s = only(k.transform.s)
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl / s, ga), transform=Tangent{typeof(k.transform)}(; s=[-gl * lin / s^2]))
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl / s, ga, gα), transform=Tangent{typeof(k.transform)}(; s=[-gl * lin / s^2]))
 end
-function _ktangent(k::TransformedKernel{<:Kernel,<:ARDTransform}, gv, gl, ga=nothing)
+function _ktangent(k::TransformedKernel{<:Kernel,<:ARDTransform}, gv, gl, ga=nothing, gα=nothing)
     v = Vector{Float64}(k.transform.v); ain = _ard(k.kernel)
-    ga === nothing && return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl), transform=NoTangent())
+    ga === nothing && return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl, nothing, gα), transform=NoTangent())
     a0 = ain === nothing ? ones(length(v)) : ain
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl, ain === nothing ? nothing : ga ./ v),
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl, ain === nothing ? nothing : ga ./ v, gα),
                               transform=Tangent{typeof(k.transform)}(; v=-ga .* a0 ./ v .^ 2))
 end
 _mtangent(::AbstractGPs.ZeroMean, g) = NoTangent()
 _mtangent(m::AbstractGPs.ConstMean, g) = Tangent{typeof(m)}(; c=g)
-# gard: nothing, or per latent d/d ard (nothing for an isotropic latent) from _ard_grads
+# gard: nothing, or per latent the tag gradients of _ard_grads (nothing for an untagged latent)
+_tagfield(gard, l, s) = (gard === nothing || gard[l] === nothing) ? nothing : getfield(gard[l], s)
 _fstangent(fs::Vector{<:AbstractGP}, gg::Vector{LmmGpGrad}, Δ, gard=nothing) =
     [Tangent{typeof(f)}(; mean=_mtangent(f.mean, Δ * g.mean),
                           kernel=_ktangent(f.kernel, Δ * g.variance, Δ * g.lengthscale,
-                                           (gard === nothing || gard[l] === nothing) ? nothing : Δ .* gard[l]))
+                                           (ga = _tagfield(gard, l, :ard); ga === nothing ? nothing : Δ .* ga),
+                                           (gα = _tagfield(gard, l, :alpha); gα === nothing ? nothing : Δ * gα)))
      for (l, (f, g)) in enumerate(zip(fs, gg))]
 _noise_tangent(fx, g) = Tangent{typeof(fx.Σy)}(; diag=Tangent{typeof(fx.Σy.diag)}(; value=g))     # Fill(σ², n p): one parameter
 _htangent(H::Orthogonal, gU, gS) = Tangent{typeof(H)}(; U=gU, S=Tangent{typeof(H.S)}(; diag=gS))

@@ -63,6 +63,31 @@ class Matern52Kernel(_Kernel):
     kind = "matern52"
 
 
+class Matern12Kernel(_Kernel):
+    """variance * exp(-r): KernelFunctions' Matern12Kernel, an alias of ExponentialKernel."""
+    kind = "matern12"
+
+
+ExponentialKernel = Matern12Kernel
+
+
+class RationalQuadraticKernel(_Kernel):
+    """variance * (1 + r^2 / (2 alpha))^(-alpha): KernelFunctions' RationalQuadraticKernel(; alpha=2.0)."""
+    kind = "rq"
+
+    def __init__(self, variance: float = 1.0, lengthscale=1.0, alpha: float = 2.0):
+        super().__init__(variance, lengthscale)
+        self.alpha = float(alpha)
+        if not (self.alpha > 0.0 and np.isfinite(self.alpha)):
+            raise ValueError("alpha must be finite and > 0")
+
+    def __eq__(self, o):
+        return super().__eq__(o) and self.alpha == o.alpha
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", alpha={self.alpha})"
+
+
 class GP:
     """GP(kernel) or GP(mean_const, kernel)."""
 
@@ -73,8 +98,10 @@ class GP:
             self.mean, self.kernel = float(args[0]), args[1]
 
     def desc(self) -> dict:
-        return {"kind": self.kernel.kind, "variance": self.kernel.variance, "lengthscale": self.kernel.lengthscale,
-                "mean": self.mean}
+        d = {"kind": self.kernel.kind, "variance": self.kernel.variance, "lengthscale": self.kernel.lengthscale, "mean": self.mean}
+        if hasattr(self.kernel, "alpha"):
+            d["alpha"] = self.kernel.alpha
+        return d
 
     def __eq__(self, o):
         return isinstance(o, GP) and self.mean == o.mean and self.kernel == o.kernel
@@ -364,7 +391,8 @@ def _split_train_grad(gy, sizes, p: int):
 def _gps_arg(mogp):
     """(descs, lmm_gp_t array) of an IndependentMOGP's latents.  The ctypes array is rebuilt only when a hyperparameter changed (the key
     is the tuple of current values: building it costs a third of filling the array, which at m = 20 is 25 us of a 380-us call)."""
-    key = tuple((g.kernel.kind, g.kernel.variance, _ls_key(g.kernel.lengthscale), g.mean) for g in mogp.fs)
+    key = tuple((g.kernel.kind, g.kernel.variance, _ls_key(g.kernel.lengthscale), getattr(g.kernel, "alpha", None), g.mean)
+                for g in mogp.fs)
     hit = getattr(mogp, "_gps_cache", None)
     if hit is not None and hit[0] == key:
         return hit[1], hit[2]
@@ -468,11 +496,14 @@ def logpdf(fx: FiniteGP, y, with_regulariser: bool = True) -> float:
 
 def _gps_grads(gg, ga, m: int, d: int) -> list:
     """The latents' kernel-parameter gradients: "lengthscale" is a float for an isotropic latent and, for a per-dimension (ARD) one,
-    the length-d array d logpdf / d lengthscale_k (its tag's lmm_ard_grad: the array passes multiplier 1)."""
+    the length-d array d logpdf / d lengthscale_k (its tag's lmm_ard_grad: the array passes multiplier 1).  An RQ latent adds
+    "alpha" (its tag's lmm_kernel_tag_alpha_grad)."""
     out = []
     for l in range(m):
-        ls = ga.ard.grad(l, d) if ga.ard.tags[l] else gg[l].lengthscale
+        ls = ga.ard.grad(l, d) if ga.ard.has_ard[l] else gg[l].lengthscale
         out.append({"variance": gg[l].variance, "lengthscale": ls, "mean": gg[l].mean})
+        if ga.ard.has_alpha[l]:
+            out[-1]["alpha"] = ga.ard.alpha_grad(l)
     return out
 
 
