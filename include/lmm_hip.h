@@ -279,6 +279,46 @@ int lmm_ilmm_post_latent_logpdf_grad_seq(const double* x, int d, int n, const in
                                          double* grad_y, double* grad_zs, double* grad_batch_sigma2, double* grad_sigma2_s,
                                          double* grad_H, lmm_gp_grad_t* grad_gps);
 
+/* Gradients with respect to the INPUT LOCATIONS (what the reference's Zygote.gradient(logpdf, fx, y) carries through fx.x): each _x
+ * entry point is the entry point of the same name without the suffix, plus trailing outputs; the entry without it is the _x entry with
+ * NULL there.  For every latent, with K its Gram (noise on the diagonal), alpha = K^-1 (T y - mean), w = alpha alpha' - K^-1, its
+ * effective per-dimension lengthscales l_k (isotropic: all equal), t_k = (x_ik - x_jk) / l_k and r^2 = sum_k t_k^2,
+ *     d logpdf / d x_ik = -(1 / l_k^2) sum_{j != i} w_ij h(r_ij) (x_ik - x_jk),
+ *     h(r) = v e^{-r^2/2} (SE), 3 v e^{-sqrt3 r} (Matern32), (5/3) v (1 + sqrt5 r) e^{-sqrt5 r} (Matern52), v e^{-r} / r (Matern12),
+ *            v (1 + r^2 / (2 alpha))^{-alpha-1} (RQ),
+ * summed over the latents (the noise, the mean, the projection and the regulariser do not depend on x).  Matern12 has a cusp at
+ * coincident points: a pair at r = 0 contributes 0 there (the convention of the lengthscale gradient).  Predictive forms: the joint
+ * over [x; xs] minus the marginal over x, as for every other derivative there.
+ *   grad_x : d x n, column-major (the layout of x); for the _seq forms all batches' points in conditioning order.
+ *   grad_xs: d x ns, column-major.
+ * OILMM / IndependentMOGP: partial sums over the latent shard, like every other gradient output.  Any output may be NULL (no extra
+ * work is done for a NULL output); requesting one with d > 32 returns LMM_ERR_UNSUPPORTED.  fp32 compute mode: K^-1 is Float32, the
+ * reduction Float64. */
+int lmm_oilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int p,
+                            const double* U, const double* S, int m, double sigma2,
+                            const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                            double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                            lmm_gp_grad_t* grad_gps, double* grad_x);
+int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
+                                     const double* y, const double* xs, int ns, const double* ys, int p, const double* U,
+                                     const double* S, int m, double sigma2_s, const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                     int with_regulariser, double* out_logpdf, double* grad_y, double* grad_ys,
+                                     double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_S, double* grad_U,
+                                     lmm_gp_grad_t* grad_gps, double* grad_x, double* grad_xs);
+int lmm_ilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int p, const double* H, int m, double sigma2,
+                           const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y, double* grad_sigma2,
+                           double* grad_H, lmm_gp_grad_t* grad_gps, double* grad_x);
+int lmm_ilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
+                                    const double* y, const double* xs, int ns, const double* ys, int p, const double* H, int m,
+                                    double sigma2_s, const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y,
+                                    double* grad_ys, double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_H,
+                                    lmm_gp_grad_t* grad_gps, double* grad_x, double* grad_xs);
+int lmm_ilmm_post_latent_logpdf_grad_seq_x(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
+                                           const double* y, const double* xs, int ns, const double* zs, int p, const double* H, int m,
+                                           double sigma2_s, const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf,
+                                           double* grad_y, double* grad_zs, double* grad_batch_sigma2, double* grad_sigma2_s,
+                                           double* grad_H, lmm_gp_grad_t* grad_gps, double* grad_x, double* grad_xs);
+
 /* logpdf(fx, Y::AbstractMatrix): one value per column of Y ((n p) x ncol, column-major) from ONE factorisation per latent
  * (the extra columns ride the factorisation as rider rows).  The reference does not overload this (it falls to AbstractGPs'
  * dense generic path); AbstractGPs.TestUtils calls it.  out: ncol values. */

@@ -464,6 +464,11 @@ int ard_grad_check(int d) {
     if (p) return fail(LMM_ERR_UNSUPPORTED, "gradients of ARD latents are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
   return LMM_OK;
 }
+// The input gradient (grad_x_kernel) keeps d sums per row in registers, as the ARD reduction does.
+int input_grad_check(int d, bool wanted) {
+  if (!wanted || d <= LMM_ARD_GRAD_DMAX) return LMM_OK;
+  return fail(LMM_ERR_UNSUPPORTED, "gradients with respect to the inputs are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
+}
 // d of the ARD gradient reduction in this call (0: every latent takes the isotropic one)
 int ard_grad_d() {
   if (!g_call_ard) return 0;
@@ -1546,9 +1551,11 @@ struct OilmmGrad {          // host results of oilmm_grad_core (partial sums ove
 // conditioning batches and the test points that the predictive logpdf is the difference of).  Per latent: factor, alpha = Kt^-1 delta, Kt^-1 = L^-T L^-1
 // (triangular solve of identity riders + an upper-triangular SYRK on the MFMA kernels), one fused contraction kernel; the chain
 // rule through T = S^-1/2 U', the projected noise s2/S and the regulariser is small host algebra.
-// xd: d x N (device), yd: N x p column-major (device), gy_dev: N x p device output or nullptr.  Caller holds g_mu.
+// xd: d x N (device), yd: N x p column-major (device), gy_dev: N x p device output or nullptr.  gx_dev: d x N device output of
+// d logpdf / d x summed over the shard's latents (grad_x_kernel), or nullptr (no launch, no allocation).  Caller holds g_mu.
 int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const double* yd, int p, const double* U, const double* S,
-                    int m, const lmm_gp_t* gps, int l0, int l1, int with_regulariser, OilmmGrad& G, double* gy_dev) {
+                    int m, const lmm_gp_t* gps, int l0, int l1, int with_regulariser, OilmmGrad& G, double* gy_dev,
+                    double* gx_dev = nullptr) {
   hipStream_t st0 = g.streams[0];
   const int ms = l1 - l0, n = N, nblk = NB.nblk;
   const bool two = nblk > 1;
@@ -1590,6 +1597,11 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   Buf<int> info(std::max(ms, 1));
   HIPCHK(hipMemsetAsync(info.p, 0, std::max(ms, 1) * sizeof(int), st0));
   HIPCHK(hipMemsetAsync(alpha.p, 0, (size_t)D.NC * std::max(ms, 1) * sizeof(double), st0));
+  // input gradient: each slot sums its latents (in order) into its own d x N buffer; the slots are summed in slot order after the join
+  std::vector<Buf<double>> gxpart, gxacc;
+  std::vector<char> gx_used(nslots, 0);
+  if (gx_dev)
+    for (int s = 0; s < nslots; ++s) { gxpart.emplace_back(grad_x_partial_elems(n, d)); gxacc.emplace_back((size_t)d * n); }
   fork_slots(nslots);
   int bi = 0;
   for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
@@ -1625,6 +1637,10 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
       const int k = k0 + j;
       launch_grad_reduce(Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, grad_dev(gps[l0 + k], l0 + k), part[s].p,
                          red.p + (size_t)NGR * k, st, ardred.p + (size_t)d * k);
+      if (gx_dev) {
+        launch_grad_x(Am[s][j].p, D.ld, n, alb.p[j], xd, d, grad_dev(gps[l0 + k], l0 + k), gxpart[s].p, gxacc[s].p, gx_used[s] != 0, st);
+        gx_used[s] = 1;
+      }
       if (nblk > 2)
         for (int b = 0; b < nblk; ++b) {
           double* o = blksum.p + ((size_t)k * nblk + b) * 2;
@@ -1634,6 +1650,16 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     }
   }
   join_slots(nslots);
+  if (gx_dev) {
+    bool first = true;
+    for (int s = 0; s < nslots; ++s) {
+      if (!gx_used[s]) continue;
+      if (first) HIPCHK(hipMemcpyAsync(gx_dev, gxacc[s].p, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, st0));
+      else launch_vec_lin(gx_dev, gxacc[s].p, 1.0, d * n, gx_dev, st0);
+      first = false;
+    }
+    if (first) HIPCHK(hipMemsetAsync(gx_dev, 0, (size_t)d * n * sizeof(double), st0));      // empty shard
+  }
   std::vector<double> lml(std::max(ms, 1), 0.0), hred((size_t)NGR * std::max(ms, 1), 0.0);
   std::vector<int> hinfo(std::max(ms, 1), 0);
   std::vector<double> hblk(nblk > 2 ? (size_t)2 * nblk * std::max(ms, 1) : 0, 0.0);
@@ -1748,6 +1774,25 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   return LMM_OK;
 }
 
+// Predictive input gradients from the joint (d x (n + ns), device) and marginal (d x n, device) ones: grad_x = joint[:, :n] - marginal,
+// grad_xs = joint[:, n:].  Either output may be NULL (host or device pointers).
+int finish_input_grads(const double* gxj, const double* gxm, int d, int n, int ns, double* grad_x, double* grad_xs) {
+  hipStream_t st0 = g.streams[0];
+  if (grad_x) {
+    DevOut o(grad_x, (size_t)d * n);
+    launch_vec_lin(gxj, gxm, -1.0, d * n, o.p, st0);
+    o.finish(st0);
+    HIPCHK(hipStreamSynchronize(st0));
+  }
+  if (grad_xs) {
+    DevOut o(grad_xs, (size_t)d * ns);
+    HIPCHK(hipMemcpyAsync(o.p, gxj + (size_t)d * n, (size_t)d * ns * sizeof(double), hipMemcpyDeviceToDevice, st0));
+    o.finish(st0);
+    HIPCHK(hipStreamSynchronize(st0));
+  }
+  return LMM_OK;
+}
+
 void write_oilmm_grad(const OilmmGrad& G, int m, int p, double* out_logpdf, double* grad_sigma2, double* grad_S, double* grad_U,
                       lmm_gp_grad_t* grad_gps) {
   *out_logpdf = G.value;
@@ -1765,10 +1810,10 @@ extern "C" {
 // Value and gradient of logpdf(fx::FiniteGP{<:OILMM}, y) (reference src/oilmm.jl:79-93; what the reference's
 // Zygote.gradient(logpdf, fx, y) differentiates, test/oilmm.jl:31-32) w.r.t. y, sigma2, S, U and every latent's
 // (variance, lengthscale, mean).  Partial sums over the shard.
-int lmm_oilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m,
-                          double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
-                          double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
-                          lmm_gp_grad_t* grad_gps) {
+int lmm_oilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m,
+                            double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                            double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                            lmm_gp_grad_t* grad_gps, double* grad_x) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
@@ -1781,17 +1826,28 @@ int lmm_oilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p,
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
-  DevOut gy(grad_y, (size_t)n * p);
+  DevOut gy(grad_y, (size_t)n * p), gx(grad_x, (size_t)d * n);
   if (int rc = ard_grad_check(d)) return rc;
+  if (int rc = input_grad_check(d, grad_x != nullptr)) return rc;
   OilmmGrad G;
   if (int rc = oilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, U, S, m, gps, latent_begin, latent_end, with_regulariser,
-                               G, gy.p))
+                               G, gy.p, gx.p))
     return rc;
   write_oilmm_grad(G, m, p, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
   ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, latent_begin, latent_end);
-  if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
+  if (grad_y) gy.finish(st0);
+  if (grad_x) gx.finish(st0);
+  if (grad_y || grad_x) HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
   LMM_CATCH
+}
+
+int lmm_oilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m,
+                          double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                          double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                          lmm_gp_grad_t* grad_gps) {
+  return lmm_oilmm_logpdf_grad_x(x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, out_logpdf, grad_y,
+                                 grad_sigma2, grad_S, grad_U, grad_gps, nullptr);
 }
 
 // Value and gradient of the predictive logpdf  logpdf(posterior(f(x, sigma2), y)(xs, sigma2_s), ys)  of an OILMM (or, with
@@ -1803,12 +1859,12 @@ int lmm_oilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p,
 // _seq: the posterior was conditioned SEQUENTIALLY, posterior(posterior(f(x1, s1), y1)(x2, s2), y2) ... (reference
 // src/oilmm.jl:116-134 applied to its own result); exact conditioning makes that the posterior given all batches at once with
 // per-batch noise.  x (d x n) and y (n x p by outputs) hold the batches' points in conditioning order, n = sum batch_n.
-int lmm_oilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
-                                   const double* y, const double* xs, int ns, const double* ys, int p, const double* U,
-                                   const double* S, int m, double sigma2_s, const lmm_gp_t* gps, int latent_begin, int latent_end,
-                                   int with_regulariser, double* out_logpdf, double* grad_y, double* grad_ys,
-                                   double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_S, double* grad_U,
-                                   lmm_gp_grad_t* grad_gps) {
+int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
+                                     const double* y, const double* xs, int ns, const double* ys, int p, const double* U,
+                                     const double* S, int m, double sigma2_s, const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                     int with_regulariser, double* out_logpdf, double* grad_y, double* grad_ys,
+                                     double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_S, double* grad_U,
+                                     lmm_gp_grad_t* grad_gps, double* grad_x, double* grad_xs) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
@@ -1829,12 +1885,18 @@ int lmm_oilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* bat
   HIPCHK(hipMemcpy2DAsync(yj.p, (size_t)N * sizeof(double), yd.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpy2DAsync(yj.p + n, (size_t)N * sizeof(double), ysd.p, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
   if (int rc = ard_grad_check(d)) return rc;
+  const bool want_gx = grad_x != nullptr || grad_xs != nullptr;
+  if (int rc = input_grad_check(d, want_gx)) return rc;
   const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
+  Buf<double> gxj, gxm;
+  if (want_gx) gxj = Buf<double>((size_t)d * N);
+  if (grad_x) gxm = Buf<double>((size_t)d * n);
   OilmmGrad GJ, GM;
   if (int rc = oilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, U, S, m, gps,
-                               latent_begin, latent_end, with_regulariser, GJ, want_gy ? gj.p : nullptr)) return rc;
+                               latent_begin, latent_end, with_regulariser, GJ, want_gy ? gj.p : nullptr, gxj.p)) return rc;
   if (int rc = oilmm_grad_core(xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd.p, p, U, S, m, gps,
-                               latent_begin, latent_end, with_regulariser, GM, grad_y ? gm.p : nullptr)) return rc;
+                               latent_begin, latent_end, with_regulariser, GM, grad_y ? gm.p : nullptr, gxm.p)) return rc;
+  if (int rc = finish_input_grads(gxj.p, gxm.p, d, n, ns, grad_x, grad_xs)) return rc;
   *out_logpdf = GJ.value - GM.value;
   if (grad_batch_sigma2) for (int b = 0; b < nbatch; ++b) grad_batch_sigma2[b] = GJ.gs2[b] - GM.gs2[b];
   if (grad_sigma2_s) *grad_sigma2_s = GJ.gs2[nbatch];
@@ -1866,6 +1928,17 @@ int lmm_oilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* bat
   }
   return LMM_OK;
   LMM_CATCH
+}
+
+int lmm_oilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
+                                   const double* y, const double* xs, int ns, const double* ys, int p, const double* U,
+                                   const double* S, int m, double sigma2_s, const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                   int with_regulariser, double* out_logpdf, double* grad_y, double* grad_ys,
+                                   double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_S, double* grad_U,
+                                   lmm_gp_grad_t* grad_gps) {
+  return lmm_oilmm_post_logpdf_grad_seq_x(x, d, n, batch_n, batch_sigma2, nbatch, y, xs, ns, ys, p, U, S, m, sigma2_s, gps, latent_begin,
+                                          latent_end, with_regulariser, out_logpdf, grad_y, grad_ys, grad_batch_sigma2, grad_sigma2_s,
+                                          grad_S, grad_U, grad_gps, nullptr, nullptr);
 }
 
 // One conditioning batch: posterior(f(x, sigma2), y).
@@ -2160,8 +2233,10 @@ struct IlmmGrad {            // host results of ilmm_grad_core
 // so the reference's projected posterior, src/ilmm.jl:184-198, is the exact conditional), one block per conditioning batch.
 // Hblk (optional): block b is observed through the mixing matrix Hblk[b] (p x m, host) instead of H -- the latent view of a posterior
 // (lmm_ilmm_post_latent_logpdf_grad_seq) observes its test block through [I_m; 0]; G.gH collects the blocks observed through H itself.
+// gx_dev (optional, d x n device): d logpdf / d x from the diagonal blocks of the inverse (the latent prior is block-diagonal).
 int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const double* yd, int p, const double* H, int m,
-                   const lmm_gp_t* gps, const lmm_jitters_t* jit, IlmmGrad& G, double* gy_dev, const double* const* Hblk = nullptr) {
+                   const lmm_gp_t* gps, const lmm_jitters_t* jit, IlmmGrad& G, double* gy_dev, const double* const* Hblk = nullptr,
+                   double* gx_dev = nullptr) {
   if ((long long)m * n > 46000) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense gradient (explicit (mn)^2 inverse)");
   hipStream_t st0 = g.streams[0];
   constexpr int KB = LMM_MAX_NOISE_BLOCKS;
@@ -2234,10 +2309,15 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   const int NGR = LMM_NGRAD;
   const size_t mm = (size_t)m * m, mp = (size_t)m * p;
   Buf<double> red((size_t)NGR * m), gpart((size_t)grad_partials(n, ard_grad_d())), Btr(KB * mm), AAt(KB * mm), AY(KB * mp);
-  Buf<double> ardred((size_t)d * m);
-  for (int l = 0; l < m; ++l)
+  Buf<double> ardred((size_t)d * m), gxpart;
+  if (gx_dev) gxpart = Buf<double>(grad_x_partial_elems(n, d));
+  for (int l = 0; l < m; ++l) {
     launch_grad_reduce(mat_at(A.p, (size_t)l * n * D.ld + (size_t)l * n), D.ld, n, n, alpha.p + (size_t)l * n, delta.p + (size_t)l * n, xd, d,
                        grad_dev(gps[l], l), gpart.p, red.p + (size_t)NGR * l, st0, ardred.p + (size_t)d * l);
+    if (gx_dev)
+      launch_grad_x(mat_at(A.p, (size_t)l * n * D.ld + (size_t)l * n), D.ld, n, alpha.p + (size_t)l * n, xd, d, grad_dev(gps[l], l), gxpart.p,
+                    gx_dev, l > 0, st0);
+  }
   // regulariser pieces: Rm = Y - (T Y)' H' (n x p), RH = Rm H (n x m), per block Rm' Ty (p x m), RH' Y (m x p)
   Buf<double> HTY((size_t)n * p), Rm((size_t)n * p), RH((size_t)N), RtTy(KB * mp), RHtY(KB * mp);
   for (int b = 0; b < nblk; ++b)
@@ -2388,9 +2468,9 @@ extern "C" {
 // here additionally its explicit inverse (triangular solve of identity riders + upper-triangular SYRK on the MFMA kernels),
 // per-latent contractions on the diagonal blocks of the inverse, and the chain rule through project(H, sigma2)
 // (src/ilmm.jl:61-68) and the regulariser (src/ilmm.jl:171-181) as small host algebra.  Does not shard.
-int lmm_ilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p, const double* H, int m, double sigma2,
-                         const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y, double* grad_sigma2,
-                         double* grad_H, lmm_gp_grad_t* grad_gps) {
+int lmm_ilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int p, const double* H, int m, double sigma2,
+                           const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y, double* grad_sigma2,
+                           double* grad_H, lmm_gp_grad_t* grad_gps, double* grad_x) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
@@ -2400,18 +2480,27 @@ int lmm_ilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p, 
   if (!jit) jit = &kDefaultJit;
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
-  DevOut gy(grad_y, (size_t)n * p);
+  DevOut gy(grad_y, (size_t)n * p), gx(grad_x, (size_t)d * n);
   if (int rc = ard_grad_check(d)) return rc;
+  if (int rc = input_grad_check(d, grad_x != nullptr)) return rc;
   IlmmGrad G;
-  if (int rc = ilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, H, m, gps, jit, G, gy.p)) return rc;
+  if (int rc = ilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, H, m, gps, jit, G, gy.p, nullptr, gx.p)) return rc;
   ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, 0, m);
   *out_logpdf = G.value;
   if (grad_sigma2) *grad_sigma2 = G.gs2[0];
   if (grad_H) std::copy(G.gH.begin(), G.gH.end(), grad_H);
   if (grad_gps) for (int l = 0; l < m; ++l) grad_gps[l] = G.ggps[l];
-  if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
+  if (grad_y) gy.finish(st0);
+  if (grad_x) gx.finish(st0);
+  if (grad_y || grad_x) HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
   LMM_CATCH
+}
+
+int lmm_ilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p, const double* H, int m, double sigma2,
+                         const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y, double* grad_sigma2,
+                         double* grad_H, lmm_gp_grad_t* grad_gps) {
+  return lmm_ilmm_logpdf_grad_x(x, d, n, y, p, H, m, sigma2, gps, jit, out_logpdf, grad_y, grad_sigma2, grad_H, grad_gps, nullptr);
 }
 
 // Value and TOTAL derivatives of logpdf(posterior(f(x, sigma2), y)(xs, sigma2_s), ys) for the dense-H ILMM -- what
@@ -2426,7 +2515,7 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
                                const double* y, const double* xs, int ns, const double* ys, int p, const double* H, int m,
                                double sigma2_s, const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y,
                                double* grad_ys, double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_H,
-                               lmm_gp_grad_t* grad_gps) {
+                               lmm_gp_grad_t* grad_gps, double* grad_x, double* grad_xs) {
   if (!x || !y || !xs || !ys || !H || !out_logpdf || d <= 0 || n <= 0 || ns <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_test && m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   RESOLVE_GPS(gps, m, d);
@@ -2453,12 +2542,18 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
     Hblk[nbatch] = Hlat.data();
   }
   if (int rc = ard_grad_check(d)) return rc;
+  const bool want_gx = grad_x != nullptr || grad_xs != nullptr;
+  if (int rc = input_grad_check(d, want_gx)) return rc;
   const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
+  Buf<double> gxj, gxm;
+  if (want_gx) gxj = Buf<double>((size_t)d * N);
+  if (grad_x) gxm = Buf<double>((size_t)d * n);
   IlmmGrad GJ, GM;
   if (int rc = ilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, H, m, gps, jit, GJ,
-                              want_gy ? gj.p : nullptr, latent_test ? Hblk : nullptr)) return rc;
+                              want_gy ? gj.p : nullptr, latent_test ? Hblk : nullptr, gxj.p)) return rc;
   if (int rc = ilmm_grad_core(xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd.p, p, H, m, gps, jit, GM,
-                              grad_y ? gm.p : nullptr)) return rc;
+                              grad_y ? gm.p : nullptr, nullptr, gxm.p)) return rc;
+  if (int rc = finish_input_grads(gxj.p, gxm.p, d, n, ns, grad_x, grad_xs)) return rc;
   const double pad = latent_test ? 0.5 * (double)ns * (double)(p - m) : 0.0;
   *out_logpdf = GJ.value - GM.value + pad * (kLog2Pi + std::log(sigma2_s));
   if (grad_batch_sigma2) for (int b = 0; b < nbatch; ++b) grad_batch_sigma2[b] = GJ.gs2[b] - GM.gs2[b];
@@ -2493,33 +2588,52 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
 
 extern "C" {
 
+int lmm_ilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
+                                    const double* y, const double* xs, int ns, const double* ys, int p, const double* H, int m,
+                                    double sigma2_s, const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y,
+                                    double* grad_ys, double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_H,
+                                    lmm_gp_grad_t* grad_gps, double* grad_x, double* grad_xs) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  return ilmm_post_logpdf_grad_impl(false, x, d, n, batch_n, batch_sigma2, nbatch, y, xs, ns, ys, p, H, m, sigma2_s, gps, jit, out_logpdf,
+                                    grad_y, grad_ys, grad_batch_sigma2, grad_sigma2_s, grad_H, grad_gps, grad_x, grad_xs);
+  LMM_CATCH
+}
+
 int lmm_ilmm_post_logpdf_grad_seq(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
                                   const double* y, const double* xs, int ns, const double* ys, int p, const double* H, int m,
                                   double sigma2_s, const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y,
                                   double* grad_ys, double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_H,
                                   lmm_gp_grad_t* grad_gps) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  REQUIRE_INIT();
-  LMM_TRY
-  return ilmm_post_logpdf_grad_impl(false, x, d, n, batch_n, batch_sigma2, nbatch, y, xs, ns, ys, p, H, m, sigma2_s, gps, jit, out_logpdf,
-                                    grad_y, grad_ys, grad_batch_sigma2, grad_sigma2_s, grad_H, grad_gps);
-  LMM_CATCH
+  return lmm_ilmm_post_logpdf_grad_seq_x(x, d, n, batch_n, batch_sigma2, nbatch, y, xs, ns, ys, p, H, m, sigma2_s, gps, jit, out_logpdf,
+                                         grad_y, grad_ys, grad_batch_sigma2, grad_sigma2_s, grad_H, grad_gps, nullptr, nullptr);
 }
 
 // The same for the LATENT view of the posterior: logpdf(get_latent_gp(posterior(...))(xs, sigma2_s), zs) with zs (ns x m, by outputs over
 // the m latents) -- reference src/ilmm.jl:39 on the posterior ILMM of :196-197, whose latent GP is the coupled PosteriorGP of the
 // IndependentMOGP; Zygote differentiates its logpdf like any other.  grad_ys: ns x m.  grad_H: through the conditioning batches only.
+int lmm_ilmm_post_latent_logpdf_grad_seq_x(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
+                                           const double* y, const double* xs, int ns, const double* zs, int p, const double* H, int m,
+                                           double sigma2_s, const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf,
+                                           double* grad_y, double* grad_zs, double* grad_batch_sigma2, double* grad_sigma2_s,
+                                           double* grad_H, lmm_gp_grad_t* grad_gps, double* grad_x, double* grad_xs) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  return ilmm_post_logpdf_grad_impl(true, x, d, n, batch_n, batch_sigma2, nbatch, y, xs, ns, zs, p, H, m, sigma2_s, gps, jit, out_logpdf,
+                                    grad_y, grad_zs, grad_batch_sigma2, grad_sigma2_s, grad_H, grad_gps, grad_x, grad_xs);
+  LMM_CATCH
+}
+
 int lmm_ilmm_post_latent_logpdf_grad_seq(const double* x, int d, int n, const int* batch_n, const double* batch_sigma2, int nbatch,
                                          const double* y, const double* xs, int ns, const double* zs, int p, const double* H, int m,
                                          double sigma2_s, const lmm_gp_t* gps, const lmm_jitters_t* jit, double* out_logpdf, double* grad_y,
                                          double* grad_zs, double* grad_batch_sigma2, double* grad_sigma2_s, double* grad_H,
                                          lmm_gp_grad_t* grad_gps) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  REQUIRE_INIT();
-  LMM_TRY
-  return ilmm_post_logpdf_grad_impl(true, x, d, n, batch_n, batch_sigma2, nbatch, y, xs, ns, zs, p, H, m, sigma2_s, gps, jit, out_logpdf,
-                                    grad_y, grad_zs, grad_batch_sigma2, grad_sigma2_s, grad_H, grad_gps);
-  LMM_CATCH
+  return lmm_ilmm_post_latent_logpdf_grad_seq_x(x, d, n, batch_n, batch_sigma2, nbatch, y, xs, ns, zs, p, H, m, sigma2_s, gps, jit,
+                                                out_logpdf, grad_y, grad_zs, grad_batch_sigma2, grad_sigma2_s, grad_H, grad_gps, nullptr,
+                                                nullptr);
 }
 
 // One conditioning batch: posterior(f(x, sigma2), y).

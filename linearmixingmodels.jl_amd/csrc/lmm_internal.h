@@ -184,6 +184,11 @@ int grad_partials(int n, int d_ard = 0);      // partial-buffer elements of laun
 // g.ils != nullptr (an ARD latent, d <= LMM_ARD_GRAD_DMAX): out8[0] is d/d multiplier and out_ard[k] = d/d l_k (d values)
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,
                         LatentDev g, double* partial, double* out7, hipStream_t st, double* out_ard = nullptr);
+// Input gradient of one latent (grad_x_kernel): gx (d x n, column-major) = d logpdf_l / d x from the lower triangle of Kinv, alpha and
+// x; accumulate: gx += instead of gx =.  partial: grad_x_partial_elems(n, d) doubles.  d <= LMM_ARD_GRAD_DMAX.
+size_t grad_x_partial_elems(int n, int d);
+void launch_grad_x(const double* Kinv, int ld, int n, const double* alpha, const double* x, int d, LatentDev g, double* partial,
+                   double* gx, bool accumulate, hipStream_t st);
 void launch_vec_axpby(const double* a, double sa, const double* b, double sb, size_t n, double* out, hipStream_t st);
 void launch_block_trace(const double* Minv, int ld, int n, int m, int i0, int i1, double* out, hipStream_t st);   // points i0..i1-1
 // Consecutive point ranges [off[b], off[b + 1]) that carry the observation-noise variance s2[b]: the conditioning batches of a

@@ -3621,6 +3621,96 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restri
   }
 }
 
+// Input gradient of one latent: with w = alpha alpha' - Kinv, t_k = (x_ik - x_jk) / l_k and h(r) of ard_pair,
+//     d kappa(x_i, x_j) / d x_ik = -h(r) t_k / l_k,    so    gx[k, i] = -(1 / l_k) sum_{j != i} w_ij h(r_ij) t_k.
+// Matern12 at coincident points (r = 0, where the kernel has a cusp): ard_pair's h = 0, so the pair contributes 0.  t_k is formed as
+// (x_ik - x_jk) / l_k, difference first, so that it is exactly 0 there (x_ik / l_k - x_jk / l_k under FMA contraction is not).
+// Workgroup (ti, c) owns the 64 rows of tile row ti and the LMM_GX_CHUNK column tiles [c LMM_GX_CHUNK, ...) of their whole row: tiles left
+// of the diagonal are read from the stored lower triangle (contiguous in i), the diagonal tile and the tiles right of it from the lower
+// triangle TRANSPOSED (Kinv[j, i] is contiguous in j), staged through LDS.  Each lower tile is thus read twice -- the bytes of one
+// full-matrix read -- and no atomics are used: a thread keeps row i's d sums for its column quarter, the four quarters are summed in a
+// fixed order, and partial[(c n + i) d + k] holds the chunk's value (grad_x_finish_kernel sums the chunks in order).  l_k = 1 / g.ils[k]
+// (ARD) or 1 / g.inv_ls; x and gx are d x n column-major.  DK >= d; DK = 1 is the d = 1 path.
+#define LMM_GX_CHUNK 16
+template <typename TS, int DK, bool EXT>
+__global__ __launch_bounds__(256) void grad_x_kernel(const void* __restrict__ Kinv, int ld, int n, const double* __restrict__ alpha,
+                                                     const double* __restrict__ x, int d, LatentDev g, double* __restrict__ partial) {
+  __shared__ double sils[DK];
+  __shared__ double tl[64][65];                  // staged transposed tile; then the cross-quarter sums
+  const int ti = blockIdx.x, c = blockIdx.y, nt = (n + 63) / 64;
+  const int t = threadIdx.x, il = t & 63, cg = t >> 6;
+  if (t < DK) sils[t] = (t < d) ? (g.ils ? g.ils[t] : g.inv_ls) : 0.0;
+  __syncthreads();
+  const int i = ti * 64 + il;
+  const bool ok = i < n;
+  double xi[DK], acc[DK];
+#pragma unroll
+  for (int k = 0; k < DK; ++k) { xi[k] = (ok && k < d) ? x[(size_t)i * d + k] : 0.0; acc[k] = 0.0; }
+  const double ai = ok ? alpha[i] : 0.0;
+  const int tj1 = min((c + 1) * LMM_GX_CHUNK, nt);
+  for (int tj = c * LMM_GX_CHUNK; tj < tj1; ++tj) {
+    const int j0 = tj * 64;
+    if (tj >= ti) {                              // (uniform) stage tl[r][s] = Kinv[j0 + s, ti 64 + r]: valid where j0 + s > ti 64 + r
+      __syncthreads();
+#pragma unroll 4
+      for (int q = 0; q < 16; ++q) {
+        const int r = cg + 4 * q, ir = ti * 64 + r, jc = j0 + il;
+        tl[r][il] = (ir < n && jc < n) ? MatIO<TS>::ld1(Kinv, (size_t)ir * ld + jc) : 0.0;
+      }
+      __syncthreads();
+    }
+    for (int q = 0; q < 16; ++q) {
+      const int jl = cg + 4 * q, j = j0 + jl;
+      if (ok && j < n && j != i) {
+        double kij;
+        if (tj < ti) kij = MatIO<TS>::ld1(Kinv, (size_t)j * ld + i);
+        else kij = (tj > ti || jl > il) ? tl[il][jl] : tl[jl][il];
+        const double* xj = x + (size_t)j * d;
+        double tk[DK], r2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < DK; ++k) {
+          tk[k] = (k < d) ? (xi[k] - xj[k]) * sils[k] : 0.0;     // difference first: exactly 0 at coincident points
+          r2 = __builtin_fma(tk[k], tk[k], r2);
+        }
+        const double w = ai * alpha[j] - kij;
+        double a0 = 0.0, ak = 0.0, aa = 0.0, wh;
+        ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, a0, ak, aa, wh);      // only wh = w h(r) is used
+#pragma unroll
+        for (int k = 0; k < DK; ++k) acc[k] = __builtin_fma(wh, tk[k], acc[k]);
+      }
+    }
+  }
+  // row i's sum over the four column quarters, in quarter order, 16 dimensions at a time (3 x 16 x 64 doubles fit in tl)
+  double* red = &tl[0][0];
+#pragma unroll
+  for (int k0 = 0; k0 < DK; k0 += 16) {
+    __syncthreads();
+    if (cg > 0)
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk)
+        if (k0 + kk < DK) red[((cg - 1) * 16 + kk) * 64 + il] = acc[k0 + kk];
+    __syncthreads();
+    if (cg == 0 && ok)
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk) {
+        const int k = k0 + kk;
+        if (k < DK && k < d) {
+          const double s = ((acc[k] + red[kk * 64 + il]) + red[(16 + kk) * 64 + il]) + red[(32 + kk) * 64 + il];
+          partial[((size_t)c * n + i) * d + k] = -s * sils[k];
+        }
+      }
+  }
+}
+
+// out[e] (+)= sum over the nch chunk partials of element e (e < n d), in chunk order
+__global__ void grad_x_finish_kernel(const double* __restrict__ partial, int nch, size_t count, int accumulate, double* __restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= count) return;
+  double s = 0.0;
+  for (int c = 0; c < nch; ++c) s += partial[(size_t)c * count + e];
+  out[e] = accumulate ? out[e] + s : s;
+}
+
 // out[l + l2*m] = sum_i Minv[(l n + i), (l2 n + i)]  for l >= l2 (mirrored into l < l2): the m x m matrix of traces of the diagonals of
 // the n x n blocks of a symmetric (m n) x (m n) matrix whose lower triangle is stored (dense-H ILMM gradient: dL/dSigmaT).
 template <typename TS>
@@ -4396,6 +4486,26 @@ void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const dou
   if (ext) LMM_TS_LAUNCH((grad_reduce_kernel<TS, true>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
   else LMM_TS_LAUNCH((grad_reduce_kernel<TS, false>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
   hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG, (double*)nullptr);
+}
+
+size_t grad_x_partial_elems(int n, int d) { const int nt = (n + 63) / 64; return (size_t)((nt + LMM_GX_CHUNK - 1) / LMM_GX_CHUNK) * n * d; }
+
+void launch_grad_x(const double* Kinv, int ld, int n, const double* alpha, const double* x, int d, LatentDev g, double* partial,
+                   double* gx, bool accumulate, hipStream_t st) {
+  const int nt = (n + 63) / 64, nch = (nt + LMM_GX_CHUNK - 1) / LMM_GX_CHUNK;
+  const bool ext = g.kind >= LMM_KERNEL_MATERN12;
+#define LMM_GX_LAUNCH(DK)                                                                                                      \
+  do {                                                                                                                        \
+    if (ext) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, true>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
+    else LMM_TS_LAUNCH((grad_x_kernel<TS, DK, false>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
+  } while (0)
+  if (d == 1) LMM_GX_LAUNCH(1);
+  else if (d <= 4) LMM_GX_LAUNCH(4);
+  else if (d <= 8) LMM_GX_LAUNCH(8);
+  else LMM_GX_LAUNCH(LMM_ARD_GRAD_DMAX);
+#undef LMM_GX_LAUNCH
+  const size_t count = (size_t)n * d;
+  hipLaunchKernelGGL(grad_x_finish_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, partial, nch, count, accumulate ? 1 : 0, gx);
 }
 
 void launch_vec_axpby(const double* a, double sa, const double* b, double sb, size_t n, double* out, hipStream_t st) {

@@ -301,10 +301,12 @@ function _merged_train(train, p::Integer)
     return X0, Cint[size(t[1], 2) for t in train], Cdouble[t[2] for t in train], y0
 end
 # d/dy of the merged points back to one by-outputs vector per batch; d/dσ² per batch (a scalar for a single batch)
-function _split_train(gy0, gb, bn, p::Integer)
-    length(bn) == 1 && return (y_train=gy0, sigma2_train=gb[1])
+# gx0: d/dx of the merged points (d x n, nothing when not computed) -> x_train, one d x n_b block per batch when there are several
+function _split_train(gy0, gb, bn, p::Integer, gx0=nothing)
+    length(bn) == 1 && return (y_train=gy0, sigma2_train=gb[1], x_train=gx0)
     G = reshape(gy0, :, p); o = cumsum(vcat(0, bn))
-    return (y_train=[vec(G[o[b]+1:o[b+1], :]) for b in eachindex(bn)], sigma2_train=copy(gb))
+    return (y_train=[vec(G[o[b]+1:o[b+1], :]) for b in eachindex(bn)], sigma2_train=copy(gb),
+            x_train=(gx0 === nothing ? nothing : [gx0[:, o[b]+1:o[b+1]] for b in eachindex(bn)]))
 end
 # reference src/oilmm.jl:116-134; on a posterior: sequential conditioning (TestUtils on `po`, test/oilmm.jl:34-37)
 function AbstractGPs.posterior(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real})
@@ -611,7 +613,8 @@ AbstractGPs.var(f::HIPMOGP, x::MOIsotopic) = _mean_var(f, x)[2]
 # ---- gradients: ChainRulesCore.rrule around the ccall --------------------------------------------------------------------
 # The reference's tests take Zygote.gradient(logpdf, fx, y) on prior and posterior models (test/oilmm.jl:31-32,
 # test/ilmm.jl:31-32, test/independent_mogp.jl:65-66).  A ccall is opaque to Zygote, so the pullbacks come from the library
-# (lmm_oilmm_logpdf_grad, lmm_ilmm_logpdf_grad, lmm_oilmm_post_logpdf_grad_seq, lmm_ilmm_post_logpdf_grad_seq) and are mapped onto the reference's structs.
+# (lmm_oilmm_logpdf_grad, lmm_ilmm_logpdf_grad, lmm_oilmm_post_logpdf_grad_seq, lmm_ilmm_post_logpdf_grad_seq, and their _x forms, which
+# add d logpdf / d x) and are mapped onto the reference's structs.
 
 # kernel cotangent: the library differentiates w.r.t. the EFFECTIVE (variance, lengthscale); the chain rule through the
 # kernel's construction: ScaledKernel: v = v_inner σ² -> d/dσ² = gv v_inner; ScaleTransform: ℓ = ℓ_inner / s -> d/ds = -gl ℓ_inner / s².
@@ -647,6 +650,15 @@ _fstangent(fs::Vector{<:AbstractGP}, gg::Vector{LmmGpGrad}, Δ, gard=nothing) =
                                            (gα = _tagfield(gard, l, :alpha); gα === nothing ? nothing : Δ * gα)))
      for (l, (f, g)) in enumerate(zip(fs, gg))]
 _noise_tangent(fx, g) = Tangent{typeof(fx.Σy)}(; diag=Tangent{typeof(fx.Σy.diag)}(; value=g))     # Fill(σ², n p): one parameter
+# Input locations: the library's d logpdf / d x (G, d x n) as the cotangent of the FiniteGP's x = MOInputIsotopicByOutputs(inner, p):
+# a Vector input gets a vector, ColVecs its X (d x n), RowVecs its X transposed (n x d).  INPUT_GRADIENTS[] = false skips the input
+# gradient (the lmm_*_grad entry points without _x; one read of each latent's K^-1 less) and leaves x without a cotangent.
+const INPUT_GRADIENTS = Ref(true)
+_xtangent(x::AbstractVector{<:Real}, G) = vec(G)
+_xtangent(x::ColVecs, G) = Tangent{typeof(x)}(; X=G)
+_xtangent(x::RowVecs, G) = Tangent{typeof(x)}(; X=permutedims(G))
+_xtangent(x, G) = NoTangent()
+_motangent(x::MOInputIsotopicByOutputs, G) = G === nothing ? NoTangent() : Tangent{typeof(x)}(; x=_xtangent(x.x, G), out_dim=NoTangent())
 _htangent(H::Orthogonal, gU, gS) = Tangent{typeof(H)}(; U=gU, S=Tangent{typeof(H.S)}(; diag=gS))
 
 function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real})
@@ -655,15 +667,25 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
     val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
     gy = Vector{Float64}(undef, n * p); gS = Vector{Float64}(undef, m); gU = Matrix{Float64}(undef, p, m)
     gg = Vector{LmmGpGrad}(undef, m)
+    wantx = INPUT_GRADIENTS[]; gx = wantx ? Matrix{Float64}(undef, d, n) : nothing
     if isposterior(fs)
         fs.train === nothing && error("this posterior does not carry its training data")
         X0, bn, bs, y0 = _merged_train(fs.train, p); n0 = size(X0, 2); gy0 = Vector{Float64}(undef, n0 * p); gb = similar(bs)
+        gx0 = wantx ? Matrix{Float64}(undef, d, n0) : nothing
         _gps(fs.fs) do gps, tags
-            GC.@preserve X0 bn bs y0 X yv U S gps gy0 gy gb gS gU gg check(ccall((:lmm_oilmm_post_logpdf_grad_seq, liblmm), Cint,
-                (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
-                 Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
-                 Ptr{Cdouble}, Ptr{LmmGpGrad}),
-                X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy0, gy, gb, gσ, gS, gU, gg))
+            if wantx
+                GC.@preserve X0 bn bs y0 X yv U S gps gy0 gy gb gS gU gg gx0 gx check(ccall((:lmm_oilmm_post_logpdf_grad_seq_x, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                     Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{LmmGpGrad}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy0, gy, gb, gσ, gS, gU, gg, gx0, gx))
+            else
+                GC.@preserve X0 bn bs y0 X yv U S gps gy0 gy gb gS gU gg check(ccall((:lmm_oilmm_post_logpdf_grad_seq, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                     Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                    X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy0, gy, gb, gσ, gS, gU, gg))
+            end
             gard = _ard_grads(tags, d)
         end
         # The library returns TOTAL derivatives through the posterior, including those w.r.t. the training data (gy0) and the
@@ -671,19 +693,27 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
         # `posterior`, whose own rrule would be the place to receive them -- so THIS pullback propagates the cotangents of the
         # latent GPs, H, the predictive noise and y* only; gy0 / gb are NOT propagated by it.  Callers who differentiate
         # θ -> logpdf(posterior(f_θ(x, σ²), y)(x*, σ²*), y*) end to end use `predictive_logpdf_and_gradient` below, which returns them.
-        fs.last_train_cotangents[] = _split_train(gy0, gb, bn, p)      # one entry per conditioning batch when there are several
+        fs.last_train_cotangents[] = _split_train(gy0, gb, bn, p, gx0)      # one entry per conditioning batch when there are several
     else
         _gps(fs.fs) do gps, tags
-            GC.@preserve X yv U S gps gy gS gU gg check(ccall((:lmm_oilmm_logpdf_grad, liblmm), Cint,
-                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
-                 Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-                X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy, gσ, gS, gU, gg))
+            if wantx
+                GC.@preserve X yv U S gps gy gS gU gg gx check(ccall((:lmm_oilmm_logpdf_grad_x, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
+                     Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}, Ptr{Cdouble}),
+                    X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy, gσ, gS, gU, gg, gx))
+            else
+                GC.@preserve X yv U S gps gy gS gU gg check(ccall((:lmm_oilmm_logpdf_grad, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
+                     Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                    X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy, gσ, gS, gU, gg))
+            end
             gard = _ard_grads(tags, d)
         end
     end
     function logpdf_pullback(Δ)
         dlat = Tangent{typeof(fs)}(; fs=_fstangent(fs.fs, gg, Δ, gard))
-        dfx = Tangent{typeof(fx)}(; f=Tangent{typeof(fx.f)}(; f=dlat, H=_htangent(H, Δ .* gU, Δ .* gS)), Σy=_noise_tangent(fx, Δ * gσ[]))
+        dx = _motangent(fx.x, gx === nothing ? nothing : Δ .* gx)
+        dfx = Tangent{typeof(fx)}(; x=dx, f=Tangent{typeof(fx.f)}(; f=dlat, H=_htangent(H, Δ .* gU, Δ .* gS)), Σy=_noise_tangent(fx, Δ * gσ[]))
         return NoTangent(), dfx, Δ .* gy
     end
     return val[], logpdf_pullback
@@ -695,7 +725,8 @@ function predictive_logpdf_and_gradient(fx::ByOutputsFill{HIPOILMM}, y::Abstract
     val, back = ChainRulesCore.rrule(AbstractGPs.logpdf, fx, y)
     _, dfx, dy = back(1.0)
     tr = unpack(fx)[1].last_train_cotangents[]
-    return (value=val, fx=dfx, y=dy, y_train=(tr === nothing ? nothing : tr.y_train), sigma2_train=(tr === nothing ? nothing : tr.sigma2_train))
+    return (value=val, fx=dfx, y=dy, y_train=(tr === nothing ? nothing : tr.y_train), sigma2_train=(tr === nothing ? nothing : tr.sigma2_train),
+            x_train=(tr === nothing ? nothing : tr.x_train))
 end
 
 # IndependentMOGP (reference test/independent_mogp.jl:65-66): the OILMM with U = I, S = 1 and no regulariser
@@ -704,28 +735,46 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), ft::ByOutputsFill{HI
     U = Matrix{Float64}(I, m, m); S = ones(m); gard = nothing; yv = Vector{Float64}(y)
     val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
     gy = Vector{Float64}(undef, n * m); gg = Vector{LmmGpGrad}(undef, m)
+    wantx = INPUT_GRADIENTS[]; gx = wantx ? Matrix{Float64}(undef, d, n) : nothing
     if isposterior(f)
         f.train === nothing && error("this posterior does not carry its training data")
         X0, bn, bs, y0 = _merged_train(f.train, m); n0 = size(X0, 2)
         _gps(f.fs) do gps, tags
-            GC.@preserve X0 bn bs y0 X yv U S gps gy gg check(ccall((:lmm_oilmm_post_logpdf_grad_seq, liblmm), Cint,
-                (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
-                 Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
-                 Ptr{Cdouble}, Ptr{LmmGpGrad}),
-                X0, d, n0, bn, bs, length(bn), y0, X, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, C_NULL, gy, C_NULL, gσ, C_NULL, C_NULL, gg))
+            if wantx        # (d/dx of the training points is not kept: this pullback does not return the training cotangents)
+                GC.@preserve X0 bn bs y0 X yv U S gps gy gg gx check(ccall((:lmm_oilmm_post_logpdf_grad_seq_x, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                     Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{LmmGpGrad}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    X0, d, n0, bn, bs, length(bn), y0, X, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, C_NULL, gy, C_NULL, gσ, C_NULL, C_NULL, gg,
+                    C_NULL, gx))
+            else
+                GC.@preserve X0 bn bs y0 X yv U S gps gy gg check(ccall((:lmm_oilmm_post_logpdf_grad_seq, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+                     Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble},
+                     Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                    X0, d, n0, bn, bs, length(bn), y0, X, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, C_NULL, gy, C_NULL, gσ, C_NULL, C_NULL, gg))
+            end
             gard = _ard_grads(tags, d)
         end
     else
         _gps(f.fs) do gps, tags
-            GC.@preserve X yv U S gps gy gg check(ccall((:lmm_oilmm_logpdf_grad, liblmm), Cint,
-                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
-                 Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-                X, d, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, gy, gσ, C_NULL, C_NULL, gg))
+            if wantx
+                GC.@preserve X yv U S gps gy gg gx check(ccall((:lmm_oilmm_logpdf_grad_x, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
+                     Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}, Ptr{Cdouble}),
+                    X, d, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, gy, gσ, C_NULL, C_NULL, gg, gx))
+            else
+                GC.@preserve X yv U S gps gy gg check(ccall((:lmm_oilmm_logpdf_grad, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
+                     Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                    X, d, n, yv, m, U, S, m, σ², gps, 0, m, 0, val, gy, gσ, C_NULL, C_NULL, gg))
+            end
             gard = _ard_grads(tags, d)
         end
     end
     function logpdf_pullback(Δ)
-        dft = Tangent{typeof(ft)}(; f=Tangent{typeof(f)}(; fs=_fstangent(f.fs, gg, Δ, gard)), Σy=_noise_tangent(ft, Δ * gσ[]))
+        dx = _motangent(ft.x, gx === nothing ? nothing : Δ .* gx)
+        dft = Tangent{typeof(ft)}(; x=dx, f=Tangent{typeof(f)}(; fs=_fstangent(f.fs, gg, Δ, gard)), Σy=_noise_tangent(ft, Δ * gσ[]))
         return NoTangent(), dft, Δ .* gy
     end
     return val[], logpdf_pullback
@@ -738,6 +787,7 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
     X = _xmat(x); d, n = size(X); p, m = size(H); gard = nothing; Hm = Matrix{Float64}(H); yv = Vector{Float64}(y)
     val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
     gy = Vector{Float64}(undef, n * p); gH = Matrix{Float64}(undef, p, m); gg = Vector{LmmGpGrad}(undef, m)
+    wantx = INPUT_GRADIENTS[]; gx = wantx ? Matrix{Float64}(undef, d, n) : nothing
     if isposterior(f) && f.mix !== nothing
         # the latent view of a dense-H posterior (latent_view; reference src/ilmm.jl:39 on :196-197): here H = I_m, p = m, y = latent
         # observations; the conditioning batches were observed through f.mix.  d/d(mix) and the training cotangents have no slot in
@@ -745,38 +795,63 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
         f.train === nothing && error("gradient of the latent view after conditioning ON latent observations is not built")
         Hp = f.mix::Matrix{Float64}; pp = size(Hp, 1)
         X0, bn, bs, y0 = _merged_train(f.train, pp); n0 = size(X0, 2); gy0 = Vector{Float64}(undef, n0 * pp); gb = similar(bs)
-        gHp = Matrix{Float64}(undef, pp, m)
+        gHp = Matrix{Float64}(undef, pp, m); gx0 = wantx ? Matrix{Float64}(undef, d, n0) : nothing
         _gps(f.fs) do gps, tags
-            GC.@preserve X0 bn bs y0 X yv Hp gps gy0 gy gb gHp gg check(ccall((:lmm_ilmm_post_latent_logpdf_grad_seq, liblmm), Cint,
-                (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
-                 Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-                X0, d, n0, bn, bs, length(bn), y0, X, n, yv, pp, Hp, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gHp, gg))
+            if wantx
+                GC.@preserve X0 bn bs y0 X yv Hp gps gy0 gy gb gHp gg gx0 gx check(ccall((:lmm_ilmm_post_latent_logpdf_grad_seq_x, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
+                     Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    X0, d, n0, bn, bs, length(bn), y0, X, n, yv, pp, Hp, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gHp, gg, gx0, gx))
+            else
+                GC.@preserve X0 bn bs y0 X yv Hp gps gy0 gy gb gHp gg check(ccall((:lmm_ilmm_post_latent_logpdf_grad_seq, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
+                     Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                    X0, d, n0, bn, bs, length(bn), y0, X, n, yv, pp, Hp, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gHp, gg))
+            end
             gard = _ard_grads(tags, d)
         end
-        f.last_train_cotangents[] = merge(_split_train(gy0, gb, bn, pp), (H_train=gHp,))
+        f.last_train_cotangents[] = merge(_split_train(gy0, gb, bn, pp, gx0), (H_train=gHp,))
         fill!(gH, 0.0)
     elseif isposterior(f)
         f.train === nothing && error("this posterior does not carry its training data")
         X0, bn, bs, y0 = _merged_train(f.train, p); n0 = size(X0, 2); gy0 = Vector{Float64}(undef, n0 * p); gb = similar(bs)
+        gx0 = wantx ? Matrix{Float64}(undef, d, n0) : nothing
         _gps(f.fs) do gps, tags
-            GC.@preserve X0 bn bs y0 X yv Hm gps gy0 gy gb gH gg check(ccall((:lmm_ilmm_post_logpdf_grad_seq, liblmm), Cint,
-                (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
-                 Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-                X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gH, gg))
+            if wantx
+                GC.@preserve X0 bn bs y0 X yv Hm gps gy0 gy gb gH gg gx0 gx check(ccall((:lmm_ilmm_post_logpdf_grad_seq_x, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
+                     Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad},
+                     Ptr{Cdouble}, Ptr{Cdouble}),
+                    X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gH, gg, gx0, gx))
+            else
+                GC.@preserve X0 bn bs y0 X yv Hm gps gy0 gy gb gH gg check(ccall((:lmm_ilmm_post_logpdf_grad_seq, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cint}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint,
+                     Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                    X0, d, n0, bn, bs, length(bn), y0, X, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy0, gy, gb, gσ, gH, gg))
+            end
             gard = _ard_grads(tags, d)
         end
-        f.last_train_cotangents[] = _split_train(gy0, gb, bn, p)
+        f.last_train_cotangents[] = _split_train(gy0, gb, bn, p, gx0)
     else
         _gps(f.fs) do gps, tags
-            GC.@preserve X yv Hm gps gy gH gg check(ccall((:lmm_ilmm_logpdf_grad, liblmm), Cint,
-                (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble},
-                 Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
-                X, d, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy, gσ, gH, gg))
+            if wantx
+                GC.@preserve X yv Hm gps gy gH gg gx check(ccall((:lmm_ilmm_logpdf_grad_x, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble},
+                     Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}, Ptr{Cdouble}),
+                    X, d, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy, gσ, gH, gg, gx))
+            else
+                GC.@preserve X yv Hm gps gy gH gg check(ccall((:lmm_ilmm_logpdf_grad, liblmm), Cint,
+                    (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Ptr{LmmJitters}, Ref{Cdouble}, Ptr{Cdouble},
+                     Ref{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+                    X, d, n, yv, p, Hm, m, σ², gps, C_NULL, val, gy, gσ, gH, gg))
+            end
             gard = _ard_grads(tags, d)
         end
     end
     function logpdf_pullback(Δ)
-        dfx = Tangent{typeof(fx)}(; f=Tangent{typeof(fx.f)}(; f=Tangent{typeof(f)}(; fs=_fstangent(f.fs, gg, Δ, gard)), H=Δ .* gH),
+        dx = _motangent(fx.x, gx === nothing ? nothing : Δ .* gx)
+        dfx = Tangent{typeof(fx)}(; x=dx, f=Tangent{typeof(fx.f)}(; f=Tangent{typeof(f)}(; fs=_fstangent(f.fs, gg, Δ, gard)), H=Δ .* gH),
                                   Σy=_noise_tangent(fx, Δ * gσ[]))
         return NoTangent(), dfx, Δ .* gy
     end

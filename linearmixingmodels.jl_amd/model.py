@@ -494,6 +494,33 @@ def logpdf(fx: FiniteGP, y, with_regulariser: bool = True) -> float:
     return out.value
 
 
+def _x_buf(x):
+    """Output buffer of d logpdf / d x for the inputs x (d x n column-major, on the side of x.x)."""
+    return _alloc_like(x.x, x.dim * x.n)
+
+
+def _x_grad(g, xv):
+    """d logpdf / d x (d x n column-major, as the library writes it) in the shape and type of the inputs xv: (n,) or (d, n)."""
+    if len(xv.shape) == 1:
+        return g
+    n, d = int(xv.shape[-1]), int(xv.shape[0])
+    return g.reshape(n, d).T.contiguous() if L._is_torch(g) else np.ascontiguousarray(g.reshape(n, d).T)
+
+
+def _split_train_x(gx0, train, sizes):
+    """d/dx of the merged conditioning points back to one array per conditioning batch (shaped like that batch's inputs); a single
+    batch gets the array itself, in the type of its inputs (the rule of _split_train_grad)."""
+    if len(sizes) == 1:
+        return _x_grad(gx0, train[0][0].x)
+    g = np.asarray(gx0.cpu() if L._is_torch(gx0) else gx0)
+    d = g.size // sum(sizes)
+    g = g.reshape(-1, d)
+    out, o = [], 0
+    for t, nb in zip(train, sizes):
+        out.append(g[o:o + nb, 0].copy() if len(t[0].x.shape) == 1 else np.ascontiguousarray(g[o:o + nb].T)); o += nb
+    return out
+
+
 def _gps_grads(gg, ga, m: int, d: int) -> list:
     """The latents' kernel-parameter gradients: "lengthscale" is a float for an isotropic latent and, for a per-dimension (ARD) one,
     the length-d array d logpdf / d lengthscale_k (its tag's lmm_ard_grad: the array passes multiplier 1).  An RQ latent adds
@@ -507,7 +534,7 @@ def _gps_grads(gg, ga, m: int, d: int) -> list:
     return out
 
 
-def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True) -> dict:
+def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True, inputs: bool = False) -> dict:
     """Value and gradient of logpdf(fx, y) -- what `Zygote.gradient(logpdf, fx, y)` differentiates in the reference's tests
     (test/oilmm.jl:31-32, test/ilmm.jl:31-32, test/independent_mogp.jl:65-66).
 
@@ -519,6 +546,10 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True) -> dict:
                                       After sequential conditioning (equal noise variance per batch) "y_train" is a LIST with one
                                       by-outputs vector per conditioning batch, while "sigma2_train" stays ONE number: the derivative
                                       with respect to the variance the batches share (= the sum of the per-batch derivatives).
+    inputs=True adds the gradient with respect to the input locations (reference: Zygote differentiates through fx.x), shaped and
+    typed like the inputs ((n,) or (d, n); NumPy or torch): prior models gain "x"; posterior models gain "x" (d/d xs, the test inputs)
+    and "x_train" (d/d the conditioning inputs: a list with one array per batch after sequential conditioning, as "y_train").  It
+    costs one more read of each latent's K^-1; d <= 32.  With inputs=False the call and its keys are unchanged.
     Partial sums over the latent shard."""
     L.ensure_init()
     lib = L.load()
@@ -544,13 +575,18 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True) -> dict:
         gy, gH = _alloc_like(y if L._is_torch(y) else x.x, n * m), np.empty(p * m)
         gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
         gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.fs])
-        L.check(lib.lmm_ilmm_post_latent_logpdf_grad_seq(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
-                                                         L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
-                                                         None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
-                                                         L.Arr(gH, True).ptr, gg))
-        return {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
-                "sigma2_train": _train_noise_grad(gb, s2b), "H": gH.reshape(m, p).T.copy(),
-                "gps": _gps_grads(gg, ga, m, x.dim)}
+        gx0, gxs = (_x_buf(x0), _x_buf(x)) if inputs else (None, None)
+        fn = lib.lmm_ilmm_post_latent_logpdf_grad_seq_x if inputs else lib.lmm_ilmm_post_latent_logpdf_grad_seq
+        L.check(fn(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
+                   L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
+                   None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
+                   L.Arr(gH, True).ptr, gg, *((L.Arr(gx0, True).ptr, L.Arr(gxs, True).ptr) if inputs else ())))
+        out = {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
+               "sigma2_train": _train_noise_grad(gb, s2b), "H": gH.reshape(m, p).T.copy(),
+               "gps": _gps_grads(gg, ga, m, x.dim)}
+        if inputs:
+            out.update(x=_x_grad(gxs, x.x), x_train=_split_train_x(gx0, post.train, sizes))
+        return out
     if not mogp and not f.is_oilmm:
         unpack(fx)
         Ha, _, p, m = _H_args(f.H)
@@ -562,19 +598,29 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True) -> dict:
             x0, s2b, y0, sizes = _merged_train(post.train, p)
             bn, bs, gb = _batch_args(s2b, sizes)
             gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
-            L.check(lib.lmm_ilmm_post_logpdf_grad_seq(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
-                                                      L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
-                                                      None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
-                                                      L.Arr(gH, True).ptr, gg))
-            return {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
-                    "sigma2_train": _train_noise_grad(gb, s2b),
-                    "H": gH.reshape(m, p).T.copy(),
-                    "gps": _gps_grads(gg, ga, m, x.dim)}
-        L.check(lib.lmm_ilmm_logpdf_grad(x.carr().ptr, x.dim, n, L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2),
-                                         ga, None, C.byref(val), L.Arr(gy, True).ptr,
-                                         C.byref(gs2), L.Arr(gH, True).ptr, gg))
-        return {"value": val.value, "y": gy, "sigma2": gs2.value, "H": gH.reshape(m, p).T.copy(),
-                "gps": _gps_grads(gg, ga, m, x.dim)}
+            gx0, gxs = (_x_buf(x0), _x_buf(x)) if inputs else (None, None)
+            fn = lib.lmm_ilmm_post_logpdf_grad_seq_x if inputs else lib.lmm_ilmm_post_logpdf_grad_seq
+            L.check(fn(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
+                       L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
+                       None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
+                       L.Arr(gH, True).ptr, gg, *((L.Arr(gx0, True).ptr, L.Arr(gxs, True).ptr) if inputs else ())))
+            out = {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
+                   "sigma2_train": _train_noise_grad(gb, s2b),
+                   "H": gH.reshape(m, p).T.copy(),
+                   "gps": _gps_grads(gg, ga, m, x.dim)}
+            if inputs:
+                out.update(x=_x_grad(gxs, x.x), x_train=_split_train_x(gx0, post.train, sizes))
+            return out
+        gx = _x_buf(x) if inputs else None
+        fn = lib.lmm_ilmm_logpdf_grad_x if inputs else lib.lmm_ilmm_logpdf_grad
+        L.check(fn(x.carr().ptr, x.dim, n, L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2),
+                   ga, None, C.byref(val), L.Arr(gy, True).ptr,
+                   C.byref(gs2), L.Arr(gH, True).ptr, gg, *((L.Arr(gx, True).ptr,) if inputs else ())))
+        out = {"value": val.value, "y": gy, "sigma2": gs2.value, "H": gH.reshape(m, p).T.copy(),
+               "gps": _gps_grads(gg, ga, m, x.dim)}
+        if inputs:
+            out["x"] = _x_grad(gx, x.x)
+        return out
     if mogp:                      # gradient(logpdf, fx, y) on an IndependentMOGP (reference test/independent_mogp.jl:65-66):
         m = p = len(f.fs)         # the OILMM with U = I, S = 1 (regulariser identically 0, so it is skipped)
         if x.out_dim != m:
@@ -589,19 +635,29 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True) -> dict:
     gy, gS, gU = _alloc_like(y if L._is_torch(y) else x.x, n * p), np.empty(m), np.empty(p * m)
     gg, ga = (L.GpGradT * m)(), L.gps_array(descs)
     out = {}
+    gx = _x_buf(x) if inputs else None
     if post is None:
-        L.check(lib.lmm_oilmm_logpdf_grad(x.carr().ptr, x.dim, n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(s2),
-                                          ga, shard[0], shard[1], int(with_regulariser), C.byref(val),
-                                          L.Arr(gy, True).ptr, C.byref(gs2), L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg))
+        fn = lib.lmm_oilmm_logpdf_grad_x if inputs else lib.lmm_oilmm_logpdf_grad
+        L.check(fn(x.carr().ptr, x.dim, n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(s2),
+                   ga, shard[0], shard[1], int(with_regulariser), C.byref(val),
+                   L.Arr(gy, True).ptr, C.byref(gs2), L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg,
+                   *((L.Arr(gx, True).ptr,) if inputs else ())))
     else:
         x0, s2b, y0, sizes = _merged_train(post.train, p)
         bn, bs, gb = _batch_args(s2b, sizes)
         gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
-        L.check(lib.lmm_oilmm_post_logpdf_grad_seq(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
-                                                   L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(s2), ga, shard[0],
-                                                   shard[1], int(with_regulariser), C.byref(val), L.Arr(gy0, True).ptr,
-                                                   L.Arr(gy, True).ptr, gb, C.byref(gs2), L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg))
+        gx0 = _x_buf(x0) if inputs else None
+        fn = lib.lmm_oilmm_post_logpdf_grad_seq_x if inputs else lib.lmm_oilmm_post_logpdf_grad_seq
+        L.check(fn(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
+                   L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(s2), ga, shard[0],
+                   shard[1], int(with_regulariser), C.byref(val), L.Arr(gy0, True).ptr,
+                   L.Arr(gy, True).ptr, gb, C.byref(gs2), L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg,
+                   *((L.Arr(gx0, True).ptr, L.Arr(gx, True).ptr) if inputs else ())))
         out.update(y_train=_split_train_grad(gy0, sizes, p), sigma2_train=_train_noise_grad(gb, s2b))
+        if inputs:
+            out["x_train"] = _split_train_x(gx0, post.train, sizes)
+    if inputs:
+        out["x"] = _x_grad(gx, x.x)
     out.update({"value": val.value, "y": gy, "sigma2": gs2.value,
                 "gps": _gps_grads(gg, ga, m, x.dim)})
     if not mogp:
