@@ -431,6 +431,18 @@ int lmm_oilmm_mean_and_var(const lmm_post_t* post, const lmm_gp_t* gps,
                            const double* xs, int d, int ns, const lmm_jitters_t* jit,
                            double* mean_out, double* var_out);
 
+/* d/d xs of  sum(dmean .* mean) + sum(dvar .* var)  for the outputs of lmm_oilmm_mean_and_var (same post / gps / U / S / shard
+ * conventions; sigma2, add_noise and jitters are constants here).  dmean, dvar: ns*p by-outputs, either may be NULL (zero
+ * cotangent; dvar == NULL takes no triangular solve).  grad_xs: d x ns, the layout of xs.  Host or device pointers.  Partial sum
+ * over the shard.  post == NULL (prior): zeros.  d <= 32.  Dense-H posterior handles and the fp32 compute mode: LMM_ERR_UNSUPPORTED.
+ * Per latent l, with mbar_l = H' dmean, vbar_l = (H .* H)' dvar, alpha_l = K_l^-1 delta_l and W_l = K_l(xs, x) K_l^-1:
+ *     grad_xs[:, s] = sum_l sum_i (mbar_l[s] alpha_li - 2 vbar_l[s] W_l[s, i]) d kappa_l(xs_s, x_i) / d xs_s
+ * (DESIGN.md 4.11).  W_l = R_l L_l^-1 from the forward path's R_l = K_l(xs, x) L_l^-T by a right solve; Matern12 pairs at coincident
+ * points contribute 0.  IndependentMOGP posteriors use this entry point with U = I_m, S = NULL and p = m. */
+int lmm_oilmm_mean_and_var_grad_xs(const lmm_post_t* post, const lmm_gp_t* gps, const double* U, const double* S, int p, int m,
+                                   int latent_begin, int latent_end, const double* xs, int d, int ns,
+                                   const double* dmean, const double* dvar, double* grad_xs);
+
 /* mean_and_cov(fx) / cov(fx): reference src/ilmm.jl:132-139,147 (+ src/independent_mogp.jl:60-63 through H = I) for
  * independent latents (OILMM prior or posterior, dense-H prior with S == NULL):
  *   C[(o,i),(o',j)] = sum_l H[o,l] H[o',l] (Cov_l[i,j] + jitter [i==j]) + sigma2 [o==o', i==j],

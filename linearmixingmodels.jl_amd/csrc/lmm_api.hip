@@ -719,8 +719,9 @@ void potrf_rec(double* A, int ld, int NR, int j0, int w, double* W, int n_real, 
 // tri: R starts as the identity and becomes the upper triangular L^-T; rows below the current column block are still
 // zero and are skipped (~n^3/3 flops instead of n^3 for a rectangular solve).
 // The same solve for a batch of (R_j, L_j, W_j) of identical shapes in lock-step launches (blockIdx.y = matrix).
+// det: no split-K in the updates (bitwise reproducible; the predictive-marginal gradients)
 void trsm_rec(const BatchPtr& R, int ldr, int nr, const BatchPtr& L, int ld, const BatchPtr& W, int nb, int j0, int w,
-              hipStream_t st, bool tri = false, bool top = true) {
+              hipStream_t st, bool tri = false, bool top = true, bool det = false) {
   if (top)
     for (int j = 0; j < nb; ++j) {
       guard_extent(R.p[j], nr, ldr, (size_t)j0 + w, true, "batched triangular solve (R)");
@@ -734,7 +735,7 @@ void trsm_rec(const BatchPtr& R, int ldr, int nr, const BatchPtr& L, int ld, con
     return;
   }
   const int h = split(w);
-  trsm_rec(R, ldr, nr, L, ld, W, nb, j0, h, st, tri, false);
+  trsm_rec(R, ldr, nr, L, ld, W, nb, j0, h, st, tri, false, det);
   const int rows = tri ? std::min(nr, j0 + h) : nr;
   {
     // R[:, j0+h : j0+w] -= R[:, j0 : j0+h] L[j0+h : j0+w, j0 : j0+h]': 2 rows (w - h) h flops; bytes: the target block read + written,
@@ -742,9 +743,9 @@ void trsm_rec(const BatchPtr& R, int ldr, int nr, const BatchPtr& L, int ld, con
     const double r = rows, c = w - h, k = h;
     ProfScope ps(LMM_PROF_SOLVE, (double)nb * 2.0 * r * c * k, st, rows, w - h, h, (double)nb * (16.0 * r * c + 8.0 * r * k + 8.0 * c * k));
     launch_gemm_nt(R, (size_t)(j0 + h) * ldr, ldr, R, (size_t)j0 * ldr, ldr, L, (size_t)j0 * ld + (j0 + h), ld, rows, w - h, h, 0, false,
-                   nb, st);
+                   nb, st, det);
   }
-  trsm_rec(R, ldr, nr, L, ld, W, nb, j0 + h, w - h, st, tri, false);
+  trsm_rec(R, ldr, nr, L, ld, W, nb, j0 + h, w - h, st, tri, false, det);
 }
 
 // One matrix: the batch of one (element offsets are applied inside the kernels in units of the storage type, so the solve is
@@ -753,6 +754,28 @@ void trsm_rec(double* R, int ldr, int nr, const double* L, int ld, const double*
   BatchPtr Rb{}, Lb{}, Wb{};
   Rb.p[0] = R; Lb.p[0] = const_cast<double*>(L); Wb.p[0] = const_cast<double*>(W);
   trsm_rec(Rb, ldr, nr, Lb, ld, Wb, 1, j0, w, st, tri);
+}
+
+// R (nr x NC, ldr) <- R * L^-1 for an already factored L (ld) with inverse diagonal blocks W, batched as trsm_rec (predictive-marginal
+// gradients: W = K(x*, x) K^-1 from the forward path's R = K(x*, x) L^-T).  X L = R is solved from the right: with L = [L11 0; L21 L22]
+// on the columns [j0, j0 + w), X2 = R2 L22^-1, then R1 -= X2 L21 (L21 = L[j0+h :, j0 : j0+h] read as it lies: an NN product), then
+// X1 = R1 L11^-1; the 64-column leaves are R_J W_J.  n^2 nr flops, the same as the forward solve.
+void trsm_right_rec(const BatchPtr& R, int ldr, int nr, const BatchPtr& L, int ld, const BatchPtr& W, int nb, int j0, int w,
+                    hipStream_t st, bool top = true) {
+  if (top)
+    for (int j = 0; j < nb; ++j) {
+      guard_extent(R.p[j], nr, ldr, (size_t)j0 + w, true, "batched right triangular solve (R)");
+      guard_extent(L.p[j], (size_t)j0 + w, ld, (size_t)j0 + w, true, "batched right triangular solve (L)");
+      guard_extent(W.p[j], 64, 64, (size_t)((j0 + w) / 64) * 64, true, "batched right triangular solve (inverse blocks)");
+    }
+  if (w <= 64) {
+    launch_trsm_nn(R, (size_t)j0 * ldr, ldr, R, (size_t)j0 * ldr, ldr, W, (size_t)(j0 / 64) * 4096, 64, nr, 64, 64, true, nb, st);
+    return;
+  }
+  const int h = split(w);
+  trsm_right_rec(R, ldr, nr, L, ld, W, nb, j0 + h, w - h, st, false);
+  launch_trsm_nn(R, (size_t)j0 * ldr, ldr, R, (size_t)(j0 + h) * ldr, ldr, L, (size_t)j0 * ld + (j0 + h), ld, nr, h, w - h, false, nb, st);
+  trsm_right_rec(R, ldr, nr, L, ld, W, nb, j0, h, st, false);
 }
 
 // alpha (in place over z = L^-1 delta) <- L^-T z for one factor matrix
@@ -3313,6 +3336,119 @@ int lmm_oilmm_mean_and_var(const lmm_post_t* post, const lmm_gp_t* gps, const do
   mix_marginals(ml.p, ns, ms, Hd.buf.p, p, 1, 0.0, 0.0, mo.p, st0);
   if (var_out) mix_marginals(vl.p, ns, ms, Hd.buf.p, p, 2, jit->default_jitter, add_noise ? sigma2 : 0.0, vo.p, st0);
   mo.finish(st0); vo.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// d/d xs (gout, d x ns, device) of sum_s mbar_l[s] mean_l(xs_s) + vbar_l[s] var_l(xs_s) summed over the posterior's ms latents
+// (DESIGN.md 4.11).  mbar, vbar: ns x ms (column = latent of the shard); vbar == nullptr: the mean-only form (no cross Gram, no solve).
+// The full form reuses latent_marginals_dev's batching: cross Gram, R = K(x*, x) L^-T (trsm_rec), W = R L^-1 (trsm_right_rec) on the
+// same R buffers, then the pair pass per latent into its slot's accumulator; the slot accumulators are added in slot order after the
+// join, so the result does not depend on stream timing.  Caller holds g_mu.
+static int mean_var_grad_xs_dev(const lmm_post* P, int ms, const double* xsd, int d, int ns, const double* mbar, const double* vbar,
+                                double* gout) {
+  hipStream_t st0 = g.streams[0];
+  const size_t count = (size_t)d * ns;
+  if (vbar == nullptr) {
+    Buf<double> part(pred_grad_x_partial_elems(P->n, ns, d));
+    for (int k = 0; k < ms; ++k)
+      launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, nullptr, nullptr, 0,
+                         to_dev(P->gps[P->l0 + k]), part.p, gout, k > 0, st0);
+    HIPCHK(hipStreamSynchronize(st0));
+    return LMM_OK;
+  }
+  const int nsr = rup(ns, 64);
+  int ldr = nsr; if ((ldr % 512) == 0) ldr += 16;
+  int nb_per = 1, nslots = 1;
+  batch_plan(ms, &nb_per, &nslots, mat_bytes((double)ldr * P->NC));
+  std::vector<std::vector<Buf<double>>> R(nslots);
+  std::vector<Buf<double>> part, acc;
+  for (int s = 0; s < nslots; ++s) {
+    for (int j = 0; j < nb_per; ++j) R[s].emplace_back(mat_count((size_t)ldr * P->NC));
+    part.emplace_back(pred_grad_x_partial_elems(P->n, ns, d));
+    acc.emplace_back(count);
+  }
+  std::vector<char> used(nslots, 0);
+  fork_slots(nslots);
+  int bi = 0;
+  for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
+    const int s = bi % nslots, nb = std::min(nb_per, ms - k0);
+    hipStream_t st = g.streams[s];
+    BatchPtr Rb{}, Lb{}, Wb{};
+    GramArgs ga[LMM_MAX_BATCH];
+    for (int j = 0; j < nb; ++j) {
+      const int k = k0 + j;
+      ga[j] = cross_gram_args(P, P->gps[P->l0 + k], xsd, d, ns, R[s][j].p, ldr, nsr);
+      Rb.p[j] = R[s][j].p; Lb.p[j] = P->L[k].p; Wb.p[j] = P->W[k].p;
+    }
+    gram_batch_g(ga, nb, st);
+    trsm_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st, false, true, true);   // R_j <- K(x*, x) L_j^-T, no split-K
+    trsm_right_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st);    // R_j <- R_j L_j^-1 = K(x*, x) K_j^-1
+    for (int j = 0; j < nb; ++j) {
+      const int k = k0 + j;
+      launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, vbar + (size_t)k * ns, R[s][j].p, ldr,
+                         to_dev(P->gps[P->l0 + k]), part[s].p, acc[s].p, used[s] != 0, st);
+      used[s] = 1;
+    }
+  }
+  join_slots(nslots);
+  bool first = true;
+  for (int s = 0; s < nslots; ++s) {
+    if (!used[s]) continue;
+    if (first) HIPCHK(hipMemcpyAsync(gout, acc[s].p, count * sizeof(double), hipMemcpyDeviceToDevice, st0));
+    else launch_vec_axpby(gout, 1.0, acc[s].p, 1.0, count, gout, st0);
+    first = false;
+  }
+  HIPCHK(hipStreamSynchronize(st0));   // R buffers are released on return
+  return LMM_OK;
+}
+
+int lmm_oilmm_mean_and_var_grad_xs(const lmm_post_t* post, const lmm_gp_t* gps, const double* U, const double* S, int p, int m,
+                                   int latent_begin, int latent_end, const double* xs, int d, int ns,
+                                   const double* dmean, const double* dvar, double* grad_xs) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "gradients of the predictive marginals are served in the Float64 compute mode only");
+  if (!U || !xs || !grad_xs || d <= 0 || ns <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (post && post->kind != 0)
+    return fail(LMM_ERR_UNSUPPORTED, "gradients of the predictive marginals of a dense-H posterior (coupled latents) are not served");
+  if (int rc = input_grad_check(d, true)) return rc;
+  int l0 = latent_begin, l1 = latent_end;
+  CallGps cg_;
+  if (post) {
+    l0 = post->l0; l1 = post->l1;
+    if (post->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", post->m, m);
+    if (post->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, xs has d=%d", post->d, d);
+  } else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
+  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
+  const int ms = l1 - l0;
+  hipStream_t st0 = g.streams[0];
+  const size_t count = (size_t)d * ns;
+  DevOut go(grad_xs, count);
+  // prior latents: constant means and variances kappa(0); no cotangent, no latent, no work
+  if (!post || ms == 0 || (!dmean && !dvar)) {
+    HIPCHK(hipMemsetAsync(go.p, 0, count * sizeof(double), st0));
+    go.finish(st0);
+    HIPCHK(hipStreamSynchronize(st0));
+    return LMM_OK;
+  }
+  // latent cotangents on the device: mbar = dmean H_s, vbar = dvar (H_s .* H_s)   (ns x ms; H_s the shard's columns of U sqrt(S))
+  std::vector<double> HT((size_t)ms * p), H2T((size_t)ms * p);
+  for (int k = 0; k < ms; ++k)
+    for (int o = 0; o < p; ++o) {
+      const double h = U[o + (size_t)(l0 + k) * p] * (S ? std::sqrt(S[l0 + k]) : 1.0);
+      HT[k + (size_t)o * ms] = h; H2T[k + (size_t)o * ms] = h * h;
+    }
+  Uploaded HTd(HT, st0), H2Td(H2T, st0);
+  DevIn xsd(xs, count, st0), dmd(dmean, (size_t)ns * p, st0), dvd(dvar, (size_t)ns * p, st0);
+  Buf<double> mbar((size_t)ns * ms), vbar(dvar ? (size_t)ns * ms : 1);
+  if (dmean) launch_tall_skinny(dmd.p, ns, ns, p, HTd.buf.p, ms, ms, mbar.p, ns, nullptr, nullptr, 0, nullptr, 0, st0);
+  else HIPCHK(hipMemsetAsync(mbar.p, 0, (size_t)ns * ms * sizeof(double), st0));
+  if (dvar) launch_tall_skinny(dvd.p, ns, ns, p, H2Td.buf.p, ms, ms, vbar.p, ns, nullptr, nullptr, 0, nullptr, 0, st0);
+  if (int rc = mean_var_grad_xs_dev(post, ms, xsd.p, d, ns, mbar.p, dvar ? vbar.p : nullptr, go.p)) return rc;
+  go.finish(st0);
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
   LMM_CATCH

@@ -143,8 +143,9 @@ bool launch_gemm32w(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
                     int M, int N, int K, int lower, int nb, int cus, bool deterministic, hipStream_t st);
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,
                    const BatchInfo& info, int nb, hipStream_t st);
+// no_splitk: never split the last round's tiles along K (their f64 atomics make the sum order run-dependent): bitwise reproducible
 void launch_gemm_nt(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B,
-                    size_t offB, int ldb, int M, int N, int K, int lower, bool set, int nb, hipStream_t st);
+                    size_t offB, int ldb, int M, int N, int K, int lower, bool set, int nb, hipStream_t st, bool no_splitk = false);
 void launch_gemm_nt(double* C, int ldc, const double* A, int lda, const double* B, int ldb, int M, int N, int K,
                     int lower, bool set, hipStream_t st);
 void launch_lml_reduce(const double* A, int ld, int n, int rider_row0, int nrhs, double* out, hipStream_t st);
@@ -189,6 +190,16 @@ void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const dou
 size_t grad_x_partial_elems(int n, int d);
 void launch_grad_x(const double* Kinv, int ld, int n, const double* alpha, const double* x, int d, LatentDev g, double* partial,
                    double* gx, bool accumulate, hipStream_t st);
+// Predictive-marginal input gradients.  C (M x N) {=, -=} A (M x K) B (K x N), NN form (trsm_nn_kernel): the products
+// of the right solve R <- R L^-1; set = true is the in-place 64-column leaf (C == A, N = K = 64).
+void launch_trsm_nn(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B, size_t offB,
+                    int ldb, int M, int N, int K, bool set, int nb, hipStream_t st);
+// gx (d x ns) {=, +=} d/d xs of sum_s mbar_s mean_l(xs_s) + vbar_s var_l(xs_s) for one latent (pred_grad_x_kernel): W = R L^-1 (ns rows,
+// ldw), or nullptr for the mean-only form.  partial: pred_grad_x_partial_elems(n, ns, d) doubles.  d <= LMM_ARD_GRAD_DMAX.
+size_t pred_grad_x_partial_elems(int n, int ns, int d);
+void launch_pred_grad_x(const double* xs, int ns, const double* x, int n, int d, const double* alpha, const double* mbar,
+                        const double* vbar, const double* W, int ldw, LatentDev g, double* partial, double* gx, bool accumulate,
+                        hipStream_t st);
 void launch_vec_axpby(const double* a, double sa, const double* b, double sb, size_t n, double* out, hipStream_t st);
 void launch_block_trace(const double* Minv, int ld, int n, int m, int i0, int i1, double* out, hipStream_t st);   // points i0..i1-1
 // Consecutive point ranges [off[b], off[b + 1]) that carry the observation-noise variance s2[b]: the conditioning batches of a

@@ -3711,6 +3711,177 @@ __global__ void grad_x_finish_kernel(const double* __restrict__ partial, int nch
   out[e] = accumulate ? out[e] + s : s;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Right solve by L^-1 (predictive-marginal gradients): C (M x N) {=, -=} A (M x K) * B (K x N), column-major, NN form,
+// batched over up to LMM_MAX_BATCH matrices (blockIdx.y), on v_mfma_f64_16x16x4_f64.  M, N multiples of 64, K of 16.
+//   SET = true : the 64-column leaf X_J = R_J W_J by a stored inverse diagonal block, IN PLACE (C == A): a workgroup owns all N = 64
+//                columns of its rows, and every global read of A has landed in LDS before the last barrier of the k loop, i.e. before
+//                the first store.
+//   SET = false: the update R_1 -= X_2 L_21 with L_21 read as it lies in the lower triangle of the factor.
+// 128 x BN workgroup tile, 4 waves (2 x 2, wave tile 64 x BN/2), BK = 16, two LDS stages with the next tile's global loads in
+// registers while the current one is multiplied (one barrier per stage).  A is staged k-major ([k][row], contiguous 16-B loads along
+// a column); B column-major as [col][k] with an odd stride (17 doubles), so the fragment reads (16 columns x 4 k per instruction)
+// fall on distinct banks.  Operand maps as in gemm16p_kernel: the first MFMA operand carries 16 columns of C, the second 16 rows,
+// so lane l holds C[row 16u + (l & 15)][col 16v + (l >> 4) + 4 r] in register r of acc[v][u].
+template <int BN, bool SET>
+__global__ __launch_bounds__(256, 2) void trsm_nn_kernel(BatchPtr Cb, size_t goffC, int ldc, BatchPtr Ab, size_t goffA, int lda,
+                                                         BatchPtr Bb, size_t goffB, int ldb, int M, int N, int K, int MT) {
+  double* C = Cb.p[blockIdx.y] + goffC;
+  const double* A = Ab.p[blockIdx.y] + goffA;
+  const double* B = Bb.p[blockIdx.y] + goffB;
+  constexpr int BM = 128, BK = 16, SA = BM + 16, SB = BK + 1;
+  constexpr int TV = BN / 32;                    // 16-column blocks per wave
+  constexpr int NQB = BN / 16;                   // B staging passes: 16 columns x 16 k per pass
+  __shared__ __attribute__((aligned(16))) double As[2][BK * SA];
+  __shared__ double Bs[2][BN * SB];
+  const int ti = blockIdx.x % MT, tj = blockIdx.x / MT;
+  const int bm = ti * BM, bn = tj * BN;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int wr = (w & 1) * 64, wc = (w >> 1) * (BN / 2);
+  const bool active = (bm + wr < M) && (bn + wc < N);
+  // staging: A rows 2 (t % 64) .. of k-columns t / 64 + 4 q; B column t / 16 + 16 q, k = t % 16
+  int rowa = bm + 2 * (t & 63); if (rowa > M - 2) rowa = M - 2;
+  const double* ga0 = A + (size_t)(t >> 6) * lda + rowa;
+  const int sa0 = (t >> 6) * SA + 2 * (t & 63);
+  const int kb = t & 15;
+  const double* gb[NQB];
+#pragma unroll
+  for (int q = 0; q < NQB; ++q) {
+    int col = bn + (t >> 4) + 16 * q; if (col > N - 1) col = N - 1;
+    gb[q] = B + (size_t)col * ldb + kb;
+  }
+  d2 ra[4];
+  double rb[NQB];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) ra[q] = *reinterpret_cast<const d2*>(ga0 + (size_t)(4 * q) * lda);
+#pragma unroll
+  for (int q = 0; q < NQB; ++q) rb[q] = gb[q][0];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) *reinterpret_cast<d2*>(&As[0][sa0 + 4 * q * SA]) = ra[q];
+#pragma unroll
+  for (int q = 0; q < NQB; ++q) Bs[0][((t >> 4) + 16 * q) * SB + kb] = rb[q];
+  __syncthreads();
+
+  d4 acc[TV][4];
+#pragma unroll
+  for (int v = 0; v < TV; ++v)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[v][u] = (d4){0.0, 0.0, 0.0, 0.0};
+  const int l15 = lane & 15, lk = lane >> 4;
+  const int offA = lk * SA + wr + l15, offB = (wc + l15) * SB + lk;
+  const int nk = K / BK;
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nk) {
+      const size_t ka = (size_t)(kt + 1) * BK;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ra[q] = *reinterpret_cast<const d2*>(ga0 + (ka + 4 * q) * lda);
+#pragma unroll
+      for (int q = 0; q < NQB; ++q) rb[q] = gb[q][ka];
+    }
+    if (active) {
+      const double* as = &As[buf][0];
+      const double* bs = &Bs[buf][0];
+#pragma unroll
+      for (int s4 = 0; s4 < BK / 4; ++s4) {
+        double fa[4], fb[TV];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) fa[u] = as[offA + 4 * s4 * SA + 16 * u];
+#pragma unroll
+        for (int v = 0; v < TV; ++v) fb[v] = bs[offB + 16 * v * SB + 4 * s4];
+#pragma unroll
+        for (int v = 0; v < TV; ++v)
+#pragma unroll
+          for (int u = 0; u < 4; ++u) acc[v][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[v], fa[u], acc[v][u], 0, 0, 0);
+      }
+    }
+    if (kt + 1 < nk) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) *reinterpret_cast<d2*>(&As[buf ^ 1][sa0 + 4 * q * SA]) = ra[q];
+#pragma unroll
+      for (int q = 0; q < NQB; ++q) Bs[buf ^ 1][((t >> 4) + 16 * q) * SB + kb] = rb[q];
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+#pragma unroll
+  for (int v = 0; v < TV; ++v) {
+    double* cpv = C + (size_t)(bn + wc + 16 * v + lk) * ldc + bm + wr + l15;
+    if (SET) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cpv[(size_t)(4 * r) * ldc + 16 * u] = acc[v][u][r];
+    } else {
+      double cv[4][4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cv[u][r] = cpv[(size_t)(4 * r) * ldc + 16 * u];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cpv[(size_t)(4 * r) * ldc + 16 * u] = cv[u][r] - acc[v][u][r];
+    }
+  }
+}
+
+// Input gradient of the predictive marginals, one latent: with c_sj = mbar_s alpha_j - 2 vbar_s W[s, j],
+// t_k = (xs_sk - x_jk) / l_k and h(r) of ard_pair,
+//     d/d xs_sk  sum_j c_sj kappa(xs_s, x_j) = -(1 / l_k) sum_j c_sj h(r_sj) t_k.
+// A thread per test point s (W is column-major with the test point on the row, so a wave reads 64 consecutive doubles of a column);
+// workgroup (sb, c) takes 256 test points against the training points [c chunk, (c + 1) chunk), staged in LDS (JS at a time).  VAR =
+// false: the mean-only form (no W).  No atomics: partial[(c ns + s) d + k] holds the chunk's sum, grad_x_finish_kernel adds the
+// chunks in order.  Matern12 pairs at coincident points contribute 0 (ard_pair's h = 0; t_k is formed difference first).
+template <int DK, bool EXT, bool VAR>
+__global__ __launch_bounds__(256) void pred_grad_x_kernel(const double* __restrict__ xs, int ns, const double* __restrict__ x, int n,
+                                                          int d, int chunk, const double* __restrict__ alpha,
+                                                          const double* __restrict__ mbar, const double* __restrict__ vbar,
+                                                          const double* __restrict__ Wm, int ldw, LatentDev g,
+                                                          double* __restrict__ partial) {
+  constexpr int JS = DK > 8 ? 128 : 256;        // training points per LDS stage (DK = 32: 32 KiB of coordinates)
+  __shared__ double sils[DK];
+  __shared__ double sx[JS * DK];
+  __shared__ double sa[JS];
+  const int t = threadIdx.x, s = blockIdx.x * 256 + t, c = blockIdx.y;
+  if (t < DK) sils[t] = (t < d) ? (g.ils ? g.ils[t] : g.inv_ls) : 0.0;
+  const bool ok = s < ns;
+  double xv[DK], acc[DK];
+#pragma unroll
+  for (int k = 0; k < DK; ++k) { xv[k] = (ok && k < d) ? xs[(size_t)s * d + k] : 0.0; acc[k] = 0.0; }
+  const double mb = ok ? mbar[s] : 0.0;
+  const double vb2 = (VAR && ok) ? -2.0 * vbar[s] : 0.0;
+  const int j0 = c * chunk, j1 = min(j0 + chunk, n);
+  for (int jb = j0; jb < j1; jb += JS) {
+    const int nj = min(JS, j1 - jb);
+    __syncthreads();
+    for (int e = t; e < nj * d; e += 256) { const int jl = e / d, k = e - jl * d; sx[jl * DK + k] = x[(size_t)(jb + jl) * d + k]; }
+    if (t < nj) sa[t] = alpha[jb + t];
+    __syncthreads();
+    if (!ok) continue;
+    const double* wp = VAR ? Wm + (size_t)jb * ldw + s : nullptr;
+    constexpr int UNR = DK > 8 ? 1 : 4;         // DK = 32: the t_k of one pair already fill the register budget
+#pragma unroll UNR
+    for (int jl = 0; jl < nj; ++jl) {
+      double tk[DK], r2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < DK; ++k) {
+        tk[k] = (k < d) ? (xv[k] - sx[jl * DK + k]) * sils[k] : 0.0;     // difference first: exactly 0 at coincident points
+        r2 = __builtin_fma(tk[k], tk[k], r2);
+      }
+      const double w = VAR ? __builtin_fma(vb2, wp[(size_t)jl * ldw], mb * sa[jl]) : mb * sa[jl];
+      double a0 = 0.0, ak = 0.0, aa = 0.0, wh;
+      ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, a0, ak, aa, wh);      // only wh = w h(r) is used
+#pragma unroll
+      for (int k = 0; k < DK; ++k) acc[k] = __builtin_fma(wh, tk[k], acc[k]);
+    }
+  }
+  if (!ok) return;
+#pragma unroll
+  for (int k = 0; k < DK; ++k)
+    if (k < d) partial[((size_t)c * ns + s) * d + k] = -acc[k] * sils[k];
+}
+
 // out[l + l2*m] = sum_i Minv[(l n + i), (l2 n + i)]  for l >= l2 (mirrored into l < l2): the m x m matrix of traces of the diagonals of
 // the n x n blocks of a symmetric (m n) x (m n) matrix whose lower triangle is stored (dense-H ILMM gradient: dL/dSigmaT).
 template <typename TS>
@@ -4240,7 +4411,7 @@ void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, si
 
 int g_f32_sched = 0;      // tools/gemm32_ab: 1 = sched_group_barrier-pinned interleave in the fp32 update kernel
 void launch_gemm_nt(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B,
-                    size_t offB, int ldb, int M, int N, int K, int lower, bool set, int nb, hipStream_t st) {
+                    size_t offB, int ldb, int M, int N, int K, int lower, bool set, int nb, hipStream_t st, bool no_splitk) {
   if (M <= 0 || N <= 0 || K <= 0 || nb <= 0) return;
   const bool narrow = (N <= 64);
   const int MT = (M + 127) / 128;
@@ -4254,7 +4425,7 @@ void launch_gemm_nt(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
   // f64 wide update with a ragged last row tile (M an odd multiple of 64, the last 64 rows below every column): the main grid takes
   // the full 128-row tiles, gemm16h_kernel the last 64 rows
   if (!g_f32 && !narrow && (M % 128) == 64 && M - 64 >= N && M > 64 && (N % 128) == 0 && K >= 1024) {   // below K ~ 1000 the extra launch costs more than the idle waves
-    launch_gemm_nt(C, offC, ldc, A, offA, lda, B, offB, ldb, M - 64, N, K, lower, false, nb, st);
+    launch_gemm_nt(C, offC, ldc, A, offA, lda, B, offB, ldb, M - 64, N, K, lower, false, nb, st, no_splitk);
     hipLaunchKernelGGL((gemm16h_kernel<true>), dim3(N / 128, nb), dim3(256), 0, st, C, offC + (size_t)(M - 64), ldc, A, offA + (size_t)(M - 64), lda,
                        B, offB, ldb, N, K, 0);
     return;
@@ -4291,7 +4462,7 @@ void launch_gemm_nt(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
   const int R = (int)(T - full_items);
   static int deterministic = -1;          // LMM_DETERMINISTIC=1: no split-K atomics (bitwise reproducible, slower tail)
   if (deterministic < 0) { const char* e = getenv("LMM_DETERMINISTIC"); deterministic = (e && atoi(e) != 0) ? 1 : 0; }
-  if (!deterministic && R > 0 && R <= slots / 2 && nk >= 8) {
+  if (!deterministic && !no_splitk && R > 0 && R <= slots / 2 && nk >= 8) {
     splitk = slots / R; if (splitk > nk / 4) splitk = nk / 4; if (splitk < 1) splitk = 1;
   }
   if (splitk == 1) full_items = (int)T;
@@ -4550,4 +4721,50 @@ void launch_normals(unsigned long long seed, unsigned long long stream, size_t c
 
 void launch_mfma_peak(double* out, int blocks, int iters, hipStream_t st) {
   hipLaunchKernelGGL(mfma_f64_peak_kernel, dim3(blocks), dim3(256), 0, st, out, iters);
+}
+
+// ---- predictive-marginal input gradients -------------------------------------------------------------------------
+// C {=, -=} A B (NN form) for the right solve R <- R L^-1: set = true the in-place leaf (N = K = 64), else the update.
+void launch_trsm_nn(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B, size_t offB,
+                    int ldb, int M, int N, int K, bool set, int nb, hipStream_t st) {
+  if (M <= 0 || N <= 0 || K <= 0 || nb <= 0) return;
+  const int MT = (M + 127) / 128;
+  if (set) {
+    hipLaunchKernelGGL((trsm_nn_kernel<64, true>), dim3(MT * ((N + 63) / 64), nb), dim3(256), 0, st, C, offC, ldc, A, offA, lda, B, offB,
+                       ldb, M, N, K, MT);
+    return;
+  }
+  hipLaunchKernelGGL((trsm_nn_kernel<128, false>), dim3(MT * ((N + 127) / 128), nb), dim3(256), 0, st, C, offC, ldc, A, offA, lda, B,
+                     offB, ldb, M, N, K, MT);
+}
+
+// training points per workgroup of pred_grad_x_kernel: a multiple of 256, at most 64 chunks (the partial buffer is chunks x ns x d)
+static int pred_grad_chunk(int n) { const int st = (n + 255) / 256; return 256 * ((st + 63) / 64); }
+size_t pred_grad_x_partial_elems(int n, int ns, int d) {
+  const int ch = pred_grad_chunk(n);
+  return (size_t)((n + ch - 1) / ch) * ns * d;
+}
+
+void launch_pred_grad_x(const double* xs, int ns, const double* x, int n, int d, const double* alpha, const double* mbar,
+                        const double* vbar, const double* W, int ldw, LatentDev g, double* partial, double* gx, bool accumulate,
+                        hipStream_t st) {
+  const int chunk = pred_grad_chunk(n), nch = (n + chunk - 1) / chunk;
+  const bool ext = g.kind >= LMM_KERNEL_MATERN12, var = W != nullptr;
+  const dim3 grid((ns + 255) / 256, nch);
+#define LMM_PGX_LAUNCH(DK, EXT)                                                                                                   \
+  do {                                                                                                                            \
+    if (var) hipLaunchKernelGGL((pred_grad_x_kernel<DK, EXT, true>), grid, dim3(256), 0, st, xs, ns, x, n, d, chunk, alpha, mbar,  \
+                                vbar, W, ldw, g, partial);                                                                        \
+    else hipLaunchKernelGGL((pred_grad_x_kernel<DK, EXT, false>), grid, dim3(256), 0, st, xs, ns, x, n, d, chunk, alpha, mbar,    \
+                            vbar, W, ldw, g, partial);                                                                            \
+  } while (0)
+#define LMM_PGX_DK(DK) do { if (ext) LMM_PGX_LAUNCH(DK, true); else LMM_PGX_LAUNCH(DK, false); } while (0)
+  if (d == 1) LMM_PGX_DK(1);
+  else if (d <= 4) LMM_PGX_DK(4);
+  else if (d <= 8) LMM_PGX_DK(8);
+  else LMM_PGX_DK(LMM_ARD_GRAD_DMAX);
+#undef LMM_PGX_DK
+#undef LMM_PGX_LAUNCH
+  const size_t count = (size_t)ns * d;
+  hipLaunchKernelGGL(grad_x_finish_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, partial, nch, count, accumulate ? 1 : 0, gx);
 }

@@ -858,6 +858,70 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
     return val[], logpdf_pullback
 end
 
+# ---- gradients of the predictive marginals w.r.t. the test inputs ---------------------------------------------------------------
+# mean_and_var / mean / var of independent latents (OILMM prior or posterior, dense-H prior, IndependentMOGP through U = I, S = NULL):
+# lmm_oilmm_mean_and_var_grad_xs returns d/dx* of sum(Δm .* mean) + sum(Δv .* var).  An AbstractZero cotangent goes in as C_NULL, so
+# mean's rule takes no triangular solve.  The parameter cotangents of the predictive marginals are not built (@not_implemented).
+# marginals(fx) goes through mean_and_var in AbstractGPs, so it needs no rule of its own.
+const _MVFinite = Union{ByOutputsFill{HIPOILMM},ByOutputsFill{HIPMOGP},ByFeaturesFill{HIPMOGP},ByOutputsFill{HIPDenseILMM}}
+_cot(Δ) = Δ isa AbstractZero ? nothing : Vector{Float64}(unthunk(Δ))
+_motangent(x::MOInputIsotopicByFeatures, G) = G === nothing ? NoTangent() : Tangent{typeof(x)}(; x=_xtangent(x.x, G), out_dim=NoTangent())
+function _mean_var_grad_xs(f::HIPMOGP, U, S, p, m, X, Δm, Δv)
+    d, ns = size(X); G = Matrix{Float64}(undef, d, ns)
+    pm = Δm === nothing ? Ptr{Cdouble}(C_NULL) : pointer(Δm); pv = Δv === nothing ? Ptr{Cdouble}(C_NULL) : pointer(Δv)
+    _gps(isposterior(f) ? nothing : f.fs) do gps, tags
+        GC.@preserve X U S gps Δm Δv G check(ccall((:lmm_oilmm_mean_and_var_grad_xs, liblmm), Cint,
+            (Ptr{Cvoid}, Ptr{LmmGp}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Cint, Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble},
+             Ptr{Cdouble}, Ptr{Cdouble}),
+            f.handle, isposterior(f) ? Ptr{LmmGp}(C_NULL) : pointer(gps), U, _ptr(S), p, m, 0, m, X, d, ns, pm, pv, G))
+    end
+    return G
+end
+function _grad_xs(fx::Union{ByOutputsFill{HIPOILMM},ByOutputsFill{HIPDenseILMM}}, Δm, Δv)
+    f, H, σ², x = unpack(fx)
+    U, S, p, m = _hargs(H)
+    return _mean_var_grad_xs(f, U, S, p, m, _xmat(x), Δm, Δv)
+end
+function _grad_xs(ft::ByOutputsFill{HIPMOGP}, Δm, Δv)
+    m = length(ft.f.fs)
+    return _mean_var_grad_xs(ft.f, Matrix{Float64}(I, m, m), nothing, m, m, _xmat(ft.x.x), Δm, Δv)
+end
+function _grad_xs(ft::ByFeaturesFill{HIPMOGP}, Δm, Δv)      # the marginals are permuted by-outputs ones: permute the cotangents back
+    n, p = _nx(ft.x), ft.x.out_dim
+    return _grad_xs(_by_outputs(ft), Δm === nothing ? nothing : _reorder(Δm, n, p, true),
+                    Δv === nothing ? nothing : _reorder(Δv, n, p, true))
+end
+function _mv_check(fx)
+    fx isa ByOutputsFill{HIPDenseILMM} && isposterior(fx.f.f) &&
+        error("gradients of the predictive marginals of a dense-H ILMM posterior (coupled latents) are not built")
+end
+function _mv_tangent(fx, Δm, Δv)
+    G = _grad_xs(fx, Δm, Δv)
+    return Tangent{typeof(fx)}(; x=_motangent(fx.x, G),
+                               f=@not_implemented("parameter gradients of the predictive marginals (kernels, means, H, training data) are not built"),
+                               Σy=_noise_tangent(fx, Δv === nothing ? 0.0 : sum(Δv)))
+end
+function ChainRulesCore.rrule(::typeof(AbstractGPs.mean_and_var), fx::_MVFinite)
+    _mv_check(fx)
+    MV = mean_and_var(fx)
+    function mean_and_var_pullback(Δ)
+        Δ = unthunk(Δ)
+        Δ isa AbstractZero && return NoTangent(), _mv_tangent(fx, nothing, nothing)
+        return NoTangent(), _mv_tangent(fx, _cot(Δ[1]), _cot(Δ[2]))
+    end
+    return MV, mean_and_var_pullback
+end
+function ChainRulesCore.rrule(::typeof(AbstractGPs.mean), fx::_MVFinite)
+    _mv_check(fx)
+    mean_pullback(Δ) = (NoTangent(), _mv_tangent(fx, _cot(Δ), nothing))
+    return mean(fx), mean_pullback
+end
+function ChainRulesCore.rrule(::typeof(AbstractGPs.var), fx::_MVFinite)
+    _mv_check(fx)
+    var_pullback(Δ) = (NoTangent(), _mv_tangent(fx, nothing, _cot(Δ)))
+    return var(fx), var_pullback
+end
+
 # ---- modes -------------------------------------------------------------------------------------------------------------
 # compute dtype of the per-latent matrices: :f64 (parity mode) | :f32 (BASELINE configs[4])
 set_compute_dtype(d::Symbol) = check(ccall((:lmm_set_compute_dtype, liblmm), Cint, (Cint,), d === :f32 ? 1 : 0))

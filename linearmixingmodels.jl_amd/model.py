@@ -802,6 +802,47 @@ def mean_and_var(fx: FiniteGP, add_noise: bool = True):
     return mean, var
 
 
+def mean_and_var_vjp(fx: FiniteGP, dmean=None, dvar=None, add_noise: bool = True) -> dict:
+    """Pullback of mean_and_var(fx, add_noise) for the cotangents dmean, dvar (shaped like its outputs; None = zero):
+    {"x": d/d fx.x.x (shaped and typed like it), "sigma2": d/d sigma2}.  dvar=None takes no triangular solve (the pullback of mean).
+    OILMM and IndependentMOGP priors and posteriors (sequentially conditioned and sharded ones included: a shard's partial sum) and
+    the dense-H prior, by lmm_oilmm_mean_and_var_grad_xs.  The dense-H posterior and the coupled latent view raise NotImplementedError."""
+    L.ensure_init()
+    lib = L.load()
+    f, x, s2 = fx.f, fx.x, fx.sigma2
+    if isinstance(x, MOInputIsotopicByFeatures):          # mean_and_var permutes by-outputs results: permute the cotangents back
+        n, p = x.n, x.out_dim
+        dm = None if dmean is None else _reorder(dmean, n, p, True)
+        dv = None if dvar is None else _reorder(dvar, n, p, True)
+        return mean_and_var_vjp(FiniteGP(f, x.by_outputs(), s2), dm, dv, add_noise)
+    if isinstance(f, IndependentMOGP):
+        m = len(f.fs)
+        if x.out_dim != m:
+            raise RuntimeError("out dim of x != out dim of f.")
+        if f._post is not None and f._post.dense:
+            raise NotImplementedError("gradients of the predictive marginals of a coupled (dense-H) latent posterior are not served")
+        Ua, Sa, p, post, mogp, (l0, l1), noise = L.Arr(L.colmajor(np.eye(m))), None, m, f._post, f, (0, m), True   # var + Sigma_y
+    else:
+        unpack(fx)
+        if not f.is_oilmm and f.f._post is not None:
+            raise NotImplementedError("gradients of the predictive marginals of a dense-H posterior (coupled latents) are not served")
+        Ua, Sa, p, m = _H_args(f.H)
+        post, mogp, (l0, l1), noise = f.f._post, f.f, f.shard, add_noise
+    xa = x.carr()
+    g = _x_buf(x)
+    dm = L.Arr(dmean) if dmean is not None else None
+    dv = L.Arr(dvar) if dvar is not None else None
+    for a in (dm, dv):
+        if a is not None and a.size != x.n * p:
+            raise ValueError(f"cotangent has {a.size} entries, mean_and_var returns {x.n * p}")
+    L.check(lib.lmm_oilmm_mean_and_var_grad_xs(post.ptr if post is not None else None, L.gps_array([g_.desc() for g_ in mogp.fs]),
+                                               Ua.ptr, Sa.ptr if Sa is not None else None, p, m, l0, l1, xa.ptr, x.dim, x.n,
+                                               dm.ptr if dm is not None else None, dv.ptr if dv is not None else None,
+                                               L.Arr(g, True).ptr))
+    gs2 = float(dvar.sum()) if (noise and dvar is not None) else 0.0
+    return {"x": _x_grad(g, x.x), "sigma2": gs2}
+
+
 def mean_and_cov(fx: FiniteGP):
     """mean_and_cov(fx): reference src/ilmm.jl:132-139 (ILMM/OILMM) and AbstractGPs' generic form over
     src/independent_mogp.jl:60-63 (IndependentMOGP).  Returns (mean, C) with C (p n) x (p n), by-outputs order."""
