@@ -75,6 +75,9 @@ typedef enum {
 typedef enum {
   LMM_KERNEL_SE = 0, LMM_KERNEL_MATERN32 = 1, LMM_KERNEL_MATERN52 = 2, LMM_KERNEL_MATERN12 = 3, LMM_KERNEL_RQ = 4
 } lmm_kernel_kind;
+/* Not a base kind: a sum of up to LMM_SUM_MAX_TERMS base kernels (lmm_kernel_sum_create below); never a term itself. */
+#define LMM_KERNEL_SUM 5
+#define LMM_SUM_MAX_TERMS 4
 
 /* One latent GP: GP(mean, variance * Kernel o ScaleTransform(1/lengthscale)).
  * kind = base | (tag << 8): the low byte is the lmm_kernel_kind; a non-zero tag (lmm_ard_create) gives the latent per-dimension
@@ -87,6 +90,8 @@ typedef struct {
   double lengthscale;
   double mean;         /* ConstMean / ZeroMean */
 } lmm_gp_t;
+/* Gradient of a scalar with respect to one latent's parameters (the gradient entry points below). */
+typedef struct { double variance; double lengthscale; double mean; } lmm_gp_grad_t;
 
 /* The reference's hard-coded numerics constants, passed explicitly so that fp32 callers can
  * widen them (SURVEY.md section 7 "jitter hazards"); pass NULL for the reference values. */
@@ -128,6 +133,31 @@ int lmm_ard_destroy(int tag);
 int lmm_ard_grad(int tag, double* out);
 int lmm_kernel_tag_create(int d, const double* ard, double alpha, int* tag);
 int lmm_kernel_tag_alpha_grad(int tag, double* out);
+
+/* ---- sum kernels (KernelFunctions' KernelSum) ------------------------------------------------
+ * A sum latent has kind = LMM_KERNEL_SUM | (tag << 8) with a tag from lmm_kernel_sum_create, and the kernel
+ *     k(x, x') = v0 * sum_c v_c * kappa_{kind_c}( |x - x'|_c / (s0 * l_c) )
+ * where v0 and s0 are the latent's own `variance` and `lengthscale` (the ScaledKernel and ScaleTransform around the whole sum) and
+ * term c has base kind kind_c, variance v_c and lengthscale l_c.  A term's kind may carry a tag of its own (lmm_kernel_tag_create):
+ * its per-dimension lengthscales are then s0 * l_c * ard_c[k], and an RQ term takes its alpha from it.  The latent's `mean` applies
+ * to the whole sum.  Sums do not nest; products, periodic kernels and an ARD transform around a whole sum are not represented.
+ *   lmm_kernel_sum_create : registers nterms (1..LMM_SUM_MAX_TERMS) terms in the tag registry above (same mutex, no lmm_init needed,
+ *                    counted against its 4096-tag limit, freed by lmm_ard_destroy).  Each term: kind = base | (ktag << 8) with base
+ *                    0..4, variance > 0, lengthscale > 0, mean == 0.  nterms out of range or a bad term value -> LMM_ERR_ARG; a term
+ *                    of kind LMM_KERNEL_SUM or a base kind > 4 -> LMM_ERR_UNSUPPORTED; a term tag that is unknown, is itself a sum
+ *                    tag, or carries an alpha while the term's base kind is not LMM_KERNEL_RQ -> LMM_ERR_ARG.
+ *   lmm_kernel_sum_grad : nterms entries (d/dv_c, d/dl_c, 0) from the most recent gradient entry point that named the tag, with the
+ *                    semantics of lmm_ard_grad (summed over that call's latents carrying the tag, partial over its shard, zeros if
+ *                    grad_gps was NULL).  A term's ARD and alpha gradients are published to the term's own tag (lmm_ard_grad,
+ *                    lmm_kernel_tag_alpha_grad) with s0 * l_c as the multiplier of its factors.  grad_gps[l].variance and
+ *                    .lengthscale of a sum latent are d/dv0 and d/ds0.
+ * Term tags are looked up when an entry point resolves its latents: a destroyed term tag is LMM_ERR_ARG and a term tag with factors
+ * of another d than the call's LMM_ERR_DIM, both naming the latent.  Posterior handles keep their own copy of the resolved terms.
+ * Sum latents are served by every entry point that takes gps: OILMM / IndependentMOGP (logpdf, _multi, posteriors, marginals,
+ * mean_and_var, rand, cov, cross-covariance and all their gradients, latent shards and the fp32 mode) and dense-H (lmm_ilmm_*, with
+ * their gradients; the decoupled shortcut requires equal term lists). */
+int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag);
+int lmm_kernel_sum_grad(int tag, lmm_gp_grad_t* out);
 
 /* ---- lifetime -------------------------------------------------------------------------- */
 int lmm_init(int device);                 /* bind this process to HIP device `device`, create streams */
@@ -212,7 +242,6 @@ int lmm_oilmm_logpdf(const double* x, int d, int n, const double* y, int p,
  * Julia shim.  Gradients w.r.t. y (n*p, by-outputs), sigma2, S (m), U (p x m, treated as an unconstrained matrix as Zygote
  * treats the field) and each latent's (variance, lengthscale, mean).  Any grad pointer may be NULL.  Outputs are partial
  * sums over the latent shard; entries of grad_gps outside the shard are 0. */
-typedef struct { double variance; double lengthscale; double mean; } lmm_gp_grad_t;
 int lmm_oilmm_logpdf_grad(const double* x, int d, int n, const double* y, int p,
                           const double* U, const double* S, int m, double sigma2,
                           const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,

@@ -15,11 +15,13 @@ LIB_PATH = os.environ.get("LMM_HIP_LIB") or os.path.join(_HERE, "liblmm_hip.so")
 LMM_OK, LMM_ERR_DIM, LMM_ERR_NOT_ORTHOGONAL, LMM_ERR_NOT_PD, LMM_ERR_HIP, LMM_ERR_ARG, LMM_ERR_UNSUPPORTED, LMM_ERR_RCCL = range(8)
 UNIQUE_ID_BYTES = 128
 KERNEL_KINDS = {"se": 0, "matern32": 1, "matern52": 2, "matern12": 3, "rq": 4}
+KERNEL_SUM = 5              # LMM_KERNEL_SUM: a sum latent (descriptor kind "sum"), not a base kind
+SUM_MAX_TERMS = 4
 
 # Every symbol include/lmm_hip.h declares (tests/test_abi.py checks the library exports each one).
 SYMBOLS = [
     "lmm_init", "lmm_shutdown", "lmm_last_error_string", "lmm_last_error_detail", "lmm_device_synchronize", "lmm_release_cached_memory",
-    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
+    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_kernel_sum_create", "lmm_kernel_sum_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
     "lmm_comm_destroy",
     "lmm_set_strict_progress", "lmm_get_strict_progress", "lmm_dev_claim_scramble", "lmm_orthogonal_validate", "lmm_oilmm_logpdf", "lmm_oilmm_logpdf_grad", "lmm_oilmm_post_logpdf_grad", "lmm_oilmm_post_logpdf_grad_seq", "lmm_ilmm_logpdf_grad", "lmm_ilmm_post_logpdf_grad", "lmm_ilmm_post_logpdf_grad_seq", "lmm_ilmm_post_latent_logpdf_grad_seq", "lmm_oilmm_logpdf_grad_x", "lmm_oilmm_post_logpdf_grad_seq_x", "lmm_ilmm_logpdf_grad_x",
     "lmm_ilmm_post_logpdf_grad_seq_x", "lmm_ilmm_post_latent_logpdf_grad_seq_x", "lmm_oilmm_logpdf_multi", "lmm_reorder", "lmm_ilmm_logpdf", "lmm_ilmm_logpdf_ex", "lmm_ilmm_logpdf_multi", "lmm_mogp_logpdf", "lmm_mogp_logpdf_diag",
@@ -312,13 +314,43 @@ KERNEL_BASE_MASK = 0xFF
 class ArdTags:
     """Owner of the kernel tags (lmm_ard_create / lmm_kernel_tag_create) of one lmm_gp_t array: destroyed with the array (gps_array
     attaches it as `.ard`).  tags[l] is latent l's tag, 0 for an isotropic latent without an RQ shape; has_ard[l] tells whether the
-    tag holds per-dimension factors, has_alpha[l] whether it holds an RQ shape."""
+    tag holds per-dimension factors, has_alpha[l] whether it holds an RQ shape.  A sum latent's tag is its lmm_kernel_sum_create tag,
+    and terms[l] is the ArdTags of its terms (None for other latents); close() destroys the sum tag before the term tags."""
 
     def __init__(self, m: int):
         self.tags = [0] * m
         self.has_ard = [False] * m
         self.has_alpha = [False] * m
+        self.terms = [None] * m
         self._lib = None
+
+    def create_sum(self, l: int, terms: Sequence[dict]) -> int:
+        """latent l's sum tag over the term descriptors `terms` (their own factor / alpha tags are created first)."""
+        self._lib = self._lib or load()
+        n = len(terms)
+        if not 1 <= n <= SUM_MAX_TERMS:
+            raise ValueError(f"a sum kernel has 1..{SUM_MAX_TERMS} terms, got {n}")
+        tarr = gps_array(terms)
+        self.terms[l] = tarr.ard
+        t = C.c_int()
+        check(self._lib.lmm_kernel_sum_create(n, tarr, C.byref(t)))
+        self.tags[l] = t.value
+        return t.value
+
+    def sum_grad(self, l: int, d: int) -> list:
+        """Per-term gradients of sum latent l after a gradient call: [{"variance", "lengthscale" (float, or the length-d array
+        d logpdf / d lengthscale_k of a term with per-dimension lengthscales), "alpha" (RQ terms)}, ...]."""
+        ta = self.terms[l]
+        n = len(ta.tags)
+        out = (GpGradT * n)()
+        check(self._lib.lmm_kernel_sum_grad(self.tags[l], out))
+        res = []
+        for c in range(n):
+            e = {"variance": out[c].variance, "lengthscale": ta.grad(c, d) if ta.has_ard[c] else out[c].lengthscale}
+            if ta.has_alpha[c]:
+                e["alpha"] = ta.alpha_grad(c)
+            res.append(e)
+        return res
 
     def create(self, l: int, ls: Optional[np.ndarray], alpha: Optional[float] = None) -> int:
         """One tag for latent l: the factors `ls` (None: none) and / or the RQ shape `alpha` (None: none)."""
@@ -351,6 +383,10 @@ class ArdTags:
             for t in self.tags:
                 if t:
                     self._lib.lmm_ard_destroy(t)
+        for ta in self.terms:
+            if ta is not None:
+                ta.close()
+        self.terms = [None] * len(self.tags)
         self.tags = [0] * len(self.tags)
         self.has_ard = [False] * len(self.tags)
         self.has_alpha = [False] * len(self.tags)
@@ -365,13 +401,24 @@ class ArdTags:
 def gps_array(gps: Sequence[dict]):
     """lmm_gp_t array of latent descriptors.  A vector "lengthscale" (length d) becomes an ARD latent: a tag holding the vector, kind
     = base | tag << 8 and lengthscale (the common multiplier) 1.  An "rq" latent's "alpha" (default 2.0) goes into its tag too (one
-    tag holds both).  The tags live as long as the returned array (its `.ard`)."""
+    tag holds both).  A "sum" latent's "terms" (descriptors as above, mean 0) get their own tags and then one sum tag
+    (lmm_kernel_sum_create); its "variance" and scalar "lengthscale" scale the whole sum.  The tags live as long as the returned array
+    (its `.ard`)."""
     arr = (GpT * max(len(gps), 1))()
     arr.ard = ArdTags(len(gps))
     for l, g in enumerate(gps):
         a = arr[l]
-        a.kind = KERNEL_KINDS[g["kind"]]
         a.variance = float(g.get("variance", 1.0))
+        if g["kind"] == "sum":
+            a.kind = KERNEL_SUM
+            ls = g.get("lengthscale", 1.0)
+            if np.ndim(ls) != 0:
+                raise ValueError("per-dimension lengthscales around a whole sum kernel are not supported")
+            a.lengthscale = float(ls)
+            a.kind |= arr.ard.create_sum(l, g["terms"]) << 8
+            a.mean = float(g.get("mean", 0.0))
+            continue
+        a.kind = KERNEL_KINDS[g["kind"]]
         ls = g.get("lengthscale", 1.0)
         alpha = float(g.get("alpha", 2.0)) if g["kind"] == "rq" else None
         vec = None

@@ -14,6 +14,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -300,15 +301,34 @@ struct Dims {
 // rest of the context.  A tag may carry an RQ shape alpha instead of, or besides, factors (lmm_kernel_tag_create): an RQ latent
 // naming it gets a slot holding its alpha (ils nullptr when it has no factors or was folded).
 #define LMM_ARD_MAX_TAGS 4096
-struct ArdTag { int d; std::vector<double> ard, grad; double alpha = 0.0, galpha = 0.0; };   // d = 0: no factors; alpha = 0: no shape
+struct ArdTag {           // d = 0: no factors; alpha = 0: no shape; terms non-empty: a sum tag (lmm_kernel_sum_create; d = 0, alpha = 0)
+  int d; std::vector<double> ard, grad; double alpha = 0.0, galpha = 0.0;
+  std::vector<lmm_gp_t> terms;
+  std::vector<lmm_gp_grad_t> tgrad;     // a sum tag's latest per-term (d/dv_c, d/dl_c, 0)
+};
 std::mutex g_ard_mu;
 std::map<int, ArdTag> g_ard_tags;
 int g_ard_next = 1;
 
 #define LMM_RQ_DEFAULT_ALPHA 2.0          // KernelFunctions' RationalQuadraticKernel(; alpha = 2.0)
-struct KernelSlot { const double* ils; double alpha; };
+struct SumTerms;
+struct KernelSlot { const double* ils; double alpha; const SumTerms* sum = nullptr; };
 std::vector<KernelSlot> g_slot;
 std::vector<int> g_slot_free;
+
+// A sum latent of one call, resolved (resolve_gps): per term c its user tag, the multiplier s0 l_c of its factors, the factor a folded
+// term's lengthscale was multiplied by (1 otherwise), its tag's RQ shape (0: none), the evaluation descriptor (var v0 v_c, the folded
+// or per-dimension lengthscales; `ev` on the host, `dterms` on the device) and the gradient-reduction descriptor (terms with factors
+// and d > 1 take the per-dimension reduction, inv_ls = 1 / multiplier).
+struct SumTerms {
+  int tag = 0, nt = 0;
+  int ttag[LMM_SUM_MAX_TERMS] = {};
+  char has_ard[LMM_SUM_MAX_TERMS] = {};
+  double v[LMM_SUM_MAX_TERMS] = {}, ls[LMM_SUM_MAX_TERMS] = {}, mult[LMM_SUM_MAX_TERMS] = {}, fold[LMM_SUM_MAX_TERMS] = {};
+  double alpha[LMM_SUM_MAX_TERMS] = {};
+  LatentDev ev[LMM_SUM_MAX_TERMS] = {}, gd[LMM_SUM_MAX_TERMS] = {};
+  const LatentDev* dterms = nullptr;
+};
 
 // The resolved ARD state of one call, shared with the posterior handles it builds (and their conditioned successors and views).
 struct ArdSet {
@@ -323,10 +343,13 @@ struct ArdSet {
   std::vector<char> has_ard;
   std::vector<double> mult, fold, alpha;
   std::vector<const double*> gils;
+  std::vector<SumTerms> sums;               // per latent: its resolved terms (nt = 0: not a sum latent)
+  std::vector<LatentDev> thost;             // the evaluation descriptors of every sum term of the call (host, then `tdev`)
+  Buf<LatentDev> tdev;
   ArdSet() = default;
   ArdSet(const ArdSet&) = delete;
   ArdSet& operator=(const ArdSet&) = delete;
-  ~ArdSet() { for (int sl : slots) { g_slot[sl] = KernelSlot{nullptr, 0.0}; g_slot_free.push_back(sl); } }
+  ~ArdSet() { for (int sl : slots) { g_slot[sl] = KernelSlot{nullptr, 0.0, nullptr}; g_slot_free.push_back(sl); } }
 };
 // The ArdSet of the entry point that is running (set by resolve_gps, cleared when the call returns): read by the gradient cores.
 const ArdSet* g_call_ard = nullptr;
@@ -338,22 +361,40 @@ inline double alpha_of(const lmm_gp_t& gp) {
   return (sl > 0 && g_slot[sl - 1].alpha > 0.0) ? g_slot[sl - 1].alpha : LMM_RQ_DEFAULT_ALPHA;
 }
 
+// the resolved terms of a (resolved) sum latent; nullptr for every other latent
+inline const SumTerms* sum_of(const lmm_gp_t& gp) {
+  const int sl = gp.kind >> 8;
+  return (base_kind(gp) == LMM_KERNEL_SUM && sl > 0) ? g_slot[sl - 1].sum : nullptr;
+}
+// kappa(0) of a (resolved) latent: its variance, or v0 sum_c v_c for a sum latent
+inline double prior_var(const lmm_gp_t& gp) {
+  const SumTerms* S = sum_of(gp);
+  if (!S) return gp.variance;
+  double v = 0.0;
+  for (int c = 0; c < S->nt; ++c) v += S->ev[c].var;
+  return v;
+}
+
 LatentDev to_dev(const lmm_gp_t& gp) {
-  LatentDev d;
+  LatentDev d{};
   d.kind = base_kind(gp); d.var = gp.variance; d.inv_ls = 1.0 / gp.lengthscale; d.mean = gp.mean; d.ils = ils_of(gp);
   d.alpha = alpha_of(gp);
+  if (const SumTerms* S = sum_of(gp)) { d.ils = nullptr; d.terms = S->dterms; d.nterms = S->nt; }
   return d;
 }
 // kernel fields of a Gram assembly from a (resolved) latent descriptor
 void set_kernel(GramArgs& a, const lmm_gp_t& gp) {
   a.kind = base_kind(gp); a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale; a.ils = ils_of(gp); a.alpha = alpha_of(gp);
+  a.terms = nullptr; a.nterms = 0;
+  if (const SumTerms* S = sum_of(gp)) { a.ils = nullptr; a.terms = S->dterms; a.nterms = S->nt; }
 }
 
 int check_gps(const lmm_gp_t* gps, int m) {
   if (!gps) return fail(LMM_ERR_ARG, "gps is NULL");
   for (int l = 0; l < m; ++l) {
     const int base = gps[l].kind & LMM_KERNEL_BASE_MASK;
-    if (gps[l].kind < 0 || base > LMM_KERNEL_RQ) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
+    if (gps[l].kind < 0 || base > LMM_KERNEL_SUM) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
+    if (base == LMM_KERNEL_SUM && (gps[l].kind >> 8) == 0) return fail(LMM_ERR_ARG, "latent %d: a sum latent needs a sum tag (lmm_kernel_sum_create)", l);
     if (!(gps[l].variance > 0.0) || !(gps[l].lengthscale > 0.0)) return fail(LMM_ERR_ARG, "latent %d: variance and lengthscale must be > 0", l);
   }
   return LMM_OK;
@@ -378,7 +419,11 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
   A->d = d;
   A->tag.assign(m, 0); A->has_ard.assign(m, 0); A->mult.assign(m, 1.0); A->fold.assign(m, 1.0); A->alpha.assign(m, 0.0);
   A->gils.assign(m, nullptr);
+  A->sums.assign(m, SumTerms{});
   out.v.assign(gps, gps + m);
+  // sum terms: entries of A->host holding a term's per-dimension vector (evaluation / gradient; -1: none), patched after the upload
+  std::vector<std::array<int, LMM_SUM_MAX_TERMS>> ev_ent(m), gd_ent(m);
+  for (int l = 0; l < m; ++l) { ev_ent[l].fill(-1); gd_ent[l].fill(-1); }
   std::map<std::pair<int, double>, int> entry_of;     // (tag, multiplier) -> entry: latents sharing both share the vector (and kind word)
   std::vector<int> ent(m, -1);
   std::vector<char> folded(m, 0);
@@ -387,14 +432,66 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
     if (tag == 0) continue;
     std::vector<double> ard;
     double alpha;
+    const bool is_sum = base_kind(gps[l]) == LMM_KERNEL_SUM;
+    std::vector<lmm_gp_t> terms;
+    std::vector<std::vector<double>> tard;
+    std::vector<double> talpha;
     {
       std::lock_guard<std::mutex> lk(g_ard_mu);
       auto it = g_ard_tags.find(tag);
       if (it == g_ard_tags.end()) return fail(LMM_ERR_ARG, "latent %d: unknown or destroyed ARD tag %d", l, tag);
+      if (is_sum != !it->second.terms.empty())
+        return fail(LMM_ERR_ARG, "latent %d: tag %d is %sa sum tag but the kernel kind is %d", l, tag, is_sum ? "not " : "", base_kind(gps[l]));
       if (it->second.d != 0 && it->second.d != d)
         return fail(LMM_ERR_DIM, "latent %d: ARD tag %d has %d dimensions, the inputs have %d", l, tag, it->second.d, d);
       ard = it->second.ard;
       alpha = it->second.alpha;
+      terms = it->second.terms;
+      for (size_t c = 0; c < terms.size(); ++c) {
+        const int tt = terms[c].kind >> 8;
+        tard.emplace_back();
+        talpha.push_back(0.0);
+        if (tt == 0) continue;
+        auto jt = g_ard_tags.find(tt);
+        if (jt == g_ard_tags.end() || !jt->second.terms.empty())
+          return fail(LMM_ERR_ARG, "latent %d: term %d: unknown or destroyed tag %d", l, (int)c, tt);
+        if (jt->second.d != 0 && jt->second.d != d)
+          return fail(LMM_ERR_DIM, "latent %d: term %d: tag %d has %d dimensions, the inputs have %d", l, (int)c, tt, jt->second.d, d);
+        tard.back() = jt->second.ard;
+        talpha.back() = jt->second.alpha;
+      }
+    }
+    if (is_sum) {                      // terms as virtual latents: var v0 v_c, lengthscale s0 l_c, factors folded as for latents
+      SumTerms& S = A->sums[l];
+      const double v0 = gps[l].variance, s0 = gps[l].lengthscale;
+      S.tag = tag; S.nt = (int)terms.size();
+      A->tag[l] = tag; A->mult[l] = s0;
+      out.v[l].kind = LMM_KERNEL_SUM;
+      for (int c = 0; c < S.nt; ++c) {
+        const int bk = terms[c].kind & LMM_KERNEL_BASE_MASK;
+        const double E = s0 * terms[c].lengthscale;
+        S.ttag[c] = terms[c].kind >> 8; S.v[c] = terms[c].variance; S.ls[c] = terms[c].lengthscale; S.mult[c] = E; S.fold[c] = 1.0;
+        S.alpha[c] = talpha[c];
+        LatentDev ev{};
+        ev.kind = bk; ev.var = v0 * terms[c].variance; ev.inv_ls = 1.0 / E; ev.alpha = talpha[c] > 0.0 ? talpha[c] : LMM_RQ_DEFAULT_ALPHA;
+        LatentDev gd = ev;
+        const std::vector<double>& ta = tard[c];
+        if (!ta.empty()) {
+          S.has_ard[c] = 1;
+          bool equal = true;
+          for (int k = 1; k < d; ++k) equal = equal && ta[k] == ta[0];
+          if (d > 1) {                 // the gradient reduction needs the per-dimension vector, folded or not
+            gd_ent[l][c] = (int)(A->host.size() / d);
+            for (int k = 0; k < d; ++k) A->host.push_back(1.0 / (E * ta[k]));
+          }
+          if (equal) {
+            S.fold[c] = ta[0]; ev.inv_ls = 1.0 / (E * ta[0]);
+            if (d == 1) gd = ev;       // d == 1: the isotropic reduction at l_eff = s0 l_c ard[0] gives the one derivative
+          } else ev_ent[l][c] = gd_ent[l][c];
+        }
+        S.ev[c] = ev; S.gd[c] = gd;
+      }
+      continue;
     }
     if (alpha > 0.0 && base_kind(gps[l]) != LMM_KERNEL_RQ)
       return fail(LMM_ERR_ARG, "latent %d: tag %d carries an RQ shape but the kernel kind is %d", l, tag, base_kind(gps[l]));
@@ -426,6 +523,31 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
     HIPCHK(hipMemcpyAsync(A->dev.p, A->host.data(), A->host.size() * sizeof(double), hipMemcpyHostToDevice, g.streams[0]));
     for (int l = 0; l < m; ++l)
       if (ent[l] >= 0) A->gils[l] = A->dev.p + (size_t)ent[l] * d;
+    for (int l = 0; l < m; ++l)
+      for (int c = 0; c < A->sums[l].nt; ++c) {
+        if (ev_ent[l][c] >= 0) A->sums[l].ev[c].ils = A->dev.p + (size_t)ev_ent[l][c] * d;
+        if (gd_ent[l][c] >= 0) A->sums[l].gd[c].ils = A->dev.p + (size_t)gd_ent[l][c] * d;
+      }
+  }
+  // the sum latents' evaluation descriptors on the device, and one slot per sum latent
+  for (int l = 0; l < m; ++l)
+    for (int c = 0; c < A->sums[l].nt; ++c) A->thost.push_back(A->sums[l].ev[c]);
+  if (!A->thost.empty()) {
+    A->tdev = Buf<LatentDev>(A->thost.size());
+    HIPCHK(hipMemcpyAsync(A->tdev.p, A->thost.data(), A->thost.size() * sizeof(LatentDev), hipMemcpyHostToDevice, g.streams[0]));
+    size_t off = 0;
+    for (int l = 0; l < m; ++l) {
+      SumTerms& S = A->sums[l];
+      if (S.nt == 0) continue;
+      S.dterms = A->tdev.p + off;
+      off += S.nt;
+      int sl;
+      if (!g_slot_free.empty()) { sl = g_slot_free.back(); g_slot_free.pop_back(); }
+      else { sl = (int)g_slot.size(); g_slot.push_back(KernelSlot{nullptr, 0.0, nullptr}); }
+      g_slot[sl] = KernelSlot{nullptr, 0.0, &S};
+      A->slots.push_back(sl);
+      out.v[l].kind = LMM_KERNEL_SUM | ((sl + 1) << 8);
+    }
   }
   // Slots: one per (tag, multiplier) among the latents that need one (a per-dimension vector, or an RQ shape); latents sharing both
   // share the slot and so the kind word.
@@ -438,8 +560,8 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
     if (it == slot_of.end()) {
       int sl;
       if (!g_slot_free.empty()) { sl = g_slot_free.back(); g_slot_free.pop_back(); }
-      else { sl = (int)g_slot.size(); g_slot.push_back(KernelSlot{nullptr, 0.0}); }
-      g_slot[sl] = KernelSlot{vec ? A->gils[l] : nullptr, A->alpha[l]};
+      else { sl = (int)g_slot.size(); g_slot.push_back(KernelSlot{nullptr, 0.0, nullptr}); }
+      g_slot[sl] = KernelSlot{vec ? A->gils[l] : nullptr, A->alpha[l], nullptr};
       A->slots.push_back(sl);
       it = slot_of.emplace(key, sl).first;
     }
@@ -457,11 +579,60 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
   if (int rc_ = resolve_gps(gps, m, d, cg_)) return rc_;        \
   if (cg_.ard) gps = cg_.v.data()
 
+// Posterior latent mean mu + K(xs, x) alpha (launch_post_mean); a sum latent takes one pass per term, added in term order.
+void post_mean_g(const double* xs, int ns, const double* x, int n, int d, const double* alpha, const lmm_gp_t& gp, double* partial,
+                 double* out, hipStream_t st) {
+  const SumTerms* S = sum_of(gp);
+  if (!S || alpha == nullptr || n == 0) { launch_post_mean(xs, ns, x, n, d, alpha, to_dev(gp), partial, out, st); return; }
+  double* tmp = S->nt > 1 ? call_scratch(ns) : nullptr;
+  for (int c = 0; c < S->nt; ++c) {
+    LatentDev tc = S->ev[c];
+    tc.mean = c == 0 ? gp.mean : 0.0;
+    launch_post_mean(xs, ns, x, n, d, alpha, tc, partial, c == 0 ? out : tmp, st);
+    if (c > 0) launch_vec_lin(out, tmp, 1.0, ns, out, st);
+  }
+}
+
+// A latent's descriptor in the dense-H latent array (DenseArgs.lat, the posterior's latd): the dense kernels read var as kappa(0),
+// which is v0 sum_c v_c for a sum latent (its terms carry their own variances).
+LatentDev dense_dev(const lmm_gp_t& gp) {
+  LatentDev d = to_dev(gp);
+  d.var = prior_var(gp);
+  return d;
+}
+// Whether any of the (resolved) latents is a sum latent (the dense kernels' instantiation)
+int any_sum(const lmm_gp_t* gps, int m) {
+  for (int l = 0; l < m; ++l) if (sum_of(gps[l])) return 1;
+  return 0;
+}
+// Whether two (resolved) latents have the same kernel (the dense-H decoupled shortcut): base kind, vector, alpha, variance and
+// lengthscale; for sum latents also the whole term lists (a term with per-dimension lengthscales counts as different: its vector
+// is the latent's own).
+bool same_kernel(const lmm_gp_t& a, const lmm_gp_t& b) {
+  if (base_kind(a) != base_kind(b) || ils_of(a) != ils_of(b) || alpha_of(a) != alpha_of(b) || a.variance != b.variance ||
+      a.lengthscale != b.lengthscale)
+    return false;
+  const SumTerms* A = sum_of(a);
+  const SumTerms* B = sum_of(b);
+  if (!A || !B) return A == B;
+  if (A->nt != B->nt) return false;
+  for (int c = 0; c < A->nt; ++c) {
+    const LatentDev& x = A->ev[c];
+    const LatentDev& y = B->ev[c];
+    if (x.kind != y.kind || x.var != y.var || x.inv_ls != y.inv_ls || x.alpha != y.alpha || x.ils != nullptr || y.ils != nullptr)
+      return false;
+  }
+  return true;
+}
+
 // Gradient entry points: the per-dimension reduction keeps d sums in registers (LMM_ARD_GRAD_DMAX).
 int ard_grad_check(int d) {
   if (!g_call_ard || d <= LMM_ARD_GRAD_DMAX) return LMM_OK;
   for (const double* p : g_call_ard->gils)
     if (p) return fail(LMM_ERR_UNSUPPORTED, "gradients of ARD latents are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
+  for (const SumTerms& S : g_call_ard->sums)
+    for (int c = 0; c < S.nt; ++c)
+      if (S.gd[c].ils) return fail(LMM_ERR_UNSUPPORTED, "gradients of ARD latents are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
   return LMM_OK;
 }
 // The input gradient (grad_x_kernel) keeps d sums per row in registers, as the ARD reduction does.
@@ -473,6 +644,8 @@ int input_grad_check(int d, bool wanted) {
 int ard_grad_d() {
   if (!g_call_ard) return 0;
   for (const double* p : g_call_ard->gils) if (p) return g_call_ard->d;
+  for (const SumTerms& S : g_call_ard->sums)
+    for (int c = 0; c < S.nt; ++c) if (S.gd[c].ils) return g_call_ard->d;
   return 0;
 }
 // The latent's descriptor for the gradient reduction: an ARD latent (folded ones included, d > 1) takes the per-dimension variant
@@ -494,19 +667,47 @@ void ard_grad_finish(int l, int d, const double* red, const double* ard, double*
 // Publishes the call's per-dimension gradients to the registry: every tag the call named gets d/d ard[k] = multiplier * d/d l_k summed
 // over the call's latents [l0, l1) carrying it, and a tag with an RQ shape gets d/d alpha summed over those latents (galpha: one per
 // latent); gard == nullptr (grad_gps NULL): zeros.
-void ard_publish(const std::vector<double>* gard, const std::vector<double>* galpha, int l0, int l1) {
+// Sum latents: tg holds per latent LMM_SUM_MAX_TERMS records of sum_grad_stride(d) values (sum_grad_finish); the sum tag gets
+// (d/dv_c, d/dl_c, 0) and each term's tag its factor and alpha gradients (multiplier s0 l_c).
+inline size_t sum_grad_stride(int d) { return 3 + (size_t)d; }
+void ard_publish(const std::vector<double>* gard, const std::vector<double>* galpha, int l0, int l1,
+                 const std::vector<double>* tg = nullptr) {
   if (!g_call_ard) return;
   const ArdSet& A = *g_call_ard;
   const int d = A.d, m = (int)A.tag.size();
   std::lock_guard<std::mutex> lk(g_ard_mu);
+  auto reset = [&](int tag) {
+    auto it = g_ard_tags.find(tag);
+    if (tag == 0 || it == g_ard_tags.end()) return;
+    it->second.grad.assign(it->second.d, 0.0); it->second.galpha = 0.0;
+    it->second.tgrad.assign(it->second.terms.size(), lmm_gp_grad_t{0.0, 0.0, 0.0});
+  };
   for (int l = 0; l < m; ++l) {
-    auto it = g_ard_tags.find(A.tag[l]);
-    if (A.tag[l] != 0 && it != g_ard_tags.end()) { it->second.grad.assign(it->second.d, 0.0); it->second.galpha = 0.0; }
+    reset(A.tag[l]);
+    for (int c = 0; c < A.sums[l].nt; ++c) reset(A.sums[l].ttag[c]);
+  }
+  if (tg && gard) {
+    const size_t sw = sum_grad_stride(d);
+    for (int l = l0; l < l1; ++l) {
+      const SumTerms& S = A.sums[l];
+      auto st = g_ard_tags.find(S.tag);
+      for (int c = 0; c < S.nt; ++c) {
+        const double* r = &(*tg)[((size_t)l * LMM_SUM_MAX_TERMS + c) * sw];
+        if (st != g_ard_tags.end() && (size_t)c < st->second.tgrad.size()) {
+          st->second.tgrad[c].variance += r[0]; st->second.tgrad[c].lengthscale += r[1];
+        }
+        auto it = g_ard_tags.find(S.ttag[c]);
+        if (S.ttag[c] == 0 || it == g_ard_tags.end()) continue;
+        if (S.has_ard[c])
+          for (int k = 0; k < it->second.d; ++k) it->second.grad[k] += S.mult[c] * r[3 + k];
+        if (S.alpha[c] > 0.0) it->second.galpha += r[2];
+      }
+    }
   }
   if (!gard) return;
   for (int l = l0; l < l1; ++l) {
     auto it = g_ard_tags.find(A.tag[l]);
-    if (A.tag[l] == 0 || it == g_ard_tags.end()) continue;
+    if (A.tag[l] == 0 || it == g_ard_tags.end() || A.sums[l].nt > 0) continue;
     if (A.has_ard[l])
       for (int k = 0; k < d; ++k) it->second.grad[k] += A.mult[l] * (*gard)[(size_t)l * d + k];
     if (A.alpha[l] > 0.0) it->second.galpha += (*galpha)[l];
@@ -1276,6 +1477,48 @@ int lmm_kernel_tag_create(int d, const double* ard, double alpha, int* tag) {
   return tag_register(d, ard, alpha, tag, "lmm_kernel_tag_create: too many live tags");
 }
 
+int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag) {
+  if (nterms < 1 || nterms > LMM_SUM_MAX_TERMS || !terms || !tag)
+    return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: nterms must be 1..4, terms and tag non-NULL");
+  for (int c = 0; c < nterms; ++c) {
+    const int base = terms[c].kind & LMM_KERNEL_BASE_MASK;
+    if (terms[c].kind < 0 || base > LMM_KERNEL_RQ)
+      return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: a term must have a base kind 0..4 (sums do not nest)");
+    if (!(terms[c].variance > 0.0) || !std::isfinite(terms[c].variance) || !(terms[c].lengthscale > 0.0) ||
+        !std::isfinite(terms[c].lengthscale) || terms[c].mean != 0.0)
+      return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term needs finite variance > 0, lengthscale > 0 and mean 0");
+  }
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  for (int c = 0; c < nterms; ++c) {
+    const int tt = terms[c].kind >> 8;
+    if (tt == 0) continue;
+    auto it = g_ard_tags.find(tt);
+    if (it == g_ard_tags.end() || !it->second.terms.empty())
+      return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term names an unknown tag or a sum tag");
+    if (it->second.alpha > 0.0 && (terms[c].kind & LMM_KERNEL_BASE_MASK) != LMM_KERNEL_RQ)
+      return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term's tag carries an RQ shape but its kind is not LMM_KERNEL_RQ");
+  }
+  if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: too many live tags");
+  while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
+  const int t = g_ard_next;
+  g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
+  ArdTag& a = g_ard_tags[t];
+  a.d = 0;
+  a.terms.assign(terms, terms + nterms);
+  a.tgrad.assign(nterms, lmm_gp_grad_t{0.0, 0.0, 0.0});
+  *tag = t;
+  return LMM_OK;
+}
+
+int lmm_kernel_sum_grad(int tag, lmm_gp_grad_t* out) {
+  if (!out) return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_grad: out is NULL");
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  auto it = g_ard_tags.find(tag);
+  if (it == g_ard_tags.end() || it->second.terms.empty()) return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_grad: unknown sum tag");
+  std::copy(it->second.tgrad.begin(), it->second.tgrad.end(), out);
+  return LMM_OK;
+}
+
 int lmm_kernel_tag_alpha_grad(int tag, double* out) {
   if (!out) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_alpha_grad: out is NULL");
   std::lock_guard<std::mutex> lk(g_ard_mu);
@@ -1567,7 +1810,53 @@ struct OilmmGrad {          // host results of oilmm_grad_core (partial sums ove
   std::vector<lmm_gp_grad_t> ggps;
   std::vector<double> gard;   // m x d: d logpdf / d l_k of the ARD latents (ard_grad_finish), zeros elsewhere
   std::vector<double> galpha; // m: d logpdf / d alpha of the RQ latents, zeros elsewhere
+  std::vector<double> tg;     // sum latents: m x LMM_SUM_MAX_TERMS records (sum_grad_finish), zeros elsewhere
 };
+
+// The resolved terms of latent l of the running call (nullptr: not a sum latent).
+inline const SumTerms* call_sum(int l) {
+  return (g_call_ard && g_call_ard->sums[l].nt > 0) ? &g_call_ard->sums[l] : nullptr;
+}
+// Terms of the shard's latents [l0, l1): offsets of each latent's first term reduction (a latent without terms takes none); returns
+// the total.
+int sum_term_offsets(int l0, int l1, std::vector<int>& toff) {
+  toff.assign(std::max(l1 - l0, 1), 0);
+  int T = 0;
+  for (int l = l0; l < l1; ++l) { toff[l - l0] = T; if (const SumTerms* S = call_sum(l)) T += S->nt; }
+  return T;
+}
+// One gradient reduction per term of a sum latent (the trace and alpha.delta partials, which do not depend on the kernel, are taken
+// from term 0's).  red: NGR values per term, ard: d values per term.
+void sum_grad_reduce(const SumTerms& S, const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta,
+                     const double* x, int d, double* partial, double* red, double* ard, hipStream_t st) {
+  for (int c = 0; c < S.nt; ++c)
+    launch_grad_reduce(Kinv, ld, n, nsplit, alpha, delta, x, d, S.gd[c], partial, red + (size_t)LMM_NGRAD * c, st, ard + (size_t)d * c);
+}
+// Chain rule of a sum latent from its term reductions: term c's kernel is V_c kappa_c(. / E_c) with V_c = v0 v_c and E_c = s0 l_c, so
+// d/dv_c = v0 d/dV_c, d/dl_c = s0 d/dE_c and d/ds0 = sum_c l_c d/dE_c (returned).  aa, tr: alpha.alpha and tr Kt^-1 over all rows
+// (d/dV_c = (sum_{i>j} w K_c,ij + V_c (aa - tr) / 2) / V_c).  out: LMM_SUM_MAX_TERMS records of sum_grad_stride(d) values
+// (d/dv_c, d/dl_c, d/dalpha_c, d/dl_k of the term's per-dimension lengthscales).
+double sum_grad_finish(const SumTerms& S, int d, const double* red, const double* ard, double aa, double tr, double v0, double s0,
+                       double* out, double* dv0 = nullptr) {
+  double ds0 = 0.0, gv0 = 0.0;
+  const size_t sw = 3 + (size_t)d;
+  for (int c = 0; c < S.nt; ++c) {
+    const double* rc = red + (size_t)LMM_NGRAD * c;
+    double* o = out + sw * c;
+    const double V = S.ev[c].var;
+    const double gV = (rc[7] + 0.5 * V * (aa - tr)) / V;
+    const double dE = S.gd[c].ils ? rc[0] : rc[0] * S.fold[c];
+    o[0] = gV * v0;
+    o[1] = dE * s0;
+    o[2] = S.alpha[c] > 0.0 ? rc[8] : 0.0;
+    if (S.gd[c].ils) for (int k = 0; k < d; ++k) o[3 + k] = ard[(size_t)d * c + k];
+    else if (S.has_ard[c]) o[3] = rc[0];                   // d == 1: d/d l_eff, l_eff = multiplier * fold
+    ds0 += dE * S.ls[c];
+    gv0 += gV * S.v[c];
+  }
+  if (dv0) *dv0 = gv0;
+  return ds0;
+}
 
 // Value and gradient of the OILMM logpdf (reference src/oilmm.jl:79-113 differentiated) over N points in NB.nblk consecutive
 // blocks, block b carrying observation noise NB.s2[b] (one block: the plain logpdf; several: the joint density of the
@@ -1615,6 +1904,9 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   const int NGR = LMM_NGRAD;
   Buf<double> alpha((size_t)D.NC * std::max(ms, 1)), lmld(std::max(ms, 1)), red((size_t)NGR * std::max(ms, 1));
   Buf<double> ardred((size_t)d * std::max(ms, 1));             // per-dimension sums of the ARD latents (d/d l_k)
+  std::vector<int> toff;                                       // sum latents: one reduction per term
+  const int nterm = sum_term_offsets(l0, l1, toff);
+  Buf<double> tred((size_t)NGR * std::max(nterm, 1)), tard((size_t)d * std::max(nterm, 1));
   // more than two noise blocks: [tr Kinv, alpha.alpha] per (latent, block) from the small per-range kernels
   Buf<double> blksum(nblk > 2 ? (size_t)2 * nblk * std::max(ms, 1) : 1);
   Buf<int> info(std::max(ms, 1));
@@ -1658,9 +1950,18 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     launch_syrk_upper_set(B.A, D.ld, Rb, D.ld, D.NC, nb, st);                // lower(A) = L^-T L^-1 = Kt^-1
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      launch_grad_reduce(Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, grad_dev(gps[l0 + k], l0 + k), part[s].p,
-                         red.p + (size_t)NGR * k, st, ardred.p + (size_t)d * k);
-      if (gx_dev) {
+      if (const SumTerms* Sk = call_sum(l0 + k)) {
+        sum_grad_reduce(*Sk, Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, part[s].p,
+                        tred.p + (size_t)NGR * toff[k], tard.p + (size_t)d * toff[k], st);
+        if (gx_dev)
+          for (int c = 0; c < Sk->nt; ++c) {
+            launch_grad_x(Am[s][j].p, D.ld, n, alb.p[j], xd, d, Sk->gd[c], gxpart[s].p, gxacc[s].p, gx_used[s] != 0, st);
+            gx_used[s] = 1;
+          }
+      } else
+        launch_grad_reduce(Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, grad_dev(gps[l0 + k], l0 + k), part[s].p,
+                           red.p + (size_t)NGR * k, st, ardred.p + (size_t)d * k);
+      if (gx_dev && !call_sum(l0 + k)) {
         launch_grad_x(Am[s][j].p, D.ld, n, alb.p[j], xd, d, grad_dev(gps[l0 + k], l0 + k), gxpart[s].p, gxacc[s].p, gx_used[s] != 0, st);
         gx_used[s] = 1;
       }
@@ -1690,6 +1991,11 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   HIPCHK(hipMemcpyAsync(hred.data(), red.p, (size_t)NGR * std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
   std::vector<double> hard(ard_grad_d() ? (size_t)d * std::max(ms, 1) : 0, 0.0);
   if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  std::vector<double> htred((size_t)NGR * nterm), htard((size_t)d * nterm);
+  if (nterm > 0) {
+    HIPCHK(hipMemcpyAsync(htred.data(), tred.p, htred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+    if (ard_grad_d()) HIPCHK(hipMemcpyAsync(htard.data(), tard.p, htard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  }
   if (!hblk.empty() && ms > 0) HIPCHK(hipMemcpyAsync(hblk.data(), blksum.p, hblk.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, st0));
   // small dense products needed by the chain rule: YA = Y' alpha (p x ms), aTy = alpha_l . (T y)_l, M2 = Y Y' (p x p) per noise block
@@ -1716,14 +2022,19 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
   G.gard.assign((size_t)m * d, 0.0);
   G.galpha.assign(m, 0.0);
+  G.tg.assign((size_t)m * LMM_SUM_MAX_TERMS * sum_grad_stride(d), 0.0);
   for (int k = 0; k < ms; ++k) {
     const int l = l0 + k;
     total += lml[k];
-    const double* r = &hred[(size_t)NGR * k];
-    G.galpha[l] = r[8];
-    double cl;
-    ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * k], &cl, &G.gard[(size_t)l * d]);
+    const SumTerms* Sl = call_sum(l);
+    const double* r = Sl ? &htred[(size_t)NGR * toff[k]] : &hred[(size_t)NGR * k];
+    double cl = 0.0;
+    if (!Sl) {
+      G.galpha[l] = r[8];
+      ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * k], &cl, &G.gard[(size_t)l * d]);
+    }
     const double ad = r[3], sa = r[4], v = gps[l].variance;
+    double aa_all = 0.0, tr_all = 0.0;
     double D_aa = 0.0, D_tr = 0.0, g_s2 = 0.0;       // a'Da, tr(Kt^-1 D) with D the projected noise; sum_b s2[b] dlml/dnoise_b
     for (int b = 0; b < nblk; ++b) {
       // tr Kinv and alpha.alpha over the block's rows
@@ -1731,12 +2042,16 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
       const double aa = nblk > 2 ? hblk[((size_t)k * nblk + b) * 2 + 1] : r[b ? 6 : 2];
       const double gb = 0.5 * (aa - tr);                                       // d lml / d (projected noise of block b)
       D_aa += ST[b][l] * aa; D_tr += ST[b][l] * tr;
+      aa_all += aa; tr_all += tr;
       G.gs2[b] += gb / S[l];
       g_s2 += gb * NB.s2[b];
     }
     // 1/2 tr((aa' - Kt^-1) K) / v  with K = Kt - D:  a'delta - a'Da - (n - tr(Kt^-1 D))
-    G.ggps[l].variance = 0.5 * ((ad - D_aa) - ((double)n - D_tr)) / v;
+    G.ggps[l].variance = 0.5 * ((ad - D_aa) - ((double)n - D_tr)) / v;      // (a sum latent's K is linear in v0 too)
     G.ggps[l].lengthscale = cl;                                                // sum_{i>j} (a_i a_j - Kinv_ij) dK_ij/dl (x2 / 2)
+    if (Sl)
+      G.ggps[l].lengthscale = sum_grad_finish(*Sl, d, r, htard.data() + (size_t)d * toff[k], aa_all, tr_all, v, gps[l].lengthscale,
+                                              &G.tg[(size_t)l * LMM_SUM_MAX_TERMS * sum_grad_stride(d)]);
     G.ggps[l].mean = sa;
     G.gS[l] += -g_s2 / (S[l] * S[l]) + 0.5 * aTy[k + (size_t)l * ms] / S[l];
     for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] += -YA[o + (size_t)k * p] / std::sqrt(S[l]);
@@ -1857,7 +2172,7 @@ int lmm_oilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int 
                                G, gy.p, gx.p))
     return rc;
   write_oilmm_grad(G, m, p, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
-  ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, latent_begin, latent_end);
+  ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, latent_begin, latent_end, &G.tg);
   if (grad_y) gy.finish(st0);
   if (grad_x) gx.finish(st0);
   if (grad_y || grad_x) HIPCHK(hipStreamSynchronize(st0));
@@ -1934,7 +2249,8 @@ int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* b
   if (grad_U) for (size_t q = 0; q < (size_t)p * m; ++q) grad_U[q] = GJ.gU[q] - GM.gU[q];
   for (size_t q = 0; q < GJ.gard.size(); ++q) GJ.gard[q] -= GM.gard[q];
   for (size_t q = 0; q < GJ.galpha.size(); ++q) GJ.galpha[q] -= GM.galpha[q];
-  ard_publish(grad_gps ? &GJ.gard : nullptr, &GJ.galpha, latent_begin, latent_end);
+  for (size_t q = 0; q < GJ.tg.size(); ++q) GJ.tg[q] -= GM.tg[q];
+  ard_publish(grad_gps ? &GJ.gard : nullptr, &GJ.galpha, latent_begin, latent_end, &GJ.tg);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);
@@ -2107,7 +2423,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   Uploaded Td(T, st0), STd(ST, st0);
   std::vector<double> Hv(H, H + (size_t)p * m), means(m);
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) { means[l] = gps[l].mean; lat[l] = to_dev(gps[l]); }
+  for (int l = 0; l < m; ++l) { means[l] = gps[l].mean; lat[l] = dense_dev(gps[l]); }
   Uploaded Hd(Hv, st0), meansd(means, st0);
   Buf<LatentDev> latd(m);
   HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
@@ -2121,8 +2437,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   };
   bool identical = allow_decoupled != 0;
   for (int l = 1; l < m && identical; ++l)
-    identical = base_kind(gps[l]) == base_kind(gps[0]) && ils_of(gps[l]) == ils_of(gps[0]) && alpha_of(gps[l]) == alpha_of(gps[0]) &&
-                gps[l].variance == gps[0].variance && gps[l].lengthscale == gps[0].lengthscale;   // two tags with one alpha: one kernel
+    identical = same_kernel(gps[l], gps[0]);        // two tags with one alpha: one kernel
   if (path_used) *path_used = identical ? 1 : 0;
   if (identical) {
     // Decoupled shortcut: with one shared latent kernel the covariance is I (x) K + SigmaT (x) I;
@@ -2161,7 +2476,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
   DenseArgs a{};
   a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd.p; a.d = d; a.n = n; a.m = m;
-  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = 1;
+  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = 1; a.has_sum = any_sum(gps, m);
   launch_dense_assemble(a, st0);
   potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, 1, lml_dev.p, st0);
@@ -2203,7 +2518,7 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   Uploaded Td(T, st0), STd(ST, st0);
   std::vector<double> Hv(H, H + (size_t)p * m), means(m);
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) { means[l] = gps[l].mean; lat[l] = to_dev(gps[l]); }
+  for (int l = 0; l < m; ++l) { means[l] = gps[l].mean; lat[l] = dense_dev(gps[l]); }
   Uploaded Hd(Hv, st0), meansd(means, st0);
   Buf<LatentDev> latd(m);
   HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
@@ -2221,7 +2536,7 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
   DenseArgs a{};
   a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd.p; a.d = d; a.n = n; a.m = m;
-  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = ncol;
+  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = ncol; a.has_sum = any_sum(gps, m);
   launch_dense_assemble(a, st0);
   potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, ncol, lml_dev.p, st0);
@@ -2248,6 +2563,7 @@ struct IlmmGrad {            // host results of ilmm_grad_core
   std::vector<lmm_gp_grad_t> ggps;
   std::vector<double> gard;  // m x d: d logpdf / d l_k of the ARD latents (ard_grad_finish), zeros elsewhere
   std::vector<double> galpha;  // m: d logpdf / d alpha of the RQ latents, zeros elsewhere
+  std::vector<double> tg;      // sum latents: m x LMM_SUM_MAX_TERMS records (sum_grad_finish), zeros elsewhere
 };
 
 // Value and gradient of the dense-H ILMM prior logpdf over n points in NB.nblk consecutive blocks, block b carrying observation
@@ -2286,7 +2602,7 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   }
   for (int l = 0; l < m; ++l) means[l] = gps[l].mean;
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) lat[l] = to_dev(gps[l]);
+  for (int l = 0; l < m; ++l) lat[l] = dense_dev(gps[l]);
   std::vector<int> sidx(n);
   for (int b = 0; b < nblk; ++b)
     for (int i = bi0[b]; i < bi0[b] + bn[b]; ++i) sidx[i] = b;
@@ -2321,6 +2637,7 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   DenseArgs a{};
   a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n; a.m = m;
   a.lat = latd.p; a.sigmaT = STd.buf.p; a.sig_idx = nblk > 1 ? sidxd.p : nullptr; a.rider = delta.p; a.rider_ld = N; a.nrider = 1;
+  a.has_sum = any_sum(gps, m);
   launch_dense_assemble(a, st0);
   potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, 1, lml_dev.p, st0);
@@ -2334,12 +2651,23 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   Buf<double> red((size_t)NGR * m), gpart((size_t)grad_partials(n, ard_grad_d())), Btr(KB * mm), AAt(KB * mm), AY(KB * mp);
   Buf<double> ardred((size_t)d * m), gxpart;
   if (gx_dev) gxpart = Buf<double>(grad_x_partial_elems(n, d));
+  std::vector<int> toff;                                       // sum latents: one reduction per term
+  const int nterm = sum_term_offsets(0, m, toff);
+  Buf<double> tred((size_t)NGR * std::max(nterm, 1)), tard((size_t)d * std::max(nterm, 1));
   for (int l = 0; l < m; ++l) {
-    launch_grad_reduce(mat_at(A.p, (size_t)l * n * D.ld + (size_t)l * n), D.ld, n, n, alpha.p + (size_t)l * n, delta.p + (size_t)l * n, xd, d,
+    const double* Kl = mat_at(A.p, (size_t)l * n * D.ld + (size_t)l * n);
+    if (const SumTerms* Sl = call_sum(l)) {
+      sum_grad_reduce(*Sl, Kl, D.ld, n, n, alpha.p + (size_t)l * n, delta.p + (size_t)l * n, xd, d, gpart.p,
+                      tred.p + (size_t)NGR * toff[l], tard.p + (size_t)d * toff[l], st0);
+      if (gx_dev)
+        for (int c = 0; c < Sl->nt; ++c)
+          launch_grad_x(Kl, D.ld, n, alpha.p + (size_t)l * n, xd, d, Sl->gd[c], gxpart.p, gx_dev, l > 0 || c > 0, st0);
+      continue;
+    }
+    launch_grad_reduce(Kl, D.ld, n, n, alpha.p + (size_t)l * n, delta.p + (size_t)l * n, xd, d,
                        grad_dev(gps[l], l), gpart.p, red.p + (size_t)NGR * l, st0, ardred.p + (size_t)d * l);
     if (gx_dev)
-      launch_grad_x(mat_at(A.p, (size_t)l * n * D.ld + (size_t)l * n), D.ld, n, alpha.p + (size_t)l * n, xd, d, grad_dev(gps[l], l), gxpart.p,
-                    gx_dev, l > 0, st0);
+      launch_grad_x(Kl, D.ld, n, alpha.p + (size_t)l * n, xd, d, grad_dev(gps[l], l), gxpart.p, gx_dev, l > 0, st0);
   }
   // regulariser pieces: Rm = Y - (T Y)' H' (n x p), RH = Rm H (n x m), per block Rm' Ty (p x m), RH' Y (m x p)
   Buf<double> HTY((size_t)n * p), Rm((size_t)n * p), RH((size_t)N), RtTy(KB * mp), RHtY(KB * mp);
@@ -2365,6 +2693,11 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   std::vector<double> hard(ard_grad_d() ? (size_t)d * m : 0, 0.0);
   if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  std::vector<double> htred((size_t)NGR * nterm), htard((size_t)d * nterm);
+  if (nterm > 0) {
+    HIPCHK(hipMemcpyAsync(htred.data(), tred.p, htred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+    if (ard_grad_d()) HIPCHK(hipMemcpyAsync(htard.data(), tard.p, htard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  }
   HIPCHK(hipMemcpyAsync(hB.data(), Btr.p, nblk * mm * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hAAt.data(), AAt.p, nblk * mm * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hAY.data(), AY.p, nblk * mp * sizeof(double), hipMemcpyDeviceToHost, st0));
@@ -2380,7 +2713,16 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   G.ggps.assign(m, lmm_gp_grad_t{});
   G.gard.assign((size_t)m * d, 0.0);
   G.galpha.assign(m, 0.0);
+  G.tg.assign((size_t)m * LMM_SUM_MAX_TERMS * sum_grad_stride(d), 0.0);
   for (int l = 0; l < m; ++l) {
+    if (const SumTerms* Sl = call_sum(l)) {       // the trace, a.a and sum-of-alpha partials from term 0's reduction
+      const double* r = &htred[(size_t)NGR * toff[l]];
+      G.ggps[l].lengthscale = sum_grad_finish(*Sl, d, r, htard.data() + (size_t)d * toff[l], r[2], r[1], gps[l].variance,
+                                              gps[l].lengthscale, &G.tg[(size_t)l * LMM_SUM_MAX_TERMS * sum_grad_stride(d)],
+                                              &G.ggps[l].variance);
+      G.ggps[l].mean = r[4];
+      continue;
+    }
     const double* r = &hred[(size_t)NGR * l];
     G.galpha[l] = r[8];
     ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * l], &G.ggps[l].lengthscale, &G.gard[(size_t)l * d]);
@@ -2508,7 +2850,7 @@ int lmm_ilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int p
   if (int rc = input_grad_check(d, grad_x != nullptr)) return rc;
   IlmmGrad G;
   if (int rc = ilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, H, m, gps, jit, G, gy.p, nullptr, gx.p)) return rc;
-  ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, 0, m);
+  ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, 0, m, &G.tg);
   *out_logpdf = G.value;
   if (grad_sigma2) *grad_sigma2 = G.gs2[0];
   if (grad_H) std::copy(G.gH.begin(), G.gH.end(), grad_H);
@@ -2590,7 +2932,8 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
     }
   for (size_t q = 0; q < GJ.gard.size(); ++q) GJ.gard[q] -= GM.gard[q];
   for (size_t q = 0; q < GJ.galpha.size(); ++q) GJ.galpha[q] -= GM.galpha[q];
-  ard_publish(grad_gps ? &GJ.gard : nullptr, &GJ.galpha, 0, m);
+  for (size_t q = 0; q < GJ.tg.size(); ++q) GJ.tg[q] -= GM.tg[q];
+  ard_publish(grad_gps ? &GJ.gard : nullptr, &GJ.galpha, 0, m, &GJ.tg);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);
@@ -2839,7 +3182,7 @@ static int dense_posterior_build(const double* xd, int d, int n, const double* H
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
   hipStream_t st0 = g.streams[0];
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) lat[l] = to_dev(gps[l]);
+  for (int l = 0; l < m; ++l) lat[l] = dense_dev(gps[l]);
   const int N = m * n;
   Dims D(N, 1);
   lmm_post* P = new lmm_post();
@@ -2868,6 +3211,7 @@ static int dense_posterior_build(const double* xd, int d, int n, const double* H
     DenseArgs a{};
     a.A = P->L[0].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = P->x.p; a.d = d; a.n = n; a.m = m;
     a.lat = P->latd.p; a.sigmaT = STd.buf.p; a.sig_idx = idxd.p; a.rider = P->ddelta.p; a.rider_ld = N; a.nrider = 1;
+    a.has_sum = any_sum(P->gps.data(), m);
     launch_dense_assemble(a, st0);
     potrf_rec(P->L[0].p, D.ld, D.NR, 0, D.NC, P->W[0].p, N, info.p, st0);
     HIPCHK(hipMemsetAsync(P->alpha[0].p, 0, (size_t)D.NC * sizeof(double), st0));
@@ -2986,7 +3330,7 @@ int lmm_ilmm_post_mean_and_var(const lmm_post_t* post, double sigma2, const doub
 static void dense_post_cross(const lmm_post* P, const double* xsd, int d, int ns, int nr, double* R, int ldr, hipStream_t st) {
   const lmm_post* D = dense_state(P);
   guard_extent(R, nr, ldr, P->NC, true, "dense-H cross-Gram");
-  launch_dense_cross(R, ldr, nr, P->NC, xsd, ns, D->x.p, P->n, d, P->m, D->latd.p, st);
+  launch_dense_cross(R, ldr, nr, P->NC, xsd, ns, D->x.p, P->n, d, P->m, D->latd.p, any_sum(D->gps.data(), P->m) != 0, st);
   trsm_rec(R, ldr, nr, D->L[0].p, P->ld, D->W[0].p, 0, P->NC, st);
 }
 // Latent posterior means at xs, ml[l ns + s].  Float64: mu_l + K(x*, x) alpha_l (no solve needed).  fp32 compute mode: that sum cancels
@@ -2999,7 +3343,7 @@ static void dense_post_means(const lmm_post* P, const double* xsd, int d, int ns
   if (!g_f32) {
     Buf<double> pm_part(post_mean_partial_elems(ns, n));
     for (int l = 0; l < m; ++l)
-      launch_post_mean(xsd, ns, D->x.p, n, d, D->alpha[0].p + (size_t)l * n, to_dev(P->gps[l]), pm_part.p, ml + (size_t)l * ns, st);
+      post_mean_g(xsd, ns, D->x.p, n, d, D->alpha[0].p + (size_t)l * n, P->gps[l], pm_part.p, ml + (size_t)l * ns, st);
     HIPCHK(hipStreamSynchronize(st));              // pm_part is released on return
     return;
   }
@@ -3019,6 +3363,7 @@ static void dense_post_cov_factor(const lmm_post* P, const double* xsd, int d, i
   DenseArgs a{};
   a.A = A; a.ld = Ds.ld; a.nrows = Ds.NR; a.ncols = Ds.NC; a.x = xsd; a.d = d; a.n = ns; a.m = m;
   a.lat = D->latd.p; a.sigmaT = sigadd_dev; a.rider = rider; a.rider_ld = m * ns; a.nrider = rider ? 1 : 0;
+  a.has_sum = any_sum(D->gps.data(), m);
   guard_extent(A, Ds.NR, Ds.ld, Ds.NC, true, "dense-H posterior covariance");
   launch_dense_assemble(a, st);
   gemm_nt_g(A, Ds.ld, R, ldr, R, ldr, Ds.NC, Ds.NC, P->NC, 1, false, st, "Schur complement (dense-H posterior covariance)");
@@ -3215,7 +3560,7 @@ static int latent_marginals_dev(const lmm_post* P, const lmm_gp_t* gps_shard, in
     for (int k = 0; k < ms; ++k) {
       LatentDev gd = to_dev(gps_shard[k]);
       // prior: constant mean, variance kappa(0)
-      rider_stats_g(nullptr, 0, ns, 0, nullptr, gd.mean, gps_shard[k].variance, nullptr, mean_lat + (size_t)k * ns,
+      rider_stats_g(nullptr, 0, ns, 0, nullptr, gd.mean, prior_var(gps_shard[k]), nullptr, mean_lat + (size_t)k * ns,
                          var_lat + (size_t)k * ns, g.streams[0]);
     }
     return LMM_OK;
@@ -3255,7 +3600,7 @@ static int latent_marginals_dev(const lmm_post* P, const lmm_gp_t* gps_shard, in
       // mean = mu + K(x*,x) alpha = mu + R' (L^-1 delta);  var = kappa(0) - colsumsq(R)   (one pass over R)
       const double rb = (double)ns * P->n * 8.0;                   // R read once
       ProfScope ps(LMM_PROF_STRIP, rb, st, ns, P->n, 0, rb);
-      rider_stats_g(R[s][j].p, ldr, ns, P->n, P->z[k].p, gp.mean, gp.variance, part[s].p, mean_lat + (size_t)k * ns,
+      rider_stats_g(R[s][j].p, ldr, ns, P->n, P->z[k].p, gp.mean, prior_var(gp), part[s].p, mean_lat + (size_t)k * ns,
                          var_lat + (size_t)k * ns, st);
     }
   }
@@ -3320,8 +3665,8 @@ int lmm_oilmm_mean_and_var(const lmm_post_t* post, const lmm_gp_t* gps, const do
     Buf<double> pm_part(post ? post_mean_partial_elems(ns, post->n) : 1);
     for (int k = 0; k < ms; ++k) {
       const lmm_gp_t& gp = post ? post->gps[l0 + k] : gps[l0 + k];
-      launch_post_mean(xsd.p, ns, post ? post->x.p : nullptr, post ? post->n : 0, d, post ? post->alpha[k].p : nullptr, to_dev(gp),
-                       pm_part.p, ml.p + (size_t)k * ns, st0);
+      post_mean_g(xsd.p, ns, post ? post->x.p : nullptr, post ? post->n : 0, d, post ? post->alpha[k].p : nullptr, gp,
+                  pm_part.p, ml.p + (size_t)k * ns, st0);
     }
     DevOut mo(mean_out, (size_t)ns * p);
     mix_marginals(ml.p, ns, ms, Hd.buf.p, p, 1, 0.0, 0.0, mo.p, st0);
@@ -3352,9 +3697,13 @@ static int mean_var_grad_xs_dev(const lmm_post* P, int ms, const double* xsd, in
   const size_t count = (size_t)d * ns;
   if (vbar == nullptr) {
     Buf<double> part(pred_grad_x_partial_elems(P->n, ns, d));
-    for (int k = 0; k < ms; ++k)
-      launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, nullptr, nullptr, 0,
-                         to_dev(P->gps[P->l0 + k]), part.p, gout, k > 0, st0);
+    for (int k = 0; k < ms; ++k) {
+      const lmm_gp_t& gp = P->gps[P->l0 + k];
+      const SumTerms* Sk = sum_of(gp);
+      for (int c = 0; c < (Sk ? Sk->nt : 1); ++c)       // a sum latent: one accumulating pass per term
+        launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, nullptr, nullptr, 0,
+                           Sk ? Sk->ev[c] : to_dev(gp), part.p, gout, k > 0 || c > 0, st0);
+    }
     HIPCHK(hipStreamSynchronize(st0));
     return LMM_OK;
   }
@@ -3387,9 +3736,13 @@ static int mean_var_grad_xs_dev(const lmm_post* P, int ms, const double* xsd, in
     trsm_right_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st);    // R_j <- R_j L_j^-1 = K(x*, x) K_j^-1
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, vbar + (size_t)k * ns, R[s][j].p, ldr,
-                         to_dev(P->gps[P->l0 + k]), part[s].p, acc[s].p, used[s] != 0, st);
-      used[s] = 1;
+      const lmm_gp_t& gp = P->gps[P->l0 + k];
+      const SumTerms* Sk = sum_of(gp);
+      for (int c = 0; c < (Sk ? Sk->nt : 1); ++c) {
+        launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, vbar + (size_t)k * ns, R[s][j].p, ldr,
+                           Sk ? Sk->ev[c] : to_dev(gp), part[s].p, acc[s].p, used[s] != 0, st);
+        used[s] = 1;
+      }
     }
   }
   join_slots(nslots);

@@ -11,11 +11,16 @@ struct BatchInfo { int* p[LMM_MAX_BATCH]; };
 // kind: the BASE kernel kind (lmm_kernel_kind); ils: nullptr (isotropic, inv_ls) or the latent's d per-dimension inverse lengthscales
 // (device; an ARD latent, d > 1).  An ARD latent keeps inv_ls = 1 / its common multiplier (the gradient reduction's d/d multiplier).
 // alpha: the RQ shape (unused by the other kinds).
+// A sum latent (kind LMM_KERNEL_SUM) has nterms (1..LMM_SUM_MAX_TERMS) resolved terms in `terms` (device): each an ordinary base-kind
+// descriptor whose var = v0 v_c, inv_ls = 1 / (s0 l_c) and ils = its per-dimension 1 / (s0 l_c ard_c[k]) (or nullptr); var and inv_ls
+// of the sum latent itself are v0 and 1 / s0.  terms is nullptr and nterms 0 for every other latent.
 struct LatentDev {
   int kind;
   double var, inv_ls, mean;
   const double* ils;
   double alpha;
+  const LatentDev* terms;
+  int nterms;
 };
 
 // Gram / factor-matrix assembly arguments (see gram_kernel).
@@ -35,6 +40,7 @@ struct GramArgs {
   int* info_zero;                              // optional: the matrix's pivot-info word, zeroed by the launch (saves a memset per call)
   int cpw;                                     // column tiles per workgroup (set by the launcher: 4, or 1 when the grid would be small)
   double alpha;                                // RQ shape (unused by the other kinds)
+  const LatentDev* terms; int nterms;          // kind LMM_KERNEL_SUM: the resolved terms (device; see LatentDev)
 };
 
 // The same assembly for up to LMM_MAX_BATCH same-shaped matrices in ONE launch (blockIdx.z = matrix): everything in `base`
@@ -49,6 +55,8 @@ struct GramBatchArgs {
   double rider_sub[LMM_MAX_BATCH];
   int* info_zero[LMM_MAX_BATCH];
   double alpha[LMM_MAX_BATCH];
+  const LatentDev* terms[LMM_MAX_BATCH];
+  int nterms[LMM_MAX_BATCH];
 };
 
 struct DenseArgs {
@@ -58,16 +66,18 @@ struct DenseArgs {
   const double* sigmaT;      // device, m x m column-major (nbatch of them when sig_idx != nullptr)
   const int* sig_idx;        // optional, device, n entries: which sigmaT the point's noise block uses (sequential conditioning)
   const double* rider; int rider_ld, nrider;
+  int has_sum;               // some lat[l] is a sum latent (the kernel instantiation that evaluates kappa_sum)
 };
 
 void launch_gram(const GramArgs& a, hipStream_t st);
-// nb same-shaped assemblies (differing only in A, kind, var, inv_ls, ils, alpha, diag_add, diag_vec, rider): one launch per run of equal kinds
+// nb same-shaped assemblies (differing only in A, kind, var, inv_ls, ils, alpha, terms, diag_add, diag_vec, rider): one launch per run of
+// equal kinds (sum latents form runs too; their terms may differ per matrix)
 void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st);
 void launch_dense_assemble(const DenseArgs& a, hipStream_t st);
 void launch_dense_cov(const double* S, int lds, int ns, int m, const double* Hm, int p, double jitter, double sigma2, double* T,
                       double* out, hipStream_t st);
 void launch_dense_cross(double* R, int ldr, int nrows, int ncols, const double* xs, int ns, const double* x, int n, int d,
-                        int m, const LatentDev* lat, hipStream_t st);
+                        int m, const LatentDev* lat, bool has_sum, hipStream_t st);
 size_t dense_var_partial_elems(int ns, int p, int Ncols);
 void launch_dense_var(const double* R, int ldr, int ns, int m, int Ncols, const double* Hm, int p, const LatentDev* lat,
                       double jitter, double sigma2, double* partial, double* out, hipStream_t st);

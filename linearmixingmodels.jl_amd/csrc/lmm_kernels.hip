@@ -177,6 +177,30 @@ __device__ __forceinline__ double sqrt_dist(double x) {
   return (x > 1e-300) ? r : 0.0;
 }
 
+// A sum latent's kernel at the pair (a, b): sum over its terms (LatentDev.terms) of kappa_c, each term with its own variance v0 v_c,
+// lengthscale and kind.  The raw difference (d == 1) or squared distance (d > 1) is computed once and scaled per isotropic term by
+// inv_ls_c (inv_ls_c^2); a term with per-dimension lengthscales (ils, d > 1 only: d == 1 terms are folded on the host) takes its own
+// pass over the d coordinates.
+__device__ __forceinline__ double kappa_sum(const LatentDev* __restrict__ T, int nt, const double* __restrict__ a,
+                                            const double* __restrict__ b, int d) {
+  double dx = 0.0, D2 = 0.0;
+  if (d == 1) dx = fabs(a[0] - b[0]);
+  else
+    for (int k = 0; k < d; ++k) { const double t = a[k] - b[k]; D2 = __builtin_fma(t, t, D2); }
+  double acc = 0.0;
+  for (int c = 0; c < nt; ++c) {
+    const LatentDev g = T[c];
+    double r, r2;
+    if (d == 1) { r = dx * g.inv_ls; r2 = r * r; }
+    else {
+      r2 = g.ils ? scaled_dist2(a, b, d, g.inv_ls, g.ils) : D2 * (g.inv_ls * g.inv_ls);
+      r = sqrt(r2);
+    }
+    acc += kappa(g.kind, g.var, r, r2, g.alpha);
+  }
+  return acc;
+}
+
 // 16-byte store of two consecutive rows of a Gram column (non-temporal stores measured no different: 4.7-4.9 TB/s either way, round 2)
 template <typename TS>
 __device__ __forceinline__ void gram_store(void* base, size_t idx, d2 v) { MatIO<TS>::st2(base, idx, v); }
@@ -231,11 +255,15 @@ __device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int
       for (int e = 0; e < 2; ++e) {
         double val = 0.0;
         if (rtype[e] == 0 || rtype[e] == 3) {
-          double r, r2;
-          if (a.d == 1) { r = fabs(rx[e] - xj) * a.inv_ls; r2 = r * r; }
-          else { r2 = scaled_dist2(rpt[e], a.x + (size_t)j * a.d, a.d, a.inv_ls, a.ils); r = sqrt(r2); }
-          if (KIND <= LMM_KERNEL_MATERN52) val = kappa(a.kind, a.var, r, r2);
-          else val = kappa_t<KIND>(a.var, r, r2, a.alpha);
+          if constexpr (KIND == LMM_KERNEL_SUM) {
+            val = kappa_sum(a.terms, a.nterms, rpt[e], a.x + (size_t)j * a.d, a.d);
+          } else {
+            double r, r2;
+            if (a.d == 1) { r = fabs(rx[e] - xj) * a.inv_ls; r2 = r * r; }
+            else { r2 = scaled_dist2(rpt[e], a.x + (size_t)j * a.d, a.d, a.inv_ls, a.ils); r = sqrt(r2); }
+            if (KIND <= LMM_KERNEL_MATERN52) val = kappa(a.kind, a.var, r, r2);
+            else val = kappa_t<KIND>(a.var, r, r2, a.alpha);
+          }
           if (rtype[e] == 0 && i0 + e == j) val += a.diag_add + (a.diag_vec ? a.diag_vec[j] : 0.0);
         } else if (rtype[e] == 2) {
           val = rpt[e][j] - a.rider_sub;
@@ -418,10 +446,24 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
   }
 }
 
+// Sum latents (KIND = LMM_KERNEL_SUM): every tile of the strip takes the generic routine, which sums the terms per element, so each
+// element is written once (assembly is write-bound: a pass per term would cost a full write each).  No separable d = 1 path.
+template <typename TS>
+__device__ __forceinline__ void gram_body_sum(const GramArgs& a) {
+  const int ti = blockIdx.x + a.row_tile0, sy = blockIdx.y;
+  for (int c4 = 0; c4 < a.cpw; ++c4) {
+    const int tj = sy * a.cpw + c4;
+    if (tj * 64 >= a.ncols) break;
+    if (!a.full && ti < tj) break;                          // lower tiles only
+    gram_tile_generic<LMM_KERNEL_SUM, TS>(a, ti, tj);
+  }
+}
+
 template <int KIND, bool ND, typename TS>
 __global__ __launch_bounds__(256) void gram_kernel(GramArgs a) {
   if (a.info_zero && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.info_zero = 0;
-  gram_body<KIND, ND, TS>(a);
+  if constexpr (KIND == LMM_KERNEL_SUM) gram_body_sum<TS>(a);
+  else gram_body<KIND, ND, TS>(a);
 }
 
 template <int KIND, bool ND, typename TS>
@@ -430,13 +472,19 @@ __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
   const int z = blockIdx.z;
   a.A = b.A[z]; a.var = b.var[z]; a.inv_ls = b.inv_ls[z]; a.ils = b.ils[z]; a.alpha = b.alpha[z]; a.diag_add = b.diag_add[z]; a.diag_vec = b.diag_vec[z]; a.rider = b.rider[z]; a.rider_sub = b.rider_sub[z];
   if (b.info_zero[z] && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *b.info_zero[z] = 0;
-  gram_body<KIND, ND, TS>(a);
+  if constexpr (KIND == LMM_KERNEL_SUM) {
+    a.terms = b.terms[z]; a.nterms = b.nterms[z];
+    gram_body_sum<TS>(a);
+  } else {
+    gram_body<KIND, ND, TS>(a);
+  }
 }
 
 // K8: dense ILMM latent covariance  blockdiag(K_1..K_m) + SigmaT (x) I_n  (+ mean-free rider row):
 // element (i, j), i = li*n + ii, j = lj*n + jj  ->  [li == lj] kappa_li(x_ii, x_jj) + [ii == jj] SigmaT[li, lj].
-// Reference: src/ilmm.jl:160 kron(SigmaT, I) + src/independent_mogp.jl:60-63 BlockDiagonal.
-template <typename TS>
+// Reference: src/ilmm.jl:160 kron(SigmaT, I) + src/independent_mogp.jl:60-63 BlockDiagonal.  A sum latent (LatentDev.terms) takes kappa_sum here and
+// in dense_cross_kernel; its var is kappa(0) = v0 sum_c v_c in these arrays (dense_var_kernel reads it).
+template <typename TS, bool SUM>      // SUM: some latent is a sum (SUM = false keeps the code and registers the kernel always had)
 __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
   const int ti = blockIdx.x, tj = blockIdx.y;
   if (ti < tj) return;
@@ -463,10 +511,14 @@ __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
         if (i < N) {
           if (li[e] == lj) {
             const LatentDev g = a.lat[lj];
-            double r, r2;
-            if (a.d == 1) { r = fabs(a.x[ii[e]] - a.x[jj]) * g.inv_ls; r2 = r * r; }
-            else { r2 = scaled_dist2(a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d, g.inv_ls, g.ils); r = sqrt(r2); }
-            val = kappa(g.kind, g.var, r, r2, g.alpha);
+            if (SUM && g.kind == LMM_KERNEL_SUM) {
+              val = kappa_sum(g.terms, g.nterms, a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d);
+            } else {
+              double r, r2;
+              if (a.d == 1) { r = fabs(a.x[ii[e]] - a.x[jj]) * g.inv_ls; r2 = r * r; }
+              else { r2 = scaled_dist2(a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d, g.inv_ls, g.ils); r = sqrt(r2); }
+              val = kappa(g.kind, g.var, r, r2, g.alpha);
+            }
           }
           if (ii[e] == jj) val += a.sigmaT[(size_t)(a.sig_idx ? a.sig_idx[jj] : 0) * a.m * a.m + li[e] + lj * a.m];
         } else if (i >= a.ncols) {
@@ -483,7 +535,7 @@ __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
 
 // Dense-ILMM cross-covariance riders: row (l, s) of R (m*ns rows) is K_l(xs_s, x) placed in the column block of
 // latent l (reference src/independent_mogp.jl:66-71: block-diagonal cov(f, x, y)); zero elsewhere and in the pad.
-template <typename TS>
+template <typename TS, bool SUM>
 __global__ __launch_bounds__(256) void dense_cross_kernel(void* __restrict__ R, int ldr, int nrows, int /*ncols*/,
                                                           const double* __restrict__ xs, int ns,
                                                           const double* __restrict__ x, int n, int d, int m,
@@ -497,10 +549,14 @@ __global__ __launch_bounds__(256) void dense_cross_kernel(void* __restrict__ R, 
     const int lj = j / n, jj = j - lj * n;
     if (lj == l) {
       const LatentDev g = lat[l];
-      double rr, r2;
-      if (d == 1) { rr = fabs(xs[s] - x[jj]) * g.inv_ls; r2 = rr * rr; }
-      else { r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)jj * d, d, g.inv_ls, g.ils); rr = sqrt(r2); }
-      val = kappa(g.kind, g.var, rr, r2, g.alpha);
+      if (SUM && g.kind == LMM_KERNEL_SUM) {
+        val = kappa_sum(g.terms, g.nterms, xs + (size_t)s * d, x + (size_t)jj * d, d);
+      } else {
+        double rr, r2;
+        if (d == 1) { rr = fabs(xs[s] - x[jj]) * g.inv_ls; r2 = rr * rr; }
+        else { r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)jj * d, d, g.inv_ls, g.ils); rr = sqrt(r2); }
+        val = kappa(g.kind, g.var, rr, r2, g.alpha);
+      }
     }
   }
   MatIO<TS>::st1(R, (size_t)j * ldr + r, val);
@@ -4030,7 +4086,8 @@ void launch_gram(const GramArgs& a0, hipStream_t st) {
     if (nd) LMM_TS_LAUNCH((gram_kernel<K, true, TS>), grid, dim3(256), 0, st, a);                   \
     else LMM_TS_LAUNCH((gram_kernel<K, false, TS>), grid, dim3(256), 0, st, a);                     \
   } while (0)
-  if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
+  if (a.kind == LMM_KERNEL_SUM) LMM_TS_LAUNCH((gram_kernel<LMM_KERNEL_SUM, false, TS>), grid, dim3(256), 0, st, a);
+  else if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
   else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
   else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
   else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
@@ -4049,6 +4106,7 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     for (int j = j0; j < j1; ++j) {
       const GramArgs& a = args[j];
       b.A[j - j0] = a.A; b.var[j - j0] = a.var; b.inv_ls[j - j0] = a.inv_ls; b.ils[j - j0] = a.ils; b.alpha[j - j0] = a.alpha; b.diag_add[j - j0] = a.diag_add;
+      b.terms[j - j0] = a.terms; b.nterms[j - j0] = a.nterms;
       b.diag_vec[j - j0] = a.diag_vec; b.rider[j - j0] = a.rider; b.rider_sub[j - j0] = a.rider_sub; b.info_zero[j - j0] = a.info_zero;
     }
     b.base.cpw = gram_cpw(b.base.nrows / 64 - b.base.row_tile0, b.base.ncols / 64, j1 - j0);
@@ -4060,7 +4118,8 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
       if (nd) LMM_TS_LAUNCH((gram_batch_kernel<K, true, TS>), grid, dim3(256), 0, st, b);           \
       else LMM_TS_LAUNCH((gram_batch_kernel<K, false, TS>), grid, dim3(256), 0, st, b);             \
     } while (0)
-    if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
+    if (a.kind == LMM_KERNEL_SUM) LMM_TS_LAUNCH((gram_batch_kernel<LMM_KERNEL_SUM, false, TS>), grid, dim3(256), 0, st, b);
+    else if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
     else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
     else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
     else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
@@ -4071,9 +4130,10 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
 }
 
 void launch_dense_cross(double* R, int ldr, int nrows, int ncols, const double* xs, int ns, const double* x, int n, int d,
-                        int m, const LatentDev* lat, hipStream_t st) {
+                        int m, const LatentDev* lat, bool has_sum, hipStream_t st) {
   dim3 grid((nrows + 255) / 256, ncols);
-  LMM_TS_LAUNCH((dense_cross_kernel<TS>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
+  if (has_sum) LMM_TS_LAUNCH((dense_cross_kernel<TS, true>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
+  else LMM_TS_LAUNCH((dense_cross_kernel<TS, false>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
 }
 
 int dense_var_kc(int Ncols) { int kc = ((Ncols + 127) / 128 + 63) / 64 * 64; return kc < 64 ? 64 : kc; }   // <= 128 chunks
@@ -4100,7 +4160,8 @@ void launch_dense_cov(const double* S, int lds, int ns, int m, const double* Hm,
 
 void launch_dense_assemble(const DenseArgs& a, hipStream_t st) {
   dim3 grid(a.nrows / 64, a.ncols / 64);
-  LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS>), grid, dim3(256), 0, st, a);      // fp32 compute mode: Float32 matrix (the dense logpdf paths)
+  if (a.has_sum) LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, true>), grid, dim3(256), 0, st, a);
+  else LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, false>), grid, dim3(256), 0, st, a);      // fp32 compute mode: Float32 matrix (the dense logpdf paths)
 }
 
 // ---- round 3: 128-column panels (leaf128 / bulk) and the update fused with the next panel's leaf (K2c) ----

@@ -113,6 +113,31 @@ _alpha(k::Kernel) = nothing
 _alpha(k::RationalQuadraticKernel) = Float64(only(k.α))
 _alpha(k::ScaledKernel) = _alpha(k.kernel)
 _alpha(k::TransformedKernel) = _alpha(k.kernel)
+# Sum kernels (KernelFunctions' KernelSum, k1 + k2): kind 5 with a sum tag (lmm_kernel_sum_create).  `_desc` of the sum is (5, 1, 1), so
+# a ScaledKernel / ScaleTransform around it gives the latent's outer variance v0 and lengthscale s0; each term is read with the
+# single-kernel methods above.  A nested sum with unit outer variance and lengthscale is flattened; any other is rejected, as is an
+# ARDTransform around a whole sum.
+_desc(k::KernelSum) = (Cint(5), 1.0, 1.0)
+_desc(k::TransformedKernel{<:KernelSum,<:ARDTransform}) =
+    error("LinearMixingModelsHIP: an ARDTransform around a whole KernelSum is not served (put it on the terms)")
+_terms(k::Kernel) = nothing
+_terms(k::ScaledKernel) = _terms(k.kernel)
+_terms(k::TransformedKernel) = _terms(k.kernel)
+function _terms(k::KernelSum)
+    out = Kernel[]
+    for t in k.kernels
+        tt = _terms(t)
+        if tt === nothing
+            push!(out, t)
+        else
+            (_, v, l) = _desc(t)
+            (v == 1.0 && l == 1.0) || error("LinearMixingModelsHIP: a scaled KernelSum cannot be a term of another sum")
+            append!(out, tt)
+        end
+    end
+    length(out) <= 4 || error("LinearMixingModelsHIP: a KernelSum has at most 4 terms (got $(length(out)))")
+    return out
+end
 _mean(::AbstractGPs.ZeroMean) = 0.0
 _mean(m::AbstractGPs.ConstMean) = Float64(m.c)
 # `_gps(fs) do gps, tags ... end`: the lmm_gp_t array of the latents fs (nothing: none, for calls on a posterior handle) for the
@@ -123,42 +148,79 @@ struct KTag
     id::Cint
     ard::Bool      # the tag holds per-dimension factors
     alpha::Bool    # the tag holds an RQ shape
+    terms::Vector{KTag}   # a sum tag: its terms' tags (empty otherwise)
+end
+KTag(id, ard, alpha) = KTag(id, ard, alpha, KTag[])
+# the factor / alpha tag of one kernel (a latent's or a sum term's); 0: none needed
+function _ktag(a, α)
+    tr = Ref{Cint}(0)
+    if a !== nothing && α === nothing
+        GC.@preserve a check(ccall((:lmm_ard_create, liblmm), Cint, (Cint, Ptr{Cdouble}, Ref{Cint}), length(a), a, tr))
+    elseif α !== nothing
+        av = a === nothing ? Float64[] : a
+        GC.@preserve av check(ccall((:lmm_kernel_tag_create, liblmm), Cint, (Cint, Ptr{Cdouble}, Cdouble, Ref{Cint}),
+                                    length(av), a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(av), α, tr))
+    end
+    return tr[]
+end
+function _destroy(t::KTag)
+    t.id == 0 || ccall((:lmm_ard_destroy, liblmm), Cint, (Cint,), t.id)      # a sum tag before its terms' tags
+    foreach(_destroy, t.terms)
 end
 function _gps(body, fs)
     gps = LmmGp[]; tags = KTag[]
     try
         for f in (fs === nothing ? () : fs)
-            (kd, v, l) = _desc(f.kernel); a = _ard(f.kernel); α = _alpha(f.kernel); t = Cint(0)
-            if a !== nothing && α === nothing
+            (kd, v, l) = _desc(f.kernel)
+            if kd == 5
+                tts = KTag[]; tgps = LmmGp[]
+                push!(tags, KTag(Cint(0), false, false, tts))    # registered first, so that the finally destroys the term tags on error
+                for k in _terms(f.kernel)
+                    (tk, tv, tl) = _desc(k); a = _ard(k); α = _alpha(k)
+                    t = _ktag(a, α)
+                    push!(tts, KTag(t, a !== nothing, α !== nothing))
+                    push!(tgps, LmmGp(t == 0 ? tk : tk | (t << 8), tv, tl, 0.0))
+                end
                 tr = Ref{Cint}(0)
-                GC.@preserve a check(ccall((:lmm_ard_create, liblmm), Cint, (Cint, Ptr{Cdouble}, Ref{Cint}), length(a), a, tr))
-                t = tr[]
-            elseif α !== nothing
-                tr = Ref{Cint}(0); av = a === nothing ? Float64[] : a
-                GC.@preserve av check(ccall((:lmm_kernel_tag_create, liblmm), Cint, (Cint, Ptr{Cdouble}, Cdouble, Ref{Cint}),
-                                            length(av), a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(av), α, tr))
-                t = tr[]
+                GC.@preserve tgps check(ccall((:lmm_kernel_sum_create, liblmm), Cint, (Cint, Ptr{LmmGp}, Ref{Cint}),
+                                              length(tgps), pointer(tgps), tr))
+                tags[end] = KTag(tr[], false, false, tts)
+                push!(gps, LmmGp(kd | (tr[] << 8), v, l, _mean(f.mean)))
+                continue
             end
+            a = _ard(f.kernel); α = _alpha(f.kernel)
+            t = _ktag(a, α)
             push!(tags, KTag(t, a !== nothing, α !== nothing))
             push!(gps, LmmGp(t == 0 ? kd : kd | (t << 8), v, l, _mean(f.mean)))
         end
         return body(gps, tags)
     finally
-        for t in tags
-            t.id == 0 || ccall((:lmm_ard_destroy, liblmm), Cint, (Cint,), t.id)
-        end
+        foreach(_destroy, tags)
     end
 end
 # after a gradient call inside _gps, per latent: nothing (no tag) or (ard = d logpdf / d ard[k] (lmm_ard_grad) or nothing,
 # alpha = d logpdf / d alpha (lmm_kernel_tag_alpha_grad) or nothing)
-function _ard_grads(tags::Vector{KTag}, d::Integer)
-    return [t.id == 0 ? nothing :
-            (ard = t.ard ? (g = Vector{Float64}(undef, d);
-                            GC.@preserve g check(ccall((:lmm_ard_grad, liblmm), Cint, (Cint, Ptr{Cdouble}), t.id, g)); g) : nothing,
-             alpha = t.alpha ? (r = Ref{Cdouble}(0.0);
-                                check(ccall((:lmm_kernel_tag_alpha_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) : nothing)
-            for t in tags]
+# A sum latent: (ard = nothing, alpha = nothing, terms = per term (variance, lengthscale, ard, alpha) from lmm_kernel_sum_grad and
+# the terms' own tags).
+function _tag_grads(t::KTag, d::Integer)
+    t.id == 0 && return nothing
+    terms = nothing
+    if !isempty(t.terms)
+        g = Vector{LmmGpGrad}(undef, length(t.terms))
+        GC.@preserve g check(ccall((:lmm_kernel_sum_grad, liblmm), Cint, (Cint, Ptr{LmmGpGrad}), t.id, pointer(g)))
+        terms = map(eachindex(t.terms)) do c
+            tg = _tag_grads(t.terms[c], d)          # the term's own tag: once per term
+            (variance = g[c].variance, lengthscale = g[c].lengthscale,
+             ard = tg === nothing ? nothing : tg.ard, alpha = tg === nothing ? nothing : tg.alpha)
+        end
+    end
+    return (ard = t.ard ? (g = Vector{Float64}(undef, d);
+                           GC.@preserve g check(ccall((:lmm_ard_grad, liblmm), Cint, (Cint, Ptr{Cdouble}), t.id, g)); g) : nothing,
+            alpha = t.alpha ? (r = Ref{Cdouble}(0.0);
+                               check(ccall((:lmm_kernel_tag_alpha_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) : nothing,
+            terms = terms)
 end
+_ard_grads(tags::Vector{KTag}, d::Integer) = [_tag_grads(t, d) for t in tags]
 
 # x as a d x n column-major matrix: Vector{Float64} => 1 x n; ColVecs => its X; RowVecs => transposed copy.
 _xmat(x::AbstractVector{<:Real}) = reshape(collect(Float64, x), 1, :)
@@ -621,22 +683,42 @@ AbstractGPs.var(f::HIPMOGP, x::MOIsotopic) = _mean_var(f, x)[2]
 # ga: d/d ard[k] of an ARD latent (lmm_ard_grad; gl is then d/d the common multiplier).  ARDTransform(v): ard = ard_inner ./ v
 # -> d/dv_k = -ga_k ard_inner_k / v_k^2 (with no inner factors, ℓ_k = multiplier / v_k: d/dv_k = -ℓ_k^2 d/dℓ_k), d/d ard_inner = ga ./ v.
 # gα: d/d alpha of an RQ latent (lmm_kernel_tag_alpha_grad), nothing otherwise
-_ktangent(k::Kernel, gv, gl, ga=nothing, gα=nothing) = NoTangent()            # SEKernel() etc. carry no parameters
-_ktangent(k::RationalQuadraticKernel, gv, gl, ga=nothing, gα=nothing) =
+# gt: the per-term gradients of a sum latent (_tag_grads(...).terms), nothing otherwise.
+_ktangent(k::Kernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) = NoTangent()            # SEKernel() etc. carry no parameters
+_ktangent(k::RationalQuadraticKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) =
     gα === nothing ? NoTangent() : Tangent{typeof(k)}(; α=[gα], metric=NoTangent())
-function _ktangent(k::ScaledKernel, gv, gl, ga=nothing, gα=nothing)
+function _ktangent(k::ScaledKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing)
     (_, vin, _) = _desc(k.kernel)
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv * only(k.σ²), gl, ga, gα), σ²=[gv * vin])
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv * only(k.σ²), gl, ga, gα, gt), σ²=[gv * vin])
 end
-function _ktangent(k::TransformedKernel{<:Kernel,<:ScaleTransform}, gv, gl, ga=nothing, gα=nothing)
+function _ktangent(k::TransformedKernel{<:Kernel,<:ScaleTransform}, gv, gl, ga=nothing, gα=nothing, gt=nothing)
     (_, _, lin) = _desc(k.kernel); s = only(k.transform.s)
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl / s, ga, gα), transform=Tangent{typeof(k.transform)}(; s=[-gl * lin / s^2]))
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl / s, ga, gα, gt), transform=Tangent{typeof(k.transform)}(; s=[-gl * lin / s^2]))
 end
-function _ktangent(k::TransformedKernel{<:Kernel,<:ARDTransform}, gv, gl, ga=nothing, gα=nothing)
+# A sum: the outer (gv, gl) went to the ScaledKernel / ScaleTransform around it; each term gets its own tangent from gt, in the
+# flattened order of _terms.  A nested sum (flattened because its wrappers have unit scale) takes the next entries; its wrappers see
+# gv = sum_c v_c d/dv_c and gl = sum_c l_c d/dl_c, the derivatives with respect to a scale of 1 on its variance and lengthscale.
+function _ktangent(k::KernelSum, gv, gl, ga=nothing, gα=nothing, gt=nothing)
+    gt === nothing && return NoTangent()
+    i = Ref(0)
+    function term(t)
+        tt = _terms(t)
+        if tt !== nothing
+            n = length(tt); sub = gt[i[] + 1:i[] + n]; i[] += n
+            gv = sum(_desc(tk)[2] * g.variance for (tk, g) in zip(tt, sub))
+            gl = sum(_desc(tk)[3] * g.lengthscale for (tk, g) in zip(tt, sub))
+            return _ktangent(t, gv, gl, nothing, nothing, sub)
+        end
+        g = gt[i[] += 1]
+        return _ktangent(t, g.variance, g.lengthscale, g.ard, g.alpha)
+    end
+    return Tangent{typeof(k)}(; kernels=Tuple(term(t) for t in k.kernels))
+end
+function _ktangent(k::TransformedKernel{<:Kernel,<:ARDTransform}, gv, gl, ga=nothing, gα=nothing, gt=nothing)
     v = Vector{Float64}(k.transform.v); ain = _ard(k.kernel)
-    ga === nothing && return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl, nothing, gα), transform=NoTangent())
+    ga === nothing && return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl, nothing, gα, gt), transform=NoTangent())
     a0 = ain === nothing ? ones(length(v)) : ain
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl, ain === nothing ? nothing : ga ./ v, gα),
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl, ain === nothing ? nothing : ga ./ v, gα, gt),
                               transform=Tangent{typeof(k.transform)}(; v=-ga .* a0 ./ v .^ 2))
 end
 _mtangent(::AbstractGPs.ZeroMean, g) = NoTangent()
@@ -647,7 +729,11 @@ _fstangent(fs::Vector{<:AbstractGP}, gg::Vector{LmmGpGrad}, Δ, gard=nothing) =
     [Tangent{typeof(f)}(; mean=_mtangent(f.mean, Δ * g.mean),
                           kernel=_ktangent(f.kernel, Δ * g.variance, Δ * g.lengthscale,
                                            (ga = _tagfield(gard, l, :ard); ga === nothing ? nothing : Δ .* ga),
-                                           (gα = _tagfield(gard, l, :alpha); gα === nothing ? nothing : Δ * gα)))
+                                           (gα = _tagfield(gard, l, :alpha); gα === nothing ? nothing : Δ * gα),
+                                           (gt = _tagfield(gard, l, :terms); gt === nothing ? nothing :
+                                            [(variance = Δ * t.variance, lengthscale = Δ * t.lengthscale,
+                                              ard = t.ard === nothing ? nothing : Δ .* t.ard, alpha = t.alpha === nothing ? nothing : Δ * t.alpha)
+                                             for t in gt])))
      for (l, (f, g)) in enumerate(zip(fs, gg))]
 _noise_tangent(fx, g) = Tangent{typeof(fx.Σy)}(; diag=Tangent{typeof(fx.Σy.diag)}(; value=g))     # Fill(σ², n p): one parameter
 # Input locations: the library's d logpdf / d x (G, d x n) as the cotangent of the FiniteGP's x = MOInputIsotopicByOutputs(inner, p):

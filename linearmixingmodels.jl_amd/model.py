@@ -50,6 +50,23 @@ class _Kernel:
         ls = self.lengthscale if isinstance(self.lengthscale, float) else list(self.lengthscale.tolist())
         return f"{type(self).__name__}(variance={self.variance}, lengthscale={ls})"
 
+    def __add__(self, o):
+        """k1 + k2: KernelFunctions' KernelSum (flattened: see KernelSum)."""
+        if not isinstance(o, _Kernel):
+            return NotImplemented
+        return KernelSum(self, o)
+
+    def desc(self) -> dict:
+        """Descriptor of this kernel (a latent's, or a term's of a sum kernel)."""
+        d = {"kind": self.kind, "variance": self.variance, "lengthscale": self.lengthscale}
+        if hasattr(self, "alpha"):
+            d["alpha"] = self.alpha
+        return d
+
+    def key(self) -> tuple:
+        """Hashable form of the kernel's values (the latent-array cache key)."""
+        return (self.kind, self.variance, _ls_key(self.lengthscale), getattr(self, "alpha", None))
+
 
 class SEKernel(_Kernel):
     kind = "se"
@@ -88,6 +105,45 @@ class RationalQuadraticKernel(_Kernel):
         return super().__repr__()[:-1] + f", alpha={self.alpha})"
 
 
+class KernelSum(_Kernel):
+    """variance * sum_c kernels[c](|x - x'| / lengthscale): KernelFunctions' KernelSum (k1 + k2 + ...), with `variance` and the scalar
+    `lengthscale` the ScaledKernel and ScaleTransform around the whole sum (1.0: none).  Each term is a base kernel with its own
+    variance, lengthscale (a float, or a length-d vector), and RQ alpha.  A term that is itself a sum with unit variance and
+    lengthscale is flattened into its terms; any other nested sum is rejected.  At most 4 terms."""
+    kind = "sum"
+
+    def __init__(self, *kernels, variance: float = 1.0, lengthscale: float = 1.0):
+        if np.ndim(lengthscale) != 0:
+            raise ValueError("per-dimension lengthscales around a whole sum kernel are not supported")
+        super().__init__(variance, lengthscale)
+        terms = []
+        for k in kernels:
+            if isinstance(k, KernelSum):
+                if k.variance != 1.0 or k.lengthscale != 1.0:
+                    raise ValueError("a scaled sum kernel cannot be a term of another sum")
+                terms.extend(k.kernels)
+            elif isinstance(k, _Kernel):
+                terms.append(k)
+            else:
+                raise TypeError(f"not a kernel: {k!r}")
+        if not 1 <= len(terms) <= L.SUM_MAX_TERMS:
+            raise ValueError(f"a sum kernel has 1..{L.SUM_MAX_TERMS} terms, got {len(terms)}")
+        self.kernels = tuple(terms)
+
+    def __eq__(self, o):
+        return super().__eq__(o) and self.kernels == o.kernels
+
+    def __repr__(self):
+        return f"KernelSum({', '.join(map(repr, self.kernels))}, variance={self.variance}, lengthscale={self.lengthscale})"
+
+    def desc(self) -> dict:
+        return {"kind": "sum", "variance": self.variance, "lengthscale": self.lengthscale,
+                "terms": [k.desc() for k in self.kernels]}
+
+    def key(self) -> tuple:
+        return ("sum", self.variance, self.lengthscale, tuple(k.key() for k in self.kernels))
+
+
 class GP:
     """GP(kernel) or GP(mean_const, kernel)."""
 
@@ -98,9 +154,8 @@ class GP:
             self.mean, self.kernel = float(args[0]), args[1]
 
     def desc(self) -> dict:
-        d = {"kind": self.kernel.kind, "variance": self.kernel.variance, "lengthscale": self.kernel.lengthscale, "mean": self.mean}
-        if hasattr(self.kernel, "alpha"):
-            d["alpha"] = self.kernel.alpha
+        d = self.kernel.desc()
+        d["mean"] = self.mean
         return d
 
     def __eq__(self, o):
@@ -391,8 +446,7 @@ def _split_train_grad(gy, sizes, p: int):
 def _gps_arg(mogp):
     """(descs, lmm_gp_t array) of an IndependentMOGP's latents.  The ctypes array is rebuilt only when a hyperparameter changed (the key
     is the tuple of current values: building it costs a third of filling the array, which at m = 20 is 25 us of a 380-us call)."""
-    key = tuple((g.kernel.kind, g.kernel.variance, _ls_key(g.kernel.lengthscale), getattr(g.kernel, "alpha", None), g.mean)
-                for g in mogp.fs)
+    key = tuple((g.kernel.key(), g.mean) for g in mogp.fs)
     hit = getattr(mogp, "_gps_cache", None)
     if hit is not None and hit[0] == key:
         return hit[1], hit[2]
@@ -524,9 +578,14 @@ def _split_train_x(gx0, train, sizes):
 def _gps_grads(gg, ga, m: int, d: int) -> list:
     """The latents' kernel-parameter gradients: "lengthscale" is a float for an isotropic latent and, for a per-dimension (ARD) one,
     the length-d array d logpdf / d lengthscale_k (its tag's lmm_ard_grad: the array passes multiplier 1).  An RQ latent adds
-    "alpha" (its tag's lmm_kernel_tag_alpha_grad)."""
+    "alpha" (its tag's lmm_kernel_tag_alpha_grad).  A sum latent's "variance" and "lengthscale" are those of the whole sum, and its
+    "terms" hold the per-term gradients (ArdTags.sum_grad)."""
     out = []
     for l in range(m):
+        if ga.ard.terms[l] is not None:
+            out.append({"variance": gg[l].variance, "lengthscale": gg[l].lengthscale, "mean": gg[l].mean,
+                        "terms": ga.ard.sum_grad(l, d)})
+            continue
         ls = ga.ard.grad(l, d) if ga.ard.has_ard[l] else gg[l].lengthscale
         out.append({"variance": gg[l].variance, "lengthscale": ls, "mean": gg[l].mean})
         if ga.ard.has_alpha[l]:
