@@ -290,16 +290,23 @@ struct Dims {
   size_t elems() const { return (size_t)ld * NC; }
 };
 
-// ---- per-dimension (ARD) lengthscales ----------------------------------------------------------------------------------------
-// The user-facing registry (lmm_ard_create / _destroy / _grad) maps a tag to d factors and keeps the tag's latest gradient; it has
-// its own mutex and never takes the context lock for longer than a try-lock on an error message.  An entry point RESOLVES the tags of
-// its latents once (resolve_gps, under the context lock): a latent whose factors are all equal (or d == 1) is folded into the
-// isotropic descriptor; every other ARD latent gets its effective inverse lengthscales 1 / (lengthscale * ard[k]) uploaded to the
-// device, and its kind word is rewritten to  base | (slot + 1) << 8  with `slot` an index of g_slot, the table of the device
-// vectors (and RQ shapes) that live calls and posterior handles hold.  Everything downstream reads the base kind (kind & 0xff), the
-// vector through ils_of() and the RQ shape through alpha_of(); the slot table is process state guarded by the context lock like the
-// rest of the context.  A tag may carry an RQ shape alpha instead of, or besides, factors (lmm_kernel_tag_create): an RQ latent
-// naming it gets a slot holding its alpha (ils nullptr when it has no factors or was folded).
+// ---- latent kernels, resolved ------------------------------------------------------------------------------------------------
+// The user-facing registry (lmm_ard_create / lmm_kernel_tag_create / lmm_kernel_sum_create / _destroy / _grad) maps a tag to d
+// per-dimension factors, an RQ shape alpha, or the terms of a sum kernel, and keeps the tag's latest gradient; it has its own mutex
+// and never takes the context lock for longer than a try-lock on an error message.  A caller's lmm_gp_t names a tag in the high bits
+// of `kind`.  An entry point turns its caller's array into a LatentSet ONCE (resolve, under the context lock) and everything below
+// it takes `const Latent&`: a caller's descriptor and a resolved latent are different types.
+//   KernelTerm  one base kernel V kappa_kind(|x - x'| ./ l).  With factors, l_k = mult * ard[k]: all-equal factors (or d == 1) fold
+//               into the isotropic lengthscale mult * fold; other factors are uploaded as 1 / l_k.  `ev` evaluates the term; `gd` is
+//               what the gradient reduction takes (d > 1 with factors, folded or not: the per-dimension reduction with
+//               inv_ls = 1 / mult; else `ev`).
+//   Latent      the caller's mean, variance and lengthscale and nt >= 1 terms.  A plain latent is its one term (v_c = l_c = 1,
+//               V = variance); a sum latent (kind LMM_KERNEL_SUM) has the terms of its sum tag, V_c = variance v_c and
+//               mult_c = lengthscale l_c, and their `ev` on the device (dterms).  "One term" is a host-side view: a plain latent
+//               keeps its base kind on the device and is never evaluated as a sum.
+//   LatentSet   the latents of one call and the host / device buffers their descriptors point into.  Terms with equal (tag, mult)
+//               share one uploaded vector, so equal plain latents compare equal (Latent::same_kernel).  Held by shared_ptr by the
+//               running call and by every posterior handle built from it (own copy of the factors: tags may go).
 #define LMM_ARD_MAX_TAGS 4096
 struct ArdTag {           // d = 0: no factors; alpha = 0: no shape; terms non-empty: a sum tag (lmm_kernel_sum_create; d = 0, alpha = 0)
   int d; std::vector<double> ard, grad; double alpha = 0.0, galpha = 0.0;
@@ -311,85 +318,130 @@ std::map<int, ArdTag> g_ard_tags;
 int g_ard_next = 1;
 
 #define LMM_RQ_DEFAULT_ALPHA 2.0          // KernelFunctions' RationalQuadraticKernel(; alpha = 2.0)
-struct SumTerms;
-struct KernelSlot { const double* ils; double alpha; const SumTerms* sum = nullptr; };
-std::vector<KernelSlot> g_slot;
-std::vector<int> g_slot_free;
 
-// A sum latent of one call, resolved (resolve_gps): per term c its user tag, the multiplier s0 l_c of its factors, the factor a folded
-// term's lengthscale was multiplied by (1 otherwise), its tag's RQ shape (0: none), the evaluation descriptor (var v0 v_c, the folded
-// or per-dimension lengthscales; `ev` on the host, `dterms` on the device) and the gradient-reduction descriptor (terms with factors
-// and d > 1 take the per-dimension reduction, inv_ls = 1 / multiplier).
-struct SumTerms {
-  int tag = 0, nt = 0;
-  int ttag[LMM_SUM_MAX_TERMS] = {};
-  char has_ard[LMM_SUM_MAX_TERMS] = {};
-  double v[LMM_SUM_MAX_TERMS] = {}, ls[LMM_SUM_MAX_TERMS] = {}, mult[LMM_SUM_MAX_TERMS] = {}, fold[LMM_SUM_MAX_TERMS] = {};
-  double alpha[LMM_SUM_MAX_TERMS] = {};
-  LatentDev ev[LMM_SUM_MAX_TERMS] = {}, gd[LMM_SUM_MAX_TERMS] = {};
-  const LatentDev* dterms = nullptr;
+struct KernelTerm {
+  int tag = 0;                     // the user tag its factors and alpha come from (0: none)
+  bool has_ard = false;            // the tag has factors
+  double mult = 1.0, fold = 1.0;   // multiplier of the factors; the factor a folded term's lengthscale was multiplied by (1 otherwise)
+  double alpha = 0.0;              // the tag's RQ shape (0: none; the term then reports no alpha gradient)
+  double v = 1.0, ls = 1.0;        // v_c, l_c
+  LatentDev ev{}, gd{};
+  int ev_ent = -1, gd_ent = -1;    // entries of LatentSet::host that ev.ils / gd.ils point to (-1: isotropic)
 };
 
-// The resolved ARD state of one call, shared with the posterior handles it builds (and their conditioned successors and views).
-struct ArdSet {
+struct Latent {
+  double variance = 1.0, lengthscale = 1.0, mean = 0.0;   // lengthscale: a folded plain latent's includes the fold factor
+  int kind = 0, tag = 0;                                  // base kind or LMM_KERNEL_SUM; user tag (0: none)
+  std::vector<KernelTerm> terms;
+  const LatentDev* dterms = nullptr;                      // a sum latent's terms[c].ev on the device
+  bool is_sum() const { return kind == LMM_KERNEL_SUM; }
+  int nt() const { return (int)terms.size(); }
+  LatentDev dev() const {
+    if (!is_sum()) { LatentDev d = terms[0].ev; d.mean = mean; return d; }
+    LatentDev d{};
+    d.kind = kind; d.var = variance; d.inv_ls = 1.0 / lengthscale; d.mean = mean; d.alpha = LMM_RQ_DEFAULT_ALPHA;
+    d.terms = dterms; d.nterms = nt();
+    return d;
+  }
+  // kernel fields of a Gram assembly
+  void set_kernel(GramArgs& a) const {
+    const LatentDev d = dev();
+    a.kind = d.kind; a.var = d.var; a.inv_ls = d.inv_ls; a.ils = d.ils; a.alpha = d.alpha; a.terms = d.terms; a.nterms = d.nterms;
+  }
+  // kappa(0): the variance, or v0 sum_c v_c for a sum latent
+  double prior_var() const {
+    if (!is_sum()) return variance;
+    double v = 0.0;
+    for (const KernelTerm& T : terms) v += T.ev.var;
+    return v;
+  }
+  // The descriptor in the dense-H latent array (DenseArgs.lat, the posterior's latd): the dense kernels read var as kappa(0).
+  LatentDev dense_dev() const { LatentDev d = dev(); d.var = prior_var(); return d; }
+  // Whether two latents have the same kernel (the dense-H decoupled shortcut).  A sum latent's term with per-dimension lengthscales
+  // counts as different.
+  bool same_kernel(const Latent& o) const {
+    if (kind != o.kind || variance != o.variance || lengthscale != o.lengthscale || nt() != o.nt()) return false;
+    for (int c = 0; c < nt(); ++c) {
+      const LatentDev& x = terms[c].ev;
+      const LatentDev& y = o.terms[c].ev;
+      if (x.kind != y.kind || x.var != y.var || x.inv_ls != y.inv_ls || x.alpha != y.alpha) return false;
+      if (is_sum() ? (x.ils != nullptr || y.ils != nullptr) : x.ils != y.ils) return false;
+    }
+    return true;
+  }
+};
+
+struct LatentSet {
   int d = 0;
+  std::vector<Latent> lat;
   std::vector<double> host;                 // effective inverse lengthscales, d per entry
   Buf<double> dev;                          // the same on the device
-  std::vector<int> slots;                   // g_slot entries this set holds
-  // per latent of the call: user tag (0: none), whether the tag has factors, the caller's lengthscale (the common multiplier), the
-  // factor a folded latent's lengthscale was multiplied by (1 otherwise), the vector the gradient reduction uses (nullptr: the
-  // isotropic reduction), and the RQ shape taken from the tag (0: none; the latent then reports no alpha gradient)
-  std::vector<int> tag;
-  std::vector<char> has_ard;
-  std::vector<double> mult, fold, alpha;
-  std::vector<const double*> gils;
-  std::vector<SumTerms> sums;               // per latent: its resolved terms (nt = 0: not a sum latent)
-  std::vector<LatentDev> thost;             // the evaluation descriptors of every sum term of the call (host, then `tdev`)
+  std::vector<LatentDev> thost;             // the evaluation descriptors of every sum term (host, then `tdev`)
   Buf<LatentDev> tdev;
-  ArdSet() = default;
-  ArdSet(const ArdSet&) = delete;
-  ArdSet& operator=(const ArdSet&) = delete;
-  ~ArdSet() { for (int sl : slots) { g_slot[sl] = KernelSlot{nullptr, 0.0, nullptr}; g_slot_free.push_back(sl); } }
+  int any_sum() const {                     // the dense kernels' instantiation
+    for (const Latent& L : lat) if (L.is_sum()) return 1;
+    return 0;
+  }
+  // d of the per-dimension gradient reduction (0: every term takes the isotropic one)
+  int ard_grad_d() const {
+    for (const Latent& L : lat)
+      for (const KernelTerm& T : L.terms) if (T.gd.ils) return d;
+    return 0;
+  }
+  // Gradient entry points: the per-dimension reduction keeps d sums in registers (LMM_ARD_GRAD_DMAX).
+  int ard_grad_check() const {
+    if (d <= LMM_ARD_GRAD_DMAX || !ard_grad_d()) return LMM_OK;
+    return fail(LMM_ERR_UNSUPPORTED, "gradients of ARD latents are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
+  }
+  // first[k] = index of the first term of latent l0 + k among the terms of the latents [l0, l1); first[l1 - l0] = their number
+  std::vector<int> term_offsets(int l0, int l1) const {
+    std::vector<int> first(l1 - l0 + 1, 0);
+    for (int l = l0; l < l1; ++l) first[l - l0 + 1] = first[l - l0] + lat[l].nt();
+    return first;
+  }
 };
-// The ArdSet of the entry point that is running (set by resolve_gps, cleared when the call returns): read by the gradient cores.
-const ArdSet* g_call_ard = nullptr;
 
-inline int base_kind(const lmm_gp_t& gp) { return gp.kind & LMM_KERNEL_BASE_MASK; }
-inline const double* ils_of(const lmm_gp_t& gp) { const int sl = gp.kind >> 8; return sl > 0 ? g_slot[sl - 1].ils : nullptr; }
-inline double alpha_of(const lmm_gp_t& gp) {
-  const int sl = gp.kind >> 8;
-  return (sl > 0 && g_slot[sl - 1].alpha > 0.0) ? g_slot[sl - 1].alpha : LMM_RQ_DEFAULT_ALPHA;
-}
-
-// the resolved terms of a (resolved) sum latent; nullptr for every other latent
-inline const SumTerms* sum_of(const lmm_gp_t& gp) {
-  const int sl = gp.kind >> 8;
-  return (base_kind(gp) == LMM_KERNEL_SUM && sl > 0) ? g_slot[sl - 1].sum : nullptr;
-}
-// kappa(0) of a (resolved) latent: its variance, or v0 sum_c v_c for a sum latent
-inline double prior_var(const lmm_gp_t& gp) {
-  const SumTerms* S = sum_of(gp);
-  if (!S) return gp.variance;
-  double v = 0.0;
-  for (int c = 0; c < S->nt; ++c) v += S->ev[c].var;
-  return v;
-}
-
-LatentDev to_dev(const lmm_gp_t& gp) {
-  LatentDev d{};
-  d.kind = base_kind(gp); d.var = gp.variance; d.inv_ls = 1.0 / gp.lengthscale; d.mean = gp.mean; d.ils = ils_of(gp);
-  d.alpha = alpha_of(gp);
-  if (const SumTerms* S = sum_of(gp)) { d.ils = nullptr; d.terms = S->dterms; d.nterms = S->nt; }
-  return d;
-}
-// kernel fields of a Gram assembly from a (resolved) latent descriptor
-void set_kernel(GramArgs& a, const lmm_gp_t& gp) {
-  a.kind = base_kind(gp); a.var = gp.variance; a.inv_ls = 1.0 / gp.lengthscale; a.ils = ils_of(gp); a.alpha = alpha_of(gp);
-  a.terms = nullptr; a.nterms = 0;
-  if (const SumTerms* S = sum_of(gp)) { a.ils = nullptr; a.terms = S->dterms; a.nterms = S->nt; }
+// One term from its base kind, V, multiplier E and the factors / shape of its tag: fold, d == 1, or a (shared) vector.
+void resolve_term(LatentSet& S, KernelTerm& T, int base, double V, double E, const std::vector<double>& ard, double alpha,
+                  std::map<std::pair<int, double>, int>& entry_of) {
+  const int d = S.d;
+  T.mult = E; T.alpha = alpha;
+  LatentDev ev{};
+  ev.kind = base; ev.var = V; ev.inv_ls = 1.0 / E; ev.alpha = alpha > 0.0 ? alpha : LMM_RQ_DEFAULT_ALPHA;
+  T.gd = ev;
+  if (!ard.empty()) {
+    T.has_ard = true;
+    bool equal = true;
+    for (int k = 1; k < d; ++k) equal = equal && ard[k] == ard[0];
+    if (equal) { T.fold = ard[0]; ev.inv_ls = 1.0 / (E * ard[0]); }      // exactly the isotropic term of lengthscale E * ard[0]
+    if (d > 1) {                           // the gradient reduction needs the per-dimension vector, folded or not
+      auto key = std::make_pair(T.tag, E);
+      auto it = entry_of.find(key);
+      if (it == entry_of.end()) {
+        it = entry_of.emplace(key, (int)(S.host.size() / d)).first;
+        for (int k = 0; k < d; ++k) S.host.push_back(1.0 / (E * ard[k]));
+      }
+      T.gd_ent = it->second;
+      if (!equal) T.ev_ent = it->second;
+    } else T.gd = ev;                      // d == 1: the isotropic reduction at l_eff = E * ard[0] gives the one derivative
+  }
+  T.ev = ev;
 }
 
-int check_gps(const lmm_gp_t* gps, int m) {
+// A latent without a tag (no validation: resolve has done it)
+Latent plain_latent(const lmm_gp_t& gp) {
+  Latent L;
+  L.variance = gp.variance; L.lengthscale = gp.lengthscale; L.mean = gp.mean; L.kind = gp.kind & LMM_KERNEL_BASE_MASK;
+  L.terms.resize(1);
+  LatentDev& ev = L.terms[0].ev;
+  ev.kind = L.kind; ev.var = gp.variance; ev.inv_ls = 1.0 / gp.lengthscale; ev.alpha = LMM_RQ_DEFAULT_ALPHA;
+  L.terms[0].mult = gp.lengthscale;
+  L.terms[0].gd = ev;
+  return L;
+}
+
+// The caller's latents, validated and resolved.  A call without tags allocates nothing on the device and copies nothing to it.
+int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) {
   if (!gps) return fail(LMM_ERR_ARG, "gps is NULL");
   for (int l = 0; l < m; ++l) {
     const int base = gps[l].kind & LMM_KERNEL_BASE_MASK;
@@ -397,42 +449,18 @@ int check_gps(const lmm_gp_t* gps, int m) {
     if (base == LMM_KERNEL_SUM && (gps[l].kind >> 8) == 0) return fail(LMM_ERR_ARG, "latent %d: a sum latent needs a sum tag (lmm_kernel_sum_create)", l);
     if (!(gps[l].variance > 0.0) || !(gps[l].lengthscale > 0.0)) return fail(LMM_ERR_ARG, "latent %d: variance and lengthscale must be > 0", l);
   }
-  return LMM_OK;
-}
-
-// The resolved latents of one call: `v` replaces the caller's array when any latent carries a tag (`ard` then holds the state).
-struct CallGps {
-  std::vector<lmm_gp_t> v;
-  std::shared_ptr<ArdSet> ard;
-  CallGps() = default;
-  CallGps(const CallGps&) = delete;
-  CallGps& operator=(const CallGps&) = delete;
-  ~CallGps() { if (ard && g_call_ard == ard.get()) g_call_ard = nullptr; }
-};
-
-int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
-  if (int rc = check_gps(gps, m)) return rc;
-  bool any = false;
-  for (int l = 0; l < m; ++l) any = any || (gps[l].kind >> 8) != 0;
-  if (!any) return LMM_OK;
-  auto A = std::make_shared<ArdSet>();
-  A->d = d;
-  A->tag.assign(m, 0); A->has_ard.assign(m, 0); A->mult.assign(m, 1.0); A->fold.assign(m, 1.0); A->alpha.assign(m, 0.0);
-  A->gils.assign(m, nullptr);
-  A->sums.assign(m, SumTerms{});
-  out.v.assign(gps, gps + m);
-  // sum terms: entries of A->host holding a term's per-dimension vector (evaluation / gradient; -1: none), patched after the upload
-  std::vector<std::array<int, LMM_SUM_MAX_TERMS>> ev_ent(m), gd_ent(m);
-  for (int l = 0; l < m; ++l) { ev_ent[l].fill(-1); gd_ent[l].fill(-1); }
-  std::map<std::pair<int, double>, int> entry_of;     // (tag, multiplier) -> entry: latents sharing both share the vector (and kind word)
-  std::vector<int> ent(m, -1);
-  std::vector<char> folded(m, 0);
+  auto S = std::make_shared<LatentSet>();
+  S->d = d;
+  S->lat.resize(m);
+  std::map<std::pair<int, double>, int> entry_of;     // (tag, multiplier) -> entry of S->host
   for (int l = 0; l < m; ++l) {
+    Latent& L = S->lat[l];
+    L = plain_latent(gps[l]);
     const int tag = gps[l].kind >> 8;
     if (tag == 0) continue;
+    L.tag = tag;
     std::vector<double> ard;
     double alpha;
-    const bool is_sum = base_kind(gps[l]) == LMM_KERNEL_SUM;
     std::vector<lmm_gp_t> terms;
     std::vector<std::vector<double>> tard;
     std::vector<double> talpha;
@@ -440,8 +468,8 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
       std::lock_guard<std::mutex> lk(g_ard_mu);
       auto it = g_ard_tags.find(tag);
       if (it == g_ard_tags.end()) return fail(LMM_ERR_ARG, "latent %d: unknown or destroyed ARD tag %d", l, tag);
-      if (is_sum != !it->second.terms.empty())
-        return fail(LMM_ERR_ARG, "latent %d: tag %d is %sa sum tag but the kernel kind is %d", l, tag, is_sum ? "not " : "", base_kind(gps[l]));
+      if (L.is_sum() != !it->second.terms.empty())
+        return fail(LMM_ERR_ARG, "latent %d: tag %d is %sa sum tag but the kernel kind is %d", l, tag, L.is_sum() ? "not " : "", L.kind);
       if (it->second.d != 0 && it->second.d != d)
         return fail(LMM_ERR_DIM, "latent %d: ARD tag %d has %d dimensions, the inputs have %d", l, tag, it->second.d, d);
       ard = it->second.ard;
@@ -461,220 +489,105 @@ int resolve_gps(const lmm_gp_t* gps, int m, int d, CallGps& out) {
         talpha.back() = jt->second.alpha;
       }
     }
-    if (is_sum) {                      // terms as virtual latents: var v0 v_c, lengthscale s0 l_c, factors folded as for latents
-      SumTerms& S = A->sums[l];
-      const double v0 = gps[l].variance, s0 = gps[l].lengthscale;
-      S.tag = tag; S.nt = (int)terms.size();
-      A->tag[l] = tag; A->mult[l] = s0;
-      out.v[l].kind = LMM_KERNEL_SUM;
-      for (int c = 0; c < S.nt; ++c) {
-        const int bk = terms[c].kind & LMM_KERNEL_BASE_MASK;
-        const double E = s0 * terms[c].lengthscale;
-        S.ttag[c] = terms[c].kind >> 8; S.v[c] = terms[c].variance; S.ls[c] = terms[c].lengthscale; S.mult[c] = E; S.fold[c] = 1.0;
-        S.alpha[c] = talpha[c];
-        LatentDev ev{};
-        ev.kind = bk; ev.var = v0 * terms[c].variance; ev.inv_ls = 1.0 / E; ev.alpha = talpha[c] > 0.0 ? talpha[c] : LMM_RQ_DEFAULT_ALPHA;
-        LatentDev gd = ev;
-        const std::vector<double>& ta = tard[c];
-        if (!ta.empty()) {
-          S.has_ard[c] = 1;
-          bool equal = true;
-          for (int k = 1; k < d; ++k) equal = equal && ta[k] == ta[0];
-          if (d > 1) {                 // the gradient reduction needs the per-dimension vector, folded or not
-            gd_ent[l][c] = (int)(A->host.size() / d);
-            for (int k = 0; k < d; ++k) A->host.push_back(1.0 / (E * ta[k]));
-          }
-          if (equal) {
-            S.fold[c] = ta[0]; ev.inv_ls = 1.0 / (E * ta[0]);
-            if (d == 1) gd = ev;       // d == 1: the isotropic reduction at l_eff = s0 l_c ard[0] gives the one derivative
-          } else ev_ent[l][c] = gd_ent[l][c];
-        }
-        S.ev[c] = ev; S.gd[c] = gd;
+    if (L.is_sum()) {
+      L.terms.assign(terms.size(), KernelTerm{});
+      for (int c = 0; c < L.nt(); ++c) {
+        KernelTerm& T = L.terms[c];
+        T.tag = terms[c].kind >> 8; T.v = terms[c].variance; T.ls = terms[c].lengthscale;
+        resolve_term(*S, T, terms[c].kind & LMM_KERNEL_BASE_MASK, L.variance * T.v, L.lengthscale * T.ls, tard[c], talpha[c], entry_of);
       }
       continue;
     }
-    if (alpha > 0.0 && base_kind(gps[l]) != LMM_KERNEL_RQ)
-      return fail(LMM_ERR_ARG, "latent %d: tag %d carries an RQ shape but the kernel kind is %d", l, tag, base_kind(gps[l]));
-    const double ls = gps[l].lengthscale;
-    A->tag[l] = tag; A->mult[l] = ls; A->alpha[l] = alpha;
-    out.v[l].kind = base_kind(gps[l]);
-    if (ard.empty()) continue;         // an RQ shape alone: isotropic, its slot is assigned below
-    A->has_ard[l] = 1;
-    bool equal = true;
-    for (int k = 1; k < d; ++k) equal = equal && ard[k] == ard[0];
-    if (equal) {                       // folded: exactly the isotropic latent of lengthscale ls * ard[0]
-      folded[l] = 1;
-      A->fold[l] = ard[0];
-      out.v[l].lengthscale = ls * ard[0];
-      if (d == 1) continue;            // d == 1: the isotropic reduction gives the one derivative
-    }
-    auto key = std::make_pair(tag, ls);
-    auto it = entry_of.find(key);
-    if (it == entry_of.end()) {
-      it = entry_of.emplace(key, (int)(A->host.size() / d)).first;
-      for (int k = 0; k < d; ++k) A->host.push_back(1.0 / (ls * ard[k]));
-    }
-    ent[l] = it->second;
+    if (alpha > 0.0 && L.kind != LMM_KERNEL_RQ)
+      return fail(LMM_ERR_ARG, "latent %d: tag %d carries an RQ shape but the kernel kind is %d", l, tag, L.kind);
+    KernelTerm& T = L.terms[0];
+    T.tag = tag;
+    resolve_term(*S, T, L.kind, L.variance, L.lengthscale, ard, alpha, entry_of);
+    L.lengthscale = gps[l].lengthscale * T.fold;
   }
-  const int ne = (int)(A->host.size() / std::max(d, 1));
-  if (ne > 0) {
-    A->dev = Buf<double>(A->host.size());
-    // (A->host lives as long as the set, so the copy may complete asynchronously; every launch that reads it is ordered behind st0)
-    HIPCHK(hipMemcpyAsync(A->dev.p, A->host.data(), A->host.size() * sizeof(double), hipMemcpyHostToDevice, g.streams[0]));
-    for (int l = 0; l < m; ++l)
-      if (ent[l] >= 0) A->gils[l] = A->dev.p + (size_t)ent[l] * d;
-    for (int l = 0; l < m; ++l)
-      for (int c = 0; c < A->sums[l].nt; ++c) {
-        if (ev_ent[l][c] >= 0) A->sums[l].ev[c].ils = A->dev.p + (size_t)ev_ent[l][c] * d;
-        if (gd_ent[l][c] >= 0) A->sums[l].gd[c].ils = A->dev.p + (size_t)gd_ent[l][c] * d;
+  if (!S->host.empty()) {
+    S->dev = Buf<double>(S->host.size());
+    // (S->host lives as long as the set, so the copy may complete asynchronously; every launch that reads it is ordered behind st0)
+    HIPCHK(hipMemcpyAsync(S->dev.p, S->host.data(), S->host.size() * sizeof(double), hipMemcpyHostToDevice, g.streams[0]));
+    for (Latent& L : S->lat)
+      for (KernelTerm& T : L.terms) {
+        if (T.ev_ent >= 0) T.ev.ils = S->dev.p + (size_t)T.ev_ent * d;
+        if (T.gd_ent >= 0) T.gd.ils = S->dev.p + (size_t)T.gd_ent * d;
       }
   }
-  // the sum latents' evaluation descriptors on the device, and one slot per sum latent
-  for (int l = 0; l < m; ++l)
-    for (int c = 0; c < A->sums[l].nt; ++c) A->thost.push_back(A->sums[l].ev[c]);
-  if (!A->thost.empty()) {
-    A->tdev = Buf<LatentDev>(A->thost.size());
-    HIPCHK(hipMemcpyAsync(A->tdev.p, A->thost.data(), A->thost.size() * sizeof(LatentDev), hipMemcpyHostToDevice, g.streams[0]));
+  // the sum latents' evaluation descriptors on the device
+  for (const Latent& L : S->lat)
+    if (L.is_sum()) for (const KernelTerm& T : L.terms) S->thost.push_back(T.ev);
+  if (!S->thost.empty()) {
+    S->tdev = Buf<LatentDev>(S->thost.size());
+    HIPCHK(hipMemcpyAsync(S->tdev.p, S->thost.data(), S->thost.size() * sizeof(LatentDev), hipMemcpyHostToDevice, g.streams[0]));
     size_t off = 0;
-    for (int l = 0; l < m; ++l) {
-      SumTerms& S = A->sums[l];
-      if (S.nt == 0) continue;
-      S.dterms = A->tdev.p + off;
-      off += S.nt;
-      int sl;
-      if (!g_slot_free.empty()) { sl = g_slot_free.back(); g_slot_free.pop_back(); }
-      else { sl = (int)g_slot.size(); g_slot.push_back(KernelSlot{nullptr, 0.0, nullptr}); }
-      g_slot[sl] = KernelSlot{nullptr, 0.0, &S};
-      A->slots.push_back(sl);
-      out.v[l].kind = LMM_KERNEL_SUM | ((sl + 1) << 8);
-    }
+    for (Latent& L : S->lat)
+      if (L.is_sum()) { L.dterms = S->tdev.p + off; off += L.nt(); }
   }
-  // Slots: one per (tag, multiplier) among the latents that need one (a per-dimension vector, or an RQ shape); latents sharing both
-  // share the slot and so the kind word.
-  std::map<std::pair<int, double>, int> slot_of;
-  for (int l = 0; l < m; ++l) {
-    const bool vec = ent[l] >= 0 && !folded[l];
-    if (!vec && !(A->alpha[l] > 0.0)) continue;
-    auto key = std::make_pair(A->tag[l], A->mult[l]);
-    auto it = slot_of.find(key);
-    if (it == slot_of.end()) {
-      int sl;
-      if (!g_slot_free.empty()) { sl = g_slot_free.back(); g_slot_free.pop_back(); }
-      else { sl = (int)g_slot.size(); g_slot.push_back(KernelSlot{nullptr, 0.0, nullptr}); }
-      g_slot[sl] = KernelSlot{vec ? A->gils[l] : nullptr, A->alpha[l], nullptr};
-      A->slots.push_back(sl);
-      it = slot_of.emplace(key, sl).first;
-    }
-    out.v[l].kind = base_kind(gps[l]) | ((it->second + 1) << 8);
-  }
-  out.ard = A;
-  g_call_ard = A.get();
+  out = std::move(S);
   return LMM_OK;
 }
-// Invariant: resolve_gps reads the high 24 bits of `kind` as a USER tag, so it is only ever given a caller's array.  A resolved array
-// (cg_.v, lmm_post.gps) carries slot indices of g_slot there instead and must never be resolved again: internal code passes it
-// straight to the launch helpers (to_dev / set_kernel / ils_of), which read the slot.
-#define RESOLVE_GPS(gps, m, d)                                  \
-  CallGps cg_;                                                  \
-  if (int rc_ = resolve_gps(gps, m, d, cg_)) return rc_;        \
-  if (cg_.ard) gps = cg_.v.data()
+// The entry points' preamble: `lts` is the resolved array every internal function takes.
+#define RESOLVE(gps, m, d)                                  \
+  std::shared_ptr<LatentSet> ls;                            \
+  if (int rc_ = resolve(gps, m, d, ls)) return rc_;         \
+  const Latent* lts = ls->lat.data()
 
-// Posterior latent mean mu + K(xs, x) alpha (launch_post_mean); a sum latent takes one pass per term, added in term order.
-void post_mean_g(const double* xs, int ns, const double* x, int n, int d, const double* alpha, const lmm_gp_t& gp, double* partial,
+// Posterior latent mean mu + K(xs, x) alpha (launch_post_mean): one pass per term, added in term order.
+void post_mean_g(const double* xs, int ns, const double* x, int n, int d, const double* alpha, const Latent& L, double* partial,
                  double* out, hipStream_t st) {
-  const SumTerms* S = sum_of(gp);
-  if (!S || alpha == nullptr || n == 0) { launch_post_mean(xs, ns, x, n, d, alpha, to_dev(gp), partial, out, st); return; }
-  double* tmp = S->nt > 1 ? call_scratch(ns) : nullptr;
-  for (int c = 0; c < S->nt; ++c) {
-    LatentDev tc = S->ev[c];
-    tc.mean = c == 0 ? gp.mean : 0.0;
+  if (alpha == nullptr || n == 0) { launch_post_mean(xs, ns, x, n, d, alpha, L.dev(), partial, out, st); return; }
+  double* tmp = L.nt() > 1 ? call_scratch(ns) : nullptr;
+  for (int c = 0; c < L.nt(); ++c) {
+    LatentDev tc = L.terms[c].ev;
+    tc.mean = c == 0 ? L.mean : 0.0;
     launch_post_mean(xs, ns, x, n, d, alpha, tc, partial, c == 0 ? out : tmp, st);
     if (c > 0) launch_vec_lin(out, tmp, 1.0, ns, out, st);
   }
 }
 
-// A latent's descriptor in the dense-H latent array (DenseArgs.lat, the posterior's latd): the dense kernels read var as kappa(0),
-// which is v0 sum_c v_c for a sum latent (its terms carry their own variances).
-LatentDev dense_dev(const lmm_gp_t& gp) {
-  LatentDev d = to_dev(gp);
-  d.var = prior_var(gp);
-  return d;
-}
-// Whether any of the (resolved) latents is a sum latent (the dense kernels' instantiation)
-int any_sum(const lmm_gp_t* gps, int m) {
-  for (int l = 0; l < m; ++l) if (sum_of(gps[l])) return 1;
-  return 0;
-}
-// Whether two (resolved) latents have the same kernel (the dense-H decoupled shortcut): base kind, vector, alpha, variance and
-// lengthscale; for sum latents also the whole term lists (a term with per-dimension lengthscales counts as different: its vector
-// is the latent's own).
-bool same_kernel(const lmm_gp_t& a, const lmm_gp_t& b) {
-  if (base_kind(a) != base_kind(b) || ils_of(a) != ils_of(b) || alpha_of(a) != alpha_of(b) || a.variance != b.variance ||
-      a.lengthscale != b.lengthscale)
-    return false;
-  const SumTerms* A = sum_of(a);
-  const SumTerms* B = sum_of(b);
-  if (!A || !B) return A == B;
-  if (A->nt != B->nt) return false;
-  for (int c = 0; c < A->nt; ++c) {
-    const LatentDev& x = A->ev[c];
-    const LatentDev& y = B->ev[c];
-    if (x.kind != y.kind || x.var != y.var || x.inv_ls != y.inv_ls || x.alpha != y.alpha || x.ils != nullptr || y.ils != nullptr)
-      return false;
-  }
-  return true;
-}
-
-// Gradient entry points: the per-dimension reduction keeps d sums in registers (LMM_ARD_GRAD_DMAX).
-int ard_grad_check(int d) {
-  if (!g_call_ard || d <= LMM_ARD_GRAD_DMAX) return LMM_OK;
-  for (const double* p : g_call_ard->gils)
-    if (p) return fail(LMM_ERR_UNSUPPORTED, "gradients of ARD latents are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
-  for (const SumTerms& S : g_call_ard->sums)
-    for (int c = 0; c < S.nt; ++c)
-      if (S.gd[c].ils) return fail(LMM_ERR_UNSUPPORTED, "gradients of ARD latents are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
-  return LMM_OK;
-}
 // The input gradient (grad_x_kernel) keeps d sums per row in registers, as the ARD reduction does.
 int input_grad_check(int d, bool wanted) {
   if (!wanted || d <= LMM_ARD_GRAD_DMAX) return LMM_OK;
   return fail(LMM_ERR_UNSUPPORTED, "gradients with respect to the inputs are served for d <= %d (d = %d)", LMM_ARD_GRAD_DMAX, d);
 }
-// d of the ARD gradient reduction in this call (0: every latent takes the isotropic one)
-int ard_grad_d() {
-  if (!g_call_ard) return 0;
-  for (const double* p : g_call_ard->gils) if (p) return g_call_ard->d;
-  for (const SumTerms& S : g_call_ard->sums)
-    for (int c = 0; c < S.nt; ++c) if (S.gd[c].ils) return g_call_ard->d;
-  return 0;
+
+// Chain rule of a latent from its term reductions: term c's kernel is V_c kappa_c(. / E_c) with V_c = v0 v_c and E_c = s0 l_c, so
+// d/dv_c = v0 d/dV_c, d/dl_c = s0 d/dE_c and d/ds0 = sum_c l_c d/dE_c (returned; a plain latent's d/d lengthscale).  red: LMM_NGRAD
+// sums per term, ard: d per-dimension sums per term (read where gd.ils is set).  aa, tr: alpha.alpha and tr Kt^-1 over all rows
+// (d/dV_c = (sum_{i>j} w K_c,ij + V_c (aa - tr) / 2) / V_c; *dv0 = sum_c v_c d/dV_c).  out: one record of term_grad_stride(d) values
+// per term: (d/dv_c, d/dl_c, d/dalpha_c, d/dl_k of the term's per-dimension lengthscales).
+inline size_t term_grad_stride(int d) { return 3 + (size_t)d; }
+double grad_finish(const Latent& L, int d, const double* red, const double* ard, double aa, double tr, double* out,
+                   double* dv0 = nullptr) {
+  double ds0 = 0.0, gv0 = 0.0;
+  const size_t sw = term_grad_stride(d);
+  for (int c = 0; c < L.nt(); ++c) {
+    const KernelTerm& T = L.terms[c];
+    const double* rc = red + (size_t)LMM_NGRAD * c;
+    double* o = out + sw * c;
+    const double V = T.ev.var;
+    const double gV = (rc[7] + 0.5 * V * (aa - tr)) / V;
+    const double dE = T.gd.ils ? rc[0] : rc[0] * T.fold;
+    o[0] = gV * L.variance;
+    o[1] = dE * L.lengthscale;
+    o[2] = T.alpha > 0.0 ? rc[8] : 0.0;
+    if (T.gd.ils) for (int k = 0; k < d; ++k) o[3 + k] = ard[(size_t)d * c + k];
+    else if (T.has_ard) o[3] = rc[0];                      // d == 1: d/d l_eff, l_eff = multiplier * fold
+    ds0 += dE * T.ls;
+    gv0 += gV * T.v;
+  }
+  if (dv0) *dv0 = gv0;
+  return ds0;
 }
-// The latent's descriptor for the gradient reduction: an ARD latent (folded ones included, d > 1) takes the per-dimension variant
-// with inv_ls = 1 / its multiplier.
-LatentDev grad_dev(const lmm_gp_t& gp, int l) {
-  LatentDev gd = to_dev(gp);
-  if (g_call_ard && g_call_ard->gils[l]) { gd.ils = g_call_ard->gils[l]; gd.inv_ls = 1.0 / g_call_ard->mult[l]; }
-  return gd;
-}
-// After the reduction: red = the LMM_NGRAD sums of latent l, ard = its d per-dimension sums (d/d l_k; unused unless gils[l]).
-// Writes d/d multiplier into *dl and d/d l_k into gard[0..d).
-void ard_grad_finish(int l, int d, const double* red, const double* ard, double* dl, double* gard) {
-  *dl = red[0];
-  if (!g_call_ard || !g_call_ard->has_ard[l]) return;
-  if (g_call_ard->gils[l]) { for (int k = 0; k < d; ++k) gard[k] = ard[k]; return; }
-  gard[0] = red[0];                           // d == 1, folded: red[0] = d/d l_eff, l_eff = multiplier * fold
-  *dl = red[0] * g_call_ard->fold[l];
-}
-// Publishes the call's per-dimension gradients to the registry: every tag the call named gets d/d ard[k] = multiplier * d/d l_k summed
-// over the call's latents [l0, l1) carrying it, and a tag with an RQ shape gets d/d alpha summed over those latents (galpha: one per
-// latent); gard == nullptr (grad_gps NULL): zeros.
-// Sum latents: tg holds per latent LMM_SUM_MAX_TERMS records of sum_grad_stride(d) values (sum_grad_finish); the sum tag gets
-// (d/dv_c, d/dl_c, 0) and each term's tag its factor and alpha gradients (multiplier s0 l_c).
-inline size_t sum_grad_stride(int d) { return 3 + (size_t)d; }
-void ard_publish(const std::vector<double>* gard, const std::vector<double>* galpha, int l0, int l1,
-                 const std::vector<double>* tg = nullptr) {
-  if (!g_call_ard) return;
-  const ArdSet& A = *g_call_ard;
-  const int d = A.d, m = (int)A.tag.size();
+// Publishes a gradient call's records (trec: m x LMM_SUM_MAX_TERMS of them, grad_finish) to the registry: every tag the call named is
+// reset; then, over the latents [l0, l1), a sum tag gets (d/dv_c, d/dl_c, 0) per term and each term's tag d/d ard[k] = multiplier *
+// d/d l_k and, with an RQ shape, d/d alpha, summed over the terms carrying it.  trec == nullptr (grad_gps NULL): zeros.
+void publish_grads(const LatentSet& S, const std::vector<double>* trec, int l0, int l1) {
+  bool any = false;
+  for (const Latent& L : S.lat) any = any || L.tag != 0;
+  if (!any) return;
   std::lock_guard<std::mutex> lk(g_ard_mu);
   auto reset = [&](int tag) {
     auto it = g_ard_tags.find(tag);
@@ -682,35 +595,27 @@ void ard_publish(const std::vector<double>* gard, const std::vector<double>* gal
     it->second.grad.assign(it->second.d, 0.0); it->second.galpha = 0.0;
     it->second.tgrad.assign(it->second.terms.size(), lmm_gp_grad_t{0.0, 0.0, 0.0});
   };
-  for (int l = 0; l < m; ++l) {
-    reset(A.tag[l]);
-    for (int c = 0; c < A.sums[l].nt; ++c) reset(A.sums[l].ttag[c]);
+  for (const Latent& L : S.lat) {
+    reset(L.tag);
+    for (const KernelTerm& T : L.terms) reset(T.tag);
   }
-  if (tg && gard) {
-    const size_t sw = sum_grad_stride(d);
-    for (int l = l0; l < l1; ++l) {
-      const SumTerms& S = A.sums[l];
-      auto st = g_ard_tags.find(S.tag);
-      for (int c = 0; c < S.nt; ++c) {
-        const double* r = &(*tg)[((size_t)l * LMM_SUM_MAX_TERMS + c) * sw];
-        if (st != g_ard_tags.end() && (size_t)c < st->second.tgrad.size()) {
-          st->second.tgrad[c].variance += r[0]; st->second.tgrad[c].lengthscale += r[1];
-        }
-        auto it = g_ard_tags.find(S.ttag[c]);
-        if (S.ttag[c] == 0 || it == g_ard_tags.end()) continue;
-        if (S.has_ard[c])
-          for (int k = 0; k < it->second.d; ++k) it->second.grad[k] += S.mult[c] * r[3 + k];
-        if (S.alpha[c] > 0.0) it->second.galpha += r[2];
-      }
-    }
-  }
-  if (!gard) return;
+  if (!trec) return;
+  const size_t sw = term_grad_stride(S.d);
   for (int l = l0; l < l1; ++l) {
-    auto it = g_ard_tags.find(A.tag[l]);
-    if (A.tag[l] == 0 || it == g_ard_tags.end() || A.sums[l].nt > 0) continue;
-    if (A.has_ard[l])
-      for (int k = 0; k < d; ++k) it->second.grad[k] += A.mult[l] * (*gard)[(size_t)l * d + k];
-    if (A.alpha[l] > 0.0) it->second.galpha += (*galpha)[l];
+    const Latent& L = S.lat[l];
+    auto st = L.is_sum() ? g_ard_tags.find(L.tag) : g_ard_tags.end();
+    for (int c = 0; c < L.nt(); ++c) {
+      const KernelTerm& T = L.terms[c];
+      const double* r = &(*trec)[((size_t)l * LMM_SUM_MAX_TERMS + c) * sw];
+      if (st != g_ard_tags.end() && (size_t)c < st->second.tgrad.size()) {
+        st->second.tgrad[c].variance += r[0]; st->second.tgrad[c].lengthscale += r[1];
+      }
+      auto it = g_ard_tags.find(T.tag);
+      if (T.tag == 0 || it == g_ard_tags.end()) continue;
+      if (T.has_ard)
+        for (int k = 0; k < std::min(S.d, it->second.d); ++k) it->second.grad[k] += T.mult * r[3 + k];
+      if (T.alpha > 0.0) it->second.galpha += r[2];
+    }
   }
 }
 
@@ -1241,7 +1146,7 @@ void residual_on_device(const double* Y, int n, int p, const double* Ty_all, int
 // delta ([latent][rhs][n]) and per-latent noise.  Returns lml[latent * nrhs + rhs] (host).  nrhs > 1: several
 // right-hand sides (matrix-Y logpdf) ride one factorisation.  noisevec ([latent of the shard][n], device) replaces the
 // scalar per-latent noise by a per-point diagonal.
-int latent_lmls(const double* xd, int d, int n, const lmm_gp_t* gps, const double* noise, int l0, int l1,
+int latent_lmls(const double* xd, int d, int n, const Latent* lts, const double* noise, int l0, int l1,
                 const double* delta, std::vector<double>& lml, int nrhs = 1, const double* noisevec = nullptr,
                 const double* rider_sub = nullptr,         // rider_sub[latent] (host): subtracted from that latent's riders
                 const std::function<void()>* pre_launch = nullptr) {      // launches that PRODUCE delta, issued on streams[0] once this
@@ -1287,10 +1192,10 @@ int latent_lmls(const double* xd, int d, int n, const lmm_gp_t* gps, const doubl
     GramArgs ga[LMM_MAX_BATCH];
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      const lmm_gp_t& gp = gps[l0 + k];
+      const Latent& gp = lts[l0 + k];
       GramArgs a{};
       a.A = s.A[j].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.row_tile0 = 0; a.row_shift = 0; a.full = 0;
-      a.x = xd; a.d = d; a.n = n; set_kernel(a, gp);
+      a.x = xd; a.d = d; a.n = n; gp.set_kernel(a);
       a.diag_add = noisevec ? 0.0 : noise[l0 + k]; a.pad_diag = 1.0;
       a.diag_vec = noisevec ? noisevec + (size_t)k * n : nullptr;      // per-point noise of latent k (device, n values)
       a.rider = delta + (size_t)k * nrhs * n; a.rider_ld = n; a.nrider = nrhs; a.xs = nullptr; a.ns = 0;
@@ -1335,8 +1240,7 @@ struct lmm_post {
   int kind = 0;               // 0: per-latent (OILMM / MOGP), 1: dense ILMM
   int n = 0, d = 0, l0 = 0, l1 = 0, m = 0;
   int NC = 0, NR = 0, ld = 0;
-  std::vector<lmm_gp_t> gps;  // all m latents (host; ARD latents resolved: their kind words name slots of `ard`)
-  std::shared_ptr<ArdSet> ard;  // the effective per-dimension lengthscales the handle was built with (own copy: tags may go)
+  std::shared_ptr<LatentSet> ls;  // all m latents as the handle was built with them (own copy of the factors: tags may go)
   Buf<double> x;              // d x n
   std::vector<Buf<double>> L; // per latent of the shard: factor matrix (NR x NC, ld)
   std::vector<Buf<double>> W; // inverse diagonal blocks
@@ -1718,7 +1622,7 @@ int lmm_oilmm_logpdf(const double* x, int d, int n, const double* y, int p, cons
   if (!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST, H;
@@ -1728,7 +1632,7 @@ int lmm_oilmm_logpdf(const double* x, int d, int n, const double* y, int p, cons
   else project_orthogonal(U, S, p, m, sigma2, T, ST, H);
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = gps[l].mean;
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
   double resid_pageable = 0.0;
   double* resid = static_cast<double*>(pin_take(sizeof(double)));      // pinned: the read-back below does not stall the host
@@ -1751,12 +1655,12 @@ int lmm_oilmm_logpdf(const double* x, int d, int n, const double* y, int p, cons
       residual_on_device(yd.p, n, p, Ty.p, m, Hdev, partial.p, resid_direct ? resid_direct : resid_dev.p, st0);
       if (!resid_direct) HIPCHK(hipMemcpyAsync(resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));    // read after latent_lmls' sync
     };
-    if (int rc = latent_lmls(xd.p, d, n, gps, ST.data(), l0, l1, Ty.p + (size_t)l0 * n, lml, 1, nullptr, means.data(), &produce)) return rc;
+    if (int rc = latent_lmls(xd.p, d, n, lts, ST.data(), l0, l1, Ty.p + (size_t)l0 * n, lml, 1, nullptr, means.data(), &produce)) return rc;
   } else {
     Uploaded Td(T, st0), meansd(means, st0);
     Buf<double> delta((size_t)n * std::max(ms, 1));
     if (ms > 0) project_on_device(yd.p, n, p, Td.buf, m, l0, ms, meansd.buf.p + l0, delta.p, st0);
-    if (int rc = latent_lmls(xd.p, d, n, gps, ST.data(), l0, l1, delta.p, lml)) return rc;
+    if (int rc = latent_lmls(xd.p, d, n, lts, ST.data(), l0, l1, delta.p, lml)) return rc;
   }
   double total = 0.0;
   for (int k = 0; k < ms; ++k) total += lml[k];
@@ -1808,55 +1712,8 @@ struct OilmmGrad {          // host results of oilmm_grad_core (partial sums ove
   std::vector<double> gs2;    // one per noise block
   std::vector<double> gS, gU;
   std::vector<lmm_gp_grad_t> ggps;
-  std::vector<double> gard;   // m x d: d logpdf / d l_k of the ARD latents (ard_grad_finish), zeros elsewhere
-  std::vector<double> galpha; // m: d logpdf / d alpha of the RQ latents, zeros elsewhere
-  std::vector<double> tg;     // sum latents: m x LMM_SUM_MAX_TERMS records (sum_grad_finish), zeros elsewhere
+  std::vector<double> trec;   // m x LMM_SUM_MAX_TERMS records per latent and term (grad_finish), zeros elsewhere
 };
-
-// The resolved terms of latent l of the running call (nullptr: not a sum latent).
-inline const SumTerms* call_sum(int l) {
-  return (g_call_ard && g_call_ard->sums[l].nt > 0) ? &g_call_ard->sums[l] : nullptr;
-}
-// Terms of the shard's latents [l0, l1): offsets of each latent's first term reduction (a latent without terms takes none); returns
-// the total.
-int sum_term_offsets(int l0, int l1, std::vector<int>& toff) {
-  toff.assign(std::max(l1 - l0, 1), 0);
-  int T = 0;
-  for (int l = l0; l < l1; ++l) { toff[l - l0] = T; if (const SumTerms* S = call_sum(l)) T += S->nt; }
-  return T;
-}
-// One gradient reduction per term of a sum latent (the trace and alpha.delta partials, which do not depend on the kernel, are taken
-// from term 0's).  red: NGR values per term, ard: d values per term.
-void sum_grad_reduce(const SumTerms& S, const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta,
-                     const double* x, int d, double* partial, double* red, double* ard, hipStream_t st) {
-  for (int c = 0; c < S.nt; ++c)
-    launch_grad_reduce(Kinv, ld, n, nsplit, alpha, delta, x, d, S.gd[c], partial, red + (size_t)LMM_NGRAD * c, st, ard + (size_t)d * c);
-}
-// Chain rule of a sum latent from its term reductions: term c's kernel is V_c kappa_c(. / E_c) with V_c = v0 v_c and E_c = s0 l_c, so
-// d/dv_c = v0 d/dV_c, d/dl_c = s0 d/dE_c and d/ds0 = sum_c l_c d/dE_c (returned).  aa, tr: alpha.alpha and tr Kt^-1 over all rows
-// (d/dV_c = (sum_{i>j} w K_c,ij + V_c (aa - tr) / 2) / V_c).  out: LMM_SUM_MAX_TERMS records of sum_grad_stride(d) values
-// (d/dv_c, d/dl_c, d/dalpha_c, d/dl_k of the term's per-dimension lengthscales).
-double sum_grad_finish(const SumTerms& S, int d, const double* red, const double* ard, double aa, double tr, double v0, double s0,
-                       double* out, double* dv0 = nullptr) {
-  double ds0 = 0.0, gv0 = 0.0;
-  const size_t sw = 3 + (size_t)d;
-  for (int c = 0; c < S.nt; ++c) {
-    const double* rc = red + (size_t)LMM_NGRAD * c;
-    double* o = out + sw * c;
-    const double V = S.ev[c].var;
-    const double gV = (rc[7] + 0.5 * V * (aa - tr)) / V;
-    const double dE = S.gd[c].ils ? rc[0] : rc[0] * S.fold[c];
-    o[0] = gV * v0;
-    o[1] = dE * s0;
-    o[2] = S.alpha[c] > 0.0 ? rc[8] : 0.0;
-    if (S.gd[c].ils) for (int k = 0; k < d; ++k) o[3 + k] = ard[(size_t)d * c + k];
-    else if (S.has_ard[c]) o[3] = rc[0];                   // d == 1: d/d l_eff, l_eff = multiplier * fold
-    ds0 += dE * S.ls[c];
-    gv0 += gV * S.v[c];
-  }
-  if (dv0) *dv0 = gv0;
-  return ds0;
-}
 
 // Value and gradient of the OILMM logpdf (reference src/oilmm.jl:79-113 differentiated) over N points in NB.nblk consecutive
 // blocks, block b carrying observation noise NB.s2[b] (one block: the plain logpdf; several: the joint density of the
@@ -1866,9 +1723,11 @@ double sum_grad_finish(const SumTerms& S, int d, const double* red, const double
 // xd: d x N (device), yd: N x p column-major (device), gy_dev: N x p device output or nullptr.  gx_dev: d x N device output of
 // d logpdf / d x summed over the shard's latents (grad_x_kernel), or nullptr (no launch, no allocation).  Caller holds g_mu.
 int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const double* yd, int p, const double* U, const double* S,
-                    int m, const lmm_gp_t* gps, int l0, int l1, int with_regulariser, OilmmGrad& G, double* gy_dev,
+                    const LatentSet* ls, int l0, int l1, int with_regulariser, OilmmGrad& G, double* gy_dev,
                     double* gx_dev = nullptr) {
   hipStream_t st0 = g.streams[0];
+  const int m = (int)ls->lat.size(), ard_d = ls->ard_grad_d();
+  const Latent* lts = ls->lat.data();
   const int ms = l1 - l0, n = N, nblk = NB.nblk;
   const bool two = nblk > 1;
   const int nsplit = nblk == 2 ? NB.off[1] : N;        // the contraction kernel splits its trace / alpha.alpha sums once
@@ -1879,7 +1738,7 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     for (int l = 0; l < m; ++l) ST[b][l] = NB.s2[b] / S[l];
   Uploaded Td(T, st0);
   std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = gps[l].mean;
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   Uploaded meansd(means, st0);
   // projections: Ty (all m, for dS), delta for the shard
   Buf<double> Ty((size_t)n * m), delta((size_t)n * std::max(ms, 1));
@@ -1899,14 +1758,13 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
       Am[s].emplace_back(mat_count(D.elems())); Wm[s].emplace_back(mat_count((size_t)(D.NC / 64) * 4096));
       Rm[s].emplace_back(mat_count((size_t)D.ld * D.NC));
     }
-    part.emplace_back((size_t)grad_partials(n, ard_grad_d()));
+    part.emplace_back((size_t)grad_partials(n, ard_d));
   }
   const int NGR = LMM_NGRAD;
-  Buf<double> alpha((size_t)D.NC * std::max(ms, 1)), lmld(std::max(ms, 1)), red((size_t)NGR * std::max(ms, 1));
-  Buf<double> ardred((size_t)d * std::max(ms, 1));             // per-dimension sums of the ARD latents (d/d l_k)
-  std::vector<int> toff;                                       // sum latents: one reduction per term
-  const int nterm = sum_term_offsets(l0, l1, toff);
-  Buf<double> tred((size_t)NGR * std::max(nterm, 1)), tard((size_t)d * std::max(nterm, 1));
+  const std::vector<int> toff = ls->term_offsets(l0, l1);     // one reduction per term of every latent of the shard
+  const int nterm = toff[ms];
+  Buf<double> alpha((size_t)D.NC * std::max(ms, 1)), lmld(std::max(ms, 1)), red((size_t)NGR * std::max(nterm, 1));
+  Buf<double> ardred((size_t)d * std::max(nterm, 1));          // per-dimension sums of the ARD terms (d/d l_k)
   // more than two noise blocks: [tr Kinv, alpha.alpha] per (latent, block) from the small per-range kernels
   Buf<double> blksum(nblk > 2 ? (size_t)2 * nblk * std::max(ms, 1) : 1);
   Buf<int> info(std::max(ms, 1));
@@ -1927,10 +1785,10 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     GramArgs ga[LMM_MAX_BATCH];
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      const lmm_gp_t& gp = gps[l0 + k];
+      const Latent& gp = lts[l0 + k];
       GramArgs a{};
       a.A = Am[s][j].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n;
-      set_kernel(a, gp); a.pad_diag = 1.0;
+      gp.set_kernel(a); a.pad_diag = 1.0;
       a.diag_add = two ? 0.0 : STa[l0 + k];
       a.diag_vec = two ? nv.p + (size_t)k * n : nullptr;
       a.rider = delta.p + (size_t)k * n; a.rider_ld = n; a.nrider = 1;
@@ -1950,20 +1808,16 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     launch_syrk_upper_set(B.A, D.ld, Rb, D.ld, D.NC, nb, st);                // lower(A) = L^-T L^-1 = Kt^-1
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      if (const SumTerms* Sk = call_sum(l0 + k)) {
-        sum_grad_reduce(*Sk, Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, part[s].p,
-                        tred.p + (size_t)NGR * toff[k], tard.p + (size_t)d * toff[k], st);
-        if (gx_dev)
-          for (int c = 0; c < Sk->nt; ++c) {
-            launch_grad_x(Am[s][j].p, D.ld, n, alb.p[j], xd, d, Sk->gd[c], gxpart[s].p, gxacc[s].p, gx_used[s] != 0, st);
-            gx_used[s] = 1;
-          }
-      } else
-        launch_grad_reduce(Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, grad_dev(gps[l0 + k], l0 + k), part[s].p,
-                           red.p + (size_t)NGR * k, st, ardred.p + (size_t)d * k);
-      if (gx_dev && !call_sum(l0 + k)) {
-        launch_grad_x(Am[s][j].p, D.ld, n, alb.p[j], xd, d, grad_dev(gps[l0 + k], l0 + k), gxpart[s].p, gxacc[s].p, gx_used[s] != 0, st);
-        gx_used[s] = 1;
+      // one reduction per term (the trace and alpha.delta partials, which do not depend on the kernel, are read from term 0's)
+      for (int c = 0; c < lts[l0 + k].nt(); ++c) {
+        const LatentDev& gd = lts[l0 + k].terms[c].gd;
+        const size_t t = (size_t)toff[k] + c;
+        launch_grad_reduce(Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, gd, part[s].p, red.p + NGR * t, st,
+                           ardred.p + d * t);
+        if (gx_dev) {
+          launch_grad_x(Am[s][j].p, D.ld, n, alb.p[j], xd, d, gd, gxpart[s].p, gxacc[s].p, gx_used[s] != 0, st);
+          gx_used[s] = 1;
+        }
       }
       if (nblk > 2)
         for (int b = 0; b < nblk; ++b) {
@@ -1984,18 +1838,13 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     }
     if (first) HIPCHK(hipMemsetAsync(gx_dev, 0, (size_t)d * n * sizeof(double), st0));      // empty shard
   }
-  std::vector<double> lml(std::max(ms, 1), 0.0), hred((size_t)NGR * std::max(ms, 1), 0.0);
+  std::vector<double> lml(std::max(ms, 1), 0.0), hred((size_t)NGR * std::max(nterm, 1), 0.0);
   std::vector<int> hinfo(std::max(ms, 1), 0);
   std::vector<double> hblk(nblk > 2 ? (size_t)2 * nblk * std::max(ms, 1) : 0, 0.0);
   HIPCHK(hipMemcpyAsync(lml.data(), lmld.p, std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(hred.data(), red.p, (size_t)NGR * std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
-  std::vector<double> hard(ard_grad_d() ? (size_t)d * std::max(ms, 1) : 0, 0.0);
+  HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  std::vector<double> hard(ard_d ? (size_t)d * std::max(nterm, 1) : 0, 0.0);
   if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  std::vector<double> htred((size_t)NGR * nterm), htard((size_t)d * nterm);
-  if (nterm > 0) {
-    HIPCHK(hipMemcpyAsync(htred.data(), tred.p, htred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-    if (ard_grad_d()) HIPCHK(hipMemcpyAsync(htard.data(), tard.p, htard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  }
   if (!hblk.empty() && ms > 0) HIPCHK(hipMemcpyAsync(hblk.data(), blksum.p, hblk.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, st0));
   // small dense products needed by the chain rule: YA = Y' alpha (p x ms), aTy = alpha_l . (T y)_l, M2 = Y Y' (p x p) per noise block
@@ -2020,20 +1869,12 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   G.gs2.assign(nblk, 0.0);
   G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
   G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
-  G.gard.assign((size_t)m * d, 0.0);
-  G.galpha.assign(m, 0.0);
-  G.tg.assign((size_t)m * LMM_SUM_MAX_TERMS * sum_grad_stride(d), 0.0);
+  G.trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
   for (int k = 0; k < ms; ++k) {
     const int l = l0 + k;
     total += lml[k];
-    const SumTerms* Sl = call_sum(l);
-    const double* r = Sl ? &htred[(size_t)NGR * toff[k]] : &hred[(size_t)NGR * k];
-    double cl = 0.0;
-    if (!Sl) {
-      G.galpha[l] = r[8];
-      ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * k], &cl, &G.gard[(size_t)l * d]);
-    }
-    const double ad = r[3], sa = r[4], v = gps[l].variance;
+    const double* r = &hred[(size_t)NGR * toff[k]];
+    const double ad = r[3], sa = r[4], v = lts[l].variance;
     double aa_all = 0.0, tr_all = 0.0;
     double D_aa = 0.0, D_tr = 0.0, g_s2 = 0.0;       // a'Da, tr(Kt^-1 D) with D the projected noise; sum_b s2[b] dlml/dnoise_b
     for (int b = 0; b < nblk; ++b) {
@@ -2048,10 +1889,9 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     }
     // 1/2 tr((aa' - Kt^-1) K) / v  with K = Kt - D:  a'delta - a'Da - (n - tr(Kt^-1 D))
     G.ggps[l].variance = 0.5 * ((ad - D_aa) - ((double)n - D_tr)) / v;      // (a sum latent's K is linear in v0 too)
-    G.ggps[l].lengthscale = cl;                                                // sum_{i>j} (a_i a_j - Kinv_ij) dK_ij/dl (x2 / 2)
-    if (Sl)
-      G.ggps[l].lengthscale = sum_grad_finish(*Sl, d, r, htard.data() + (size_t)d * toff[k], aa_all, tr_all, v, gps[l].lengthscale,
-                                              &G.tg[(size_t)l * LMM_SUM_MAX_TERMS * sum_grad_stride(d)]);
+    // sum_{i>j} (a_i a_j - Kinv_ij) dK_ij/dl (x2 / 2), through the terms
+    G.ggps[l].lengthscale = grad_finish(lts[l], d, r, hard.empty() ? nullptr : &hard[(size_t)d * toff[k]], aa_all, tr_all,
+                                        &G.trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)]);
     G.ggps[l].mean = sa;
     G.gS[l] += -g_s2 / (S[l] * S[l]) + 0.5 * aTy[k + (size_t)l * ms] / S[l];
     for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] += -YA[o + (size_t)k * p] / std::sqrt(S[l]);
@@ -2160,19 +2000,19 @@ int lmm_oilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int 
   if (!x || !y || !U || !S || !out_logpdf || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   DevOut gy(grad_y, (size_t)n * p), gx(grad_x, (size_t)d * n);
-  if (int rc = ard_grad_check(d)) return rc;
+  if (int rc = ls->ard_grad_check()) return rc;
   if (int rc = input_grad_check(d, grad_x != nullptr)) return rc;
   OilmmGrad G;
-  if (int rc = oilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, U, S, m, gps, latent_begin, latent_end, with_regulariser,
+  if (int rc = oilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, U, S, ls.get(), latent_begin, latent_end, with_regulariser,
                                G, gy.p, gx.p))
     return rc;
   write_oilmm_grad(G, m, p, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
-  ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, latent_begin, latent_end, &G.tg);
+  publish_grads(*ls, grad_gps ? &G.trec : nullptr, latent_begin, latent_end);
   if (grad_y) gy.finish(st0);
   if (grad_x) gx.finish(st0);
   if (grad_y || grad_x) HIPCHK(hipStreamSynchronize(st0));
@@ -2211,7 +2051,7 @@ int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* b
     return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   if (int rc = check_batches(batch_n, batch_sigma2, nbatch, n)) return rc;
   if (!(sigma2_s > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
@@ -2222,7 +2062,7 @@ int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* b
   HIPCHK(hipMemcpyAsync(xj.p + (size_t)d * n, xsd.p, (size_t)d * ns * sizeof(double), hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpy2DAsync(yj.p, (size_t)N * sizeof(double), yd.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpy2DAsync(yj.p + n, (size_t)N * sizeof(double), ysd.p, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
-  if (int rc = ard_grad_check(d)) return rc;
+  if (int rc = ls->ard_grad_check()) return rc;
   const bool want_gx = grad_x != nullptr || grad_xs != nullptr;
   if (int rc = input_grad_check(d, want_gx)) return rc;
   const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
@@ -2230,9 +2070,9 @@ int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* b
   if (want_gx) gxj = Buf<double>((size_t)d * N);
   if (grad_x) gxm = Buf<double>((size_t)d * n);
   OilmmGrad GJ, GM;
-  if (int rc = oilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, U, S, m, gps,
+  if (int rc = oilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, U, S, ls.get(),
                                latent_begin, latent_end, with_regulariser, GJ, want_gy ? gj.p : nullptr, gxj.p)) return rc;
-  if (int rc = oilmm_grad_core(xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd.p, p, U, S, m, gps,
+  if (int rc = oilmm_grad_core(xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd.p, p, U, S, ls.get(),
                                latent_begin, latent_end, with_regulariser, GM, grad_y ? gm.p : nullptr, gxm.p)) return rc;
   if (int rc = finish_input_grads(gxj.p, gxm.p, d, n, ns, grad_x, grad_xs)) return rc;
   *out_logpdf = GJ.value - GM.value;
@@ -2247,10 +2087,8 @@ int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* b
     }
   }
   if (grad_U) for (size_t q = 0; q < (size_t)p * m; ++q) grad_U[q] = GJ.gU[q] - GM.gU[q];
-  for (size_t q = 0; q < GJ.gard.size(); ++q) GJ.gard[q] -= GM.gard[q];
-  for (size_t q = 0; q < GJ.galpha.size(); ++q) GJ.galpha[q] -= GM.galpha[q];
-  for (size_t q = 0; q < GJ.tg.size(); ++q) GJ.tg[q] -= GM.tg[q];
-  ard_publish(grad_gps ? &GJ.gard : nullptr, &GJ.galpha, latent_begin, latent_end, &GJ.tg);
+  for (size_t q = 0; q < GJ.trec.size(); ++q) GJ.trec[q] -= GM.trec[q];
+  publish_grads(*ls, grad_gps ? &GJ.trec : nullptr, latent_begin, latent_end);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);
@@ -2301,14 +2139,14 @@ int lmm_oilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p
   if (!x || !Y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0 || ncol <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST, H;
   project_orthogonal(U, S, p, m, sigma2, T, ST, H);
   DevIn xd(x, (size_t)d * n, st0), yd(Y, (size_t)n * p * ncol, st0);
   Uploaded Td(T, st0), Hd(H, st0);
   std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = gps[l].mean;
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   Uploaded meansd(means, st0);
   const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
   Buf<double> delta((size_t)n * std::max(ms, 1) * ncol), Ty((size_t)n * m), partial(tall_skinny_partials(n, p)), resid_dev(ncol);
@@ -2325,7 +2163,7 @@ int lmm_oilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p
   }
   if (with_regulariser) HIPCHK(hipMemcpyAsync(resid.data(), resid_dev.p, ncol * sizeof(double), hipMemcpyDeviceToHost, st0));
   std::vector<double> lml;
-  if (int rc = latent_lmls(xd.p, d, n, gps, ST.data(), l0, l1, delta.p, lml, ncol)) return rc;
+  if (int rc = latent_lmls(xd.p, d, n, lts, ST.data(), l0, l1, delta.p, lml, ncol)) return rc;
   double logdetS = 0.0;
   for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
   for (int c = 0; c < ncol; ++c) {
@@ -2362,18 +2200,18 @@ int lmm_mogp_logpdf(const double* x, int d, int n, const double* y, int m, doubl
   LMM_TRY
   if (!x || !y || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   hipStream_t st0 = g.streams[0];
   const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0);
   // delta_l = y_l - mean_l  via the projection kernel with T = I restricted to the shard
   std::vector<double> T((size_t)m * m, 0.0), means(m), noise(m, sigma2);
-  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = gps[l].mean; }
+  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = lts[l].mean; }
   Uploaded Td(T, st0), meansd(means, st0);
   Buf<double> delta((size_t)n * std::max(ms, 1));
   if (ms > 0) project_on_device(yd.p, n, m, Td.buf, m, l0, ms, meansd.buf.p + l0, delta.p, st0);
   std::vector<double> lml;
-  if (int rc = latent_lmls(xd.p, d, n, gps, noise.data(), l0, l1, delta.p, lml)) return rc;
+  if (int rc = latent_lmls(xd.p, d, n, lts, noise.data(), l0, l1, delta.p, lml)) return rc;
   double total = 0.0;
   for (int k = 0; k < ms; ++k) total += lml[k];
   *out = total;
@@ -2388,17 +2226,17 @@ int lmm_mogp_logpdf_diag(const double* x, int d, int n, const double* y, int m, 
   LMM_TRY
   if (!x || !y || !noise_diag || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   hipStream_t st0 = g.streams[0];
   const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0), nd(noise_diag, (size_t)n * m, st0);
   std::vector<double> T((size_t)m * m, 0.0), means(m), noise(m, 0.0);
-  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = gps[l].mean; }
+  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = lts[l].mean; }
   Uploaded Td(T, st0), meansd(means, st0);
   Buf<double> delta((size_t)n * std::max(ms, 1));
   if (ms > 0) project_on_device(yd.p, n, m, Td.buf, m, l0, ms, meansd.buf.p + l0, delta.p, st0);
   std::vector<double> lml;
-  if (int rc = latent_lmls(xd.p, d, n, gps, noise.data(), l0, l1, delta.p, lml, 1, nd.p + (size_t)l0 * n)) return rc;
+  if (int rc = latent_lmls(xd.p, d, n, lts, noise.data(), l0, l1, delta.p, lml, 1, nd.p + (size_t)l0 * n)) return rc;
   double total = 0.0;
   for (int k = 0; k < ms; ++k) total += lml[k];
   *out = total;
@@ -2412,7 +2250,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !y || !H || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   if (!jit) jit = &kDefaultJit;
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
   hipStream_t st0 = g.streams[0];
@@ -2423,7 +2261,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   Uploaded Td(T, st0), STd(ST, st0);
   std::vector<double> Hv(H, H + (size_t)p * m), means(m);
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) { means[l] = gps[l].mean; lat[l] = dense_dev(gps[l]); }
+  for (int l = 0; l < m; ++l) { means[l] = lts[l].mean; lat[l] = lts[l].dense_dev(); }
   Uploaded Hd(Hv, st0), meansd(means, st0);
   Buf<LatentDev> latd(m);
   HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
@@ -2437,7 +2275,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   };
   bool identical = allow_decoupled != 0;
   for (int l = 1; l < m && identical; ++l)
-    identical = same_kernel(gps[l], gps[0]);        // two tags with one alpha: one kernel
+    identical = lts[l].same_kernel(lts[0]);        // two tags with one alpha: one kernel
   if (path_used) *path_used = identical ? 1 : 0;
   if (identical) {
     // Decoupled shortcut: with one shared latent kernel the covariance is I (x) K + SigmaT (x) I;
@@ -2452,12 +2290,12 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
         for (int b = 0; b < m; ++b) s += Q[b + (size_t)aI * m] * T[b + (size_t)o * m];
         T2[aI + (size_t)o * m] = s;
       }
-      for (int b = 0; b < m; ++b) mu2[aI] += Q[b + (size_t)aI * m] * gps[b].mean;
+      for (int b = 0; b < m; ++b) mu2[aI] += Q[b + (size_t)aI * m] * lts[b].mean;
       if (!(lam[aI] > 0.0)) return fail(LMM_ERR_NOT_PD, "PosDefException: SigmaT has a non-positive eigenvalue");
     }
     Uploaded T2d(T2, st0), mu2d(mu2, st0);
     project_on_device(yd.p, n, p, T2d.buf, m, 0, m, mu2d.buf.p, delta.p, st0);
-    std::vector<lmm_gp_t> g2(m, gps[0]);
+    std::vector<Latent> g2(m, lts[0]);
     std::vector<double> lml;
     double resid = 0.0;
     HIPCHK(hipMemcpyAsync(&resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
@@ -2476,7 +2314,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
   DenseArgs a{};
   a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd.p; a.d = d; a.n = n; a.m = m;
-  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = 1; a.has_sum = any_sum(gps, m);
+  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = 1; a.has_sum = ls->any_sum();
   launch_dense_assemble(a, st0);
   potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, 1, lml_dev.p, st0);
@@ -2506,7 +2344,7 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !Y || !H || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0 || ncol <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   if (!jit) jit = &kDefaultJit;
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
@@ -2518,7 +2356,7 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   Uploaded Td(T, st0), STd(ST, st0);
   std::vector<double> Hv(H, H + (size_t)p * m), means(m);
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) { means[l] = gps[l].mean; lat[l] = dense_dev(gps[l]); }
+  for (int l = 0; l < m; ++l) { means[l] = lts[l].mean; lat[l] = lts[l].dense_dev(); }
   Uploaded Hd(Hv, st0), meansd(means, st0);
   Buf<LatentDev> latd(m);
   HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
@@ -2536,7 +2374,7 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
   DenseArgs a{};
   a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd.p; a.d = d; a.n = n; a.m = m;
-  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = ncol; a.has_sum = any_sum(gps, m);
+  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = ncol; a.has_sum = ls->any_sum();
   launch_dense_assemble(a, st0);
   potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, ncol, lml_dev.p, st0);
@@ -2561,9 +2399,7 @@ struct IlmmGrad {            // host results of ilmm_grad_core
   double value = 0.0, gs2[LMM_MAX_NOISE_BLOCKS] = {};
   std::vector<double> gH;    // p x m
   std::vector<lmm_gp_grad_t> ggps;
-  std::vector<double> gard;  // m x d: d logpdf / d l_k of the ARD latents (ard_grad_finish), zeros elsewhere
-  std::vector<double> galpha;  // m: d logpdf / d alpha of the RQ latents, zeros elsewhere
-  std::vector<double> tg;      // sum latents: m x LMM_SUM_MAX_TERMS records (sum_grad_finish), zeros elsewhere
+  std::vector<double> trec;  // m x LMM_SUM_MAX_TERMS records per latent and term (grad_finish), zeros elsewhere
 };
 
 // Value and gradient of the dense-H ILMM prior logpdf over n points in NB.nblk consecutive blocks, block b carrying observation
@@ -2574,8 +2410,10 @@ struct IlmmGrad {            // host results of ilmm_grad_core
 // (lmm_ilmm_post_latent_logpdf_grad_seq) observes its test block through [I_m; 0]; G.gH collects the blocks observed through H itself.
 // gx_dev (optional, d x n device): d logpdf / d x from the diagonal blocks of the inverse (the latent prior is block-diagonal).
 int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const double* yd, int p, const double* H, int m,
-                   const lmm_gp_t* gps, const lmm_jitters_t* jit, IlmmGrad& G, double* gy_dev, const double* const* Hblk = nullptr,
+                   const LatentSet* ls, const lmm_jitters_t* jit, IlmmGrad& G, double* gy_dev, const double* const* Hblk = nullptr,
                    double* gx_dev = nullptr) {
+  const Latent* lts = ls->lat.data();
+  const int ard_d = ls->ard_grad_d();
   if ((long long)m * n > 46000) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense gradient (explicit (mn)^2 inverse)");
   hipStream_t st0 = g.streams[0];
   constexpr int KB = LMM_MAX_NOISE_BLOCKS;
@@ -2600,9 +2438,9 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
     Hv.insert(Hv.end(), Hq[b], Hq[b] + (size_t)p * m);
     Ht.insert(Ht.end(), Htb.begin(), Htb.end());
   }
-  for (int l = 0; l < m; ++l) means[l] = gps[l].mean;
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) lat[l] = dense_dev(gps[l]);
+  for (int l = 0; l < m; ++l) lat[l] = lts[l].dense_dev();
   std::vector<int> sidx(n);
   for (int b = 0; b < nblk; ++b)
     for (int i = bi0[b]; i < bi0[b] + bn[b]; ++i) sidx[i] = b;
@@ -2637,7 +2475,7 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   DenseArgs a{};
   a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n; a.m = m;
   a.lat = latd.p; a.sigmaT = STd.buf.p; a.sig_idx = nblk > 1 ? sidxd.p : nullptr; a.rider = delta.p; a.rider_ld = N; a.nrider = 1;
-  a.has_sum = any_sum(gps, m);
+  a.has_sum = ls->any_sum();
   launch_dense_assemble(a, st0);
   potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, 1, lml_dev.p, st0);
@@ -2648,26 +2486,20 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   launch_syrk_upper_set(A.p, D.ld, R.p, D.ld, D.NC, st0);                         // lower(A) = Sigma^-1
   const int NGR = LMM_NGRAD;
   const size_t mm = (size_t)m * m, mp = (size_t)m * p;
-  Buf<double> red((size_t)NGR * m), gpart((size_t)grad_partials(n, ard_grad_d())), Btr(KB * mm), AAt(KB * mm), AY(KB * mp);
-  Buf<double> ardred((size_t)d * m), gxpart;
+  const std::vector<int> toff = ls->term_offsets(0, m);       // one reduction per term of every latent
+  const int nterm = toff[m];
+  Buf<double> red((size_t)NGR * nterm), gpart((size_t)grad_partials(n, ard_d)), Btr(KB * mm), AAt(KB * mm), AY(KB * mp);
+  Buf<double> ardred((size_t)d * nterm), gxpart;
   if (gx_dev) gxpart = Buf<double>(grad_x_partial_elems(n, d));
-  std::vector<int> toff;                                       // sum latents: one reduction per term
-  const int nterm = sum_term_offsets(0, m, toff);
-  Buf<double> tred((size_t)NGR * std::max(nterm, 1)), tard((size_t)d * std::max(nterm, 1));
   for (int l = 0; l < m; ++l) {
     const double* Kl = mat_at(A.p, (size_t)l * n * D.ld + (size_t)l * n);
-    if (const SumTerms* Sl = call_sum(l)) {
-      sum_grad_reduce(*Sl, Kl, D.ld, n, n, alpha.p + (size_t)l * n, delta.p + (size_t)l * n, xd, d, gpart.p,
-                      tred.p + (size_t)NGR * toff[l], tard.p + (size_t)d * toff[l], st0);
-      if (gx_dev)
-        for (int c = 0; c < Sl->nt; ++c)
-          launch_grad_x(Kl, D.ld, n, alpha.p + (size_t)l * n, xd, d, Sl->gd[c], gxpart.p, gx_dev, l > 0 || c > 0, st0);
-      continue;
+    for (int c = 0; c < lts[l].nt(); ++c) {
+      const LatentDev& gd = lts[l].terms[c].gd;
+      const size_t t = (size_t)toff[l] + c;
+      launch_grad_reduce(Kl, D.ld, n, n, alpha.p + (size_t)l * n, delta.p + (size_t)l * n, xd, d, gd, gpart.p, red.p + NGR * t, st0,
+                         ardred.p + d * t);
+      if (gx_dev) launch_grad_x(Kl, D.ld, n, alpha.p + (size_t)l * n, xd, d, gd, gxpart.p, gx_dev, l > 0 || c > 0, st0);
     }
-    launch_grad_reduce(Kl, D.ld, n, n, alpha.p + (size_t)l * n, delta.p + (size_t)l * n, xd, d,
-                       grad_dev(gps[l], l), gpart.p, red.p + (size_t)NGR * l, st0, ardred.p + (size_t)d * l);
-    if (gx_dev)
-      launch_grad_x(Kl, D.ld, n, alpha.p + (size_t)l * n, xd, d, grad_dev(gps[l], l), gxpart.p, gx_dev, l > 0, st0);
   }
   // regulariser pieces: Rm = Y - (T Y)' H' (n x p), RH = Rm H (n x m), per block Rm' Ty (p x m), RH' Y (m x p)
   Buf<double> HTY((size_t)n * p), Rm((size_t)n * p), RH((size_t)N), RtTy(KB * mp), RHtY(KB * mp);
@@ -2684,20 +2516,15 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
     launch_atb(Rm.p + i0, n, Ty.p + i0, n, nb_, p, m, RtTy.p + b * mp, st0);
     launch_atb(RH.p + i0, n, yd + i0, n, nb_, m, p, RHtY.p + b * mp, st0);
   }
-  std::vector<double> hred((size_t)NGR * m), hB(KB * mm), hAAt(KB * mm), hAY(KB * mp), hRtTy(KB * mp), hRHtY(KB * mp);
+  std::vector<double> hred((size_t)NGR * nterm), hB(KB * mm), hAAt(KB * mm), hAY(KB * mp), hRtTy(KB * mp), hRHtY(KB * mp);
   double lml = 0.0, resid[KB] = {};
   int hinfo = 0;
   HIPCHK(hipMemcpyAsync(&lml, lml_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(resid, resid_dev.p, nblk * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  std::vector<double> hard(ard_grad_d() ? (size_t)d * m : 0, 0.0);
+  std::vector<double> hard(ard_d ? (size_t)d * nterm : 0, 0.0);
   if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  std::vector<double> htred((size_t)NGR * nterm), htard((size_t)d * nterm);
-  if (nterm > 0) {
-    HIPCHK(hipMemcpyAsync(htred.data(), tred.p, htred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-    if (ard_grad_d()) HIPCHK(hipMemcpyAsync(htard.data(), tard.p, htard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  }
   HIPCHK(hipMemcpyAsync(hB.data(), Btr.p, nblk * mm * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hAAt.data(), AAt.p, nblk * mm * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hAY.data(), AY.p, nblk * mp * sizeof(double), hipMemcpyDeviceToHost, st0));
@@ -2711,22 +2538,11 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
     G.value -= ((double)bn[b] * ((double)(p - m) * kLog2Pi + ((double)p * std::log(s2[b]) - logdetST[b])) + resid[b] / s2[b]) / 2.0;
   // ---- kernel-parameter gradients: 1/2 tr((aa' - Sigma^-1) dSigma/dtheta_l), dSigma = E_ll (x) dK_l ----
   G.ggps.assign(m, lmm_gp_grad_t{});
-  G.gard.assign((size_t)m * d, 0.0);
-  G.galpha.assign(m, 0.0);
-  G.tg.assign((size_t)m * LMM_SUM_MAX_TERMS * sum_grad_stride(d), 0.0);
-  for (int l = 0; l < m; ++l) {
-    if (const SumTerms* Sl = call_sum(l)) {       // the trace, a.a and sum-of-alpha partials from term 0's reduction
-      const double* r = &htred[(size_t)NGR * toff[l]];
-      G.ggps[l].lengthscale = sum_grad_finish(*Sl, d, r, htard.data() + (size_t)d * toff[l], r[2], r[1], gps[l].variance,
-                                              gps[l].lengthscale, &G.tg[(size_t)l * LMM_SUM_MAX_TERMS * sum_grad_stride(d)],
-                                              &G.ggps[l].variance);
-      G.ggps[l].mean = r[4];
-      continue;
-    }
-    const double* r = &hred[(size_t)NGR * l];
-    G.galpha[l] = r[8];
-    ard_grad_finish(l, d, r, hard.empty() ? nullptr : &hard[(size_t)d * l], &G.ggps[l].lengthscale, &G.gard[(size_t)l * d]);
-    G.ggps[l].variance = (r[7] + 0.5 * gps[l].variance * (r[2] - r[1])) / gps[l].variance;     // K_ii = variance
+  G.trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
+  for (int l = 0; l < m; ++l) {                     // the trace, a.a and sum-of-alpha partials from term 0's reduction; K_ii = kappa(0)
+    const double* r = &hred[(size_t)NGR * toff[l]];
+    G.ggps[l].lengthscale = grad_finish(lts[l], d, r, hard.empty() ? nullptr : &hard[(size_t)d * toff[l]], r[2], r[1],
+                                        &G.trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)], &G.ggps[l].variance);
     G.ggps[l].mean = r[4];
   }
   std::vector<double> Hacc((size_t)p * m, 0.0), HtH(mm, 0.0);
@@ -2840,17 +2656,17 @@ int lmm_ilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int p
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !y || !H || !out_logpdf || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   if (!jit) jit = &kDefaultJit;
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   DevOut gy(grad_y, (size_t)n * p), gx(grad_x, (size_t)d * n);
-  if (int rc = ard_grad_check(d)) return rc;
+  if (int rc = ls->ard_grad_check()) return rc;
   if (int rc = input_grad_check(d, grad_x != nullptr)) return rc;
   IlmmGrad G;
-  if (int rc = ilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, H, m, gps, jit, G, gy.p, nullptr, gx.p)) return rc;
-  ard_publish(grad_gps ? &G.gard : nullptr, &G.galpha, 0, m, &G.tg);
+  if (int rc = ilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, H, m, ls.get(), jit, G, gy.p, nullptr, gx.p)) return rc;
+  publish_grads(*ls, grad_gps ? &G.trec : nullptr, 0, m);
   *out_logpdf = G.value;
   if (grad_sigma2) *grad_sigma2 = G.gs2[0];
   if (grad_H) std::copy(G.gH.begin(), G.gH.end(), grad_H);
@@ -2883,7 +2699,7 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
                                lmm_gp_grad_t* grad_gps, double* grad_x, double* grad_xs) {
   if (!x || !y || !xs || !ys || !H || !out_logpdf || d <= 0 || n <= 0 || ns <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_test && m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   if (int rc = check_batches(batch_n, batch_sigma2, nbatch, n)) return rc;
   if (!(sigma2_s > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   if (!jit) jit = &kDefaultJit;
@@ -2906,7 +2722,7 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
     for (int l = 0; l < m; ++l) Hlat[l + (size_t)l * p] = 1.0;
     Hblk[nbatch] = Hlat.data();
   }
-  if (int rc = ard_grad_check(d)) return rc;
+  if (int rc = ls->ard_grad_check()) return rc;
   const bool want_gx = grad_x != nullptr || grad_xs != nullptr;
   if (int rc = input_grad_check(d, want_gx)) return rc;
   const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
@@ -2914,9 +2730,9 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
   if (want_gx) gxj = Buf<double>((size_t)d * N);
   if (grad_x) gxm = Buf<double>((size_t)d * n);
   IlmmGrad GJ, GM;
-  if (int rc = ilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, H, m, gps, jit, GJ,
+  if (int rc = ilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, H, m, ls.get(), jit, GJ,
                               want_gy ? gj.p : nullptr, latent_test ? Hblk : nullptr, gxj.p)) return rc;
-  if (int rc = ilmm_grad_core(xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd.p, p, H, m, gps, jit, GM,
+  if (int rc = ilmm_grad_core(xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd.p, p, H, m, ls.get(), jit, GM,
                               grad_y ? gm.p : nullptr, nullptr, gxm.p)) return rc;
   if (int rc = finish_input_grads(gxj.p, gxm.p, d, n, ns, grad_x, grad_xs)) return rc;
   const double pad = latent_test ? 0.5 * (double)ns * (double)(p - m) : 0.0;
@@ -2930,10 +2746,8 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
       grad_gps[l].lengthscale = GJ.ggps[l].lengthscale - GM.ggps[l].lengthscale;
       grad_gps[l].mean = GJ.ggps[l].mean - GM.ggps[l].mean;
     }
-  for (size_t q = 0; q < GJ.gard.size(); ++q) GJ.gard[q] -= GM.gard[q];
-  for (size_t q = 0; q < GJ.galpha.size(); ++q) GJ.galpha[q] -= GM.galpha[q];
-  for (size_t q = 0; q < GJ.tg.size(); ++q) GJ.tg[q] -= GM.tg[q];
-  ard_publish(grad_gps ? &GJ.gard : nullptr, &GJ.galpha, 0, m, &GJ.tg);
+  for (size_t q = 0; q < GJ.trec.size(); ++q) GJ.trec[q] -= GM.trec[q];
+  publish_grads(*ls, grad_gps ? &GJ.trec : nullptr, 0, m);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);
@@ -3015,17 +2829,17 @@ int lmm_ilmm_post_logpdf_grad(const double* x, int d, int n, const double* y, co
 // posterior
 // ------------------------------------------------------------------------------------------------
 // noise: per-latent scalar (host, indexed by latent) used when noisevec == NULL; noisevec: device [k][n] per-point noise.
-static int posterior_create_common(const double* xd, int d, int n, const lmm_gp_t* gps, int m, const double* noise,
-                                   int l0, int l1, const double* delta, lmm_post_t** out, std::shared_ptr<ArdSet> ard,
-                                   const double* noisevec = nullptr) {
+static int posterior_create_common(const double* xd, int d, int n, std::shared_ptr<LatentSet> ls, const double* noise,
+                                   int l0, int l1, const double* delta, lmm_post_t** out, const double* noisevec = nullptr) {
+  const int m = (int)ls->lat.size();
+  const Latent* lts = ls->lat.data();
   const int ms = l1 - l0;
   lmm_post* P = new lmm_post();
   try {
     Dims D(n, 1);
     P->kind = 0; P->f32 = g_f32; P->n = n; P->d = d; P->l0 = l0; P->l1 = l1; P->m = m;
     P->NC = D.NC; P->NR = D.NR; P->ld = D.ld;
-    P->gps.assign(gps, gps + m);
-    P->ard = std::move(ard);
+    P->ls = std::move(ls);
     P->x = Buf<double>((size_t)d * n);
     HIPCHK(hipMemcpyAsync(P->x.p, xd, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, g.streams[0]));
     Buf<int> info(std::max(ms, 1));
@@ -3055,10 +2869,10 @@ static int posterior_create_common(const double* xd, int d, int n, const lmm_gp_
       GramArgs ga[LMM_MAX_BATCH];
       for (int j = 0; j < nb; ++j) {
         const int k = k0 + j;
-        const lmm_gp_t& gp = gps[l0 + k];
+        const Latent& gp = lts[l0 + k];
         GramArgs a{};
         a.A = P->L[k].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = P->x.p; a.d = d; a.n = n;
-        set_kernel(a, gp); a.pad_diag = 1.0;
+        gp.set_kernel(a); a.pad_diag = 1.0;
         a.diag_add = noisevec ? 0.0 : noise[l0 + k];
         a.diag_vec = noisevec ? P->noise_all.p + (size_t)k * n : nullptr;
         a.rider = delta + (size_t)k * n; a.rider_ld = n; a.nrider = 1;
@@ -3096,19 +2910,19 @@ int lmm_oilmm_posterior_create(const double* x, int d, int n, const double* y, i
   if (!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST, H;
   project_orthogonal(U, S, p, m, sigma2, T, ST, H);
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   Uploaded Td(T, st0);
   std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = gps[l].mean;
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   Uploaded meansd(means, st0);
   const int ms = latent_end - latent_begin;
   Buf<double> delta((size_t)n * std::max(ms, 1));
   if (ms > 0) project_on_device(yd.p, n, p, Td.buf, m, latent_begin, ms, meansd.buf.p + latent_begin, delta.p, st0);
-  return posterior_create_common(xd.p, d, n, gps, m, ST.data(), latent_begin, latent_end, delta.p, out, cg_.ard);
+  return posterior_create_common(xd.p, d, n, ls, ST.data(), latent_begin, latent_end, delta.p, out);
   LMM_CATCH
 }
 
@@ -3136,7 +2950,7 @@ int lmm_post_condition(const lmm_post_t* post, const double* U, const double* S,
   DevIn x2d(x2, (size_t)d * n2, st0), y2d(y2, (size_t)n2 * p, st0);
   Uploaded Td(T, st0);
   std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = P->gps[l].mean;
+  for (int l = 0; l < m; ++l) means[l] = P->ls->lat[l].mean;
   Uploaded meansd(means, st0);
   Buf<double> xall((size_t)d * n), delta((size_t)n * std::max(ms, 1)), nv((size_t)n * std::max(ms, 1)), d2buf((size_t)n2 * std::max(ms, 1));
   HIPCHK(hipMemcpyAsync(xall.p, P->x.p, (size_t)d * n1 * sizeof(double), hipMemcpyDeviceToDevice, st0));
@@ -3150,7 +2964,7 @@ int lmm_post_condition(const lmm_post_t* post, const double* U, const double* S,
     else launch_fill(nv.p + (size_t)k * n, n1, P->noise_scalar[k], st0);
     launch_fill(nv.p + (size_t)k * n + n1, n2, ST[l0 + k], st0);
   }
-  return posterior_create_common(xall.p, d, n, P->gps.data(), m, ST.data(), l0, l1, delta.p, out, P->ard, nv.p);
+  return posterior_create_common(xall.p, d, n, P->ls, ST.data(), l0, l1, delta.p, out, nv.p);
   LMM_CATCH
 }
 
@@ -3161,36 +2975,37 @@ int lmm_mogp_posterior_create(const double* x, int d, int n, const double* y, in
   LMM_TRY
   if (!x || !y || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0);
   std::vector<double> T((size_t)m * m, 0.0), means(m), noise(m, sigma2);
-  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = gps[l].mean; }
+  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = lts[l].mean; }
   Uploaded Td(T, st0), meansd(means, st0);
   const int ms = latent_end - latent_begin;
   Buf<double> delta((size_t)n * std::max(ms, 1));
   if (ms > 0) project_on_device(yd.p, n, m, Td.buf, m, latent_begin, ms, meansd.buf.p + latent_begin, delta.p, st0);
-  return posterior_create_common(xd.p, d, n, gps, m, noise.data(), latent_begin, latent_end, delta.p, out, cg_.ard);
+  return posterior_create_common(xd.p, d, n, ls, noise.data(), latent_begin, latent_end, delta.p, out);
   LMM_CATCH
 }
 
 // Dense-H posterior state from the stacked inputs xd (d x n, device), the projected residuals delta ([latent][point], m n,
 // device) and the per-batch SigmaT list: assemble blockdiag(K_l) + SigmaT_{batch(i)} (x) e_i e_i', factor, alpha = C \ delta.
-static int dense_posterior_build(const double* xd, int d, int n, const double* H, int p, int m, const lmm_gp_t* gps,
+static int dense_posterior_build(const double* xd, int d, int n, const double* H, int p, std::shared_ptr<LatentSet> ls,
                                  const double* delta, const std::vector<double>& sigs, const std::vector<int>& sigidx,
-                                 lmm_post_t** out, std::shared_ptr<ArdSet> ard) {
+                                 lmm_post_t** out) {
+  const int m = (int)ls->lat.size();
+  const Latent* lts = ls->lat.data();
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
   hipStream_t st0 = g.streams[0];
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) lat[l] = dense_dev(gps[l]);
+  for (int l = 0; l < m; ++l) lat[l] = lts[l].dense_dev();
   const int N = m * n;
   Dims D(N, 1);
   lmm_post* P = new lmm_post();
   try {
     P->kind = 1; P->f32 = g_f32; P->n = n; P->d = d; P->l0 = 0; P->l1 = m; P->m = m; P->p = p;
     P->NC = D.NC; P->NR = D.NR; P->ld = D.ld;
-    P->gps.assign(gps, gps + m);
-    P->ard = std::move(ard);
+    P->ls = std::move(ls);
     P->H.assign(H, H + (size_t)p * m);
     P->sigs = sigs; P->sigidx = sigidx;
     P->x = Buf<double>((size_t)d * n);
@@ -3211,7 +3026,7 @@ static int dense_posterior_build(const double* xd, int d, int n, const double* H
     DenseArgs a{};
     a.A = P->L[0].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = P->x.p; a.d = d; a.n = n; a.m = m;
     a.lat = P->latd.p; a.sigmaT = STd.buf.p; a.sig_idx = idxd.p; a.rider = P->ddelta.p; a.rider_ld = N; a.nrider = 1;
-    a.has_sum = any_sum(P->gps.data(), m);
+    a.has_sum = P->ls->any_sum();
     launch_dense_assemble(a, st0);
     potrf_rec(P->L[0].p, D.ld, D.NR, 0, D.NC, P->W[0].p, N, info.p, st0);
     HIPCHK(hipMemsetAsync(P->alpha[0].p, 0, (size_t)D.NC * sizeof(double), st0));
@@ -3235,7 +3050,7 @@ int lmm_ilmm_posterior_create(const double* x, int d, int n, const double* y, in
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !y || !H || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  RESOLVE_GPS(gps, m, d);
+  RESOLVE(gps, m, d);
   if (!jit) jit = &kDefaultJit;
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST;
@@ -3243,11 +3058,11 @@ int lmm_ilmm_posterior_create(const double* x, int d, int n, const double* y, in
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   Uploaded Td(T, st0);
   std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = gps[l].mean;
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   Uploaded meansd(means, st0);
   Buf<double> delta((size_t)n * m);
   project_on_device(yd.p, n, p, Td.buf, m, 0, m, meansd.buf.p, delta.p, st0);
-  return dense_posterior_build(xd.p, d, n, H, p, m, gps, delta.p, ST, std::vector<int>(n, 0), out, cg_.ard);
+  return dense_posterior_build(xd.p, d, n, H, p, ls, delta.p, ST, std::vector<int>(n, 0), out);
   LMM_CATCH
 }
 
@@ -3273,7 +3088,7 @@ int lmm_ilmm_post_condition(const lmm_post_t* post, double sigma2, const double*
   DevIn x2d(x2, (size_t)d * n2, st0), y2d(y2, (size_t)n2 * p, st0);
   Uploaded Td(T, st0);
   std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = P->gps[l].mean;
+  for (int l = 0; l < m; ++l) means[l] = P->ls->lat[l].mean;
   Uploaded meansd(means, st0);
   Buf<double> d2((size_t)n2 * m), delta((size_t)n * m), xall((size_t)d * n);
   project_on_device(y2d.p, n2, p, Td.buf, m, 0, m, meansd.buf.p, d2.p, st0);
@@ -3287,7 +3102,7 @@ int lmm_ilmm_post_condition(const lmm_post_t* post, double sigma2, const double*
   sigs.insert(sigs.end(), ST.begin(), ST.end());
   std::vector<int> idx = P->sigidx;
   idx.resize(n, (int)(P->sigs.size() / ((size_t)m * m)));
-  return dense_posterior_build(xall.p, d, n, P->H.data(), p, m, P->gps.data(), delta.p, sigs, idx, out, P->ard);
+  return dense_posterior_build(xall.p, d, n, P->H.data(), p, P->ls, delta.p, sigs, idx, out);
   LMM_CATCH
 }
 
@@ -3330,7 +3145,7 @@ int lmm_ilmm_post_mean_and_var(const lmm_post_t* post, double sigma2, const doub
 static void dense_post_cross(const lmm_post* P, const double* xsd, int d, int ns, int nr, double* R, int ldr, hipStream_t st) {
   const lmm_post* D = dense_state(P);
   guard_extent(R, nr, ldr, P->NC, true, "dense-H cross-Gram");
-  launch_dense_cross(R, ldr, nr, P->NC, xsd, ns, D->x.p, P->n, d, P->m, D->latd.p, any_sum(D->gps.data(), P->m) != 0, st);
+  launch_dense_cross(R, ldr, nr, P->NC, xsd, ns, D->x.p, P->n, d, P->m, D->latd.p, D->ls->any_sum() != 0, st);
   trsm_rec(R, ldr, nr, D->L[0].p, P->ld, D->W[0].p, 0, P->NC, st);
 }
 // Latent posterior means at xs, ml[l ns + s].  Float64: mu_l + K(x*, x) alpha_l (no solve needed).  fp32 compute mode: that sum cancels
@@ -3343,13 +3158,13 @@ static void dense_post_means(const lmm_post* P, const double* xsd, int d, int ns
   if (!g_f32) {
     Buf<double> pm_part(post_mean_partial_elems(ns, n));
     for (int l = 0; l < m; ++l)
-      post_mean_g(xsd, ns, D->x.p, n, d, D->alpha[0].p + (size_t)l * n, P->gps[l], pm_part.p, ml + (size_t)l * ns, st);
+      post_mean_g(xsd, ns, D->x.p, n, d, D->alpha[0].p + (size_t)l * n, P->ls->lat[l], pm_part.p, ml + (size_t)l * ns, st);
     HIPCHK(hipStreamSynchronize(st));              // pm_part is released on return
     return;
   }
   Buf<double> part(strip_partial_elems(m * ns, m * n, 1)), mu((size_t)m * ns);
   rider_stats_g(R, ldr, m * ns, m * n, D->z[0].p, 0.0, 0.0, part.p, ml, nullptr, st);
-  for (int l = 0; l < m; ++l) launch_fill(mu.p + (size_t)l * ns, ns, P->gps[l].mean, st);
+  for (int l = 0; l < m; ++l) launch_fill(mu.p + (size_t)l * ns, ns, P->ls->lat[l].mean, st);
   launch_vec_lin(ml, mu.p, 1.0, m * ns, ml, st);
   HIPCHK(hipStreamSynchronize(st));
 }
@@ -3363,7 +3178,7 @@ static void dense_post_cov_factor(const lmm_post* P, const double* xsd, int d, i
   DenseArgs a{};
   a.A = A; a.ld = Ds.ld; a.nrows = Ds.NR; a.ncols = Ds.NC; a.x = xsd; a.d = d; a.n = ns; a.m = m;
   a.lat = D->latd.p; a.sigmaT = sigadd_dev; a.rider = rider; a.rider_ld = m * ns; a.nrider = rider ? 1 : 0;
-  a.has_sum = any_sum(D->gps.data(), m);
+  a.has_sum = D->ls->any_sum();
   guard_extent(A, Ds.NR, Ds.ld, Ds.NC, true, "dense-H posterior covariance");
   launch_dense_assemble(a, st);
   gemm_nt_g(A, Ds.ld, R, ldr, R, ldr, Ds.NC, Ds.NC, P->NC, 1, false, st, "Schur complement (dense-H posterior covariance)");
@@ -3509,7 +3324,7 @@ int lmm_ilmm_post_latent_view(const lmm_post_t* post, lmm_post_t** out) {
   lmm_post* V = new lmm_post();
   V->f32 = B->f32; V->kind = 1; V->n = B->n; V->d = B->d; V->l0 = 0; V->l1 = B->m; V->m = B->m; V->p = B->m;
   V->NC = B->NC; V->NR = B->NR; V->ld = B->ld;
-  V->gps = B->gps; V->ard = B->ard; V->sigs = B->sigs; V->sigidx = B->sigidx;
+  V->ls = B->ls; V->sigs = B->sigs; V->sigidx = B->sigidx;
   V->H.assign((size_t)B->m * B->m, 0.0);
   for (int l = 0; l < B->m; ++l) V->H[l + (size_t)l * B->m] = 1.0;
   V->base = B;
@@ -3537,30 +3352,29 @@ int lmm_post_destroy(lmm_post_t* post) {
 }
 
 // Rk (nsr x NC, ldr) = K(xs, x): the cross-Gram of a posterior latent's training inputs as rider rows (rows beyond ns zero).
-static GramArgs cross_gram_args(const lmm_post* P, const lmm_gp_t& gp, const double* xsd, int d, int ns, double* Rk, int ldr,
+static GramArgs cross_gram_args(const lmm_post* P, const Latent& gp, const double* xsd, int d, int ns, double* Rk, int ldr,
                                 int nsr) {
   GramArgs r{};
   r.A = Rk; r.ld = ldr; r.nrows = P->NC + nsr; r.ncols = P->NC; r.row_tile0 = P->NC / 64; r.row_shift = P->NC; r.full = 1;
-  r.x = P->x.p; r.d = d; r.n = P->n; set_kernel(r, gp);
+  r.x = P->x.p; r.d = d; r.n = P->n; gp.set_kernel(r);
   r.xs = xsd; r.ns = ns;
   return r;
 }
-static void cross_gram(const lmm_post* P, const lmm_gp_t& gp, const double* xsd, int d, int ns, double* Rk, int ldr, int nsr,
+static void cross_gram(const lmm_post* P, const Latent& gp, const double* xsd, int d, int ns, double* Rk, int ldr, int nsr,
                        hipStream_t st) {
   gram_g(cross_gram_args(P, gp, xsd, d, ns, Rk, ldr, nsr), st);
 }
 
 // Latent marginals (mean, var) of latents [l0, l1) at xs into device arrays (ns per latent).
-// post != NULL: posterior latents; else prior latents gps[l0..l1).  Caller holds g_mu.
-static int latent_marginals_dev(const lmm_post* P, const lmm_gp_t* gps_shard, int ms, const double* xsd, int d, int ns,
+// post != NULL: posterior latents; else the prior latents lts_shard[0..ms).  Caller holds g_mu.
+static int latent_marginals_dev(const lmm_post* P, const Latent* lts_shard, int ms, const double* xsd, int d, int ns,
                                 double* mean_lat, double* var_lat) {
   if (ms == 0) return LMM_OK;
   if (P == nullptr) {
     fork_slots(1);
     for (int k = 0; k < ms; ++k) {
-      LatentDev gd = to_dev(gps_shard[k]);
       // prior: constant mean, variance kappa(0)
-      rider_stats_g(nullptr, 0, ns, 0, nullptr, gd.mean, prior_var(gps_shard[k]), nullptr, mean_lat + (size_t)k * ns,
+      rider_stats_g(nullptr, 0, ns, 0, nullptr, lts_shard[k].mean, lts_shard[k].prior_var(), nullptr, mean_lat + (size_t)k * ns,
                          var_lat + (size_t)k * ns, g.streams[0]);
     }
     return LMM_OK;
@@ -3585,7 +3399,7 @@ static int latent_marginals_dev(const lmm_post* P, const lmm_gp_t* gps_shard, in
     GramArgs ga[LMM_MAX_BATCH];
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      ga[j] = cross_gram_args(P, P->gps[P->l0 + k], xsd, d, ns, R[s][j].p, ldr, nsr);
+      ga[j] = cross_gram_args(P, P->ls->lat[P->l0 + k], xsd, d, ns, R[s][j].p, ldr, nsr);
       Rb.p[j] = R[s][j].p; Lb.p[j] = P->L[k].p; Wb.p[j] = P->W[k].p;
     }
     {
@@ -3596,11 +3410,11 @@ static int latent_marginals_dev(const lmm_post* P, const lmm_gp_t* gps_shard, in
     trsm_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st);       // R_j <- K(x*, x) L_j^-T for the whole batch
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      const lmm_gp_t& gp = P->gps[P->l0 + k];
+      const Latent& gp = P->ls->lat[P->l0 + k];
       // mean = mu + K(x*,x) alpha = mu + R' (L^-1 delta);  var = kappa(0) - colsumsq(R)   (one pass over R)
       const double rb = (double)ns * P->n * 8.0;                   // R read once
       ProfScope ps(LMM_PROF_STRIP, rb, st, ns, P->n, 0, rb);
-      rider_stats_g(R[s][j].p, ldr, ns, P->n, P->z[k].p, gp.mean, prior_var(gp), part[s].p, mean_lat + (size_t)k * ns,
+      rider_stats_g(R[s][j].p, ldr, ns, P->n, P->z[k].p, gp.mean, gp.prior_var(), part[s].p, mean_lat + (size_t)k * ns,
                          var_lat + (size_t)k * ns, st);
     }
   }
@@ -3618,12 +3432,12 @@ int lmm_latent_marginals(const lmm_post_t* post, const lmm_gp_t* gps, int m_shar
   if (!xs || !mean_lat || !var_lat || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (post && post->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "per-latent marginals of the dense-H posterior (coupled latents): use lmm_ilmm_post_mean_and_var");
   const int ms = post ? (post->l1 - post->l0) : m_shard;
-  CallGps cg_;
-  if (!post) { if (int rc = resolve_gps(gps, m_shard, d, cg_)) return rc; if (cg_.ard) gps = cg_.v.data(); }
+  std::shared_ptr<LatentSet> ls;
+  if (!post) { if (int rc = resolve(gps, m_shard, d, ls)) return rc; }
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)d * ns, st0);
   DevOut mo(mean_lat, (size_t)ns * ms), vo(var_lat, (size_t)ns * ms);
-  if (int rc = latent_marginals_dev(post, gps, ms, xsd.p, d, ns, mo.p, vo.p)) return rc;
+  if (int rc = latent_marginals_dev(post, post ? nullptr : ls->lat.data(), ms, xsd.p, d, ns, mo.p, vo.p)) return rc;
   mo.finish(st0); vo.finish(st0);
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
@@ -3641,10 +3455,10 @@ int lmm_oilmm_mean_and_var(const lmm_post_t* post, const lmm_gp_t* gps, const do
   if (post && post->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "dense-H posterior handle: use lmm_ilmm_post_mean_and_var");
   if (!jit) jit = &kDefaultJit;
   int l0 = latent_begin, l1 = latent_end;
-  CallGps cg_;
-  if (post) { l0 = post->l0; l1 = post->l1; if (post->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", post->m, m); }
-  else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
-  if (cg_.ard) gps = cg_.v.data();
+  std::shared_ptr<LatentSet> ls;
+  if (post) { l0 = post->l0; l1 = post->l1; ls = post->ls; if (post->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", post->m, m); }
+  else if (int rc = resolve(gps, m, d, ls)) return rc;
+  const Latent* lts = ls->lat.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   const int ms = l1 - l0;
   hipStream_t st0 = g.streams[0];
@@ -3664,7 +3478,7 @@ int lmm_oilmm_mean_and_var(const lmm_post_t* post, const lmm_gp_t* gps, const do
     if (post && post->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, xs has d=%d", post->d, d);
     Buf<double> pm_part(post ? post_mean_partial_elems(ns, post->n) : 1);
     for (int k = 0; k < ms; ++k) {
-      const lmm_gp_t& gp = post ? post->gps[l0 + k] : gps[l0 + k];
+      const Latent& gp = lts[l0 + k];
       post_mean_g(xsd.p, ns, post ? post->x.p : nullptr, post ? post->n : 0, d, post ? post->alpha[k].p : nullptr, gp,
                   pm_part.p, ml.p + (size_t)k * ns, st0);
     }
@@ -3674,7 +3488,7 @@ int lmm_oilmm_mean_and_var(const lmm_post_t* post, const lmm_gp_t* gps, const do
     HIPCHK(hipStreamSynchronize(st0));
     return LMM_OK;
   }
-  if (int rc = latent_marginals_dev(post, post ? nullptr : gps + l0, ms, xsd.p, d, ns, ml.p, vl.p)) return rc;
+  if (int rc = latent_marginals_dev(post, post ? nullptr : lts + l0, ms, xsd.p, d, ns, ml.p, vl.p)) return rc;
   DevOut mo(mean_out, (size_t)ns * p), vo(var_out, (size_t)ns * p);
   // reference src/oilmm.jl:69,72: M = H M_latent;  V = abs2.(H) V_latent .+ sigma2   (V_latent carries the 1e-18 jitter);
   // Float64 VALU by default, v_mfma_f32_16x16x32_bf16 under lmm_set_projection_dtype(LMM_PROJ_BF16 / _BF16X2)
@@ -3698,11 +3512,10 @@ static int mean_var_grad_xs_dev(const lmm_post* P, int ms, const double* xsd, in
   if (vbar == nullptr) {
     Buf<double> part(pred_grad_x_partial_elems(P->n, ns, d));
     for (int k = 0; k < ms; ++k) {
-      const lmm_gp_t& gp = P->gps[P->l0 + k];
-      const SumTerms* Sk = sum_of(gp);
-      for (int c = 0; c < (Sk ? Sk->nt : 1); ++c)       // a sum latent: one accumulating pass per term
+      const Latent& gp = P->ls->lat[P->l0 + k];
+      for (int c = 0; c < gp.nt(); ++c)                 // one accumulating pass per term
         launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, nullptr, nullptr, 0,
-                           Sk ? Sk->ev[c] : to_dev(gp), part.p, gout, k > 0 || c > 0, st0);
+                           gp.terms[c].ev, part.p, gout, k > 0 || c > 0, st0);
     }
     HIPCHK(hipStreamSynchronize(st0));
     return LMM_OK;
@@ -3728,7 +3541,7 @@ static int mean_var_grad_xs_dev(const lmm_post* P, int ms, const double* xsd, in
     GramArgs ga[LMM_MAX_BATCH];
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      ga[j] = cross_gram_args(P, P->gps[P->l0 + k], xsd, d, ns, R[s][j].p, ldr, nsr);
+      ga[j] = cross_gram_args(P, P->ls->lat[P->l0 + k], xsd, d, ns, R[s][j].p, ldr, nsr);
       Rb.p[j] = R[s][j].p; Lb.p[j] = P->L[k].p; Wb.p[j] = P->W[k].p;
     }
     gram_batch_g(ga, nb, st);
@@ -3736,11 +3549,10 @@ static int mean_var_grad_xs_dev(const lmm_post* P, int ms, const double* xsd, in
     trsm_right_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st);    // R_j <- R_j L_j^-1 = K(x*, x) K_j^-1
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      const lmm_gp_t& gp = P->gps[P->l0 + k];
-      const SumTerms* Sk = sum_of(gp);
-      for (int c = 0; c < (Sk ? Sk->nt : 1); ++c) {
+      const Latent& gp = P->ls->lat[P->l0 + k];
+      for (int c = 0; c < gp.nt(); ++c) {
         launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, vbar + (size_t)k * ns, R[s][j].p, ldr,
-                           Sk ? Sk->ev[c] : to_dev(gp), part[s].p, acc[s].p, used[s] != 0, st);
+                           gp.terms[c].ev, part[s].p, acc[s].p, used[s] != 0, st);
         used[s] = 1;
       }
     }
@@ -3769,12 +3581,12 @@ int lmm_oilmm_mean_and_var_grad_xs(const lmm_post_t* post, const lmm_gp_t* gps, 
     return fail(LMM_ERR_UNSUPPORTED, "gradients of the predictive marginals of a dense-H posterior (coupled latents) are not served");
   if (int rc = input_grad_check(d, true)) return rc;
   int l0 = latent_begin, l1 = latent_end;
-  CallGps cg_;
+  std::shared_ptr<LatentSet> ls;
   if (post) {
     l0 = post->l0; l1 = post->l1;
     if (post->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", post->m, m);
     if (post->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, xs has d=%d", post->d, d);
-  } else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
+  } else if (int rc = resolve(gps, m, d, ls)) return rc;
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   const int ms = l1 - l0;
   hipStream_t st0 = g.streams[0];
@@ -3808,7 +3620,7 @@ int lmm_oilmm_mean_and_var_grad_xs(const lmm_post_t* post, const lmm_gp_t* gps, 
 }
 
 // R (nsr x NC, ldr) = K(xs, x) L^-T for latent k of the posterior: the riders of the cross-Gram solved against the factor.
-static void cross_solve(const lmm_post* P, int k, const lmm_gp_t& gp, const double* xsd, int d, int ns, double* Rk, int ldr,
+static void cross_solve(const lmm_post* P, int k, const Latent& gp, const double* xsd, int d, int ns, double* Rk, int ldr,
                         int nsr, hipStream_t st) {
   cross_gram(P, gp, xsd, d, ns, Rk, ldr, nsr, st);
   trsm_rec(Rk, ldr, nsr, P->L[k].p, P->ld, P->W[k].p, 0, P->NC, st);
@@ -3816,15 +3628,15 @@ static void cross_solve(const lmm_post* P, int k, const lmm_gp_t& gp, const doub
 
 // Per-latent posterior (or prior) covariance at xs as a factor matrix B (NRs x NCs): gram(xs) + diag_add - R R' (posterior,
 // R from cross_solve), rider row = rider_vec.  Not factorised here (the caller batches potrf_rec).  Caller holds g_mu.
-static GramArgs cov_args(const lmm_gp_t& gp, const double* xsd, int d, int ns, double diag_add, const double* rider_vec,
+static GramArgs cov_args(const Latent& gp, const double* xsd, int d, int ns, double diag_add, const double* rider_vec,
                          const Dims& Ds, double* B) {
   GramArgs a{};
   a.A = B; a.ld = Ds.ld; a.nrows = Ds.NR; a.ncols = Ds.NC; a.x = xsd; a.d = d; a.n = ns;
-  set_kernel(a, gp); a.diag_add = diag_add; a.pad_diag = 1.0;
+  gp.set_kernel(a); a.diag_add = diag_add; a.pad_diag = 1.0;
   a.rider = rider_vec; a.rider_ld = ns; a.nrider = rider_vec ? 1 : 0;
   return a;
 }
-static void cov_at_xs(const lmm_post* P, const lmm_gp_t& gp, const double* xsd, int d, int ns, double diag_add,
+static void cov_at_xs(const lmm_post* P, const Latent& gp, const double* xsd, int d, int ns, double diag_add,
                       const double* rider_vec, const Dims& Ds, double* B, const double* Rk, int ldr, hipStream_t st) {
   gram_g(cov_args(gp, xsd, d, ns, diag_add, rider_vec, Ds, B), st);
   // Schur complement on the leading NCs x NCs block (rows of R beyond ns are zero)
@@ -3863,13 +3675,13 @@ struct XsSlots {
     BatchPtr Rb{}, Lb{}, Wb{};
     GramArgs ga[LMM_MAX_BATCH];
     for (int j = 0; j < nb; ++j) {
-      ga[j] = cross_gram_args(P, P->gps[P->l0 + k0 + j], xsd, d, ns, R[s][j].p, ldr, nsr);
+      ga[j] = cross_gram_args(P, P->ls->lat[P->l0 + k0 + j], xsd, d, ns, R[s][j].p, ldr, nsr);
       Rb.p[j] = R[s][j].p; Lb.p[j] = P->L[k0 + j].p; Wb.p[j] = P->W[k0 + j].p;
     }
     gram_batch_g(ga, nb, st);
     trsm_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st);
     for (int j = 0; j < nb; ++j)
-      rider_stats_g(R[s][j].p, ldr, ns, P->n, P->z[k0 + j].p, P->gps[P->l0 + k0 + j].mean, 0.0, part[s].p, mu[s][j].p, nullptr, st);
+      rider_stats_g(R[s][j].p, ldr, ns, P->n, P->z[k0 + j].p, P->ls->lat[P->l0 + k0 + j].mean, 0.0, part[s].p, mu[s][j].p, nullptr, st);
   }
 };
 
@@ -3885,14 +3697,14 @@ extern "C" int lmm_lmm_mean_and_cov(const lmm_post_t* post, const lmm_gp_t* gps,
   if (!jit) jit = &kDefaultJit;
   const lmm_post* P = post;
   int l0 = latent_begin, l1 = latent_end;
-  CallGps cg_;
+  std::shared_ptr<LatentSet> ls;
   if (P) {
     if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "full covariance of the dense-H posterior is not built");
-    l0 = P->l0; l1 = P->l1;
+    l0 = P->l0; l1 = P->l1; ls = P->ls;
     if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", P->m, m);
     if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  } else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
-  if (cg_.ard) gps = cg_.v.data();
+  } else if (int rc = resolve(gps, m, d, ls)) return rc;
+  const Latent* lts = ls->lat.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   const int ms = l1 - l0;
   hipStream_t st0 = g.streams[0];
@@ -3920,7 +3732,7 @@ extern "C" int lmm_lmm_mean_and_cov(const lmm_post_t* post, const lmm_gp_t* gps,
     BatchPtr cl{};
     for (int j = 0; j < nl; ++j) {
       const int k = k0 + j;
-      const lmm_gp_t& gp = P ? P->gps[l0 + k] : gps[l0 + k];
+      const Latent& gp = lts[l0 + k];
       if (P) cross_solve(P, k, gp, xsd.p, d, ns, R.p, ldr, nsr, st0);
       rider_stats_g(P ? R.p : nullptr, ldr, ns, P ? P->n : 0, P ? P->z[k].p : nullptr, gp.mean, 0.0, part.p,
                          ml.p + (size_t)k * ns, nullptr, st0);
@@ -3951,14 +3763,14 @@ extern "C" int lmm_mogp_cross_cov(const lmm_post_t* post, const lmm_gp_t* gps, i
   if ((double)m * n * (double)m * n2 > 4e8) return fail(LMM_ERR_UNSUPPORTED, "cross-covariance (m n) x (m n2) too large");
   const lmm_post* P = post;
   int l0 = latent_begin, l1 = latent_end;
-  CallGps cg_;
+  std::shared_ptr<LatentSet> ls;
   if (P) {
     if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "cross-covariance of the coupled latents of a dense-H posterior is not built");
-    l0 = P->l0; l1 = P->l1;
+    l0 = P->l0; l1 = P->l1; ls = P->ls;
     if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, m = %d", P->m, m);
     if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, x has d=%d", P->d, d);
-  } else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
-  if (cg_.ard) gps = cg_.v.data();
+  } else if (int rc = resolve(gps, m, d, ls)) return rc;
+  const Latent* lts = ls->lat.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)d * n2, st0);
@@ -3973,10 +3785,10 @@ extern "C" int lmm_mogp_cross_cov(const lmm_post_t* post, const lmm_gp_t* gps, i
   int ldr = std::max(nxr, NCy); if ((ldr % 512) == 0) ldr += 16;
   Buf<double> Rx(P ? mat_count((size_t)ldr * P->NC) : 1), Ry(P ? mat_count((size_t)ldr * P->NC) : 1);
   for (int l = l0; l < l1; ++l) {
-    const lmm_gp_t& gp = P ? P->gps[l] : gps[l];
+    const Latent& gp = lts[l];
     GramArgs a{};
     a.A = Kb.p; a.ld = ldk; a.nrows = NCy + nxr; a.ncols = NCy; a.row_tile0 = NCy / 64; a.row_shift = NCy; a.full = 1;
-    a.x = yd.p; a.d = d; a.n = n2; set_kernel(a, gp);
+    a.x = yd.p; a.d = d; a.n = n2; gp.set_kernel(a);
     a.xs = xd.p; a.ns = n;
     gram_g(a, st0, "cross-covariance K(x, y)");
     if (P) {
@@ -4042,7 +3854,7 @@ int lmm_oilmm_post_logpdf(const lmm_post_t* post, const double* U, const double*
     BatchPtr Bb{}, Rb{};
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      const lmm_gp_t& gp = P->gps[l0 + k];
+      const Latent& gp = P->ls->lat[l0 + k];
       launch_vec_lin(Ty_shard + (size_t)k * ns, X.mu[s][j].p, -1.0, ns, X.rid[s][j].p, st);
       ga[j] = cov_args(gp, xsd.p, d, ns, ST[l0 + k], X.rid[s][j].p, Ds, X.B[s][j].p);
       Bb.p[j] = X.B[s][j].p; Rb.p[j] = X.R[s][j].p;
@@ -4083,14 +3895,14 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps, const double
   if (!jit) jit = &kDefaultJit;
   const lmm_post* P = post;
   int l0 = latent_begin, l1 = latent_end;
-  CallGps cg_;
+  std::shared_ptr<LatentSet> ls;
   if (P) {
     if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "dense-H posterior handle: use lmm_ilmm_post_rand");
-    l0 = P->l0; l1 = P->l1;
+    l0 = P->l0; l1 = P->l1; ls = P->ls;
     if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", P->m, m);
     if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  } else if (int rc = resolve_gps(gps, m, d, cg_)) return rc;
-  if (cg_.ard) gps = cg_.v.data();
+  } else if (int rc = resolve(gps, m, d, ls)) return rc;
+  const Latent* lts = ls->lat.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   const int ms = l1 - l0;
   // OILMM: f(x) default jitter 1e-18 (reference src/oilmm.jl:47); dense-H ILMM: 1e-12 (src/ilmm.jl:84)
@@ -4120,7 +3932,7 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps, const double
     BatchPtr Bb{}, Rb{};
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      const lmm_gp_t& gp = P ? P->gps[l0 + k] : gps[l0 + k];
+      const Latent& gp = lts[l0 + k];
       ga[j] = cov_args(gp, xsd.p, d, ns, jitter, nullptr, Ds, Xs.B[s][j].p);
       Bb.p[j] = Xs.B[s][j].p; Rb.p[j] = Xs.R[s][j].p;
       Bt.add(Xs.B[s][j].p, Xs.WB[s][j].p, info.p + k);
@@ -4129,7 +3941,7 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps, const double
     potrf_batch(Bt, Ds.ld, Ds.NR, Ds.NC, ns, st);      // ONE factorisation per latent, nsamples triangular products
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
-      const double mu_const = P ? 0.0 : gps[l0 + k].mean;
+      const double mu_const = P ? 0.0 : lts[l0 + k].mean;
       for (int q = 0; q < nsamples; ++q) {
         double* Xq = X.p + ((size_t)q * ms + k) * ns;
         launch_trmv_lower(Xs.B[s][j].p, Ds.ld, ns, zd.p + ((size_t)q * m + l0 + k) * ns, mu_const, Xs.part[s].p, Xq, st);
@@ -4258,12 +4070,12 @@ int lmm_dev_gram(double* A, int ld, int nrows, int ncols, const double* x, int d
   if (!A || !x || !gp || nrows % 64 || ncols % 64 || (ld & 1) || ld < nrows) return fail(LMM_ERR_ARG, "bad arguments");
   GramArgs a{};
   a.A = A; a.ld = ld; a.nrows = nrows; a.ncols = ncols; a.x = x; a.d = d; a.n = n;
-  CallGps cg_;
-  if (gp->kind >> 8) {                  // an ARD latent: resolve its tag like the entry points do
-    if (int rc = resolve_gps(gp, 1, d, cg_)) return rc;
-    gp = cg_.v.data();
-  }
-  set_kernel(a, *gp); a.diag_add = diag_add; a.pad_diag = 1.0;
+  std::shared_ptr<LatentSet> ls;
+  if (gp->kind >> 8) {                  // a tagged latent: resolve its tag like the entry points do
+    if (int rc = resolve(gp, 1, d, ls)) return rc;
+    ls->lat[0].set_kernel(a);
+  } else plain_latent(*gp).set_kernel(a);
+  a.diag_add = diag_add; a.pad_diag = 1.0;
   gram_g(a, g.streams[0]);
   HIPCHK(hipStreamSynchronize(g.streams[0]));
   return LMM_OK;
