@@ -310,6 +310,7 @@ struct Dims {
 #define LMM_ARD_MAX_TAGS 4096
 struct ArdTag {           // d = 0: no factors; alpha = 0: no shape; terms non-empty: a sum tag (lmm_kernel_sum_create; d = 0, alpha = 0)
   int d; std::vector<double> ard, grad; double alpha = 0.0, galpha = 0.0;
+  double rho = 0.0, grho = 0.0;         // a periodic latent's rho (lmm_kernel_tag_create_periodic; 0: none) and its latest gradient
   std::vector<lmm_gp_t> terms;
   std::vector<lmm_gp_grad_t> tgrad;     // a sum tag's latest per-term (d/dv_c, d/dl_c, 0)
 };
@@ -324,6 +325,7 @@ struct KernelTerm {
   bool has_ard = false;            // the tag has factors
   double mult = 1.0, fold = 1.0;   // multiplier of the factors; the factor a folded term's lengthscale was multiplied by (1 otherwise)
   double alpha = 0.0;              // the tag's RQ shape (0: none; the term then reports no alpha gradient)
+  double rho = 0.0;                // the tag's periodic rho (0: none: rho = 1, and the term reports no rho gradient)
   double v = 1.0, ls = 1.0;        // v_c, l_c
   LatentDev ev{}, gd{};
   int ev_ent = -1, gd_ent = -1;    // entries of LatentSet::host that ev.ils / gd.ils point to (-1: isotropic)
@@ -336,6 +338,10 @@ struct Latent {
   const LatentDev* dterms = nullptr;                      // a sum latent's terms[c].ev on the device
   bool is_sum() const { return kind == LMM_KERNEL_SUM; }
   int nt() const { return (int)terms.size(); }
+  bool has_periodic() const {
+    for (const KernelTerm& T : terms) if (T.ev.kind == LMM_KERNEL_PERIODIC) return true;
+    return false;
+  }
   LatentDev dev() const {
     if (!is_sum()) { LatentDev d = terms[0].ev; d.mean = mean; return d; }
     LatentDev d{};
@@ -347,6 +353,7 @@ struct Latent {
   void set_kernel(GramArgs& a) const {
     const LatentDev d = dev();
     a.kind = d.kind; a.var = d.var; a.inv_ls = d.inv_ls; a.ils = d.ils; a.alpha = d.alpha; a.terms = d.terms; a.nterms = d.nterms;
+    a.sum_per = is_sum() && has_periodic();
   }
   // kappa(0): the variance, or v0 sum_c v_c for a sum latent
   double prior_var() const {
@@ -378,9 +385,13 @@ struct LatentSet {
   Buf<double> dev;                          // the same on the device
   std::vector<LatentDev> thost;             // the evaluation descriptors of every sum term (host, then `tdev`)
   Buf<LatentDev> tdev;
-  int any_sum() const {                     // the dense kernels' instantiation
-    for (const Latent& L : lat) if (L.is_sum()) return 1;
-    return 0;
+  int any_sum() const {                     // the dense kernels' instantiation: 2 with a periodic latent or term, 1 with a sum latent
+    int r = 0;
+    for (const Latent& L : lat) {
+      if (L.has_periodic()) return 2;
+      if (L.is_sum()) r = 1;
+    }
+    return r;
   }
   // d of the per-dimension gradient reduction (0: every term takes the isotropic one)
   int ard_grad_d() const {
@@ -401,13 +412,15 @@ struct LatentSet {
   }
 };
 
-// One term from its base kind, V, multiplier E and the factors / shape of its tag: fold, d == 1, or a (shared) vector.
-void resolve_term(LatentSet& S, KernelTerm& T, int base, double V, double E, const std::vector<double>& ard, double alpha,
+// One term from its base kind, V, multiplier E and the factors / shape of its tag: fold, d == 1, or a (shared) vector.  A periodic
+// term's descriptor carries 1 / rho^2 in the alpha slot, which it does not otherwise use (so same_kernel compares rho with it).
+void resolve_term(LatentSet& S, KernelTerm& T, int base, double V, double E, const std::vector<double>& ard, double alpha, double rho,
                   std::map<std::pair<int, double>, int>& entry_of) {
   const int d = S.d;
-  T.mult = E; T.alpha = alpha;
+  T.mult = E; T.alpha = alpha; T.rho = rho;
   LatentDev ev{};
   ev.kind = base; ev.var = V; ev.inv_ls = 1.0 / E; ev.alpha = alpha > 0.0 ? alpha : LMM_RQ_DEFAULT_ALPHA;
+  if (base == LMM_KERNEL_PERIODIC) ev.alpha = rho > 0.0 ? 1.0 / (rho * rho) : 1.0;
   T.gd = ev;
   if (!ard.empty()) {
     T.has_ard = true;
@@ -435,6 +448,7 @@ Latent plain_latent(const lmm_gp_t& gp) {
   L.terms.resize(1);
   LatentDev& ev = L.terms[0].ev;
   ev.kind = L.kind; ev.var = gp.variance; ev.inv_ls = 1.0 / gp.lengthscale; ev.alpha = LMM_RQ_DEFAULT_ALPHA;
+  if (L.kind == LMM_KERNEL_PERIODIC) ev.alpha = 1.0;      // 1 / rho^2 at the default rho = 1
   L.terms[0].mult = gp.lengthscale;
   L.terms[0].gd = ev;
   return L;
@@ -445,7 +459,7 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
   if (!gps) return fail(LMM_ERR_ARG, "gps is NULL");
   for (int l = 0; l < m; ++l) {
     const int base = gps[l].kind & LMM_KERNEL_BASE_MASK;
-    if (gps[l].kind < 0 || base > LMM_KERNEL_SUM) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
+    if (gps[l].kind < 0 || (base > LMM_KERNEL_SUM && base != LMM_KERNEL_PERIODIC)) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
     if (base == LMM_KERNEL_SUM && (gps[l].kind >> 8) == 0) return fail(LMM_ERR_ARG, "latent %d: a sum latent needs a sum tag (lmm_kernel_sum_create)", l);
     if (!(gps[l].variance > 0.0) || !(gps[l].lengthscale > 0.0)) return fail(LMM_ERR_ARG, "latent %d: variance and lengthscale must be > 0", l);
   }
@@ -460,10 +474,10 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
     if (tag == 0) continue;
     L.tag = tag;
     std::vector<double> ard;
-    double alpha;
+    double alpha, rho;
     std::vector<lmm_gp_t> terms;
     std::vector<std::vector<double>> tard;
-    std::vector<double> talpha;
+    std::vector<double> talpha, trho;
     {
       std::lock_guard<std::mutex> lk(g_ard_mu);
       auto it = g_ard_tags.find(tag);
@@ -474,11 +488,13 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
         return fail(LMM_ERR_DIM, "latent %d: ARD tag %d has %d dimensions, the inputs have %d", l, tag, it->second.d, d);
       ard = it->second.ard;
       alpha = it->second.alpha;
+      rho = it->second.rho;
       terms = it->second.terms;
       for (size_t c = 0; c < terms.size(); ++c) {
         const int tt = terms[c].kind >> 8;
         tard.emplace_back();
         talpha.push_back(0.0);
+        trho.push_back(0.0);
         if (tt == 0) continue;
         auto jt = g_ard_tags.find(tt);
         if (jt == g_ard_tags.end() || !jt->second.terms.empty())
@@ -487,6 +503,10 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
           return fail(LMM_ERR_DIM, "latent %d: term %d: tag %d has %d dimensions, the inputs have %d", l, (int)c, tt, jt->second.d, d);
         tard.back() = jt->second.ard;
         talpha.back() = jt->second.alpha;
+        trho.back() = jt->second.rho;
+        const int tb = terms[c].kind & LMM_KERNEL_BASE_MASK;
+        if ((talpha.back() > 0.0 && tb != LMM_KERNEL_RQ) || (trho.back() > 0.0 && tb != LMM_KERNEL_PERIODIC))
+          return fail(LMM_ERR_ARG, "latent %d: term %d: tag %d carries a shape its kernel kind %d does not take", l, (int)c, tt, tb);
       }
     }
     if (L.is_sum()) {
@@ -494,15 +514,17 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
       for (int c = 0; c < L.nt(); ++c) {
         KernelTerm& T = L.terms[c];
         T.tag = terms[c].kind >> 8; T.v = terms[c].variance; T.ls = terms[c].lengthscale;
-        resolve_term(*S, T, terms[c].kind & LMM_KERNEL_BASE_MASK, L.variance * T.v, L.lengthscale * T.ls, tard[c], talpha[c], entry_of);
+        resolve_term(*S, T, terms[c].kind & LMM_KERNEL_BASE_MASK, L.variance * T.v, L.lengthscale * T.ls, tard[c], talpha[c], trho[c], entry_of);
       }
       continue;
     }
     if (alpha > 0.0 && L.kind != LMM_KERNEL_RQ)
       return fail(LMM_ERR_ARG, "latent %d: tag %d carries an RQ shape but the kernel kind is %d", l, tag, L.kind);
+    if (rho > 0.0 && L.kind != LMM_KERNEL_PERIODIC)
+      return fail(LMM_ERR_ARG, "latent %d: tag %d carries a periodic rho but the kernel kind is %d", l, tag, L.kind);
     KernelTerm& T = L.terms[0];
     T.tag = tag;
-    resolve_term(*S, T, L.kind, L.variance, L.lengthscale, ard, alpha, entry_of);
+    resolve_term(*S, T, L.kind, L.variance, L.lengthscale, ard, alpha, rho, entry_of);
     L.lengthscale = gps[l].lengthscale * T.fold;
   }
   if (!S->host.empty()) {
@@ -572,7 +594,7 @@ double grad_finish(const Latent& L, int d, const double* red, const double* ard,
     const double dE = T.gd.ils ? rc[0] : rc[0] * T.fold;
     o[0] = gV * L.variance;
     o[1] = dE * L.lengthscale;
-    o[2] = T.alpha > 0.0 ? rc[8] : 0.0;
+    o[2] = (T.alpha > 0.0 || T.rho > 0.0) ? rc[8] : 0.0;      // d/d alpha (RQ) or d/d rho (periodic): one slot, a term has one of them
     if (T.gd.ils) for (int k = 0; k < d; ++k) o[3 + k] = ard[(size_t)d * c + k];
     else if (T.has_ard) o[3] = rc[0];                      // d == 1: d/d l_eff, l_eff = multiplier * fold
     ds0 += dE * T.ls;
@@ -583,7 +605,7 @@ double grad_finish(const Latent& L, int d, const double* red, const double* ard,
 }
 // Publishes a gradient call's records (trec: m x LMM_SUM_MAX_TERMS of them, grad_finish) to the registry: every tag the call named is
 // reset; then, over the latents [l0, l1), a sum tag gets (d/dv_c, d/dl_c, 0) per term and each term's tag d/d ard[k] = multiplier *
-// d/d l_k and, with an RQ shape, d/d alpha, summed over the terms carrying it.  trec == nullptr (grad_gps NULL): zeros.
+// d/d l_k and, with an RQ shape, d/d alpha (with a periodic rho, d/d rho), summed over the terms carrying it.  trec == nullptr (grad_gps NULL): zeros.
 void publish_grads(const LatentSet& S, const std::vector<double>* trec, int l0, int l1) {
   bool any = false;
   for (const Latent& L : S.lat) any = any || L.tag != 0;
@@ -592,7 +614,7 @@ void publish_grads(const LatentSet& S, const std::vector<double>* trec, int l0, 
   auto reset = [&](int tag) {
     auto it = g_ard_tags.find(tag);
     if (tag == 0 || it == g_ard_tags.end()) return;
-    it->second.grad.assign(it->second.d, 0.0); it->second.galpha = 0.0;
+    it->second.grad.assign(it->second.d, 0.0); it->second.galpha = 0.0; it->second.grho = 0.0;
     it->second.tgrad.assign(it->second.terms.size(), lmm_gp_grad_t{0.0, 0.0, 0.0});
   };
   for (const Latent& L : S.lat) {
@@ -615,6 +637,7 @@ void publish_grads(const LatentSet& S, const std::vector<double>* trec, int l0, 
       if (T.has_ard)
         for (int k = 0; k < std::min(S.d, it->second.d); ++k) it->second.grad[k] += T.mult * r[3 + k];
       if (T.alpha > 0.0) it->second.galpha += r[2];
+      if (T.rho > 0.0) it->second.grho += r[2];
     }
   }
 }
@@ -1352,14 +1375,14 @@ static int ard_fail(int code, const char* msg) {
 }
 
 // Registers a validated tag (d = 0, ard unused: no factors; alpha = 0: no RQ shape).
-static int tag_register(int d, const double* ard, double alpha, int* tag, const char* full_msg) {
+static int tag_register(int d, const double* ard, double alpha, int* tag, const char* full_msg, double rho = 0.0) {
   std::lock_guard<std::mutex> lk(g_ard_mu);
   if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, full_msg);
   while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;     // tag << 8 stays a positive int
   const int t = g_ard_next;
   g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
   ArdTag& a = g_ard_tags[t];
-  a.d = d; a.ard.assign(ard, ard + d); a.grad.assign(d, 0.0); a.alpha = alpha;
+  a.d = d; a.ard.assign(ard, ard + d); a.grad.assign(d, 0.0); a.alpha = alpha; a.rho = rho;
   *tag = t;
   return LMM_OK;
 }
@@ -1381,13 +1404,21 @@ int lmm_kernel_tag_create(int d, const double* ard, double alpha, int* tag) {
   return tag_register(d, ard, alpha, tag, "lmm_kernel_tag_create: too many live tags");
 }
 
+int lmm_kernel_tag_create_periodic(int d, const double* ard, double rho, int* tag) {
+  if (d < 0 || !tag || (d == 0) != (ard == nullptr)) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create_periodic: bad arguments");
+  if (!(rho > 0.0 && std::isfinite(rho))) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create_periodic: rho must be finite and > 0");
+  for (int k = 0; k < d; ++k)
+    if (!(ard[k] > 0.0) || !std::isfinite(ard[k])) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create_periodic: factors must be finite and > 0");
+  return tag_register(d, ard, 0.0, tag, "lmm_kernel_tag_create_periodic: too many live tags", rho);
+}
+
 int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag) {
   if (nterms < 1 || nterms > LMM_SUM_MAX_TERMS || !terms || !tag)
     return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: nterms must be 1..4, terms and tag non-NULL");
   for (int c = 0; c < nterms; ++c) {
     const int base = terms[c].kind & LMM_KERNEL_BASE_MASK;
-    if (terms[c].kind < 0 || base > LMM_KERNEL_RQ)
-      return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: a term must have a base kind 0..4 (sums do not nest)");
+    if (terms[c].kind < 0 || (base > LMM_KERNEL_RQ && base != LMM_KERNEL_PERIODIC))
+      return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: a term must have a base kind 0..4 or 7 (sums do not nest)");
     if (!(terms[c].variance > 0.0) || !std::isfinite(terms[c].variance) || !(terms[c].lengthscale > 0.0) ||
         !std::isfinite(terms[c].lengthscale) || terms[c].mean != 0.0)
       return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term needs finite variance > 0, lengthscale > 0 and mean 0");
@@ -1401,6 +1432,8 @@ int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag) {
       return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term names an unknown tag or a sum tag");
     if (it->second.alpha > 0.0 && (terms[c].kind & LMM_KERNEL_BASE_MASK) != LMM_KERNEL_RQ)
       return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term's tag carries an RQ shape but its kind is not LMM_KERNEL_RQ");
+    if (it->second.rho > 0.0 && (terms[c].kind & LMM_KERNEL_BASE_MASK) != LMM_KERNEL_PERIODIC)
+      return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term's tag carries a periodic rho but its kind is not LMM_KERNEL_PERIODIC");
   }
   if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: too many live tags");
   while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
@@ -1428,7 +1461,17 @@ int lmm_kernel_tag_alpha_grad(int tag, double* out) {
   std::lock_guard<std::mutex> lk(g_ard_mu);
   auto it = g_ard_tags.find(tag);
   if (it == g_ard_tags.end()) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_alpha_grad: unknown tag");
+  if (it->second.rho > 0.0) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_alpha_grad: the tag carries a periodic rho, not an alpha");
   *out = it->second.galpha;
+  return LMM_OK;
+}
+
+int lmm_kernel_tag_rho_grad(int tag, double* out) {
+  if (!out) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_rho_grad: out is NULL");
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  auto it = g_ard_tags.find(tag);
+  if (it == g_ard_tags.end() || !(it->second.rho > 0.0)) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_rho_grad: unknown tag, or a tag without a rho");
+  *out = it->second.grho;
   return LMM_OK;
 }
 
@@ -3145,7 +3188,7 @@ int lmm_ilmm_post_mean_and_var(const lmm_post_t* post, double sigma2, const doub
 static void dense_post_cross(const lmm_post* P, const double* xsd, int d, int ns, int nr, double* R, int ldr, hipStream_t st) {
   const lmm_post* D = dense_state(P);
   guard_extent(R, nr, ldr, P->NC, true, "dense-H cross-Gram");
-  launch_dense_cross(R, ldr, nr, P->NC, xsd, ns, D->x.p, P->n, d, P->m, D->latd.p, D->ls->any_sum() != 0, st);
+  launch_dense_cross(R, ldr, nr, P->NC, xsd, ns, D->x.p, P->n, d, P->m, D->latd.p, D->ls->any_sum(), st);
   trsm_rec(R, ldr, nr, D->L[0].p, P->ld, D->W[0].p, 0, P->NC, st);
 }
 // Latent posterior means at xs, ml[l ns + s].  Float64: mu_l + K(x*, x) alpha_l (no solve needed).  fp32 compute mode: that sum cancels

@@ -10,7 +10,8 @@ struct BatchInfo { int* p[LMM_MAX_BATCH]; };
 
 // kind: the BASE kernel kind (lmm_kernel_kind); ils: nullptr (isotropic, inv_ls) or the latent's d per-dimension inverse lengthscales
 // (device; an ARD latent, d > 1).  An ARD latent keeps inv_ls = 1 / its common multiplier (the gradient reduction's d/d multiplier).
-// alpha: the RQ shape (unused by the other kinds).
+// alpha: the RQ shape; for a periodic latent (LMM_KERNEL_PERIODIC) the slot carries 1 / rho^2, inv_ls 1 / period and ils the
+// per-dimension 1 / P_k (unused by the other kinds).
 // A sum latent (kind LMM_KERNEL_SUM) has nterms (1..LMM_SUM_MAX_TERMS) resolved terms in `terms` (device): each an ordinary base-kind
 // descriptor whose var = v0 v_c, inv_ls = 1 / (s0 l_c) and ils = its per-dimension 1 / (s0 l_c ard_c[k]) (or nullptr); var and inv_ls
 // of the sum latent itself are v0 and 1 / s0.  terms is nullptr and nterms 0 for every other latent.
@@ -39,8 +40,9 @@ struct GramArgs {
   const double* xs; int ns;                    // rows ncols + r  <- kappa(xs_r, x_j)
   int* info_zero;                              // optional: the matrix's pivot-info word, zeroed by the launch (saves a memset per call)
   int cpw;                                     // column tiles per workgroup (set by the launcher: 4, or 1 when the grid would be small)
-  double alpha;                                // RQ shape (unused by the other kinds)
+  double alpha;                                // RQ shape; periodic: 1 / rho^2 (unused by the other kinds)
   const LatentDev* terms; int nterms;          // kind LMM_KERNEL_SUM: the resolved terms (device; see LatentDev)
+  int sum_per;                                 // kind LMM_KERNEL_SUM: some term is periodic (the instantiation that evaluates one)
 };
 
 // The same assembly for up to LMM_MAX_BATCH same-shaped matrices in ONE launch (blockIdx.z = matrix): everything in `base`
@@ -66,7 +68,8 @@ struct DenseArgs {
   const double* sigmaT;      // device, m x m column-major (nbatch of them when sig_idx != nullptr)
   const int* sig_idx;        // optional, device, n entries: which sigmaT the point's noise block uses (sequential conditioning)
   const double* rider; int rider_ld, nrider;
-  int has_sum;               // some lat[l] is a sum latent (the kernel instantiation that evaluates kappa_sum)
+  int has_sum;               // 1: some lat[l] is a sum latent (the kernel instantiation that evaluates kappa_sum); 2: some latent is
+                             // periodic or has a periodic term (the instantiation that also evaluates kappa_per)
 };
 
 void launch_gram(const GramArgs& a, hipStream_t st);
@@ -77,7 +80,7 @@ void launch_dense_assemble(const DenseArgs& a, hipStream_t st);
 void launch_dense_cov(const double* S, int lds, int ns, int m, const double* Hm, int p, double jitter, double sigma2, double* T,
                       double* out, hipStream_t st);
 void launch_dense_cross(double* R, int ldr, int nrows, int ncols, const double* xs, int ns, const double* x, int n, int d,
-                        int m, const LatentDev* lat, bool has_sum, hipStream_t st);
+                        int m, const LatentDev* lat, int has_sum, hipStream_t st);
 size_t dense_var_partial_elems(int ns, int p, int Ncols);
 void launch_dense_var(const double* R, int ldr, int ns, int m, int Ncols, const double* Hm, int p, const LatentDev* lat,
                       double jitter, double sigma2, double* partial, double* out, hipStream_t st);

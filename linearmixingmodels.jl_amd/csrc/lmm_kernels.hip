@@ -124,6 +124,26 @@ __device__ __forceinline__ double kappa(int kind, double var, double r, double r
   return kappa(kind, var, r, r2);
 }
 
+// PeriodicKernel: v exp(-q / (2 rho^2)), q = sum_k sin^2(pi (a_k - b_k) / P_k).  A periodic latent carries 1 / rho^2 in the alpha slot of
+// LatentDev / GramArgs (it has no alpha), 1 / P in inv_ls and the per-dimension 1 / P_k in ils.  It is not a function of a scaled
+// Euclidean distance, so every site that evaluates kappa(r) has a branch of its own for it.
+__device__ __forceinline__ double kappa_per(double var, double irho2, double q) { return var * exp_nonpos(-0.5 * irho2 * q); }
+// q by direct differences: sinpi reduces its argument exactly, so whole periods drop out without a rounding error.
+__device__ __forceinline__ double per_q(const double* __restrict__ a, const double* __restrict__ b, int d, double inv_ls,
+                                        const double* __restrict__ ils) {
+  double q = 0.0;
+  for (int k = 0; k < d; ++k) {
+    const double s = sinpi((a[k] - b[k]) * (ils ? ils[k] : inv_ls));
+    q = __builtin_fma(s, s, q);
+  }
+  return q;
+}
+// (sin, cos)(pi u) of a scaled coordinate u = x / P, reduced modulo 2 first (exact: u - 2 rint(u / 2) is representable).
+__device__ __forceinline__ void per_sincos(double u, double& s, double& c) {
+  u = __builtin_fma(-2.0, __builtin_rint(0.5 * u), u);
+  sincospi(u, &s, &c);
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -180,7 +200,10 @@ __device__ __forceinline__ double sqrt_dist(double x) {
 // A sum latent's kernel at the pair (a, b): sum over its terms (LatentDev.terms) of kappa_c, each term with its own variance v0 v_c,
 // lengthscale and kind.  The raw difference (d == 1) or squared distance (d > 1) is computed once and scaled per isotropic term by
 // inv_ls_c (inv_ls_c^2); a term with per-dimension lengthscales (ils, d > 1 only: d == 1 terms are folded on the host) takes its own
-// pass over the d coordinates.
+// pass over the d coordinates.  So does a periodic term (kappa_per), at every d; PER: the sum may hold one (PER = false
+// keeps the code and registers that sums of the other kinds always had).
+#define LMM_KERNEL_SUM_PER 8      // instantiation index of the Gram kernels for a sum latent with a periodic term (never a GramArgs.kind)
+template <bool PER>
 __device__ __forceinline__ double kappa_sum(const LatentDev* __restrict__ T, int nt, const double* __restrict__ a,
                                             const double* __restrict__ b, int d) {
   double dx = 0.0, D2 = 0.0;
@@ -190,6 +213,10 @@ __device__ __forceinline__ double kappa_sum(const LatentDev* __restrict__ T, int
   double acc = 0.0;
   for (int c = 0; c < nt; ++c) {
     const LatentDev g = T[c];
+    if (PER && g.kind == LMM_KERNEL_PERIODIC) {   // its own pass over the coordinates, as an ARD term
+      acc += kappa_per(g.var, g.alpha, per_q(a, b, d, g.inv_ls, g.ils));
+      continue;
+    }
     double r, r2;
     if (d == 1) { r = dx * g.inv_ls; r2 = r * r; }
     else {
@@ -255,8 +282,10 @@ __device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int
       for (int e = 0; e < 2; ++e) {
         double val = 0.0;
         if (rtype[e] == 0 || rtype[e] == 3) {
-          if constexpr (KIND == LMM_KERNEL_SUM) {
-            val = kappa_sum(a.terms, a.nterms, rpt[e], a.x + (size_t)j * a.d, a.d);
+          if constexpr (KIND == LMM_KERNEL_SUM || KIND == LMM_KERNEL_SUM_PER) {
+            val = kappa_sum<KIND == LMM_KERNEL_SUM_PER>(a.terms, a.nterms, rpt[e], a.x + (size_t)j * a.d, a.d);
+          } else if constexpr (KIND == LMM_KERNEL_PERIODIC) {
+            val = kappa_per(a.var, a.alpha, per_q(rpt[e], a.x + (size_t)j * a.d, a.d, a.inv_ls, a.ils));
           } else {
             double r, r2;
             if (a.d == 1) { r = fabs(rx[e] - xj) * a.inv_ls; r2 = r * r; }
@@ -446,23 +475,93 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
   }
 }
 
-// Sum latents (KIND = LMM_KERNEL_SUM): every tile of the strip takes the generic routine, which sums the terms per element, so each
+// Sum latents (KIND = LMM_KERNEL_SUM, or LMM_KERNEL_SUM_PER with a periodic term): every tile of the strip takes the generic routine, which sums the terms per element, so each
 // element is written once (assembly is write-bound: a pass per term would cost a full write each).  No separable d = 1 path.
-template <typename TS>
+template <int KIND, typename TS>
 __device__ __forceinline__ void gram_body_sum(const GramArgs& a) {
   const int ti = blockIdx.x + a.row_tile0, sy = blockIdx.y;
   for (int c4 = 0; c4 < a.cpw; ++c4) {
     const int tj = sy * a.cpw + c4;
     if (tj * 64 >= a.ncols) break;
     if (!a.full && ti < tj) break;                          // lower tiles only
-    gram_tile_generic<LMM_KERNEL_SUM, TS>(a, ti, tj);
+    gram_tile_generic<KIND, TS>(a, ti, tj);
+  }
+}
+
+// Periodic latents (KIND = LMM_KERNEL_PERIODIC).  Interior tiles (64 rows and 64 columns of points; d == 1, or 1 < d <= 8 when ND) do
+// not evaluate a sine per element:  sin(pi (x_i - x_j) / P) = s_i c_j - c_i s_j  with (s, c) = per_sincos(x / P).  A thread computes
+// (s, c) once for its two rows (per dimension), the 64 columns of a tile are staged in LDS, and an element costs 2 multiply/FMAs and
+// one FMA per dimension, a scale and one exp_nonpos -- what the SE path spends.  Nothing can overflow, so there is no range guard.
+// Against the direct form the difference is the rounding of x / P: pi eps |x| / P in the angle, i.e. up to pi eps (|x| / P) / rho^2
+// relative in an element.  Border / rider / pad tiles and d > 8 take the generic tile (direct differences and sinpi).
+template <bool ND, typename TS>
+__device__ __forceinline__ void gram_body_per(const GramArgs& a) {
+  constexpr int DM = ND ? 8 : 1;
+  __shared__ double colS[64 * DM], colC[64 * DM];
+  const int ti = blockIdx.x + a.row_tile0, sy = blockIdx.y;
+  const int t = threadIdx.x;
+  const int i0 = ti * 64 + 2 * (t & 31);
+  const int cg = t >> 5;
+  const double* rsrc = nullptr;                               // as in gram_body: x, or the cross-Gram inputs xs
+  int rbase = 0;
+  if (ti * 64 + 63 < a.n) { rsrc = a.x; }
+  else if (a.xs != nullptr && ti * 64 >= a.ncols && ti * 64 + 63 - a.ncols < a.ns) { rsrc = a.xs; rbase = a.ncols; }
+  const bool rows_fast = rsrc != nullptr && (ND ? (a.d > 1 && a.d <= DM) : a.d == 1);
+  double rs0[DM], rc0[DM], rs1[DM], rc1[DM];
+#pragma unroll
+  for (int k = 0; k < DM; ++k) { rs0[k] = 0.0; rc0[k] = 0.0; rs1[k] = 0.0; rc1[k] = 0.0; }
+  if (rows_fast) {
+#pragma unroll
+    for (int k = 0; k < DM; ++k)
+      if (k < a.d) {
+        const double sk = a.ils ? a.ils[k] : a.inv_ls;
+        per_sincos(rsrc[(size_t)(i0 - rbase) * a.d + k] * sk, rs0[k], rc0[k]);
+        per_sincos(rsrc[(size_t)(i0 + 1 - rbase) * a.d + k] * sk, rs1[k], rc1[k]);
+      }
+  }
+  const double hq = -0.5 * a.alpha;                           // -1 / (2 rho^2)
+  for (int c4 = 0; c4 < a.cpw; ++c4) {
+    const int tj = sy * a.cpw + c4;
+    if (tj * 64 >= a.ncols) break;
+    if (!a.full && ti < tj) break;                            // lower tiles only
+    if (!(rows_fast && tj * 64 + 63 < a.n)) { gram_tile_generic<LMM_KERNEL_PERIODIC, TS>(a, ti, tj); continue; }
+    const size_t out = (size_t)(tj * 64 + cg) * a.ld + (i0 - a.row_shift);
+    __syncthreads();                                          // previous tile's readers are done with colS / colC
+    for (int e = t; e < 64 * a.d; e += 256) {
+      const double sk = a.ils ? a.ils[ND ? e % a.d : 0] : a.inv_ls;
+      per_sincos(a.x[(size_t)tj * 64 * a.d + e] * sk, colS[e], colC[e]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int jl = cg + 8 * q;
+      double q0 = 0.0, q1 = 0.0;
+#pragma unroll
+      for (int k = 0; k < DM; ++k)
+        if (k < a.d) {
+          const double cs = colS[jl * a.d + k], cc = colC[jl * a.d + k];
+          const double s0 = __builtin_fma(rs0[k], cc, -rc0[k] * cs), s1 = __builtin_fma(rs1[k], cc, -rc1[k] * cs);
+          q0 = __builtin_fma(s0, s0, q0); q1 = __builtin_fma(s1, s1, q1);
+        }
+      d2 v;
+      v.x = a.var * exp_nonpos(hq * q0);
+      v.y = a.var * exp_nonpos(hq * q1);
+      if (ti == tj) {
+        const int j = tj * 64 + jl;
+        const double da = a.diag_add + (a.diag_vec ? a.diag_vec[j] : 0.0);
+        if (i0 == j) v.x += da;
+        if (i0 + 1 == j) v.y += da;
+      }
+      gram_store<TS>(a.A, out + (size_t)(8 * q) * a.ld, v);
+    }
   }
 }
 
 template <int KIND, bool ND, typename TS>
 __global__ __launch_bounds__(256) void gram_kernel(GramArgs a) {
   if (a.info_zero && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.info_zero = 0;
-  if constexpr (KIND == LMM_KERNEL_SUM) gram_body_sum<TS>(a);
+  if constexpr (KIND == LMM_KERNEL_SUM || KIND == LMM_KERNEL_SUM_PER) gram_body_sum<KIND, TS>(a);
+  else if constexpr (KIND == LMM_KERNEL_PERIODIC) gram_body_per<ND, TS>(a);
   else gram_body<KIND, ND, TS>(a);
 }
 
@@ -472,9 +571,11 @@ __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
   const int z = blockIdx.z;
   a.A = b.A[z]; a.var = b.var[z]; a.inv_ls = b.inv_ls[z]; a.ils = b.ils[z]; a.alpha = b.alpha[z]; a.diag_add = b.diag_add[z]; a.diag_vec = b.diag_vec[z]; a.rider = b.rider[z]; a.rider_sub = b.rider_sub[z];
   if (b.info_zero[z] && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *b.info_zero[z] = 0;
-  if constexpr (KIND == LMM_KERNEL_SUM) {
+  if constexpr (KIND == LMM_KERNEL_SUM || KIND == LMM_KERNEL_SUM_PER) {
     a.terms = b.terms[z]; a.nterms = b.nterms[z];
-    gram_body_sum<TS>(a);
+    gram_body_sum<KIND, TS>(a);
+  } else if constexpr (KIND == LMM_KERNEL_PERIODIC) {
+    gram_body_per<ND, TS>(a);
   } else {
     gram_body<KIND, ND, TS>(a);
   }
@@ -484,7 +585,8 @@ __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
 // element (i, j), i = li*n + ii, j = lj*n + jj  ->  [li == lj] kappa_li(x_ii, x_jj) + [ii == jj] SigmaT[li, lj].
 // Reference: src/ilmm.jl:160 kron(SigmaT, I) + src/independent_mogp.jl:60-63 BlockDiagonal.  A sum latent (LatentDev.terms) takes kappa_sum here and
 // in dense_cross_kernel; its var is kappa(0) = v0 sum_c v_c in these arrays (dense_var_kernel reads it).
-template <typename TS, bool SUM>      // SUM: some latent is a sum (SUM = false keeps the code and registers the kernel always had)
+// SUM = 1: some latent is a sum; 2: some latent is periodic or has a periodic term (0 and 1 keep the code and registers they always had)
+template <typename TS, int SUM>
 __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
   const int ti = blockIdx.x, tj = blockIdx.y;
   if (ti < tj) return;
@@ -511,8 +613,10 @@ __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
         if (i < N) {
           if (li[e] == lj) {
             const LatentDev g = a.lat[lj];
-            if (SUM && g.kind == LMM_KERNEL_SUM) {
-              val = kappa_sum(g.terms, g.nterms, a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d);
+            if (SUM == 2 && g.kind == LMM_KERNEL_PERIODIC) {
+              val = kappa_per(g.var, g.alpha, per_q(a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d, g.inv_ls, g.ils));
+            } else if (SUM && g.kind == LMM_KERNEL_SUM) {
+              val = kappa_sum<SUM == 2>(g.terms, g.nterms, a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d);
             } else {
               double r, r2;
               if (a.d == 1) { r = fabs(a.x[ii[e]] - a.x[jj]) * g.inv_ls; r2 = r * r; }
@@ -535,7 +639,7 @@ __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
 
 // Dense-ILMM cross-covariance riders: row (l, s) of R (m*ns rows) is K_l(xs_s, x) placed in the column block of
 // latent l (reference src/independent_mogp.jl:66-71: block-diagonal cov(f, x, y)); zero elsewhere and in the pad.
-template <typename TS, bool SUM>
+template <typename TS, int SUM>
 __global__ __launch_bounds__(256) void dense_cross_kernel(void* __restrict__ R, int ldr, int nrows, int /*ncols*/,
                                                           const double* __restrict__ xs, int ns,
                                                           const double* __restrict__ x, int n, int d, int m,
@@ -549,8 +653,10 @@ __global__ __launch_bounds__(256) void dense_cross_kernel(void* __restrict__ R, 
     const int lj = j / n, jj = j - lj * n;
     if (lj == l) {
       const LatentDev g = lat[l];
-      if (SUM && g.kind == LMM_KERNEL_SUM) {
-        val = kappa_sum(g.terms, g.nterms, xs + (size_t)s * d, x + (size_t)jj * d, d);
+      if (SUM == 2 && g.kind == LMM_KERNEL_PERIODIC) {
+        val = kappa_per(g.var, g.alpha, per_q(xs + (size_t)s * d, x + (size_t)jj * d, d, g.inv_ls, g.ils));
+      } else if (SUM && g.kind == LMM_KERNEL_SUM) {
+        val = kappa_sum<SUM == 2>(g.terms, g.nterms, xs + (size_t)s * d, x + (size_t)jj * d, d);
       } else {
         double rr, r2;
         if (d == 1) { rr = fabs(xs[s] - x[jj]) * g.inv_ls; r2 = rr * rr; }
@@ -3261,9 +3367,9 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restr
 // ---------------------------------------------------------------------------------------------------
 // Latent mean at xs from the weights:  mean[s] = mu + sum_i kappa(xs_s, x_i) alpha_i   (cross-Gram fused with the GEMV;
 // never materialised).  The i range is cut into chunks of ichunk (blockIdx.y) whose partial sums strip_finish_kernel adds.
-// EXT: a Matern12 / RQ latent (the three original kinds keep the instantiation they always had).
+// EXT = 1: a Matern12 / RQ latent, 2: a periodic latent (the three original kinds keep the instantiation they always had).
 // ---------------------------------------------------------------------------------------------------
-template <bool EXT>
+template <int EXT>
 __global__ __launch_bounds__(256) void post_mean_kernel(const double* __restrict__ xs, int ns,
                                                         const double* __restrict__ x, int n, int d, int ichunk,
                                                         const double* __restrict__ alpha, LatentDev g,
@@ -3284,12 +3390,21 @@ __global__ __launch_bounds__(256) void post_mean_kernel(const double* __restrict
       const int lim = (iend - i0 < 256) ? (iend - i0) : 256;
 #pragma unroll 4
       for (int k = 0; k < lim; ++k) {
+        if constexpr (EXT == 2) {
+          const double sn = sinpi((xv - xa[k]) * g.inv_ls);
+          acc = __builtin_fma(kappa_per(g.var, g.alpha, sn * sn), xa[256 + k], acc);
+          continue;
+        }
         const double r = fabs(xv - xa[k]) * g.inv_ls;
         acc = __builtin_fma(EXT ? kappa(g.kind, g.var, r, r * r, g.alpha) : kappa(g.kind, g.var, r, r * r), xa[256 + k], acc);
       }
     }
   } else if (s < ns) {
     for (int i = ibeg; i < iend; ++i) {
+      if constexpr (EXT == 2) {
+        acc = __builtin_fma(kappa_per(g.var, g.alpha, per_q(xs + (size_t)s * d, x + (size_t)i * d, d, g.inv_ls, g.ils)), alpha[i], acc);
+        continue;
+      }
       const double r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)i * d, d, g.inv_ls, g.ils);
       const double rr = sqrt(r2);
       acc = __builtin_fma(EXT ? kappa(g.kind, g.var, rr, r2, g.alpha) : kappa(g.kind, g.var, rr, r2), alpha[i], acc);
@@ -3476,6 +3591,15 @@ __device__ __forceinline__ void rq_pair(double var, double alpha, double r2, dou
   h = kap * q;
   dal = kap * (u * q - lg);
 }
+// Periodic pairs (EXT = 2 below).  With t_k = (x_ik - x_jk) / P_k (unreduced), (s_k, c_k) = sincospi(t_k), q = sum_k s_k^2 and
+// kap = v exp(-q / (2 rho^2)):
+//     d kap / d P_k = kap p_k / P_k,  p_k = pi t_k sin(2 pi t_k) / (2 rho^2) = (pi / rho^2) t_k s_k c_k;   d kap / d multiplier = kap sum_k p_k / multiplier;
+//     d kap / d x_ik = -kap u_k / P_k,  u_k = pi sin(2 pi t_k) / (2 rho^2) = (pi / rho^2) s_k c_k;          d kap / d rho = kap q / rho^3.
+// The kernels are bound by the read of Kinv, so sincospi is called per pair and dimension.  The rho sum takes the partial slot alpha
+// takes for RQ ([8]); g.alpha holds 1 / rho^2.
+#define LMM_PI 3.141592653589793
+__device__ __forceinline__ double per_rho3(double irho2) { return irho2 * sqrt(irho2); }     // 1 / rho^3
+
 // kappa, d kappa / d ell and (RQ) d kappa / d alpha of a Matern12 or RQ pair
 __device__ __forceinline__ void ext_pair(const LatentDev& g, double r, double r2, double& kap, double& dell, double& dal) {
   if (g.kind == LMM_KERNEL_RQ) {
@@ -3499,8 +3623,8 @@ __device__ __forceinline__ void ext_pair(const LatentDev& g, double r, double r2
 // The split at nsplit serves the predictive logpdf (joint of training and test points, each block with its own noise).
 #define LMM_NG 9
 // TS: storage type of the inverse Kinv (a MATRIX: Float32 in the fp32 compute mode); all sums in Float64.  EXT: a Matern12 / RQ latent
-// (the three original kinds keep the instantiation, and the register budget, they always had).
-template <typename TS, bool EXT>
+// (the three original kinds keep the instantiation, and the register budget, they always had); EXT = 2: a periodic latent.
+template <typename TS, int EXT>
 __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict__ Kinv, int ld, int n, int nsplit,
                                                           const double* __restrict__ alpha, const double* __restrict__ delta,
                                                           const double* __restrict__ x, int d, LatentDev g, int nt,
@@ -3517,6 +3641,22 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
     for (int q = 0; q < 16; ++q) {
       const int j = tj * 64 + cg + 4 * q;
       if (j < i0 && j < n) {
+        if constexpr (EXT == 2) {
+          double qq = 0.0, pp = 0.0;
+          for (int k = 0; k < d; ++k) {
+            const double tk = (x[(size_t)i0 * d + k] - x[(size_t)j * d + k]) * g.inv_ls;
+            double sn, cs;
+            sincospi(tk, &sn, &cs);
+            qq = __builtin_fma(sn, sn, qq);
+            pp = __builtin_fma(tk, sn * cs, pp);
+          }
+          const double w = ai * alpha[j] - MatIO<TS>::ld1(Kinv, (size_t)j * ld + i0);
+          const double wk = w * kappa_per(g.var, g.alpha, qq);
+          acc = __builtin_fma(wk, pp, acc);
+          acck += wk;
+          acca = __builtin_fma(wk, qq, acca);
+          continue;
+        }
         double r, r2;
         if (d == 1) { r = fabs(x[i0] - x[j]) * g.inv_ls; r2 = r * r; }
         else { r2 = scaled_dist2(x + (size_t)i0 * d, x + (size_t)j * d, d, g.inv_ls, nullptr); r = sqrt(r2); }
@@ -3535,9 +3675,10 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
     }
   }
   const int tile = ti * nt + tj;
+  if (EXT == 2) { acc *= LMM_PI * g.alpha * g.inv_ls; acca *= per_rho3(g.alpha); }
   const double tl = block_sum_256(acc, sh);
   const double tk = block_sum_256(acck, sh);
-  const double ta = (EXT && g.kind == LMM_KERNEL_RQ) ? block_sum_256(acca, sh) : 0.0;     // (g.kind is uniform: the barrier is too)
+  const double ta = (EXT == 2 || (EXT && g.kind == LMM_KERNEL_RQ)) ? block_sum_256(acca, sh) : 0.0;     // (g.kind is uniform: the barrier is too)
   double tra = 0.0, aaa = 0.0, trb = 0.0, aab = 0.0, ad = 0.0, sa = 0.0;
   if (ti == tj && t < 64 && i0 < n) {
     const double ai = alpha[i0], kii = MatIO<TS>::ld1(Kinv, (size_t)i0 * ld + i0);
@@ -3560,10 +3701,17 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
 // The tile partials hold LMM_NG + d entries: the LMM_NG of grad_reduce_kernel ([0] = d/d multiplier) followed by the d sums
 // sum_{i>j in tile} w_ij d kappa_ij / d l_k.  Kinv is read once per tile, as in the isotropic kernel; the d extra FMAs per pair (and,
 // for DK <= 8, the t_k^2 kept in registers) leave the kernel bound by that read.  All sums of a tile are reduced with ONE barrier.
-template <int DK, bool EXT>
+// EXT = 2 (periodic): r2 is q and alpha 1 / rho^2;  wh = w kap, acca += w kap q, and acc0 is left to the caller (sum_k wh p_k).
+template <int DK, int EXT>
 __device__ __forceinline__ void ard_pair(int kind, double var, double alpha, double r2, double w, double& acc0, double& acck,
                                          double& acca, double& wh) {
   double e, kap, h;
+  if constexpr (EXT == 2) {
+    wh = w * kappa_per(var, alpha, r2);
+    acck += wh;
+    acca = __builtin_fma(wh, r2, acca);
+    return;
+  }
   if (EXT) {
     if (kind == LMM_KERNEL_RQ) {
       double dal;
@@ -3590,7 +3738,7 @@ __device__ __forceinline__ void ard_pair(int kind, double var, double alpha, dou
   acck = __builtin_fma(w, kap, acck);
 }
 
-template <typename TS, int DK, bool EXT>
+template <typename TS, int DK, int EXT>
 __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __restrict__ Kinv, int ld, int n, int nsplit,
                                                               const double* __restrict__ alpha, const double* __restrict__ delta,
                                                               const double* __restrict__ x, int d, LatentDev g, int nt,
@@ -3623,8 +3771,15 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
         for (int k = 0; k < DK; ++k)
           if (k < d) {
             const double tk = xi[k] - xj[k] * sils[k];
-            if (KEEP) t2[k] = tk * tk;
-            r2 = __builtin_fma(tk, tk, r2);
+            if constexpr (EXT == 2) {              // t2[k] <- t_k s_k c_k (p_k without its constant), r2 <- q
+              double sn, cs;
+              sincospi(tk, &sn, &cs);
+              if (KEEP) t2[k] = tk * (sn * cs);
+              r2 = __builtin_fma(sn, sn, r2);
+            } else {
+              if (KEEP) t2[k] = tk * tk;
+              r2 = __builtin_fma(tk, tk, r2);
+            }
           }
         const double w = ai * alpha[j] - MatIO<TS>::ld1(Kinv, (size_t)j * ld + i0);
         double wh;
@@ -3634,8 +3789,13 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
           if (k < d) {
             double tk2;
             if (KEEP) tk2 = t2[k];
-            else { const double tk = xi[k] - xj[k] * sils[k]; tk2 = tk * tk; }
+            else {
+              const double tk = xi[k] - xj[k] * sils[k];
+              if constexpr (EXT == 2) { double sn, cs; sincospi(tk, &sn, &cs); tk2 = tk * (sn * cs); }
+              else tk2 = tk * tk;
+            }
             acc[k] = __builtin_fma(wh, tk2, acc[k]);
+            if constexpr (EXT == 2) acc0 = __builtin_fma(wh, tk2, acc0);
           }
       }
     }
@@ -3651,6 +3811,12 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
   v[0] = acc0 * g.inv_ls; v[1] = tra; v[2] = aaa; v[3] = ad; v[4] = sa; v[5] = trb; v[6] = aab; v[7] = acck; v[8] = acca;
 #pragma unroll
   for (int k = 0; k < DK; ++k) v[LMM_NG + k] = acc[k] * sils[k];
+  if constexpr (EXT == 2) {
+    const double pc = LMM_PI * g.alpha;
+    v[0] *= pc; v[8] *= per_rho3(g.alpha);
+#pragma unroll
+    for (int k = 0; k < DK; ++k) v[LMM_NG + k] *= pc;
+  }
 #pragma unroll
   for (int c = 0; c < NV; ++c) {
     const double sc = wave_sum(v[c]);
@@ -3688,7 +3854,7 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restri
 // fixed order, and partial[(c n + i) d + k] holds the chunk's value (grad_x_finish_kernel sums the chunks in order).  l_k = 1 / g.ils[k]
 // (ARD) or 1 / g.inv_ls; x and gx are d x n column-major.  DK >= d; DK = 1 is the d = 1 path.
 #define LMM_GX_CHUNK 16
-template <typename TS, int DK, bool EXT>
+template <typename TS, int DK, int EXT>
 __global__ __launch_bounds__(256) void grad_x_kernel(const void* __restrict__ Kinv, int ld, int n, const double* __restrict__ alpha,
                                                      const double* __restrict__ x, int d, LatentDev g, double* __restrict__ partial) {
   __shared__ double sils[DK];
@@ -3726,6 +3892,12 @@ __global__ __launch_bounds__(256) void grad_x_kernel(const void* __restrict__ Ki
 #pragma unroll
         for (int k = 0; k < DK; ++k) {
           tk[k] = (k < d) ? (xi[k] - xj[k]) * sils[k] : 0.0;     // difference first: exactly 0 at coincident points
+          if constexpr (EXT == 2) {                              // tk[k] <- u_k, r2 <- q
+            double sn, cs;
+            sincospi(tk[k], &sn, &cs);
+            tk[k] = (LMM_PI * g.alpha) * (sn * cs);
+            r2 = __builtin_fma(sn, sn, r2);
+          } else
           r2 = __builtin_fma(tk[k], tk[k], r2);
         }
         const double w = ai * alpha[j] - kij;
@@ -3889,7 +4061,7 @@ __global__ __launch_bounds__(256, 2) void trsm_nn_kernel(BatchPtr Cb, size_t gof
 // workgroup (sb, c) takes 256 test points against the training points [c chunk, (c + 1) chunk), staged in LDS (JS at a time).  VAR =
 // false: the mean-only form (no W).  No atomics: partial[(c ns + s) d + k] holds the chunk's sum, grad_x_finish_kernel adds the
 // chunks in order.  Matern12 pairs at coincident points contribute 0 (ard_pair's h = 0; t_k is formed difference first).
-template <int DK, bool EXT, bool VAR>
+template <int DK, int EXT, bool VAR>
 __global__ __launch_bounds__(256) void pred_grad_x_kernel(const double* __restrict__ xs, int ns, const double* __restrict__ x, int n,
                                                           int d, int chunk, const double* __restrict__ alpha,
                                                           const double* __restrict__ mbar, const double* __restrict__ vbar,
@@ -3923,6 +4095,12 @@ __global__ __launch_bounds__(256) void pred_grad_x_kernel(const double* __restri
 #pragma unroll
       for (int k = 0; k < DK; ++k) {
         tk[k] = (k < d) ? (xv[k] - sx[jl * DK + k]) * sils[k] : 0.0;     // difference first: exactly 0 at coincident points
+        if constexpr (EXT == 2) {                                        // tk[k] <- u_k, r2 <- q
+          double sn, cs;
+          sincospi(tk[k], &sn, &cs);
+          tk[k] = (LMM_PI * g.alpha) * (sn * cs);
+          r2 = __builtin_fma(sn, sn, r2);
+        } else
         r2 = __builtin_fma(tk[k], tk[k], r2);
       }
       const double w = VAR ? __builtin_fma(vb2, wp[(size_t)jl * ldw], mb * sa[jl]) : mb * sa[jl];
@@ -4086,11 +4264,13 @@ void launch_gram(const GramArgs& a0, hipStream_t st) {
     if (nd) LMM_TS_LAUNCH((gram_kernel<K, true, TS>), grid, dim3(256), 0, st, a);                   \
     else LMM_TS_LAUNCH((gram_kernel<K, false, TS>), grid, dim3(256), 0, st, a);                     \
   } while (0)
-  if (a.kind == LMM_KERNEL_SUM) LMM_TS_LAUNCH((gram_kernel<LMM_KERNEL_SUM, false, TS>), grid, dim3(256), 0, st, a);
+  if (a.kind == LMM_KERNEL_SUM && a.sum_per) LMM_TS_LAUNCH((gram_kernel<LMM_KERNEL_SUM_PER, false, TS>), grid, dim3(256), 0, st, a);
+  else if (a.kind == LMM_KERNEL_SUM) LMM_TS_LAUNCH((gram_kernel<LMM_KERNEL_SUM, false, TS>), grid, dim3(256), 0, st, a);
   else if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
   else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
   else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
   else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
+  else if (a.kind == LMM_KERNEL_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_PERIODIC);
   else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
 #undef LMM_GRAM_LAUNCH
 }
@@ -4109,6 +4289,7 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
       b.terms[j - j0] = a.terms; b.nterms[j - j0] = a.nterms;
       b.diag_vec[j - j0] = a.diag_vec; b.rider[j - j0] = a.rider; b.rider_sub[j - j0] = a.rider_sub; b.info_zero[j - j0] = a.info_zero;
     }
+    for (int j = j0; j < j1; ++j) b.base.sum_per |= args[j].sum_per;       // one sum of the run has a periodic term: that instantiation for all
     b.base.cpw = gram_cpw(b.base.nrows / 64 - b.base.row_tile0, b.base.ncols / 64, j1 - j0);
     const GramArgs& a = b.base;
     dim3 grid(a.nrows / 64 - a.row_tile0, (a.ncols / 64 + a.cpw - 1) / a.cpw, j1 - j0);
@@ -4118,11 +4299,13 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
       if (nd) LMM_TS_LAUNCH((gram_batch_kernel<K, true, TS>), grid, dim3(256), 0, st, b);           \
       else LMM_TS_LAUNCH((gram_batch_kernel<K, false, TS>), grid, dim3(256), 0, st, b);             \
     } while (0)
-    if (a.kind == LMM_KERNEL_SUM) LMM_TS_LAUNCH((gram_batch_kernel<LMM_KERNEL_SUM, false, TS>), grid, dim3(256), 0, st, b);
+    if (a.kind == LMM_KERNEL_SUM && a.sum_per) LMM_TS_LAUNCH((gram_batch_kernel<LMM_KERNEL_SUM_PER, false, TS>), grid, dim3(256), 0, st, b);
+    else if (a.kind == LMM_KERNEL_SUM) LMM_TS_LAUNCH((gram_batch_kernel<LMM_KERNEL_SUM, false, TS>), grid, dim3(256), 0, st, b);
     else if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
     else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
     else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
     else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
+    else if (a.kind == LMM_KERNEL_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_PERIODIC);
     else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
 #undef LMM_GRAM_LAUNCH
     j0 = j1;
@@ -4130,10 +4313,11 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
 }
 
 void launch_dense_cross(double* R, int ldr, int nrows, int ncols, const double* xs, int ns, const double* x, int n, int d,
-                        int m, const LatentDev* lat, bool has_sum, hipStream_t st) {
+                        int m, const LatentDev* lat, int has_sum, hipStream_t st) {
   dim3 grid((nrows + 255) / 256, ncols);
-  if (has_sum) LMM_TS_LAUNCH((dense_cross_kernel<TS, true>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
-  else LMM_TS_LAUNCH((dense_cross_kernel<TS, false>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
+  if (has_sum == 2) LMM_TS_LAUNCH((dense_cross_kernel<TS, 2>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
+  else if (has_sum) LMM_TS_LAUNCH((dense_cross_kernel<TS, 1>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
+  else LMM_TS_LAUNCH((dense_cross_kernel<TS, 0>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
 }
 
 int dense_var_kc(int Ncols) { int kc = ((Ncols + 127) / 128 + 63) / 64 * 64; return kc < 64 ? 64 : kc; }   // <= 128 chunks
@@ -4160,8 +4344,9 @@ void launch_dense_cov(const double* S, int lds, int ns, int m, const double* Hm,
 
 void launch_dense_assemble(const DenseArgs& a, hipStream_t st) {
   dim3 grid(a.nrows / 64, a.ncols / 64);
-  if (a.has_sum) LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, true>), grid, dim3(256), 0, st, a);
-  else LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, false>), grid, dim3(256), 0, st, a);      // fp32 compute mode: Float32 matrix (the dense logpdf paths)
+  if (a.has_sum == 2) LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, 2>), grid, dim3(256), 0, st, a);
+  else if (a.has_sum) LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, 1>), grid, dim3(256), 0, st, a);
+  else LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, 0>), grid, dim3(256), 0, st, a);      // fp32 compute mode: Float32 matrix (the dense logpdf paths)
 }
 
 // ---- round 3: 128-column panels (leaf128 / bulk) and the update fused with the next panel's leaf (K2c) ----
@@ -4655,8 +4840,9 @@ void launch_post_mean(const double* xs, int ns, const double* x, int n, int d, c
     return;
   }
   const int ic = post_mean_ichunk(n), nch = (n + ic - 1) / ic, nsp = (ns + 255) / 256 * 256;
-  if (g.kind >= LMM_KERNEL_MATERN12) hipLaunchKernelGGL(post_mean_kernel<true>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
-  else hipLaunchKernelGGL(post_mean_kernel<false>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  if (g.kind == LMM_KERNEL_PERIODIC) hipLaunchKernelGGL(post_mean_kernel<2>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  else if (g.kind >= LMM_KERNEL_MATERN12) hipLaunchKernelGGL(post_mean_kernel<1>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  else hipLaunchKernelGGL(post_mean_kernel<0>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
   hipLaunchKernelGGL(strip_finish_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, partial, nsp, nch, 1, ns, 0, g.mean, 0.0,
                      out, (double*)nullptr);
 }
@@ -4701,12 +4887,13 @@ int grad_partials(int n, int d_ard) { const int nt = (n + 63) / 64; return (LMM_
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,
                         LatentDev g, double* partial, double* out7, hipStream_t st, double* out_ard) {
   const int nt = (n + 63) / 64;
-  const bool ext = g.kind >= LMM_KERNEL_MATERN12;      // Matern12 / RQ: the EXT instantiations
+  const int ext = g.kind == LMM_KERNEL_PERIODIC ? 2 : (g.kind >= LMM_KERNEL_MATERN12 ? 1 : 0);      // Matern12 / RQ, periodic: the EXT instantiations
   if (g.ils != nullptr) {          // ARD latent (the caller guarantees 1 < d <= LMM_ARD_GRAD_DMAX and out_ard != nullptr)
 #define LMM_ARD_LAUNCH(DK)                                                                                                      \
     do {                                                                                                                        \
-      if (ext) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, true>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
-      else LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, false>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
+      if (ext == 2) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 2>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
+      else if (ext) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 1>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
+      else LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 0>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
     } while (0)
     if (d <= 4) LMM_ARD_LAUNCH(4);
     else if (d <= 8) LMM_ARD_LAUNCH(8);
@@ -4715,8 +4902,9 @@ void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const dou
     hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG + d, out_ard);
     return;
   }
-  if (ext) LMM_TS_LAUNCH((grad_reduce_kernel<TS, true>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
-  else LMM_TS_LAUNCH((grad_reduce_kernel<TS, false>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  if (ext == 2) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 2>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  else if (ext) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 1>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  else LMM_TS_LAUNCH((grad_reduce_kernel<TS, 0>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
   hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG, (double*)nullptr);
 }
 
@@ -4725,11 +4913,12 @@ size_t grad_x_partial_elems(int n, int d) { const int nt = (n + 63) / 64; return
 void launch_grad_x(const double* Kinv, int ld, int n, const double* alpha, const double* x, int d, LatentDev g, double* partial,
                    double* gx, bool accumulate, hipStream_t st) {
   const int nt = (n + 63) / 64, nch = (nt + LMM_GX_CHUNK - 1) / LMM_GX_CHUNK;
-  const bool ext = g.kind >= LMM_KERNEL_MATERN12;
+  const int ext = g.kind == LMM_KERNEL_PERIODIC ? 2 : (g.kind >= LMM_KERNEL_MATERN12 ? 1 : 0);
 #define LMM_GX_LAUNCH(DK)                                                                                                      \
   do {                                                                                                                        \
-    if (ext) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, true>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
-    else LMM_TS_LAUNCH((grad_x_kernel<TS, DK, false>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
+    if (ext == 2) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 2>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
+    else if (ext) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 1>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
+    else LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 0>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
   } while (0)
   if (d == 1) LMM_GX_LAUNCH(1);
   else if (d <= 4) LMM_GX_LAUNCH(4);
@@ -4810,7 +4999,8 @@ void launch_pred_grad_x(const double* xs, int ns, const double* x, int n, int d,
                         const double* vbar, const double* W, int ldw, LatentDev g, double* partial, double* gx, bool accumulate,
                         hipStream_t st) {
   const int chunk = pred_grad_chunk(n), nch = (n + chunk - 1) / chunk;
-  const bool ext = g.kind >= LMM_KERNEL_MATERN12, var = W != nullptr;
+  const int ext = g.kind == LMM_KERNEL_PERIODIC ? 2 : (g.kind >= LMM_KERNEL_MATERN12 ? 1 : 0);
+  const bool var = W != nullptr;
   const dim3 grid((ns + 255) / 256, nch);
 #define LMM_PGX_LAUNCH(DK, EXT)                                                                                                   \
   do {                                                                                                                            \
@@ -4819,7 +5009,7 @@ void launch_pred_grad_x(const double* xs, int ns, const double* x, int n, int d,
     else hipLaunchKernelGGL((pred_grad_x_kernel<DK, EXT, false>), grid, dim3(256), 0, st, xs, ns, x, n, d, chunk, alpha, mbar,    \
                             vbar, W, ldw, g, partial);                                                                            \
   } while (0)
-#define LMM_PGX_DK(DK) do { if (ext) LMM_PGX_LAUNCH(DK, true); else LMM_PGX_LAUNCH(DK, false); } while (0)
+#define LMM_PGX_DK(DK) do { if (ext == 2) LMM_PGX_LAUNCH(DK, 2); else if (ext) LMM_PGX_LAUNCH(DK, 1); else LMM_PGX_LAUNCH(DK, 0); } while (0)
   if (d == 1) LMM_PGX_DK(1);
   else if (d <= 4) LMM_PGX_DK(4);
   else if (d <= 8) LMM_PGX_DK(8);

@@ -95,6 +95,9 @@ _euclidean(k) = nameof(typeof(k.metric)) === :Euclidean ||
     error("LinearMixingModelsHIP: $(nameof(typeof(k))) with metric $(k.metric) is not served (Euclidean only)")
 _kind(k::ExponentialKernel) = (_euclidean(k); Cint(3))
 _kind(k::RationalQuadraticKernel) = (_euclidean(k); Cint(4))
+# PeriodicKernel(; r): v exp(-sum_k sin^2(pi (x_k - x'_k)) / (2 r^2)) under a ScaleTransform(1 / P) or ARDTransform(1 ./ P): the
+# lengthscale slot (and the ARD factors) carry the period(s).  The library takes ONE rho for all dimensions: r = fill(rho, d).
+_kind(k::PeriodicKernel) = Cint(7)
 _desc(k::Kernel) = (_kind(k), 1.0, 1.0)
 _desc(k::ScaledKernel) = ((kd, v, l) = _desc(k.kernel); (kd, v * only(k.σ²), l))
 _desc(k::TransformedKernel{<:Kernel,<:ScaleTransform}) = ((kd, v, l) = _desc(k.kernel); (kd, v, l / only(k.transform.s)))
@@ -113,6 +116,15 @@ _alpha(k::Kernel) = nothing
 _alpha(k::RationalQuadraticKernel) = Float64(only(k.α))
 _alpha(k::ScaledKernel) = _alpha(k.kernel)
 _alpha(k::TransformedKernel) = _alpha(k.kernel)
+# a periodic kernel's rho (it travels in the latent's tag, lmm_kernel_tag_create_periodic); nothing for the other kernels
+_rho(k::Kernel) = nothing
+function _rho(k::PeriodicKernel)
+    r = k.r
+    all(==(first(r)), r) || error("LinearMixingModelsHIP: PeriodicKernel with unequal entries of r is not served (r = fill(rho, d) only)")
+    return Float64(first(r))
+end
+_rho(k::ScaledKernel) = _rho(k.kernel)
+_rho(k::TransformedKernel) = _rho(k.kernel)
 # Sum kernels (KernelFunctions' KernelSum, k1 + k2): kind 5 with a sum tag (lmm_kernel_sum_create).  `_desc` of the sum is (5, 1, 1), so
 # a ScaledKernel / ScaleTransform around it gives the latent's outer variance v0 and lengthscale s0; each term is read with the
 # single-kernel methods above.  A nested sum with unit outer variance and lengthscale is flattened; any other is rejected, as is an
@@ -148,13 +160,18 @@ struct KTag
     id::Cint
     ard::Bool      # the tag holds per-dimension factors
     alpha::Bool    # the tag holds an RQ shape
+    rho::Bool      # the tag holds a periodic kernel's rho (its gradient travels in the `alpha` field of the gradient tuples)
     terms::Vector{KTag}   # a sum tag: its terms' tags (empty otherwise)
 end
-KTag(id, ard, alpha) = KTag(id, ard, alpha, KTag[])
+KTag(id, ard, alpha, rho::Bool=false) = KTag(id, ard, alpha, rho, KTag[])
 # the factor / alpha tag of one kernel (a latent's or a sum term's); 0: none needed
-function _ktag(a, α)
+function _ktag(a, α, ρ=nothing)
     tr = Ref{Cint}(0)
-    if a !== nothing && α === nothing
+    if ρ !== nothing
+        av = a === nothing ? Float64[] : a
+        GC.@preserve av check(ccall((:lmm_kernel_tag_create_periodic, liblmm), Cint, (Cint, Ptr{Cdouble}, Cdouble, Ref{Cint}),
+                                    length(av), a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(av), ρ, tr))
+    elseif a !== nothing && α === nothing
         GC.@preserve a check(ccall((:lmm_ard_create, liblmm), Cint, (Cint, Ptr{Cdouble}, Ref{Cint}), length(a), a, tr))
     elseif α !== nothing
         av = a === nothing ? Float64[] : a
@@ -174,23 +191,23 @@ function _gps(body, fs)
             (kd, v, l) = _desc(f.kernel)
             if kd == 5
                 tts = KTag[]; tgps = LmmGp[]
-                push!(tags, KTag(Cint(0), false, false, tts))    # registered first, so that the finally destroys the term tags on error
+                push!(tags, KTag(Cint(0), false, false, false, tts))    # registered first, so that the finally destroys the term tags on error
                 for k in _terms(f.kernel)
-                    (tk, tv, tl) = _desc(k); a = _ard(k); α = _alpha(k)
-                    t = _ktag(a, α)
-                    push!(tts, KTag(t, a !== nothing, α !== nothing))
+                    (tk, tv, tl) = _desc(k); a = _ard(k); α = _alpha(k); ρ = _rho(k)
+                    t = _ktag(a, α, ρ)
+                    push!(tts, KTag(t, a !== nothing, α !== nothing, ρ !== nothing))
                     push!(tgps, LmmGp(t == 0 ? tk : tk | (t << 8), tv, tl, 0.0))
                 end
                 tr = Ref{Cint}(0)
                 GC.@preserve tgps check(ccall((:lmm_kernel_sum_create, liblmm), Cint, (Cint, Ptr{LmmGp}, Ref{Cint}),
                                               length(tgps), pointer(tgps), tr))
-                tags[end] = KTag(tr[], false, false, tts)
+                tags[end] = KTag(tr[], false, false, false, tts)
                 push!(gps, LmmGp(kd | (tr[] << 8), v, l, _mean(f.mean)))
                 continue
             end
-            a = _ard(f.kernel); α = _alpha(f.kernel)
-            t = _ktag(a, α)
-            push!(tags, KTag(t, a !== nothing, α !== nothing))
+            a = _ard(f.kernel); α = _alpha(f.kernel); ρ = _rho(f.kernel)
+            t = _ktag(a, α, ρ)
+            push!(tags, KTag(t, a !== nothing, α !== nothing, ρ !== nothing))
             push!(gps, LmmGp(t == 0 ? kd : kd | (t << 8), v, l, _mean(f.mean)))
         end
         return body(gps, tags)
@@ -199,7 +216,7 @@ function _gps(body, fs)
     end
 end
 # after a gradient call inside _gps, per latent: nothing (no tag) or (ard = d logpdf / d ard[k] (lmm_ard_grad) or nothing,
-# alpha = d logpdf / d alpha (lmm_kernel_tag_alpha_grad) or nothing)
+# alpha = d logpdf / d alpha (lmm_kernel_tag_alpha_grad), of a periodic latent d logpdf / d rho (lmm_kernel_tag_rho_grad), or nothing)
 # A sum latent: (ard = nothing, alpha = nothing, terms = per term (variance, lengthscale, ard, alpha) from lmm_kernel_sum_grad and
 # the terms' own tags).
 function _tag_grads(t::KTag, d::Integer)
@@ -217,7 +234,9 @@ function _tag_grads(t::KTag, d::Integer)
     return (ard = t.ard ? (g = Vector{Float64}(undef, d);
                            GC.@preserve g check(ccall((:lmm_ard_grad, liblmm), Cint, (Cint, Ptr{Cdouble}), t.id, g)); g) : nothing,
             alpha = t.alpha ? (r = Ref{Cdouble}(0.0);
-                               check(ccall((:lmm_kernel_tag_alpha_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) : nothing,
+                               check(ccall((:lmm_kernel_tag_alpha_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) :
+                    t.rho ? (r = Ref{Cdouble}(0.0);
+                             check(ccall((:lmm_kernel_tag_rho_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) : nothing,
             terms = terms)
 end
 _ard_grads(tags::Vector{KTag}, d::Integer) = [_tag_grads(t, d) for t in tags]
@@ -682,11 +701,15 @@ AbstractGPs.var(f::HIPMOGP, x::MOIsotopic) = _mean_var(f, x)[2]
 # kernel's construction: ScaledKernel: v = v_inner σ² -> d/dσ² = gv v_inner; ScaleTransform: ℓ = ℓ_inner / s -> d/ds = -gl ℓ_inner / s².
 # ga: d/d ard[k] of an ARD latent (lmm_ard_grad; gl is then d/d the common multiplier).  ARDTransform(v): ard = ard_inner ./ v
 # -> d/dv_k = -ga_k ard_inner_k / v_k^2 (with no inner factors, ℓ_k = multiplier / v_k: d/dv_k = -ℓ_k^2 d/dℓ_k), d/d ard_inner = ga ./ v.
-# gα: d/d alpha of an RQ latent (lmm_kernel_tag_alpha_grad), nothing otherwise
+# gα: d/d alpha of an RQ latent (lmm_kernel_tag_alpha_grad), d/d rho of a periodic one (lmm_kernel_tag_rho_grad), nothing otherwise
 # gt: the per-term gradients of a sum latent (_tag_grads(...).terms), nothing otherwise.
 _ktangent(k::Kernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) = NoTangent()            # SEKernel() etc. carry no parameters
 _ktangent(k::RationalQuadraticKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) =
     gα === nothing ? NoTangent() : Tangent{typeof(k)}(; α=[gα], metric=NoTangent())
+# PeriodicKernel: gα carries d/d rho, the derivative along r = fill(rho, d); it is spread evenly over the d entries of r (their sum is
+# d/d rho, which is all the library's one-rho kernel defines; exact for d = 1).
+_ktangent(k::PeriodicKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) =
+    gα === nothing ? NoTangent() : Tangent{typeof(k)}(; r=fill(gα / length(k.r), length(k.r)))
 function _ktangent(k::ScaledKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing)
     (_, vin, _) = _desc(k.kernel)
     return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv * only(k.σ²), gl, ga, gα, gt), σ²=[gv * vin])

@@ -61,10 +61,14 @@ class _Kernel:
         d = {"kind": self.kind, "variance": self.variance, "lengthscale": self.lengthscale}
         if hasattr(self, "alpha"):
             d["alpha"] = self.alpha
+        if hasattr(self, "r"):
+            d["r"] = self.r
         return d
 
     def key(self) -> tuple:
         """Hashable form of the kernel's values (the latent-array cache key)."""
+        if hasattr(self, "r"):
+            return (self.kind, self.variance, _ls_key(self.lengthscale), None, self.r)
         return (self.kind, self.variance, _ls_key(self.lengthscale), getattr(self, "alpha", None))
 
 
@@ -103,6 +107,38 @@ class RationalQuadraticKernel(_Kernel):
 
     def __repr__(self):
         return super().__repr__()[:-1] + f", alpha={self.alpha})"
+
+
+class PeriodicKernel(_Kernel):
+    """variance * exp(-sum_k sin^2(pi (x_k - x'_k) / period_k) / (2 r^2)): KernelFunctions' PeriodicKernel(; r) o ScaleTransform(1 /
+    period) (a vector: ARDTransform(1 ./ period)).  `lengthscale` is the period, a float or a length-d vector (`.period` is an alias);
+    `r` is one scalar for all dimensions (a vector with equal entries is accepted, unequal entries are refused)."""
+    kind = "periodic"
+
+    def __init__(self, variance: float = 1.0, lengthscale=1.0, r=1.0):
+        super().__init__(variance, lengthscale)
+        if np.ndim(r) != 0:
+            rv = np.asarray(r, dtype=np.float64).reshape(-1)
+            if rv.size == 0 or not np.all(rv == rv[0]):
+                raise ValueError("r must be one scalar for all dimensions (a vector with equal entries is accepted)")
+            r = rv[0]
+        self.r = float(r)
+        if not (self.r > 0.0 and np.isfinite(self.r)):
+            raise ValueError("r must be finite and > 0")
+
+    @property
+    def period(self):
+        return self.lengthscale
+
+    @period.setter
+    def period(self, v):
+        self.lengthscale = float(v) if np.ndim(v) == 0 else np.array(v, dtype=np.float64).reshape(-1)
+
+    def __eq__(self, o):
+        return super().__eq__(o) and self.r == o.r
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", r={self.r})"
 
 
 class KernelSum(_Kernel):
@@ -590,6 +626,8 @@ def _gps_grads(gg, ga, m: int, d: int) -> list:
         out.append({"variance": gg[l].variance, "lengthscale": ls, "mean": gg[l].mean})
         if ga.ard.has_alpha[l]:
             out[-1]["alpha"] = ga.ard.alpha_grad(l)
+        if ga.ard.has_rho[l]:
+            out[-1]["r"] = ga.ard.rho_grad(l)
     return out
 
 
