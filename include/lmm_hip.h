@@ -84,6 +84,13 @@ typedef enum {
  * their meaning, "the ScaleTransform"; rho = KernelFunctions' r, one scalar for all dimensions, from the latent's tag
  * (lmm_kernel_tag_create_periodic below), 1 without one.  kappa(0) = v, and the kernel is smooth at coincident points. */
 #define LMM_KERNEL_PERIODIC 7
+/* A base kind outside the enum (codes 6, 8 and 9 stay refused): the locally periodic kernel, KernelFunctions'
+ * (SEKernel o ScaleTransform(1 / l)) * (PeriodicKernel(; r) o ScaleTransform(1 / P)) (or ARDTransform for a vector period),
+ *     k(x, x') = v exp( -|x - x'|^2 / (2 l^2) - (1 / (2 rho^2)) sum_k sin^2( pi (x_k - x'_k) / P_k ) ).
+ * v, the period P_k (the `lengthscale` slot, times the tag's ard[k]) and rho are those of LMM_KERNEL_PERIODIC; l is the `decay`, one
+ * scalar SE lengthscale.  rho and decay come from the latent's tag (lmm_kernel_tag_create_locally_periodic below), 1 and 1 without
+ * one.  kappa(0) = v, smooth at coincident points.  It is the one product the library represents: a base kind, so it may be a sum term. */
+#define LMM_KERNEL_LOCALLY_PERIODIC 10
 
 /* One latent GP: GP(mean, variance * Kernel o ScaleTransform(1/lengthscale)).
  * kind = base | (tag << 8): the low byte is the lmm_kernel_kind; a non-zero tag (lmm_ard_create) gives the latent per-dimension
@@ -131,14 +138,20 @@ typedef struct lmm_post lmm_post_t;   /* opaque posterior state (device resident
  *   lmm_kernel_tag_rho_grad : d logpdf / d rho, with the semantics of lmm_kernel_tag_alpha_grad (the most recent gradient entry
  *                    point that named the tag; summed over that call's latents carrying it, partial over its shard, 0 if grad_gps
  *                    was NULL).  LMM_ERR_ARG on a tag without a rho; lmm_kernel_tag_alpha_grad on a tag with a rho is LMM_ERR_ARG.
- * Validation in every entry point: the base kind must be 0..4 or 7 (LMM_ERR_UNSUPPORTED otherwise) and the tag live (LMM_ERR_ARG
- * otherwise); a tag with an alpha on a latent whose base kind is not LMM_KERNEL_RQ is LMM_ERR_ARG, and so is a tag with a rho on a
- * latent whose base kind is not LMM_KERNEL_PERIODIC; a tag with factors must have the
+ *   lmm_kernel_tag_create_locally_periodic : a tag for a locally periodic latent (LMM_KERNEL_LOCALLY_PERIODIC): d, ard as in
+ *                    lmm_kernel_tag_create_periodic (factors of the period); rho and decay finite and > 0, otherwise LMM_ERR_ARG.
+ *                    Same registry, mutex and 4096 limit; freed by lmm_ard_destroy.  lmm_kernel_tag_rho_grad serves its rho.
+ *   lmm_kernel_tag_decay_grad : d logpdf / d decay, with the semantics of lmm_kernel_tag_rho_grad.  LMM_ERR_ARG on a tag without a
+ *                    decay.
+ * Validation in every entry point: the base kind must be 0..4, 7 or 10 (LMM_ERR_UNSUPPORTED otherwise) and the tag live (LMM_ERR_ARG
+ * otherwise); a tag with an alpha on a latent whose base kind is not LMM_KERNEL_RQ is LMM_ERR_ARG, and so is a tag with a rho (and no
+ * decay) on a latent whose base kind is not LMM_KERNEL_PERIODIC, and a tag with a decay on one whose base kind is not
+ * LMM_KERNEL_LOCALLY_PERIODIC; a tag with factors must have the
  * call's d (LMM_ERR_DIM, naming the latent).  With d == 1, or when all ard[k] are equal, the latent is folded into the isotropic
  * descriptor (lengthscale * ard[0]) before anything runs: its values are then exactly those of the isotropic latent, and it keeps
  * its alpha or rho.  An RQ latent without a tag, or whose tag has no alpha, uses alpha = 2 (KernelFunctions' default) and reports no alpha
  * gradient.  lmm_ard_destroy frees any tag; lmm_ard_grad on a tag without factors writes nothing.  The 4096-tag limit counts every
- * tag.  Posterior handles keep their own copy of alpha and rho, as of the lengthscales.  The gradient entry points serve d <= 32 for
+ * tag.  Posterior handles keep their own copy of alpha, rho and decay, as of the lengthscales.  The gradient entry points serve d <= 32 for
  * latents with d > 1 factors (LMM_ERR_UNSUPPORTED beyond). */
 #define LMM_KERNEL_BASE_MASK 0xff
 int lmm_ard_create(int d, const double* lengthscale, int* tag);
@@ -148,6 +161,8 @@ int lmm_kernel_tag_create(int d, const double* ard, double alpha, int* tag);
 int lmm_kernel_tag_alpha_grad(int tag, double* out);
 int lmm_kernel_tag_create_periodic(int d, const double* ard, double rho, int* tag);
 int lmm_kernel_tag_rho_grad(int tag, double* out);
+int lmm_kernel_tag_create_locally_periodic(int d, const double* ard, double rho, double decay, int* tag);
+int lmm_kernel_tag_decay_grad(int tag, double* out);
 
 /* ---- sum kernels (KernelFunctions' KernelSum) ------------------------------------------------
  * A sum latent has kind = LMM_KERNEL_SUM | (tag << 8) with a tag from lmm_kernel_sum_create, and the kernel
@@ -155,18 +170,19 @@ int lmm_kernel_tag_rho_grad(int tag, double* out);
  * where v0 and s0 are the latent's own `variance` and `lengthscale` (the ScaledKernel and ScaleTransform around the whole sum) and
  * term c has base kind kind_c, variance v_c and lengthscale l_c.  A term's kind may carry a tag of its own (lmm_kernel_tag_create):
  * its per-dimension lengthscales are then s0 * l_c * ard_c[k], and an RQ term takes its alpha from it and a periodic term (whose l_c is its
- * period) its rho.  The latent's `mean` applies to the whole sum.  Sums do not nest; products and an ARD transform around a whole sum
- * are not represented.
+ * period) its rho; a locally periodic term its rho and decay, and the outer ScaleTransform acts on both of its factors: its period is
+ * s0 * l_c and its decay s0 * decay (d/ds0 collects both).  The latent's `mean` applies to the whole sum.  Sums do not nest; general
+ * products and an ARD transform around a whole sum are not represented.
  *   lmm_kernel_sum_create : registers nterms (1..LMM_SUM_MAX_TERMS) terms in the tag registry above (same mutex, no lmm_init needed,
  *                    counted against its 4096-tag limit, freed by lmm_ard_destroy).  Each term: kind = base | (ktag << 8) with base
- *                    0..4 or 7 (LMM_KERNEL_PERIODIC), variance > 0, lengthscale > 0, mean == 0.  nterms out of range or a bad term value -> LMM_ERR_ARG; a term
- *                    of kind LMM_KERNEL_SUM, 6 or a base kind > 7 -> LMM_ERR_UNSUPPORTED; a term tag that is unknown, is itself a sum
+ *                    0..4, 7 (LMM_KERNEL_PERIODIC) or 10 (LMM_KERNEL_LOCALLY_PERIODIC), variance > 0, lengthscale > 0, mean == 0.  nterms out of range or a bad term value -> LMM_ERR_ARG; a term
+ *                    of kind LMM_KERNEL_SUM, 6, 8, 9 or a base kind > 10 -> LMM_ERR_UNSUPPORTED; a term tag that is unknown, is itself a sum
  *                    tag, carries an alpha while the term's base kind is not LMM_KERNEL_RQ, or a rho while it is not
- *                    LMM_KERNEL_PERIODIC -> LMM_ERR_ARG.
+ *                    LMM_KERNEL_PERIODIC, or a decay while it is not LMM_KERNEL_LOCALLY_PERIODIC -> LMM_ERR_ARG.
  *   lmm_kernel_sum_grad : nterms entries (d/dv_c, d/dl_c, 0) from the most recent gradient entry point that named the tag, with the
  *                    semantics of lmm_ard_grad (summed over that call's latents carrying the tag, partial over its shard, zeros if
- *                    grad_gps was NULL).  A term's ARD, alpha and rho gradients are published to the term's own tag (lmm_ard_grad,
- *                    lmm_kernel_tag_alpha_grad, lmm_kernel_tag_rho_grad) with s0 * l_c as the multiplier of its factors.  grad_gps[l].variance and
+ *                    grad_gps was NULL).  A term's ARD, alpha, rho and decay gradients are published to the term's own tag (lmm_ard_grad,
+ *                    lmm_kernel_tag_alpha_grad, lmm_kernel_tag_rho_grad, lmm_kernel_tag_decay_grad) with s0 * l_c as the multiplier of its factors.  grad_gps[l].variance and
  *                    .lengthscale of a sum latent are d/dv0 and d/ds0.
  * Term tags are looked up when an entry point resolves its latents: a destroyed term tag is LMM_ERR_ARG and a term tag with factors
  * of another d than the call's LMM_ERR_DIM, both naming the latent.  Posterior handles keep their own copy of the resolved terms.
@@ -332,7 +348,8 @@ int lmm_ilmm_post_latent_logpdf_grad_seq(const double* x, int d, int n, const in
  *     d logpdf / d x_ik = -(1 / l_k^2) sum_{j != i} w_ij h(r_ij) (x_ik - x_jk),
  *     h(r) = v e^{-r^2/2} (SE), 3 v e^{-sqrt3 r} (Matern32), (5/3) v (1 + sqrt5 r) e^{-sqrt5 r} (Matern52), v e^{-r} / r (Matern12),
  *            v (1 + r^2 / (2 alpha))^{-alpha-1} (RQ);  a periodic latent, not a function of r, contributes
- *     d kappa / d x_ik = -kappa pi sin(2 pi t_k) / (2 rho^2 P_k), t_k = (x_ik - x_jk) / P_k, in place of -h t_k / l_k,
+ *     d kappa / d x_ik = -kappa pi sin(2 pi t_k) / (2 rho^2 P_k), t_k = (x_ik - x_jk) / P_k, in place of -h t_k / l_k
+ *     (a locally periodic latent: that plus -kappa (x_ik - x_jk) / decay^2),
  * summed over the latents (the noise, the mean, the projection and the regulariser do not depend on x).  Matern12 has a cusp at
  * coincident points: a pair at r = 0 contributes 0 there (the convention of the lengthscale gradient).  Predictive forms: the joint
  * over [x; xs] minus the marginal over x, as for every other derivative there.

@@ -18,11 +18,12 @@ KERNEL_KINDS = {"se": 0, "matern32": 1, "matern52": 2, "matern12": 3, "rq": 4}
 KERNEL_SUM = 5              # LMM_KERNEL_SUM: a sum latent (descriptor kind "sum"), not a base kind
 SUM_MAX_TERMS = 4
 KERNEL_PERIODIC = 7         # LMM_KERNEL_PERIODIC: a base kind outside lmm_kernel_kind (descriptor kind "periodic")
+KERNEL_LOCALLY_PERIODIC = 10     # LMM_KERNEL_LOCALLY_PERIODIC: SE x Periodic as one base kind (descriptor kind "locally_periodic")
 
 # Every symbol include/lmm_hip.h declares (tests/test_abi.py checks the library exports each one).
 SYMBOLS = [
     "lmm_init", "lmm_shutdown", "lmm_last_error_string", "lmm_last_error_detail", "lmm_device_synchronize", "lmm_release_cached_memory",
-    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_kernel_tag_create_periodic", "lmm_kernel_tag_rho_grad", "lmm_kernel_sum_create", "lmm_kernel_sum_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
+    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_kernel_tag_create_periodic", "lmm_kernel_tag_rho_grad", "lmm_kernel_tag_create_locally_periodic", "lmm_kernel_tag_decay_grad", "lmm_kernel_sum_create", "lmm_kernel_sum_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
     "lmm_comm_destroy",
     "lmm_set_strict_progress", "lmm_get_strict_progress", "lmm_dev_claim_scramble", "lmm_orthogonal_validate", "lmm_oilmm_logpdf", "lmm_oilmm_logpdf_grad", "lmm_oilmm_post_logpdf_grad", "lmm_oilmm_post_logpdf_grad_seq", "lmm_ilmm_logpdf_grad", "lmm_ilmm_post_logpdf_grad", "lmm_ilmm_post_logpdf_grad_seq", "lmm_ilmm_post_latent_logpdf_grad_seq", "lmm_oilmm_logpdf_grad_x", "lmm_oilmm_post_logpdf_grad_seq_x", "lmm_ilmm_logpdf_grad_x",
     "lmm_ilmm_post_logpdf_grad_seq_x", "lmm_ilmm_post_latent_logpdf_grad_seq_x", "lmm_oilmm_logpdf_multi", "lmm_reorder", "lmm_ilmm_logpdf", "lmm_ilmm_logpdf_ex", "lmm_ilmm_logpdf_multi", "lmm_mogp_logpdf", "lmm_mogp_logpdf_diag",
@@ -315,7 +316,7 @@ KERNEL_BASE_MASK = 0xFF
 class ArdTags:
     """Owner of the kernel tags (lmm_ard_create / lmm_kernel_tag_create) of one lmm_gp_t array: destroyed with the array (gps_array
     attaches it as `.ard`).  tags[l] is latent l's tag, 0 for an isotropic latent without an RQ shape; has_ard[l] tells whether the
-    tag holds per-dimension factors, has_alpha[l] whether it holds an RQ shape, has_rho[l] whether it holds a periodic latent's r.  A sum latent's tag is its lmm_kernel_sum_create tag,
+    tag holds per-dimension factors, has_alpha[l] whether it holds an RQ shape, has_rho[l] whether it holds a periodic or locally periodic latent's r, has_decay[l] whether it holds a locally periodic latent's decay.  A sum latent's tag is its lmm_kernel_sum_create tag,
     and terms[l] is the ArdTags of its terms (None for other latents); close() destroys the sum tag before the term tags."""
 
     def __init__(self, m: int):
@@ -323,6 +324,7 @@ class ArdTags:
         self.has_ard = [False] * m
         self.has_alpha = [False] * m
         self.has_rho = [False] * m
+        self.has_decay = [False] * m
         self.terms = [None] * m
         self._lib = None
 
@@ -341,7 +343,7 @@ class ArdTags:
 
     def sum_grad(self, l: int, d: int) -> list:
         """Per-term gradients of sum latent l after a gradient call: [{"variance", "lengthscale" (float, or the length-d array
-        d logpdf / d lengthscale_k of a term with per-dimension lengthscales), "alpha" (RQ terms), "r" (periodic terms)}, ...]."""
+        d logpdf / d lengthscale_k of a term with per-dimension lengthscales), "alpha" (RQ terms), "r" (periodic and locally periodic terms), "decay" (locally periodic terms)}, ...]."""
         ta = self.terms[l]
         n = len(ta.tags)
         out = (GpGradT * n)()
@@ -353,15 +355,21 @@ class ArdTags:
                 e["alpha"] = ta.alpha_grad(c)
             if ta.has_rho[c]:
                 e["r"] = ta.rho_grad(c)
+            if ta.has_decay[c]:
+                e["decay"] = ta.decay_grad(c)
             res.append(e)
         return res
 
-    def create(self, l: int, ls: Optional[np.ndarray], alpha: Optional[float] = None, rho: Optional[float] = None) -> int:
+    def create(self, l: int, ls: Optional[np.ndarray], alpha: Optional[float] = None, rho: Optional[float] = None,
+               decay: Optional[float] = None) -> int:
         """One tag for latent l: the factors `ls` (None: none) and / or the RQ shape `alpha` (None: none), or a periodic latent's
-        `rho` (None: none)."""
+        `rho` (None: none), or a locally periodic latent's `rho` and `decay` (both given)."""
         self._lib = self._lib or load()
         t = C.c_int()
-        if rho is not None:
+        if decay is not None:
+            d, p = (0, None) if ls is None else (int(ls.size), ls.ctypes.data_as(C.POINTER(C.c_double)))
+            check(self._lib.lmm_kernel_tag_create_locally_periodic(d, p, C.c_double(rho), C.c_double(decay), C.byref(t)))
+        elif rho is not None:
             d, p = (0, None) if ls is None else (int(ls.size), ls.ctypes.data_as(C.POINTER(C.c_double)))
             check(self._lib.lmm_kernel_tag_create_periodic(d, p, C.c_double(rho), C.byref(t)))
         elif alpha is None:
@@ -373,6 +381,7 @@ class ArdTags:
         self.has_ard[l] = ls is not None
         self.has_alpha[l] = alpha is not None
         self.has_rho[l] = rho is not None
+        self.has_decay[l] = decay is not None
         return t.value
 
     def alpha_grad(self, l: int) -> float:
@@ -385,6 +394,12 @@ class ArdTags:
         """d logpdf / d r of latent l's tag after a gradient call."""
         out = C.c_double(0.0)
         check(self._lib.lmm_kernel_tag_rho_grad(self.tags[l], C.byref(out)))
+        return out.value
+
+    def decay_grad(self, l: int) -> float:
+        """d logpdf / d decay of latent l's tag after a gradient call."""
+        out = C.c_double(0.0)
+        check(self._lib.lmm_kernel_tag_decay_grad(self.tags[l], C.byref(out)))
         return out.value
 
     def grad(self, l: int, d: int) -> np.ndarray:
@@ -406,6 +421,7 @@ class ArdTags:
         self.has_ard = [False] * len(self.tags)
         self.has_alpha = [False] * len(self.tags)
         self.has_rho = [False] * len(self.tags)
+        self.has_decay = [False] * len(self.tags)
 
     def __del__(self):
         try:
@@ -418,7 +434,9 @@ def gps_array(gps: Sequence[dict]):
     """lmm_gp_t array of latent descriptors.  A vector "lengthscale" (length d) becomes an ARD latent: a tag holding the vector, kind
     = base | tag << 8 and lengthscale (the common multiplier) 1.  An "rq" latent's "alpha" (default 2.0) goes into its tag too (one
     tag holds both).  A "periodic" latent's "lengthscale" is its period and its "r" (default 1.0) goes into a tag
-    (lmm_kernel_tag_create_periodic) with the vector, if any; a descriptor without "r" and with a scalar period needs no tag.  A "sum" latent's "terms" (descriptors as above, mean 0) get their own tags and then one sum tag
+    (lmm_kernel_tag_create_periodic) with the vector, if any; a descriptor without "r" and with a scalar period needs no tag.  A "locally_periodic" latent is a
+    periodic one with a scalar "decay" (default 1.0) next to "r": both go into one tag (lmm_kernel_tag_create_locally_periodic), needed
+    when the descriptor has "r", "decay" or a vector period.  A "sum" latent's "terms" (descriptors as above, mean 0) get their own tags and then one sum tag
     (lmm_kernel_sum_create); its "variance" and scalar "lengthscale" scale the whole sum.  The tags live as long as the returned array
     (its `.ard`)."""
     arr = (GpT * max(len(gps), 1))()
@@ -435,11 +453,12 @@ def gps_array(gps: Sequence[dict]):
             a.kind |= arr.ard.create_sum(l, g["terms"]) << 8
             a.mean = float(g.get("mean", 0.0))
             continue
-        a.kind = KERNEL_PERIODIC if g["kind"] == "periodic" else KERNEL_KINDS[g["kind"]]
+        special = {"periodic": KERNEL_PERIODIC, "locally_periodic": KERNEL_LOCALLY_PERIODIC}
+        a.kind = special[g["kind"]] if g["kind"] in special else KERNEL_KINDS[g["kind"]]
         ls = g.get("lengthscale", 1.0)
         alpha = float(g.get("alpha", 2.0)) if g["kind"] == "rq" else None
-        rho = None
-        if g["kind"] == "periodic":
+        rho = decay = None
+        if g["kind"] in ("periodic", "locally_periodic"):
             r = g.get("r", 1.0)
             if np.ndim(r) != 0:
                 r = np.asarray(r, dtype=np.float64).reshape(-1)
@@ -449,8 +468,19 @@ def gps_array(gps: Sequence[dict]):
             r = float(r)
             if not (r > 0.0 and np.isfinite(r)):
                 raise ValueError("r must be finite and > 0")
-            if "r" in g or np.ndim(ls) != 0:      # a descriptor without "r" and with a scalar period needs no tag (and reports no r gradient)
+            if "r" in g or "decay" in g or np.ndim(ls) != 0:      # a descriptor without "r" and with a scalar period needs no tag (and reports no r gradient)
                 rho = r
+        if g["kind"] == "locally_periodic":
+            dc = g.get("decay", 1.0)
+            if np.ndim(dc) != 0:
+                raise ValueError("a locally periodic kernel's decay is one scalar (a per-dimension decay is not supported)")
+            dc = float(dc)
+            if not (dc > 0.0 and np.isfinite(dc)):
+                raise ValueError("decay must be finite and > 0")
+            if rho is not None:
+                decay = dc
+        elif "decay" in g:
+            raise ValueError(f"a {g['kind']!r} kernel takes no decay")
         vec = None
         if np.ndim(ls) == 0:
             a.lengthscale = float(ls)
@@ -458,7 +488,7 @@ def gps_array(gps: Sequence[dict]):
             vec = np.ascontiguousarray(ls, dtype=np.float64).reshape(-1)
             a.lengthscale = 1.0
         if vec is not None or alpha is not None or rho is not None:
-            a.kind |= arr.ard.create(l, vec, alpha, rho) << 8
+            a.kind |= arr.ard.create(l, vec, alpha, rho, decay) << 8
         a.mean = float(g.get("mean", 0.0))
     return arr
 

@@ -311,6 +311,7 @@ struct Dims {
 struct ArdTag {           // d = 0: no factors; alpha = 0: no shape; terms non-empty: a sum tag (lmm_kernel_sum_create; d = 0, alpha = 0)
   int d; std::vector<double> ard, grad; double alpha = 0.0, galpha = 0.0;
   double rho = 0.0, grho = 0.0;         // a periodic latent's rho (lmm_kernel_tag_create_periodic; 0: none) and its latest gradient
+  double decay = 0.0, gdecay = 0.0;     // a locally periodic latent's decay (lmm_kernel_tag_create_locally_periodic, with its rho; 0: none)
   std::vector<lmm_gp_t> terms;
   std::vector<lmm_gp_grad_t> tgrad;     // a sum tag's latest per-term (d/dv_c, d/dl_c, 0)
 };
@@ -326,6 +327,8 @@ struct KernelTerm {
   double mult = 1.0, fold = 1.0;   // multiplier of the factors; the factor a folded term's lengthscale was multiplied by (1 otherwise)
   double alpha = 0.0;              // the tag's RQ shape (0: none; the term then reports no alpha gradient)
   double rho = 0.0;                // the tag's periodic rho (0: none: rho = 1, and the term reports no rho gradient)
+  double decay = 0.0;              // the tag's locally periodic decay (0: none: decay = 1, and the term reports no decay gradient)
+  double dscale = 1.0;             // what multiplies the decay: a sum latent's s0 (the outer ScaleTransform acts on the SE factor too), else 1
   double v = 1.0, ls = 1.0;        // v_c, l_c
   LatentDev ev{}, gd{};
   int ev_ent = -1, gd_ent = -1;    // entries of LatentSet::host that ev.ils / gd.ils point to (-1: isotropic)
@@ -339,7 +342,7 @@ struct Latent {
   bool is_sum() const { return kind == LMM_KERNEL_SUM; }
   int nt() const { return (int)terms.size(); }
   bool has_periodic() const {
-    for (const KernelTerm& T : terms) if (T.ev.kind == LMM_KERNEL_PERIODIC) return true;
+    for (const KernelTerm& T : terms) if (T.ev.kind == LMM_KERNEL_PERIODIC || T.ev.kind == LMM_KERNEL_LOCALLY_PERIODIC) return true;
     return false;
   }
   LatentDev dev() const {
@@ -354,6 +357,7 @@ struct Latent {
     const LatentDev d = dev();
     a.kind = d.kind; a.var = d.var; a.inv_ls = d.inv_ls; a.ils = d.ils; a.alpha = d.alpha; a.terms = d.terms; a.nterms = d.nterms;
     a.sum_per = is_sum() && has_periodic();
+    a.inv_decay = d.inv_decay;
   }
   // kappa(0): the variance, or v0 sum_c v_c for a sum latent
   double prior_var() const {
@@ -371,7 +375,7 @@ struct Latent {
     for (int c = 0; c < nt(); ++c) {
       const LatentDev& x = terms[c].ev;
       const LatentDev& y = o.terms[c].ev;
-      if (x.kind != y.kind || x.var != y.var || x.inv_ls != y.inv_ls || x.alpha != y.alpha) return false;
+      if (x.kind != y.kind || x.var != y.var || x.inv_ls != y.inv_ls || x.alpha != y.alpha || x.inv_decay != y.inv_decay) return false;
       if (is_sum() ? (x.ils != nullptr || y.ils != nullptr) : x.ils != y.ils) return false;
     }
     return true;
@@ -385,7 +389,7 @@ struct LatentSet {
   Buf<double> dev;                          // the same on the device
   std::vector<LatentDev> thost;             // the evaluation descriptors of every sum term (host, then `tdev`)
   Buf<LatentDev> tdev;
-  int any_sum() const {                     // the dense kernels' instantiation: 2 with a periodic latent or term, 1 with a sum latent
+  int any_sum() const {                     // the dense kernels' instantiation: 2 with a (locally) periodic latent or term, 1 with a sum latent
     int r = 0;
     for (const Latent& L : lat) {
       if (L.has_periodic()) return 2;
@@ -413,14 +417,16 @@ struct LatentSet {
 };
 
 // One term from its base kind, V, multiplier E and the factors / shape of its tag: fold, d == 1, or a (shared) vector.  A periodic
-// term's descriptor carries 1 / rho^2 in the alpha slot, which it does not otherwise use (so same_kernel compares rho with it).
+// term's descriptor carries 1 / rho^2 in the alpha slot, which it does not otherwise use (so same_kernel compares rho with it); a
+// locally periodic one the same and 1 / (dscale decay) in inv_decay (the factors and E act on its period only).
 void resolve_term(LatentSet& S, KernelTerm& T, int base, double V, double E, const std::vector<double>& ard, double alpha, double rho,
-                  std::map<std::pair<int, double>, int>& entry_of) {
+                  double decay, double dscale, std::map<std::pair<int, double>, int>& entry_of) {
   const int d = S.d;
-  T.mult = E; T.alpha = alpha; T.rho = rho;
+  T.mult = E; T.alpha = alpha; T.rho = rho; T.decay = decay; T.dscale = dscale;
   LatentDev ev{};
   ev.kind = base; ev.var = V; ev.inv_ls = 1.0 / E; ev.alpha = alpha > 0.0 ? alpha : LMM_RQ_DEFAULT_ALPHA;
-  if (base == LMM_KERNEL_PERIODIC) ev.alpha = rho > 0.0 ? 1.0 / (rho * rho) : 1.0;
+  if (base == LMM_KERNEL_PERIODIC || base == LMM_KERNEL_LOCALLY_PERIODIC) ev.alpha = rho > 0.0 ? 1.0 / (rho * rho) : 1.0;
+  if (base == LMM_KERNEL_LOCALLY_PERIODIC) ev.inv_decay = 1.0 / (dscale * (decay > 0.0 ? decay : 1.0));
   T.gd = ev;
   if (!ard.empty()) {
     T.has_ard = true;
@@ -448,18 +454,28 @@ Latent plain_latent(const lmm_gp_t& gp) {
   L.terms.resize(1);
   LatentDev& ev = L.terms[0].ev;
   ev.kind = L.kind; ev.var = gp.variance; ev.inv_ls = 1.0 / gp.lengthscale; ev.alpha = LMM_RQ_DEFAULT_ALPHA;
-  if (L.kind == LMM_KERNEL_PERIODIC) ev.alpha = 1.0;      // 1 / rho^2 at the default rho = 1
+  if (L.kind == LMM_KERNEL_PERIODIC || L.kind == LMM_KERNEL_LOCALLY_PERIODIC) ev.alpha = 1.0;      // 1 / rho^2 at the default rho = 1
+  if (L.kind == LMM_KERNEL_LOCALLY_PERIODIC) ev.inv_decay = 1.0;                                   // and the default decay = 1
   L.terms[0].mult = gp.lengthscale;
   L.terms[0].gd = ev;
   return L;
 }
+
+// Whether a tag's shape (alpha: RQ; rho alone: periodic; rho and decay: locally periodic; none: any kind) fits a base kind.
+inline bool tag_shape_fits(int base, double alpha, double rho, double decay) {
+  if (alpha > 0.0 && base != LMM_KERNEL_RQ) return false;
+  if (decay > 0.0) return base == LMM_KERNEL_LOCALLY_PERIODIC;
+  if (rho > 0.0 && base != LMM_KERNEL_PERIODIC) return false;
+  return true;
+}
+inline bool base_kind_ok(int base) { return base <= LMM_KERNEL_RQ || base == LMM_KERNEL_PERIODIC || base == LMM_KERNEL_LOCALLY_PERIODIC; }
 
 // The caller's latents, validated and resolved.  A call without tags allocates nothing on the device and copies nothing to it.
 int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) {
   if (!gps) return fail(LMM_ERR_ARG, "gps is NULL");
   for (int l = 0; l < m; ++l) {
     const int base = gps[l].kind & LMM_KERNEL_BASE_MASK;
-    if (gps[l].kind < 0 || (base > LMM_KERNEL_SUM && base != LMM_KERNEL_PERIODIC)) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
+    if (gps[l].kind < 0 || (base != LMM_KERNEL_SUM && !base_kind_ok(base))) return fail(LMM_ERR_UNSUPPORTED, "latent %d: unsupported kernel kind %d", l, gps[l].kind);
     if (base == LMM_KERNEL_SUM && (gps[l].kind >> 8) == 0) return fail(LMM_ERR_ARG, "latent %d: a sum latent needs a sum tag (lmm_kernel_sum_create)", l);
     if (!(gps[l].variance > 0.0) || !(gps[l].lengthscale > 0.0)) return fail(LMM_ERR_ARG, "latent %d: variance and lengthscale must be > 0", l);
   }
@@ -474,10 +490,10 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
     if (tag == 0) continue;
     L.tag = tag;
     std::vector<double> ard;
-    double alpha, rho;
+    double alpha, rho, decay;
     std::vector<lmm_gp_t> terms;
     std::vector<std::vector<double>> tard;
-    std::vector<double> talpha, trho;
+    std::vector<double> talpha, trho, tdecay;
     {
       std::lock_guard<std::mutex> lk(g_ard_mu);
       auto it = g_ard_tags.find(tag);
@@ -489,12 +505,14 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
       ard = it->second.ard;
       alpha = it->second.alpha;
       rho = it->second.rho;
+      decay = it->second.decay;
       terms = it->second.terms;
       for (size_t c = 0; c < terms.size(); ++c) {
         const int tt = terms[c].kind >> 8;
         tard.emplace_back();
         talpha.push_back(0.0);
         trho.push_back(0.0);
+        tdecay.push_back(0.0);
         if (tt == 0) continue;
         auto jt = g_ard_tags.find(tt);
         if (jt == g_ard_tags.end() || !jt->second.terms.empty())
@@ -504,8 +522,9 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
         tard.back() = jt->second.ard;
         talpha.back() = jt->second.alpha;
         trho.back() = jt->second.rho;
+        tdecay.back() = jt->second.decay;
         const int tb = terms[c].kind & LMM_KERNEL_BASE_MASK;
-        if ((talpha.back() > 0.0 && tb != LMM_KERNEL_RQ) || (trho.back() > 0.0 && tb != LMM_KERNEL_PERIODIC))
+        if (!tag_shape_fits(tb, talpha.back(), trho.back(), tdecay.back()))
           return fail(LMM_ERR_ARG, "latent %d: term %d: tag %d carries a shape its kernel kind %d does not take", l, (int)c, tt, tb);
       }
     }
@@ -514,17 +533,19 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
       for (int c = 0; c < L.nt(); ++c) {
         KernelTerm& T = L.terms[c];
         T.tag = terms[c].kind >> 8; T.v = terms[c].variance; T.ls = terms[c].lengthscale;
-        resolve_term(*S, T, terms[c].kind & LMM_KERNEL_BASE_MASK, L.variance * T.v, L.lengthscale * T.ls, tard[c], talpha[c], trho[c], entry_of);
+        resolve_term(*S, T, terms[c].kind & LMM_KERNEL_BASE_MASK, L.variance * T.v, L.lengthscale * T.ls, tard[c], talpha[c], trho[c], tdecay[c],
+                     L.lengthscale, entry_of);
       }
       continue;
     }
     if (alpha > 0.0 && L.kind != LMM_KERNEL_RQ)
       return fail(LMM_ERR_ARG, "latent %d: tag %d carries an RQ shape but the kernel kind is %d", l, tag, L.kind);
-    if (rho > 0.0 && L.kind != LMM_KERNEL_PERIODIC)
-      return fail(LMM_ERR_ARG, "latent %d: tag %d carries a periodic rho but the kernel kind is %d", l, tag, L.kind);
+    if (!tag_shape_fits(L.kind, alpha, rho, decay))
+      return fail(LMM_ERR_ARG, "latent %d: tag %d carries a %s but the kernel kind is %d", l, tag,
+                  decay > 0.0 ? "locally periodic rho and decay" : "periodic rho", L.kind);
     KernelTerm& T = L.terms[0];
     T.tag = tag;
-    resolve_term(*S, T, L.kind, L.variance, L.lengthscale, ard, alpha, rho, entry_of);
+    resolve_term(*S, T, L.kind, L.variance, L.lengthscale, ard, alpha, rho, decay, 1.0, entry_of);
     L.lengthscale = gps[l].lengthscale * T.fold;
   }
   if (!S->host.empty()) {
@@ -579,8 +600,10 @@ int input_grad_check(int d, bool wanted) {
 // d/dv_c = v0 d/dV_c, d/dl_c = s0 d/dE_c and d/ds0 = sum_c l_c d/dE_c (returned; a plain latent's d/d lengthscale).  red: LMM_NGRAD
 // sums per term, ard: d per-dimension sums per term (read where gd.ils is set).  aa, tr: alpha.alpha and tr Kt^-1 over all rows
 // (d/dV_c = (sum_{i>j} w K_c,ij + V_c (aa - tr) / 2) / V_c; *dv0 = sum_c v_c d/dV_c).  out: one record of term_grad_stride(d) values
-// per term: (d/dv_c, d/dl_c, d/dalpha_c, d/dl_k of the term's per-dimension lengthscales).
-inline size_t term_grad_stride(int d) { return 3 + (size_t)d; }
+// per term: (d/dv_c, d/dl_c, d/dalpha_c or d/drho_c, d/ddecay_c, d/dl_k of the term's per-dimension lengthscales).  A locally periodic
+// term's SE lengthscale is dscale * decay (dscale = s0 in a sum): red[9] is the derivative with respect to that product, so
+// d/ddecay_c = dscale red[9] and, in a sum, d/ds0 gains decay red[9].
+inline size_t term_grad_stride(int d) { return 4 + (size_t)d; }
 double grad_finish(const Latent& L, int d, const double* red, const double* ard, double aa, double tr, double* out,
                    double* dv0 = nullptr) {
   double ds0 = 0.0, gv0 = 0.0;
@@ -595,9 +618,13 @@ double grad_finish(const Latent& L, int d, const double* red, const double* ard,
     o[0] = gV * L.variance;
     o[1] = dE * L.lengthscale;
     o[2] = (T.alpha > 0.0 || T.rho > 0.0) ? rc[8] : 0.0;      // d/d alpha (RQ) or d/d rho (periodic): one slot, a term has one of them
-    if (T.gd.ils) for (int k = 0; k < d; ++k) o[3 + k] = ard[(size_t)d * c + k];
-    else if (T.has_ard) o[3] = rc[0];                      // d == 1: d/d l_eff, l_eff = multiplier * fold
+    if (T.gd.ils) for (int k = 0; k < d; ++k) o[4 + k] = ard[(size_t)d * c + k];
+    else if (T.has_ard) o[4] = rc[0];                      // d == 1: d/d l_eff, l_eff = multiplier * fold
     ds0 += dE * T.ls;
+    if (T.ev.kind == LMM_KERNEL_LOCALLY_PERIODIC) {
+      o[3] = T.decay > 0.0 ? T.dscale * rc[9] : 0.0;
+      if (L.is_sum()) ds0 += (T.decay > 0.0 ? T.decay : 1.0) * rc[9];
+    }
     gv0 += gV * T.v;
   }
   if (dv0) *dv0 = gv0;
@@ -614,7 +641,7 @@ void publish_grads(const LatentSet& S, const std::vector<double>* trec, int l0, 
   auto reset = [&](int tag) {
     auto it = g_ard_tags.find(tag);
     if (tag == 0 || it == g_ard_tags.end()) return;
-    it->second.grad.assign(it->second.d, 0.0); it->second.galpha = 0.0; it->second.grho = 0.0;
+    it->second.grad.assign(it->second.d, 0.0); it->second.galpha = 0.0; it->second.grho = 0.0; it->second.gdecay = 0.0;
     it->second.tgrad.assign(it->second.terms.size(), lmm_gp_grad_t{0.0, 0.0, 0.0});
   };
   for (const Latent& L : S.lat) {
@@ -635,9 +662,10 @@ void publish_grads(const LatentSet& S, const std::vector<double>* trec, int l0, 
       auto it = g_ard_tags.find(T.tag);
       if (T.tag == 0 || it == g_ard_tags.end()) continue;
       if (T.has_ard)
-        for (int k = 0; k < std::min(S.d, it->second.d); ++k) it->second.grad[k] += T.mult * r[3 + k];
+        for (int k = 0; k < std::min(S.d, it->second.d); ++k) it->second.grad[k] += T.mult * r[4 + k];
       if (T.alpha > 0.0) it->second.galpha += r[2];
       if (T.rho > 0.0) it->second.grho += r[2];
+      if (T.decay > 0.0) it->second.gdecay += r[3];
     }
   }
 }
@@ -1375,14 +1403,14 @@ static int ard_fail(int code, const char* msg) {
 }
 
 // Registers a validated tag (d = 0, ard unused: no factors; alpha = 0: no RQ shape).
-static int tag_register(int d, const double* ard, double alpha, int* tag, const char* full_msg, double rho = 0.0) {
+static int tag_register(int d, const double* ard, double alpha, int* tag, const char* full_msg, double rho = 0.0, double decay = 0.0) {
   std::lock_guard<std::mutex> lk(g_ard_mu);
   if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, full_msg);
   while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;     // tag << 8 stays a positive int
   const int t = g_ard_next;
   g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
   ArdTag& a = g_ard_tags[t];
-  a.d = d; a.ard.assign(ard, ard + d); a.grad.assign(d, 0.0); a.alpha = alpha; a.rho = rho;
+  a.d = d; a.ard.assign(ard, ard + d); a.grad.assign(d, 0.0); a.alpha = alpha; a.rho = rho; a.decay = decay;
   *tag = t;
   return LMM_OK;
 }
@@ -1412,13 +1440,22 @@ int lmm_kernel_tag_create_periodic(int d, const double* ard, double rho, int* ta
   return tag_register(d, ard, 0.0, tag, "lmm_kernel_tag_create_periodic: too many live tags", rho);
 }
 
+int lmm_kernel_tag_create_locally_periodic(int d, const double* ard, double rho, double decay, int* tag) {
+  if (d < 0 || !tag || (d == 0) != (ard == nullptr)) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create_locally_periodic: bad arguments");
+  if (!(rho > 0.0 && std::isfinite(rho))) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create_locally_periodic: rho must be finite and > 0");
+  if (!(decay > 0.0 && std::isfinite(decay))) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create_locally_periodic: decay must be finite and > 0");
+  for (int k = 0; k < d; ++k)
+    if (!(ard[k] > 0.0) || !std::isfinite(ard[k])) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_create_locally_periodic: factors must be finite and > 0");
+  return tag_register(d, ard, 0.0, tag, "lmm_kernel_tag_create_locally_periodic: too many live tags", rho, decay);
+}
+
 int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag) {
   if (nterms < 1 || nterms > LMM_SUM_MAX_TERMS || !terms || !tag)
     return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: nterms must be 1..4, terms and tag non-NULL");
   for (int c = 0; c < nterms; ++c) {
     const int base = terms[c].kind & LMM_KERNEL_BASE_MASK;
-    if (terms[c].kind < 0 || (base > LMM_KERNEL_RQ && base != LMM_KERNEL_PERIODIC))
-      return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: a term must have a base kind 0..4 or 7 (sums do not nest)");
+    if (terms[c].kind < 0 || !base_kind_ok(base))
+      return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: a term must have a base kind 0..4, 7 or 10 (sums do not nest)");
     if (!(terms[c].variance > 0.0) || !std::isfinite(terms[c].variance) || !(terms[c].lengthscale > 0.0) ||
         !std::isfinite(terms[c].lengthscale) || terms[c].mean != 0.0)
       return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term needs finite variance > 0, lengthscale > 0 and mean 0");
@@ -1432,8 +1469,8 @@ int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag) {
       return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term names an unknown tag or a sum tag");
     if (it->second.alpha > 0.0 && (terms[c].kind & LMM_KERNEL_BASE_MASK) != LMM_KERNEL_RQ)
       return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term's tag carries an RQ shape but its kind is not LMM_KERNEL_RQ");
-    if (it->second.rho > 0.0 && (terms[c].kind & LMM_KERNEL_BASE_MASK) != LMM_KERNEL_PERIODIC)
-      return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term's tag carries a periodic rho but its kind is not LMM_KERNEL_PERIODIC");
+    if (!tag_shape_fits(terms[c].kind & LMM_KERNEL_BASE_MASK, 0.0, it->second.rho, it->second.decay))
+      return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term's tag carries a rho (or a rho and a decay) its kind does not take");
   }
   if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: too many live tags");
   while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
@@ -1472,6 +1509,15 @@ int lmm_kernel_tag_rho_grad(int tag, double* out) {
   auto it = g_ard_tags.find(tag);
   if (it == g_ard_tags.end() || !(it->second.rho > 0.0)) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_rho_grad: unknown tag, or a tag without a rho");
   *out = it->second.grho;
+  return LMM_OK;
+}
+
+int lmm_kernel_tag_decay_grad(int tag, double* out) {
+  if (!out) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_decay_grad: out is NULL");
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  auto it = g_ard_tags.find(tag);
+  if (it == g_ard_tags.end() || !(it->second.decay > 0.0)) return ard_fail(LMM_ERR_ARG, "lmm_kernel_tag_decay_grad: unknown tag, or a tag without a decay");
+  *out = it->second.gdecay;
   return LMM_OK;
 }
 

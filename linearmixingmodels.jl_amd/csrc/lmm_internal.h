@@ -11,18 +11,21 @@ struct BatchInfo { int* p[LMM_MAX_BATCH]; };
 // kind: the BASE kernel kind (lmm_kernel_kind); ils: nullptr (isotropic, inv_ls) or the latent's d per-dimension inverse lengthscales
 // (device; an ARD latent, d > 1).  An ARD latent keeps inv_ls = 1 / its common multiplier (the gradient reduction's d/d multiplier).
 // alpha: the RQ shape; for a periodic latent (LMM_KERNEL_PERIODIC) the slot carries 1 / rho^2, inv_ls 1 / period and ils the
-// per-dimension 1 / P_k (unused by the other kinds).
+// per-dimension 1 / P_k (unused by the other kinds).  A locally periodic latent (LMM_KERNEL_LOCALLY_PERIODIC) is described as a periodic
+// one, plus inv_decay = 1 / (its SE lengthscale) (0 for every other kind).
 // A sum latent (kind LMM_KERNEL_SUM) has nterms (1..LMM_SUM_MAX_TERMS) resolved terms in `terms` (device): each an ordinary base-kind
 // descriptor whose var = v0 v_c, inv_ls = 1 / (s0 l_c) and ils = its per-dimension 1 / (s0 l_c ard_c[k]) (or nullptr); var and inv_ls
 // of the sum latent itself are v0 and 1 / s0.  terms is nullptr and nterms 0 for every other latent.
 struct LatentDev {
   int kind;
+  int nterms;              // (next to kind: the descriptor keeps the 64 bytes it had before inv_decay)
   double var, inv_ls, mean;
   const double* ils;
   double alpha;
   const LatentDev* terms;
-  int nterms;
+  double inv_decay;
 };
+static_assert(sizeof(LatentDev) == 64, "LatentDev is read per element by the dense and sum kernels: keep it at 64 bytes");
 
 // Gram / factor-matrix assembly arguments (see gram_kernel).
 struct GramArgs {
@@ -42,7 +45,8 @@ struct GramArgs {
   int cpw;                                     // column tiles per workgroup (set by the launcher: 4, or 1 when the grid would be small)
   double alpha;                                // RQ shape; periodic: 1 / rho^2 (unused by the other kinds)
   const LatentDev* terms; int nterms;          // kind LMM_KERNEL_SUM: the resolved terms (device; see LatentDev)
-  int sum_per;                                 // kind LMM_KERNEL_SUM: some term is periodic (the instantiation that evaluates one)
+  int sum_per;                                 // kind LMM_KERNEL_SUM: some term is periodic or locally periodic (the instantiation that evaluates one)
+  double inv_decay;                            // locally periodic: 1 / decay (unused by the other kinds)
 };
 
 // The same assembly for up to LMM_MAX_BATCH same-shaped matrices in ONE launch (blockIdx.z = matrix): everything in `base`
@@ -59,7 +63,9 @@ struct GramBatchArgs {
   double alpha[LMM_MAX_BATCH];
   const LatentDev* terms[LMM_MAX_BATCH];
   int nterms[LMM_MAX_BATCH];
+  double inv_decay[LMM_MAX_BATCH];
 };
+static_assert(sizeof(GramBatchArgs) <= 4096, "GramBatchArgs is passed by value: kernel arguments are limited to 4096 bytes");
 
 struct DenseArgs {
   double* A; int ld, nrows, ncols;
@@ -69,11 +75,11 @@ struct DenseArgs {
   const int* sig_idx;        // optional, device, n entries: which sigmaT the point's noise block uses (sequential conditioning)
   const double* rider; int rider_ld, nrider;
   int has_sum;               // 1: some lat[l] is a sum latent (the kernel instantiation that evaluates kappa_sum); 2: some latent is
-                             // periodic or has a periodic term (the instantiation that also evaluates kappa_per)
+                             // periodic or locally periodic or has such a term (the instantiation that also evaluates kappa_per / kappa_lp)
 };
 
 void launch_gram(const GramArgs& a, hipStream_t st);
-// nb same-shaped assemblies (differing only in A, kind, var, inv_ls, ils, alpha, terms, diag_add, diag_vec, rider): one launch per run of
+// nb same-shaped assemblies (differing only in A, kind, var, inv_ls, ils, alpha, inv_decay, terms, diag_add, diag_vec, rider): one launch per run of
 // equal kinds (sum latents form runs too; their terms may differ per matrix)
 void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st);
 void launch_dense_assemble(const DenseArgs& a, hipStream_t st);
@@ -193,7 +199,7 @@ void launch_syrk_upper_set(double* C, int ldc, const double* X, int ldx, int N, 
 void launch_syrk_upper_set(const BatchPtr& C, int ldc, const BatchPtr& X, int ldx, int N, int nb, hipStream_t st);
 void launch_set_identity(double* R, int ld, int nc, hipStream_t st);
 int grad_partials(int n, int d_ard = 0);      // partial-buffer elements of launch_grad_reduce (d_ard: the d of an ARD latent, else 0)
-#define LMM_NGRAD 9
+#define LMM_NGRAD 10                          // sums of one reduction: the 9 common ones and a locally periodic latent's d/d decay ([9], written for that kind only)
 #define LMM_ARD_GRAD_DMAX 32                  // widest ARD latent the gradient reduction serves (per-dimension sums in registers)
 // g.ils != nullptr (an ARD latent, d <= LMM_ARD_GRAD_DMAX): out8[0] is d/d multiplier and out_ard[k] = d/d l_k (d values)
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,

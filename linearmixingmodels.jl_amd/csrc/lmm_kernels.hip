@@ -144,6 +144,30 @@ __device__ __forceinline__ void per_sincos(double u, double& s, double& c) {
   sincospi(u, &s, &c);
 }
 
+// Locally periodic (SE x Periodic, LMM_KERNEL_LOCALLY_PERIODIC): v exp(-D2 / (2 l^2) - q / (2 rho^2)) with q as above and D2 = |a - b|^2.
+// The SE factor is one more term of the exponent, so an element still costs one exp.  The descriptor is a periodic latent's (1 / rho^2 in
+// the alpha slot, the period in inv_ls / ils) plus inv_decay = 1 / l.
+__device__ __forceinline__ double kappa_lp(double var, double irho2, double q, double inv_decay, double D2) {
+  return var * exp_nonpos(-0.5 * __builtin_fma(inv_decay * inv_decay, D2, irho2 * q));
+}
+// q and D2 by direct differences (per_q's form)
+__device__ __forceinline__ void lp_qd(const double* __restrict__ a, const double* __restrict__ b, int d, double inv_ls,
+                                      const double* __restrict__ ils, double& q, double& D2) {
+  q = 0.0; D2 = 0.0;
+  for (int k = 0; k < d; ++k) {
+    const double dx = a[k] - b[k];
+    const double s = sinpi(dx * (ils ? ils[k] : inv_ls));
+    q = __builtin_fma(s, s, q);
+    D2 = __builtin_fma(dx, dx, D2);
+  }
+}
+__device__ __forceinline__ double kappa_lp_at(double var, double irho2, double inv_decay, const double* __restrict__ a,
+                                              const double* __restrict__ b, int d, double inv_ls, const double* __restrict__ ils) {
+  double q, D2;
+  lp_qd(a, b, d, inv_ls, ils, q, D2);
+  return kappa_lp(var, irho2, q, inv_decay, D2);
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -200,9 +224,9 @@ __device__ __forceinline__ double sqrt_dist(double x) {
 // A sum latent's kernel at the pair (a, b): sum over its terms (LatentDev.terms) of kappa_c, each term with its own variance v0 v_c,
 // lengthscale and kind.  The raw difference (d == 1) or squared distance (d > 1) is computed once and scaled per isotropic term by
 // inv_ls_c (inv_ls_c^2); a term with per-dimension lengthscales (ils, d > 1 only: d == 1 terms are folded on the host) takes its own
-// pass over the d coordinates.  So does a periodic term (kappa_per), at every d; PER: the sum may hold one (PER = false
-// keeps the code and registers that sums of the other kinds always had).
-#define LMM_KERNEL_SUM_PER 8      // instantiation index of the Gram kernels for a sum latent with a periodic term (never a GramArgs.kind)
+// pass over the d coordinates.  So does a periodic or locally periodic term (kappa_per, kappa_lp), at every d; PER: the sum may hold
+// one (PER = false keeps the code and registers that sums of the other kinds always had).
+#define LMM_KERNEL_SUM_PER 8      // instantiation index of the Gram kernels for a sum latent with a periodic or locally periodic term (never a GramArgs.kind)
 template <bool PER>
 __device__ __forceinline__ double kappa_sum(const LatentDev* __restrict__ T, int nt, const double* __restrict__ a,
                                             const double* __restrict__ b, int d) {
@@ -215,6 +239,10 @@ __device__ __forceinline__ double kappa_sum(const LatentDev* __restrict__ T, int
     const LatentDev g = T[c];
     if (PER && g.kind == LMM_KERNEL_PERIODIC) {   // its own pass over the coordinates, as an ARD term
       acc += kappa_per(g.var, g.alpha, per_q(a, b, d, g.inv_ls, g.ils));
+      continue;
+    }
+    if (PER && g.kind == LMM_KERNEL_LOCALLY_PERIODIC) {   // the same pass, with the SE exponent from the shared squared distance
+      acc += kappa_lp(g.var, g.alpha, per_q(a, b, d, g.inv_ls, g.ils), g.inv_decay, d == 1 ? dx * dx : D2);
       continue;
     }
     double r, r2;
@@ -286,6 +314,8 @@ __device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int
             val = kappa_sum<KIND == LMM_KERNEL_SUM_PER>(a.terms, a.nterms, rpt[e], a.x + (size_t)j * a.d, a.d);
           } else if constexpr (KIND == LMM_KERNEL_PERIODIC) {
             val = kappa_per(a.var, a.alpha, per_q(rpt[e], a.x + (size_t)j * a.d, a.d, a.inv_ls, a.ils));
+          } else if constexpr (KIND == LMM_KERNEL_LOCALLY_PERIODIC) {
+            val = kappa_lp_at(a.var, a.alpha, a.inv_decay, rpt[e], a.x + (size_t)j * a.d, a.d, a.inv_ls, a.ils);
           } else {
             double r, r2;
             if (a.d == 1) { r = fabs(rx[e] - xj) * a.inv_ls; r2 = r * r; }
@@ -494,10 +524,15 @@ __device__ __forceinline__ void gram_body_sum(const GramArgs& a) {
 // one FMA per dimension, a scale and one exp_nonpos -- what the SE path spends.  Nothing can overflow, so there is no range guard.
 // Against the direct form the difference is the rounding of x / P: pi eps |x| / P in the angle, i.e. up to pi eps (|x| / P) / rho^2
 // relative in an element.  Border / rider / pad tiles and d > 8 take the generic tile (direct differences and sinpi).
-template <bool ND, typename TS>
+// LP (KIND = LMM_KERNEL_LOCALLY_PERIODIC): the same tiles with the SE exponent -|x_i - x_j|^2 / (2 l^2) added before the one exp_nonpos.
+// Its squared distance comes from the direct difference of the raw coordinates (the rows' in registers, the columns' staged in LDS next
+// to their sines), one subtraction and one FMA per dimension more.  LP = false is the periodic body as it always was.
+template <bool LP, bool ND, typename TS>
 __device__ __forceinline__ void gram_body_per(const GramArgs& a) {
   constexpr int DM = ND ? 8 : 1;
+  constexpr int KIND = LP ? LMM_KERNEL_LOCALLY_PERIODIC : LMM_KERNEL_PERIODIC;
   __shared__ double colS[64 * DM], colC[64 * DM];
+  __shared__ double colX[LP ? 64 * DM : 1];
   const int ti = blockIdx.x + a.row_tile0, sy = blockIdx.y;
   const int t = threadIdx.x;
   const int i0 = ti * 64 + 2 * (t & 31);
@@ -508,8 +543,13 @@ __device__ __forceinline__ void gram_body_per(const GramArgs& a) {
   else if (a.xs != nullptr && ti * 64 >= a.ncols && ti * 64 + 63 - a.ncols < a.ns) { rsrc = a.xs; rbase = a.ncols; }
   const bool rows_fast = rsrc != nullptr && (ND ? (a.d > 1 && a.d <= DM) : a.d == 1);
   double rs0[DM], rc0[DM], rs1[DM], rc1[DM];
+  [[maybe_unused]] double rx0[LP ? DM : 1], rx1[LP ? DM : 1];
 #pragma unroll
   for (int k = 0; k < DM; ++k) { rs0[k] = 0.0; rc0[k] = 0.0; rs1[k] = 0.0; rc1[k] = 0.0; }
+  if constexpr (LP) {
+#pragma unroll
+    for (int k = 0; k < DM; ++k) { rx0[k] = 0.0; rx1[k] = 0.0; }
+  }
   if (rows_fast) {
 #pragma unroll
     for (int k = 0; k < DM; ++k)
@@ -517,35 +557,48 @@ __device__ __forceinline__ void gram_body_per(const GramArgs& a) {
         const double sk = a.ils ? a.ils[k] : a.inv_ls;
         per_sincos(rsrc[(size_t)(i0 - rbase) * a.d + k] * sk, rs0[k], rc0[k]);
         per_sincos(rsrc[(size_t)(i0 + 1 - rbase) * a.d + k] * sk, rs1[k], rc1[k]);
+        if constexpr (LP) { rx0[k] = rsrc[(size_t)(i0 - rbase) * a.d + k]; rx1[k] = rsrc[(size_t)(i0 + 1 - rbase) * a.d + k]; }
       }
   }
   const double hq = -0.5 * a.alpha;                           // -1 / (2 rho^2)
+  const double hd = LP ? -0.5 * a.inv_decay * a.inv_decay : 0.0;      // -1 / (2 l^2)
   for (int c4 = 0; c4 < a.cpw; ++c4) {
     const int tj = sy * a.cpw + c4;
     if (tj * 64 >= a.ncols) break;
     if (!a.full && ti < tj) break;                            // lower tiles only
-    if (!(rows_fast && tj * 64 + 63 < a.n)) { gram_tile_generic<LMM_KERNEL_PERIODIC, TS>(a, ti, tj); continue; }
+    if (!(rows_fast && tj * 64 + 63 < a.n)) { gram_tile_generic<KIND, TS>(a, ti, tj); continue; }
     const size_t out = (size_t)(tj * 64 + cg) * a.ld + (i0 - a.row_shift);
     __syncthreads();                                          // previous tile's readers are done with colS / colC
     for (int e = t; e < 64 * a.d; e += 256) {
       const double sk = a.ils ? a.ils[ND ? e % a.d : 0] : a.inv_ls;
-      per_sincos(a.x[(size_t)tj * 64 * a.d + e] * sk, colS[e], colC[e]);
+      const double xe = a.x[(size_t)tj * 64 * a.d + e];
+      per_sincos(xe * sk, colS[e], colC[e]);
+      if constexpr (LP) colX[e] = xe;
     }
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int jl = cg + 8 * q;
-      double q0 = 0.0, q1 = 0.0;
+      double q0 = 0.0, q1 = 0.0, D0 = 0.0, D1 = 0.0;
 #pragma unroll
       for (int k = 0; k < DM; ++k)
         if (k < a.d) {
           const double cs = colS[jl * a.d + k], cc = colC[jl * a.d + k];
           const double s0 = __builtin_fma(rs0[k], cc, -rc0[k] * cs), s1 = __builtin_fma(rs1[k], cc, -rc1[k] * cs);
           q0 = __builtin_fma(s0, s0, q0); q1 = __builtin_fma(s1, s1, q1);
+          if constexpr (LP) {
+            const double cx = colX[jl * a.d + k], d0 = rx0[k] - cx, d1 = rx1[k] - cx;
+            D0 = __builtin_fma(d0, d0, D0); D1 = __builtin_fma(d1, d1, D1);
+          }
         }
       d2 v;
-      v.x = a.var * exp_nonpos(hq * q0);
-      v.y = a.var * exp_nonpos(hq * q1);
+      if constexpr (LP) {
+        v.x = a.var * exp_nonpos(__builtin_fma(hd, D0, hq * q0));
+        v.y = a.var * exp_nonpos(__builtin_fma(hd, D1, hq * q1));
+      } else {
+        v.x = a.var * exp_nonpos(hq * q0);
+        v.y = a.var * exp_nonpos(hq * q1);
+      }
       if (ti == tj) {
         const int j = tj * 64 + jl;
         const double da = a.diag_add + (a.diag_vec ? a.diag_vec[j] : 0.0);
@@ -561,7 +614,7 @@ template <int KIND, bool ND, typename TS>
 __global__ __launch_bounds__(256) void gram_kernel(GramArgs a) {
   if (a.info_zero && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.info_zero = 0;
   if constexpr (KIND == LMM_KERNEL_SUM || KIND == LMM_KERNEL_SUM_PER) gram_body_sum<KIND, TS>(a);
-  else if constexpr (KIND == LMM_KERNEL_PERIODIC) gram_body_per<ND, TS>(a);
+  else if constexpr (KIND == LMM_KERNEL_PERIODIC || KIND == LMM_KERNEL_LOCALLY_PERIODIC) gram_body_per<KIND == LMM_KERNEL_LOCALLY_PERIODIC, ND, TS>(a);
   else gram_body<KIND, ND, TS>(a);
 }
 
@@ -575,7 +628,10 @@ __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
     a.terms = b.terms[z]; a.nterms = b.nterms[z];
     gram_body_sum<KIND, TS>(a);
   } else if constexpr (KIND == LMM_KERNEL_PERIODIC) {
-    gram_body_per<ND, TS>(a);
+    gram_body_per<false, ND, TS>(a);
+  } else if constexpr (KIND == LMM_KERNEL_LOCALLY_PERIODIC) {
+    a.inv_decay = b.inv_decay[z];
+    gram_body_per<true, ND, TS>(a);
   } else {
     gram_body<KIND, ND, TS>(a);
   }
@@ -585,7 +641,7 @@ __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
 // element (i, j), i = li*n + ii, j = lj*n + jj  ->  [li == lj] kappa_li(x_ii, x_jj) + [ii == jj] SigmaT[li, lj].
 // Reference: src/ilmm.jl:160 kron(SigmaT, I) + src/independent_mogp.jl:60-63 BlockDiagonal.  A sum latent (LatentDev.terms) takes kappa_sum here and
 // in dense_cross_kernel; its var is kappa(0) = v0 sum_c v_c in these arrays (dense_var_kernel reads it).
-// SUM = 1: some latent is a sum; 2: some latent is periodic or has a periodic term (0 and 1 keep the code and registers they always had)
+// SUM = 1: some latent is a sum; 2: some latent is periodic or locally periodic or has such a term (0 and 1 keep the code and registers they always had)
 template <typename TS, int SUM>
 __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
   const int ti = blockIdx.x, tj = blockIdx.y;
@@ -615,6 +671,8 @@ __global__ __launch_bounds__(256) void ilmm_dense_assemble_kernel(DenseArgs a) {
             const LatentDev g = a.lat[lj];
             if (SUM == 2 && g.kind == LMM_KERNEL_PERIODIC) {
               val = kappa_per(g.var, g.alpha, per_q(a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d, g.inv_ls, g.ils));
+            } else if (SUM == 2 && g.kind == LMM_KERNEL_LOCALLY_PERIODIC) {
+              val = kappa_lp_at(g.var, g.alpha, g.inv_decay, a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d, g.inv_ls, g.ils);
             } else if (SUM && g.kind == LMM_KERNEL_SUM) {
               val = kappa_sum<SUM == 2>(g.terms, g.nterms, a.x + (size_t)ii[e] * a.d, a.x + (size_t)jj * a.d, a.d);
             } else {
@@ -655,6 +713,8 @@ __global__ __launch_bounds__(256) void dense_cross_kernel(void* __restrict__ R, 
       const LatentDev g = lat[l];
       if (SUM == 2 && g.kind == LMM_KERNEL_PERIODIC) {
         val = kappa_per(g.var, g.alpha, per_q(xs + (size_t)s * d, x + (size_t)jj * d, d, g.inv_ls, g.ils));
+      } else if (SUM == 2 && g.kind == LMM_KERNEL_LOCALLY_PERIODIC) {
+        val = kappa_lp_at(g.var, g.alpha, g.inv_decay, xs + (size_t)s * d, x + (size_t)jj * d, d, g.inv_ls, g.ils);
       } else if (SUM && g.kind == LMM_KERNEL_SUM) {
         val = kappa_sum<SUM == 2>(g.terms, g.nterms, xs + (size_t)s * d, x + (size_t)jj * d, d);
       } else {
@@ -3367,7 +3427,8 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restr
 // ---------------------------------------------------------------------------------------------------
 // Latent mean at xs from the weights:  mean[s] = mu + sum_i kappa(xs_s, x_i) alpha_i   (cross-Gram fused with the GEMV;
 // never materialised).  The i range is cut into chunks of ichunk (blockIdx.y) whose partial sums strip_finish_kernel adds.
-// EXT = 1: a Matern12 / RQ latent, 2: a periodic latent (the three original kinds keep the instantiation they always had).
+// EXT = 1: a Matern12 / RQ latent, 2: a periodic latent, 3: a locally periodic one (the three original kinds keep the instantiation
+// they always had).
 // ---------------------------------------------------------------------------------------------------
 template <int EXT>
 __global__ __launch_bounds__(256) void post_mean_kernel(const double* __restrict__ xs, int ns,
@@ -3395,6 +3456,11 @@ __global__ __launch_bounds__(256) void post_mean_kernel(const double* __restrict
           acc = __builtin_fma(kappa_per(g.var, g.alpha, sn * sn), xa[256 + k], acc);
           continue;
         }
+        if constexpr (EXT == 3) {
+          const double dx = xv - xa[k], sn = sinpi(dx * g.inv_ls);
+          acc = __builtin_fma(kappa_lp(g.var, g.alpha, sn * sn, g.inv_decay, dx * dx), xa[256 + k], acc);
+          continue;
+        }
         const double r = fabs(xv - xa[k]) * g.inv_ls;
         acc = __builtin_fma(EXT ? kappa(g.kind, g.var, r, r * r, g.alpha) : kappa(g.kind, g.var, r, r * r), xa[256 + k], acc);
       }
@@ -3403,6 +3469,10 @@ __global__ __launch_bounds__(256) void post_mean_kernel(const double* __restrict
     for (int i = ibeg; i < iend; ++i) {
       if constexpr (EXT == 2) {
         acc = __builtin_fma(kappa_per(g.var, g.alpha, per_q(xs + (size_t)s * d, x + (size_t)i * d, d, g.inv_ls, g.ils)), alpha[i], acc);
+        continue;
+      }
+      if constexpr (EXT == 3) {
+        acc = __builtin_fma(kappa_lp_at(g.var, g.alpha, g.inv_decay, xs + (size_t)s * d, x + (size_t)i * d, d, g.inv_ls, g.ils), alpha[i], acc);
         continue;
       }
       const double r2 = scaled_dist2(xs + (size_t)s * d, x + (size_t)i * d, d, g.inv_ls, g.ils);
@@ -3597,6 +3667,9 @@ __device__ __forceinline__ void rq_pair(double var, double alpha, double r2, dou
 //     d kap / d x_ik = -kap u_k / P_k,  u_k = pi sin(2 pi t_k) / (2 rho^2) = (pi / rho^2) s_k c_k;          d kap / d rho = kap q / rho^3.
 // The kernels are bound by the read of Kinv, so sincospi is called per pair and dimension.  The rho sum takes the partial slot alpha
 // takes for RQ ([8]); g.alpha holds 1 / rho^2.
+// Locally periodic pairs (EXT = 3): kap = v exp(-q / (2 rho^2) - D2 / (2 l^2)), D2 = sum_k (x_ik - x_jk)^2.  The periodic formulas hold with
+// this kap, and in addition  d kap / d l = kap D2 / l^3  and  d kap / d x_ik = -kap (u_k / P_k + (x_ik - x_jk) / l^2).  The decay sum has a
+// partial slot of its own behind the LMM_NG common ones ([LMM_NG]; the per-dimension sums of the ARD kernel follow it); g.inv_decay = 1 / l.
 #define LMM_PI 3.141592653589793
 __device__ __forceinline__ double per_rho3(double irho2) { return irho2 * sqrt(irho2); }     // 1 / rho^3
 
@@ -3623,7 +3696,8 @@ __device__ __forceinline__ void ext_pair(const LatentDev& g, double r, double r2
 // The split at nsplit serves the predictive logpdf (joint of training and test points, each block with its own noise).
 #define LMM_NG 9
 // TS: storage type of the inverse Kinv (a MATRIX: Float32 in the fp32 compute mode); all sums in Float64.  EXT: a Matern12 / RQ latent
-// (the three original kinds keep the instantiation, and the register budget, they always had); EXT = 2: a periodic latent.
+// (the three original kinds keep the instantiation, and the register budget, they always had); EXT = 2: a periodic latent; EXT = 3: a
+// locally periodic one, whose tiles hold LMM_NG + 1 partials.
 template <typename TS, int EXT>
 __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict__ Kinv, int ld, int n, int nsplit,
                                                           const double* __restrict__ alpha, const double* __restrict__ delta,
@@ -3635,12 +3709,32 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
   const int t = threadIdx.x;
   const int i0 = ti * 64 + (t & 63);
   const int cg = t >> 6;
+  constexpr int NG = EXT == 3 ? LMM_NG + 1 : LMM_NG;
   double acc = 0.0, acck = 0.0, acca = 0.0;
+  [[maybe_unused]] double accd = 0.0;
   if (i0 < n) {
     const double ai = alpha[i0];
     for (int q = 0; q < 16; ++q) {
       const int j = tj * 64 + cg + 4 * q;
       if (j < i0 && j < n) {
+        if constexpr (EXT == 3) {
+          double qq = 0.0, pp = 0.0, DD = 0.0;
+          for (int k = 0; k < d; ++k) {
+            const double dx = x[(size_t)i0 * d + k] - x[(size_t)j * d + k], tk = dx * g.inv_ls;
+            double sn, cs;
+            sincospi(tk, &sn, &cs);
+            qq = __builtin_fma(sn, sn, qq);
+            pp = __builtin_fma(tk, sn * cs, pp);
+            DD = __builtin_fma(dx, dx, DD);
+          }
+          const double w = ai * alpha[j] - MatIO<TS>::ld1(Kinv, (size_t)j * ld + i0);
+          const double wk = w * kappa_lp(g.var, g.alpha, qq, g.inv_decay, DD);
+          acc = __builtin_fma(wk, pp, acc);
+          acck += wk;
+          acca = __builtin_fma(wk, qq, acca);
+          accd = __builtin_fma(wk, DD, accd);
+          continue;
+        }
         if constexpr (EXT == 2) {
           double qq = 0.0, pp = 0.0;
           for (int k = 0; k < d; ++k) {
@@ -3675,10 +3769,12 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
     }
   }
   const int tile = ti * nt + tj;
-  if (EXT == 2) { acc *= LMM_PI * g.alpha * g.inv_ls; acca *= per_rho3(g.alpha); }
+  if (EXT >= 2) { acc *= LMM_PI * g.alpha * g.inv_ls; acca *= per_rho3(g.alpha); }
   const double tl = block_sum_256(acc, sh);
   const double tk = block_sum_256(acck, sh);
-  const double ta = (EXT == 2 || (EXT && g.kind == LMM_KERNEL_RQ)) ? block_sum_256(acca, sh) : 0.0;     // (g.kind is uniform: the barrier is too)
+  const double ta = (EXT >= 2 || (EXT && g.kind == LMM_KERNEL_RQ)) ? block_sum_256(acca, sh) : 0.0;     // (g.kind is uniform: the barrier is too)
+  [[maybe_unused]] double td = 0.0;
+  if constexpr (EXT == 3) td = block_sum_256(accd * (g.inv_decay * g.inv_decay * g.inv_decay), sh);
   double tra = 0.0, aaa = 0.0, trb = 0.0, aab = 0.0, ad = 0.0, sa = 0.0;
   if (ti == tj && t < 64 && i0 < n) {
     const double ai = alpha[i0], kii = MatIO<TS>::ld1(Kinv, (size_t)i0 * ld + i0);
@@ -3688,8 +3784,9 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
   const double s1 = block_sum_256(tra, sh), s2 = block_sum_256(aaa, sh), s3 = block_sum_256(ad, sh), s4 = block_sum_256(sa, sh);
   const double s5 = block_sum_256(trb, sh), s6 = block_sum_256(aab, sh);
   if (t == 0) {
-    double* o = partial + (size_t)LMM_NG * tile;
+    double* o = partial + (size_t)NG * tile;
     o[0] = tl; o[1] = s1; o[2] = s2; o[3] = s3; o[4] = s4; o[5] = s5; o[6] = s6; o[7] = tk; o[8] = ta;
+    if constexpr (EXT == 3) o[LMM_NG] = td;
   }
 }
 
@@ -3702,6 +3799,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
 // sum_{i>j in tile} w_ij d kappa_ij / d l_k.  Kinv is read once per tile, as in the isotropic kernel; the d extra FMAs per pair (and,
 // for DK <= 8, the t_k^2 kept in registers) leave the kernel bound by that read.  All sums of a tile are reduced with ONE barrier.
 // EXT = 2 (periodic): r2 is q and alpha 1 / rho^2;  wh = w kap, acca += w kap q, and acc0 is left to the caller (sum_k wh p_k).
+// EXT = 3 (locally periodic) does not come here: lp_pair below.
 template <int DK, int EXT>
 __device__ __forceinline__ void ard_pair(int kind, double var, double alpha, double r2, double w, double& acc0, double& acck,
                                          double& acca, double& wh) {
@@ -3738,12 +3836,22 @@ __device__ __forceinline__ void ard_pair(int kind, double var, double alpha, dou
   acck = __builtin_fma(w, kap, acck);
 }
 
+// Locally periodic pair: wh = w kap with the SE factor in kap; the decay sum accd += w kap D2.
+__device__ __forceinline__ void lp_pair(const LatentDev& g, double q, double D2, double w, double& acck, double& acca, double& accd,
+                                        double& wh) {
+  wh = w * kappa_lp(g.var, g.alpha, q, g.inv_decay, D2);
+  acck += wh;
+  acca = __builtin_fma(wh, q, acca);
+  accd = __builtin_fma(wh, D2, accd);
+}
+
 template <typename TS, int DK, int EXT>
 __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __restrict__ Kinv, int ld, int n, int nsplit,
                                                               const double* __restrict__ alpha, const double* __restrict__ delta,
                                                               const double* __restrict__ x, int d, LatentDev g, int nt,
                                                               double* __restrict__ partial) {
-  constexpr int NV = LMM_NG + DK;
+  constexpr int NG = EXT == 3 ? LMM_NG + 1 : LMM_NG;     // locally periodic: the decay sum at [LMM_NG], the per-dimension sums behind it
+  constexpr int NV = NG + DK;
   constexpr bool KEEP = DK <= 8;                  // keep t_k^2 in registers between the distance and the accumulation
   __shared__ double sils[DK];
   __shared__ double red[4][NV];
@@ -3755,11 +3863,12 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
   const int i0 = ti * 64 + (t & 63);
   const int cg = t >> 6;
   double acc0 = 0.0, acck = 0.0, acca = 0.0, acc[DK], xi[DK];
+  [[maybe_unused]] double accd = 0.0;
 #pragma unroll
   for (int k = 0; k < DK; ++k) { acc[k] = 0.0; xi[k] = 0.0; }
   if (i0 < n) {
 #pragma unroll
-    for (int k = 0; k < DK; ++k) if (k < d) xi[k] = x[(size_t)i0 * d + k] * sils[k];
+    for (int k = 0; k < DK; ++k) if (k < d) xi[k] = (EXT == 3) ? x[(size_t)i0 * d + k] : x[(size_t)i0 * d + k] * sils[k];      // EXT = 3: raw (D2 needs the difference)
     const double ai = alpha[i0];
     for (int q = 0; q < 16; ++q) {
       const int j = tj * 64 + cg + 4 * q;
@@ -3767,11 +3876,14 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
         const double* xj = x + (size_t)j * d;
         double t2[KEEP ? DK : 1];
         double r2 = 0.0;
+        [[maybe_unused]] double D2 = 0.0;
 #pragma unroll
         for (int k = 0; k < DK; ++k)
           if (k < d) {
-            const double tk = xi[k] - xj[k] * sils[k];
-            if constexpr (EXT == 2) {              // t2[k] <- t_k s_k c_k (p_k without its constant), r2 <- q
+            double tk;
+            if constexpr (EXT == 3) { const double dx = xi[k] - xj[k]; D2 = __builtin_fma(dx, dx, D2); tk = dx * sils[k]; }
+            else tk = xi[k] - xj[k] * sils[k];
+            if constexpr (EXT >= 2) {              // t2[k] <- t_k s_k c_k (p_k without its constant), r2 <- q
               double sn, cs;
               sincospi(tk, &sn, &cs);
               if (KEEP) t2[k] = tk * (sn * cs);
@@ -3783,19 +3895,20 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
           }
         const double w = ai * alpha[j] - MatIO<TS>::ld1(Kinv, (size_t)j * ld + i0);
         double wh;
-        ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, acc0, acck, acca, wh);
+        if constexpr (EXT == 3) lp_pair(g, r2, D2, w, acck, acca, accd, wh);
+        else ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, acc0, acck, acca, wh);
 #pragma unroll
         for (int k = 0; k < DK; ++k)
           if (k < d) {
             double tk2;
             if (KEEP) tk2 = t2[k];
             else {
-              const double tk = xi[k] - xj[k] * sils[k];
-              if constexpr (EXT == 2) { double sn, cs; sincospi(tk, &sn, &cs); tk2 = tk * (sn * cs); }
+              const double tk = (EXT == 3) ? (xi[k] - xj[k]) * sils[k] : xi[k] - xj[k] * sils[k];
+              if constexpr (EXT >= 2) { double sn, cs; sincospi(tk, &sn, &cs); tk2 = tk * (sn * cs); }
               else tk2 = tk * tk;
             }
             acc[k] = __builtin_fma(wh, tk2, acc[k]);
-            if constexpr (EXT == 2) acc0 = __builtin_fma(wh, tk2, acc0);
+            if constexpr (EXT >= 2) acc0 = __builtin_fma(wh, tk2, acc0);
           }
       }
     }
@@ -3809,13 +3922,14 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
   const int lane = t & 63, wv = t >> 6;
   double v[NV];
   v[0] = acc0 * g.inv_ls; v[1] = tra; v[2] = aaa; v[3] = ad; v[4] = sa; v[5] = trb; v[6] = aab; v[7] = acck; v[8] = acca;
+  if constexpr (EXT == 3) v[LMM_NG] = accd * (g.inv_decay * g.inv_decay * g.inv_decay);
 #pragma unroll
-  for (int k = 0; k < DK; ++k) v[LMM_NG + k] = acc[k] * sils[k];
-  if constexpr (EXT == 2) {
+  for (int k = 0; k < DK; ++k) v[NG + k] = acc[k] * sils[k];
+  if constexpr (EXT >= 2) {
     const double pc = LMM_PI * g.alpha;
     v[0] *= pc; v[8] *= per_rho3(g.alpha);
 #pragma unroll
-    for (int k = 0; k < DK; ++k) v[LMM_NG + k] *= pc;
+    for (int k = 0; k < DK; ++k) v[NG + k] *= pc;
   }
 #pragma unroll
   for (int c = 0; c < NV; ++c) {
@@ -3823,14 +3937,14 @@ __global__ __launch_bounds__(256) void grad_reduce_ard_kernel(const void* __rest
     if (lane == 0) red[wv][c] = sc;
   }
   __syncthreads();
-  const int ngs = LMM_NG + d;
+  const int ngs = NG + d;
   if (t < ngs) partial[(size_t)ngs * (ti * nt + tj) + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
 }
 
-// out[c] = sum over the nt*nt tile partials of component c (c < LMM_NG; the partials hold ngs >= LMM_NG components per tile, the
-// ones from LMM_NG on go to out_ard); upper tiles were never written -> skip them.
+// out[c] = sum over the nt*nt tile partials of component c (c < nout: LMM_NG, or LMM_NG + 1 for a locally periodic latent; the partials
+// hold ngs >= nout components per tile, the ones from nout on go to out_ard); upper tiles were never written -> skip them.
 __global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restrict__ partial, int nt, double* __restrict__ out, int ngs,
-                                                          double* __restrict__ out_ard) {
+                                                          double* __restrict__ out_ard, int nout) {
   __shared__ double sh[4];
   for (int c = 0; c < ngs; ++c) {
     double s = 0.0;
@@ -3839,7 +3953,7 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(const double* __restri
       if (ti >= tj) s += partial[(size_t)ngs * k + c];
     }
     const double tot = block_sum_256(s, sh);
-    if (threadIdx.x == 0) { if (c < LMM_NG) out[c] = tot; else out_ard[c - LMM_NG] = tot; }
+    if (threadIdx.x == 0) { if (c < nout) out[c] = tot; else out_ard[c - nout] = tot; }
   }
 }
 
@@ -3858,10 +3972,12 @@ template <typename TS, int DK, int EXT>
 __global__ __launch_bounds__(256) void grad_x_kernel(const void* __restrict__ Kinv, int ld, int n, const double* __restrict__ alpha,
                                                      const double* __restrict__ x, int d, LatentDev g, double* __restrict__ partial) {
   __shared__ double sils[DK];
+  __shared__ double sdec[EXT == 3 ? DK : 1];     // locally periodic: P_k / l^2, so that -sils[k] (u_k + dx_k sdec[k]) is d kap / d x_ik / kap
   __shared__ double tl[64][65];                  // staged transposed tile; then the cross-quarter sums
   const int ti = blockIdx.x, c = blockIdx.y, nt = (n + 63) / 64;
   const int t = threadIdx.x, il = t & 63, cg = t >> 6;
   if (t < DK) sils[t] = (t < d) ? (g.ils ? g.ils[t] : g.inv_ls) : 0.0;
+  if constexpr (EXT == 3) { if (t < DK) sdec[t] = (t < d) ? g.inv_decay * g.inv_decay / (g.ils ? g.ils[t] : g.inv_ls) : 0.0; }
   __syncthreads();
   const int i = ti * 64 + il;
   const bool ok = i < n;
@@ -3889,20 +4005,24 @@ __global__ __launch_bounds__(256) void grad_x_kernel(const void* __restrict__ Ki
         else kij = (tj > ti || jl > il) ? tl[il][jl] : tl[jl][il];
         const double* xj = x + (size_t)j * d;
         double tk[DK], r2 = 0.0;
+        [[maybe_unused]] double D2 = 0.0;
 #pragma unroll
         for (int k = 0; k < DK; ++k) {
           tk[k] = (k < d) ? (xi[k] - xj[k]) * sils[k] : 0.0;     // difference first: exactly 0 at coincident points
-          if constexpr (EXT == 2) {                              // tk[k] <- u_k, r2 <- q
+          [[maybe_unused]] const double dx = (k < d) ? xi[k] - xj[k] : 0.0;
+          if constexpr (EXT >= 2) {                              // tk[k] <- u_k, r2 <- q
             double sn, cs;
             sincospi(tk[k], &sn, &cs);
             tk[k] = (LMM_PI * g.alpha) * (sn * cs);
             r2 = __builtin_fma(sn, sn, r2);
+            if constexpr (EXT == 3) { tk[k] = __builtin_fma(dx, sdec[k], tk[k]); D2 = __builtin_fma(dx, dx, D2); }
           } else
           r2 = __builtin_fma(tk[k], tk[k], r2);
         }
         const double w = ai * alpha[j] - kij;
         double a0 = 0.0, ak = 0.0, aa = 0.0, wh;
-        ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, a0, ak, aa, wh);      // only wh = w h(r) is used
+        if constexpr (EXT == 3) lp_pair(g, r2, D2, w, ak, aa, a0, wh);
+        else ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, a0, ak, aa, wh);      // only wh = w h(r) is used
 #pragma unroll
         for (int k = 0; k < DK; ++k) acc[k] = __builtin_fma(wh, tk[k], acc[k]);
       }
@@ -4069,10 +4189,12 @@ __global__ __launch_bounds__(256) void pred_grad_x_kernel(const double* __restri
                                                           double* __restrict__ partial) {
   constexpr int JS = DK > 8 ? 128 : 256;        // training points per LDS stage (DK = 32: 32 KiB of coordinates)
   __shared__ double sils[DK];
+  __shared__ double sdec[EXT == 3 ? DK : 1];    // locally periodic: P_k / l^2 (grad_x_kernel)
   __shared__ double sx[JS * DK];
   __shared__ double sa[JS];
   const int t = threadIdx.x, s = blockIdx.x * 256 + t, c = blockIdx.y;
   if (t < DK) sils[t] = (t < d) ? (g.ils ? g.ils[t] : g.inv_ls) : 0.0;
+  if constexpr (EXT == 3) { if (t < DK) sdec[t] = (t < d) ? g.inv_decay * g.inv_decay / (g.ils ? g.ils[t] : g.inv_ls) : 0.0; }
   const bool ok = s < ns;
   double xv[DK], acc[DK];
 #pragma unroll
@@ -4092,20 +4214,24 @@ __global__ __launch_bounds__(256) void pred_grad_x_kernel(const double* __restri
 #pragma unroll UNR
     for (int jl = 0; jl < nj; ++jl) {
       double tk[DK], r2 = 0.0;
+      [[maybe_unused]] double D2 = 0.0;
 #pragma unroll
       for (int k = 0; k < DK; ++k) {
         tk[k] = (k < d) ? (xv[k] - sx[jl * DK + k]) * sils[k] : 0.0;     // difference first: exactly 0 at coincident points
-        if constexpr (EXT == 2) {                                        // tk[k] <- u_k, r2 <- q
+        [[maybe_unused]] const double dx = (k < d) ? xv[k] - sx[jl * DK + k] : 0.0;
+        if constexpr (EXT >= 2) {                                        // tk[k] <- u_k, r2 <- q
           double sn, cs;
           sincospi(tk[k], &sn, &cs);
           tk[k] = (LMM_PI * g.alpha) * (sn * cs);
           r2 = __builtin_fma(sn, sn, r2);
+          if constexpr (EXT == 3) { tk[k] = __builtin_fma(dx, sdec[k], tk[k]); D2 = __builtin_fma(dx, dx, D2); }
         } else
         r2 = __builtin_fma(tk[k], tk[k], r2);
       }
       const double w = VAR ? __builtin_fma(vb2, wp[(size_t)jl * ldw], mb * sa[jl]) : mb * sa[jl];
       double a0 = 0.0, ak = 0.0, aa = 0.0, wh;
-      ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, a0, ak, aa, wh);      // only wh = w h(r) is used
+      if constexpr (EXT == 3) lp_pair(g, r2, D2, w, ak, aa, a0, wh);
+      else ard_pair<DK, EXT>(g.kind, g.var, g.alpha, r2, w, a0, ak, aa, wh);      // only wh = w h(r) is used
 #pragma unroll
       for (int k = 0; k < DK; ++k) acc[k] = __builtin_fma(wh, tk[k], acc[k]);
     }
@@ -4271,6 +4397,7 @@ void launch_gram(const GramArgs& a0, hipStream_t st) {
   else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
   else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
   else if (a.kind == LMM_KERNEL_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_PERIODIC);
+  else if (a.kind == LMM_KERNEL_LOCALLY_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_LOCALLY_PERIODIC);
   else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
 #undef LMM_GRAM_LAUNCH
 }
@@ -4286,10 +4413,11 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     for (int j = j0; j < j1; ++j) {
       const GramArgs& a = args[j];
       b.A[j - j0] = a.A; b.var[j - j0] = a.var; b.inv_ls[j - j0] = a.inv_ls; b.ils[j - j0] = a.ils; b.alpha[j - j0] = a.alpha; b.diag_add[j - j0] = a.diag_add;
+      b.inv_decay[j - j0] = a.inv_decay;
       b.terms[j - j0] = a.terms; b.nterms[j - j0] = a.nterms;
       b.diag_vec[j - j0] = a.diag_vec; b.rider[j - j0] = a.rider; b.rider_sub[j - j0] = a.rider_sub; b.info_zero[j - j0] = a.info_zero;
     }
-    for (int j = j0; j < j1; ++j) b.base.sum_per |= args[j].sum_per;       // one sum of the run has a periodic term: that instantiation for all
+    for (int j = j0; j < j1; ++j) b.base.sum_per |= args[j].sum_per;       // one sum of the run has a periodic or locally periodic term: that instantiation for all
     b.base.cpw = gram_cpw(b.base.nrows / 64 - b.base.row_tile0, b.base.ncols / 64, j1 - j0);
     const GramArgs& a = b.base;
     dim3 grid(a.nrows / 64 - a.row_tile0, (a.ncols / 64 + a.cpw - 1) / a.cpw, j1 - j0);
@@ -4306,6 +4434,7 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
     else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
     else if (a.kind == LMM_KERNEL_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_PERIODIC);
+    else if (a.kind == LMM_KERNEL_LOCALLY_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_LOCALLY_PERIODIC);
     else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
 #undef LMM_GRAM_LAUNCH
     j0 = j1;
@@ -4840,7 +4969,8 @@ void launch_post_mean(const double* xs, int ns, const double* x, int n, int d, c
     return;
   }
   const int ic = post_mean_ichunk(n), nch = (n + ic - 1) / ic, nsp = (ns + 255) / 256 * 256;
-  if (g.kind == LMM_KERNEL_PERIODIC) hipLaunchKernelGGL(post_mean_kernel<2>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  if (g.kind == LMM_KERNEL_LOCALLY_PERIODIC) hipLaunchKernelGGL(post_mean_kernel<3>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  else if (g.kind == LMM_KERNEL_PERIODIC) hipLaunchKernelGGL(post_mean_kernel<2>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
   else if (g.kind >= LMM_KERNEL_MATERN12) hipLaunchKernelGGL(post_mean_kernel<1>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
   else hipLaunchKernelGGL(post_mean_kernel<0>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
   hipLaunchKernelGGL(strip_finish_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, partial, nsp, nch, 1, ns, 0, g.mean, 0.0,
@@ -4880,18 +5010,28 @@ void launch_set_identity(double* R, int ld, int nc, hipStream_t st) {
   LMM_TS_LAUNCH((set_identity_kernel<TS>), dim3((nc + 255) / 256, nc), dim3(256), 0, st, (void*)R, ld, nc);
 }
 
-int grad_partials(int n, int d_ard) { const int nt = (n + 63) / 64; return (LMM_NG + d_ard) * nt * nt; }
+int grad_partials(int n, int d_ard) { const int nt = (n + 63) / 64; return (LMM_NG + 1 + d_ard) * nt * nt; }      // + 1: a locally periodic latent's decay sum
+
+// The EXT instantiation of the gradient kernels: 1 Matern12 / RQ, 2 periodic, 3 locally periodic
+static int grad_ext(int kind) {
+  if (kind == LMM_KERNEL_LOCALLY_PERIODIC) return 3;
+  if (kind == LMM_KERNEL_PERIODIC) return 2;
+  return kind >= LMM_KERNEL_MATERN12 ? 1 : 0;
+}
 
 // out (LMM_NGRAD values): [dl/d ell, tr Kinv (rows < nsplit), a.a (rows < nsplit), a.delta, sum a, tr Kinv (rows >= nsplit),
-//        a.a (rows >= nsplit), sum_{i>j} (a_i a_j - Kinv_ij) K_ij, dl/d alpha (RQ; 0 otherwise)]
+//        a.a (rows >= nsplit), sum_{i>j} (a_i a_j - Kinv_ij) K_ij, dl/d alpha (RQ) or dl/d rho (periodic kinds; 0 otherwise),
+//        dl/d decay (written for a locally periodic latent only)]
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,
                         LatentDev g, double* partial, double* out7, hipStream_t st, double* out_ard) {
   const int nt = (n + 63) / 64;
-  const int ext = g.kind == LMM_KERNEL_PERIODIC ? 2 : (g.kind >= LMM_KERNEL_MATERN12 ? 1 : 0);      // Matern12 / RQ, periodic: the EXT instantiations
+  const int ext = grad_ext(g.kind);
+  const int nout = ext == 3 ? LMM_NG + 1 : LMM_NG;
   if (g.ils != nullptr) {          // ARD latent (the caller guarantees 1 < d <= LMM_ARD_GRAD_DMAX and out_ard != nullptr)
 #define LMM_ARD_LAUNCH(DK)                                                                                                      \
     do {                                                                                                                        \
-      if (ext == 2) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 2>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
+      if (ext == 3) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 3>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
+      else if (ext == 2) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 2>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
       else if (ext) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 1>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
       else LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 0>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
     } while (0)
@@ -4899,13 +5039,14 @@ void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const dou
     else if (d <= 8) LMM_ARD_LAUNCH(8);
     else LMM_ARD_LAUNCH(LMM_ARD_GRAD_DMAX);
 #undef LMM_ARD_LAUNCH
-    hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG + d, out_ard);
+    hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, nout + d, out_ard, nout);
     return;
   }
-  if (ext == 2) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 2>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  if (ext == 3) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 3>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  else if (ext == 2) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 2>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
   else if (ext) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 1>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
   else LMM_TS_LAUNCH((grad_reduce_kernel<TS, 0>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
-  hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, LMM_NG, (double*)nullptr);
+  hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, nout, (double*)nullptr, nout);
 }
 
 size_t grad_x_partial_elems(int n, int d) { const int nt = (n + 63) / 64; return (size_t)((nt + LMM_GX_CHUNK - 1) / LMM_GX_CHUNK) * n * d; }
@@ -4913,10 +5054,11 @@ size_t grad_x_partial_elems(int n, int d) { const int nt = (n + 63) / 64; return
 void launch_grad_x(const double* Kinv, int ld, int n, const double* alpha, const double* x, int d, LatentDev g, double* partial,
                    double* gx, bool accumulate, hipStream_t st) {
   const int nt = (n + 63) / 64, nch = (nt + LMM_GX_CHUNK - 1) / LMM_GX_CHUNK;
-  const int ext = g.kind == LMM_KERNEL_PERIODIC ? 2 : (g.kind >= LMM_KERNEL_MATERN12 ? 1 : 0);
+  const int ext = grad_ext(g.kind);
 #define LMM_GX_LAUNCH(DK)                                                                                                      \
   do {                                                                                                                        \
-    if (ext == 2) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 2>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
+    if (ext == 3) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 3>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
+    else if (ext == 2) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 2>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
     else if (ext) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 1>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
     else LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 0>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
   } while (0)
@@ -4999,7 +5141,7 @@ void launch_pred_grad_x(const double* xs, int ns, const double* x, int n, int d,
                         const double* vbar, const double* W, int ldw, LatentDev g, double* partial, double* gx, bool accumulate,
                         hipStream_t st) {
   const int chunk = pred_grad_chunk(n), nch = (n + chunk - 1) / chunk;
-  const int ext = g.kind == LMM_KERNEL_PERIODIC ? 2 : (g.kind >= LMM_KERNEL_MATERN12 ? 1 : 0);
+  const int ext = grad_ext(g.kind);
   const bool var = W != nullptr;
   const dim3 grid((ns + 255) / 256, nch);
 #define LMM_PGX_LAUNCH(DK, EXT)                                                                                                   \
@@ -5009,7 +5151,7 @@ void launch_pred_grad_x(const double* xs, int ns, const double* x, int n, int d,
     else hipLaunchKernelGGL((pred_grad_x_kernel<DK, EXT, false>), grid, dim3(256), 0, st, xs, ns, x, n, d, chunk, alpha, mbar,    \
                             vbar, W, ldw, g, partial);                                                                            \
   } while (0)
-#define LMM_PGX_DK(DK) do { if (ext == 2) LMM_PGX_LAUNCH(DK, 2); else if (ext) LMM_PGX_LAUNCH(DK, 1); else LMM_PGX_LAUNCH(DK, 0); } while (0)
+#define LMM_PGX_DK(DK) do { if (ext == 3) LMM_PGX_LAUNCH(DK, 3); else if (ext == 2) LMM_PGX_LAUNCH(DK, 2); else if (ext) LMM_PGX_LAUNCH(DK, 1); else LMM_PGX_LAUNCH(DK, 0); } while (0)
   if (d == 1) LMM_PGX_DK(1);
   else if (d <= 4) LMM_PGX_DK(4);
   else if (d <= 8) LMM_PGX_DK(8);

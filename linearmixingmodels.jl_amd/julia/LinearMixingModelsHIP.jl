@@ -125,6 +125,32 @@ function _rho(k::PeriodicKernel)
 end
 _rho(k::ScaledKernel) = _rho(k.kernel)
 _rho(k::TransformedKernel) = _rho(k.kernel)
+# Locally periodic kernels: the ONE KernelProduct that is served, SqExponentialKernel * PeriodicKernel in either order (kind 10,
+# LMM_KERNEL_LOCALLY_PERIODIC).  The SE factor may sit under a ScaleTransform (1 / decay), the periodic factor under a ScaleTransform or
+# ARDTransform (1 / period); the product itself may sit under ScaledKernel / ScaleTransform (which then scales the period AND the decay)
+# and inside a KernelSum.  rho and the decay travel in one tag (lmm_kernel_tag_create_locally_periodic).  Everything else is refused.
+const _SEFactor = Union{SqExponentialKernel,TransformedKernel{<:SqExponentialKernel,<:ScaleTransform}}
+const _PerFactor = Union{PeriodicKernel,TransformedKernel{<:PeriodicKernel,<:ScaleTransform},TransformedKernel{<:PeriodicKernel,<:ARDTransform}}
+_product_refused(k) = error("LinearMixingModelsHIP: this KernelProduct is not served (only SqExponentialKernel * PeriodicKernel, " *
+                            "each optionally under a ScaleTransform, the periodic factor also under an ARDTransform): $(k)")
+function _lpfactors(k::KernelProduct)      # (SE factor, periodic factor)
+    ks = k.kernels
+    length(ks) == 2 || _product_refused(k)
+    (a, b) = (ks[1], ks[2])
+    a isa _SEFactor && b isa _PerFactor && return (a, b)
+    b isa _SEFactor && a isa _PerFactor && return (b, a)
+    _product_refused(k)
+end
+_desc(k::KernelProduct) = ((_, per) = _lpfactors(k); (Cint(10), 1.0, _desc(per)[3]))
+_desc(k::TransformedKernel{<:KernelProduct,<:ARDTransform}) =
+    error("LinearMixingModelsHIP: an ARDTransform around a whole KernelProduct is not served (a per-dimension decay; put it on the periodic factor)")
+_ard(k::KernelProduct) = _ard(_lpfactors(k)[2])
+_rho(k::KernelProduct) = _rho(_lpfactors(k)[2])
+# the decay (the SE factor's lengthscale) of a locally periodic product; nothing for the other kernels
+_decay(k::Kernel) = nothing
+_decay(k::KernelProduct) = Float64(_desc(_lpfactors(k)[1])[3])
+_decay(k::ScaledKernel) = _decay(k.kernel)
+_decay(k::TransformedKernel{<:Kernel,<:ScaleTransform}) = (δ = _decay(k.kernel); δ === nothing ? nothing : δ / only(k.transform.s))
 # Sum kernels (KernelFunctions' KernelSum, k1 + k2): kind 5 with a sum tag (lmm_kernel_sum_create).  `_desc` of the sum is (5, 1, 1), so
 # a ScaledKernel / ScaleTransform around it gives the latent's outer variance v0 and lengthscale s0; each term is read with the
 # single-kernel methods above.  A nested sum with unit outer variance and lengthscale is flattened; any other is rejected, as is an
@@ -161,13 +187,18 @@ struct KTag
     ard::Bool      # the tag holds per-dimension factors
     alpha::Bool    # the tag holds an RQ shape
     rho::Bool      # the tag holds a periodic kernel's rho (its gradient travels in the `alpha` field of the gradient tuples)
+    decay::Bool    # the tag holds a locally periodic kernel's rho and decay (the `alpha` field is then the tuple (rho = , decay = ))
     terms::Vector{KTag}   # a sum tag: its terms' tags (empty otherwise)
 end
-KTag(id, ard, alpha, rho::Bool=false) = KTag(id, ard, alpha, rho, KTag[])
+KTag(id, ard, alpha, rho::Bool=false, decay::Bool=false) = KTag(id, ard, alpha, rho, decay, KTag[])
 # the factor / alpha tag of one kernel (a latent's or a sum term's); 0: none needed
-function _ktag(a, α, ρ=nothing)
+function _ktag(a, α, ρ=nothing, δ=nothing)
     tr = Ref{Cint}(0)
-    if ρ !== nothing
+    if δ !== nothing
+        av = a === nothing ? Float64[] : a
+        GC.@preserve av check(ccall((:lmm_kernel_tag_create_locally_periodic, liblmm), Cint, (Cint, Ptr{Cdouble}, Cdouble, Cdouble, Ref{Cint}),
+                                    length(av), a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(av), ρ, δ, tr))
+    elseif ρ !== nothing
         av = a === nothing ? Float64[] : a
         GC.@preserve av check(ccall((:lmm_kernel_tag_create_periodic, liblmm), Cint, (Cint, Ptr{Cdouble}, Cdouble, Ref{Cint}),
                                     length(av), a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(av), ρ, tr))
@@ -191,23 +222,23 @@ function _gps(body, fs)
             (kd, v, l) = _desc(f.kernel)
             if kd == 5
                 tts = KTag[]; tgps = LmmGp[]
-                push!(tags, KTag(Cint(0), false, false, false, tts))    # registered first, so that the finally destroys the term tags on error
+                push!(tags, KTag(Cint(0), false, false, false, false, tts))    # registered first, so that the finally destroys the term tags on error
                 for k in _terms(f.kernel)
-                    (tk, tv, tl) = _desc(k); a = _ard(k); α = _alpha(k); ρ = _rho(k)
-                    t = _ktag(a, α, ρ)
-                    push!(tts, KTag(t, a !== nothing, α !== nothing, ρ !== nothing))
+                    (tk, tv, tl) = _desc(k); a = _ard(k); α = _alpha(k); ρ = _rho(k); δ = _decay(k)
+                    t = _ktag(a, α, ρ, δ)
+                    push!(tts, KTag(t, a !== nothing, α !== nothing, ρ !== nothing, δ !== nothing))
                     push!(tgps, LmmGp(t == 0 ? tk : tk | (t << 8), tv, tl, 0.0))
                 end
                 tr = Ref{Cint}(0)
                 GC.@preserve tgps check(ccall((:lmm_kernel_sum_create, liblmm), Cint, (Cint, Ptr{LmmGp}, Ref{Cint}),
                                               length(tgps), pointer(tgps), tr))
-                tags[end] = KTag(tr[], false, false, false, tts)
+                tags[end] = KTag(tr[], false, false, false, false, tts)
                 push!(gps, LmmGp(kd | (tr[] << 8), v, l, _mean(f.mean)))
                 continue
             end
-            a = _ard(f.kernel); α = _alpha(f.kernel); ρ = _rho(f.kernel)
-            t = _ktag(a, α, ρ)
-            push!(tags, KTag(t, a !== nothing, α !== nothing, ρ !== nothing))
+            a = _ard(f.kernel); α = _alpha(f.kernel); ρ = _rho(f.kernel); δ = _decay(f.kernel)
+            t = _ktag(a, α, ρ, δ)
+            push!(tags, KTag(t, a !== nothing, α !== nothing, ρ !== nothing, δ !== nothing))
             push!(gps, LmmGp(t == 0 ? kd : kd | (t << 8), v, l, _mean(f.mean)))
         end
         return body(gps, tags)
@@ -216,9 +247,16 @@ function _gps(body, fs)
     end
 end
 # after a gradient call inside _gps, per latent: nothing (no tag) or (ard = d logpdf / d ard[k] (lmm_ard_grad) or nothing,
-# alpha = d logpdf / d alpha (lmm_kernel_tag_alpha_grad), of a periodic latent d logpdf / d rho (lmm_kernel_tag_rho_grad), or nothing)
+# alpha = d logpdf / d alpha (lmm_kernel_tag_alpha_grad), of a periodic latent d logpdf / d rho (lmm_kernel_tag_rho_grad), of a locally
+# periodic one (rho = that, decay = d logpdf / d decay (lmm_kernel_tag_decay_grad)), or nothing)
 # A sum latent: (ard = nothing, alpha = nothing, terms = per term (variance, lengthscale, ard, alpha) from lmm_kernel_sum_grad and
 # the terms' own tags).
+function _rho_decay_grads(id)
+    ρ = Ref{Cdouble}(0.0); δ = Ref{Cdouble}(0.0)
+    check(ccall((:lmm_kernel_tag_rho_grad, liblmm), Cint, (Cint, Ref{Cdouble}), id, ρ))
+    check(ccall((:lmm_kernel_tag_decay_grad, liblmm), Cint, (Cint, Ref{Cdouble}), id, δ))
+    return (rho = ρ[], decay = δ[])
+end
 function _tag_grads(t::KTag, d::Integer)
     t.id == 0 && return nothing
     terms = nothing
@@ -235,6 +273,7 @@ function _tag_grads(t::KTag, d::Integer)
                            GC.@preserve g check(ccall((:lmm_ard_grad, liblmm), Cint, (Cint, Ptr{Cdouble}), t.id, g)); g) : nothing,
             alpha = t.alpha ? (r = Ref{Cdouble}(0.0);
                                check(ccall((:lmm_kernel_tag_alpha_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) :
+                    t.decay ? _rho_decay_grads(t.id) :
                     t.rho ? (r = Ref{Cdouble}(0.0);
                              check(ccall((:lmm_kernel_tag_rho_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) : nothing,
             terms = terms)
@@ -701,7 +740,8 @@ AbstractGPs.var(f::HIPMOGP, x::MOIsotopic) = _mean_var(f, x)[2]
 # kernel's construction: ScaledKernel: v = v_inner σ² -> d/dσ² = gv v_inner; ScaleTransform: ℓ = ℓ_inner / s -> d/ds = -gl ℓ_inner / s².
 # ga: d/d ard[k] of an ARD latent (lmm_ard_grad; gl is then d/d the common multiplier).  ARDTransform(v): ard = ard_inner ./ v
 # -> d/dv_k = -ga_k ard_inner_k / v_k^2 (with no inner factors, ℓ_k = multiplier / v_k: d/dv_k = -ℓ_k^2 d/dℓ_k), d/d ard_inner = ga ./ v.
-# gα: d/d alpha of an RQ latent (lmm_kernel_tag_alpha_grad), d/d rho of a periodic one (lmm_kernel_tag_rho_grad), nothing otherwise
+# gα: d/d alpha of an RQ latent (lmm_kernel_tag_alpha_grad), d/d rho of a periodic one (lmm_kernel_tag_rho_grad), the tuple
+# (rho = d/d rho, decay = d/d decay) of a locally periodic one (lmm_kernel_tag_decay_grad), nothing otherwise
 # gt: the per-term gradients of a sum latent (_tag_grads(...).terms), nothing otherwise.
 _ktangent(k::Kernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) = NoTangent()            # SEKernel() etc. carry no parameters
 _ktangent(k::RationalQuadraticKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) =
@@ -716,7 +756,21 @@ function _ktangent(k::ScaledKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing)
 end
 function _ktangent(k::TransformedKernel{<:Kernel,<:ScaleTransform}, gv, gl, ga=nothing, gα=nothing, gt=nothing)
     (_, _, lin) = _desc(k.kernel); s = only(k.transform.s)
-    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl / s, ga, gα, gt), transform=Tangent{typeof(k.transform)}(; s=[-gl * lin / s^2]))
+    gs = -gl * lin / s^2
+    if gα isa NamedTuple          # a locally periodic product inside: the transform scales its decay too (decay = decay_inner / s)
+        gs -= gα.decay * _decay(k.kernel) / s^2
+        gα = (rho = gα.rho, decay = gα.decay / s)
+    end
+    return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv, gl / s, ga, gα, gt), transform=Tangent{typeof(k.transform)}(; s=[gs]))
+end
+# The locally periodic product: gα = (rho, decay).  The periodic factor takes (gl, ga, rho) as a periodic latent would, the SE factor the
+# decay cotangent as the lengthscale gradient of its ScaleTransform (a bare SqExponentialKernel carries no parameter); gv belongs to the
+# ScaledKernel around the product.
+function _ktangent(k::KernelProduct, gv, gl, ga=nothing, gα=nothing, gt=nothing)
+    (se, per) = _lpfactors(k)
+    tper = _ktangent(per, 0.0, gl, ga, gα === nothing ? nothing : gα.rho)
+    tse = _ktangent(se, 0.0, gα === nothing ? 0.0 : gα.decay)
+    return Tangent{typeof(k)}(; kernels=Tuple(t === se ? tse : tper for t in k.kernels))
 end
 # A sum: the outer (gv, gl) went to the ScaledKernel / ScaleTransform around it; each term gets its own tangent from gt, in the
 # flattened order of _terms.  A nested sum (flattened because its wrappers have unit scale) takes the next entries; its wrappers see
@@ -748,14 +802,17 @@ _mtangent(::AbstractGPs.ZeroMean, g) = NoTangent()
 _mtangent(m::AbstractGPs.ConstMean, g) = Tangent{typeof(m)}(; c=g)
 # gard: nothing, or per latent the tag gradients of _ard_grads (nothing for an untagged latent)
 _tagfield(gard, l, s) = (gard === nothing || gard[l] === nothing) ? nothing : getfield(gard[l], s)
+_scaleα(Δ, ::Nothing) = nothing
+_scaleα(Δ, g::Real) = Δ * g
+_scaleα(Δ, g::NamedTuple) = map(x -> Δ * x, g)          # (rho, decay) of a locally periodic latent
 _fstangent(fs::Vector{<:AbstractGP}, gg::Vector{LmmGpGrad}, Δ, gard=nothing) =
     [Tangent{typeof(f)}(; mean=_mtangent(f.mean, Δ * g.mean),
                           kernel=_ktangent(f.kernel, Δ * g.variance, Δ * g.lengthscale,
                                            (ga = _tagfield(gard, l, :ard); ga === nothing ? nothing : Δ .* ga),
-                                           (gα = _tagfield(gard, l, :alpha); gα === nothing ? nothing : Δ * gα),
+                                           _scaleα(Δ, _tagfield(gard, l, :alpha)),
                                            (gt = _tagfield(gard, l, :terms); gt === nothing ? nothing :
                                             [(variance = Δ * t.variance, lengthscale = Δ * t.lengthscale,
-                                              ard = t.ard === nothing ? nothing : Δ .* t.ard, alpha = t.alpha === nothing ? nothing : Δ * t.alpha)
+                                              ard = t.ard === nothing ? nothing : Δ .* t.ard, alpha = _scaleα(Δ, t.alpha))
                                              for t in gt])))
      for (l, (f, g)) in enumerate(zip(fs, gg))]
 _noise_tangent(fx, g) = Tangent{typeof(fx.Σy)}(; diag=Tangent{typeof(fx.Σy.diag)}(; value=g))     # Fill(σ², n p): one parameter

@@ -56,6 +56,18 @@ class _Kernel:
             return NotImplemented
         return KernelSum(self, o)
 
+    def __mul__(self, o):
+        """k1 * k2: only SEKernel * PeriodicKernel (either order), the locally periodic kernel; see LocallyPeriodicKernel."""
+        if not isinstance(o, _Kernel):
+            return NotImplemented
+        se, per = (self, o) if type(self) is SEKernel else (o, self)
+        if type(se) is not SEKernel or type(per) is not PeriodicKernel:
+            raise NotImplementedError("the only product kernel served is SEKernel * PeriodicKernel (LocallyPeriodicKernel); "
+                                      f"got {type(self).__name__} * {type(o).__name__}")
+        if not isinstance(se.lengthscale, float):
+            raise ValueError("SEKernel * PeriodicKernel needs a scalar SE lengthscale (a per-dimension decay is not supported)")
+        return LocallyPeriodicKernel(se.variance * per.variance, per.lengthscale, per.r, se.lengthscale)
+
     def desc(self) -> dict:
         """Descriptor of this kernel (a latent's, or a term's of a sum kernel)."""
         d = {"kind": self.kind, "variance": self.variance, "lengthscale": self.lengthscale}
@@ -63,10 +75,14 @@ class _Kernel:
             d["alpha"] = self.alpha
         if hasattr(self, "r"):
             d["r"] = self.r
+        if hasattr(self, "decay"):
+            d["decay"] = self.decay
         return d
 
     def key(self) -> tuple:
         """Hashable form of the kernel's values (the latent-array cache key)."""
+        if hasattr(self, "decay"):
+            return (self.kind, self.variance, _ls_key(self.lengthscale), None, self.r, self.decay)
         if hasattr(self, "r"):
             return (self.kind, self.variance, _ls_key(self.lengthscale), None, self.r)
         return (self.kind, self.variance, _ls_key(self.lengthscale), getattr(self, "alpha", None))
@@ -139,6 +155,29 @@ class PeriodicKernel(_Kernel):
 
     def __repr__(self):
         return super().__repr__()[:-1] + f", r={self.r})"
+
+
+class LocallyPeriodicKernel(PeriodicKernel):
+    """variance * exp(-|x - x'|^2 / (2 decay^2) - sum_k sin^2(pi (x_k - x'_k) / period_k) / (2 r^2)): the locally periodic (quasi-periodic)
+    kernel, KernelFunctions' (SEKernel() o ScaleTransform(1 / decay)) * (PeriodicKernel(; r) o ScaleTransform(1 / period)); also what
+    SEKernel(v1, decay) * PeriodicKernel(v2, period, r) returns (variance v1 v2).  `lengthscale` is the period (float or length-d vector,
+    alias `.period`) and `r` as for PeriodicKernel; `decay` is the SE lengthscale, one positive finite scalar.  It is a base kernel (the
+    one product the library serves), so it may be a term of a KernelSum, whose outer lengthscale then scales the period and the decay."""
+    kind = "locally_periodic"
+
+    def __init__(self, variance: float = 1.0, lengthscale=1.0, r=1.0, decay: float = 1.0):
+        super().__init__(variance, lengthscale, r)
+        if np.ndim(decay) != 0:
+            raise ValueError("decay must be one scalar (a per-dimension decay is not supported)")
+        self.decay = float(decay)
+        if not (self.decay > 0.0 and np.isfinite(self.decay)):
+            raise ValueError("decay must be finite and > 0")
+
+    def __eq__(self, o):
+        return super().__eq__(o) and self.decay == o.decay
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", decay={self.decay})"
 
 
 class KernelSum(_Kernel):
@@ -628,6 +667,8 @@ def _gps_grads(gg, ga, m: int, d: int) -> list:
             out[-1]["alpha"] = ga.ard.alpha_grad(l)
         if ga.ard.has_rho[l]:
             out[-1]["r"] = ga.ard.rho_grad(l)
+        if ga.ard.has_decay[l]:
+            out[-1]["decay"] = ga.ard.decay_grad(l)
     return out
 
 
