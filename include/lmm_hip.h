@@ -536,6 +536,53 @@ int lmm_oilmm_post_logpdf(const lmm_post_t* post, const double* U, const double*
                           double sigma2, const double* xs, int d, int ns, const double* ys,
                           int with_regulariser, double* out);
 
+/* ---- missing observations (NaN in y) ----------------------------------------------------------
+ * The reference's notebook (examples/oilmm_and_ilmm.ipynb) says: "Heterotopic and missing data (semi-heterotopic) are not supported
+ * yet ... using the missing data techniques identified in the paper".  These entry points are that technique, the diagonal approximation of Bruinsma et al.
+ * 2020 (the OILMM paper) for missing data.  An entry of y is missing iff it is NaN (+-Inf is data).  With H = U sqrt(S) and, for point
+ * t, O_t its observed outputs, p_t = |O_t|, H_t = H[O_t, :], G_t = H_t' H_t (m x m):
+ *     z_t = G_t^-1 H_t' y_t[O_t];   latent l sees the pseudo-observation z_t[l] at x_t with noise variance sigma2 (G_t^-1)_ll;
+ *     r_t = -1/2 [(p_t - m) log(2 pi sigma2) + log det G_t + |y_t[O_t] - H_t z_t|^2 / sigma2];
+ *     logpdf = sum_l log N(z_{.,l}; mean_l, K_l + diag_t(sigma2 (G_t^-1)_ll)) + sum_t r_t      (with_regulariser switches sum_t r_t).
+ * N(y_t | H_t x, sigma2 I) = N(z_t | x, sigma2 G_t^-1) exp(r_t) is exact; the one approximation is dropping the off-diagonal of
+ * G_t^-1, so the value is exact whenever every G_t is diagonal.  Without NaN, G_t = S and every formula is that of lmm_oilmm_logpdf
+ * (reference src/oilmm.jl:20-30, 101-113), evaluated by other arithmetic (agreement to rounding, not bitwise).
+ * Points with equal O_t share one pattern: a device kernel writes one ceil(p / 64)-word mask per point, only those words reach the
+ * host (y may be a device pointer and is never downloaded), and the m x m work is done once per pattern.
+ * Refusals: a point with p_t < m (p_t = 0 included: drop such points before the call) -> LMM_ERR_UNSUPPORTED; a G_t that is not
+ * positive definite although p_t >= m -> LMM_ERR_NOT_PD; both report the 0-based index of the first such point in
+ * lmm_last_error_detail's `info` (latent = -1).  m > 128 -> LMM_ERR_UNSUPPORTED.  This stage is Float64 in both compute dtypes.
+ * Not served with NaN: lmm_post_condition, the predictive logpdf (NaN ys), matrix Y (_multi), dense-H ILMM, IndependentMOGP, rand.
+ *   lmm_missing_patterns : host-only (no lmm_init): groups the n points of y_host (n x p) by their mask, numbering the patterns by
+ *                    first appearance: pattern_of_point[t] (n ints), *npatterns, *n_observed = sum_t p_t; any output may be NULL.
+ *                    Gives the p_t < m refusal above.
+ *   lmm_oilmm_project_missing : the front end alone: z_out[t + l n] = z_t[l] - means[l] (means NULL: 0), noise_out[t + l n] =
+ *                    sigma2 (G_t^-1)_ll (both n x m, host or device, may be NULL), *reg_out = sum_t r_t, *npatterns_out.
+ *                    y, z_out and noise_out may be host or device pointers; U, S and means are host arrays (as everywhere).
+ *   All four device entry points return LMM_ERR_ARG for an S[l] that is not finite and > 0.
+ *   lmm_oilmm_logpdf_missing, lmm_oilmm_posterior_create_missing : the arguments and shard semantics of lmm_oilmm_logpdf and
+ *                    lmm_oilmm_posterior_create; the handle is an ordinary one (every prediction entry point, and sequential
+ *                    conditioning on complete further data, work on it).
+ *   lmm_oilmm_logpdf_grad_missing : value and gradients with respect to the observed entries of y (grad_y: n*p, exactly 0 at the
+ *                    missing entries), sigma2 and each latent's parameters (tags, sums, ARD, alpha, rho and decay exactly as in
+ *                    lmm_oilmm_logpdf_grad).  It has NO grad_S, grad_U or grad_x arguments: derivatives through the per-point
+ *                    projection with respect to the mixing matrix and the inputs are not built.  Any grad pointer may be NULL. */
+int lmm_missing_patterns(const double* y_host, int n, int p, int m, int* pattern_of_point, int* npatterns, int* n_observed);
+int lmm_oilmm_project_missing(const double* y, int n, int p, const double* U, const double* S, int m, double sigma2,
+                              const double* means, double* z_out, double* noise_out, double* reg_out, int* npatterns_out);
+int lmm_oilmm_logpdf_missing(const double* x, int d, int n, const double* y, int p,
+                             const double* U, const double* S, int m, double sigma2,
+                             const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                             double* out);
+int lmm_oilmm_posterior_create_missing(const double* x, int d, int n, const double* y, int p,
+                                       const double* U, const double* S, int m, double sigma2,
+                                       const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                       lmm_post_t** out);
+int lmm_oilmm_logpdf_grad_missing(const double* x, int d, int n, const double* y, int p,
+                                  const double* U, const double* S, int m, double sigma2,
+                                  const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                  double* out_logpdf, double* grad_y, double* grad_sigma2, lmm_gp_grad_t* grad_gps);
+
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard
  * normals in the reference's draw order: z_lat = m blocks of ns (latent order), eps = ns*p (by-outputs),

@@ -27,6 +27,7 @@ SYMBOLS = [
     "lmm_comm_destroy",
     "lmm_set_strict_progress", "lmm_get_strict_progress", "lmm_dev_claim_scramble", "lmm_orthogonal_validate", "lmm_oilmm_logpdf", "lmm_oilmm_logpdf_grad", "lmm_oilmm_post_logpdf_grad", "lmm_oilmm_post_logpdf_grad_seq", "lmm_ilmm_logpdf_grad", "lmm_ilmm_post_logpdf_grad", "lmm_ilmm_post_logpdf_grad_seq", "lmm_ilmm_post_latent_logpdf_grad_seq", "lmm_oilmm_logpdf_grad_x", "lmm_oilmm_post_logpdf_grad_seq_x", "lmm_ilmm_logpdf_grad_x",
     "lmm_ilmm_post_logpdf_grad_seq_x", "lmm_ilmm_post_latent_logpdf_grad_seq_x", "lmm_oilmm_logpdf_multi", "lmm_reorder", "lmm_ilmm_logpdf", "lmm_ilmm_logpdf_ex", "lmm_ilmm_logpdf_multi", "lmm_mogp_logpdf", "lmm_mogp_logpdf_diag",
+    "lmm_missing_patterns", "lmm_oilmm_project_missing", "lmm_oilmm_logpdf_missing", "lmm_oilmm_posterior_create_missing", "lmm_oilmm_logpdf_grad_missing",
     "lmm_oilmm_posterior_create", "lmm_mogp_posterior_create", "lmm_post_condition", "lmm_ilmm_posterior_create", "lmm_post_destroy", "lmm_ilmm_post_latent_view", "lmm_ilmm_post_mean_and_var", "lmm_ilmm_post_mean_and_cov", "lmm_ilmm_post_condition", "lmm_ilmm_post_logpdf", "lmm_ilmm_post_rand",
     "lmm_latent_marginals", "lmm_oilmm_mean_and_var", "lmm_oilmm_mean_and_var_grad_xs", "lmm_lmm_mean_and_cov", "lmm_mogp_cross_cov", "lmm_oilmm_post_logpdf", "lmm_lmm_rand", "lmm_lmm_rand_multi", "lmm_normals",
     "lmm_profile_begin", "lmm_profile_end",

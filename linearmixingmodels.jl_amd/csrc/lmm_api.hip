@@ -25,6 +25,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "lmm_internal.h"
@@ -3054,6 +3055,330 @@ int lmm_post_condition(const lmm_post_t* post, const double* U, const double* S,
     launch_fill(nv.p + (size_t)k * n + n1, n2, ST[l0 + k], st0);
   }
   return posterior_create_common(xall.p, d, n, P->ls, ST.data(), l0, l1, delta.p, out, nv.p);
+  LMM_CATCH
+}
+
+// ------------------------------------------------------------------------------------------------
+// missing observations (NaN in y): the diagonal approximation of the OILMM paper (Bruinsma et al. 2020) for missing data, which
+// the reference's notebook names as not yet supported ("Heterotopic and missing data ... are not supported yet").  DESIGN.md 4.15.
+// Per point t with observed outputs O_t: H_t = H[O_t, :], G_t = H_t' H_t, z_t = G_t^-1 H_t' y_t[O_t]; latent l sees z_t[l] with noise
+// sigma2 (G_t^-1)_ll; the regulariser gains -1/2 [(p_t - m) log(2 pi sigma2) + log det G_t + |y_t[O_t] - H_t z_t|^2 / sigma2].
+// ------------------------------------------------------------------------------------------------
+// Groups the points' masks (nw words each) into patterns numbered by first appearance.  A point with fewer than m observed outputs
+// is refused (LMM_ERR_UNSUPPORTED, the 0-based point index in the error detail's `info`).
+static int missing_group(const unsigned long long* masks, int n, int m, int nw, std::vector<int>& pat_of,
+                         std::vector<unsigned long long>& pmask, std::vector<int>& first_point, long long* n_observed) {
+  std::unordered_map<std::string, int> seen;
+  pat_of.resize(n); pmask.clear(); first_point.clear();
+  long long tot = 0;
+  for (int t = 0; t < n; ++t) {
+    const unsigned long long* mk = masks + (size_t)t * nw;
+    int pt = 0;
+    for (int w = 0; w < nw; ++w) pt += __builtin_popcountll(mk[w]);
+    if (pt < m) {
+      g.err_latent = -1; g.err_info = t;
+      if (pt == 0) return fail(LMM_ERR_UNSUPPORTED, "missing data: point %d has no observed output (drop it before the call)", t);
+      return fail(LMM_ERR_UNSUPPORTED, "missing data: point %d observes %d outputs, fewer than the m = %d latent processes", t, pt, m);
+    }
+    tot += pt;
+    const auto ins = seen.emplace(std::string(reinterpret_cast<const char*>(mk), (size_t)nw * sizeof(unsigned long long)), (int)first_point.size());
+    if (ins.second) { pmask.insert(pmask.end(), mk, mk + nw); first_point.push_back(t); }
+    pat_of[t] = ins.first->second;
+  }
+  if (n_observed) *n_observed = tot;
+  return LMM_OK;
+}
+
+int lmm_missing_patterns(const double* y_host, int n, int p, int m, int* pattern_of_point, int* npatterns, int* n_observed) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!y_host || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  const int nw = (p + 63) / 64;
+  std::vector<unsigned long long> masks((size_t)n * nw, 0ull);
+  for (int o = 0; o < p; ++o)
+    for (int t = 0; t < n; ++t) {
+      const double v = y_host[t + (size_t)o * n];
+      if (v == v) masks[(size_t)t * nw + (o >> 6)] |= 1ull << (o & 63);
+    }
+  std::vector<int> pat_of, first_point;
+  std::vector<unsigned long long> pmask;
+  long long tot = 0;
+  if (int rc = missing_group(masks.data(), n, m, nw, pat_of, pmask, first_point, &tot)) return rc;
+  if (pattern_of_point) std::copy(pat_of.begin(), pat_of.end(), pattern_of_point);
+  if (npatterns) *npatterns = (int)first_point.size();
+  if (n_observed) *n_observed = (int)std::min<long long>(tot, 2147483647LL);
+  return LMM_OK;
+}
+
+// Device state of the front end for one call: the patterns, their projections and the per-latent pseudo-observations of the shard.
+struct MissingFront {
+  int npat = 0;
+  Buf<int> pat_of;
+  Buf<unsigned long long> pmask;
+  Buf<double> Hd, Tpat, dinv, z, nv, resid;      // z, nv: [latent of the shard][n] (z - mean, sigma2 (G_t^-1)_ll); resid: n x p or empty
+  double rss = 0.0, sum_pt = 0.0, sum_logdet = 0.0;
+  // sum_t r_t
+  double reg(int n, int m, double s2) const {
+    return -0.5 * ((sum_pt - (double)n * m) * std::log(2.0 * M_PI * s2) + sum_logdet + rss / s2);
+  }
+};
+
+// yd: n x p (device; NaN = missing, never downloaded: only the n * nw mask words are).  means: m host values or nullptr.  Returns with
+// streams[0] drained.  A G_t that is not positive definite: LMM_ERR_NOT_PD with the first such point in the detail's `info`.
+static int missing_front(const double* yd, int n, int p, const double* U, const double* S, int m, double s2, const double* means,
+                         int l0, int l1, bool want_resid, MissingFront& F) {
+  if (m > LMM_MISSING_MMAX) return fail(LMM_ERR_UNSUPPORTED, "missing data is served for m <= %d latent processes (m = %d)", LMM_MISSING_MMAX, m);
+  hipStream_t st0 = g.streams[0];
+  const int nw = (p + 63) / 64, ms = l1 - l0;
+  Buf<unsigned long long> masks((size_t)n * nw);
+  Buf<int> pt(n);
+  launch_missing_masks(yd, n, p, masks.p, pt.p, st0);
+  std::vector<unsigned long long> hmasks((size_t)n * nw), pmask;
+  HIPCHK(hipMemcpyAsync(hmasks.data(), masks.p, hmasks.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  std::vector<int> pat_of, first_point;
+  if (int rc = missing_group(hmasks.data(), n, m, nw, pat_of, pmask, first_point, nullptr)) return rc;
+  const int npat = (int)first_point.size();
+  F.npat = npat;
+  F.pat_of = Buf<int>(n); F.pmask = Buf<unsigned long long>(pmask.size());
+  HIPCHK(hipMemcpyAsync(F.pat_of.p, pat_of.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st0));
+  HIPCHK(hipMemcpyAsync(F.pmask.p, pmask.data(), pmask.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st0));
+  std::vector<double> Hh((size_t)p * m);
+  for (int l = 0; l < m; ++l) {
+    const double rs = std::sqrt(S[l]);
+    for (int o = 0; o < p; ++o) Hh[o + (size_t)l * p] = U[o + (size_t)l * p] * rs;          // reference src/orthogonal_matrix.jl:27-30
+  }
+  F.Hd = Buf<double>(Hh.size());
+  HIPCHK(hipMemcpyAsync(F.Hd.p, Hh.data(), Hh.size() * sizeof(double), hipMemcpyHostToDevice, st0));
+  Buf<double> meansd(m);
+  if (means) HIPCHK(hipMemcpyAsync(meansd.p, means, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st0));
+  F.Tpat = Buf<double>((size_t)npat * m * p); F.dinv = Buf<double>((size_t)npat * m);
+  F.z = Buf<double>((size_t)n * std::max(ms, 1)); F.nv = Buf<double>((size_t)n * std::max(ms, 1));
+  if (want_resid) F.resid = Buf<double>((size_t)n * p);
+  Buf<double> scratch(missing_pattern_scratch_elems(m, npat)), logdet(npat), part(3 * (size_t)n), sums(3);
+  Buf<int> info(npat);
+  launch_missing_patterns(F.Hd.p, p, m, F.pmask.p, npat, scratch.p, F.Tpat.p, F.dinv.p, logdet.p, info.p, st0);
+  launch_missing_apply(yd, n, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, F.dinv.p, logdet.p, pt.p, F.Hd.p, s2, means ? meansd.p : nullptr,
+                       l0, l1, F.z.p, F.nv.p, want_resid ? F.resid.p : nullptr, part.p, sums.p, st0);
+  std::vector<int> hinfo(npat);
+  double hs[3] = {0.0, 0.0, 0.0};
+  HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, (size_t)npat * sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipMemcpyAsync(hs, sums.p, sizeof hs, hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  for (int q = 0; q < npat; ++q)
+    if (hinfo[q] != 0) {       // patterns are numbered by first appearance: this is the first point with a singular G_t
+      g.err_latent = -1; g.err_info = first_point[q];
+      return fail(LMM_ERR_NOT_PD, "PosDefException: H_t' H_t of point %d is not positive definite over its observed outputs (pivot %d)",
+                  first_point[q], hinfo[q]);
+    }
+  F.rss = hs[0]; F.sum_pt = hs[1]; F.sum_logdet = hs[2];
+  return LMM_OK;
+}
+
+#define LMM_MISSING_ARGCHECK(extra)                                                                                              \
+  if (!y || !U || !S || (extra) || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");                        \
+  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");                                                          \
+  if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");                                                          \
+  for (int l_ = 0; l_ < m; ++l_)                                                                                                 \
+    if (!(S[l_] > 0.0) || !std::isfinite(S[l_])) return fail(LMM_ERR_ARG, "S must be finite and > 0 (S[%d] = %g)", l_, S[l_])
+
+int lmm_oilmm_project_missing(const double* y, int n, int p, const double* U, const double* S, int m, double sigma2,
+                              const double* means, double* z_out, double* noise_out, double* reg_out, int* npatterns_out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  LMM_MISSING_ARGCHECK(false);
+  hipStream_t st0 = g.streams[0];
+  DevIn yd(y, (size_t)n * p, st0);
+  MissingFront F;
+  if (int rc = missing_front(yd.p, n, p, U, S, m, sigma2, means, 0, m, false, F)) return rc;
+  DevOut zo(z_out, (size_t)n * m), no(noise_out, (size_t)n * m);
+  if (z_out) HIPCHK(hipMemcpyAsync(zo.p, F.z.p, (size_t)n * m * sizeof(double), hipMemcpyDeviceToDevice, st0));
+  if (noise_out) HIPCHK(hipMemcpyAsync(no.p, F.nv.p, (size_t)n * m * sizeof(double), hipMemcpyDeviceToDevice, st0));
+  zo.finish(st0); no.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  if (reg_out) *reg_out = F.reg(n, m, sigma2);
+  if (npatterns_out) *npatterns_out = F.npat;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_oilmm_logpdf_missing(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m,
+                             double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  LMM_MISSING_ARGCHECK(!x || !out || d <= 0);
+  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
+  RESOLVE(gps, m, d);
+  hipStream_t st0 = g.streams[0];
+  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
+  std::vector<double> means(m);
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  MissingFront F;
+  if (int rc = missing_front(yd.p, n, p, U, S, m, sigma2, means.data(), latent_begin, latent_end, false, F)) return rc;
+  std::vector<double> lml;
+  if (int rc = latent_lmls(xd.p, d, n, lts, nullptr, latent_begin, latent_end, F.z.p, lml, 1, F.nv.p)) return rc;
+  double total = 0.0;
+  for (double v : lml) total += v;
+  if (with_regulariser) total += F.reg(n, m, sigma2);
+  *out = total;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_oilmm_posterior_create_missing(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m,
+                                       double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_post_t** out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  LMM_MISSING_ARGCHECK(!x || !out || d <= 0);
+  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
+  RESOLVE(gps, m, d);
+  hipStream_t st0 = g.streams[0];
+  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
+  std::vector<double> means(m);
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  MissingFront F;
+  if (int rc = missing_front(yd.p, n, p, U, S, m, sigma2, means.data(), latent_begin, latent_end, false, F)) return rc;
+  return posterior_create_common(xd.p, d, n, ls, nullptr, latent_begin, latent_end, F.z.p, out, F.nv.p);
+  LMM_CATCH
+}
+
+// The path beside oilmm_grad_core for precomputed per-latent residuals and per-point noise (F.z, F.nv): the same per-latent factor,
+// alpha, Kt^-1 and launch_grad_reduce; the chain rule runs through the per-point noise (missing_wdiag_kernel) instead of s2 / S, and
+// d/dy through the per-point projection (missing_grad_y_kernel).  No derivatives with respect to S, U or x.
+static int oilmm_grad_missing_core(const double* xd, int d, int n, int p, double s2, const LatentSet* ls, int l0, int l1,
+                                   int with_regulariser, const MissingFront& F, double* value, double* gs2_out,
+                                   std::vector<lmm_gp_grad_t>& ggps, std::vector<double>& trec, double* gy_dev) {
+  hipStream_t st0 = g.streams[0];
+  const int m = (int)ls->lat.size(), ard_d = ls->ard_grad_d(), ms = l1 - l0;
+  const Latent* lts = ls->lat.data();
+  Dims D(n, 1);
+  int nb_per = 1, nslots = 1;
+  batch_plan(std::max(ms, 1), &nb_per, &nslots, 2.0 * mat_bytes((double)D.elems()));
+  std::vector<std::vector<Buf<double>>> Am(nslots), Wm(nslots), Rm(nslots);
+  std::vector<Buf<double>> part;
+  for (int s = 0; s < nslots; ++s) {
+    for (int j = 0; j < nb_per; ++j) {
+      Am[s].emplace_back(mat_count(D.elems())); Wm[s].emplace_back(mat_count((size_t)(D.NC / 64) * 4096));
+      Rm[s].emplace_back(mat_count((size_t)D.ld * D.NC));
+    }
+    part.emplace_back((size_t)grad_partials(n, ard_d));
+  }
+  const int NGR = LMM_NGRAD;
+  const std::vector<int> toff = ls->term_offsets(l0, l1);
+  const int nterm = toff[ms];
+  Buf<double> alpha((size_t)D.NC * std::max(ms, 1)), lmld(std::max(ms, 1)), red((size_t)NGR * std::max(nterm, 1));
+  Buf<double> ardred((size_t)d * std::max(nterm, 1)), wd(2 * (size_t)std::max(ms, 1));
+  Buf<int> info(std::max(ms, 1));
+  HIPCHK(hipMemsetAsync(info.p, 0, std::max(ms, 1) * sizeof(int), st0));
+  HIPCHK(hipMemsetAsync(alpha.p, 0, (size_t)D.NC * std::max(ms, 1) * sizeof(double), st0));
+  fork_slots(nslots);
+  int bi = 0;
+  for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
+    const int s = bi % nslots, nb = std::min(nb_per, ms - k0);
+    hipStream_t st = g.streams[s];
+    Batch B;
+    BatchPtr Rb{}, alb{};
+    GramArgs ga[LMM_MAX_BATCH];
+    for (int j = 0; j < nb; ++j) {
+      const int k = k0 + j;
+      GramArgs a{};
+      a.A = Am[s][j].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n;
+      lts[l0 + k].set_kernel(a); a.pad_diag = 1.0;
+      a.diag_add = 0.0; a.diag_vec = F.nv.p + (size_t)k * n;
+      a.rider = F.z.p + (size_t)k * n; a.rider_ld = n; a.nrider = 1;
+      ga[j] = a;
+      B.add(Am[s][j].p, Wm[s][j].p, info.p + k);
+      Rb.p[j] = Rm[s][j].p; alb.p[j] = alpha.p + (size_t)k * D.NC;
+    }
+    gram_batch_g(ga, nb, st);
+    potrf_batch(B, D.ld, D.NR, D.NC, n, st, D.NC + 1);
+    launch_lml_reduce(B.A, nb, D.ld, n, D.NC, 1, lmld.p + k0, st);
+    for (int j = 0; j < nb; ++j) {
+      launch_extract_row(Am[s][j].p, D.ld, D.NC, n, alb.p[j], st);
+      launch_set_identity(Rm[s][j].p, D.ld, D.NC, st);
+    }
+    launch_backsolve(B.A, D.ld, B.W, D.NC / 64, alb, nb, st);
+    trsm_rec(Rb, D.ld, D.NC, B.A, D.ld, B.W, nb, 0, D.NC, st, true);        // R = L^-T
+    launch_syrk_upper_set(B.A, D.ld, Rb, D.ld, D.NC, nb, st);                // lower(A) = Kt^-1
+    for (int j = 0; j < nb; ++j) {
+      const int k = k0 + j;
+      for (int c = 0; c < lts[l0 + k].nt(); ++c) {
+        const size_t t = (size_t)toff[k] + c;
+        launch_grad_reduce(Am[s][j].p, D.ld, n, n, alb.p[j], F.z.p + (size_t)k * n, xd, d, lts[l0 + k].terms[c].gd, part[s].p,
+                           red.p + NGR * t, st, ardred.p + d * t);
+      }
+      launch_missing_wdiag(Am[s][j].p, D.ld, n, alb.p[j], F.nv.p + (size_t)k * n, wd.p + 2 * (size_t)k, st);
+    }
+  }
+  join_slots(nslots);
+  std::vector<double> lml(std::max(ms, 1), 0.0), hred((size_t)NGR * std::max(nterm, 1), 0.0), hwd(2 * (size_t)std::max(ms, 1), 0.0);
+  std::vector<int> hinfo(std::max(ms, 1), 0);
+  std::vector<double> hard(ard_d ? (size_t)d * std::max(nterm, 1) : 0, 0.0);
+  HIPCHK(hipMemcpyAsync(lml.data(), lmld.p, std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  if (ms > 0) HIPCHK(hipMemcpyAsync(hwd.data(), wd.p, hwd.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, st0));
+  if (gy_dev)
+    launch_missing_grad_y(n, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, alpha.p, D.NC, l0, ms, with_regulariser ? F.resid.p : nullptr, s2,
+                          gy_dev, st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  if (ms > 0)
+    if (int rc = check_info(hinfo, l0)) return rc;
+  double total = 0.0, gs2 = 0.0;
+  ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
+  trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
+  for (int k = 0; k < ms; ++k) {
+    const int l = l0 + k;
+    total += lml[k];
+    const double* r = &hred[(size_t)NGR * toff[k]];
+    const double tr = r[1], aa = r[2], ad = r[3], sa = r[4];
+    const double D_aa = hwd[2 * (size_t)k], D_tr = hwd[2 * (size_t)k + 1];      // alpha' D alpha, tr(Kt^-1 D), D = diag(s2 (G_t^-1)_ll)
+    ggps[l].variance = 0.5 * ((ad - D_aa) - ((double)n - D_tr)) / lts[l].variance;
+    ggps[l].lengthscale = grad_finish(lts[l], d, r, hard.empty() ? nullptr : &hard[(size_t)d * toff[k]], aa, tr,
+                                      &trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)]);
+    ggps[l].mean = sa;
+    gs2 += 0.5 * (D_aa - D_tr) / s2;            // sum_t c_lt (alpha_t^2 - (Kt^-1)_tt) / 2, c_lt = (G_t^-1)_ll
+  }
+  if (with_regulariser) {
+    total += F.reg(n, m, s2);
+    gs2 += -0.5 * ((F.sum_pt - (double)n * m) / s2 - F.rss / (s2 * s2));
+  }
+  *value = total; *gs2_out = gs2;
+  return LMM_OK;
+}
+
+int lmm_oilmm_logpdf_grad_missing(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m,
+                                  double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                  double* out_logpdf, double* grad_y, double* grad_sigma2, lmm_gp_grad_t* grad_gps) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  LMM_MISSING_ARGCHECK(!x || !out_logpdf || d <= 0);
+  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
+  RESOLVE(gps, m, d);
+  if (int rc = ls->ard_grad_check()) return rc;
+  hipStream_t st0 = g.streams[0];
+  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
+  DevOut gy(grad_y, (size_t)n * p);
+  std::vector<double> means(m);
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  MissingFront F;
+  if (int rc = missing_front(yd.p, n, p, U, S, m, sigma2, means.data(), latent_begin, latent_end, grad_y && with_regulariser, F)) return rc;
+  double value = 0.0, gs2 = 0.0;
+  std::vector<lmm_gp_grad_t> ggps;
+  std::vector<double> trec;
+  if (int rc = oilmm_grad_missing_core(xd.p, d, n, p, sigma2, ls.get(), latent_begin, latent_end, with_regulariser, F, &value, &gs2,
+                                       ggps, trec, gy.p))
+    return rc;
+  *out_logpdf = value;
+  if (grad_sigma2) *grad_sigma2 = gs2;
+  if (grad_gps) std::copy(ggps.begin(), ggps.end(), grad_gps);
+  publish_grads(*ls, grad_gps ? &trec : nullptr, latent_begin, latent_end);
+  if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
+  return LMM_OK;
   LMM_CATCH
 }
 

@@ -232,6 +232,26 @@ struct NoiseBlocks {
 };
 // out[k] = a[k] + (num / s2[block of row k]) * b[k]   with row(k) = k mod N  (column-major N x p operands)
 void launch_vec_lin_blocks(const double* a, const double* b, const NoiseBlocks& nb, double num, int N, size_t count, double* out, hipStream_t st);
+// Missing observations (NaN in y).  p outputs, nw = ceil(p / 64) mask words per point or pattern; all Float64.
+#define LMM_MISSING_MMAX 128                  // widest m the per-pattern m x m work serves
+// masks[t nw + w], pt[t]: observed-output bits and their count for every point of y (n x p column-major, device)
+void launch_missing_masks(const double* y, int n, int p, unsigned long long* masks, int* pt, hipStream_t st);
+// per pattern: Tpat (m x p, zero columns at missing outputs) = G^-1 H_O', dinv (m) = diag G^-1, logdet = log det G, info = failed pivot
+// or 0.  scratch: missing_pattern_scratch_elems(m, npat) doubles (0 for m <= 64: the m x m work is in LDS).
+size_t missing_pattern_scratch_elems(int m, int npat);
+void launch_missing_patterns(const double* H, int p, int m, const unsigned long long* pmask, int npat, double* scratch, double* Tpat,
+                             double* dinv, double* logdet, int* info, hipStream_t st);
+// out_z, out_noise: [l1 - l0][n] (z - means, s2 dinv); resid: n x p or nullptr; part: 3 n doubles; sums3: sum_t |resid_t|^2, sum_t p_t,
+// sum_t log det G_t (fixed order)
+void launch_missing_apply(const double* y, int n, int p, int m, const int* pat_of, const unsigned long long* pmask, const double* Tpat,
+                          const double* dinv, const double* logdet, const int* pt, const double* H, double s2, const double* means,
+                          int l0, int l1, double* out_z, double* out_noise, double* resid, double* part, double* sums3,
+                          hipStream_t st);
+// out2 = [sum_t w_t alpha_t^2, sum_t w_t Kinv_tt]
+void launch_missing_wdiag(const double* Kinv, int ld, int n, const double* alpha, const double* w, double* out2, hipStream_t st);
+// gy (n x p) = -T_t' alpha_t - resid / s2 at observed entries (resid nullptr: first term only), 0 at missing ones; alpha: [ms][lda]
+void launch_missing_grad_y(int n, int p, int m, const int* pat_of, const unsigned long long* pmask, const double* Tpat,
+                           const double* alpha, int lda, int l0, int ms, const double* resid, double s2, double* gy, hipStream_t st);
 void launch_atb(const double* X, int ldx, const double* Z, int ldz, int n, int na, int nb, double* out, hipStream_t st);
 void launch_fill(double* p, int n, double v, hipStream_t st);
 void launch_reorder(const double* in, int n, int p, int to_outputs, double* out, hipStream_t st);

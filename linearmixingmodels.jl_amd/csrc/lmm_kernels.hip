@@ -4256,6 +4256,215 @@ __global__ __launch_bounds__(256) void block_trace_kernel(const void* __restrict
   if (threadIdx.x == 0) { out[l + (size_t)l2 * m] = tot; out[l2 + (size_t)l * m] = tot; }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Missing observations (NaN in y): the per-point projection of the OILMM.  With O_t the observed outputs of point
+// t, H_t = H[O_t, :] and G_t = H_t' H_t:  z_t = G_t^-1 H_t' y_t[O_t], latent l sees z_t[l] with noise sigma2 (G_t^-1)_ll, and the
+// point adds  -1/2 [(p_t - m) log(2 pi sigma2) + log det G_t + |y_t[O_t] - H_t z_t|^2 / sigma2]  to the regulariser.  Points with equal
+// O_t share one PATTERN (grouped on the host from the masks below).  Everything here is Float64 in both compute dtypes.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool missing_observed(const unsigned long long* __restrict__ mask, int o) {
+  return (mask[o >> 6] >> (o & 63)) & 1ull;
+}
+
+// masks[t nw + w]: bit (o & 63) of word o / 64 is set iff y[t + o n] is not NaN (+-Inf is data); pt[t]: the number of set bits.
+__global__ __launch_bounds__(256) void missing_mask_kernel(const double* __restrict__ y, int n, int p, int nw,
+                                                           unsigned long long* __restrict__ masks, int* __restrict__ pt) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  int cnt = 0;
+  for (int w = 0; w < nw; ++w) {
+    unsigned long long bits = 0;
+    const int o1 = min(p, 64 * (w + 1));
+    for (int o = 64 * w; o < o1; ++o) {
+      const double v = y[t + (size_t)o * n];
+      if (v == v) { bits |= 1ull << (o & 63); ++cnt; }
+    }
+    masks[(size_t)t * nw + w] = bits;
+  }
+  pt[t] = cnt;
+}
+
+// One workgroup per pattern (grid-stride over the patterns): G = H_O' H_O, its Cholesky factor, W = L^-1, G^-1 = W' W,
+// T = G^-1 H_O' (m x p column-major, zero columns at the missing outputs), dinv = diag(G^-1), logdet = log det G.  info[pat] = 0, or
+// the LAPACK-style index of the pivot that was not positive (T and dinv of that pattern are zeroed).  m <= 64: G and W live in LDS
+// (2 x 32 KB); 64 < m <= LMM_MISSING_MMAX: in the workgroup's block of `scratch` (2 m^2 doubles per workgroup of the grid).
+__global__ __launch_bounds__(256) void missing_pattern_kernel(const double* __restrict__ H, int p, int m, int nw,
+                                                              const unsigned long long* __restrict__ pmask, int npat,
+                                                              double* __restrict__ scratch, double* __restrict__ Tpat,
+                                                              double* __restrict__ dinv, double* __restrict__ logdet,
+                                                              int* __restrict__ info) {
+  __shared__ double sh[2 * 64 * 64];
+  double* G = m <= 64 ? sh : scratch + (size_t)blockIdx.x * 2 * m * m;
+  double* W = G + (size_t)m * m;
+  const int tid = threadIdx.x;
+  for (int pat = blockIdx.x; pat < npat; pat += gridDim.x) {
+    const unsigned long long* mk = pmask + (size_t)pat * nw;
+    double* T = Tpat + (size_t)pat * m * p;
+    for (int e = tid; e < m * m; e += 256) {
+      const int i = e % m, j = e / m;
+      double s = 0.0;
+      if (i >= j)
+        for (int o = 0; o < p; ++o)
+          if (missing_observed(mk, o)) s = __builtin_fma(H[o + (size_t)i * p], H[o + (size_t)j * p], s);
+      G[e] = s;
+    }
+    __syncthreads();
+    // right-looking Cholesky of the lower triangle; every thread reads the same pivot, so `fail` is uniform
+    int fail = 0;
+    for (int j = 0; j < m; ++j) {
+      const double dj = G[j + j * m];
+      if (!(dj > 0.0)) { fail = j + 1; break; }
+      __syncthreads();
+      const double rs = sqrt(dj);
+      for (int i = j + tid; i < m; i += 256) G[i + j * m] = (i == j) ? rs : G[i + j * m] / rs;
+      __syncthreads();
+      const int r = m - 1 - j;
+      for (int e = tid; e < r * r; e += 256) {
+        const int i = j + 1 + e % r, k = j + 1 + e / r;
+        if (i >= k) G[i + k * m] -= G[i + j * m] * G[k + j * m];
+      }
+      __syncthreads();
+    }
+    if (fail) {
+      for (int e = tid; e < m * p; e += 256) T[e] = 0.0;
+      for (int l = tid; l < m; l += 256) dinv[(size_t)pat * m + l] = 0.0;
+      if (tid == 0) { info[pat] = fail; logdet[pat] = 0.0; }
+      __syncthreads();
+      continue;
+    }
+    for (int c = tid; c < m; c += 256) {          // column c of W = L^-1 by forward substitution
+      W[c + c * m] = 1.0 / G[c + c * m];
+      for (int i = c + 1; i < m; ++i) {
+        double s = 0.0;
+        for (int k = c; k < i; ++k) s = __builtin_fma(G[i + k * m], W[k + c * m], s);
+        W[i + c * m] = -s / G[i + i * m];
+      }
+    }
+    if (tid == 0) {
+      double ld = 0.0;
+      for (int j = 0; j < m; ++j) ld += log(G[j + j * m]);
+      logdet[pat] = 2.0 * ld; info[pat] = 0;
+    }
+    __syncthreads();
+    for (int e = tid; e < m * m; e += 256) {      // G <- G^-1 = W' W (both triangles, the same sum order: exactly symmetric)
+      const int i = e % m, j = e / m;
+      double s = 0.0;
+      for (int k = max(i, j); k < m; ++k) s = __builtin_fma(W[k + i * m], W[k + j * m], s);
+      G[e] = s;
+    }
+    __syncthreads();
+    for (int e = tid; e < m * p; e += 256) {
+      const int l = e % m, o = e / m;
+      double s = 0.0;
+      if (missing_observed(mk, o))
+        for (int j = 0; j < m; ++j) s = __builtin_fma(G[l + j * m], H[o + (size_t)j * p], s);
+      T[e] = s;
+    }
+    for (int l = tid; l < m; l += 256) dinv[(size_t)pat * m + l] = G[l + l * m];
+    __syncthreads();
+  }
+}
+
+// One workgroup per point t: z_t = T_pat(t) y_t (NaN read as 0), out_z[k n + t] = z_t[l0 + k] - means[l0 + k] and
+// out_noise[k n + t] = s2 dinv[pat(t)][l0 + k] for the latents [l0, l1); resid (n x p, optional) = y_t - H z_t at the observed outputs,
+// 0 elsewhere; part[t], part[n + t], part[2 n + t] = |resid_t|^2, p_t, log det G_pat(t) (summed in point order by missing_sums_kernel).
+// Thread (l, c) = (tid % m, tid / m) sums the outputs c, c + nc, ... of latent l; the nc slices are added in slice order.
+__global__ __launch_bounds__(256) void missing_apply_kernel(const double* __restrict__ y, int n, int p, int m, int nw,
+                                                            const int* __restrict__ pat_of, const unsigned long long* __restrict__ pmask,
+                                                            const double* __restrict__ Tpat, const double* __restrict__ dinv,
+                                                            const double* __restrict__ logdet, const int* __restrict__ pt,
+                                                            const double* __restrict__ H, double s2, const double* __restrict__ means,
+                                                            int l0, int l1, double* __restrict__ out_z, double* __restrict__ out_noise,
+                                                            double* __restrict__ resid, double* __restrict__ part) {
+  __shared__ double red[256];
+  __shared__ double zs[LMM_MISSING_MMAX];
+  __shared__ double sh[4];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const int pat = pat_of[t];
+  const unsigned long long* mk = pmask + (size_t)pat * nw;
+  const double* T = Tpat + (size_t)pat * m * p;
+  const int nc = 256 / m, l = tid % m, c = tid / m;
+  double acc = 0.0;
+  if (c < nc)
+    for (int o = c; o < p; o += nc) {
+      const double v = y[t + (size_t)o * n];
+      acc = __builtin_fma(T[l + (size_t)o * m], v == v ? v : 0.0, acc);
+    }
+  red[tid] = acc;
+  __syncthreads();
+  if (tid < m) {
+    double s = 0.0;
+    for (int k = 0; k < nc; ++k) s += red[tid + k * m];
+    zs[tid] = s;
+  }
+  __syncthreads();
+  double ss = 0.0;
+  for (int o = tid; o < p; o += 256) {
+    double r = 0.0;
+    if (missing_observed(mk, o)) {
+      r = y[t + (size_t)o * n];
+      for (int j = 0; j < m; ++j) r = __builtin_fma(-H[o + (size_t)j * p], zs[j], r);
+      ss = __builtin_fma(r, r, ss);
+    }
+    if (resid) resid[t + (size_t)o * n] = r;
+  }
+  const double tot = block_sum_256(ss, sh);
+  if (tid == 0) { part[t] = tot; part[(size_t)n + t] = (double)pt[t]; part[2 * (size_t)n + t] = logdet[pat]; }
+  for (int k = tid; k < l1 - l0; k += 256) {
+    out_z[(size_t)k * n + t] = zs[l0 + k] - (means ? means[l0 + k] : 0.0);
+    out_noise[(size_t)k * n + t] = s2 * dinv[(size_t)pat * m + l0 + k];
+  }
+}
+
+// out[j] = sum_t part[j n + t], j < 3: one workgroup, fixed order (no atomics)
+__global__ __launch_bounds__(256) void missing_sums_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
+  __shared__ double sh[4];
+  for (int j = 0; j < 3; ++j) {
+    double s = 0.0;
+    for (int t = threadIdx.x; t < n; t += 256) s += part[(size_t)j * n + t];
+    const double tot = block_sum_256(s, sh);
+    if (threadIdx.x == 0) out[j] = tot;
+  }
+}
+
+// out[0] = sum_t w_t alpha_t^2, out[1] = sum_t w_t (Kinv)_tt: with w = the per-point noise of a latent these are alpha' D alpha and
+// tr(Kt^-1 D) (d lml / d sigma2 through the per-point noise is their difference over 2 sigma2).  Kinv in the compute dtype.
+template <typename TS>
+__global__ __launch_bounds__(256) void missing_wdiag_kernel(const void* __restrict__ Kinv, int ld, int n, const double* __restrict__ alpha,
+                                                            const double* __restrict__ w, double* __restrict__ out) {
+  __shared__ double sh[4];
+  double sa = 0.0, sk = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const double wi = w[i], a = alpha[i];
+    sa = __builtin_fma(wi * a, a, sa);
+    sk = __builtin_fma(wi, MatIO<TS>::ld1(Kinv, (size_t)i * ld + i), sk);
+  }
+  const double ta = block_sum_256(sa, sh);
+  const double tk = block_sum_256(sk, sh);
+  if (threadIdx.x == 0) { out[0] = ta; out[1] = tk; }
+}
+
+// One workgroup per point: gy[t + o n] = -sum_k T_pat(t)[l0 + k, o] alpha_k[t] - resid[t + o n] / s2 at the observed outputs (resid may be
+// nullptr: no regulariser), exactly 0 at the missing ones.  alpha: [ms][lda].
+__global__ __launch_bounds__(256) void missing_grad_y_kernel(int n, int p, int m, int nw, const int* __restrict__ pat_of,
+                                                             const unsigned long long* __restrict__ pmask,
+                                                             const double* __restrict__ Tpat, const double* __restrict__ alpha, int lda,
+                                                             int l0, int ms, const double* __restrict__ resid, double s2,
+                                                             double* __restrict__ gy) {
+  const int t = blockIdx.x;
+  const int pat = pat_of[t];
+  const unsigned long long* mk = pmask + (size_t)pat * nw;
+  const double* T = Tpat + (size_t)pat * m * p;
+  for (int o = threadIdx.x; o < p; o += 256) {
+    double s = 0.0;
+    if (missing_observed(mk, o)) {
+      for (int k = 0; k < ms; ++k) s = __builtin_fma(-T[(l0 + k) + (size_t)o * m], alpha[(size_t)k * lda + t], s);
+      if (resid) s -= resid[t + (size_t)o * n] / s2;
+    }
+    gy[t + (size_t)o * n] = s;
+  }
+}
+
 // out[k] = a[k] + (num / s2[block of row(k)]) * b[k]  with row(k) = k mod N  (column-major N x p operands; blocks: NoiseBlocks)
 __global__ void vec_lin_blocks_kernel(const double* a, const double* b, NoiseBlocks nb, double num, int N, size_t count, double* out) {
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -5077,6 +5286,38 @@ void launch_vec_axpby(const double* a, double sa, const double* b, double sb, si
 
 void launch_block_trace(const double* Minv, int ld, int n, int m, int i0, int i1, double* out, hipStream_t st) {
   LMM_TS_LAUNCH((block_trace_kernel<TS>), dim3(m, m), dim3(256), 0, st, (const void*)Minv, ld, n, m, i0, i1, out);
+}
+
+void launch_missing_masks(const double* y, int n, int p, unsigned long long* masks, int* pt, hipStream_t st) {
+  hipLaunchKernelGGL(missing_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, st, y, n, p, (p + 63) / 64, masks, pt);
+}
+
+int missing_pattern_grid(int npat) { return npat < 256 ? npat : 256; }
+size_t missing_pattern_scratch_elems(int m, int npat) { return m <= 64 ? 0 : (size_t)missing_pattern_grid(npat) * 2 * m * m; }
+
+void launch_missing_patterns(const double* H, int p, int m, const unsigned long long* pmask, int npat, double* scratch, double* Tpat,
+                             double* dinv, double* logdet, int* info, hipStream_t st) {
+  hipLaunchKernelGGL(missing_pattern_kernel, dim3(missing_pattern_grid(npat)), dim3(256), 0, st, H, p, m, (p + 63) / 64, pmask, npat,
+                     scratch, Tpat, dinv, logdet, info);
+}
+
+void launch_missing_apply(const double* y, int n, int p, int m, const int* pat_of, const unsigned long long* pmask, const double* Tpat,
+                          const double* dinv, const double* logdet, const int* pt, const double* H, double s2, const double* means,
+                          int l0, int l1, double* out_z, double* out_noise, double* resid, double* part, double* sums3,
+                          hipStream_t st) {
+  hipLaunchKernelGGL(missing_apply_kernel, dim3(n), dim3(256), 0, st, y, n, p, m, (p + 63) / 64, pat_of, pmask, Tpat, dinv, logdet, pt,
+                     H, s2, means, l0, l1, out_z, out_noise, resid, part);
+  hipLaunchKernelGGL(missing_sums_kernel, dim3(1), dim3(256), 0, st, part, n, sums3);
+}
+
+void launch_missing_wdiag(const double* Kinv, int ld, int n, const double* alpha, const double* w, double* out2, hipStream_t st) {
+  LMM_TS_LAUNCH((missing_wdiag_kernel<TS>), dim3(1), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, w, out2);
+}
+
+void launch_missing_grad_y(int n, int p, int m, const int* pat_of, const unsigned long long* pmask, const double* Tpat,
+                           const double* alpha, int lda, int l0, int ms, const double* resid, double s2, double* gy, hipStream_t st) {
+  hipLaunchKernelGGL(missing_grad_y_kernel, dim3(n), dim3(256), 0, st, n, p, m, (p + 63) / 64, pat_of, pmask, Tpat, alpha, lda, l0, ms,
+                     resid, s2, gy);
 }
 
 void launch_vec_lin_blocks(const double* a, const double* b, const NoiseBlocks& nb, double num, int N, size_t count, double* out, hipStream_t st) {

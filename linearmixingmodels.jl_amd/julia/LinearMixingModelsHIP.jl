@@ -447,6 +447,45 @@ function AbstractGPs.posterior(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:
     return ILMM(HIPMOGP(fs.fs, h[], [(X, Float64(σ²), yv)]), H)    # again an ILMM with the same H (src/oilmm.jl:133)
 end
 
+# ---- missing observations: y::AbstractVector{Union{Missing,Float64}} ----------------------------------------------------------------
+# The reference's notebook: "Heterotopic and missing data ... are not supported yet ... using the missing data techniques identified in
+# the paper".  `missing` becomes NaN and the prior OILMM goes through the library's *_missing entry points (include/lmm_hip.h, "missing
+# observations": the diagonal approximation of the OILMM paper).  Points without any observation are dropped first (they carry no
+# information; the C ABI refuses them).  Posterior models, dense-H ILMM, IndependentMOGP, matrix Y and rand do not take missing data.
+const MissingVec = AbstractVector{Union{Missing,Float64}}
+_nan(y::MissingVec) = Float64[ismissing(v) ? NaN : v for v in y]
+function _drop_unobserved(X::Matrix{Float64}, yv::Vector{Float64}, p::Integer)
+    Y = reshape(yv, :, p)                           # n x p, by outputs
+    keep = [!all(isnan, view(Y, t, :)) for t in 1:size(Y, 1)]
+    all(keep) && return X, yv, keep
+    return X[:, keep], vec(Y[keep, :]), keep
+end
+_no_missing(fs) = isposterior(fs) && error("posterior models do not take missing data (lmm_post_condition and the predictive logpdf are not served with NaN)")
+
+function AbstractGPs.logpdf(fx::ByOutputsFill{HIPOILMM}, y::MissingVec)
+    fs, H, σ², x = unpack(fx); _no_missing(fs)
+    U, S, p, m = _hargs(H); X, yv, _ = _drop_unobserved(_xmat(x), _nan(y), p); d, n = size(X)
+    out = Ref{Cdouble}(0.0)
+    _gps(fs.fs) do gps, tags
+        GC.@preserve X yv U S gps check(ccall((:lmm_oilmm_logpdf_missing, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}),
+            X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, out))
+    end
+    return out[]
+end
+
+function AbstractGPs.posterior(fx::ByOutputsFill{HIPOILMM}, y::MissingVec)
+    fs, H, σ², x = unpack(fx); _no_missing(fs)
+    U, S, p, m = _hargs(H); X, yv, _ = _drop_unobserved(_xmat(x), _nan(y), p); d, n = size(X)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    _gps(fs.fs) do gps, tags
+        GC.@preserve X yv U S gps check(ccall((:lmm_oilmm_posterior_create_missing, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Ref{Ptr{Cvoid}}),
+            X, d, n, yv, p, U, S, m, σ², gps, 0, m, h))
+    end
+    return ILMM(HIPMOGP(fs.fs, h[], nothing), H)    # no training record: predictive gradients through NaN-carrying data are not built
+end
+
 # reference src/independent_mogp.jl:119-126; on a posterior: sequential conditioning (test/independent_mogp.jl:68-76)
 function AbstractGPs.posterior(ft::ByOutputsFill{HIPMOGP}, y::AbstractVector{<:Real})
     X = _xmat(ft.x.x); d, n = size(X); m = length(ft.f.fs); yv = Vector{Float64}(y); σ² = noise_var(ft.Σy)
@@ -827,7 +866,8 @@ _xtangent(x, G) = NoTangent()
 _motangent(x::MOInputIsotopicByOutputs, G) = G === nothing ? NoTangent() : Tangent{typeof(x)}(; x=_xtangent(x.x, G), out_dim=NoTangent())
 _htangent(H::Orthogonal, gU, gS) = Tangent{typeof(H)}(; U=gU, S=Tangent{typeof(H.S)}(; diag=gS))
 
-function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real})
+function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HIPOILMM}, y::Union{AbstractVector{<:Real},MissingVec})
+    y isa MissingVec && return _logpdf_missing_rrule(fx, y)       # missing observations: below
     fs, H, σ², x = unpack(fx)
     X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); gard = nothing; yv = Vector{Float64}(y)
     val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
@@ -883,6 +923,30 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
         return NoTangent(), dfx, Δ .* gy
     end
     return val[], logpdf_pullback
+end
+
+# logpdf with missing observations (lmm_oilmm_logpdf_grad_missing): cotangents for the latent GPs, the noise and the observed entries
+# of y (0 at the missing ones); the library builds no derivative through the per-point projection, so H gets ZeroTangent.  Reached
+# from the OILMM logpdf rrule above, whose signature admits a y with `missing`.
+function _logpdf_missing_rrule(fx::ByOutputsFill{HIPOILMM}, y::MissingVec)
+    fs, H, σ², x = unpack(fx); _no_missing(fs)
+    U, S, p, m = _hargs(H); X, yv, keep = _drop_unobserved(_xmat(x), _nan(y), p); d, n = size(X); gard = nothing
+    val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
+    gy = Vector{Float64}(undef, n * p); gg = Vector{LmmGpGrad}(undef, m)
+    _gps(fs.fs) do gps, tags
+        GC.@preserve X yv U S gps gy gg check(ccall((:lmm_oilmm_logpdf_grad_missing, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
+             Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{LmmGpGrad}),
+            X, d, n, yv, p, U, S, m, σ², gps, 0, m, 1, val, gy, gσ, gg))
+        gard = _ard_grads(tags, d)
+    end
+    gfull = zeros(length(keep), p); gfull[keep, :] = reshape(gy, :, p)
+    function logpdf_missing_pullback(Δ)
+        dlat = Tangent{typeof(fs)}(; fs=_fstangent(fs.fs, gg, Δ, gard))
+        dfx = Tangent{typeof(fx)}(; x=NoTangent(), f=Tangent{typeof(fx.f)}(; f=dlat, H=ZeroTangent()), Σy=_noise_tangent(fx, Δ * gσ[]))
+        return NoTangent(), dfx, Δ .* vec(gfull)
+    end
+    return val[], logpdf_missing_pullback
 end
 
 # Value, pullback-at-1 and the training cotangents of the predictive logpdf in one call: what an end-to-end differentiation of

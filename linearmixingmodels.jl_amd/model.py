@@ -547,6 +547,119 @@ def _alloc_like(ref, count: int):
     return np.empty(count, dtype=np.float64)
 
 
+# ---- missing observations (NaN in y) ---------------------------------------------------------------------
+# The reference's notebook: "Heterotopic and missing data ... are not supported yet ... using the missing data techniques identified in
+# the paper".  logpdf, posterior and logpdf_and_gradient of a PRIOR OILMM take a by-outputs vector y whose missing entries are NaN
+# (include/lmm_hip.h, "missing observations"); nothing else does.
+def _has_nan(y) -> bool:
+    if L._is_torch(y):
+        import torch
+        return bool(torch.isnan(y).any())
+    return bool(np.isnan(y).any())
+
+
+def _drop_unobserved(xv, y, p: int):
+    """Removes the points that have no observed output (a point without observations carries no information, and the C ABI refuses
+    it): (x, y, keep) with x (n,) or (d, n), y the by-outputs vector (n * p) and keep the boolean mask of the points kept (on the side
+    of y).  Arrays are returned unchanged when every point is kept."""
+    tor = L._is_torch(y)
+    Y = y.reshape(p, -1)
+    if tor:
+        import torch
+        keep = ~torch.isnan(Y).all(dim=0)
+    else:
+        keep = ~np.isnan(Y).all(axis=0)
+    if bool(keep.all()):
+        return xv, y, keep
+    kx = keep
+    if L._is_torch(xv) and not tor:
+        import torch
+        kx = torch.as_tensor(keep, device=xv.device)
+    elif tor and not L._is_torch(xv):
+        kx = keep.cpu().numpy()
+    y2 = Y[:, keep].reshape(-1)
+    return xv[..., kx], (y2.contiguous() if tor else np.ascontiguousarray(y2)), keep
+
+
+def _missing_args(fx: "FiniteGP", y, what: str):
+    """(x without the unobserved points, y without them, keep) for the *_missing entry points, or NotImplementedError when `fx` is not a
+    prior OILMM over by-outputs inputs with a vector y."""
+    f, x = fx.f, fx.x
+    if not hasattr(y, "shape"):
+        y = np.asarray(y, dtype=np.float64)
+    if (not isinstance(f, ILMM) or not f.is_oilmm or f.f._post is not None or not isinstance(x, MOInputIsotopicByOutputs)
+            or fx.heteroscedastic or (hasattr(y, "shape") and len(y.shape) != 1)):
+        raise NotImplementedError(
+            f"{what}: missing observations (NaN in y) are served for a vector y on a prior OILMM (logpdf, posterior, "
+            "logpdf_and_gradient) over MOInputIsotopicByOutputs only; sequential conditioning (lmm_post_condition), the predictive "
+            "logpdf, matrix Y, by-features inputs, per-point noise, dense-H ILMM, IndependentMOGP and rand do not take missing data")
+    unpack(fx)
+    if y.shape[0] != x.n * x.out_dim:
+        raise ValueError("length(y) != n * out_dim")
+    xv, y2, keep = _drop_unobserved(x.x, y, x.out_dim)
+    return MOInputIsotopicByOutputs(xv, x.out_dim), y2, keep
+
+
+def _logpdf_missing(fx: "FiniteGP", y, with_regulariser: bool) -> float:
+    lib = L.load()
+    x, y2, _ = _missing_args(fx, y, "logpdf")
+    f = fx.f
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    out = C.c_double()
+    L.check(lib.lmm_oilmm_logpdf_missing(x.carr().ptr, x.dim, x.n, L.Arr(y2).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(fx.sigma2), gps,
+                                         f.shard[0], f.shard[1], int(with_regulariser), C.byref(out)))
+    return out.value
+
+
+def _posterior_missing(fx: "FiniteGP", y):
+    lib = L.load()
+    x, y2, _ = _missing_args(fx, y, "posterior")
+    f = fx.f
+    gps = L.gps_array([g.desc() for g in f.f.fs])
+    Ua, Sa, p, m = _H_args(f.H)
+    handle = C.c_void_p()
+    L.check(lib.lmm_oilmm_posterior_create_missing(x.carr().ptr, x.dim, x.n, L.Arr(y2).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(fx.sigma2),
+                                                   gps, f.shard[0], f.shard[1], C.byref(handle)))
+    # train=None: the gradient of the predictive logpdf through NaN-carrying training data is not built
+    return ILMM(IndependentMOGP(f.f.fs, _PostHandle(handle, f.shard[0], f.shard[1])), f.H, shard=f.shard)
+
+
+def _gradient_missing(fx: "FiniteGP", y, with_regulariser: bool, inputs: bool) -> dict:
+    if inputs:
+        raise NotImplementedError("logpdf_and_gradient: the gradient with respect to the inputs is not built for data with NaN")
+    lib = L.load()
+    x, y2, keep = _missing_args(fx, y, "logpdf_and_gradient")
+    f = fx.f
+    Ua, Sa, p, m = _H_args(f.H)
+    val, gs2 = C.c_double(), C.c_double()
+    gy2 = _alloc_like(y2, x.n * p)
+    gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.f.fs])
+    L.check(lib.lmm_oilmm_logpdf_grad_missing(x.carr().ptr, x.dim, x.n, L.Arr(y2).ptr, p, Ua.ptr, Sa.ptr, m, C.c_double(fx.sigma2), ga,
+                                              f.shard[0], f.shard[1], int(with_regulariser), C.byref(val), L.Arr(gy2, True).ptr,
+                                              C.byref(gs2), gg))
+    gy = gy2
+    if not bool(keep.all()):          # the dropped points' entries are missing ones: 0
+        if L._is_torch(gy2):
+            import torch
+            gy = torch.zeros(p, fx.x.n, dtype=torch.float64, device=gy2.device)
+            gy[:, keep.to(gy2.device)] = gy2.reshape(p, -1)
+        else:
+            gy = np.zeros((p, fx.x.n))
+            gy[:, np.asarray(keep.cpu() if L._is_torch(keep) else keep)] = gy2.reshape(p, -1)
+        gy = gy.reshape(-1)
+    return {"value": val.value, "y": gy, "sigma2": gs2.value, "gps": _gps_grads(gg, ga, m, x.dim)}
+
+
+class _NoMixingGradient(dict):
+    """The gradient dict for data with NaN: "S", "U" (and "x") are not built."""
+
+    def __missing__(self, key):
+        if key in ("S", "U", "x"):
+            raise NotImplementedError(f"logpdf_and_gradient: the gradient with respect to {key!r} is not built for data with NaN")
+        raise KeyError(key)
+
+
 # Dense-H ILMM logpdf: allow the identical-kernel decoupled shortcut (exact; SURVEY.md section 3.2).  Set False to force
 # the reference's single (mn) x (mn) factorisation.  ILMM_LAST_PATH records which ran.
 ILMM_ALLOW_DECOUPLED = True
@@ -560,6 +673,8 @@ def logpdf(fx: FiniteGP, y, with_regulariser: bool = True) -> float:
     is not sharded)."""
     L.ensure_init()
     lib = L.load()
+    if _has_nan(y):
+        return _logpdf_missing(fx, y, with_regulariser)
     f, x, s2 = fx.f, fx.x, fx.sigma2
     if isinstance(x, MOInputIsotopicByFeatures):          # reference src/independent_mogp.jl:222-229
         if not isinstance(f, IndependentMOGP):
@@ -688,9 +803,13 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True, inputs: 
     typed like the inputs ((n,) or (d, n); NumPy or torch): prior models gain "x"; posterior models gain "x" (d/d xs, the test inputs)
     and "x_train" (d/d the conditioning inputs: a list with one array per batch after sequential conditioning, as "y_train").  It
     costs one more read of each latent's K^-1; d <= 32.  With inputs=False the call and its keys are unchanged.
+    A y with NaN (missing observations, prior OILMM only): {"value", "y" (0 at the missing entries), "sigma2", "gps"}; "S", "U" and
+    inputs=True raise NotImplementedError.
     Partial sums over the latent shard."""
     L.ensure_init()
     lib = L.load()
+    if _has_nan(y):
+        return _NoMixingGradient(_gradient_missing(fx, y, with_regulariser, inputs))
     f, x, s2 = fx.f, fx.x, fx.sigma2
     mogp = isinstance(f, IndependentMOGP)
     post = f._post if mogp else (f.f._post if isinstance(f, ILMM) else None)
@@ -856,6 +975,8 @@ def posterior(fx: FiniteGP, y):
     an OILMM with the same H) and src/independent_mogp.jl:119-126."""
     L.ensure_init()
     lib = L.load()
+    if _has_nan(y):
+        return _posterior_missing(fx, y)
     f, x, s2 = fx.f, fx.x, fx.sigma2
     if isinstance(x, MOInputIsotopicByFeatures):
         return posterior(FiniteGP(f, x.by_outputs(), s2), _reorder(y, x.n, x.out_dim, True))
