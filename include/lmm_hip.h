@@ -583,6 +583,49 @@ int lmm_oilmm_logpdf_grad_missing(const double* x, int d, int n, const double* y
                                   const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
                                   double* out_logpdf, double* grad_y, double* grad_sigma2, lmm_gp_grad_t* grad_gps);
 
+/* ---- inducing points (VFE) --------------------------------------------------------------------
+ * Titsias' collapsed bound on the independent latents of an OILMM, as AbstractGPs states it for VFE(f(z, jitter))
+ * (src/sparse_approximations.jl): linear cost in n.  z: d x nz inducing inputs shared by all latents (host or device), nz <= 1024
+ * (LMM_ERR_UNSUPPORTED beyond, before any launch), d <= 32, jitter > 0 is added to the diagonal of K_uu.  Per latent l of the shard,
+ * with r = (T y)_l - mean_l and w = sigma2 / S_l (the projection of reference src/oilmm.jl:20-30):
+ *     Phi = sum_t k_u(x_t) k_u(x_t)' / w,  b = sum_t k_u(x_t) r_t / w,  s = sum_t r_t^2 / w,  kappa = sum_t k(x_t, x_t) / w,
+ *     lambda = sum_t log w_t (= n log w here),  L_u = chol(K_uu + jitter I),  B = I + L_u^-1 Phi L_u^-T,  L_B = chol(B),  c = L_B^-1 L_u^-1 b,
+ *     dtc_l = -(n log 2pi + lambda + log det B + s - c'c) / 2,   elbo_l = dtc_l - (kappa - tr(L_u^-1 Phi L_u^-T)) / 2.
+ * Only Phi, b, s, kappa, lambda touch the n points: one pass that generates K_uf tiles on the fly and never stores K_uf
+ * (DESIGN.md 4.16); no atomics, so these moments are bitwise reproducible whatever LMM_DETERMINISTIC says (the two M x M
+ * factorisations follow the library's rule: split-K atomics only in large trailing updates).  Float64 only: the fp32
+ * compute mode is refused (LMM_ERR_UNSUPPORTED).  A failed pivot of K_uu + jitter I or of B is LMM_ERR_NOT_PD with the latent and the
+ * pivot in lmm_last_error_detail.  Not built: gradients, NaN in y, dense H.
+ *   lmm_oilmm_elbo : elbo(VFE(f(z, jitter)), fx, y) and dtc(VFE(f(z, jitter)), fx, y) of AbstractGPs for fx::FiniteGP{<:OILMM}.
+ *                    Arguments as lmm_oilmm_logpdf; *elbo = sum_{l in shard} elbo_l + (with_regulariser ? the regulariser of
+ *                    reference src/oilmm.jl:101-113 : 0), *dtc likewise; either output may be NULL.
+ *   lmm_oilmm_sparse_posterior_create : posterior(VFE(f(z, jitter)), fx, y) of AbstractGPs (ApproxPosteriorGP), per latent of the
+ *                    shard: the handle keeps z, L_u, L_B and c.
+ *   lmm_sparse_post_destroy : releases such a handle.
+ *   lmm_oilmm_sparse_mean_and_var : mean_and_var(fx) (reference src/oilmm.jl:57-76) on the posterior OILMM whose latents are those
+ *                    ApproxPosteriorGPs: with a = L_u^-1 k_u(x*), latent mean = mean_l + a' L_B^-T c and latent variance
+ *                    k** - |a|^2 + |L_B^-1 a|^2, mixed through H = U sqrt(S) and sigma2 exactly as lmm_oilmm_mean_and_var does;
+ *                    output layout as there (partial sums over the handle's shard; var may be NULL).  gps is not read (the handle
+ *                    keeps its latents) and may be NULL.
+ *   lmm_dev_sparse_moments : building block exported for tests (DEVICE pointers x, z, w, r, Phi, b, scalars; gp on the host): one
+ *                    latent's Phi (nz x nz column-major, ld >= nz; only the lower triangle is written), b (nz) and scalars = (s,
+ *                    kappa, lambda) for per-point noise w (n) and data r (n).  chunk: points per partial sum (0: the library's
+ *                    default); partials are added in chunk order, so equal arguments give bitwise equal results. */
+typedef struct lmm_sparse_post lmm_sparse_post_t;
+int lmm_oilmm_elbo(const double* x, int d, int n, const double* y, int p,
+                   const double* U, const double* S, int m, double sigma2,
+                   const lmm_gp_t* gps, int latent_begin, int latent_end,
+                   const double* z, int nz, double jitter, int with_regulariser, double* elbo, double* dtc);
+int lmm_oilmm_sparse_posterior_create(const double* x, int d, int n, const double* y, int p,
+                                      const double* U, const double* S, int m, double sigma2,
+                                      const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                      const double* z, int nz, double jitter, lmm_sparse_post_t** out);
+int lmm_sparse_post_destroy(lmm_sparse_post_t* post);
+int lmm_oilmm_sparse_mean_and_var(const lmm_sparse_post_t* post, const lmm_gp_t* gps, const double* U, const double* S, int p, int m,
+                                  double sigma2, int add_noise, const double* xs, int d, int ns, double* mean, double* var);
+int lmm_dev_sparse_moments(const double* x, int d, int n, const double* z, int nz, const lmm_gp_t* gp, const double* w,
+                           const double* r, int chunk, double* Phi, int ld, double* b, double* scalars);
+
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard
  * normals in the reference's draw order: z_lat = m blocks of ns (latent order), eps = ns*p (by-outputs),

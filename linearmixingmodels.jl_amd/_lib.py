@@ -31,8 +31,20 @@ SYMBOLS = [
     "lmm_oilmm_posterior_create", "lmm_mogp_posterior_create", "lmm_post_condition", "lmm_ilmm_posterior_create", "lmm_post_destroy", "lmm_ilmm_post_latent_view", "lmm_ilmm_post_mean_and_var", "lmm_ilmm_post_mean_and_cov", "lmm_ilmm_post_condition", "lmm_ilmm_post_logpdf", "lmm_ilmm_post_rand",
     "lmm_latent_marginals", "lmm_oilmm_mean_and_var", "lmm_oilmm_mean_and_var_grad_xs", "lmm_lmm_mean_and_cov", "lmm_mogp_cross_cov", "lmm_oilmm_post_logpdf", "lmm_lmm_rand", "lmm_lmm_rand_multi", "lmm_normals",
     "lmm_profile_begin", "lmm_profile_end",
+    "lmm_oilmm_elbo", "lmm_oilmm_sparse_posterior_create", "lmm_sparse_post_destroy", "lmm_oilmm_sparse_mean_and_var", "lmm_dev_sparse_moments",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
 ]
+
+
+# Argument types of the inducing-point entry points (include/lmm_hip.h, "inducing points"), set on the library by load().
+_P, _I, _D = C.c_void_p, C.c_int, C.c_double
+SPARSE_ARGTYPES = {
+    "lmm_oilmm_elbo": [_P, _I, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _P, _I, _D, _I, _P, _P],
+    "lmm_oilmm_sparse_posterior_create": [_P, _I, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _P, _I, _D, _P],
+    "lmm_sparse_post_destroy": [_P],
+    "lmm_oilmm_sparse_mean_and_var": [_P, _P, _P, _P, _I, _I, _D, _I, _P, _I, _I, _P, _P],
+    "lmm_dev_sparse_moments": [_P, _I, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P],
+}
 
 
 class GpT(C.Structure):
@@ -86,6 +98,9 @@ def load() -> C.CDLL:
             pass
         _lib = C.CDLL(LIB_PATH)
         _lib.lmm_last_error_string.restype = C.c_char_p
+        for name, types in SPARSE_ARGTYPES.items():
+            fn = getattr(_lib, name)
+            fn.argtypes, fn.restype = types, C.c_int
     return _lib
 
 

@@ -4383,6 +4383,310 @@ int lmm_lmm_rand(const lmm_post_t* post, const lmm_gp_t* gps, const double* U, c
   return lmm_lmm_rand_multi(post, gps, U, S, p, m, latent_begin, latent_end, sigma2, add_noise, xs, d, ns, 1, z_lat, eps, jit, out);
 }
 
+// ------------------------------------------------------------------------------------------------
+// inducing points (VFE)
+// ------------------------------------------------------------------------------------------------
+#define LMM_SPARSE_POST_MAGIC 0x56464531     // a handle of another kind handed to a sparse entry point is refused, not read
+struct lmm_sparse_post {
+  int magic = LMM_SPARSE_POST_MAGIC;
+  int d = 0, nz = 0, l0 = 0, l1 = 0, m = 0;
+  int NC = 0, NR = 0, ld = 0;
+  std::shared_ptr<LatentSet> ls;
+  Buf<double> z;                            // d x nz
+  std::vector<Buf<double>> Lu, Wu;          // per latent of the shard: factor of K_uu + jitter I and its inverse diagonal blocks
+  std::vector<Buf<double>> LB, WB;          // the same for B = I + L_u^-1 Phi L_u^-T
+  std::vector<Buf<double>> c;               // L_B^-1 L_u^-1 b (NC values, zero beyond nz)
+};
+
+// What the n data points contribute, and the two M x M factorisations, for the latents [l0, l1).
+struct SparseState {
+  std::vector<Buf<double>> Lu, Wu, LB, WB, c;
+  std::vector<double> dtc, elbo;            // per latent of the shard
+};
+
+static int sparse_shape_check(int d, int nz, double jitter) {
+  if (nz > LMM_SPARSE_MMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for at most %d inducing points (nz = %d)", LMM_SPARSE_MMAX, nz);
+  if (d > LMM_SPARSE_DMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for d <= %d (d = %d)", LMM_SPARSE_DMAX, d);
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  if (!(jitter > 0.0) || !std::isfinite(jitter)) return fail(LMM_ERR_ARG, "jitter must be finite and > 0");
+  return LMM_OK;
+}
+
+static void sparse_fill_lat(SparseLat& s, const Latent& gp, const double* w, double wconst, const double* r, double rsub) {
+  s.g = gp.dev(); s.w = w; s.wconst = wconst; s.r = r; s.rsub = rsub; s.kdiag = gp.prior_var();
+  s.sum_per = gp.is_sum() && gp.has_periodic();
+}
+
+// Partials per chunk for nb latents: checks an explicit chunk, or picks the default.
+static int sparse_plan(int n, int nz, int nb, int chunk, int* chunk_out, int* nch_out) {
+  if (chunk < 0) return fail(LMM_ERR_ARG, "chunk must be >= 0");
+  if (chunk == 0) chunk = sparse_default_chunk(n, nz, nb);
+  const long long nch = ((long long)n + chunk - 1) / chunk;
+  if (nch > 65535 || (double)nch * nb * (double)sparse_partial_stride(nz) * 8.0 > 2e9)
+    return fail(LMM_ERR_ARG, "chunk = %d gives %lld partials for n = %d: too many (raise chunk, or pass 0)", chunk, nch, n);
+  *chunk_out = chunk; *nch_out = (int)nch;
+  return LMM_OK;
+}
+
+// rv: device, the projected data of latent l0 + k at rv + k * n (its mean rsub[l0 + k] is subtracted by the kernel); wconst[l0 + k]: its
+// noise.  keep: the factors stay in `out` (posterior), else only dtc / elbo are filled.  Caller holds g_mu; runs on streams[0].
+static int sparse_core(const double* xd, int d, int n, const double* zd, int nz, double jitter, const Latent* lts, int l0, int l1,
+                       const double* rv, const double* rsub, const double* wconst, SparseState& out) {
+  const int ms = l1 - l0, M = nz;
+  out.dtc.assign(ms, 0.0); out.elbo.assign(ms, 0.0);
+  if (ms == 0) return LMM_OK;
+  hipStream_t st = g.streams[0];
+  Dims D(M, 1);
+  const int nb_per = std::min(ms, LMM_MAX_BATCH);
+  for (int k = 0; k < ms; ++k) {
+    out.Lu.emplace_back(D.elems()); out.Wu.emplace_back((size_t)(D.NC / 64) * 4096);
+    out.LB.emplace_back(D.elems()); out.WB.emplace_back((size_t)(D.NC / 64) * 4096);
+    out.c.emplace_back((size_t)D.NC);
+  }
+  std::vector<Buf<double>> Q;
+  for (int j = 0; j < nb_per; ++j) Q.emplace_back(D.elems());
+  // b (NC per latent); res = [3 ms: s, kappa, lambda | ms: tr Q | 2 ms: -(M log 2pi + log det B + q) / 2 with q = c'c, then q = 0 (the zero row under the rider)]; two pivot-info words per latent
+  Buf<double> bvec((size_t)D.NC * ms), res((size_t)6 * ms);
+  Buf<int> info((size_t)2 * ms);
+  HIPCHK(hipMemsetAsync(info.p, 0, (size_t)2 * ms * sizeof(int), st));
+  int chunk = 0, nch = 0;
+  if (int rc = sparse_plan(n, nz, nb_per, 0, &chunk, &nch)) return rc;
+  Buf<double> scratch((size_t)nb_per * nch * sparse_partial_stride(nz));
+  fork_slots(1);
+  for (int k0 = 0; k0 < ms; k0 += nb_per) {
+    const int nb = std::min(nb_per, ms - k0);
+    SparseMomArgs a{};
+    a.x = xd; a.z = zd; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.scratch = scratch.p;
+    BatchPtr Pb{}, Qb{}, bb{}, sb{};
+    Batch Bu, Bb;
+    GramArgs ga[LMM_MAX_BATCH];
+    for (int j = 0; j < nb; ++j) {
+      const int k = k0 + j;
+      const Latent& gp = lts[l0 + k];
+      sparse_fill_lat(a.lat[j], gp, nullptr, wconst[l0 + k], rv + (size_t)k * n, rsub[l0 + k]);
+      Pb.p[j] = out.LB[k].p; Qb.p[j] = Q[j].p; bb.p[j] = bvec.p + (size_t)k * D.NC; sb.p[j] = res.p + (size_t)3 * k;
+      HIPCHK(hipMemsetAsync(out.LB[k].p, 0, D.elems() * sizeof(double), st));      // Phi's pad rows and columns
+      GramArgs r{};
+      r.A = out.Lu[k].p; r.ld = D.ld; r.nrows = D.NR; r.ncols = D.NC; r.x = zd; r.d = d; r.n = M;
+      gp.set_kernel(r); r.pad_diag = 1.0; r.diag_add = jitter;
+      r.rider = bb.p[j]; r.rider_ld = D.NC; r.nrider = 1;
+      ga[j] = r;
+      Bu.add(out.Lu[k].p, out.Wu[k].p, info.p + k);
+      Bb.add(out.LB[k].p, out.WB[k].p, info.p + ms + k);
+    }
+    launch_sparse_moments(a, nb, st);
+    launch_sparse_finish(scratch.p, nch, nz, Pb, D.ld, true, bb, sb, nb, st);
+    // L_u = chol(K_uu + jitter I), with b as the rider row: it becomes c0 = L_u^-1 b
+    gram_batch_g(ga, nb, st, "inducing Gram assembly");
+    potrf_batch(Bu, D.ld, D.NR, D.NC, M, st, D.NC + 1);
+    // Q = L_u^-1 Phi L_u^-T: Phi L_u^-T, transposed, solved again (Phi is symmetric)
+    trsm_rec(Pb, D.ld, D.NC, Bu.A, D.ld, Bu.W, nb, 0, D.NC, st, false, true, true);      // (no split-K atomics: M x M work)
+    launch_sparse_transpose(Pb, Qb, D.ld, D.NC, nb, st);
+    trsm_rec(Qb, D.ld, D.NC, Bu.A, D.ld, Bu.W, nb, 0, D.NC, st, false, true, true);
+    // B = I + Q with the rider c0 (overwrites the Phi buffer), L_B = chol(B), rider c = L_B^-1 c0
+    for (int j = 0; j < nb; ++j) guard_extent(Pb.p[j], D.NR, D.ld, D.NC, true, "B assembly");
+    launch_sparse_bmat(Qb, Bu.A, Pb, D.ld, D.NC, D.NR, M, res.p + (size_t)3 * ms + k0, nb, st);
+    potrf_batch(Bb, D.ld, D.NR, D.NC, M, st, D.NC + 1);
+    launch_lml_reduce(Bb.A, nb, D.ld, M, D.NC, 2, res.p + (size_t)4 * ms + (size_t)2 * k0, st);
+    BatchPtr cb{};
+    for (int j = 0; j < nb; ++j) cb.p[j] = out.c[k0 + j].p;
+    launch_extract_rows(Bb.A, nb, D.ld, D.NC, M, D.NC, cb, cb, st);
+  }
+  join_slots(1);
+  std::vector<double> hres((size_t)6 * ms);
+  std::vector<int> hinfo((size_t)2 * ms);
+  HIPCHK(hipMemcpyAsync(hres.data(), res.p, hres.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, hinfo.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (int rc = check_info(hinfo.data(), ms, l0)) { if (rc == LMM_ERR_NOT_PD) g.err += " [K_uu + jitter I of the inducing points]"; return rc; }
+  if (int rc = check_info(hinfo.data() + ms, ms, l0)) { if (rc == LMM_ERR_NOT_PD) g.err += " [B = I + L_u^-1 Phi L_u^-T]"; return rc; }
+  for (int k = 0; k < ms; ++k) {
+    const double* r = hres.data() + (size_t)3 * k;       // s, kappa, lambda
+    // the Gaussian form carries -c'c / 2, the bound +c'c / 2: c'c = 2 (g0 - gc) from the two reductions
+    const double gc = hres[(size_t)4 * ms + 2 * k], g0 = hres[(size_t)4 * ms + 2 * k + 1];
+    out.dtc[k] = 2.0 * g0 - gc + 0.5 * M * kLog2Pi - 0.5 * ((double)n * kLog2Pi + r[2] + r[0]);
+    out.elbo[k] = out.dtc[k] - 0.5 * (r[1] - hres[(size_t)3 * ms + k]);
+  }
+  return LMM_OK;
+}
+
+// The per-latent residual rows (T y)_l, the projected noise and (with_regulariser) the regulariser of lmm_oilmm_logpdf, then sparse_core.
+static int sparse_oilmm(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                        const lmm_gp_t* gps, int l0, int l1, const double* z, int nz, double jitter, int with_regulariser,
+                        SparseState& out, double* reg, std::shared_ptr<LatentSet>* ls_out, Buf<double>* z_keep) {
+  if (!x || !y || !U || !S || !z || d <= 0 || n <= 0 || p <= 0 || m <= 0 || nz <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
+  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
+  if (int rc = sparse_shape_check(d, nz, jitter)) return rc;
+  if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
+  RESOLVE(gps, m, d);
+  hipStream_t st0 = g.streams[0];
+  std::vector<double> T, ST, H;
+  project_orthogonal(U, S, p, m, sigma2, T, ST, H);
+  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
+  Buf<double> zown((size_t)d * nz);
+  HIPCHK(hipMemcpyAsync(zown.p, z, (size_t)d * nz * sizeof(double), hipMemcpyDefault, st0));
+  std::vector<double> means(m);
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  // (T y) of every latent when the regulariser needs the residual, else of the shard
+  const int c0 = with_regulariser ? 0 : l0, C = with_regulariser ? m : std::max(l1 - l0, 1);
+  Uploaded Td(T, st0), Hd(H, st0);
+  Buf<double> Ty((size_t)n * C), resid_dev(1), partial(tall_skinny_partials(n, p));
+  if (with_regulariser || l1 > l0) project_on_device(yd.p, n, p, Td.buf, m, c0, with_regulariser ? m : l1 - l0, nullptr, Ty.p, st0);
+  double resid = 0.0;
+  if (with_regulariser) {
+    residual_on_device(yd.p, n, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p, st0);
+    HIPCHK(hipMemcpyAsync(&resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
+  }
+  if (int rc = sparse_core(xd.p, d, n, zown.p, nz, jitter, lts, l0, l1, Ty.p + (size_t)(l0 - c0) * n, means.data(), ST.data(), out)) {
+    (void)hipStreamSynchronize(st0);      // the residual's copy targets this frame
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(st0));
+  *reg = 0.0;
+  if (with_regulariser) {        // reference src/oilmm.jl:101-113, as lmm_oilmm_logpdf
+    double logdetS = 0.0;
+    for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
+    *reg = -((double)n * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * sigma2)) + resid / sigma2) / 2.0;
+  }
+  if (ls_out) *ls_out = ls;
+  if (z_keep) *z_keep = std::move(zown);
+  return LMM_OK;
+}
+
+// elbo(VFE(f(z, jitter)), fx, y) and dtc(...) of AbstractGPs (src/sparse_approximations.jl) on the latents of an OILMM after the
+// projection of reference src/oilmm.jl:79-93: *elbo = sum_{l in shard} elbo_l + (with_regulariser ? reg : 0), *dtc likewise.
+int lmm_oilmm_elbo(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                   const lmm_gp_t* gps, int latent_begin, int latent_end, const double* z, int nz, double jitter,
+                   int with_regulariser, double* elbo, double* dtc) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!elbo && !dtc) return fail(LMM_ERR_ARG, "bad arguments");
+  SparseState st;
+  double reg = 0.0;
+  if (int rc = sparse_oilmm(x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, with_regulariser, st, &reg,
+                            nullptr, nullptr)) return rc;
+  double e = reg, t = reg;
+  for (size_t k = 0; k < st.elbo.size(); ++k) { e += st.elbo[k]; t += st.dtc[k]; }
+  if (elbo) *elbo = e;
+  if (dtc) *dtc = t;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// posterior(VFE(f(z, jitter)), fx, y) of AbstractGPs (ApproxPosteriorGP) per latent of the shard: keeps z, L_u, L_B and c.
+int lmm_oilmm_sparse_posterior_create(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m,
+                                      double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, const double* z, int nz,
+                                      double jitter, lmm_sparse_post_t** out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!out) return fail(LMM_ERR_ARG, "bad arguments");
+  SparseState st;
+  double reg = 0.0;
+  auto P = std::make_unique<lmm_sparse_post>();
+  if (int rc = sparse_oilmm(x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, 0, st, &reg, &P->ls, &P->z))
+    return rc;
+  Dims D(nz, 1);
+  P->d = d; P->nz = nz; P->l0 = latent_begin; P->l1 = latent_end; P->m = m; P->NC = D.NC; P->NR = D.NR; P->ld = D.ld;
+  P->Lu = std::move(st.Lu); P->Wu = std::move(st.Wu); P->LB = std::move(st.LB); P->WB = std::move(st.WB); P->c = std::move(st.c);
+  *out = P.release();
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_sparse_post_destroy(lmm_sparse_post_t* post) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (post) {
+    if (post->magic != LMM_SPARSE_POST_MAGIC) return fail(LMM_ERR_ARG, "not a handle of lmm_oilmm_sparse_posterior_create");
+    if (g.init) (void)hipDeviceSynchronize();
+    post->magic = 0;
+    delete post;
+  }
+  return LMM_OK;
+}
+
+// mean_and_var(post(xs, sigma2)) of the ApproxPosteriorGP latents, mixed as lmm_oilmm_mean_and_var mixes exact ones (reference
+// src/oilmm.jl:57-76).  Per latent, with a = L_u^-1 k_u(x*): mean = mean_l + (L_B^-1 a)' c, var = k** - |a|^2 + |L_B^-1 a|^2.
+// gps is not read (the handle keeps its latents).  Outputs: the shard's partial sums, ns * p, by outputs; var may be NULL.
+int lmm_oilmm_sparse_mean_and_var(const lmm_sparse_post_t* post, const lmm_gp_t* gps, const double* U, const double* S, int p, int m,
+                                  double sigma2, int add_noise, const double* xs, int d, int ns, double* mean_out, double* var_out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  (void)gps;
+  if (!post || !U || !S || !xs || !mean_out || d <= 0 || ns <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  if (post->magic != LMM_SPARSE_POST_MAGIC) return fail(LMM_ERR_ARG, "not a handle of lmm_oilmm_sparse_posterior_create");
+  if (post->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", post->m, m);
+  if (post->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, xs has d=%d", post->d, d);
+  const lmm_sparse_post* P = post;
+  const int l0 = P->l0, l1 = P->l1, ms = l1 - l0, M = P->nz;
+  hipStream_t st0 = g.streams[0];
+  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
+  for (int k = 0; k < ms; ++k)
+    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
+  Uploaded Hd(Hs, st0);
+  DevIn xsd(xs, (size_t)d * ns, st0);
+  Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1)), v1(ns), v2(ns), tmp(ns);
+  const int nsr = rup(ns, 64);
+  int ldr = nsr; if ((ldr % 512) == 0) ldr += 16;
+  Buf<double> R((size_t)ldr * P->NC), part(strip_partial_elems(nsr, P->NC, 2));
+  fork_slots(1);
+  for (int k = 0; k < ms; ++k) {
+    const Latent& gp = P->ls->lat[l0 + k];
+    GramArgs r{};      // R (nsr x NC, ldr) = K(xs, z) as rider rows, rows beyond ns zero
+    r.A = R.p; r.ld = ldr; r.nrows = P->NC + nsr; r.ncols = P->NC; r.row_tile0 = P->NC / 64; r.row_shift = P->NC; r.full = 1;
+    r.x = P->z.p; r.d = d; r.n = M; gp.set_kernel(r);
+    r.xs = xsd.p; r.ns = ns;
+    gram_g(r, st0, "inducing cross-Gram assembly");
+    BatchPtr Rb{}, Lub{}, Wub{}, LBb{}, WBb{};
+    Rb.p[0] = R.p; Lub.p[0] = P->Lu[k].p; Wub.p[0] = P->Wu[k].p; LBb.p[0] = P->LB[k].p; WBb.p[0] = P->WB[k].p;
+    trsm_rec(Rb, ldr, nsr, Lub, P->ld, Wub, 1, 0, P->NC, st0, false, true, true);      // rows a' = k_u(x*)' L_u^-T (no split-K atomics)
+    rider_stats_g(R.p, ldr, ns, M, P->c[k].p, 0.0, gp.prior_var(), part.p, tmp.p, v1.p, st0);      // v1 = k** - |a|^2
+    trsm_rec(Rb, ldr, nsr, LBb, P->ld, WBb, 1, 0, P->NC, st0, false, true, true);      // rows (L_B^-1 a)'
+    rider_stats_g(R.p, ldr, ns, M, P->c[k].p, gp.mean, 0.0, part.p, ml.p + (size_t)k * ns, v2.p, st0);   // v2 = -|L_B^-1 a|^2
+    launch_vec_lin(v1.p, v2.p, -1.0, ns, vl.p + (size_t)k * ns, st0);
+  }
+  join_slots(1);
+  DevOut mo(mean_out, (size_t)ns * p), vo(var_out, (size_t)ns * p);
+  mix_marginals(ml.p, ns, ms, Hd.buf.p, p, 1, 0.0, 0.0, mo.p, st0);
+  if (var_out) mix_marginals(vl.p, ns, ms, Hd.buf.p, p, 2, kDefaultJit.default_jitter, add_noise ? sigma2 : 0.0, vo.p, st0);
+  mo.finish(st0); vo.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Building block for tests: the moments of ONE latent from device pointers.  Phi: nz x nz column-major (ld), only its lower triangle
+// is written; b: nz; scalars: s, kappa, lambda.  chunk: points per partial (0: the library's default).
+int lmm_dev_sparse_moments(const double* x, int d, int n, const double* z, int nz, const lmm_gp_t* gp, const double* w, const double* r,
+                           int chunk, double* Phi, int ld, double* b, double* scalars) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !z || !gp || !w || !r || !Phi || !b || !scalars || d <= 0 || n <= 0 || nz <= 0 || ld < nz) return fail(LMM_ERR_ARG, "bad arguments");
+  if (nz > LMM_SPARSE_MMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for at most %d inducing points (nz = %d)", LMM_SPARSE_MMAX, nz);
+  if (d > LMM_SPARSE_DMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for d <= %d (d = %d)", LMM_SPARSE_DMAX, d);
+  RESOLVE(gp, 1, d);
+  int nch = 0;
+  if (int rc = sparse_plan(n, nz, 1, chunk, &chunk, &nch)) return rc;
+  hipStream_t st0 = g.streams[0];
+  Buf<double> scratch((size_t)nch * sparse_partial_stride(nz));
+  SparseMomArgs a{};
+  a.x = x; a.z = z; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.scratch = scratch.p;
+  sparse_fill_lat(a.lat[0], lts[0], w, 0.0, r, 0.0);
+  BatchPtr Pb{}, bb{}, sb{};
+  Pb.p[0] = Phi; bb.p[0] = b; sb.p[0] = scalars;
+  launch_sparse_moments(a, 1, st0);
+  launch_sparse_finish(scratch.p, nch, nz, Pb, ld, false, bb, sb, 1, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
 // Standard normals on the device (Philox4x32-10 + Box-Muller, Float64): out[j], j < count, reproducible for (seed, stream).
 // out may be a host or a device pointer.  Optional companion of lmm_lmm_rand / lmm_lmm_rand_multi, whose normals are
 // caller-supplied: the Julia shim draws them from the reference's rng on the host; this generator serves callers that do not

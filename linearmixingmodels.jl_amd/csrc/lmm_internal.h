@@ -252,6 +252,33 @@ void launch_missing_wdiag(const double* Kinv, int ld, int n, const double* alpha
 // gy (n x p) = -T_t' alpha_t - resid / s2 at observed entries (resid nullptr: first term only), 0 at missing ones; alpha: [ms][lda]
 void launch_missing_grad_y(int n, int p, int m, const int* pat_of, const unsigned long long* pmask, const double* Tpat,
                            const double* alpha, int lda, int l0, int ms, const double* resid, double s2, double* gy, hipStream_t st);
+// Inducing-point (VFE) moments.  All Float64 in both compute dtypes.
+#define LMM_SPARSE_MMAX 1024                  // most inducing points
+#define LMM_SPARSE_DMAX 32                    // widest input
+// One latent of a moments launch: its kernel, per-point noise w (device, n values; nullptr: the constant wconst), the projected data r
+// (device, n values; rsub is subtracted) and kdiag = kappa(0).
+struct SparseLat { LatentDev g; const double* w; const double* r; double wconst, rsub, kdiag; int sum_per; };   // sum_per: a sum with a (locally) periodic term
+struct SparseMomArgs {
+  const double* x; const double* z;           // d x n inputs, d x nz inducing inputs (device)
+  int d, n, nz, chunk, nch;                   // chunk points per partial, nch = ceil(n / chunk) partials
+  double* scratch;                            // nb * nch * sparse_partial_stride(nz) doubles
+  SparseLat lat[LMM_MAX_BATCH];
+};
+static_assert(sizeof(SparseMomArgs) <= 4096, "SparseMomArgs is passed by value: kernel arguments are limited to 4096 bytes");
+size_t sparse_partial_stride(int nz);         // doubles of one (latent, chunk) partial: the 64 x 64 tiles of Phi's lower triangle, b, 3 scalars
+int sparse_default_chunk(int n, int nz, int nb);
+// Phi (the lower 64 x 64 tiles with nz padded to 64, zero rows beyond nz), b, (s, kappa, lambda) of nb latents in one launch
+// (blockIdx.z = latent) into a.scratch, one partial per chunk; no atomics.
+void launch_sparse_moments(const SparseMomArgs& a, int nb, hipStream_t st);
+// The partials added in chunk order: Phi.p[l] (nz x nz, column-major ld; the lower triangle, mirror: also the upper), b.p[l] (nz),
+// scal.p[l] (3).
+void launch_sparse_finish(const double* scratch, int nch, int nz, const BatchPtr& Phi, int ld, bool mirror, const BatchPtr& b,
+                          const BatchPtr& scal, int nb, hipStream_t st);
+// Out.p[l] (N x N, ld) = In.p[l]'
+void launch_sparse_transpose(const BatchPtr& In, const BatchPtr& Out, int ld, int N, int nb, hipStream_t st);
+// Bm.p[l] (NR x NC, ld) = [I + sym(Q.p[l]) on the leading M x M, identity pad; rider row NC = row NC of Au.p[l]]; trace[l] = tr Q.p[l]
+void launch_sparse_bmat(const BatchPtr& Q, const BatchPtr& Au, const BatchPtr& Bm, int ld, int NC, int NR, int M, double* trace,
+                        int nb, hipStream_t st);
 void launch_atb(const double* X, int ldx, const double* Z, int ldz, int n, int na, int nb, double* out, hipStream_t st);
 void launch_fill(double* p, int n, double v, hipStream_t st);
 void launch_reorder(const double* in, int n, int p, int to_outputs, double* out, hipStream_t st);

@@ -4060,6 +4060,207 @@ __global__ void grad_x_finish_kernel(const double* __restrict__ partial, int nch
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Inducing-point (VFE) moments: for one latent, with A = K_uf diag(w)^-1/2 (M x n, never stored),
+//     Phi = A A',  b = A (r w^-1/2),  s = sum r^2 / w,  kappa = sum k(x_t, x_t) / w_t,  lambda = sum log w_t.
+// Workgroup (pair, c, l): the 64 x 64 tile (ti, tj), ti >= tj, of Phi of latent l over the points of chunk c.  Per step of SPM_KT points
+// the 256 threads evaluate the two 64-row panels of A (one on the diagonal) into LDS, k-major, each column scaled by w_t^-1/2; wave
+// w then multiplies rows 16 w .. 16 w + 15 of panel I with the 64 rows of panel J on v_mfma_f64_16x16x4_f64 (4 accumulator blocks
+// in architectural VGPRs).  Operand map as in trsm_nn_kernel: register r of acc[cb] of lane l is Phi[16 w + (l >> 4) + 4 r][16 cb + (l & 15)].
+// The pairs (ti, 0) also form b for their 64 rows, the pair (0, 0) the three scalars.  Rows beyond nz and points beyond the chunk are
+// zeros and are never evaluated (neither z nor x is read there).  Every sum has a fixed order: the partial of a chunk depends on
+// (chunk, c) only, and sparse_finish_kernel adds the partials in chunk order.
+// ---------------------------------------------------------------------------------------------------
+constexpr int SPM_KT = 32;                    // points per step
+constexpr int SPM_SA = 128 + 16;              // LDS stride of one point's 128 panel rows (fragment reads of the 4 k-lanes on distinct banks)
+
+// kappa of one latent at the pair (a, b) from its LatentDev, every kind: SUM as in dense_cross_kernel (1: sums, 2: also (locally) periodic)
+template <int SUM>
+__device__ __forceinline__ double kappa_lat(const LatentDev& g, const double* __restrict__ a, const double* __restrict__ b, int d) {
+  if (SUM == 2 && g.kind == LMM_KERNEL_PERIODIC) return kappa_per(g.var, g.alpha, per_q(a, b, d, g.inv_ls, g.ils));
+  if (SUM == 2 && g.kind == LMM_KERNEL_LOCALLY_PERIODIC) return kappa_lp_at(g.var, g.alpha, g.inv_decay, a, b, d, g.inv_ls, g.ils);
+  if (SUM && g.kind == LMM_KERNEL_SUM) return kappa_sum<SUM == 2>(g.terms, g.nterms, a, b, d);
+  double rr, r2;
+  if (d == 1) { rr = fabs(a[0] - b[0]) * g.inv_ls; r2 = rr * rr; }
+  else { r2 = scaled_dist2(a, b, d, g.inv_ls, g.ils); rr = sqrt(r2); }
+  return kappa(g.kind, g.var, rr, r2, g.alpha);
+}
+
+__device__ __forceinline__ void sparse_pair(int idx, int& ti, int& tj) {      // idx = ti (ti + 1) / 2 + tj, tj <= ti
+  ti = 0;
+  while ((ti + 1) * (ti + 2) / 2 <= idx) ++ti;
+  tj = idx - ti * (ti + 1) / 2;
+}
+
+template <int SUM>
+__global__ __launch_bounds__(256) void sparse_moments_kernel(SparseMomArgs a, size_t stride) {
+  __shared__ double P[SPM_KT * SPM_SA];
+  __shared__ double sc[SPM_KT], rs[SPM_KT];
+  __shared__ double red[3][SPM_KT];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  int ti, tj;
+  sparse_pair(blockIdx.x, ti, tj);
+  const int c = blockIdx.y, l = blockIdx.z;
+  const SparseLat& S = a.lat[l];
+  const LatentDev g = S.g;
+  const bool diag = ti == tj;
+  const int nrows = diag ? 64 : 128;                   // panel rows in LDS: 0..63 tile ti, 64..127 tile tj
+  const int prow = t & (nrows - 1), k0 = t / nrows, kstep = 256 / nrows;
+  const int zi = prow < 64 ? ti * 64 + prow : tj * 64 + prow - 64;
+  const bool zlive = zi < a.nz;
+  const double* zp = a.z + (size_t)(zlive ? zi : 0) * a.d;
+  const long long tbeg = (long long)c * a.chunk;
+  long long tend = tbeg + a.chunk;
+  if (tend > a.n) tend = a.n;
+  d4 acc[4];
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb) acc[cb] = (d4){0.0, 0.0, 0.0, 0.0};
+  double bacc = 0.0, s_acc = 0.0, k_acc = 0.0, l_acc = 0.0;
+  const int l15 = lane & 15, lk = lane >> 4;
+  const int offI = lk * SPM_SA + 16 * wv + l15;
+  const int offJ = lk * SPM_SA + (diag ? 0 : 64) + l15;
+  for (long long t0 = tbeg; t0 < tend; t0 += SPM_KT) {
+    if (t < SPM_KT) {
+      const long long tt = t0 + t;
+      double s = 0.0, rv = 0.0;
+      if (tt < tend) {
+        const double w = S.w ? S.w[tt] : S.wconst;
+        const double iw = 1.0 / w;
+        const double r = S.r[tt] - S.rsub;
+        s = sqrt(iw);
+        rv = r * s;
+        s_acc = __builtin_fma(r * r, iw, s_acc);
+        k_acc = __builtin_fma(S.kdiag, iw, k_acc);
+        l_acc += log(w);
+      }
+      sc[t] = s; rs[t] = rv;
+    }
+    __syncthreads();
+    for (int k = k0; k < SPM_KT; k += kstep) {
+      const long long tt = t0 + k;
+      double v = 0.0;
+      if (zlive && tt < tend) v = kappa_lat<SUM>(g, zp, a.x + (size_t)tt * a.d, a.d) * sc[k];
+      P[k * SPM_SA + prow] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s4 = 0; s4 < SPM_KT / 4; ++s4) {
+      const double fi = P[offI + 4 * s4 * SPM_SA];
+      double fj[4];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) fj[cb] = P[offJ + 4 * s4 * SPM_SA + 16 * cb];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(fi, fj[cb], acc[cb], 0, 0, 0);
+    }
+    if (tj == 0 && t < 64) {
+#pragma unroll 8
+      for (int k = 0; k < SPM_KT; ++k) bacc = __builtin_fma(P[k * SPM_SA + t], rs[k], bacc);
+    }
+    __syncthreads();
+  }
+  double* part = a.scratch + ((size_t)l * a.nch + c) * stride;
+  double* tile = part + (size_t)blockIdx.x * 4096;
+  // the tile leaves column-major (element (row, col) at col * 64 + row, the order sparse_finish_kernel reads and writes in), staged
+  // through the panel's LDS (free after the loop's last barrier) so that the global stores are contiguous
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) P[(16 * cb + l15) * 64 + 16 * wv + lk + 4 * r] = acc[cb][r];
+  __syncthreads();
+  for (int e = t; e < 4096; e += 256) tile[e] = P[e];
+  const size_t off_b = (size_t)gridDim.x * 4096;
+  const int Mp = (a.nz + 63) / 64 * 64;
+  if (tj == 0 && t < 64) part[off_b + ti * 64 + t] = bacc;
+  if (blockIdx.x == 0) {
+    if (t < SPM_KT) { red[0][t] = s_acc; red[1][t] = k_acc; red[2][t] = l_acc; }
+    __syncthreads();
+    if (t < 3) {
+      double v = 0.0;
+      for (int k = 0; k < SPM_KT; ++k) v += red[t][k];
+      part[off_b + Mp + t] = v;
+    }
+  }
+}
+
+// grid (npairs + 1, nb, 16): slice blockIdx.z (256 elements, four columns) of each tile of Phi; block npairs of slice 0: b and the
+// scalars.  Lanes walk the rows of a column: the partials are read and Phi is written contiguously.
+__global__ __launch_bounds__(256) void sparse_finish_kernel(const double* __restrict__ scratch, size_t stride, int nch, int nz, int npairs,
+                                                            BatchPtr Phi, int ld, int mirror, BatchPtr bv, BatchPtr scal) {
+  const int l = blockIdx.y, t = threadIdx.x;
+  const double* base = scratch + (size_t)l * nch * stride;
+  if ((int)blockIdx.x < npairs) {
+    int ti, tj;
+    sparse_pair(blockIdx.x, ti, tj);
+    double* out = Phi.p[l];
+    const int e = blockIdx.z * 256 + t;
+    const int row = e & 63, col = e >> 6;
+    const int gi = ti * 64 + row, gj = tj * 64 + col;
+    if (gi >= nz || gj >= nz || gi < gj) return;
+    const double* src = base + (size_t)blockIdx.x * 4096 + e;
+    double v = 0.0;
+    for (int c = 0; c < nch; ++c) v += src[(size_t)c * stride];
+    out[(size_t)gj * ld + gi] = v;
+    if (mirror && gi != gj) out[(size_t)gi * ld + gj] = v;
+    return;
+  }
+  if (blockIdx.z != 0) return;
+  const size_t off_b = (size_t)npairs * 4096;
+  const int Mp = (nz + 63) / 64 * 64;
+  for (int i = t; i < nz; i += 256) {
+    double v = 0.0;
+    for (int c = 0; c < nch; ++c) v += base[(size_t)c * stride + off_b + i];
+    bv.p[l][i] = v;
+  }
+  if (t < 3) {
+    double v = 0.0;
+    for (int c = 0; c < nch; ++c) v += base[(size_t)c * stride + off_b + Mp + t];
+    scal.p[l][t] = v;
+  }
+}
+
+// Out (N x N, ld) = In', 32 x 32 tiles through LDS; grid (ceil(N / 32), ceil(N / 32), nb)
+__global__ __launch_bounds__(256) void sparse_transpose_kernel(BatchPtr In, BatchPtr Out, int ld, int N) {
+  __shared__ double tl[32][33];
+  const double* __restrict__ in = In.p[blockIdx.z];
+  double* __restrict__ out = Out.p[blockIdx.z];
+  const int bx = blockIdx.x * 32, by = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = bx + tx, c = by + ty + 8 * q;
+    tl[ty + 8 * q][tx] = (r < N && c < N) ? in[(size_t)c * ld + r] : 0.0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = by + tx, c = bx + ty + 8 * q;
+    if (r < N && c < N) out[(size_t)c * ld + r] = tl[tx][ty + 8 * q];
+  }
+}
+
+// The factor matrix of B = I + L_u^-1 Phi L_u^-T from Q = L_u^-1 Phi L_u^-T (symmetrised: the two solves round its halves
+// differently), with the identity pad and the rider row c0 = L_u^-1 b, which is the rider row of the factored K_uu matrix Au.
+// grid (ceil(NR / 256), NC, nb)
+__global__ __launch_bounds__(256) void sparse_bmat_kernel(BatchPtr Q, BatchPtr Au, BatchPtr Bm, int ld, int NC, int NR, int M) {
+  const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, l = blockIdx.z;
+  if (i >= NR) return;
+  const double* __restrict__ q = Q.p[l];
+  double v = 0.0;
+  if (i < M && j < M) v = 0.5 * (q[(size_t)j * ld + i] + q[(size_t)i * ld + j]) + (i == j ? 1.0 : 0.0);
+  else if (i == j) v = 1.0;
+  else if (i == NC && j < M) v = Au.p[l][(size_t)j * ld + NC];
+  Bm.p[l][(size_t)j * ld + i] = v;
+}
+
+// trace[l] = sum_k Q[k, k], k < M; one workgroup per matrix
+__global__ __launch_bounds__(256) void sparse_trace_kernel(BatchPtr Q, int ld, int M, double* __restrict__ trace) {
+  __shared__ double sh[4];
+  const double* __restrict__ q = Q.p[blockIdx.x];
+  double s = 0.0;
+  for (int k = threadIdx.x; k < M; k += 256) s += q[(size_t)k * ld + k];
+  const double tot = block_sum_256(s, sh);
+  if (threadIdx.x == 0) trace[blockIdx.x] = tot;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Right solve by L^-1 (predictive-marginal gradients): C (M x N) {=, -=} A (M x K) * B (K x N), column-major, NN form,
 // batched over up to LMM_MAX_BATCH matrices (blockIdx.y), on v_mfma_f64_16x16x4_f64.  M, N multiples of 64, K of 16.
 //   SET = true : the 64-column leaf X_J = R_J W_J by a stored inverse diagonal block, IN PLACE (C == A): a workgroup owns all N = 64
@@ -5401,4 +5602,50 @@ void launch_pred_grad_x(const double* xs, int ns, const double* x, int n, int d,
 #undef LMM_PGX_LAUNCH
   const size_t count = (size_t)ns * d;
   hipLaunchKernelGGL(grad_x_finish_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, partial, nch, count, accumulate ? 1 : 0, gx);
+}
+
+// ---- inducing-point moments ---------------------------------------------------------------------------------------
+size_t sparse_partial_stride(int nz) {
+  const size_t tm = (nz + 63) / 64;
+  return tm * (tm + 1) / 2 * 4096 + tm * 64 + 4;
+}
+// Points per partial: enough chunks that the launch has ~2048 workgroups, none shorter than 256 points (a partial is a 32-KB tile per
+// pair, written once and read once), a multiple of the SPM_KT-point step.
+int sparse_default_chunk(int n, int nz, int nb) {
+  const long long tm = (nz + 63) / 64, pairs = tm * (tm + 1) / 2 * (nb < 1 ? 1 : nb);
+  long long nch = (2048 + pairs - 1) / pairs;
+  const long long most = ((long long)n + 255) / 256;
+  if (nch > most) nch = most;
+  if (nch < 1) nch = 1;
+  long long chunk = ((long long)n + nch - 1) / nch;
+  chunk = (chunk + SPM_KT - 1) / SPM_KT * SPM_KT;
+  return (int)chunk;
+}
+void launch_sparse_moments(const SparseMomArgs& a, int nb, hipStream_t st) {
+  const int tm = (a.nz + 63) / 64;
+  const dim3 grid(tm * (tm + 1) / 2, a.nch, nb);
+  const size_t stride = sparse_partial_stride(a.nz);
+  int mode = 0;
+  for (int l = 0; l < nb; ++l) {
+    const LatentDev& g = a.lat[l].g;
+    if (g.kind == LMM_KERNEL_PERIODIC || g.kind == LMM_KERNEL_LOCALLY_PERIODIC || a.lat[l].sum_per) mode = 2;
+    else if (g.kind == LMM_KERNEL_SUM && mode < 1) mode = 1;
+  }
+  if (mode == 2) hipLaunchKernelGGL(sparse_moments_kernel<2>, grid, dim3(256), 0, st, a, stride);
+  else if (mode == 1) hipLaunchKernelGGL(sparse_moments_kernel<1>, grid, dim3(256), 0, st, a, stride);
+  else hipLaunchKernelGGL(sparse_moments_kernel<0>, grid, dim3(256), 0, st, a, stride);
+}
+void launch_sparse_finish(const double* scratch, int nch, int nz, const BatchPtr& Phi, int ld, bool mirror, const BatchPtr& b,
+                          const BatchPtr& scal, int nb, hipStream_t st) {
+  const int tm = (nz + 63) / 64, npairs = tm * (tm + 1) / 2;
+  hipLaunchKernelGGL(sparse_finish_kernel, dim3(npairs + 1, nb, 16), dim3(256), 0, st, scratch, sparse_partial_stride(nz), nch, nz, npairs,
+                     Phi, ld, mirror ? 1 : 0, b, scal);
+}
+void launch_sparse_transpose(const BatchPtr& In, const BatchPtr& Out, int ld, int N, int nb, hipStream_t st) {
+  hipLaunchKernelGGL(sparse_transpose_kernel, dim3((N + 31) / 32, (N + 31) / 32, nb), dim3(256), 0, st, In, Out, ld, N);
+}
+void launch_sparse_bmat(const BatchPtr& Q, const BatchPtr& Au, const BatchPtr& Bm, int ld, int NC, int NR, int M, double* trace,
+                        int nb, hipStream_t st) {
+  hipLaunchKernelGGL(sparse_bmat_kernel, dim3((NR + 255) / 256, NC, nb), dim3(256), 0, st, Q, Au, Bm, ld, NC, NR, M);
+  hipLaunchKernelGGL(sparse_trace_kernel, dim3(nb), dim3(256), 0, st, Q, ld, M, trace);
 }

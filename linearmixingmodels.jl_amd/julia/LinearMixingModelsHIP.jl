@@ -447,6 +447,29 @@ function AbstractGPs.posterior(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:
     return ILMM(HIPMOGP(fs.fs, h[], [(X, Float64(σ²), yv)]), H)    # again an ILMM with the same H (src/oilmm.jl:133)
 end
 
+# ---- inducing points: AbstractGPs' VFE(f(z, ε)) on the latents of an OILMM -----------------------------------------------------------
+# elbo(VFE(f(z, ε)), fx, y) and dtc(...) (AbstractGPs src/sparse_approximations.jl) through lmm_oilmm_elbo (include/lmm_hip.h,
+# "inducing points"): Titsias' collapsed bound per latent after the OILMM projection, plus the regulariser of src/oilmm.jl:101-113.
+# z = vfe.fz.x.x (by outputs, shared by all latents), ε = the Fill noise of vfe.fz.  Prior OILMM only.  posterior(::VFE, fx, y) is
+# served by the C ABI and the Python mirror (lmm_oilmm_sparse_posterior_create, approx_posterior) and not yet by this shim.
+function _elbo_dtc(vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real})
+    fs, H, σ², x = unpack(fx)
+    isposterior(fs) && error("inducing-point inference is served on a prior OILMM only")
+    X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); yv = Vector{Float64}(y)
+    Z = _xmat(vfe.fz.x.x); ε = Float64(noise_var(vfe.fz.Σy))
+    size(Z, 1) == d || error("the inducing inputs have d = $(size(Z, 1)), the inputs d = $d")
+    e = Ref{Cdouble}(0.0); t = Ref{Cdouble}(0.0)
+    _gps(fs.fs) do gps, tags
+        GC.@preserve X yv U S Z gps check(ccall((:lmm_oilmm_elbo, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint,
+             Ptr{Cdouble}, Cint, Cdouble, Cint, Ref{Cdouble}, Ref{Cdouble}),
+            X, d, n, yv, p, U, S, m, σ², gps, 0, m, Z, size(Z, 2), ε, 1, e, t))
+    end
+    return e[], t[]
+end
+AbstractGPs.elbo(vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real}) = _elbo_dtc(vfe, fx, y)[1]
+AbstractGPs.dtc(vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real}) = _elbo_dtc(vfe, fx, y)[2]
+
 # ---- missing observations: y::AbstractVector{Union{Missing,Float64}} ----------------------------------------------------------------
 # The reference's notebook: "Heterotopic and missing data ... are not supported yet ... using the missing data techniques identified in
 # the paper".  `missing` becomes NaN and the prior OILMM goes through the library's *_missing entry points (include/lmm_hip.h, "missing

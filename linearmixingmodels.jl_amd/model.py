@@ -660,6 +660,145 @@ class _NoMixingGradient(dict):
         raise KeyError(key)
 
 
+# ---- inducing points (VFE) -------------------------------------------------------------------------------
+# AbstractGPs' VFE(f(z)) with elbo, dtc and posterior(VFE(...), fx, y) on the independent latents of an OILMM (include/lmm_hip.h,
+# "inducing points"): linear cost in n.  `posterior` keeps its two-argument form; the sparse one is approx_posterior.
+class VFE:
+    """VFE(z, jitter=1e-6): the inducing inputs z, shaped like the model's inputs ((M,) or (d, M)), shared by all latents, and the jitter
+    added to the diagonal of K_uu (AbstractGPs' VFE(f(z, jitter)))."""
+
+    def __init__(self, z, jitter: float = 1e-6):
+        if not hasattr(z, "shape"):
+            z = np.asarray(z, dtype=np.float64)
+        if len(z.shape) not in (1, 2) or int(z.shape[-1]) == 0 or (len(z.shape) == 2 and int(z.shape[0]) == 0):
+            raise ValueError("VFE: z must be a non-empty (M,) or (d, M) array of inducing inputs")
+        jitter = float(jitter)
+        if not (jitter > 0.0 and np.isfinite(jitter)):
+            raise ValueError("VFE: jitter must be finite and > 0")
+        self.z, self.jitter = z, jitter
+
+    @property
+    def dim(self) -> int:
+        return 1 if len(self.z.shape) == 1 else int(self.z.shape[0])
+
+    @property
+    def nz(self) -> int:
+        return int(self.z.shape[-1])
+
+    def carr(self) -> L.Arr:
+        return MOInputIsotopicByOutputs(self.z, 1).carr()
+
+
+class _SparsePostHandle:
+    """Owns an lmm_sparse_post_t* (z, L_u, L_B and c per latent, on the device)."""
+    sparse = True
+
+    def __init__(self, ptr: C.c_void_p, l0: int, l1: int):
+        self.ptr, self.l0, self.l1, self.dense, self.train = ptr, l0, l1, False, None
+
+    def __del__(self):
+        try:
+            if self.ptr:
+                L.load().lmm_sparse_post_destroy(self.ptr)
+                self.ptr = None
+        except Exception:
+            pass
+
+
+def _sparse_post(fx) -> Optional[_SparsePostHandle]:
+    """The inducing-point handle behind a FiniteGP, or behind a model passed as it is (cov(f::IndependentMOGP, x, y)), else None."""
+    f = fx if isinstance(fx, (IndependentMOGP, ILMM)) else getattr(fx, "f", None)
+    post = f._post if isinstance(f, IndependentMOGP) else (f.f._post if isinstance(f, ILMM) else None)
+    return post if isinstance(post, _SparsePostHandle) else None
+
+
+def _refuse_sparse(fx, what: str) -> None:
+    if _sparse_post(fx) is not None:
+        raise NotImplementedError(f"{what} is not served on an inducing-point posterior (approx_posterior): it answers mean_and_var, "
+                                  "mean, var and marginals")
+
+
+def _sparse_args(vfe: VFE, fx: "FiniteGP", y, what: str):
+    """Checks of elbo / dtc / approx_posterior, all before any library call."""
+    if not isinstance(vfe, VFE):
+        raise TypeError(f"{what}: the first argument is a VFE(z, jitter)")
+    f, x = fx.f, fx.x
+    if isinstance(f, IndependentMOGP):
+        raise NotImplementedError(f"{what}: inducing-point inference is not served for an IndependentMOGP (wrap it in an OILMM)")
+    if not isinstance(f, ILMM) or not f.is_oilmm:
+        raise NotImplementedError(f"{what}: inducing-point inference is not served for a dense-H ILMM (OILMM only)")
+    if f.f._post is not None:
+        raise NotImplementedError(f"{what}: inducing-point inference is not served on a posterior model (prior OILMM only)")
+    if f.shard != (0, len(f.f.fs)):
+        raise NotImplementedError(f"{what}: inducing-point inference is not served with latents sharded across processes")
+    if not isinstance(x, MOInputIsotopicByOutputs) or fx.heteroscedastic:
+        raise NotImplementedError(f"{what}: inducing-point inference takes MOInputIsotopicByOutputs inputs and a scalar noise variance")
+    if not hasattr(y, "shape"):
+        y = np.asarray(y, dtype=np.float64)
+    if len(y.shape) != 1:
+        raise NotImplementedError(f"{what}: inducing-point inference is not served for a matrix Y (one vector y)")
+    if _has_nan(y):
+        raise NotImplementedError(f"{what}: inducing-point inference is not served with missing observations (NaN in y)")
+    unpack(fx)
+    if y.shape[0] != x.n * x.out_dim:
+        raise ValueError("length(y) != n * out_dim")
+    if vfe.dim != x.dim:
+        raise ValueError(f"{what}: the inducing inputs have d = {vfe.dim}, the inputs d = {x.dim}")
+    return y
+
+
+def _elbo_dtc(vfe: VFE, fx: "FiniteGP", y, with_regulariser: bool, what: str):
+    y = _sparse_args(vfe, fx, y, what)
+    L.ensure_init()
+    f, x = fx.f, fx.x
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    e, t = C.c_double(), C.c_double()
+    L.check(L.load().lmm_oilmm_elbo(x.carr().ptr, x.dim, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps, 0, m,
+                                    vfe.carr().ptr, vfe.nz, vfe.jitter, int(with_regulariser), C.byref(e), C.byref(t)))
+    return e.value, t.value
+
+
+def elbo(vfe: VFE, fx: "FiniteGP", y, with_regulariser: bool = True) -> float:
+    """elbo(VFE(f(z)), fx, y) of AbstractGPs (Titsias' collapsed bound) summed over the latents of an OILMM, plus the OILMM
+    regulariser (reference src/oilmm.jl:101-113): a lower bound of logpdf(fx, y)."""
+    return _elbo_dtc(vfe, fx, y, with_regulariser, "elbo")[0]
+
+
+def dtc(vfe: VFE, fx: "FiniteGP", y, with_regulariser: bool = True) -> float:
+    """dtc(VFE(f(z)), fx, y) of AbstractGPs: the log density under the low-rank prior Q_ff (the bound without its trace term)."""
+    return _elbo_dtc(vfe, fx, y, with_regulariser, "dtc")[1]
+
+
+def approx_posterior(vfe: VFE, fx: "FiniteGP", y) -> "ILMM":
+    """posterior(VFE(f(z)), fx, y) of AbstractGPs: an OILMM with the same H whose latents are ApproxPosteriorGPs.  mean_and_var, mean,
+    var and marginals work on it; nothing else does."""
+    y = _sparse_args(vfe, fx, y, "approx_posterior")
+    L.ensure_init()
+    f, x = fx.f, fx.x
+    gps = L.gps_array([g.desc() for g in f.f.fs])
+    Ua, Sa, p, m = _H_args(f.H)
+    handle = C.c_void_p()
+    L.check(L.load().lmm_oilmm_sparse_posterior_create(x.carr().ptr, x.dim, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2),
+                                                       gps, 0, m, vfe.carr().ptr, vfe.nz, vfe.jitter, C.byref(handle)))
+    return ILMM(IndependentMOGP(f.f.fs, _SparsePostHandle(handle, 0, m)), f.H, shard=f.shard)
+
+
+def _sparse_mean_and_var(fx: "FiniteGP", add_noise: bool, want_var: bool):
+    f, x = fx.f, fx.x
+    if not isinstance(f, ILMM) or not isinstance(x, MOInputIsotopicByOutputs):
+        raise NotImplementedError("an inducing-point posterior is an OILMM over MOInputIsotopicByOutputs inputs")
+    unpack(fx)
+    L.ensure_init()
+    Ua, Sa, p, m = _H_args(f.H)
+    mean = _alloc_like(x.x, x.n * p)
+    var = _alloc_like(x.x, x.n * p) if want_var else None
+    L.check(L.load().lmm_oilmm_sparse_mean_and_var(f.f._post.ptr, None, Ua.ptr, Sa.ptr, p, m, float(fx.sigma2), int(add_noise),
+                                                   x.carr().ptr, x.dim, x.n, L.Arr(mean, True).ptr,
+                                                   L.Arr(var, True).ptr if want_var else None))
+    return mean, var
+
+
 # Dense-H ILMM logpdf: allow the identical-kernel decoupled shortcut (exact; SURVEY.md section 3.2).  Set False to force
 # the reference's single (mn) x (mn) factorisation.  ILMM_LAST_PATH records which ran.
 ILMM_ALLOW_DECOUPLED = True
@@ -671,6 +810,7 @@ def logpdf(fx: FiniteGP, y, with_regulariser: bool = True) -> float:
     """logpdf(fx, y).  ILMM/OILMM: reference src/oilmm.jl:79-93, src/ilmm.jl:150-163; IndependentMOGP:
     src/independent_mogp.jl:74-80.  Returns this process's shard of the sum (the whole value when the model
     is not sharded)."""
+    _refuse_sparse(fx, "logpdf")
     L.ensure_init()
     lib = L.load()
     if _has_nan(y):
@@ -806,6 +946,7 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True, inputs: 
     A y with NaN (missing observations, prior OILMM only): {"value", "y" (0 at the missing entries), "sigma2", "gps"}; "S", "U" and
     inputs=True raise NotImplementedError.
     Partial sums over the latent shard."""
+    _refuse_sparse(fx, "logpdf_and_gradient")
     L.ensure_init()
     lib = L.load()
     if _has_nan(y):
@@ -973,6 +1114,7 @@ def _more_train(post: "_PostHandle", x, s2, y):
 def posterior(fx: FiniteGP, y):
     """posterior(fx, y): reference src/oilmm.jl:116-134 (returns ILMM(independent_mogp(posteriors), H) -- again
     an OILMM with the same H) and src/independent_mogp.jl:119-126."""
+    _refuse_sparse(fx, "posterior (conditioning on further data)")
     L.ensure_init()
     lib = L.load()
     if _has_nan(y):
@@ -1021,6 +1163,8 @@ def posterior(fx: FiniteGP, y):
 def mean_and_var(fx: FiniteGP, add_noise: bool = True):
     """mean_and_var(fx): reference src/oilmm.jl:57-76 (OILMM) and src/independent_mogp.jl:50,55.  For a sharded
     model the outputs are this shard's partial sums (add_noise only on one rank)."""
+    if _sparse_post(fx) is not None:
+        return _sparse_mean_and_var(fx, add_noise, True)
     L.ensure_init()
     lib = L.load()
     f, x, s2 = fx.f, fx.x, fx.sigma2
@@ -1066,6 +1210,7 @@ def mean_and_var_vjp(fx: FiniteGP, dmean=None, dvar=None, add_noise: bool = True
     {"x": d/d fx.x.x (shaped and typed like it), "sigma2": d/d sigma2}.  dvar=None takes no triangular solve (the pullback of mean).
     OILMM and IndependentMOGP priors and posteriors (sequentially conditioned and sharded ones included: a shard's partial sum) and
     the dense-H prior, by lmm_oilmm_mean_and_var_grad_xs.  The dense-H posterior and the coupled latent view raise NotImplementedError."""
+    _refuse_sparse(fx, "mean_and_var_vjp")
     L.ensure_init()
     lib = L.load()
     f, x, s2 = fx.f, fx.x, fx.sigma2
@@ -1105,6 +1250,7 @@ def mean_and_var_vjp(fx: FiniteGP, dmean=None, dvar=None, add_noise: bool = True
 def mean_and_cov(fx: FiniteGP):
     """mean_and_cov(fx): reference src/ilmm.jl:132-139 (ILMM/OILMM) and AbstractGPs' generic form over
     src/independent_mogp.jl:60-63 (IndependentMOGP).  Returns (mean, C) with C (p n) x (p n), by-outputs order."""
+    _refuse_sparse(fx, "mean_and_cov")
     L.ensure_init()
     lib = L.load()
     f, x, s2 = fx.f, fx.x, fx.sigma2
@@ -1144,6 +1290,7 @@ def cov(fx, x=None, y=None):
     cov(f::IndependentMOGP, x, y): the two-input cross-covariance, reference src/independent_mogp.jl:66-71 (both inputs by outputs)
     and :184-215 (either one MOInputIsotopicByFeatures); cov(f::IndependentMOGP, x) = cov(f, x, x) (:60-63, :176-181).  Prior or
     (independent) posterior latents; (m n) x (m n2), one lmm_mogp_cross_cov call."""
+    _refuse_sparse(fx, "cov")
     if isinstance(fx, IndependentMOGP):
         if x is None:
             raise TypeError("cov(f::IndependentMOGP, x[, y]) needs the inputs")
@@ -1154,6 +1301,9 @@ def cov(fx, x=None, y=None):
 
 
 def _mogp_cross_cov(f: IndependentMOGP, x, y) -> np.ndarray:
+    if isinstance(f._post, _SparsePostHandle):      # its pointer is no lmm_post_t*: never hand it to an entry point that takes one
+        raise NotImplementedError("cov is not served on an inducing-point posterior (approx_posterior): it answers mean_and_var, "
+                                  "mean, var and marginals")
     L.ensure_init()
     m = len(f.fs)
     if x.out_dim != m or y.out_dim != m:
@@ -1177,6 +1327,8 @@ def mean(fx: FiniteGP):
     """reference src/ilmm.jl:142 (mean_and_var(fx)[1]).  For an OILMM (prior or posterior, by-outputs inputs) the means alone
     are computed -- mu + K(x*, x) alpha per latent, no triangular solve for variances that would be discarded."""
     f, x = fx.f, fx.x
+    if _sparse_post(fx) is not None:
+        return _sparse_mean_and_var(fx, False, False)[0]
     if isinstance(f, ILMM) and isinstance(x, MOInputIsotopicByOutputs) and (f.is_oilmm or f.f._post is None):
         L.ensure_init()
         unpack(fx)
@@ -1232,6 +1384,7 @@ def rand(rng, fx: FiniteGP, N: Optional[int] = None, jitters=None, add_noise: bo
     """rand(rng, fx[, N]): reference src/oilmm.jl:40-54, src/ilmm.jl:78-92, src/independent_mogp.jl:83-96.
     `rng` is a numpy Generator; standard normals are drawn on the host in the reference's order (m blocks of n
     latent normals, then n*p noise normals) and handed to the device, as the Julia shim does with randn(rng, ...)."""
+    _refuse_sparse(fx, "rand")
     f, x, s2 = fx.f, fx.x, fx.sigma2
     if isinstance(x, MOInputIsotopicByFeatures):          # reference src/independent_mogp.jl:217-220
         s = rand(rng, FiniteGP(f, x.by_outputs(), s2), N, jitters, add_noise)
