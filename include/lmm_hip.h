@@ -595,7 +595,7 @@ int lmm_oilmm_logpdf_grad_missing(const double* x, int d, int n, const double* y
  * (DESIGN.md 4.16); no atomics, so these moments are bitwise reproducible whatever LMM_DETERMINISTIC says (the two M x M
  * factorisations follow the library's rule: split-K atomics only in large trailing updates).  Float64 only: the fp32
  * compute mode is refused (LMM_ERR_UNSUPPORTED).  A failed pivot of K_uu + jitter I or of B is LMM_ERR_NOT_PD with the latent and the
- * pivot in lmm_last_error_detail.  Not built: gradients, NaN in y, dense H.
+ * pivot in lmm_last_error_detail.  Not built: NaN in y, dense H, gradients of dtc.
  *   lmm_oilmm_elbo : elbo(VFE(f(z, jitter)), fx, y) and dtc(VFE(f(z, jitter)), fx, y) of AbstractGPs for fx::FiniteGP{<:OILMM}.
  *                    Arguments as lmm_oilmm_logpdf; *elbo = sum_{l in shard} elbo_l + (with_regulariser ? the regulariser of
  *                    reference src/oilmm.jl:101-113 : 0), *dtc likewise; either output may be NULL.
@@ -610,7 +610,22 @@ int lmm_oilmm_logpdf_grad_missing(const double* x, int d, int n, const double* y
  *   lmm_dev_sparse_moments : building block exported for tests (DEVICE pointers x, z, w, r, Phi, b, scalars; gp on the host): one
  *                    latent's Phi (nz x nz column-major, ld >= nz; only the lower triangle is written), b (nz) and scalars = (s,
  *                    kappa, lambda) for per-point noise w (n) and data r (n).  chunk: points per partial sum (0: the library's
- *                    default); partials are added in chunk order, so equal arguments give bitwise equal results. */
+ *                    default); partials are added in chunk order, so equal arguments give bitwise equal results.
+ *   lmm_oilmm_elbo_grad : value and gradient of the bound of lmm_oilmm_elbo: *out_elbo is bitwise that call's *elbo;
+ *                    grad_y (n x p, the layout of y), grad_sigma2, grad_S (m), grad_U (p x m), grad_gps (m; per-dimension lengthscales,
+ *                    alpha, rho, decay and sum terms through the tag registry) exactly as lmm_oilmm_logpdf_grad returns them, and
+ *                    grad_z (d x nz, the layout of z).  Any output may be NULL; grad_y and grad_z may be host or device pointers.
+ *                    Partial sums over the shard.  A second pass over the n points forms G = PhiBar K_uf on the FP64 MFMA from K_uf
+ *                    tiles generated on the fly and contracts (2 G + beta r') / w with the kernel derivatives; no atomics.  Refusals
+ *                    are those of lmm_oilmm_elbo.  There is no gradient of dtc.
+ *   lmm_dev_sparse_grad : building block exported for tests (DEVICE pointers x, z, w, r, PhiBar, beta and outputs; gp on the host):
+ *                    that second pass for one latent with per-point noise w, a symmetric PhiBar (nz x nz column-major, ld >= nz,
+ *                    both triangles read) and beta (nz).  term_records: LMM_SUM_MAX_TERMS records of 10 + d raw sums over (i, t) of
+ *                    g_it d k_c(z_i, x_t) -- [0] d / d (the term's lengthscale multiplier), [7] sum g k_c, [8] d / d alpha (RQ) or rho
+ *                    (periodic kinds), [9] d / d decay, [10 + k] d / d (the term's k-th per-dimension lengthscale); zeros elsewhere
+ *                    and in the records of terms the latent does not have.  grad_z (d x nz, may be NULL): sum_t g_it d k / d z_i.
+ *                    grad_r (n, may be NULL): (beta' k_u(x_t) - r_t) / w_t.  chunk as in lmm_dev_sparse_moments; equal arguments give
+ *                    bitwise equal results. */
 typedef struct lmm_sparse_post lmm_sparse_post_t;
 int lmm_oilmm_elbo(const double* x, int d, int n, const double* y, int p,
                    const double* U, const double* S, int m, double sigma2,
@@ -625,6 +640,14 @@ int lmm_oilmm_sparse_mean_and_var(const lmm_sparse_post_t* post, const lmm_gp_t*
                                   double sigma2, int add_noise, const double* xs, int d, int ns, double* mean, double* var);
 int lmm_dev_sparse_moments(const double* x, int d, int n, const double* z, int nz, const lmm_gp_t* gp, const double* w,
                            const double* r, int chunk, double* Phi, int ld, double* b, double* scalars);
+int lmm_oilmm_elbo_grad(const double* x, int d, int n, const double* y, int p,
+                        const double* U, const double* S, int m, double sigma2,
+                        const lmm_gp_t* gps, int latent_begin, int latent_end,
+                        const double* z, int nz, double jitter, int with_regulariser, double* out_elbo, double* grad_y,
+                        double* grad_sigma2, double* grad_S, double* grad_U, lmm_gp_grad_t* grad_gps, double* grad_z);
+int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, const lmm_gp_t* gp, const double* w,
+                        const double* r, const double* PhiBar, int ld, const double* beta, int chunk, double* term_records,
+                        double* grad_z, double* grad_r);
 
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard

@@ -32,6 +32,7 @@ SYMBOLS = [
     "lmm_latent_marginals", "lmm_oilmm_mean_and_var", "lmm_oilmm_mean_and_var_grad_xs", "lmm_lmm_mean_and_cov", "lmm_mogp_cross_cov", "lmm_oilmm_post_logpdf", "lmm_lmm_rand", "lmm_lmm_rand_multi", "lmm_normals",
     "lmm_profile_begin", "lmm_profile_end",
     "lmm_oilmm_elbo", "lmm_oilmm_sparse_posterior_create", "lmm_sparse_post_destroy", "lmm_oilmm_sparse_mean_and_var", "lmm_dev_sparse_moments",
+    "lmm_oilmm_elbo_grad", "lmm_dev_sparse_grad",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
 ]
 
@@ -44,6 +45,8 @@ SPARSE_ARGTYPES = {
     "lmm_sparse_post_destroy": [_P],
     "lmm_oilmm_sparse_mean_and_var": [_P, _P, _P, _P, _I, _I, _D, _I, _P, _I, _I, _P, _P],
     "lmm_dev_sparse_moments": [_P, _I, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P],
+    "lmm_oilmm_elbo_grad": [_P, _I, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _P, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P],
+    "lmm_dev_sparse_grad": [_P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P],
 }
 
 

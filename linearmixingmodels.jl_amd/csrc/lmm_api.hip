@@ -245,14 +245,14 @@ void gemm_nt_g(double* C, int ldc, const double* A, int lda, const double* B, in
   launch_gemm_nt(C, ldc, A, lda, B, ldb, M, N, K, lower, set, st);
 }
 void gemm_nt_g(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B, size_t offB, int ldb,
-               int M, int N, int K, int lower, bool set, int nb, hipStream_t st, const char* what) {
+               int M, int N, int K, int lower, bool set, int nb, hipStream_t st, const char* what, bool no_splitk = false) {
   const size_t eb = g_f32 ? 4 : 8;
   for (int j = 0; j < nb; ++j) {
     guard_extent(reinterpret_cast<const char*>(C.p[j]) + offC * eb, M, ldc, N, true, what);
     guard_extent(reinterpret_cast<const char*>(A.p[j]) + offA * eb, M, lda, K, true, what);
     guard_extent(reinterpret_cast<const char*>(B.p[j]) + offB * eb, N, ldb, K, true, what);
   }
-  launch_gemm_nt(C, offC, ldc, A, offA, lda, B, offB, ldb, M, N, K, lower, set, nb, st);
+  launch_gemm_nt(C, offC, ldc, A, offA, lda, B, offB, ldb, M, N, K, lower, set, nb, st, no_splitk);
 }
 void rider_stats_g(const double* R, int ld, int nr, int nk, const double* z, double mu, double base, double* partial,
                    double* mean_out, double* var_out, hipStream_t st) {
@@ -1805,6 +1805,43 @@ struct OilmmGrad {          // host results of oilmm_grad_core (partial sums ove
   std::vector<double> trec;   // m x LMM_SUM_MAX_TERMS records per latent and term (grad_finish), zeros elsewhere
 };
 
+// The regulariser of reference src/oilmm.jl:101-113, once per noise block: its value (added to `total`), its share of d/dS, d/dU and
+// d/dsigma2 (added to G) and PtP = P'P for its d/dY.  M2all: Y Y' (p x p) per noise block.
+void oilmm_regulariser_grad(const double* U, const double* S, int p, int m, const NoiseBlocks& NB, const std::vector<double>& M2all,
+                            double& total, OilmmGrad& G, std::vector<double>& PtP) {
+  const int nblk = NB.nblk;
+  const size_t pp = (size_t)p * p;
+  std::vector<double> Pm((size_t)p * p, 0.0);
+  for (int a1 = 0; a1 < p; ++a1)
+    for (int b1 = 0; b1 < p; ++b1) {
+      double s = (a1 == b1) ? 1.0 : 0.0;
+      for (int l = 0; l < m; ++l) s -= U[a1 + (size_t)l * p] * U[b1 + (size_t)l * p];
+      Pm[a1 + (size_t)b1 * p] = s;
+    }
+  auto matmul = [&](const std::vector<double>& A1, int r, int c, const std::vector<double>& B1, int c2) {
+    std::vector<double> Cc((size_t)r * c2, 0.0);
+    for (int j = 0; j < c2; ++j) for (int kk = 0; kk < c; ++kk) { const double b = B1[kk + (size_t)j * c]; for (int i = 0; i < r; ++i) Cc[i + (size_t)j * r] += A1[i + (size_t)kk * r] * b; }
+    return Cc;
+  };
+  PtP = matmul(Pm, p, p, Pm, p);                               // P symmetric: P'P = P P
+  double logdetS = 0.0;
+  for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
+  std::vector<double> Uv(U, U + (size_t)p * m);
+  std::vector<double> PU = matmul(Pm, p, p, Uv, m);
+  for (int blk = 0; blk < nblk; ++blk) {                        // reference src/oilmm.jl:101-113, once per noise block
+    const std::vector<double> M2(M2all.begin() + pp * blk, M2all.begin() + pp * (blk + 1));
+    const double s2 = NB.s2[blk], cnt = NB.count(blk);
+    double Rn = 0.0;                                           // |P Y|_F^2 = tr(P'P Y Y')
+    for (int a1 = 0; a1 < p; ++a1) for (int b1 = 0; b1 < p; ++b1) Rn += PtP[a1 + (size_t)b1 * p] * M2[b1 + (size_t)a1 * p];
+    total += -(cnt * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * s2)) + Rn / s2) / 2.0;
+    for (int l = 0; l < m; ++l) G.gS[l] += -cnt / (2.0 * S[l]);
+    G.gs2[blk] += -0.5 * (cnt * (double)(p - m) / s2 - Rn / (s2 * s2));
+    std::vector<double> M2U = matmul(M2, p, p, Uv, m);
+    std::vector<double> t1 = matmul(Pm, p, p, M2U, m), t2 = matmul(M2, p, p, PU, m);
+    for (size_t q = 0; q < G.gU.size(); ++q) G.gU[q] += (t1[q] + t2[q]) / s2;
+  }
+}
+
 // Value and gradient of the OILMM logpdf (reference src/oilmm.jl:79-113 differentiated) over N points in NB.nblk consecutive
 // blocks, block b carrying observation noise NB.s2[b] (one block: the plain logpdf; several: the joint density of the
 // conditioning batches and the test points that the predictive logpdf is the difference of).  Per latent: factor, alpha = Kt^-1 delta, Kt^-1 = L^-T L^-1
@@ -1987,37 +2024,7 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
     for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] += -YA[o + (size_t)k * p] / std::sqrt(S[l]);
   }
   std::vector<double> PtP;       // P'P for the regulariser's dY
-  if (with_regulariser) {
-    std::vector<double> Pm((size_t)p * p, 0.0);
-    for (int a1 = 0; a1 < p; ++a1)
-      for (int b1 = 0; b1 < p; ++b1) {
-        double s = (a1 == b1) ? 1.0 : 0.0;
-        for (int l = 0; l < m; ++l) s -= U[a1 + (size_t)l * p] * U[b1 + (size_t)l * p];
-        Pm[a1 + (size_t)b1 * p] = s;
-      }
-    auto matmul = [&](const std::vector<double>& A1, int r, int c, const std::vector<double>& B1, int c2) {
-      std::vector<double> Cc((size_t)r * c2, 0.0);
-      for (int j = 0; j < c2; ++j) for (int kk = 0; kk < c; ++kk) { const double b = B1[kk + (size_t)j * c]; for (int i = 0; i < r; ++i) Cc[i + (size_t)j * r] += A1[i + (size_t)kk * r] * b; }
-      return Cc;
-    };
-    PtP = matmul(Pm, p, p, Pm, p);                               // P symmetric: P'P = P P
-    double logdetS = 0.0;
-    for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
-    std::vector<double> Uv(U, U + (size_t)p * m);
-    std::vector<double> PU = matmul(Pm, p, p, Uv, m);
-    for (int blk = 0; blk < nblk; ++blk) {                        // reference src/oilmm.jl:101-113, once per noise block
-      const std::vector<double> M2(M2all.begin() + pp * blk, M2all.begin() + pp * (blk + 1));
-      const double s2 = NB.s2[blk], cnt = NB.count(blk);
-      double Rn = 0.0;                                           // |P Y|_F^2 = tr(P'P Y Y')
-      for (int a1 = 0; a1 < p; ++a1) for (int b1 = 0; b1 < p; ++b1) Rn += PtP[a1 + (size_t)b1 * p] * M2[b1 + (size_t)a1 * p];
-      total += -(cnt * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * s2)) + Rn / s2) / 2.0;
-      for (int l = 0; l < m; ++l) G.gS[l] += -cnt / (2.0 * S[l]);
-      G.gs2[blk] += -0.5 * (cnt * (double)(p - m) / s2 - Rn / (s2 * s2));
-      std::vector<double> M2U = matmul(M2, p, p, Uv, m);
-      std::vector<double> t1 = matmul(Pm, p, p, M2U, m), t2 = matmul(M2, p, p, PU, m);
-      for (size_t q = 0; q < G.gU.size(); ++q) G.gU[q] += (t1[q] + t2[q]) / s2;
-    }
-  }
+  if (with_regulariser) oilmm_regulariser_grad(U, S, p, m, NB, M2all, total, G, PtP);
   G.value = total;
   if (gy_dev) {
     // dL/dY[o, i] = - sum_l T[l, o] alpha_l[i]  - (P'P Y)[o, i] / sigma2(i)
@@ -4402,6 +4409,9 @@ struct lmm_sparse_post {
 struct SparseState {
   std::vector<Buf<double>> Lu, Wu, LB, WB, c;
   std::vector<double> dtc, elbo;            // per latent of the shard
+  bool keep_grad = false;                   // the gradient's inputs: Q = L_u^-1 Phi L_u^-T per latent and the scalars s, kappa, c'c
+  std::vector<Buf<double>> Q;
+  std::vector<double> s, kappa, ctc;
 };
 
 static int sparse_shape_check(int d, int nz, double jitter) {
@@ -4443,8 +4453,8 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
     out.LB.emplace_back(D.elems()); out.WB.emplace_back((size_t)(D.NC / 64) * 4096);
     out.c.emplace_back((size_t)D.NC);
   }
-  std::vector<Buf<double>> Q;
-  for (int j = 0; j < nb_per; ++j) Q.emplace_back(D.elems());
+  std::vector<Buf<double>> Q;                // one per batch slot, or (keep_grad) one per latent
+  for (int j = 0; j < (out.keep_grad ? ms : nb_per); ++j) Q.emplace_back(D.elems());
   // b (NC per latent); res = [3 ms: s, kappa, lambda | ms: tr Q | 2 ms: -(M log 2pi + log det B + q) / 2 with q = c'c, then q = 0 (the zero row under the rider)]; two pivot-info words per latent
   Buf<double> bvec((size_t)D.NC * ms), res((size_t)6 * ms);
   Buf<int> info((size_t)2 * ms);
@@ -4464,7 +4474,7 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
       const int k = k0 + j;
       const Latent& gp = lts[l0 + k];
       sparse_fill_lat(a.lat[j], gp, nullptr, wconst[l0 + k], rv + (size_t)k * n, rsub[l0 + k]);
-      Pb.p[j] = out.LB[k].p; Qb.p[j] = Q[j].p; bb.p[j] = bvec.p + (size_t)k * D.NC; sb.p[j] = res.p + (size_t)3 * k;
+      Pb.p[j] = out.LB[k].p; Qb.p[j] = Q[out.keep_grad ? k : j].p; bb.p[j] = bvec.p + (size_t)k * D.NC; sb.p[j] = res.p + (size_t)3 * k;
       HIPCHK(hipMemsetAsync(out.LB[k].p, 0, D.elems() * sizeof(double), st));      // Phi's pad rows and columns
       GramArgs r{};
       r.A = out.Lu[k].p; r.ld = D.ld; r.nrows = D.NR; r.ncols = D.NC; r.x = zd; r.d = d; r.n = M;
@@ -4506,20 +4516,161 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
     const double gc = hres[(size_t)4 * ms + 2 * k], g0 = hres[(size_t)4 * ms + 2 * k + 1];
     out.dtc[k] = 2.0 * g0 - gc + 0.5 * M * kLog2Pi - 0.5 * ((double)n * kLog2Pi + r[2] + r[0]);
     out.elbo[k] = out.dtc[k] - 0.5 * (r[1] - hres[(size_t)3 * ms + k]);
+    if (out.keep_grad) { out.s.push_back(r[0]); out.kappa.push_back(r[1]); out.ctc.push_back(2.0 * (g0 - gc)); }
   }
+  if (out.keep_grad) out.Q = std::move(Q);
+  return LMM_OK;
+}
+
+
+// ---- gradient of the bound ----------------------------------------------------------------------------------------
+// Per latent l, un-whitened: K = K_uu + jitter I, Sigma = K + Phi, beta = Sigma^-1 b,
+//     PhiBar = d elbo_l / d Phi = (K^-1 - Sigma^-1 - beta beta') / 2,   KuuBar = d elbo_l / d K_uu = PhiBar - K^-1 Phi K^-1 / 2,
+// from the forward pass's factors: X' = L_u^-T (identity riders through trsm_rec), Y' = X' L_B^-T, K^-1 = X'X, Sigma^-1 = Y'Y,
+// beta = Y' c, K^-1 Phi K^-1 = X' Q X.  The second pass over the points (sparse_grad_kernel) contracts g = (2 PhiBar K_uf + beta r') / w with
+// d k; the K_uu terms are the gradient reductions of the exact path over x = z with alpha = 0 and -2 KuuBar as the inverse.
+struct SparseGradOut {
+  OilmmGrad G;
+  double* gy_dev = nullptr;                 // n x p (device) or nullptr
+  double* gz_dev = nullptr;                 // d x nz (device) or nullptr
+};
+
+static int sparse_grad_mode(const Latent* lts, int l0, int l1) {
+  int mode = 0;
+  for (int l = l0; l < l1; ++l) {
+    if (lts[l].has_periodic()) return 2;
+    if (lts[l].is_sum()) mode = 1;
+  }
+  return mode;
+}
+
+static void sparse_grad_fill_lat(SparseGradLat& s, const Latent& gp, const LatentDev* gd, const double* w, double wconst, const double* r,
+                                 double rsub, const double* PhiBar, const double* beta, double* grad_r) {
+  s.g = gp.dev(); s.gd = gd; s.nterms = gp.nt();
+  s.w = w; s.wconst = wconst; s.r = r; s.rsub = rsub; s.PhiBar = PhiBar; s.beta = beta; s.grad_r = grad_r;
+}
+
+// hred: LMM_NGRAD sums per term of the latents [l0, l1) (K_uf and K_uu contributions added; [1] of a latent's first term: tr(-2 KuuBar)),
+// hard: d per-dimension sums per term; gksum: sum_{i,t} g_it k(z_i, x_t) per latent (the K_uf share of [7] over its terms); gr_dev: d elbo / d r, n per latent; gz_dev: d x nz summed over the latents, or nullptr.
+static int sparse_grad_core(const double* xd, int d, int n, const double* zd, int nz, const LatentSet* ls, int l0, int l1, const double* rv,
+                            const double* rsub, const double* wconst, const SparseState& S, std::vector<double>& hred,
+                            std::vector<double>& hard, std::vector<double>& gksum, double* gr_dev, double* gz_dev) {
+  const Latent* lts = ls->lat.data();
+  const int ms = l1 - l0, M = nz, NGR = LMM_NGRAD, no = LMM_NGRAD + d;
+  hipStream_t st = g.streams[0];
+  const std::vector<int> toff = ls->term_offsets(l0, l1);
+  const int nterm = toff[ms];
+  hred.assign((size_t)NGR * std::max(nterm, 1), 0.0); hard.assign((size_t)d * std::max(nterm, 1), 0.0);
+  gksum.assign(std::max(ms, 1), 0.0);
+  if (gz_dev) HIPCHK(hipMemsetAsync(gz_dev, 0, (size_t)d * nz * sizeof(double), st));
+  if (ms == 0) return LMM_OK;
+  Dims D(M, 1);
+  const int nb_per = std::min(ms, LMM_MAX_BATCH);
+  std::vector<LatentDev> hgd;
+  for (int k = 0; k < ms; ++k) for (const KernelTerm& T : lts[l0 + k].terms) hgd.push_back(T.gd);
+  Buf<LatentDev> gdd(nterm);
+  HIPCHK(hipMemcpyAsync(gdd.p, hgd.data(), hgd.size() * sizeof(LatentDev), hipMemcpyHostToDevice, st));
+  std::vector<SparseGradLat> hlat(nb_per);
+  Buf<SparseGradLat> dlat(nb_per);
+  std::vector<Buf<double>> Ru, Ki, Si, T1, T2, gzl;      // five M x M buffers per batch slot (Y' is built in place of X')
+  for (int j = 0; j < nb_per; ++j) {
+    Ru.emplace_back(D.elems()); Ki.emplace_back(D.elems()); Si.emplace_back(D.elems());
+    T1.emplace_back(D.elems()); T2.emplace_back(D.elems());
+    if (gz_dev) gzl.emplace_back((size_t)d * nz);
+  }
+  const size_t nrec = (size_t)LMM_SUM_MAX_TERMS * no;
+  Buf<double> beta((size_t)D.NC * ms), recF(nrec * ms), recK((size_t)NGR * nterm), ardK((size_t)d * nterm), zeros((size_t)D.NC);
+  Buf<double> gpart((size_t)grad_partials(M, d)), gxpart(gz_dev ? grad_x_partial_elems(M, d) : 1);
+  HIPCHK(hipMemsetAsync(recK.p, 0, (size_t)NGR * nterm * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(ardK.p, 0, (size_t)d * nterm * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(zeros.p, 0, (size_t)D.NC * sizeof(double), st));
+  int chunk = 0, nch = 0;
+  if (int rc = sparse_plan(n, nz, nb_per, 0, &chunk, &nch)) return rc;
+  const int tm = (nz + 63) / 64;
+  Buf<double> scratch((size_t)nb_per * nch * tm * sparse_grad_partial_stride(d));
+  const int mode = sparse_grad_mode(lts, l0, l1);
+  bool gz_first = true;
+  fork_slots(1);
+  for (int k0 = 0; k0 < ms; k0 += nb_per) {
+    const int nb = std::min(nb_per, ms - k0);
+    BatchPtr Rub{}, Kib{}, Sib{}, T1b{}, T2b{}, Lub{}, Wub{}, LBb{}, WBb{}, Qb{}, cb{}, betab{}, recb{}, gzb{};
+    for (int j = 0; j < nb; ++j) {
+      const int k = k0 + j;
+      Rub.p[j] = Ru[j].p; Kib.p[j] = Ki[j].p; Sib.p[j] = Si[j].p; T1b.p[j] = T1[j].p; T2b.p[j] = T2[j].p;
+      Lub.p[j] = S.Lu[k].p; Wub.p[j] = S.Wu[k].p; LBb.p[j] = S.LB[k].p; WBb.p[j] = S.WB[k].p; Qb.p[j] = S.Q[k].p; cb.p[j] = S.c[k].p;
+      betab.p[j] = beta.p + (size_t)k * D.NC; recb.p[j] = recF.p + nrec * k; gzb.p[j] = gz_dev ? gzl[j].p : nullptr;
+      launch_set_identity(Ru[j].p, D.ld, D.NC, st);
+      HIPCHK(hipMemsetAsync(T1[j].p, 0, D.elems() * sizeof(double), st));
+      HIPCHK(hipMemsetAsync(T2[j].p, 0, D.elems() * sizeof(double), st));
+    }
+    trsm_rec(Rub, D.ld, D.NC, Lub, D.ld, Wub, nb, 0, D.NC, st, true, true, true);          // X' = L_u^-T (upper triangular)
+    launch_syrk_upper_set(Kib, D.ld, Rub, D.ld, D.NC, nb, st);                             // lower(Ki) = X'X = K^-1
+    // T2 = X' Q' X = K^-1 Phi K^-1 through two C -= A B' products (no split-K atomics: M x M work)
+    gemm_nt_g(T1b, 0, D.ld, Rub, 0, D.ld, Qb, 0, D.ld, D.NC, D.NC, D.NC, 0, false, nb, st, "K^-1 Phi K^-1 (first product)", true);
+    gemm_nt_g(T2b, 0, D.ld, T1b, 0, D.ld, Rub, 0, D.ld, D.NC, D.NC, D.NC, 0, false, nb, st, "K^-1 Phi K^-1 (second product)", true);
+    trsm_rec(Rub, D.ld, D.NC, LBb, D.ld, WBb, nb, 0, D.NC, st, false, true, true);         // in place: Y' = X' L_B^-T (upper triangular)
+    launch_syrk_upper_set(Sib, D.ld, Rub, D.ld, D.NC, nb, st);                             // lower(Si) = Y'Y = Sigma^-1
+    launch_sparse_beta(Rub, D.ld, M, cb, betab, nb, st);
+    launch_sparse_phibar(Kib, Sib, T2b, betab, T1b, D.ld, M, nb, st);                      // T1 <- PhiBar, lower(Si) <- -2 KuuBar
+    SparseGradArgs a{};
+    a.x = xd; a.z = zd; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.ld = D.ld; a.scratch = scratch.p; a.lat = dlat.p;
+    for (int j = 0; j < nb; ++j) {
+      const int k = k0 + j;
+      sparse_grad_fill_lat(hlat[j], lts[l0 + k], gdd.p + toff[k], nullptr, wconst[l0 + k], rv + (size_t)k * n, rsub[l0 + k], T1[j].p,
+                           betab.p[j], gr_dev + (size_t)k * n);
+    }
+    HIPCHK(hipMemcpyAsync(dlat.p, hlat.data(), (size_t)nb * sizeof(SparseGradLat), hipMemcpyHostToDevice, st));
+    launch_sparse_grad(a, nb, mode, st);
+    launch_sparse_grad_finish(scratch.p, nch, nz, d, recb, gzb, nb, st);
+    for (int j = 0; j < nb; ++j) {
+      const int k = k0 + j;
+      for (int c = 0; c < lts[l0 + k].nt(); ++c) {
+        const LatentDev& gd = lts[l0 + k].terms[c].gd;
+        const size_t t = (size_t)toff[k] + c;
+        launch_grad_reduce(Si[j].p, D.ld, M, M, zeros.p, zeros.p, zd, d, gd, gpart.p, recK.p + NGR * t, st, ardK.p + d * t);
+        if (gz_dev) launch_grad_x(Si[j].p, D.ld, M, zeros.p, zd, d, gd, gxpart.p, gzl[j].p, true, st);
+      }
+      if (gz_dev) {                              // the latents in order
+        if (gz_first) HIPCHK(hipMemcpyAsync(gz_dev, gzl[j].p, (size_t)d * nz * sizeof(double), hipMemcpyDeviceToDevice, st));
+        else launch_vec_lin(gz_dev, gzl[j].p, 1.0, d * nz, gz_dev, st);
+        gz_first = false;
+      }
+    }
+    HIPCHK(hipStreamSynchronize(st));            // hlat is rewritten by the next batch
+  }
+  join_slots(1);
+  std::vector<double> hF(nrec * ms), hK((size_t)NGR * nterm), hA((size_t)d * nterm);
+  HIPCHK(hipMemcpyAsync(hF.data(), recF.p, hF.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hK.data(), recK.p, hK.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hA.data(), ardK.p, hA.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  static const int slots[4] = {0, 7, 8, 9};
+  for (int k = 0; k < ms; ++k)
+    for (int c = 0; c < lts[l0 + k].nt(); ++c) {
+      const size_t t = (size_t)toff[k] + c;
+      const double* F = &hF[nrec * k + (size_t)no * c];
+      for (int e : slots) hred[NGR * t + e] = F[e] + hK[NGR * t + e];
+      hred[NGR * t + 1] = hK[NGR * t + 1];
+      gksum[k] += F[7];
+      const bool ard = lts[l0 + k].terms[c].gd.ils != nullptr;
+      for (int kk = 0; kk < d; ++kk) hard[(size_t)d * t + kk] = F[NGR + kk] + (ard ? hA[(size_t)d * t + kk] : 0.0);
+    }
   return LMM_OK;
 }
 
 // The per-latent residual rows (T y)_l, the projected noise and (with_regulariser) the regulariser of lmm_oilmm_logpdf, then sparse_core.
 static int sparse_oilmm(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
                         const lmm_gp_t* gps, int l0, int l1, const double* z, int nz, double jitter, int with_regulariser,
-                        SparseState& out, double* reg, std::shared_ptr<LatentSet>* ls_out, Buf<double>* z_keep) {
+                        SparseState& out, double* reg, std::shared_ptr<LatentSet>* ls_out, Buf<double>* z_keep,
+                        SparseGradOut* grad = nullptr) {
   if (!x || !y || !U || !S || !z || d <= 0 || n <= 0 || p <= 0 || m <= 0 || nz <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
   if (int rc = sparse_shape_check(d, nz, jitter)) return rc;
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   RESOLVE(gps, m, d);
+  if (grad) { if (int rc = ls->ard_grad_check()) return rc; }
+  out.keep_grad = grad != nullptr;
   hipStream_t st0 = g.streams[0];
   std::vector<double> T, ST, H;
   project_orthogonal(U, S, p, m, sigma2, T, ST, H);
@@ -4549,6 +4700,77 @@ static int sparse_oilmm(const double* x, int d, int n, const double* y, int p, c
     for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
     *reg = -((double)n * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * sigma2)) + resid / sigma2) / 2.0;
   }
+  if (grad) {
+    // host chain rule, as oilmm_grad_core's: a_l = -d elbo_l / d r in the place of alpha, d elbo_l / d w in the place of d lml / d noise
+    const int ms = l1 - l0, NGR = LMM_NGRAD;
+    OilmmGrad& G = grad->G;
+    std::vector<double> hred, hard, gksum;
+    Buf<double> gr((size_t)n * std::max(ms, 1)), ones(n);
+    const double* rvs = Ty.p + (size_t)(l0 - c0) * n;
+    if (int rc = sparse_grad_core(xd.p, d, n, zown.p, nz, ls.get(), l0, l1, rvs, means.data(), ST.data(), out, hred, hard, gksum, gr.p,
+                                  grad->gz_dev)) return rc;
+    const size_t pp = (size_t)p * p;
+    Buf<double> YAd((size_t)p * std::max(ms, 1)), aTyd(std::max(ms, 1)), sad(std::max(ms, 1)), M2d(pp);
+    std::vector<double> YA((size_t)p * std::max(ms, 1), 0.0), aTy(std::max(ms, 1), 0.0), sa(std::max(ms, 1), 0.0), M2all(pp, 0.0);
+    if (ms > 0) {
+      launch_fill(ones.p, n, 1.0, st0);
+      launch_atb(yd.p, n, gr.p, n, n, p, ms, YAd.p, st0);                   // Y' (d elbo / d r_l), p x ms
+      launch_atb(gr.p, n, ones.p, n, n, ms, 1, sad.p, st0);
+      for (int k = 0; k < ms; ++k) launch_atb(gr.p + (size_t)k * n, n, rvs + (size_t)k * n, n, n, 1, 1, aTyd.p + k, st0);
+      HIPCHK(hipMemcpyAsync(YA.data(), YAd.p, YA.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+      HIPCHK(hipMemcpyAsync(aTy.data(), aTyd.p, (size_t)ms * sizeof(double), hipMemcpyDeviceToHost, st0));
+      HIPCHK(hipMemcpyAsync(sa.data(), sad.p, (size_t)ms * sizeof(double), hipMemcpyDeviceToHost, st0));
+    }
+    if (with_regulariser) {
+      launch_atb(yd.p, n, yd.p, n, n, p, p, M2d.p, st0);
+      HIPCHK(hipMemcpyAsync(M2all.data(), M2d.p, pp * sizeof(double), hipMemcpyDeviceToHost, st0));
+    }
+    HIPCHK(hipStreamSynchronize(st0));
+    const std::vector<int> toff = ls->term_offsets(l0, l1);
+    G.gs2.assign(1, 0.0);
+    G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
+    G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
+    G.trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
+    for (int k = 0; k < ms; ++k) {
+      const int l = l0 + k;
+      const double w = ST[l];
+      double* r = &hred[(size_t)NGR * toff[k]];
+      const double gk = gksum[k];                          // sum_{i,t} g_it k_it = 2 tr(PhiBar Phi) + beta'b
+      const double trK = -0.5 * r[1];                      // tr KuuBar
+      const double dw = -(0.5 * gk + 0.5 * out.ctc[k] - 0.5 * out.s[k] - 0.5 * out.kappa[k]) / w - (double)n / (2.0 * w);
+      // [7] of a term: + the diagonal of K_uu and the kappa term, both linear in V_c
+      for (int c = 0; c < lts[l].nt(); ++c) r[NGR * c + 7] += lts[l].terms[c].ev.var * (trK - 0.5 * (double)n / w);
+      double dv0 = 0.0;
+      G.ggps[l].lengthscale = grad_finish(lts[l], d, r, &hard[(size_t)d * toff[k]], 0.0, 0.0,
+                                          &G.trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)], &dv0);
+      G.ggps[l].variance = dv0;
+      G.ggps[l].mean = -sa[k];
+      G.gs2[0] += dw / S[l];
+      G.gS[l] += -dw * sigma2 / (S[l] * S[l]) - 0.5 * aTy[k] / S[l];
+      for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] += YA[o + (size_t)k * p] / std::sqrt(S[l]);
+    }
+    double total = 0.0;
+    std::vector<double> PtP;
+    const NoiseBlocks NB1 = one_noise_block(n, sigma2);
+    if (with_regulariser) oilmm_regulariser_grad(U, S, p, m, NB1, M2all, total, G, PtP);
+    G.value = *reg;                                        // the sum of lmm_oilmm_elbo, in its order
+    for (int k = 0; k < ms; ++k) G.value += out.elbo[k];
+    if (grad->gy_dev) {
+      // d/dY[o, i] = sum_l T[l, o] (d elbo_l / d r)[i] - (P'P Y)[o, i] / sigma2
+      std::vector<double> Tt((size_t)p * std::max(ms, 1), 0.0);
+      for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) Tt[o + (size_t)k * p] = T[(l0 + k) + (size_t)o * m];
+      Uploaded Ttd(Tt, st0);
+      Buf<double> ga((size_t)n * p);
+      launch_mix(gr.p, n, ms, Ttd.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, with_regulariser ? ga.p : grad->gy_dev, st0);
+      if (with_regulariser) {
+        Uploaded Qd(PtP, st0);
+        Buf<double> gq((size_t)n * p);
+        launch_tall_skinny(yd.p, n, n, p, Qd.buf.p, p, p, gq.p, n, nullptr, nullptr, 0, nullptr, 0, st0);
+        launch_vec_lin_blocks(ga.p, gq.p, NB1, -1.0, n, (size_t)n * p, grad->gy_dev, st0);
+      }
+      HIPCHK(hipStreamSynchronize(st0));
+    }
+  }
   if (ls_out) *ls_out = ls;
   if (z_keep) *z_keep = std::move(zown);
   return LMM_OK;
@@ -4571,6 +4793,38 @@ int lmm_oilmm_elbo(const double* x, int d, int n, const double* y, int p, const 
   for (size_t k = 0; k < st.elbo.size(); ++k) { e += st.elbo[k]; t += st.dtc[k]; }
   if (elbo) *elbo = e;
   if (dtc) *dtc = t;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Value and gradient of elbo(VFE(f(z, jitter)), fx, y) with respect to y, sigma2, S, U, every latent's kernel parameters and mean (as
+// lmm_oilmm_logpdf_grad returns them: grad_gps and the tag registry) and the inducing inputs z.  *out_elbo is bitwise the value of
+// lmm_oilmm_elbo.  Any output may be NULL.
+int lmm_oilmm_elbo_grad(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                        const lmm_gp_t* gps, int latent_begin, int latent_end, const double* z, int nz, double jitter,
+                        int with_regulariser, double* out_elbo, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                        lmm_gp_grad_t* grad_gps, double* grad_z) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !y || !U || !S || !z || d <= 0 || n <= 0 || p <= 0 || m <= 0 || nz <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (int rc = sparse_shape_check(d, nz, jitter)) return rc;
+  hipStream_t st0 = g.streams[0];
+  DevOut gy(grad_y, (size_t)n * p), gz(grad_z, (size_t)d * nz);
+  SparseState st;
+  SparseGradOut GO;
+  GO.gy_dev = gy.p; GO.gz_dev = gz.p;
+  double reg = 0.0;
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = sparse_oilmm(x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, with_regulariser, st, &reg,
+                            &ls, nullptr, &GO)) return rc;
+  double value = 0.0;
+  write_oilmm_grad(GO.G, m, p, &value, grad_sigma2, grad_S, grad_U, grad_gps);
+  if (out_elbo) *out_elbo = value;
+  publish_grads(*ls, grad_gps ? &GO.G.trec : nullptr, latent_begin, latent_end);
+  if (grad_y) gy.finish(st0);
+  if (grad_z) gz.finish(st0);
+  if (grad_y || grad_z) HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
   LMM_CATCH
 }
@@ -4681,6 +4935,46 @@ int lmm_dev_sparse_moments(const double* x, int d, int n, const double* z, int n
   Pb.p[0] = Phi; bb.p[0] = b; sb.p[0] = scalars;
   launch_sparse_moments(a, 1, st0);
   launch_sparse_finish(scratch.p, nch, nz, Pb, ld, false, bb, sb, 1, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Building block for tests: the second pass over the points for ONE latent from device pointers (sparse_grad_kernel and its finish).
+// PhiBar: nz x nz column-major (ld), symmetric, both triangles; beta: nz.  term_records: LMM_SUM_MAX_TERMS records of LMM_NGRAD + d raw
+// sums of the K_uf pass ([0] d/d multiplier, [7] sum g k_c, [8] alpha or rho, [9] decay, then the d per-dimension sums; zeros elsewhere and
+// for the terms the latent does not have); grad_z: sum_t g_it d k / d z_i (d x nz); grad_r: (beta' k_t - r_t) / w_t (n).
+int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, const lmm_gp_t* gp, const double* w, const double* r,
+                        const double* PhiBar, int ld, const double* beta, int chunk, double* term_records, double* grad_z,
+                        double* grad_r) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !z || !gp || !w || !r || !PhiBar || !beta || !term_records || d <= 0 || n <= 0 || nz <= 0 || ld < nz)
+    return fail(LMM_ERR_ARG, "bad arguments");
+  if (nz > LMM_SPARSE_MMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for at most %d inducing points (nz = %d)", LMM_SPARSE_MMAX, nz);
+  if (d > LMM_SPARSE_DMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for d <= %d (d = %d)", LMM_SPARSE_DMAX, d);
+  RESOLVE(gp, 1, d);
+  int nch = 0;
+  if (int rc = sparse_plan(n, nz, 1, chunk, &chunk, &nch)) return rc;
+  hipStream_t st0 = g.streams[0];
+  const int tm = (nz + 63) / 64;
+  Buf<double> scratch((size_t)nch * tm * sparse_grad_partial_stride(d));
+  std::vector<LatentDev> hgd;
+  for (const KernelTerm& T : lts[0].terms) hgd.push_back(T.gd);
+  Buf<LatentDev> gdd(hgd.size());
+  HIPCHK(hipMemcpyAsync(gdd.p, hgd.data(), hgd.size() * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  SparseGradLat hl{};
+  sparse_grad_fill_lat(hl, lts[0], gdd.p, w, 0.0, r, 0.0, PhiBar, beta, grad_r);
+  Buf<SparseGradLat> dl(1);
+  HIPCHK(hipMemcpyAsync(dl.p, &hl, sizeof(SparseGradLat), hipMemcpyHostToDevice, st0));
+  SparseGradArgs a{};
+  a.x = x; a.z = z; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.ld = ld; a.scratch = scratch.p; a.lat = dl.p;
+  BatchPtr rb{}, zb{};
+  rb.p[0] = term_records; zb.p[0] = grad_z;
+  launch_sparse_grad(a, 1, sparse_grad_mode(lts, 0, 1), st0);
+  launch_sparse_grad_finish(scratch.p, nch, nz, d, rb, zb, 1, st0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;

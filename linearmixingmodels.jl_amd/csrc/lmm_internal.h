@@ -279,6 +279,31 @@ void launch_sparse_transpose(const BatchPtr& In, const BatchPtr& Out, int ld, in
 // Bm.p[l] (NR x NC, ld) = [I + sym(Q.p[l]) on the leading M x M, identity pad; rider row NC = row NC of Au.p[l]]; trace[l] = tr Q.p[l]
 void launch_sparse_bmat(const BatchPtr& Q, const BatchPtr& Au, const BatchPtr& Bm, int ld, int NC, int NR, int M, double* trace,
                         int nb, hipStream_t st);
+// Gradient of the bound: the second pass over the points (sparse_grad_kernel).  One latent of a launch: its kernel as
+// the forward pass evaluates it (g), its nterms gradient descriptors (gd, device: a plain latent has one), w / r as SparseLat, PhiBar
+// (nz x nz, both triangles, leading dimension SparseGradArgs.ld), beta (nz) and the output d elbo / d r (n values, or nullptr).
+struct SparseGradLat {
+  LatentDev g; const LatentDev* gd; int nterms;
+  const double* w; const double* r; double wconst, rsub;
+  const double* PhiBar; const double* beta; double* grad_r;
+};
+struct SparseGradArgs {
+  const double* x; const double* z;           // d x n inputs, d x nz inducing inputs (device)
+  int d, n, nz, chunk, nch, ld;
+  double* scratch;                            // nb * nch * ceil(nz / 64) * sparse_grad_partial_stride(d) doubles
+  const SparseGradLat* lat;                   // device, one per latent of the launch (blockIdx.z)
+};
+size_t sparse_grad_partial_stride(int d);     // doubles of one (latent, chunk, tile row) partial: LMM_SUM_MAX_TERMS (4 + d) sums and 64 x d input sums
+void launch_sparse_grad(const SparseGradArgs& a, int nb, int mode, hipStream_t st);
+// recs.p[l]: LMM_SUM_MAX_TERMS records of LMM_NGRAD + d sums ([0], [7], [8], [9] and the d per-dimension ones; zeros elsewhere);
+// gz.p[l]: d x nz input sums (or nullptr).  Partials added in chunk order, then in tile-row order.
+void launch_sparse_grad_finish(const double* scratch, int nch, int nz, int d, const BatchPtr& recs, const BatchPtr& gz, int nb,
+                               hipStream_t st);
+// beta.p[l] (M) = R.p[l] c.p[l] for the upper triangular R (M x M, ld)
+void launch_sparse_beta(const BatchPtr& R, int ld, int M, const BatchPtr& c, const BatchPtr& beta, int nb, hipStream_t st);
+// PB.p[l] = (Ki - Si - beta beta') / 2 (both triangles); lower(Si.p[l]) <- -2 PB + sym(T2)
+void launch_sparse_phibar(const BatchPtr& Ki, const BatchPtr& Si, const BatchPtr& T2, const BatchPtr& beta, const BatchPtr& PB, int ld,
+                          int M, int nb, hipStream_t st);
 void launch_atb(const double* X, int ldx, const double* Z, int ldz, int n, int na, int nb, double* out, hipStream_t st);
 void launch_fill(double* p, int n, double v, hipStream_t st);
 void launch_reorder(const double* in, int n, int p, int to_outputs, double* out, hipStream_t st);

@@ -4261,6 +4261,296 @@ __global__ __launch_bounds__(256) void sparse_trace_kernel(BatchPtr Q, int ld, i
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Gradient of the inducing-point bound: the second pass over the n points.  For one latent, with PhiBar = d elbo / d Phi
+// (M x M, symmetric, both triangles stored), beta = Sigma^-1 b and the weights
+//     g_it = (2 (PhiBar k_u(x_t))_i + beta_i r_t) / w_t                                             (M x n, never stored),
+// it forms per term c of the latent  sum_{i,t} g_it d k_c(z_i, x_t) / d theta_c  (the sums of grad_reduce_kernel / grad_reduce_ard_kernel),
+// per inducing point  sum_t g_it d k(z_i, x_t) / d z_i  (the convention of grad_x_kernel: difference first) and per point
+// d elbo / d r_t = (beta' k_u(x_t) - r_t) / w_t.
+// Workgroup (ti, c, l): the 64 rows of tile row ti of G = PhiBar K_uf of latent l over the points of chunk c, SPM_KT points per step.
+// For every column tile tj the 256 threads evaluate the 64 x SPM_KT panel K_uf[tj] into LDS through kappa_lat (the forward pass's
+// evaluator) and wave w multiplies rows 16 w .. 16 w + 15 of PhiBar[ti, tj] (read from global memory: all of PhiBar stays in L2) with it
+// on v_mfma_f64_16x16x4_f64, two 16 x 16 accumulators in architectural VGPRs; operand map as in sparse_moments_kernel: register r of
+// acc[cb] of lane l is G[16 w + (l >> 4) + 4 r][16 cb + (l & 15)].  The workgroups ti = 0 also accumulate beta' k_t.  The weights then go
+// to LDS and thread (row i, point quarter) walks its 8 points and the latent's terms through ard_pair / lp_pair with weight g_it.
+// No atomics: the partial of (chunk, ti) depends on (arguments, chunk) only; sparse_grad_finish_kernel adds the partials in chunk order,
+// then in tile-row order.  Rows beyond nz and points beyond the chunk are never evaluated (neither z, x nor PhiBar is read there).
+// Partial of (l, c, ti): LMM_SUM_MAX_TERMS records of (4 + d) sums -- d/d multiplier, sum g k_c, d/d alpha or rho, d/d decay, then the d
+// per-dimension sums d/d l_k (l_k = the term's own per-dimension lengthscale, or its common one) -- followed by 64 x d input sums.
+// ---------------------------------------------------------------------------------------------------
+constexpr int SPG_SP = 64 + 4;                // LDS stride of one point's 64 panel rows (the fragment reads of 16 points x 4 k on distinct banks)
+constexpr int SPG_SG = SPM_KT + 1;            // LDS stride of one row's SPM_KT weights
+
+// One pair (z_i, x_t) of one term with weight wgt.  sils: the term's d inverse lengthscales (or periods), sdec: a locally periodic
+// term's P_k / l^2.  rec: acc0 (sum w h r^2, or sum w kap sum_k t_k s_k c_k), acck, acca, accd;  ard[k]: sum w h t_k^2 (or w kap t_k s_k c_k);
+// gz[k] += d k / d z_ik with its sign and 1 / l_k.
+template <int DK, bool PER>
+__device__ __forceinline__ void sparse_grad_pair(const LatentDev& g, const double* __restrict__ sils, const double* __restrict__ sdec,
+                                                 const double* zi, const double* __restrict__ xt, int d, double wgt, double* rec,
+                                                 double* ard, double* gz) {
+  const bool per = PER && (g.kind == LMM_KERNEL_PERIODIC || g.kind == LMM_KERNEL_LOCALLY_PERIODIC);
+  const bool lp = PER && g.kind == LMM_KERNEL_LOCALLY_PERIODIC;
+  double v[DK], r2 = 0.0, D2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < DK; ++k) {
+    v[k] = 0.0;
+    if (k < d) {
+      const double dx = zi[k] - xt[k], tk = dx * sils[k];       // difference first: exactly 0 at coincident points
+      if (per) {
+        double sn, cs;
+        sincospi(tk, &sn, &cs);
+        v[k] = sn * cs;
+        r2 = __builtin_fma(sn, sn, r2);
+        D2 = __builtin_fma(dx, dx, D2);
+      } else {
+        v[k] = tk;
+        r2 = __builtin_fma(tk, tk, r2);
+      }
+    }
+  }
+  double wh;
+  if (lp) lp_pair(g, r2, D2, wgt, rec[1], rec[2], rec[3], wh);
+  else if (per) ard_pair<DK, 2>(g.kind, g.var, g.alpha, r2, wgt, rec[0], rec[1], rec[2], wh);
+  else if (g.kind >= LMM_KERNEL_MATERN12) ard_pair<DK, 1>(g.kind, g.var, g.alpha, r2, wgt, rec[0], rec[1], rec[2], wh);
+  else ard_pair<DK, 0>(g.kind, g.var, g.alpha, r2, wgt, rec[0], rec[1], rec[2], wh);
+  const double pc = LMM_PI * g.alpha;
+#pragma unroll
+  for (int k = 0; k < DK; ++k)
+    if (k < d) {
+      double lk, zk;
+      if (per) {
+        const double dx = zi[k] - xt[k];
+        lk = (dx * sils[k]) * v[k];
+        zk = pc * v[k];
+        if (lp) zk = __builtin_fma(dx, sdec[k], zk);
+        rec[0] = __builtin_fma(wh, lk, rec[0]);
+      } else {
+        lk = v[k] * v[k];
+        zk = v[k];
+      }
+      ard[k] = __builtin_fma(wh, lk, ard[k]);
+      gz[k] = __builtin_fma(-sils[k] * wh, zk, gz[k]);
+    }
+}
+
+template <int SUM, int DK>
+__global__ __launch_bounds__(256) void sparse_grad_kernel(SparseGradArgs a, size_t stride) {
+  constexpr int NT = SUM ? LMM_SUM_MAX_TERMS : 1;
+  constexpr int NV = 4 + DK;
+  __shared__ double P[SPM_KT * SPG_SP];
+  __shared__ double Gs[64 * SPG_SG];
+  __shared__ double iw[SPM_KT], rr[SPM_KT];
+  __shared__ double xs[SPM_KT * DK];
+  __shared__ double sils[NT][DK], sdec[NT][DK];
+  __shared__ LatentDev gds[NT];
+  __shared__ double red[4][NT * NV];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int ti = blockIdx.x, c = blockIdx.y, l = blockIdx.z;
+  const SparseGradLat& S = a.lat[l];
+  const LatentDev g = S.g;
+  const int nterms = S.nterms < NT ? S.nterms : NT, d = a.d, nz = a.nz, ld = a.ld;
+  const int tm = (nz + 63) / 64;
+  const double* __restrict__ PhiBar = S.PhiBar;
+  const double* __restrict__ beta = S.beta;
+  if (t < NT) {
+    LatentDev q{};
+    if (t < nterms) q = S.gd[t];
+    gds[t] = q;
+  }
+  __syncthreads();
+  for (int e = t; e < NT * DK; e += 256) {
+    const int cc = e / DK, k = e - cc * DK;
+    double s = 0.0, sd = 0.0;
+    if (cc < nterms && k < d) {
+      const LatentDev& q = gds[cc];
+      s = q.ils ? q.ils[k] : q.inv_ls;
+      if (q.kind == LMM_KERNEL_LOCALLY_PERIODIC) sd = q.inv_decay * q.inv_decay / s;
+    }
+    sils[cc][k] = s; sdec[cc][k] = sd;
+  }
+  __syncthreads();                                     // sils, sdec: read by the epilogue whatever the chunk loop does
+  const int prow = t & 63, k0 = t >> 6;                // evaluation: panel row, first point (then every 4th); derivative stage: row, point quarter
+  const int gi = ti * 64 + prow;
+  const bool live = gi < nz;
+  double zi[DK], gz[DK], rec[NT][4], ard[NT][DK];
+#pragma unroll
+  for (int k = 0; k < DK; ++k) { zi[k] = (live && k < d) ? a.z[(size_t)gi * d + k] : 0.0; gz[k] = 0.0; }
+#pragma unroll
+  for (int cc = 0; cc < NT; ++cc) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) rec[cc][e] = 0.0;
+#pragma unroll
+    for (int k = 0; k < DK; ++k) ard[cc][k] = 0.0;
+  }
+  const long long tbeg = (long long)c * a.chunk;
+  long long tend = tbeg + a.chunk;
+  if (tend > a.n) tend = a.n;
+  const int l15 = lane & 15, lk = lane >> 4;
+  const int ar = ti * 64 + 16 * wv + l15;              // the lane's row of PhiBar (first MFMA operand)
+  for (long long t0 = tbeg; t0 < tend; t0 += SPM_KT) {
+    __syncthreads();                                   // the previous step's derivative stage has read Gs, iw, xs
+    if (t < SPM_KT) {
+      const long long tt = t0 + t;
+      double i1 = 0.0, rv = 0.0;
+      if (tt < tend) { i1 = 1.0 / (S.w ? S.w[tt] : S.wconst); rv = S.r[tt] - S.rsub; }
+      iw[t] = i1; rr[t] = rv;
+    }
+    for (int e = t; e < SPM_KT * DK; e += 256) {
+      const int pt = e / DK, k = e - pt * DK;
+      xs[e] = (k < d && t0 + pt < tend) ? a.x[(size_t)(t0 + pt) * d + k] : 0.0;
+    }
+    d4 acc[2];
+    acc[0] = (d4){0.0, 0.0, 0.0, 0.0}; acc[1] = (d4){0.0, 0.0, 0.0, 0.0};
+    double bacc = 0.0;
+    for (int tj = 0; tj < tm; ++tj) {
+      __syncthreads();                                 // the previous panel has been multiplied
+      {
+        const int zj = tj * 64 + prow;
+        const bool zlive = zj < nz;
+        const double* zp = a.z + (size_t)(zlive ? zj : 0) * d;
+        for (int k = k0; k < SPM_KT; k += 4) {
+          const long long tt = t0 + k;
+          double v = 0.0;
+          if (zlive && tt < tend) v = kappa_lat<SUM>(g, zp, a.x + (size_t)tt * d, d);
+          P[k * SPG_SP + prow] = v;
+        }
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int s4 = 0; s4 < 16; ++s4) {
+        const int ac = tj * 64 + 4 * s4 + lk;
+        const double fa = (ar < nz && ac < nz) ? PhiBar[(size_t)ac * ld + ar] : 0.0;
+        const double f0 = P[l15 * SPG_SP + 4 * s4 + lk], f1 = P[(16 + l15) * SPG_SP + 4 * s4 + lk];
+        acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, f0, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, f1, acc[1], 0, 0, 0);
+      }
+      if (ti == 0 && t < SPM_KT) {
+        const int nr = nz - tj * 64 < 64 ? nz - tj * 64 : 64;
+        for (int r = 0; r < nr; ++r) bacc = __builtin_fma(P[t * SPG_SP + r], beta[tj * 64 + r], bacc);
+      }
+    }
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * wv + lk + 4 * r, pt = 16 * cb + l15, gr = ti * 64 + row;
+        Gs[row * SPG_SG + pt] = gr < nz ? __builtin_fma(2.0, acc[cb][r], beta[gr] * rr[pt]) * iw[pt] : 0.0;
+      }
+    if (ti == 0 && t < SPM_KT && t0 + t < tend && S.grad_r) S.grad_r[t0 + t] = (bacc - rr[t]) * iw[t];
+    __syncthreads();
+    if (live) {
+      for (int j = 0; j < SPM_KT / 4; ++j) {
+        const int pt = (SPM_KT / 4) * k0 + j;
+        if (t0 + pt >= tend) break;
+        const double wgt = Gs[prow * SPG_SG + pt];
+#pragma unroll
+        for (int cc = 0; cc < NT; ++cc)
+          if (cc < nterms) sparse_grad_pair<DK, SUM == 2>(gds[cc], sils[cc], sdec[cc], zi, xs + pt * DK, d, wgt, rec[cc], ard[cc], gz);
+      }
+    }
+  }
+  // ---- the workgroup's partial ----
+  double* part = a.scratch + (((size_t)l * a.nch + c) * tm + ti) * stride;
+  const int nv = 4 + d;
+#pragma unroll
+  for (int cc = 0; cc < NT; ++cc) {
+    const LatentDev& q = gds[cc];
+    const bool per = q.kind == LMM_KERNEL_PERIODIC || q.kind == LMM_KERNEL_LOCALLY_PERIODIC;
+    const double pc = per ? LMM_PI * q.alpha : 1.0;
+    double v[NV];
+    v[0] = rec[cc][0] * q.inv_ls * pc;
+    v[1] = rec[cc][1];
+    v[2] = per ? rec[cc][2] * per_rho3(q.alpha) : rec[cc][2];
+    v[3] = rec[cc][3] * (q.inv_decay * q.inv_decay * q.inv_decay);
+#pragma unroll
+    for (int k = 0; k < DK; ++k) v[4 + k] = ard[cc][k] * sils[cc][k] * pc;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) {
+      const double sc = wave_sum(v[e]);
+      if (lane == 0) red[wv][cc * NV + e] = sc;
+    }
+  }
+  __syncthreads();
+  for (int e = t; e < LMM_SUM_MAX_TERMS * nv; e += 256) {
+    const int cc = e / nv, f = e - cc * nv;
+    double s = 0.0;
+    if (cc < nterms) { const int o = cc * NV + f; s = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o]; }
+    part[e] = s;
+  }
+  // row i's input sums over the four point quarters, in quarter order, 8 dimensions at a time (3 x 8 x 64 doubles fit in Gs)
+  double* zpart = part + (size_t)LMM_SUM_MAX_TERMS * nv;
+#pragma unroll
+  for (int kb = 0; kb < DK; kb += 8) {
+    __syncthreads();
+    if (k0 > 0)
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk)
+        if (kb + kk < DK) Gs[((k0 - 1) * 8 + kk) * 64 + prow] = gz[kb + kk];
+    __syncthreads();
+    if (k0 == 0)
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) {
+        const int k = kb + kk;
+        if (k < DK && k < d) zpart[(size_t)prow * d + k] = live ? ((gz[k] + Gs[kk * 64 + prow]) + Gs[(8 + kk) * 64 + prow]) + Gs[(16 + kk) * 64 + prow] : 0.0;
+      }
+  }
+}
+
+// grid (nb): per latent, the term records in the LMM_NGRAD + d layout of the gradient reductions ([0], [7], [8], [9], then d; zeros
+// elsewhere) and the d x nz input sums; chunk order, then tile-row order.
+__global__ __launch_bounds__(256) void sparse_grad_finish_kernel(const double* __restrict__ scratch, size_t stride, int nch, int nz, int d,
+                                                                 BatchPtr recs, BatchPtr gz) {
+  const int l = blockIdx.x, t = threadIdx.x, tm = (nz + 63) / 64, nv = 4 + d, no = LMM_NGRAD + d;
+  const double* base = scratch + (size_t)l * nch * tm * stride;
+  for (int e = t; e < LMM_SUM_MAX_TERMS * no; e += 256) {
+    const int cc = e / no, o = e - cc * no;
+    const int f = o == 0 ? 0 : o == 7 ? 1 : o == 8 ? 2 : o == 9 ? 3 : o >= LMM_NGRAD ? 4 + (o - LMM_NGRAD) : -1;
+    double tot = 0.0;
+    if (f >= 0)
+      for (int ti = 0; ti < tm; ++ti) {
+        double s = 0.0;
+        for (int c = 0; c < nch; ++c) s += base[((size_t)c * tm + ti) * stride + cc * nv + f];
+        tot += s;
+      }
+    recs.p[l][e] = tot;
+  }
+  if (gz.p[l] == nullptr) return;
+  const size_t zoff = (size_t)LMM_SUM_MAX_TERMS * nv;
+  for (int e = t; e < nz * d; e += 256) {
+    const int i = e / d, k = e - i * d, ti = i >> 6, row = i & 63;
+    double s = 0.0;
+    for (int c = 0; c < nch; ++c) s += base[((size_t)c * tm + ti) * stride + zoff + (size_t)row * d + k];
+    gz.p[l][e] = s;
+  }
+}
+
+// beta = R c for the upper triangular R = L_u^-T L_B^-T (M x M, ld) and c = L_B^-1 L_u^-1 b; grid (ceil(M / 256), nb)
+__global__ __launch_bounds__(256) void sparse_beta_kernel(BatchPtr R, int ld, int M, BatchPtr cv, BatchPtr beta) {
+  const int i = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (i >= M) return;
+  const double* __restrict__ r = R.p[l];
+  const double* __restrict__ c = cv.p[l];
+  double s = 0.0;
+  for (int j = i; j < M; ++j) s = __builtin_fma(r[(size_t)j * ld + i], c[j], s);
+  beta.p[l][i] = s;
+}
+
+// From the lower triangles Ki = K^-1 and Si = Sigma^-1, beta and T2 = K^-1 Phi K^-1 (full; symmetrised here: its two products round its
+// halves differently):  PhiBar = (Ki - Si - beta beta') / 2 into PB (both triangles), and -2 KuuBar = -2 PhiBar + sym(T2) into the lower
+// triangle of Si, in place -- the "inverse" argument of the gradient reductions over z.  grid (ceil(M / 256), M, nb)
+__global__ __launch_bounds__(256) void sparse_phibar_kernel(BatchPtr Ki, BatchPtr Si, BatchPtr T2, BatchPtr beta, BatchPtr PB, int ld, int M) {
+  const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, l = blockIdx.z;
+  if (i >= M || i < j) return;
+  const size_t lo = (size_t)j * ld + i, up = (size_t)i * ld + j;
+  const double* __restrict__ b = beta.p[l];
+  const double pb = 0.5 * (Ki.p[l][lo] - Si.p[l][lo] - b[i] * b[j]);
+  const double t2 = 0.5 * (T2.p[l][lo] + T2.p[l][up]);
+  PB.p[l][lo] = pb;
+  PB.p[l][up] = pb;
+  Si.p[l][lo] = t2 - 2.0 * pb;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Right solve by L^-1 (predictive-marginal gradients): C (M x N) {=, -=} A (M x K) * B (K x N), column-major, NN form,
 // batched over up to LMM_MAX_BATCH matrices (blockIdx.y), on v_mfma_f64_16x16x4_f64.  M, N multiples of 64, K of 16.
 //   SET = true : the 64-column leaf X_J = R_J W_J by a stored inverse diagonal block, IN PLACE (C == A): a workgroup owns all N = 64
@@ -5648,4 +5938,32 @@ void launch_sparse_bmat(const BatchPtr& Q, const BatchPtr& Au, const BatchPtr& B
                         int nb, hipStream_t st) {
   hipLaunchKernelGGL(sparse_bmat_kernel, dim3((NR + 255) / 256, NC, nb), dim3(256), 0, st, Q, Au, Bm, ld, NC, NR, M);
   hipLaunchKernelGGL(sparse_trace_kernel, dim3(nb), dim3(256), 0, st, Q, ld, M, trace);
+}
+size_t sparse_grad_partial_stride(int d) { return (size_t)LMM_SUM_MAX_TERMS * (4 + d) + (size_t)64 * d; }
+// mode: 0 plain latents of the five distance kinds, 1 some sum latent, 2 some (locally) periodic latent or term
+void launch_sparse_grad(const SparseGradArgs& a, int nb, int mode, hipStream_t st) {
+  const dim3 grid((a.nz + 63) / 64, a.nch, nb);
+  const size_t stride = sparse_grad_partial_stride(a.d);
+#define LMM_SPG_LAUNCH(DK)                                                                                       \
+  do {                                                                                                          \
+    if (mode == 2) hipLaunchKernelGGL((sparse_grad_kernel<2, DK>), grid, dim3(256), 0, st, a, stride);           \
+    else if (mode == 1) hipLaunchKernelGGL((sparse_grad_kernel<1, DK>), grid, dim3(256), 0, st, a, stride);      \
+    else hipLaunchKernelGGL((sparse_grad_kernel<0, DK>), grid, dim3(256), 0, st, a, stride);                     \
+  } while (0)
+  if (a.d == 1) LMM_SPG_LAUNCH(1);
+  else if (a.d <= 4) LMM_SPG_LAUNCH(4);
+  else if (a.d <= 8) LMM_SPG_LAUNCH(8);
+  else LMM_SPG_LAUNCH(LMM_SPARSE_DMAX);
+#undef LMM_SPG_LAUNCH
+}
+void launch_sparse_grad_finish(const double* scratch, int nch, int nz, int d, const BatchPtr& recs, const BatchPtr& gz, int nb,
+                               hipStream_t st) {
+  hipLaunchKernelGGL(sparse_grad_finish_kernel, dim3(nb), dim3(256), 0, st, scratch, sparse_grad_partial_stride(d), nch, nz, d, recs, gz);
+}
+void launch_sparse_beta(const BatchPtr& R, int ld, int M, const BatchPtr& c, const BatchPtr& beta, int nb, hipStream_t st) {
+  hipLaunchKernelGGL(sparse_beta_kernel, dim3((M + 255) / 256, nb), dim3(256), 0, st, R, ld, M, c, beta);
+}
+void launch_sparse_phibar(const BatchPtr& Ki, const BatchPtr& Si, const BatchPtr& T2, const BatchPtr& beta, const BatchPtr& PB, int ld,
+                          int M, int nb, hipStream_t st) {
+  hipLaunchKernelGGL(sparse_phibar_kernel, dim3((M + 255) / 256, M, nb), dim3(256), 0, st, Ki, Si, T2, beta, PB, ld, M);
 }

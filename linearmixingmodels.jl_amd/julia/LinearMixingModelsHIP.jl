@@ -451,7 +451,8 @@ end
 # elbo(VFE(f(z, ε)), fx, y) and dtc(...) (AbstractGPs src/sparse_approximations.jl) through lmm_oilmm_elbo (include/lmm_hip.h,
 # "inducing points"): Titsias' collapsed bound per latent after the OILMM projection, plus the regulariser of src/oilmm.jl:101-113.
 # z = vfe.fz.x.x (by outputs, shared by all latents), ε = the Fill noise of vfe.fz.  Prior OILMM only.  posterior(::VFE, fx, y) is
-# served by the C ABI and the Python mirror (lmm_oilmm_sparse_posterior_create, approx_posterior) and not yet by this shim.
+# served by the C ABI and the Python mirror (lmm_oilmm_sparse_posterior_create, approx_posterior) and not yet by this shim.  The rrule of
+# elbo (lmm_oilmm_elbo_grad) is with the other rrules below.
 function _elbo_dtc(vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real})
     fs, H, σ², x = unpack(fx)
     isposterior(fs) && error("inducing-point inference is served on a prior OILMM only")
@@ -946,6 +947,38 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.logpdf), fx::ByOutputsFill{HI
         return NoTangent(), dfx, Δ .* gy
     end
     return val[], logpdf_pullback
+end
+
+# elbo(VFE(f(z, ε)), fx, y) (lmm_oilmm_elbo_grad; include/lmm_hip.h "inducing points"): cotangents for the latent GPs' kernel parameters
+# and means, H = (U, S), σ², y and the inducing inputs z, in the way the logpdf rrule above is written.  The model's cotangent is
+# attached to fx.f: vfe.fz.f is the same model, and its slot in the VFE's tangent carries only z (a model given twice would otherwise
+# receive its cotangent twice).  The jitter ε gets no cotangent.  There is no rrule for dtc.
+function ChainRulesCore.rrule(::typeof(AbstractGPs.elbo), vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOILMM},
+                              y::AbstractVector{<:Real})
+    fs, H, σ², x = unpack(fx)
+    isposterior(fs) && error("inducing-point inference is served on a prior OILMM only")
+    X = _xmat(x); d, n = size(X); U, S, p, m = _hargs(H); gard = nothing; yv = Vector{Float64}(y)
+    Z = _xmat(vfe.fz.x.x); ε = Float64(noise_var(vfe.fz.Σy)); nz = size(Z, 2)
+    size(Z, 1) == d || error("the inducing inputs have d = $(size(Z, 1)), the inputs d = $d")
+    val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
+    gy = Vector{Float64}(undef, n * p); gS = Vector{Float64}(undef, m); gU = Matrix{Float64}(undef, p, m)
+    gg = Vector{LmmGpGrad}(undef, m); gz = Matrix{Float64}(undef, d, nz)
+    _gps(fs.fs) do gps, tags
+        GC.@preserve X yv U S Z gps gy gS gU gg gz check(ccall((:lmm_oilmm_elbo_grad, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint,
+             Ptr{Cdouble}, Cint, Cdouble, Cint, Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad},
+             Ptr{Cdouble}),
+            X, d, n, yv, p, U, S, m, σ², gps, 0, m, Z, nz, ε, 1, val, gy, gσ, gS, gU, gg, gz))
+        gard = _ard_grads(tags, d)
+    end
+    function elbo_pullback(Δ)
+        dlat = Tangent{typeof(fs)}(; fs=_fstangent(fs.fs, gg, Δ, gard))
+        dfx = Tangent{typeof(fx)}(; x=NoTangent(), f=Tangent{typeof(fx.f)}(; f=dlat, H=_htangent(H, Δ .* gU, Δ .* gS)),
+                                  Σy=_noise_tangent(fx, Δ * gσ[]))
+        dvfe = Tangent{typeof(vfe)}(; fz=Tangent{typeof(vfe.fz)}(; x=_motangent(vfe.fz.x, Δ .* gz), f=NoTangent(), Σy=NoTangent()))
+        return NoTangent(), dvfe, dfx, Δ .* gy
+    end
+    return val[], elbo_pullback
 end
 
 # logpdf with missing observations (lmm_oilmm_logpdf_grad_missing): cotangents for the latent GPs, the noise and the observed entries

@@ -770,6 +770,26 @@ def dtc(vfe: VFE, fx: "FiniteGP", y, with_regulariser: bool = True) -> float:
     return _elbo_dtc(vfe, fx, y, with_regulariser, "dtc")[1]
 
 
+def elbo_and_gradient(vfe: VFE, fx: "FiniteGP", y, with_regulariser: bool = True) -> dict:
+    """Value and gradient of elbo(vfe, fx, y): {"value", "y", "sigma2", "S", "U", "gps", "z"}.  "value" is bitwise elbo(vfe, fx, y);
+    "y", "sigma2", "S", "U" and "gps" are as logpdf_and_gradient returns them for a prior OILMM ("gps" through _gps_grads: per-dimension
+    lengthscales, alpha, r, decay and sum terms included); "z" is the gradient with respect to the inducing inputs, shaped and typed
+    like vfe.z ((M,) or (d, M); NumPy or torch).  There is no gradient of dtc."""
+    y = _sparse_args(vfe, fx, y, "elbo_and_gradient")
+    L.ensure_init()
+    f, x = fx.f, fx.x
+    Ua, Sa, p, m = _H_args(f.H)
+    val, gs2 = C.c_double(), C.c_double()
+    gy, gS, gU = _alloc_like(y if L._is_torch(y) else x.x, x.n * p), np.empty(m), np.empty(p * m)
+    gz = _alloc_like(vfe.z, x.dim * vfe.nz)
+    gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.f.fs])
+    L.check(L.load().lmm_oilmm_elbo_grad(x.carr().ptr, x.dim, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), ga, 0, m,
+                                         vfe.carr().ptr, vfe.nz, vfe.jitter, int(with_regulariser), C.byref(val), L.Arr(gy, True).ptr,
+                                         C.byref(gs2), L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg, L.Arr(gz, True).ptr))
+    return {"value": val.value, "y": gy, "sigma2": gs2.value, "S": gS, "U": gU.reshape(m, p).T.copy(),
+            "gps": _gps_grads(gg, ga, m, x.dim), "z": _x_grad(gz, vfe.z)}
+
+
 def approx_posterior(vfe: VFE, fx: "FiniteGP", y) -> "ILMM":
     """posterior(VFE(f(z)), fx, y) of AbstractGPs: an OILMM with the same H whose latents are ApproxPosteriorGPs.  mean_and_var, mean,
     var and marginals work on it; nothing else does."""
