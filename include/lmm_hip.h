@@ -702,6 +702,19 @@ int lmm_dev_claim_scramble(int on);
 /* C[MxN] -= A[MxK] * B[NxK]^T (column-major, device). lower != 0: only tiles on/below the diagonal. */
 int lmm_dev_gemm_nt_sub(double* C, int ldc, const double* A, int lda, const double* B, int ldb,
                         int M, int N, int K, int lower);
+/* Exact int8 modular emulation of the large Float64 trailing updates (switches LMM_F64_EMUL, LMM_F64_EMUL_MINK, read
+ * once).  Test hook of the switches: on = 0 / 1, min_k >= 128 (updates with K >= min_k are emulated), 8 <= nmod <= 16 moduli;
+ * on < 0 goes back to the env defaults. */
+int lmm_dev_set_f64_emul(int on, int min_k, int nmod);
+/* C[MxN] -= A[MxK] * A[0:N, :]^T for i >= j only (column-major, device pointers, one matrix) through the emulation kernels.
+ * M >= N, K a multiple of 128, K <= 16384.  |error_ij| <= 4 K 2^-b amax_i amax_j + rounding of C, b = the bit budget for K. */
+int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N, int K, int nmod);
+/* Host-only (no GPU, no lmm_init needed): out[MxN] (ldo) = the emulated product A[MxK] * B[NxK]^T (column-major host pointers, K <=
+ * 4096) -- row scaling, residues, products modulo each modulus and the CRT combine in plain C++ with the constants and scalar steps of
+ * the kernels; the bit budget b is the one of depth k_bound >= K.  consts (may be NULL, 68 doubles): [0..15] moduli, [16..31],
+ * [32..47], [48..63] the three chunks of the CRT weights, [64..66] the chunks of the moduli's product, [67] b. */
+int lmm_dev_emul_host(const double* A, int lda, const double* B, int ldb, int M, int N, int K, int nmod, int k_bound, double* out,
+                      int ldo, double* consts);
 /* Gram assembly of one latent into a padded factor matrix (lower triangle + pad identity). */
 int lmm_dev_gram(double* A, int ld, int nrows, int ncols, const double* x, int d, int n,
                  const lmm_gp_t* gp, double diag_add);

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "lmm_internal.h"
+#include "lmm_emul.h"
 
 namespace {
 
@@ -48,6 +49,9 @@ struct Ctx {
   size_t pin_cap = 0, pin_off = 0;
   char* pin_dev = nullptr;           // the arena as the device addresses it (hipHostGetDevicePointer); nullptr: not mapped
   std::vector<void*> scratch;          // device blocks that live until the NEXT API call starts (call_scratch)
+  struct EmulBlock { void* p; size_t bytes; };
+  std::map<hipStream_t, EmulBlock> emul_blocks;   // scratch of the emulated updates: ONE block per stream per API call, shared by that stream's batches
+  bool emul_denied = false;            // this API call could not get such a block: its remaining batches take the f64 path without asking again
   int* region_flags = nullptr;         // dependency flags of potrf_region_kernel: [stream][matrix][region_flag_ints], zeroed ONCE (lmm_init)
                                        // -- every launch tags its flags with a fresh epoch, so they never need resetting
   std::multimap<size_t, void*> pool;   // cached device blocks (size -> ptr)
@@ -148,6 +152,20 @@ double* call_scratch(size_t count) {
 void release_call_scratch() {
   for (void* p : g.scratch) dev_free(p);
   g.scratch.clear();
+  g.emul_blocks.clear();
+  g.emul_denied = false;
+}
+// call_scratch that may be refused: nullptr when neither the pool nor hipMalloc has a block of that size (the pool is NOT flushed
+// and no error is recorded: the caller has another way)
+void* call_scratch_try(size_t bytes) {
+  bytes = (bytes + 255) & ~size_t(255);
+  void* p = nullptr;
+  auto it = g.pool.find(bytes);
+  if (it != g.pool.end()) { p = it->second; g.pool.erase(it); }
+  else if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  g.live[p] = bytes;
+  g.scratch.push_back(p);
+  return p;
 }
 
 template <typename T>
@@ -730,7 +748,23 @@ static int g_slots_in_flight = 1;       // batches that run concurrently on the 
 static int g_region_whole = 1;          // LMM_REGION_ALL=1: also as the base case of the recursion for larger matrices (measured: no gain)
 static int g_region_cols = -1;          // widest block column potrf_region_kernel takes in one launch (LMM_REGION=<columns>, up to 1024; default 0: off)
 // bulk_done (implies first_done): the rows below that block are solved as well (the update launch that factored it ran them too).
-struct NodeFlags { int* p = nullptr; int stride = 0; int min_k = 0, max_k = 1 << 30; int rows_real = -1; BatchPtr S{}; int region_cols = 0; };   // region_cols: widest block column that becomes ONE dataflow launch in this factorisation   // S: region assistants' scratch      // rows_real: rows that hold data (-1: all NR)
+struct NodeFlags { int* p = nullptr; int stride = 0; int min_k = 0, max_k = 1 << 30; int rows_real = -1; BatchPtr S{}; int region_cols = 0;
+                   void* emul = nullptr; size_t emul_bytes = 0; int emul_G = 0, emul_mink = 0, emul_nmod = 0; };      // emul: scratch of the int8 emulation of the updates with K >= emul_mink (nullptr: off)   // region_cols: widest block column that becomes ONE dataflow launch in this factorisation   // S: region assistants' scratch      // rows_real: rows that hold data (-1: all NR)
+// Float64 updates with K >= LMM_F64_EMUL_MINK run as exact int8 modular GEMMs (lmm_kernels_i8.hip): LMM_F64_EMUL=0 keeps
+// them on the f64 MFMA kernel.  The env values are read once; lmm_dev_set_f64_emul replaces them (tests).
+static int g_emul_on = -1, g_emul_mink = -1, g_emul_nmod = LMM_EMUL_MAXMOD;
+static void emul_switches() {
+  if (g_emul_on < 0) { const char* e = getenv("LMM_F64_EMUL"); g_emul_on = e ? (atoi(e) != 0) : 1; }
+  if (g_emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_emul_mink = e ? std::max(128, atoi(e)) : 4096; }      // measured crossover: K = 2048 is slower emulated
+}
+// scratch bytes of the widest emulated update of the recursion over the columns [j0, j0 + w)
+static size_t emul_need(int NR, int j0, int w, int mink, int G, int nmod) {
+  if (w < 256) return 0;
+  const int h = split(w), r0 = j0 + h, Nc = w - h;
+  if (h < mink) return 0;
+  size_t need = (Nc >= 128 && emul_shape_ok(NR - r0, Nc, h)) ? emul_scratch_bytes(NR - r0, Nc, h, G, nmod) : 0;
+  return std::max(need, std::max(emul_need(NR, j0, h, mink, G, nmod), emul_need(NR, r0, Nc, mink, G, nmod)));
+}
 void potrf_rec_panel(const Batch& B, const BatchPtr& W2, const BatchInfo& flags, const NodeFlags& nfl, int ld, int NR, int j0, int w, int n_real,
                      hipStream_t st, bool first_done, bool bulk_done = false) {
   const double nb = B.nb;
@@ -769,10 +803,21 @@ void potrf_rec_panel(const Batch& B, const BatchPtr& W2, const BatchInfo& flags,
     {
       // K >= 1024: potrf_node_kernel<2> (+ gemm16h_kernel for a ragged last 64 rows) -- the dominant kernel; below: potrf_node_kernel<1>.
       // With the bulk rows of the next panel in the same launch (nfl.p): + their Mb * 128^2 flops and 16 B per entry
-      const double Mb = (nfl.p && h >= nfl.min_k && h <= nfl.max_k) ? std::max(0.0, Mr - 128.0) : 0;
+      // emulated (lmm_kernels_i8.hip): convert + int8 GEMMs + combine in place of the f64 update, then the leaf as a launch of its own;
+      // the same flop count, so the class's rate reads as an f64-EQUIVALENT rate
+      const bool emul = nfl.emul != nullptr && h >= nfl.emul_mink && emul_shape_ok(NR - r0, Nc, h);
+      const double Mb = (!emul && nfl.p && h >= nfl.min_k && h <= nfl.max_k) ? std::max(0.0, Mr - 128.0) : 0;
       ProfScope ps(h >= 1024 ? LMM_PROF_UPDATE : LMM_PROF_UPDATE_SHORT,
                    nb * (2.0 * h * outs + 2.0 * 128.0 * 128.0 * 128.0 / 3.0 + Mb * 128.0 * 128.0), st, NR - r0, Nc, h,
                    nb * (16.0 * outs + 8.0 * Mr * h + 16.0 * Mb * 128.0));
+      if (emul) {
+        const size_t need = emul_scratch_bytes(NR - r0, Nc, h, nfl.emul_G, nfl.emul_nmod);
+        if (need > nfl.emul_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", need, nfl.emul_bytes);
+        guard_extent(nfl.emul, need / 8, need / 8, 1, false, "emulated update (scratch)");
+        HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, NR - r0, Nc, h, B.nb, nfl.emul_G, nfl.emul_nmod, nfl.emul, st));
+        launch_leaf128(B.A, (size_t)r0 * ld + r0, ld, B.W, (size_t)(r0 / 64) * 4096, W2, (size_t)(r0 / 128) * 16384, r0, n_real, B.info, B.nb, st);
+        fused = false;
+      } else
       fused = launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, h, Nc, n_real, B.nb, st, (h >= nfl.min_k && h <= nfl.max_k) ? nfl.p : nullptr, nfl.stride);
     }
     potrf_rec_panel(B, W2, flags, nfl, ld, NR, r0, Nc, n_real, st, true, fused);
@@ -863,6 +908,31 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
     const size_t per_s = (size_t)LMM_REGION_ASST_TILES * 4096;
     double* sb = call_scratch(per_s * B.nb);
     for (int j = 0; j < B.nb; ++j) nfl.S.p[j] = sb + per_s * j;
+  }
+  // Scratch of the emulated updates: sized for the widest emulated level of this factorisation and reused by every level; the batch
+  // goes through it in groups of G matrices (at most ~12 GB).  ONE block per stream per API call (g.emul_blocks): the batches a stream
+  // factors one after the other share it (stream order keeps them apart), so an API call holds at most one block per stream it uses
+  // however many batches it has -- plus the smaller ones a stream outgrew, if its batches differ in shape.  If a block cannot be
+  // had the f64 path runs, for the rest of the call (said once per process on stderr).
+  emul_switches();
+  if (g_emul_on && !g.emul_denied) {
+    const size_t one = emul_need(NR, 0, NC, g_emul_mink, 1, g_emul_nmod);
+    if (one > 0) {
+      const int G = (int)std::max<size_t>(1, std::min<size_t>(std::min(4, B.nb), (size_t)12e9 / one));
+      const size_t bytes = emul_need(NR, 0, NC, g_emul_mink, G, g_emul_nmod);
+      auto it = g.emul_blocks.find(st);
+      void* blk = (it != g.emul_blocks.end() && it->second.bytes >= bytes) ? it->second.p : nullptr;
+      if (blk == nullptr) {
+        blk = call_scratch_try(bytes);
+        if (blk != nullptr) g.emul_blocks[st] = Ctx::EmulBlock{blk, bytes};
+        else {
+          g.emul_denied = true;
+          static bool said = false;
+          if (!said) { said = true; fprintf(stderr, "lmm: no %zu-byte scratch for the int8-emulated updates: they run on the f64 kernel\n", bytes); }
+        }
+      }
+      if (blk != nullptr) { nfl.emul = blk; nfl.emul_bytes = bytes; nfl.emul_G = G; nfl.emul_mink = g_emul_mink; nfl.emul_nmod = g_emul_nmod; }
+    }
   }
   potrf_rec_panel(B, W2, flags, nfl, ld, NR, 0, NC, n_real, st, false);
 }
@@ -966,7 +1036,11 @@ void batch_plan(int ms, int* nb_per, int* nstreams_used, double bytes_per_latent
       double avail = (double)fr;
       for (const auto& kv : g.pool) avail += (double)kv.first;
       const double budget = 0.8 * avail;
-      while ((double)b * ns * bytes_per_latent > budget && (b > 1 || ns > 1)) {
+      // + one scratch block of the emulated updates per stream (potrf_batch: at most ~12 GB each), for working sets whose matrices
+      // are large enough to have an emulated level (n >= 2 LMM_F64_EMUL_MINK)
+      emul_switches();
+      const double per_stream = (g_emul_on && !g_f32 && bytes_per_latent >= 32.0 * g_emul_mink * g_emul_mink) ? 12e9 : 0.0;
+      while ((double)b * ns * bytes_per_latent + ns * per_stream > budget && (b > 1 || ns > 1)) {
         if (b > 1) b = (b + 1) / 2; else --ns;
         nbatches = (ms + b - 1) / b;
         ns = std::max(1, std::min(ns, nbatches));
@@ -5055,6 +5129,75 @@ int lmm_dev_check_info(const int* info, int count, int latent_begin) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (!info || count < 0) return fail(LMM_ERR_ARG, "bad arguments");
   return check_info(info, (size_t)count, latent_begin);
+}
+
+// Test hook of the emulation switches (the env values are read once): on < 0 goes back to the env defaults.
+int lmm_dev_set_f64_emul(int on, int min_k, int nmod) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (on < 0) { g_emul_on = -1; g_emul_mink = -1; g_emul_nmod = LMM_EMUL_MAXMOD; return LMM_OK; }
+  if (min_k < 128 || nmod < LMM_EMUL_MINMOD || nmod > LMM_EMUL_MAXMOD) return fail(LMM_ERR_ARG, "lmm_dev_set_f64_emul: min_k >= 128, %d <= nmod <= %d", LMM_EMUL_MINMOD, LMM_EMUL_MAXMOD);
+  g_emul_on = on ? 1 : 0; g_emul_mink = min_k; g_emul_nmod = nmod;
+  return LMM_OK;
+}
+// C (M x N, lower trapezoid i >= j) -= A A[0:N]' through the emulation kernels: one matrix, device pointers.
+int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N, int K, int nmod) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!C || !A || nmod < LMM_EMUL_MINMOD || nmod > LMM_EMUL_MAXMOD || ldc < M || lda < M || !emul_shape_ok(M, N, K)) return fail(LMM_ERR_ARG, "bad arguments");
+  guard_extent(C, M, ldc, N, false, "lmm_dev_syrk_emul (C)"); guard_extent(A, M, lda, K, false, "lmm_dev_syrk_emul (A)");
+  const size_t bytes = emul_scratch_bytes(M, N, K, 1, nmod);
+  double* scratch = call_scratch((bytes + 7) / 8);
+  BatchPtr Cb{}, Pb{};
+  Cb.p[0] = C; Pb.p[0] = const_cast<double*>(A);
+  HIPCHK(launch_emul_update(Cb, 0, ldc, Pb, 0, lda, M, N, K, 1, 1, nmod, scratch, g.streams[0]));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(g.streams[0]));
+  return LMM_OK;
+  LMM_CATCH
+}
+// Host-only (no GPU, no lmm_init needed): row scaling, residues, integer products modulo each modulus and the CRT combine of one
+// small product in plain C++, with the constants and the scalar steps the kernels use (lmm_emul.h).
+int lmm_dev_emul_host(const double* A, int lda, const double* B, int ldb, int M, int N, int K, int nmod, int k_bound, double* out,
+                      int ldo, double* consts) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!A || !B || !out || M < 1 || N < 1 || K < 1 || K > 4096 || lda < M || ldb < N || ldo < M || nmod < LMM_EMUL_MINMOD || nmod > LMM_EMUL_MAXMOD || k_bound < K)
+    return fail(LMM_ERR_ARG, "lmm_dev_emul_host: bad arguments");
+  const EmulConst c = emul_make_const(nmod);
+  const int bits = emul_bits(nmod, k_bound);
+  struct Rows { std::vector<int8_t> res; std::vector<double> sc; std::vector<int> ex; };
+  auto convert = [&](const double* X, int ld, int n) {
+    Rows r; r.res.assign((size_t)nmod * n * K, 0); r.sc.assign(n, 0.0); r.ex.assign(n, 0);
+    for (int i = 0; i < n; ++i) {
+      double amax = 0.0; bool finite = true;
+      for (int k = 0; k < K; ++k) { const double a = std::fabs(X[i + (size_t)k * ld]); if (!(a <= 1.79769313486231570815e308)) finite = false; else if (a > amax) amax = a; }
+      if (!finite) { r.sc[i] = std::nan(""); continue; }
+      if (amax == 0.0) continue;
+      const int e = emul_row_exp(amax);
+      r.sc[i] = 1.0; r.ex[i] = e - bits;
+      for (int k = 0; k < K; ++k) {
+        const long long v = emul_trunc(X[i + (size_t)k * ld], bits - e);
+        for (int t = 0; t < nmod; ++t) r.res[((size_t)t * n + i) * K + k] = (int8_t)emul_residue(v, c.p[t], 1.0f / (float)c.p[t], c.c1[t], c.c2[t]);
+      }
+    }
+    return r;
+  };
+  const Rows ra = convert(A, lda, M), rb = convert(B, ldb, N);
+  for (int j = 0; j < N; ++j)
+    for (int i = 0; i < M; ++i) {
+      int u[LMM_EMUL_MAXMOD] = {0};
+      for (int t = 0; t < nmod; ++t) {
+        int acc = 0;
+        for (int k = 0; k < K; ++k) acc += (int)ra.res[((size_t)t * M + i) * K + k] * (int)rb.res[((size_t)t * N + j) * K + k];
+        u[t] = emul_mod_sym(acc, c.p[t], 1.0f / (float)c.p[t]);
+      }
+      out[i + (size_t)j * ldo] = std::ldexp(emul_crt(u, c) * ra.sc[i] * rb.sc[j], ra.ex[i] + rb.ex[j]);
+    }
+  if (consts) {      // [0..15] p_t, [16..31] w_t1, [32..47] w_t2, [48..63] w_t3, [64..66] P1..P3, [67] b
+    for (int t = 0; t < LMM_EMUL_MAXMOD; ++t) { consts[t] = c.p[t]; consts[16 + t] = c.w1[t]; consts[32 + t] = c.w2[t]; consts[48 + t] = c.w3[t]; }
+    consts[64] = c.P1; consts[65] = c.P2; consts[66] = c.P3; consts[67] = bits;
+  }
+  return LMM_OK;
 }
 
 int lmm_dev_gemm_nt_sub(double* C, int ldc, const double* A, int lda, const double* B, int ldb, int M, int N, int K,

@@ -160,6 +160,12 @@ size_t node_flag_ints(int NR);            // ints per matrix of the NODE_FUSE fl
 // lmm_kernels_f32w.hip: fp32 C -= A B' on 256 x 256 tiles (one workgroup per CU); false: not launched (shape / switch), use the 128-tile kernel
 bool launch_gemm32w(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B, size_t offB, int ldb,
                     int M, int N, int K, int lower, int nb, int cus, bool deterministic, hipStream_t st);
+// lmm_kernels_i8.hip: Float64 C_m -= P_m P_m[0:N]' (C_m at C.p[m] + offC, the M x K panel P_m at P.p[m] + offP; lower trapezoid, i >= j) as exact int8 modular GEMMs.  emul_shape_ok:
+// M >= N, K a multiple of 128 within the int32 accumulator bound.  Matrices go through `scratch` (emul_scratch_bytes) in groups of G.
+bool emul_shape_ok(int M, int N, int K);
+size_t emul_scratch_bytes(int M, int N, int K, int G, int nmod);
+hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
+                              int G, int nmod, void* scratch, hipStream_t st);      // the first HIP error of its host-side calls
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,
                    const BatchInfo& info, int nb, hipStream_t st);
 // no_splitk: never split the last round's tiles along K (their f64 atomics make the sum order run-dependent): bitwise reproducible

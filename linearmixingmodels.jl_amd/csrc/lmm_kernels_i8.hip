@@ -1,0 +1,262 @@
+// lmm_kernels_i8.hip -- the large Float64 trailing updates C -= A B' of the factorisation as exact int8 modular GEMMs.
+// Built WITHOUT -amdgpu-mfma-vgpr-form=1.  Three steps per update, for groups of matrices:
+//   1. emul_rowmax_kernel + emul_convert_kernel: per panel row the exponent e_i = ceil(log2 max_k |a_ik|), the integers
+//      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows;
+//   2. emul_gemm_kernel: one int8 SYRK-shaped GEMM per (matrix, modulus) on 256 x 256 tiles of the lower trapezoid, int32
+//      accumulators, reduced mod p to one byte per output (a copy of the 16x16x64 form of tools/i8_gemm_probe.hip's kernel, which
+//      stands alone: a change here has to be made there too before the probe's numbers speak for this kernel);
+//   3. emul_combine_kernel: CRT reconstruction in Float64 (lmm_emul.h) and C_ij -= X 2^(e_i + e_j - 2b) for i >= j.
+// Integer sums are exact in any order: the result is bitwise reproducible.
+#include "lmm_internal.h"
+#include "lmm_emul.h"
+#include <algorithm>
+#include <map>
+#include <utility>
+#include <vector>
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+constexpr int TILE = 256, BK = 128;
+constexpr int STAGE_BYTES = 2 * TILE * BK;      // A tile + B tile of one K step
+constexpr unsigned long long ABS_MASK = 0x7FFFFFFFFFFFFFFFull, INF_BITS = 0x7FF0000000000000ull;
+
+inline size_t rup256(size_t v) { return (v + 255) & ~size_t(255); }
+
+// amax[z Mp + i] = max_k |a_ik| as a bit pattern (order-preserving for non-negative doubles; a NaN is above everything)
+__global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, unsigned long long* amax) {
+  const int i = blockIdx.x * 256 + threadIdx.x, z = blockIdx.z;
+  if (i >= M) return;
+  const double* P = A.p[g0 + z] + off + i;
+  const int k0 = blockIdx.y * 64, k1 = min(K, k0 + 64);
+  unsigned long long m = 0;
+  for (int k = k0; k < k1; ++k) m = max(m, (unsigned long long)__double_as_longlong(P[(size_t)k * ld]) & ABS_MASK);
+  atomicMax(&amax[(size_t)z * Mp + i], m);
+}
+
+// 32 rows x 128 k per workgroup: reads coalesced along the rows of the column-major panel, residues transposed through LDS into
+// K-contiguous int8 rows R[(z nmod + t) Mp + i][k].  Rows M .. Mp - 1 (padding up to the GEMM tile) get zero residues.
+constexpr int CV_ROWS = 32, CV_K = 128, CV_PITCH = 132;
+__global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, int bits, EmulConst c,
+                                                           const unsigned long long* amax, int8_t* R, double* sc, int* ex) {
+  __shared__ int8_t lds[LMM_EMUL_MAXMOD * CV_ROWS * CV_PITCH];
+  const int tid = threadIdx.x, ti = tid & 31, tk = tid >> 5, z = blockIdx.z;
+  const int i = blockIdx.x * CV_ROWS + ti, k0 = blockIdx.y * CV_K;
+  unsigned long long mb = 0;
+  if (i < M) mb = amax[(size_t)z * Mp + i];
+  const bool finite = mb < INF_BITS, live = mb != 0 && finite;
+  int e = 0;
+  if (live) e = emul_row_exp(__longlong_as_double((long long)mb));
+  if (blockIdx.y == 0 && tk == 0) {      // row scale: 0 for an all-zero (or padding) row, NaN for a row with a non-finite entry
+    sc[(size_t)z * Mp + i] = live ? 1.0 : (finite ? 0.0 : __longlong_as_double(0x7FF8000000000000ll));
+    ex[(size_t)z * Mp + i] = live ? e - bits : 0;
+  }
+  const double* P = A.p[g0 + z] + off + i;
+#pragma unroll 4
+  for (int s = 0; s < CV_K / 8; ++s) {
+    const int kk = tk + 8 * s;
+    long long v = 0;
+    if (live) v = emul_trunc(P[(size_t)(k0 + kk) * ld], bits - e);
+#pragma unroll
+    for (int t = 0; t < LMM_EMUL_MAXMOD; ++t)
+      if (t < c.nmod) lds[(t * CV_ROWS + ti) * CV_PITCH + kk] = (int8_t)emul_residue(v, c.p[t], 1.0f / (float)c.p[t], c.c1[t], c.c2[t]);
+  }
+  __syncthreads();
+  for (int idx = tid; idx < c.nmod * CV_ROWS * (CV_K / 4); idx += 256) {
+    const int w = idx & 31, row = (idx >> 5) & 31, t = idx >> 10;
+    const int v = *reinterpret_cast<const int*>(&lds[(t * CV_ROWS + row) * CV_PITCH + 4 * w]);
+    *reinterpret_cast<int*>(R + (((size_t)z * c.nmod + t) * Mp + blockIdx.x * CV_ROWS + row) * K + k0 + 4 * w) = v;
+  }
+}
+
+// lower-trapezoid tiles in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles share at most 12 operand panels
+inline int emul_tile_count(int tm, int tn) {
+  int n = 0;
+  for (int i = 0; i < tm; ++i) n += (i + 1 < tn) ? i + 1 : tn;
+  return n;
+}
+// The list is built on the host once per (tile rows, tile columns) and kept on the device for the life of the process (a few KB per
+// shape; one process drives one GPU).  nullptr: the allocation or the copy failed (*err says why).
+const int2* emul_tiles(int tm, int tn, hipError_t* err) {
+  static std::map<std::pair<int, int>, int2*> cache;
+  auto it = cache.find({tm, tn});
+  if (it != cache.end()) return it->second;
+  std::vector<int2> v;
+  for (int I = 0; I < tm; I += 8)
+    for (int J = 0; J < tn; J += 4)
+      for (int i = I; i < std::min(I + 8, tm); ++i)
+        for (int j = J; j < std::min(J + 4, tn); ++j)
+          if (j <= i) v.push_back(make_int2(i, j));
+  int2* d = nullptr;
+  *err = hipMalloc((void**)&d, v.size() * sizeof(int2));
+  if (*err != hipSuccess) return nullptr;
+  *err = hipMemcpy(d, v.data(), v.size() * sizeof(int2), hipMemcpyHostToDevice);
+  if (*err != hipSuccess) { (void)hipFree(d); return nullptr; }
+  cache[{tm, tn}] = d;
+  return d;
+}
+
+__device__ __forceinline__ void glds16(const int8_t* src, int8_t* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+// One batch item = one (matrix, modulus): U[item][j][i] = (sum_k R[item][i][k] R[item][j][k]) mod p, i contiguous.
+//   workgroup tile 256 x 256 x 128, 8 waves as 2 (M) x 4 (N), v_mfma_i32_16x16x64_i8 (wave tile 128 x 64 = 8 x 4 accumulators);
+//   two LDS stages of 64 KiB filled by global_load_lds_dwordx4 (tile t + 1 in flight while tile t is multiplied);
+//   LDS rows are 128 B; the 16-B chunk index is XORed with (row >> 1) & 7 on the SOURCE address and on the fragment read, so every
+//   ds_read_b128 lane group hits 16 distinct 16-B slots of the 256-B bank row.
+// Both operands are fragment-loaded the same way (lane l: row l & 15, bytes 16 (l >> 4) .. + 15 of the 64-deep k range), so the k
+// order inside an MFMA is the same for A and B whatever the hardware's k map is.  Mp, Np multiples of 256, K of 128: no edges.
+__global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
+                                                           int Mp, int Np, int K, EmulConst c) {
+  __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
+  // blocks b and b + 8 share an XCD: give each XCD a contiguous range of work ids, so that its 32 resident blocks are one supertile
+  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  const int item = wg / ntiles;
+  const int2 t = tiles[wg - item * ntiles];
+  const int8_t* Rb = R + (size_t)item * Mp * K;
+  const int8_t* srcA[4];
+  const int8_t* srcB[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = wid * 32 + q * 8 + (lane >> 3), chunk = (lane & 7) ^ ((row >> 1) & 7);
+    srcA[q] = Rb + ((size_t)t.x * TILE + row) * K + chunk * 16;
+    srcB[q] = Rb + ((size_t)t.y * TILE + row) * K + chunk * 16;
+  }
+  auto stage = [&](int buf, int k0) {
+    int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) glds16(srcA[q] + k0, base + q * 1024);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) glds16(srcB[q] + k0, base + TILE * BK + q * 1024);
+  };
+  v4i acc[8][4];
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = (v4i){0, 0, 0, 0};
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk) stage((kt + 1) & 1, (kt + 1) * BK);
+    const int8_t* la = lds + (kt & 1) * STAGE_BYTES;
+    const int8_t* lb = la + TILE * BK;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int chunk = ks * 4 + fk;
+      v4i a[8], b[4];
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const int row = wr * 128 + m * 16 + frow;
+        a[m] = *reinterpret_cast<const v4i*>(la + row * BK + ((chunk ^ ((row >> 1) & 7)) << 4));
+      }
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int row = wc * 64 + n * 16 + frow;
+        b[n] = *reinterpret_cast<const v4i*>(lb + row * BK + ((chunk ^ ((row >> 1) & 7)) << 4));
+      }
+#pragma unroll
+      for (int m = 0; m < 8; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[m], b[n], acc[m][n], 0, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  // epilogue: reduce mod p (|acc| <= K 128^2 <= 2^28), pack the 4 consecutive rows a lane holds into one dword of U[j][i]
+  const int p = c.p[item % c.nmod];
+  const float rp = 1.0f / (float)p;
+  int8_t* Ub = U + (size_t)item * Np * Mp;
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const size_t j = (size_t)t.y * TILE + wc * 64 + n * 16 + frow;      // C/D map of 16x16: column = lane & 15, row = 4 (lane >> 4) + e
+      const int i = t.x * TILE + wr * 128 + m * 16 + 4 * fk;
+      unsigned w = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w |= (unsigned)(emul_mod_sym(acc[m][n][e], p, rp) & 0xFF) << (8 * e);
+      *reinterpret_cast<unsigned*>(Ub + j * Mp + i) = w;
+    }
+}
+
+// 4 consecutive rows x 1 column per thread: 16 dword loads of residues (coalesced along i), CRT, read-modify-write of C for i >= j
+__global__ __launch_bounds__(256) void emul_combine_kernel(BatchPtr A, int g0, size_t offC, int ldc, int M, int N, int Mp, int Np, EmulConst c,
+                                                           const int8_t* __restrict__ U, const double* __restrict__ sc, const int* __restrict__ ex) {
+  const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4, j = blockIdx.y, z = blockIdx.z;
+  if (i0 + 3 < j || i0 >= M) return;
+  unsigned w[LMM_EMUL_MAXMOD];
+#pragma unroll
+  for (int t = 0; t < LMM_EMUL_MAXMOD; ++t)
+    w[t] = t < c.nmod ? *reinterpret_cast<const unsigned*>(U + (((size_t)z * c.nmod + t) * Np + j) * Mp + i0) : 0u;
+  const double scj = sc[(size_t)z * Mp + j];
+  const int exj = ex[(size_t)z * Mp + j];
+  double* C = A.p[g0 + z] + offC + (size_t)j * ldc;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int i = i0 + e;
+    if (i < j || i >= M) continue;
+    int u[LMM_EMUL_MAXMOD];
+#pragma unroll
+    for (int t = 0; t < LMM_EMUL_MAXMOD; ++t) u[t] = (int)(int8_t)(w[t] >> (8 * e));
+    const double X = emul_crt(u, c);
+    C[i] -= ldexp(X * sc[(size_t)z * Mp + i] * scj, ex[(size_t)z * Mp + i] + exj);
+  }
+}
+
+struct EmulLayout { size_t R, U, amax, sc, ex, total; int Mp, Np, ntiles; };
+EmulLayout emul_layout(int M, int N, int K, int G, int nmod) {
+  EmulLayout L{};
+  L.Mp = (M + TILE - 1) / TILE * TILE; L.Np = (N + TILE - 1) / TILE * TILE;
+  L.ntiles = emul_tile_count(L.Mp / TILE, L.Np / TILE);
+  size_t o = 0;
+  L.R = o; o += rup256((size_t)G * nmod * L.Mp * K);
+  L.U = o; o += rup256((size_t)G * nmod * L.Np * L.Mp);
+  L.amax = o; o += rup256((size_t)G * L.Mp * 8);
+  L.sc = o; o += rup256((size_t)G * L.Mp * 8);
+  L.ex = o; o += rup256((size_t)G * L.Mp * 4);
+  L.total = o;
+  return L;
+}
+
+}  // namespace
+
+bool emul_shape_ok(int M, int N, int K) { return M >= N && N >= 1 && K >= BK && K % BK == 0 && K <= 16384; }      // int32 accumulators: K 128^2 <= 2^28
+
+size_t emul_scratch_bytes(int M, int N, int K, int G, int nmod) { return emul_layout(M, N, K, G, nmod).total; }
+
+// C_m (M x N at C.p[m] + offC, ldc) -= P_m P_m[0:N]' for the panels P_m (M x K at P.p[m] + offP, ldp), m < nb, lower trapezoid
+// (i >= j) only, in groups of G matrices through `scratch` (emul_scratch_bytes(M, N, K, G, nmod) bytes).  Returns the first HIP
+// error of its host-side calls (nothing is launched after one).
+hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
+                              int G, int nmod, void* scratch, hipStream_t st) {
+  static EmulConst consts[LMM_EMUL_MAXMOD + 1];
+  if (consts[nmod].nmod != nmod) consts[nmod] = emul_make_const(nmod);
+  const EmulConst& c = consts[nmod];
+  const int bits = emul_bits(nmod, K);
+  const EmulLayout L = emul_layout(M, N, K, G, nmod);
+  hipError_t err = hipSuccess;
+  const int2* tiles = emul_tiles(L.Mp / TILE, L.Np / TILE, &err);
+  if (tiles == nullptr) return err;
+  char* s = static_cast<char*>(scratch);
+  int8_t* R = reinterpret_cast<int8_t*>(s + L.R);
+  int8_t* U = reinterpret_cast<int8_t*>(s + L.U);
+  unsigned long long* amax = reinterpret_cast<unsigned long long*>(s + L.amax);
+  double* sc = reinterpret_cast<double*>(s + L.sc);
+  int* ex = reinterpret_cast<int*>(s + L.ex);
+  for (int g0 = 0; g0 < nb; g0 += G) {
+    const int gc = std::min(G, nb - g0);
+    err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
+    if (err != hipSuccess) return err;
+    emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, K, amax);
+    emul_convert_kernel<<<dim3(L.Mp / CV_ROWS, K / CV_K, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, K, bits, c, amax, R, sc, ex);
+    emul_gemm_kernel<<<L.ntiles * gc * nmod, 512, 0, st>>>(R, U, tiles, L.ntiles, L.Mp, L.Np, K, c);
+    emul_combine_kernel<<<dim3((M + 1023) / 1024, N, gc), 256, 0, st>>>(C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);
+  }
+  return hipSuccess;
+}

@@ -1,0 +1,335 @@
+// Go/no-go probe for the int8 modular emulation of the large f64 Cholesky updates: the sustained rate of a
+// batched int8 SYRK-shaped GEMM on gfx950 at the C2 level shapes, with the mod-p epilogue that writes one byte per output.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/i8_gemm_probe.hip -o tools/i8_gemm_probe && tools/i8_gemm_probe [nmat]
+// One batch item is one (matrix, modulus) pair: operand R[M][K] int8, K-contiguous; output U[N][M] bytes (i contiguous, as the
+// column-major C of the update wants it), U[j][i] = (sum_k R[i][k] R[j][k]) mod p in the symmetric range.  Only 256 x 256 tiles
+// of the lower trapezoid (tile row >= tile column) are computed.  Shapes must be multiples of the tile (M, N % 256, K % 128).
+//   workgroup tile 256 x 256 x 128, 8 waves as 2 (M) x 4 (N), v_mfma_i32_32x32x32_i8 or v_mfma_i32_16x16x64_i8, int32 accumulators;
+//   two LDS stages of 64 KiB filled by global_load_lds_dwordx4 (tile t+1 is in flight while tile t is multiplied);
+//   LDS rows are 128 B; the 16-B chunk index is XORed with (row >> 1) & 7 on the SOURCE address and on the fragment read,
+//   which makes every ds_read_b128 lane group hit 16 distinct 16-B slots of the 256-B bank row.
+// Both operands are fragment-loaded the same way (lane l: row l & 31 or l & 15, 16 consecutive k), so the k order inside an
+// MFMA is the same permutation for A and B whatever the hardware's k map is; the row/column map is checked with exact
+// asymmetric integer data (full check at a small shape, sampled check at every timed shape).
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+
+#define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(2); } } while (0)
+
+constexpr int TILE = 256, BK = 128, NMOD = 16;
+constexpr int STAGE_BYTES = 2 * TILE * BK;  // A tile + B tile
+struct Moduli { int p[NMOD]; };
+static const Moduli kModuli = {{256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 217, 211, 199, 197, 193}};
+
+__device__ __forceinline__ int mod_sym(int x, int p, float rp, int lo) {
+  // |x| <= 2^27: the float quotient is off by less than 0.3, so one correction each way lands in [lo, lo + p - 1]
+  const int q = __float2int_rn((float)x * rp);
+  int r = x - q * p;
+  r += (r < lo) ? p : 0;
+  r -= (r > lo + p - 1) ? p : 0;
+  return r;
+}
+
+__device__ __forceinline__ void glds16(const int8_t* src, int8_t* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+// SHAPE 32: v_mfma_i32_32x32x32_i8 (wave tile 128 x 64 = 4 x 2 accumulators of 16); SHAPE 16: v_mfma_i32_16x16x64_i8 (8 x 4 of 4)
+template <int SHAPE, bool STAMP>
+__global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
+                                                             int M, int N, int K, Moduli mod, unsigned long long* __restrict__ stamps) {
+  __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
+  // blocks b and b + 8 share an XCD: give each XCD a contiguous range of work ids, so that its 32 resident blocks are one supertile
+  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  const int batch = wg / ntiles;
+  const int2 t = tiles[wg - batch * ntiles];
+  const int8_t* Rb = R + (size_t)batch * M * K;
+  const int8_t* srcA[4];
+  const int8_t* srcB[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = wid * 32 + q * 8 + (lane >> 3), chunk = (lane & 7) ^ ((row >> 1) & 7);
+    srcA[q] = Rb + ((size_t)t.x * TILE + row) * K + chunk * 16;
+    srcB[q] = Rb + ((size_t)t.y * TILE + row) * K + chunk * 16;
+  }
+  auto stage = [&](int buf, int k0) {
+    int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) glds16(srcA[q] + k0, base + q * 1024);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) glds16(srcB[q] + k0, base + TILE * BK + q * 1024);
+  };
+  constexpr int MR = SHAPE == 32 ? 4 : 8, NR = SHAPE == 32 ? 2 : 4, KS = SHAPE == 32 ? 4 : 2, NACC = SHAPE == 32 ? 16 : 4;
+  typedef int acc_t __attribute__((ext_vector_type(NACC)));
+  acc_t acc[MR][NR];
+#pragma unroll
+  for (int m = 0; m < MR; ++m)
+#pragma unroll
+    for (int n = 0; n < NR; ++n)
+#pragma unroll
+      for (int e = 0; e < NACC; ++e) acc[m][n][e] = 0;
+  unsigned long long t0 = 0, r0 = 0;
+  if (STAMP) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const int nk = K / BK;
+  const int frow = lane & (SHAPE - 1), fk = lane / SHAPE;  // fragment row and 16-B k-chunk within one MFMA's k range
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk) stage((kt + 1) & 1, (kt + 1) * BK);
+    const int8_t* la = lds + (kt & 1) * STAGE_BYTES;
+    const int8_t* lb = la + TILE * BK;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int chunk = ks * (8 / KS) + fk;
+      v4i a[MR], b[NR];
+#pragma unroll
+      for (int m = 0; m < MR; ++m) {
+        const int row = wr * 128 + m * SHAPE + frow;
+        a[m] = *reinterpret_cast<const v4i*>(la + row * BK + ((chunk ^ ((row >> 1) & 7)) << 4));
+      }
+#pragma unroll
+      for (int n = 0; n < NR; ++n) {
+        const int row = wc * 64 + n * SHAPE + frow;
+        b[n] = *reinterpret_cast<const v4i*>(lb + row * BK + ((chunk ^ ((row >> 1) & 7)) << 4));
+      }
+#pragma unroll
+      for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int n = 0; n < NR; ++n) {
+          if constexpr (SHAPE == 32) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[m], b[n], acc[m][n], 0, 0, 0);
+          else acc[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[m], b[n], acc[m][n], 0, 0, 0);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  if (STAMP) {
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    if (tid == 0) { stamps[2 * (size_t)blockIdx.x] = t1 - t0; stamps[2 * (size_t)blockIdx.x + 1] = r1 - r0; }
+  }
+  // epilogue: reduce mod p, pack the 4 consecutive rows (i) a lane holds per register group into one dword of U[j][i]
+  const int p = mod.p[batch % NMOD], lo = -(p / 2);
+  const float rp = 1.0f / (float)p;
+  int8_t* Ub = U + (size_t)batch * N * M;
+#pragma unroll
+  for (int m = 0; m < MR; ++m)
+#pragma unroll
+    for (int n = 0; n < NR; ++n) {
+      const size_t j = (size_t)t.y * TILE + wc * 64 + n * SHAPE + frow;
+#pragma unroll
+      for (int g = 0; g < NACC / 4; ++g) {
+        // C/D map: 32x32: row = 8 g + 4 (lane >> 5) + e; 16x16: row = 4 (lane >> 4) + e
+        const int i = t.x * TILE + wr * 128 + m * SHAPE + (SHAPE == 32 ? 8 * g + 4 * fk : 4 * fk);
+        unsigned w = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w |= (unsigned)(mod_sym(acc[m][n][4 * g + e], p, rp, lo) & 0xFF) << (8 * e);
+        *reinterpret_cast<unsigned*>(Ub + j * M + i) = w;
+      }
+    }
+}
+
+// bare issue rate: operands in registers, 4 independent accumulators, no memory traffic
+__global__ __launch_bounds__(256) void mfma_i8_bare(int* out, unsigned long long* stamps, int iters) {
+  v16i acc[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[q][e] = 0;
+  unsigned h = (blockIdx.x * 256u + threadIdx.x + 1u) * 2654435761u;
+  v4i a, b;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { h = h * 1664525u + 1013904223u; a[e] = (int)h; h = h * 1664525u + 1013904223u; b[e] = (int)h; }
+  const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[q & 3] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc[q & 3], 0, 0, 0);
+  }
+  const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+  int s = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s += acc[q][e];
+  out[blockIdx.x * 256 + threadIdx.x] = s;
+  if ((threadIdx.x & 63) == 0) {
+    stamps[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 2] = t1 - t0;
+    stamps[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + 1] = r1 - r0;
+  }
+}
+
+__global__ void fill_rand_i8(int8_t* p, size_t n, unsigned seed) {
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  for (; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    unsigned long long z = (i + 1) * 0x9E3779B97F4A7C15ull + seed; z ^= z >> 29; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 32;
+    p[i] = (int8_t)(z & 0xFF);
+  }
+}
+
+// lower-trapezoid tiles in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles share at most 12 operand panels
+static std::vector<int2> tile_list(int M, int N) {
+  std::vector<int2> v;
+  const int tm = M / TILE, tn = N / TILE;
+  for (int I = 0; I < tm; I += 8)
+    for (int J = 0; J < tn; J += 4)
+      for (int i = I; i < std::min(I + 8, tm); ++i)
+        for (int j = J; j < std::min(J + 4, tn); ++j)
+          if (j <= i) v.push_back(make_int2(i, j));
+  return v;
+}
+
+static int mod_sym_host(long long x, int p) {
+  const int lo = -(p / 2);
+  long long r = x % p;
+  if (r < lo) r += p;
+  if (r > lo + p - 1) r -= p;
+  return (int)r;
+}
+
+template <int SHAPE, bool STAMP>
+static void launch(const int8_t* R, int8_t* U, const int2* tiles, int ntiles, int M, int N, int K, int batch, unsigned long long* stamps) {
+  i8_syrk_mod_kernel<SHAPE, STAMP><<<ntiles * batch, 512>>>(R, U, tiles, ntiles, M, N, K, kModuli, stamps);
+}
+
+// exact check of U against a host integer product; every == true checks every computed tile and that nothing else was written
+static long check(const int8_t* dR, const int8_t* dU, int M, int N, int K, int batch, bool every, const char* what) {
+  std::vector<int8_t> hR((size_t)M * K), hU((size_t)N * M);
+  long bad = 0, checked = 0;
+  for (int b = 0; b < batch; b += every ? 1 : 5) {
+    CHECK(hipMemcpy(hR.data(), dR + (size_t)b * M * K, hR.size(), hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(hU.data(), dU + (size_t)b * N * M, hU.size(), hipMemcpyDeviceToHost));
+    const int p = kModuli.p[b % NMOD];
+    unsigned long long z = 12345 + b;
+    const long n = every ? (long)N * M : 4096;
+    for (long s = 0; s < n; ++s) {
+      int i, j;
+      if (every) { j = (int)(s / M); i = (int)(s % M); }
+      else {
+        z = z * 6364136223846793005ull + 1442695040888963407ull; i = (int)((z >> 33) % M);
+        z = z * 6364136223846793005ull + 1442695040888963407ull; j = (int)((z >> 33) % N);
+      }
+      const bool computed = i / TILE >= j / TILE;
+      if (!computed) { if (every && hU[(size_t)j * M + i] != 0x5A) ++bad; continue; }
+      long long d = 0;
+      for (int k = 0; k < K; ++k) d += (long long)hR[(size_t)i * K + k] * hR[(size_t)j * K + k];
+      ++checked;
+      if (hU[(size_t)j * M + i] != (int8_t)mod_sym_host(d, p)) {
+        if (bad < 5) printf("  MISMATCH %s b=%d i=%d j=%d got %d want %d\n", what, b, i, j, hU[(size_t)j * M + i], mod_sym_host(d, p));
+        ++bad;
+      }
+    }
+  }
+  printf("check %-28s M=%5d N=%5d K=%5d: %ld entries compared exactly, %ld wrong\n", what, M, N, K, checked, bad);
+  return bad;
+}
+
+int main(int argc, char** argv) {
+  const int nmat = argc > 1 ? atoi(argv[1]) : 1;
+  const int batch = NMOD * nmat;
+  hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+  long bad = 0;
+
+  {  // 1. bare v_mfma_i32_32x32x32_i8 issue rate and the clock held
+    int* out; unsigned long long* st;
+    for (int blocks : {256, 512}) {
+      const int iters = 200000;
+      CHECK(hipMalloc(&out, blocks * 256 * 4)); CHECK(hipMalloc(&st, blocks * 8 * 8));
+      mfma_i8_bare<<<blocks, 256>>>(out, st, iters / 10);
+      CHECK(hipDeviceSynchronize());
+      hipEventRecord(e0);
+      mfma_i8_bare<<<blocks, 256>>>(out, st, iters);
+      hipEventRecord(e1); CHECK(hipEventSynchronize(e1));
+      float ms; hipEventElapsedTime(&ms, e0, e1);
+      std::vector<unsigned long long> h(blocks * 8);
+      CHECK(hipMemcpy(h.data(), st, blocks * 8 * 8, hipMemcpyDeviceToHost));
+      std::vector<double> clk, cyc;
+      for (int w = 0; w < blocks * 4; ++w) { clk.push_back((double)h[2 * w] / (double)h[2 * w + 1] * 100.0); cyc.push_back((double)h[2 * w] / iters / 8); }
+      std::sort(clk.begin(), clk.end()); std::sort(cyc.begin(), cyc.end());
+      printf("bare v_mfma_i32_32x32x32_i8, %d wave(s)/SIMD: %.3f ms  %.0f TOPS  %.1f wave cycles per MFMA  clock %.0f MHz\n", blocks / 256, ms,
+             blocks * 4.0 * iters * 8 * 65536.0 / ms / 1e9, cyc[cyc.size() / 2], clk[clk.size() / 2]);
+      CHECK(hipFree(out)); CHECK(hipFree(st));
+    }
+    fflush(stdout);
+  }
+
+  {  // 2. full exact check at a small shape: two tile rows, one tile column, three K tiles, every modulus
+    const int M = 512, N = 256, K = 384;
+    int8_t *R, *U; int2* dt;
+    CHECK(hipMalloc(&R, (size_t)NMOD * M * K)); CHECK(hipMalloc(&U, (size_t)NMOD * N * M));
+    fill_rand_i8<<<512, 256>>>(R, (size_t)NMOD * M * K, 7u);
+    std::vector<int2> tl = tile_list(M, N);
+    CHECK(hipMalloc(&dt, tl.size() * sizeof(int2))); CHECK(hipMemcpy(dt, tl.data(), tl.size() * sizeof(int2), hipMemcpyHostToDevice));
+    CHECK(hipMemset(U, 0x5A, (size_t)NMOD * N * M));
+    launch<32, false>(R, U, dt, (int)tl.size(), M, N, K, NMOD, nullptr);
+    CHECK(hipDeviceSynchronize());
+    bad += check(R, U, M, N, K, NMOD, true, "32x32x32 full");
+    CHECK(hipMemset(U, 0x5A, (size_t)NMOD * N * M));
+    launch<16, false>(R, U, dt, (int)tl.size(), M, N, K, NMOD, nullptr);
+    CHECK(hipDeviceSynchronize());
+    bad += check(R, U, M, N, K, NMOD, true, "16x16x64 full");
+    CHECK(hipFree(R)); CHECK(hipFree(U)); CHECK(hipFree(dt));
+    fflush(stdout);
+    if (bad) { printf("operand or output map wrong: not timing\n"); return 1; }
+  }
+
+  // 3. the C2 level shapes
+  struct Shape { int M, N, K; };
+  const Shape shapes[] = {{8192, 8192, 8192}, {12288, 4096, 4096}, {14336, 2048, 2048}, {15360, 1024, 1024}};
+  for (const Shape& s : shapes) {
+    int8_t *R, *U; int2* dt; unsigned long long* st;
+    const size_t rb = (size_t)batch * s.M * s.K, ub = (size_t)batch * s.N * s.M;
+    CHECK(hipMalloc(&R, rb)); CHECK(hipMalloc(&U, ub));
+    fill_rand_i8<<<4096, 256>>>(R, rb, 100u + s.K);
+    CHECK(hipMemset(U, 0x5A, ub));
+    std::vector<int2> tl = tile_list(s.M, s.N);
+    const int nt = (int)tl.size();
+    CHECK(hipMalloc(&dt, tl.size() * sizeof(int2))); CHECK(hipMemcpy(dt, tl.data(), tl.size() * sizeof(int2), hipMemcpyHostToDevice));
+    CHECK(hipMalloc(&st, (size_t)nt * batch * 16));
+    const double outs = (double)s.N * (s.N + 1) / 2 + (double)(s.M - s.N) * s.N;
+    const double useful = 2.0 * s.K * outs * batch, issued = 2.0 * s.K * (double)TILE * TILE * nt * batch;
+    const int reps = (int)std::max(4.0, 0.15 / (issued / 2.0e15));  // about 150 ms per window at 2 POPS
+    std::vector<float> t32, t16;
+    for (int round = 0; round < 3; ++round)
+      for (int v = 0; v < 2; ++v) {
+        auto go = [&]() { if (v == 0) launch<32, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr); else launch<16, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr); };
+        go();
+        hipEventRecord(e0);
+        for (int r = 0; r < reps; ++r) go();
+        hipEventRecord(e1); CHECK(hipEventSynchronize(e1));
+        float ms; hipEventElapsedTime(&ms, e0, e1);
+        (v == 0 ? t32 : t16).push_back(ms / reps);
+      }
+    double clk[2];
+    for (int v = 0; v < 2; ++v) {  // diagnostic build with stamps, after the timed windows (the chip is warm)
+      for (int r = 0; r < 3; ++r) { if (v == 0) launch<32, true>(R, U, dt, nt, s.M, s.N, s.K, batch, st); else launch<16, true>(R, U, dt, nt, s.M, s.N, s.K, batch, st); }
+      CHECK(hipDeviceSynchronize());
+      std::vector<unsigned long long> h((size_t)nt * batch * 2);
+      CHECK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
+      std::vector<double> c;
+      for (size_t w = 0; w < h.size() / 2; ++w) c.push_back((double)h[2 * w] / (double)h[2 * w + 1] * 100.0);
+      std::sort(c.begin(), c.end());
+      clk[v] = c[c.size() / 2];
+    }
+    std::sort(t32.begin(), t32.end()); std::sort(t16.begin(), t16.end());
+    printf("i8 syrk M=%5d N=%5d K=%5d batch=%d (%d tiles, %d reps) | 32x32x32: min %.3f med %.3f ms, %.0f TOPS useful (%.0f issued), clock %.0f MHz"
+           " | 16x16x64: min %.3f med %.3f ms, %.0f TOPS useful (%.0f issued), clock %.0f MHz\n",
+           s.M, s.N, s.K, batch, nt, reps, t32[0], t32[1], useful / t32[0] / 1e9, issued / t32[0] / 1e9, clk[0], t16[0], t16[1], useful / t16[0] / 1e9,
+           issued / t16[0] / 1e9, clk[1]);
+    launch<32, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
+    CHECK(hipDeviceSynchronize());
+    bad += check(R, U, s.M, s.N, s.K, batch, false, "32x32x32 sampled");
+    fflush(stdout);
+    CHECK(hipFree(R)); CHECK(hipFree(U)); CHECK(hipFree(dt)); CHECK(hipFree(st));
+  }
+  printf(bad ? "FAILED: %ld wrong entries\n" : "all checks exact (%ld wrong)\n", bad);
+  return bad ? 1 : 0;
+}
