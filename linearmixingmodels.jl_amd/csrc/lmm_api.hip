@@ -216,6 +216,8 @@ struct DevOut {
 };
 
 inline int rup(int v, int m) { return (v + m - 1) / m * m; }
+// leading dimension for `rows` rows: keeps column starts off the same HBM channel / L2 set
+inline int pad_ld(int rows) { return (rows % 512) == 0 ? rows + 16 : rows; }
 
 // fp32 compute mode (lmm_set_compute_dtype): MATRICES (factor matrices, inverse diagonal blocks, cross-solve blocks) are float
 // buffers; they are still carried as Buf<double> / double* (opaque to the host, which never dereferences them), sized by
@@ -303,8 +305,7 @@ struct Dims {
   Dims(int n_, int nrider) : n(n_) {
     NC = rup(std::max(n, 1), 128);      // whole 128-column panels (round 3: the panel / region kernels work on them; the pad is identity)
     NR = rup(NC + std::max(nrider, 0), 64);
-    ld = NR;
-    if ((ld % 512) == 0) ld += 16;   // keep column starts off the same HBM channel / L2 set
+    ld = pad_ld(NR);
   }
   size_t elems() const { return (size_t)ld * NC; }
 };
@@ -1052,17 +1053,20 @@ void batch_plan(int ms, int* nb_per, int* nstreams_used, double bytes_per_latent
 }
 
 struct Slot {                 // one stream + the factor matrices of the batch it carries
-  std::vector<Buf<double>> A, W;
+  std::vector<Buf<double>> A, W, R;      // R: optional second matrix per latent (the gradient cores' identity riders -> L^-T)
+  Buf<double> part;                      // optional reduction scratch, reused latent after latent in stream order
   hipStream_t st;
 };
 
-void make_slots(std::vector<Slot>& slots, int count, int nb_per, size_t a_elems, int NC) {
+void make_slots(std::vector<Slot>& slots, int count, int nb_per, size_t a_elems, int NC, size_t r_elems = 0, size_t part_elems = 0) {
   slots.resize(count);
   for (int s = 0; s < count; ++s) {
     for (int j = 0; j < nb_per; ++j) {
       slots[s].A.emplace_back(mat_count(a_elems));
       slots[s].W.emplace_back(mat_count((size_t)(NC / 64) * 4096));
+      if (r_elems) slots[s].R.emplace_back(mat_count(r_elems));
     }
+    if (part_elems) slots[s].part = Buf<double>(part_elems);
     slots[s].st = g.streams[s];
   }
 }
@@ -1082,6 +1086,54 @@ void join_slots(int count) {       // main stream waits for every slot stream
     HIPCHK(hipStreamWaitEvent(g.streams[0], g.ev_slot[s], 0));
   }
 }
+
+int check_info(const int* info, size_t count, int latent_begin);
+
+// The host-side fan-out every per-latent loop goes through: the ms latents of a shard in batches of nb_per, batch bi on slot stream
+// bi % nslots, between fork_slots and join_slots.  It also owns the pivot-info words of the shard's factorisations.
+struct FanBatch { int s; hipStream_t st; int k0, nb; };      // slot, its stream, first latent of the batch (shard index), latents in it
+struct FanOut {
+  int ms, mk;                    // latents of the shard; max(ms, 1), the count the per-latent buffers of a possibly empty shard take
+  int nb_per = 1, nslots = 1;
+  int* info = nullptr;           // device: info[k] of latent k (alloc_info; or the caller's own words, which the caller then reads back)
+  FanOut(int ms_, double bytes_per_latent) : ms(ms_), mk(std::max(ms_, 1)) { batch_plan(mk, &nb_per, &nslots, bytes_per_latent); }
+  // the one-slot form: every batch on the main stream, as many latents per batch as one launch takes
+  static FanOut one_slot(int ms_) { FanOut F(ms_); F.nb_per = std::min(F.mk, LMM_MAX_BATCH); return F; }
+  int* alloc_info(int words_per_latent = 1) {      // zeroed on the main stream, ahead of the fork
+    own = Buf<int>((size_t)words_per_latent * mk);
+    HIPCHK(hipMemsetAsync(own.p, 0, own.n * sizeof(int), g.streams[0]));
+    return info = own.p;
+  }
+  template <class Body>
+  void run(Body&& body) {
+    struct Scope {               // the "several batches in flight" state must not outlive the loop, whichever way it is left
+      explicit Scope(int count) { fork_slots(count); }
+      ~Scope() { g_slots_in_flight = 1; g_concurrent_batches = 1; }
+    } scope(nslots);
+    int bi = 0;
+    for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
+      const int s = bi % nslots;
+      body(FanBatch{s, g.streams[s], k0, std::min(nb_per, ms - k0)});
+    }
+    join_slots(nslots);
+  }
+  // After run(): the copy of the info words to the host (main stream), for callers with copies of their own to queue behind it ...
+  void fetch_info() {
+    hinfo.assign(own.n, 0);
+    HIPCHK(hipMemcpyAsync(hinfo.data(), own.p, own.n * sizeof(int), hipMemcpyDeviceToHost, g.streams[0]));
+  }
+  // ... the words on the host once the main stream has drained, and their status
+  const int* host_info() {
+    if (hinfo.empty()) fetch_info();
+    HIPCHK(hipStreamSynchronize(g.streams[0]));
+    return hinfo.data();
+  }
+  int check(int l0) { return check_info(host_info(), hinfo.size(), l0); }
+ private:
+  explicit FanOut(int ms_) : ms(ms_), mk(std::max(ms_, 1)) {}
+  Buf<int> own;
+  std::vector<int> hinfo;
+};
 
 // Pivot-info words of a batch -> status.  A dependency-wait timeout of potrf_region_kernel (LMM_INFO_SYNC_TIMEOUT in ANY word) outranks
 // a PosDefException in an earlier latent: it means the launch was drained with results undefined, which must never be reported as a
@@ -1268,6 +1320,22 @@ void residual_on_device(const double* Y, int n, int p, const double* Ty_all, int
   residual_on_device(Y, n, p, Ty_all, m, Hd.p, partial, out1, st);
 }
 
+// The training matrix of one latent as a factor matrix A (D.NR x D.NC, D.ld): K(x, x) + noise on the diagonal -- the scalar `noise`, or
+// the per-point values noisevec (device, n of them) when given -- the identity on the padding, and nrider rider rows (rider, n apart)
+// less rider_sub.  info_zero: the matrix's pivot-info word, zeroed by the launch.
+GramArgs train_gram_args(const Latent& gp, const double* xd, int d, int n, const Dims& D, double* A, double noise, const double* noisevec,
+                         const double* rider, int nrider, double rider_sub = 0.0, int* info_zero = nullptr) {
+  GramArgs a{};
+  a.A = A; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n;
+  gp.set_kernel(a); a.pad_diag = 1.0;
+  a.diag_add = noisevec ? 0.0 : noise; a.diag_vec = noisevec;
+  a.rider = rider; a.rider_ld = n; a.nrider = nrider; a.rider_sub = rider_sub;
+  a.info_zero = info_zero;
+  return a;
+}
+// bytes of the lower triangle a training Gram launch writes (its ProfScope's work and bytes, per latent)
+inline double train_gram_bytes(int n) { return (double)n * ((double)n + 1.0) / 2.0 * 8.0; }
+
 // Core: per-latent log marginal likelihoods for latents [l0, l1) given the device rider vectors
 // delta ([latent][rhs][n]) and per-latent noise.  Returns lml[latent * nrhs + rhs] (host).  nrhs > 1: several
 // right-hand sides (matrix-Y logpdf) ride one factorisation.  noisevec ([latent of the shard][n], device) replaces the
@@ -1287,17 +1355,16 @@ int latent_lmls(const double* xd, int d, int n, const Latent* lts, const double*
     return LMM_OK;
   }
   Dims D(n, nrhs);
-  int nb_per = 1, nslots = 1;
-  batch_plan(ms, &nb_per, &nslots, mat_bytes((double)D.elems()));
+  FanOut F(ms, mat_bytes((double)D.elems()));
   std::vector<Slot> slots;
-  make_slots(slots, nslots, nb_per, D.elems(), D.NC);
+  make_slots(slots, F.nslots, F.nb_per, D.elems(), D.NC);
   // results: [ms * nrhs doubles | ms pivot-info ints] in ONE buffer.  When the pinned arena is mapped into the device, lml_reduce
   // writes both straight into host memory (pk) and nothing is copied back; else one copy brings both back.  The pivot-info words
   // the kernels work on are zeroed by each latent's Gram launch (no memset).
   const size_t nout = (size_t)ms * nrhs;
   const size_t nbytes = (nout + ((size_t)ms + 1) / 2) * sizeof(double);
   Buf<double> out(nout + ((size_t)ms + 1) / 2);
-  struct { int* p; } info{reinterpret_cast<int*>(out.p + nout)};
+  F.info = reinterpret_cast<int*>(out.p + nout);
   std::vector<double> pageable;
   char* pk = static_cast<char*>(pin_take(nbytes));
   char* pk_dev = pin_dev(pk);
@@ -1305,45 +1372,32 @@ int latent_lmls(const double* xd, int d, int n, const Latent* lts, const double*
   // The kernels that produce the riders go out only now: issued before the plan / slot / pool work above, they finished while the
   // host was still preparing and the device then idled ~5 us ahead of the Gram launch (a twentieth of a C0-sized evaluation)
   if (pre_launch) (*pre_launch)();
-  fork_slots(nslots);
-  int bi = 0;
-  for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
-    Slot& s = slots[bi % nslots];
-    const int nb = std::min(nb_per, ms - k0);
+  F.run([&](const FanBatch& b) {
+    Slot& s = slots[b.s];
     Batch B;
     {
     // the batch's Gram launches share one event pair (back-to-back launches: the event overhead is not charged per launch)
-    const double gb = (double)n * ((double)n + 1.0) / 2.0 * 8.0;
-    ProfScope ps(LMM_PROF_GRAM, nb * gb, s.st, 0, 0, 0, nb * gb, nb);
+    const double gb = train_gram_bytes(n);
+    ProfScope ps(LMM_PROF_GRAM, b.nb * gb, s.st, 0, 0, 0, b.nb * gb, b.nb);
     GramArgs ga[LMM_MAX_BATCH];
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
-      const Latent& gp = lts[l0 + k];
-      GramArgs a{};
-      a.A = s.A[j].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.row_tile0 = 0; a.row_shift = 0; a.full = 0;
-      a.x = xd; a.d = d; a.n = n; gp.set_kernel(a);
-      a.diag_add = noisevec ? 0.0 : noise[l0 + k]; a.pad_diag = 1.0;
-      a.diag_vec = noisevec ? noisevec + (size_t)k * n : nullptr;      // per-point noise of latent k (device, n values)
-      a.rider = delta + (size_t)k * nrhs * n; a.rider_ld = n; a.nrider = nrhs; a.xs = nullptr; a.ns = 0;
-      a.rider_sub = rider_sub ? rider_sub[l0 + k] : 0.0;
-      a.info_zero = info.p + k;
-      ga[j] = a;
-      B.add(s.A[j].p, s.W[j].p, info.p + k);
+    for (int j = 0; j < b.nb; ++j) {
+      const int k = b.k0 + j;
+      // (noisevec: per-point noise of latent k, n device values)
+      ga[j] = train_gram_args(lts[l0 + k], xd, d, n, D, s.A[j].p, noisevec ? 0.0 : noise[l0 + k], noisevec ? noisevec + (size_t)k * n : nullptr,
+                              delta + (size_t)k * nrhs * n, nrhs, rider_sub ? rider_sub[l0 + k] : 0.0, F.info + k);
+      B.add(s.A[j].p, s.W[j].p, F.info + k);
     }
-    gram_batch_g(ga, nb, s.st);       // one launch per run of equal kernel kinds (blockIdx.z = latent)
+    gram_batch_g(ga, b.nb, s.st);       // one launch per run of equal kernel kinds (blockIdx.z = latent)
     }
     potrf_batch(B, D.ld, D.NR, D.NC, n, s.st, D.NC + nrhs);      // the rider rows NC + nrhs .. NR - 1 are zero padding
-    if (pk_dev) launch_lml_reduce(B.A, nb, D.ld, n, D.NC, nrhs, reinterpret_cast<double*>(pk_dev) + (size_t)k0 * nrhs, s.st, &B.info,
-                                  reinterpret_cast<int*>(pk_dev + nout * sizeof(double)) + k0);
-    else launch_lml_reduce(B.A, nb, D.ld, n, D.NC, nrhs, out.p + (size_t)k0 * nrhs, s.st);
-  }
-  join_slots(nslots);
-  std::vector<int> hinfo(ms);
+    if (pk_dev) launch_lml_reduce(B.A, b.nb, D.ld, n, D.NC, nrhs, reinterpret_cast<double*>(pk_dev) + (size_t)b.k0 * nrhs, s.st, &B.info,
+                                  reinterpret_cast<int*>(pk_dev + nout * sizeof(double)) + b.k0);
+    else launch_lml_reduce(B.A, b.nb, D.ld, n, D.NC, nrhs, out.p + (size_t)b.k0 * nrhs, s.st);
+  });
   if (!pk_dev) HIPCHK(hipMemcpyAsync(pk, out.p, nbytes, hipMemcpyDeviceToHost, g.streams[0]));
   HIPCHK(hipStreamSynchronize(g.streams[0]));
   std::memcpy(lml.data(), pk, nout * sizeof(double));
-  std::memcpy(hinfo.data(), pk + nout * sizeof(double), (size_t)ms * sizeof(int));
-  return check_info(hinfo, l0);
+  return check_info(reinterpret_cast<const int*>(pk + nout * sizeof(double)), (size_t)ms, l0);
 }
 
 const lmm_jitters_t kDefaultJit = {1e-9, 1e-12, 1e-18};
@@ -1916,6 +1970,124 @@ void oilmm_regulariser_grad(const double* U, const double* S, int p, int m, cons
   }
 }
 
+// What oilmm_grad_core and oilmm_grad_missing_core share, per latent of the shard: the training matrix with the residual as its rider,
+// its factor, alpha = Kt^-1 delta, Kt^-1 = L^-T L^-1 (triangular solve of identity riders + an upper-triangular SYRK, over the factor's
+// lower triangle) and one kernel-gradient reduction per term; then the read-back of the reductions and the host formulas of the
+// latent's own (variance, lengthscale, mean) gradients.  What a caller does with the reductions beyond that stays with the caller.
+struct KernelGradPass {
+  const Latent* lts;
+  const int l0, ms, n, d, ard_d;
+  const Dims D;
+  FanOut F;
+  std::vector<Slot> slots;
+  const std::vector<int> toff;     // one reduction per term of every latent of the shard
+  const int nterm;
+  Buf<double> alpha, lmld, red, ardred;      // ardred: per-dimension sums of the ARD terms (d/d l_k)
+  std::vector<double> lml, hred, hard;       // their host copies (read_back)
+
+  KernelGradPass(const LatentSet* ls, int l0_, int l1, int n_, int d_)
+      : lts(ls->lat.data()), l0(l0_), ms(l1 - l0_), n(n_), d(d_), ard_d(ls->ard_grad_d()), D(n_, 1),
+        F(ms, 2.0 * mat_bytes((double)D.elems())),     // factor + inverse-factor matrices
+        toff(ls->term_offsets(l0_, l1)), nterm(toff[ms]),
+        alpha((size_t)D.NC * F.mk), lmld(F.mk), red((size_t)LMM_NGRAD * std::max(nterm, 1)), ardred((size_t)d * std::max(nterm, 1)) {
+    make_slots(slots, F.nslots, F.nb_per, D.elems(), D.NC, (size_t)D.ld * D.NC, (size_t)grad_partials(n, ard_d));
+    F.alloc_info();
+    HIPCHK(hipMemsetAsync(alpha.p, 0, (size_t)D.NC * F.mk * sizeof(double), g.streams[0]));
+  }
+
+  // delta: the residuals ([latent of the shard][n], device); the noise: noise[latent] (host), or per point noisevec ([latent of the
+  // shard][n], device) when given; nsplit: where the contraction kernel splits its trace / alpha.alpha sums.  The hooks run on the
+  // batch's stream with Kt^-1 and alpha of latent k (shard index): per_term after the reduction of each of its terms (gd),
+  // per_latent after the last.
+  template <class PerTerm, class PerLatent>
+  void launch(const double* xd, const double* delta, const double* noise, const double* noisevec, int nsplit, PerTerm&& per_term,
+              PerLatent&& per_latent) {
+    F.run([&](const FanBatch& b) {
+      Slot& s = slots[b.s];
+      hipStream_t st = b.st;
+      const int nb = b.nb;
+      Batch B;
+      BatchPtr Rb{}, alb{};
+      GramArgs ga[LMM_MAX_BATCH];
+      for (int j = 0; j < nb; ++j) {
+        const int k = b.k0 + j;
+        ga[j] = train_gram_args(lts[l0 + k], xd, d, n, D, s.A[j].p, noisevec ? 0.0 : noise[l0 + k],
+                                noisevec ? noisevec + (size_t)k * n : nullptr, delta + (size_t)k * n, 1);
+        B.add(s.A[j].p, s.W[j].p, F.info + k);
+        Rb.p[j] = s.R[j].p; alb.p[j] = alpha.p + (size_t)k * D.NC;
+      }
+      gram_batch_g(ga, nb, st);
+      potrf_batch(B, D.ld, D.NR, D.NC, n, st, D.NC + 1);        // one rider row (delta); rows NC + 1 .. NR - 1 are zero padding
+      launch_lml_reduce(B.A, nb, D.ld, n, D.NC, 1, lmld.p + b.k0, st);
+      for (int j = 0; j < nb; ++j) {
+        launch_extract_row(s.A[j].p, D.ld, D.NC, n, alb.p[j], st);
+        launch_set_identity(s.R[j].p, D.ld, D.NC, st);
+      }
+      launch_backsolve(B.A, D.ld, B.W, D.NC / 64, alb, nb, st);
+      trsm_rec(Rb, D.ld, D.NC, B.A, D.ld, B.W, nb, 0, D.NC, st, true);        // R = L^-T (upper triangular), whole batch
+      launch_syrk_upper_set(B.A, D.ld, Rb, D.ld, D.NC, nb, st);                // lower(A) = L^-T L^-1 = Kt^-1
+      for (int j = 0; j < nb; ++j) {
+        const int k = b.k0 + j;
+        // one reduction per term (the trace and alpha.delta partials, which do not depend on the kernel, are read from term 0's)
+        for (int c = 0; c < lts[l0 + k].nt(); ++c) {
+          const LatentDev& gd = lts[l0 + k].terms[c].gd;
+          const size_t t = (size_t)toff[k] + c;
+          launch_grad_reduce(s.A[j].p, D.ld, n, nsplit, alb.p[j], delta + (size_t)k * n, xd, d, gd, s.part.p, red.p + LMM_NGRAD * t, st,
+                             ardred.p + d * t);
+          per_term(b, k, s.A[j].p, alb.p[j], gd);
+        }
+        per_latent(b, k, s.A[j].p, alb.p[j]);
+      }
+    });
+  }
+
+  void read_back() {       // queued on the main stream after the join: lml, the reductions and the ARD sums
+    hipStream_t st0 = g.streams[0];
+    lml.assign(F.mk, 0.0); hred.assign((size_t)LMM_NGRAD * std::max(nterm, 1), 0.0);
+    HIPCHK(hipMemcpyAsync(lml.data(), lmld.p, F.mk * sizeof(double), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+    hard.assign(ard_d ? (size_t)d * std::max(nterm, 1) : 0, 0.0);
+    if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  }
+
+  // ---- host, once the main stream has drained ----
+  void init_outputs(int m, std::vector<lmm_gp_grad_t>& ggps, std::vector<double>& trec) const {
+    ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
+    trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
+  }
+  // the sums of latent k's first term: [1] tr Kt^-1 and [2] alpha.alpha over the rows below nsplit ([5], [6]: from nsplit on),
+  // [3] alpha.delta, [4] sum(alpha)
+  const double* sums(int k) const { return &hred[(size_t)LMM_NGRAD * toff[k]]; }
+  // ggps[l] and the term records of latent k from D_aa = alpha' D alpha and D_tr = tr(Kt^-1 D), D its diagonal noise, and
+  // alpha.alpha, tr Kt^-1 over all rows
+  void finish(int k, double D_aa, double D_tr, double aa, double tr, std::vector<lmm_gp_grad_t>& ggps, std::vector<double>& trec) const {
+    const int l = l0 + k;
+    const double* r = sums(k);
+    // 1/2 tr((aa' - Kt^-1) K) / v  with K = Kt - D:  a'delta - a'Da - (n - tr(Kt^-1 D))     (a sum latent's K is linear in v0 too)
+    ggps[l].variance = 0.5 * ((r[3] - D_aa) - ((double)n - D_tr)) / lts[l].variance;
+    // sum_{i>j} (a_i a_j - Kinv_ij) dK_ij/dl (x2 / 2), through the terms
+    ggps[l].lengthscale = grad_finish(lts[l], d, r, hard.empty() ? nullptr : &hard[(size_t)d * toff[k]], aa, tr,
+                                      &trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)]);
+    ggps[l].mean = r[4];
+  }
+};
+
+// Sum of the per-slot accumulators into out, in slot order (so the result does not depend on stream timing), skipping slots that
+// carried no latent; on the main stream after the join.  Returns false when no slot was used (out untouched).  axpby: the caller's
+// add is vec_axpby_kernel, else vec_lin_kernel -- out + 1.0 * acc and 1.0 * out + 1.0 * acc round alike, but each caller keeps its launch.
+bool sum_slots(double* out, const std::vector<Buf<double>>& acc, const std::vector<char>& used, size_t count, hipStream_t st0,
+               bool axpby = false) {
+  bool first = true;
+  for (size_t s = 0; s < acc.size(); ++s) {
+    if (!used[s]) continue;
+    if (first) HIPCHK(hipMemcpyAsync(out, acc[s].p, count * sizeof(double), hipMemcpyDeviceToDevice, st0));
+    else if (axpby) launch_vec_axpby(out, 1.0, acc[s].p, 1.0, count, out, st0);
+    else launch_vec_lin(out, acc[s].p, 1.0, (int)count, out, st0);
+    first = false;
+  }
+  return !first;
+}
+
 // Value and gradient of the OILMM logpdf (reference src/oilmm.jl:79-113 differentiated) over N points in NB.nblk consecutive
 // blocks, block b carrying observation noise NB.s2[b] (one block: the plain logpdf; several: the joint density of the
 // conditioning batches and the test points that the predictive logpdf is the difference of).  Per latent: factor, alpha = Kt^-1 delta, Kt^-1 = L^-T L^-1
@@ -1927,9 +2099,9 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
                     const LatentSet* ls, int l0, int l1, int with_regulariser, OilmmGrad& G, double* gy_dev,
                     double* gx_dev = nullptr) {
   hipStream_t st0 = g.streams[0];
-  const int m = (int)ls->lat.size(), ard_d = ls->ard_grad_d();
+  const int m = (int)ls->lat.size();
   const Latent* lts = ls->lat.data();
-  const int ms = l1 - l0, n = N, nblk = NB.nblk;
+  const int ms = l1 - l0, mk = std::max(ms, 1), n = N, nblk = NB.nblk;      // mk: what the per-latent buffers of a possibly empty shard take
   const bool two = nblk > 1;
   const int nsplit = nblk == 2 ? NB.off[1] : N;        // the contraction kernel splits its trace / alpha.alpha sums once
   std::vector<double> T, STa, H;
@@ -1942,140 +2114,69 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   Uploaded meansd(means, st0);
   // projections: Ty (all m, for dS), delta for the shard
-  Buf<double> Ty((size_t)n * m), delta((size_t)n * std::max(ms, 1));
+  Buf<double> Ty((size_t)n * m), delta((size_t)n * mk);
   project_on_device(yd, n, p, Td.buf, m, 0, m, nullptr, Ty.p, st0);
   if (ms > 0) project_on_device(yd, n, p, Td.buf, m, l0, ms, meansd.buf.p + l0, delta.p, st0);
-  Buf<double> nv(two ? (size_t)n * std::max(ms, 1) : 1);          // per-point projected noise of the shard's latents
+  Buf<double> nv(two ? (size_t)n * mk : 1);          // per-point projected noise of the shard's latents
   if (two)
     for (int k = 0; k < ms; ++k)
       for (int b = 0; b < nblk; ++b) launch_fill(nv.p + (size_t)k * n + NB.off[b], NB.count(b), ST[b][l0 + k], st0);
-  Dims D(n, 1);
-  int nb_per = 1, nslots = 1;
-  batch_plan(std::max(ms, 1), &nb_per, &nslots, 2.0 * mat_bytes((double)D.elems()));     // factor + inverse-factor matrices
-  std::vector<std::vector<Buf<double>>> Am(nslots), Wm(nslots), Rm(nslots);
-  std::vector<Buf<double>> part;
-  for (int s = 0; s < nslots; ++s) {
-    for (int j = 0; j < nb_per; ++j) {
-      Am[s].emplace_back(mat_count(D.elems())); Wm[s].emplace_back(mat_count((size_t)(D.NC / 64) * 4096));
-      Rm[s].emplace_back(mat_count((size_t)D.ld * D.NC));
-    }
-    part.emplace_back((size_t)grad_partials(n, ard_d));
-  }
-  const int NGR = LMM_NGRAD;
-  const std::vector<int> toff = ls->term_offsets(l0, l1);     // one reduction per term of every latent of the shard
-  const int nterm = toff[ms];
-  Buf<double> alpha((size_t)D.NC * std::max(ms, 1)), lmld(std::max(ms, 1)), red((size_t)NGR * std::max(nterm, 1));
-  Buf<double> ardred((size_t)d * std::max(nterm, 1));          // per-dimension sums of the ARD terms (d/d l_k)
+  KernelGradPass K(ls, l0, l1, n, d);
+  const Dims& D = K.D;
+  const int nslots = K.F.nslots;
+  Buf<double>& alpha = K.alpha;
   // more than two noise blocks: [tr Kinv, alpha.alpha] per (latent, block) from the small per-range kernels
-  Buf<double> blksum(nblk > 2 ? (size_t)2 * nblk * std::max(ms, 1) : 1);
-  Buf<int> info(std::max(ms, 1));
-  HIPCHK(hipMemsetAsync(info.p, 0, std::max(ms, 1) * sizeof(int), st0));
-  HIPCHK(hipMemsetAsync(alpha.p, 0, (size_t)D.NC * std::max(ms, 1) * sizeof(double), st0));
+  Buf<double> blksum(nblk > 2 ? (size_t)2 * nblk * mk : 1);
   // input gradient: each slot sums its latents (in order) into its own d x N buffer; the slots are summed in slot order after the join
   std::vector<Buf<double>> gxpart, gxacc;
   std::vector<char> gx_used(nslots, 0);
   if (gx_dev)
     for (int s = 0; s < nslots; ++s) { gxpart.emplace_back(grad_x_partial_elems(n, d)); gxacc.emplace_back((size_t)d * n); }
-  fork_slots(nslots);
-  int bi = 0;
-  for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
-    const int s = bi % nslots, nb = std::min(nb_per, ms - k0);
-    hipStream_t st = g.streams[s];
-    Batch B;
-    BatchPtr Rb{}, alb{};
-    GramArgs ga[LMM_MAX_BATCH];
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
-      const Latent& gp = lts[l0 + k];
-      GramArgs a{};
-      a.A = Am[s][j].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n;
-      gp.set_kernel(a); a.pad_diag = 1.0;
-      a.diag_add = two ? 0.0 : STa[l0 + k];
-      a.diag_vec = two ? nv.p + (size_t)k * n : nullptr;
-      a.rider = delta.p + (size_t)k * n; a.rider_ld = n; a.nrider = 1;
-      ga[j] = a;
-      B.add(Am[s][j].p, Wm[s][j].p, info.p + k);
-      Rb.p[j] = Rm[s][j].p; alb.p[j] = alpha.p + (size_t)k * D.NC;
-    }
-    gram_batch_g(ga, nb, st);
-    potrf_batch(B, D.ld, D.NR, D.NC, n, st, D.NC + 1);        // one rider row (delta); rows NC + 1 .. NR - 1 are zero padding
-    launch_lml_reduce(B.A, nb, D.ld, n, D.NC, 1, lmld.p + k0, st);
-    for (int j = 0; j < nb; ++j) {
-      launch_extract_row(Am[s][j].p, D.ld, D.NC, n, alb.p[j], st);
-      launch_set_identity(Rm[s][j].p, D.ld, D.NC, st);
-    }
-    launch_backsolve(B.A, D.ld, B.W, D.NC / 64, alb, nb, st);
-    trsm_rec(Rb, D.ld, D.NC, B.A, D.ld, B.W, nb, 0, D.NC, st, true);        // R = L^-T (upper triangular), whole batch
-    launch_syrk_upper_set(B.A, D.ld, Rb, D.ld, D.NC, nb, st);                // lower(A) = L^-T L^-1 = Kt^-1
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
-      // one reduction per term (the trace and alpha.delta partials, which do not depend on the kernel, are read from term 0's)
-      for (int c = 0; c < lts[l0 + k].nt(); ++c) {
-        const LatentDev& gd = lts[l0 + k].terms[c].gd;
-        const size_t t = (size_t)toff[k] + c;
-        launch_grad_reduce(Am[s][j].p, D.ld, n, nsplit, alb.p[j], delta.p + (size_t)k * n, xd, d, gd, part[s].p, red.p + NGR * t, st,
-                           ardred.p + d * t);
-        if (gx_dev) {
-          launch_grad_x(Am[s][j].p, D.ld, n, alb.p[j], xd, d, gd, gxpart[s].p, gxacc[s].p, gx_used[s] != 0, st);
-          gx_used[s] = 1;
-        }
-      }
-      if (nblk > 2)
-        for (int b = 0; b < nblk; ++b) {
-          double* o = blksum.p + ((size_t)k * nblk + b) * 2;
-          launch_block_trace(Am[s][j].p, D.ld, n, 1, NB.off[b], NB.off[b + 1], o, st);
-          launch_atb(alb.p[j] + NB.off[b], n, alb.p[j] + NB.off[b], n, NB.count(b), 1, 1, o + 1, st);
-        }
-    }
-  }
-  join_slots(nslots);
-  if (gx_dev) {
-    bool first = true;
-    for (int s = 0; s < nslots; ++s) {
-      if (!gx_used[s]) continue;
-      if (first) HIPCHK(hipMemcpyAsync(gx_dev, gxacc[s].p, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, st0));
-      else launch_vec_lin(gx_dev, gxacc[s].p, 1.0, d * n, gx_dev, st0);
-      first = false;
-    }
-    if (first) HIPCHK(hipMemsetAsync(gx_dev, 0, (size_t)d * n * sizeof(double), st0));      // empty shard
-  }
-  std::vector<double> lml(std::max(ms, 1), 0.0), hred((size_t)NGR * std::max(nterm, 1), 0.0);
-  std::vector<int> hinfo(std::max(ms, 1), 0);
-  std::vector<double> hblk(nblk > 2 ? (size_t)2 * nblk * std::max(ms, 1) : 0, 0.0);
-  HIPCHK(hipMemcpyAsync(lml.data(), lmld.p, std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  std::vector<double> hard(ard_d ? (size_t)d * std::max(nterm, 1) : 0, 0.0);
-  if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  K.launch(xd, delta.p, two ? nullptr : STa.data(), two ? nv.p : nullptr, nsplit,
+           [&](const FanBatch& b, int, const double* Kinv, const double* al, const LatentDev& gd) {
+             if (!gx_dev) return;
+             launch_grad_x(Kinv, D.ld, n, al, xd, d, gd, gxpart[b.s].p, gxacc[b.s].p, gx_used[b.s] != 0, b.st);
+             gx_used[b.s] = 1;
+           },
+           [&](const FanBatch& b, int k, const double* Kinv, const double* al) {
+             if (nblk > 2)
+               for (int blk = 0; blk < nblk; ++blk) {
+                 double* o = blksum.p + ((size_t)k * nblk + blk) * 2;
+                 launch_block_trace(Kinv, D.ld, n, 1, NB.off[blk], NB.off[blk + 1], o, b.st);
+                 launch_atb(al + NB.off[blk], n, al + NB.off[blk], n, NB.count(blk), 1, 1, o + 1, b.st);
+               }
+           });
+  if (gx_dev && !sum_slots(gx_dev, gxacc, gx_used, (size_t)d * n, st0))
+    HIPCHK(hipMemsetAsync(gx_dev, 0, (size_t)d * n * sizeof(double), st0));      // empty shard
+  K.read_back();
+  std::vector<double> hblk(nblk > 2 ? (size_t)2 * nblk * mk : 0, 0.0);
   if (!hblk.empty() && ms > 0) HIPCHK(hipMemcpyAsync(hblk.data(), blksum.p, hblk.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, st0));
+  K.F.fetch_info();
   // small dense products needed by the chain rule: YA = Y' alpha (p x ms), aTy = alpha_l . (T y)_l, M2 = Y Y' (p x p) per noise block
   const size_t pp = (size_t)p * p;
-  Buf<double> YAd((size_t)p * std::max(ms, 1)), aTyd((size_t)std::max(ms, 1) * m), M2d(pp * nblk);
+  Buf<double> YAd((size_t)p * mk), aTyd((size_t)mk * m), M2d(pp * nblk);
   if (ms > 0) {
     launch_atb(yd, n, alpha.p, D.NC, n, p, ms, YAd.p, st0);
     launch_atb(alpha.p, D.NC, Ty.p, n, n, ms, m, aTyd.p, st0);       // [k, l]; only l = l0 + k is used
   }
-  std::vector<double> YA((size_t)p * std::max(ms, 1), 0.0), aTy((size_t)std::max(ms, 1) * m, 0.0), M2all(pp * nblk, 0.0);
+  std::vector<double> YA((size_t)p * mk, 0.0), aTy((size_t)mk * m, 0.0), M2all(pp * nblk, 0.0);
   if (with_regulariser) {
     for (int b = 0; b < nblk; ++b) launch_atb(yd + NB.off[b], n, yd + NB.off[b], n, NB.count(b), p, p, M2d.p + pp * b, st0);
     HIPCHK(hipMemcpyAsync(M2all.data(), M2d.p, M2all.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   }
   HIPCHK(hipMemcpyAsync(YA.data(), YAd.p, YA.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(aTy.data(), aTyd.p, aTy.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  if (int rc = check_info(hinfo, l0)) return rc;
+  if (int rc = K.F.check(l0)) return rc;
 
   // ---- host chain rule ----
   double total = 0.0;
   G.gs2.assign(nblk, 0.0);
   G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
-  G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
-  G.trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
+  K.init_outputs(m, G.ggps, G.trec);
   for (int k = 0; k < ms; ++k) {
     const int l = l0 + k;
-    total += lml[k];
-    const double* r = &hred[(size_t)NGR * toff[k]];
-    const double ad = r[3], sa = r[4], v = lts[l].variance;
+    total += K.lml[k];
+    const double* r = K.sums(k);
     double aa_all = 0.0, tr_all = 0.0;
     double D_aa = 0.0, D_tr = 0.0, g_s2 = 0.0;       // a'Da, tr(Kt^-1 D) with D the projected noise; sum_b s2[b] dlml/dnoise_b
     for (int b = 0; b < nblk; ++b) {
@@ -2088,12 +2189,7 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
       G.gs2[b] += gb / S[l];
       g_s2 += gb * NB.s2[b];
     }
-    // 1/2 tr((aa' - Kt^-1) K) / v  with K = Kt - D:  a'delta - a'Da - (n - tr(Kt^-1 D))
-    G.ggps[l].variance = 0.5 * ((ad - D_aa) - ((double)n - D_tr)) / v;      // (a sum latent's K is linear in v0 too)
-    // sum_{i>j} (a_i a_j - Kinv_ij) dK_ij/dl (x2 / 2), through the terms
-    G.ggps[l].lengthscale = grad_finish(lts[l], d, r, hard.empty() ? nullptr : &hard[(size_t)d * toff[k]], aa_all, tr_all,
-                                        &G.trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)]);
-    G.ggps[l].mean = sa;
+    K.finish(k, D_aa, D_tr, aa_all, tr_all, G.ggps, G.trec);
     G.gS[l] += -g_s2 / (S[l] * S[l]) + 0.5 * aTy[k + (size_t)l * ms] / S[l];
     for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] += -YA[o + (size_t)k * p] / std::sqrt(S[l]);
   }
@@ -2102,12 +2198,12 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   G.value = total;
   if (gy_dev) {
     // dL/dY[o, i] = - sum_l T[l, o] alpha_l[i]  - (P'P Y)[o, i] / sigma2(i)
-    std::vector<double> negTt((size_t)p * std::max(ms, 1), 0.0);
+    std::vector<double> negTt((size_t)p * mk, 0.0);
     for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) negTt[o + (size_t)k * p] = -T[(l0 + k) + (size_t)o * m];
     Uploaded nT(negTt, st0);
     Buf<double> ga((size_t)n * p);
     // mix reads lat[l*ns + s] with ns = n: alpha is stored with stride NC -> compact copy first
-    Buf<double> ac((size_t)n * std::max(ms, 1));
+    Buf<double> ac((size_t)n * mk);
     for (int k = 0; k < ms; ++k) HIPCHK(hipMemcpyAsync(ac.p + (size_t)k * n, alpha.p + (size_t)k * D.NC, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
     launch_mix(ac.p, n, ms, nT.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, with_regulariser ? ga.p : gy_dev, st0);
     if (with_regulariser) {
@@ -3004,7 +3100,7 @@ static int posterior_create_common(const double* xd, int d, int n, std::shared_p
                                    int l0, int l1, const double* delta, lmm_post_t** out, const double* noisevec = nullptr) {
   const int m = (int)ls->lat.size();
   const Latent* lts = ls->lat.data();
-  const int ms = l1 - l0;
+  const int ms = l1 - l0, mk = std::max(ms, 1);
   lmm_post* P = new lmm_post();
   try {
     Dims D(n, 1);
@@ -3013,60 +3109,46 @@ static int posterior_create_common(const double* xd, int d, int n, std::shared_p
     P->ls = std::move(ls);
     P->x = Buf<double>((size_t)d * n);
     HIPCHK(hipMemcpyAsync(P->x.p, xd, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, g.streams[0]));
-    Buf<int> info(std::max(ms, 1));
-    HIPCHK(hipMemsetAsync(info.p, 0, std::max(ms, 1) * sizeof(int), g.streams[0]));
-    int nb_per = 1, nslots = 1;
-    batch_plan(std::max(ms, 1), &nb_per, &nslots, mat_bytes((double)D.elems()));
+    FanOut F(ms, mat_bytes((double)D.elems()));
+    int* info = F.alloc_info();
     for (int k = 0; k < ms; ++k) {
       P->L.emplace_back(mat_count((size_t)D.elems()));
       P->W.emplace_back(mat_count((size_t)(D.NC / 64) * 4096));
       P->alpha.emplace_back((size_t)D.NC);
       P->z.emplace_back((size_t)D.NC);
     }
-    P->delta_all = Buf<double>((size_t)n * std::max(ms, 1));
+    P->delta_all = Buf<double>((size_t)n * mk);
     if (ms > 0) HIPCHK(hipMemcpyAsync(P->delta_all.p, delta, (size_t)n * ms * sizeof(double), hipMemcpyDeviceToDevice, g.streams[0]));
     if (noisevec) {
-      P->noise_all = Buf<double>((size_t)n * std::max(ms, 1));
+      P->noise_all = Buf<double>((size_t)n * mk);
       if (ms > 0) HIPCHK(hipMemcpyAsync(P->noise_all.p, noisevec, (size_t)n * ms * sizeof(double), hipMemcpyDeviceToDevice, g.streams[0]));
     } else {
       P->noise_scalar.assign(noise + l0, noise + l1);
     }
-    fork_slots(nslots);
-    int bi = 0;
-    for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
-      hipStream_t st = g.streams[bi % nslots];
-      const int nb = std::min(nb_per, ms - k0);
+    F.run([&](const FanBatch& b) {
+      hipStream_t st = b.st;
+      const int nb = b.nb;
       Batch B;
       GramArgs ga[LMM_MAX_BATCH];
       for (int j = 0; j < nb; ++j) {
-        const int k = k0 + j;
-        const Latent& gp = lts[l0 + k];
-        GramArgs a{};
-        a.A = P->L[k].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = P->x.p; a.d = d; a.n = n;
-        gp.set_kernel(a); a.pad_diag = 1.0;
-        a.diag_add = noisevec ? 0.0 : noise[l0 + k];
-        a.diag_vec = noisevec ? P->noise_all.p + (size_t)k * n : nullptr;
-        a.rider = delta + (size_t)k * n; a.rider_ld = n; a.nrider = 1;
-        ga[j] = a;
-        B.add(P->L[k].p, P->W[k].p, info.p + k);
+        const int k = b.k0 + j;
+        ga[j] = train_gram_args(lts[l0 + k], P->x.p, d, n, D, P->L[k].p, noisevec ? 0.0 : noise[l0 + k],
+                                noisevec ? P->noise_all.p + (size_t)k * n : nullptr, delta + (size_t)k * n, 1);
+        B.add(P->L[k].p, P->W[k].p, info + k);
       }
       {
-        const double gb = (double)n * ((double)n + 1.0) / 2.0 * 8.0;
+        const double gb = train_gram_bytes(n);
         ProfScope ps(LMM_PROF_GRAM, nb * gb, st, 0, 0, 0, nb * gb, nb);
         gram_batch_g(ga, nb, st);
       }
       potrf_batch(B, D.ld, D.NR, D.NC, n, st, D.NC + 1);        // one rider row (delta); rows NC + 1 .. NR - 1 are zero padding
       // alpha = L^-T (L^-1 delta): the rider row is z = L^-1 delta (kept as P->z, zero-padded to NC)
       BatchPtr ab{}, zb{};
-      for (int j = 0; j < nb; ++j) { ab.p[j] = P->alpha[k0 + j].p; zb.p[j] = P->z[k0 + j].p; }
+      for (int j = 0; j < nb; ++j) { ab.p[j] = P->alpha[b.k0 + j].p; zb.p[j] = P->z[b.k0 + j].p; }
       launch_extract_rows(B.A, nb, D.ld, D.NC, n, D.NC, ab, zb, st);
       launch_backsolve(B.A, D.ld, B.W, D.NC / 64, ab, nb, st);
-    }
-    join_slots(nslots);
-    std::vector<int> hinfo(std::max(ms, 1), 0);
-    HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, g.streams[0]));
-    HIPCHK(hipStreamSynchronize(g.streams[0]));
-    if (int rc = check_info(hinfo, l0)) { delete P; return rc; }
+    });
+    if (int rc = F.check(l0)) { delete P; return rc; }
   } catch (int code) { drain_after_error(); delete P; return code; }
   *out = P;
   return LMM_OK;
@@ -3332,95 +3414,28 @@ static int oilmm_grad_missing_core(const double* xd, int d, int n, int p, double
                                    int with_regulariser, const MissingFront& F, double* value, double* gs2_out,
                                    std::vector<lmm_gp_grad_t>& ggps, std::vector<double>& trec, double* gy_dev) {
   hipStream_t st0 = g.streams[0];
-  const int m = (int)ls->lat.size(), ard_d = ls->ard_grad_d(), ms = l1 - l0;
-  const Latent* lts = ls->lat.data();
-  Dims D(n, 1);
-  int nb_per = 1, nslots = 1;
-  batch_plan(std::max(ms, 1), &nb_per, &nslots, 2.0 * mat_bytes((double)D.elems()));
-  std::vector<std::vector<Buf<double>>> Am(nslots), Wm(nslots), Rm(nslots);
-  std::vector<Buf<double>> part;
-  for (int s = 0; s < nslots; ++s) {
-    for (int j = 0; j < nb_per; ++j) {
-      Am[s].emplace_back(mat_count(D.elems())); Wm[s].emplace_back(mat_count((size_t)(D.NC / 64) * 4096));
-      Rm[s].emplace_back(mat_count((size_t)D.ld * D.NC));
-    }
-    part.emplace_back((size_t)grad_partials(n, ard_d));
-  }
-  const int NGR = LMM_NGRAD;
-  const std::vector<int> toff = ls->term_offsets(l0, l1);
-  const int nterm = toff[ms];
-  Buf<double> alpha((size_t)D.NC * std::max(ms, 1)), lmld(std::max(ms, 1)), red((size_t)NGR * std::max(nterm, 1));
-  Buf<double> ardred((size_t)d * std::max(nterm, 1)), wd(2 * (size_t)std::max(ms, 1));
-  Buf<int> info(std::max(ms, 1));
-  HIPCHK(hipMemsetAsync(info.p, 0, std::max(ms, 1) * sizeof(int), st0));
-  HIPCHK(hipMemsetAsync(alpha.p, 0, (size_t)D.NC * std::max(ms, 1) * sizeof(double), st0));
-  fork_slots(nslots);
-  int bi = 0;
-  for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
-    const int s = bi % nslots, nb = std::min(nb_per, ms - k0);
-    hipStream_t st = g.streams[s];
-    Batch B;
-    BatchPtr Rb{}, alb{};
-    GramArgs ga[LMM_MAX_BATCH];
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
-      GramArgs a{};
-      a.A = Am[s][j].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n;
-      lts[l0 + k].set_kernel(a); a.pad_diag = 1.0;
-      a.diag_add = 0.0; a.diag_vec = F.nv.p + (size_t)k * n;
-      a.rider = F.z.p + (size_t)k * n; a.rider_ld = n; a.nrider = 1;
-      ga[j] = a;
-      B.add(Am[s][j].p, Wm[s][j].p, info.p + k);
-      Rb.p[j] = Rm[s][j].p; alb.p[j] = alpha.p + (size_t)k * D.NC;
-    }
-    gram_batch_g(ga, nb, st);
-    potrf_batch(B, D.ld, D.NR, D.NC, n, st, D.NC + 1);
-    launch_lml_reduce(B.A, nb, D.ld, n, D.NC, 1, lmld.p + k0, st);
-    for (int j = 0; j < nb; ++j) {
-      launch_extract_row(Am[s][j].p, D.ld, D.NC, n, alb.p[j], st);
-      launch_set_identity(Rm[s][j].p, D.ld, D.NC, st);
-    }
-    launch_backsolve(B.A, D.ld, B.W, D.NC / 64, alb, nb, st);
-    trsm_rec(Rb, D.ld, D.NC, B.A, D.ld, B.W, nb, 0, D.NC, st, true);        // R = L^-T
-    launch_syrk_upper_set(B.A, D.ld, Rb, D.ld, D.NC, nb, st);                // lower(A) = Kt^-1
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
-      for (int c = 0; c < lts[l0 + k].nt(); ++c) {
-        const size_t t = (size_t)toff[k] + c;
-        launch_grad_reduce(Am[s][j].p, D.ld, n, n, alb.p[j], F.z.p + (size_t)k * n, xd, d, lts[l0 + k].terms[c].gd, part[s].p,
-                           red.p + NGR * t, st, ardred.p + d * t);
-      }
-      launch_missing_wdiag(Am[s][j].p, D.ld, n, alb.p[j], F.nv.p + (size_t)k * n, wd.p + 2 * (size_t)k, st);
-    }
-  }
-  join_slots(nslots);
-  std::vector<double> lml(std::max(ms, 1), 0.0), hred((size_t)NGR * std::max(nterm, 1), 0.0), hwd(2 * (size_t)std::max(ms, 1), 0.0);
-  std::vector<int> hinfo(std::max(ms, 1), 0);
-  std::vector<double> hard(ard_d ? (size_t)d * std::max(nterm, 1) : 0, 0.0);
-  HIPCHK(hipMemcpyAsync(lml.data(), lmld.p, std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  const int m = (int)ls->lat.size(), ms = l1 - l0;
+  KernelGradPass K(ls, l0, l1, n, d);
+  Buf<double> wd(2 * (size_t)K.F.mk);        // alpha' D alpha and tr(Kt^-1 D) per latent, D its per-point noise
+  K.launch(xd, F.z.p, nullptr, F.nv.p, n, [](const FanBatch&, int, const double*, const double*, const LatentDev&) {},
+           [&](const FanBatch& b, int k, const double* Kinv, const double* al) {
+             launch_missing_wdiag(Kinv, K.D.ld, n, al, F.nv.p + (size_t)k * n, wd.p + 2 * (size_t)k, b.st);
+           });
+  K.read_back();
+  std::vector<double> hwd(2 * (size_t)K.F.mk, 0.0);
   if (ms > 0) HIPCHK(hipMemcpyAsync(hwd.data(), wd.p, hwd.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, st0));
+  K.F.fetch_info();
   if (gy_dev)
-    launch_missing_grad_y(n, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, alpha.p, D.NC, l0, ms, with_regulariser ? F.resid.p : nullptr, s2,
+    launch_missing_grad_y(n, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, K.alpha.p, K.D.NC, l0, ms, with_regulariser ? F.resid.p : nullptr, s2,
                           gy_dev, st0);
-  HIPCHK(hipStreamSynchronize(st0));
-  if (ms > 0)
-    if (int rc = check_info(hinfo, l0)) return rc;
+  if (int rc = K.F.check(l0)) return rc;
   double total = 0.0, gs2 = 0.0;
-  ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
-  trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
+  K.init_outputs(m, ggps, trec);
   for (int k = 0; k < ms; ++k) {
-    const int l = l0 + k;
-    total += lml[k];
-    const double* r = &hred[(size_t)NGR * toff[k]];
-    const double tr = r[1], aa = r[2], ad = r[3], sa = r[4];
+    total += K.lml[k];
+    const double* r = K.sums(k);
     const double D_aa = hwd[2 * (size_t)k], D_tr = hwd[2 * (size_t)k + 1];      // alpha' D alpha, tr(Kt^-1 D), D = diag(s2 (G_t^-1)_ll)
-    ggps[l].variance = 0.5 * ((ad - D_aa) - ((double)n - D_tr)) / lts[l].variance;
-    ggps[l].lengthscale = grad_finish(lts[l], d, r, hard.empty() ? nullptr : &hard[(size_t)d * toff[k]], aa, tr,
-                                      &trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)]);
-    ggps[l].mean = sa;
+    K.finish(k, D_aa, D_tr, r[2], r[1], ggps, trec);
     gs2 += 0.5 * (D_aa - D_tr) / s2;            // sum_t c_lt (alpha_t^2 - (Kt^-1)_tt) / 2, c_lt = (G_t^-1)_ll
   }
   if (with_regulariser) {
@@ -3622,7 +3637,7 @@ int lmm_ilmm_post_mean_and_var(const lmm_post_t* post, double sigma2, const doub
   Uploaded Hd(P->H, st0);
   Buf<double> ml((size_t)ns * m);
   const int nr = rup(m * ns, 64);
-  int ldr = nr; if ((ldr % 512) == 0) ldr += 16;
+  const int ldr = pad_ld(nr);
   Buf<double> R(mat_count((size_t)ldr * P->NC));
   dense_post_cross(P, xsd.p, d, ns, nr, R.p, ldr, st0);
   dense_post_means(P, xsd.p, d, ns, R.p, ldr, ml.p, st0);
@@ -3702,7 +3717,7 @@ int lmm_ilmm_post_mean_and_cov(const lmm_post_t* post, double sigma2, const doub
   Uploaded Hd(P->H, st0), Zd(std::vector<double>((size_t)m * m, 0.0), st0);
   Buf<double> ml((size_t)Ns);
   Dims Ds(Ns, 0);
-  int ldr = Ds.NC; if ((ldr % 512) == 0) ldr += 16;
+  const int ldr = pad_ld(Ds.NC);
   Buf<double> A(mat_count(Ds.elems())), R(mat_count((size_t)ldr * P->NC)), T((size_t)p * ns * Ns);
   dense_post_cross(P, xsd.p, d, ns, Ds.NC, R.p, ldr, st0);
   dense_post_means(P, xsd.p, d, ns, R.p, ldr, ml.p, st0);
@@ -3741,7 +3756,7 @@ int lmm_ilmm_post_logpdf(const lmm_post_t* post, double sigma2, const double* xs
   project_on_device(ysd.p, ns, p, Td.buf, m, 0, m, nullptr, Ty.p, st0);
   residual_on_device(ysd.p, ns, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p, st0);
   Dims Ds(Ns, 1);
-  int ldr = Ds.NC; if ((ldr % 512) == 0) ldr += 16;
+  const int ldr = pad_ld(Ds.NC);
   Buf<double> A(mat_count(Ds.elems())), WA(mat_count((size_t)(Ds.NC / 64) * 4096)), R(mat_count((size_t)ldr * P->NC)), lml_dev(1);
   dense_post_cross(P, xsd.p, d, ns, Ds.NC, R.p, ldr, st0);
   dense_post_means(P, xsd.p, d, ns, R.p, ldr, ml.p, st0);
@@ -3784,7 +3799,7 @@ int lmm_ilmm_post_rand(const lmm_post_t* post, double sigma2, int add_noise, con
   Uploaded Jd(J, st0), Hd(P->H, st0);
   Buf<double> ml((size_t)Ns), X((size_t)Ns);
   Dims Ds(Ns, 0);
-  int ldr = Ds.NC; if ((ldr % 512) == 0) ldr += 16;
+  const int ldr = pad_ld(Ds.NC);
   Buf<double> A(mat_count(Ds.elems())), WA(mat_count((size_t)(Ds.NC / 64) * 4096)), R(mat_count((size_t)ldr * P->NC)), part(strip_partial_elems(Ns, Ns, 1));
   dense_post_cross(P, xsd.p, d, ns, Ds.NC, R.p, ldr, st0);
   dense_post_means(P, xsd.p, d, ns, R.p, ldr, ml.p, st0);
@@ -3860,13 +3875,42 @@ static void cross_gram(const lmm_post* P, const Latent& gp, const double* xsd, i
   gram_g(cross_gram_args(P, gp, xsd, d, ns, Rk, ldr, nsr), st);
 }
 
+// The cross-solve blocks of a fan-out over a posterior's latents: per slot nb_per buffers R (nsr x P->NC, ldr), and for a batch
+// R_j <- K(xs, x) L_j^-T of its latents -- one batched cross-Gram launch (rows beyond ns zero), one batched triangular solve.
+struct CrossSlots {
+  int nsr, ldr;
+  std::vector<std::vector<Buf<double>>> R;
+  BatchPtr Rb{}, Lb{}, Wb{};       // the operands of the batch solved last (for what a caller runs on them next)
+  explicit CrossSlots(int nsr_) : nsr(nsr_), ldr(pad_ld(nsr_)) {}
+  double elems(const lmm_post* P) const { return (double)ldr * P->NC; }
+  void alloc(const lmm_post* P, const FanOut& F) {
+    R.resize(F.nslots);
+    for (int s = 0; s < F.nslots; ++s)
+      for (int j = 0; j < F.nb_per; ++j) R[s].emplace_back(mat_count((size_t)ldr * P->NC));
+  }
+  // det: no split-K in the solve's updates; prof: the Gram launch is one ProfScope of the cross-Gram's n* x n rectangle
+  void solve(const lmm_post* P, const FanBatch& b, const double* xsd, int d, int ns, bool det, bool prof) {
+    GramArgs ga[LMM_MAX_BATCH];
+    for (int j = 0; j < b.nb; ++j) {
+      const int k = b.k0 + j;
+      ga[j] = cross_gram_args(P, P->ls->lat[P->l0 + k], xsd, d, ns, R[b.s][j].p, ldr, nsr);
+      Rb.p[j] = R[b.s][j].p; Lb.p[j] = P->L[k].p; Wb.p[j] = P->W[k].p;
+    }
+    if (prof) {
+      const double gb = (double)ns * P->n * 8.0;                   // cross-Gram K(x*, x): a full n* x n rectangle written once
+      ProfScope ps(LMM_PROF_GRAM, b.nb * gb, b.st, 0, 0, 0, b.nb * gb, b.nb);
+      gram_batch_g(ga, b.nb, b.st);
+    } else gram_batch_g(ga, b.nb, b.st);
+    trsm_rec(Rb, ldr, nsr, Lb, P->ld, Wb, b.nb, 0, P->NC, b.st, false, true, det);       // R_j <- K(x*, x) L_j^-T for the whole batch
+  }
+};
+
 // Latent marginals (mean, var) of latents [l0, l1) at xs into device arrays (ns per latent).
 // post != NULL: posterior latents; else the prior latents lts_shard[0..ms).  Caller holds g_mu.
 static int latent_marginals_dev(const lmm_post* P, const Latent* lts_shard, int ms, const double* xsd, int d, int ns,
                                 double* mean_lat, double* var_lat) {
   if (ms == 0) return LMM_OK;
   if (P == nullptr) {
-    fork_slots(1);
     for (int k = 0; k < ms; ++k) {
       // prior: constant mean, variance kappa(0)
       rider_stats_g(nullptr, 0, ns, 0, nullptr, lts_shard[k].mean, lts_shard[k].prior_var(), nullptr, mean_lat + (size_t)k * ns,
@@ -3875,45 +3919,23 @@ static int latent_marginals_dev(const lmm_post* P, const Latent* lts_shard, int 
     return LMM_OK;
   }
   if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, xs has d=%d", P->d, d);
-  const int nsr = rup(ns, 64);
-  int ldr = nsr; if ((ldr % 512) == 0) ldr += 16;
-  int nb_per = 1, nslots = 1;
-  batch_plan(ms, &nb_per, &nslots, mat_bytes((double)ldr * P->NC));
-  std::vector<std::vector<Buf<double>>> R(nslots);
+  CrossSlots C(rup(ns, 64));
+  FanOut F(ms, mat_bytes(C.elems(P)));
+  C.alloc(P, F);
   std::vector<Buf<double>> part;
-  for (int s = 0; s < nslots; ++s) {
-    for (int j = 0; j < nb_per; ++j) R[s].emplace_back(mat_count((size_t)ldr * P->NC));
-    part.emplace_back(strip_partial_elems(nsr, P->NC, 2));
-  }
-  fork_slots(nslots);
-  int bi = 0;
-  for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
-    const int s = bi % nslots, nb = std::min(nb_per, ms - k0);
-    hipStream_t st = g.streams[s];
-    BatchPtr Rb{}, Lb{}, Wb{};
-    GramArgs ga[LMM_MAX_BATCH];
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
-      ga[j] = cross_gram_args(P, P->ls->lat[P->l0 + k], xsd, d, ns, R[s][j].p, ldr, nsr);
-      Rb.p[j] = R[s][j].p; Lb.p[j] = P->L[k].p; Wb.p[j] = P->W[k].p;
-    }
-    {
-      const double gb = (double)ns * P->n * 8.0;                   // cross-Gram K(x*, x): a full n* x n rectangle written once
-      ProfScope ps(LMM_PROF_GRAM, nb * gb, st, 0, 0, 0, nb * gb, nb);
-      gram_batch_g(ga, nb, st);
-    }
-    trsm_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st);       // R_j <- K(x*, x) L_j^-T for the whole batch
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
+  for (int s = 0; s < F.nslots; ++s) part.emplace_back(strip_partial_elems(C.nsr, P->NC, 2));
+  F.run([&](const FanBatch& b) {
+    C.solve(P, b, xsd, d, ns, false, true);
+    for (int j = 0; j < b.nb; ++j) {
+      const int k = b.k0 + j;
       const Latent& gp = P->ls->lat[P->l0 + k];
       // mean = mu + K(x*,x) alpha = mu + R' (L^-1 delta);  var = kappa(0) - colsumsq(R)   (one pass over R)
       const double rb = (double)ns * P->n * 8.0;                   // R read once
-      ProfScope ps(LMM_PROF_STRIP, rb, st, ns, P->n, 0, rb);
-      rider_stats_g(R[s][j].p, ldr, ns, P->n, P->z[k].p, gp.mean, gp.prior_var(), part[s].p, mean_lat + (size_t)k * ns,
-                         var_lat + (size_t)k * ns, st);
+      ProfScope ps(LMM_PROF_STRIP, rb, b.st, ns, P->n, 0, rb);
+      rider_stats_g(C.R[b.s][j].p, C.ldr, ns, P->n, P->z[k].p, gp.mean, gp.prior_var(), part[b.s].p, mean_lat + (size_t)k * ns,
+                         var_lat + (size_t)k * ns, b.st);
     }
-  }
-  join_slots(nslots);
+  });
   HIPCHK(hipStreamSynchronize(g.streams[0]));   // R buffers are released on return
   return LMM_OK;
 }
@@ -4015,51 +4037,29 @@ static int mean_var_grad_xs_dev(const lmm_post* P, int ms, const double* xsd, in
     HIPCHK(hipStreamSynchronize(st0));
     return LMM_OK;
   }
-  const int nsr = rup(ns, 64);
-  int ldr = nsr; if ((ldr % 512) == 0) ldr += 16;
-  int nb_per = 1, nslots = 1;
-  batch_plan(ms, &nb_per, &nslots, mat_bytes((double)ldr * P->NC));
-  std::vector<std::vector<Buf<double>>> R(nslots);
+  CrossSlots C(rup(ns, 64));
+  FanOut F(ms, mat_bytes(C.elems(P)));
+  C.alloc(P, F);
   std::vector<Buf<double>> part, acc;
-  for (int s = 0; s < nslots; ++s) {
-    for (int j = 0; j < nb_per; ++j) R[s].emplace_back(mat_count((size_t)ldr * P->NC));
+  for (int s = 0; s < F.nslots; ++s) {
     part.emplace_back(pred_grad_x_partial_elems(P->n, ns, d));
     acc.emplace_back(count);
   }
-  std::vector<char> used(nslots, 0);
-  fork_slots(nslots);
-  int bi = 0;
-  for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
-    const int s = bi % nslots, nb = std::min(nb_per, ms - k0);
-    hipStream_t st = g.streams[s];
-    BatchPtr Rb{}, Lb{}, Wb{};
-    GramArgs ga[LMM_MAX_BATCH];
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
-      ga[j] = cross_gram_args(P, P->ls->lat[P->l0 + k], xsd, d, ns, R[s][j].p, ldr, nsr);
-      Rb.p[j] = R[s][j].p; Lb.p[j] = P->L[k].p; Wb.p[j] = P->W[k].p;
-    }
-    gram_batch_g(ga, nb, st);
-    trsm_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st, false, true, true);   // R_j <- K(x*, x) L_j^-T, no split-K
-    trsm_right_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st);    // R_j <- R_j L_j^-1 = K(x*, x) K_j^-1
-    for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
+  std::vector<char> used(F.nslots, 0);
+  F.run([&](const FanBatch& b) {
+    C.solve(P, b, xsd, d, ns, true, false);                                              // R_j <- K(x*, x) L_j^-T, no split-K
+    trsm_right_rec(C.Rb, C.ldr, C.nsr, C.Lb, P->ld, C.Wb, b.nb, 0, P->NC, b.st);         // R_j <- R_j L_j^-1 = K(x*, x) K_j^-1
+    for (int j = 0; j < b.nb; ++j) {
+      const int k = b.k0 + j;
       const Latent& gp = P->ls->lat[P->l0 + k];
       for (int c = 0; c < gp.nt(); ++c) {
-        launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, vbar + (size_t)k * ns, R[s][j].p, ldr,
-                           gp.terms[c].ev, part[s].p, acc[s].p, used[s] != 0, st);
-        used[s] = 1;
+        launch_pred_grad_x(xsd, ns, P->x.p, P->n, d, P->alpha[k].p, mbar + (size_t)k * ns, vbar + (size_t)k * ns, C.R[b.s][j].p, C.ldr,
+                           gp.terms[c].ev, part[b.s].p, acc[b.s].p, used[b.s] != 0, b.st);
+        used[b.s] = 1;
       }
     }
-  }
-  join_slots(nslots);
-  bool first = true;
-  for (int s = 0; s < nslots; ++s) {
-    if (!used[s]) continue;
-    if (first) HIPCHK(hipMemcpyAsync(gout, acc[s].p, count * sizeof(double), hipMemcpyDeviceToDevice, st0));
-    else launch_vec_axpby(gout, 1.0, acc[s].p, 1.0, count, gout, st0);
-    first = false;
-  }
+  });
+  sum_slots(gout, acc, used, count, st0, true);
   HIPCHK(hipStreamSynchronize(st0));   // R buffers are released on return
   return LMM_OK;
 }
@@ -4148,35 +4148,35 @@ static void cov_at_xs_batch(const lmm_post* P, const GramArgs* ga, int nb, const
 // with their inverse blocks, means, riders and cross-solve blocks R, and one reduction scratch (reused latent after latent in
 // stream order).
 struct XsSlots {
-  int nb_per = 1, nslots = 1, ldr = 0, nsr = 0;
-  std::vector<std::vector<Buf<double>>> B, WB, mu, rid, R;
+  CrossSlots C;                        // the Schur complement reads Ds.NC rows of R (rows beyond ns are zero)
+  FanOut F;
+  std::vector<std::vector<Buf<double>>> B, WB, mu, rid;
   std::vector<Buf<double>> part;
-  XsSlots(const lmm_post* P, int ms, int ns, const Dims& Ds) {
-    nsr = Ds.NC;                     // the Schur complement reads Ds.NC rows of R (rows beyond ns are zero)
-    ldr = nsr; if ((ldr % 512) == 0) ldr += 16;
-    batch_plan(std::max(ms, 1), &nb_per, &nslots, mat_bytes((double)Ds.elems() + (P ? (double)ldr * P->NC : 0.0)));
-    B.resize(nslots); WB.resize(nslots); mu.resize(nslots); rid.resize(nslots); R.resize(nslots);
+  XsSlots(const lmm_post* P, int ms, int ns, const Dims& Ds)
+      : C(Ds.NC), F(ms, mat_bytes((double)Ds.elems() + (P ? C.elems(P) : 0.0))) {
+    const int nslots = F.nslots;
+    B.resize(nslots); WB.resize(nslots); mu.resize(nslots); rid.resize(nslots);
     for (int s = 0; s < nslots; ++s) {
-      for (int j = 0; j < nb_per; ++j) {
+      for (int j = 0; j < F.nb_per; ++j) {
         B[s].emplace_back(mat_count(Ds.elems())); WB[s].emplace_back(mat_count((size_t)(Ds.NC / 64) * 4096));
         mu[s].emplace_back((size_t)ns); rid[s].emplace_back((size_t)ns);
-        R[s].emplace_back(P ? mat_count((size_t)ldr * P->NC) : 1);
       }
-      part.emplace_back(std::max(strip_partial_elems(nsr, P ? P->NC : 1, 1), strip_partial_elems(ns, ns, 1)));
+      part.emplace_back(std::max(strip_partial_elems(C.nsr, P ? P->NC : 1, 1), strip_partial_elems(ns, ns, 1)));
     }
+    if (P) C.alloc(P, F);
   }
-  // R[s][j] <- K(xs, x) L_k^-T and mu[s][j] <- mean_k(xs) for the latents k0..k0+nb-1 of the posterior's shard (one batched solve)
-  void cross_solve_batch(const lmm_post* P, int s, int k0, int nb, const double* xsd, int d, int ns, hipStream_t st) {
-    BatchPtr Rb{}, Lb{}, Wb{};
-    GramArgs ga[LMM_MAX_BATCH];
-    for (int j = 0; j < nb; ++j) {
-      ga[j] = cross_gram_args(P, P->ls->lat[P->l0 + k0 + j], xsd, d, ns, R[s][j].p, ldr, nsr);
-      Rb.p[j] = R[s][j].p; Lb.p[j] = P->L[k0 + j].p; Wb.p[j] = P->W[k0 + j].p;
-    }
-    gram_batch_g(ga, nb, st);
-    trsm_rec(Rb, ldr, nsr, Lb, P->ld, Wb, nb, 0, P->NC, st);
-    for (int j = 0; j < nb; ++j)
-      rider_stats_g(R[s][j].p, ldr, ns, P->n, P->z[k0 + j].p, P->ls->lat[P->l0 + k0 + j].mean, 0.0, part[s].p, mu[s][j].p, nullptr, st);
+  // R[s][j] <- K(xs, x) L_k^-T and mu[s][j] <- mean_k(xs) for the latents of the batch (one batched solve)
+  void cross_solve_batch(const lmm_post* P, const FanBatch& b, const double* xsd, int d, int ns) {
+    C.solve(P, b, xsd, d, ns, false, false);
+    for (int j = 0; j < b.nb; ++j)
+      rider_stats_g(C.R[b.s][j].p, C.ldr, ns, P->n, P->z[b.k0 + j].p, P->ls->lat[P->l0 + b.k0 + j].mean, 0.0, part[b.s].p, mu[b.s][j].p,
+                    nullptr, b.st);
+  }
+  // the batch's covariance at xs: one Gram launch per run of equal kinds, ONE batched Schur-complement GEMM against the batch's R
+  void cov_batch(const lmm_post* P, const FanBatch& b, const GramArgs* ga, const Dims& Ds) {
+    BatchPtr Bb{};
+    for (int j = 0; j < b.nb; ++j) Bb.p[j] = B[b.s][j].p;
+    cov_at_xs_batch(P, ga, b.nb, Ds, Bb, C.Rb, C.ldr, b.st);
   }
 };
 
@@ -4212,7 +4212,7 @@ extern "C" int lmm_lmm_mean_and_cov(const lmm_post_t* post, const lmm_gp_t* gps,
   Buf<double> ml((size_t)ns * std::max(ms, 1));
   Dims Ds(ns, 0);
   const int nsr = Ds.NC;           // the Schur complement reads Ds.NC rows of R
-  int ldr = nsr; if ((ldr % 512) == 0) ldr += 16;
+  const int ldr = pad_ld(nsr);
   const int CH = LMM_MAX_BATCH;
   std::vector<Buf<double>> Cm;
   for (int c = 0; c < std::min(CH, std::max(ms, 1)); ++c) Cm.emplace_back(mat_count(Ds.elems()));
@@ -4275,9 +4275,9 @@ extern "C" int lmm_mogp_cross_cov(const lmm_post_t* post, const lmm_gp_t* gps, i
   // K(x, y) as the "rider rows" of a Gram launch whose column points are y: rows [NCy, NCy + nxr) of a (NCy + nxr) x NCy layout,
   // stored from buffer row 0 (the cross-Gram form of the predictive paths)
   const int nxr = rup(n, 128), NCy = rup(n2, 128);
-  int ldk = nxr; if ((ldk % 512) == 0) ldk += 16;
+  const int ldk = pad_ld(nxr);
   Buf<double> Kb(mat_count((size_t)ldk * NCy));
-  int ldr = std::max(nxr, NCy); if ((ldr % 512) == 0) ldr += 16;
+  const int ldr = pad_ld(std::max(nxr, NCy));
   Buf<double> Rx(P ? mat_count((size_t)ldr * P->NC) : 1), Ry(P ? mat_count((size_t)ldr * P->NC) : 1);
   for (int l = l0; l < l1; ++l) {
     const Latent& gp = lts[l];
@@ -4334,38 +4334,29 @@ int lmm_oilmm_post_logpdf(const lmm_post_t* post, const double* U, const double*
   const double* Ty_shard = Ty.p + (size_t)(l0 - c0) * ns;
   Dims Ds(ns, 1);
   XsSlots X(P, ms, ns, Ds);
-  const int nslots = X.nslots;
-  Buf<double> outd(std::max(ms, 1));
-  Buf<int> info(std::max(ms, 1));
-  HIPCHK(hipMemsetAsync(info.p, 0, std::max(ms, 1) * sizeof(int), st0));
-  fork_slots(nslots);
-  int bi = 0;
-  for (int k0 = 0; k0 < ms; k0 += X.nb_per, ++bi) {
-    const int s = bi % nslots, nb = std::min(X.nb_per, ms - k0);
-    hipStream_t st = g.streams[s];
+  const int mk = X.F.mk;
+  Buf<double> outd(mk);
+  int* info = X.F.alloc_info();
+  X.F.run([&](const FanBatch& b) {
+    const int s = b.s, nb = b.nb;
+    hipStream_t st = b.st;
     Batch Bt;
-    X.cross_solve_batch(P, s, k0, nb, xsd.p, d, ns, st);
+    X.cross_solve_batch(P, b, xsd.p, d, ns);
     GramArgs ga[LMM_MAX_BATCH];
-    BatchPtr Bb{}, Rb{};
     for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
+      const int k = b.k0 + j;
       const Latent& gp = P->ls->lat[l0 + k];
       launch_vec_lin(Ty_shard + (size_t)k * ns, X.mu[s][j].p, -1.0, ns, X.rid[s][j].p, st);
       ga[j] = cov_args(gp, xsd.p, d, ns, ST[l0 + k], X.rid[s][j].p, Ds, X.B[s][j].p);
-      Bb.p[j] = X.B[s][j].p; Rb.p[j] = X.R[s][j].p;
-      Bt.add(X.B[s][j].p, X.WB[s][j].p, info.p + k);
+      Bt.add(X.B[s][j].p, X.WB[s][j].p, info + k);
     }
-    cov_at_xs_batch(P, ga, nb, Ds, Bb, Rb, X.ldr, st);
+    X.cov_batch(P, b, ga, Ds);
     potrf_batch(Bt, Ds.ld, Ds.NR, Ds.NC, ns, st);
-    launch_lml_reduce(Bt.A, nb, Ds.ld, ns, Ds.NC, 1, outd.p + k0, st);
-  }
-  join_slots(nslots);
-  std::vector<double> lml(std::max(ms, 1), 0.0);
-  std::vector<int> hinfo(std::max(ms, 1), 0);
-  HIPCHK(hipMemcpyAsync(lml.data(), outd.p, std::max(ms, 1) * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  if (int rc = check_info(hinfo, l0)) return rc;
+    launch_lml_reduce(Bt.A, nb, Ds.ld, ns, Ds.NC, 1, outd.p + b.k0, st);
+  });
+  std::vector<double> lml(mk, 0.0);
+  HIPCHK(hipMemcpyAsync(lml.data(), outd.p, mk * sizeof(double), hipMemcpyDeviceToHost, st0));
+  if (int rc = X.F.check(l0)) return rc;
   double total = 0.0;
   for (int k = 0; k < ms; ++k) total += lml[k];
   if (with_regulariser) {
@@ -4399,11 +4390,11 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps, const double
   } else if (int rc = resolve(gps, m, d, ls)) return rc;
   const Latent* lts = ls->lat.data();
   if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
-  const int ms = l1 - l0;
+  const int ms = l1 - l0, mk = std::max(ms, 1);
   // OILMM: f(x) default jitter 1e-18 (reference src/oilmm.jl:47); dense-H ILMM: 1e-12 (src/ilmm.jl:84)
   const double jitter = S ? jit->default_jitter : jit->ilmm_rand_jitter;
   hipStream_t st0 = g.streams[0];
-  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
+  std::vector<double> Hs((size_t)p * mk, 0.0);
   for (int k = 0; k < ms; ++k)
     for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * (S ? std::sqrt(S[l0 + k]) : 1.0);
   Uploaded Hd(Hs, st0);
@@ -4412,30 +4403,23 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps, const double
   DevIn epsd(add_noise ? eps : nullptr, (size_t)ns * p * nsamples, st0);
   Dims Ds(ns, 0);
   XsSlots Xs(P, ms, ns, Ds);
-  const int nslots = Xs.nslots;
-  Buf<double> X((size_t)ns * std::max(ms, 1) * nsamples);     // [sample][latent of the shard][ns]
-  Buf<int> info(std::max(ms, 1));
-  HIPCHK(hipMemsetAsync(info.p, 0, std::max(ms, 1) * sizeof(int), st0));
-  fork_slots(nslots);
-  int bi = 0;
-  for (int k0 = 0; k0 < ms; k0 += Xs.nb_per, ++bi) {
-    const int s = bi % nslots, nb = std::min(Xs.nb_per, ms - k0);
-    hipStream_t st = g.streams[s];
+  Buf<double> X((size_t)ns * mk * nsamples);     // [sample][latent of the shard][ns]
+  int* info = Xs.F.alloc_info();
+  Xs.F.run([&](const FanBatch& b) {
+    const int s = b.s, nb = b.nb;
+    hipStream_t st = b.st;
     Batch Bt;
-    if (P) Xs.cross_solve_batch(P, s, k0, nb, xsd.p, d, ns, st);      // posterior: R_k and the mean vectors (sample = mean + L z)
+    if (P) Xs.cross_solve_batch(P, b, xsd.p, d, ns);      // posterior: R_k and the mean vectors (sample = mean + L z)
     GramArgs ga[LMM_MAX_BATCH];
-    BatchPtr Bb{}, Rb{};
     for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
-      const Latent& gp = lts[l0 + k];
-      ga[j] = cov_args(gp, xsd.p, d, ns, jitter, nullptr, Ds, Xs.B[s][j].p);
-      Bb.p[j] = Xs.B[s][j].p; Rb.p[j] = Xs.R[s][j].p;
-      Bt.add(Xs.B[s][j].p, Xs.WB[s][j].p, info.p + k);
+      const int k = b.k0 + j;
+      ga[j] = cov_args(lts[l0 + k], xsd.p, d, ns, jitter, nullptr, Ds, Xs.B[s][j].p);
+      Bt.add(Xs.B[s][j].p, Xs.WB[s][j].p, info + k);
     }
-    cov_at_xs_batch(P, ga, nb, Ds, Bb, Rb, Xs.ldr, st);
+    Xs.cov_batch(P, b, ga, Ds);
     potrf_batch(Bt, Ds.ld, Ds.NR, Ds.NC, ns, st);      // ONE factorisation per latent, nsamples triangular products
     for (int j = 0; j < nb; ++j) {
-      const int k = k0 + j;
+      const int k = b.k0 + j;
       const double mu_const = P ? 0.0 : lts[l0 + k].mean;
       for (int q = 0; q < nsamples; ++q) {
         double* Xq = X.p + ((size_t)q * ms + k) * ns;
@@ -4443,18 +4427,14 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps, const double
         if (P) launch_vec_lin(Xq, Xs.mu[s][j].p, 1.0, ns, Xq, st);
       }
     }
-  }
-  join_slots(nslots);
+  });
   DevOut od(out, (size_t)ns * p * nsamples);
   // reference src/oilmm.jl:50-53 / src/ilmm.jl:86: F = vec((H X')') + sqrt(sigma2) eps
   for (int q = 0; q < nsamples; ++q)
     launch_mix(X.p + (size_t)q * ms * ns, ns, ms, Hd.buf.p, p, 1, 0.0, 0.0, add_noise ? epsd.p + (size_t)q * ns * p : nullptr,
                std::sqrt(sigma2), od.p + (size_t)q * ns * p, st0);
   od.finish(st0);
-  std::vector<int> hinfo(std::max(ms, 1), 0);
-  HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, std::max(ms, 1) * sizeof(int), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  return check_info(hinfo, l0);
+  return Xs.F.check(l0);
   LMM_CATCH
 }
 
@@ -4521,7 +4501,8 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
   if (ms == 0) return LMM_OK;
   hipStream_t st = g.streams[0];
   Dims D(M, 1);
-  const int nb_per = std::min(ms, LMM_MAX_BATCH);
+  FanOut F = FanOut::one_slot(ms);
+  const int nb_per = F.nb_per;
   for (int k = 0; k < ms; ++k) {
     out.Lu.emplace_back(D.elems()); out.Wu.emplace_back((size_t)(D.NC / 64) * 4096);
     out.LB.emplace_back(D.elems()); out.WB.emplace_back((size_t)(D.NC / 64) * 4096);
@@ -4531,14 +4512,12 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
   for (int j = 0; j < (out.keep_grad ? ms : nb_per); ++j) Q.emplace_back(D.elems());
   // b (NC per latent); res = [3 ms: s, kappa, lambda | ms: tr Q | 2 ms: -(M log 2pi + log det B + q) / 2 with q = c'c, then q = 0 (the zero row under the rider)]; two pivot-info words per latent
   Buf<double> bvec((size_t)D.NC * ms), res((size_t)6 * ms);
-  Buf<int> info((size_t)2 * ms);
-  HIPCHK(hipMemsetAsync(info.p, 0, (size_t)2 * ms * sizeof(int), st));
+  int* info = F.alloc_info(2);
   int chunk = 0, nch = 0;
   if (int rc = sparse_plan(n, nz, nb_per, 0, &chunk, &nch)) return rc;
   Buf<double> scratch((size_t)nb_per * nch * sparse_partial_stride(nz));
-  fork_slots(1);
-  for (int k0 = 0; k0 < ms; k0 += nb_per) {
-    const int nb = std::min(nb_per, ms - k0);
+  F.run([&](const FanBatch& fb) {
+    const int k0 = fb.k0, nb = fb.nb;
     SparseMomArgs a{};
     a.x = xd; a.z = zd; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.scratch = scratch.p;
     BatchPtr Pb{}, Qb{}, bb{}, sb{};
@@ -4555,8 +4534,8 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
       gp.set_kernel(r); r.pad_diag = 1.0; r.diag_add = jitter;
       r.rider = bb.p[j]; r.rider_ld = D.NC; r.nrider = 1;
       ga[j] = r;
-      Bu.add(out.Lu[k].p, out.Wu[k].p, info.p + k);
-      Bb.add(out.LB[k].p, out.WB[k].p, info.p + ms + k);
+      Bu.add(out.Lu[k].p, out.Wu[k].p, info + k);
+      Bb.add(out.LB[k].p, out.WB[k].p, info + ms + k);
     }
     launch_sparse_moments(a, nb, st);
     launch_sparse_finish(scratch.p, nch, nz, Pb, D.ld, true, bb, sb, nb, st);
@@ -4575,15 +4554,12 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
     BatchPtr cb{};
     for (int j = 0; j < nb; ++j) cb.p[j] = out.c[k0 + j].p;
     launch_extract_rows(Bb.A, nb, D.ld, D.NC, M, D.NC, cb, cb, st);
-  }
-  join_slots(1);
+  });
   std::vector<double> hres((size_t)6 * ms);
-  std::vector<int> hinfo((size_t)2 * ms);
   HIPCHK(hipMemcpyAsync(hres.data(), res.p, hres.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, hinfo.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (int rc = check_info(hinfo.data(), ms, l0)) { if (rc == LMM_ERR_NOT_PD) g.err += " [K_uu + jitter I of the inducing points]"; return rc; }
-  if (int rc = check_info(hinfo.data() + ms, ms, l0)) { if (rc == LMM_ERR_NOT_PD) g.err += " [B = I + L_u^-1 Phi L_u^-T]"; return rc; }
+  const int* hinfo = F.host_info();
+  if (int rc = check_info(hinfo, ms, l0)) { if (rc == LMM_ERR_NOT_PD) g.err += " [K_uu + jitter I of the inducing points]"; return rc; }
+  if (int rc = check_info(hinfo + ms, ms, l0)) { if (rc == LMM_ERR_NOT_PD) g.err += " [B = I + L_u^-1 Phi L_u^-T]"; return rc; }
   for (int k = 0; k < ms; ++k) {
     const double* r = hres.data() + (size_t)3 * k;       // s, kappa, lambda
     // the Gaussian form carries -c'c / 2, the bound +c'c / 2: c'c = 2 (g0 - gc) from the two reductions
@@ -4639,7 +4615,8 @@ static int sparse_grad_core(const double* xd, int d, int n, const double* zd, in
   if (gz_dev) HIPCHK(hipMemsetAsync(gz_dev, 0, (size_t)d * nz * sizeof(double), st));
   if (ms == 0) return LMM_OK;
   Dims D(M, 1);
-  const int nb_per = std::min(ms, LMM_MAX_BATCH);
+  FanOut fan = FanOut::one_slot(ms);
+  const int nb_per = fan.nb_per;
   std::vector<LatentDev> hgd;
   for (int k = 0; k < ms; ++k) for (const KernelTerm& T : lts[l0 + k].terms) hgd.push_back(T.gd);
   Buf<LatentDev> gdd(nterm);
@@ -4664,9 +4641,8 @@ static int sparse_grad_core(const double* xd, int d, int n, const double* zd, in
   Buf<double> scratch((size_t)nb_per * nch * tm * sparse_grad_partial_stride(d));
   const int mode = sparse_grad_mode(lts, l0, l1);
   bool gz_first = true;
-  fork_slots(1);
-  for (int k0 = 0; k0 < ms; k0 += nb_per) {
-    const int nb = std::min(nb_per, ms - k0);
+  fan.run([&](const FanBatch& fb) {
+    const int k0 = fb.k0, nb = fb.nb;
     BatchPtr Rub{}, Kib{}, Sib{}, T1b{}, T2b{}, Lub{}, Wub{}, LBb{}, WBb{}, Qb{}, cb{}, betab{}, recb{}, gzb{};
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
@@ -4711,8 +4687,7 @@ static int sparse_grad_core(const double* xd, int d, int n, const double* zd, in
       }
     }
     HIPCHK(hipStreamSynchronize(st));            // hlat is rewritten by the next batch
-  }
-  join_slots(1);
+  });
   std::vector<double> hF(nrec * ms), hK((size_t)NGR * nterm), hA((size_t)d * nterm);
   HIPCHK(hipMemcpyAsync(hF.data(), recF.p, hF.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(hK.data(), recK.p, hK.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4959,9 +4934,8 @@ int lmm_oilmm_sparse_mean_and_var(const lmm_sparse_post_t* post, const lmm_gp_t*
   DevIn xsd(xs, (size_t)d * ns, st0);
   Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1)), v1(ns), v2(ns), tmp(ns);
   const int nsr = rup(ns, 64);
-  int ldr = nsr; if ((ldr % 512) == 0) ldr += 16;
+  const int ldr = pad_ld(nsr);
   Buf<double> R((size_t)ldr * P->NC), part(strip_partial_elems(nsr, P->NC, 2));
-  fork_slots(1);
   for (int k = 0; k < ms; ++k) {
     const Latent& gp = P->ls->lat[l0 + k];
     GramArgs r{};      // R (nsr x NC, ldr) = K(xs, z) as rider rows, rows beyond ns zero
@@ -4977,7 +4951,6 @@ int lmm_oilmm_sparse_mean_and_var(const lmm_sparse_post_t* post, const lmm_gp_t*
     rider_stats_g(R.p, ldr, ns, M, P->c[k].p, gp.mean, 0.0, part.p, ml.p + (size_t)k * ns, v2.p, st0);   // v2 = -|L_B^-1 a|^2
     launch_vec_lin(v1.p, v2.p, -1.0, ns, vl.p + (size_t)k * ns, st0);
   }
-  join_slots(1);
   DevOut mo(mean_out, (size_t)ns * p), vo(var_out, (size_t)ns * p);
   mix_marginals(ml.p, ns, ms, Hd.buf.p, p, 1, 0.0, 0.0, mo.p, st0);
   if (var_out) mix_marginals(vl.p, ns, ms, Hd.buf.p, p, 2, kDefaultJit.default_jitter, add_noise ? sigma2 : 0.0, vo.p, st0);
