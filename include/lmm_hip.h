@@ -649,6 +649,50 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
                         const double* r, const double* PhiBar, int ld, const double* beta, int chunk, double* term_records,
                         double* grad_z, double* grad_r);
 
+/* ---- state space (Matern latents over a one-dimensional input) --------------------------------------
+ * Matern12, Matern32 and Matern52 over a one-dimensional input are exactly a 1-, 2- or 3-dimensional linear SDE, so once the OILMM
+ * projection has decoupled the latents a Kalman filter gives the value of lmm_oilmm_logpdf and a Rauch-Tung-Striebel smoother the
+ * posterior marginals, both in O(n) and without approximation (the OILMM paper names state-space methods next to
+ * inducing points as the two ways to linear cost).  Both recursions run as parallel scans over the points (Sarkka & Garcia-Fernandez,
+ * "Temporal parallelization of Bayesian smoothers"): each thread folds `chunk` consecutive points, the aggregates are scanned, each
+ * thread restarts the ordinary recursion from its prefix.  No atomics: results depend only on (arguments, chunk) and are bitwise
+ * reproducible.  x: n inputs (d = 1 is part of the signature), NON-DECREASING (equal points are legal); anything else is LMM_ERR_ARG
+ * with the index of the first x[t] that is not >= x[t - 1] in lmm_last_error_detail's `info` (the Python mirror sorts).
+ * Per latent l, with lam = 1 / l, sqrt(3) / l or sqrt(5) / l: the state is (f, f', f''), F the companion matrix of (s + lam)^D,
+ * A(dt) = exp(-lam dt) (I + N dt + N^2 dt^2 / 2) with N = F + lam I, Q(dt) = Pinf - A Pinf A', prior N(0, Pinf); the observation is the
+ * first component plus N(0, w_t).
+ * Data: y as for lmm_oilmm_logpdf, NaN = missing.  The front end is that of the missing-data entry points (the diagonal approximation,
+ * exact without NaN and whenever every G_t is diagonal; m <= 128): per point the pseudo-observation z_t[l] - mean_l with noise variance
+ * sigma2 (G_t^-1)_ll, and the same regulariser.  Additionally a point with NO observed output is kept, as a predict-only step that
+ * contributes no term: that is how marginals at new inputs are asked for (merge them into x with all-NaN rows of y).
+ * Refusals, all before any kernel of the scan is launched: a latent that is not a plain Matern12 / 32 / 52 (SE, RQ, the periodic
+ * kinds, sums, latents with a tag) -> LMM_ERR_UNSUPPORTED with the latent in the error detail; the fp32 compute mode ->
+ * LMM_ERR_UNSUPPORTED; a point with 0 < p_t < m -> LMM_ERR_UNSUPPORTED with the point in `info`; S not finite and > 0, sigma2 <= 0 ->
+ * LMM_ERR_ARG.  Not built: gradients, sums of Matern terms, rand.
+ *   lmm_oilmm_logpdf_statespace : the value of lmm_oilmm_logpdf (no NaN) or lmm_oilmm_logpdf_missing (NaN) by the filter: agreement
+ *                    to rounding, not bitwise.  Shard semantics and with_regulariser as there.
+ *   lmm_oilmm_mean_and_var_statespace : the smoothed latent marginals at the n inputs, mixed through H = U sqrt(S) exactly as
+ *                    lmm_oilmm_mean_and_var mixes (+ sigma2 when add_noise): mean_and_var(posterior(fx, y)(x, sigma2)) at the
+ *                    training inputs.  mean, var: n x p in the layout of y, host or device; var may be NULL.  Partial sums over the
+ *                    shard.  The filtered states it keeps are D + D (D + 1) / 2 doubles per point and latent; latents run in groups
+ *                    that keep them within 1 GiB.
+ *   lmm_dev_statespace_filter, lmm_dev_statespace_smooth : building blocks exported for tests (DEVICE pointers x, w, r and outputs; gp
+ *                    on the host, its mean is not read): one latent with per-point noise w (n; +Inf = unobserved) and data r (n).
+ *                    fmean, fvar: the filtered first-component mean and variance (the predicted ones at an unobserved point);
+ *                    *lml: sum_t -1/2 (log 2 pi S_t + e_t^2 / S_t) over the observed points; smean, svar: the smoothed ones.
+ *                    chunk: points per thread (0: the library's plan, a function of n alone); chunk >= n is one sequential thread. */
+int lmm_oilmm_logpdf_statespace(const double* x, int n, const double* y, int p,
+                                const double* U, const double* S, int m, double sigma2,
+                                const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out);
+int lmm_oilmm_mean_and_var_statespace(const double* x, int n, const double* y, int p,
+                                      const double* U, const double* S, int m, double sigma2,
+                                      const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise,
+                                      double* mean, double* var);
+int lmm_dev_statespace_filter(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
+                              double* fmean, double* fvar, double* lml);
+int lmm_dev_statespace_smooth(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
+                              double* smean, double* svar);
+
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard
  * normals in the reference's draw order: z_lat = m blocks of ns (latent order), eps = ns*p (by-outputs),

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -5025,6 +5026,242 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
+  LMM_CATCH
+}
+
+// ------------------------------------------------------------------------------------------------
+// State-space inference for Matern12 / 32 / 52 latents over a one-dimensional input (include/lmm_hip.h "state space"):
+// the Kalman filter and the RTS smoother as parallel scans over the points (lmm_kernels_ss.hip), linear in n and exact.
+// ------------------------------------------------------------------------------------------------
+#define LMM_SS_BATCH_BYTES (size_t(1) << 30)       // device memory one launch's latents may take (aggregates, filtered states)
+
+// Every latent must be a plain Matern12 / 32 / 52: no tag (per-dimension factors), no sum.  Names the first that is not.
+static int ss_check_latents(const Latent* lts, int m) {
+  for (int l = 0; l < m; ++l) {
+    const Latent& L = lts[l];
+    if (L.is_sum() || L.tag != 0 || ss_state_dim(L.kind) == 0 || L.terms.size() != 1 || L.terms[0].ev.ils != nullptr) {
+      g.err_latent = l; g.err_info = 0;
+      return fail(LMM_ERR_UNSUPPORTED, "state-space inference is served for plain Matern12, Matern32 and Matern52 latents: latent %d is not one", l);
+    }
+  }
+  return LMM_OK;
+}
+
+// x (device, n values) must be non-decreasing: LMM_ERR_ARG with the first offending index in the error detail's `info`.
+static int ss_check_sorted(const double* xd, int n) {
+  hipStream_t st0 = g.streams[0];
+  Buf<int> flag(1);
+  int h = INT_MAX;
+  HIPCHK(hipMemcpyAsync(flag.p, &h, sizeof(int), hipMemcpyHostToDevice, st0));
+  launch_ss_sorted(xd, n, flag.p, st0);
+  HIPCHK(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  if (h != INT_MAX) {
+    g.err_latent = -1; g.err_info = h;
+    return fail(LMM_ERR_ARG, "state-space inference needs non-decreasing inputs: x[%d] is not >= x[%d] (sort the points first)", h, h - 1);
+  }
+  return LMM_OK;
+}
+
+// The filter (and, smean != nullptr, the smoother) of the ms latents lts[0 .. ms): w, r, fmean, fvar, smean, svar are [latent][n] on
+// the device (outputs may be nullptr); lml: ms host values or nullptr; add_mean: the smoothed means get the latent's mean added.
+// Latents run in launches of equal state dimension, as many per launch as LMM_SS_BATCH_BYTES admits.  Returns with streams[0] drained.
+static int ss_core(const double* xd, int n, const Latent* lts, int ms, const double* w, const double* r, int chunk, double* lml,
+                   double* fmean, double* fvar, double* smean, double* svar, bool add_mean) {
+  hipStream_t st0 = g.streams[0];
+  if (chunk <= 0) chunk = ss_default_chunk(n);
+  if (chunk > n) chunk = n;
+  const int nch = (n + chunk - 1) / chunk;
+  const bool smooth = smean != nullptr;
+  for (int k0 = 0; k0 < ms;) {
+    const int D = ss_state_dim(lts[k0].kind);
+    const size_t comps = (size_t)ss_state_comps(D);
+    const size_t per = (ss_fwd_agg_elems(D, nch) + (size_t)nch + (smooth ? comps * n + ss_bwd_agg_elems(D, nch) : 0)) * sizeof(double);
+    const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / per));
+    int nb = 1;
+    while (k0 + nb < ms && nb < nbmax && ss_state_dim(lts[k0 + nb].kind) == D) ++nb;
+    Buf<double> agg((size_t)nb * ss_fwd_agg_elems(D, nch)), part((size_t)nb * nch), lmld(nb), state, bagg;
+    if (smooth) { state = Buf<double>((size_t)nb * comps * n); bagg = Buf<double>((size_t)nb * ss_bwd_agg_elems(D, nch)); }
+    SSArgs a{};
+    a.x = xd; a.n = n; a.chunk = chunk; a.nch = nch;
+    a.agg = agg.p; a.bagg = bagg.p; a.part = part.p;
+    a.fmean = fmean ? fmean + (size_t)k0 * n : nullptr; a.fvar = fvar ? fvar + (size_t)k0 * n : nullptr;
+    a.state = state.p; a.state_stride = comps * n;
+    a.smean = smooth ? smean + (size_t)k0 * n : nullptr; a.svar = (smooth && svar) ? svar + (size_t)k0 * n : nullptr;
+    for (int j = 0; j < nb; ++j) {
+      const Latent& L = lts[k0 + j];
+      a.lat[j].var = L.terms[0].ev.var; a.lat[j].inv_ls = L.terms[0].ev.inv_ls; a.lat[j].mean = add_mean ? L.mean : 0.0;
+      a.lat[j].w = w + (size_t)(k0 + j) * n; a.lat[j].r = r + (size_t)(k0 + j) * n;
+    }
+    launch_ss_filter(a, D, nb, lmld.p, st0);
+    if (smooth) launch_ss_smooth(a, D, nb, st0);
+    HIPCHK(hipGetLastError());
+    if (lml) HIPCHK(hipMemcpyAsync(lml + k0, lmld.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));          // the buffers above go back to the pool
+    k0 += nb;
+  }
+  return LMM_OK;
+}
+
+// The OILMM front end of the state-space path: per latent of the shard and point, the pseudo-observation r = z_t[l] - mean_l and its
+// noise variance w = sigma2 (G_t^-1)_ll of the missing-data projection (missing_front; without NaN that is (T y)_l - mean_l and
+// sigma2 / S_l), with w = +Inf and r = 0 at the points without any observed output, which the front end itself never sees.
+struct SSFront {
+  Buf<double> w, r;        // [l1 - l0][n]
+  double reg = 0.0;        // sum_t r_t over the points with observations
+};
+static int ss_front(const double* yd, int n, int p, const double* U, const double* S, int m, double s2, const Latent* lts, int l0, int l1,
+                    SSFront& Fr) {
+  hipStream_t st0 = g.streams[0];
+  const int nw = (p + 63) / 64, ms = l1 - l0;
+  std::vector<int> hpt(n), idx;
+  {
+    Buf<unsigned long long> masks((size_t)n * nw);
+    Buf<int> pt(n);
+    launch_missing_masks(yd, n, p, masks.p, pt.p, st0);
+    HIPCHK(hipMemcpyAsync(hpt.data(), pt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));
+  }
+  for (int t = 0; t < n; ++t) {
+    if (hpt[t] > 0 && hpt[t] < m) {
+      g.err_latent = -1; g.err_info = t;
+      return fail(LMM_ERR_UNSUPPORTED, "missing data: point %d observes %d outputs, fewer than the m = %d latent processes", t, hpt[t], m);
+    }
+    if (hpt[t] > 0) idx.push_back(t);
+  }
+  const int nobs = (int)idx.size();
+  std::vector<double> means(m);
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  MissingFront F;
+  if (nobs == n) {
+    if (int rc = missing_front(yd, n, p, U, S, m, s2, means.data(), l0, l1, false, F)) return rc;
+    Fr.w = std::move(F.nv); Fr.r = std::move(F.z);
+    Fr.reg = F.reg(n, m, s2);
+    return LMM_OK;
+  }
+  Fr.w = Buf<double>((size_t)n * std::max(ms, 1)); Fr.r = Buf<double>((size_t)n * std::max(ms, 1));
+  for (int k = 0; k < ms; ++k) {
+    launch_fill(Fr.w.p + (size_t)k * n, n, INFINITY, st0);
+    launch_fill(Fr.r.p + (size_t)k * n, n, 0.0, st0);
+  }
+  if (nobs > 0) {
+    Buf<int> idxd(nobs);
+    Buf<double> yc((size_t)nobs * p);
+    HIPCHK(hipMemcpyAsync(idxd.p, idx.data(), (size_t)nobs * sizeof(int), hipMemcpyHostToDevice, st0));
+    launch_ss_gather_rows(yd, n, p, idxd.p, nobs, yc.p, st0);
+    if (int rc = missing_front(yc.p, nobs, p, U, S, m, s2, means.data(), l0, l1, false, F)) {
+      if (rc == LMM_ERR_NOT_PD && g.err_info >= 0 && g.err_info < nobs) {      // the front end numbered the points it saw
+        g.err_info = idx[g.err_info];
+        return fail(LMM_ERR_NOT_PD, "PosDefException: H_t' H_t of point %d is not positive definite over its observed outputs", g.err_info);
+      }
+      return rc;
+    }
+    if (ms > 0) {
+      launch_ss_scatter_rows(F.nv.p, n, ms, idxd.p, nobs, Fr.w.p, st0);
+      launch_ss_scatter_rows(F.z.p, n, ms, idxd.p, nobs, Fr.r.p, st0);
+    }
+    Fr.reg = F.reg(nobs, m, s2);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));            // idxd, yc and F's buffers go back to the pool
+  return LMM_OK;
+}
+
+#define LMM_SS_ARGCHECK(extra)                                                                                                   \
+  LMM_MISSING_ARGCHECK(!x || (extra));                                                                                            \
+  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");             \
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))")
+
+int lmm_oilmm_logpdf_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                                const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  LMM_SS_ARGCHECK(!out);
+  RESOLVE(gps, m, 1);
+  if (int rc = ss_check_latents(lts, m)) return rc;
+  hipStream_t st0 = g.streams[0];
+  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
+  if (int rc = ss_check_sorted(xd.p, n)) return rc;
+  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
+  SSFront Fr;
+  if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr)) return rc;
+  std::vector<double> lml(std::max(ms, 1), 0.0);
+  if (int rc = ss_core(xd.p, n, lts + l0, ms, Fr.w.p, Fr.r.p, 0, lml.data(), nullptr, nullptr, nullptr, nullptr, false)) return rc;
+  double total = 0.0;
+  for (int k = 0; k < ms; ++k) total += lml[k];
+  if (with_regulariser) total += Fr.reg;
+  *out = total;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_oilmm_mean_and_var_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                      double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise,
+                                      double* mean_out, double* var_out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  LMM_SS_ARGCHECK(!mean_out);
+  RESOLVE(gps, m, 1);
+  if (int rc = ss_check_latents(lts, m)) return rc;
+  hipStream_t st0 = g.streams[0];
+  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
+  if (int rc = ss_check_sorted(xd.p, n)) return rc;
+  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
+  SSFront Fr;
+  if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr)) return rc;
+  Buf<double> ml((size_t)n * std::max(ms, 1)), vl((size_t)n * std::max(ms, 1));
+  if (int rc = ss_core(xd.p, n, lts + l0, ms, Fr.w.p, Fr.r.p, 0, nullptr, nullptr, nullptr, ml.p, vl.p, true)) return rc;
+  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
+  for (int k = 0; k < ms; ++k)
+    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
+  Uploaded Hd(Hs, st0);
+  DevOut mo(mean_out, (size_t)n * p), vo(var_out, (size_t)n * p);
+  // the mixing of lmm_oilmm_mean_and_var (reference src/oilmm.jl:69,72)
+  mix_marginals(ml.p, n, ms, Hd.buf.p, p, 1, 0.0, 0.0, mo.p, st0);
+  if (var_out) mix_marginals(vl.p, n, ms, Hd.buf.p, p, 2, kDefaultJit.default_jitter, add_noise ? sigma2 : 0.0, vo.p, st0);
+  mo.finish(st0); vo.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Building blocks for tests: ONE latent from device pointers, per-point noise w (+Inf: unobserved) and data r; the latent's mean is
+// not read (r is the residual).  chunk: points per thread (0: the library's plan).
+static int ss_dev_block(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* fmean,
+                        double* fvar, double* lml_dev, double* smean, double* svar) {
+  if (n <= 0 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  RESOLVE(gp, 1, 1);
+  if (int rc = ss_check_latents(lts, 1)) return rc;
+  if (int rc = ss_check_sorted(x, n)) return rc;
+  double lml = 0.0;
+  if (int rc = ss_core(x, n, lts, 1, w, r, chunk, &lml, fmean, fvar, smean, svar, false)) return rc;
+  if (lml_dev) {
+    HIPCHK(hipMemcpyAsync(lml_dev, &lml, sizeof(double), hipMemcpyHostToDevice, g.streams[0]));
+    HIPCHK(hipStreamSynchronize(g.streams[0]));
+  }
+  return LMM_OK;
+}
+
+int lmm_dev_statespace_filter(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* fmean,
+                              double* fvar, double* lml) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !gp || !w || !r || !fmean || !fvar || !lml) return fail(LMM_ERR_ARG, "bad arguments");
+  return ss_dev_block(x, n, gp, w, r, chunk, fmean, fvar, lml, nullptr, nullptr);
+  LMM_CATCH
+}
+
+int lmm_dev_statespace_smooth(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* smean,
+                              double* svar) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !gp || !w || !r || !smean || !svar) return fail(LMM_ERR_ARG, "bad arguments");
+  return ss_dev_block(x, n, gp, w, r, chunk, nullptr, nullptr, nullptr, smean, svar);
   LMM_CATCH
 }
 

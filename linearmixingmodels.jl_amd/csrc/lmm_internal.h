@@ -310,6 +310,35 @@ void launch_sparse_beta(const BatchPtr& R, int ld, int M, const BatchPtr& c, con
 // PB.p[l] = (Ki - Si - beta beta') / 2 (both triangles); lower(Si.p[l]) <- -2 PB + sym(T2)
 void launch_sparse_phibar(const BatchPtr& Ki, const BatchPtr& Si, const BatchPtr& T2, const BatchPtr& beta, const BatchPtr& PB, int ld,
                           int M, int nb, hipStream_t st);
+// State-space inference for Matern latents over a one-dimensional input (lmm_kernels_ss.hip).  All Float64.
+// One latent of a launch: variance, 1 / lengthscale, the constant added to the smoothed means, per-point noise w (device, n values;
+// +Inf: unobserved) and data r (device, n values).
+struct SSLat { double var, inv_ls, mean; const double* w; const double* r; };
+struct SSArgs {
+  const double* x; int n, chunk, nch;         // sorted inputs (device); points per thread; nch = ceil(n / chunk) threads per latent
+  double* agg;                                // nb * ss_fwd_agg_elems(D, nch) doubles: the forward aggregates and the scan's levels
+  double* bagg;                               // nb * ss_bwd_agg_elems(D, nch) doubles (smoother only)
+  double* fmean; double* fvar;                // filtered first-component mean / variance, [latent][n] (nullptr: not written)
+  double* state; size_t state_stride;         // filtered states, [latent][ss_state_comps(D)][n] (nullptr: not kept); doubles per latent
+  double* part;                               // nb * nch log-density partials
+  double* smean; double* svar;                // smoothed first-component mean (+ lat.mean) / variance, [latent][n]
+  SSLat lat[LMM_MAX_BATCH];
+};
+static_assert(sizeof(SSArgs) <= 4096, "SSArgs is passed by value: kernel arguments are limited to 4096 bytes");
+int ss_state_dim(int kind);                   // 1 / 2 / 3 for Matern12 / 32 / 52, 0 for every other kind
+int ss_state_comps(int D);                    // doubles of one filtered state: D + D (D + 1) / 2
+int ss_default_chunk(int n);                  // the library's plan: a function of n alone
+size_t ss_fwd_agg_elems(int D, int nch);      // per latent
+size_t ss_bwd_agg_elems(int D, int nch);
+// fold, scan, filter (and, lml != nullptr, lml[l] = latent l's log density) of nb latents with state dimension D
+void launch_ss_filter(const SSArgs& a, int D, int nb, double* lml, hipStream_t st);
+// the same in reverse over the filtered states a.state: smoothed marginals into a.smean / a.svar
+void launch_ss_smooth(const SSArgs& a, int D, int nb, hipStream_t st);
+// *flag (preset to INT_MAX) = the first t with !(x_t >= x_{t-1})
+void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st);
+// rows idx[0 .. nsel) of an n x p column-major matrix into an nsel x p one, and back
+void launch_ss_gather_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st);
+void launch_ss_scatter_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st);
 void launch_atb(const double* X, int ldx, const double* Z, int ldz, int n, int na, int nb, double* out, hipStream_t st);
 void launch_fill(double* p, int n, double v, hipStream_t st);
 void launch_reorder(const double* in, int n, int p, int to_outputs, double* out, hipStream_t st);

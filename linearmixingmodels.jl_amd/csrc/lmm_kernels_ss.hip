@@ -1,0 +1,319 @@
+// lmm_kernels_ss.hip -- linear-time state-space inference for Matern12 / 32 / 52 latents over a one-dimensional input:
+// the Kalman filter and the Rauch-Tung-Striebel smoother as parallel scans over the n points.  Float64 only; built WITHOUT
+// -amdgpu-mfma-vgpr-form=1 (no MFMA here).  Three phases per direction, no atomics, results depend only on (arguments, chunk):
+//   1. ss_fold_kernel / ss_bfold_kernel: each thread folds the scan elements of its `chunk` consecutive points into one aggregate;
+//   2. ss_scan_kernel (+ ss_addprefix_kernel): the aggregates are scanned, 128 per workgroup through LDS (Hillis-Steele); with more
+//      aggregates than one workgroup takes, the workgroups' totals are scanned by the same kernel (recursion on the host) and applied;
+//   3. ss_filter_kernel / ss_rts_kernel: each thread restarts the ordinary recursion from its prefix (suffix) state over its run and
+//      writes the marginals; the filter's log-density partials are added in thread order by ss_finish_kernel.
+// A(dt) and Q(dt) are evaluated on the fly from x_t - x_{t-1}; blockIdx.z is the latent.  Every latent of a launch has the same state
+// dimension D (the template argument).
+#include "lmm_internal.h"
+#include "lmm_statespace.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int SS_THREADS = 256;      // fold / filter / rts: one thread per chunk
+constexpr int SS_SCAN = 128;         // aggregates per workgroup of the scan (one per thread; 128 SSFwd<3> are 33 KiB of LDS)
+
+template <int D>
+__device__ __forceinline__ SSModel<D> ss_lat_model(const SSLat& L) {
+  SSModel<D> M;
+  ss_model<D>(L.var, L.inv_ls, M);
+  return M;
+}
+
+template <int D>
+__global__ __launch_bounds__(SS_THREADS) void ss_fold_kernel(SSArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const SSLat& L = a.lat[z];
+  const SSModel<D> M = ss_lat_model<D>(L);
+  const long long t0 = (long long)j * a.chunk;
+  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  SSFwd<D> acc, el;
+  double xp = a.x[t0];
+  ss_fwd_element<D>(M, t0 == 0, t0 == 0 ? 0.0 : xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
+  for (long long t = t0 + 1; t < t1; ++t) {
+    const double xt = a.x[t];
+    ss_fwd_element<D>(M, false, xt - xp, L.w[t], L.r[t], el);
+    ss_fwd_combine<D>(acc, el, acc);
+    xp = xt;
+  }
+  reinterpret_cast<SSFwd<D>*>(a.agg)[(size_t)z * a.nch + j] = acc;
+}
+
+struct FwdOp {
+  template <int D> static __device__ __forceinline__ void combine(const SSFwd<D>& a, const SSFwd<D>& b, SSFwd<D>& o) { ss_fwd_combine<D>(a, b, o); }
+};
+struct BwdOp {
+  template <int D> static __device__ __forceinline__ void combine(const SSBwd<D>& a, const SSBwd<D>& b, SSBwd<D>& o) { ss_bwd_combine<D>(a, b, o); }
+};
+
+// Inclusive scan of N items per latent, SS_SCAN per workgroup.  REV: a suffix scan -- logical position q is item N - 1 - q, and the
+// earlier-in-time operand of the combine is the item itself.  totals (nullptr: none): the workgroups' totals, stored like the items
+// (logical workgroup k at nblk - 1 - k when REV), so the same kernel scans them.
+template <int D, typename T, typename Op, bool REV>
+__global__ __launch_bounds__(SS_SCAN) void ss_scan_kernel(T* items, int N, T* totals) {
+  __shared__ T sh[SS_SCAN];
+  const int tid = threadIdx.x, q = blockIdx.x * SS_SCAN + tid, z = blockIdx.z;
+  const int nblk = gridDim.x;
+  const bool live = q < N;
+  const size_t i = (size_t)z * N + (REV ? N - 1 - q : q);
+  T mine;
+  if (live) { mine = items[i]; sh[tid] = mine; }
+  __syncthreads();
+  for (int off = 1; off < SS_SCAN; off <<= 1) {
+    const bool take = live && tid >= off;
+    T other;
+    if (take) other = sh[tid - off];
+    __syncthreads();
+    if (take) {
+      if (REV) Op::template combine<D>(mine, other, mine);
+      else Op::template combine<D>(other, mine, mine);
+      sh[tid] = mine;
+    }
+    __syncthreads();
+  }
+  if (live) {
+    items[i] = mine;
+    const int last = (N - blockIdx.x * SS_SCAN < SS_SCAN ? N - blockIdx.x * SS_SCAN : SS_SCAN) - 1;
+    if (totals != nullptr && tid == last) totals[(size_t)z * nblk + (REV ? nblk - 1 - (int)blockIdx.x : (int)blockIdx.x)] = mine;
+  }
+}
+
+// items of logical workgroup k >= 1 take the scanned total of workgroup k - 1 in front
+template <int D, typename T, typename Op, bool REV>
+__global__ __launch_bounds__(SS_SCAN) void ss_addprefix_kernel(T* items, int N, const T* totals) {
+  const int blk = blockIdx.x + 1, q = blk * SS_SCAN + threadIdx.x, z = blockIdx.z;
+  const int nblk = gridDim.x + 1;
+  if (q >= N) return;
+  const size_t i = (size_t)z * N + (REV ? N - 1 - q : q);
+  const T pre = totals[(size_t)z * nblk + (REV ? nblk - 1 - (blk - 1) : blk - 1)];
+  T mine = items[i];
+  if (REV) Op::template combine<D>(mine, pre, mine);
+  else Op::template combine<D>(pre, mine, mine);
+  items[i] = mine;
+}
+
+template <int D, typename T, typename Op, bool REV>
+void scan_levels(T* items, int N, int nb, T* scratch, hipStream_t st) {
+  const int nblk = (N + SS_SCAN - 1) / SS_SCAN;
+  if (nblk == 1) {
+    hipLaunchKernelGGL((ss_scan_kernel<D, T, Op, REV>), dim3(1, 1, nb), dim3(SS_SCAN), 0, st, items, N, (T*)nullptr);
+    return;
+  }
+  hipLaunchKernelGGL((ss_scan_kernel<D, T, Op, REV>), dim3(nblk, 1, nb), dim3(SS_SCAN), 0, st, items, N, scratch);
+  scan_levels<D, T, Op, REV>(scratch, nblk, nb, scratch + (size_t)nb * nblk, st);
+  hipLaunchKernelGGL((ss_addprefix_kernel<D, T, Op, REV>), dim3(nblk - 1, 1, nb), dim3(SS_SCAN), 0, st, items, N, (const T*)scratch);
+}
+
+// packed index of the symmetric entry (i, j), i <= j, behind the D mean components of a filtered state
+__host__ __device__ constexpr int ss_sym_at(int D, int i, int j) { return D + i * D - i * (i - 1) / 2 + (j - i); }
+
+template <int D>
+__global__ __launch_bounds__(SS_THREADS) void ss_filter_kernel(SSArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const SSLat& L = a.lat[z];
+  const SSModel<D> M = ss_lat_model<D>(L);
+  const long long t0 = (long long)j * a.chunk;
+  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  double m[D], P[D][D];
+  if (j == 0) {
+    for (int i = 0; i < D; ++i) {
+      m[i] = 0.0;
+      for (int k = 0; k < D; ++k) P[i][k] = M.Pinf[i][k];
+    }
+  } else {
+    const SSFwd<D>& pre = reinterpret_cast<const SSFwd<D>*>(a.agg)[(size_t)z * a.nch + j - 1];
+    for (int i = 0; i < D; ++i) {
+      m[i] = pre.b[i];
+      for (int k = 0; k < D; ++k) P[i][k] = pre.C[i][k];
+    }
+  }
+  double* fm = a.fmean ? a.fmean + (size_t)z * a.n : nullptr;
+  double* fv = a.fvar ? a.fvar + (size_t)z * a.n : nullptr;
+  double* stt = a.state ? a.state + (size_t)z * a.state_stride : nullptr;
+  double lp = 0.0;
+  double xp = t0 == 0 ? a.x[0] : a.x[t0 - 1];
+  for (long long t = t0; t < t1; ++t) {
+    const double xt = a.x[t];
+    lp += ss_filter_step<D>(M, xt - xp, L.w[t], L.r[t], m, P);
+    xp = xt;
+    if (fm) fm[t] = m[0];
+    if (fv) fv[t] = P[0][0];
+    if (stt) {
+      for (int i = 0; i < D; ++i) {
+        stt[(size_t)i * a.n + t] = m[i];
+        for (int k = i; k < D; ++k) stt[(size_t)ss_sym_at(D, i, k) * a.n + t] = P[i][k];
+      }
+    }
+  }
+  a.part[(size_t)z * a.nch + j] = lp;
+}
+
+// lml[z] = the nch partials of latent z: each thread adds a contiguous strip in order, thread 0 adds the strips in thread order
+__global__ __launch_bounds__(SS_THREADS) void ss_finish_kernel(const double* __restrict__ part, int nch, double* __restrict__ lml) {
+  __shared__ double sh[SS_THREADS];
+  const int z = blockIdx.x, per = (nch + SS_THREADS - 1) / SS_THREADS;
+  const int k0 = threadIdx.x * per, k1 = k0 + per < nch ? k0 + per : nch;
+  double s = 0.0;
+  for (int k = k0; k < k1; ++k) s += part[(size_t)z * nch + k];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int k = 0; k < SS_THREADS; ++k) tot += sh[k];
+    lml[z] = tot;
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void ss_load_state(const double* stt, int n, long long t, double m[D], double P[D][D]) {
+  for (int i = 0; i < D; ++i) {
+    m[i] = stt[(size_t)i * n + t];
+    for (int k = i; k < D; ++k) P[i][k] = P[k][i] = stt[(size_t)ss_sym_at(D, i, k) * n + t];
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(SS_THREADS) void ss_bfold_kernel(SSArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const SSModel<D> M = ss_lat_model<D>(a.lat[z]);
+  const long long t0 = (long long)j * a.chunk;
+  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  const double* stt = a.state + (size_t)z * a.state_stride;
+  SSBwd<D> acc, el;
+  double m[D], P[D][D];
+  for (long long t = t0; t < t1; ++t) {
+    const bool last = t == a.n - 1;
+    ss_load_state<D>(stt, a.n, t, m, P);
+    ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, t == t0 ? acc : el);
+    if (t > t0) ss_bwd_combine<D>(acc, el, acc);
+  }
+  reinterpret_cast<SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j] = acc;
+}
+
+template <int D>
+__global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const SSLat& L = a.lat[z];
+  const SSModel<D> M = ss_lat_model<D>(L);
+  const long long t0 = (long long)j * a.chunk;
+  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  const double* stt = a.state + (size_t)z * a.state_stride;
+  double ms[D], Ps[D][D];
+  for (int i = 0; i < D; ++i) {       // the last chunk has no successor: its first element has E = 0 and ignores this state
+    ms[i] = 0.0;
+    for (int k = 0; k < D; ++k) Ps[i][k] = 0.0;
+  }
+  if (j + 1 < a.nch) {
+    const SSBwd<D>& suf = reinterpret_cast<const SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j + 1];
+    for (int i = 0; i < D; ++i) {
+      ms[i] = suf.g[i];
+      for (int k = 0; k < D; ++k) Ps[i][k] = suf.L[i][k];
+    }
+  }
+  double* sm = a.smean + (size_t)z * a.n;
+  double* sv = a.svar ? a.svar + (size_t)z * a.n : nullptr;
+  SSBwd<D> el;
+  double m[D], P[D][D];
+  for (long long t = t1 - 1; t >= t0; --t) {
+    const bool last = t == a.n - 1;
+    ss_load_state<D>(stt, a.n, t, m, P);
+    ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, el);
+    ss_rts_step<D>(el, ms, Ps);
+    sm[t] = ms[0] + L.mean;
+    if (sv) sv[t] = Ps[0][0];
+  }
+}
+
+// *flag = the smallest t >= 1 with !(x_t >= x_{t-1}) (a NaN counts), left at its initial value (INT_MAX) when x is non-decreasing.
+// atomicMin on an index: the result does not depend on the order of arrival.
+__global__ __launch_bounds__(256) void ss_sorted_kernel(const double* __restrict__ x, int n, int* flag) {
+  for (long long t = 1 + blockIdx.x * 256ll + threadIdx.x; t < n; t += (long long)gridDim.x * 256)
+    if (!(x[t] >= x[t - 1])) atomicMin(flag, (int)t);
+}
+
+// out[j + o nsel] = in[idx[j] + o n]: the selected rows of an n x p column-major matrix
+__global__ __launch_bounds__(256) void ss_gather_rows_kernel(const double* __restrict__ in, int n, const int* __restrict__ idx, int nsel,
+                                                             double* __restrict__ out) {
+  const int j = blockIdx.x * 256 + threadIdx.x, o = blockIdx.y;
+  if (j < nsel) out[j + (size_t)o * nsel] = in[idx[j] + (size_t)o * n];
+}
+// out[idx[j] + o n] = in[j + o nsel]
+__global__ __launch_bounds__(256) void ss_scatter_rows_kernel(const double* __restrict__ in, int n, const int* __restrict__ idx, int nsel,
+                                                              double* __restrict__ out) {
+  const int j = blockIdx.x * 256 + threadIdx.x, o = blockIdx.y;
+  if (j < nsel) out[idx[j] + (size_t)o * n] = in[j + (size_t)o * nsel];
+}
+
+size_t scan_items(int nch) {         // items of every level below the first
+  size_t tot = 0;
+  int N = nch;
+  while (N > SS_SCAN) { N = (N + SS_SCAN - 1) / SS_SCAN; tot += N; }
+  return tot;
+}
+
+template <int D>
+void filter_D(const SSArgs& a, int nb, double* lml, hipStream_t st) {
+  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
+  hipLaunchKernelGGL(ss_fold_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  SSFwd<D>* agg = reinterpret_cast<SSFwd<D>*>(a.agg);
+  scan_levels<D, SSFwd<D>, FwdOp, false>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
+  hipLaunchKernelGGL(ss_filter_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  if (lml) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
+}
+
+template <int D>
+void smooth_D(const SSArgs& a, int nb, hipStream_t st) {
+  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
+  hipLaunchKernelGGL(ss_bfold_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  SSBwd<D>* agg = reinterpret_cast<SSBwd<D>*>(a.bagg);
+  scan_levels<D, SSBwd<D>, BwdOp, true>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
+  hipLaunchKernelGGL(ss_rts_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+}
+
+}  // namespace
+
+int ss_state_dim(int kind) { return kind == LMM_KERNEL_MATERN12 ? 1 : kind == LMM_KERNEL_MATERN32 ? 2 : kind == LMM_KERNEL_MATERN52 ? 3 : 0; }
+int ss_state_comps(int D) { return D + D * (D + 1) / 2; }
+int ss_default_chunk(int n) { return n <= 4096 ? 16 : 64; }
+size_t ss_fwd_agg_elems(int D, int nch) {
+  const size_t e = D == 1 ? sizeof(SSFwd<1>) : D == 2 ? sizeof(SSFwd<2>) : sizeof(SSFwd<3>);
+  return ((size_t)nch + scan_items(nch)) * (e / sizeof(double));
+}
+size_t ss_bwd_agg_elems(int D, int nch) {
+  const size_t e = D == 1 ? sizeof(SSBwd<1>) : D == 2 ? sizeof(SSBwd<2>) : sizeof(SSBwd<3>);
+  return ((size_t)nch + scan_items(nch)) * (e / sizeof(double));
+}
+
+void launch_ss_filter(const SSArgs& a, int D, int nb, double* lml, hipStream_t st) {
+  if (D == 1) filter_D<1>(a, nb, lml, st);
+  else if (D == 2) filter_D<2>(a, nb, lml, st);
+  else filter_D<3>(a, nb, lml, st);
+}
+
+void launch_ss_smooth(const SSArgs& a, int D, int nb, hipStream_t st) {
+  if (D == 1) smooth_D<1>(a, nb, st);
+  else if (D == 2) smooth_D<2>(a, nb, st);
+  else smooth_D<3>(a, nb, st);
+}
+
+void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st) {
+  const int blocks = (int)std::min<long long>(2048, ((long long)n + 255) / 256);
+  hipLaunchKernelGGL(ss_sorted_kernel, dim3(blocks), dim3(256), 0, st, x, n, flag);
+}
+
+void launch_ss_gather_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(ss_gather_rows_kernel, dim3((nsel + 255) / 256, p), dim3(256), 0, st, in, n, idx, nsel, out);
+}
+
+void launch_ss_scatter_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(ss_scatter_rows_kernel, dim3((nsel + 255) / 256, p), dim3(256), 0, st, in, n, idx, nsel, out);
+}

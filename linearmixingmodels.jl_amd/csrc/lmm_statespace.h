@@ -1,0 +1,326 @@
+// lmm_statespace.h -- the per-point arithmetic of the state-space (Kalman / RTS) path for Matern latents over a one-dimensional input
+// (include/lmm_hip.h "state space").  Everything is templated on the state dimension D (Matern12 / 32 / 52: 1 / 2 / 3)
+// and fully unrolled, so every matrix lives in registers.  The functions are __host__ __device__: lmm_kernels_ss.hip runs them on the
+// GPU, and a host build of the same text can be stepped through on the CPU.
+//
+// Model: F is the companion matrix of (s + lam)^D, N = F + lam I is nilpotent (N^D = 0), A(dt) = exp(-lam dt) (I + N dt + N^2 dt^2 / 2),
+// Q(dt) = Pinf - A Pinf A', prior state N(0, Pinf), observation h = e_1'.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#define SS_HD __host__ __device__ __forceinline__
+
+template <int D>
+struct SSModel {
+  double lam;
+  double N[D][D], N2[D][D], Pinf[D][D];
+};
+
+// lam = sqrt(2 nu) / lengthscale and the stationary covariance of (f, f', f'') for variance v
+template <int D>
+SS_HD void ss_model(double var, double inv_ls, SSModel<D>& M) {
+  const double lam = (D == 1 ? 1.0 : D == 2 ? 1.7320508075688772 : 2.23606797749979) * inv_ls;
+  M.lam = lam;
+  double F[D][D];
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) { F[i][j] = (j == i + 1) ? 1.0 : 0.0; M.Pinf[i][j] = 0.0; }
+  if (D == 1) F[0][0] = -lam;
+  if (D == 2) { F[D - 1][0] = -lam * lam; F[D - 1][D - 1] = -2.0 * lam; }
+  if (D == 3) { F[D - 1][0] = -lam * lam * lam; F[D - 1][D == 3 ? 1 : 0] = -3.0 * lam * lam; F[D - 1][D - 1] = -3.0 * lam; }
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) M.N[i][j] = F[i][j] + (i == j ? lam : 0.0);
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < D; ++k) s += M.N[i][k] * M.N[k][j];
+      M.N2[i][j] = s;
+    }
+  const double l2 = lam * lam;
+  M.Pinf[0][0] = var;
+  if (D == 2) M.Pinf[D - 1][D - 1] = l2 * var;
+  if (D == 3) {
+    M.Pinf[0][D - 1] = M.Pinf[D - 1][0] = -l2 * var / 3.0;
+    M.Pinf[D == 3 ? 1 : 0][D == 3 ? 1 : 0] = l2 * var / 3.0;
+    M.Pinf[D - 1][D - 1] = l2 * l2 * var;
+  }
+}
+
+// A(dt) and Q(dt); dt = 0 gives A = I and Q = 0 exactly
+template <int D>
+SS_HD void ss_AQ(const SSModel<D>& M, double dt, double A[D][D], double Q[D][D]) {
+  const double e = exp(-M.lam * dt), h = 0.5 * dt * dt;
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) A[i][j] = e * ((i == j ? 1.0 : 0.0) + M.N[i][j] * dt + (D > 2 ? M.N2[i][j] * h : 0.0));
+  double T[D][D];
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < D; ++k) s += A[i][k] * M.Pinf[k][j];
+      T[i][j] = s;
+    }
+  for (int i = 0; i < D; ++i)
+    for (int j = i; j < D; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < D; ++k) s += T[i][k] * A[j][k];
+      Q[i][j] = Q[j][i] = M.Pinf[i][j] - s;
+    }
+}
+
+template <int D>
+SS_HD void ss_mm(const double X[D][D], const double Y[D][D], double Z[D][D]) {      // Z = X Y
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < D; ++k) s += X[i][k] * Y[k][j];
+      Z[i][j] = s;
+    }
+}
+template <int D>
+SS_HD void ss_mmt(const double X[D][D], const double Y[D][D], double Z[D][D]) {     // Z = X Y'
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < D; ++k) s += X[i][k] * Y[j][k];
+      Z[i][j] = s;
+    }
+}
+template <int D>
+SS_HD void ss_sym(double X[D][D]) {
+  for (int i = 0; i < D; ++i)
+    for (int j = i + 1; j < D; ++j) X[i][j] = X[j][i] = 0.5 * (X[i][j] + X[j][i]);
+}
+
+// X^-1 of a general D x D matrix by cofactors (relative accuracy is invariant under the diagonal scalings that separate f, f', f'')
+template <int D>
+SS_HD void ss_inv(const double X[D][D], double Y[D][D]) {
+  if (D == 1) { Y[0][0] = 1.0 / X[0][0]; return; }
+  if (D == 2) {
+    const double a = X[0][0], b = X[0][D - 1], c = X[D - 1][0], d = X[D - 1][D - 1];
+    const double r = 1.0 / (a * d - b * c);
+    Y[0][0] = d * r; Y[0][D - 1] = -b * r; Y[D - 1][0] = -c * r; Y[D - 1][D - 1] = a * r;
+    return;
+  }
+  double Cf[D][D];
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      const int i1 = (i + 1) % D, i2 = (i + 2) % D, j1 = (j + 1) % D, j2 = (j + 2) % D;
+      Cf[i][j] = X[i1][j1] * X[i2][j2] - X[i1][j2] * X[i2][j1];      // cofactor (cyclic indices carry the sign)
+    }
+  double det = 0.0;
+  for (int j = 0; j < D; ++j) det += X[0][j] * Cf[0][j];
+  const double r = 1.0 / det;
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) Y[i][j] = Cf[j][i] * r;
+}
+
+// X^-1 of a symmetric positive definite matrix through its Cholesky factor
+template <int D>
+SS_HD void ss_inv_spd(const double X[D][D], double Y[D][D]) {
+  double L[D][D], W[D][D];
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) { L[i][j] = 0.0; W[i][j] = 0.0; }
+  for (int j = 0; j < D; ++j) {
+    double s = X[j][j];
+    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+    const double dj = sqrt(s);
+    L[j][j] = dj;
+    for (int i = j + 1; i < D; ++i) {
+      double t = X[i][j];
+      for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+      L[i][j] = t / dj;
+    }
+  }
+  for (int j = 0; j < D; ++j) {               // W = L^-1 (lower)
+    W[j][j] = 1.0 / L[j][j];
+    for (int i = j + 1; i < D; ++i) {
+      double t = 0.0;
+      for (int k = j; k < i; ++k) t -= L[i][k] * W[k][j];
+      W[i][j] = t / L[i][i];
+    }
+  }
+  for (int i = 0; i < D; ++i)
+    for (int j = i; j < D; ++j) {
+      double s = 0.0;
+      for (int k = j; k < D; ++k) s += W[k][i] * W[k][j];
+      Y[i][j] = Y[j][i] = s;
+    }
+}
+
+// ---- forward (filtering) elements of Sarkka & Garcia-Fernandez, "Temporal parallelization of Bayesian smoothers" ------------------
+template <int D>
+struct SSFwd { double A[D][D], b[D], C[D][D], eta[D], J[D][D]; };
+
+// The element of one point.  first: the prior takes the place of the transition (A = 0, Q = Pinf).  w = +Inf: unobserved.
+template <int D>
+SS_HD void ss_fwd_element(const SSModel<D>& M, bool first, double dt, double w, double r, SSFwd<D>& e) {
+  double A[D][D], Q[D][D];
+  if (first) {
+    for (int i = 0; i < D; ++i)
+      for (int j = 0; j < D; ++j) { A[i][j] = 0.0; Q[i][j] = M.Pinf[i][j]; }
+  } else ss_AQ<D>(M, dt, A, Q);
+  if (!(w < INFINITY)) {
+    for (int i = 0; i < D; ++i) {
+      e.b[i] = 0.0; e.eta[i] = 0.0;
+      for (int j = 0; j < D; ++j) { e.A[i][j] = A[i][j]; e.C[i][j] = Q[i][j]; e.J[i][j] = 0.0; }
+    }
+    return;
+  }
+  const double Sinv = 1.0 / (Q[0][0] + w);
+  for (int i = 0; i < D; ++i) {
+    const double K = Q[i][0] * Sinv;
+    e.b[i] = K * r;
+    e.eta[i] = A[0][i] * r * Sinv;
+    for (int j = 0; j < D; ++j) {
+      e.A[i][j] = A[i][j] - K * A[0][j];
+      e.C[i][j] = Q[i][j] - K * Q[0][j];
+      e.J[i][j] = A[0][i] * A[0][j] * Sinv;
+    }
+  }
+}
+
+// out = a (.) b with a the earlier run; out may alias a or b
+template <int D>
+SS_HD void ss_fwd_combine(const SSFwd<D>& a, const SSFwd<D>& b, SSFwd<D>& out) {
+  double T[D][D], Ti[D][D], Mx[D][D], Mp[D][D], X[D][D];
+  ss_mm<D>(a.C, b.J, T);
+  for (int i = 0; i < D; ++i) T[i][i] += 1.0;
+  ss_inv<D>(T, Ti);
+  ss_mm<D>(b.A, Ti, Mx);                      // M = A_j (I + C_i J_j)^-1
+  ss_mm<D>(Ti, a.A, X);                       // M' = A_i' (I + J_j C_i)^-1 = ((I + C_i J_j)^-1 A_i)'
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) Mp[i][j] = X[j][i];
+  SSFwd<D> o;
+  ss_mm<D>(Mx, a.A, o.A);
+  double u[D], v[D];
+  for (int i = 0; i < D; ++i) {
+    double s = a.b[i], t = b.eta[i];
+    for (int k = 0; k < D; ++k) { s += a.C[i][k] * b.eta[k]; t -= b.J[i][k] * a.b[k]; }
+    u[i] = s; v[i] = t;
+  }
+  for (int i = 0; i < D; ++i) {
+    double s = b.b[i], t = a.eta[i];
+    for (int k = 0; k < D; ++k) { s += Mx[i][k] * u[k]; t += Mp[i][k] * v[k]; }
+    o.b[i] = s; o.eta[i] = t;
+  }
+  ss_mm<D>(Mx, a.C, X);
+  ss_mmt<D>(X, b.A, o.C);
+  ss_mm<D>(Mp, b.J, X);
+  ss_mm<D>(X, a.A, o.J);
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) { o.C[i][j] += b.C[i][j]; o.J[i][j] += a.J[i][j]; }
+  ss_sym<D>(o.C); ss_sym<D>(o.J);
+  out = o;
+}
+
+// One step of the ordinary Kalman filter: (m, P) at the previous point -> (m, P) at this one.  Returns the point's log-density term
+// (0 for an unobserved point, which takes the predict step only).
+template <int D>
+SS_HD double ss_filter_step(const SSModel<D>& M, double dt, double w, double r, double m[D], double P[D][D]) {
+  double A[D][D], Q[D][D], T[D][D], mp[D];
+  ss_AQ<D>(M, dt, A, Q);
+  ss_mm<D>(A, P, T);
+  for (int i = 0; i < D; ++i) {
+    double s = 0.0;
+    for (int k = 0; k < D; ++k) s += A[i][k] * m[k];
+    mp[i] = s;
+    for (int j = i; j < D; ++j) {
+      double q = Q[i][j];
+      for (int k = 0; k < D; ++k) q += T[i][k] * A[j][k];
+      P[i][j] = P[j][i] = q;
+    }
+  }
+  for (int i = 0; i < D; ++i) m[i] = mp[i];
+  if (!(w < INFINITY)) return 0.0;
+  const double S = P[0][0] + w, Sinv = 1.0 / S, e = r - m[0];
+  double K[D], p0[D];
+  for (int i = 0; i < D; ++i) { p0[i] = P[0][i]; K[i] = P[i][0] * Sinv; }
+  for (int i = 0; i < D; ++i) {
+    m[i] += K[i] * e;
+    for (int j = 0; j < D; ++j) P[i][j] -= K[i] * p0[j];
+  }
+  ss_sym<D>(P);
+  return -0.5 * (log(6.283185307179586 * S) + e * e * Sinv);
+}
+
+// ---- backward (smoothing) elements -----------------------------------------------------------------------------------------------
+template <int D>
+struct SSBwd { double E[D][D], g[D], L[D][D]; };
+
+// The element of a point with filtered state (m, P) whose successor lies dt further; last: the final point (0, m, P).
+template <int D>
+SS_HD void ss_bwd_element(const SSModel<D>& M, bool last, double dt, const double m[D], const double P[D][D], SSBwd<D>& e) {
+  if (last) {
+    for (int i = 0; i < D; ++i) {
+      e.g[i] = m[i];
+      for (int j = 0; j < D; ++j) { e.E[i][j] = 0.0; e.L[i][j] = P[i][j]; }
+    }
+    return;
+  }
+  double A[D][D], Q[D][D], T[D][D], Pp[D][D], Pi[D][D], X[D][D];
+  ss_AQ<D>(M, dt, A, Q);
+  ss_mm<D>(A, P, T);                          // A P
+  for (int i = 0; i < D; ++i)
+    for (int j = i; j < D; ++j) {
+      double q = Q[i][j];
+      for (int k = 0; k < D; ++k) q += T[i][k] * A[j][k];
+      Pp[i][j] = Pp[j][i] = q;
+    }
+  ss_inv_spd<D>(Pp, Pi);
+  for (int i = 0; i < D; ++i)                 // E = (A P)' Pp^-1
+    for (int j = 0; j < D; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < D; ++k) s += T[k][i] * Pi[k][j];
+      e.E[i][j] = s;
+    }
+  ss_mm<D>(e.E, T, X);                        // E A P
+  double Am[D];
+  for (int i = 0; i < D; ++i) {
+    double s = 0.0;
+    for (int k = 0; k < D; ++k) s += A[i][k] * m[k];
+    Am[i] = s;
+  }
+  for (int i = 0; i < D; ++i) {
+    double s = m[i];
+    for (int k = 0; k < D; ++k) s -= e.E[i][k] * Am[k];
+    e.g[i] = s;
+    for (int j = 0; j < D; ++j) e.L[i][j] = P[i][j] - X[i][j];
+  }
+  ss_sym<D>(e.L);
+}
+
+// out = a (.) b with a the earlier run: (E_a E_b, E_a g_b + g_a, E_a L_b E_a' + L_a); out may alias a or b
+template <int D>
+SS_HD void ss_bwd_combine(const SSBwd<D>& a, const SSBwd<D>& b, SSBwd<D>& out) {
+  SSBwd<D> o;
+  double X[D][D];
+  ss_mm<D>(a.E, b.E, o.E);
+  ss_mm<D>(a.E, b.L, X);
+  ss_mmt<D>(X, a.E, o.L);
+  for (int i = 0; i < D; ++i) {
+    double s = a.g[i];
+    for (int k = 0; k < D; ++k) s += a.E[i][k] * b.g[k];
+    o.g[i] = s;
+    for (int j = 0; j < D; ++j) o.L[i][j] += a.L[i][j];
+  }
+  ss_sym<D>(o.L);
+  out = o;
+}
+
+// One step of the Rauch-Tung-Striebel recursion: the smoothed state (ms, Ps) of the successor -> that of the point with element e.
+template <int D>
+SS_HD void ss_rts_step(const SSBwd<D>& e, double ms[D], double Ps[D][D]) {
+  double X[D][D], Y[D][D], t[D];
+  ss_mm<D>(e.E, Ps, X);
+  ss_mmt<D>(X, e.E, Y);
+  for (int i = 0; i < D; ++i) {
+    double s = e.g[i];
+    for (int k = 0; k < D; ++k) s += e.E[i][k] * ms[k];
+    t[i] = s;
+  }
+  for (int i = 0; i < D; ++i) {
+    ms[i] = t[i];
+    for (int j = 0; j < D; ++j) Ps[i][j] = Y[i][j] + e.L[i][j];
+  }
+  ss_sym<D>(Ps);
+}

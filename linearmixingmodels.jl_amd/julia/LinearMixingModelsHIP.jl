@@ -20,7 +20,7 @@ using AbstractGPs, KernelFunctions, LinearAlgebra, Random, FillArrays, ChainRule
 using LinearMixingModels
 using LinearMixingModels: ILMM, IndependentMOGP, Orthogonal, unpack, noise_var
 
-export hip, HIPMOGP
+export hip, HIPMOGP, statespace_logpdf, statespace_mean_and_var
 
 const liblmm = get(ENV, "LMM_HIP_LIB", "liblmm_hip.so")
 
@@ -470,6 +470,54 @@ function _elbo_dtc(vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOIL
 end
 AbstractGPs.elbo(vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real}) = _elbo_dtc(vfe, fx, y)[1]
 AbstractGPs.dtc(vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOILMM}, y::AbstractVector{<:Real}) = _elbo_dtc(vfe, fx, y)[2]
+
+# ---- state space: Matern12 / 32 / 52 latents over a one-dimensional input -------------------------------------------------------------
+# statespace_logpdf(fx, y) and statespace_mean_and_var(fx, y; add_noise, xs) through lmm_oilmm_logpdf_statespace and
+# lmm_oilmm_mean_and_var_statespace (include/lmm_hip.h, "state space"): a Kalman filter / RTS smoother per latent, O(n) and exact.
+# The library takes sorted inputs: the points are sorted here (stably) and the results put back in the caller's order.  `missing` or
+# NaN entries of y are missing observations; new inputs xs are merged in as points without observations.  Prior OILMM only.
+function _statespace_sorted(x, y::AbstractVector, p::Integer, xs)
+    X = _xmat(x)
+    size(X, 1) == 1 || error("state-space inference is served for one-dimensional inputs (d = $(size(X, 1)))")
+    xv = vec(X); n = length(xv)
+    Y = reshape(Float64[ismissing(v) ? NaN : Float64(v) for v in y], n, p)
+    if xs !== nothing
+        xn = vec(_xmat(xs))
+        xv = vcat(xv, xn); Y = vcat(Y, fill(NaN, length(xn), p))
+    end
+    perm = sortperm(xv; alg=MergeSort)
+    return xv[perm], vec(Y[perm, :]), perm, n
+end
+function statespace_logpdf(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector; with_regulariser::Bool=true)
+    fs, H, σ², x = unpack(fx)
+    isposterior(fs) && error("state-space inference is served on a prior OILMM only")
+    U, S, p, m = _hargs(H)
+    xv, yv, _, _ = _statespace_sorted(x, y, p, nothing)
+    out = Ref{Cdouble}(0.0)
+    _gps(fs.fs) do gps, tags
+        GC.@preserve xv yv U S gps check(ccall((:lmm_oilmm_logpdf_statespace, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Ref{Cdouble}),
+            xv, length(xv), yv, p, U, S, m, σ², gps, 0, m, Cint(with_regulariser), out))
+    end
+    return out[]
+end
+function statespace_mean_and_var(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector; add_noise::Bool=true, xs=nothing)
+    fs, H, σ², x = unpack(fx)
+    isposterior(fs) && error("state-space inference is served on a prior OILMM only")
+    U, S, p, m = _hargs(H)
+    xv, yv, perm, n = _statespace_sorted(x, y, p, xs)
+    N = length(xv)
+    mean = Vector{Float64}(undef, N * p); var = Vector{Float64}(undef, N * p)
+    _gps(fs.fs) do gps, tags
+        GC.@preserve xv yv U S gps mean var check(ccall((:lmm_oilmm_mean_and_var_statespace, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
+             Ptr{Cdouble}, Ptr{Cdouble}),
+            xv, N, yv, p, U, S, m, σ², gps, 0, m, Cint(add_noise), mean, var))
+    end
+    rows = xs === nothing ? (1:n) : (n+1:N)
+    back(v) = (B = similar(reshape(v, N, p)); B[perm, :] = reshape(v, N, p); vec(B[rows, :]))
+    return back(mean), back(var)
+end
 
 # ---- missing observations: y::AbstractVector{Union{Missing,Float64}} ----------------------------------------------------------------
 # The reference's notebook: "Heterotopic and missing data ... are not supported yet ... using the missing data techniques identified in

@@ -819,6 +819,126 @@ def _sparse_mean_and_var(fx: "FiniteGP", add_noise: bool, want_var: bool):
     return mean, var
 
 
+# ---- state space (Matern latents over a one-dimensional input) -----------------------------------------------
+# Matern12 / 32 / 52 latents over a one-dimensional input are finite-dimensional linear SDEs, so a Kalman filter gives logpdf and an RTS
+# smoother the posterior marginals in O(n), exactly (include/lmm_hip.h, "state space").  The library takes sorted
+# inputs; the sorting, and the merging of new inputs as points without observations, happen here.
+_STATESPACE_KINDS = ("matern12", "matern32", "matern52")
+
+
+def _statespace_sorted(xv, y, p: int, xs=None):
+    """(x sorted, y permuted, perm, n) for inputs xv (n,) and the by-outputs vector y (n * p); with xs (ns,) the new inputs are appended
+    as points whose outputs are all NaN before sorting.  The sort is stable; perm[k] is the original index of sorted point k.  NumPy
+    arrays unless xv or y is a torch tensor (then tensors on that one's device)."""
+    n = int(xv.shape[-1])
+    if L._is_torch(xv) or L._is_torch(y):
+        import torch
+        dev = xv.device if L._is_torch(xv) else y.device
+        xa = torch.as_tensor(xv, dtype=torch.float64, device=dev).reshape(-1)
+        Y = torch.as_tensor(y, dtype=torch.float64, device=dev).reshape(p, n)
+        if xs is not None:
+            xn = torch.as_tensor(xs, dtype=torch.float64, device=dev).reshape(-1)
+            xa = torch.cat([xa, xn])
+            Y = torch.cat([Y, torch.full((p, int(xn.shape[0])), float("nan"), dtype=torch.float64, device=dev)], dim=1)
+        xa, perm = torch.sort(xa, stable=True)
+        return xa.contiguous(), Y[:, perm].reshape(-1).contiguous(), perm, n
+    xa = np.asarray(xv, dtype=np.float64).reshape(-1)
+    Y = np.asarray(y, dtype=np.float64).reshape(p, n)
+    if xs is not None:
+        xn = np.asarray(xs, dtype=np.float64).reshape(-1)
+        xa = np.concatenate([xa, xn])
+        Y = np.concatenate([Y, np.full((p, xn.shape[0]), np.nan)], axis=1)
+    perm = np.argsort(xa, kind="stable")
+    return np.ascontiguousarray(xa[perm]), np.ascontiguousarray(Y[:, perm]).reshape(-1), perm, n
+
+
+def _statespace_unsorted(out, perm, p: int, n: int, only_new: bool):
+    """A by-outputs result over the sorted points back in the callers' order: the n training inputs, or (only_new) the inputs
+    appended behind them."""
+    N = int(perm.shape[0])
+    O = out.reshape(p, N)
+    if L._is_torch(out):
+        import torch
+        B = torch.empty_like(O)
+        B[:, perm] = O
+        return (B[:, n:] if only_new else B[:, :n]).reshape(-1).contiguous()
+    B = np.empty_like(O)
+    B[:, perm] = O
+    return np.ascontiguousarray(B[:, n:] if only_new else B[:, :n]).reshape(-1)
+
+
+def _statespace_args(fx: "FiniteGP", y, what: str):
+    """Checks of statespace_logpdf / statespace_mean_and_var, all before any library call."""
+    f, x = fx.f, fx.x
+    if isinstance(f, IndependentMOGP):
+        raise NotImplementedError(f"{what}: state-space inference is not served for an IndependentMOGP (wrap it in an OILMM)")
+    if not isinstance(f, ILMM) or not f.is_oilmm:
+        raise NotImplementedError(f"{what}: state-space inference is not served for a dense-H ILMM (OILMM only)")
+    if f.f._post is not None:
+        raise NotImplementedError(f"{what}: state-space inference is not served on a posterior model (prior OILMM only)")
+    if f.shard != (0, len(f.f.fs)):
+        raise NotImplementedError(f"{what}: state-space inference is not served with latents sharded across processes")
+    if not isinstance(x, MOInputIsotopicByOutputs):
+        raise NotImplementedError(f"{what}: state-space inference takes MOInputIsotopicByOutputs inputs")
+    if fx.heteroscedastic:
+        raise NotImplementedError(f"{what}: state-space inference takes a scalar noise variance (no per-point noise)")
+    if x.dim != 1:
+        raise NotImplementedError(f"{what}: state-space inference is served for one-dimensional inputs (d = {x.dim})")
+    for l, gp in enumerate(f.f.fs):
+        k = gp.kernel
+        if k.kind not in _STATESPACE_KINDS or np.ndim(k.lengthscale) != 0:
+            raise NotImplementedError(f"{what}: state-space inference is served for plain Matern12, Matern32 and Matern52 latents; "
+                                      f"latent {l} is {k!r}")
+    if not hasattr(y, "shape"):
+        y = np.asarray(y, dtype=np.float64)
+    if len(y.shape) != 1:
+        raise NotImplementedError(f"{what}: state-space inference is not served for a matrix Y (one vector y)")
+    unpack(fx)
+    if y.shape[0] != x.n * x.out_dim:
+        raise ValueError("length(y) != n * out_dim")
+    return y
+
+
+def statespace_logpdf(fx: "FiniteGP", y, with_regulariser: bool = True) -> float:
+    """logpdf(fx, y) of a prior OILMM whose latents are Matern12 / 32 / 52 over one-dimensional inputs, by a Kalman filter per latent:
+    the value of logpdf (NaN in y included: the missing-data approximation of logpdf) in O(n).  Points may come in any order (they are
+    sorted here, stably); a point whose outputs are all NaN is a predict-only step and leaves the value unchanged."""
+    y = _statespace_args(fx, y, "statespace_logpdf")
+    f, x = fx.f, fx.x
+    xa, ya, _, _ = _statespace_sorted(x.x.reshape(-1), y, x.out_dim)
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    out = C.c_double()
+    L.check(L.load().lmm_oilmm_logpdf_statespace(L.Arr(xa).ptr, x.n, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps, 0, m,
+                                                 int(with_regulariser), C.byref(out)))
+    return out.value
+
+
+def statespace_mean_and_var(fx: "FiniteGP", y, add_noise: bool = True, xs=None):
+    """mean_and_var(posterior(fx, y)(x*, sigma2)) of the same models by a Kalman filter and an RTS smoother per latent, in O(n): at the
+    training inputs (xs=None) or at the new inputs xs ((ns,); they are merged into the inputs as points without observations, and only
+    their rows are returned).  By-outputs vectors (mean, var), NumPy or torch like the inputs; add_noise adds sigma2 to the variances."""
+    y = _statespace_args(fx, y, "statespace_mean_and_var")
+    f, x = fx.f, fx.x
+    if xs is not None:
+        if not hasattr(xs, "shape"):
+            xs = np.asarray(xs, dtype=np.float64)
+        if len(xs.shape) != 1:
+            raise ValueError("statespace_mean_and_var: xs is a (ns,) array of one-dimensional inputs")
+        if int(xs.shape[0]) == 0:
+            xs = None
+    xa, ya, perm, n = _statespace_sorted(x.x.reshape(-1), y, x.out_dim, xs)
+    N = int(perm.shape[0])
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    mean, var = _alloc_like(xa, N * p), _alloc_like(xa, N * p)
+    L.check(L.load().lmm_oilmm_mean_and_var_statespace(L.Arr(xa).ptr, N, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps, 0, m,
+                                                       int(add_noise), L.Arr(mean, True).ptr, L.Arr(var, True).ptr))
+    return _statespace_unsorted(mean, perm, p, n, xs is not None), _statespace_unsorted(var, perm, p, n, xs is not None)
+
+
 # Dense-H ILMM logpdf: allow the identical-kernel decoupled shortcut (exact; SURVEY.md section 3.2).  Set False to force
 # the reference's single (mn) x (mn) factorisation.  ILMM_LAST_PATH records which ran.
 ILMM_ALLOW_DECOUPLED = True
