@@ -759,6 +759,10 @@ int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N
  * [32..47], [48..63] the three chunks of the CRT weights, [64..66] the chunks of the moduli's product, [67] b. */
 int lmm_dev_emul_host(const double* A, int lda, const double* B, int ldb, int M, int N, int K, int nmod, int k_bound, double* out,
                       int ldo, double* consts);
+/* Host-only (no GPU, no lmm_init needed): the residue step of the emulation's convert kernel on `count` integers |v| <= 2^58:
+ * out[i * nmod + t] = v[i] modulo the t-th modulus as an int8 (congruent, inside the symmetric range).  exhaustive (may be NULL, 2
+ * words): the reduction behind it run on every input it can see, every odd modulus, both signs: [0] cases, [1] failures. */
+int lmm_dev_emul_residues(const long long* v, int count, int nmod, signed char* out, long long* exhaustive);
 /* Gram assembly of one latent into a padded factor matrix (lower triangle + pad identity). */
 int lmm_dev_gram(double* A, int ld, int nrows, int ncols, const double* x, int d, int n,
                  const lmm_gp_t* gp, double diag_add);

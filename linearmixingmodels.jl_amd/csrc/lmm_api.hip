@@ -5387,7 +5387,9 @@ int lmm_dev_emul_host(const double* A, int lda, const double* B, int ldb, int M,
       r.sc[i] = 1.0; r.ex[i] = e - bits;
       for (int k = 0; k < K; ++k) {
         const long long v = emul_trunc(X[i + (size_t)k * ld], bits - e);
-        for (int t = 0; t < nmod; ++t) r.res[((size_t)t * n + i) * K + k] = (int8_t)emul_residue(v, c.p[t], 1.0f / (float)c.p[t], c.c1[t], c.c2[t]);
+        int res[LMM_EMUL_MAXMOD];
+        emul_residues<LMM_EMUL_MAXMOD>(v, res);
+        for (int t = 0; t < nmod; ++t) r.res[((size_t)t * n + i) * K + k] = (int8_t)res[t];
       }
     }
     return r;
@@ -5406,6 +5408,32 @@ int lmm_dev_emul_host(const double* A, int lda, const double* B, int ldb, int M,
   if (consts) {      // [0..15] p_t, [16..31] w_t1, [32..47] w_t2, [48..63] w_t3, [64..66] P1..P3, [67] b
     for (int t = 0; t < LMM_EMUL_MAXMOD; ++t) { consts[t] = c.p[t]; consts[16 + t] = c.w1[t]; consts[32 + t] = c.w2[t]; consts[48 + t] = c.w3[t]; }
     consts[64] = c.P1; consts[65] = c.P2; consts[66] = c.P3; consts[67] = bits;
+  }
+  return LMM_OK;
+}
+// Host-only (no GPU, no lmm_init needed): the convert kernel's residue step (emul_residues, lmm_emul.h) on `count` integers, |v| <= 2^58:
+// out[i nmod + t] = the int8 residue of v[i] modulo the t-th modulus.  exhaustive (may be NULL, 2 words): the reduction step
+// (emul_reduce_odd) run on every x it can see, for every odd modulus and both signs -- [0] = the number of (modulus, x) cases, [1] = how
+// many of them gave a result that is not congruent to +-x or lies outside [-(p - 1) / 2, (p - 1) / 2].
+int lmm_dev_emul_residues(const long long* v, int count, int nmod, signed char* out, long long* exhaustive) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (count < 0 || (count > 0 && (!v || !out)) || nmod < LMM_EMUL_MINMOD || nmod > LMM_EMUL_MAXMOD) return fail(LMM_ERR_ARG, "lmm_dev_emul_residues: bad arguments");
+  for (int i = 0; i < count; ++i) {
+    if (v[i] > (1ll << LMM_EMUL_MAXBITS) || v[i] < -(1ll << LMM_EMUL_MAXBITS)) return fail(LMM_ERR_ARG, "lmm_dev_emul_residues: |v| <= 2^%d", LMM_EMUL_MAXBITS);
+    int res[LMM_EMUL_MAXMOD];
+    emul_residues<LMM_EMUL_MAXMOD>(v[i], res);
+    for (int t = 0; t < nmod; ++t) out[(size_t)i * nmod + t] = (signed char)(int8_t)res[t];
+  }
+  if (exhaustive) {
+    long long cases = 0, bad = 0;
+    for (int t = 1; t < LMM_EMUL_MAXMOD; ++t) {
+      const int p = kEmulModuli[t], half = (p - 1) / 2;
+      for (int x = 0; x <= kEmulDot.xmax[t]; ++x, ++cases) {
+        const int rp = emul_reduce_odd(LMM_EMUL_MAGIC_BITS + (unsigned)x, 1.0f, t), rn = emul_reduce_odd(LMM_EMUL_MAGIC_BITS + (unsigned)x, -1.0f, t);
+        if ((rp - x) % p != 0 || rp < -half || rp > half || (rn + x) % p != 0 || rn < -half || rn > half) ++bad;
+      }
+    }
+    exhaustive[0] = cases; exhaustive[1] = bad;
   }
   return LMM_OK;
 }

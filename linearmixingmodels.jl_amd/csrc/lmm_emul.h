@@ -13,17 +13,16 @@
 
 #define LMM_EMUL_MAXMOD 16
 #define LMM_EMUL_MINMOD 8
-#define LMM_EMUL_MAXBITS 58      // |a'| <= 2^58: emul_residue's three limbs stay below 2^29
+#define LMM_EMUL_MAXBITS 58      // |a'| <= 2^58: the bit budget of 16 moduli at K = 128 (emul_residues takes any |v| < 2^63)
 
 // The 16 largest pairwise-coprime integers <= 256; the first nmod of them are used.
-static const int kEmulModuli[LMM_EMUL_MAXMOD] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 217, 211, 199, 197, 193};
+static constexpr int kEmulModuli[LMM_EMUL_MAXMOD] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 217, 211, 199, 197, 193};
 
 // By-value kernel argument.  w_t = (P / p_t) ((P / p_t)^-1 mod p_t) < P; every w_t and P itself are cut at bits 85 and 44 into three
 // doubles (41 + 41 + 44 bits, each exact).
 struct EmulConst {
   int nmod;
   int p[LMM_EMUL_MAXMOD];
-  int c1[LMM_EMUL_MAXMOD], c2[LMM_EMUL_MAXMOD];      // 2^20 mod p, 2^40 mod p (emul_residue)
   double w1[LMM_EMUL_MAXMOD], w2[LMM_EMUL_MAXMOD], w3[LMM_EMUL_MAXMOD];
   double P1, P2, P3, Pinv, Phalf;
 };
@@ -50,8 +49,6 @@ inline EmulConst emul_make_const(int nmod) {
   for (int t = 0; t < nmod; ++t) {
     const int p = kEmulModuli[t];
     c.p[t] = p;
-    c.c1[t] = (int)((uint64_t(1) << 20) % p);
-    c.c2[t] = (int)((uint64_t(1) << 40) % p);
     const emul_u128 Mt = P / (emul_u128)p;
     const int r = (int)(Mt % (emul_u128)p);
     int inv = 1;
@@ -78,25 +75,85 @@ LMM_HD inline int emul_row_exp(double amax) {
 LMM_HD inline long long emul_trunc(double a, int sh) { return (long long)ldexp(a, sh); }
 // v mod p in the symmetric range ([-128, 127] for p = 256; +128 is returned as 128 and wraps to -128 in the int8 store)
 LMM_HD inline int emul_mod_sym(int x, int p, float rp) {
-  // |x| < 2^29: the float quotient is off by less than 0.5, so one correction each way lands in [lo, lo + p - 1]
+  // |x| < 2^29: the float quotient is off by less than 0.5, so one correction each way lands in [lo, lo + p - 1]; |q| < 2^23 and
+  // p <= 256, so the 24-bit multiply is exact
 #if defined(__HIP_DEVICE_COMPILE__)
   const int q = __float2int_rn((float)x * rp);
+  int r = x - __mul24(q, p);
 #else
   const int q = (int)lrintf((float)x * rp);
+  int r = x - q * p;
 #endif
   const int lo = -(p / 2);
-  int r = x - q * p;
   r += (r < lo) ? p : 0;
   r -= (r > lo + p - 1) ? p : 0;
   return r;
 }
-LMM_HD inline int emul_residue(long long v, int p, float rp, int c1, int c2) {
+
+// ---- the convert kernel's residue step: no branch, no division, no 32-bit multiply per modulus ----
+// |v| <= 2^58 is cut into its 8 bytes d_i.  For an odd modulus p, x = sum_i d_i (256^i mod p) <= 8 255 (p - 1) < 2^19 is congruent
+// to |v|; the eight products are two 4-byte dot products against the packed constants lo and hi.  q = rint(x fl(1 / p)) is THE
+// nearest integer to x / p: the float product is off by less than 2^-11.6 (x / p < 2^11.5, two roundings of 2^-24 each), and x / p
+// is at least 1 / (2 p) >= 1 / 510 away from every half-integer because p is odd.  So x - q p lies in [-(p - 1) / 2, (p - 1) / 2]
+// with no correction step.  Modulo 256 the residue is the low byte of v itself.
+struct EmulDot { unsigned lo[LMM_EMUL_MAXMOD], hi[LMM_EMUL_MAXMOD]; float p[LMM_EMUL_MAXMOD], rp[LMM_EMUL_MAXMOD]; int xmax[LMM_EMUL_MAXMOD]; };
+constexpr EmulDot emul_make_dot() {
+  EmulDot d{};
+  for (int t = 0; t < LMM_EMUL_MAXMOD; ++t) {
+    const unsigned p = (unsigned)kEmulModuli[t];
+    unsigned c = 1 % p, sum = 0;
+    for (int i = 0; i < 8; ++i) {
+      if (i < 4) d.lo[t] |= c << (8 * i); else d.hi[t] |= c << (8 * (i - 4));
+      sum += c;
+      c = (c * 256u) % p;
+    }
+    d.p[t] = (float)p;
+    d.rp[t] = 1.0f / (float)p;
+    d.xmax[t] = (int)(255u * sum);      // the largest x the reduction can see
+  }
+  return d;
+}
+static constexpr EmulDot kEmulDot = emul_make_dot();
+
+#define LMM_EMUL_MAGIC 12582912.0f      // 1.5 2^23 = the float with the bits 0x4B400000: MAGIC + x has the bits 0x4B400000 + x for 0 <= x < 2^22
+#define LMM_EMUL_MAGIC_BITS 0x4B400000u
+
+LMM_HD inline unsigned emul_udot4(unsigned a, unsigned b, unsigned c) {      // c + sum of the four byte products of a and b
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_udot4(a, b, c, false);
+#else
+  for (int i = 0; i < 4; ++i) c += ((a >> (8 * i)) & 0xFFu) * ((b >> (8 * i)) & 0xFFu);
+  return c;
+#endif
+}
+LMM_HD inline float emul_bits_as_float(unsigned u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __uint_as_float(u);
+#else
+  float f;
+  __builtin_memcpy(&f, &u, 4);
+  return f;
+#endif
+}
+// sgn x mod p_t for 0 <= x <= xmax[t], sgn = +-1.0f and t >= 1, given xb = LMM_EMUL_MAGIC_BITS + x.  Every float operation is exact
+// but the product with rp: sgn (MAGIC + x) - sgn MAGIC = +-x, and x - q p is a small integer.
+LMM_HD inline int emul_reduce_odd(unsigned xb, float sgn, int t) {
+  const float xf = fmaf(emul_bits_as_float(xb), sgn, -sgn * LMM_EMUL_MAGIC);
+  const float q = rintf(xf * kEmulDot.rp[t]);
+  return (int)fmaf(-q, kEmulDot.p[t], xf);
+}
+// The residues of v modulo the first NMOD moduli, as int8 bit patterns in the low bytes of r[0 .. NMOD - 1]
+template <int NMOD>
+LMM_HD inline void emul_residues(long long v, int* r) {
   const bool neg = v < 0;
   const unsigned long long m = neg ? (unsigned long long)(-v) : (unsigned long long)v;
-  const int x = (int)(m & 0xFFFFF) + (int)((m >> 20) & 0xFFFFF) * c1 + (int)(m >> 40) * c2;
-  const int r = emul_mod_sym(x, p, rp);
-  return neg ? -r : r;
+  const unsigned lo = (unsigned)m, hi = (unsigned)(m >> 32);
+  const float sgn = neg ? -1.0f : 1.0f;
+  r[0] = (int)((unsigned)v & 0xFFu);
+#pragma unroll
+  for (int t = 1; t < NMOD; ++t) r[t] = emul_reduce_odd(emul_udot4(hi, kEmulDot.hi[t], emul_udot4(lo, kEmulDot.lo[t], LMM_EMUL_MAGIC_BITS)), sgn, t) & 0xFF;
 }
+
 // The integer X, |X| < P / 2, with X = u_t mod p_t for all t, rounded once to Float64.  S1 and S2 are exact (41-bit chunks, 8-bit
 // residues, 16 terms); S1 - q P1 and S2 - q P2 are exact; their sum rounds X to 53 bits; the third term is below one ulp of P.
 LMM_HD inline double emul_crt_at(double S1, double S2, double S3, double q, const EmulConst& c) {

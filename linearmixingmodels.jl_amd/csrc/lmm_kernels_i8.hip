@@ -3,8 +3,8 @@
 //   1. emul_rowmax_kernel + emul_convert_kernel: per panel row the exponent e_i = ceil(log2 max_k |a_ik|), the integers
 //      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows;
 //   2. emul_gemm_kernel: one int8 SYRK-shaped GEMM per (matrix, modulus) on 256 x 256 tiles of the lower trapezoid, int32
-//      accumulators, reduced mod p to one byte per output (a copy of the 16x16x64 form of tools/i8_gemm_probe.hip's kernel, which
-//      stands alone: a change here has to be made there too before the probe's numbers speak for this kernel);
+//      accumulators, reduced mod p to one byte per output (tools/i8_gemm_probe.hip holds a copy, i8_syrk_mod_kernel_pf, beside the
+//      kernel this one replaced; the probe stands alone: a change here has to be made there too before its numbers speak for this kernel);
 //   3. emul_combine_kernel: CRT reconstruction in Float64 (lmm_emul.h) and C_ij -= X 2^(e_i + e_j - 2b) for i >= j.
 // Integer sums are exact in any order: the result is bitwise reproducible.
 #include "lmm_internal.h"
@@ -35,13 +35,17 @@ __global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, si
   atomicMax(&amax[(size_t)z * Mp + i], m);
 }
 
-// 32 rows x 128 k per workgroup: reads coalesced along the rows of the column-major panel, residues transposed through LDS into
-// K-contiguous int8 rows R[(z nmod + t) Mp + i][k].  Rows M .. Mp - 1 (padding up to the GEMM tile) get zero residues.
-constexpr int CV_ROWS = 32, CV_K = 128, CV_PITCH = 132;
-__global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, int bits, EmulConst c,
-                                                           const unsigned long long* amax, int8_t* R, double* sc, int* ex) {
-  __shared__ int8_t lds[LMM_EMUL_MAXMOD * CV_ROWS * CV_PITCH];
-  const int tid = threadIdx.x, ti = tid & 31, tk = tid >> 5, z = blockIdx.z;
+// 16 rows x 128 k per workgroup of 256 threads, NMOD moduli.  Each thread first issues its 8 loads (8 k of one row; 16 lanes cover
+// 128 contiguous bytes of a column of the column-major panel), truncates them and writes the integers to LDS, [row][k] with a pitch
+// of 130 (16.6 KB: nine workgroups fit on a CU).  It then takes 4 consecutive k of two rows from LDS, forms the residues
+// (emul_residues: constants folded into the instructions) and stores one dword per modulus straight to the K-contiguous int8 rows
+// R[(z NMOD + t) Mp + i][k]: 32 lanes write 128 contiguous bytes.  Rows M .. Mp - 1 (padding up to the GEMM tile) get zero residues.
+constexpr int CV_ROWS = 16, CV_K = 128, CV_PITCH = 130;
+template <int NMOD>
+__global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
+                                                           const unsigned long long* __restrict__ amax, int8_t* __restrict__ R, double* sc, int* ex) {
+  __shared__ long long lds[CV_ROWS * CV_PITCH];
+  const int tid = threadIdx.x, ti = tid & 15, tk = tid >> 4, z = blockIdx.z;
   const int i = blockIdx.x * CV_ROWS + ti, k0 = blockIdx.y * CV_K;
   unsigned long long mb = 0;
   if (i < M) mb = amax[(size_t)z * Mp + i];
@@ -52,22 +56,39 @@ __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, s
     sc[(size_t)z * Mp + i] = live ? 1.0 : (finite ? 0.0 : __longlong_as_double(0x7FF8000000000000ll));
     ex[(size_t)z * Mp + i] = live ? e - bits : 0;
   }
-  const double* P = A.p[g0 + z] + off + i;
-#pragma unroll 4
-  for (int s = 0; s < CV_K / 8; ++s) {
-    const int kk = tk + 8 * s;
-    long long v = 0;
-    if (live) v = emul_trunc(P[(size_t)(k0 + kk) * ld], bits - e);
+  const double* P = A.p[g0 + z] + off + i + (size_t)(k0 + tk) * ld;
+  double a[CV_K / 16];
 #pragma unroll
-    for (int t = 0; t < LMM_EMUL_MAXMOD; ++t)
-      if (t < c.nmod) lds[(t * CV_ROWS + ti) * CV_PITCH + kk] = (int8_t)emul_residue(v, c.p[t], 1.0f / (float)c.p[t], c.c1[t], c.c2[t]);
-  }
+  for (int s = 0; s < CV_K / 16; ++s) a[s] = live ? P[(size_t)(16 * s) * ld] : 0.0;
+#pragma unroll
+  for (int s = 0; s < CV_K / 16; ++s) lds[ti * CV_PITCH + tk + 16 * s] = emul_trunc(a[s], bits - e);
   __syncthreads();
-  for (int idx = tid; idx < c.nmod * CV_ROWS * (CV_K / 4); idx += 256) {
-    const int w = idx & 31, row = (idx >> 5) & 31, t = idx >> 10;
-    const int v = *reinterpret_cast<const int*>(&lds[(t * CV_ROWS + row) * CV_PITCH + 4 * w]);
-    *reinterpret_cast<int*>(R + (((size_t)z * c.nmod + t) * Mp + blockIdx.x * CV_ROWS + row) * K + k0 + 4 * w) = v;
+  const int kg = tid & 31;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int row = (tid >> 5) + 8 * h;
+    unsigned w[NMOD];
+#pragma unroll
+    for (int t = 0; t < NMOD; ++t) w[t] = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int r[NMOD];
+      emul_residues<NMOD>(lds[row * CV_PITCH + 4 * kg + j], r);
+#pragma unroll
+      for (int t = 0; t < NMOD; ++t) w[t] |= (unsigned)r[t] << (8 * j);
+    }
+    int8_t* dst = R + ((size_t)z * NMOD * Mp + blockIdx.x * CV_ROWS + row) * K + k0 + 4 * kg;
+#pragma unroll
+    for (int t = 0; t < NMOD; ++t) *reinterpret_cast<unsigned*>(dst + (size_t)t * Mp * K) = w[t];
   }
+}
+template <int NMOD>
+void launch_convert(int nmod, dim3 grid, hipStream_t st, const BatchPtr& P, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
+                    const unsigned long long* amax, int8_t* R, double* sc, int* ex) {
+  if constexpr (NMOD > LMM_EMUL_MINMOD) {
+    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, R, sc, ex);
+  }
+  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, R, sc, ex);
 }
 
 // lower-trapezoid tiles in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles share at most 12 operand panels
@@ -108,6 +129,25 @@ __device__ __forceinline__ void glds16(const int8_t* src, int8_t* lds_wave_base)
 //   ds_read_b128 lane group hits 16 distinct 16-B slots of the 256-B bank row.
 // Both operands are fragment-loaded the same way (lane l: row l & 15, bytes 16 (l >> 4) .. + 15 of the 64-deep k range), so the k
 // order inside an MFMA is the same for A and B whatever the hardware's k map is.  Mp, Np multiples of 256, K of 128: no edges.
+//
+// The K loop: one K step is four phases of 16 MFMAs, (ks, mh) = the 64-byte half of the k range x the upper / lower 4 of the wave's 8
+// row fragments.  The fragments of a phase are read into registers in the MIDDLE of the phase before it, between its two groups of 8
+// MFMAs, so they are 8 MFMAs old when the wait before their first use comes (the compiler waits with lgkmcnt(0) there, so reads
+// issued right before that wait would be waited for too).  sched_barrier(0) pins that order: left alone, the scheduler sinks the
+// reads down to their uses.  The one barrier of a K step stands between phases 3 and 4.  Stage t lives in buffer t & 1.
+//
+//   phase of step t | MFMAs use (registers)        | ds_reads issued (buffer)                 | global_load_lds issued
+//   1 (ks 0, mh 0)  | a[0..3], b[0..3]   of t      | a[4..7] ks 0 of t  (t & 1)               |
+//   2 (ks 0, mh 1)  | a[4..7], b[0..3]   of t      | a[0..3], b[0..3] ks 1 of t  (t & 1)      |
+//   3 (ks 1, mh 0)  | a[0..3]', b[0..3]' of t      | a[4..7] ks 1 of t  (t & 1): the LAST read of buffer t & 1
+//   -- s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier: every wave holds all its fragments of stage t in registers, and every wave's
+//      loads of stage t + 1 (issued one whole K step earlier, at this point of step t - 1) have landed in buffer (t + 1) & 1 --
+//   4 (ks 1, mh 1)  | a[4..7]', b[0..3]' of t      | a[0..3], b[0..3] ks 0 of t + 1 ((t+1)&1) | stage t + 2 into buffer t & 1
+//
+//   read after write: buffer (t + 1) & 1 is first read in phase 4 of step t, after the wait-plus-barrier that retires stage t + 1.
+//   write after read: buffer t & 1 is restaged in phase 4 of step t, after the barrier every wave reaches only with its last reads
+//   of that buffer (phase 3) complete.  One stage is in flight at a time, so the wait is vmcnt(0); it waits for loads that are one
+//   K step (64 MFMAs per wave) old.  nk = 1 and 2: the prologue stages tiles 0 and 1, the loop stages t + 2 < nk only.
 __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
                                                            int Mp, int Np, int K, EmulConst c) {
   __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
@@ -133,6 +173,11 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
 #pragma unroll
     for (int q = 0; q < 4; ++q) glds16(srcB[q] + k0, base + TILE * BK + q * 1024);
   };
+  const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
+  // byte offset of a fragment in its stage: (row 128) + ((ks 4 + fk) ^ (row >> 1) & 7) 16 with row = 16 m + frow (+ the wave's first
+  // row, a multiple of 64): the swizzle is (frow >> 1), and ks = 1 flips bit 6 of the offset
+  const int offA = (wr * 128 + frow) * BK + ((fk ^ (frow >> 1)) << 4), offB = TILE * BK + (wc * 64 + frow) * BK + ((fk ^ (frow >> 1)) << 4);
+  auto frag = [&](const int8_t* st, int off, int ks, int f) { return *reinterpret_cast<const v4i*>(st + (off ^ (ks << 6)) + f * 16 * BK); };
   v4i acc[8][4];
 #pragma unroll
   for (int m = 0; m < 8; ++m)
@@ -141,33 +186,42 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
+  if (nk > 1) stage(1, BK);
+  v4i alo[4], ahi[4], b[4], alo1[4], ahi1[4], b1[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) { alo[f] = frag(lds, offA, 0, f); b[f] = frag(lds, offB, 0, f); }
+  // 8 MFMAs: row fragments 2 h, 2 h + 1 of A4 (accumulator rows M0 + 2 h ..) x the 4 column fragments
+#define EMUL_MMA8(A4, B4, M0, h)                                                                                                   \
+  _Pragma("unroll") for (int m = 2 * (h); m < 2 * (h) + 2; ++m)                                                                    \
+  _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + m][n], 0, 0, 0)
+#define EMUL_PIN() __builtin_amdgcn_sched_barrier(0)
   for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) stage((kt + 1) & 1, (kt + 1) * BK);
-    const int8_t* la = lds + (kt & 1) * STAGE_BYTES;
-    const int8_t* lb = la + TILE * BK;
+    const int8_t* cur = lds + (kt & 1) * STAGE_BYTES;
+    const int8_t* nxt = lds + ((kt + 1) & 1) * STAGE_BYTES;
+    EMUL_MMA8(alo, b, 0, 0); EMUL_PIN();      // phase 1
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int chunk = ks * 4 + fk;
-      v4i a[8], b[4];
+    for (int f = 0; f < 4; ++f) ahi[f] = frag(cur, offA, 0, 4 + f);
+    EMUL_PIN(); EMUL_MMA8(alo, b, 0, 1); EMUL_PIN();
+    EMUL_MMA8(ahi, b, 4, 0); EMUL_PIN();      // phase 2
 #pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const int row = wr * 128 + m * 16 + frow;
-        a[m] = *reinterpret_cast<const v4i*>(la + row * BK + ((chunk ^ ((row >> 1) & 7)) << 4));
-      }
+    for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }
+    EMUL_PIN(); EMUL_MMA8(ahi, b, 4, 1); EMUL_PIN();
+    EMUL_MMA8(alo1, b1, 0, 0); EMUL_PIN();    // phase 3
 #pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const int row = wc * 64 + n * 16 + frow;
-        b[n] = *reinterpret_cast<const v4i*>(lb + row * BK + ((chunk ^ ((row >> 1) & 7)) << 4));
-      }
-#pragma unroll
-      for (int m = 0; m < 8; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[m], b[n], acc[m][n], 0, 0, 0);
-    }
+    for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);
+    EMUL_PIN(); EMUL_MMA8(alo1, b1, 0, 1); EMUL_PIN();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if (kt + 2 < nk) stage(kt & 1, (kt + 2) * BK);
+    EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
+    if (kt + 1 < nk) {
+#pragma unroll
+      for (int f = 0; f < 4; ++f) { alo[f] = frag(nxt, offA, 0, f); b[f] = frag(nxt, offB, 0, f); }
+    }
+    EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
   }
+#undef EMUL_MMA8
+#undef EMUL_PIN
   // epilogue: reduce mod p (|acc| <= K 128^2 <= 2^28), pack the 4 consecutive rows a lane holds into one dword of U[j][i]
   const int p = c.p[item % c.nmod];
   const float rp = 1.0f / (float)p;
@@ -254,7 +308,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
     err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
     if (err != hipSuccess) return err;
     emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, K, amax);
-    emul_convert_kernel<<<dim3(L.Mp / CV_ROWS, K / CV_K, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, K, bits, c, amax, R, sc, ex);
+    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, amax, R, sc, ex);
     emul_gemm_kernel<<<L.ntiles * gc * nmod, 512, 0, st>>>(R, U, tiles, L.ntiles, L.Mp, L.Np, K, c);
     emul_combine_kernel<<<dim3((M + 1023) / 1024, N, gc), 256, 0, st>>>(C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);
   }

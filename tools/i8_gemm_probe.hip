@@ -138,6 +138,132 @@ __global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel(const int8_t* __res
     }
 }
 
+__device__ __forceinline__ int mod_sym24(int x, int p, float rp, int lo) {
+  const int q = __float2int_rn((float)x * rp);
+  int r = x - __mul24(q, p);
+  r += (r < lo) ? p : 0;
+  r -= (r > lo + p - 1) ? p : 0;
+  return r;
+}
+
+// The library's emul_gemm_kernel (lmm_kernels_i8.hip), 16x16x64 form, as it stands now; i8_syrk_mod_kernel<16> above is the kernel
+// it replaced and stays as the baseline.
+// The K loop: one K step is four phases of 16 MFMAs, (ks, mh) = the 64-byte half of the k range x the upper / lower 4 of the wave's 8
+// row fragments.  The fragments of a phase are read into registers in the MIDDLE of the phase before it, between its two groups of 8
+// MFMAs, so they are 8 MFMAs old when the wait before their first use comes (the compiler waits with lgkmcnt(0) there, so reads
+// issued right before that wait would be waited for too).  sched_barrier(0) pins that order: left alone, the scheduler sinks the
+// reads down to their uses.  The one barrier of a K step stands between phases 3 and 4.  Stage t lives in buffer t & 1.
+//
+//   phase of step t | MFMAs use (registers)        | ds_reads issued (buffer)                 | global_load_lds issued
+//   1 (ks 0, mh 0)  | a[0..3], b[0..3]   of t      | a[4..7] ks 0 of t  (t & 1)               |
+//   2 (ks 0, mh 1)  | a[4..7], b[0..3]   of t      | a[0..3], b[0..3] ks 1 of t  (t & 1)      |
+//   3 (ks 1, mh 0)  | a[0..3]', b[0..3]' of t      | a[4..7] ks 1 of t  (t & 1): the LAST read of buffer t & 1
+//   -- s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier: every wave holds all its fragments of stage t in registers, and every wave's
+//      loads of stage t + 1 (issued one whole K step earlier, at this point of step t - 1) have landed in buffer (t + 1) & 1 --
+//   4 (ks 1, mh 1)  | a[4..7]', b[0..3]' of t      | a[0..3], b[0..3] ks 0 of t + 1 ((t+1)&1) | stage t + 2 into buffer t & 1
+//
+//   read after write: buffer (t + 1) & 1 is first read in phase 4 of step t, after the wait-plus-barrier that retires stage t + 1.
+//   write after read: buffer t & 1 is restaged in phase 4 of step t, after the barrier every wave reaches only with its last reads
+//   of that buffer (phase 3) complete.  One stage is in flight at a time, so the wait is vmcnt(0); it waits for loads that are one
+//   K step (64 MFMAs per wave) old.  nk = 1 and 2: the prologue stages tiles 0 and 1, the loop stages t + 2 < nk only.
+template <bool STAMP>
+__global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_pf(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
+                                                                int Mp, int Np, int K, Moduli mod, unsigned long long* __restrict__ stamps) {
+  __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
+  // blocks b and b + 8 share an XCD: give each XCD a contiguous range of work ids, so that its 32 resident blocks are one supertile
+  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
+  const int item = wg / ntiles;
+  const int2 t = tiles[wg - item * ntiles];
+  const int8_t* Rb = R + (size_t)item * Mp * K;
+  const int8_t* srcA[4];
+  const int8_t* srcB[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = wid * 32 + q * 8 + (lane >> 3), chunk = (lane & 7) ^ ((row >> 1) & 7);
+    srcA[q] = Rb + ((size_t)t.x * TILE + row) * K + chunk * 16;
+    srcB[q] = Rb + ((size_t)t.y * TILE + row) * K + chunk * 16;
+  }
+  auto stage = [&](int buf, int k0) {
+    int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) glds16(srcA[q] + k0, base + q * 1024);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) glds16(srcB[q] + k0, base + TILE * BK + q * 1024);
+  };
+  const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
+  // byte offset of a fragment in its stage: (row 128) + ((ks 4 + fk) ^ (row >> 1) & 7) 16 with row = 16 m + frow (+ the wave's first
+  // row, a multiple of 64): the swizzle is (frow >> 1), and ks = 1 flips bit 6 of the offset
+  const int offA = (wr * 128 + frow) * BK + ((fk ^ (frow >> 1)) << 4), offB = TILE * BK + (wc * 64 + frow) * BK + ((fk ^ (frow >> 1)) << 4);
+  auto frag = [&](const int8_t* st, int off, int ks, int f) { return *reinterpret_cast<const v4i*>(st + (off ^ (ks << 6)) + f * 16 * BK); };
+  v4i acc[8][4];
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = (v4i){0, 0, 0, 0};
+  unsigned long long t0 = 0, r0 = 0;
+  if (STAMP) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (nk > 1) stage(1, BK);
+  v4i alo[4], ahi[4], b[4], alo1[4], ahi1[4], b1[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) { alo[f] = frag(lds, offA, 0, f); b[f] = frag(lds, offB, 0, f); }
+  // 8 MFMAs: row fragments 2 h, 2 h + 1 of A4 (accumulator rows M0 + 2 h ..) x the 4 column fragments
+#define EMUL_MMA8(A4, B4, M0, h)                                                                                                   \
+  _Pragma("unroll") for (int m = 2 * (h); m < 2 * (h) + 2; ++m)                                                                    \
+  _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + m][n], 0, 0, 0)
+#define EMUL_PIN() __builtin_amdgcn_sched_barrier(0)
+  for (int kt = 0; kt < nk; ++kt) {
+    const int8_t* cur = lds + (kt & 1) * STAGE_BYTES;
+    const int8_t* nxt = lds + ((kt + 1) & 1) * STAGE_BYTES;
+    EMUL_MMA8(alo, b, 0, 0); EMUL_PIN();      // phase 1
+#pragma unroll
+    for (int f = 0; f < 4; ++f) ahi[f] = frag(cur, offA, 0, 4 + f);
+    EMUL_PIN(); EMUL_MMA8(alo, b, 0, 1); EMUL_PIN();
+    EMUL_MMA8(ahi, b, 4, 0); EMUL_PIN();      // phase 2
+#pragma unroll
+    for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }
+    EMUL_PIN(); EMUL_MMA8(ahi, b, 4, 1); EMUL_PIN();
+    EMUL_MMA8(alo1, b1, 0, 0); EMUL_PIN();    // phase 3
+#pragma unroll
+    for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);
+    EMUL_PIN(); EMUL_MMA8(alo1, b1, 0, 1); EMUL_PIN();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (kt + 2 < nk) stage(kt & 1, (kt + 2) * BK);
+    EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
+    if (kt + 1 < nk) {
+#pragma unroll
+      for (int f = 0; f < 4; ++f) { alo[f] = frag(nxt, offA, 0, f); b[f] = frag(nxt, offB, 0, f); }
+    }
+    EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
+  }
+#undef EMUL_MMA8
+#undef EMUL_PIN
+  if (STAMP) {
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    if (tid == 0) { stamps[2 * (size_t)blockIdx.x] = t1 - t0; stamps[2 * (size_t)blockIdx.x + 1] = r1 - r0; }
+  }
+  // epilogue: reduce mod p with the 24-bit multiply (|q| < 2^23), pack the 4 consecutive rows a lane holds into one dword of U[j][i]
+  const int p = mod.p[item % NMOD], lo = -(p / 2);
+  const float rp = 1.0f / (float)p;
+  int8_t* Ub = U + (size_t)item * Np * Mp;
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const size_t j = (size_t)t.y * TILE + wc * 64 + n * 16 + frow;      // C/D map of 16x16: column = lane & 15, row = 4 (lane >> 4) + e
+      const int i = t.x * TILE + wr * 128 + m * 16 + 4 * fk;
+      unsigned w = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w |= (unsigned)(mod_sym24(acc[m][n][e], p, rp, lo) & 0xFF) << (8 * e);
+      *reinterpret_cast<unsigned*>(Ub + j * Mp + i) = w;
+    }
+}
+
 // bare issue rate: operands in registers, 4 independent accumulators, no memory traffic
 __global__ __launch_bounds__(256) void mfma_i8_bare(int* out, unsigned long long* stamps, int iters) {
   v16i acc[4];
@@ -197,7 +323,8 @@ static int mod_sym_host(long long x, int p) {
 
 template <int SHAPE, bool STAMP>
 static void launch(const int8_t* R, int8_t* U, const int2* tiles, int ntiles, int M, int N, int K, int batch, unsigned long long* stamps) {
-  i8_syrk_mod_kernel<SHAPE, STAMP><<<ntiles * batch, 512>>>(R, U, tiles, ntiles, M, N, K, kModuli, stamps);
+  if constexpr (SHAPE == 0) i8_syrk_mod_kernel_pf<STAMP><<<ntiles * batch, 512>>>(R, U, tiles, ntiles, M, N, K, kModuli, stamps);      // SHAPE 0: the register-prefetch kernel
+  else i8_syrk_mod_kernel<SHAPE, STAMP><<<ntiles * batch, 512>>>(R, U, tiles, ntiles, M, N, K, kModuli, stamps);
 }
 
 // exact check of U against a host integer product; every == true checks every computed tile and that nothing else was written
@@ -276,6 +403,13 @@ int main(int argc, char** argv) {
     launch<16, false>(R, U, dt, (int)tl.size(), M, N, K, NMOD, nullptr);
     CHECK(hipDeviceSynchronize());
     bad += check(R, U, M, N, K, NMOD, true, "16x16x64 full");
+    for (int Kp : {128, 256, 384, 512}) {      // the register-prefetch kernel: K loops shorter than its pipeline, odd and even counts (R holds 512 x 384 x 16 bytes: the same rows, read with K = Kp, for Kp <= 384; 512 fits as M K NMOD = 512 * 512 * 12)
+      const int nb = Kp <= K ? NMOD : 12;
+      CHECK(hipMemset(U, 0x5A, (size_t)NMOD * N * M));
+      launch<0, false>(R, U, dt, (int)tl.size(), M, N, Kp, nb, nullptr);
+      CHECK(hipDeviceSynchronize());
+      bad += check(R, U, M, N, Kp, nb, true, "16x16x64 prefetch full");
+    }
     CHECK(hipFree(R)); CHECK(hipFree(U)); CHECK(hipFree(dt));
     fflush(stdout);
     if (bad) { printf("operand or output map wrong: not timing\n"); return 1; }
@@ -297,20 +431,24 @@ int main(int argc, char** argv) {
     const double outs = (double)s.N * (s.N + 1) / 2 + (double)(s.M - s.N) * s.N;
     const double useful = 2.0 * s.K * outs * batch, issued = 2.0 * s.K * (double)TILE * TILE * nt * batch;
     const int reps = (int)std::max(4.0, 0.15 / (issued / 2.0e15));  // about 150 ms per window at 2 POPS
-    std::vector<float> t32, t16;
+    std::vector<float> t32, t16, tpf;
     for (int round = 0; round < 3; ++round)
-      for (int v = 0; v < 2; ++v) {
-        auto go = [&]() { if (v == 0) launch<32, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr); else launch<16, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr); };
+      for (int v = 0; v < 3; ++v) {
+        auto go = [&]() {
+          if (v == 0) launch<32, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
+          else if (v == 1) launch<16, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
+          else launch<0, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
+        };
         go();
         hipEventRecord(e0);
         for (int r = 0; r < reps; ++r) go();
         hipEventRecord(e1); CHECK(hipEventSynchronize(e1));
         float ms; hipEventElapsedTime(&ms, e0, e1);
-        (v == 0 ? t32 : t16).push_back(ms / reps);
+        (v == 0 ? t32 : v == 1 ? t16 : tpf).push_back(ms / reps);
       }
-    double clk[2];
-    for (int v = 0; v < 2; ++v) {  // diagnostic build with stamps, after the timed windows (the chip is warm)
-      for (int r = 0; r < 3; ++r) { if (v == 0) launch<32, true>(R, U, dt, nt, s.M, s.N, s.K, batch, st); else launch<16, true>(R, U, dt, nt, s.M, s.N, s.K, batch, st); }
+    double clk[3];
+    for (int v = 0; v < 3; ++v) {  // diagnostic build with stamps, after the timed windows (the chip is warm)
+      for (int r = 0; r < 3; ++r) { if (v == 0) launch<32, true>(R, U, dt, nt, s.M, s.N, s.K, batch, st); else if (v == 1) launch<16, true>(R, U, dt, nt, s.M, s.N, s.K, batch, st); else launch<0, true>(R, U, dt, nt, s.M, s.N, s.K, batch, st); }
       CHECK(hipDeviceSynchronize());
       std::vector<unsigned long long> h((size_t)nt * batch * 2);
       CHECK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
@@ -319,14 +457,20 @@ int main(int argc, char** argv) {
       std::sort(c.begin(), c.end());
       clk[v] = c[c.size() / 2];
     }
-    std::sort(t32.begin(), t32.end()); std::sort(t16.begin(), t16.end());
+    std::sort(t32.begin(), t32.end()); std::sort(t16.begin(), t16.end()); std::sort(tpf.begin(), tpf.end());
     printf("i8 syrk M=%5d N=%5d K=%5d batch=%d (%d tiles, %d reps) | 32x32x32: min %.3f med %.3f ms, %.0f TOPS useful (%.0f issued), clock %.0f MHz"
            " | 16x16x64: min %.3f med %.3f ms, %.0f TOPS useful (%.0f issued), clock %.0f MHz\n",
            s.M, s.N, s.K, batch, nt, reps, t32[0], t32[1], useful / t32[0] / 1e9, issued / t32[0] / 1e9, clk[0], t16[0], t16[1], useful / t16[0] / 1e9,
            issued / t16[0] / 1e9, clk[1]);
+    printf("                                                  | 16x16x64 prefetch (the library's kernel): min %.3f med %.3f ms, %.0f TOPS useful (%.0f issued), clock %.0f MHz"
+           " | baseline 16x16x64 / prefetch: medians %.3f\n", tpf[0], tpf[1], useful / tpf[0] / 1e9, issued / tpf[0] / 1e9, clk[2], t16[1] / tpf[1]);
     launch<32, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
     CHECK(hipDeviceSynchronize());
     bad += check(R, U, s.M, s.N, s.K, batch, false, "32x32x32 sampled");
+    CHECK(hipMemset(U, 0x5A, ub));
+    launch<0, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
+    CHECK(hipDeviceSynchronize());
+    bad += check(R, U, s.M, s.N, s.K, batch, false, "16x16x64 prefetch sampled");
     fflush(stdout);
     CHECK(hipFree(R)); CHECK(hipFree(U)); CHECK(hipFree(dt)); CHECK(hipFree(st));
   }
