@@ -668,7 +668,7 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
  * Refusals, all before any kernel of the scan is launched: a latent that is not a plain Matern12 / 32 / 52 (SE, RQ, the periodic
  * kinds, sums, latents with a tag) -> LMM_ERR_UNSUPPORTED with the latent in the error detail; the fp32 compute mode ->
  * LMM_ERR_UNSUPPORTED; a point with 0 < p_t < m -> LMM_ERR_UNSUPPORTED with the point in `info`; S not finite and > 0, sigma2 <= 0 ->
- * LMM_ERR_ARG.  Not built: gradients, sums of Matern terms, rand.
+ * LMM_ERR_ARG.  Not built: gradients with respect to x, gradients of the marginals, sums of Matern terms, rand.
  *   lmm_oilmm_logpdf_statespace : the value of lmm_oilmm_logpdf (no NaN) or lmm_oilmm_logpdf_missing (NaN) by the filter: agreement
  *                    to rounding, not bitwise.  Shard semantics and with_regulariser as there.
  *   lmm_oilmm_mean_and_var_statespace : the smoothed latent marginals at the n inputs, mixed through H = U sqrt(S) exactly as
@@ -680,7 +680,21 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
  *                    on the host, its mean is not read): one latent with per-point noise w (n; +Inf = unobserved) and data r (n).
  *                    fmean, fvar: the filtered first-component mean and variance (the predicted ones at an unobserved point);
  *                    *lml: sum_t -1/2 (log 2 pi S_t + e_t^2 / S_t) over the observed points; smean, svar: the smoothed ones.
- *                    chunk: points per thread (0: the library's plan, a function of n alone); chunk >= n is one sequential thread. */
+ *                    chunk: points per thread (0: the library's plan, a function of n alone); chunk >= n is one sequential thread.
+ *   lmm_oilmm_logpdf_grad_statespace : value and gradient of lmm_oilmm_logpdf_statespace in O(n), with respect to y (grad_y: n x p in
+ *                    the layout of y, host or device; exactly 0 at NaN entries and in the rows of points without observations), sigma2,
+ *                    S (m), U (p x m, column-major) and every latent's (variance, lengthscale, mean) (grad_gps: m records, zeros
+ *                    outside the shard).  Any output may be NULL.  *out_logpdf is bitwise the value of lmm_oilmm_logpdf_statespace.
+ *                    Per latent, with C = K + diag(w) over the observed points: d/d r_t = -alpha_t, alpha = C^-1 r, and d/d w_t =
+ *                    (alpha_t^2 - (C^-1)_tt) / 2, both read off the smoothed marginals (alpha_t = (r_t - mu_t) / w_t, (C^-1)_tt =
+ *                    (w_t - P_t) / w_t^2); d/d variance and d/d lengthscale by forward-mode differentiation of the filter scan (the same
+ *                    fold, scan and filter on (value, tangent) pairs, one launch serving both parameters).  No atomics: the result
+ *                    depends on the arguments only.  y, sigma2, S and U follow by the chain rule of lmm_oilmm_logpdf_grad (complete
+ *                    data) or lmm_oilmm_logpdf_grad_missing (NaN in y, all-NaN points included: then grad_S or grad_U non-NULL is
+ *                    LMM_ERR_UNSUPPORTED).  Every refusal of lmm_oilmm_logpdf_statespace applies, in its order.  Partial sums over
+ *                    the shard; with_regulariser as there.
+ *   lmm_dev_statespace_grad : the building block beside lmm_dev_statespace_filter (DEVICE pointers throughout): *lml as there (bitwise),
+ *                    grad_r and grad_w (n each; 0 at unobserved points), grad_theta = {d lml / d variance, d lml / d lengthscale}. */
 int lmm_oilmm_logpdf_statespace(const double* x, int n, const double* y, int p,
                                 const double* U, const double* S, int m, double sigma2,
                                 const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out);
@@ -692,6 +706,13 @@ int lmm_dev_statespace_filter(const double* x, int n, const lmm_gp_t* gp, const 
                               double* fmean, double* fvar, double* lml);
 int lmm_dev_statespace_smooth(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
                               double* smean, double* svar);
+int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, int p,
+                                     const double* U, const double* S, int m, double sigma2,
+                                     const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                     double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                                     lmm_gp_grad_t* grad_gps);
+int lmm_dev_statespace_grad(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
+                            double* lml, double* grad_r, double* grad_w, double* grad_theta);
 
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard

@@ -34,6 +34,7 @@ SYMBOLS = [
     "lmm_oilmm_elbo", "lmm_oilmm_sparse_posterior_create", "lmm_sparse_post_destroy", "lmm_oilmm_sparse_mean_and_var", "lmm_dev_sparse_moments",
     "lmm_oilmm_elbo_grad", "lmm_dev_sparse_grad",
     "lmm_oilmm_logpdf_statespace", "lmm_oilmm_mean_and_var_statespace", "lmm_dev_statespace_filter", "lmm_dev_statespace_smooth",
+    "lmm_oilmm_logpdf_grad_statespace", "lmm_dev_statespace_grad",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
     "lmm_dev_set_f64_emul", "lmm_dev_syrk_emul", "lmm_dev_emul_host", "lmm_dev_emul_residues",
 ]
@@ -58,6 +59,8 @@ STATESPACE_ARGTYPES = {
     "lmm_oilmm_mean_and_var_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P],
     "lmm_dev_statespace_filter": [_P, _I, _P, _P, _P, _I, _P, _P, _P],
     "lmm_dev_statespace_smooth": [_P, _I, _P, _P, _P, _I, _P, _P],
+    "lmm_oilmm_logpdf_grad_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "lmm_dev_statespace_grad": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
 }
 
 

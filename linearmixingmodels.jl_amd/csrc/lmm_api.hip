@@ -5066,8 +5066,14 @@ static int ss_check_sorted(const double* xd, int n) {
 // The filter (and, smean != nullptr, the smoother) of the ms latents lts[0 .. ms): w, r, fmean, fvar, smean, svar are [latent][n] on
 // the device (outputs may be nullptr); lml: ms host values or nullptr; add_mean: the smoothed means get the latent's mean added.
 // Latents run in launches of equal state dimension, as many per launch as LMM_SS_BATCH_BYTES admits.  Returns with streams[0] drained.
+// go != nullptr (with smean, svar and add_mean = false): the gradients of every latent's log density as well.
+struct SSGradOut {
+  double* alpha; double* grad_w;       // device, [latent][n]: alpha_t = -d lml / d r_t, d lml / d w_t
+  double* sums;                        // host, 4 per latent: sum_t alpha_t, w_t alpha_t^2, w_t c_t, d lml / d w_t
+  double* gtheta;                      // host, 2 per latent: d lml / d variance, d lml / d lengthscale
+};
 static int ss_core(const double* xd, int n, const Latent* lts, int ms, const double* w, const double* r, int chunk, double* lml,
-                   double* fmean, double* fvar, double* smean, double* svar, bool add_mean) {
+                   double* fmean, double* fvar, double* smean, double* svar, bool add_mean, const SSGradOut* go = nullptr) {
   hipStream_t st0 = g.streams[0];
   if (chunk <= 0) chunk = ss_default_chunk(n);
   if (chunk > n) chunk = n;
@@ -5076,18 +5082,26 @@ static int ss_core(const double* xd, int n, const Latent* lts, int ms, const dou
   for (int k0 = 0; k0 < ms;) {
     const int D = ss_state_dim(lts[k0].kind);
     const size_t comps = (size_t)ss_state_comps(D);
-    const size_t per = (ss_fwd_agg_elems(D, nch) + (size_t)nch + (smooth ? comps * n + ss_bwd_agg_elems(D, nch) : 0)) * sizeof(double);
+    const int npb = ss_point_blocks(n);
+    const size_t per = (ss_fwd_agg_elems(D, nch) + (size_t)nch + (smooth ? comps * n + ss_bwd_agg_elems(D, nch) : 0) +
+                        (go ? ss_dual_agg_elems(D, nch) + 2 * (size_t)nch + 4 * (size_t)npb : 0)) * sizeof(double);
     const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / per));
     int nb = 1;
     while (k0 + nb < ms && nb < nbmax && ss_state_dim(lts[k0 + nb].kind) == D) ++nb;
     Buf<double> agg((size_t)nb * ss_fwd_agg_elems(D, nch)), part((size_t)nb * nch), lmld(nb), state, bagg;
     if (smooth) { state = Buf<double>((size_t)nb * comps * n); bagg = Buf<double>((size_t)nb * ss_bwd_agg_elems(D, nch)); }
+    Buf<double> dagg, dpart, ppart, gsum;
+    if (go) {
+      dagg = Buf<double>((size_t)nb * ss_dual_agg_elems(D, nch)); dpart = Buf<double>((size_t)nb * 2 * nch);
+      ppart = Buf<double>((size_t)nb * 4 * npb); gsum = Buf<double>((size_t)nb * 6);
+    }
     SSArgs a{};
     a.x = xd; a.n = n; a.chunk = chunk; a.nch = nch;
     a.agg = agg.p; a.bagg = bagg.p; a.part = part.p;
     a.fmean = fmean ? fmean + (size_t)k0 * n : nullptr; a.fvar = fvar ? fvar + (size_t)k0 * n : nullptr;
     a.state = state.p; a.state_stride = comps * n;
     a.smean = smooth ? smean + (size_t)k0 * n : nullptr; a.svar = (smooth && svar) ? svar + (size_t)k0 * n : nullptr;
+    a.dagg = dagg.p; a.dpart = dpart.p;
     for (int j = 0; j < nb; ++j) {
       const Latent& L = lts[k0 + j];
       a.lat[j].var = L.terms[0].ev.var; a.lat[j].inv_ls = L.terms[0].ev.inv_ls; a.lat[j].mean = add_mean ? L.mean : 0.0;
@@ -5095,8 +5109,16 @@ static int ss_core(const double* xd, int n, const Latent* lts, int ms, const dou
     }
     launch_ss_filter(a, D, nb, lmld.p, st0);
     if (smooth) launch_ss_smooth(a, D, nb, st0);
+    if (go) {
+      launch_ss_point(a, nb, go->alpha + (size_t)k0 * n, go->grad_w + (size_t)k0 * n, ppart.p, gsum.p, st0);
+      launch_ss_grad(a, D, nb, gsum.p + (size_t)nb * 4, st0);
+    }
     HIPCHK(hipGetLastError());
     if (lml) HIPCHK(hipMemcpyAsync(lml + k0, lmld.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st0));
+    if (go) {
+      HIPCHK(hipMemcpyAsync(go->sums + (size_t)k0 * 4, gsum.p, (size_t)nb * 4 * sizeof(double), hipMemcpyDeviceToHost, st0));
+      HIPCHK(hipMemcpyAsync(go->gtheta + (size_t)k0 * 2, gsum.p + (size_t)nb * 4, (size_t)nb * 2 * sizeof(double), hipMemcpyDeviceToHost, st0));
+    }
     HIPCHK(hipStreamSynchronize(st0));          // the buffers above go back to the pool
     k0 += nb;
   }
@@ -5109,12 +5131,21 @@ static int ss_core(const double* xd, int n, const Latent* lts, int ms, const dou
 struct SSFront {
   Buf<double> w, r;        // [l1 - l0][n]
   double reg = 0.0;        // sum_t r_t over the points with observations
+  // for the gradient: whether any entry of y is NaN, the points with observations (idx, on the device idxd; all n when nobs == n) and
+  // the front end's state over those nobs points (its z and nv have moved into r and w when nobs == n)
+  bool has_nan = false;
+  int nobs = 0;
+  std::vector<int> idx;
+  Buf<int> idxd;
+  MissingFront F;
 };
 static int ss_front(const double* yd, int n, int p, const double* U, const double* S, int m, double s2, const Latent* lts, int l0, int l1,
-                    SSFront& Fr) {
+                    SSFront& Fr, bool want_resid = false) {
   hipStream_t st0 = g.streams[0];
   const int nw = (p + 63) / 64, ms = l1 - l0;
-  std::vector<int> hpt(n), idx;
+  std::vector<int> hpt(n);
+  std::vector<int>& idx = Fr.idx;
+  MissingFront& F = Fr.F;
   {
     Buf<unsigned long long> masks((size_t)n * nw);
     Buf<int> pt(n);
@@ -5128,13 +5159,14 @@ static int ss_front(const double* yd, int n, int p, const double* U, const doubl
       return fail(LMM_ERR_UNSUPPORTED, "missing data: point %d observes %d outputs, fewer than the m = %d latent processes", t, hpt[t], m);
     }
     if (hpt[t] > 0) idx.push_back(t);
+    if (hpt[t] != p) Fr.has_nan = true;
   }
   const int nobs = (int)idx.size();
+  Fr.nobs = nobs;
   std::vector<double> means(m);
   for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
-  MissingFront F;
   if (nobs == n) {
-    if (int rc = missing_front(yd, n, p, U, S, m, s2, means.data(), l0, l1, false, F)) return rc;
+    if (int rc = missing_front(yd, n, p, U, S, m, s2, means.data(), l0, l1, want_resid, F)) return rc;
     Fr.w = std::move(F.nv); Fr.r = std::move(F.z);
     Fr.reg = F.reg(n, m, s2);
     return LMM_OK;
@@ -5145,11 +5177,12 @@ static int ss_front(const double* yd, int n, int p, const double* U, const doubl
     launch_fill(Fr.r.p + (size_t)k * n, n, 0.0, st0);
   }
   if (nobs > 0) {
-    Buf<int> idxd(nobs);
+    Fr.idxd = Buf<int>(nobs);
+    Buf<int>& idxd = Fr.idxd;
     Buf<double> yc((size_t)nobs * p);
     HIPCHK(hipMemcpyAsync(idxd.p, idx.data(), (size_t)nobs * sizeof(int), hipMemcpyHostToDevice, st0));
     launch_ss_gather_rows(yd, n, p, idxd.p, nobs, yc.p, st0);
-    if (int rc = missing_front(yc.p, nobs, p, U, S, m, s2, means.data(), l0, l1, false, F)) {
+    if (int rc = missing_front(yc.p, nobs, p, U, S, m, s2, means.data(), l0, l1, want_resid, F)) {
       if (rc == LMM_ERR_NOT_PD && g.err_info >= 0 && g.err_info < nobs) {      // the front end numbered the points it saw
         g.err_info = idx[g.err_info];
         return fail(LMM_ERR_NOT_PD, "PosDefException: H_t' H_t of point %d is not positive definite over its observed outputs", g.err_info);
@@ -5163,7 +5196,8 @@ static int ss_front(const double* yd, int n, int p, const double* U, const doubl
     Fr.reg = F.reg(nobs, m, s2);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st0));            // idxd, yc and F's buffers go back to the pool
+  HIPCHK(hipStreamSynchronize(st0));            // yc and the front end's compacted z and nv go back to the pool
+  F.z = Buf<double>(); F.nv = Buf<double>();
   return LMM_OK;
 }
 
@@ -5227,6 +5261,125 @@ int lmm_oilmm_mean_and_var_statespace(const double* x, int n, const double* y, i
   LMM_CATCH
 }
 
+// Value and gradient of lmm_oilmm_logpdf_statespace with respect to y, sigma2, S, U and every latent's (variance, lengthscale, mean), in
+// O(n).  Per latent the smoother gives d lml / d r_t = -alpha_t and d lml / d w_t = (alpha_t^2 - c_t) / 2, and the
+// forward-mode pass d lml / d variance and d lml / d lengthscale (ss_core with SSGradOut); the front end's chain rule is that of
+// lmm_oilmm_elbo_grad for complete data and that of oilmm_grad_missing_core for data with NaN (then without S and U).  *out_logpdf is
+// the sum of lmm_oilmm_logpdf_statespace in its order.  Partial sums over the shard; any output may be NULL.
+int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                     double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                     double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                                     lmm_gp_grad_t* grad_gps) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  LMM_SS_ARGCHECK(false);
+  RESOLVE(gps, m, 1);
+  if (int rc = ss_check_latents(lts, m)) return rc;
+  hipStream_t st0 = g.streams[0];
+  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
+  if (int rc = ss_check_sorted(xd.p, n)) return rc;
+  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0, msa = std::max(ms, 1);
+  SSFront Fr;
+  if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr, grad_y && with_regulariser)) return rc;
+  if (Fr.has_nan && (grad_S || grad_U))
+    return fail(LMM_ERR_UNSUPPORTED, "state-space gradients with respect to S and U are not built for data with NaN (pass NULL for grad_S and grad_U)");
+  DevOut gy(grad_y, (size_t)n * p);
+  std::vector<double> lml(msa, 0.0), sums(4 * (size_t)msa, 0.0), gth(2 * (size_t)msa, 0.0);
+  Buf<double> sm((size_t)n * msa), sv((size_t)n * msa), al((size_t)n * msa), gw((size_t)n * msa);
+  const SSGradOut go{al.p, gw.p, sums.data(), gth.data()};
+  if (int rc = ss_core(xd.p, n, lts + l0, ms, Fr.w.p, Fr.r.p, 0, lml.data(), nullptr, nullptr, sm.p, sv.p, false, &go)) return rc;
+  double total = 0.0;
+  for (int k = 0; k < ms; ++k) total += lml[k];
+  if (with_regulariser) total += Fr.reg;
+  OilmmGrad G;
+  G.value = total;
+  G.gs2.assign(1, 0.0);
+  G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
+  G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
+  for (int k = 0; k < ms; ++k) {
+    G.ggps[l0 + k].variance = gth[2 * (size_t)k]; G.ggps[l0 + k].lengthscale = gth[2 * (size_t)k + 1];
+    G.ggps[l0 + k].mean = sums[4 * (size_t)k];                 // sum_t alpha_t
+  }
+  if (Fr.has_nan) {
+    const MissingFront& F = Fr.F;
+    const int nobs = Fr.nobs;
+    // w_t = sigma2 (G_t^-1)_ll: sum_t (d lml / d w_t) w_t / sigma2, as oilmm_grad_missing_core
+    for (int k = 0; k < ms; ++k) G.gs2[0] += 0.5 * (sums[4 * (size_t)k + 1] - sums[4 * (size_t)k + 2]) / sigma2;
+    if (with_regulariser && nobs > 0) G.gs2[0] += -0.5 * ((F.sum_pt - (double)nobs * m) / sigma2 - F.rss / (sigma2 * sigma2));
+    if (grad_y) {
+      if (nobs == n) {
+        launch_missing_grad_y(n, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, al.p, n, l0, ms, with_regulariser ? F.resid.p : nullptr, sigma2,
+                              gy.p, st0);
+      } else {
+        // the front end numbered the nobs points with observations: alpha in that numbering, the rows of grad_y scattered back
+        for (int o = 0; o < p; ++o) launch_fill(gy.p + (size_t)o * n, n, 0.0, st0);
+        if (nobs > 0) {
+          Buf<double> ac((size_t)nobs * msa), gyc((size_t)nobs * p);
+          if (ms > 0) launch_ss_gather_rows(al.p, n, ms, Fr.idxd.p, nobs, ac.p, st0);
+          launch_missing_grad_y(nobs, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, ac.p, nobs, l0, ms, with_regulariser ? F.resid.p : nullptr,
+                                sigma2, gyc.p, st0);
+          launch_ss_scatter_rows(gyc.p, n, p, Fr.idxd.p, nobs, gy.p, st0);
+          HIPCHK(hipGetLastError());
+          HIPCHK(hipStreamSynchronize(st0));      // ac and gyc go back to the pool
+        }
+      }
+    }
+  } else {
+    // complete data: r = (T y)_l - mean_l with T = S^-1/2 U' and w = sigma2 / S_l; the host chain rule of lmm_oilmm_elbo_grad
+    std::vector<double> T, ST, H;
+    project_orthogonal(U, S, p, m, sigma2, T, ST, H);
+    const size_t pp = (size_t)p * p;
+    Buf<double> YAd((size_t)p * msa), aTyd(msa), M2d(pp);
+    std::vector<double> YA((size_t)p * msa, 0.0), aTy(msa, 0.0), M2all(pp, 0.0);
+    if (ms > 0) {
+      launch_atb(yd.p, n, al.p, n, n, p, ms, YAd.p, st0);                   // Y' alpha_l, p x ms
+      for (int k = 0; k < ms; ++k) launch_atb(al.p + (size_t)k * n, n, Fr.r.p + (size_t)k * n, n, n, 1, 1, aTyd.p + k, st0);
+      HIPCHK(hipMemcpyAsync(YA.data(), YAd.p, YA.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+      HIPCHK(hipMemcpyAsync(aTy.data(), aTyd.p, (size_t)ms * sizeof(double), hipMemcpyDeviceToHost, st0));
+    }
+    if (with_regulariser) {
+      launch_atb(yd.p, n, yd.p, n, n, p, p, M2d.p, st0);
+      HIPCHK(hipMemcpyAsync(M2all.data(), M2d.p, pp * sizeof(double), hipMemcpyDeviceToHost, st0));
+    }
+    HIPCHK(hipStreamSynchronize(st0));
+    for (int k = 0; k < ms; ++k) {
+      const int l = l0 + k;
+      const double dw = sums[4 * (size_t)k + 3];                            // sum_t d lml / d w_t
+      const double aTyl = aTy[k] + lts[l].mean * sums[4 * (size_t)k];       // alpha' (T y)_l: r has the mean taken off
+      G.gs2[0] += dw / S[l];
+      G.gS[l] += -dw * sigma2 / (S[l] * S[l]) + 0.5 * aTyl / S[l];          // d lml / d r = -alpha
+      for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] -= YA[o + (size_t)k * p] / std::sqrt(S[l]);
+    }
+    double reg_value = 0.0;                  // the regulariser's value is in G.value already (Fr.reg)
+    std::vector<double> PtP;
+    const NoiseBlocks NB1 = one_noise_block(n, sigma2);
+    if (with_regulariser) oilmm_regulariser_grad(U, S, p, m, NB1, M2all, reg_value, G, PtP);
+    if (grad_y) {
+      // d/dY[o, i] = -sum_l T[l, o] alpha_l[i] - (P'P Y)[o, i] / sigma2
+      std::vector<double> Tt((size_t)p * msa, 0.0);
+      for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) Tt[o + (size_t)k * p] = -T[(l0 + k) + (size_t)o * m];
+      Uploaded Ttd(Tt, st0);
+      Buf<double> ga((size_t)n * p);
+      launch_mix(al.p, n, ms, Ttd.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, with_regulariser ? ga.p : gy.p, st0);
+      if (with_regulariser) {
+        Uploaded Qd(PtP, st0);
+        Buf<double> gq((size_t)n * p);
+        launch_tall_skinny(yd.p, n, n, p, Qd.buf.p, p, p, gq.p, n, nullptr, nullptr, 0, nullptr, 0, st0);
+        launch_vec_lin_blocks(ga.p, gq.p, NB1, -1.0, n, (size_t)n * p, gy.p, st0);
+      }
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(st0));
+    }
+  }
+  double value = 0.0;
+  write_oilmm_grad(G, m, p, &value, grad_sigma2, grad_S, grad_U, grad_gps);
+  if (out_logpdf) *out_logpdf = value;
+  if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
+  return LMM_OK;
+  LMM_CATCH
+}
+
 // Building blocks for tests: ONE latent from device pointers, per-point noise w (+Inf: unobserved) and data r; the latent's mean is
 // not read (r is the residual).  chunk: points per thread (0: the library's plan).
 static int ss_dev_block(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* fmean,
@@ -5262,6 +5415,32 @@ int lmm_dev_statespace_smooth(const double* x, int n, const lmm_gp_t* gp, const 
   LMM_TRY
   if (!x || !gp || !w || !r || !smean || !svar) return fail(LMM_ERR_ARG, "bad arguments");
   return ss_dev_block(x, n, gp, w, r, chunk, nullptr, nullptr, nullptr, smean, svar);
+  LMM_CATCH
+}
+
+// Building block for tests beside lmm_dev_statespace_filter: lml as there, grad_r and grad_w (n values each) and grad_theta =
+// {d lml / d variance, d lml / d lengthscale}, all on the device.
+int lmm_dev_statespace_grad(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* lml,
+                            double* grad_r, double* grad_w, double* grad_theta) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !gp || !w || !r || !lml || !grad_r || !grad_w || !grad_theta || n <= 0 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  RESOLVE(gp, 1, 1);
+  if (int rc = ss_check_latents(lts, 1)) return rc;
+  if (int rc = ss_check_sorted(x, n)) return rc;
+  hipStream_t st0 = g.streams[0];
+  Buf<double> sm(n), sv(n);
+  double hl = 0.0, sums[4], gth[2];
+  const SSGradOut go{grad_r, grad_w, sums, gth};
+  if (int rc = ss_core(x, n, lts, 1, w, r, chunk, &hl, nullptr, nullptr, sm.p, sv.p, false, &go)) return rc;
+  launch_vec_lin(grad_r, grad_r, -2.0, n, grad_r, st0);      // ss_core left alpha there: d lml / d r = -alpha
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(lml, &hl, sizeof(double), hipMemcpyHostToDevice, st0));
+  HIPCHK(hipMemcpyAsync(grad_theta, gth, 2 * sizeof(double), hipMemcpyHostToDevice, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
   LMM_CATCH
 }
 

@@ -322,6 +322,8 @@ struct SSArgs {
   double* state; size_t state_stride;         // filtered states, [latent][ss_state_comps(D)][n] (nullptr: not kept); doubles per latent
   double* part;                               // nb * nch log-density partials
   double* smean; double* svar;                // smoothed first-component mean (+ lat.mean) / variance, [latent][n]
+  double* dagg;                               // nb * ss_dual_agg_elems(D, nch) doubles: the (value, tangent) aggregates (gradients only)
+  double* dpart;                              // nb * 2 * nch tangents of the log-density partials (gradients only)
   SSLat lat[LMM_MAX_BATCH];
 };
 static_assert(sizeof(SSArgs) <= 4096, "SSArgs is passed by value: kernel arguments are limited to 4096 bytes");
@@ -334,6 +336,14 @@ size_t ss_bwd_agg_elems(int D, int nch);
 void launch_ss_filter(const SSArgs& a, int D, int nb, double* lml, hipStream_t st);
 // the same in reverse over the filtered states a.state: smoothed marginals into a.smean / a.svar
 void launch_ss_smooth(const SSArgs& a, int D, int nb, hipStream_t st);
+// Gradients.  gtheta[2 l + s]: d lml_l / d variance (s = 0) and d lml_l / d lengthscale (s = 1) by the forward-mode (dual number)
+// instantiation of fold, scan and filter; a.dagg and a.dpart are its workspace
+size_t ss_dual_agg_elems(int D, int nch);     // per latent, both seeds
+void launch_ss_grad(const SSArgs& a, int D, int nb, double* gtheta, hipStream_t st);
+// from a.smean / a.svar (no mean added): alpha, grad_w ([latent][n]) = -d lml / d r_t, d lml / d w_t (0 at unobserved points) and
+// sums[4 l + q] = sum_t alpha, w alpha^2, w c, grad_w in a fixed order; ppart: nb * 4 * ss_point_blocks(n) doubles
+int ss_point_blocks(int n);
+void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, double* ppart, double* sums, hipStream_t st);
 // *flag (preset to INT_MAX) = the first t with !(x_t >= x_{t-1})
 void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st);
 // rows idx[0 .. nsel) of an n x p column-major matrix into an nsel x p one, and back

@@ -8,6 +8,10 @@
 //      writes the marginals; the filter's log-density partials are added in thread order by ss_finish_kernel.
 // A(dt) and Q(dt) are evaluated on the fly from x_t - x_{t-1}; blockIdx.z is the latent.  Every latent of a launch has the same state
 // dimension D (the template argument).
+// Gradients (launch_ss_grad): d lml / d variance and d lml / d lengthscale are the forward-mode derivative of phases 1 - 3 of the filter,
+// the same text instantiated with SSDual (lmm_statespace.h): ss_dfold_kernel, the scan over SSFwd<D, SSDual> and ss_dfilter_kernel, with
+// blockIdx.y in {0, 1} the seeded parameter, so a thread carries one tangent.  d lml / d r_t and d lml / d w_t come from the smoothed
+// marginals (ss_point_kernel), with fixed-order sums of what the OILMM chain rule needs.
 #include "lmm_internal.h"
 #include "lmm_statespace.h"
 
@@ -17,6 +21,8 @@ namespace {
 
 constexpr int SS_THREADS = 256;      // fold / filter / rts: one thread per chunk
 constexpr int SS_SCAN = 128;         // aggregates per workgroup of the scan (one per thread; 128 SSFwd<3> are 33 KiB of LDS)
+// 128 SSFwd<3, SSDual> would be 66 KiB, above the 64 KiB of static LDS: elements that large are scanned 64 per workgroup
+template <typename T> constexpr int ss_scan_width() { return sizeof(T) * SS_SCAN <= 65536 ? SS_SCAN : SS_SCAN / 2; }
 
 template <int D>
 __device__ __forceinline__ SSModel<D> ss_lat_model(const SSLat& L) {
@@ -47,6 +53,9 @@ __global__ __launch_bounds__(SS_THREADS) void ss_fold_kernel(SSArgs a) {
 
 struct FwdOp {
   template <int D> static __device__ __forceinline__ void combine(const SSFwd<D>& a, const SSFwd<D>& b, SSFwd<D>& o) { ss_fwd_combine<D>(a, b, o); }
+  template <int D> static __device__ __forceinline__ void combine(const SSFwd<D, SSDual>& a, const SSFwd<D, SSDual>& b, SSFwd<D, SSDual>& o) {
+    ss_fwd_combine<D, SSDual>(a, b, o);
+  }
 };
 struct BwdOp {
   template <int D> static __device__ __forceinline__ void combine(const SSBwd<D>& a, const SSBwd<D>& b, SSBwd<D>& o) { ss_bwd_combine<D>(a, b, o); }
@@ -57,15 +66,16 @@ struct BwdOp {
 // (logical workgroup k at nblk - 1 - k when REV), so the same kernel scans them.
 template <int D, typename T, typename Op, bool REV>
 __global__ __launch_bounds__(SS_SCAN) void ss_scan_kernel(T* items, int N, T* totals) {
-  __shared__ T sh[SS_SCAN];
-  const int tid = threadIdx.x, q = blockIdx.x * SS_SCAN + tid, z = blockIdx.z;
+  constexpr int W = ss_scan_width<T>();
+  __shared__ T sh[W];
+  const int tid = threadIdx.x, q = blockIdx.x * W + tid, z = blockIdx.z;
   const int nblk = gridDim.x;
   const bool live = q < N;
   const size_t i = (size_t)z * N + (REV ? N - 1 - q : q);
   T mine;
   if (live) { mine = items[i]; sh[tid] = mine; }
   __syncthreads();
-  for (int off = 1; off < SS_SCAN; off <<= 1) {
+  for (int off = 1; off < W; off <<= 1) {
     const bool take = live && tid >= off;
     T other;
     if (take) other = sh[tid - off];
@@ -79,7 +89,7 @@ __global__ __launch_bounds__(SS_SCAN) void ss_scan_kernel(T* items, int N, T* to
   }
   if (live) {
     items[i] = mine;
-    const int last = (N - blockIdx.x * SS_SCAN < SS_SCAN ? N - blockIdx.x * SS_SCAN : SS_SCAN) - 1;
+    const int last = (N - blockIdx.x * W < W ? N - blockIdx.x * W : W) - 1;
     if (totals != nullptr && tid == last) totals[(size_t)z * nblk + (REV ? nblk - 1 - (int)blockIdx.x : (int)blockIdx.x)] = mine;
   }
 }
@@ -87,7 +97,8 @@ __global__ __launch_bounds__(SS_SCAN) void ss_scan_kernel(T* items, int N, T* to
 // items of logical workgroup k >= 1 take the scanned total of workgroup k - 1 in front
 template <int D, typename T, typename Op, bool REV>
 __global__ __launch_bounds__(SS_SCAN) void ss_addprefix_kernel(T* items, int N, const T* totals) {
-  const int blk = blockIdx.x + 1, q = blk * SS_SCAN + threadIdx.x, z = blockIdx.z;
+  constexpr int W = ss_scan_width<T>();
+  const int blk = blockIdx.x + 1, q = blk * W + threadIdx.x, z = blockIdx.z;
   const int nblk = gridDim.x + 1;
   if (q >= N) return;
   const size_t i = (size_t)z * N + (REV ? N - 1 - q : q);
@@ -100,14 +111,15 @@ __global__ __launch_bounds__(SS_SCAN) void ss_addprefix_kernel(T* items, int N, 
 
 template <int D, typename T, typename Op, bool REV>
 void scan_levels(T* items, int N, int nb, T* scratch, hipStream_t st) {
-  const int nblk = (N + SS_SCAN - 1) / SS_SCAN;
+  constexpr int W = ss_scan_width<T>();
+  const int nblk = (N + W - 1) / W;
   if (nblk == 1) {
-    hipLaunchKernelGGL((ss_scan_kernel<D, T, Op, REV>), dim3(1, 1, nb), dim3(SS_SCAN), 0, st, items, N, (T*)nullptr);
+    hipLaunchKernelGGL((ss_scan_kernel<D, T, Op, REV>), dim3(1, 1, nb), dim3(W), 0, st, items, N, (T*)nullptr);
     return;
   }
-  hipLaunchKernelGGL((ss_scan_kernel<D, T, Op, REV>), dim3(nblk, 1, nb), dim3(SS_SCAN), 0, st, items, N, scratch);
+  hipLaunchKernelGGL((ss_scan_kernel<D, T, Op, REV>), dim3(nblk, 1, nb), dim3(W), 0, st, items, N, scratch);
   scan_levels<D, T, Op, REV>(scratch, nblk, nb, scratch + (size_t)nb * nblk, st);
-  hipLaunchKernelGGL((ss_addprefix_kernel<D, T, Op, REV>), dim3(nblk - 1, 1, nb), dim3(SS_SCAN), 0, st, items, N, (const T*)scratch);
+  hipLaunchKernelGGL((ss_addprefix_kernel<D, T, Op, REV>), dim3(nblk - 1, 1, nb), dim3(W), 0, st, items, N, (const T*)scratch);
 }
 
 // packed index of the symmetric entry (i, j), i <= j, behind the D mean components of a filtered state
@@ -169,6 +181,107 @@ __global__ __launch_bounds__(SS_THREADS) void ss_finish_kernel(const double* __r
     for (int k = 0; k < SS_THREADS; ++k) tot += sh[k];
     lml[z] = tot;
   }
+}
+
+
+// ---- gradients ---------------------------------------------------------------------------------------------------------------
+// The model of latent L with the tangent of parameter `seed` set: 0 = variance, 1 = lengthscale (d (1 / l) = -1 / l^2)
+template <int D>
+__device__ __forceinline__ SSModel<D, SSDual> ss_lat_dmodel(const SSLat& L, int seed) {
+  SSModel<D, SSDual> M;
+  ss_model<D, SSDual>(SSDual(L.var, seed == 0 ? 1.0 : 0.0), SSDual(L.inv_ls, seed == 0 ? 0.0 : -L.inv_ls * L.inv_ls), M);
+  return M;
+}
+
+// ss_fold_kernel on (value, tangent): blockIdx.y is the seeded parameter, the aggregates of (latent z, seed s) are item 2 z + s
+template <int D>
+__global__ __launch_bounds__(SS_THREADS) void ss_dfold_kernel(SSArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = blockIdx.y;
+  if (j >= a.nch) return;
+  const SSLat& L = a.lat[z];
+  const SSModel<D, SSDual> M = ss_lat_dmodel<D>(L, s);
+  const long long t0 = (long long)j * a.chunk;
+  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  SSFwd<D, SSDual> acc, el;
+  double xp = a.x[t0];
+  ss_fwd_element<D, SSDual>(M, t0 == 0, t0 == 0 ? 0.0 : xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
+  for (long long t = t0 + 1; t < t1; ++t) {
+    const double xt = a.x[t];
+    ss_fwd_element<D, SSDual>(M, false, xt - xp, L.w[t], L.r[t], el);
+    ss_fwd_combine<D, SSDual>(acc, el, acc);
+    xp = xt;
+  }
+  reinterpret_cast<SSFwd<D, SSDual>*>(a.dagg)[(size_t)(2 * z + s) * a.nch + j] = acc;
+}
+
+// ss_filter_kernel on (value, tangent): writes only the tangent of its log-density partial
+template <int D>
+__global__ __launch_bounds__(SS_THREADS) void ss_dfilter_kernel(SSArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = blockIdx.y;
+  if (j >= a.nch) return;
+  const SSLat& L = a.lat[z];
+  const SSModel<D, SSDual> M = ss_lat_dmodel<D>(L, s);
+  const long long t0 = (long long)j * a.chunk;
+  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  SSDual m[D], P[D][D];
+  if (j == 0) {
+    for (int i = 0; i < D; ++i) {
+      m[i] = 0.0;
+      for (int k = 0; k < D; ++k) P[i][k] = M.Pinf[i][k];
+    }
+  } else {
+    const SSFwd<D, SSDual>& pre = reinterpret_cast<const SSFwd<D, SSDual>*>(a.dagg)[(size_t)(2 * z + s) * a.nch + j - 1];
+    for (int i = 0; i < D; ++i) {
+      m[i] = pre.b[i];
+      for (int k = 0; k < D; ++k) P[i][k] = pre.C[i][k];
+    }
+  }
+  SSDual lp = 0.0;
+  double xp = t0 == 0 ? a.x[0] : a.x[t0 - 1];
+  for (long long t = t0; t < t1; ++t) {
+    const double xt = a.x[t];
+    lp += ss_filter_step<D, SSDual>(M, xt - xp, L.w[t], L.r[t], m, P);
+    xp = xt;
+  }
+  a.dpart[(size_t)(2 * z + s) * a.nch + j] = lp.t;
+}
+
+constexpr int SS_POINT_PER = 8;      // points per thread of ss_point_kernel
+
+// Per point, from the smoothed first-component mean mu and variance Ps (without the latent's mean): alpha_t = (r_t - mu_t) / w_t and
+// c_t = (w_t - Ps_t) / w_t^2, the t-th entry of C^-1 r and of diag C^-1 for C = K + diag(w) over the observed points: d lml / d r_t =
+// -alpha_t and d lml / d w_t = grad_w = (alpha^2 - c) / 2.  Both outputs are 0 at an unobserved point.  ppart[((z 4 + q) nblk) + block]: this block's sums of alpha,
+// w alpha^2, w c and grad_w, added in a fixed order (a thread its points in order, then a tree over the threads).
+__global__ __launch_bounds__(SS_THREADS) void ss_point_kernel(SSArgs a, double* __restrict__ alpha, double* __restrict__ grad_w,
+                                                              double* __restrict__ ppart) {
+  __shared__ double sh[4][SS_THREADS];
+  const int z = blockIdx.z, nblk = gridDim.x;
+  const SSLat& L = a.lat[z];
+  const double* sm = a.smean + (size_t)z * a.n;
+  const double* sv = a.svar + (size_t)z * a.n;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < SS_POINT_PER; ++k) {
+    const long long t = ((long long)blockIdx.x * SS_POINT_PER + k) * SS_THREADS + threadIdx.x;
+    if (t >= a.n) break;
+    const double w = L.w[t];
+    double al = 0.0, gw = 0.0;
+    if (w < INFINITY) {
+      al = (L.r[t] - sm[t]) / w;
+      const double c = (w - sv[t]) / (w * w);
+      gw = 0.5 * (al * al - c);
+      s[0] += al; s[1] += w * al * al; s[2] += w * c; s[3] += gw;
+    }
+    alpha[(size_t)z * a.n + t] = al;
+    grad_w[(size_t)z * a.n + t] = gw;
+  }
+  for (int q = 0; q < 4; ++q) sh[q][threadIdx.x] = s[q];
+  __syncthreads();
+  for (int off = SS_THREADS / 2; off > 0; off >>= 1) {
+    if (threadIdx.x < off)
+      for (int q = 0; q < 4; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) ppart[((size_t)z * 4 + threadIdx.x) * nblk + blockIdx.x] = sh[threadIdx.x][0];
 }
 
 template <int D>
@@ -253,10 +366,10 @@ __global__ __launch_bounds__(256) void ss_scatter_rows_kernel(const double* __re
   if (j < nsel) out[idx[j] + (size_t)o * n] = in[j + (size_t)o * nsel];
 }
 
-size_t scan_items(int nch) {         // items of every level below the first
+size_t scan_items(int nch, int W = SS_SCAN) {         // items of every level below the first
   size_t tot = 0;
   int N = nch;
-  while (N > SS_SCAN) { N = (N + SS_SCAN - 1) / SS_SCAN; tot += N; }
+  while (N > W) { N = (N + W - 1) / W; tot += N; }
   return tot;
 }
 
@@ -279,6 +392,17 @@ void smooth_D(const SSArgs& a, int nb, hipStream_t st) {
   hipLaunchKernelGGL(ss_rts_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
 }
 
+template <int D>
+void grad_D(const SSArgs& a, int nb, double* gtheta, hipStream_t st) {
+  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 2, nb);
+  hipLaunchKernelGGL(ss_dfold_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  typedef SSFwd<D, SSDual> E;
+  E* agg = reinterpret_cast<E*>(a.dagg);
+  scan_levels<D, E, FwdOp, false>(agg, a.nch, 2 * nb, agg + (size_t)2 * nb * a.nch, st);
+  hipLaunchKernelGGL(ss_dfilter_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  hipLaunchKernelGGL(ss_finish_kernel, dim3(2 * nb), dim3(SS_THREADS), 0, st, (const double*)a.dpart, a.nch, gtheta);
+}
+
 }  // namespace
 
 int ss_state_dim(int kind) { return kind == LMM_KERNEL_MATERN12 ? 1 : kind == LMM_KERNEL_MATERN32 ? 2 : kind == LMM_KERNEL_MATERN52 ? 3 : 0; }
@@ -291,6 +415,25 @@ size_t ss_fwd_agg_elems(int D, int nch) {
 size_t ss_bwd_agg_elems(int D, int nch) {
   const size_t e = D == 1 ? sizeof(SSBwd<1>) : D == 2 ? sizeof(SSBwd<2>) : sizeof(SSBwd<3>);
   return ((size_t)nch + scan_items(nch)) * (e / sizeof(double));
+}
+
+size_t ss_dual_agg_elems(int D, int nch) {
+  const size_t e = D == 1 ? sizeof(SSFwd<1, SSDual>) : D == 2 ? sizeof(SSFwd<2, SSDual>) : sizeof(SSFwd<3, SSDual>);
+  const int W = D == 1 ? ss_scan_width<SSFwd<1, SSDual>>() : D == 2 ? ss_scan_width<SSFwd<2, SSDual>>() : ss_scan_width<SSFwd<3, SSDual>>();
+  return 2 * ((size_t)nch + scan_items(nch, W)) * (e / sizeof(double));
+}
+int ss_point_blocks(int n) { return (n + SS_THREADS * SS_POINT_PER - 1) / (SS_THREADS * SS_POINT_PER); }
+
+void launch_ss_grad(const SSArgs& a, int D, int nb, double* gtheta, hipStream_t st) {
+  if (D == 1) grad_D<1>(a, nb, gtheta, st);
+  else if (D == 2) grad_D<2>(a, nb, gtheta, st);
+  else grad_D<3>(a, nb, gtheta, st);
+}
+
+void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, double* ppart, double* sums, hipStream_t st) {
+  const int nblk = ss_point_blocks(a.n);
+  hipLaunchKernelGGL(ss_point_kernel, dim3(nblk, 1, nb), dim3(SS_THREADS), 0, st, a, alpha, grad_w, ppart);
+  hipLaunchKernelGGL(ss_finish_kernel, dim3(4 * nb), dim3(SS_THREADS), 0, st, (const double*)ppart, nblk, sums);
 }
 
 void launch_ss_filter(const SSArgs& a, int D, int nb, double* lml, hipStream_t st) {

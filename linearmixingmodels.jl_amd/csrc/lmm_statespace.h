@@ -5,24 +5,62 @@
 //
 // Model: F is the companion matrix of (s + lam)^D, N = F + lam I is nilpotent (N^D = 0), A(dt) = exp(-lam dt) (I + N dt + N^2 dt^2 / 2),
 // Q(dt) = Pinf - A Pinf A', prior state N(0, Pinf), observation h = e_1'.
+//
+// The forward (filtering) arithmetic is also templated on its scalar type Sc.  Sc = double (the default) is the arithmetic of the value;
+// Sc = SSDual carries one tangent beside every value, which makes the same text the forward-mode derivative of the filter with respect
+// to one kernel parameter (the gradient of the log density with respect to variance and lengthscale).  The inputs x, the spacings dt,
+// the noise w and the data r stay plain doubles, and the branches (`first`, w = +Inf) do not depend on the parameters.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #define SS_HD __host__ __device__ __forceinline__
 
-template <int D>
+// value and tangent of one scalar; comparisons look at the value
+struct SSDual {
+  double v, t;
+  SSDual() = default;
+  SS_HD SSDual(double v_) : v(v_), t(0.0) {}
+  SS_HD SSDual(double v_, double t_) : v(v_), t(t_) {}
+};
+SS_HD SSDual operator-(SSDual a) { return SSDual(-a.v, -a.t); }
+SS_HD SSDual operator+(SSDual a, SSDual b) { return SSDual(a.v + b.v, a.t + b.t); }
+SS_HD SSDual operator+(SSDual a, double b) { return SSDual(a.v + b, a.t); }
+SS_HD SSDual operator+(double a, SSDual b) { return SSDual(a + b.v, b.t); }
+SS_HD SSDual operator-(SSDual a, SSDual b) { return SSDual(a.v - b.v, a.t - b.t); }
+SS_HD SSDual operator-(SSDual a, double b) { return SSDual(a.v - b, a.t); }
+SS_HD SSDual operator-(double a, SSDual b) { return SSDual(a - b.v, -b.t); }
+SS_HD SSDual operator*(SSDual a, SSDual b) { return SSDual(a.v * b.v, a.t * b.v + a.v * b.t); }
+SS_HD SSDual operator*(SSDual a, double b) { return SSDual(a.v * b, a.t * b); }
+SS_HD SSDual operator*(double a, SSDual b) { return SSDual(a * b.v, a * b.t); }
+SS_HD SSDual operator/(SSDual a, SSDual b) { const double q = a.v / b.v; return SSDual(q, (a.t - q * b.t) / b.v); }
+SS_HD SSDual operator/(SSDual a, double b) { return SSDual(a.v / b, a.t / b); }
+SS_HD SSDual operator/(double a, SSDual b) { const double q = a / b.v; return SSDual(q, -q * b.t / b.v); }
+SS_HD SSDual& operator+=(SSDual& a, SSDual b) { a.v += b.v; a.t += b.t; return a; }
+SS_HD SSDual& operator+=(SSDual& a, double b) { a.v += b; return a; }
+SS_HD SSDual& operator-=(SSDual& a, SSDual b) { a.v -= b.v; a.t -= b.t; return a; }
+SS_HD SSDual& operator-=(SSDual& a, double b) { a.v -= b; return a; }
+SS_HD SSDual exp(SSDual a) { const double e = exp(a.v); return SSDual(e, e * a.t); }
+SS_HD SSDual log(SSDual a) { return SSDual(log(a.v), a.t / a.v); }
+SS_HD bool operator<(SSDual a, SSDual b) { return a.v < b.v; }
+SS_HD bool operator>(SSDual a, SSDual b) { return a.v > b.v; }
+SS_HD bool operator<=(SSDual a, SSDual b) { return a.v <= b.v; }
+SS_HD bool operator>=(SSDual a, SSDual b) { return a.v >= b.v; }
+SS_HD bool operator==(SSDual a, SSDual b) { return a.v == b.v; }
+SS_HD bool operator!=(SSDual a, SSDual b) { return a.v != b.v; }
+
+template <int D, typename Sc = double>
 struct SSModel {
-  double lam;
-  double N[D][D], N2[D][D], Pinf[D][D];
+  Sc lam;
+  Sc N[D][D], N2[D][D], Pinf[D][D];
 };
 
 // lam = sqrt(2 nu) / lengthscale and the stationary covariance of (f, f', f'') for variance v
-template <int D>
-SS_HD void ss_model(double var, double inv_ls, SSModel<D>& M) {
-  const double lam = (D == 1 ? 1.0 : D == 2 ? 1.7320508075688772 : 2.23606797749979) * inv_ls;
+template <int D, typename Sc = double>
+SS_HD void ss_model(Sc var, Sc inv_ls, SSModel<D, Sc>& M) {
+  const Sc lam = (D == 1 ? 1.0 : D == 2 ? 1.7320508075688772 : 2.23606797749979) * inv_ls;
   M.lam = lam;
-  double F[D][D];
+  Sc F[D][D];
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) { F[i][j] = (j == i + 1) ? 1.0 : 0.0; M.Pinf[i][j] = 0.0; }
   if (D == 1) F[0][0] = -lam;
@@ -32,11 +70,11 @@ SS_HD void ss_model(double var, double inv_ls, SSModel<D>& M) {
     for (int j = 0; j < D; ++j) M.N[i][j] = F[i][j] + (i == j ? lam : 0.0);
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) {
-      double s = 0.0;
+      Sc s = 0.0;
       for (int k = 0; k < D; ++k) s += M.N[i][k] * M.N[k][j];
       M.N2[i][j] = s;
     }
-  const double l2 = lam * lam;
+  const Sc l2 = lam * lam;
   M.Pinf[0][0] = var;
   if (D == 2) M.Pinf[D - 1][D - 1] = l2 * var;
   if (D == 3) {
@@ -47,69 +85,70 @@ SS_HD void ss_model(double var, double inv_ls, SSModel<D>& M) {
 }
 
 // A(dt) and Q(dt); dt = 0 gives A = I and Q = 0 exactly
-template <int D>
-SS_HD void ss_AQ(const SSModel<D>& M, double dt, double A[D][D], double Q[D][D]) {
-  const double e = exp(-M.lam * dt), h = 0.5 * dt * dt;
+template <int D, typename Sc = double>
+SS_HD void ss_AQ(const SSModel<D, Sc>& M, double dt, Sc A[D][D], Sc Q[D][D]) {
+  const Sc e = exp(-M.lam * dt);
+  const double h = 0.5 * dt * dt;
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) A[i][j] = e * ((i == j ? 1.0 : 0.0) + M.N[i][j] * dt + (D > 2 ? M.N2[i][j] * h : 0.0));
-  double T[D][D];
+  Sc T[D][D];
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) {
-      double s = 0.0;
+      Sc s = 0.0;
       for (int k = 0; k < D; ++k) s += A[i][k] * M.Pinf[k][j];
       T[i][j] = s;
     }
   for (int i = 0; i < D; ++i)
     for (int j = i; j < D; ++j) {
-      double s = 0.0;
+      Sc s = 0.0;
       for (int k = 0; k < D; ++k) s += T[i][k] * A[j][k];
       Q[i][j] = Q[j][i] = M.Pinf[i][j] - s;
     }
 }
 
-template <int D>
-SS_HD void ss_mm(const double X[D][D], const double Y[D][D], double Z[D][D]) {      // Z = X Y
+template <int D, typename Sc = double>
+SS_HD void ss_mm(const Sc X[D][D], const Sc Y[D][D], Sc Z[D][D]) {      // Z = X Y
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) {
-      double s = 0.0;
+      Sc s = 0.0;
       for (int k = 0; k < D; ++k) s += X[i][k] * Y[k][j];
       Z[i][j] = s;
     }
 }
-template <int D>
-SS_HD void ss_mmt(const double X[D][D], const double Y[D][D], double Z[D][D]) {     // Z = X Y'
+template <int D, typename Sc = double>
+SS_HD void ss_mmt(const Sc X[D][D], const Sc Y[D][D], Sc Z[D][D]) {     // Z = X Y'
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) {
-      double s = 0.0;
+      Sc s = 0.0;
       for (int k = 0; k < D; ++k) s += X[i][k] * Y[j][k];
       Z[i][j] = s;
     }
 }
-template <int D>
-SS_HD void ss_sym(double X[D][D]) {
+template <int D, typename Sc = double>
+SS_HD void ss_sym(Sc X[D][D]) {
   for (int i = 0; i < D; ++i)
     for (int j = i + 1; j < D; ++j) X[i][j] = X[j][i] = 0.5 * (X[i][j] + X[j][i]);
 }
 
 // X^-1 of a general D x D matrix by cofactors (relative accuracy is invariant under the diagonal scalings that separate f, f', f'')
-template <int D>
-SS_HD void ss_inv(const double X[D][D], double Y[D][D]) {
+template <int D, typename Sc = double>
+SS_HD void ss_inv(const Sc X[D][D], Sc Y[D][D]) {
   if (D == 1) { Y[0][0] = 1.0 / X[0][0]; return; }
   if (D == 2) {
-    const double a = X[0][0], b = X[0][D - 1], c = X[D - 1][0], d = X[D - 1][D - 1];
-    const double r = 1.0 / (a * d - b * c);
+    const Sc a = X[0][0], b = X[0][D - 1], c = X[D - 1][0], d = X[D - 1][D - 1];
+    const Sc r = 1.0 / (a * d - b * c);
     Y[0][0] = d * r; Y[0][D - 1] = -b * r; Y[D - 1][0] = -c * r; Y[D - 1][D - 1] = a * r;
     return;
   }
-  double Cf[D][D];
+  Sc Cf[D][D];
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) {
       const int i1 = (i + 1) % D, i2 = (i + 2) % D, j1 = (j + 1) % D, j2 = (j + 2) % D;
       Cf[i][j] = X[i1][j1] * X[i2][j2] - X[i1][j2] * X[i2][j1];      // cofactor (cyclic indices carry the sign)
     }
-  double det = 0.0;
+  Sc det = 0.0;
   for (int j = 0; j < D; ++j) det += X[0][j] * Cf[0][j];
-  const double r = 1.0 / det;
+  const Sc r = 1.0 / det;
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) Y[i][j] = Cf[j][i] * r;
 }
@@ -148,17 +187,17 @@ SS_HD void ss_inv_spd(const double X[D][D], double Y[D][D]) {
 }
 
 // ---- forward (filtering) elements of Sarkka & Garcia-Fernandez, "Temporal parallelization of Bayesian smoothers" ------------------
-template <int D>
-struct SSFwd { double A[D][D], b[D], C[D][D], eta[D], J[D][D]; };
+template <int D, typename Sc = double>
+struct SSFwd { Sc A[D][D], b[D], C[D][D], eta[D], J[D][D]; };
 
 // The element of one point.  first: the prior takes the place of the transition (A = 0, Q = Pinf).  w = +Inf: unobserved.
-template <int D>
-SS_HD void ss_fwd_element(const SSModel<D>& M, bool first, double dt, double w, double r, SSFwd<D>& e) {
-  double A[D][D], Q[D][D];
+template <int D, typename Sc = double>
+SS_HD void ss_fwd_element(const SSModel<D, Sc>& M, bool first, double dt, double w, double r, SSFwd<D, Sc>& e) {
+  Sc A[D][D], Q[D][D];
   if (first) {
     for (int i = 0; i < D; ++i)
       for (int j = 0; j < D; ++j) { A[i][j] = 0.0; Q[i][j] = M.Pinf[i][j]; }
-  } else ss_AQ<D>(M, dt, A, Q);
+  } else ss_AQ<D, Sc>(M, dt, A, Q);
   if (!(w < INFINITY)) {
     for (int i = 0; i < D; ++i) {
       e.b[i] = 0.0; e.eta[i] = 0.0;
@@ -166,9 +205,9 @@ SS_HD void ss_fwd_element(const SSModel<D>& M, bool first, double dt, double w, 
     }
     return;
   }
-  const double Sinv = 1.0 / (Q[0][0] + w);
+  const Sc Sinv = 1.0 / (Q[0][0] + w);
   for (int i = 0; i < D; ++i) {
-    const double K = Q[i][0] * Sinv;
+    const Sc K = Q[i][0] * Sinv;
     e.b[i] = K * r;
     e.eta[i] = A[0][i] * r * Sinv;
     for (int j = 0; j < D; ++j) {
@@ -180,66 +219,66 @@ SS_HD void ss_fwd_element(const SSModel<D>& M, bool first, double dt, double w, 
 }
 
 // out = a (.) b with a the earlier run; out may alias a or b
-template <int D>
-SS_HD void ss_fwd_combine(const SSFwd<D>& a, const SSFwd<D>& b, SSFwd<D>& out) {
-  double T[D][D], Ti[D][D], Mx[D][D], Mp[D][D], X[D][D];
-  ss_mm<D>(a.C, b.J, T);
+template <int D, typename Sc = double>
+SS_HD void ss_fwd_combine(const SSFwd<D, Sc>& a, const SSFwd<D, Sc>& b, SSFwd<D, Sc>& out) {
+  Sc T[D][D], Ti[D][D], Mx[D][D], Mp[D][D], X[D][D];
+  ss_mm<D, Sc>(a.C, b.J, T);
   for (int i = 0; i < D; ++i) T[i][i] += 1.0;
-  ss_inv<D>(T, Ti);
-  ss_mm<D>(b.A, Ti, Mx);                      // M = A_j (I + C_i J_j)^-1
-  ss_mm<D>(Ti, a.A, X);                       // M' = A_i' (I + J_j C_i)^-1 = ((I + C_i J_j)^-1 A_i)'
+  ss_inv<D, Sc>(T, Ti);
+  ss_mm<D, Sc>(b.A, Ti, Mx);                      // M = A_j (I + C_i J_j)^-1
+  ss_mm<D, Sc>(Ti, a.A, X);                       // M' = A_i' (I + J_j C_i)^-1 = ((I + C_i J_j)^-1 A_i)'
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) Mp[i][j] = X[j][i];
-  SSFwd<D> o;
-  ss_mm<D>(Mx, a.A, o.A);
-  double u[D], v[D];
+  SSFwd<D, Sc> o;
+  ss_mm<D, Sc>(Mx, a.A, o.A);
+  Sc u[D], v[D];
   for (int i = 0; i < D; ++i) {
-    double s = a.b[i], t = b.eta[i];
+    Sc s = a.b[i], t = b.eta[i];
     for (int k = 0; k < D; ++k) { s += a.C[i][k] * b.eta[k]; t -= b.J[i][k] * a.b[k]; }
     u[i] = s; v[i] = t;
   }
   for (int i = 0; i < D; ++i) {
-    double s = b.b[i], t = a.eta[i];
+    Sc s = b.b[i], t = a.eta[i];
     for (int k = 0; k < D; ++k) { s += Mx[i][k] * u[k]; t += Mp[i][k] * v[k]; }
     o.b[i] = s; o.eta[i] = t;
   }
-  ss_mm<D>(Mx, a.C, X);
-  ss_mmt<D>(X, b.A, o.C);
-  ss_mm<D>(Mp, b.J, X);
-  ss_mm<D>(X, a.A, o.J);
+  ss_mm<D, Sc>(Mx, a.C, X);
+  ss_mmt<D, Sc>(X, b.A, o.C);
+  ss_mm<D, Sc>(Mp, b.J, X);
+  ss_mm<D, Sc>(X, a.A, o.J);
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) { o.C[i][j] += b.C[i][j]; o.J[i][j] += a.J[i][j]; }
-  ss_sym<D>(o.C); ss_sym<D>(o.J);
+  ss_sym<D, Sc>(o.C); ss_sym<D, Sc>(o.J);
   out = o;
 }
 
 // One step of the ordinary Kalman filter: (m, P) at the previous point -> (m, P) at this one.  Returns the point's log-density term
 // (0 for an unobserved point, which takes the predict step only).
-template <int D>
-SS_HD double ss_filter_step(const SSModel<D>& M, double dt, double w, double r, double m[D], double P[D][D]) {
-  double A[D][D], Q[D][D], T[D][D], mp[D];
-  ss_AQ<D>(M, dt, A, Q);
-  ss_mm<D>(A, P, T);
+template <int D, typename Sc = double>
+SS_HD Sc ss_filter_step(const SSModel<D, Sc>& M, double dt, double w, double r, Sc m[D], Sc P[D][D]) {
+  Sc A[D][D], Q[D][D], T[D][D], mp[D];
+  ss_AQ<D, Sc>(M, dt, A, Q);
+  ss_mm<D, Sc>(A, P, T);
   for (int i = 0; i < D; ++i) {
-    double s = 0.0;
+    Sc s = 0.0;
     for (int k = 0; k < D; ++k) s += A[i][k] * m[k];
     mp[i] = s;
     for (int j = i; j < D; ++j) {
-      double q = Q[i][j];
+      Sc q = Q[i][j];
       for (int k = 0; k < D; ++k) q += T[i][k] * A[j][k];
       P[i][j] = P[j][i] = q;
     }
   }
   for (int i = 0; i < D; ++i) m[i] = mp[i];
-  if (!(w < INFINITY)) return 0.0;
-  const double S = P[0][0] + w, Sinv = 1.0 / S, e = r - m[0];
-  double K[D], p0[D];
+  if (!(w < INFINITY)) return Sc(0.0);
+  const Sc S = P[0][0] + w, Sinv = 1.0 / S, e = r - m[0];
+  Sc K[D], p0[D];
   for (int i = 0; i < D; ++i) { p0[i] = P[0][i]; K[i] = P[i][0] * Sinv; }
   for (int i = 0; i < D; ++i) {
     m[i] += K[i] * e;
     for (int j = 0; j < D; ++j) P[i][j] -= K[i] * p0[j];
   }
-  ss_sym<D>(P);
+  ss_sym<D, Sc>(P);
   return -0.5 * (log(6.283185307179586 * S) + e * e * Sinv);
 }
 

@@ -939,6 +939,43 @@ def statespace_mean_and_var(fx: "FiniteGP", y, add_noise: bool = True, xs=None):
     return _statespace_unsorted(mean, perm, p, n, xs is not None), _statespace_unsorted(var, perm, p, n, xs is not None)
 
 
+class _NoStateSpaceMixingGradient(dict):
+    """The gradient dict of statespace_logpdf_and_gradient for data with NaN: "S" and "U" are not built (as _NoMixingGradient)."""
+
+    def __missing__(self, key):
+        if key in ("S", "U"):
+            raise NotImplementedError(f"statespace_logpdf_and_gradient: the gradient with respect to {key!r} is not built for data with NaN")
+        raise KeyError(key)
+
+
+def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = True) -> dict:
+    """Value and gradient of statespace_logpdf(fx, y) in O(n): {"value", "y", "sigma2", "S", "U", "gps"}, as logpdf_and_gradient returns
+    them for a prior OILMM.  "value" is bitwise statespace_logpdf(fx, y, with_regulariser); "y" is shaped and typed like y, in the
+    callers' order of points whatever the order of the inputs, and exactly 0 at NaN entries; "gps" (through _gps_grads) holds every
+    latent's "variance", "lengthscale" and "mean".  With NaN in y (points whose outputs are all NaN included) "S" and "U" raise
+    NotImplementedError, as after logpdf_and_gradient.  There is no gradient with respect to the inputs."""
+    y = _statespace_args(fx, y, "statespace_logpdf_and_gradient")
+    f, x = fx.f, fx.x
+    nan = _has_nan(y)
+    xa, ya, perm, n = _statespace_sorted(x.x.reshape(-1), y, x.out_dim)
+    L.ensure_init()
+    Ua, Sa, p, m = _H_args(f.H)
+    val, gs2 = C.c_double(), C.c_double()
+    gy, gS, gU = _alloc_like(ya, n * p), np.empty(m), np.empty(p * m)
+    gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.f.fs])
+    L.check(L.load().lmm_oilmm_logpdf_grad_statespace(L.Arr(xa).ptr, n, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), ga, 0, m,
+                                                      int(with_regulariser), C.byref(val), L.Arr(gy, True).ptr, C.byref(gs2),
+                                                      None if nan else L.Arr(gS, True).ptr, None if nan else L.Arr(gU, True).ptr, gg))
+    gy = _statespace_unsorted(gy, perm, p, n, False)
+    if L._is_torch(gy) and not L._is_torch(y):        # torch inputs x with a NumPy y
+        gy = gy.cpu().numpy()
+    out = {"value": val.value, "y": gy, "sigma2": gs2.value, "gps": _gps_grads(gg, ga, m, 1)}
+    if nan:
+        return _NoStateSpaceMixingGradient(out)
+    out.update(S=gS, U=gU.reshape(m, p).T.copy())
+    return out
+
+
 # Dense-H ILMM logpdf: allow the identical-kernel decoupled shortcut (exact; SURVEY.md section 3.2).  Set False to force
 # the reference's single (mn) x (mn) factorisation.  ILMM_LAST_PATH records which ran.
 ILMM_ALLOW_DECOUPLED = True

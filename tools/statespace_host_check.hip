@@ -1,0 +1,53 @@
+// statespace_host_check.hip -- the double and the SSDual instantiations of csrc/lmm_statespace.h run on the CPU, with the chunked schedule
+// of lmm_kernels_ss.hip (fold, a sequential scan of the aggregates, filter restarted from the prefix) for chunk = 1, 7, 64 and n, Matern12 /
+// 32 / 52, a quarter of the points unobserved and a run of equal inputs.  Checks that the value of the dual instantiation is bitwise the
+// double one's and that both tangents agree with central differences of the value (step 1e-5: 1e-6 relative).  A stand-alone program for
+// host sanitizers; it needs no GPU:
+//   hipcc -x hip --offload-arch=gfx950 -O1 -std=c++17 -I linearmixingmodels.jl_amd/csrc -Xarch_host -fsanitize=address,undefined \
+//         tools/statespace_host_check.hip -o statespace_host_check && ./statespace_host_check
+#include "lmm_statespace.h"
+#include <cstdio>
+#include <vector>
+#include <cmath>
+template <int D, typename Sc>
+Sc run(Sc var, Sc il, const std::vector<double>& x, const std::vector<double>& w, const std::vector<double>& r, int chunk) {
+  SSModel<D, Sc> M; ss_model<D, Sc>(var, il, M);
+  const int n = (int)x.size(), nch = (n + chunk - 1) / chunk;
+  std::vector<SSFwd<D, Sc>> agg(nch);
+  for (int j = 0; j < nch; ++j) {
+    int t0 = j * chunk, t1 = std::min(n, t0 + chunk);
+    SSFwd<D, Sc> acc, el;
+    ss_fwd_element<D, Sc>(M, t0 == 0, t0 == 0 ? 0.0 : x[t0] - x[t0 - 1], w[t0], r[t0], acc);
+    for (int t = t0 + 1; t < t1; ++t) { ss_fwd_element<D, Sc>(M, false, x[t] - x[t - 1], w[t], r[t], el); ss_fwd_combine<D, Sc>(acc, el, acc); }
+    agg[j] = acc;
+  }
+  for (int j = 1; j < nch; ++j) ss_fwd_combine<D, Sc>(agg[j - 1], agg[j], agg[j]);
+  Sc tot = 0.0;
+  for (int j = 0; j < nch; ++j) {
+    int t0 = j * chunk, t1 = std::min(n, t0 + chunk);
+    Sc m[D], P[D][D];
+    for (int i = 0; i < D; ++i) { m[i] = j ? agg[j - 1].b[i] : Sc(0.0); for (int k = 0; k < D; ++k) P[i][k] = j ? agg[j - 1].C[i][k] : M.Pinf[i][k]; }
+    double xp = t0 == 0 ? x[0] : x[t0 - 1];
+    for (int t = t0; t < t1; ++t) { tot += ss_filter_step<D, Sc>(M, x[t] - xp, w[t], r[t], m, P); xp = x[t]; }
+  }
+  return tot;
+}
+template <int D> int check() {
+  const int n = 200; std::vector<double> x(n), w(n), r(n);
+  unsigned s = 12345u + D; auto u = [&]() { s = s * 1664525u + 1013904223u; return (s >> 8) / 16777216.0; };
+  double xx = 0; for (int t = 0; t < n; ++t) { xx += 0.7 * std::pow(10.0, -2.0 * u()); x[t] = xx; w[t] = u() < 0.25 ? INFINITY : 0.05 + 0.45 * u(); r[t] = 2 * u() - 1; }
+  x[11] = x[10]; x[12] = x[10];
+  const double v = 1.3, ell = 0.7, il = 1 / ell; int bad = 0;
+  for (int chunk : {1, 7, 64, 200}) {
+    double val = run<D, double>(v, il, x, w, r, chunk);
+    SSDual gv = run<D, SSDual>(SSDual(v, 1.0), SSDual(il, 0.0), x, w, r, chunk);
+    SSDual gl = run<D, SSDual>(SSDual(v, 0.0), SSDual(il, -il * il), x, w, r, chunk);
+    const double h = 1e-5;
+    double fv = (run<D, double>(v + h, il, x, w, r, chunk) - run<D, double>(v - h, il, x, w, r, chunk)) / (2 * h);
+    double fl = (run<D, double>(v, 1 / (ell + h), x, w, r, chunk) - run<D, double>(v, 1 / (ell - h), x, w, r, chunk)) / (2 * h);
+    std::printf("D=%d chunk=%3d val=%.15g dual.v==val:%d dv %.12g fd %.12g dl %.12g fd %.12g\n", D, chunk, val, gv.v == val && gl.v == val, gv.t, fv, gl.t, fl);
+    if (!(gv.v == val) || std::fabs(gv.t - fv) > 1e-6 * std::fabs(fv) + 1e-7 || std::fabs(gl.t - fl) > 1e-6 * std::fabs(fl) + 1e-7) ++bad;
+  }
+  return bad;
+}
+int main() { int bad = check<1>() + check<2>() + check<3>(); std::printf("bad=%d\n", bad); return bad != 0; }
