@@ -771,6 +771,9 @@ int lmm_dev_gemm_nt_sub(double* C, int ldc, const double* A, int lda, const doub
  * once).  Test hook of the switches: on = 0 / 1, min_k >= 128 (updates with K >= min_k are emulated), 8 <= nmod <= 16 moduli;
  * on < 0 goes back to the env defaults. */
 int lmm_dev_set_f64_emul(int on, int min_k, int nmod);
+/* Test hook: the emulation's GEMM is a persistent kernel of min(work items, CUs) workgroups; wgs >= 1 caps that grid (a small shape
+ * then makes one workgroup walk several tiles), 0 goes back to the default.  Results do not depend on it. */
+int lmm_dev_set_emul_gemm_workgroups(int wgs);
 /* C[MxN] -= A[MxK] * A[0:N, :]^T for i >= j only (column-major, device pointers, one matrix) through the emulation kernels.
  * M >= N, K a multiple of 128, K <= 16384.  |error_ij| <= 4 K 2^-b amax_i amax_j + rounding of C, b = the bit budget for K. */
 int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N, int K, int nmod);
@@ -784,6 +787,10 @@ int lmm_dev_emul_host(const double* A, int lda, const double* B, int ldb, int M,
  * out[i * nmod + t] = v[i] modulo the t-th modulus as an int8 (congruent, inside the symmetric range).  exhaustive (may be NULL, 2
  * words): the reduction behind it run on every input it can see, every odd modulus, both signs: [0] cases, [1] failures. */
 int lmm_dev_emul_residues(const long long* v, int count, int nmod, signed char* out, long long* exhaustive);
+/* Host-only (no GPU, no lmm_init needed): the reduction of the emulation's GEMM epilogue on `count` int32 accumulators |x| <= 2^28:
+ * out[i * nmod + t] = x[i] modulo the t-th modulus as an int8 (congruent, inside the symmetric range).  exhaustive (may be NULL, 2
+ * words): its float step run on every folded value it can see, every modulus: [0] cases, [1] failures. */
+int lmm_dev_emul_acc_residues(const int* x, int count, int nmod, signed char* out, long long* exhaustive);
 /* Gram assembly of one latent into a padded factor matrix (lower triangle + pad identity). */
 int lmm_dev_gram(double* A, int ld, int nrows, int ncols, const double* x, int d, int n,
                  const lmm_gp_t* gp, double diag_add);

@@ -757,7 +757,7 @@ struct NodeFlags { int* p = nullptr; int stride = 0; int min_k = 0, max_k = 1 <<
 static int g_emul_on = -1, g_emul_mink = -1, g_emul_nmod = LMM_EMUL_MAXMOD;
 static void emul_switches() {
   if (g_emul_on < 0) { const char* e = getenv("LMM_F64_EMUL"); g_emul_on = e ? (atoi(e) != 0) : 1; }
-  if (g_emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_emul_mink = e ? std::max(128, atoi(e)) : 4096; }      // measured crossover: K = 2048 is slower emulated
+  if (g_emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_emul_mink = e ? std::max(128, atoi(e)) : 4096; }      // at 2048 C2 and configs[3] gain, but C1 (one 2048^3 update of 8 latents) loses
 }
 // scratch bytes of the widest emulated update of the recursion over the columns [j0, j0 + w)
 static size_t emul_need(int NR, int j0, int w, int mink, int G, int nmod) {
@@ -5528,6 +5528,14 @@ int lmm_dev_set_f64_emul(int on, int min_k, int nmod) {
   g_emul_on = on ? 1 : 0; g_emul_mink = min_k; g_emul_nmod = nmod;
   return LMM_OK;
 }
+// Test hook: at most wgs workgroups in the persistent grid of the emulation's GEMM (0: the default, one per CU), so that a small shape
+// makes one workgroup walk several tiles.
+int lmm_dev_set_emul_gemm_workgroups(int wgs) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (wgs < 0) return fail(LMM_ERR_ARG, "lmm_dev_set_emul_gemm_workgroups: wgs >= 0");
+  emul_set_gemm_workgroups(wgs);
+  return LMM_OK;
+}
 // C (M x N, lower trapezoid i >= j) -= A A[0:N]' through the emulation kernels: one matrix, device pointers.
 int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N, int K, int nmod) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -5580,7 +5588,7 @@ int lmm_dev_emul_host(const double* A, int lda, const double* B, int ldb, int M,
       for (int t = 0; t < nmod; ++t) {
         int acc = 0;
         for (int k = 0; k < K; ++k) acc += (int)ra.res[((size_t)t * M + i) * K + k] * (int)rb.res[((size_t)t * N + j) * K + k];
-        u[t] = emul_mod_sym(acc, c.p[t], 1.0f / (float)c.p[t]);
+        u[t] = (int)(int8_t)emul_acc_residue(acc, emul_fold_const(c.p[t]), (float)c.p[t], 1.0f / (float)c.p[t]);
       }
       out[i + (size_t)j * ldo] = std::ldexp(emul_crt(u, c) * ra.sc[i] * rb.sc[j], ra.ex[i] + rb.ex[j]);
     }
@@ -5610,6 +5618,33 @@ int lmm_dev_emul_residues(const long long* v, int count, int nmod, signed char* 
       for (int x = 0; x <= kEmulDot.xmax[t]; ++x, ++cases) {
         const int rp = emul_reduce_odd(LMM_EMUL_MAGIC_BITS + (unsigned)x, 1.0f, t), rn = emul_reduce_odd(LMM_EMUL_MAGIC_BITS + (unsigned)x, -1.0f, t);
         if ((rp - x) % p != 0 || rp < -half || rp > half || (rn + x) % p != 0 || rn < -half || rn > half) ++bad;
+      }
+    }
+    exhaustive[0] = cases; exhaustive[1] = bad;
+  }
+  return LMM_OK;
+}
+// Host-only (no GPU, no lmm_init needed): the GEMM epilogue's reduction (emul_acc_residue, lmm_emul.h) of `count` int32 accumulators,
+// |x| <= 2^28: out[i nmod + t] = the int8 residue of x[i] modulo the t-th modulus.  exhaustive (may be NULL, 2 words): the float step
+// (emul_fold_reduce) run on every value y of the folded accumulator it can see, |y| <= emul_acc_fold_max, for every modulus -- [0] = the
+// number of (modulus, y) cases, [1] = how many gave a byte that is not y's residue in [-(p - 1) / 2, (p - 1) / 2] ([-128, 127] for 256).
+int lmm_dev_emul_acc_residues(const int* x, int count, int nmod, signed char* out, long long* exhaustive) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (count < 0 || (count > 0 && (!x || !out)) || nmod < LMM_EMUL_MINMOD || nmod > LMM_EMUL_MAXMOD) return fail(LMM_ERR_ARG, "lmm_dev_emul_acc_residues: bad arguments");
+  for (int i = 0; i < count; ++i) {
+    if (x[i] > (1 << 28) || x[i] < -(1 << 28)) return fail(LMM_ERR_ARG, "lmm_dev_emul_acc_residues: |x| <= 2^28");
+    for (int t = 0; t < nmod; ++t) {
+      const int p = kEmulModuli[t];
+      out[(size_t)i * nmod + t] = (signed char)(int8_t)emul_acc_residue(x[i], emul_fold_const(p), (float)p, 1.0f / (float)p);
+    }
+  }
+  if (exhaustive) {
+    long long cases = 0, bad = 0;
+    for (int t = 0; t < LMM_EMUL_MAXMOD; ++t) {
+      const int p = kEmulModuli[t], lo = -(p / 2), ymax = emul_acc_fold_max(emul_fold_const(p));
+      for (int y = -ymax; y <= ymax; ++y, ++cases) {
+        const int r = (int)(int8_t)emul_fold_reduce(LMM_EMUL_MAGIC_BITS + (unsigned)y, (float)p, 1.0f / (float)p);
+        if ((r - y) % p != 0 || r < lo || r > lo + p - 1) ++bad;
       }
     }
     exhaustive[0] = cases; exhaustive[1] = bad;

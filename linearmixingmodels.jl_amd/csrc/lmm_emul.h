@@ -73,23 +73,6 @@ LMM_HD inline int emul_row_exp(double amax) {
 }
 // a' = trunc(a 2^sh), sh = b - e_row: an exact power-of-two scaling, |a'| <= 2^b
 LMM_HD inline long long emul_trunc(double a, int sh) { return (long long)ldexp(a, sh); }
-// v mod p in the symmetric range ([-128, 127] for p = 256; +128 is returned as 128 and wraps to -128 in the int8 store)
-LMM_HD inline int emul_mod_sym(int x, int p, float rp) {
-  // |x| < 2^29: the float quotient is off by less than 0.5, so one correction each way lands in [lo, lo + p - 1]; |q| < 2^23 and
-  // p <= 256, so the 24-bit multiply is exact
-#if defined(__HIP_DEVICE_COMPILE__)
-  const int q = __float2int_rn((float)x * rp);
-  int r = x - __mul24(q, p);
-#else
-  const int q = (int)lrintf((float)x * rp);
-  int r = x - q * p;
-#endif
-  const int lo = -(p / 2);
-  r += (r < lo) ? p : 0;
-  r -= (r > lo + p - 1) ? p : 0;
-  return r;
-}
-
 // ---- the convert kernel's residue step: no branch, no division, no 32-bit multiply per modulus ----
 // |v| <= 2^58 is cut into its 8 bytes d_i.  For an odd modulus p, x = sum_i d_i (256^i mod p) <= 8 255 (p - 1) < 2^19 is congruent
 // to |v|; the eight products are two 4-byte dot products against the packed constants lo and hi.  q = rint(x fl(1 / p)) is THE
@@ -154,24 +137,70 @@ LMM_HD inline void emul_residues(long long v, int* r) {
   for (int t = 1; t < NMOD; ++t) r[t] = emul_reduce_odd(emul_udot4(hi, kEmulDot.hi[t], emul_udot4(lo, kEmulDot.lo[t], LMM_EMUL_MAGIC_BITS)), sgn, t) & 0xFF;
 }
 
+// ---- the GEMM kernel's epilogue: an int32 accumulator, |x| <= 2^28 (K <= 16384 products of int8), modulo p ----
+// x = hi 2^16 + lo with hi = x >> 16 (arithmetic, |hi| <= 2^12) and 0 <= lo < 2^16.  With c = 2^16 mod p in the symmetric range
+// (|c| <= 127), y = hi c + lo is congruent to x and |y| <= 2^12 127 + 65535 < 2^19.2.  For an odd p, q = rint(y fl(1 / p)) is THE
+// nearest integer to y / p: y is exact in float, the product carries two roundings of 2^-24 each, so it is off by less than
+// 2^-23 |y| / p < 2^-23 2^19.2 / 193 < 2^-11.3, and y / p is at least 1 / (2 p) >= 1 / 510 > 2^-9 away from every half-integer.  So
+// r = y - q p lies in [-(p - 1) / 2, (p - 1) / 2]: the symmetric residue, with no correction step.  The float steps run on MAGIC + y
+// (bits LMM_EMUL_MAGIC_BITS + y for |y| < 2^22), and fma(-q, p, MAGIC + y) = MAGIC + r is exact, so the low byte of its bit pattern
+// is r as an int8 and no int <-> float conversion is issued.  p = 256 takes the same steps: c = 0, y = lo, and whichever way the
+// tie at lo mod 256 = 128 rounds, r = -+128 is congruent to x and has the low byte of x, which is the int8 residue in [-128, 127].
+LMM_HD inline int emul_fold_const(int p) {
+  const int r = 65536 % p;
+  return r > p / 2 ? r - p : r;
+}
+// LMM_EMUL_MAGIC_BITS + y: lo is ORed into the zero low half of the constant, and hi c fits the 24-bit multiply-add
+LMM_HD inline unsigned emul_acc_fold(int x, int c) {
+  const int lo = (int)(((unsigned)x & 0xFFFFu) | LMM_EMUL_MAGIC_BITS);
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (unsigned)(__mul24(x >> 16, c) + lo);
+#else
+  return (unsigned)((x >> 16) * c + lo);
+#endif
+}
+// the largest |y| the quotient can see for |x| <= 2^28
+LMM_HD inline int emul_acc_fold_max(int c) { return 4096 * (c < 0 ? -c : c) + 65535; }
+// y mod p as an int8 bit pattern in the low byte, given yb = LMM_EMUL_MAGIC_BITS + y, |y| < 2^22; pf = (float)p, rp = 1.0f / pf
+LMM_HD inline unsigned emul_fold_reduce(unsigned yb, float pf, float rp) {
+  const float ym = emul_bits_as_float(yb);                                     // MAGIC + y
+  const float q = rintf((ym - LMM_EMUL_MAGIC) * rp);
+  const float rm = fmaf(-q, pf, ym);                                           // MAGIC + (y - q p)
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __float_as_uint(rm) & 0xFFu;
+#else
+  unsigned u;
+  __builtin_memcpy(&u, &rm, 4);
+  return u & 0xFFu;
+#endif
+}
+// x mod p as an int8 bit pattern in the low byte; c = emul_fold_const(p)
+LMM_HD inline unsigned emul_acc_residue(int x, int c, float pf, float rp) { return emul_fold_reduce(emul_acc_fold(x, c), pf, rp); }
+
 // The integer X, |X| < P / 2, with X = u_t mod p_t for all t, rounded once to Float64.  S1 and S2 are exact (41-bit chunks, 8-bit
 // residues, 16 terms); S1 - q P1 and S2 - q P2 are exact; their sum rounds X to 53 bits; the third term is below one ulp of P.
 LMM_HD inline double emul_crt_at(double S1, double S2, double S3, double q, const EmulConst& c) {
   return ((S1 - q * c.P1) + (S2 - q * c.P2)) + (S3 - q * c.P3);
 }
-LMM_HD inline double emul_crt(const int* u, const EmulConst& c) {
-  double S1 = 0.0, S2 = 0.0, S3 = 0.0;
-#pragma unroll
-  for (int t = 0; t < LMM_EMUL_MAXMOD; ++t)
-    if (t < c.nmod) {
-      const double ut = (double)u[t];
-      S1 += ut * c.w1[t];
-      S2 += ut * c.w2[t];
-      S3 += ut * c.w3[t];
-    }
+// one modulus' term of the three sums, and the reconstruction from them: emul_crt in two pieces, for a caller that runs the sums of
+// several outputs side by side (the combine kernel)
+LMM_HD inline void emul_crt_term(int u, int t, const EmulConst& c, double& S1, double& S2, double& S3) {
+  const double ut = (double)u;
+  S1 += ut * c.w1[t];
+  S2 += ut * c.w2[t];
+  S3 += ut * c.w3[t];
+}
+LMM_HD inline double emul_crt_finish(double S1, double S2, double S3, const EmulConst& c) {
   double q = rint((S1 + S2) * c.Pinv);
   double X = emul_crt_at(S1, S2, S3, q, c);
   if (X > c.Phalf) X = emul_crt_at(S1, S2, S3, q + 1.0, c);
   else if (X < -c.Phalf) X = emul_crt_at(S1, S2, S3, q - 1.0, c);
   return X;
+}
+LMM_HD inline double emul_crt(const int* u, const EmulConst& c) {
+  double S1 = 0.0, S2 = 0.0, S3 = 0.0;
+#pragma unroll
+  for (int t = 0; t < LMM_EMUL_MAXMOD; ++t)
+    if (t < c.nmod) emul_crt_term(u[t], t, c, S1, S2, S3);
+  return emul_crt_finish(S1, S2, S3, c);
 }

@@ -164,6 +164,7 @@ bool launch_gemm32w(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
 // M >= N, K a multiple of 128 within the int32 accumulator bound.  Matrices go through `scratch` (emul_scratch_bytes) in groups of G.
 bool emul_shape_ok(int M, int N, int K);
 size_t emul_scratch_bytes(int M, int N, int K, int G, int nmod);
+void emul_set_gemm_workgroups(int wgs);      // cap of the persistent GEMM grid (tests); 0: one workgroup per CU
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
                               int G, int nmod, void* scratch, hipStream_t st);      // the first HIP error of its host-side calls
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,

@@ -3,8 +3,9 @@
 //   1. emul_rowmax_kernel + emul_convert_kernel: per panel row the exponent e_i = ceil(log2 max_k |a_ik|), the integers
 //      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows;
 //   2. emul_gemm_kernel: one int8 SYRK-shaped GEMM per (matrix, modulus) on 256 x 256 tiles of the lower trapezoid, int32
-//      accumulators, reduced mod p to one byte per output (tools/i8_gemm_probe.hip holds a copy, i8_syrk_mod_kernel_pf, beside the
-//      kernel this one replaced; the probe stands alone: a change here has to be made there too before its numbers speak for this kernel);
+//      accumulators, reduced mod p to one byte per output, as a persistent kernel (tools/i8_gemm_probe.hip holds a copy,
+//      i8_syrk_mod_kernel_ps, beside the kernels this one replaced; the probe stands alone: a change here has to be made there too
+//      before its numbers speak for this kernel);
 //   3. emul_combine_kernel: CRT reconstruction in Float64 (lmm_emul.h) and C_ij -= X 2^(e_i + e_j - 2b) for i >= j.
 // Integer sums are exact in any order: the result is bitwise reproducible.
 #include "lmm_internal.h"
@@ -124,54 +125,91 @@ __device__ __forceinline__ void glds16(const int8_t* src, int8_t* lds_wave_base)
 
 // One batch item = one (matrix, modulus): U[item][j][i] = (sum_k R[item][i][k] R[item][j][k]) mod p, i contiguous.
 //   workgroup tile 256 x 256 x 128, 8 waves as 2 (M) x 4 (N), v_mfma_i32_16x16x64_i8 (wave tile 128 x 64 = 8 x 4 accumulators);
-//   two LDS stages of 64 KiB filled by global_load_lds_dwordx4 (tile t + 1 in flight while tile t is multiplied);
+//   two LDS stages of 64 KiB filled by global_load_lds_dwordx4 (stage s + 1 in flight while stage s is multiplied);
 //   LDS rows are 128 B; the 16-B chunk index is XORed with (row >> 1) & 7 on the SOURCE address and on the fragment read, so every
 //   ds_read_b128 lane group hits 16 distinct 16-B slots of the 256-B bank row.
 // Both operands are fragment-loaded the same way (lane l: row l & 15, bytes 16 (l >> 4) .. + 15 of the 64-deep k range), so the k
 // order inside an MFMA is the same for A and B whatever the hardware's k map is.  Mp, Np multiples of 256, K of 128: no edges.
 //
-// The K loop: one K step is four phases of 16 MFMAs, (ks, mh) = the 64-byte half of the k range x the upper / lower 4 of the wave's 8
-// row fragments.  The fragments of a phase are read into registers in the MIDDLE of the phase before it, between its two groups of 8
+// Persistent: the grid is min(work ids, CUs) workgroups (emul_set_gemm_workgroups caps it), a work id = an (item, tile) pair in the
+// order item-major, tile list inside.  Blocks b and b + 8 share an XCD: XCD b & 7 owns a contiguous range of ids and its w workgroups
+// walk it from (b >> 3) with stride w, so at any moment the workgroups of an XCD sit on w consecutive ids, one supertile.  The walk
+// is static: no workgroup waits for, or reads anything written by, another one.
+//
+// The K steps of the tiles a workgroup walks form ONE stream of stages s = 0, 1, 2, ..; stage s lives in buffer s & 1 (not kt & 1:
+// nk may be odd).  A staging cursor (tile base pointers, k offset) runs two stages ahead of the MFMAs and steps into the next work
+// id when it has issued a tile's last K step, so the last two K steps of a tile stage the first two of the next one (with nk = 1
+// the cursor is two TILES ahead), and between the last MFMA of a tile and the first of the next only the epilogue stands, with the
+// next tile's loads and its first fragment reads issued above it.
+//
+// One K step is four phases of 16 MFMAs, (ks, mh) = the 64-byte half of the k range x the upper / lower 4 of the wave's 8 row
+// fragments.  The fragments of a phase are read into registers in the MIDDLE of the phase before it, between its two groups of 8
 // MFMAs, so they are 8 MFMAs old when the wait before their first use comes (the compiler waits with lgkmcnt(0) there, so reads
 // issued right before that wait would be waited for too).  sched_barrier(0) pins that order: left alone, the scheduler sinks the
-// reads down to their uses.  The one barrier of a K step stands between phases 3 and 4.  Stage t lives in buffer t & 1.
+// reads down to their uses.  The one barrier of a K step stands between phases 3 and 4.
 //
-//   phase of step t | MFMAs use (registers)        | ds_reads issued (buffer)                 | global_load_lds issued
-//   1 (ks 0, mh 0)  | a[0..3], b[0..3]   of t      | a[4..7] ks 0 of t  (t & 1)               |
-//   2 (ks 0, mh 1)  | a[4..7], b[0..3]   of t      | a[0..3], b[0..3] ks 1 of t  (t & 1)      |
-//   3 (ks 1, mh 0)  | a[0..3]', b[0..3]' of t      | a[4..7] ks 1 of t  (t & 1): the LAST read of buffer t & 1
-//   -- s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier: every wave holds all its fragments of stage t in registers, and every wave's
-//      loads of stage t + 1 (issued one whole K step earlier, at this point of step t - 1) have landed in buffer (t + 1) & 1 --
-//   4 (ks 1, mh 1)  | a[4..7]', b[0..3]' of t      | a[0..3], b[0..3] ks 0 of t + 1 ((t+1)&1) | stage t + 2 into buffer t & 1
+//   phase of stage s | MFMAs use (registers)        | ds_reads issued (buffer)                 | global_load_lds issued
+//   1 (ks 0, mh 0)   | a[0..3], b[0..3]   of s      | a[4..7] ks 0 of s  (s & 1)               |
+//   2 (ks 0, mh 1)   | a[4..7], b[0..3]   of s      | a[0..3], b[0..3] ks 1 of s  (s & 1)      |
+//   3 (ks 1, mh 0)   | a[0..3]', b[0..3]' of s      | a[4..7] ks 1 of s  (s & 1): the LAST read of buffer s & 1
+//   -- s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier: every wave holds all its fragments of stage s in registers, and every wave's
+//      loads of stage s + 1 (issued one whole K step earlier, at this point of stage s - 1) have landed in buffer (s + 1) & 1 --
+//   4 (ks 1, mh 1)   | a[4..7]', b[0..3]' of s      | a[0..3], b[0..3] ks 0 of s + 1 ((s+1)&1) | stage s + 2 into buffer s & 1
+//   -- after the last stage of a tile: the epilogue of that tile (registers and global stores only) --
 //
-//   read after write: buffer (t + 1) & 1 is first read in phase 4 of step t, after the wait-plus-barrier that retires stage t + 1.
-//   write after read: buffer t & 1 is restaged in phase 4 of step t, after the barrier every wave reaches only with its last reads
-//   of that buffer (phase 3) complete.  One stage is in flight at a time, so the wait is vmcnt(0); it waits for loads that are one
-//   K step (64 MFMAs per wave) old.  nk = 1 and 2: the prologue stages tiles 0 and 1, the loop stages t + 2 < nk only.
+//   read after write: buffer (s + 1) & 1 is first read in phase 4 of stage s, after the wait-plus-barrier that retires stage s + 1.
+//   write after read: buffer s & 1 is restaged in phase 4 of stage s, after the barrier every wave reaches only with its last reads
+//   of that buffer (phase 3) complete.  Neither argument looks at which tile a stage belongs to: stages s, s + 1, s + 2 may lie in
+//   one, two or three tiles, and the epilogue touches no LDS and stands after phase 4 of a stage and before phase 1 of the next,
+//   where the schedule has no LDS ordering to keep.  One stage is in flight at a time, so the wait is vmcnt(0); it waits for loads
+//   that are one K step (64 MFMAs per wave) old, and after a tile boundary also for the epilogue's 32 stores per lane, as old.
+//   The prologue (once per workgroup) stages 0, waits, and stages 1 if the walk has a second stage at all.
 __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
-                                                           int Mp, int Np, int K, EmulConst c) {
+                                                           int nids, int Mp, int Np, int K, EmulConst c) {
   __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
-  // blocks b and b + 8 share an XCD: give each XCD a contiguous range of work ids, so that its 32 resident blocks are one supertile
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-  const int item = wg / ntiles;
-  const int2 t = tiles[wg - item * ntiles];
-  const int8_t* Rb = R + (size_t)item * Mp * K;
-  const int8_t* srcA[4];
-  const int8_t* srcB[4];
+  // the walk of this workgroup: ids first, first + step, .. (cnt of them) of its XCD's range; fewer than 8 workgroups split the ids
+  // among themselves
+  const int nwg = gridDim.x, parts = nwg < 8 ? nwg : 8, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int step = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
+  const int qi = nids / parts, ri = nids - qi * parts;
+  const int first = xcd * qi + (xcd < ri ? xcd : ri) + slot, span = qi + (xcd < ri ? 1 : 0) - slot;
+  const int cnt = span > 0 ? (span + step - 1) / step : 0;
+  if (cnt == 0) return;
+  // source offsets of a lane's four 16-byte loads of one operand, from the tile's first row at k = 0
+  unsigned roff[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int row = wid * 32 + q * 8 + (lane >> 3), chunk = (lane & 7) ^ ((row >> 1) & 7);
-    srcA[q] = Rb + ((size_t)t.x * TILE + row) * K + chunk * 16;
-    srcB[q] = Rb + ((size_t)t.y * TILE + row) * K + chunk * 16;
+    roff[q] = (unsigned)row * (unsigned)K + chunk * 16;
   }
-  auto stage = [&](int buf, int k0) {
+  // the staging cursor: operand panels of the cn-th work id of the walk, next k offset ck; (pitem, pt) is the (cn + 1)-th work id,
+  // loaded one tile ahead so that stepping into it waits for no load
+  const int8_t* cA = nullptr;
+  const int8_t* cB = nullptr;
+  int cn = 0, ck = 0, pitem = 0;
+  int2 pt = make_int2(0, 0);
+  auto cursor_peek = [&](int idn) {
+    pitem = idn / ntiles;
+    pt = tiles[idn - pitem * ntiles];
+  };
+  auto cursor_tile = [&]() {
+    const int8_t* Rb = R + (size_t)pitem * Mp * K;
+    cA = Rb + (size_t)pt.x * TILE * K;
+    cB = Rb + (size_t)pt.y * TILE * K;
+    if (cn + 1 < cnt) cursor_peek(first + (cn + 1) * step);
+  };
+  auto stage_next = [&](int buf) {      // cn < cnt
     int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) glds16(srcA[q] + k0, base + q * 1024);
+    for (int q = 0; q < 4; ++q) glds16(cA + ck + roff[q], base + q * 1024);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) glds16(srcB[q] + k0, base + TILE * BK + q * 1024);
+    for (int q = 0; q < 4; ++q) glds16(cB + ck + roff[q], base + TILE * BK + q * 1024);
+    ck += BK;
+    if (ck == K) {
+      ck = 0; ++cn;
+      if (cn < cnt) cursor_tile();
+    }
   };
   const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
   // byte offset of a fragment in its stage: (row 128) + ((ks 4 + fk) ^ (row >> 1) & 7) 16 with row = 16 m + frow (+ the wave's first
@@ -183,10 +221,12 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
   for (int m = 0; m < 8; ++m)
 #pragma unroll
     for (int n = 0; n < 4; ++n) acc[m][n] = (v4i){0, 0, 0, 0};
-  stage(0, 0);
+  cursor_peek(first);
+  cursor_tile();
+  stage_next(0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (nk > 1) stage(1, BK);
+  if (cn < cnt) stage_next(1);
   v4i alo[4], ahi[4], b[4], alo1[4], ahi1[4], b1[4];
 #pragma unroll
   for (int f = 0; f < 4; ++f) { alo[f] = frag(lds, offA, 0, f); b[f] = frag(lds, offB, 0, f); }
@@ -195,73 +235,111 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
   _Pragma("unroll") for (int m = 2 * (h); m < 2 * (h) + 2; ++m)                                                                    \
   _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + m][n], 0, 0, 0)
 #define EMUL_PIN() __builtin_amdgcn_sched_barrier(0)
-  for (int kt = 0; kt < nk; ++kt) {
-    const int8_t* cur = lds + (kt & 1) * STAGE_BYTES;
-    const int8_t* nxt = lds + ((kt + 1) & 1) * STAGE_BYTES;
-    EMUL_MMA8(alo, b, 0, 0); EMUL_PIN();      // phase 1
+  int par = 0;      // s & 1
+  for (int n = 0, id = first; n < cnt; ++n, id += step) {
+    // what the epilogue of this work id needs, loaded above its K loop
+    const int item = id / ntiles;
+    const int2 t = tiles[id - item * ntiles];
+    const int p = c.p[item % c.nmod];
+    for (int kt = 0; kt < nk; ++kt, par ^= 1) {
+      const int8_t* cur = lds + par * STAGE_BYTES;
+      const int8_t* nxt = lds + (par ^ 1) * STAGE_BYTES;
+      EMUL_MMA8(alo, b, 0, 0); EMUL_PIN();      // phase 1
 #pragma unroll
-    for (int f = 0; f < 4; ++f) ahi[f] = frag(cur, offA, 0, 4 + f);
-    EMUL_PIN(); EMUL_MMA8(alo, b, 0, 1); EMUL_PIN();
-    EMUL_MMA8(ahi, b, 4, 0); EMUL_PIN();      // phase 2
+      for (int f = 0; f < 4; ++f) ahi[f] = frag(cur, offA, 0, 4 + f);
+      EMUL_PIN(); EMUL_MMA8(alo, b, 0, 1); EMUL_PIN();
+      EMUL_MMA8(ahi, b, 4, 0); EMUL_PIN();      // phase 2
 #pragma unroll
-    for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }
-    EMUL_PIN(); EMUL_MMA8(ahi, b, 4, 1); EMUL_PIN();
-    EMUL_MMA8(alo1, b1, 0, 0); EMUL_PIN();    // phase 3
+      for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }
+      EMUL_PIN(); EMUL_MMA8(ahi, b, 4, 1); EMUL_PIN();
+      EMUL_MMA8(alo1, b1, 0, 0); EMUL_PIN();    // phase 3
 #pragma unroll
-    for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);
-    EMUL_PIN(); EMUL_MMA8(alo1, b1, 0, 1); EMUL_PIN();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + 2 < nk) stage(kt & 1, (kt + 2) * BK);
-    EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
-    if (kt + 1 < nk) {
+      for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);
+      EMUL_PIN(); EMUL_MMA8(alo1, b1, 0, 1); EMUL_PIN();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (cn < cnt) stage_next(par);
+      EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
+      if (kt + 1 < nk || n + 1 < cnt) {
 #pragma unroll
-      for (int f = 0; f < 4; ++f) { alo[f] = frag(nxt, offA, 0, f); b[f] = frag(nxt, offB, 0, f); }
+        for (int f = 0; f < 4; ++f) { alo[f] = frag(nxt, offA, 0, f); b[f] = frag(nxt, offB, 0, f); }
+      }
+      EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
     }
-    EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
+    // epilogue of work id `id`: reduce mod p (emul_acc_residue: |acc| <= K 128^2 <= 2^28), pack the 4 consecutive rows a lane holds
+    // into one dword of U[j][i], and clear the accumulators for the next tile
+    const int cf = emul_fold_const(p);
+    const float pf = (float)p, rp = 1.0f / pf;
+    int8_t* Ub = U + (size_t)item * Np * Mp;
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int nn = 0; nn < 4; ++nn) {
+        const size_t j = (size_t)t.y * TILE + wc * 64 + nn * 16 + frow;      // C/D map of 16x16: column = lane & 15, row = 4 (lane >> 4) + e
+        const int i = t.x * TILE + wr * 128 + m * 16 + 4 * fk;
+        unsigned w = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w |= emul_acc_residue(acc[m][nn][e], cf, pf, rp) << (8 * e);
+        *reinterpret_cast<unsigned*>(Ub + j * Mp + i) = w;
+        acc[m][nn] = (v4i){0, 0, 0, 0};
+      }
   }
 #undef EMUL_MMA8
 #undef EMUL_PIN
-  // epilogue: reduce mod p (|acc| <= K 128^2 <= 2^28), pack the 4 consecutive rows a lane holds into one dword of U[j][i]
-  const int p = c.p[item % c.nmod];
-  const float rp = 1.0f / (float)p;
-  int8_t* Ub = U + (size_t)item * Np * Mp;
-#pragma unroll
-  for (int m = 0; m < 8; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      const size_t j = (size_t)t.y * TILE + wc * 64 + n * 16 + frow;      // C/D map of 16x16: column = lane & 15, row = 4 (lane >> 4) + e
-      const int i = t.x * TILE + wr * 128 + m * 16 + 4 * fk;
-      unsigned w = 0;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) w |= (unsigned)(emul_mod_sym(acc[m][n][e], p, rp) & 0xFF) << (8 * e);
-      *reinterpret_cast<unsigned*>(Ub + j * Mp + i) = w;
-    }
 }
 
-// 4 consecutive rows x 1 column per thread: 16 dword loads of residues (coalesced along i), CRT, read-modify-write of C for i >= j
+// 4 consecutive rows x 1 column per thread, NMOD moduli: 16 dword loads of residues (coalesced along i) and the thread's entries of C,
+// the row scales and exponents, all issued before any of them is used (one memory latency per thread); CRT; C for i >= j written back.
+// The sums of emul_crt run modulus-outer over the thread's 4 outputs (each output sees the same operations in the same order), so a
+// CRT weight is a scalar operand that is dead after 4 FMAs: held for all 16 moduli at once, the 96 dwords of weights do not fit the
+// scalar registers.
+template <int NMOD>
 __global__ __launch_bounds__(256) void emul_combine_kernel(BatchPtr A, int g0, size_t offC, int ldc, int M, int N, int Mp, int Np, EmulConst c,
                                                            const int8_t* __restrict__ U, const double* __restrict__ sc, const int* __restrict__ ex) {
   const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4, j = blockIdx.y, z = blockIdx.z;
   if (i0 + 3 < j || i0 >= M) return;
-  unsigned w[LMM_EMUL_MAXMOD];
+  unsigned w[NMOD];
 #pragma unroll
-  for (int t = 0; t < LMM_EMUL_MAXMOD; ++t)
-    w[t] = t < c.nmod ? *reinterpret_cast<const unsigned*>(U + (((size_t)z * c.nmod + t) * Np + j) * Mp + i0) : 0u;
+  for (int t = 0; t < NMOD; ++t) w[t] = *reinterpret_cast<const unsigned*>(U + (((size_t)z * NMOD + t) * Np + j) * Mp + i0);
   const double scj = sc[(size_t)z * Mp + j];
   const int exj = ex[(size_t)z * Mp + j];
   double* C = A.p[g0 + z] + offC + (size_t)j * ldc;
+  double cv[4], sci[4];
+  int exi[4];
+  bool on[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {      // i0 + 3 < Mp: the scales and exponents of the padding rows exist; C does not
+    const int i = i0 + e;
+    on[e] = i >= j && i < M;
+    sci[e] = sc[(size_t)z * Mp + i];
+    exi[e] = ex[(size_t)z * Mp + i];
+    cv[e] = on[e] ? C[i] : 0.0;
+  }
+  double S1[4] = {0.0, 0.0, 0.0, 0.0}, S2[4] = {0.0, 0.0, 0.0, 0.0}, S3[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int t = 0; t < NMOD; ++t)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) emul_crt_term((int)(int8_t)(w[t] >> (8 * e)), t, c, S1[e], S2[e], S3[e]);
+  // all twelve sums exist here: without this the compiler sinks each output's sums into its branch below, output-outer again
+#pragma unroll
+  for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(S1[e]), "+v"(S2[e]), "+v"(S3[e]));
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const int i = i0 + e;
-    if (i < j || i >= M) continue;
-    int u[LMM_EMUL_MAXMOD];
-#pragma unroll
-    for (int t = 0; t < LMM_EMUL_MAXMOD; ++t) u[t] = (int)(int8_t)(w[t] >> (8 * e));
-    const double X = emul_crt(u, c);
-    C[i] -= ldexp(X * sc[(size_t)z * Mp + i] * scj, ex[(size_t)z * Mp + i] + exj);
+    if (!on[e]) continue;
+    const double X = emul_crt_finish(S1[e], S2[e], S3[e], c);
+    C[i0 + e] = cv[e] - ldexp(X * sci[e] * scj, exi[e] + exj);
   }
 }
+template <int NMOD>
+void launch_combine(int nmod, dim3 grid, hipStream_t st, const BatchPtr& C, int g0, size_t offC, int ldc, int M, int N, int Mp, int Np, const EmulConst& c,
+                    const int8_t* U, const double* sc, const int* ex) {
+  if constexpr (NMOD > LMM_EMUL_MINMOD) {
+    if (nmod != NMOD) return launch_combine<NMOD - 1>(nmod, grid, st, C, g0, offC, ldc, M, N, Mp, Np, c, U, sc, ex);
+  }
+  emul_combine_kernel<NMOD><<<grid, 256, 0, st>>>(C, g0, offC, ldc, M, N, Mp, Np, c, U, sc, ex);
+}
+
+int g_emul_gemm_wgs = 0;      // emul_set_gemm_workgroups: 0 = one workgroup per CU
 
 struct EmulLayout { size_t R, U, amax, sc, ex, total; int Mp, Np, ntiles; };
 EmulLayout emul_layout(int M, int N, int K, int G, int nmod) {
@@ -281,6 +359,8 @@ EmulLayout emul_layout(int M, int N, int K, int G, int nmod) {
 }  // namespace
 
 bool emul_shape_ok(int M, int N, int K) { return M >= N && N >= 1 && K >= BK && K % BK == 0 && K <= 16384; }      // int32 accumulators: K 128^2 <= 2^28
+
+void emul_set_gemm_workgroups(int wgs) { g_emul_gemm_wgs = wgs; }
 
 size_t emul_scratch_bytes(int M, int N, int K, int G, int nmod) { return emul_layout(M, N, K, G, nmod).total; }
 
@@ -303,14 +383,18 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
   unsigned long long* amax = reinterpret_cast<unsigned long long*>(s + L.amax);
   double* sc = reinterpret_cast<double*>(s + L.sc);
   int* ex = reinterpret_cast<int*>(s + L.ex);
+  static int cus = 0;
+  if (cus == 0) { int dev = 0; cus = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
+  const int wgs = g_emul_gemm_wgs > 0 ? g_emul_gemm_wgs : cus;      // one 128-KiB workgroup fits on a CU
   for (int g0 = 0; g0 < nb; g0 += G) {
     const int gc = std::min(G, nb - g0);
     err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
     if (err != hipSuccess) return err;
     emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, K, amax);
     launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, amax, R, sc, ex);
-    emul_gemm_kernel<<<L.ntiles * gc * nmod, 512, 0, st>>>(R, U, tiles, L.ntiles, L.Mp, L.Np, K, c);
-    emul_combine_kernel<<<dim3((M + 1023) / 1024, N, gc), 256, 0, st>>>(C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);
+    const int nids = L.ntiles * gc * nmod;
+    emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, L.ntiles, nids, L.Mp, L.Np, K, c);
+    launch_combine<LMM_EMUL_MAXMOD>(nmod, dim3((M + 1023) / 1024, N, gc), st, C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);
   }
   return hipSuccess;
 }

@@ -1,0 +1,134 @@
+"""Bit-exact GPU check of the persistent form of the emulation's GEMM: lmm_dev_syrk_emul on C = 0 against minus the
+product of the host entry lmm_dev_emul_host, with the grid capped through lmm_dev_set_emul_gemm_workgroups so that one workgroup walks
+several (matrix, modulus, tile) work ids.  A stage of the next tile landing in a buffer still being read, a tile computed from the
+wrong panels or reduced with the wrong modulus, and an accumulator not cleared between tiles all show as mismatching bits.
+Operands and helpers are those of tests/test_gpu_emul_exact.py."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+DP = C.POINTER(C.c_double)
+CANARY = 7.25
+
+
+@pytest.fixture(scope="module")
+def lmm():
+    import lmm_amd
+    lmm_amd.init(0)
+    return lmm_amd
+
+
+def operands(M, K, seed):
+    """2^-20 .. 2^20 between rows, 2^-12 .. 1 inside a row, both signs, plus an all-zero row, a row whose largest entry is an exact
+    power of two and a row spanning 60 binades (rows 5, 7, 9: inside every N used here)."""
+    rng = np.random.default_rng(seed)
+    A = rng.standard_normal((M, K)) * np.exp2(rng.integers(-20, 21, size=(M, 1))) * np.exp2(-rng.uniform(0, 12, size=(M, K)))
+    A[5] = 0.0
+    A[7, 3 % K] = -np.exp2(np.ceil(np.log2(np.abs(A[7]).max())) + 1.0)
+    A[9] = rng.standard_normal(K) * np.exp2(-rng.uniform(0, 60, size=K))
+    A[9, 0] = 1.0
+    A[9, K - 1] = 2.0 ** -60
+    return A
+
+
+_CASES = {}
+
+
+def case(lmm, M, N, K, nmod=16):
+    """(A, minus the host-emulated A A[:N]'), computed once per shape and left unchanged."""
+    key = (M, N, K, nmod)
+    if key not in _CASES:
+        lib = lmm.load()
+        A = operands(M, K, M + N + K)
+        Af = np.asfortranarray(A)
+        Bf = np.asfortranarray(A[:N])
+        out = np.zeros((M, N), order="F")
+        lib.lmm_dev_emul_host.restype = C.c_int
+        rc = lib.lmm_dev_emul_host(Af.ctypes.data_as(DP), M, Bf.ctypes.data_as(DP), N, M, N, K, nmod, K, out.ctypes.data_as(DP), M, None)
+        assert rc == 0, lib.lmm_last_error_string()
+        want = -out
+        want.setflags(write=False)
+        A.setflags(write=False)
+        _CASES[key] = (A, want)
+    return _CASES[key]
+
+
+def run_syrk(lmm, A, N, nmod=16, pad_a=3, pad_c=5):
+    """C (zero on and below the diagonal, CANARY elsewhere, pad rows included) after lmm_dev_syrk_emul, with lda = M + pad_a (NaN in the
+    pad rows) and ldc = M + pad_c: (the M x N block, everything else of the buffer)."""
+    import torch
+    lib = lmm.load()
+    M, K = A.shape
+    lda, ldc = M + pad_a, M + pad_c
+    Ah = np.full((K, lda), np.nan)
+    Ah[:, :M] = A.T                                                   # (K, lda) row-major = column-major with leading dimension lda
+    Ch = np.full((N, ldc), CANARY)
+    lower = np.arange(M)[:, None] >= np.arange(N)[None, :]
+    Ch[:, :M][lower.T] = 0.0
+    At, Ct = torch.from_numpy(Ah).cuda(), torch.from_numpy(Ch).cuda()
+    torch.cuda.synchronize()
+    rc = lib.lmm_dev_syrk_emul(C.c_void_p(Ct.data_ptr()), ldc, C.c_void_p(At.data_ptr()), lda, M, N, K, nmod)
+    assert rc == 0, lib.lmm_last_error_string()
+    got = Ct.cpu().numpy()
+    return got[:, :M].T, got[:, M:], lower
+
+
+def check(lmm, M, N, K, cap, nmod=16):
+    A, want = case(lmm, M, N, K, nmod)
+    lib = lmm.load()
+    try:
+        assert lib.lmm_dev_set_emul_gemm_workgroups(cap) == 0, lib.lmm_last_error_string()
+        got, pad, lower = run_syrk(lmm, A, N, nmod)
+    finally:
+        lib.lmm_dev_set_emul_gemm_workgroups(0)
+    assert np.all(pad == CANARY) and np.all(got[~lower] == CANARY)      # nothing outside i >= j is written
+    bad = lower & (got != want)
+    print(f"syrk_emul {M}x{N}x{K}, nmod = {nmod}, at most {cap} workgroups: {int(bad.sum())} of {int(lower.sum())} entries differ")
+    assert not bad.any(), np.argwhere(bad)[:8]
+    assert np.all(got[5, :6] == 0.0) and np.all(got[5:, 5] == 0.0)      # the all-zero row
+    return got
+
+
+@pytest.mark.parametrize("cap", [1, 2, 5, 0])
+@pytest.mark.parametrize("nk", [1, 2, 3, 4])
+def test_one_workgroup_walks_tiles_and_moduli(lmm, nk, cap):
+    """M = N = 320: 3 ragged tiles x 16 moduli = 48 work ids.  One workgroup walks every tile-to-tile and modulus-to-modulus transition;
+    K / 128 = 1 and 2 are tiles shorter than the staging pipeline, 1 and 3 flip the buffer parity between tiles; 2 and 5 workgroups
+    put the item boundaries at other phases of the walk; 0 is the default grid."""
+    check(lmm, 320, 320, 128 * nk, cap)
+
+
+@pytest.mark.parametrize("cap", [1, 3, 7])
+def test_off_diagonal_tiles(lmm, cap):
+    check(lmm, 576, 320, 640, cap)                                    # a 3 x 2 tile grid, 5 tiles
+
+
+@pytest.mark.parametrize("nmod", [8, 15])
+def test_fewer_moduli(lmm, nmod):
+    check(lmm, 100, 100, 384, 1, nmod)
+
+
+def test_repeated_calls_give_identical_bits(lmm):
+    A, _ = case(lmm, 320, 320, 384)
+    first = check(lmm, 320, 320, 384, 2)
+    lib = lmm.load()
+    try:
+        assert lib.lmm_dev_set_emul_gemm_workgroups(2) == 0
+        for _ in range(9):
+            got, _, _ = run_syrk(lmm, A, 320)
+            assert np.array_equal(got.view(np.int64), first.view(np.int64))
+    finally:
+        lib.lmm_dev_set_emul_gemm_workgroups(0)
+
+
+def test_hook_refuses_a_negative_count(lmm):
+    from lmm_amd import _lib as L
+    lib = lmm.load()
+    lib.lmm_dev_set_emul_gemm_workgroups.restype = C.c_int
+    try:
+        assert lib.lmm_dev_set_emul_gemm_workgroups(-1) == L.LMM_ERR_ARG
+    finally:
+        assert lib.lmm_dev_set_emul_gemm_workgroups(0) == L.LMM_OK

@@ -146,8 +146,8 @@ __device__ __forceinline__ int mod_sym24(int x, int p, float rp, int lo) {
   return r;
 }
 
-// The library's emul_gemm_kernel (lmm_kernels_i8.hip), 16x16x64 form, as it stands now; i8_syrk_mod_kernel<16> above is the kernel
-// it replaced and stays as the baseline.
+// The library's emul_gemm_kernel (lmm_kernels_i8.hip), 16x16x64 form, as it stood before the persistent kernel below: one workgroup
+// per tile; i8_syrk_mod_kernel<16> above is the kernel it replaced.
 // The K loop: one K step is four phases of 16 MFMAs, (ks, mh) = the 64-byte half of the k range x the upper / lower 4 of the wave's 8
 // row fragments.  The fragments of a phase are read into registers in the MIDDLE of the phase before it, between its two groups of 8
 // MFMAs, so they are 8 MFMAs old when the wait before their first use comes (the compiler waits with lgkmcnt(0) there, so reads
@@ -264,6 +264,187 @@ __global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_pf(const int8_t* __
     }
 }
 
+// The library's epilogue reduction (lmm_emul.h, emul_acc_residue): x = hi 2^16 + lo is folded to y = hi (2^16 mod p) + lo, |y| < 2^19.2,
+// where rint(y fl(1 / p)) is the nearest integer to y / p, so y - q p is the symmetric residue with no correction; the float steps run
+// on 1.5 2^23 + y, whose bit pattern's low byte ends as the residue's.
+__device__ __forceinline__ int fold_const(int p) { const int r = 65536 % p; return r > p / 2 ? r - p : r; }
+__device__ __forceinline__ unsigned acc_residue(int x, int c, float pf, float rp) {
+  const float ym = __uint_as_float((unsigned)(__mul24(x >> 16, c) + (int)(((unsigned)x & 0xFFFFu) | 0x4B400000u)));
+  const float q = rintf((ym - 12582912.0f) * rp);
+  return __float_as_uint(fmaf(-q, pf, ym)) & 0xFFu;
+}
+
+// The library's emul_gemm_kernel (lmm_kernels_i8.hip) as it stands now: i8_syrk_mod_kernel_pf above with a persistent grid, the K steps
+// of consecutive tiles as one stream of stages, and the fold reduction in the epilogue; i8_syrk_mod_kernel_pf stays as the baseline.
+// Persistent: the grid is min(work ids, CUs) workgroups (launch_ps takes the cap), a work id = an (item, tile) pair in the
+// order item-major, tile list inside.  Blocks b and b + 8 share an XCD: XCD b & 7 owns a contiguous range of ids and its w workgroups
+// walk it from (b >> 3) with stride w, so at any moment the workgroups of an XCD sit on w consecutive ids, one supertile.  The walk
+// is static: no workgroup waits for, or reads anything written by, another one.
+//
+// The K steps of the tiles a workgroup walks form ONE stream of stages s = 0, 1, 2, ..; stage s lives in buffer s & 1 (not kt & 1:
+// nk may be odd).  A staging cursor (tile base pointers, k offset) runs two stages ahead of the MFMAs and steps into the next work
+// id when it has issued a tile's last K step, so the last two K steps of a tile stage the first two of the next one (with nk = 1
+// the cursor is two TILES ahead), and between the last MFMA of a tile and the first of the next only the epilogue stands, with the
+// next tile's loads and its first fragment reads issued above it.
+//
+// One K step is four phases of 16 MFMAs, (ks, mh) = the 64-byte half of the k range x the upper / lower 4 of the wave's 8 row
+// fragments.  The fragments of a phase are read into registers in the MIDDLE of the phase before it, between its two groups of 8
+// MFMAs, so they are 8 MFMAs old when the wait before their first use comes (the compiler waits with lgkmcnt(0) there, so reads
+// issued right before that wait would be waited for too).  sched_barrier(0) pins that order: left alone, the scheduler sinks the
+// reads down to their uses.  The one barrier of a K step stands between phases 3 and 4.
+//
+//   phase of stage s | MFMAs use (registers)        | ds_reads issued (buffer)                 | global_load_lds issued
+//   1 (ks 0, mh 0)   | a[0..3], b[0..3]   of s      | a[4..7] ks 0 of s  (s & 1)               |
+//   2 (ks 0, mh 1)   | a[4..7], b[0..3]   of s      | a[0..3], b[0..3] ks 1 of s  (s & 1)      |
+//   3 (ks 1, mh 0)   | a[0..3]', b[0..3]' of s      | a[4..7] ks 1 of s  (s & 1): the LAST read of buffer s & 1
+//   -- s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier: every wave holds all its fragments of stage s in registers, and every wave's
+//      loads of stage s + 1 (issued one whole K step earlier, at this point of stage s - 1) have landed in buffer (s + 1) & 1 --
+//   4 (ks 1, mh 1)   | a[4..7]', b[0..3]' of s      | a[0..3], b[0..3] ks 0 of s + 1 ((s+1)&1) | stage s + 2 into buffer s & 1
+//   -- after the last stage of a tile: the epilogue of that tile (registers and global stores only) --
+//
+//   read after write: buffer (s + 1) & 1 is first read in phase 4 of stage s, after the wait-plus-barrier that retires stage s + 1.
+//   write after read: buffer s & 1 is restaged in phase 4 of stage s, after the barrier every wave reaches only with its last reads
+//   of that buffer (phase 3) complete.  Neither argument looks at which tile a stage belongs to: stages s, s + 1, s + 2 may lie in
+//   one, two or three tiles, and the epilogue touches no LDS and stands after phase 4 of a stage and before phase 1 of the next,
+//   where the schedule has no LDS ordering to keep.  One stage is in flight at a time, so the wait is vmcnt(0); it waits for loads
+//   that are one K step (64 MFMAs per wave) old, and after a tile boundary also for the epilogue's 32 stores per lane, as old.
+//   The prologue (once per workgroup) stages 0, waits, and stages 1 if the walk has a second stage at all.
+template <bool STAMP, int EPI>
+__global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_ps(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
+                                                                int nids, int Mp, int Np, int K, Moduli mod, unsigned long long* __restrict__ stamps) {
+  __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
+  // the walk of this workgroup: ids first, first + step, .. (cnt of them) of its XCD's range; fewer than 8 workgroups split the ids
+  // among themselves
+  const int nwg = gridDim.x, parts = nwg < 8 ? nwg : 8, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int step = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
+  const int qi = nids / parts, ri = nids - qi * parts;
+  const int first = xcd * qi + (xcd < ri ? xcd : ri) + slot, span = qi + (xcd < ri ? 1 : 0) - slot;
+  const int cnt = span > 0 ? (span + step - 1) / step : 0;
+  if (cnt == 0) return;
+  // source offsets of a lane's four 16-byte loads of one operand, from the tile's first row at k = 0
+  unsigned roff[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = wid * 32 + q * 8 + (lane >> 3), chunk = (lane & 7) ^ ((row >> 1) & 7);
+    roff[q] = (unsigned)row * (unsigned)K + chunk * 16;
+  }
+  // the staging cursor: operand panels of the cn-th work id of the walk, next k offset ck; (pitem, pt) is the (cn + 1)-th work id,
+  // loaded one tile ahead so that stepping into it waits for no load
+  const int8_t* cA = nullptr;
+  const int8_t* cB = nullptr;
+  int cn = 0, ck = 0, pitem = 0;
+  int2 pt = make_int2(0, 0);
+  auto cursor_peek = [&](int idn) {
+    pitem = idn / ntiles;
+    pt = tiles[idn - pitem * ntiles];
+  };
+  auto cursor_tile = [&]() {
+    const int8_t* Rb = R + (size_t)pitem * Mp * K;
+    cA = Rb + (size_t)pt.x * TILE * K;
+    cB = Rb + (size_t)pt.y * TILE * K;
+    if (cn + 1 < cnt) cursor_peek(first + (cn + 1) * step);
+  };
+  auto stage_next = [&](int buf) {      // cn < cnt
+    int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) glds16(cA + ck + roff[q], base + q * 1024);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) glds16(cB + ck + roff[q], base + TILE * BK + q * 1024);
+    ck += BK;
+    if (ck == K) {
+      ck = 0; ++cn;
+      if (cn < cnt) cursor_tile();
+    }
+  };
+  const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
+  // byte offset of a fragment in its stage: (row 128) + ((ks 4 + fk) ^ (row >> 1) & 7) 16 with row = 16 m + frow (+ the wave's first
+  // row, a multiple of 64): the swizzle is (frow >> 1), and ks = 1 flips bit 6 of the offset
+  const int offA = (wr * 128 + frow) * BK + ((fk ^ (frow >> 1)) << 4), offB = TILE * BK + (wc * 64 + frow) * BK + ((fk ^ (frow >> 1)) << 4);
+  auto frag = [&](const int8_t* st, int off, int ks, int f) { return *reinterpret_cast<const v4i*>(st + (off ^ (ks << 6)) + f * 16 * BK); };
+  v4i acc[8][4];
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = (v4i){0, 0, 0, 0};
+  unsigned long long t0 = 0, r0 = 0;
+  if (STAMP) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
+  cursor_peek(first);
+  cursor_tile();
+  stage_next(0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (cn < cnt) stage_next(1);
+  v4i alo[4], ahi[4], b[4], alo1[4], ahi1[4], b1[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) { alo[f] = frag(lds, offA, 0, f); b[f] = frag(lds, offB, 0, f); }
+  // 8 MFMAs: row fragments 2 h, 2 h + 1 of A4 (accumulator rows M0 + 2 h ..) x the 4 column fragments
+#define EMUL_MMA8(A4, B4, M0, h)                                                                                                   \
+  _Pragma("unroll") for (int m = 2 * (h); m < 2 * (h) + 2; ++m)                                                                    \
+  _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + m][n], 0, 0, 0)
+#define EMUL_PIN() __builtin_amdgcn_sched_barrier(0)
+  int par = 0;      // s & 1
+  for (int n = 0, id = first; n < cnt; ++n, id += step) {
+    // what the epilogue of this work id needs, loaded above its K loop
+    const int item = id / ntiles;
+    const int2 t = tiles[id - item * ntiles];
+    const int p = mod.p[item % NMOD];
+    for (int kt = 0; kt < nk; ++kt, par ^= 1) {
+      const int8_t* cur = lds + par * STAGE_BYTES;
+      const int8_t* nxt = lds + (par ^ 1) * STAGE_BYTES;
+      EMUL_MMA8(alo, b, 0, 0); EMUL_PIN();      // phase 1
+#pragma unroll
+      for (int f = 0; f < 4; ++f) ahi[f] = frag(cur, offA, 0, 4 + f);
+      EMUL_PIN(); EMUL_MMA8(alo, b, 0, 1); EMUL_PIN();
+      EMUL_MMA8(ahi, b, 4, 0); EMUL_PIN();      // phase 2
+#pragma unroll
+      for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }
+      EMUL_PIN(); EMUL_MMA8(ahi, b, 4, 1); EMUL_PIN();
+      EMUL_MMA8(alo1, b1, 0, 0); EMUL_PIN();    // phase 3
+#pragma unroll
+      for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);
+      EMUL_PIN(); EMUL_MMA8(alo1, b1, 0, 1); EMUL_PIN();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (cn < cnt) stage_next(par);
+      EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
+      if (kt + 1 < nk || n + 1 < cnt) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) { alo[f] = frag(nxt, offA, 0, f); b[f] = frag(nxt, offB, 0, f); }
+      }
+      EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
+    }
+    // epilogue of work id `id`: reduce mod p (|acc| <= K 128^2 <= 2^28), pack the 4 consecutive rows a lane holds into one dword of
+    // U[j][i], and clear the accumulators for the next tile.  EPI 0: the fold reduction (the library's), 1: the low byte as it is
+    // (wrong but for p = 256: the floor of any epilogue), 2: the two-correction reduction of the kernel before
+    const int cf = fold_const(p), lo = -(p / 2);
+    const float pf = (float)p, rp = 1.0f / pf;
+    int8_t* Ub = U + (size_t)item * Np * Mp;
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int nn = 0; nn < 4; ++nn) {
+        const size_t j = (size_t)t.y * TILE + wc * 64 + nn * 16 + frow;      // C/D map of 16x16: column = lane & 15, row = 4 (lane >> 4) + e
+        const int i = t.x * TILE + wr * 128 + m * 16 + 4 * fk;
+        unsigned w = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int x = acc[m][nn][e];
+          w |= (EPI == 0 ? acc_residue(x, cf, pf, rp) : EPI == 1 ? (unsigned)x & 0xFFu : (unsigned)(mod_sym24(x, p, rp, lo) & 0xFF)) << (8 * e);
+        }
+        *reinterpret_cast<unsigned*>(Ub + j * Mp + i) = w;
+        acc[m][nn] = (v4i){0, 0, 0, 0};
+      }
+  }
+#undef EMUL_MMA8
+#undef EMUL_PIN
+  if (STAMP) {
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    if (tid == 0) { stamps[2 * (size_t)blockIdx.x] = t1 - t0; stamps[2 * (size_t)blockIdx.x + 1] = r1 - r0; }
+  }
+}
+
+
 // bare issue rate: operands in registers, 4 independent accumulators, no memory traffic
 __global__ __launch_bounds__(256) void mfma_i8_bare(int* out, unsigned long long* stamps, int iters) {
   v16i acc[4];
@@ -327,6 +508,14 @@ static void launch(const int8_t* R, int8_t* U, const int2* tiles, int ntiles, in
   else i8_syrk_mod_kernel<SHAPE, STAMP><<<ntiles * batch, 512>>>(R, U, tiles, ntiles, M, N, K, kModuli, stamps);
 }
 
+// the persistent kernel on at most `wgs` workgroups (0: one per CU)
+static int g_cus = 256;
+template <bool STAMP, int EPI>
+static void launch_ps(const int8_t* R, int8_t* U, const int2* tiles, int ntiles, int M, int N, int K, int batch, int wgs, unsigned long long* stamps) {
+  const int nids = ntiles * batch;
+  i8_syrk_mod_kernel_ps<STAMP, EPI><<<std::min(nids, wgs > 0 ? wgs : g_cus), 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps);
+}
+
 // exact check of U against a host integer product; every == true checks every computed tile and that nothing else was written
 static long check(const int8_t* dR, const int8_t* dU, int M, int N, int K, int batch, bool every, const char* what) {
   std::vector<int8_t> hR((size_t)M * K), hU((size_t)N * M);
@@ -364,6 +553,7 @@ int main(int argc, char** argv) {
   const int batch = NMOD * nmat;
   hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
   long bad = 0;
+  { int dev = 0; CHECK(hipGetDevice(&dev)); CHECK(hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev)); }
 
   {  // 1. bare v_mfma_i32_32x32x32_i8 issue rate and the clock held
     int* out; unsigned long long* st;
@@ -410,6 +600,18 @@ int main(int argc, char** argv) {
       CHECK(hipDeviceSynchronize());
       bad += check(R, U, M, N, Kp, nb, true, "16x16x64 prefetch full");
     }
+    for (int Kp : {128, 256, 384, 512})      // the persistent kernel: one, two, five workgroups walk the 3 tiles x 16 (12) moduli, and the default grid
+      for (int wgs : {1, 2, 5, 0}) {
+        const int nb = Kp <= K ? NMOD : 12;
+        CHECK(hipMemset(U, 0x5A, (size_t)NMOD * N * M));
+        launch_ps<false, 0>(R, U, dt, (int)tl.size(), M, N, Kp, nb, wgs, nullptr);
+        CHECK(hipDeviceSynchronize());
+        char what[64]; snprintf(what, sizeof what, "persistent full, %d wgs", wgs);
+        bad += check(R, U, M, N, Kp, nb, true, what);
+        launch_ps<false, 2>(R, U, dt, (int)tl.size(), M, N, Kp, nb, wgs, nullptr);      // the old reduction gives the same bytes
+        CHECK(hipDeviceSynchronize());
+        bad += check(R, U, M, N, Kp, nb, true, "persistent, old epilogue");
+      }
     CHECK(hipFree(R)); CHECK(hipFree(U)); CHECK(hipFree(dt));
     fflush(stdout);
     if (bad) { printf("operand or output map wrong: not timing\n"); return 1; }
@@ -464,6 +666,51 @@ int main(int argc, char** argv) {
            issued / t16[0] / 1e9, clk[1]);
     printf("                                                  | 16x16x64 prefetch (the library's kernel): min %.3f med %.3f ms, %.0f TOPS useful (%.0f issued), clock %.0f MHz"
            " | baseline 16x16x64 / prefetch: medians %.3f\n", tpf[0], tpf[1], useful / tpf[0] / 1e9, issued / tpf[0] / 1e9, clk[2], t16[1] / tpf[1]);
+    {  // the persistent kernel and the split of the per-tile fixed cost: grid (one workgroup per tile / per CU) x epilogue (fold
+       // reduction / low byte only / the prefetch kernel's), interleaved with the prefetch kernel in every round
+      const char* names[7] = {"prefetch (before)", "per tile, fold", "per tile, low byte", "persistent, old epilogue", "persistent, fold (the library's kernel)",
+                              "persistent, low byte", "prefetch (before), again"};
+      std::vector<float> tv[7];
+      const int nids = nt * batch;
+      for (int round = 0; round < 3; ++round)
+        for (int v = 0; v < 7; ++v) {
+          auto go = [&]() {
+            switch (v) {
+              case 1: launch_ps<false, 0>(R, U, dt, nt, s.M, s.N, s.K, batch, nids, nullptr); break;
+              case 2: launch_ps<false, 1>(R, U, dt, nt, s.M, s.N, s.K, batch, nids, nullptr); break;
+              case 3: launch_ps<false, 2>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr); break;
+              case 4: launch_ps<false, 0>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr); break;
+              case 5: launch_ps<false, 1>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr); break;
+              default: launch<0, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
+            }
+          };
+          go();
+          hipEventRecord(e0);
+          for (int r = 0; r < reps; ++r) go();
+          hipEventRecord(e1); CHECK(hipEventSynchronize(e1));
+          float ms; hipEventElapsedTime(&ms, e0, e1);
+          tv[v].push_back(ms / reps);
+        }
+      for (int r = 0; r < 3; ++r) launch_ps<true, 0>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, st);
+      CHECK(hipDeviceSynchronize());
+      const int g = std::min(nids, g_cus);
+      std::vector<unsigned long long> h((size_t)g * 2);
+      CHECK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
+      std::vector<double> cl;
+      for (int w = 0; w < g; ++w) cl.push_back((double)h[2 * w] / (double)h[2 * w + 1] * 100.0);
+      std::sort(cl.begin(), cl.end());
+      const double tiles_per_cu = (double)nids / g_cus;
+      for (int v = 0; v < 7; ++v) {
+        std::sort(tv[v].begin(), tv[v].end());
+        printf("    %-42s min %.3f med %.3f max %.3f ms, %.0f TOPS useful, %.2f us per tile and CU\n", names[v], tv[v][0], tv[v][1], tv[v][2], useful / tv[v][1] / 1e9,
+               tv[v][1] * 1e3 / tiles_per_cu);
+      }
+      printf("    persistent kernel's clock %.0f MHz; before / persistent medians %.3f\n", cl[cl.size() / 2], tv[0][1] / tv[4][1]);
+      CHECK(hipMemset(U, 0x5A, ub));
+      launch_ps<false, 0>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr);
+      CHECK(hipDeviceSynchronize());
+      bad += check(R, U, s.M, s.N, s.K, batch, false, "persistent sampled");
+    }
     launch<32, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
     CHECK(hipDeviceSynchronize());
     bad += check(R, U, s.M, s.N, s.K, batch, false, "32x32x32 sampled");
