@@ -668,7 +668,7 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
  * Refusals, all before any kernel of the scan is launched: a latent that is not a plain Matern12 / 32 / 52 (SE, RQ, the periodic
  * kinds, sums, latents with a tag) -> LMM_ERR_UNSUPPORTED with the latent in the error detail; the fp32 compute mode ->
  * LMM_ERR_UNSUPPORTED; a point with 0 < p_t < m -> LMM_ERR_UNSUPPORTED with the point in `info`; S not finite and > 0, sigma2 <= 0 ->
- * LMM_ERR_ARG.  Not built: gradients with respect to x, gradients of the marginals, sums of Matern terms, rand.
+ * LMM_ERR_ARG.  Not built: gradients with respect to x, gradients of the marginals, sums of Matern terms.
  *   lmm_oilmm_logpdf_statespace : the value of lmm_oilmm_logpdf (no NaN) or lmm_oilmm_logpdf_missing (NaN) by the filter: agreement
  *                    to rounding, not bitwise.  Shard semantics and with_regulariser as there.
  *   lmm_oilmm_mean_and_var_statespace : the smoothed latent marginals at the n inputs, mixed through H = U sqrt(S) exactly as
@@ -694,7 +694,29 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
  *                    LMM_ERR_UNSUPPORTED).  Every refusal of lmm_oilmm_logpdf_statespace applies, in its order.  Partial sums over
  *                    the shard; with_regulariser as there.
  *   lmm_dev_statespace_grad : the building block beside lmm_dev_statespace_filter (DEVICE pointers throughout): *lml as there (bitwise),
- *                    grad_r and grad_w (n each; 0 at unobserved points), grad_theta = {d lml / d variance, d lml / d lengthscale}. */
+ *                    grad_r and grad_w (n each; 0 at unobserved points), grad_theta = {d lml / d variance, d lml / d lengthscale}.
+ *   lmm_oilmm_rand_statespace : rand in O(n), exact: joint samples of the prior (y == NULL) or of the posterior given y, at the n inputs,
+ *                    from caller-supplied standard normals.  The prior path of a latent is the recursion s_0 = chol(Pinf) zeta_0,
+ *                    s_t = A(dt_t) s_{t-1} + chol(Q(dt_t)) zeta_t, f_t = (s_t)_1 (chol: the lower factor with non-negative diagonal;
+ *                    a pivot that is not > 0 gives a zero column, so equal points repeat the state), run as a scan over affine maps.
+ *                    A posterior path is mean_l + f + the smoothed mean of the data r_t - f_t - sqrt(w_t) xi_t (pathwise conditioning,
+ *                    Matheron's rule), through the filter and smoother above: an exact joint sample at observed and unobserved points
+ *                    alike.  With y given every rule of lmm_oilmm_mean_and_var_statespace holds (NaN = missing; a point whose outputs
+ *                    are all NaN is predict-only, which is how samples at new inputs are asked for; 0 < p_t < m is refused); with
+ *                    y == NULL there is no front end and xi is not read.  Layouts, points in the order of x, every buffer host or
+ *                    device: z per sample the latents 0 .. m - 1 one after the other, latent l taking D_l n doubles with component i
+ *                    of point t at i n + t (one sample: n sum_l D_l doubles; a shard reads only its own); xi [sample][m][n] (posterior
+ *                    only; ignored where a point is unobserved); eps and out [sample][p][n], the layout of lmm_lmm_rand_multi.  out =
+ *                    H (latent paths) + sqrt(sigma2) eps (iff add_noise), H = U sqrt(S): the partial sum over the shard's latents.
+ *                    Every refusal of lmm_oilmm_logpdf_statespace applies, in its order; then nsamples < 1, z == NULL, xi == NULL
+ *                    with y given and eps == NULL with add_noise are LMM_ERR_ARG.  Bitwise reproducible, and sample q of an
+ *                    nsamples-call is bitwise the single-sample call with the same normals.  As a function of FIXED normals the path
+ *                    is ill-conditioned where dt / lengthscale is small (Q's small pivots come out of a cancellation); its law is not
+ *                    (DESIGN.md 4.18 "Sampling").
+ *   lmm_dev_statespace_sample, lmm_dev_statespace_sample_posterior : building blocks exported for tests (DEVICE pointers; gp on the
+ *                    host, its mean is not read; chunk as for lmm_dev_statespace_filter): f [sample][n], the zero-mean latent path of
+ *                    one latent from z [sample][D n] (and, posterior, w, r and xi [sample][n]).  With z = xi = 0 the posterior block
+ *                    returns bitwise the smean of lmm_dev_statespace_smooth at the same chunk. */
 int lmm_oilmm_logpdf_statespace(const double* x, int n, const double* y, int p,
                                 const double* U, const double* S, int m, double sigma2,
                                 const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out);
@@ -713,6 +735,14 @@ int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, in
                                      lmm_gp_grad_t* grad_gps);
 int lmm_dev_statespace_grad(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
                             double* lml, double* grad_r, double* grad_w, double* grad_theta);
+int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
+                              const double* U, const double* S, int m, double sigma2,
+                              const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,
+                              const double* z, const double* xi /* posterior only */, const double* eps /* iff add_noise */,
+                              double* out);
+int lmm_dev_statespace_sample(const double* x, int n, const lmm_gp_t* gp, const double* z, int nsamples, int chunk, double* f);
+int lmm_dev_statespace_sample_posterior(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r,
+                                        const double* z, const double* xi, int nsamples, int chunk, double* f);
 
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard

@@ -35,6 +35,7 @@ SYMBOLS = [
     "lmm_oilmm_elbo_grad", "lmm_dev_sparse_grad",
     "lmm_oilmm_logpdf_statespace", "lmm_oilmm_mean_and_var_statespace", "lmm_dev_statespace_filter", "lmm_dev_statespace_smooth",
     "lmm_oilmm_logpdf_grad_statespace", "lmm_dev_statespace_grad",
+    "lmm_oilmm_rand_statespace", "lmm_dev_statespace_sample", "lmm_dev_statespace_sample_posterior",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
     "lmm_dev_set_f64_emul", "lmm_dev_syrk_emul", "lmm_dev_emul_host", "lmm_dev_emul_residues", "lmm_dev_set_emul_gemm_workgroups", "lmm_dev_emul_acc_residues",
 ]
@@ -61,6 +62,9 @@ STATESPACE_ARGTYPES = {
     "lmm_dev_statespace_smooth": [_P, _I, _P, _P, _P, _I, _P, _P],
     "lmm_oilmm_logpdf_grad_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "lmm_dev_statespace_grad": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "lmm_oilmm_rand_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "lmm_dev_statespace_sample": [_P, _I, _P, _P, _I, _I, _P],
+    "lmm_dev_statespace_sample_posterior": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P],
 }
 
 

@@ -5072,22 +5072,25 @@ struct SSGradOut {
   double* sums;                        // host, 4 per latent: sum_t alpha_t, w_t alpha_t^2, w_t c_t, d lml / d w_t
   double* gtheta;                      // host, 2 per latent: d lml / d variance, d lml / d lengthscale
 };
-static int ss_core(const double* xd, int n, const Latent* lts, int ms, const double* w, const double* r, int chunk, double* lml,
-                   double* fmean, double* fvar, double* smean, double* svar, bool add_mean, const SSGradOut* go = nullptr) {
+// One entry of the latent dimension of a launch: a latent with its own noise and data (n values each, on the device).  Samples ride
+// through the filter and smoother as several entries of one latent, with the same w and their own r.
+struct SSEntry { const Latent* L; const double* w; const double* r; };
+static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, int chunk, double* lml, double* fmean, double* fvar,
+                           double* smean, double* svar, bool add_mean, const SSGradOut* go = nullptr) {
   hipStream_t st0 = g.streams[0];
   if (chunk <= 0) chunk = ss_default_chunk(n);
   if (chunk > n) chunk = n;
   const int nch = (n + chunk - 1) / chunk;
   const bool smooth = smean != nullptr;
   for (int k0 = 0; k0 < ms;) {
-    const int D = ss_state_dim(lts[k0].kind);
+    const int D = ss_state_dim(es[k0].L->kind);
     const size_t comps = (size_t)ss_state_comps(D);
     const int npb = ss_point_blocks(n);
     const size_t per = (ss_fwd_agg_elems(D, nch) + (size_t)nch + (smooth ? comps * n + ss_bwd_agg_elems(D, nch) : 0) +
                         (go ? ss_dual_agg_elems(D, nch) + 2 * (size_t)nch + 4 * (size_t)npb : 0)) * sizeof(double);
     const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / per));
     int nb = 1;
-    while (k0 + nb < ms && nb < nbmax && ss_state_dim(lts[k0 + nb].kind) == D) ++nb;
+    while (k0 + nb < ms && nb < nbmax && ss_state_dim(es[k0 + nb].L->kind) == D) ++nb;
     Buf<double> agg((size_t)nb * ss_fwd_agg_elems(D, nch)), part((size_t)nb * nch), lmld(nb), state, bagg;
     if (smooth) { state = Buf<double>((size_t)nb * comps * n); bagg = Buf<double>((size_t)nb * ss_bwd_agg_elems(D, nch)); }
     Buf<double> dagg, dpart, ppart, gsum;
@@ -5103,9 +5106,9 @@ static int ss_core(const double* xd, int n, const Latent* lts, int ms, const dou
     a.smean = smooth ? smean + (size_t)k0 * n : nullptr; a.svar = (smooth && svar) ? svar + (size_t)k0 * n : nullptr;
     a.dagg = dagg.p; a.dpart = dpart.p;
     for (int j = 0; j < nb; ++j) {
-      const Latent& L = lts[k0 + j];
+      const Latent& L = *es[k0 + j].L;
       a.lat[j].var = L.terms[0].ev.var; a.lat[j].inv_ls = L.terms[0].ev.inv_ls; a.lat[j].mean = add_mean ? L.mean : 0.0;
-      a.lat[j].w = w + (size_t)(k0 + j) * n; a.lat[j].r = r + (size_t)(k0 + j) * n;
+      a.lat[j].w = es[k0 + j].w; a.lat[j].r = es[k0 + j].r;
     }
     launch_ss_filter(a, D, nb, lmld.p, st0);
     if (smooth) launch_ss_smooth(a, D, nb, st0);
@@ -5123,6 +5126,13 @@ static int ss_core(const double* xd, int n, const Latent* lts, int ms, const dou
     k0 += nb;
   }
   return LMM_OK;
+}
+
+static int ss_core(const double* xd, int n, const Latent* lts, int ms, const double* w, const double* r, int chunk, double* lml,
+                   double* fmean, double* fvar, double* smean, double* svar, bool add_mean, const SSGradOut* go = nullptr) {
+  std::vector<SSEntry> es(ms);
+  for (int k = 0; k < ms; ++k) es[k] = SSEntry{lts + k, w + (size_t)k * n, r + (size_t)k * n};
+  return ss_core_entries(xd, n, es.data(), ms, chunk, lml, fmean, fvar, smean, svar, add_mean, go);
 }
 
 // The OILMM front end of the state-space path: per latent of the shard and point, the pseudo-observation r = z_t[l] - mean_l and its
@@ -5441,6 +5451,186 @@ int lmm_dev_statespace_grad(const double* x, int n, const lmm_gp_t* gp, const do
   HIPCHK(hipMemcpyAsync(grad_theta, gth, 2 * sizeof(double), hipMemcpyHostToDevice, st0));
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
+  LMM_CATCH
+}
+
+// ---- sampling (DESIGN.md 4.18 "Sampling") ----------------------------------------------------------------------------------------
+// Prior paths of the ms latents lts[0 .. ms) for N samples: f[sample][latent][n] on the device, with the latent's mean when add_mean.
+// z: sample 0's normals of lts[0] on the device, the latents one after the other (D_l n values each, component-major), the samples
+// z_stride doubles apart.  The (latent, sample) pairs run in launches of equal state dimension.  Returns with streams[0] drained.
+static int ss_paths(const double* xd, int n, const Latent* lts, int ms, int N, const double* z, size_t z_stride, int chunk, bool add_mean,
+                    double* f) {
+  hipStream_t st0 = g.streams[0];
+  if (chunk <= 0) chunk = ss_default_chunk(n);
+  if (chunk > n) chunk = n;
+  const int nch = (n + chunk - 1) / chunk;
+  std::vector<size_t> zoff(std::max(ms, 1), 0);
+  for (int k = 1; k < ms; ++k) zoff[k] = zoff[k - 1] + (size_t)ss_state_dim(lts[k - 1].kind) * n;
+  const long long ne = (long long)ms * N;
+  for (long long e0 = 0; e0 < ne;) {
+    const int D = ss_state_dim(lts[e0 / N].kind);
+    const size_t per = ss_aff_agg_elems(D, nch) * sizeof(double);
+    const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / per));
+    int nb = 1;
+    while (e0 + nb < ne && nb < nbmax && ss_state_dim(lts[(e0 + nb) / N].kind) == D) ++nb;
+    Buf<double> agg((size_t)nb * ss_aff_agg_elems(D, nch));
+    SSPathArgs a{};
+    a.x = xd; a.n = n; a.chunk = chunk; a.nch = nch; a.agg = agg.p;
+    for (int j = 0; j < nb; ++j) {
+      const int k = (int)((e0 + j) / N), q = (int)((e0 + j) % N);
+      const Latent& L = lts[k];
+      a.lat[j].var = L.terms[0].ev.var; a.lat[j].inv_ls = L.terms[0].ev.inv_ls; a.lat[j].mean = add_mean ? L.mean : 0.0;
+      a.lat[j].z = z + (size_t)q * z_stride + zoff[k];
+      a.lat[j].f = f + ((size_t)q * ms + k) * n;
+    }
+    launch_ss_path(a, D, nb, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));          // agg goes back to the pool
+    e0 += nb;
+  }
+  return LMM_OK;
+}
+
+// Pathwise conditioning (Matheron's rule): the zero-mean prior paths f[sample][latent][n] become posterior paths given the latents'
+// data r with noise w ([latent][n]; w = +Inf: unobserved): f += the smoothed mean of r - f - sqrt(w) xi (+ the latent's mean when
+// add_mean).  xi: sample 0's normals of lts[0], n per latent, the samples xi_stride doubles apart.  The samples are further entries of
+// the latent dimension of the filter and smoother, [latent][sample], with the latent's w and their own data.
+static int ss_condition(const double* xd, int n, const Latent* lts, int ms, int N, const double* w, const double* r, const double* xi,
+                        size_t xi_stride, int chunk, bool add_mean, double* f) {
+  if (ms == 0) return LMM_OK;
+  hipStream_t st0 = g.streams[0];
+  const size_t ne = (size_t)ms * N;
+  Buf<double> rp(ne * n), sm(ne * n);
+  launch_ss_pathwise(r, w, f, xi, xi_stride, n, ms, N, rp.p, st0);
+  HIPCHK(hipGetLastError());
+  std::vector<SSEntry> es(ne);
+  for (size_t e = 0; e < ne; ++e) es[e] = SSEntry{lts + e / N, w + (e / N) * n, rp.p + e * n};
+  if (int rc = ss_core_entries(xd, n, es.data(), (int)ne, chunk, nullptr, nullptr, nullptr, sm.p, nullptr, add_mean)) return rc;
+  launch_ss_addpath(f, sm.p, n, ms, N, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));            // rp and sm go back to the pool
+  return LMM_OK;
+}
+
+// samples of one group: the buffers of a group stay within LMM_SS_BATCH_BYTES, and a group is one grid dimension of the elementwise kernels
+static int ss_sample_group(int n, int ms, int N) {
+  const size_t per = (size_t)std::max(ms, 1) * n * sizeof(double) * 4;
+  return (int)std::max<size_t>(1, std::min<size_t>(std::min(N, 32768), LMM_SS_BATCH_BYTES / per));
+}
+
+// The normals of samples [q0, q0 + ng) of one shard on the device: src holds `per_sample` doubles per sample, of which the shard reads
+// `count` from `offset` on.  A device pointer is used where it lies; a host pointer's slices are uploaded side by side.
+struct SSNormals {
+  const double* p = nullptr; size_t stride = 0;
+  Buf<double> own;
+  SSNormals(const double* src, size_t per_sample, size_t offset, size_t count, int q0, int ng, hipStream_t st) {
+    if (src == nullptr) return;
+    if (is_device_ptr(src)) { p = src + (size_t)q0 * per_sample + offset; stride = per_sample; return; }
+    own = Buf<double>(std::max<size_t>(count, 1) * ng);
+    for (int q = 0; q < ng && count > 0; ++q)
+      HIPCHK(hipMemcpyAsync(own.p + (size_t)q * count, src + (size_t)(q0 + q) * per_sample + offset, count * sizeof(double),
+                            hipMemcpyHostToDevice, st));
+    p = own.p; stride = count;
+  }
+};
+
+int lmm_oilmm_rand_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                              const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples, const double* z,
+                              const double* xi, const double* eps, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !U || !S || !out || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
+  if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
+  for (int l = 0; l < m; ++l)
+    if (!(S[l] > 0.0) || !std::isfinite(S[l])) return fail(LMM_ERR_ARG, "S must be finite and > 0 (S[%d] = %g)", l, S[l]);
+  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
+  if (!z) return fail(LMM_ERR_ARG, "z is NULL");
+  if (y && !xi) return fail(LMM_ERR_ARG, "xi is NULL (a posterior sample needs it)");
+  if (add_noise && !eps) return fail(LMM_ERR_ARG, "eps is NULL");
+  RESOLVE(gps, m, 1);
+  if (int rc = ss_check_latents(lts, m)) return rc;
+  hipStream_t st0 = g.streams[0];
+  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
+  if (int rc = ss_check_sorted(xd.p, n)) return rc;
+  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0, mk = std::max(ms, 1);
+  SSFront Fr;
+  if (y)
+    if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr)) return rc;
+  size_t zall = 0, zbefore = 0, zshard = 0;        // doubles of one sample's z: every latent, those before the shard, the shard's
+  for (int l = 0; l < m; ++l) {
+    const size_t c = (size_t)ss_state_dim(lts[l].kind) * n;
+    zall += c;
+    if (l < l0) zbefore += c;
+    else if (l < l1) zshard += c;
+  }
+  std::vector<double> Hs((size_t)p * mk, 0.0);
+  for (int k = 0; k < ms; ++k)
+    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
+  Uploaded Hd(Hs, st0);
+  DevOut od(out, (size_t)n * p * nsamples);
+  const int group = ss_sample_group(n, ms, nsamples);
+  for (int q0 = 0; q0 < nsamples; q0 += group) {
+    const int ng = std::min(group, nsamples - q0);
+    SSNormals zd(z, zall, zbefore, zshard, q0, ng, st0), xid(y ? xi : nullptr, (size_t)m * n, (size_t)l0 * n, (size_t)ms * n, q0, ng, st0);
+    SSNormals epsd(add_noise ? eps : nullptr, (size_t)n * p, 0, (size_t)n * p, q0, ng, st0);
+    Buf<double> f((size_t)ng * mk * n);            // [sample][latent of the shard][n]
+    if (int rc = ss_paths(xd.p, n, lts + l0, ms, ng, zd.p, zd.stride, 0, y == nullptr, f.p)) return rc;
+    if (y)
+      if (int rc = ss_condition(xd.p, n, lts + l0, ms, ng, Fr.w.p, Fr.r.p, xid.p, xid.stride, 0, true, f.p)) return rc;
+    // the mixing of lmm_lmm_rand (reference src/oilmm.jl:50-53): H X + sqrt(sigma2) eps
+    for (int q = 0; q < ng; ++q)
+      launch_mix(f.p + (size_t)q * ms * n, n, ms, Hd.buf.p, p, 1, 0.0, 0.0, add_noise ? epsd.p + (size_t)q * epsd.stride : nullptr,
+                 std::sqrt(sigma2), od.p + (size_t)(q0 + q) * n * p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));            // the group's buffers go back to the pool
+  }
+  od.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Building blocks for tests beside lmm_dev_statespace_smooth: ONE latent from DEVICE pointers, its mean not read.  f: [sample][n].
+static int ss_dev_sample(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, const double* z, const double* xi,
+                         int nsamples, int chunk, double* f) {
+  if (n <= 0 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  RESOLVE(gp, 1, 1);
+  if (int rc = ss_check_latents(lts, 1)) return rc;
+  if (int rc = ss_check_sorted(x, n)) return rc;
+  const size_t zs = (size_t)ss_state_dim(lts[0].kind) * n;
+  const int group = ss_sample_group(n, 1, nsamples);
+  for (int q0 = 0; q0 < nsamples; q0 += group) {
+    const int ng = std::min(group, nsamples - q0);
+    double* fq = f + (size_t)q0 * n;
+    if (int rc = ss_paths(x, n, lts, 1, ng, z + (size_t)q0 * zs, zs, chunk, false, fq)) return rc;
+    if (w)
+      if (int rc = ss_condition(x, n, lts, 1, ng, w, r, xi + (size_t)q0 * n, (size_t)n, chunk, false, fq)) return rc;
+  }
+  return LMM_OK;
+}
+
+int lmm_dev_statespace_sample(const double* x, int n, const lmm_gp_t* gp, const double* z, int nsamples, int chunk, double* f) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !gp || !z || !f) return fail(LMM_ERR_ARG, "bad arguments");
+  return ss_dev_sample(x, n, gp, nullptr, nullptr, z, nullptr, nsamples, chunk, f);
+  LMM_CATCH
+}
+
+int lmm_dev_statespace_sample_posterior(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, const double* z,
+                                        const double* xi, int nsamples, int chunk, double* f) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !gp || !w || !r || !z || !xi || !f) return fail(LMM_ERR_ARG, "bad arguments");
+  return ss_dev_sample(x, n, gp, w, r, z, xi, nsamples, chunk, f);
   LMM_CATCH
 }
 

@@ -345,6 +345,22 @@ void launch_ss_grad(const SSArgs& a, int D, int nb, double* gtheta, hipStream_t 
 // sums[4 l + q] = sum_t alpha, w alpha^2, w c, grad_w in a fixed order; ppart: nb * 4 * ss_point_blocks(n) doubles
 int ss_point_blocks(int n);
 void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, double* ppart, double* sums, hipStream_t st);
+// Sampling.  One (latent, sample) pair of a launch: variance, 1 / lengthscale, its standard normals z (device, D n values, component i
+// of point t at z[i n + t]), the constant added to the path, and the path it writes (device, n values: the first component of the state).
+struct SSPathLat { double var, inv_ls, mean; const double* z; double* f; };
+struct SSPathArgs {
+  const double* x; int n, chunk, nch;         // as SSArgs
+  double* agg;                                // nb * ss_aff_agg_elems(D, nch) doubles: the affine aggregates and the scan's levels
+  SSPathLat lat[LMM_MAX_BATCH];
+};
+size_t ss_aff_agg_elems(int D, int nch);      // per pair
+// fold, scan and restart of the prior paths of nb pairs with state dimension D
+void launch_ss_path(const SSPathArgs& a, int D, int nb, hipStream_t st);
+// rp[latent k][sample q][n] = r_k - f[q][k] - sqrt(w_k) xi[q xi_stride + k n] at observed points, r_k where w = +Inf (xi not read)
+void launch_ss_pathwise(const double* r, const double* w, const double* f, const double* xi, size_t xi_stride, int n, int ms, int N,
+                        double* rp, hipStream_t st);
+// f[sample q][latent k][n] += sm[k][q][n]
+void launch_ss_addpath(double* f, const double* sm, int n, int ms, int N, hipStream_t st);
 // *flag (preset to INT_MAX) = the first t with !(x_t >= x_{t-1})
 void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st);
 // rows idx[0 .. nsel) of an n x p column-major matrix into an nsel x p one, and back

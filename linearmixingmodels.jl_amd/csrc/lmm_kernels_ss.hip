@@ -12,6 +12,9 @@
 // the same text instantiated with SSDual (lmm_statespace.h): ss_dfold_kernel, the scan over SSFwd<D, SSDual> and ss_dfilter_kernel, with
 // blockIdx.y in {0, 1} the seeded parameter, so a thread carries one tangent.  d lml / d r_t and d lml / d w_t come from the smoothed
 // marginals (ss_point_kernel), with fixed-order sums of what the OILMM chain rule needs.
+// Sampling (launch_ss_path): the prior path is an affine recursion in the caller's normals, so phases 1 - 3 run on SSAff<D> elements
+// (ss_sfold_kernel, the scan with AffOp, ss_path_kernel); a posterior path is the prior path plus the smoothed mean of the residual
+// data r - f - sqrt(w) xi (ss_pathwise_kernel, then the filter and smoother above, then ss_addpath_kernel).
 #include "lmm_internal.h"
 #include "lmm_statespace.h"
 
@@ -366,6 +369,98 @@ __global__ __launch_bounds__(256) void ss_scatter_rows_kernel(const double* __re
   if (j < nsel) out[idx[j] + (size_t)o * n] = in[j + (size_t)o * nsel];
 }
 
+// ---- sampling ------------------------------------------------------------------------------------------------------------------
+// The prior path s_t = A(dt_t) s_{t-1} + chol(Q(dt_t)) zeta_t, s_0 = chol(Pinf) zeta_0, is an affine recursion, so the same three
+// phases serve it with SSAff<D> elements (D^2 + D doubles): ss_sfold_kernel, the scan with AffOp, ss_path_kernel.  blockIdx.z runs over
+// the (latent, sample) pairs of a launch; zeta is read straight from the caller's buffer, component i of point t at z[i n + t].
+template <int D>
+__device__ __forceinline__ SSModel<D> ss_path_model(const SSPathLat& L) {
+  SSModel<D> M;
+  ss_model<D>(L.var, L.inv_ls, M);
+  return M;
+}
+
+template <int D>
+__device__ __forceinline__ void ss_load_zeta(const double* __restrict__ z, int n, long long t, double zeta[D]) {
+  for (int i = 0; i < D; ++i) zeta[i] = z[(size_t)i * n + t];
+}
+
+template <int D>
+__global__ __launch_bounds__(SS_THREADS) void ss_sfold_kernel(SSPathArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const SSPathLat& L = a.lat[z];
+  const SSModel<D> M = ss_path_model<D>(L);
+  const long long t0 = (long long)j * a.chunk;
+  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  SSAff<D> acc, el;
+  double zeta[D];
+  double xp = a.x[t0];
+  ss_load_zeta<D>(L.z, a.n, t0, zeta);
+  ss_aff_element<D>(M, t0 == 0, t0 == 0 ? 0.0 : xp - a.x[t0 - 1], zeta, acc);
+  for (long long t = t0 + 1; t < t1; ++t) {
+    const double xt = a.x[t];
+    ss_load_zeta<D>(L.z, a.n, t, zeta);
+    ss_aff_element<D>(M, false, xt - xp, zeta, el);
+    ss_aff_combine<D>(acc, el, acc);
+    xp = xt;
+  }
+  reinterpret_cast<SSAff<D>*>(a.agg)[(size_t)z * a.nch + j] = acc;
+}
+
+struct AffOp {
+  template <int D> static __device__ __forceinline__ void combine(const SSAff<D>& a, const SSAff<D>& b, SSAff<D>& o) { ss_aff_combine<D>(a, b, o); }
+};
+
+// each thread restarts the recursion from its prefix state (the c of the scanned aggregate before its run) and writes f_t = (s_t)_1 (+ lat.mean)
+template <int D>
+__global__ __launch_bounds__(SS_THREADS) void ss_path_kernel(SSPathArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const SSPathLat& L = a.lat[z];
+  const SSModel<D> M = ss_path_model<D>(L);
+  const long long t0 = (long long)j * a.chunk;
+  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  double s[D], zeta[D];
+  for (int i = 0; i < D; ++i) s[i] = 0.0;           // the first element has A = 0 and ignores this state
+  if (j > 0) {
+    const SSAff<D>& pre = reinterpret_cast<const SSAff<D>*>(a.agg)[(size_t)z * a.nch + j - 1];
+    for (int i = 0; i < D; ++i) s[i] = pre.c[i];
+  }
+  SSAff<D> el;
+  double xp = t0 == 0 ? a.x[0] : a.x[t0 - 1];
+  for (long long t = t0; t < t1; ++t) {
+    const double xt = a.x[t];
+    ss_load_zeta<D>(L.z, a.n, t, zeta);
+    ss_aff_element<D>(M, t == 0, xt - xp, zeta, el);
+    ss_aff_step<D>(el, s);
+    xp = xt;
+    L.f[t] = s[0] + L.mean;
+  }
+}
+
+// Pathwise conditioning, entry (latent k, sample q) = blockIdx.z, blockIdx.y: rp = r - f - sqrt(w) xi at an observed point; an
+// unobserved one (w = +Inf) keeps its r, and xi is not read there.  r, w: [latent][n]; f: [sample][latent][n]; xi: sample q's values of
+// latent k at q xi_stride + k n; rp: [latent][sample][n], the entry order of the filter and smoother that follow.
+__global__ __launch_bounds__(256) void ss_pathwise_kernel(const double* __restrict__ r, const double* __restrict__ w,
+                                                          const double* __restrict__ f, const double* __restrict__ xi, size_t xi_stride,
+                                                          int n, double* __restrict__ rp) {
+  const int t = blockIdx.x * 256 + threadIdx.x, q = blockIdx.y, k = blockIdx.z, ms = gridDim.z, N = gridDim.y;
+  if (t >= n) return;
+  const double wt = w[(size_t)k * n + t];
+  double v = r[(size_t)k * n + t];
+  if (wt < INFINITY) v = v - f[((size_t)q * ms + k) * n + t] - sqrt(wt) * xi[(size_t)q * xi_stride + (size_t)k * n + t];
+  rp[((size_t)k * N + q) * n + t] = v;
+}
+
+// f[sample][latent][n] += sm[latent][sample][n]: the posterior path, prior path + smoothed mean of the residual (+ the latent's mean)
+__global__ __launch_bounds__(256) void ss_addpath_kernel(double* __restrict__ f, const double* __restrict__ sm, int n) {
+  const int t = blockIdx.x * 256 + threadIdx.x, q = blockIdx.y, k = blockIdx.z, ms = gridDim.z, N = gridDim.y;
+  if (t >= n) return;
+  const size_t i = ((size_t)q * ms + k) * n + t;
+  f[i] = f[i] + sm[((size_t)k * N + q) * n + t];
+}
+
 size_t scan_items(int nch, int W = SS_SCAN) {         // items of every level below the first
   size_t tot = 0;
   int N = nch;
@@ -401,6 +496,15 @@ void grad_D(const SSArgs& a, int nb, double* gtheta, hipStream_t st) {
   scan_levels<D, E, FwdOp, false>(agg, a.nch, 2 * nb, agg + (size_t)2 * nb * a.nch, st);
   hipLaunchKernelGGL(ss_dfilter_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
   hipLaunchKernelGGL(ss_finish_kernel, dim3(2 * nb), dim3(SS_THREADS), 0, st, (const double*)a.dpart, a.nch, gtheta);
+}
+
+template <int D>
+void path_D(const SSPathArgs& a, int nb, hipStream_t st) {
+  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
+  hipLaunchKernelGGL(ss_sfold_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  SSAff<D>* agg = reinterpret_cast<SSAff<D>*>(a.agg);
+  scan_levels<D, SSAff<D>, AffOp, false>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
+  hipLaunchKernelGGL(ss_path_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
 }
 
 }  // namespace
@@ -446,6 +550,23 @@ void launch_ss_smooth(const SSArgs& a, int D, int nb, hipStream_t st) {
   if (D == 1) smooth_D<1>(a, nb, st);
   else if (D == 2) smooth_D<2>(a, nb, st);
   else smooth_D<3>(a, nb, st);
+}
+
+size_t ss_aff_agg_elems(int D, int nch) { return ((size_t)nch + scan_items(nch)) * (size_t)(D * D + D); }
+
+void launch_ss_path(const SSPathArgs& a, int D, int nb, hipStream_t st) {
+  if (D == 1) path_D<1>(a, nb, st);
+  else if (D == 2) path_D<2>(a, nb, st);
+  else path_D<3>(a, nb, st);
+}
+
+void launch_ss_pathwise(const double* r, const double* w, const double* f, const double* xi, size_t xi_stride, int n, int ms, int N,
+                        double* rp, hipStream_t st) {
+  hipLaunchKernelGGL(ss_pathwise_kernel, dim3((n + 255) / 256, N, ms), dim3(256), 0, st, r, w, f, xi, xi_stride, n, rp);
+}
+
+void launch_ss_addpath(double* f, const double* sm, int n, int ms, int N, hipStream_t st) {
+  hipLaunchKernelGGL(ss_addpath_kernel, dim3((n + 255) / 256, N, ms), dim3(256), 0, st, f, sm, n);
 }
 
 void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st) {

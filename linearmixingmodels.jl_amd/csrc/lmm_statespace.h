@@ -363,3 +363,70 @@ SS_HD void ss_rts_step(const SSBwd<D>& e, double ms[D], double Ps[D][D]) {
   }
   ss_sym<D>(Ps);
 }
+
+// ---- sampling: the prior path as an affine scan ------------------------------------------------------------------------------------
+// Lower Cholesky factor with non-negative diagonal of a symmetric positive SEMI-definite X (its lower triangle is read).  A pivot that
+// is not > 0 gives a zero column (its diagonal and everything below it), so X = 0 gives L = 0 exactly and a Q that rounding has made
+// slightly indefinite (Q = Pinf - A Pinf A' is a difference) is served.
+template <int D>
+SS_HD void ss_chol_psd(const double X[D][D], double L[D][D]) {
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) L[i][j] = 0.0;
+  for (int j = 0; j < D; ++j) {
+    double s = X[j][j];
+    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+    if (!(s > 0.0)) continue;
+    const double dj = sqrt(s);
+    L[j][j] = dj;
+    for (int i = j + 1; i < D; ++i) {
+      double t = X[i][j];
+      for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+      L[i][j] = t / dj;
+    }
+  }
+}
+
+// s -> A s + c
+template <int D>
+struct SSAff { double A[D][D], c[D]; };
+
+// The element of one point of the prior path s_t = A(dt) s_{t-1} + chol(Q(dt)) zeta_t.  first: (0, chol(Pinf) zeta_0).
+template <int D>
+SS_HD void ss_aff_element(const SSModel<D>& M, bool first, double dt, const double zeta[D], SSAff<D>& e) {
+  double Q[D][D], L[D][D];
+  if (first) {
+    for (int i = 0; i < D; ++i)
+      for (int j = 0; j < D; ++j) { e.A[i][j] = 0.0; Q[i][j] = M.Pinf[i][j]; }
+  } else ss_AQ<D>(M, dt, e.A, Q);
+  ss_chol_psd<D>(Q, L);
+  for (int i = 0; i < D; ++i) {
+    double s = 0.0;
+    for (int k = 0; k <= i; ++k) s += L[i][k] * zeta[k];
+    e.c[i] = s;
+  }
+}
+
+// out = a (.) b with a the earlier run: (A_b A_a, A_b c_a + c_b); out may alias a or b
+template <int D>
+SS_HD void ss_aff_combine(const SSAff<D>& a, const SSAff<D>& b, SSAff<D>& out) {
+  SSAff<D> o;
+  ss_mm<D>(b.A, a.A, o.A);
+  for (int i = 0; i < D; ++i) {
+    double s = b.c[i];
+    for (int k = 0; k < D; ++k) s += b.A[i][k] * a.c[k];
+    o.c[i] = s;
+  }
+  out = o;
+}
+
+// One step of the path: the state s of the previous point -> that of the point with element e
+template <int D>
+SS_HD void ss_aff_step(const SSAff<D>& e, double s[D]) {
+  double t[D];
+  for (int i = 0; i < D; ++i) {
+    double v = e.c[i];
+    for (int k = 0; k < D; ++k) v += e.A[i][k] * s[k];
+    t[i] = v;
+  }
+  for (int i = 0; i < D; ++i) s[i] = t[i];
+}

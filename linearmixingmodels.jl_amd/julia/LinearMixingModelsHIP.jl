@@ -20,7 +20,7 @@ using AbstractGPs, KernelFunctions, LinearAlgebra, Random, FillArrays, ChainRule
 using LinearMixingModels
 using LinearMixingModels: ILMM, IndependentMOGP, Orthogonal, unpack, noise_var
 
-export hip, HIPMOGP, statespace_logpdf, statespace_mean_and_var
+export hip, HIPMOGP, statespace_logpdf, statespace_mean_and_var, statespace_rand
 
 const liblmm = get(ENV, "LMM_HIP_LIB", "liblmm_hip.so")
 
@@ -518,6 +518,55 @@ function statespace_mean_and_var(fx::ByOutputsFill{HIPOILMM}, y::AbstractVector;
     back(v) = (B = similar(reshape(v, N, p)); B[perm, :] = reshape(v, N, p); vec(B[rows, :]))
     return back(mean), back(var)
 end
+
+# statespace_rand(rng, fx[, N]; y, xs, add_noise) through lmm_oilmm_rand_statespace: joint samples in O(n), exact -- of the prior fx
+# (y === nothing), or of the posterior given y at the training inputs or at new inputs xs (only their rows are returned).  The normals
+# are drawn with randn(rng, ...) per sample in the library's order, all indexed by SORTED point (N_all points, new inputs included):
+# for each latent l in order D_l * N_all (D = 1 / 2 / 3 for Matern12 / 32 / 52; component i of sorted point t at i * N_all + t), then,
+# with y only, m * N_all, then, if add_noise, N_all * p.  Returns a vector (no N) or an (n p) x N matrix, by outputs.
+_statespace_dim(kd) = kd == 3 ? 1 : kd == 1 ? 2 : kd == 2 ? 3 : error("state-space inference is served for Matern12, Matern32 and Matern52 latents")
+function _statespace_rand(rng::AbstractRNG, fx::ByOutputsFill{HIPOILMM}, N::Integer, y, xs, add_noise::Bool)
+    fs, H, σ², x = unpack(fx)
+    isposterior(fs) && error("state-space inference is served on a prior OILMM only")
+    y === nothing && xs !== nothing && throw(ArgumentError("statespace_rand: xs needs y; to sample the prior at other inputs, put them into fx.x"))
+    N >= 1 || throw(ArgumentError("statespace_rand: N must be >= 1"))
+    U, S, p, m = _hargs(H)
+    if y === nothing
+        X = _xmat(x)
+        size(X, 1) == 1 || error("state-space inference is served for one-dimensional inputs (d = $(size(X, 1)))")
+        xv = vec(X); n = length(xv); perm = sortperm(xv; alg=MergeSort); xv = xv[perm]; yv = Float64[]
+    else
+        xv, yv, perm, n = _statespace_sorted(x, y, p, xs)
+    end
+    Na = length(xv)
+    dims = [_statespace_dim(_desc(f.kernel)[1]) for f in fs.fs]
+    z = Matrix{Float64}(undef, sum(dims) * Na, N)
+    ξ = Matrix{Float64}(undef, y === nothing ? 0 : m * Na, N)
+    ε = Matrix{Float64}(undef, add_noise ? Na * p : 0, N)
+    for q in 1:N
+        off = 0
+        for D in dims
+            z[off+1:off+D*Na, q] = randn(rng, D * Na); off += D * Na
+        end
+        y === nothing || (ξ[:, q] = randn(rng, m * Na))
+        add_noise && (ε[:, q] = randn(rng, Na * p))
+    end
+    out = Matrix{Float64}(undef, Na * p, N)
+    _gps(fs.fs) do gps, tags
+        GC.@preserve xv yv U S gps z ξ ε out check(ccall((:lmm_oilmm_rand_statespace, liblmm), Cint,
+            (Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint, Cint,
+             Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+            xv, Na, y === nothing ? Ptr{Cdouble}(C_NULL) : pointer(yv), p, U, S, m, σ², gps, 0, m, Cint(add_noise), N,
+            z, y === nothing ? Ptr{Cdouble}(C_NULL) : pointer(ξ), add_noise ? pointer(ε) : Ptr{Cdouble}(C_NULL), out))
+    end
+    rows = xs === nothing ? (1:n) : (n+1:Na)
+    back(v) = (B = similar(reshape(v, Na, p)); B[perm, :] = reshape(v, Na, p); vec(B[rows, :]))
+    return reduce(hcat, [back(out[:, q]) for q in 1:N])
+end
+statespace_rand(rng::AbstractRNG, fx::ByOutputsFill{HIPOILMM}; y=nothing, xs=nothing, add_noise::Bool=true) =
+    vec(_statespace_rand(rng, fx, 1, y, xs, add_noise))
+statespace_rand(rng::AbstractRNG, fx::ByOutputsFill{HIPOILMM}, N::Integer; y=nothing, xs=nothing, add_noise::Bool=true) =
+    _statespace_rand(rng, fx, N, y, xs, add_noise)
 
 # ---- missing observations: y::AbstractVector{Union{Missing,Float64}} ----------------------------------------------------------------
 # The reference's notebook: "Heterotopic and missing data ... are not supported yet ... using the missing data techniques identified in

@@ -829,8 +829,17 @@ _STATESPACE_KINDS = ("matern12", "matern32", "matern52")
 def _statespace_sorted(xv, y, p: int, xs=None):
     """(x sorted, y permuted, perm, n) for inputs xv (n,) and the by-outputs vector y (n * p); with xs (ns,) the new inputs are appended
     as points whose outputs are all NaN before sorting.  The sort is stable; perm[k] is the original index of sorted point k.  NumPy
-    arrays unless xv or y is a torch tensor (then tensors on that one's device)."""
+    arrays unless xv or y is a torch tensor (then tensors on that one's device).  y = None (no xs): only the inputs are sorted, and the
+    second value is None."""
     n = int(xv.shape[-1])
+    if y is None:
+        if L._is_torch(xv):
+            import torch
+            xa, perm = torch.sort(torch.as_tensor(xv, dtype=torch.float64).reshape(-1), stable=True)
+            return xa.contiguous(), None, perm, n
+        xa = np.asarray(xv, dtype=np.float64).reshape(-1)
+        perm = np.argsort(xa, kind="stable")
+        return np.ascontiguousarray(xa[perm]), None, perm, n
     if L._is_torch(xv) or L._is_torch(y):
         import torch
         dev = xv.device if L._is_torch(xv) else y.device
@@ -974,6 +983,72 @@ def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = T
         return _NoStateSpaceMixingGradient(out)
     out.update(S=gS, U=gU.reshape(m, p).T.copy())
     return out
+
+
+_STATESPACE_DIM = {"matern12": 1, "matern32": 2, "matern52": 3}
+
+
+def statespace_rand(rng, fx: "FiniteGP", y=None, N: Optional[int] = None, add_noise: bool = True, xs=None):
+    """Joint samples of the same models in O(n), exact: of the prior fx (y=None: rand(rng, fx)), or of the posterior given y
+    (rand(rng, posterior(fx, y)(x*, sigma2))) at the training inputs (xs=None) or at the new inputs xs ((ns,); merged into the inputs
+    as points without observations, only their rows are returned).  Per latent the prior path is the SDE's recursion driven by D
+    standard normals per point (D = 1 / 2 / 3 for Matern12 / 32 / 52), run as a scan; a posterior path is the prior path plus the
+    smoothed mean of the residual data (pathwise conditioning), through the filter and smoother of statespace_mean_and_var.
+    `rng` is a NumPy Generator or a DeviceNormals, as for rand; buffers and the result live where the normals do.  Draw order, per
+    sample, all indexed by SORTED point (the stable sort of the inputs; n_all counts the new inputs as well):
+      for each latent l in order, standard_normal(D_l * n_all)     (component-major: component i of sorted point t at i * n_all + t);
+      then, with y only, standard_normal(m * n_all)                (latent-major);
+      then, if add_noise, standard_normal(n_all * p)               (by outputs).
+    Returns the by-outputs vector (n * p,) for N=None, else (n * p, N), in the callers' order of points.  For fixed normals the path is
+    ill-conditioned in the spacings where they are small against the lengthscale; its distribution is not."""
+    f, x = fx.f, fx.x
+    yc = _statespace_args(fx, np.broadcast_to(0.0, (x.n * x.out_dim,)) if y is None else y, "statespace_rand")
+    if y is None and xs is not None:
+        raise ValueError("statespace_rand: xs needs y; to sample the prior at other inputs, put them into fx.x")
+    if N is not None and (int(N) != N or N < 1):
+        raise ValueError("statespace_rand: N is None or a number of samples >= 1")
+    if xs is not None:
+        if not hasattr(xs, "shape"):
+            xs = np.asarray(xs, dtype=np.float64)
+        if len(xs.shape) != 1:
+            raise ValueError("statespace_rand: xs is a (ns,) array of one-dimensional inputs")
+        if int(xs.shape[0]) == 0:
+            xs = None
+    xa, ya, perm, n = _statespace_sorted(x.x.reshape(-1), None if y is None else yc, x.out_dim, xs)
+    na, Ns = int(perm.shape[0]), 1 if N is None else int(N)
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    dims = [_STATESPACE_DIM[g.kernel.kind] for g in f.f.fs]
+    z = _empty_for(rng, Ns, sum(dims) * na)
+    xi = _empty_for(rng, Ns, m * na) if y is not None else None
+    eps = _empty_for(rng, Ns, na * p) if add_noise else None
+    for q in range(Ns):
+        off = 0
+        for D in dims:
+            z[q, off:off + D * na] = rng.standard_normal(D * na)
+            off += D * na
+        if xi is not None:
+            xi[q] = rng.standard_normal(m * na)
+        if eps is not None:
+            eps[q] = rng.standard_normal(na * p)
+    out = _empty_for(rng, Ns, na * p)
+    L.check(L.load().lmm_oilmm_rand_statespace(L.Arr(xa).ptr, na, None if y is None else L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m,
+                                               float(fx.sigma2), gps, 0, m, int(add_noise), Ns, L.Arr(z).ptr,
+                                               None if xi is None else L.Arr(xi).ptr, None if eps is None else L.Arr(eps).ptr,
+                                               L.Arr(out, True).ptr))
+    if L._is_torch(out) and not L._is_torch(perm):        # the un-permuting happens where the result lives
+        import torch
+        perm = torch.as_tensor(perm, device=out.device)
+    elif L._is_torch(perm) and not L._is_torch(out):
+        perm = perm.cpu().numpy()
+    cols = [_statespace_unsorted(out[q], perm, p, n, xs is not None) for q in range(Ns)]
+    if N is None:
+        return cols[0]
+    if L._is_torch(out):
+        import torch
+        return torch.stack(cols, dim=1)
+    return np.stack(cols, axis=1)
 
 
 # Dense-H ILMM logpdf: allow the identical-kernel decoupled shortcut (exact; SURVEY.md section 3.2).  Set False to force
@@ -1543,8 +1618,10 @@ class DeviceNormals:
         import torch
         L.ensure_init()
         out = torch.empty(int(count), dtype=torch.float64, device="cuda")
+        # through Arr, so that the library's stream waits for what torch has queued: the allocator may hand out memory that work still
+        # in flight on torch's stream (the temporaries of a sort, say) was using
         L.check(L.load().lmm_normals(C.c_ulonglong(self.seed), C.c_ulonglong(self.stream), C.c_size_t(int(count)),
-                                     C.c_void_p(out.data_ptr())))
+                                     L.Arr(out, True).ptr))
         self.stream += 1
         return out
 

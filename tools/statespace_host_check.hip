@@ -1,7 +1,9 @@
 // statespace_host_check.hip -- the double and the SSDual instantiations of csrc/lmm_statespace.h run on the CPU, with the chunked schedule
 // of lmm_kernels_ss.hip (fold, a sequential scan of the aggregates, filter restarted from the prefix) for chunk = 1, 7, 64 and n, Matern12 /
 // 32 / 52, a quarter of the points unobserved and a run of equal inputs.  Checks that the value of the dual instantiation is bitwise the
-// double one's and that both tangents agree with central differences of the value (step 1e-5: 1e-6 relative).  A stand-alone program for
+// double one's and that both tangents agree with central differences of the value (step 1e-5: 1e-6 relative).  Sampling: ss_chol_psd on a
+// zero, a rank-deficient and a slightly indefinite matrix, and the affine fold / scan / restart of the prior path at the same chunks
+// against the sequential recursion (1e-12 sqrt(v); an equal input repeats the state bitwise).  A stand-alone program for
 // host sanitizers; it needs no GPU:
 //   hipcc -x hip --offload-arch=gfx950 -O1 -std=c++17 -I linearmixingmodels.jl_amd/csrc -Xarch_host -fsanitize=address,undefined \
 //         tools/statespace_host_check.hip -o statespace_host_check && ./statespace_host_check
@@ -9,6 +11,7 @@
 #include <cstdio>
 #include <vector>
 #include <cmath>
+#include <algorithm>
 template <int D, typename Sc>
 Sc run(Sc var, Sc il, const std::vector<double>& x, const std::vector<double>& w, const std::vector<double>& r, int chunk) {
   SSModel<D, Sc> M; ss_model<D, Sc>(var, il, M);
@@ -50,4 +53,75 @@ template <int D> int check() {
   }
   return bad;
 }
-int main() { int bad = check<1>() + check<2>() + check<3>(); std::printf("bad=%d\n", bad); return bad != 0; }
+// the prior path by the chunked schedule: fold the affine elements, scan the aggregates, restart from the prefix state
+template <int D>
+std::vector<double> path(double var, double il, const std::vector<double>& x, const std::vector<double>& z, int chunk) {
+  SSModel<D> M; ss_model<D>(var, il, M);
+  const int n = (int)x.size(), nch = (n + chunk - 1) / chunk;
+  auto zeta = [&](int t, double* o) { for (int i = 0; i < D; ++i) o[i] = z[(size_t)i * n + t]; };
+  std::vector<SSAff<D>> agg(nch);
+  double zt[D];
+  for (int j = 0; j < nch; ++j) {
+    int t0 = j * chunk, t1 = std::min(n, t0 + chunk);
+    SSAff<D> acc, el;
+    zeta(t0, zt);
+    ss_aff_element<D>(M, t0 == 0, t0 == 0 ? 0.0 : x[t0] - x[t0 - 1], zt, acc);
+    for (int t = t0 + 1; t < t1; ++t) { zeta(t, zt); ss_aff_element<D>(M, false, x[t] - x[t - 1], zt, el); ss_aff_combine<D>(acc, el, acc); }
+    agg[j] = acc;
+  }
+  for (int j = 1; j < nch; ++j) ss_aff_combine<D>(agg[j - 1], agg[j], agg[j]);
+  std::vector<double> f(n);
+  for (int j = 0; j < nch; ++j) {
+    int t0 = j * chunk, t1 = std::min(n, t0 + chunk);
+    double s[D];
+    for (int i = 0; i < D; ++i) s[i] = j ? agg[j - 1].c[i] : 0.0;
+    SSAff<D> el;
+    for (int t = t0; t < t1; ++t) { zeta(t, zt); ss_aff_element<D>(M, t == 0, t == 0 ? 0.0 : x[t] - x[t - 1], zt, el); ss_aff_step<D>(el, s); f[t] = s[0]; }
+  }
+  return f;
+}
+template <int D> int check_chol() {
+  int bad = 0;
+  double X[D][D], L[D][D];
+  for (int i = 0; i < D; ++i) for (int j = 0; j < D; ++j) X[i][j] = 0.0;
+  ss_chol_psd<D>(X, L);                                                  // zero matrix: zero factor
+  for (int i = 0; i < D; ++i) for (int j = 0; j < D; ++j) if (L[i][j] != 0.0) ++bad;
+  for (int i = 0; i < D; ++i) for (int j = 0; j < D; ++j) X[i][j] = (i + 1.0) * (j + 1.0);      // rank one: only the first column
+  X[D - 1][D - 1] += (D > 1 ? -1e-18 : 0.0);                             // and a last pivot that rounding has made negative
+  ss_chol_psd<D>(X, L);
+  for (int i = 0; i < D; ++i) for (int j = 0; j < D; ++j) {
+    const double want = j == 0 ? i + 1.0 : 0.0;
+    if (!(std::fabs(L[i][j] - want) <= 1e-15) || (j > 0 && L[i][j] != 0.0)) ++bad;
+  }
+  SSModel<D> M; ss_model<D>(1.3, 1 / 0.7, M);                            // Q of a tiny step: finite, non-negative diagonal, L L' = Q to rounding
+  double A[D][D], Q[D][D];
+  ss_AQ<D>(M, 1e-4, A, Q);
+  ss_chol_psd<D>(Q, L);
+  for (int i = 0; i < D; ++i) for (int j = 0; j < D; ++j) if (!std::isfinite(L[i][j]) || (i == j && L[i][j] < 0.0) || (j > i && L[i][j] != 0.0)) ++bad;
+  std::printf("D=%d chol_psd bad=%d\n", D, bad);
+  return bad;
+}
+template <int D> int check_path() {
+  const int n = 200; std::vector<double> x(n), z((size_t)D * n);
+  unsigned s = 777u + D; auto u = [&]() { s = s * 1664525u + 1013904223u; return (s >> 8) / 16777216.0; };
+  double xx = 0; for (int t = 0; t < n; ++t) { xx += 0.7 * (0.5 + 1.5 * u()); x[t] = xx; }
+  for (auto& v : z) v = 2 * u() - 1 + 2 * u() - 1;
+  x[11] = x[10]; x[12] = x[10];
+  for (int t = 100; t < n; ++t) x[t] += 7000.0;                           // one gap of 1e4 lengthscales
+  const double v = 1.3, il = 1 / 0.7; int bad = 0;
+  const std::vector<double> seq = path<D>(v, il, x, z, n);
+  if (seq[11] != seq[10] || seq[12] != seq[10]) ++bad;
+  for (int chunk : {1, 7, 64, 200}) {
+    const std::vector<double> f = path<D>(v, il, x, z, chunk);
+    double err = 0; for (int t = 0; t < n; ++t) err = std::max(err, std::fabs(f[t] - seq[t]));
+    std::printf("D=%d chunk=%3d path err %.3g\n", D, chunk, err);
+    if (!(err <= 1e-12 * std::sqrt(v))) ++bad;
+  }
+  return bad;
+}
+int main() {
+  int bad = check<1>() + check<2>() + check<3>();
+  bad += check_chol<1>() + check_chol<2>() + check_chol<3>() + check_path<1>() + check_path<2>() + check_path<3>();
+  std::printf("bad=%d\n", bad);
+  return bad != 0;
+}
