@@ -801,6 +801,20 @@ int lmm_dev_gemm_nt_sub(double* C, int ldc, const double* A, int lda, const doub
  * once).  Test hook of the switches: on = 0 / 1, min_k >= 128 (updates with K >= min_k are emulated), 8 <= nmod <= 16 moduli;
  * on < 0 goes back to the env defaults. */
 int lmm_dev_set_f64_emul(int on, int min_k, int nmod);
+/* Test hook of the shape rule that decides which updates are emulated while no explicit threshold is set (neither LMM_F64_EMUL_MINK nor
+ * lmm_dev_set_f64_emul): K >= min_k_always always, min_k_shape <= K < min_k_always when (matrices of the batch) x (outputs of the update's
+ * lower trapezoid) >= min_outputs, smaller K never.  min_k_always < 0 goes back to the defaults (4096, 2048 and the measured crossover). */
+int lmm_dev_set_f64_emul_rule(int min_k_always, int min_k_shape, double min_outputs);
+/* Test hook: an emulated update walks its batch in groups of as many matrices as its scratch block holds; g >= 1 caps the group size,
+ * 0 goes back to the default.  Results do not depend on it. */
+int lmm_dev_set_emul_group(int g);
+/* Host-only (no GPU, no lmm_init needed): the emulation plan of a factorisation of nb matrices with NR rows and NC columns, by the code
+ * the factorisation itself runs.  out[0] = bytes of the scratch block it asks for (0: nothing is emulated), out[1] = matrices per group
+ * that block is sized for; then 6 words per trailing update with at least 128 columns, in launch order: M, N, K, emulated (0 / 1),
+ * matrices per group, scratch bytes needed at that group size.  out holds 2 + 6 cap words.  Returns the number of updates (those beyond
+ * cap are counted, not written), or -LMM_ERR_ARG.  Updates inside a block column that one dataflow launch factors are listed too; they
+ * never run on their own. */
+int lmm_dev_emul_plan(int NR, int NC, int nb, long long* out, int cap);
 /* Test hook: the emulation's GEMM is a persistent kernel of min(work items, CUs) workgroups; wgs >= 1 caps that grid (a small shape
  * then makes one workgroup walk several tiles), 0 goes back to the default.  Results do not depend on it. */
 int lmm_dev_set_emul_gemm_workgroups(int wgs);

@@ -749,23 +749,69 @@ void potrf_rec(const Batch& B, int ld, int NR, int j0, int w, int n_real, hipStr
 static int g_slots_in_flight = 1;       // batches that run concurrently on the slot streams (set by fork_slots; read by potrf_batch's base-case rule)
 static int g_region_whole = 1;          // LMM_REGION_ALL=1: also as the base case of the recursion for larger matrices (measured: no gain)
 static int g_region_cols = -1;          // widest block column potrf_region_kernel takes in one launch (LMM_REGION=<columns>, up to 1024; default 0: off)
+// The scratch block potrf_batch asks for (emul_block_plan): sized for the widest emulated level at G = min(4, nb, 12 GB / that level) matrices (0: none)
+struct EmulBlockPlan { size_t bytes = 0; int G = 0; };
 // bulk_done (implies first_done): the rows below that block are solved as well (the update launch that factored it ran them too).
 struct NodeFlags { int* p = nullptr; int stride = 0; int min_k = 0, max_k = 1 << 30; int rows_real = -1; BatchPtr S{}; int region_cols = 0;
-                   void* emul = nullptr; size_t emul_bytes = 0; int emul_G = 0, emul_mink = 0, emul_nmod = 0; };      // emul: scratch of the int8 emulation of the updates with K >= emul_mink (nullptr: off)   // region_cols: widest block column that becomes ONE dataflow launch in this factorisation   // S: region assistants' scratch      // rows_real: rows that hold data (-1: all NR)
-// Float64 updates with K >= LMM_F64_EMUL_MINK run as exact int8 modular GEMMs (lmm_kernels_i8.hip): LMM_F64_EMUL=0 keeps
-// them on the f64 MFMA kernel.  The env values are read once; lmm_dev_set_f64_emul replaces them (tests).
+                   void* emul = nullptr; EmulBlockPlan emul_plan; int emul_nmod = 0; };      // emul: scratch of the int8 emulation of the updates emul_pays accepts (nullptr: off)   // region_cols: widest block column that becomes ONE dataflow launch in this factorisation   // S: region assistants' scratch      // rows_real: rows that hold data (-1: all NR)
+// Float64 updates run as exact int8 modular GEMMs (lmm_kernels_i8.hip) where that pays: LMM_F64_EMUL=0 keeps them all
+// on the f64 MFMA kernel.  The env values are read once; lmm_dev_set_f64_emul replaces them (tests).
+//   An explicit threshold -- LMM_F64_EMUL_MINK or lmm_dev_set_f64_emul(on, min_k, nmod) -- emulates every update with K >= min_k.
+//   With nothing set (g_emul_mink == 0) the shape rule decides, emul_pays: K >= g_rule_always always; K < g_rule_shape never; between
+//   them when the batch's trapezoid has at least g_rule_outs outputs -- at a fixed K = N both paths grow linearly with the rows and the
+//   matrix count, but the emulated one carries fixed costs (launches per group, the leaf and bulk launches of their own) that only a
+//   large enough update earns back (the crossover table of DESIGN.md 4.17).
 static int g_emul_on = -1, g_emul_mink = -1, g_emul_nmod = LMM_EMUL_MAXMOD;
+constexpr int kRuleAlways = 4096, kRuleShape = 2048;
+constexpr double kRuleOuts = 4.0e7;      // between 16 x (2112 x 2048), which gains under 5 % emulated, and 4 x (6208 x 2048), which gains 20 %
+static int g_rule_always = kRuleAlways, g_rule_shape = kRuleShape;
+static double g_rule_outs = kRuleOuts;
+static int g_emul_group_cap = 0;      // lmm_dev_set_emul_group: at most this many matrices per group of an emulated update (0: no cap)
 static void emul_switches() {
   if (g_emul_on < 0) { const char* e = getenv("LMM_F64_EMUL"); g_emul_on = e ? (atoi(e) != 0) : 1; }
-  if (g_emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_emul_mink = e ? std::max(128, atoi(e)) : 4096; }      // at 2048 C2 and configs[3] gain, but C1 (one 2048^3 update of 8 latents) loses
+  if (g_emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_emul_mink = e ? std::max(128, atoi(e)) : 0; }
 }
-// scratch bytes of the widest emulated update of the recursion over the columns [j0, j0 + w)
-static size_t emul_need(int NR, int j0, int w, int mink, int G, int nmod) {
-  if (w < 256) return 0;
+// Does emulating the M x N (x K) trailing update of nb matrices pay?  The ONE place that decides (after emul_switches()).
+static bool emul_pays(int M, int N, int K, int nb) {
+  if (g_emul_mink > 0) return K >= g_emul_mink;
+  if (K >= g_rule_always) return true;
+  if (K < g_rule_shape) return false;
+  const double outs = (double)N * (N + 1.0) / 2.0 + ((double)M - N) * N;
+  return nb * outs >= g_rule_outs;
+}
+// fn(M, N, K) for every trailing update with N >= 128 columns of the recursion over the columns [j0, j0 + w), in the order
+// potrf_rec_panel reaches them (a block column the region kernel takes in one launch has its updates inside that launch: the
+// walk still names them, which only makes the scratch estimate generous)
+template <class F>
+static void emul_walk(int NR, int j0, int w, F&& fn) {
+  if (w < 256) return;
   const int h = split(w), r0 = j0 + h, Nc = w - h;
-  if (h < mink) return 0;
-  size_t need = (Nc >= 128 && emul_shape_ok(NR - r0, Nc, h)) ? emul_scratch_bytes(NR - r0, Nc, h, G, nmod) : 0;
-  return std::max(need, std::max(emul_need(NR, j0, h, mink, G, nmod), emul_need(NR, r0, Nc, mink, G, nmod)));
+  emul_walk(NR, j0, h, fn);
+  if (Nc >= 128) fn(NR - r0, Nc, h);
+  emul_walk(NR, r0, Nc, fn);
+}
+static bool emul_takes(int M, int N, int K, int nb) { return emul_shape_ok(M, N, K) && emul_pays(M, N, K, nb); }
+// scratch bytes of the widest update of a factorisation of nb matrices that will be emulated, at G matrices per group
+static size_t emul_need(int NR, int NC, int nb, int G, int nmod) {
+  size_t need = 0;
+  emul_walk(NR, 0, NC, [&](int M, int N, int K) { if (emul_takes(M, N, K, nb)) need = std::max(need, emul_scratch_bytes(M, N, K, G, nmod)); });
+  return need;
+}
+static EmulBlockPlan emul_block_plan(int NR, int NC, int nb, int nmod) {
+  EmulBlockPlan P;
+  const size_t one = emul_need(NR, NC, nb, 1, nmod);
+  if (one == 0) return P;
+  P.G = (int)std::max<size_t>(1, std::min<size_t>(std::min(4, nb), (size_t)12e9 / one));
+  P.bytes = emul_need(NR, NC, nb, P.G, nmod);
+  return P;
+}
+// Matrices per group of ONE update inside that block: as many as fit (a level below the widest needs less per matrix, so fewer groups
+// and fewer launches), never fewer than the G the block was sized for
+static int emul_group(int M, int N, int K, int nb, const EmulBlockPlan& P, int nmod) {
+  int gs = (int)std::min<size_t>((size_t)nb, P.bytes / emul_scratch_bytes(M, N, K, 1, nmod));
+  gs = std::max(gs, std::min(P.G, nb));
+  if (g_emul_group_cap > 0) gs = std::min(gs, g_emul_group_cap);
+  return gs;
 }
 void potrf_rec_panel(const Batch& B, const BatchPtr& W2, const BatchInfo& flags, const NodeFlags& nfl, int ld, int NR, int j0, int w, int n_real,
                      hipStream_t st, bool first_done, bool bulk_done = false) {
@@ -807,16 +853,17 @@ void potrf_rec_panel(const Batch& B, const BatchPtr& W2, const BatchInfo& flags,
       // With the bulk rows of the next panel in the same launch (nfl.p): + their Mb * 128^2 flops and 16 B per entry
       // emulated (lmm_kernels_i8.hip): convert + int8 GEMMs + combine in place of the f64 update, then the leaf as a launch of its own;
       // the same flop count, so the class's rate reads as an f64-EQUIVALENT rate
-      const bool emul = nfl.emul != nullptr && h >= nfl.emul_mink && emul_shape_ok(NR - r0, Nc, h);
+      const bool emul = nfl.emul != nullptr && emul_takes(NR - r0, Nc, h, B.nb);
       const double Mb = (!emul && nfl.p && h >= nfl.min_k && h <= nfl.max_k) ? std::max(0.0, Mr - 128.0) : 0;
       ProfScope ps(h >= 1024 ? LMM_PROF_UPDATE : LMM_PROF_UPDATE_SHORT,
                    nb * (2.0 * h * outs + 2.0 * 128.0 * 128.0 * 128.0 / 3.0 + Mb * 128.0 * 128.0), st, NR - r0, Nc, h,
                    nb * (16.0 * outs + 8.0 * Mr * h + 16.0 * Mb * 128.0));
       if (emul) {
-        const size_t need = emul_scratch_bytes(NR - r0, Nc, h, nfl.emul_G, nfl.emul_nmod);
-        if (need > nfl.emul_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", need, nfl.emul_bytes);
+        const int gs = emul_group(NR - r0, Nc, h, B.nb, nfl.emul_plan, nfl.emul_nmod);
+        const size_t need = emul_scratch_bytes(NR - r0, Nc, h, gs, nfl.emul_nmod);
+        if (need > nfl.emul_plan.bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", need, nfl.emul_plan.bytes);
         guard_extent(nfl.emul, need / 8, need / 8, 1, false, "emulated update (scratch)");
-        HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, NR - r0, Nc, h, B.nb, nfl.emul_G, nfl.emul_nmod, nfl.emul, st));
+        HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, NR - r0, Nc, h, B.nb, gs, nfl.emul_nmod, nfl.emul, st));
         launch_leaf128(B.A, (size_t)r0 * ld + r0, ld, B.W, (size_t)(r0 / 64) * 4096, W2, (size_t)(r0 / 128) * 16384, r0, n_real, B.info, B.nb, st);
         fused = false;
       } else
@@ -912,16 +959,15 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
     for (int j = 0; j < B.nb; ++j) nfl.S.p[j] = sb + per_s * j;
   }
   // Scratch of the emulated updates: sized for the widest emulated level of this factorisation and reused by every level; the batch
-  // goes through it in groups of G matrices (at most ~12 GB).  ONE block per stream per API call (g.emul_blocks): the batches a stream
+  // goes through it in groups (emul_block_plan: at most ~12 GB; emul_group: per update).  ONE block per stream per API call (g.emul_blocks): the batches a stream
   // factors one after the other share it (stream order keeps them apart), so an API call holds at most one block per stream it uses
   // however many batches it has -- plus the smaller ones a stream outgrew, if its batches differ in shape.  If a block cannot be
   // had the f64 path runs, for the rest of the call (said once per process on stderr).
   emul_switches();
   if (g_emul_on && !g.emul_denied) {
-    const size_t one = emul_need(NR, 0, NC, g_emul_mink, 1, g_emul_nmod);
-    if (one > 0) {
-      const int G = (int)std::max<size_t>(1, std::min<size_t>(std::min(4, B.nb), (size_t)12e9 / one));
-      const size_t bytes = emul_need(NR, 0, NC, g_emul_mink, G, g_emul_nmod);
+    const EmulBlockPlan plan = emul_block_plan(NR, NC, B.nb, g_emul_nmod);
+    if (plan.bytes > 0) {
+      const size_t bytes = plan.bytes;
       auto it = g.emul_blocks.find(st);
       void* blk = (it != g.emul_blocks.end() && it->second.bytes >= bytes) ? it->second.p : nullptr;
       if (blk == nullptr) {
@@ -933,7 +979,7 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
           if (!said) { said = true; fprintf(stderr, "lmm: no %zu-byte scratch for the int8-emulated updates: they run on the f64 kernel\n", bytes); }
         }
       }
-      if (blk != nullptr) { nfl.emul = blk; nfl.emul_bytes = bytes; nfl.emul_G = G; nfl.emul_mink = g_emul_mink; nfl.emul_nmod = g_emul_nmod; }
+      if (blk != nullptr) { nfl.emul = blk; nfl.emul_plan = plan; nfl.emul_nmod = g_emul_nmod; }
     }
   }
   potrf_rec_panel(B, W2, flags, nfl, ld, NR, 0, NC, n_real, st, false);
@@ -1039,9 +1085,11 @@ void batch_plan(int ms, int* nb_per, int* nstreams_used, double bytes_per_latent
       for (const auto& kv : g.pool) avail += (double)kv.first;
       const double budget = 0.8 * avail;
       // + one scratch block of the emulated updates per stream (potrf_batch: at most ~12 GB each), for working sets whose matrices
-      // are large enough to have an emulated level (n >= 2 LMM_F64_EMUL_MINK)
+      // have an emulated level at the batch size the plan starts from (emul_need: the question potrf_batch asks; the shape is the
+      // square one of this working set, n = sqrt(bytes / 8) rounded up to whole panels, with one 64-row block of riders)
       emul_switches();
-      const double per_stream = (g_emul_on && !g_f32 && bytes_per_latent >= 32.0 * g_emul_mink * g_emul_mink) ? 12e9 : 0.0;
+      const int nce = (int)rup((size_t)std::sqrt(bytes_per_latent / 8.0), 128);
+      const double per_stream = (g_emul_on && !g_f32 && emul_need(nce + 64, nce, b, 1, g_emul_nmod) > 0) ? 12e9 : 0.0;
       while ((double)b * ns * bytes_per_latent + ns * per_stream > budget && (b > 1 || ns > 1)) {
         if (b > 1) b = (b + 1) / 2; else --ns;
         nbatches = (ms + b - 1) / b;
@@ -5717,6 +5765,45 @@ int lmm_dev_set_f64_emul(int on, int min_k, int nmod) {
   if (min_k < 128 || nmod < LMM_EMUL_MINMOD || nmod > LMM_EMUL_MAXMOD) return fail(LMM_ERR_ARG, "lmm_dev_set_f64_emul: min_k >= 128, %d <= nmod <= %d", LMM_EMUL_MINMOD, LMM_EMUL_MAXMOD);
   g_emul_on = on ? 1 : 0; g_emul_mink = min_k; g_emul_nmod = nmod;
   return LMM_OK;
+}
+// Test hook of the shape rule that decides when nothing explicit is set (emul_pays): updates with K >= min_k_always are emulated, those
+// with min_k_shape <= K < min_k_always when nb * outputs >= min_outputs; min_k_always < 0 goes back to the defaults.
+int lmm_dev_set_f64_emul_rule(int min_k_always, int min_k_shape, double min_outputs) {
+  g.err.clear();
+  if (min_k_always < 0) { g_rule_always = kRuleAlways; g_rule_shape = kRuleShape; g_rule_outs = kRuleOuts; return LMM_OK; }
+  if (min_k_shape < 128 || min_k_always < min_k_shape || !(min_outputs >= 0.0)) return fail(LMM_ERR_ARG, "lmm_dev_set_f64_emul_rule: 128 <= min_k_shape <= min_k_always, min_outputs >= 0");
+  g_rule_always = min_k_always; g_rule_shape = min_k_shape; g_rule_outs = min_outputs;
+  return LMM_OK;
+}
+// Test hook: at most g matrices per group of an emulated update (0: as many as the scratch block holds).  Results do not depend on it.
+int lmm_dev_set_emul_group(int gcap) {
+  g.err.clear();
+  if (gcap < 0) return fail(LMM_ERR_ARG, "lmm_dev_set_emul_group: g >= 0");
+  g_emul_group_cap = gcap;
+  return LMM_OK;
+}
+// Host-only (no GPU, no lmm_init needed): what potrf_batch would do with nb matrices of NR rows and NC columns -- the same walk, the
+// same predicate, the same sizing.  out[0] = bytes of the scratch block it asks for (0: nothing is emulated), out[1] = the G that block
+// is sized for; then 6 words per trailing update with at least 128 columns, in launch order: M, N, K, emulated (0 / 1), matrices per
+// group, scratch bytes at that group size (0, 0 when not emulated).  Returns the number of updates (records beyond cap are counted,
+// not written), or -LMM_ERR_ARG.
+int lmm_dev_emul_plan(int NR, int NC, int nb, long long* out, int cap) {
+  g.err.clear();
+  if (!out || cap < 0 || nb < 1 || nb > LMM_MAX_BATCH || NC < 128 || (NC % 64) != 0 || NR < NC) return -fail(LMM_ERR_ARG, "lmm_dev_emul_plan: bad arguments");
+  emul_switches();
+  const EmulBlockPlan P = g_emul_on ? emul_block_plan(NR, NC, nb, g_emul_nmod) : EmulBlockPlan{};
+  out[0] = (long long)P.bytes; out[1] = P.G;
+  int count = 0;
+  emul_walk(NR, 0, NC, [&](int M, int N, int K) {
+    if (count < cap) {
+      long long* r = out + 2 + 6 * (size_t)count;
+      const bool em = P.bytes > 0 && emul_takes(M, N, K, nb);
+      const int gs = em ? emul_group(M, N, K, nb, P, g_emul_nmod) : 0;
+      r[0] = M; r[1] = N; r[2] = K; r[3] = em; r[4] = gs; r[5] = em ? (long long)emul_scratch_bytes(M, N, K, gs, g_emul_nmod) : 0;
+    }
+    ++count;
+  });
+  return count;
 }
 // Test hook: at most wgs workgroups in the persistent grid of the emulation's GEMM (0: the default, one per CU), so that a small shape
 // makes one workgroup walk several tiles.

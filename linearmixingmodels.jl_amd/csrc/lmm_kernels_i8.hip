@@ -18,6 +18,7 @@
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 constexpr int TILE = 256, BK = 128;
 constexpr int STAGE_BYTES = 2 * TILE * BK;      // A tile + B tile of one K step
@@ -123,6 +124,22 @@ __device__ __forceinline__ void glds16(const int8_t* src, int8_t* lds_wave_base)
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
+// 4 x 4 transpose of w[0..3] over the lanes c, c + 16, c + 32, c + 48 (the four 16-lane rows of a wave), for every c: afterwards w[k]
+// of row g is what w[g] of row k was.  Two rounds of 2 x 2 block swaps: v_permlane32_swap_b32 exchanges rows 2, 3 of its first operand
+// with rows 0, 1 of its second, v_permlane16_swap_b32 the odd rows of the first with the even rows of the second.  All 64 lanes
+// must be active.
+__device__ __forceinline__ void emul_transpose4(unsigned (&w)[4]) {
+  typedef unsigned v2u __attribute__((ext_vector_type(2)));
+  v2u s = __builtin_amdgcn_permlane32_swap(w[0], w[2], false, false);
+  w[0] = s[0]; w[2] = s[1];
+  s = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
+  w[1] = s[0]; w[3] = s[1];
+  s = __builtin_amdgcn_permlane16_swap(w[0], w[1], false, false);
+  w[0] = s[0]; w[1] = s[1];
+  s = __builtin_amdgcn_permlane16_swap(w[2], w[3], false, false);
+  w[2] = s[0]; w[3] = s[1];
+}
+
 // One batch item = one (matrix, modulus): U[item][j][i] = (sum_k R[item][i][k] R[item][j][k]) mod p, i contiguous.
 //   workgroup tile 256 x 256 x 128, 8 waves as 2 (M) x 4 (N), v_mfma_i32_16x16x64_i8 (wave tile 128 x 64 = 8 x 4 accumulators);
 //   two LDS stages of 64 KiB filled by global_load_lds_dwordx4 (stage s + 1 in flight while stage s is multiplied);
@@ -162,7 +179,7 @@ __device__ __forceinline__ void glds16(const int8_t* src, int8_t* lds_wave_base)
 //   of that buffer (phase 3) complete.  Neither argument looks at which tile a stage belongs to: stages s, s + 1, s + 2 may lie in
 //   one, two or three tiles, and the epilogue touches no LDS and stands after phase 4 of a stage and before phase 1 of the next,
 //   where the schedule has no LDS ordering to keep.  One stage is in flight at a time, so the wait is vmcnt(0); it waits for loads
-//   that are one K step (64 MFMAs per wave) old, and after a tile boundary also for the epilogue's 32 stores per lane, as old.
+//   that are one K step (64 MFMAs per wave) old, and after a tile boundary also for the epilogue's 8 stores per lane, as old.
 //   The prologue (once per workgroup) stages 0, waits, and stages 1 if the walk has a second stage at all.
 __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
                                                            int nids, int Mp, int Np, int K, EmulConst c) {
@@ -266,22 +283,32 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
       }
       EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
     }
-    // epilogue of work id `id`: reduce mod p (emul_acc_residue: |acc| <= K 128^2 <= 2^28), pack the 4 consecutive rows a lane holds
-    // into one dword of U[j][i], and clear the accumulators for the next tile
+    // epilogue of work id `id`: reduce mod p (emul_acc_residue: |acc| <= K 128^2 <= 2^28) and pack the 4 consecutive rows a lane holds of
+    // a 16 x 16 block into one dword.  C/D map of 16x16: column = lane & 15, rows = 4 (lane >> 4) + e, so the dword of row fragment m
+    // in lane (c, g) is rows 16 m + 4 g .. + 3 of column c, and storing it as it is makes a wave store 16 pieces of 16 bytes in 16
+    // lines (the columns of U are Mp bytes apart).  Instead the four row groups of a column exchange the dwords of row fragments
+    // 4 q .. 4 q + 3 (emul_transpose4: registers only), after which lane (c, g) holds rows 16 (4 q + g) .. + 15 of its column: one
+    // 16-byte store per lane, 16 columns x 64 contiguous bytes per wave store, 8 stores per lane and tile instead of 32.  The
+    // accumulators are cleared for the next tile.
     const int cf = emul_fold_const(p);
     const float pf = (float)p, rp = 1.0f / pf;
     int8_t* Ub = U + (size_t)item * Np * Mp;
 #pragma unroll
-    for (int m = 0; m < 8; ++m)
+    for (int q = 0; q < 2; ++q)
 #pragma unroll
       for (int nn = 0; nn < 4; ++nn) {
-        const size_t j = (size_t)t.y * TILE + wc * 64 + nn * 16 + frow;      // C/D map of 16x16: column = lane & 15, row = 4 (lane >> 4) + e
-        const int i = t.x * TILE + wr * 128 + m * 16 + 4 * fk;
-        unsigned w = 0;
+        unsigned w[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) w |= emul_acc_residue(acc[m][nn][e], cf, pf, rp) << (8 * e);
-        *reinterpret_cast<unsigned*>(Ub + j * Mp + i) = w;
-        acc[m][nn] = (v4i){0, 0, 0, 0};
+        for (int k = 0; k < 4; ++k) {
+          w[k] = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) w[k] |= emul_acc_residue(acc[4 * q + k][nn][e], cf, pf, rp) << (8 * e);
+          acc[4 * q + k][nn] = (v4i){0, 0, 0, 0};
+        }
+        emul_transpose4(w);
+        const size_t j = (size_t)t.y * TILE + wc * 64 + nn * 16 + frow;
+        const int i = t.x * TILE + wr * 128 + (4 * q + fk) * 16;
+        *reinterpret_cast<v4u*>(Ub + j * Mp + i) = (v4u){w[0], w[1], w[2], w[3]};
       }
   }
 #undef EMUL_MMA8

@@ -1,37 +1,106 @@
 """Per-level kernel times of the int8-emulated updates from a rocprofv3 kernel trace (CSV) of ONE batch on ONE stream
 (`LMM_F64_EMUL_MINK=1024 rocprofv3 --kernel-trace -f csv -- python bench.py --full --steps 0 --no-cpu-baseline`).
 
-    python tools/emul_level_times.py TRACE_kernel_trace.csv
+    python tools/emul_level_times.py TRACE_kernel_trace.csv [--f64 NR NC]
 
 A level is recognised by the K of the emul_rowmax_kernel launch that opens every update (grid y = K / 64); the three kernels after
-it belong to the same update.  Prints ms summed over the launches of a level, per kernel, and the totals of every other kernel."""
+it belong to the same update.  Prints ms summed over the launches of a level, per kernel, and the totals of every other kernel.
+
+Then one line per emulated UPDATE, in launch order: an update is a maximal run of emulation kernels and the fills between them
+(two emulated updates are never neighbours: the factorisation of the columns between them lies in between).  Its key is (K, Mp,
+nb): Mp = the rows padded to the GEMM tile (convert's grid), nb = the matrices of all its groups.  `span` is first start to last end,
+the leaf128_kernel launch that follows an emulated update included (the f64 update runs that leaf inside its own launch).
+
+--f64 NR NC: the trace is of the f64 path (LMM_F64_EMUL=0) of matrices with NR rows and NC columns; the potrf_node_kernel<2>
+launches (the updates with K >= 1024) are named by walking the factorisation's recursion, evaluation after evaluation."""
 import collections
 import csv
 import sys
 
+EMUL = ("emul_rowmax", "emul_convert", "emul_gemm", "emul_combine")
 
-def main(path):
+
+def grid(r, ax):
+    return int(r["Grid_Size_" + ax]) // max(1, int(r["Workgroup_Size_" + ax]))
+
+
+def split(w):
+    return (w // 2 + 127) // 128 * 128 if w >= 256 else (128 if w == 192 else 64)
+
+
+def updates(NR, j0, w, out):
+    """(M, N, K) of the trailing updates with N >= 128 of the columns [j0, j0 + w), in launch order"""
+    if w < 256:
+        return
+    h = split(w)
+    updates(NR, j0, h, out)
+    if w - h >= 128:
+        out.append((NR - j0 - h, w - h, h))
+    updates(NR, j0 + h, w - h, out)
+
+
+def main(argv):
+    path = argv[0]
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     per = collections.defaultdict(lambda: collections.defaultdict(float))
     other = collections.defaultdict(float)
     K = None
+    runs, cur = [], None
     for r in rows:
         name = r["Kernel_Name"]
-        ms = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-6
-        hit = next((k for k in ("emul_rowmax", "emul_convert", "emul_gemm", "emul_combine") if k + "_kernel" in name), None)
+        t0, t1 = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
+        ms = (t1 - t0) * 1e-6
+        hit = next((k for k in EMUL if k + "_kernel" in name), None)
         if hit is None:
             other[name.split("(")[0][:60]] += ms
+            if cur is not None and "fillBuffer" in name:
+                cur["fill"] += ms
+                continue
+            if cur is not None:
+                if "leaf128_kernel" in name:
+                    cur["leaf"] = ms
+                    cur["t1"] = t1
+                runs.append(cur)
+                cur = None
             continue
         if hit == "emul_rowmax":
-            K = 64 * int(r["Grid_Size_Y"]) // int(r["Workgroup_Size_Y"])
+            K = 64 * grid(r, "Y")
         per[hit][K] += ms
+        if cur is None:
+            cur = collections.defaultdict(float, t0=t0, K=K, nb=0, groups=0)
+        if hit == "emul_rowmax":
+            cur["nb"] += grid(r, "Z")
+            cur["groups"] += 1
+        if hit == "emul_convert":
+            cur["Mp"] = 16 * grid(r, "X")
+        cur[hit] += ms
+        cur["t1"] = t1
+    if cur is not None:
+        runs.append(cur)
     levels = sorted({k for d in per.values() for k in d})
-    for kern in ("emul_rowmax", "emul_convert", "emul_gemm", "emul_combine"):
+    for kern in EMUL:
         print(f"{kern}: " + str({k: round(per[kern][k], 2) for k in levels}))
     print("emulated total: " + str({k: round(sum(per[kern][k] for kern in per), 2) for k in levels}))
     print("other kernels ms: " + str({k: round(v, 2) for k, v in sorted(other.items(), key=lambda kv: -kv[1])[:10]}))
+    if runs:
+        print("emulated updates in launch order: K Mp nb groups | rowmax convert gemm combine fill leaf | kernel sum, span (ms)")
+    for u in runs:
+        tot = sum(u[k] for k in EMUL) + u["fill"] + u["leaf"]
+        print(f"  K={u['K']:5d} Mp={int(u['Mp']):5d} nb={u['nb']:2d} groups={u['groups']:2d} | " + " ".join(f"{u[k]:7.3f}" for k in EMUL)
+              + f" {u['fill']:6.3f} {u['leaf']:6.3f} | {tot:8.3f} {(u['t1'] - u['t0']) * 1e-6:8.3f}")
+    if "--f64" in argv:
+        NR, NC = int(argv[argv.index("--f64") + 1]), int(argv[argv.index("--f64") + 2])
+        seq = []
+        updates(NR, 0, NC, seq)
+        seq = [u for u in seq if u[2] >= 1024]
+        node = [r for r in rows if "potrf_node_kernel<2" in r["Kernel_Name"]]
+        print(f"f64 updates with K >= 1024 ({len(seq)} per evaluation), in launch order: evaluation M N K | grid | ms")
+        for i, r in enumerate(node):
+            M, N, Kk = seq[i % len(seq)]
+            ms = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-6
+            print(f"  eval={i // len(seq):2d} M={M:5d} N={N:5d} K={Kk:5d} | {grid(r, 'X')} x {grid(r, 'Y')} x {grid(r, 'Z')} | {ms:8.3f}")
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(sys.argv[1:])

@@ -274,8 +274,25 @@ __device__ __forceinline__ unsigned acc_residue(int x, int c, float pf, float rp
   return __float_as_uint(fmaf(-q, pf, ym)) & 0xFFu;
 }
 
+// 4 x 4 transpose of w[0..3] over the lanes c, c + 16, c + 32, c + 48, for every c (the library's emul_transpose4): afterwards w[k] of
+// row g is what w[g] of row k was.  v_permlane32_swap_b32 exchanges rows 2, 3 of its first operand with rows 0, 1 of its second,
+// v_permlane16_swap_b32 the odd rows of the first with the even rows of the second.
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void transpose4(unsigned (&w)[4]) {
+  typedef unsigned v2u __attribute__((ext_vector_type(2)));
+  v2u s = __builtin_amdgcn_permlane32_swap(w[0], w[2], false, false);
+  w[0] = s[0]; w[2] = s[1];
+  s = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
+  w[1] = s[0]; w[3] = s[1];
+  s = __builtin_amdgcn_permlane16_swap(w[0], w[1], false, false);
+  w[0] = s[0]; w[1] = s[1];
+  s = __builtin_amdgcn_permlane16_swap(w[2], w[3], false, false);
+  w[2] = s[0]; w[3] = s[1];
+}
+
 // The library's emul_gemm_kernel (lmm_kernels_i8.hip) as it stands now: i8_syrk_mod_kernel_pf above with a persistent grid, the K steps
-// of consecutive tiles as one stream of stages, and the fold reduction in the epilogue; i8_syrk_mod_kernel_pf stays as the baseline.
+// of consecutive tiles as one stream of stages, and the fold reduction in the epilogue (EPI 3: with 16-byte stores, the library's; EPI 0:
+// with dword stores, the library's before); i8_syrk_mod_kernel_pf stays as the baseline.
 // Persistent: the grid is min(work ids, CUs) workgroups (launch_ps takes the cap), a work id = an (item, tile) pair in the
 // order item-major, tile list inside.  Blocks b and b + 8 share an XCD: XCD b & 7 owns a contiguous range of ids and its w workgroups
 // walk it from (b >> 3) with stride w, so at any moment the workgroups of an XCD sit on w consecutive ids, one supertile.  The walk
@@ -415,26 +432,48 @@ __global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_ps(const int8_t* __
       EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
     }
     // epilogue of work id `id`: reduce mod p (|acc| <= K 128^2 <= 2^28), pack the 4 consecutive rows a lane holds into one dword of
-    // U[j][i], and clear the accumulators for the next tile.  EPI 0: the fold reduction (the library's), 1: the low byte as it is
-    // (wrong but for p = 256: the floor of any epilogue), 2: the two-correction reduction of the kernel before
+    // U[j][i], and clear the accumulators for the next tile.  EPI 0: the fold reduction with one dword store per 16 x 16 block (the
+    // library's before the 16-byte stores), 1: the low byte as it is (wrong but for p = 256: the floor of any epilogue), 2: the
+    // two-correction reduction of the kernel before, 3: the fold reduction, the dwords of four row fragments transposed over the four
+    // row groups of a column (transpose4) and stored as one 16-byte piece per lane (the library's)
     const int cf = fold_const(p), lo = -(p / 2);
     const float pf = (float)p, rp = 1.0f / pf;
     int8_t* Ub = U + (size_t)item * Np * Mp;
+    if (EPI == 3) {
 #pragma unroll
-    for (int m = 0; m < 8; ++m)
+      for (int q = 0; q < 2; ++q)
 #pragma unroll
-      for (int nn = 0; nn < 4; ++nn) {
-        const size_t j = (size_t)t.y * TILE + wc * 64 + nn * 16 + frow;      // C/D map of 16x16: column = lane & 15, row = 4 (lane >> 4) + e
-        const int i = t.x * TILE + wr * 128 + m * 16 + 4 * fk;
-        unsigned w = 0;
+        for (int nn = 0; nn < 4; ++nn) {
+          unsigned w[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int x = acc[m][nn][e];
-          w |= (EPI == 0 ? acc_residue(x, cf, pf, rp) : EPI == 1 ? (unsigned)x & 0xFFu : (unsigned)(mod_sym24(x, p, rp, lo) & 0xFF)) << (8 * e);
+          for (int k = 0; k < 4; ++k) {
+            w[k] = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[k] |= acc_residue(acc[4 * q + k][nn][e], cf, pf, rp) << (8 * e);
+            acc[4 * q + k][nn] = (v4i){0, 0, 0, 0};
+          }
+          transpose4(w);
+          const size_t j = (size_t)t.y * TILE + wc * 64 + nn * 16 + frow;
+          const int i = t.x * TILE + wr * 128 + (4 * q + fk) * 16;
+          *reinterpret_cast<v4u*>(Ub + j * Mp + i) = (v4u){w[0], w[1], w[2], w[3]};
         }
-        *reinterpret_cast<unsigned*>(Ub + j * Mp + i) = w;
-        acc[m][nn] = (v4i){0, 0, 0, 0};
-      }
+    } else {
+#pragma unroll
+      for (int m = 0; m < 8; ++m)
+#pragma unroll
+        for (int nn = 0; nn < 4; ++nn) {
+          const size_t j = (size_t)t.y * TILE + wc * 64 + nn * 16 + frow;      // C/D map of 16x16: column = lane & 15, row = 4 (lane >> 4) + e
+          const int i = t.x * TILE + wr * 128 + m * 16 + 4 * fk;
+          unsigned w = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int x = acc[m][nn][e];
+            w |= (EPI == 0 ? acc_residue(x, cf, pf, rp) : EPI == 1 ? (unsigned)x & 0xFFu : (unsigned)(mod_sym24(x, p, rp, lo) & 0xFF)) << (8 * e);
+          }
+          *reinterpret_cast<unsigned*>(Ub + j * Mp + i) = w;
+          acc[m][nn] = (v4i){0, 0, 0, 0};
+        }
+    }
   }
 #undef EMUL_MMA8
 #undef EMUL_PIN
@@ -550,12 +589,13 @@ static long check(const int8_t* dR, const int8_t* dU, int M, int N, int K, int b
 
 int main(int argc, char** argv) {
   const int nmat = argc > 1 ? atoi(argv[1]) : 1;
+  const bool brief = argc > 2;      // any second argument: the exact checks and one round of the older kernels only
   const int batch = NMOD * nmat;
   hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
   long bad = 0;
   { int dev = 0; CHECK(hipGetDevice(&dev)); CHECK(hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev)); }
 
-  {  // 1. bare v_mfma_i32_32x32x32_i8 issue rate and the clock held
+  if (!brief) {  // 1. bare v_mfma_i32_32x32x32_i8 issue rate and the clock held
     int* out; unsigned long long* st;
     for (int blocks : {256, 512}) {
       const int iters = 200000;
@@ -611,6 +651,10 @@ int main(int argc, char** argv) {
         launch_ps<false, 2>(R, U, dt, (int)tl.size(), M, N, Kp, nb, wgs, nullptr);      // the old reduction gives the same bytes
         CHECK(hipDeviceSynchronize());
         bad += check(R, U, M, N, Kp, nb, true, "persistent, old epilogue");
+        CHECK(hipMemset(U, 0x5A, (size_t)NMOD * N * M));
+        launch_ps<false, 3>(R, U, dt, (int)tl.size(), M, N, Kp, nb, wgs, nullptr);      // ... and so do the 16-byte stores
+        CHECK(hipDeviceSynchronize());
+        bad += check(R, U, M, N, Kp, nb, true, "persistent, 16-byte stores");
       }
     CHECK(hipFree(R)); CHECK(hipFree(U)); CHECK(hipFree(dt));
     fflush(stdout);
@@ -634,7 +678,7 @@ int main(int argc, char** argv) {
     const double useful = 2.0 * s.K * outs * batch, issued = 2.0 * s.K * (double)TILE * TILE * nt * batch;
     const int reps = (int)std::max(4.0, 0.15 / (issued / 2.0e15));  // about 150 ms per window at 2 POPS
     std::vector<float> t32, t16, tpf;
-    for (int round = 0; round < 3; ++round)
+    for (int round = 0; round < (brief ? 1 : 3); ++round)
       for (int v = 0; v < 3; ++v) {
         auto go = [&]() {
           if (v == 0) launch<32, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
@@ -659,6 +703,7 @@ int main(int argc, char** argv) {
       std::sort(c.begin(), c.end());
       clk[v] = c[c.size() / 2];
     }
+    if (brief) for (std::vector<float>* tvp : {&t32, &t16, &tpf}) tvp->resize(2, (*tvp)[0]);
     std::sort(t32.begin(), t32.end()); std::sort(t16.begin(), t16.end()); std::sort(tpf.begin(), tpf.end());
     printf("i8 syrk M=%5d N=%5d K=%5d batch=%d (%d tiles, %d reps) | 32x32x32: min %.3f med %.3f ms, %.0f TOPS useful (%.0f issued), clock %.0f MHz"
            " | 16x16x64: min %.3f med %.3f ms, %.0f TOPS useful (%.0f issued), clock %.0f MHz\n",
@@ -668,14 +713,15 @@ int main(int argc, char** argv) {
            " | baseline 16x16x64 / prefetch: medians %.3f\n", tpf[0], tpf[1], useful / tpf[0] / 1e9, issued / tpf[0] / 1e9, clk[2], t16[1] / tpf[1]);
     {  // the persistent kernel and the split of the per-tile fixed cost: grid (one workgroup per tile / per CU) x epilogue (fold
        // reduction / low byte only / the prefetch kernel's), interleaved with the prefetch kernel in every round
-      const char* names[7] = {"prefetch (before)", "per tile, fold", "per tile, low byte", "persistent, old epilogue", "persistent, fold (the library's kernel)",
-                              "persistent, low byte", "prefetch (before), again"};
-      std::vector<float> tv[7];
+      const char* names[8] = {"prefetch (before)", "per tile, fold", "per tile, low byte", "persistent, old epilogue", "persistent, fold, dword stores (before)",
+                              "persistent, low byte", "prefetch (before), again", "persistent, fold, 16-byte stores (library)"};
+      std::vector<float> tv[8];
       const int nids = nt * batch;
       for (int round = 0; round < 3; ++round)
-        for (int v = 0; v < 7; ++v) {
+        for (int v = 0; v < 8; ++v) {
           auto go = [&]() {
             switch (v) {
+              case 7: launch_ps<false, 3>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr); break;
               case 1: launch_ps<false, 0>(R, U, dt, nt, s.M, s.N, s.K, batch, nids, nullptr); break;
               case 2: launch_ps<false, 1>(R, U, dt, nt, s.M, s.N, s.K, batch, nids, nullptr); break;
               case 3: launch_ps<false, 2>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr); break;
@@ -700,14 +746,15 @@ int main(int argc, char** argv) {
       for (int w = 0; w < g; ++w) cl.push_back((double)h[2 * w] / (double)h[2 * w + 1] * 100.0);
       std::sort(cl.begin(), cl.end());
       const double tiles_per_cu = (double)nids / g_cus;
-      for (int v = 0; v < 7; ++v) {
+      for (int v = 0; v < 8; ++v) {
         std::sort(tv[v].begin(), tv[v].end());
         printf("    %-42s min %.3f med %.3f max %.3f ms, %.0f TOPS useful, %.2f us per tile and CU\n", names[v], tv[v][0], tv[v][1], tv[v][2], useful / tv[v][1] / 1e9,
                tv[v][1] * 1e3 / tiles_per_cu);
       }
-      printf("    persistent kernel's clock %.0f MHz; before / persistent medians %.3f\n", cl[cl.size() / 2], tv[0][1] / tv[4][1]);
+      printf("    persistent kernel's clock %.0f MHz; before / persistent medians %.3f; dword / 16-byte stores medians %.3f\n", cl[cl.size() / 2], tv[0][1] / tv[7][1],
+             tv[4][1] / tv[7][1]);
       CHECK(hipMemset(U, 0x5A, ub));
-      launch_ps<false, 0>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr);
+      launch_ps<false, 3>(R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr);
       CHECK(hipDeviceSynchronize());
       bad += check(R, U, s.M, s.N, s.K, batch, false, "persistent sampled");
     }
