@@ -4,8 +4,8 @@
 //      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows;
 //   2. emul_gemm_kernel: one int8 SYRK-shaped GEMM per (matrix, modulus) on 256 x 256 tiles of the lower trapezoid, int32
 //      accumulators, reduced mod p to one byte per output, as a persistent kernel (tools/i8_gemm_probe.hip holds a copy,
-//      i8_syrk_mod_kernel_ps, beside the kernels this one replaced; the probe stands alone: a change here has to be made there too
-//      before its numbers speak for this kernel);
+//      i8_syrk_mod_kernel_ps with ABL = 6, beside the loops and kernels this one replaced; the probe stands alone: a change here
+//      has to be made there too before its numbers speak for this kernel);
 //   3. emul_combine_kernel: CRT reconstruction in Float64 (lmm_emul.h) and C_ij -= X 2^(e_i + e_j - 2b) for i >= j.
 // Integer sums are exact in any order: the result is bitwise reproducible.
 #include "lmm_internal.h"
@@ -154,32 +154,45 @@ __device__ __forceinline__ void emul_transpose4(unsigned (&w)[4]) {
 // is static: no workgroup waits for, or reads anything written by, another one.
 //
 // The K steps of the tiles a workgroup walks form ONE stream of stages s = 0, 1, 2, ..; stage s lives in buffer s & 1 (not kt & 1:
-// nk may be odd).  A staging cursor (tile base pointers, k offset) runs two stages ahead of the MFMAs and steps into the next work
-// id when it has issued a tile's last K step, so the last two K steps of a tile stage the first two of the next one (with nk = 1
-// the cursor is two TILES ahead), and between the last MFMA of a tile and the first of the next only the epilogue stands, with the
-// next tile's loads and its first fragment reads issued above it.
+// nk may be odd).  A buffer is two halves of 32 KiB, the A tile and the B tile of the stage, which are restaged separately.  A staging
+// cursor (tile base pointers, k offset) runs two stages ahead of the MFMAs and steps into the next work id when it has issued a
+// tile's last K step, so the last two K steps of a tile stage the first two of the next one (with nk = 1 the cursor is two TILES
+// ahead), and between the last MFMA of a tile and the first of the next only the epilogue stands, with the next tile's loads and
+// its first fragment reads issued above it.
 //
 // One K step is four phases of 16 MFMAs, (ks, mh) = the 64-byte half of the k range x the upper / lower 4 of the wave's 8 row
 // fragments.  The fragments of a phase are read into registers in the MIDDLE of the phase before it, between its two groups of 8
 // MFMAs, so they are 8 MFMAs old when the wait before their first use comes (the compiler waits with lgkmcnt(0) there, so reads
 // issued right before that wait would be waited for too).  sched_barrier(0) pins that order: left alone, the scheduler sinks the
-// reads down to their uses.  The one barrier of a K step stands between phases 3 and 4.
+// reads down to their uses.  A wave's 8 pieces of a stage (global_load_lds_dwordx4, 8 rows x 128 B each: whole 128-byte lines) are
+// issued one after each group of 4 MFMAs, never as a burst in front of them.  A K step has two barriers, both s_barrier with a
+// hand-written s_waitcnt (__syncthreads() would wait for vmcnt(0)): X after phase 2, Y after phase 3.
 //
 //   phase of stage s | MFMAs use (registers)        | ds_reads issued (buffer)                 | global_load_lds issued
 //   1 (ks 0, mh 0)   | a[0..3], b[0..3]   of s      | a[4..7] ks 0 of s  (s & 1)               |
-//   2 (ks 0, mh 1)   | a[4..7], b[0..3]   of s      | a[0..3], b[0..3] ks 1 of s  (s & 1)      |
-//   3 (ks 1, mh 0)   | a[0..3]', b[0..3]' of s      | a[4..7] ks 1 of s  (s & 1): the LAST read of buffer s & 1
-//   -- s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier: every wave holds all its fragments of stage s in registers, and every wave's
-//      loads of stage s + 1 (issued one whole K step earlier, at this point of stage s - 1) have landed in buffer (s + 1) & 1 --
-//   4 (ks 1, mh 1)   | a[4..7]', b[0..3]' of s      | a[0..3], b[0..3] ks 0 of s + 1 ((s+1)&1) | stage s + 2 into buffer s & 1
+//   2 (ks 0, mh 1)   | a[4..7], b[0..3]   of s      | a[0..3], b[0..3] ks 1 of s  (s & 1): the LAST read of the B half of buffer s & 1
+//   -- X: s_waitcnt lgkmcnt(0); s_barrier: every wave holds all its B fragments of stage s in registers --
+//   3 (ks 1, mh 0)   | a[0..3]', b[0..3]' of s      | a[4..7] ks 1 of s  (s & 1): the LAST read | B tile of stage s + 2 into the B half of
+//                                                     of the A half of buffer s & 1              buffer s & 1 (4 pieces)
+//   -- Y: s_waitcnt lgkmcnt(0) vmcnt(4); s_barrier: every wave holds all its fragments of stage s in registers, and every wave's
+//      loads of stage s + 1 have landed in buffer (s + 1) & 1; the 4 pieces of phase 3 may still be in flight --
+//   4 (ks 1, mh 1)   | a[4..7]', b[0..3]' of s      | a[0..3], b[0..3] ks 0 of s + 1 ((s+1)&1) | A tile of stage s + 2 into the A half of
+//                                                                                                buffer s & 1 (4 pieces)
 //   -- after the last stage of a tile: the epilogue of that tile (registers and global stores only) --
 //
-//   read after write: buffer (s + 1) & 1 is first read in phase 4 of stage s, after the wait-plus-barrier that retires stage s + 1.
-//   write after read: buffer s & 1 is restaged in phase 4 of stage s, after the barrier every wave reaches only with its last reads
-//   of that buffer (phase 3) complete.  Neither argument looks at which tile a stage belongs to: stages s, s + 1, s + 2 may lie in
-//   one, two or three tiles, and the epilogue touches no LDS and stands after phase 4 of a stage and before phase 1 of the next,
-//   where the schedule has no LDS ordering to keep.  One stage is in flight at a time, so the wait is vmcnt(0); it waits for loads
-//   that are one K step (64 MFMAs per wave) old, and after a tile boundary also for the epilogue's 8 stores per lane, as old.
+//   read after write: buffer (s + 1) & 1 is first read in phase 4 of stage s, after Y of stage s.  A wave issues its loads in the
+//   order B(s + 1) [phase 3 of s - 1], A(s + 1) [phase 4 of s - 1], B(s + 2) [phase 3 of s] and they retire in that order, so
+//   at most 4 outstanding at Y means that its pieces of stage s + 1 have landed, and the barrier makes that true of all eight waves
+//   before any of them reads.  The pieces in flight across Y go to buffer s & 1, which nobody reads before Y of stage s + 1.
+//   write after read: the B half of buffer s & 1 is restaged in phase 3 of stage s, after X, which every wave reaches only with its
+//   last reads of that half (phase 2) complete; the A half in phase 4, after Y, which every wave reaches only with its last reads of
+//   that half (phase 3) complete.  Neither argument looks at which tile a stage belongs to: stages s, s + 1, s + 2 may lie in one,
+//   two or three tiles, and the epilogue touches no LDS and stands after phase 4 of a stage and before phase 1 of the next, where
+//   the schedule has no LDS ordering to keep.
+//   The count: when the cursor has run out (the last two stages of a walk) phase 3 issues nothing and Y waits for vmcnt(0), a
+//   uniform branch; vmcnt(4) there would not wait for the stage about to be read.  The epilogue's 8 stores per lane count in vmcnt
+//   too and nothing here relies on how stores retire relative to loads: the first Y after an epilogue waits for vmcnt(0), once per
+//   tile.  A load is 3 (A) or 4 (B) phases old when it is waited for, and Y never empties the queue inside a tile.
 //   The prologue (once per workgroup) stages 0, waits, and stages 1 if the walk has a second stage at all.
 __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
                                                            int nids, int Mp, int Np, int K, EmulConst c) {
@@ -216,17 +229,24 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
     cB = Rb + (size_t)pt.y * TILE * K;
     if (cn + 1 < cnt) cursor_peek(first + (cn + 1) * step);
   };
-  auto stage_next = [&](int buf) {      // cn < cnt
+  // piece q (0..3: A, 4..7: B) of the cursor's stage into buffer buf; the cursor moves on after piece 3, the last one issued
+  auto piece = [&](int buf, int q) {      // cn < cnt
     int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) glds16(cA + ck + roff[q], base + q * 1024);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) glds16(cB + ck + roff[q], base + TILE * BK + q * 1024);
-    ck += BK;
-    if (ck == K) {
-      ck = 0; ++cn;
-      if (cn < cnt) cursor_tile();
+    if (q < 4) glds16(cA + ck + roff[q], base + q * 1024);
+    else glds16(cB + ck + roff[q - 4], base + TILE * BK + (q - 4) * 1024);
+    if (q == 3) {
+      ck += BK;
+      if (ck == K) {
+        ck = 0; ++cn;
+        if (cn < cnt) cursor_tile();
+      }
     }
+  };
+  auto stage_next = [&](int buf) {      // cn < cnt: a whole stage at once (the prologue)
+#pragma unroll
+    for (int q = 4; q < 8; ++q) piece(buf, q);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) piece(buf, q);
   };
   const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
   // byte offset of a fragment in its stage: (row 128) + ((ks 4 + fk) ^ (row >> 1) & 7) 16 with row = 16 m + frow (+ the wave's first
@@ -251,8 +271,12 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
 #define EMUL_MMA8(A4, B4, M0, h)                                                                                                   \
   _Pragma("unroll") for (int m = 2 * (h); m < 2 * (h) + 2; ++m)                                                                    \
   _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + m][n], 0, 0, 0)
+  // 4 MFMAs: row fragment m of A4 (accumulator row M0 + m) x the 4 column fragments
+#define EMUL_MMA4(A4, B4, M0, m)                                                                                                   \
+  _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + (m)][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + (m)][n], 0, 0, 0)
 #define EMUL_PIN() __builtin_amdgcn_sched_barrier(0)
   int par = 0;      // s & 1
+  bool stored = false;      // an epilogue's stores have been issued since the last wait for vmcnt
   for (int n = 0, id = first; n < cnt; ++n, id += step) {
     // what the epilogue of this work id needs, loaded above its K loop
     const int item = id / ntiles;
@@ -269,19 +293,38 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
 #pragma unroll
       for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }
       EMUL_PIN(); EMUL_MMA8(ahi, b, 4, 1); EMUL_PIN();
-      EMUL_MMA8(alo1, b1, 0, 0); EMUL_PIN();    // phase 3
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // X
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      const bool more = cn < cnt;      // stage s + 2 exists
+      EMUL_PIN(); EMUL_MMA4(alo1, b1, 0, 0); EMUL_PIN();      // phase 3
+      if (more) piece(par, 4);
+      EMUL_PIN(); EMUL_MMA4(alo1, b1, 0, 1); EMUL_PIN();
+      if (more) piece(par, 5);
 #pragma unroll
       for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);
-      EMUL_PIN(); EMUL_MMA8(alo1, b1, 0, 1); EMUL_PIN();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (cn < cnt) stage_next(par);
-      EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
+      EMUL_PIN(); EMUL_MMA4(alo1, b1, 0, 2); EMUL_PIN();
+      if (more) piece(par, 6);
+      EMUL_PIN(); EMUL_MMA4(alo1, b1, 0, 3); EMUL_PIN();
+      if (more) piece(par, 7);
+      if (more && !stored) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");      // Y
+      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      stored = false;
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
+      if (more) piece(par, 0);
+      EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 1); EMUL_PIN();
+      if (more) piece(par, 1);
       if (kt + 1 < nk || n + 1 < cnt) {
 #pragma unroll
         for (int f = 0; f < 4; ++f) { alo[f] = frag(nxt, offA, 0, f); b[f] = frag(nxt, offB, 0, f); }
       }
-      EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
+      EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 2); EMUL_PIN();
+      if (more) piece(par, 2);
+      EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 3); EMUL_PIN();
+      if (more) piece(par, 3);
+      EMUL_PIN();
     }
     // epilogue of work id `id`: reduce mod p (emul_acc_residue: |acc| <= K 128^2 <= 2^28) and pack the 4 consecutive rows a lane holds of
     // a 16 x 16 block into one dword.  C/D map of 16x16: column = lane & 15, rows = 4 (lane >> 4) + e, so the dword of row fragment m
@@ -310,8 +353,10 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
         const int i = t.x * TILE + wr * 128 + (4 * q + fk) * 16;
         *reinterpret_cast<v4u*>(Ub + j * Mp + i) = (v4u){w[0], w[1], w[2], w[3]};
       }
+    stored = true;
   }
 #undef EMUL_MMA8
+#undef EMUL_MMA4
 #undef EMUL_PIN
 }
 

@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -290,9 +291,17 @@ __device__ __forceinline__ void transpose4(unsigned (&w)[4]) {
   w[2] = s[0]; w[3] = s[1];
 }
 
-// The library's emul_gemm_kernel (lmm_kernels_i8.hip) as it stands now: i8_syrk_mod_kernel_pf above with a persistent grid, the K steps
-// of consecutive tiles as one stream of stages, and the fold reduction in the epilogue (EPI 3: with 16-byte stores, the library's; EPI 0:
+// The library's emul_gemm_kernel (lmm_kernels_i8.hip): i8_syrk_mod_kernel_pf above with a persistent grid, the K steps of
+// consecutive tiles as one stream of stages, and the fold reduction in the epilogue (EPI 3: with 16-byte stores, the library's; EPI 0:
 // with dword stores, the library's before); i8_syrk_mod_kernel_pf stays as the baseline.
+// ABL picks the K loop.  0: the loop the library had before the half-stage staging, described below.  1 .. 4 are its ablation legs,
+// which differ from it by one thing each, compute wrong products on purpose and are timed only: 1 (a) no global_load_lds after the
+// prologue (the LDS keeps stages 0 and 1), 2 (b) no fragment reads after the prologue, 3 (c) no wait and no barrier, 4 (d) every
+// tile of an item on operand panels 0 and 1 (L2-resident).  5 (e): the 8 pieces of a stage issued 2 at a time after the first and
+// third group of 4 MFMAs of phase 4 and of the next step's phase 1, still waited for with vmcnt(0).  6 (f): THE LIBRARY'S LOOP NOW:
+// the B half of buffer s & 1 restaged in phase 3 behind a second barrier after phase 2, the A half in phase 4, one piece after each
+// group of 4 MFMAs, the wait between phases 3 and 4 vmcnt(4) (vmcnt(0) when phase 3 issued nothing and after an epilogue); the
+// phase table and the ordering argument of that loop are in lmm_kernels_i8.hip.
 // Persistent: the grid is min(work ids, CUs) workgroups (launch_ps takes the cap), a work id = an (item, tile) pair in the
 // order item-major, tile list inside.  Blocks b and b + 8 share an XCD: XCD b & 7 owns a contiguous range of ids and its w workgroups
 // walk it from (b >> 3) with stride w, so at any moment the workgroups of an XCD sit on w consecutive ids, one supertile.  The walk
@@ -326,7 +335,7 @@ __device__ __forceinline__ void transpose4(unsigned (&w)[4]) {
 //   where the schedule has no LDS ordering to keep.  One stage is in flight at a time, so the wait is vmcnt(0); it waits for loads
 //   that are one K step (64 MFMAs per wave) old, and after a tile boundary also for the epilogue's 32 stores per lane, as old.
 //   The prologue (once per workgroup) stages 0, waits, and stages 1 if the walk has a second stage at all.
-template <bool STAMP, int EPI>
+template <bool STAMP, int EPI, int ABL = 0>
 __global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_ps(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
                                                                 int nids, int Mp, int Np, int K, Moduli mod, unsigned long long* __restrict__ stamps) {
   __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
@@ -358,21 +367,37 @@ __global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_ps(const int8_t* __
   };
   auto cursor_tile = [&]() {
     const int8_t* Rb = R + (size_t)pitem * Mp * K;
-    cA = Rb + (size_t)pt.x * TILE * K;
-    cB = Rb + (size_t)pt.y * TILE * K;
+    cA = Rb + (size_t)(ABL == 4 ? 0 : pt.x) * TILE * K;
+    cB = Rb + (size_t)(ABL == 4 ? 1 : pt.y) * TILE * K;
     if (cn + 1 < cnt) cursor_peek(first + (cn + 1) * step);
   };
-  auto stage_next = [&](int buf) {      // cn < cnt
-    int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) glds16(cA + ck + roff[q], base + q * 1024);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) glds16(cB + ck + roff[q], base + TILE * BK + q * 1024);
+  auto cursor_step = [&]() {
     ck += BK;
     if (ck == K) {
       ck = 0; ++cn;
       if (cn < cnt) cursor_tile();
     }
+  };
+  // pieces q0, q0 + 1 of the cursor's stage (0..3: A, 4..7: B) into buffer buf
+  auto pieces2 = [&](int buf, int q0) {
+    int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
+#pragma unroll
+    for (int q = q0; q < q0 + 2; ++q) {
+      if (q < 4) glds16(cA + ck + roff[q], base + q * 1024);
+      else glds16(cB + ck + roff[q - 4], base + TILE * BK + (q - 4) * 1024);
+    }
+  };
+  auto piece1 = [&](int buf, int q) {
+    int8_t* base = lds + buf * STAGE_BYTES + wid * 4096;
+    if (q < 4) glds16(cA + ck + roff[q], base + q * 1024);
+    else glds16(cB + ck + roff[q - 4], base + TILE * BK + (q - 4) * 1024);
+  };
+  auto stage_next = [&](int buf, bool load) {      // cn < cnt
+    if (load) {
+#pragma unroll
+      for (int q0 = 0; q0 < 8; q0 += 2) pieces2(buf, q0);
+    }
+    cursor_step();
   };
   const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
   // byte offset of a fragment in its stage: (row 128) + ((ks 4 + fk) ^ (row >> 1) & 7) 16 with row = 16 m + frow (+ the wave's first
@@ -388,17 +413,25 @@ __global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_ps(const int8_t* __
   if (STAMP) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
   cursor_peek(first);
   cursor_tile();
-  stage_next(0);
+  stage_next(0, true);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (cn < cnt) stage_next(1);
+  if (cn < cnt) stage_next(1, true);
   v4i alo[4], ahi[4], b[4], alo1[4], ahi1[4], b1[4];
 #pragma unroll
   for (int f = 0; f < 4; ++f) { alo[f] = frag(lds, offA, 0, f); b[f] = frag(lds, offB, 0, f); }
+  if (ABL == 2) {      // every fragment register is read once, here, from stage 0
+#pragma unroll
+    for (int f = 0; f < 4; ++f) { ahi[f] = frag(lds, offA, 0, 4 + f); alo1[f] = frag(lds, offA, 1, f); b1[f] = frag(lds, offB, 1, f); ahi1[f] = frag(lds, offA, 1, 4 + f); }
+  }
+  bool stored = false;    // ABL 6: an epilogue's stores have been issued since the last wait
+  bool pend = false;      // ABL 5: the B pieces of the cursor's stage are still to be issued, in phase 1 of the next K step
   // 8 MFMAs: row fragments 2 h, 2 h + 1 of A4 (accumulator rows M0 + 2 h ..) x the 4 column fragments
 #define EMUL_MMA8(A4, B4, M0, h)                                                                                                   \
   _Pragma("unroll") for (int m = 2 * (h); m < 2 * (h) + 2; ++m)                                                                    \
   _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + m][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + m][n], 0, 0, 0)
+#define EMUL_MMA4(A4, B4, M0, m)                                                                                                   \
+  _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + (m)][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + (m)][n], 0, 0, 0)
 #define EMUL_PIN() __builtin_amdgcn_sched_barrier(0)
   int par = 0;      // s & 1
   for (int n = 0, id = first; n < cnt; ++n, id += step) {
@@ -409,27 +442,104 @@ __global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_ps(const int8_t* __
     for (int kt = 0; kt < nk; ++kt, par ^= 1) {
       const int8_t* cur = lds + par * STAGE_BYTES;
       const int8_t* nxt = lds + (par ^ 1) * STAGE_BYTES;
-      EMUL_MMA8(alo, b, 0, 0); EMUL_PIN();      // phase 1
+      if (ABL == 6) {      // the split ring: the B half of a buffer is free after phase 2, the A half after phase 3
+        EMUL_MMA8(alo, b, 0, 0); EMUL_PIN();      // phase 1
 #pragma unroll
-      for (int f = 0; f < 4; ++f) ahi[f] = frag(cur, offA, 0, 4 + f);
-      EMUL_PIN(); EMUL_MMA8(alo, b, 0, 1); EMUL_PIN();
+        for (int f = 0; f < 4; ++f) ahi[f] = frag(cur, offA, 0, 4 + f);
+        EMUL_PIN(); EMUL_MMA8(alo, b, 0, 1); EMUL_PIN();
+        EMUL_MMA8(ahi, b, 4, 0); EMUL_PIN();      // phase 2
+#pragma unroll
+        for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }      // b1: the LAST read of the B half
+        EMUL_PIN(); EMUL_MMA8(ahi, b, 4, 1); EMUL_PIN();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        pend = cn < cnt;      // stage s + 2 exists: its B half goes into this buffer now, its A half in phase 4
+        EMUL_PIN(); EMUL_MMA4(alo1, b1, 0, 0); EMUL_PIN();      // phase 3
+        if (pend) piece1(par, 4);
+        EMUL_PIN(); EMUL_MMA4(alo1, b1, 0, 1); EMUL_PIN();
+        if (pend) piece1(par, 5);
+#pragma unroll
+        for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);      // the LAST read of the A half
+        EMUL_PIN(); EMUL_MMA4(alo1, b1, 0, 2); EMUL_PIN();
+        if (pend) piece1(par, 6);
+        EMUL_PIN(); EMUL_MMA4(alo1, b1, 0, 3); EMUL_PIN();
+        if (pend) piece1(par, 7);
+        // stage s + 1 (8 pieces) has to have landed; only the 4 pieces just issued are younger.  After an epilogue its stores count too.
+        if (pend && !stored) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        stored = false;
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
+        if (pend) piece1(par, 0);
+        EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 1); EMUL_PIN();
+        if (pend) piece1(par, 1);
+        if (kt + 1 < nk || n + 1 < cnt) {
+#pragma unroll
+          for (int f = 0; f < 4; ++f) { alo[f] = frag(nxt, offA, 0, f); b[f] = frag(nxt, offB, 0, f); }
+        }
+        EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 2); EMUL_PIN();
+        if (pend) piece1(par, 2);
+        EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 3); EMUL_PIN();
+        if (pend) { piece1(par, 3); cursor_step(); }
+        EMUL_PIN();
+        continue;
+      }
+      if (ABL == 5) {      // phase 1 with the second half of the stage begun in phase 4 of the step before (buffer par ^ 1)
+        EMUL_MMA4(alo, b, 0, 0); EMUL_PIN();
+        if (pend) pieces2(par ^ 1, 4);
+        EMUL_PIN(); EMUL_MMA4(alo, b, 0, 1); EMUL_PIN();
+      } else {
+        EMUL_MMA8(alo, b, 0, 0); EMUL_PIN();      // phase 1
+      }
+      if (ABL != 2) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) ahi[f] = frag(cur, offA, 0, 4 + f);
+      }
+      if (ABL == 5) {
+        EMUL_PIN(); EMUL_MMA4(alo, b, 0, 2); EMUL_PIN();
+        if (pend) { pieces2(par ^ 1, 6); cursor_step(); pend = false; }
+        EMUL_PIN(); EMUL_MMA4(alo, b, 0, 3); EMUL_PIN();
+      } else {
+        EMUL_PIN(); EMUL_MMA8(alo, b, 0, 1); EMUL_PIN();
+      }
       EMUL_MMA8(ahi, b, 4, 0); EMUL_PIN();      // phase 2
+      if (ABL != 2) {
 #pragma unroll
-      for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }
+        for (int f = 0; f < 4; ++f) { alo1[f] = frag(cur, offA, 1, f); b1[f] = frag(cur, offB, 1, f); }
+      }
       EMUL_PIN(); EMUL_MMA8(ahi, b, 4, 1); EMUL_PIN();
       EMUL_MMA8(alo1, b1, 0, 0); EMUL_PIN();    // phase 3
+      if (ABL != 2) {
 #pragma unroll
-      for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);
+        for (int f = 0; f < 4; ++f) ahi1[f] = frag(cur, offA, 1, 4 + f);
+      }
       EMUL_PIN(); EMUL_MMA8(alo1, b1, 0, 1); EMUL_PIN();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (cn < cnt) stage_next(par);
-      EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
-      if (kt + 1 < nk || n + 1 < cnt) {
+      if (ABL != 3) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+      }
+      if (ABL == 5) {      // phase 4 with the first half of stage s + 2: 2 pieces after the first and the third group of 4 MFMAs
+        pend = cn < cnt;
+        EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 0); EMUL_PIN();
+        if (pend) pieces2(par, 0);
+        EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 1); EMUL_PIN();
+      } else {
+        if (cn < cnt) stage_next(par, ABL != 1);
+        EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 0); EMUL_PIN();      // phase 4
+      }
+      if (ABL != 2 && (kt + 1 < nk || n + 1 < cnt)) {
 #pragma unroll
         for (int f = 0; f < 4; ++f) { alo[f] = frag(nxt, offA, 0, f); b[f] = frag(nxt, offB, 0, f); }
       }
-      EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
+      if (ABL == 5) {
+        EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 2); EMUL_PIN();
+        if (pend) pieces2(par, 2);
+        EMUL_PIN(); EMUL_MMA4(ahi1, b1, 4, 3); EMUL_PIN();
+      } else {
+        EMUL_PIN(); EMUL_MMA8(ahi1, b1, 4, 1); EMUL_PIN();
+      }
     }
     // epilogue of work id `id`: reduce mod p (|acc| <= K 128^2 <= 2^28), pack the 4 consecutive rows a lane holds into one dword of
     // U[j][i], and clear the accumulators for the next tile.  EPI 0: the fold reduction with one dword store per 16 x 16 block (the
@@ -474,9 +584,228 @@ __global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_ps(const int8_t* __
           acc[m][nn] = (v4i){0, 0, 0, 0};
         }
     }
+    stored = true;
   }
 #undef EMUL_MMA8
+#undef EMUL_MMA4
 #undef EMUL_PIN
+  if (ABL == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no wave ends with a load into LDS in flight
+  if (STAMP) {
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    if (tid == 0) { stamps[2 * (size_t)blockIdx.x] = t1 - t0; stamps[2 * (size_t)blockIdx.x + 1] = r1 - r0; }
+  }
+}
+
+
+constexpr int HK = 64, HALF_BYTES = 2 * TILE * HK;      // a half-stage: 64 bytes of k of the A tile + of the B tile
+
+// MEASURED AND NOT KEPT: the persistent walk and the epilogue of i8_syrk_mod_kernel_ps<.., 3> above, with the K loop
+// staged in half-stages of 64 bytes of k through a ring of four LDS slots and waited for with counted vmcnt.  Exact, and slower than
+// the loop it was to replace: its pieces are 16 rows x 64 B, half a 128-byte line per row.  SWZ false: the same kernel without the
+// chunk XOR on either side (the same bytes out; it is there to time the bank conflicts the XOR removes).
+//   workgroup tile 256 x 256 x 128, 8 waves as 2 (M) x 4 (N), v_mfma_i32_16x16x64_i8 (wave tile 128 x 64 = 8 x 4 accumulators);
+//   the 128 KiB of LDS are a ring of four 32-KiB slots; a slot holds one HALF-STAGE: 64 bytes of k of the A tile (256 rows x 64 B)
+//   and of the B tile, filled by global_load_lds_dwordx4 in pieces of 16 rows x 64 B (each wave 2 of A and 2 of B per half-stage);
+//   LDS rows are 64 B, four to a 256-B bank row; the 16-B chunk c of row r is stored at chunk c ^ ((0 - (r >> 2)) & 3), the XOR put
+//   on the SOURCE address of the piece and on the fragment read, so every ds_read_b128 lane group hits 16 distinct 16-B slots.
+// Both operands are fragment-loaded the same way (lane l: row l & 15, bytes 16 (l >> 4) .. + 15 of the 64-deep k range), so the k
+// order inside an MFMA is the same for A and B whatever the hardware's k map is.  Mp, Np multiples of 256, K of 128: no edges.
+//
+// Persistent: the grid is min(work ids, CUs) workgroups (launch_hs takes the cap), a work id = an (item, tile) pair in the
+// order item-major, tile list inside.  Blocks b and b + 8 share an XCD: XCD b & 7 owns a contiguous range of ids and its w workgroups
+// walk it from (b >> 3) with stride w, so at any moment the workgroups of an XCD sit on w consecutive ids, one supertile.  The walk
+// is static: no workgroup waits for, or reads anything written by, another one.
+//
+// The half-stages of the tiles a workgroup walks form ONE stream h = 0, 1, 2, .. (two per K step of 128, 2 nk per tile); half-stage h
+// lives in slot h & 3.  A staging cursor (tile base pointers, k offset) runs four half-stages ahead of the MFMAs and steps into the
+// next work id when it has issued a tile's last half-stage (with nk = 1 the cursor is two TILES ahead), so between the last MFMA
+// of a tile and the first of the next only the epilogue stands, with the next tile's loads and first fragment reads issued above it.
+//
+// A half-stage is two phases of 16 MFMAs (mh = the upper / lower 4 of the wave's 8 row fragments).  The fragments of a phase are read
+// into registers in the MIDDLE of the phase before it, between its two groups of 8 MFMAs, so they are 8 MFMAs old when the wait before
+// their first use comes.  sched_barrier(0) pins that order: left alone, the scheduler sinks the reads down to their uses.  The loop
+// body is one K step = half-stages h (even) and h + 1, which alternate between two sets of fragment registers.
+//
+//   phase of half-stage h | MFMAs use (registers)   | ds_reads issued (slot)                  | global_load_lds issued
+//   1 (mh 0)              | a[0..3], b[0..3] of h   | a[4..7] of h (h & 3): the LAST read of slot h & 3
+//   -- s_waitcnt lgkmcnt(0) vmcnt(n); s_barrier: every wave holds all its fragments of h in registers, and every wave's pieces of
+//      h + 1 have landed in slot (h + 1) & 3.  n = 8: the wave's pieces of h + 2 and h + 3, issued after those of h + 1, may still
+//      be in flight; less at the tail of the walk, 0 right after an epilogue (see below) --
+//   2 (mh 1)              | a[4..7], b[0..3] of h   | a[0..3], b[0..3] of h + 1 ((h + 1) & 3) | h + 4 into slot h & 3: one piece
+//                                                                                               after each group of 4 MFMAs
+//   -- after the last half-stage of a tile: the epilogue of that tile (registers and global stores only) --
+//
+//   read after write: slot (h + 1) & 3 is first read in phase 2 of h, after the wait-plus-barrier of h: each wave has waited for its
+//   own pieces of h + 1 (a wave's loads retire in the order it issued them, so at most 8 outstanding means h + 1 and everything
+//   older have landed), and the barrier makes that true of all eight waves before any of them reads.
+//   write after read: slot h & 3 is restaged with h + 4 in phase 2 of h, after the barrier of h, which every wave reaches only with
+//   its last reads of that slot (phase 1 of h) complete (lgkmcnt(0)).  The pieces of h + 4 are waited for three half-stages
+//   (96 MFMAs per wave) later, at the barrier of h + 3.
+//   Neither argument looks at which tile a half-stage belongs to: h .. h + 4 may lie in one to three tiles (five with nk = 1), and
+//   the epilogue touches no LDS and stands after phase 2 of a half-stage and before phase 1 of the next, where the schedule has no
+//   LDS ordering to keep.
+//   The count: `issued` half-stages have been issued when the wait of h comes, so issued - h - 2 of them are younger than h + 1,
+//   4 loads each.  That is 2 in the steady state and 1, 0, 0 for the last three half-stages of the walk, when the cursor has run
+//   out: vmcnt(8) there would not wait for the half-stage about to be read.  The epilogue's 8 stores per lane count in vmcnt too
+//   and nothing here relies on how stores retire relative to loads: the first wait after an epilogue is vmcnt(0), once per tile.
+//   The prologue (once per workgroup) issues up to four half-stages and waits for the first with the same count.
+template <bool STAMP, bool SWZ>
+__global__ __launch_bounds__(512, 2) void i8_syrk_mod_kernel_hs(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
+                                                                int nids, int Mp, int Np, int K, Moduli mod, unsigned long long* __restrict__ stamps) {
+  __shared__ __attribute__((aligned(1024))) int8_t lds[4 * HALF_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
+  // the walk of this workgroup: ids first, first + step, .. (cnt of them) of its XCD's range; fewer than 8 workgroups split the ids
+  // among themselves
+  const int nwg = gridDim.x, parts = nwg < 8 ? nwg : 8, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int step = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
+  const int qi = nids / parts, ri = nids - qi * parts;
+  const int first = xcd * qi + (xcd < ri ? xcd : ri) + slot, span = qi + (xcd < ri ? 1 : 0) - slot;
+  const int cnt = span > 0 ? (span + step - 1) / step : 0;
+  if (cnt == 0) return;
+  // source offsets of a lane's two 16-byte loads of one operand, from the tile's first row at k = 0: lane l of a piece lands at
+  // row l >> 2, chunk slot l & 3 and fetches the source chunk that the swizzle stores there
+  unsigned roff[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int row = wid * 32 + q * 16 + (lane >> 2), chunk = (lane & 3) ^ (SWZ ? (0 - (row >> 2)) & 3 : 0);
+    roff[q] = (unsigned)row * (unsigned)K + chunk * 16;
+  }
+  // the staging cursor: operand panels of the cn-th work id of the walk, next k offset ck; (pitem, pt) is the (cn + 1)-th work id,
+  // loaded one tile ahead so that stepping into it waits for no load
+  const int8_t* cA = nullptr;
+  const int8_t* cB = nullptr;
+  int cn = 0, ck = 0, pitem = 0;
+  int2 pt = make_int2(0, 0);
+  auto cursor_peek = [&](int idn) {
+    pitem = idn / ntiles;
+    pt = tiles[idn - pitem * ntiles];
+  };
+  auto cursor_tile = [&]() {
+    const int8_t* Rb = R + (size_t)pitem * Mp * K;
+    cA = Rb + (size_t)pt.x * TILE * K;
+    cB = Rb + (size_t)pt.y * TILE * K;
+    if (cn + 1 < cnt) cursor_peek(first + (cn + 1) * step);
+  };
+  int issued = 0, h = 0;      // half-stages issued so far; the half-stage the MFMAs are in
+  // piece i (0, 1: A; 2, 3: B) of the cursor's half-stage into slot sl; the cursor moves on with the last one
+  auto piece = [&](int sl, int i) {      // cn < cnt
+    int8_t* base = lds + sl * HALF_BYTES + wid * 2048;
+    if (i < 2) glds16(cA + ck + roff[i], base + i * 1024);
+    else glds16(cB + ck + roff[i - 2], base + TILE * HK + (i - 2) * 1024);
+    if (i == 3) {
+      ck += HK; ++issued;
+      if (ck == K) {
+        ck = 0; ++cn;
+        if (cn < cnt) cursor_tile();
+      }
+    }
+  };
+  bool stored = false;      // an epilogue's stores have been issued since the last wait
+  // the wait-plus-barrier of half-stage h (see above); all branches are uniform
+  auto retire = [&]() {
+    const int younger = stored ? 0 : issued - h - 2;
+    if (younger >= 3) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
+    else if (younger == 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+    else if (younger == 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    stored = false; ++h;
+  };
+  const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
+  // byte offset of a fragment in its slot: (row 64) + ((fk ^ (0 - (row >> 2)) & 3) 16) with row = 16 m + frow (+ the wave's first
+  // row, a multiple of 64): the swizzle is that of frow
+  const int fsw = (fk ^ (SWZ ? (0 - (frow >> 2)) & 3 : 0)) << 4;
+  const int offA = (wr * 128 + frow) * HK + fsw, offB = TILE * HK + (wc * 64 + frow) * HK + fsw;
+  auto frag = [&](const int8_t* st, int off, int f) { return *reinterpret_cast<const v4i*>(st + off + f * 16 * HK); };
+  v4i acc[8][4];
+#pragma unroll
+  for (int m = 0; m < 8; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = (v4i){0, 0, 0, 0};
+  unsigned long long t0 = 0, r0 = 0;
+  if (STAMP) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
+  cursor_peek(first);
+  cursor_tile();
+#pragma unroll
+  for (int sl = 0; sl < 4; ++sl)
+    if (cn < cnt) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) piece(sl, i);
+    }
+  h = -1;      // the wait for half-stage 0 is that of a half-stage -1
+  retire();
+  v4i alo[4], ahi[4], b[4], alo1[4], ahi1[4], b1[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) { alo[f] = frag(lds, offA, f); b[f] = frag(lds, offB, f); }
+  // 4 MFMAs: row fragment m of A4 (accumulator row M0 + m) x the 4 column fragments
+#define EMUL_MMA4(A4, B4, M0, m)                                                                                                   \
+  _Pragma("unroll") for (int n = 0; n < 4; ++n) acc[(M0) + (m)][n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A4[m], B4[n], acc[(M0) + (m)][n], 0, 0, 0)
+#define EMUL_PIN() __builtin_amdgcn_sched_barrier(0)
+  // phase 1 of a half-stage held in (ALO, B): its a[4..7] are read from slot SL into AHI, then the wait-plus-barrier
+#define EMUL_PHASE1(ALO, AHI, B, SL)                                                                                               \
+  EMUL_MMA4(ALO, B, 0, 0); EMUL_MMA4(ALO, B, 0, 1); EMUL_PIN();                                                                    \
+  _Pragma("unroll") for (int f = 0; f < 4; ++f) AHI[f] = frag(lds + (SL) * HALF_BYTES, offA, 4 + f);                               \
+  EMUL_PIN(); EMUL_MMA4(ALO, B, 0, 2); EMUL_MMA4(ALO, B, 0, 3); EMUL_PIN();                                                        \
+  retire(); EMUL_PIN()
+  // phase 2 of the half-stage in slot SL, held in (AHI, B): the cursor's half-stage goes into SL, one piece after each group of 4
+  // MFMAs, and if MORE the first fragments of the next half-stage are read from slot SN into (ALO, BN)
+#define EMUL_PHASE2(AHI, B, SL, ALO, BN, SN, MORE)                                                                                 \
+  {                                                                                                                                \
+    const bool st = cn < cnt;                                                                                                      \
+    EMUL_MMA4(AHI, B, 4, 0); EMUL_PIN();                                                                                           \
+    if (st) piece(SL, 0);                                                                                                          \
+    EMUL_PIN(); EMUL_MMA4(AHI, B, 4, 1); EMUL_PIN();                                                                               \
+    if (st) piece(SL, 1);                                                                                                          \
+    if (MORE) {                                                                                                                    \
+      _Pragma("unroll") for (int f = 0; f < 4; ++f) { ALO[f] = frag(lds + (SN) * HALF_BYTES, offA, f); BN[f] = frag(lds + (SN) * HALF_BYTES, offB, f); } \
+    }                                                                                                                              \
+    EMUL_PIN(); EMUL_MMA4(AHI, B, 4, 2); EMUL_PIN();                                                                               \
+    if (st) piece(SL, 2);                                                                                                          \
+    EMUL_PIN(); EMUL_MMA4(AHI, B, 4, 3); EMUL_PIN();                                                                               \
+    if (st) piece(SL, 3);                                                                                                          \
+    EMUL_PIN();                                                                                                                    \
+  }
+  int par = 0;      // (h >> 1) & 1 at the top of a K step: its half-stages live in slots 2 par and 2 par + 1
+  for (int n = 0, id = first; n < cnt; ++n, id += step) {
+    // what the epilogue of this work id needs, loaded above its K loop
+    const int item = id / ntiles;
+    const int2 t = tiles[id - item * ntiles];
+    const int p = mod.p[item % NMOD];
+    for (int kt = 0; kt < nk; ++kt, par ^= 1) {
+      const int s0 = 2 * par, s1 = s0 + 1, s2 = s0 ^ 2;
+      EMUL_PHASE1(alo, ahi, b, s0);
+      EMUL_PHASE2(ahi, b, s0, alo1, b1, s1, true);
+      EMUL_PHASE1(alo1, ahi1, b1, s1);
+      EMUL_PHASE2(ahi1, b1, s1, alo, b, s2, kt + 1 < nk || n + 1 < cnt);
+    }
+    // epilogue of work id `id`: that of i8_syrk_mod_kernel_ps<.., 3>; the accumulators are cleared for the next tile
+    const int cf = fold_const(p);
+    const float pf = (float)p, rp = 1.0f / pf;
+    int8_t* Ub = U + (size_t)item * Np * Mp;
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int nn = 0; nn < 4; ++nn) {
+        unsigned w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          w[k] = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) w[k] |= acc_residue(acc[4 * q + k][nn][e], cf, pf, rp) << (8 * e);
+          acc[4 * q + k][nn] = (v4i){0, 0, 0, 0};
+        }
+        transpose4(w);
+        const size_t j = (size_t)t.y * TILE + wc * 64 + nn * 16 + frow;
+        const int i = t.x * TILE + wr * 128 + (4 * q + fk) * 16;
+        *reinterpret_cast<v4u*>(Ub + j * Mp + i) = (v4u){w[0], w[1], w[2], w[3]};
+      }
+    stored = true;
+  }
+#undef EMUL_MMA4
+#undef EMUL_PIN
+#undef EMUL_PHASE1
+#undef EMUL_PHASE2
   if (STAMP) {
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     if (tid == 0) { stamps[2 * (size_t)blockIdx.x] = t1 - t0; stamps[2 * (size_t)blockIdx.x + 1] = r1 - r0; }
@@ -555,6 +884,29 @@ static void launch_ps(const int8_t* R, int8_t* U, const int2* tiles, int ntiles,
   i8_syrk_mod_kernel_ps<STAMP, EPI><<<std::min(nids, wgs > 0 ? wgs : g_cus), 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps);
 }
 
+// variant v of the K loop on at most `wgs` workgroups (0: one per CU).  0: the loop the library had before the half-stage ring
+// (i8_syrk_mod_kernel_ps<.., 3, 0>); 1 .. 5: its legs (a) .. (e) (ABL 1 .. 5 of that kernel); 6: the ring of four 64-byte-deep slots
+// (i8_syrk_mod_kernel_hs: built first, slower, not the library's); 7: that ring without the LDS swizzle; 8: (f), the library's loop
+// (ABL 6).  1 .. 4 compute wrong products on purpose: they are timed only.
+constexpr int NVAR = 9;
+static const char* kVarNames[NVAR] = {"shipped before (full-stage burst)", "(a) no global_load_lds", "(b) no fragment reads", "(c) no wait, no barrier",
+                                      "(d) operands L2-resident", "(e) pieces spread, vmcnt(0)", "ring of four 64-B slots (rejected)", "ring of four 64-B slots, no swizzle", "(f) halves restaged apart (library)"};
+template <bool STAMP>
+static void launch_var(int v, const int8_t* R, int8_t* U, const int2* tiles, int ntiles, int M, int N, int K, int batch, int wgs, unsigned long long* stamps) {
+  const int nids = ntiles * batch, g = std::min(nids, wgs > 0 ? wgs : g_cus);
+  switch (v) {
+    case 0: i8_syrk_mod_kernel_ps<STAMP, 3, 0><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps); break;
+    case 1: i8_syrk_mod_kernel_ps<STAMP, 3, 1><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps); break;
+    case 2: i8_syrk_mod_kernel_ps<STAMP, 3, 2><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps); break;
+    case 3: i8_syrk_mod_kernel_ps<STAMP, 3, 3><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps); break;
+    case 4: i8_syrk_mod_kernel_ps<STAMP, 3, 4><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps); break;
+    case 5: i8_syrk_mod_kernel_ps<STAMP, 3, 5><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps); break;
+    case 6: i8_syrk_mod_kernel_hs<STAMP, true><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps); break;
+    case 7: i8_syrk_mod_kernel_hs<STAMP, false><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps); break;
+    default: i8_syrk_mod_kernel_ps<STAMP, 3, 6><<<g, 512>>>(R, U, tiles, ntiles, nids, M, N, K, kModuli, stamps);
+  }
+}
+
 // exact check of U against a host integer product; every == true checks every computed tile and that nothing else was written
 static long check(const int8_t* dR, const int8_t* dU, int M, int N, int K, int batch, bool every, const char* what) {
   std::vector<int8_t> hR((size_t)M * K), hU((size_t)N * M);
@@ -590,6 +942,7 @@ static long check(const int8_t* dR, const int8_t* dU, int M, int N, int K, int b
 int main(int argc, char** argv) {
   const int nmat = argc > 1 ? atoi(argv[1]) : 1;
   const bool brief = argc > 2;      // any second argument: the exact checks and one round of the older kernels only
+  const bool looponly = argc > 2 && !strcmp(argv[2], "loop");      // "loop": the exact checks and the timing of the K loop's variants (section 4) only
   const int batch = NMOD * nmat;
   hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
   long bad = 0;
@@ -633,6 +986,7 @@ int main(int argc, char** argv) {
     launch<16, false>(R, U, dt, (int)tl.size(), M, N, K, NMOD, nullptr);
     CHECK(hipDeviceSynchronize());
     bad += check(R, U, M, N, K, NMOD, true, "16x16x64 full");
+    if (!looponly)
     for (int Kp : {128, 256, 384, 512}) {      // the register-prefetch kernel: K loops shorter than its pipeline, odd and even counts (R holds 512 x 384 x 16 bytes: the same rows, read with K = Kp, for Kp <= 384; 512 fits as M K NMOD = 512 * 512 * 12)
       const int nb = Kp <= K ? NMOD : 12;
       CHECK(hipMemset(U, 0x5A, (size_t)NMOD * N * M));
@@ -640,6 +994,7 @@ int main(int argc, char** argv) {
       CHECK(hipDeviceSynchronize());
       bad += check(R, U, M, N, Kp, nb, true, "16x16x64 prefetch full");
     }
+    if (!looponly)
     for (int Kp : {128, 256, 384, 512})      // the persistent kernel: one, two, five workgroups walk the 3 tiles x 16 (12) moduli, and the default grid
       for (int wgs : {1, 2, 5, 0}) {
         const int nb = Kp <= K ? NMOD : 12;
@@ -656,6 +1011,32 @@ int main(int argc, char** argv) {
         CHECK(hipDeviceSynchronize());
         bad += check(R, U, M, N, Kp, nb, true, "persistent, 16-byte stores");
       }
+    // the K loop's variants that compute the product (kVarNames 5 .. 8): K / 128 = 1 .. 5 and 9 (the ring wraps at every phase; odd
+    // counts; one K step per tile, where the cursor runs two tiles ahead), one to seven workgroups and the default grid.  The loop
+    // before (variant 0) on the default grid is checked against the host once per K; its bytes, canaries included, are the reference
+    // of every other launch.
+    for (int Kp : {128, 256, 384, 512, 640, 1152}) {
+      const int nb = std::min(NMOD, NMOD * K / Kp);      // R holds 512 x 384 x 16 bytes: the same bytes read as nb matrices of 512 x Kp
+      const size_t ub = (size_t)nb * N * M;
+      std::vector<int8_t> ref(ub), got(ub);
+      CHECK(hipMemset(U, 0x5A, ub));
+      launch_var<false>(0, R, U, dt, (int)tl.size(), M, N, Kp, nb, 0, nullptr);
+      CHECK(hipDeviceSynchronize());
+      bad += check(R, U, M, N, Kp, nb, true, "loop before, full");
+      CHECK(hipMemcpy(ref.data(), U, ub, hipMemcpyDeviceToHost));
+      for (int v : {5, 6, 7, 8})
+        for (int wgs : {1, 2, 3, 5, 7, 0}) {
+          CHECK(hipMemset(U, 0x5A, ub));
+          launch_var<false>(v, R, U, dt, (int)tl.size(), M, N, Kp, nb, wgs, nullptr);
+          CHECK(hipDeviceSynchronize());
+          CHECK(hipMemcpy(got.data(), U, ub, hipMemcpyDeviceToHost));
+          long diff = 0;
+          for (size_t i = 0; i < ub; ++i) diff += got[i] != ref[i];
+          if (diff) printf("  MISMATCH %s, K=%d, %d wgs: %ld bytes differ from the loop before\n", kVarNames[v], Kp, wgs, diff);
+          bad += diff;
+        }
+      printf("check K=%4d: variants (e), (f), half-stage ring, ring without swizzle on 1, 2, 3, 5, 7 workgroups and the default grid: %s\n", Kp, bad ? "WRONG" : "same bytes");
+    }
     CHECK(hipFree(R)); CHECK(hipFree(U)); CHECK(hipFree(dt));
     fflush(stdout);
     if (bad) { printf("operand or output map wrong: not timing\n"); return 1; }
@@ -677,6 +1058,7 @@ int main(int argc, char** argv) {
     const double outs = (double)s.N * (s.N + 1) / 2 + (double)(s.M - s.N) * s.N;
     const double useful = 2.0 * s.K * outs * batch, issued = 2.0 * s.K * (double)TILE * TILE * nt * batch;
     const int reps = (int)std::max(4.0, 0.15 / (issued / 2.0e15));  // about 150 ms per window at 2 POPS
+    if (!looponly) {
     std::vector<float> t32, t16, tpf;
     for (int round = 0; round < (brief ? 1 : 3); ++round)
       for (int v = 0; v < 3; ++v) {
@@ -765,6 +1147,40 @@ int main(int argc, char** argv) {
     launch<0, false>(R, U, dt, nt, s.M, s.N, s.K, batch, nullptr);
     CHECK(hipDeviceSynchronize());
     bad += check(R, U, s.M, s.N, s.K, batch, false, "16x16x64 prefetch sampled");
+    }
+    {  // 4. the K loop: the loop before, its ablation legs, and the half-stage ring, interleaved in every round; the clock of each
+      std::vector<float> tv[NVAR];
+      const int nids = nt * batch, g = std::min(nids, g_cus);
+      const double tiles_per_cu = (double)nids / g_cus;
+      for (int round = 0; round < 3; ++round)
+        for (int v = 0; v < NVAR; ++v) {
+          launch_var<false>(v, R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr);
+          hipEventRecord(e0);
+          for (int r = 0; r < reps; ++r) launch_var<false>(v, R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr);
+          hipEventRecord(e1); CHECK(hipEventSynchronize(e1));
+          float ms; hipEventElapsedTime(&ms, e0, e1);
+          tv[v].push_back(ms / reps);
+        }
+      printf("  K loop variants, M=%5d N=%5d K=%5d, %.2f tiles per CU: us per tile and CU, median (min - max) of 3 windows of %d launches; clock\n", s.M, s.N, s.K, tiles_per_cu, reps);
+      for (int v = 0; v < NVAR; ++v) {
+        for (int r = 0; r < 3; ++r) launch_var<true>(v, R, U, dt, nt, s.M, s.N, s.K, batch, 0, st);
+        CHECK(hipDeviceSynchronize());
+        std::vector<unsigned long long> h((size_t)g * 2);
+        CHECK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
+        std::vector<double> cl;
+        for (int w = 0; w < g; ++w) cl.push_back((double)h[2 * w] / (double)h[2 * w + 1] * 100.0);
+        std::sort(cl.begin(), cl.end());
+        std::sort(tv[v].begin(), tv[v].end());
+        const double u = 1e3 / tiles_per_cu;
+        printf("    %-36s %8.2f (%8.2f - %8.2f) us   %.3f ms   clock %.0f MHz\n", kVarNames[v], tv[v][1] * u, tv[v][0] * u, tv[v][2] * u, tv[v][1], cl[cl.size() / 2]);
+      }
+      for (int v : {5, 6, 8}) {
+        CHECK(hipMemset(U, 0x5A, ub));
+        launch_var<false>(v, R, U, dt, nt, s.M, s.N, s.K, batch, 0, nullptr);
+        CHECK(hipDeviceSynchronize());
+        bad += check(R, U, s.M, s.N, s.K, batch, false, v == 5 ? "(e) sampled" : v == 6 ? "ring of four slots sampled" : "(f) sampled");
+      }
+    }
     fflush(stdout);
     CHECK(hipFree(R)); CHECK(hipFree(U)); CHECK(hipFree(dt)); CHECK(hipFree(st));
   }
