@@ -815,6 +815,24 @@ int lmm_dev_set_emul_group(int g);
  * cap are counted, not written), or -LMM_ERR_ARG.  Updates inside a block column that one dataflow launch factors are listed too; they
  * never run on their own. */
 int lmm_dev_emul_plan(int NR, int NC, int nb, long long* out, int cap);
+/* Host-only (no GPU, no lmm_init needed): what the batched Cholesky launches for nb matrices of NR rows and NC columns (multiples of 64;
+ * rows_real of the rows hold data, NC <= rows_real <= NR, or -1: all) while in_flight batches run side by side on a device of cus CUs, in Float32 (f32 != 0) or
+ * Float64, with strict progress on or off, under the current switches (the decision table and the step kinds).
+ * out holds LMM_POTRF_PLAN_HEADER + LMM_POTRF_PLAN_STEP cap words.
+ *   header: [0] 1 = 128-column panel path, 0 = 64-column recursion; [1] widest block column that is one region launch (0: none);
+ *           per matrix: [2] doubles of the W2 scratch, [3] ints of the fused-bulk flags (0: no launch fuses), [4] doubles of the region
+ *           assistants' scratch; [5] bytes and [6] matrices-per-group G of the emulation block, [7] moduli.
+ *   step:   [0] kind -- 0 diag64, 1 64-column solve by inverse, 2 plain update, 3 leaf128, 4 panel bulk, 5 update + leaf, 6 emulated
+ *           update + leaf, 7 region; [1] j0 (first column); [2] h (depth K of an update's product; the block's width otherwise);
+ *           [3] N (columns); [4] M (rows; of an update: from row j0 + h); [5] profile class (lmm_prof_class); [6] 1 when the profile
+ *           names the step's (M, N, K) = ([4], [3], [2]); [7] work and [8] bytes booked for the class, as the bits of a double;
+ *           [9] first_done (region: its first diagonal block is already factored); [10] fused_bulk (update + leaf: the next panel's
+ *           bulk rows ride in the launch); [11] a ragged last 64 rows: 0 none, 1 as items of the launch, 2 as a launch of their own;
+ *           [12] matrices per group and [13] scratch bytes of an emulated update.
+ * Returns the number of steps (those beyond cap are counted, not written), or -LMM_ERR_ARG. */
+#define LMM_POTRF_PLAN_HEADER 8
+#define LMM_POTRF_PLAN_STEP 14
+int lmm_dev_potrf_plan(int NR, int NC, int nb, int rows_real, int in_flight, int cus, int f32, int strict, long long* out, int cap);
 /* Test hook: the emulation's GEMM is a persistent kernel of min(work items, CUs) workgroups; wgs >= 1 caps that grid (a small shape
  * then makes one workgroup walk several tiles), 0 goes back to the default.  Results do not depend on it. */
 int lmm_dev_set_emul_gemm_workgroups(int wgs);

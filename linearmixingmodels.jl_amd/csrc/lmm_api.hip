@@ -694,10 +694,7 @@ void publish_grads(const LatentSet& S, const std::vector<double>* trec, int l0, 
 // ------------------------------------------------------------------------------------------------
 // blocked factorisation drivers
 // ------------------------------------------------------------------------------------------------
-inline int split(int w) {            // left width of the recursive split (multiple of 64; of 128 when w >= 256)
-  if (w >= 256) return rup(w / 2, 128);
-  return (w == 192) ? 128 : 64;
-}
+inline int split(int w) { return potrf_split(w); }      // left width of the recursive split (lmm_potrf_plan.h)
 
 // A batch of up to LMM_MAX_BATCH same-shaped factor matrices factored in lock-step by the same launches
 // (blockIdx.y / blockIdx.x selects the matrix): the small recursion levels then fill the chip and the launch
@@ -709,221 +706,36 @@ struct Batch {
   void add(double* a, double* w, int* i) { A.p[nb] = a; W.p[nb] = w; info.p[nb] = i; ++nb; }
 };
 
-// Factor columns [j0, j0+w) of every matrix of the batch (rows j0..NR-1 participate).  W: NC/64 inverse diagonal blocks.
-void potrf_rec(const Batch& B, int ld, int NR, int j0, int w, int n_real, hipStream_t st) {
-  const double nb = B.nb;
-  if (w <= 64) {
-    const size_t offW = (size_t)(j0 / 64) * 4096;
-    {
-      ProfScope ps(LMM_PROF_DIAG, nb * 2.0 * 64.0 * 64.0 * 64.0 / 3.0, st);
-      launch_diag64(B.A, (size_t)j0 * ld + j0, ld, B.W, offW, j0, n_real, B.info, B.nb, st);
-    }
-    const int M = NR - (j0 + 64);
-    if (M > 0) {
-      const size_t offP = (size_t)j0 * ld + (j0 + 64);
-      ProfScope ps(LMM_PROF_TRSM, nb * (double)M * 64.0 * 64.0, st);   // triangular solve: M * 64^2 flops
-      launch_gemm_nt(B.A, offP, ld, B.A, offP, ld, B.W, offW, 64, M, 64, 64, 0, true, B.nb, st);
-    }
-    return;
-  }
-  const int h = split(w);
-  potrf_rec(B, ld, NR, j0, h, n_real, st);
-  const int r0 = j0 + h;
-  {
-    const double Mr = NR - r0, Nc = w - h;     // lower trapezoid: Nc(Nc+1)/2 + (Mr-Nc)Nc outputs, 2h flops each
-    const double outs = Nc * (Nc + 1.0) / 2.0 + (Mr - Nc) * Nc;
-    // algorithmic bytes: C read + written once (16 B per output), the A panel (Mr x h, which contains B) read once
-    ProfScope ps(Nc <= 64 ? LMM_PROF_UPDATE_NARROW : LMM_PROF_UPDATE, nb * 2.0 * h * outs, st, NR - r0, w - h, h,
-                 nb * (16.0 * outs + 8.0 * Mr * h));
-    const size_t offA = (size_t)j0 * ld + r0;
-    launch_gemm_nt(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, B.A, offA, ld, NR - r0, w - h, h, 1, false, B.nb, st);
-  }
-  potrf_rec(B, ld, NR, r0, w - h, n_real, st);
+static int g_in_flight = 1;       // batches that run concurrently on the slot streams (fork_slots / join_slots)
+// The emulation side of a Float64 factorisation's plan, whatever path and base case the other switches choose (lmm_dev_emul_plan, batch_plan)
+static PotrfPlan emul_view(int NR, int NC, int nb) {
+  FactorSwitches sw = factor_switches();
+  sw.panel128 = 1;
+  return plan_potrf(NR, NC, nb, -1, 1, 256, false, false, true, true, sw);
 }
 
-// Round 3: the same recursion with 128-column panels (lmm_kernels.hip K2c).  A panel = leaf128 (its 128 x 128 diagonal block: factor,
-// 64 x 64 inverse blocks, full inverse into the W2 scratch) + ONE bulk GEMM (rows below: X = P Dinv'); and every trailing update
-// also runs the leaf of the panel that follows it (launch_update_leaf), so that per 128 columns the stream sees two launches
-// (update + leaf, bulk) instead of six.  first_done: the diagonal block of the first panel of [j0, j0 + w) is already factored.
-// Widths that are not multiples of 128 (NC = 64 mod 128) end in the round-2 path for their last 64 columns.
-static int g_slots_in_flight = 1;       // batches that run concurrently on the slot streams (set by fork_slots; read by potrf_batch's base-case rule)
-static int g_region_whole = 1;          // LMM_REGION_ALL=1: also as the base case of the recursion for larger matrices (measured: no gain)
-static int g_region_cols = -1;          // widest block column potrf_region_kernel takes in one launch (LMM_REGION=<columns>, up to 1024; default 0: off)
-// The scratch block potrf_batch asks for (emul_block_plan): sized for the widest emulated level at G = min(4, nb, 12 GB / that level) matrices (0: none)
-struct EmulBlockPlan { size_t bytes = 0; int G = 0; };
-// bulk_done (implies first_done): the rows below that block are solved as well (the update launch that factored it ran them too).
-struct NodeFlags { int* p = nullptr; int stride = 0; int min_k = 0, max_k = 1 << 30; int rows_real = -1; BatchPtr S{}; int region_cols = 0;
-                   void* emul = nullptr; EmulBlockPlan emul_plan; int emul_nmod = 0; };      // emul: scratch of the int8 emulation of the updates emul_pays accepts (nullptr: off)   // region_cols: widest block column that becomes ONE dataflow launch in this factorisation   // S: region assistants' scratch      // rows_real: rows that hold data (-1: all NR)
-// Float64 updates run as exact int8 modular GEMMs (lmm_kernels_i8.hip) where that pays: LMM_F64_EMUL=0 keeps them all
-// on the f64 MFMA kernel.  The env values are read once; lmm_dev_set_f64_emul replaces them (tests).
-//   An explicit threshold -- LMM_F64_EMUL_MINK or lmm_dev_set_f64_emul(on, min_k, nmod) -- emulates every update with K >= min_k.
-//   With nothing set (g_emul_mink == 0) the shape rule decides, emul_pays: K >= g_rule_always always; K < g_rule_shape never; between
-//   them when the batch's trapezoid has at least g_rule_outs outputs -- at a fixed K = N both paths grow linearly with the rows and the
-//   matrix count, but the emulated one carries fixed costs (launches per group, the leaf and bulk launches of their own) that only a
-//   large enough update earns back (the crossover table of DESIGN.md 4.17).
-static int g_emul_on = -1, g_emul_mink = -1, g_emul_nmod = LMM_EMUL_MAXMOD;
-constexpr int kRuleAlways = 4096, kRuleShape = 2048;
-constexpr double kRuleOuts = 4.0e7;      // between 16 x (2112 x 2048), which gains under 5 % emulated, and 4 x (6208 x 2048), which gains 20 %
-static int g_rule_always = kRuleAlways, g_rule_shape = kRuleShape;
-static double g_rule_outs = kRuleOuts;
-static int g_emul_group_cap = 0;      // lmm_dev_set_emul_group: at most this many matrices per group of an emulated update (0: no cap)
-static void emul_switches() {
-  if (g_emul_on < 0) { const char* e = getenv("LMM_F64_EMUL"); g_emul_on = e ? (atoi(e) != 0) : 1; }
-  if (g_emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_emul_mink = e ? std::max(128, atoi(e)) : 0; }
-}
-// Does emulating the M x N (x K) trailing update of nb matrices pay?  The ONE place that decides (after emul_switches()).
-static bool emul_pays(int M, int N, int K, int nb) {
-  if (g_emul_mink > 0) return K >= g_emul_mink;
-  if (K >= g_rule_always) return true;
-  if (K < g_rule_shape) return false;
-  const double outs = (double)N * (N + 1.0) / 2.0 + ((double)M - N) * N;
-  return nb * outs >= g_rule_outs;
-}
-// fn(M, N, K) for every trailing update with N >= 128 columns of the recursion over the columns [j0, j0 + w), in the order
-// potrf_rec_panel reaches them (a block column the region kernel takes in one launch has its updates inside that launch: the
-// walk still names them, which only makes the scratch estimate generous)
-template <class F>
-static void emul_walk(int NR, int j0, int w, F&& fn) {
-  if (w < 256) return;
-  const int h = split(w), r0 = j0 + h, Nc = w - h;
-  emul_walk(NR, j0, h, fn);
-  if (Nc >= 128) fn(NR - r0, Nc, h);
-  emul_walk(NR, r0, Nc, fn);
-}
-static bool emul_takes(int M, int N, int K, int nb) { return emul_shape_ok(M, N, K) && emul_pays(M, N, K, nb); }
-// scratch bytes of the widest update of a factorisation of nb matrices that will be emulated, at G matrices per group
-static size_t emul_need(int NR, int NC, int nb, int G, int nmod) {
-  size_t need = 0;
-  emul_walk(NR, 0, NC, [&](int M, int N, int K) { if (emul_takes(M, N, K, nb)) need = std::max(need, emul_scratch_bytes(M, N, K, G, nmod)); });
-  return need;
-}
-static EmulBlockPlan emul_block_plan(int NR, int NC, int nb, int nmod) {
-  EmulBlockPlan P;
-  const size_t one = emul_need(NR, NC, nb, 1, nmod);
-  if (one == 0) return P;
-  P.G = (int)std::max<size_t>(1, std::min<size_t>(std::min(4, nb), (size_t)12e9 / one));
-  P.bytes = emul_need(NR, NC, nb, P.G, nmod);
-  return P;
-}
-// Matrices per group of ONE update inside that block: as many as fit (a level below the widest needs less per matrix, so fewer groups
-// and fewer launches), never fewer than the G the block was sized for
-static int emul_group(int M, int N, int K, int nb, const EmulBlockPlan& P, int nmod) {
-  int gs = (int)std::min<size_t>((size_t)nb, P.bytes / emul_scratch_bytes(M, N, K, 1, nmod));
-  gs = std::max(gs, std::min(P.G, nb));
-  if (g_emul_group_cap > 0) gs = std::min(gs, g_emul_group_cap);
-  return gs;
-}
-void potrf_rec_panel(const Batch& B, const BatchPtr& W2, const BatchInfo& flags, const NodeFlags& nfl, int ld, int NR, int j0, int w, int n_real,
-                     hipStream_t st, bool first_done, bool bulk_done = false) {
-  const double nb = B.nb;
-  if (nfl.region_cols > 0 && w <= nfl.region_cols && w >= 128 && (w % 128) == 0 && flags.p[0] != nullptr) {
-    // the whole block column as ONE dataflow launch (lmm_kernels.hip K2d): leaves, bulk products and all updates inside it
-    const double Mr = (nfl.rows_real >= 0 ? std::min(NR, nfl.rows_real) : NR) - j0, Wd = w;
-    const double fl = Mr * Wd * Wd - 2.0 * Wd * Wd * Wd / 3.0;           // flops of factoring an Mr x Wd tall panel: Mr Wd^2 - 2 Wd^3 / 3
-    ProfScope ps(LMM_PROF_REGION, nb * fl, st, NR - j0, w, w);
-    launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, w, n_real, B.nb, first_done, st, nfl.rows_real, &nfl.S);
-    return;
-  }
-  if (w == 128) {
-    if (!first_done) {
-      ProfScope ps(LMM_PROF_DIAG, nb * 2.0 * 128.0 * 128.0 * 128.0 / 3.0, st, 128, 128, 128);
-      launch_leaf128(B.A, (size_t)j0 * ld + j0, ld, B.W, (size_t)(j0 / 64) * 4096, W2, (size_t)(j0 / 128) * 16384, j0, n_real, B.info, B.nb, st);
-    }
-    const int M = NR - (j0 + 128);
-    if (M > 0 && !bulk_done) {
-      const double Mreal = (nfl.rows_real >= 0 ? std::min(NR, nfl.rows_real) : NR) - (j0 + 128);
-      ProfScope ps(LMM_PROF_TRSM, nb * Mreal * 128.0 * 128.0, st, M, 128, 128);       // triangular solve: (real rows) * 128^2 flops
-      launch_panel_bulk(B.A, W2, ld, NR, j0, B.nb, st);
-    }
-    return;
-  }
-  if (w <= 64) { potrf_rec(B, ld, NR, j0, w, n_real, st); return; }          // a trailing 64-column leaf (never pre-factored)
-  const int h = split(w);
-  potrf_rec_panel(B, W2, flags, nfl, ld, NR, j0, h, n_real, st, first_done, bulk_done);
-  const int r0 = j0 + h, Nc = w - h;
-  // algorithmic rows: those that hold data (rows_real: the Gram rows + the real rider rows), not the 64-row padding of the riders
-  const double Mr = (nfl.rows_real >= 0 ? std::min(NR, nfl.rows_real) : NR) - r0;
-  const double outs = (double)Nc * (Nc + 1.0) / 2.0 + (Mr - Nc) * Nc;
-  const size_t offA = (size_t)j0 * ld + r0;
-  if (Nc >= 128) {
-    // + the leaf's 2 * 128^3 / 3 flops, run by one workgroup of this launch
-    bool fused;
-    {
-      // K >= 1024: potrf_node_kernel<2> (+ gemm16h_kernel for a ragged last 64 rows) -- the dominant kernel; below: potrf_node_kernel<1>.
-      // With the bulk rows of the next panel in the same launch (nfl.p): + their Mb * 128^2 flops and 16 B per entry
-      // emulated (lmm_kernels_i8.hip): convert + int8 GEMMs + combine in place of the f64 update, then the leaf as a launch of its own;
-      // the same flop count, so the class's rate reads as an f64-EQUIVALENT rate
-      const bool emul = nfl.emul != nullptr && emul_takes(NR - r0, Nc, h, B.nb);
-      const double Mb = (!emul && nfl.p && h >= nfl.min_k && h <= nfl.max_k) ? std::max(0.0, Mr - 128.0) : 0;
-      ProfScope ps(h >= 1024 ? LMM_PROF_UPDATE : LMM_PROF_UPDATE_SHORT,
-                   nb * (2.0 * h * outs + 2.0 * 128.0 * 128.0 * 128.0 / 3.0 + Mb * 128.0 * 128.0), st, NR - r0, Nc, h,
-                   nb * (16.0 * outs + 8.0 * Mr * h + 16.0 * Mb * 128.0));
-      if (emul) {
-        const int gs = emul_group(NR - r0, Nc, h, B.nb, nfl.emul_plan, nfl.emul_nmod);
-        const size_t need = emul_scratch_bytes(NR - r0, Nc, h, gs, nfl.emul_nmod);
-        if (need > nfl.emul_plan.bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", need, nfl.emul_plan.bytes);
-        guard_extent(nfl.emul, need / 8, need / 8, 1, false, "emulated update (scratch)");
-        HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, NR - r0, Nc, h, B.nb, gs, nfl.emul_nmod, nfl.emul, st));
-        launch_leaf128(B.A, (size_t)r0 * ld + r0, ld, B.W, (size_t)(r0 / 64) * 4096, W2, (size_t)(r0 / 128) * 16384, r0, n_real, B.info, B.nb, st);
-        fused = false;
-      } else
-      fused = launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, h, Nc, n_real, B.nb, st, (h >= nfl.min_k && h <= nfl.max_k) ? nfl.p : nullptr, nfl.stride);
-    }
-    potrf_rec_panel(B, W2, flags, nfl, ld, NR, r0, Nc, n_real, st, true, fused);
-  } else {
-    {
-      ProfScope ps(LMM_PROF_UPDATE_NARROW, nb * 2.0 * h * outs, st, NR - r0, Nc, h, nb * (16.0 * outs + 8.0 * Mr * h));
-      launch_gemm_nt(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, B.A, offA, ld, NR - r0, Nc, h, 1, false, B.nb, st);
-    }
-    potrf_rec(B, ld, NR, r0, Nc, n_real, st);
-  }
-}
-
-// Entry point of the factorisation of a batch: columns [0, NC) of every matrix.  Float64 batches take the 128-column panel path
-// (LMM_PANEL128=0: the round-2 path); its W2 scratch -- one 128 x 128 inverse per panel and matrix -- lives until the API call ends.
+// Entry point of the factorisation of a batch: columns [0, NC) of every matrix (rows 0 .. NR - 1 participate; W: NC / 64 inverse
+// diagonal blocks).  plan_potrf decides what is launched; this function takes the scratch the plan asks for -- all of it lives until
+// the API call ends -- and launches the steps.
 void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t st, int rows_real = -1) {
   for (int j = 0; j < B.nb; ++j) {
     guard_extent(B.A.p[j], NR, ld, NC, true, "factorisation (factor matrix)");
     guard_extent(B.W.p[j], 64, 64, (size_t)(NC / 64) * 64, true, "factorisation (inverse diagonal blocks)");
   }
-  static int panel128 = -1;
-  if (panel128 < 0) { const char* e = getenv("LMM_PANEL128"); panel128 = e ? (atoi(e) != 0) : 1; }
-  if (g_f32 || !panel128 || NC < 128 || (ld & 1)) { potrf_rec(B, ld, NR, 0, NC, n_real, st); return; }
-  if (g_region_cols < 0) { const char* e = getenv("LMM_REGION"); g_region_cols = e ? atoi(e) : 1024; const char* ea = getenv("LMM_REGION_ALL"); g_region_whole = (ea && atoi(ea) != 0) ? 0 : 1; if (g_region_cols > 128 * LMM_REGION_MAX_PANELS) g_region_cols = 128 * LMM_REGION_MAX_PANELS; }
-  const size_t per = (size_t)(NC / 128) * 16384;
-  double* w2 = call_scratch(per * B.nb);
-  BatchPtr W2{};
-  for (int j = 0; j < B.nb; ++j) W2.p[j] = w2 + per * j;
+  const FactorSwitches& sw = factor_switches();
+  auto make_plan = [&]() { return plan_potrf(NR, NC, B.nb, rows_real, g_in_flight, device_cus(), g_f32 != 0, (ld & 1) != 0, g_strict_progress != 0, !g.emul_denied, sw); };
+  PotrfPlan P = make_plan();
+  auto per_matrix = [&](size_t doubles) {
+    BatchPtr S{};
+    double* base = call_scratch(doubles * B.nb);
+    for (int j = 0; j < B.nb; ++j) S.p[j] = base + doubles * j;
+    return S;
+  };
+  BatchPtr W2{}, asst{};
   BatchInfo flags{};
-  // Default: the region kernel serves matrices that are ONE region (NC <= 1024: the whole factorisation in one launch, the small-n
-  // path); larger matrices take the panel recursion throughout (as their base case the region kernel measured no faster than the
-  // panel launches: DESIGN.md).  LMM_REGION_ALL=1 enables it there too, LMM_REGION=0 disables it.
-  // Mid sizes / few matrices (round 3, tools/mid_probe.py): while a block column's dataflow launch -- 2 P square tasks + one per
-  // 128-row tile below, per matrix -- is at most ~2.3 workgroups per CU, it beats the panel launches it replaces (8 latents: n = 1536
-  // 1.34 -> 0.96 ms, 2048 1.97 -> 1.51, 3072 3.50 -> 2.93, 4096 5.80 -> 5.2, 8192 27.1 -> 26.5; 16 x 2048: 2.19 -> 2.01; a rank's
-  // 4-latent share of C2: 94.5 -> 93.9); with more work per launch it does not (16 x 4096: a tie; the two concurrent 16-latent batches
-  // of C2 at N = 1: 696 -> 706 ms).  LMM_REGION_ALL=1 forces it, =0 (explicit) never.
-  static int region_auto = -1, cus = 0;
-  if (region_auto < 0) { const char* ea = getenv("LMM_REGION_ALL"); region_auto = ea ? 0 : 1; }
-  if (cus == 0) { int dev = 0; cus = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
-  bool region_base = !g_region_whole;
-  if (region_auto && g_region_cols >= 1024 && NC > g_region_cols && (NC % 128) == 0) {
-    const long long tasks = 2LL * (g_region_cols / 128) + ((NR + 127) / 128 - g_region_cols / 128);      // of the first (tallest) block column
-    // (concurrent batches count together: configs[3]'s 8-latent batches at n = 8192 fit the rule one by one, but four of them in
-    // flight do not -- 724 -> 748 ms per step with the dataflow base case, the same effect as for C2's two 16-latent batches)
-    region_base = tasks * B.nb * g_slots_in_flight <= (long long)(2.3 * cus);
-  }
-  // Round 4: when the 1024-column block column is over that bound -- many matrices per launch: C2's 16-latent batches, 32 latents at
-  // n = 2048 ... 4096 -- the base case is a 512-column block column instead of the panel launches: its row chains are 10 units long
-  // instead of 36 (finer tasks for a machine that is oversubscribed many times over), the square's workgroups hold their CUs half as
-  // long, and the K = 512 update between two of them runs at 60-64 TFLOP/s.  32 x 2048: 2.98 -> 2.64 ms, 32 x 4096: 15.2 -> 14.0,
-  // 16 x 16384 on one stream: 346.8 -> 343.6, C2 at N = 1: 685.7-687.5 -> 683.1-684.2 ms (LMM_REGION_SMALL=<columns>, 0: panel launches).
-  static int region_small = -1;
-  if (region_small < 0) { const char* e = getenv("LMM_REGION_SMALL"); region_small = e ? atoi(e) : 512; if (region_small % 128) region_small = 0; if (region_small > g_region_cols) region_small = g_region_cols; }
-  int region_cols = g_region_cols;
-  if (region_auto && g_region_cols >= 1024 && NC > g_region_cols && (NC % 128) == 0 && !region_base && region_small > 0) { region_cols = region_small; region_base = true; }
-  const bool region_here = region_cols > 0 && (region_base || (NC <= region_cols && (NC % 128) == 0));
-  if (region_here) {                       // dependency flags of the region launches: this stream's slice of the persistent, once-zeroed
+  int* nflags = nullptr;
+  if (P.w2_doubles) W2 = per_matrix(P.w2_doubles);
+  if (P.region_cols > 0) {                 // dependency flags of the region launches: this stream's slice of the persistent, once-zeroed
     int si = -1;                           // array (launches are told apart by epoch); an unknown stream gets a zeroed scratch
     for (int s = 0; s < kMaxStreams; ++s) if (g.streams[s] == st) si = s;
     const size_t fi = region_flag_ints(NR);
@@ -935,60 +747,61 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
     }
     for (int j = 0; j < B.nb; ++j) flags.p[j] = fl + fi * j;
   }
-  // LMM_FUSE_BULK (default 1): the bulk rows of a panel ride in the update launch that factors its diagonal block (NODE_FUSE), behind
-  // per-call flags zeroed here; not when the region kernel serves as the base case (it solves the first panel's rows itself).
-  static int fuse_bulk = -1;
-  if (fuse_bulk < 0) { const char* e = getenv("LMM_FUSE_BULK"); fuse_bulk = e ? (atoi(e) != 0) : 1; }
-  // ... in the launches with 512 <= K <= 2048 (LMM_FUSE_BULK_MINK / _MAXK): below, the chain update -> leaf -> bulk inside one launch
-  // is no shorter than two launches (K = 128: 115 us against 72 + 34); above, the fused build's 3-4 spilled registers cost the long
-  // launches more (0.3 % of 11-30 ms) than the bulk launch they absorb (33 us)
-  constexpr int fuse_min_k = 512, fuse_max_k = 2048;
-  NodeFlags nfl;
-  nfl.min_k = fuse_min_k; nfl.max_k = fuse_max_k;
-  nfl.rows_real = rows_real;
-  nfl.region_cols = region_here ? region_cols : 0;
-  if (fuse_bulk && !g_strict_progress && !region_here && NC > 128) {
-    nfl.stride = (int)node_flag_ints(NR);
-    const size_t ints = (size_t)nfl.stride * B.nb;
-    nfl.p = reinterpret_cast<int*>(call_scratch((ints + 1) / 2));
-    HIPCHK(hipMemsetAsync(nfl.p, 0, ints * sizeof(int), st));
+  if (P.node_flag_ints) {
+    const size_t ints = P.node_flag_ints * B.nb;
+    nflags = reinterpret_cast<int*>(call_scratch((ints + 1) / 2));
+    HIPCHK(hipMemsetAsync(nflags, 0, ints * sizeof(int), st));
   }
-  if (region_here && std::min(NC, region_cols) > 64 * LMM_REGION_ASST_MIN_R) {      // block columns with assistant rows: their scratch tiles
-    const size_t per_s = (size_t)LMM_REGION_ASST_TILES * 4096;
-    double* sb = call_scratch(per_s * B.nb);
-    for (int j = 0; j < B.nb; ++j) nfl.S.p[j] = sb + per_s * j;
-  }
-  // Scratch of the emulated updates: sized for the widest emulated level of this factorisation and reused by every level; the batch
-  // goes through it in groups (emul_block_plan: at most ~12 GB; emul_group: per update).  ONE block per stream per API call (g.emul_blocks): the batches a stream
-  // factors one after the other share it (stream order keeps them apart), so an API call holds at most one block per stream it uses
-  // however many batches it has -- plus the smaller ones a stream outgrew, if its batches differ in shape.  If a block cannot be
-  // had the f64 path runs, for the rest of the call (said once per process on stderr).
-  emul_switches();
-  if (g_emul_on && !g.emul_denied) {
-    const EmulBlockPlan plan = emul_block_plan(NR, NC, B.nb, g_emul_nmod);
-    if (plan.bytes > 0) {
-      const size_t bytes = plan.bytes;
-      auto it = g.emul_blocks.find(st);
-      void* blk = (it != g.emul_blocks.end() && it->second.bytes >= bytes) ? it->second.p : nullptr;
-      if (blk == nullptr) {
-        blk = call_scratch_try(bytes);
-        if (blk != nullptr) g.emul_blocks[st] = Ctx::EmulBlock{blk, bytes};
-        else {
-          g.emul_denied = true;
-          static bool said = false;
-          if (!said) { said = true; fprintf(stderr, "lmm: no %zu-byte scratch for the int8-emulated updates: they run on the f64 kernel\n", bytes); }
-        }
+  if (P.asst_doubles) asst = per_matrix(P.asst_doubles);
+  // Scratch of the emulated updates: ONE block per stream per API call (g.emul_blocks): the batches a stream factors one after the
+  // other share it (stream order keeps them apart), so an API call holds at most one block per stream it uses however many batches it
+  // has -- plus the smaller ones a stream outgrew, if its batches differ in shape.  If a block cannot be had the f64 path runs, for the
+  // rest of the call (said once per process on stderr).
+  void* emul_blk = nullptr;
+  if (P.emul_bytes > 0) {
+    auto it = g.emul_blocks.find(st);
+    emul_blk = (it != g.emul_blocks.end() && it->second.bytes >= P.emul_bytes) ? it->second.p : nullptr;
+    if (emul_blk == nullptr) {
+      emul_blk = call_scratch_try(P.emul_bytes);
+      if (emul_blk != nullptr) g.emul_blocks[st] = Ctx::EmulBlock{emul_blk, P.emul_bytes};
+      else {
+        g.emul_denied = true;
+        static bool said = false;
+        if (!said) { said = true; fprintf(stderr, "lmm: no %zu-byte scratch for the int8-emulated updates: they run on the f64 kernel\n", P.emul_bytes); }
+        P = make_plan();
       }
-      if (blk != nullptr) { nfl.emul = blk; nfl.emul_plan = plan; nfl.emul_nmod = g_emul_nmod; }
     }
   }
-  potrf_rec_panel(B, W2, flags, nfl, ld, NR, 0, NC, n_real, st, false);
+  auto leaf128 = [&](int c) { launch_leaf128(B.A, (size_t)c * ld + c, ld, B.W, (size_t)(c / 64) * 4096, W2, (size_t)(c / 128) * 16384, c, n_real, B.info, B.nb, st); };
+  for (const PotrfStep& s : P.steps) {
+    const bool named = s.named();
+    ProfScope ps(s.cls, s.work, st, named ? s.M : 0, named ? s.N : 0, named ? s.h : 0, s.bytes);
+    const int j0 = s.j0, r0 = s.j0 + s.h;
+    const size_t offW = (size_t)(j0 / 64) * 4096, offA = (size_t)j0 * ld + r0;      // the inverse block at j0; the rows from r0 of the columns from j0
+    switch (s.kind) {
+      case POTRF_DIAG64: launch_diag64(B.A, (size_t)j0 * ld + j0, ld, B.W, offW, j0, n_real, B.info, B.nb, st); break;
+      case POTRF_SOLVE64: launch_gemm_nt(B.A, offA, ld, B.A, offA, ld, B.W, offW, 64, s.M, 64, 64, 0, true, B.nb, st); break;
+      case POTRF_UPDATE: launch_gemm_nt(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, B.A, offA, ld, s.M, s.N, s.h, 1, false, B.nb, st); break;
+      case POTRF_LEAF128: leaf128(j0); break;
+      case POTRF_PANEL_BULK: launch_panel_bulk(B.A, W2, ld, NR, j0, B.nb, st); break;
+      case POTRF_UPDATE_LEAF:
+        launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, s.h, s.N, n_real, B.nb, st, s.strip, s.fused_bulk ? nflags : nullptr, (int)P.node_flag_ints);
+        break;
+      case POTRF_EMUL_UPDATE_LEAF:
+        if (s.scratch > P.emul_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", s.scratch, P.emul_bytes);
+        guard_extent(emul_blk, s.scratch / 8, s.scratch / 8, 1, false, "emulated update (scratch)");
+        HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, st));
+        leaf128(r0);
+        break;
+      case POTRF_REGION: launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst); break;
+    }
+  }
 }
 
-void potrf_rec(double* A, int ld, int NR, int j0, int w, double* W, int n_real, int* info, hipStream_t st) {
+// One matrix: the batch of one
+void potrf_one(double* A, int ld, int NR, int NC, double* W, int n_real, int* info, hipStream_t st) {
   Batch B; B.add(A, W, info);
-  if (j0 == 0) potrf_batch(B, ld, NR, w, n_real, st);
-  else potrf_rec(B, ld, NR, j0, w, n_real, st);
+  potrf_batch(B, ld, NR, NC, n_real, st);
 }
 
 // R (nr x NC, ldr) <- R * L^-T for an already factored L (ld) with inverse diagonal blocks W.
@@ -1085,11 +898,10 @@ void batch_plan(int ms, int* nb_per, int* nstreams_used, double bytes_per_latent
       for (const auto& kv : g.pool) avail += (double)kv.first;
       const double budget = 0.8 * avail;
       // + one scratch block of the emulated updates per stream (potrf_batch: at most ~12 GB each), for working sets whose matrices
-      // have an emulated level at the batch size the plan starts from (emul_need: the question potrf_batch asks; the shape is the
+      // have an emulated level at the batch size the plan starts from (emul_view: the plan potrf_batch makes; the shape is the
       // square one of this working set, n = sqrt(bytes / 8) rounded up to whole panels, with one 64-row block of riders)
-      emul_switches();
       const int nce = (int)rup((size_t)std::sqrt(bytes_per_latent / 8.0), 128);
-      const double per_stream = (g_emul_on && !g_f32 && emul_need(nce + 64, nce, b, 1, g_emul_nmod) > 0) ? 12e9 : 0.0;
+      const double per_stream = (!g_f32 && emul_view(nce + 64, nce, b).emul_bytes > 0) ? 12e9 : 0.0;
       while ((double)b * ns * bytes_per_latent + ns * per_stream > budget && (b > 1 || ns > 1)) {
         if (b > 1) b = (b + 1) / 2; else --ns;
         nbatches = (ms + b - 1) / b;
@@ -1121,7 +933,7 @@ void make_slots(std::vector<Slot>& slots, int count, int nb_per, size_t a_elems,
 }
 
 void fork_slots(int count) {       // slot streams wait for everything queued on the main stream
-  g_slots_in_flight = count > 1 ? count : 1; g_concurrent_batches = g_slots_in_flight;
+  g_in_flight = count > 1 ? count : 1;
   if (count <= 1) return;          // (one slot = the main stream itself: no event -- a recorded event is a marker packet the queue
                                    // takes microseconds to retire, in front of a small problem's Gram launch)
   HIPCHK(hipEventRecord(g.ev_main, g.streams[0]));
@@ -1129,7 +941,7 @@ void fork_slots(int count) {       // slot streams wait for everything queued on
 }
 
 void join_slots(int count) {       // main stream waits for every slot stream
-  g_slots_in_flight = 1; g_concurrent_batches = 1;
+  g_in_flight = 1;
   for (int s = 1; s < count; ++s) {
     HIPCHK(hipEventRecord(g.ev_slot[s], g.streams[s]));
     HIPCHK(hipStreamWaitEvent(g.streams[0], g.ev_slot[s], 0));
@@ -1157,7 +969,7 @@ struct FanOut {
   void run(Body&& body) {
     struct Scope {               // the "several batches in flight" state must not outlive the loop, whichever way it is left
       explicit Scope(int count) { fork_slots(count); }
-      ~Scope() { g_slots_in_flight = 1; g_concurrent_batches = 1; }
+      ~Scope() { g_in_flight = 1; }
     } scope(nslots);
     int bi = 0;
     for (int k0 = 0; k0 < ms; k0 += nb_per, ++bi) {
@@ -1455,7 +1267,7 @@ void drain_after_error() {
   if (g.init) { (void)hipDeviceSynchronize(); (void)hipGetLastError(); }
   // a throw between fork_slots and join_slots must not leave "several batches in flight" behind: the base-case rule of potrf_batch
   // and the ragged-row choice of the update launches read these, so later calls would silently take another launch plan
-  g_slots_in_flight = 1; g_concurrent_batches = 1;
+  g_in_flight = 1;
   if (g.init) strict_ticket_reset();
 }
 
@@ -2632,7 +2444,7 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd.p; a.d = d; a.n = n; a.m = m;
   a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = 1; a.has_sum = ls->any_sum();
   launch_dense_assemble(a, st0);
-  potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
+  potrf_one(A.p, D.ld, D.NR, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, 1, lml_dev.p, st0);
   double lml = 0.0, resid = 0.0;
   int hinfo = 0;
@@ -2692,7 +2504,7 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd.p; a.d = d; a.n = n; a.m = m;
   a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = ncol; a.has_sum = ls->any_sum();
   launch_dense_assemble(a, st0);
-  potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
+  potrf_one(A.p, D.ld, D.NR, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, ncol, lml_dev.p, st0);
   std::vector<double> lml(ncol), resid(ncol);
   int hinfo = 0;
@@ -2793,7 +2605,7 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   a.lat = latd.p; a.sigmaT = STd.buf.p; a.sig_idx = nblk > 1 ? sidxd.p : nullptr; a.rider = delta.p; a.rider_ld = N; a.nrider = 1;
   a.has_sum = ls->any_sum();
   launch_dense_assemble(a, st0);
-  potrf_rec(A.p, D.ld, D.NR, 0, D.NC, W.p, N, info.p, st0);
+  potrf_one(A.p, D.ld, D.NR, D.NC, W.p, N, info.p, st0);
   launch_lml_reduce(A.p, D.ld, N, D.NC, 1, lml_dev.p, st0);
   launch_extract_row(A.p, D.ld, D.NC, N, alpha.p, st0);
   backsolve1(A.p, D.ld, W.p, D.NC / 64, alpha.p, st0);
@@ -3587,7 +3399,7 @@ static int dense_posterior_build(const double* xd, int d, int n, const double* H
     a.lat = P->latd.p; a.sigmaT = STd.buf.p; a.sig_idx = idxd.p; a.rider = P->ddelta.p; a.rider_ld = N; a.nrider = 1;
     a.has_sum = P->ls->any_sum();
     launch_dense_assemble(a, st0);
-    potrf_rec(P->L[0].p, D.ld, D.NR, 0, D.NC, P->W[0].p, N, info.p, st0);
+    potrf_one(P->L[0].p, D.ld, D.NR, D.NC, P->W[0].p, N, info.p, st0);
     HIPCHK(hipMemsetAsync(P->alpha[0].p, 0, (size_t)D.NC * sizeof(double), st0));
     launch_extract_row(P->L[0].p, D.ld, D.NC, N, P->alpha[0].p, st0);
     HIPCHK(hipMemcpyAsync(P->z[0].p, P->alpha[0].p, (size_t)D.NC * sizeof(double), hipMemcpyDeviceToDevice, st0));
@@ -3741,7 +3553,7 @@ static void dense_post_cov_factor(const lmm_post* P, const double* xsd, int d, i
   guard_extent(A, Ds.NR, Ds.ld, Ds.NC, true, "dense-H posterior covariance");
   launch_dense_assemble(a, st);
   gemm_nt_g(A, Ds.ld, R, ldr, R, ldr, Ds.NC, Ds.NC, P->NC, 1, false, st, "Schur complement (dense-H posterior covariance)");
-  if (factor) potrf_rec(A, Ds.ld, Ds.NR, 0, Ds.NC, WA, m * ns, info, st);
+  if (factor) potrf_one(A, Ds.ld, Ds.NR, Ds.NC, WA, m * ns, info, st);
 }
 
 // mean_and_cov(pi(xs, sigma2)) / cov on the dense-H posterior ILMM (reference src/ilmm.jl:132-147 with the PosteriorGP latent
@@ -4171,7 +3983,7 @@ static void cross_solve(const lmm_post* P, int k, const Latent& gp, const double
 }
 
 // Per-latent posterior (or prior) covariance at xs as a factor matrix B (NRs x NCs): gram(xs) + diag_add - R R' (posterior,
-// R from cross_solve), rider row = rider_vec.  Not factorised here (the caller batches potrf_rec).  Caller holds g_mu.
+// R from cross_solve), rider row = rider_vec.  Not factorised here (the caller batches potrf_batch).  Caller holds g_mu.
 static GramArgs cov_args(const Latent& gp, const double* xsd, int d, int ns, double diag_add, const double* rider_vec,
                          const Dims& Ds, double* B) {
   GramArgs a{};
@@ -5709,7 +5521,7 @@ int lmm_dev_potrf(double* A, int nrows, int ncols, int ld, double* Winv, int n_r
   LMM_TRY
   if (!A || !Winv || !info_dev || nrows % 64 || ncols % 64 || nrows < ncols || ld < nrows || (ld & 1))
     return fail(LMM_ERR_ARG, "bad arguments");
-  potrf_rec(A, ld, nrows, 0, ncols, Winv, n_real, info_dev, g.streams[0]);
+  potrf_one(A, ld, nrows, ncols, Winv, n_real, info_dev, g.streams[0]);
   int hinfo = 0;
   HIPCHK(hipMemcpyAsync(&hinfo, info_dev, sizeof(int), hipMemcpyDeviceToHost, g.streams[0]));
   HIPCHK(hipStreamSynchronize(g.streams[0]));
@@ -5761,49 +5573,62 @@ int lmm_dev_check_info(const int* info, int count, int latent_begin) {
 // Test hook of the emulation switches (the env values are read once): on < 0 goes back to the env defaults.
 int lmm_dev_set_f64_emul(int on, int min_k, int nmod) {
   std::lock_guard<std::mutex> lk(g_mu);
-  if (on < 0) { g_emul_on = -1; g_emul_mink = -1; g_emul_nmod = LMM_EMUL_MAXMOD; return LMM_OK; }
+  if (on < 0) { g_switches.emul_on = -1; g_switches.emul_mink = -1; g_switches.emul_nmod = LMM_EMUL_MAXMOD; return LMM_OK; }
   if (min_k < 128 || nmod < LMM_EMUL_MINMOD || nmod > LMM_EMUL_MAXMOD) return fail(LMM_ERR_ARG, "lmm_dev_set_f64_emul: min_k >= 128, %d <= nmod <= %d", LMM_EMUL_MINMOD, LMM_EMUL_MAXMOD);
-  g_emul_on = on ? 1 : 0; g_emul_mink = min_k; g_emul_nmod = nmod;
+  g_switches.emul_on = on ? 1 : 0; g_switches.emul_mink = min_k; g_switches.emul_nmod = nmod;
   return LMM_OK;
 }
 // Test hook of the shape rule that decides when nothing explicit is set (emul_pays): updates with K >= min_k_always are emulated, those
 // with min_k_shape <= K < min_k_always when nb * outputs >= min_outputs; min_k_always < 0 goes back to the defaults.
 int lmm_dev_set_f64_emul_rule(int min_k_always, int min_k_shape, double min_outputs) {
   g.err.clear();
-  if (min_k_always < 0) { g_rule_always = kRuleAlways; g_rule_shape = kRuleShape; g_rule_outs = kRuleOuts; return LMM_OK; }
+  if (min_k_always < 0) { g_switches.rule_always = kRuleAlways; g_switches.rule_shape = kRuleShape; g_switches.rule_outs = kRuleOuts; return LMM_OK; }
   if (min_k_shape < 128 || min_k_always < min_k_shape || !(min_outputs >= 0.0)) return fail(LMM_ERR_ARG, "lmm_dev_set_f64_emul_rule: 128 <= min_k_shape <= min_k_always, min_outputs >= 0");
-  g_rule_always = min_k_always; g_rule_shape = min_k_shape; g_rule_outs = min_outputs;
+  g_switches.rule_always = min_k_always; g_switches.rule_shape = min_k_shape; g_switches.rule_outs = min_outputs;
   return LMM_OK;
 }
 // Test hook: at most g matrices per group of an emulated update (0: as many as the scratch block holds).  Results do not depend on it.
 int lmm_dev_set_emul_group(int gcap) {
   g.err.clear();
   if (gcap < 0) return fail(LMM_ERR_ARG, "lmm_dev_set_emul_group: g >= 0");
-  g_emul_group_cap = gcap;
+  g_switches.emul_group_cap = gcap;
   return LMM_OK;
 }
-// Host-only (no GPU, no lmm_init needed): what potrf_batch would do with nb matrices of NR rows and NC columns -- the same walk, the
-// same predicate, the same sizing.  out[0] = bytes of the scratch block it asks for (0: nothing is emulated), out[1] = the G that block
-// is sized for; then 6 words per trailing update with at least 128 columns, in launch order: M, N, K, emulated (0 / 1), matrices per
-// group, scratch bytes at that group size (0, 0 when not emulated).  Returns the number of updates (records beyond cap are counted,
-// not written), or -LMM_ERR_ARG.
+// Host-only (no GPU, no lmm_init needed): the emulation side of the plan potrf_batch makes for nb matrices of NR rows and NC columns.
+// out[0] = bytes of the scratch block it asks for (0: nothing is emulated), out[1] = the G that block is sized for; then 6 words per
+// trailing update with at least 128 columns, in launch order: M, N, K, emulated (0 / 1), matrices per group, scratch bytes at that
+// group size (0, 0 when not emulated).  Returns the number of updates (records beyond cap are counted, not written), or -LMM_ERR_ARG.
 int lmm_dev_emul_plan(int NR, int NC, int nb, long long* out, int cap) {
   g.err.clear();
   if (!out || cap < 0 || nb < 1 || nb > LMM_MAX_BATCH || NC < 128 || (NC % 64) != 0 || NR < NC) return -fail(LMM_ERR_ARG, "lmm_dev_emul_plan: bad arguments");
-  emul_switches();
-  const EmulBlockPlan P = g_emul_on ? emul_block_plan(NR, NC, nb, g_emul_nmod) : EmulBlockPlan{};
-  out[0] = (long long)P.bytes; out[1] = P.G;
-  int count = 0;
-  emul_walk(NR, 0, NC, [&](int M, int N, int K) {
-    if (count < cap) {
-      long long* r = out + 2 + 6 * (size_t)count;
-      const bool em = P.bytes > 0 && emul_takes(M, N, K, nb);
-      const int gs = em ? emul_group(M, N, K, nb, P, g_emul_nmod) : 0;
-      r[0] = M; r[1] = N; r[2] = K; r[3] = em; r[4] = gs; r[5] = em ? (long long)emul_scratch_bytes(M, N, K, gs, g_emul_nmod) : 0;
-    }
-    ++count;
-  });
-  return count;
+  const PotrfPlan P = emul_view(NR, NC, nb);
+  out[0] = (long long)P.emul_bytes; out[1] = P.emul_G;
+  for (size_t i = 0; i < P.updates.size() && i < (size_t)cap; ++i) {
+    const PotrfUpdate& u = P.updates[i];
+    long long* r = out + 2 + 6 * i;
+    r[0] = u.M; r[1] = u.N; r[2] = u.K; r[3] = u.emulated; r[4] = u.group; r[5] = (long long)u.scratch;
+  }
+  return (int)P.updates.size();
+}
+// Host-only (no GPU, no lmm_init needed): what potrf_batch launches for nb matrices of NR rows and NC columns (rows_real of them holding
+// data, -1: all) with in_flight batches running side by side on a device of cus CUs, in the compute dtype f32 != 0 / Float64, with
+// strict progress on or off, under the current switches.  The layout of out is documented in include/lmm_hip.h.
+int lmm_dev_potrf_plan(int NR, int NC, int nb, int rows_real, int in_flight, int cus, int f32, int strict, long long* out, int cap) {
+  g.err.clear();
+  if (!out || cap < 0 || nb < 1 || nb > LMM_MAX_BATCH || NC < 64 || (NC % 64) != 0 || (NR % 64) != 0 || NR < NC || rows_real > NR || rows_real < -1 ||
+      (rows_real >= 0 && rows_real < NC) || in_flight < 1 || cus < 1)
+    return -fail(LMM_ERR_ARG, "lmm_dev_potrf_plan: bad arguments");
+  const PotrfPlan P = plan_potrf(NR, NC, nb, rows_real, in_flight, cus, f32 != 0, false, strict != 0, true, factor_switches());
+  out[0] = P.panel128; out[1] = P.region_cols; out[2] = (long long)P.w2_doubles; out[3] = (long long)P.node_flag_ints;
+  out[4] = (long long)P.asst_doubles; out[5] = (long long)P.emul_bytes; out[6] = P.emul_G; out[7] = P.emul_nmod;
+  for (size_t i = 0; i < P.steps.size() && i < (size_t)cap; ++i) {
+    const PotrfStep& s = P.steps[i];
+    long long* r = out + LMM_POTRF_PLAN_HEADER + LMM_POTRF_PLAN_STEP * i;
+    r[0] = s.kind; r[1] = s.j0; r[2] = s.h; r[3] = s.N; r[4] = s.M; r[5] = s.cls; r[6] = s.named();
+    memcpy(&r[7], &s.work, 8); memcpy(&r[8], &s.bytes, 8);
+    r[9] = s.first_done; r[10] = s.fused_bulk; r[11] = s.strip; r[12] = s.group; r[13] = (long long)s.scratch;
+  }
+  return (int)P.steps.size();
 }
 // Test hook: at most wgs workgroups in the persistent grid of the emulation's GEMM (0: the default, one per CU), so that a small shape
 // makes one workgroup walk several tiles.

@@ -65,6 +65,27 @@ inline int emul_bits(int nmod, long long K) {
   return b;
 }
 
+// Shapes the emulation takes, and the scratch one update needs: host arithmetic shared by the launcher (lmm_kernels_i8.hip) and the
+// factorisation's planner (lmm_potrf_plan.h).  M x N outputs (M >= N) of depth K in 256 x 256 tiles; int32 accumulators: K 128^2 <= 2^28.
+#define LMM_EMUL_TILE 256
+inline bool emul_shape_ok(int M, int N, int K) { return M >= N && N >= 1 && K >= 128 && K % 128 == 0 && K <= 16384; }
+// byte offsets in the scratch of G matrices going through it together: residues of the panel, of the product, row maxima, scales, exponents
+struct EmulLayout { size_t R, U, amax, sc, ex, total; int Mp, Np; };
+inline EmulLayout emul_layout(int M, int N, int K, int G, int nmod) {
+  auto rup256 = [](size_t v) { return (v + 255) & ~size_t(255); };
+  EmulLayout L{};
+  L.Mp = (M + LMM_EMUL_TILE - 1) / LMM_EMUL_TILE * LMM_EMUL_TILE; L.Np = (N + LMM_EMUL_TILE - 1) / LMM_EMUL_TILE * LMM_EMUL_TILE;
+  size_t o = 0;
+  L.R = o; o += rup256((size_t)G * nmod * L.Mp * K);
+  L.U = o; o += rup256((size_t)G * nmod * L.Np * L.Mp);
+  L.amax = o; o += rup256((size_t)G * L.Mp * 8);
+  L.sc = o; o += rup256((size_t)G * L.Mp * 8);
+  L.ex = o; o += rup256((size_t)G * L.Mp * 4);
+  L.total = o;
+  return L;
+}
+inline size_t emul_scratch_bytes(int M, int N, int K, int G, int nmod) { return emul_layout(M, N, K, G, nmod).total; }
+
 // ceil(log2 amax) for a finite amax > 0
 LMM_HD inline int emul_row_exp(double amax) {
   int q;

@@ -2,6 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/lmm_hip.h"
+#include "lmm_potrf_plan.h"
+// the planner names the profile classes without seeing lmm_hip.h
+static_assert((int)POTRF_CLS_UPDATE == LMM_PROF_UPDATE && (int)POTRF_CLS_UPDATE_NARROW == LMM_PROF_UPDATE_NARROW && (int)POTRF_CLS_TRSM == LMM_PROF_TRSM &&
+              (int)POTRF_CLS_DIAG == LMM_PROF_DIAG && (int)POTRF_CLS_REGION == LMM_PROF_REGION && (int)POTRF_CLS_UPDATE_SHORT == LMM_PROF_UPDATE_SHORT,
+              "the POTRF_CLS_* values of lmm_potrf_plan.h are lmm_prof_class values");
 
 extern int g_f32;              // compute dtype of the matrices: 0 = Float64, 1 = Float32 (lmm_kernels.hip)
 #define LMM_MAX_BATCH 32
@@ -126,44 +131,41 @@ struct RegionArgs {
 extern int g_strict_progress;
 extern int g_claim_scramble;              // test hook: see RegionArgs.claim_scramble
 void strict_ticket_reset();               // drop the claim counters (after an error drained the device; at shutdown)
-#define LMM_REGION_MAX_PANELS 8
-#define LMM_REGION_ASST_MIN_C 4           // a helper's product for column block c >= this is split with its row's assistant
-#define LMM_REGION_ASST_MIN_R (LMM_REGION_ASST_MIN_C + 2)
+// (LMM_REGION_MAX_PANELS, LMM_REGION_ASST_MIN_C / _MIN_R / _TILES: lmm_potrf_plan.h)
 // the assistant of a row takes the blocks [0, LMM_REGION_ASST_SPLIT(c)) of the helper's K-long product for column block c.  Round 3:
 // c / 2; round 4: 3 c / 4 -- once the chain's hand-offs got cheaper (sc1 loads instead of acquire fences) the helpers of rows >= 9 were
 // again the slower side of the walker <-> helper cycle (walker waits of 3-10 us at n = 1024), and what a helper does per column AFTER
 // W_c arrives cannot shrink, so the part before it must: the blocks [0, 3 c / 4) are final c / 4 - 1 block periods before they are needed.
 #define LMM_REGION_ASST_SPLIT(c) ((3 * (c)) / 4)
-#define LMM_REGION_ASST_TILES ((2 * LMM_REGION_MAX_PANELS - LMM_REGION_ASST_MIN_R) * 16)
 // Bound of every dependency spin of the dataflow kernels, in ticks of the 100 MHz wall clock (4 s).  The deadlock argument (a workgroup
 // only waits for workgroups dispatched before it, the walker excepted) covers one launch on an otherwise free device; kernels of other
 // streams holding CUs or a serialising profiler can delay the one later-dispatched workgroup a walker waits for, hence seconds, not ms.
 #define LMM_REGION_SPIN_TICKS 400000000LL
 #define LMM_INFO_SYNC_TIMEOUT (-7777)     // pivot-info value a region launch leaves when a dependency wait timed out (never expected)
 void region_flags_register(int* base, size_t ints);     // the context's persistent flag array (cleared when the launch epoch wraps)
-extern int g_concurrent_batches;          // batches in flight on the slot streams (set by lmm_api.hip's fork_slots / join_slots)
+int device_cus();                         // compute units of the current device (256 when it cannot be asked); read once
+extern FactorSwitches g_switches;         // the factorisation's knobs; the lmm_dev_set_* hooks write it, everything else reads it through ...
+const FactorSwitches& factor_switches();  // ... which fills it from the environment at its first call
 void region_plan_probe(int P, int nb, int Mb, int Mb_real, int cus, int na_full, int out[3]);   // lmm_dev_region_plan
 int region_flag_epoch(int set_to);                       // lmm_dev_flag_epoch: returns the current launch epoch; set_to >= 0 replaces it
 size_t region_flag_ints(int NR);          // ints per matrix that the flags of any region of a matrix with NR rows need
 void launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, const BatchInfo& flags, int ld, int NR,
                    int c0, int width, int n_real, int nb, bool first_done, hipStream_t st, int rows_real = -1, const BatchPtr* S = nullptr);
-// plain trailing update (no leaf) through the node kernel: C -= A B' for the region at j0 + h
 void launch_leaf128(const BatchPtr& A, size_t offD, int ld, const BatchPtr& W, size_t offW, const BatchPtr& W2, size_t offW2,
                     int gcol0, int n_real, const BatchInfo& info, int nb, hipStream_t st);
 // bulk rows of the panel at column r0 (its diagonal block factored, its inverse in W2): X = P Dinv' in place
 void launch_panel_bulk(const BatchPtr& A, const BatchPtr& W2, int ld, int NR, int r0, int nb, hipStream_t st);
 // C -= A B' for the region at r0 = j0 + h (N columns, multiple of 128) + leaf128 on its top-left block
-// nflags != nullptr: also the bulk rows of that panel, in the same launch (NODE_FUSE); returns true when it did
-bool launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, int ld, int NR, int j0, int h,
-                        int N, int n_real, int nb, hipStream_t st, int* nflags = nullptr, int nf_stride = 0);
-size_t node_flag_ints(int NR);            // ints per matrix of the NODE_FUSE flags of a matrix with NR rows
+// strip (POTRF_STRIP_*): where the plan puts a ragged last 64 rows; nflags != nullptr (the plan's fused_bulk): also the bulk rows of that
+// panel, in the same launch (NODE_FUSE, flags of nf_stride ints per matrix)
+void launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, int ld, int NR, int j0, int h,
+                        int N, int n_real, int nb, hipStream_t st, int strip, int* nflags = nullptr, int nf_stride = 0);
 // lmm_kernels_f32w.hip: fp32 C -= A B' on 256 x 256 tiles (one workgroup per CU); false: not launched (shape / switch), use the 128-tile kernel
 bool launch_gemm32w(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B, size_t offB, int ldb,
                     int M, int N, int K, int lower, int nb, int cus, bool deterministic, hipStream_t st);
 // lmm_kernels_i8.hip: Float64 C_m -= P_m P_m[0:N]' (C_m at C.p[m] + offC, the M x K panel P_m at P.p[m] + offP; lower trapezoid, i >= j) as exact int8 modular GEMMs.  emul_shape_ok:
 // M >= N, K a multiple of 128 within the int32 accumulator bound.  Matrices go through `scratch` (emul_scratch_bytes) in groups of G.
-bool emul_shape_ok(int M, int N, int K);
-size_t emul_scratch_bytes(int M, int N, int K, int G, int nmod);
+// (emul_shape_ok, emul_scratch_bytes: lmm_emul.h)
 void emul_set_gemm_workgroups(int wgs);      // cap of the persistent GEMM grid (tests); 0: one workgroup per CU
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
                               int G, int nmod, void* scratch, hipStream_t st);      // the first HIP error of its host-side calls

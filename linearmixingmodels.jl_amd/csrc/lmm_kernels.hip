@@ -5254,36 +5254,59 @@ int region_flag_epoch(int set_to) {
   if (set_to >= 0) g_region_epoch = set_to;
   return old;
 }
-int g_concurrent_batches = 1;        // batches in flight on the slot streams (lmm_api.hip's fork_slots)
-size_t node_flag_ints(int NR) { return (size_t)(2 + (NR + 127) / 128 + 1); }
-bool launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, int ld, int NR, int j0, int h,
-                        int N, int n_real, int nb, hipStream_t st, int* nflags, int nf_stride) {
+int device_cus() {
+  static int cus = 0;
+  if (cus == 0) { int dev = 0; cus = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
+  return cus;
+}
+// The factorisation's knobs (FactorSwitches, lmm_potrf_plan.h): the environment is read here, once and all of it together -- at the first
+// call, whether a launch, potrf_batch or a host-only plan hook asks, not at load time; a variable set after that is not seen (the statics
+// this replaces read each value at its own first use).  The two emulation values are read again after lmm_dev_set_f64_emul(-1, ..) put them back to "unread".
+FactorSwitches g_switches;
+const FactorSwitches& factor_switches() {
+  auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+  static bool read = false;
+  if (!read) {
+    read = true;
+    g_switches.panel128 = num("LMM_PANEL128", 1) != 0;
+    g_switches.region = std::min(num("LMM_REGION", 1024), 128 * LMM_REGION_MAX_PANELS);
+    const char* all = getenv("LMM_REGION_ALL");
+    g_switches.region_all = !all ? LMM_REGION_BY_RULE : atoi(all) != 0 ? LMM_REGION_EVERYWHERE : LMM_REGION_NEVER;
+    g_switches.region_small = num("LMM_REGION_SMALL", 512);
+    if (g_switches.region_small % 128) g_switches.region_small = 0;
+    g_switches.region_small = std::min(g_switches.region_small, g_switches.region);
+    g_switches.fuse_bulk = num("LMM_FUSE_BULK", 1) != 0;
+    g_switches.strip_items = num("LMM_STRIP_ITEMS", 1);
+    g_switches.deterministic = num("LMM_DETERMINISTIC", 0) != 0;
+    g_switches.region_asst = num("LMM_REGION_ASST", 1);
+    g_switches.region_occ = num("LMM_REGION_OCC", 0);
+    g_switches.region_th = num("LMM_REGION_TH", 0);
+    g_switches.region_trace = num("LMM_REGION_TRACE", 0);
+  }
+  if (g_switches.emul_on < 0) g_switches.emul_on = num("LMM_F64_EMUL", 1) != 0;
+  if (g_switches.emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_switches.emul_mink = e ? std::max(128, atoi(e)) : 0; }
+  return g_switches;
+}
+void launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, int ld, int NR, int j0, int h,
+                        int N, int n_real, int nb, hipStream_t st, int strip_mode, int* nflags, int nf_stride) {
   const int r0 = j0 + h, NT = (N + 127) / 128;     // N may end in a 64-column half tile
-  if (nb <= 0 || N <= 0 || h <= 0) return false;
+  if (nb <= 0 || N <= 0 || h <= 0) return;
   node_lds_attr();
-  // ragged last row tile (the rider rows make the row count an odd multiple of 64): on the long products the node kernel takes the
-  // full 128-row tiles and gemm16h_kernel the last 64 rows, as in launch_gemm_nt (two idle waves for a whole tile time otherwise)
+  // ragged last row tile (lmm_potrf_plan.h): the node kernel takes the full 128-row tiles and gemm16h_kernel the last 64 rows
   int M = NR - r0;
-  const bool strip = (M % 128) == 64 && M - 64 >= N && (N % 128) == 0 && h >= 1024;
+  const bool strip = strip_mode != POTRF_STRIP_NONE, strip_in = strip_mode == POTRF_STRIP_IN_LAUNCH;
   const int Mfull = M;
   if (strip) M -= 64;
   const int MT = (M + 127) / 128;
   const int MTb = (Mfull + 127) / 128;
   // the ragged rows first when the bulk tiles ride along: they cover those rows too (the two launches touch disjoint entries)
-  const bool fuse = nflags != nullptr && N >= 128 && MTb > 1;
+  const bool fuse = nflags != nullptr;
   auto launch_strip = [&]() {
     const size_t offA = (size_t)j0 * ld + r0 + (size_t)M;
     hipLaunchKernelGGL((gemm16h_kernel<true>), dim3(N / 128, nb), dim3(256), 0, st, A, (size_t)r0 * ld + r0 + (size_t)M, ld, A, offA, ld,
                        A, (size_t)j0 * ld + r0, ld, N, h, 0);
   };
-  static int strip_items = -1;                     // LMM_STRIP_ITEMS=0: the ragged rows as a separate launch (the round-2/3 form)
-  if (strip_items < 0) { const char* e = getenv("LMM_STRIP_ITEMS"); strip_items = e ? atoi(e) : 1; }
-  // ... and only while no other batch runs beside this one: with two batches in flight (C2 at N = 1) the other stream's kernels fill the
-  // CUs a separate strip launch leaves idle, and the in-launch items measured slower (687.2 -> 689.9 ms per step)
-  const bool strip_in = strip && strip_items && (g_concurrent_batches <= 1 || strip_items == 2);
   if (strip && !strip_in && fuse) launch_strip();
-  static int cus = 0;
-  if (cus == 0) { int dev = 0; cus = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
   long long T = 0;                                            // tiles of the column tiles 1 .. NT-1 (lower trapezoid)
   for (int tj = 1; tj < NT; ++tj) T += MT - tj;
   // Split-K tail.  The matrices of the batch run back to back (the next matrix's tiles fill the CUs as the previous one's drain), so
@@ -5291,9 +5314,8 @@ bool launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2
   // (two per CU).  (a) a launch that does not even fill half of that is split uniformly; (b) otherwise the LAST cap / s tiles of
   // the last matrix are split s ways, so that the final cap work items are short (drain ~ a tile time / s) and nothing else pays
   // for atomics.  LMM_DETERMINISTIC=1: no split (bitwise reproducible sums).
-  const int cap = 2 * cus, nk = h / 16;
-  static int deterministic = -1;
-  if (deterministic < 0) { const char* e = getenv("LMM_DETERMINISTIC"); deterministic = (e && atoi(e) != 0) ? 1 : 0; }
+  const int cap = 2 * device_cus(), nk = h / 16;
+  const int deterministic = factor_switches().deterministic;
   int full_a = (int)T, split_a = 1, full_l = (int)T, split_l = 1;
   if (!deterministic && T > 0 && nk >= 8) {
     const long long all = (long long)nb * T + (long long)nb * MT;
@@ -5338,7 +5360,6 @@ bool launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2
     else hipLaunchKernelGGL(potrf_node_kernel<1>, grid, dim3(256), LEAF_LDS_DOUBLES * 8, st, a);
   }
   if (strip && !strip_in && !fuse) launch_strip();
-  return fuse;
 }
 
 // Plan of a region launch's row tasks.  One workgroup per row tile, dispatched in order behind the square's workgroups, one per CU:
@@ -5418,18 +5439,14 @@ void launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, con
   a.epoch = next_flag_epoch(); a.first_done = first_done ? 1 : 0;
   a.M_real = (rows_real >= 0 && rows_real <= NR) ? rows_real - c0 : M;
   // assistants (LMM_REGION_ASST=0 disables them): one per square row from LMM_REGION_ASST_MIN_R on, when the caller gave scratch
-  static int asst_env = -1;
-  if (asst_env < 0) { const char* e = getenv("LMM_REGION_ASST"); asst_env = e ? atoi(e) : 1; }       // 2: also when they are not resident from the start (measured slower)
-  static int cus = 0;
-  if (cus == 0) { int dev = 0; cus = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
+  const FactorSwitches& sw = factor_switches();
+  const int asst_env = sw.region_asst, occ_env = sw.region_occ, th_env = sw.region_th, trace_env = sw.region_trace, cus = device_cus();
   a.na = (asst_env && S != nullptr && S->p[0] != nullptr && 2 * P > LMM_REGION_ASST_MIN_R) ? 2 * P - LMM_REGION_ASST_MIN_R : 0;
   // ... and only while the launch with them still fits one workgroup per CU: pushed into the two-per-CU build (where the walker spills)
   // they cost more than they bring (8 latents, n = 2048: 1.60 -> 1.87 ms)
   // Row tiles that take the thin stream (or hold padding only) need not be resident from the start: they wait for the square, never
   // the square for them, and catch up within a panel's time.  What must fit one workgroup per CU for that build: square + full rows.
   // LMM_REGION_OCC=1 / 2 forces a build; default: one workgroup per CU (414 registers per lane, no spills in the walker)
-  static int occ_env = -1;
-  if (occ_env < 0) { const char* e = getenv("LMM_REGION_OCC"); occ_env = e ? atoi(e) : 0; }
   // (Until late in round 3 the default went to the two-per-CU build whenever the launch did not fit one workgroup per CU.  Measured
   // again with the thin row stream in place, the one-per-CU build wins at EVERY size: 32 x 1024: 0.82 against 1.05 ms, 8 x 3072: 2.98
   // against 3.42, 8 x 4096: 5.23 against 5.65, 8 x 8192: 26.5 against 28.6 -- the walker's 432 spilled registers sit on the chain every
@@ -5439,8 +5456,6 @@ void launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, con
   if (occ != 1) a.na = 0;
   // Row tiles: the first n128 are 128 rows high, the rest 64 (region_plan: a list-scheduling estimate of the launch for a few splits;
   // LMM_REGION_TH=128 / 64 forces all-128 / all-64).  Assistants only while everything is resident from the start.
-  static int th_env = -1;
-  if (th_env < 0) { const char* e = getenv("LMM_REGION_TH"); th_env = e ? atoi(e) : 0; }
   const RegionPlan plan = region_plan(P, nb, M - 128 * P, a.M_real - 128 * P, cus, a.na, asst_env == 2, (M % 64) != 0 || occ != 1 ? 128 : th_env);
   a.n128 = plan.n128; a.na = plan.na;
   if (a.na > 0) a.S = *S;
@@ -5448,8 +5463,6 @@ void launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, con
   const long long tasks = 2LL * P + a.na + row_tasks;     // the square's 64-row blocks + assistants + one task per row tile below it
   // LMM_REGION_TRACE=1: per-workgroup start / end ticks (100 MHz) of every region launch, printed to stderr (a debugging aid: it
   // synchronises the stream after each launch)
-  static int trace_env = -1;
-  if (trace_env < 0) { const char* e = getenv("LMM_REGION_TRACE"); trace_env = e ? atoi(e) : 0; }
   long long* tr = nullptr;
   if (trace_env) { if (hipMalloc((void**)&tr, ((size_t)tasks * nb * 2 + 64 * (size_t)nb) * sizeof(long long)) != hipSuccess) tr = nullptr; }
   a.trace = tr; a.ntasks = (int)tasks;
@@ -5507,14 +5520,12 @@ void launch_gemm_nt(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
   }
   // underfilled wide update (the 128 x 128 tiles of all nb matrices together do not fill the CUs once): 64 x 128 tiles instead
   if (!g_f32 && !narrow && lower && M >= N && (N % 128) == 0 && (M % 64) == 0 && K >= 64 && K < 1024) {
-    static int cus_h = 0;
-    if (cus_h == 0) { int dev = 0; cus_h = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus_h, hipDeviceAttributeMultiprocessorCount, dev); }
     long long T128 = 0;
     for (int tj = 0; tj < N / 128; ++tj) T128 += MT - tj;
     const int MT64 = M / 64;
     long long T64 = 0;
     for (int tj = 0; tj < N / 128; ++tj) T64 += MT64 - 2 * tj;
-    if (T128 * nb <= cus_h && T64 > 0) {
+    if (T128 * nb <= device_cus() && T64 > 0) {
       hipLaunchKernelGGL((gemm16h_kernel<false>), dim3((unsigned)T64, nb), dim3(256), 0, st, C, offC, ldc, A, offA, lda, B, offB, ldb, N, K, MT64);
       return;
     }
@@ -5523,11 +5534,7 @@ void launch_gemm_nt(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
   const int NT = narrow ? 1 : (N + 127) / 128;
   long long T = 0;
   for (int tj = 0; tj < NT; ++tj) T += lower ? (MT - (tj * BNsel) / 128) : MT;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0; cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  }
+  const int cus = device_cus();
   // Scheduling round = one tile per CU: the MFMA pipe, not residency, is the resource (one workgroup per CU already runs
   // at ~80 % of the CU's f64 rate, tools/stream_overlap).  With nb matrices in the batch a round holds cus / nb tiles of
   // each.  Tiles of the last, partial round are split along K (f64 atomics) so the launch ends without a long tail.
@@ -5535,8 +5542,7 @@ void launch_gemm_nt(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
   const int nk = K / 16;
   int full_items = (int)(T / slots) * slots, splitk = 1;
   const int R = (int)(T - full_items);
-  static int deterministic = -1;          // LMM_DETERMINISTIC=1: no split-K atomics (bitwise reproducible, slower tail)
-  if (deterministic < 0) { const char* e = getenv("LMM_DETERMINISTIC"); deterministic = (e && atoi(e) != 0) ? 1 : 0; }
+  const int deterministic = factor_switches().deterministic;          // LMM_DETERMINISTIC=1: no split-K atomics (bitwise reproducible, slower tail)
   if (!deterministic && !no_splitk && R > 0 && R <= slots / 2 && nk >= 8) {
     splitk = slots / R; if (splitk > nk / 4) splitk = nk / 4; if (splitk < 1) splitk = 1;
   }

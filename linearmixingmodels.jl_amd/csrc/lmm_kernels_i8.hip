@@ -20,11 +20,9 @@ namespace {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
-constexpr int TILE = 256, BK = 128;
+constexpr int TILE = LMM_EMUL_TILE, BK = 128;
 constexpr int STAGE_BYTES = 2 * TILE * BK;      // A tile + B tile of one K step
 constexpr unsigned long long ABS_MASK = 0x7FFFFFFFFFFFFFFFull, INF_BITS = 0x7FF0000000000000ull;
-
-inline size_t rup256(size_t v) { return (v + 255) & ~size_t(255); }
 
 // amax[z Mp + i] = max_k |a_ik| as a bit pattern (order-preserving for non-negative doubles; a NaN is above everything)
 __global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, unsigned long long* amax) {
@@ -413,28 +411,9 @@ void launch_combine(int nmod, dim3 grid, hipStream_t st, const BatchPtr& C, int 
 
 int g_emul_gemm_wgs = 0;      // emul_set_gemm_workgroups: 0 = one workgroup per CU
 
-struct EmulLayout { size_t R, U, amax, sc, ex, total; int Mp, Np, ntiles; };
-EmulLayout emul_layout(int M, int N, int K, int G, int nmod) {
-  EmulLayout L{};
-  L.Mp = (M + TILE - 1) / TILE * TILE; L.Np = (N + TILE - 1) / TILE * TILE;
-  L.ntiles = emul_tile_count(L.Mp / TILE, L.Np / TILE);
-  size_t o = 0;
-  L.R = o; o += rup256((size_t)G * nmod * L.Mp * K);
-  L.U = o; o += rup256((size_t)G * nmod * L.Np * L.Mp);
-  L.amax = o; o += rup256((size_t)G * L.Mp * 8);
-  L.sc = o; o += rup256((size_t)G * L.Mp * 8);
-  L.ex = o; o += rup256((size_t)G * L.Mp * 4);
-  L.total = o;
-  return L;
-}
-
 }  // namespace
 
-bool emul_shape_ok(int M, int N, int K) { return M >= N && N >= 1 && K >= BK && K % BK == 0 && K <= 16384; }      // int32 accumulators: K 128^2 <= 2^28
-
 void emul_set_gemm_workgroups(int wgs) { g_emul_gemm_wgs = wgs; }
-
-size_t emul_scratch_bytes(int M, int N, int K, int G, int nmod) { return emul_layout(M, N, K, G, nmod).total; }
 
 // C_m (M x N at C.p[m] + offC, ldc) -= P_m P_m[0:N]' for the panels P_m (M x K at P.p[m] + offP, ldp), m < nb, lower trapezoid
 // (i >= j) only, in groups of G matrices through `scratch` (emul_scratch_bytes(M, N, K, G, nmod) bytes).  Returns the first HIP
@@ -446,6 +425,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
   const EmulConst& c = consts[nmod];
   const int bits = emul_bits(nmod, K);
   const EmulLayout L = emul_layout(M, N, K, G, nmod);
+  const int ntiles = emul_tile_count(L.Mp / TILE, L.Np / TILE);
   hipError_t err = hipSuccess;
   const int2* tiles = emul_tiles(L.Mp / TILE, L.Np / TILE, &err);
   if (tiles == nullptr) return err;
@@ -455,17 +435,15 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
   unsigned long long* amax = reinterpret_cast<unsigned long long*>(s + L.amax);
   double* sc = reinterpret_cast<double*>(s + L.sc);
   int* ex = reinterpret_cast<int*>(s + L.ex);
-  static int cus = 0;
-  if (cus == 0) { int dev = 0; cus = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); }
-  const int wgs = g_emul_gemm_wgs > 0 ? g_emul_gemm_wgs : cus;      // one 128-KiB workgroup fits on a CU
+  const int wgs = g_emul_gemm_wgs > 0 ? g_emul_gemm_wgs : device_cus();      // one 128-KiB workgroup fits on a CU
   for (int g0 = 0; g0 < nb; g0 += G) {
     const int gc = std::min(G, nb - g0);
     err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
     if (err != hipSuccess) return err;
     emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, K, amax);
     launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, amax, R, sc, ex);
-    const int nids = L.ntiles * gc * nmod;
-    emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, L.ntiles, nids, L.Mp, L.Np, K, c);
+    const int nids = ntiles * gc * nmod;
+    emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, ntiles, nids, L.Mp, L.Np, K, c);
     launch_combine<LMM_EMUL_MAXMOD>(nmod, dim3((M + 1023) / 1024, N, gc), st, C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);
   }
   return hipSuccess;

@@ -4,7 +4,7 @@ FETCH_SIZE (KiB) is doubled (gfx950 counts 128-B requests at 64 B: MI355X_MICROA
 is exact.  Infinity-Cache hits are counted, so this is fabric (L2-miss) traffic, an upper bound on HBM bytes."""
 import csv, json, sys, collections
 # the dominant kernel under a stable key (bench.py reads it for roofline.traffic): the wide trailing update.  One update "launch" of
-# the library (lmm_api.hip potrf_rec) is one gemm16p_kernel<DEPTH> launch plus, for a ragged last 64 rows, one gemm16h_kernel launch:
+# the library (the plain update step of lmm_potrf_plan.h) is one gemm16p_kernel<DEPTH> launch plus, for a ragged last 64 rows, one gemm16h_kernel launch:
 # bytes of both, divided by the gemm16p launches (the count bench.py's roofline.launches uses).
 def aggregate_update(out):
     # round 3: the dominant kernel is potrf_node_kernel<2> (K >= 1024 updates + the next panel's leaf) plus gemm16h_kernel<true> on the
