@@ -808,6 +808,10 @@ int lmm_dev_set_f64_emul_rule(int min_k_always, int min_k_shape, double min_outp
 /* Test hook: an emulated update walks its batch in groups of as many matrices as its scratch block holds; g >= 1 caps the group size,
  * 0 goes back to the default.  Results do not depend on it. */
 int lmm_dev_set_emul_group(int g);
+/* Test hook: an emulated update of a factorisation takes the row maxima of the part of its panel that earlier emulated updates of the
+ * same factorisation scanned from the arrays those kept, and scans only the rest; on = 0 makes every update scan its whole panel,
+ * on != 0 goes back to the default.  Results do not depend on it. */
+int lmm_dev_set_emul_amax_reuse(int on);
 /* Host-only (no GPU, no lmm_init needed): the emulation plan of a factorisation of nb matrices with NR rows and NC columns, by the code
  * the factorisation itself runs.  out[0] = bytes of the scratch block it asks for (0: nothing is emulated), out[1] = matrices per group
  * that block is sized for; then 6 words per trailing update with at least 128 columns, in launch order: M, N, K, emulated (0 / 1),

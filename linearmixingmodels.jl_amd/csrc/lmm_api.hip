@@ -707,6 +707,7 @@ struct Batch {
 };
 
 static int g_in_flight = 1;       // batches that run concurrently on the slot streams (fork_slots / join_slots)
+static int g_emul_amax_reuse = 1; // lmm_dev_set_emul_amax_reuse: 0 = every emulated update scans its whole panel for the row maxima
 // The emulation side of a Float64 factorisation's plan, whatever path and base case the other switches choose (lmm_dev_emul_plan, batch_plan)
 static PotrfPlan emul_view(int NR, int NC, int nb) {
   FactorSwitches sw = factor_switches();
@@ -772,6 +773,11 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
       }
     }
   }
+  // Row maxima of the emulated updates: one array per emulated step, [matrix][NR], kept until the API call ends like W2 -- a later
+  // update whose panel contains an earlier one's reads its maxima there instead of scanning those columns again (emul_amax_cover)
+  std::vector<unsigned long long*> amax_kept(P.steps.size(), nullptr);
+  for (size_t i = 0; i < P.steps.size(); ++i)
+    if (P.steps[i].kind == POTRF_EMUL_UPDATE_LEAF) amax_kept[i] = reinterpret_cast<unsigned long long*>(call_scratch((size_t)B.nb * NR));
   auto leaf128 = [&](int c) { launch_leaf128(B.A, (size_t)c * ld + c, ld, B.W, (size_t)(c / 64) * 4096, W2, (size_t)(c / 128) * 16384, c, n_real, B.info, B.nb, st); };
   for (const PotrfStep& s : P.steps) {
     const bool named = s.named();
@@ -790,7 +796,14 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
       case POTRF_EMUL_UPDATE_LEAF:
         if (s.scratch > P.emul_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", s.scratch, P.emul_bytes);
         guard_extent(emul_blk, s.scratch / 8, s.scratch / 8, 1, false, "emulated update (scratch)");
-        HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, st));
+        {
+          const int si = (int)(&s - P.steps.data());
+          const EmulCover cov = emul_amax_cover(P.steps, si, g_emul_amax_reuse != 0);
+          EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0};
+          for (int q = 0; q < cov.n; ++q) keep.src[q] = amax_kept[cov.step[q]];
+          if (r0 + s.M > NR) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's rows %d + %d exceed %d", r0, s.M, NR);
+          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, st, &keep));
+        }
         leaf128(r0);
         break;
       case POTRF_REGION: launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst); break;
@@ -5592,6 +5605,13 @@ int lmm_dev_set_emul_group(int gcap) {
   g.err.clear();
   if (gcap < 0) return fail(LMM_ERR_ARG, "lmm_dev_set_emul_group: g >= 0");
   g_switches.emul_group_cap = gcap;
+  return LMM_OK;
+}
+// Test hook: on = 0 makes every emulated update of a factorisation scan its whole panel for the row maxima, as if no earlier update
+// had kept any; the default, 1, reads what earlier updates kept (emul_amax_cover).  Results do not depend on it.
+int lmm_dev_set_emul_amax_reuse(int on) {
+  g.err.clear();
+  g_emul_amax_reuse = on ? 1 : 0;
   return LMM_OK;
 }
 // Host-only (no GPU, no lmm_init needed): the emulation side of the plan potrf_batch makes for nb matrices of NR rows and NC columns.

@@ -1,7 +1,8 @@
 // lmm_kernels_i8.hip -- the large Float64 trailing updates C -= A B' of the factorisation as exact int8 modular GEMMs.
 // Built WITHOUT -amdgpu-mfma-vgpr-form=1.  Three steps per update, for groups of matrices:
 //   1. emul_rowmax_kernel + emul_convert_kernel: per panel row the exponent e_i = ceil(log2 max_k |a_ik|), the integers
-//      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows;
+//      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows (inside a factorisation
+//      the maxima outlive the update, and a later update reads them for the columns it shares: emul_amax_fold_kernel);
 //   2. emul_gemm_kernel: one int8 SYRK-shaped GEMM per (matrix, modulus) on 256 x 256 tiles of the lower trapezoid, int32
 //      accumulators, reduced mod p to one byte per output, as a persistent kernel (tools/i8_gemm_probe.hip holds a copy,
 //      i8_syrk_mod_kernel_ps with ABL = 6, beside the loops and kernels this one replaced; the probe stands alone: a change here
@@ -24,15 +25,27 @@ constexpr int TILE = LMM_EMUL_TILE, BK = 128;
 constexpr int STAGE_BYTES = 2 * TILE * BK;      // A tile + B tile of one K step
 constexpr unsigned long long ABS_MASK = 0x7FFFFFFFFFFFFFFFull, INF_BITS = 0x7FF0000000000000ull;
 
-// amax[z Mp + i] = max_k |a_ik| as a bit pattern (order-preserving for non-negative doubles; a NaN is above everything)
-__global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, unsigned long long* amax) {
+// amax[z as + i] = max(what is there, max_k |a_ik| over the columns k = kb .. K - 1) as a bit pattern (order-preserving for
+// non-negative doubles; a NaN is above everything).  as: entries per matrix of amax.
+__global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int as, int kb, int K, unsigned long long* amax) {
   const int i = blockIdx.x * 256 + threadIdx.x, z = blockIdx.z;
   if (i >= M) return;
   const double* P = A.p[g0 + z] + off + i;
-  const int k0 = blockIdx.y * 64, k1 = min(K, k0 + 64);
+  const int k0 = kb + blockIdx.y * 64, k1 = min(K, k0 + 64);
   unsigned long long m = 0;
   for (int k = k0; k < k1; ++k) m = max(m, (unsigned long long)__double_as_longlong(P[(size_t)k * ld]) & ABS_MASK);
-  atomicMax(&amax[(size_t)z * Mp + i], m);
+  atomicMax(&amax[(size_t)z * as + i], m);
+}
+// The first write of an update's kept row maxima: per row the largest of the maxima that earlier updates kept for parts of its panel
+// (bit patterns again, so a NaN or an infinity found then is still there), 0 when there are none.  emul_rowmax_kernel adds the
+// columns nobody has scanned yet.
+__global__ __launch_bounds__(256) void emul_amax_fold_kernel(EmulAmaxKeep k, int M) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  const size_t at = (size_t)blockIdx.y * k.ld + k.row0 + i;
+  unsigned long long m = 0;
+  for (int s = 0; s < k.n; ++s) m = max(m, k.src[s][at]);
+  k.out[at] = m;
 }
 
 // 16 rows x 128 k per workgroup of 256 threads, NMOD moduli.  Each thread first issues its 8 loads (8 k of one row; 16 lanes cover
@@ -43,12 +56,12 @@ __global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, si
 constexpr int CV_ROWS = 16, CV_K = 128, CV_PITCH = 130;
 template <int NMOD>
 __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
-                                                           const unsigned long long* __restrict__ amax, int8_t* __restrict__ R, double* sc, int* ex) {
+                                                           const unsigned long long* __restrict__ amax, int as, int8_t* __restrict__ R, double* sc, int* ex) {
   __shared__ long long lds[CV_ROWS * CV_PITCH];
   const int tid = threadIdx.x, ti = tid & 15, tk = tid >> 4, z = blockIdx.z;
   const int i = blockIdx.x * CV_ROWS + ti, k0 = blockIdx.y * CV_K;
   unsigned long long mb = 0;
-  if (i < M) mb = amax[(size_t)z * Mp + i];
+  if (i < M) mb = amax[(size_t)z * as + i];      // as: entries per matrix of amax
   const bool finite = mb < INF_BITS, live = mb != 0 && finite;
   int e = 0;
   if (live) e = emul_row_exp(__longlong_as_double((long long)mb));
@@ -84,11 +97,11 @@ __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, s
 }
 template <int NMOD>
 void launch_convert(int nmod, dim3 grid, hipStream_t st, const BatchPtr& P, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
-                    const unsigned long long* amax, int8_t* R, double* sc, int* ex) {
+                    const unsigned long long* amax, int as, int8_t* R, double* sc, int* ex) {
   if constexpr (NMOD > LMM_EMUL_MINMOD) {
-    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, R, sc, ex);
+    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex);
   }
-  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, R, sc, ex);
+  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex);
 }
 
 // lower-trapezoid tiles in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles share at most 12 operand panels
@@ -417,9 +430,10 @@ void emul_set_gemm_workgroups(int wgs) { g_emul_gemm_wgs = wgs; }
 
 // C_m (M x N at C.p[m] + offC, ldc) -= P_m P_m[0:N]' for the panels P_m (M x K at P.p[m] + offP, ldp), m < nb, lower trapezoid
 // (i >= j) only, in groups of G matrices through `scratch` (emul_scratch_bytes(M, N, K, G, nmod) bytes).  Returns the first HIP
-// error of its host-side calls (nothing is launched after one).
+// error of its host-side calls (nothing is launched after one).  keep: the row maxima go to an array of the caller's, for all nb matrices
+// before the first group, and start from what earlier updates found (EmulAmaxKeep, lmm_internal.h).
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
-                              int G, int nmod, void* scratch, hipStream_t st) {
+                              int G, int nmod, void* scratch, hipStream_t st, const EmulAmaxKeep* keep) {
   static EmulConst consts[LMM_EMUL_MAXMOD + 1];
   if (consts[nmod].nmod != nmod) consts[nmod] = emul_make_const(nmod);
   const EmulConst& c = consts[nmod];
@@ -436,12 +450,22 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
   double* sc = reinterpret_cast<double*>(s + L.sc);
   int* ex = reinterpret_cast<int*>(s + L.ex);
   const int wgs = g_emul_gemm_wgs > 0 ? g_emul_gemm_wgs : device_cus();      // one 128-KiB workgroup fits on a CU
+  if (keep) {      // every row of every matrix gets its first write from the fold: no memset
+    emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(*keep, M);
+    if (keep->scan0 < K)
+      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep->scan0 + 63) / 64, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep->ld, keep->scan0, K, keep->out + keep->row0);
+  }
   for (int g0 = 0; g0 < nb; g0 += G) {
     const int gc = std::min(G, nb - g0);
-    err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
-    if (err != hipSuccess) return err;
-    emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, K, amax);
-    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, amax, R, sc, ex);
+    const unsigned long long* am = amax;
+    int as = L.Mp;
+    if (keep) { am = keep->out + (size_t)g0 * keep->ld + keep->row0; as = keep->ld; }
+    else {
+      err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
+      if (err != hipSuccess) return err;
+      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, K, amax);
+    }
+    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, am, as, R, sc, ex);
     const int nids = ntiles * gc * nmod;
     emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, ntiles, nids, L.Mp, L.Np, K, c);
     launch_combine<LMM_EMUL_MAXMOD>(nmod, dim3((M + 1023) / 1024, N, gc), st, C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);

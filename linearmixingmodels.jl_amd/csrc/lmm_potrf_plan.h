@@ -224,6 +224,33 @@ struct PotrfPlanner {
   }
 };
 
+// Row maxima kept across the emulated updates of one factorisation.  An emulated update scans its panel -- columns
+// [j0, j0 + h), rows from j0 + h -- for the largest |entry| of every row, and potrf_batch keeps that array until the factorisation
+// ends.  The entries below a factored block column never change again, so a later update whose panel contains those columns, and
+// whose rows begin at or below the kept array's first row, finds the exact maximum of that column range in it.  emul_amax_cover
+// covers a prefix [j0, scan0) of the panel of steps[si] with the kept arrays of earlier emulated steps: from c = j0, the widest
+// earlier panel that begins at c and ends at or before j0 + h (so its rows begin no later than ours, at j0 + h), then on from its
+// end.  The columns [scan0, j0 + h) are left to scan.  It reads the step list only: no shape of the recursion is assumed.
+#define LMM_EMUL_COVER_MAX 8
+struct EmulCover { int n = 0; int step[LMM_EMUL_COVER_MAX] = {}; int scan0 = 0; };
+inline EmulCover emul_amax_cover(const std::vector<PotrfStep>& steps, int si, bool reuse) {
+  const PotrfStep& s = steps[si];
+  EmulCover c;
+  c.scan0 = s.j0;
+  const int end = s.j0 + s.h;
+  while (reuse && c.n < LMM_EMUL_COVER_MAX && c.scan0 < end) {
+    int best = -1;
+    for (int t = 0; t < si; ++t) {
+      const PotrfStep& e = steps[t];
+      if (e.kind == POTRF_EMUL_UPDATE_LEAF && e.j0 == c.scan0 && e.j0 + e.h <= end && (best < 0 || e.h > steps[best].h)) best = t;
+    }
+    if (best < 0) break;
+    c.step[c.n++] = best;
+    c.scan0 += steps[best].h;
+  }
+  return c;
+}
+
 // in_flight: batches that run concurrently on the slot streams; ld_odd: the leading dimension is odd (the panel kernels' 16-byte
 // accesses need an even one); emul_allowed: false once the API call could not get an emulation block (its remaining batches take the
 // f64 path without asking again)

@@ -3,8 +3,10 @@
 
     python tools/emul_level_times.py TRACE_kernel_trace.csv [--f64 NR NC]
 
-A level is recognised by the K of the emul_rowmax_kernel launch that opens every update (grid y = K / 64); the three kernels after
-it belong to the same update.  Prints ms summed over the launches of a level, per kernel, and the totals of every other kernel.
+A level is recognised by the K of the update's emul_convert_kernel launches (grid y = K / 128): the row-maximum kernels that open
+an update scan only the columns no earlier update has scanned (emul_amax_fold_kernel, counted with emul_rowmax, starts them from the
+kept maxima), so their grid does not tell.  Prints ms summed over the launches of a level, per kernel, and the totals of every other
+kernel.
 
 Then one line per emulated UPDATE, in launch order: an update is a maximal run of emulation kernels and the fills between them
 (two emulated updates are never neighbours: the factorisation of the columns between them lies in between).  Its key is (K, Mp,
@@ -18,6 +20,7 @@ import csv
 import sys
 
 EMUL = ("emul_rowmax", "emul_convert", "emul_gemm", "emul_combine")
+ALIAS = {"emul_amax_fold": "emul_rowmax"}
 
 
 def grid(r, ax):
@@ -45,13 +48,17 @@ def main(argv):
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     per = collections.defaultdict(lambda: collections.defaultdict(float))
     other = collections.defaultdict(float)
-    K = None
-    runs, cur = [], None
+    runs, cur, last_k = [], None, 0      # last_k: a run cut in two by another kernel continues the level of its first part
+
+    def close(u):
+        for k in EMUL:
+            per[k][u["K"]] += u[k]
+        runs.append(u)
     for r in rows:
         name = r["Kernel_Name"]
         t0, t1 = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
         ms = (t1 - t0) * 1e-6
-        hit = next((k for k in EMUL if k + "_kernel" in name), None)
+        hit = next((ALIAS.get(k, k) for k in EMUL + tuple(ALIAS) if k + "_kernel" in name), None)
         if hit is None:
             other[name.split("(")[0][:60]] += ms
             if cur is not None and "fillBuffer" in name:
@@ -61,23 +68,20 @@ def main(argv):
                 if "leaf128_kernel" in name:
                     cur["leaf"] = ms
                     cur["t1"] = t1
-                runs.append(cur)
+                close(cur)
                 cur = None
             continue
-        if hit == "emul_rowmax":
-            K = 64 * grid(r, "Y")
-        per[hit][K] += ms
         if cur is None:
-            cur = collections.defaultdict(float, t0=t0, K=K, nb=0, groups=0)
-        if hit == "emul_rowmax":
+            cur = collections.defaultdict(float, t0=t0, K=last_k, nb=0, groups=0)
+        if hit == "emul_convert":
+            cur["K"] = last_k = 128 * grid(r, "Y")
+            cur["Mp"] = 16 * grid(r, "X")
             cur["nb"] += grid(r, "Z")
             cur["groups"] += 1
-        if hit == "emul_convert":
-            cur["Mp"] = 16 * grid(r, "X")
         cur[hit] += ms
         cur["t1"] = t1
     if cur is not None:
-        runs.append(cur)
+        close(cur)
     levels = sorted({k for d in per.values() for k in d})
     for kern in EMUL:
         print(f"{kern}: " + str({k: round(per[kern][k], 2) for k in levels}))
