@@ -91,6 +91,26 @@ typedef enum {
  * scalar SE lengthscale.  rho and decay come from the latent's tag (lmm_kernel_tag_create_locally_periodic below), 1 and 1 without
  * one.  kappa(0) = v, smooth at coincident points.  It is the one product the library represents: a base kind, so it may be a sum term. */
 #define LMM_KERNEL_LOCALLY_PERIODIC 10
+/* A base kind outside the enum (codes 6, 8, 9 and 11 stay refused): the stochastically driven damped harmonic oscillator ("SHO", the
+ * celerite kernel of Foreman-Mackey et al. 2017), underdamped, over a ONE-dimensional input:
+ *     k(tau) = v exp(-a tau) ( cos(eta tau) + (a / eta) sin(eta tau) ),   tau = |x - x'|,
+ *     w0 = 2 pi / P,   a = w0 / (2 Q),   eta = w0 sqrt(1 - 1 / (4 Q^2)).
+ * v = variance; P = lengthscale, the undamped period (so `lengthscale` and its gradient slot keep their meaning); Q > 1 / 2 is the
+ * quality factor, from the latent's tag (lmm_kernel_tag_create_sho below), 1 without one.  kappa(0) = v; paths are once differentiable;
+ * the spectrum peaks near 1 / P with a width set by Q.  Q -> 1 / 2 is LMM_KERNEL_MATERN32 with sqrt3 / lengthscale = 2 pi / P; Q <= 1 / 2
+ * (critically and overdamped) is not served.  The kernel is exactly the two-dimensional SDE
+ *     F = [0 1; -w0^2 -w0 / Q],  Pinf = diag(v, w0^2 v),  A(dt) = exp(-a dt) (cos(eta dt) I + sin(eta dt) / eta (F + a I)),
+ * observed in its first component, which the state-space entry points run ("state space" below).  The dense entry points evaluate it
+ * as a function of r = tau / P with Q in the descriptor's alpha slot, as RQ its shape:
+ *     kappa(r) = v exp(-pi r / Q) ( cos(2 pi h r) + sin(2 pi h r) / (2 h Q) ),   h = sqrt(1 - 1 / (4 Q^2)),
+ * one exp and one sincospi per element; they serve it for d = 1 wherever a plain latent is served: logpdf, the posteriors and what is
+ * asked of them (marginals, covariances, samples, predictive logpdf), the gradient entry points (variance, period, quality through
+ * lmm_kernel_tag_quality_grad, mean, y, sigma2, S, U, H), missing data, OILMM, IndependentMOGP and dense-H, latent shards, the fp32
+ * compute mode and lmm_dev_gram.  Refused with LMM_ERR_UNSUPPORTED, naming the latent, before any device work: d > 1 (the radial form
+ * is not positive definite there) in every entry point; gradients with respect to the inputs (a non-NULL grad_x / grad_xs, and
+ * lmm_oilmm_mean_and_var_grad_xs); the inducing-point entry points (lmm_oilmm_elbo and its kin, lmm_dev_sparse_moments / _grad); and a
+ * kind-12 term of lmm_kernel_sum_create.  No entry point evaluates another kernel in its place. */
+#define LMM_KERNEL_SHO 12
 
 /* One latent GP: GP(mean, variance * Kernel o ScaleTransform(1/lengthscale)).
  * kind = base | (tag << 8): the low byte is the lmm_kernel_kind; a non-zero tag (lmm_ard_create) gives the latent per-dimension
@@ -143,7 +163,16 @@ typedef struct lmm_post lmm_post_t;   /* opaque posterior state (device resident
  *                    Same registry, mutex and 4096 limit; freed by lmm_ard_destroy.  lmm_kernel_tag_rho_grad serves its rho.
  *   lmm_kernel_tag_decay_grad : d logpdf / d decay, with the semantics of lmm_kernel_tag_rho_grad.  LMM_ERR_ARG on a tag without a
  *                    decay.
- * Validation in every entry point: the base kind must be 0..4, 7 or 10 (LMM_ERR_UNSUPPORTED otherwise) and the tag live (LMM_ERR_ARG
+ *   lmm_kernel_tag_create_sho : a tag for an SHO latent (LMM_KERNEL_SHO) carrying its quality factor: finite and > 1 / 2, otherwise
+ *                    LMM_ERR_ARG.  No factors (the kernel is defined for d = 1).  Same registry, mutex and 4096 limit; freed by
+ *                    lmm_ard_destroy.  A kind-12 latent without a tag has quality 1 and reports no quality gradient.
+ *   lmm_kernel_tag_quality_grad : d logpdf / d quality, with the semantics of lmm_kernel_tag_alpha_grad (the most recent gradient
+ *                    entry point that named the tag: the dense ones and lmm_oilmm_logpdf_grad_statespace).  LMM_ERR_ARG on a tag without a quality;
+ *                    lmm_kernel_tag_alpha_grad, _rho_grad and _decay_grad on a tag with a quality are LMM_ERR_ARG.
+ *                    A tag with a quality on a latent whose base kind is not LMM_KERNEL_SHO is LMM_ERR_ARG, and so is a tag with
+ *                    an alpha, a rho, a decay or factors on a kind-12 latent.
+ * Validation in every entry point: the base kind must be 0..4, 7, 10 or (LMM_KERNEL_SHO above, d = 1 only) 12 (LMM_ERR_UNSUPPORTED
+ * otherwise) and the tag live (LMM_ERR_ARG
  * otherwise); a tag with an alpha on a latent whose base kind is not LMM_KERNEL_RQ is LMM_ERR_ARG, and so is a tag with a rho (and no
  * decay) on a latent whose base kind is not LMM_KERNEL_PERIODIC, and a tag with a decay on one whose base kind is not
  * LMM_KERNEL_LOCALLY_PERIODIC; a tag with factors must have the
@@ -163,6 +192,8 @@ int lmm_kernel_tag_create_periodic(int d, const double* ard, double rho, int* ta
 int lmm_kernel_tag_rho_grad(int tag, double* out);
 int lmm_kernel_tag_create_locally_periodic(int d, const double* ard, double rho, double decay, int* tag);
 int lmm_kernel_tag_decay_grad(int tag, double* out);
+int lmm_kernel_tag_create_sho(double quality, int* tag);
+int lmm_kernel_tag_quality_grad(int tag, double* out);
 
 /* ---- sum kernels (KernelFunctions' KernelSum) ------------------------------------------------
  * A sum latent has kind = LMM_KERNEL_SUM | (tag << 8) with a tag from lmm_kernel_sum_create, and the kernel
@@ -661,12 +692,19 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
  * Per latent l, with lam = 1 / l, sqrt(3) / l or sqrt(5) / l: the state is (f, f', f''), F the companion matrix of (s + lam)^D,
  * A(dt) = exp(-lam dt) (I + N dt + N^2 dt^2 / 2) with N = F + lam I, Q(dt) = Pinf - A Pinf A', prior N(0, Pinf); the observation is the
  * first component plus N(0, w_t).
+ * An SHO latent (LMM_KERNEL_SHO, above; its tag carries the quality Q, 1 without one) is the two-dimensional SDE of a damped
+ * oscillator: state (f, f'), a = w0 / (2 Q), eta = w0 sqrt(1 - 1 / (4 Q^2)), N = F + a I with N^2 = -eta^2 I, A(dt) = exp(-a dt)
+ * (cos(eta dt) I + sin(eta dt) / eta N), Pinf = diag(v, w0^2 v), Q(dt) and the observation as above; everything downstream of A(dt) is
+ * the text the Matern latents run.  Matern and SHO latents mix freely in one call, in any order: launches group latents by MODEL
+ * (Matern32 and SHO share D = 2 but not a launch).  Its z takes 2 n doubles per sample, like a Matern32 latent's.  grad_gps[l] of an
+ * SHO latent holds d/d variance, d/d period (the `lengthscale` slot) and d/d mean; d/d quality goes to the latent's tag
+ * (lmm_kernel_tag_quality_grad), seeded as a third parameter of the forward-mode pass.
  * Data: y as for lmm_oilmm_logpdf, NaN = missing.  The front end is that of the missing-data entry points (the diagonal approximation,
  * exact without NaN and whenever every G_t is diagonal; m <= 128): per point the pseudo-observation z_t[l] - mean_l with noise variance
  * sigma2 (G_t^-1)_ll, and the same regulariser.  Additionally a point with NO observed output is kept, as a predict-only step that
  * contributes no term: that is how marginals at new inputs are asked for (merge them into x with all-NaN rows of y).
- * Refusals, all before any kernel of the scan is launched: a latent that is not a plain Matern12 / 32 / 52 (SE, RQ, the periodic
- * kinds, sums, latents with a tag) -> LMM_ERR_UNSUPPORTED with the latent in the error detail; the fp32 compute mode ->
+ * Refusals, all before any kernel of the scan is launched: a latent that is not a plain Matern12 / 32 / 52 or an SHO latent (SE, RQ,
+ * the periodic kinds, sums, Matern latents with a tag) -> LMM_ERR_UNSUPPORTED with the latent in the error detail; the fp32 compute mode ->
  * LMM_ERR_UNSUPPORTED; a point with 0 < p_t < m -> LMM_ERR_UNSUPPORTED with the point in `info`; S not finite and > 0, sigma2 <= 0 ->
  * LMM_ERR_ARG.  Not built: gradients with respect to x, gradients of the marginals, sums of Matern terms.
  *   lmm_oilmm_logpdf_statespace : the value of lmm_oilmm_logpdf (no NaN) or lmm_oilmm_logpdf_missing (NaN) by the filter: agreement
@@ -695,6 +733,9 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
  *                    the shard; with_regulariser as there.
  *   lmm_dev_statespace_grad : the building block beside lmm_dev_statespace_filter (DEVICE pointers throughout): *lml as there (bitwise),
  *                    grad_r and grad_w (n each; 0 at unobserved points), grad_theta = {d lml / d variance, d lml / d lengthscale}.
+ *   lmm_dev_statespace_grad_sho : the same block with grad_theta = {d lml / d variance, d lml / d lengthscale, d lml / d quality} (3
+ *                    values; the third is 0 for a Matern latent): lmm_dev_statespace_grad keeps its two-value output, which cannot
+ *                    carry an SHO latent's quality.
  *   lmm_oilmm_rand_statespace : rand in O(n), exact: joint samples of the prior (y == NULL) or of the posterior given y, at the n inputs,
  *                    from caller-supplied standard normals.  The prior path of a latent is the recursion s_0 = chol(Pinf) zeta_0,
  *                    s_t = A(dt_t) s_{t-1} + chol(Q(dt_t)) zeta_t, f_t = (s_t)_1 (chol: the lower factor with non-negative diagonal;
@@ -735,6 +776,8 @@ int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, in
                                      lmm_gp_grad_t* grad_gps);
 int lmm_dev_statespace_grad(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
                             double* lml, double* grad_r, double* grad_w, double* grad_theta);
+int lmm_dev_statespace_grad_sho(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
+                                double* lml, double* grad_r, double* grad_w, double* grad_theta);
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
                               const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,

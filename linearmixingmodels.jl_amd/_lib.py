@@ -19,11 +19,12 @@ KERNEL_SUM = 5              # LMM_KERNEL_SUM: a sum latent (descriptor kind "sum
 SUM_MAX_TERMS = 4
 KERNEL_PERIODIC = 7         # LMM_KERNEL_PERIODIC: a base kind outside lmm_kernel_kind (descriptor kind "periodic")
 KERNEL_LOCALLY_PERIODIC = 10     # LMM_KERNEL_LOCALLY_PERIODIC: SE x Periodic as one base kind (descriptor kind "locally_periodic")
+KERNEL_SHO = 12             # LMM_KERNEL_SHO: the damped oscillator, a base kind outside lmm_kernel_kind (descriptor kind "sho"; d = 1 only)
 
 # Every symbol include/lmm_hip.h declares (tests/test_abi.py checks the library exports each one).
 SYMBOLS = [
     "lmm_init", "lmm_shutdown", "lmm_last_error_string", "lmm_last_error_detail", "lmm_device_synchronize", "lmm_release_cached_memory",
-    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_kernel_tag_create_periodic", "lmm_kernel_tag_rho_grad", "lmm_kernel_tag_create_locally_periodic", "lmm_kernel_tag_decay_grad", "lmm_kernel_sum_create", "lmm_kernel_sum_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
+    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_kernel_tag_create_periodic", "lmm_kernel_tag_rho_grad", "lmm_kernel_tag_create_locally_periodic", "lmm_kernel_tag_decay_grad", "lmm_kernel_tag_create_sho", "lmm_kernel_tag_quality_grad", "lmm_kernel_sum_create", "lmm_kernel_sum_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
     "lmm_comm_destroy",
     "lmm_set_strict_progress", "lmm_get_strict_progress", "lmm_dev_claim_scramble", "lmm_orthogonal_validate", "lmm_oilmm_logpdf", "lmm_oilmm_logpdf_grad", "lmm_oilmm_post_logpdf_grad", "lmm_oilmm_post_logpdf_grad_seq", "lmm_ilmm_logpdf_grad", "lmm_ilmm_post_logpdf_grad", "lmm_ilmm_post_logpdf_grad_seq", "lmm_ilmm_post_latent_logpdf_grad_seq", "lmm_oilmm_logpdf_grad_x", "lmm_oilmm_post_logpdf_grad_seq_x", "lmm_ilmm_logpdf_grad_x",
     "lmm_ilmm_post_logpdf_grad_seq_x", "lmm_ilmm_post_latent_logpdf_grad_seq_x", "lmm_oilmm_logpdf_multi", "lmm_reorder", "lmm_ilmm_logpdf", "lmm_ilmm_logpdf_ex", "lmm_ilmm_logpdf_multi", "lmm_mogp_logpdf", "lmm_mogp_logpdf_diag",
@@ -34,7 +35,7 @@ SYMBOLS = [
     "lmm_oilmm_elbo", "lmm_oilmm_sparse_posterior_create", "lmm_sparse_post_destroy", "lmm_oilmm_sparse_mean_and_var", "lmm_dev_sparse_moments",
     "lmm_oilmm_elbo_grad", "lmm_dev_sparse_grad",
     "lmm_oilmm_logpdf_statespace", "lmm_oilmm_mean_and_var_statespace", "lmm_dev_statespace_filter", "lmm_dev_statespace_smooth",
-    "lmm_oilmm_logpdf_grad_statespace", "lmm_dev_statespace_grad",
+    "lmm_oilmm_logpdf_grad_statespace", "lmm_dev_statespace_grad", "lmm_dev_statespace_grad_sho",
     "lmm_oilmm_rand_statespace", "lmm_dev_statespace_sample", "lmm_dev_statespace_sample_posterior",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
     "lmm_dev_set_f64_emul", "lmm_dev_syrk_emul", "lmm_dev_emul_host", "lmm_dev_emul_residues", "lmm_dev_set_emul_gemm_workgroups", "lmm_dev_emul_acc_residues",
@@ -63,9 +64,16 @@ STATESPACE_ARGTYPES = {
     "lmm_dev_statespace_smooth": [_P, _I, _P, _P, _P, _I, _P, _P],
     "lmm_oilmm_logpdf_grad_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "lmm_dev_statespace_grad": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "lmm_dev_statespace_grad_sho": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
     "lmm_oilmm_rand_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "lmm_dev_statespace_sample": [_P, _I, _P, _P, _I, _I, _P],
     "lmm_dev_statespace_sample_posterior": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P],
+}
+
+# Argument types of the SHO tag entry points (include/lmm_hip.h, LMM_KERNEL_SHO), set on the library by load().
+SHO_ARGTYPES = {
+    "lmm_kernel_tag_create_sho": [_D, C.POINTER(C.c_int)],
+    "lmm_kernel_tag_quality_grad": [_I, C.POINTER(C.c_double)],
 }
 
 
@@ -120,7 +128,7 @@ def load() -> C.CDLL:
             pass
         _lib = C.CDLL(LIB_PATH)
         _lib.lmm_last_error_string.restype = C.c_char_p
-        for name, types in list(SPARSE_ARGTYPES.items()) + list(STATESPACE_ARGTYPES.items()):
+        for name, types in list(SPARSE_ARGTYPES.items()) + list(STATESPACE_ARGTYPES.items()) + list(SHO_ARGTYPES.items()):
             fn = getattr(_lib, name)
             fn.argtypes, fn.restype = types, C.c_int
     return _lib
@@ -363,6 +371,7 @@ class ArdTags:
         self.has_alpha = [False] * m
         self.has_rho = [False] * m
         self.has_decay = [False] * m
+        self.has_quality = [False] * m
         self.terms = [None] * m
         self._lib = None
 
@@ -372,6 +381,9 @@ class ArdTags:
         n = len(terms)
         if not 1 <= n <= SUM_MAX_TERMS:
             raise ValueError(f"a sum kernel has 1..{SUM_MAX_TERMS} terms, got {n}")
+        for c, t in enumerate(terms):
+            if t["kind"] == "sho":
+                raise NotImplementedError(f"latent {l}: an SHO term inside a sum kernel is not served (term {c})")
         tarr = gps_array(terms)
         self.terms[l] = tarr.ard
         t = C.c_int()
@@ -422,6 +434,21 @@ class ArdTags:
         self.has_decay[l] = decay is not None
         return t.value
 
+    def create_sho(self, l: int, quality: float) -> int:
+        """latent l's tag carrying an SHO latent's quality factor (lmm_kernel_tag_create_sho)."""
+        self._lib = self._lib or load()
+        t = C.c_int()
+        check(self._lib.lmm_kernel_tag_create_sho(C.c_double(quality), C.byref(t)))
+        self.tags[l] = t.value
+        self.has_quality[l] = True
+        return t.value
+
+    def quality_grad(self, l: int) -> float:
+        """d logpdf / d quality of latent l's tag after a gradient call."""
+        out = C.c_double(0.0)
+        check(self._lib.lmm_kernel_tag_quality_grad(self.tags[l], C.byref(out)))
+        return out.value
+
     def alpha_grad(self, l: int) -> float:
         """d logpdf / d alpha of latent l's tag after a gradient call."""
         out = C.c_double(0.0)
@@ -460,12 +487,23 @@ class ArdTags:
         self.has_alpha = [False] * len(self.tags)
         self.has_rho = [False] * len(self.tags)
         self.has_decay = [False] * len(self.tags)
+        self.has_quality = [False] * len(self.tags)
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+def sho_quality(q) -> float:
+    """An SHO latent's quality factor, validated: one finite scalar > 1 / 2 (the underdamped oscillator)."""
+    if np.ndim(q) != 0:
+        raise ValueError("an SHO kernel's quality is one scalar")
+    q = float(q)
+    if not (q > 0.5 and np.isfinite(q)):
+        raise ValueError("quality must be finite and > 0.5 (the underdamped oscillator; Q <= 1/2 is not served)")
+    return q
 
 
 def gps_array(gps: Sequence[dict]):
@@ -475,8 +513,10 @@ def gps_array(gps: Sequence[dict]):
     (lmm_kernel_tag_create_periodic) with the vector, if any; a descriptor without "r" and with a scalar period needs no tag.  A "locally_periodic" latent is a
     periodic one with a scalar "decay" (default 1.0) next to "r": both go into one tag (lmm_kernel_tag_create_locally_periodic), needed
     when the descriptor has "r", "decay" or a vector period.  A "sum" latent's "terms" (descriptors as above, mean 0) get their own tags and then one sum tag
-    (lmm_kernel_sum_create); its "variance" and scalar "lengthscale" scale the whole sum.  The tags live as long as the returned array
-    (its `.ard`)."""
+    (lmm_kernel_sum_create); its "variance" and scalar "lengthscale" scale the whole sum.  An "sho" latent's "lengthscale" is its period
+    (a scalar: the kernel is defined for d = 1) and its "quality" (default 1.0) goes into a tag (lmm_kernel_tag_create_sho) when the
+    descriptor has one.  An "sho" term of a sum raises NotImplementedError naming the latent, before any library call.  The tags live
+    as long as the returned array (its `.ard`)."""
     arr = (GpT * max(len(gps), 1))()
     arr.ard = ArdTags(len(gps))
     for l, g in enumerate(gps):
@@ -489,6 +529,16 @@ def gps_array(gps: Sequence[dict]):
                 raise ValueError("per-dimension lengthscales around a whole sum kernel are not supported")
             a.lengthscale = float(ls)
             a.kind |= arr.ard.create_sum(l, g["terms"]) << 8
+            a.mean = float(g.get("mean", 0.0))
+            continue
+        if g["kind"] == "sho":
+            ls = g.get("lengthscale", 1.0)
+            if np.ndim(ls) != 0:
+                raise ValueError("an SHO kernel's period is one scalar (the kernel is defined for one-dimensional inputs)")
+            a.kind = KERNEL_SHO
+            a.lengthscale = float(ls)
+            if "quality" in g:
+                a.kind |= arr.ard.create_sho(l, sho_quality(g["quality"])) << 8
             a.mean = float(g.get("mean", 0.0))
             continue
         special = {"periodic": KERNEL_PERIODIC, "locally_periodic": KERNEL_LOCALLY_PERIODIC}

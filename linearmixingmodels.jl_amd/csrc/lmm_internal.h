@@ -318,10 +318,10 @@ void launch_sparse_beta(const BatchPtr& R, int ld, int M, const BatchPtr& c, con
 // PB.p[l] = (Ki - Si - beta beta') / 2 (both triangles); lower(Si.p[l]) <- -2 PB + sym(T2)
 void launch_sparse_phibar(const BatchPtr& Ki, const BatchPtr& Si, const BatchPtr& T2, const BatchPtr& beta, const BatchPtr& PB, int ld,
                           int M, int nb, hipStream_t st);
-// State-space inference for Matern latents over a one-dimensional input (lmm_kernels_ss.hip).  All Float64.
-// One latent of a launch: variance, 1 / lengthscale, the constant added to the smoothed means, per-point noise w (device, n values;
-// +Inf: unobserved) and data r (device, n values).
-struct SSLat { double var, inv_ls, mean; const double* w; const double* r; };
+// State-space inference for Matern and SHO latents over a one-dimensional input (lmm_kernels_ss.hip).  All Float64.
+// One latent of a launch: variance, 1 / lengthscale (an SHO latent's 1 / period), the constant added to the smoothed means, per-point
+// noise w (device, n values; +Inf: unobserved), data r (device, n values) and an SHO latent's quality factor (unused by the Matern models).
+struct SSLat { double var, inv_ls, mean; const double* w; const double* r; double quality; };
 struct SSArgs {
   const double* x; int n, chunk, nch;         // sorted inputs (device); points per thread; nch = ceil(n / chunk) threads per latent
   double* agg;                                // nb * ss_fwd_agg_elems(D, nch) doubles: the forward aggregates and the scan's levels
@@ -330,39 +330,45 @@ struct SSArgs {
   double* state; size_t state_stride;         // filtered states, [latent][ss_state_comps(D)][n] (nullptr: not kept); doubles per latent
   double* part;                               // nb * nch log-density partials
   double* smean; double* svar;                // smoothed first-component mean (+ lat.mean) / variance, [latent][n]
-  double* dagg;                               // nb * ss_dual_agg_elems(D, nch) doubles: the (value, tangent) aggregates (gradients only)
-  double* dpart;                              // nb * 2 * nch tangents of the log-density partials (gradients only)
+  double* dagg;                               // nb * ss_dual_agg_elems(D, nch, seeds) doubles: the (value, tangent) aggregates (gradients only)
+  double* dpart;                              // nb * seeds * nch tangents of the log-density partials (gradients only)
   SSLat lat[LMM_MAX_BATCH];
 };
 static_assert(sizeof(SSArgs) <= 4096, "SSArgs is passed by value: kernel arguments are limited to 4096 bytes");
-int ss_state_dim(int kind);                   // 1 / 2 / 3 for Matern12 / 32 / 52, 0 for every other kind
+// The model of a launch: 1 / 2 / 3 = Matern12 / 32 / 52 (the state dimension), SS_MODEL_SHO = the damped oscillator (state dimension 2)
+#define SS_MODEL_SHO 4
+int ss_model_of(int kind);                    // the model of a base kind, 0 for a kind without one
+int ss_model_dim(int model);                  // its state dimension
+int ss_model_seeds(int model);                // parameters its forward-mode gradient seeds: 2 (variance, lengthscale), SHO 3 (+ quality)
+int ss_state_dim(int kind);                   // 1 / 2 / 3 for Matern12 / 32 / 52, 2 for SHO, 0 for every other kind
 int ss_state_comps(int D);                    // doubles of one filtered state: D + D (D + 1) / 2
 int ss_default_chunk(int n);                  // the library's plan: a function of n alone
 size_t ss_fwd_agg_elems(int D, int nch);      // per latent
 size_t ss_bwd_agg_elems(int D, int nch);
-// fold, scan, filter (and, lml != nullptr, lml[l] = latent l's log density) of nb latents with state dimension D
-void launch_ss_filter(const SSArgs& a, int D, int nb, double* lml, hipStream_t st);
+// fold, scan, filter (and, lml != nullptr, lml[l] = latent l's log density) of nb latents of one model
+void launch_ss_filter(const SSArgs& a, int model, int nb, double* lml, hipStream_t st);
 // the same in reverse over the filtered states a.state: smoothed marginals into a.smean / a.svar
-void launch_ss_smooth(const SSArgs& a, int D, int nb, hipStream_t st);
-// Gradients.  gtheta[2 l + s]: d lml_l / d variance (s = 0) and d lml_l / d lengthscale (s = 1) by the forward-mode (dual number)
-// instantiation of fold, scan and filter; a.dagg and a.dpart are its workspace
-size_t ss_dual_agg_elems(int D, int nch);     // per latent, both seeds
-void launch_ss_grad(const SSArgs& a, int D, int nb, double* gtheta, hipStream_t st);
+void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st);
+// Gradients.  gtheta[NS l + s], NS = ss_model_seeds(model): d lml_l / d variance (s = 0), d lml_l / d lengthscale (s = 1) and, SHO,
+// d lml_l / d quality (s = 2) by the forward-mode (dual number) instantiation of fold, scan and filter; a.dagg and a.dpart are its workspace
+size_t ss_dual_agg_elems(int D, int nch, int nseeds);     // per latent, all seeds
+void launch_ss_grad(const SSArgs& a, int model, int nb, double* gtheta, hipStream_t st);
 // from a.smean / a.svar (no mean added): alpha, grad_w ([latent][n]) = -d lml / d r_t, d lml / d w_t (0 at unobserved points) and
 // sums[4 l + q] = sum_t alpha, w alpha^2, w c, grad_w in a fixed order; ppart: nb * 4 * ss_point_blocks(n) doubles
 int ss_point_blocks(int n);
 void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, double* ppart, double* sums, hipStream_t st);
 // Sampling.  One (latent, sample) pair of a launch: variance, 1 / lengthscale, its standard normals z (device, D n values, component i
-// of point t at z[i n + t]), the constant added to the path, and the path it writes (device, n values: the first component of the state).
-struct SSPathLat { double var, inv_ls, mean; const double* z; double* f; };
+// of point t at z[i n + t]), the constant added to the path, the path it writes (device, n values: the first component of the state)
+// and an SHO latent's quality factor.
+struct SSPathLat { double var, inv_ls, mean; const double* z; double* f; double quality; };
 struct SSPathArgs {
   const double* x; int n, chunk, nch;         // as SSArgs
   double* agg;                                // nb * ss_aff_agg_elems(D, nch) doubles: the affine aggregates and the scan's levels
   SSPathLat lat[LMM_MAX_BATCH];
 };
 size_t ss_aff_agg_elems(int D, int nch);      // per pair
-// fold, scan and restart of the prior paths of nb pairs with state dimension D
-void launch_ss_path(const SSPathArgs& a, int D, int nb, hipStream_t st);
+// fold, scan and restart of the prior paths of nb pairs of one model
+void launch_ss_path(const SSPathArgs& a, int model, int nb, hipStream_t st);
 // rp[latent k][sample q][n] = r_k - f[q][k] - sqrt(w_k) xi[q xi_stride + k n] at observed points, r_k where w = +Inf (xi not read)
 void launch_ss_pathwise(const double* r, const double* w, const double* f, const double* xi, size_t xi_stride, int n, int ms, int N,
                         double* rp, hipStream_t st);

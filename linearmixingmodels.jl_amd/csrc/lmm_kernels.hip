@@ -108,6 +108,7 @@ __device__ __forceinline__ double kappa(int kind, double var, double r, double r
   return var * (1.0 + s + (5.0 / 3.0) * r2) * exp_nonpos(-s);
 }
 
+#define LMM_PI 3.141592653589793
 // log(1 + u) for u >= 0 (the RQ kernel): the device library's log1p, documented within 1 ulp in Float64 (no cancellation near u = 0,
 // unlike log(1 + u)).
 __device__ __forceinline__ double log1p_nonneg(double u) { return log1p(u); }
@@ -117,9 +118,22 @@ __device__ __forceinline__ double kappa_rq(double var, double r2, double alpha) 
   return var * exp_nonpos(-alpha * log1p_nonneg(r2 * (0.5 / alpha)));
 }
 
-// All five kinds: Matern12 (KernelFunctions' ExponentialKernel) v e^{-r}, RQ with shape alpha, the others as kappa above.
+// SHO (LMM_KERNEL_SHO, d = 1 only): v e^{-pi r / Q} [cos(2 pi h r) + sin(2 pi h r) / (2 h Q)], r = |x - x'| / P, h = sqrt(1 - 1 / (4 Q^2))
+// taken as sqrt((2 Q - 1)(2 Q + 1)) / (2 Q) (no cancellation as Q -> 1/2; the state-space model's form).  Q travels in the alpha slot.
+// sincospi reduces 2 h r exactly, so far-apart points cost no accuracy in the angle.
+__device__ __forceinline__ double sho_eta(double Q) { return sqrt((2.0 * Q - 1.0) * (2.0 * Q + 1.0)) * (0.5 / Q); }
+__device__ __forceinline__ double kappa_sho(double var, double r, double Q) {
+  const double h = sho_eta(Q);
+  double sn, cs;
+  sincospi(2.0 * h * r, &sn, &cs);
+  return var * exp_nonpos(-LMM_PI * r / Q) * __builtin_fma(sn, 0.5 / (h * Q), cs);
+}
+
+// Every kind that is a function of r: Matern12 (KernelFunctions' ExponentialKernel) v e^{-r}, RQ with shape alpha, SHO with quality
+// alpha, the others as kappa above.
 __device__ __forceinline__ double kappa(int kind, double var, double r, double r2, double alpha) {
   if (kind == LMM_KERNEL_MATERN12) return var * exp_nonpos(-r);
+  if (kind == LMM_KERNEL_SHO) return kappa_sho(var, r, alpha);
   if (kind == LMM_KERNEL_RQ) return kappa_rq(var, r2, alpha);
   return kappa(kind, var, r, r2);
 }
@@ -269,6 +283,7 @@ __device__ __forceinline__ double kappa_t(double var, double r, double r2, doubl
   }
   if (KIND == LMM_KERNEL_MATERN12) return var * exp_nonpos(-r);
   if (KIND == LMM_KERNEL_RQ) return kappa_rq(var, r2, alpha);
+  if (KIND == LMM_KERNEL_SHO) return kappa_sho(var, r, alpha);
   const double s = 2.23606797749979 * r;
   return var * __builtin_fma(5.0 / 3.0, r2, 1.0 + s) * exp_nonpos(-s);
 }
@@ -392,7 +407,7 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
       xr1[k] = (k < a.d) ? rsrc[(size_t)(i0 + 1 - rbase) * a.d + k] * sk : 0.0;
     }
   }
-  constexpr bool SEP = (KIND != LMM_KERNEL_SE && KIND != LMM_KERNEL_RQ);
+  constexpr bool SEP = (KIND != LMM_KERNEL_SE && KIND != LMM_KERNEL_RQ && KIND != LMM_KERNEL_SHO);      // (SHO: the phase is not separable)
   const double aS = KIND == LMM_KERNEL_MATERN12 ? a.inv_ls : (KIND == LMM_KERNEL_MATERN32 ? 1.7320508075688772 : 2.23606797749979) * a.inv_ls;
   double x0 = 0.0, x1 = 0.0, cr = 0.0, E0 = 0.0, F0 = 0.0, E1 = 0.0, F1 = 0.0;
   bool rows_ok = false;
@@ -3670,12 +3685,26 @@ __device__ __forceinline__ void rq_pair(double var, double alpha, double r2, dou
 // Locally periodic pairs (EXT = 3): kap = v exp(-q / (2 rho^2) - D2 / (2 l^2)), D2 = sum_k (x_ik - x_jk)^2.  The periodic formulas hold with
 // this kap, and in addition  d kap / d l = kap D2 / l^3  and  d kap / d x_ik = -kap (u_k / P_k + (x_ik - x_jk) / l^2).  The decay sum has a
 // partial slot of its own behind the LMM_NG common ones ([LMM_NG]; the per-dimension sums of the ARD kernel follow it); g.inv_decay = 1 / l.
-#define LMM_PI 3.141592653589793
 __device__ __forceinline__ double per_rho3(double irho2) { return irho2 * sqrt(irho2); }     // 1 / rho^3
 
-// kappa, d kappa / d ell and (RQ) d kappa / d alpha of a Matern12 or RQ pair
+// SHO at scaled distance r, E = e^{-pi r / Q}, (s, c) = sincospi(2 h r), h = sho_eta(Q), so that h' = 1 / (4 h Q^3):
+//     kap = v E (c + s / (2 h Q));    d kap / d r = -2 pi v E s / h,  so  d kap / d P = 2 pi v E s r / (h P);
+//     d kap / d Q = v E { (pi r / Q^2) (c + s / (2 h Q)) + (pi r / (2 h Q^3)) (c / (2 h Q) - s) - s / (2 h^3 Q^2) }.
+__device__ __forceinline__ void sho_pair(double var, double Q, double inv_ls, double r, double& kap, double& dell, double& dq) {
+  const double h = sho_eta(Q), ihq = 0.5 / (h * Q), iq2 = 1.0 / (Q * Q);
+  double sn, cs;
+  sincospi(2.0 * h * r, &sn, &cs);
+  const double vE = var * exp_nonpos(-LMM_PI * r / Q), amp = __builtin_fma(sn, ihq, cs), pr = LMM_PI * r;
+  kap = vE * amp;
+  dell = 2.0 * vE * sn * pr * inv_ls / h;
+  dq = vE * (pr * iq2 * amp + pr * iq2 * ihq * __builtin_fma(cs, ihq, -sn) - sn * iq2 * 0.5 / (h * h * h));
+}
+
+// kappa, d kappa / d ell and (RQ) d kappa / d alpha or (SHO) d kappa / d Q of a Matern12, RQ or SHO pair
 __device__ __forceinline__ void ext_pair(const LatentDev& g, double r, double r2, double& kap, double& dell, double& dal) {
-  if (g.kind == LMM_KERNEL_RQ) {
+  if (g.kind == LMM_KERNEL_SHO) {
+    sho_pair(g.var, g.alpha, g.inv_ls, r, kap, dell, dal);
+  } else if (g.kind == LMM_KERNEL_RQ) {
     double h;
     rq_pair(g.var, g.alpha, r2, kap, h, dal);
     dell = h * r2 * g.inv_ls;
@@ -3692,7 +3721,7 @@ __device__ __forceinline__ void ext_pair(const LatentDev& g, double r, double r2
 //   partial[NG*tile + 2], [6] = alpha.alpha over the same two row ranges
 //   partial[NG*tile + 3..4]   = alpha.delta, sum alpha over the tile's rows                   (diagonal tiles only)
 //   partial[NG*tile + 7]      = sum_{i>j in tile} (alpha_i alpha_j - Kinv_ij) K_ij            (variance, when Kinv is a block of a larger inverse)
-//   partial[NG*tile + 8]      = sum_{i>j in tile} (alpha_i alpha_j - Kinv_ij) dK_ij/d alpha   (the RQ shape; 0 for the other kinds)
+//   partial[NG*tile + 8]      = sum_{i>j in tile} (alpha_i alpha_j - Kinv_ij) dK_ij/d alpha   (the RQ shape, or an SHO latent's quality; 0 for the other kinds)
 // The split at nsplit serves the predictive logpdf (joint of training and test points, each block with its own noise).
 #define LMM_NG 9
 // TS: storage type of the inverse Kinv (a MATRIX: Float32 in the fp32 compute mode); all sums in Float64.  EXT: a Matern12 / RQ latent
@@ -3772,7 +3801,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const void* __restrict
   if (EXT >= 2) { acc *= LMM_PI * g.alpha * g.inv_ls; acca *= per_rho3(g.alpha); }
   const double tl = block_sum_256(acc, sh);
   const double tk = block_sum_256(acck, sh);
-  const double ta = (EXT >= 2 || (EXT && g.kind == LMM_KERNEL_RQ)) ? block_sum_256(acca, sh) : 0.0;     // (g.kind is uniform: the barrier is too)
+  const double ta = (EXT >= 2 || (EXT && (g.kind == LMM_KERNEL_RQ || g.kind == LMM_KERNEL_SHO))) ? block_sum_256(acca, sh) : 0.0;     // (g.kind is uniform: the barrier is too)
   [[maybe_unused]] double td = 0.0;
   if constexpr (EXT == 3) td = block_sum_256(accd * (g.inv_decay * g.inv_decay * g.inv_decay), sh);
   double tra = 0.0, aaa = 0.0, trb = 0.0, aab = 0.0, ad = 0.0, sa = 0.0;
@@ -5096,6 +5125,7 @@ void launch_gram(const GramArgs& a0, hipStream_t st) {
   else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
   else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
   else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
+  else if (a.kind == LMM_KERNEL_SHO) LMM_GRAM_LAUNCH(LMM_KERNEL_SHO);
   else if (a.kind == LMM_KERNEL_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_PERIODIC);
   else if (a.kind == LMM_KERNEL_LOCALLY_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_LOCALLY_PERIODIC);
   else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
@@ -5133,6 +5163,7 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
     else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
     else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
+    else if (a.kind == LMM_KERNEL_SHO) LMM_GRAM_LAUNCH(LMM_KERNEL_SHO);
     else if (a.kind == LMM_KERNEL_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_PERIODIC);
     else if (a.kind == LMM_KERNEL_LOCALLY_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_LOCALLY_PERIODIC);
     else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
@@ -5726,7 +5757,7 @@ static int grad_ext(int kind) {
 }
 
 // out (LMM_NGRAD values): [dl/d ell, tr Kinv (rows < nsplit), a.a (rows < nsplit), a.delta, sum a, tr Kinv (rows >= nsplit),
-//        a.a (rows >= nsplit), sum_{i>j} (a_i a_j - Kinv_ij) K_ij, dl/d alpha (RQ) or dl/d rho (periodic kinds; 0 otherwise),
+//        a.a (rows >= nsplit), sum_{i>j} (a_i a_j - Kinv_ij) K_ij, dl/d alpha (RQ), dl/d quality (SHO) or dl/d rho (periodic kinds; 0 otherwise),
 //        dl/d decay (written for a locally periodic latent only)]
 void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const double* alpha, const double* delta, const double* x, int d,
                         LatentDev g, double* partial, double* out7, hipStream_t st, double* out_ard) {

@@ -1,4 +1,4 @@
-// lmm_kernels_ss.hip -- linear-time state-space inference for Matern12 / 32 / 52 latents over a one-dimensional input:
+// lmm_kernels_ss.hip -- linear-time state-space inference for Matern12 / 32 / 52 and SHO latents over a one-dimensional input:
 // the Kalman filter and the Rauch-Tung-Striebel smoother as parallel scans over the n points.  Float64 only; built WITHOUT
 // -amdgpu-mfma-vgpr-form=1 (no MFMA here).  Three phases per direction, no atomics, results depend only on (arguments, chunk):
 //   1. ss_fold_kernel / ss_bfold_kernel: each thread folds the scan elements of its `chunk` consecutive points into one aggregate;
@@ -6,11 +6,13 @@
 //      aggregates than one workgroup takes, the workgroups' totals are scanned by the same kernel (recursion on the host) and applied;
 //   3. ss_filter_kernel / ss_rts_kernel: each thread restarts the ordinary recursion from its prefix (suffix) state over its run and
 //      writes the marginals; the filter's log-density partials are added in thread order by ss_finish_kernel.
-// A(dt) and Q(dt) are evaluated on the fly from x_t - x_{t-1}; blockIdx.z is the latent.  Every latent of a launch has the same state
-// dimension D (the template argument).
-// Gradients (launch_ss_grad): d lml / d variance and d lml / d lengthscale are the forward-mode derivative of phases 1 - 3 of the filter,
-// the same text instantiated with SSDual (lmm_statespace.h): ss_dfold_kernel, the scan over SSFwd<D, SSDual> and ss_dfilter_kernel, with
-// blockIdx.y in {0, 1} the seeded parameter, so a thread carries one tangent.  d lml / d r_t and d lml / d w_t come from the smoothed
+// A(dt) and Q(dt) are evaluated on the fly from x_t - x_{t-1}; blockIdx.z is the latent.  Every latent of a launch has the same MODEL
+// (the template arguments D and OSC: Matern12 / 32 / 52, or the damped oscillator of an SHO latent, which shares D = 2 with Matern32
+// but not its A(dt)); the scans see elements only and are shared between models of equal D.
+// Gradients (launch_ss_grad): d lml / d variance and d lml / d lengthscale (and an SHO latent's d lml / d quality) are the forward-mode
+// derivative of phases 1 - 3 of the filter, the same text instantiated with SSDual (lmm_statespace.h): ss_dfold_kernel, the scan over
+// SSFwd<D, SSDual> and ss_dfilter_kernel, with blockIdx.y the seeded parameter (2 per Matern latent, 3 per SHO latent), so a thread
+// carries one tangent.  d lml / d r_t and d lml / d w_t come from the smoothed
 // marginals (ss_point_kernel), with fixed-order sums of what the OILMM chain rule needs.
 // Sampling (launch_ss_path): the prior path is an affine recursion in the caller's normals, so phases 1 - 3 run on SSAff<D> elements
 // (ss_sfold_kernel, the scan with AffOp, ss_path_kernel); a posterior path is the prior path plus the smoothed mean of the residual
@@ -27,19 +29,31 @@ constexpr int SS_SCAN = 128;         // aggregates per workgroup of the scan (on
 // 128 SSFwd<3, SSDual> would be 66 KiB, above the 64 KiB of static LDS: elements that large are scanned 64 per workgroup
 template <typename T> constexpr int ss_scan_width() { return sizeof(T) * SS_SCAN <= 65536 ? SS_SCAN : SS_SCAN / 2; }
 
-template <int D>
-__device__ __forceinline__ SSModel<D> ss_lat_model(const SSLat& L) {
-  SSModel<D> M;
-  ss_model<D>(L.var, L.inv_ls, M);
+// The model of a launch: OSC = false, the Matern model of state dimension D; OSC = true (D = 2), the oscillator
+template <int D, bool OSC, typename Sc = double> struct SSModelOf { typedef SSModel<D, Sc> type; };
+template <typename Sc> struct SSModelOf<2, true, Sc> { typedef SSOsc<Sc> type; };
+// seeded parameters of the forward-mode gradient: variance and lengthscale, and an oscillator's quality
+template <bool OSC> constexpr int ss_seeds() { return OSC ? 3 : 2; }
+
+template <int D, bool OSC, typename Sc>
+__device__ __forceinline__ typename SSModelOf<D, OSC, Sc>::type ss_make_model(Sc var, Sc inv_ls, Sc quality) {
+  typename SSModelOf<D, OSC, Sc>::type M;
+  if constexpr (OSC) ss_osc_model<Sc>(var, inv_ls, quality, M);
+  else ss_model<D, Sc>(var, inv_ls, M);
   return M;
 }
 
-template <int D>
+template <int D, bool OSC>
+__device__ __forceinline__ typename SSModelOf<D, OSC>::type ss_lat_model(const SSLat& L) {
+  return ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
+}
+
+template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_fold_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
-  const SSModel<D> M = ss_lat_model<D>(L);
+  const auto M = ss_lat_model<D, OSC>(L);
   const long long t0 = (long long)j * a.chunk;
   const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
   SSFwd<D> acc, el;
@@ -128,12 +142,12 @@ void scan_levels(T* items, int N, int nb, T* scratch, hipStream_t st) {
 // packed index of the symmetric entry (i, j), i <= j, behind the D mean components of a filtered state
 __host__ __device__ constexpr int ss_sym_at(int D, int i, int j) { return D + i * D - i * (i - 1) / 2 + (j - i); }
 
-template <int D>
+template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_filter_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
-  const SSModel<D> M = ss_lat_model<D>(L);
+  const auto M = ss_lat_model<D, OSC>(L);
   const long long t0 = (long long)j * a.chunk;
   const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
   double m[D], P[D][D];
@@ -188,21 +202,22 @@ __global__ __launch_bounds__(SS_THREADS) void ss_finish_kernel(const double* __r
 
 
 // ---- gradients ---------------------------------------------------------------------------------------------------------------
-// The model of latent L with the tangent of parameter `seed` set: 0 = variance, 1 = lengthscale (d (1 / l) = -1 / l^2)
-template <int D>
-__device__ __forceinline__ SSModel<D, SSDual> ss_lat_dmodel(const SSLat& L, int seed) {
-  SSModel<D, SSDual> M;
-  ss_model<D, SSDual>(SSDual(L.var, seed == 0 ? 1.0 : 0.0), SSDual(L.inv_ls, seed == 0 ? 0.0 : -L.inv_ls * L.inv_ls), M);
-  return M;
+// The model of latent L with the tangent of parameter `seed` set: 0 = variance, 1 = lengthscale (d (1 / l) = -1 / l^2; an oscillator's
+// period), 2 = an oscillator's quality
+template <int D, bool OSC>
+__device__ __forceinline__ typename SSModelOf<D, OSC, SSDual>::type ss_lat_dmodel(const SSLat& L, int seed) {
+  return ss_make_model<D, OSC, SSDual>(SSDual(L.var, seed == 0 ? 1.0 : 0.0), SSDual(L.inv_ls, seed == 1 ? -L.inv_ls * L.inv_ls : 0.0),
+                                       SSDual(L.quality, seed == 2 ? 1.0 : 0.0));
 }
 
-// ss_fold_kernel on (value, tangent): blockIdx.y is the seeded parameter, the aggregates of (latent z, seed s) are item 2 z + s
-template <int D>
+// ss_fold_kernel on (value, tangent): blockIdx.y is the seeded parameter (NS = ss_seeds<OSC>() of them), the aggregates of (latent z,
+// seed s) are item NS z + s
+template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_dfold_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = blockIdx.y;
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
-  const SSModel<D, SSDual> M = ss_lat_dmodel<D>(L, s);
+  const auto M = ss_lat_dmodel<D, OSC>(L, s);
   const long long t0 = (long long)j * a.chunk;
   const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
   SSFwd<D, SSDual> acc, el;
@@ -214,16 +229,16 @@ __global__ __launch_bounds__(SS_THREADS) void ss_dfold_kernel(SSArgs a) {
     ss_fwd_combine<D, SSDual>(acc, el, acc);
     xp = xt;
   }
-  reinterpret_cast<SSFwd<D, SSDual>*>(a.dagg)[(size_t)(2 * z + s) * a.nch + j] = acc;
+  reinterpret_cast<SSFwd<D, SSDual>*>(a.dagg)[(size_t)(ss_seeds<OSC>() * z + s) * a.nch + j] = acc;
 }
 
 // ss_filter_kernel on (value, tangent): writes only the tangent of its log-density partial
-template <int D>
+template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_dfilter_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = blockIdx.y;
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
-  const SSModel<D, SSDual> M = ss_lat_dmodel<D>(L, s);
+  const auto M = ss_lat_dmodel<D, OSC>(L, s);
   const long long t0 = (long long)j * a.chunk;
   const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
   SSDual m[D], P[D][D];
@@ -233,7 +248,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_dfilter_kernel(SSArgs a) {
       for (int k = 0; k < D; ++k) P[i][k] = M.Pinf[i][k];
     }
   } else {
-    const SSFwd<D, SSDual>& pre = reinterpret_cast<const SSFwd<D, SSDual>*>(a.dagg)[(size_t)(2 * z + s) * a.nch + j - 1];
+    const SSFwd<D, SSDual>& pre = reinterpret_cast<const SSFwd<D, SSDual>*>(a.dagg)[(size_t)(ss_seeds<OSC>() * z + s) * a.nch + j - 1];
     for (int i = 0; i < D; ++i) {
       m[i] = pre.b[i];
       for (int k = 0; k < D; ++k) P[i][k] = pre.C[i][k];
@@ -246,7 +261,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_dfilter_kernel(SSArgs a) {
     lp += ss_filter_step<D, SSDual>(M, xt - xp, L.w[t], L.r[t], m, P);
     xp = xt;
   }
-  a.dpart[(size_t)(2 * z + s) * a.nch + j] = lp.t;
+  a.dpart[(size_t)(ss_seeds<OSC>() * z + s) * a.nch + j] = lp.t;
 }
 
 constexpr int SS_POINT_PER = 8;      // points per thread of ss_point_kernel
@@ -295,11 +310,11 @@ __device__ __forceinline__ void ss_load_state(const double* stt, int n, long lon
   }
 }
 
-template <int D>
+template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_bfold_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
-  const SSModel<D> M = ss_lat_model<D>(a.lat[z]);
+  const auto M = ss_lat_model<D, OSC>(a.lat[z]);
   const long long t0 = (long long)j * a.chunk;
   const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
   const double* stt = a.state + (size_t)z * a.state_stride;
@@ -314,12 +329,12 @@ __global__ __launch_bounds__(SS_THREADS) void ss_bfold_kernel(SSArgs a) {
   reinterpret_cast<SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j] = acc;
 }
 
-template <int D>
+template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
-  const SSModel<D> M = ss_lat_model<D>(L);
+  const auto M = ss_lat_model<D, OSC>(L);
   const long long t0 = (long long)j * a.chunk;
   const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
   const double* stt = a.state + (size_t)z * a.state_stride;
@@ -373,11 +388,9 @@ __global__ __launch_bounds__(256) void ss_scatter_rows_kernel(const double* __re
 // The prior path s_t = A(dt_t) s_{t-1} + chol(Q(dt_t)) zeta_t, s_0 = chol(Pinf) zeta_0, is an affine recursion, so the same three
 // phases serve it with SSAff<D> elements (D^2 + D doubles): ss_sfold_kernel, the scan with AffOp, ss_path_kernel.  blockIdx.z runs over
 // the (latent, sample) pairs of a launch; zeta is read straight from the caller's buffer, component i of point t at z[i n + t].
-template <int D>
-__device__ __forceinline__ SSModel<D> ss_path_model(const SSPathLat& L) {
-  SSModel<D> M;
-  ss_model<D>(L.var, L.inv_ls, M);
-  return M;
+template <int D, bool OSC>
+__device__ __forceinline__ typename SSModelOf<D, OSC>::type ss_path_model(const SSPathLat& L) {
+  return ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
 }
 
 template <int D>
@@ -385,12 +398,12 @@ __device__ __forceinline__ void ss_load_zeta(const double* __restrict__ z, int n
   for (int i = 0; i < D; ++i) zeta[i] = z[(size_t)i * n + t];
 }
 
-template <int D>
+template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_sfold_kernel(SSPathArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const SSPathLat& L = a.lat[z];
-  const SSModel<D> M = ss_path_model<D>(L);
+  const auto M = ss_path_model<D, OSC>(L);
   const long long t0 = (long long)j * a.chunk;
   const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
   SSAff<D> acc, el;
@@ -413,12 +426,12 @@ struct AffOp {
 };
 
 // each thread restarts the recursion from its prefix state (the c of the scanned aggregate before its run) and writes f_t = (s_t)_1 (+ lat.mean)
-template <int D>
+template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_path_kernel(SSPathArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const SSPathLat& L = a.lat[z];
-  const SSModel<D> M = ss_path_model<D>(L);
+  const auto M = ss_path_model<D, OSC>(L);
   const long long t0 = (long long)j * a.chunk;
   const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
   double s[D], zeta[D];
@@ -468,48 +481,54 @@ size_t scan_items(int nch, int W = SS_SCAN) {         // items of every level be
   return tot;
 }
 
-template <int D>
+template <int D, bool OSC>
 void filter_D(const SSArgs& a, int nb, double* lml, hipStream_t st) {
   const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
-  hipLaunchKernelGGL(ss_fold_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  hipLaunchKernelGGL((ss_fold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
   SSFwd<D>* agg = reinterpret_cast<SSFwd<D>*>(a.agg);
   scan_levels<D, SSFwd<D>, FwdOp, false>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
-  hipLaunchKernelGGL(ss_filter_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  hipLaunchKernelGGL((ss_filter_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
   if (lml) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
 }
 
-template <int D>
+template <int D, bool OSC>
 void smooth_D(const SSArgs& a, int nb, hipStream_t st) {
   const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
-  hipLaunchKernelGGL(ss_bfold_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  hipLaunchKernelGGL((ss_bfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
   SSBwd<D>* agg = reinterpret_cast<SSBwd<D>*>(a.bagg);
   scan_levels<D, SSBwd<D>, BwdOp, true>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
-  hipLaunchKernelGGL(ss_rts_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  hipLaunchKernelGGL((ss_rts_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
 }
 
-template <int D>
+template <int D, bool OSC>
 void grad_D(const SSArgs& a, int nb, double* gtheta, hipStream_t st) {
-  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 2, nb);
-  hipLaunchKernelGGL(ss_dfold_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  constexpr int NS = ss_seeds<OSC>();
+  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, NS, nb);
+  hipLaunchKernelGGL((ss_dfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
   typedef SSFwd<D, SSDual> E;
   E* agg = reinterpret_cast<E*>(a.dagg);
-  scan_levels<D, E, FwdOp, false>(agg, a.nch, 2 * nb, agg + (size_t)2 * nb * a.nch, st);
-  hipLaunchKernelGGL(ss_dfilter_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
-  hipLaunchKernelGGL(ss_finish_kernel, dim3(2 * nb), dim3(SS_THREADS), 0, st, (const double*)a.dpart, a.nch, gtheta);
+  scan_levels<D, E, FwdOp, false>(agg, a.nch, NS * nb, agg + (size_t)NS * nb * a.nch, st);
+  hipLaunchKernelGGL((ss_dfilter_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
+  hipLaunchKernelGGL(ss_finish_kernel, dim3(NS * nb), dim3(SS_THREADS), 0, st, (const double*)a.dpart, a.nch, gtheta);
 }
 
-template <int D>
+template <int D, bool OSC>
 void path_D(const SSPathArgs& a, int nb, hipStream_t st) {
   const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
-  hipLaunchKernelGGL(ss_sfold_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  hipLaunchKernelGGL((ss_sfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
   SSAff<D>* agg = reinterpret_cast<SSAff<D>*>(a.agg);
   scan_levels<D, SSAff<D>, AffOp, false>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
-  hipLaunchKernelGGL(ss_path_kernel<D>, grid, dim3(SS_THREADS), 0, st, a);
+  hipLaunchKernelGGL((ss_path_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
 }
 
 }  // namespace
 
-int ss_state_dim(int kind) { return kind == LMM_KERNEL_MATERN12 ? 1 : kind == LMM_KERNEL_MATERN32 ? 2 : kind == LMM_KERNEL_MATERN52 ? 3 : 0; }
+int ss_model_of(int kind) {
+  return kind == LMM_KERNEL_MATERN12 ? 1 : kind == LMM_KERNEL_MATERN32 ? 2 : kind == LMM_KERNEL_MATERN52 ? 3 : kind == LMM_KERNEL_SHO ? SS_MODEL_SHO : 0;
+}
+int ss_model_dim(int model) { return model == SS_MODEL_SHO ? 2 : model; }
+int ss_model_seeds(int model) { return model == SS_MODEL_SHO ? ss_seeds<true>() : ss_seeds<false>(); }
+int ss_state_dim(int kind) { return ss_model_dim(ss_model_of(kind)); }
 int ss_state_comps(int D) { return D + D * (D + 1) / 2; }
 int ss_default_chunk(int n) { return n <= 4096 ? 16 : 64; }
 size_t ss_fwd_agg_elems(int D, int nch) {
@@ -521,17 +540,18 @@ size_t ss_bwd_agg_elems(int D, int nch) {
   return ((size_t)nch + scan_items(nch)) * (e / sizeof(double));
 }
 
-size_t ss_dual_agg_elems(int D, int nch) {
+size_t ss_dual_agg_elems(int D, int nch, int nseeds) {
   const size_t e = D == 1 ? sizeof(SSFwd<1, SSDual>) : D == 2 ? sizeof(SSFwd<2, SSDual>) : sizeof(SSFwd<3, SSDual>);
   const int W = D == 1 ? ss_scan_width<SSFwd<1, SSDual>>() : D == 2 ? ss_scan_width<SSFwd<2, SSDual>>() : ss_scan_width<SSFwd<3, SSDual>>();
-  return 2 * ((size_t)nch + scan_items(nch, W)) * (e / sizeof(double));
+  return nseeds * ((size_t)nch + scan_items(nch, W)) * (e / sizeof(double));
 }
 int ss_point_blocks(int n) { return (n + SS_THREADS * SS_POINT_PER - 1) / (SS_THREADS * SS_POINT_PER); }
 
-void launch_ss_grad(const SSArgs& a, int D, int nb, double* gtheta, hipStream_t st) {
-  if (D == 1) grad_D<1>(a, nb, gtheta, st);
-  else if (D == 2) grad_D<2>(a, nb, gtheta, st);
-  else grad_D<3>(a, nb, gtheta, st);
+void launch_ss_grad(const SSArgs& a, int model, int nb, double* gtheta, hipStream_t st) {
+  if (model == SS_MODEL_SHO) grad_D<2, true>(a, nb, gtheta, st);
+  else if (model == 1) grad_D<1, false>(a, nb, gtheta, st);
+  else if (model == 2) grad_D<2, false>(a, nb, gtheta, st);
+  else grad_D<3, false>(a, nb, gtheta, st);
 }
 
 void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, double* ppart, double* sums, hipStream_t st) {
@@ -540,24 +560,27 @@ void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, dou
   hipLaunchKernelGGL(ss_finish_kernel, dim3(4 * nb), dim3(SS_THREADS), 0, st, (const double*)ppart, nblk, sums);
 }
 
-void launch_ss_filter(const SSArgs& a, int D, int nb, double* lml, hipStream_t st) {
-  if (D == 1) filter_D<1>(a, nb, lml, st);
-  else if (D == 2) filter_D<2>(a, nb, lml, st);
-  else filter_D<3>(a, nb, lml, st);
+void launch_ss_filter(const SSArgs& a, int model, int nb, double* lml, hipStream_t st) {
+  if (model == SS_MODEL_SHO) filter_D<2, true>(a, nb, lml, st);
+  else if (model == 1) filter_D<1, false>(a, nb, lml, st);
+  else if (model == 2) filter_D<2, false>(a, nb, lml, st);
+  else filter_D<3, false>(a, nb, lml, st);
 }
 
-void launch_ss_smooth(const SSArgs& a, int D, int nb, hipStream_t st) {
-  if (D == 1) smooth_D<1>(a, nb, st);
-  else if (D == 2) smooth_D<2>(a, nb, st);
-  else smooth_D<3>(a, nb, st);
+void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st) {
+  if (model == SS_MODEL_SHO) smooth_D<2, true>(a, nb, st);
+  else if (model == 1) smooth_D<1, false>(a, nb, st);
+  else if (model == 2) smooth_D<2, false>(a, nb, st);
+  else smooth_D<3, false>(a, nb, st);
 }
 
 size_t ss_aff_agg_elems(int D, int nch) { return ((size_t)nch + scan_items(nch)) * (size_t)(D * D + D); }
 
-void launch_ss_path(const SSPathArgs& a, int D, int nb, hipStream_t st) {
-  if (D == 1) path_D<1>(a, nb, st);
-  else if (D == 2) path_D<2>(a, nb, st);
-  else path_D<3>(a, nb, st);
+void launch_ss_path(const SSPathArgs& a, int model, int nb, hipStream_t st) {
+  if (model == SS_MODEL_SHO) path_D<2, true>(a, nb, st);
+  else if (model == 1) path_D<1, false>(a, nb, st);
+  else if (model == 2) path_D<2, false>(a, nb, st);
+  else path_D<3, false>(a, nb, st);
 }
 
 void launch_ss_pathwise(const double* r, const double* w, const double* f, const double* xi, size_t xi_stride, int n, int ms, int N,

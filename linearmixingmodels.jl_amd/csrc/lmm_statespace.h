@@ -1,10 +1,14 @@
-// lmm_statespace.h -- the per-point arithmetic of the state-space (Kalman / RTS) path for Matern latents over a one-dimensional input
-// (include/lmm_hip.h "state space").  Everything is templated on the state dimension D (Matern12 / 32 / 52: 1 / 2 / 3)
-// and fully unrolled, so every matrix lives in registers.  The functions are __host__ __device__: lmm_kernels_ss.hip runs them on the
+// lmm_statespace.h -- the per-point arithmetic of the state-space (Kalman / RTS) path for Matern and SHO latents over a one-dimensional
+// input (include/lmm_hip.h "state space").  Everything is templated on the state dimension D (Matern12 / 32 / 52: 1 / 2 /
+// 3; SHO: 2) and on the latent's model (SSModel<D>: Matern; SSOsc: the damped oscillator), and fully unrolled, so every matrix lives in
+// registers.  The functions are __host__ __device__: lmm_kernels_ss.hip runs them on the
 // GPU, and a host build of the same text can be stepped through on the CPU.
 //
 // Model: F is the companion matrix of (s + lam)^D, N = F + lam I is nilpotent (N^D = 0), A(dt) = exp(-lam dt) (I + N dt + N^2 dt^2 / 2),
 // Q(dt) = Pinf - A Pinf A', prior state N(0, Pinf), observation h = e_1'.
+// The oscillator (SSOsc, D = 2): F = [0 1; -w0^2 -w0 / Q] with w0 = 2 pi / P, a = w0 / (2 Q), eta = w0 sqrt(1 - 1 / (4 Q^2)); N = F + a I
+// has N^2 = -eta^2 I, so A(dt) = exp(-a dt) (cos(eta dt) I + sin(eta dt) / eta N); Pinf = diag(v, w0^2 v), Q(dt) and h as above.  Only
+// A(dt) differs between the models: everything from ss_fwd_element down is one text, instantiated on the model's type.
 //
 // The forward (filtering) arithmetic is also templated on its scalar type Sc.  Sc = double (the default) is the arithmetic of the value;
 // Sc = SSDual carries one tangent beside every value, which makes the same text the forward-mode derivative of the filter with respect
@@ -42,6 +46,14 @@ SS_HD SSDual& operator-=(SSDual& a, SSDual b) { a.v -= b.v; a.t -= b.t; return a
 SS_HD SSDual& operator-=(SSDual& a, double b) { a.v -= b; return a; }
 SS_HD SSDual exp(SSDual a) { const double e = exp(a.v); return SSDual(e, e * a.t); }
 SS_HD SSDual log(SSDual a) { return SSDual(log(a.v), a.t / a.v); }
+SS_HD SSDual sqrt(SSDual a) { const double r = sqrt(a.v); return SSDual(r, 0.5 * a.t / r); }
+// (sin x, cos x) of one argument
+SS_HD void ss_sincos(double x, double& s, double& c) { s = sin(x); c = cos(x); }
+SS_HD void ss_sincos(SSDual x, SSDual& s, SSDual& c) {
+  double sv, cv;
+  ss_sincos(x.v, sv, cv);
+  s = SSDual(sv, cv * x.t); c = SSDual(cv, -sv * x.t);
+}
 SS_HD bool operator<(SSDual a, SSDual b) { return a.v < b.v; }
 SS_HD bool operator>(SSDual a, SSDual b) { return a.v > b.v; }
 SS_HD bool operator<=(SSDual a, SSDual b) { return a.v <= b.v; }
@@ -84,6 +96,24 @@ SS_HD void ss_model(Sc var, Sc inv_ls, SSModel<D, Sc>& M) {
   }
 }
 
+// Q = Pinf - A Pinf A' (symmetric by construction)
+template <int D, typename Sc = double>
+SS_HD void ss_stationary_Q(const Sc Pinf[D][D], const Sc A[D][D], Sc Q[D][D]) {
+  Sc T[D][D];
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      Sc s = 0.0;
+      for (int k = 0; k < D; ++k) s += A[i][k] * Pinf[k][j];
+      T[i][j] = s;
+    }
+  for (int i = 0; i < D; ++i)
+    for (int j = i; j < D; ++j) {
+      Sc s = 0.0;
+      for (int k = 0; k < D; ++k) s += T[i][k] * A[j][k];
+      Q[i][j] = Q[j][i] = Pinf[i][j] - s;
+    }
+}
+
 // A(dt) and Q(dt); dt = 0 gives A = I and Q = 0 exactly
 template <int D, typename Sc = double>
 SS_HD void ss_AQ(const SSModel<D, Sc>& M, double dt, Sc A[D][D], Sc Q[D][D]) {
@@ -91,19 +121,40 @@ SS_HD void ss_AQ(const SSModel<D, Sc>& M, double dt, Sc A[D][D], Sc Q[D][D]) {
   const double h = 0.5 * dt * dt;
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) A[i][j] = e * ((i == j ? 1.0 : 0.0) + M.N[i][j] * dt + (D > 2 ? M.N2[i][j] * h : 0.0));
-  Sc T[D][D];
+  ss_stationary_Q<D, Sc>(M.Pinf, A, Q);
+}
+
+// ---- the stochastically driven damped harmonic oscillator (SHO; underdamped, Q > 1 / 2) --------------------------------------------
+template <typename Sc = double>
+struct SSOsc {
+  Sc a, eta;
+  Sc N[2][2], Pinf[2][2];
+};
+
+// inv_p = 1 / P (the undamped period), q the quality factor.  1 - 1 / (4 q^2) is taken as (2 q - 1) (2 q + 1) / (4 q^2), which keeps
+// its relative accuracy as q -> 1 / 2: eta = a sqrt((2 q - 1) (2 q + 1)).
+template <typename Sc = double>
+SS_HD void ss_osc_model(Sc var, Sc inv_p, Sc q, SSOsc<Sc>& M) {
+  const Sc w0 = 6.283185307179586 * inv_p;
+  const Sc a = w0 / (2.0 * q);
+  const Sc w2 = w0 * w0;
+  M.a = a;
+  M.eta = a * sqrt((2.0 * q - 1.0) * (2.0 * q + 1.0));
+  M.N[0][0] = a; M.N[0][1] = 1.0; M.N[1][0] = -w2; M.N[1][1] = -a;
+  M.Pinf[0][0] = var; M.Pinf[0][1] = 0.0; M.Pinf[1][0] = 0.0; M.Pinf[1][1] = w2 * var;
+}
+
+// A(dt) and Q(dt) of the oscillator; dt = 0 gives e = c = 1 and s = 0, so A = I and Q = 0 exactly
+template <int D, typename Sc = double>
+SS_HD void ss_AQ(const SSOsc<Sc>& M, double dt, Sc A[D][D], Sc Q[D][D]) {
+  static_assert(D == 2, "the oscillator has a two-dimensional state");
+  const Sc e = exp(-M.a * dt);
+  Sc sn, cs;
+  ss_sincos(M.eta * dt, sn, cs);
+  const Sc c = e * cs, s = e * sn / M.eta;
   for (int i = 0; i < D; ++i)
-    for (int j = 0; j < D; ++j) {
-      Sc s = 0.0;
-      for (int k = 0; k < D; ++k) s += A[i][k] * M.Pinf[k][j];
-      T[i][j] = s;
-    }
-  for (int i = 0; i < D; ++i)
-    for (int j = i; j < D; ++j) {
-      Sc s = 0.0;
-      for (int k = 0; k < D; ++k) s += T[i][k] * A[j][k];
-      Q[i][j] = Q[j][i] = M.Pinf[i][j] - s;
-    }
+    for (int j = 0; j < D; ++j) A[i][j] = (i == j ? c : Sc(0.0)) + s * M.N[i][j];
+  ss_stationary_Q<D, Sc>(M.Pinf, A, Q);
 }
 
 template <int D, typename Sc = double>
@@ -191,8 +242,8 @@ template <int D, typename Sc = double>
 struct SSFwd { Sc A[D][D], b[D], C[D][D], eta[D], J[D][D]; };
 
 // The element of one point.  first: the prior takes the place of the transition (A = 0, Q = Pinf).  w = +Inf: unobserved.
-template <int D, typename Sc = double>
-SS_HD void ss_fwd_element(const SSModel<D, Sc>& M, bool first, double dt, double w, double r, SSFwd<D, Sc>& e) {
+template <int D, typename Sc = double, typename Mod>
+SS_HD void ss_fwd_element(const Mod& M, bool first, double dt, double w, double r, SSFwd<D, Sc>& e) {
   Sc A[D][D], Q[D][D];
   if (first) {
     for (int i = 0; i < D; ++i)
@@ -254,8 +305,8 @@ SS_HD void ss_fwd_combine(const SSFwd<D, Sc>& a, const SSFwd<D, Sc>& b, SSFwd<D,
 
 // One step of the ordinary Kalman filter: (m, P) at the previous point -> (m, P) at this one.  Returns the point's log-density term
 // (0 for an unobserved point, which takes the predict step only).
-template <int D, typename Sc = double>
-SS_HD Sc ss_filter_step(const SSModel<D, Sc>& M, double dt, double w, double r, Sc m[D], Sc P[D][D]) {
+template <int D, typename Sc = double, typename Mod>
+SS_HD Sc ss_filter_step(const Mod& M, double dt, double w, double r, Sc m[D], Sc P[D][D]) {
   Sc A[D][D], Q[D][D], T[D][D], mp[D];
   ss_AQ<D, Sc>(M, dt, A, Q);
   ss_mm<D, Sc>(A, P, T);
@@ -287,8 +338,8 @@ template <int D>
 struct SSBwd { double E[D][D], g[D], L[D][D]; };
 
 // The element of a point with filtered state (m, P) whose successor lies dt further; last: the final point (0, m, P).
-template <int D>
-SS_HD void ss_bwd_element(const SSModel<D>& M, bool last, double dt, const double m[D], const double P[D][D], SSBwd<D>& e) {
+template <int D, typename Mod>
+SS_HD void ss_bwd_element(const Mod& M, bool last, double dt, const double m[D], const double P[D][D], SSBwd<D>& e) {
   if (last) {
     for (int i = 0; i < D; ++i) {
       e.g[i] = m[i];
@@ -391,8 +442,8 @@ template <int D>
 struct SSAff { double A[D][D], c[D]; };
 
 // The element of one point of the prior path s_t = A(dt) s_{t-1} + chol(Q(dt)) zeta_t.  first: (0, chol(Pinf) zeta_0).
-template <int D>
-SS_HD void ss_aff_element(const SSModel<D>& M, bool first, double dt, const double zeta[D], SSAff<D>& e) {
+template <int D, typename Mod>
+SS_HD void ss_aff_element(const Mod& M, bool first, double dt, const double zeta[D], SSAff<D>& e) {
   double Q[D][D], L[D][D];
   if (first) {
     for (int i = 0; i < D; ++i)

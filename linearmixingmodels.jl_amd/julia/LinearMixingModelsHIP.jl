@@ -20,7 +20,7 @@ using AbstractGPs, KernelFunctions, LinearAlgebra, Random, FillArrays, ChainRule
 using LinearMixingModels
 using LinearMixingModels: ILMM, IndependentMOGP, Orthogonal, unpack, noise_var
 
-export hip, HIPMOGP, statespace_logpdf, statespace_mean_and_var, statespace_rand
+export hip, HIPMOGP, SHOKernel, statespace_logpdf, statespace_mean_and_var, statespace_rand
 
 const liblmm = get(ENV, "LMM_HIP_LIB", "liblmm_hip.so")
 
@@ -98,6 +98,27 @@ _kind(k::RationalQuadraticKernel) = (_euclidean(k); Cint(4))
 # PeriodicKernel(; r): v exp(-sum_k sin^2(pi (x_k - x'_k)) / (2 r^2)) under a ScaleTransform(1 / P) or ARDTransform(1 ./ P): the
 # lengthscale slot (and the ARD factors) carry the period(s).  The library takes ONE rho for all dimensions: r = fill(rho, d).
 _kind(k::PeriodicKernel) = Cint(7)
+# SHOKernel(; quality): the stochastically driven damped harmonic oscillator (the celerite "SHO" kernel; kind 12, LMM_KERNEL_SHO),
+#     kappa(r) = exp(-pi r / Q) (cos(2 pi eta r) + sin(2 pi eta r) / (2 eta Q)),  eta = sqrt(1 - 1 / (4 Q^2)),  r = |x - x'| / P,
+# under a ScaleTransform(1 / P) (the lengthscale slot carries the undamped period P) and a ScaledKernel.  A SimpleKernel with its own
+# kappa, so the reference's CPU methods work on it too.  Underdamped only (Q > 1/2); one-dimensional inputs only (the radial form is
+# not positive definite for d > 1).  Q travels in the latent's tag (lmm_kernel_tag_create_sho).  The library serves it on the state-space
+# path (statespace_logpdf, statespace_mean_and_var, statespace_rand and the rrule of statespace_logpdf) and refuses it everywhere else.
+const LMM_KERNEL_SHO = 12
+struct SHOKernel{T<:Real} <: KernelFunctions.SimpleKernel
+    quality::Vector{T}
+    function SHOKernel(; quality::Real=1.0)
+        (isfinite(quality) && quality > 0.5) || throw(ArgumentError("SHOKernel: quality must be finite and > 1/2 (underdamped)"))
+        return new{typeof(quality)}([quality])
+    end
+end
+function KernelFunctions.kappa(k::SHOKernel, r::Real)
+    Q = only(k.quality); η = sqrt((2Q - 1) * (2Q + 1)) / (2Q)
+    return exp(-π * r / Q) * (cos(2π * η * r) + sin(2π * η * r) / (2η * Q))
+end
+KernelFunctions.metric(::SHOKernel) = KernelFunctions.Euclidean()
+Base.show(io::IO, k::SHOKernel) = print(io, "SHO Kernel (quality = ", only(k.quality), ")")
+_kind(k::SHOKernel) = Cint(LMM_KERNEL_SHO)
 _desc(k::Kernel) = (_kind(k), 1.0, 1.0)
 _desc(k::ScaledKernel) = ((kd, v, l) = _desc(k.kernel); (kd, v * only(k.σ²), l))
 _desc(k::TransformedKernel{<:Kernel,<:ScaleTransform}) = ((kd, v, l) = _desc(k.kernel); (kd, v, l / only(k.transform.s)))
@@ -125,6 +146,14 @@ function _rho(k::PeriodicKernel)
 end
 _rho(k::ScaledKernel) = _rho(k.kernel)
 _rho(k::TransformedKernel) = _rho(k.kernel)
+# an SHO kernel's quality (it travels in the latent's tag, lmm_kernel_tag_create_sho); nothing for the other kernels.  An SHO kernel
+# takes a ScaleTransform and a ScaledKernel only.
+_quality(k::Kernel) = nothing
+_quality(k::SHOKernel) = Float64(only(k.quality))
+_quality(k::ScaledKernel) = _quality(k.kernel)
+_quality(k::TransformedKernel{<:Kernel,<:ScaleTransform}) = _quality(k.kernel)
+_desc(k::TransformedKernel{<:SHOKernel,<:ARDTransform}) =
+    error("LinearMixingModelsHIP: an SHOKernel under an ARDTransform is not served (the kernel is defined for one-dimensional inputs)")
 # Locally periodic kernels: the ONE KernelProduct that is served, SqExponentialKernel * PeriodicKernel in either order (kind 10,
 # LMM_KERNEL_LOCALLY_PERIODIC).  The SE factor may sit under a ScaleTransform (1 / decay), the periodic factor under a ScaleTransform or
 # ARDTransform (1 / period); the product itself may sit under ScaledKernel / ScaleTransform (which then scales the period AND the decay)
@@ -189,12 +218,16 @@ struct KTag
     rho::Bool      # the tag holds a periodic kernel's rho (its gradient travels in the `alpha` field of the gradient tuples)
     decay::Bool    # the tag holds a locally periodic kernel's rho and decay (the `alpha` field is then the tuple (rho = , decay = ))
     terms::Vector{KTag}   # a sum tag: its terms' tags (empty otherwise)
+    quality::Bool  # the tag holds an SHO kernel's quality (its gradient travels in the `alpha` field of the gradient tuples)
 end
-KTag(id, ard, alpha, rho::Bool=false, decay::Bool=false) = KTag(id, ard, alpha, rho, decay, KTag[])
+KTag(id, ard, alpha, rho::Bool=false, decay::Bool=false; terms::Vector{KTag}=KTag[], quality::Bool=false) =
+    KTag(id, ard, alpha, rho, decay, terms, quality)
 # the factor / alpha tag of one kernel (a latent's or a sum term's); 0: none needed
-function _ktag(a, α, ρ=nothing, δ=nothing)
+function _ktag(a, α, ρ=nothing, δ=nothing, q=nothing)
     tr = Ref{Cint}(0)
-    if δ !== nothing
+    if q !== nothing
+        check(ccall((:lmm_kernel_tag_create_sho, liblmm), Cint, (Cdouble, Ref{Cint}), q, tr))
+    elseif δ !== nothing
         av = a === nothing ? Float64[] : a
         GC.@preserve av check(ccall((:lmm_kernel_tag_create_locally_periodic, liblmm), Cint, (Cint, Ptr{Cdouble}, Cdouble, Cdouble, Ref{Cint}),
                                     length(av), a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(av), ρ, δ, tr))
@@ -222,7 +255,7 @@ function _gps(body, fs)
             (kd, v, l) = _desc(f.kernel)
             if kd == 5
                 tts = KTag[]; tgps = LmmGp[]
-                push!(tags, KTag(Cint(0), false, false, false, false, tts))    # registered first, so that the finally destroys the term tags on error
+                push!(tags, KTag(Cint(0), false, false; terms=tts))    # registered first, so that the finally destroys the term tags on error
                 for k in _terms(f.kernel)
                     (tk, tv, tl) = _desc(k); a = _ard(k); α = _alpha(k); ρ = _rho(k); δ = _decay(k)
                     t = _ktag(a, α, ρ, δ)
@@ -232,8 +265,15 @@ function _gps(body, fs)
                 tr = Ref{Cint}(0)
                 GC.@preserve tgps check(ccall((:lmm_kernel_sum_create, liblmm), Cint, (Cint, Ptr{LmmGp}, Ref{Cint}),
                                               length(tgps), pointer(tgps), tr))
-                tags[end] = KTag(tr[], false, false, false, false, tts)
+                tags[end] = KTag(tr[], false, false; terms=tts)
                 push!(gps, LmmGp(kd | (tr[] << 8), v, l, _mean(f.mean)))
+                continue
+            end
+            q = _quality(f.kernel)
+            if q !== nothing                                   # an SHO latent: its tag carries the quality alone
+                t = _ktag(nothing, nothing, nothing, nothing, q)
+                push!(tags, KTag(t, false, false; quality=true))
+                push!(gps, LmmGp(kd | (t << 8), v, l, _mean(f.mean)))
                 continue
             end
             a = _ard(f.kernel); α = _alpha(f.kernel); ρ = _rho(f.kernel); δ = _decay(f.kernel)
@@ -274,6 +314,8 @@ function _tag_grads(t::KTag, d::Integer)
             alpha = t.alpha ? (r = Ref{Cdouble}(0.0);
                                check(ccall((:lmm_kernel_tag_alpha_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) :
                     t.decay ? _rho_decay_grads(t.id) :
+                    t.quality ? (r = Ref{Cdouble}(0.0);
+                                 check(ccall((:lmm_kernel_tag_quality_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) :
                     t.rho ? (r = Ref{Cdouble}(0.0);
                              check(ccall((:lmm_kernel_tag_rho_grad, liblmm), Cint, (Cint, Ref{Cdouble}), t.id, r)); r[]) : nothing,
             terms = terms)
@@ -524,7 +566,7 @@ end
 # are drawn with randn(rng, ...) per sample in the library's order, all indexed by SORTED point (N_all points, new inputs included):
 # for each latent l in order D_l * N_all (D = 1 / 2 / 3 for Matern12 / 32 / 52; component i of sorted point t at i * N_all + t), then,
 # with y only, m * N_all, then, if add_noise, N_all * p.  Returns a vector (no N) or an (n p) x N matrix, by outputs.
-_statespace_dim(kd) = kd == 3 ? 1 : kd == 1 ? 2 : kd == 2 ? 3 : error("state-space inference is served for Matern12, Matern32 and Matern52 latents")
+_statespace_dim(kd) = kd == 3 ? 1 : kd == 1 ? 2 : kd == 2 ? 3 : kd == LMM_KERNEL_SHO ? 2 : error("state-space inference is served for Matern12, Matern32 and Matern52 latents")
 function _statespace_rand(rng::AbstractRNG, fx::ByOutputsFill{HIPOILMM}, N::Integer, y, xs, add_noise::Bool)
     fs, H, σ², x = unpack(fx)
     isposterior(fs) && error("state-space inference is served on a prior OILMM only")
@@ -910,6 +952,9 @@ _ktangent(k::RationalQuadraticKernel, gv, gl, ga=nothing, gα=nothing, gt=nothin
 # d/d rho, which is all the library's one-rho kernel defines; exact for d = 1).
 _ktangent(k::PeriodicKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) =
     gα === nothing ? NoTangent() : Tangent{typeof(k)}(; r=fill(gα / length(k.r), length(k.r)))
+# SHOKernel: gα carries d/d quality (lmm_kernel_tag_quality_grad)
+_ktangent(k::SHOKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing) =
+    gα === nothing ? NoTangent() : Tangent{typeof(k)}(; quality=[gα])
 function _ktangent(k::ScaledKernel, gv, gl, ga=nothing, gα=nothing, gt=nothing)
     (_, vin, _) = _desc(k.kernel)
     return Tangent{typeof(k)}(; kernel=_ktangent(k.kernel, gv * only(k.σ²), gl, ga, gα, gt), σ²=[gv * vin])

@@ -180,6 +180,50 @@ class LocallyPeriodicKernel(PeriodicKernel):
         return super().__repr__()[:-1] + f", decay={self.decay})"
 
 
+class SHOKernel(_Kernel):
+    """variance * exp(-a tau) (cos(eta tau) + (a / eta) sin(eta tau)), tau = |x - x'|, w0 = 2 pi / period, a = w0 / (2 quality),
+    eta = w0 sqrt(1 - 1 / (4 quality^2)): the stochastically driven damped harmonic oscillator (the celerite "SHO" kernel of
+    Foreman-Mackey et al. 2017), a quasi-periodic kernel whose spectrum peaks near 1 / period with a width set by `quality`, and whose
+    paths are once differentiable.  `lengthscale` is the undamped period, one scalar (`.period` is an alias, the PeriodicKernel
+    convention): the kernel is defined for one-dimensional inputs only, the radial form is not positive definite for d > 1.  `quality`
+    is one finite scalar > 1/2 (underdamped).  quality -> 1/2 is Matern32Kernel with sqrt(3) / lengthscale = 2 pi / period; quality <=
+    1/2 (critically damped and overdamped) is not served.  It is exactly a two-dimensional linear SDE: the state-space functions
+    (statespace_logpdf, statespace_mean_and_var, statespace_logpdf_and_gradient, statespace_rand) serve it alone or mixed with Matern
+    latents, in O(n).  The dense verbs serve it too (logpdf, posterior and what is asked of it, logpdf_and_gradient with "quality", NaN
+    data; OILMM, IndependentMOGP and dense-H); inputs=True, mean_and_var_vjp, the VFE functions and sum kernels refuse it."""
+    kind = "sho"
+
+    def __init__(self, variance: float = 1.0, lengthscale=1.0, quality: float = 1.0):
+        if np.ndim(lengthscale) != 0:
+            raise ValueError("an SHOKernel's period is one scalar (the kernel is defined for one-dimensional inputs)")
+        super().__init__(variance, lengthscale)
+        self.quality = L.sho_quality(quality)
+
+    @property
+    def period(self):
+        return self.lengthscale
+
+    @period.setter
+    def period(self, v):
+        if np.ndim(v) != 0:
+            raise ValueError("an SHOKernel's period is one scalar")
+        self.lengthscale = float(v)
+
+    def __eq__(self, o):
+        return super().__eq__(o) and self.quality == o.quality
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", quality={self.quality})"
+
+    def desc(self) -> dict:
+        d = super().desc()
+        d["quality"] = self.quality
+        return d
+
+    def key(self) -> tuple:
+        return (self.kind, self.variance, self.lengthscale, None, None, None, self.quality)
+
+
 class KernelSum(_Kernel):
     """variance * sum_c kernels[c](|x - x'| / lengthscale): KernelFunctions' KernelSum (k1 + k2 + ...), with `variance` and the scalar
     `lengthscale` the ScaledKernel and ScaleTransform around the whole sum (1.0: none).  Each term is a base kernel with its own
@@ -718,10 +762,48 @@ def _refuse_sparse(fx, what: str) -> None:
                                   "mean, var and marginals")
 
 
+def _has_sho(k) -> bool:
+    return isinstance(k, SHOKernel) or (isinstance(k, KernelSum) and any(isinstance(t, SHOKernel) for t in k.kernels))
+
+
+def _sho_latent(fx):
+    """(index, kernel) of the first SHO latent of a FiniteGP's (or a model's) latents, else None."""
+    f = fx if isinstance(fx, (IndependentMOGP, ILMM)) else getattr(fx, "f", None)
+    mogp = f if isinstance(f, IndependentMOGP) else (f.f if isinstance(f, ILMM) else None)
+    for l, gp in enumerate(mogp.fs if mogp is not None else ()):
+        if _has_sho(gp.kernel):
+            return l, gp.kernel
+    return None
+
+
+def _refuse_sho(fx, what: str) -> None:
+    """What is not served for SHO latents (gradients with respect to inputs, inducing-point inference) refuses them here, before any
+    library call, so no route evaluates another kernel in their place."""
+    hit = _sho_latent(fx)
+    if hit is not None:
+        raise NotImplementedError(f"{what} is not served for SHO latents (latent {hit[0]} is {hit[1]!r})")
+
+
+def _refuse_sho_dims(fx, what: str, *xs) -> None:
+    """An SHO latent is defined over one-dimensional inputs only: d > 1 is refused before any library call.  xs: the inputs of the
+    call (default: fx.x)."""
+    hit = _sho_latent(fx)
+    if hit is None:
+        return
+    if isinstance(hit[1], KernelSum):
+        raise NotImplementedError(f"{what}: an SHO term inside a KernelSum is not served (latent {hit[0]} is {hit[1]!r})")
+    for x in (xs or (getattr(fx, "x", None),)):
+        d = getattr(x, "dim", 1)
+        if d != 1:
+            raise NotImplementedError(f"{what}: an SHO latent (latent {hit[0]} is {hit[1]!r}) is served for one-dimensional inputs "
+                                      f"only (d = {d})")
+
+
 def _sparse_args(vfe: VFE, fx: "FiniteGP", y, what: str):
     """Checks of elbo / dtc / approx_posterior, all before any library call."""
     if not isinstance(vfe, VFE):
         raise TypeError(f"{what}: the first argument is a VFE(z, jitter)")
+    _refuse_sho(fx, what)
     f, x = fx.f, fx.x
     if isinstance(f, IndependentMOGP):
         raise NotImplementedError(f"{what}: inducing-point inference is not served for an IndependentMOGP (wrap it in an OILMM)")
@@ -823,7 +905,7 @@ def _sparse_mean_and_var(fx: "FiniteGP", add_noise: bool, want_var: bool):
 # Matern12 / 32 / 52 latents over a one-dimensional input are finite-dimensional linear SDEs, so a Kalman filter gives logpdf and an RTS
 # smoother the posterior marginals in O(n), exactly (include/lmm_hip.h, "state space").  The library takes sorted
 # inputs; the sorting, and the merging of new inputs as points without observations, happen here.
-_STATESPACE_KINDS = ("matern12", "matern32", "matern52")
+_STATESPACE_KINDS = ("matern12", "matern32", "matern52", "sho")
 
 
 def _statespace_sorted(xv, y, p: int, xs=None):
@@ -909,7 +991,8 @@ def _statespace_args(fx: "FiniteGP", y, what: str):
 
 
 def statespace_logpdf(fx: "FiniteGP", y, with_regulariser: bool = True) -> float:
-    """logpdf(fx, y) of a prior OILMM whose latents are Matern12 / 32 / 52 over one-dimensional inputs, by a Kalman filter per latent:
+    """logpdf(fx, y) of a prior OILMM whose latents are Matern12 / 32 / 52 or SHO (in any mixture and order) over one-dimensional inputs, by a
+    Kalman filter per latent:
     the value of logpdf (NaN in y included: the missing-data approximation of logpdf) in O(n).  Points may come in any order (they are
     sorted here, stably); a point whose outputs are all NaN is a predict-only step and leaves the value unchanged."""
     y = _statespace_args(fx, y, "statespace_logpdf")
@@ -961,7 +1044,7 @@ def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = T
     """Value and gradient of statespace_logpdf(fx, y) in O(n): {"value", "y", "sigma2", "S", "U", "gps"}, as logpdf_and_gradient returns
     them for a prior OILMM.  "value" is bitwise statespace_logpdf(fx, y, with_regulariser); "y" is shaped and typed like y, in the
     callers' order of points whatever the order of the inputs, and exactly 0 at NaN entries; "gps" (through _gps_grads) holds every
-    latent's "variance", "lengthscale" and "mean".  With NaN in y (points whose outputs are all NaN included) "S" and "U" raise
+    latent's "variance", "lengthscale" and "mean", and an SHO latent's "quality" ("lengthscale" is then d / d period).  With NaN in y (points whose outputs are all NaN included) "S" and "U" raise
     NotImplementedError, as after logpdf_and_gradient.  There is no gradient with respect to the inputs."""
     y = _statespace_args(fx, y, "statespace_logpdf_and_gradient")
     f, x = fx.f, fx.x
@@ -985,14 +1068,14 @@ def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = T
     return out
 
 
-_STATESPACE_DIM = {"matern12": 1, "matern32": 2, "matern52": 3}
+_STATESPACE_DIM = {"matern12": 1, "matern32": 2, "matern52": 3, "sho": 2}
 
 
 def statespace_rand(rng, fx: "FiniteGP", y=None, N: Optional[int] = None, add_noise: bool = True, xs=None):
     """Joint samples of the same models in O(n), exact: of the prior fx (y=None: rand(rng, fx)), or of the posterior given y
     (rand(rng, posterior(fx, y)(x*, sigma2))) at the training inputs (xs=None) or at the new inputs xs ((ns,); merged into the inputs
     as points without observations, only their rows are returned).  Per latent the prior path is the SDE's recursion driven by D
-    standard normals per point (D = 1 / 2 / 3 for Matern12 / 32 / 52), run as a scan; a posterior path is the prior path plus the
+    standard normals per point (D = 1 / 2 / 3 for Matern12 / 32 / 52, 2 for SHO), run as a scan; a posterior path is the prior path plus the
     smoothed mean of the residual data (pathwise conditioning), through the filter and smoother of statespace_mean_and_var.
     `rng` is a NumPy Generator or a DeviceNormals, as for rand; buffers and the result live where the normals do.  Draw order, per
     sample, all indexed by SORTED point (the stable sort of the inputs; n_all counts the new inputs as well):
@@ -1063,6 +1146,7 @@ def logpdf(fx: FiniteGP, y, with_regulariser: bool = True) -> float:
     src/independent_mogp.jl:74-80.  Returns this process's shard of the sum (the whole value when the model
     is not sharded)."""
     _refuse_sparse(fx, "logpdf")
+    _refuse_sho_dims(fx, "logpdf")
     L.ensure_init()
     lib = L.load()
     if _has_nan(y):
@@ -1160,7 +1244,7 @@ def _split_train_x(gx0, train, sizes):
 def _gps_grads(gg, ga, m: int, d: int) -> list:
     """The latents' kernel-parameter gradients: "lengthscale" is a float for an isotropic latent and, for a per-dimension (ARD) one,
     the length-d array d logpdf / d lengthscale_k (its tag's lmm_ard_grad: the array passes multiplier 1).  An RQ latent adds
-    "alpha" (its tag's lmm_kernel_tag_alpha_grad).  A sum latent's "variance" and "lengthscale" are those of the whole sum, and its
+    "alpha" (its tag's lmm_kernel_tag_alpha_grad), an SHO latent "quality" (lmm_kernel_tag_quality_grad; its "lengthscale" is d / d period).  A sum latent's "variance" and "lengthscale" are those of the whole sum, and its
     "terms" hold the per-term gradients (ArdTags.sum_grad)."""
     out = []
     for l in range(m):
@@ -1176,6 +1260,8 @@ def _gps_grads(gg, ga, m: int, d: int) -> list:
             out[-1]["r"] = ga.ard.rho_grad(l)
         if ga.ard.has_decay[l]:
             out[-1]["decay"] = ga.ard.decay_grad(l)
+        if ga.ard.has_quality[l]:
+            out[-1]["quality"] = ga.ard.quality_grad(l)
     return out
 
 
@@ -1199,6 +1285,9 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True, inputs: 
     inputs=True raise NotImplementedError.
     Partial sums over the latent shard."""
     _refuse_sparse(fx, "logpdf_and_gradient")
+    _refuse_sho_dims(fx, "logpdf_and_gradient")
+    if inputs:
+        _refuse_sho(fx, "logpdf_and_gradient(inputs=True)")
     L.ensure_init()
     lib = L.load()
     if _has_nan(y):
@@ -1367,6 +1456,7 @@ def posterior(fx: FiniteGP, y):
     """posterior(fx, y): reference src/oilmm.jl:116-134 (returns ILMM(independent_mogp(posteriors), H) -- again
     an OILMM with the same H) and src/independent_mogp.jl:119-126."""
     _refuse_sparse(fx, "posterior (conditioning on further data)")
+    _refuse_sho_dims(fx, "posterior (conditioning on further data)")
     L.ensure_init()
     lib = L.load()
     if _has_nan(y):
@@ -1417,6 +1507,7 @@ def mean_and_var(fx: FiniteGP, add_noise: bool = True):
     model the outputs are this shard's partial sums (add_noise only on one rank)."""
     if _sparse_post(fx) is not None:
         return _sparse_mean_and_var(fx, add_noise, True)
+    _refuse_sho_dims(fx, "mean_and_var")
     L.ensure_init()
     lib = L.load()
     f, x, s2 = fx.f, fx.x, fx.sigma2
@@ -1463,6 +1554,7 @@ def mean_and_var_vjp(fx: FiniteGP, dmean=None, dvar=None, add_noise: bool = True
     OILMM and IndependentMOGP priors and posteriors (sequentially conditioned and sharded ones included: a shard's partial sum) and
     the dense-H prior, by lmm_oilmm_mean_and_var_grad_xs.  The dense-H posterior and the coupled latent view raise NotImplementedError."""
     _refuse_sparse(fx, "mean_and_var_vjp")
+    _refuse_sho(fx, "mean_and_var_vjp")
     L.ensure_init()
     lib = L.load()
     f, x, s2 = fx.f, fx.x, fx.sigma2
@@ -1503,6 +1595,7 @@ def mean_and_cov(fx: FiniteGP):
     """mean_and_cov(fx): reference src/ilmm.jl:132-139 (ILMM/OILMM) and AbstractGPs' generic form over
     src/independent_mogp.jl:60-63 (IndependentMOGP).  Returns (mean, C) with C (p n) x (p n), by-outputs order."""
     _refuse_sparse(fx, "mean_and_cov")
+    _refuse_sho_dims(fx, "mean_and_cov")
     L.ensure_init()
     lib = L.load()
     f, x, s2 = fx.f, fx.x, fx.sigma2
@@ -1543,6 +1636,7 @@ def cov(fx, x=None, y=None):
     and :184-215 (either one MOInputIsotopicByFeatures); cov(f::IndependentMOGP, x) = cov(f, x, x) (:60-63, :176-181).  Prior or
     (independent) posterior latents; (m n) x (m n2), one lmm_mogp_cross_cov call."""
     _refuse_sparse(fx, "cov")
+    _refuse_sho_dims(fx, "cov", *((getattr(fx, "x", None),) if x is None else (x, x if y is None else y)))
     if isinstance(fx, IndependentMOGP):
         if x is None:
             raise TypeError("cov(f::IndependentMOGP, x[, y]) needs the inputs")
@@ -1581,6 +1675,7 @@ def mean(fx: FiniteGP):
     f, x = fx.f, fx.x
     if _sparse_post(fx) is not None:
         return _sparse_mean_and_var(fx, False, False)[0]
+    _refuse_sho_dims(fx, "mean")
     if isinstance(f, ILMM) and isinstance(x, MOInputIsotopicByOutputs) and (f.is_oilmm or f.f._post is None):
         L.ensure_init()
         unpack(fx)
@@ -1639,6 +1734,7 @@ def rand(rng, fx: FiniteGP, N: Optional[int] = None, jitters=None, add_noise: bo
     `rng` is a numpy Generator; standard normals are drawn on the host in the reference's order (m blocks of n
     latent normals, then n*p noise normals) and handed to the device, as the Julia shim does with randn(rng, ...)."""
     _refuse_sparse(fx, "rand")
+    _refuse_sho_dims(fx, "rand")
     f, x, s2 = fx.f, fx.x, fx.sigma2
     if isinstance(x, MOInputIsotopicByFeatures):          # reference src/independent_mogp.jl:217-220
         s = rand(rng, FiniteGP(f, x.by_outputs(), s2), N, jitters, add_noise)
