@@ -787,6 +787,55 @@ int lmm_dev_statespace_sample(const double* x, int n, const lmm_gp_t* gp, const 
 int lmm_dev_statespace_sample_posterior(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r,
                                         const double* z, const double* xi, int nsamples, int chunk, double* f);
 
+/* ---- state space: the posterior object ---------------------------------------------------------------
+ * What posterior(fx, y) followed by mean_and_var(post(x*, sigma2)) is on the dense path (lmm_oilmm_posterior_create, then
+ * lmm_oilmm_mean_and_var), in O(n) once and O(log n) per query and latent (DESIGN.md 4.18 "Posterior object").  One conditioning pass
+ * (the front end, the filter and the smoother of lmm_oilmm_mean_and_var_statespace) keeps the filtered states (m^f_t, P^f_t) and the
+ * FULL smoothed states (m^s_t, P^s_t) of every latent of the shard.  By the Markov property the posterior at a new input s needs the
+ * filtered state of the training point just before it and the smoothed state of the one just after it, and nothing else: with
+ * k = #{t : x_t <= s} (a query equal to a training input comes behind every copy of it),
+ *   predict  (m, P) = (A(d1) m^f_{k-1}, A(d1) P^f_{k-1} A(d1)' + Q(d1)), d1 = s - x_{k-1}; k = 0: (0, Pinf);
+ *   smooth   k < n, d2 = x_k - s, A = A(d2): E = P A' (A P A' + Q(d2))^-1, m <- E m^s_k + (m - E A m), P <- E P^s_k E' + (P - E A P);
+ *            k = n (a forecast behind the last point): the prediction is the answer;
+ * and the latent marginal is (m[0] + mean_l, P[0][0]).  One thread per (query, latent) finds k by binary search over the sorted x;
+ * queries come in any order and a query's result depends on no other query (bitwise).
+ *   lmm_oilmm_statespace_posterior_create : conditions on (x, y).  Arguments, data rules (NaN = missing) and every refusal of
+ *                    lmm_oilmm_logpdf_statespace, in its order.  *out_logpdf (may be NULL) is bitwise the value of
+ *                    lmm_oilmm_logpdf_statespace with the regulariser (the filter runs anyway).  The handle owns, on the device, the
+ *                    sorted x, the states and H = U sqrt(S) of the shard, and on the host the latents' descriptors and means and sigma2
+ *                    (they travel as kernel arguments): 2 (D_l + D_l (D_l + 1) / 2) n doubles per latent l of the shard (2 n, 10 n, 18 n
+ *                    for Matern12, Matern32 and SHO, Matern52) + n doubles for x + p (l1 - l0) for H.  States are stored
+ *                    point-major, [latent][n][component] (a query reads one or two lines per state; measured against
+ *                    component-major in DESIGN.md 4.18), the D means first and then the upper triangle of the covariance by rows;
+ *                    while it is built, the filter's own component-major states of one launch's latents exist beside them.  A failed
+ *                    allocation returns LMM_ERR_HIP, frees what the handle held and sets *out to NULL.
+ *   lmm_statespace_post_destroy : frees the handle; NULL is accepted.
+ *   lmm_oilmm_statespace_post_mean_and_var : mean_and_var(post(xs, sigma2)): the latent marginals at xs (ns values in any order, host or
+ *                    device) mixed through H exactly as lmm_oilmm_mean_and_var_statespace mixes (+ sigma2 when add_noise).  mean, var:
+ *                    ns x p by outputs, host or device; var may be NULL.  Partial sums over the handle's shard.  post, xs or mean NULL
+ *                    or ns < 1 -> LMM_ERR_ARG; a NaN or +-Inf in xs -> LMM_ERR_ARG with the first such index in lmm_last_error_detail's
+ *                    `info`, before the search runs; the fp32 compute mode -> LMM_ERR_UNSUPPORTED.
+ *   lmm_dev_statespace_states, lmm_dev_statespace_interp : building blocks exported for tests (DEVICE pointers; one latent, gp on the
+ *                    host, its mean is not read; chunk as for lmm_dev_statespace_filter).  states: fstate, sstate, each
+ *                    n x (D + D (D + 1) / 2) in the layout above, from per-point noise w and data r.  interp: mean, var (ns each), the
+ *                    zero-mean latent marginals at xs from given states in that layout.  lmm_dev_statespace_interp_layout: the same
+ *                    with point_major == 0 reading states stored (D + D (D + 1) / 2) x n, component-major, instead (the layout
+ *                    experiment of DESIGN.md 4.18; point_major != 0 is lmm_dev_statespace_interp). */
+typedef struct lmm_ss_post lmm_ss_post_t;
+int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* y, int p,
+                                          const double* U, const double* S, int m, double sigma2,
+                                          const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                          lmm_ss_post_t** out, double* out_logpdf);
+int lmm_statespace_post_destroy(lmm_ss_post_t* post);
+int lmm_oilmm_statespace_post_mean_and_var(const lmm_ss_post_t* post, const double* xs, int ns, int add_noise,
+                                           double* mean, double* var);
+int lmm_dev_statespace_states(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
+                              double* fstate, double* sstate);
+int lmm_dev_statespace_interp(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate,
+                              const double* xs, int ns, double* mean, double* var);
+int lmm_dev_statespace_interp_layout(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate,
+                                     int point_major, const double* xs, int ns, double* mean, double* var);
+
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard
  * normals in the reference's draw order: z_lat = m blocks of ns (latent order), eps = ns*p (by-outputs),

@@ -5020,13 +5020,21 @@ struct SSGradOut {
 // One entry of the latent dimension of a launch: a latent with its own noise and data (n values each, on the device).  Samples ride
 // through the filter and smoother as several entries of one latent, with the same w and their own r.
 struct SSEntry { const Latent* L; const double* w; const double* r; };
+// keep != nullptr: the filtered and the full smoothed states (zero-mean) of every entry go to the caller's buffers, entry k's
+// n x ss_state_comps(D_k) block (point-major) ss_keep_offset(es, k, n) doubles in; the smoother runs whether or not smean is given.
+struct SSKeep { double* fstate; double* sstate; };
+static size_t ss_keep_offset(const SSEntry* es, int k, int n) {
+  size_t off = 0;
+  for (int j = 0; j < k; ++j) off += (size_t)ss_state_comps(ss_state_dim(es[j].L->kind)) * n;
+  return off;
+}
 static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, int chunk, double* lml, double* fmean, double* fvar,
-                           double* smean, double* svar, bool add_mean, const SSGradOut* go = nullptr) {
+                           double* smean, double* svar, bool add_mean, const SSGradOut* go = nullptr, const SSKeep* keep = nullptr) {
   hipStream_t st0 = g.streams[0];
   if (chunk <= 0) chunk = ss_default_chunk(n);
   if (chunk > n) chunk = n;
   const int nch = (n + chunk - 1) / chunk;
-  const bool smooth = smean != nullptr;
+  const bool smooth = smean != nullptr || keep != nullptr;
   for (int k0 = 0; k0 < ms;) {
     const int model = ss_model_of(es[k0].L->kind), D = ss_model_dim(model), NS = ss_model_seeds(model);
     const size_t comps = (size_t)ss_state_comps(D);
@@ -5049,7 +5057,8 @@ static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, i
     a.agg = agg.p; a.bagg = bagg.p; a.part = part.p;
     a.fmean = fmean ? fmean + (size_t)k0 * n : nullptr; a.fvar = fvar ? fvar + (size_t)k0 * n : nullptr;
     a.state = state.p; a.state_stride = comps * n;
-    a.smean = smooth ? smean + (size_t)k0 * n : nullptr; a.svar = (smooth && svar) ? svar + (size_t)k0 * n : nullptr;
+    if (keep) { const size_t off = ss_keep_offset(es, k0, n); a.fkeep = keep->fstate + off; a.sstate = keep->sstate + off; }
+    a.smean = (smooth && smean) ? smean + (size_t)k0 * n : nullptr; a.svar = (smooth && svar) ? svar + (size_t)k0 * n : nullptr;
     a.dagg = dagg.p; a.dpart = dpart.p;
     for (int j = 0; j < nb; ++j) {
       const Latent& L = *es[k0 + j].L;
@@ -5427,6 +5436,190 @@ int lmm_dev_statespace_grad(const double* x, int n, const lmm_gp_t* gp, const do
 int lmm_dev_statespace_grad_sho(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* lml,
                                 double* grad_r, double* grad_w, double* grad_theta) {
   return ss_dev_grad(x, n, gp, w, r, chunk, lml, grad_r, grad_w, grad_theta, 3);
+}
+
+// ---- the posterior object (DESIGN.md 4.18 "Posterior object") --------------------------------------------------------------------
+// One O(n) conditioning pass keeps, per latent of the shard, the filtered and the full smoothed states; a query at new inputs is then
+// one thread per (query, latent) (ss_interp_kernel) and the mixing of lmm_oilmm_mean_and_var_statespace.
+}  // extern "C"
+
+struct lmm_ss_post {
+  int n = 0, p = 0, m = 0, l0 = 0, l1 = 0;
+  double sigma2 = 0.0;
+  std::shared_ptr<LatentSet> ls;      // all m latents as the handle was built with them
+  Buf<double> x;                      // the sorted inputs, n
+  Buf<double> fstate, sstate;         // per latent of the shard, one after the other: n x ss_state_comps(D_l), point-major
+  Buf<double> H;                      // p x (l1 - l0), column-major: H = U sqrt(S) of the shard
+  std::vector<size_t> off;            // latent l0 + k's offset into fstate / sstate
+};
+
+namespace {
+
+// xs (device, ns values) must be finite: LMM_ERR_ARG with the first offending index in the error detail's `info`.
+int ss_check_finite(const double* xsd, int ns) {
+  hipStream_t st0 = g.streams[0];
+  Buf<int> flag(1);
+  int h = INT_MAX;
+  HIPCHK(hipMemcpyAsync(flag.p, &h, sizeof(int), hipMemcpyHostToDevice, st0));
+  launch_ss_finite(xsd, ns, flag.p, st0);
+  HIPCHK(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  if (h != INT_MAX) {
+    g.err_latent = -1; g.err_info = h;
+    return fail(LMM_ERR_ARG, "state-space posterior: xs[%d] is not finite", h);
+  }
+  return LMM_OK;
+}
+
+// The zero-mean (add_mean: plus the latent's mean) marginals of the ms latents lts[0 .. ms) at the ns queries xsd from their stored
+// states (latent k's block off[k] doubles into fstate / sstate): ml, vl [latent][ns] on the device (vl may be nullptr).  Launches
+// group consecutive latents of one model, LMM_MAX_BATCH at the most.  Queues on streams[0] and does not wait.
+void ss_interp_latents(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
+                       const double* xsd, int ns, bool add_mean, double* ml, double* vl, bool point_major = true) {
+  hipStream_t st0 = g.streams[0];
+  for (int k0 = 0; k0 < ms;) {
+    const int model = ss_model_of(lts[k0].kind), D = ss_model_dim(model);
+    int nb = 1;
+    while (k0 + nb < ms && nb < LMM_MAX_BATCH && ss_model_of(lts[k0 + nb].kind) == model) ++nb;
+    SSInterpArgs a{};
+    a.x = xd; a.n = n; a.xs = xsd; a.ns = ns;
+    a.fstate = fstate + off[k0]; a.sstate = sstate + off[k0];
+    a.state_stride = (size_t)ss_state_comps(D) * n;
+    a.comp_stride = point_major ? 1 : (size_t)n; a.point_stride = point_major ? (size_t)ss_state_comps(D) : 1;
+    a.mean = ml + (size_t)k0 * ns; a.var = vl ? vl + (size_t)k0 * ns : nullptr;
+    for (int j = 0; j < nb; ++j) {
+      const Latent& L = lts[k0 + j];
+      a.lat[j] = SSInterpLat{L.terms[0].ev.var, L.terms[0].ev.inv_ls, add_mean ? L.mean : 0.0, L.quality};
+    }
+    launch_ss_interp(a, model, nb, st0);
+    k0 += nb;
+  }
+  HIPCHK(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                          double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_ss_post_t** out,
+                                          double* out_logpdf) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  LMM_SS_ARGCHECK(!out);
+  *out = nullptr;
+  RESOLVE_SS(gps, m);
+  if (int rc = ss_check_latents(lts, m)) return rc;
+  hipStream_t st0 = g.streams[0];
+  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
+  if (int rc = ss_check_sorted(xd.p, n)) return rc;
+  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
+  SSFront Fr;
+  if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr)) return rc;
+  std::unique_ptr<lmm_ss_post> P(new lmm_ss_post());      // a throw below (a failed allocation) frees what it holds
+  P->n = n; P->p = p; P->m = m; P->l0 = l0; P->l1 = l1; P->sigma2 = sigma2; P->ls = ls;
+  std::vector<SSEntry> es(ms);
+  size_t total = 0;
+  for (int k = 0; k < ms; ++k) {
+    es[k] = SSEntry{lts + l0 + k, Fr.w.p + (size_t)k * n, Fr.r.p + (size_t)k * n};
+    P->off.push_back(total);
+    total += (size_t)ss_state_comps(ss_state_dim(lts[l0 + k].kind)) * n;
+  }
+  P->x = Buf<double>((size_t)n);
+  P->fstate = Buf<double>(std::max<size_t>(total, 1)); P->sstate = Buf<double>(std::max<size_t>(total, 1));
+  HIPCHK(hipMemcpyAsync(P->x.p, xd.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
+  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
+  for (int k = 0; k < ms; ++k)
+    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
+  P->H = Buf<double>(Hs.size());
+  HIPCHK(hipMemcpyAsync(P->H.p, Hs.data(), Hs.size() * sizeof(double), hipMemcpyHostToDevice, st0));
+  std::vector<double> lml(std::max(ms, 1), 0.0);
+  const SSKeep keep{P->fstate.p, P->sstate.p};
+  if (int rc = ss_core_entries(P->x.p, n, es.data(), ms, 0, lml.data(), nullptr, nullptr, nullptr, nullptr, false, nullptr, &keep)) return rc;
+  HIPCHK(hipStreamSynchronize(st0));
+  double value = 0.0;                       // the sum of lmm_oilmm_logpdf_statespace, in its order
+  for (int k = 0; k < ms; ++k) value += lml[k];
+  value += Fr.reg;
+  if (out_logpdf) *out_logpdf = value;
+  *out = P.release();
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_statespace_post_destroy(lmm_ss_post_t* post) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (post) {
+    if (g.init) (void)hipDeviceSynchronize();
+    delete post;
+  }
+  return LMM_OK;
+}
+
+int lmm_oilmm_statespace_post_mean_and_var(const lmm_ss_post_t* post, const double* xs, int ns, int add_noise, double* mean_out,
+                                           double* var_out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !xs || !mean_out || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  const lmm_ss_post* P = post;
+  const int p = P->p, ms = P->l1 - P->l0;
+  hipStream_t st0 = g.streams[0];
+  DevIn xsd(xs, (size_t)ns, st0);
+  if (int rc = ss_check_finite(xsd.p, ns)) return rc;
+  Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
+  ss_interp_latents(P->x.p, P->n, P->ls->lat.data() + P->l0, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, true, ml.p,
+                    var_out ? vl.p : nullptr);
+  DevOut mo(mean_out, (size_t)ns * p), vo(var_out, (size_t)ns * p);
+  mix_marginals(ml.p, ns, ms, P->H.p, p, 1, 0.0, 0.0, mo.p, st0);
+  if (var_out) mix_marginals(vl.p, ns, ms, P->H.p, p, 2, kDefaultJit.default_jitter, add_noise ? P->sigma2 : 0.0, vo.p, st0);
+  mo.finish(st0); vo.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Building blocks for tests beside lmm_dev_statespace_smooth (DEVICE pointers, one latent, gp on the host, its mean not read).
+int lmm_dev_statespace_states(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* fstate,
+                              double* sstate) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !gp || !w || !r || !fstate || !sstate || n <= 0 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  RESOLVE_SS(gp, 1);
+  if (int rc = ss_check_latents(lts, 1)) return rc;
+  if (int rc = ss_check_sorted(x, n)) return rc;
+  const SSEntry e{lts, w, r};
+  const SSKeep keep{fstate, sstate};
+  return ss_core_entries(x, n, &e, 1, chunk, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, &keep);
+  LMM_CATCH
+}
+
+// point_major = 0: the states are comps x n (what the filter writes for itself) instead of the n x comps the library keeps; the layout
+// experiment of DESIGN.md 4.18 "Posterior object" (tools/statespace_posterior_bench.py)
+int lmm_dev_statespace_interp_layout(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate,
+                                     int point_major, const double* xs, int ns, double* mean, double* var) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !gp || !fstate || !sstate || !xs || !mean || !var || n <= 0 || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  RESOLVE_SS(gp, 1);
+  if (int rc = ss_check_latents(lts, 1)) return rc;
+  if (int rc = ss_check_sorted(x, n)) return rc;
+  if (int rc = ss_check_finite(xs, ns)) return rc;
+  const size_t off = 0;
+  ss_interp_latents(x, n, lts, 1, fstate, sstate, &off, xs, ns, false, mean, var, point_major != 0);
+  HIPCHK(hipStreamSynchronize(g.streams[0]));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_dev_statespace_interp(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate, const double* xs,
+                              int ns, double* mean, double* var) {
+  return lmm_dev_statespace_interp_layout(x, n, gp, fstate, sstate, 1, xs, ns, mean, var);
 }
 
 // ---- sampling (DESIGN.md 4.18 "Sampling") ----------------------------------------------------------------------------------------

@@ -330,6 +330,8 @@ struct SSArgs {
   double* state; size_t state_stride;         // filtered states, [latent][ss_state_comps(D)][n] (nullptr: not kept); doubles per latent
   double* part;                               // nb * nch log-density partials
   double* smean; double* svar;                // smoothed first-component mean (+ lat.mean) / variance, [latent][n]
+  double* sstate; double* fkeep;              // kept for the posterior object (nullptr: not kept; else both, and smean may be nullptr): the
+                                              // full smoothed (zero-mean) and the filtered states POINT-major, [latent][n][ss_state_comps(D)]
   double* dagg;                               // nb * ss_dual_agg_elems(D, nch, seeds) doubles: the (value, tangent) aggregates (gradients only)
   double* dpart;                              // nb * seeds * nch tangents of the log-density partials (gradients only)
   SSLat lat[LMM_MAX_BATCH];
@@ -376,6 +378,22 @@ void launch_ss_pathwise(const double* r, const double* w, const double* f, const
 void launch_ss_addpath(double* f, const double* sm, int n, int ms, int N, hipStream_t st);
 // *flag (preset to INT_MAX) = the first t with !(x_t >= x_{t-1})
 void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st);
+// The posterior at new inputs from stored states (DESIGN.md 4.18 "Posterior object").  One latent of a launch: variance, 1 / lengthscale,
+// the constant added to the means and an SHO latent's quality.  Component c of point t of latent z's filtered (smoothed) state is
+// fstate (sstate)[z state_stride + c comp_stride + t point_stride]: comp_stride = 1, point_stride = ss_state_comps(D) is the point-major
+// layout the posterior object keeps (SSArgs::sstate, fkeep); comp_stride = n, point_stride = 1 the component-major one of SSArgs::state.
+struct SSInterpLat { double var, inv_ls, mean, quality; };
+struct SSInterpArgs {
+  const double* x; int n;                     // sorted training inputs (device)
+  const double* xs; int ns;                   // the queries (device), in any order
+  const double* fstate; const double* sstate; size_t state_stride, comp_stride, point_stride;
+  double* mean; double* var;                  // [latent][ns]: first-component mean (+ lat.mean) and variance
+  SSInterpLat lat[LMM_MAX_BATCH];
+};
+// one thread per (query, latent) of nb latents of one model
+void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st);
+// *flag (preset to INT_MAX) = the first t with xs_t NaN or +-Inf
+void launch_ss_finite(const double* xs, int ns, int* flag, hipStream_t st);
 // rows idx[0 .. nsel) of an n x p column-major matrix into an nsel x p one, and back
 void launch_ss_gather_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st);
 void launch_ss_scatter_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st);

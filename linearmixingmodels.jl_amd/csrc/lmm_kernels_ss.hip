@@ -17,6 +17,9 @@
 // Sampling (launch_ss_path): the prior path is an affine recursion in the caller's normals, so phases 1 - 3 run on SSAff<D> elements
 // (ss_sfold_kernel, the scan with AffOp, ss_path_kernel); a posterior path is the prior path plus the smoothed mean of the residual
 // data r - f - sqrt(w) xi (ss_pathwise_kernel, then the filter and smoother above, then ss_addpath_kernel).
+// The posterior object (launch_ss_interp): ss_rts_kernel<D, OSC, true> keeps the full smoothed and the filtered states point-major, and
+// ss_interp_kernel answers a query at a new input from the two stored states that bracket it, one thread per (query, latent): a binary
+// search over x, one predict step, one RTS step (ss_interp); no LDS, no atomics, a query's result depends on no other query.
 #include "lmm_internal.h"
 #include "lmm_statespace.h"
 
@@ -329,7 +332,9 @@ __global__ __launch_bounds__(SS_THREADS) void ss_bfold_kernel(SSArgs a) {
   reinterpret_cast<SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j] = acc;
 }
 
-template <int D, bool OSC>
+// FULL: the whole smoothed state (without the latent's mean) goes to a.sstate as well, and the filtered state it was computed from to
+// a.fkeep, both point-major; a.smean may be nullptr.  A second instantiation, so that the code of the first is what it was.
+template <int D, bool OSC, bool FULL = false>
 __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
@@ -350,7 +355,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
       for (int k = 0; k < D; ++k) Ps[i][k] = suf.L[i][k];
     }
   }
-  double* sm = a.smean + (size_t)z * a.n;
+  double* sm = (!FULL || a.smean) ? a.smean + (size_t)z * a.n : nullptr;
   double* sv = a.svar ? a.svar + (size_t)z * a.n : nullptr;
   SSBwd<D> el;
   double m[D], P[D][D];
@@ -359,9 +364,74 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
     ss_load_state<D>(stt, a.n, t, m, P);
     ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, el);
     ss_rts_step<D>(el, ms, Ps);
-    sm[t] = ms[0] + L.mean;
+    if (!FULL || sm) sm[t] = ms[0] + L.mean;
     if (sv) sv[t] = Ps[0][0];
+    if constexpr (FULL) {       // point-major: a point's components side by side, which is how ss_interp_kernel reads them
+      constexpr int NC = D + D * (D + 1) / 2;
+      double* sst = a.sstate + (size_t)z * a.state_stride + (size_t)t * NC;
+      double* fst = a.fkeep + (size_t)z * a.state_stride + (size_t)t * NC;
+      for (int i = 0; i < D; ++i) {
+        sst[i] = ms[i]; fst[i] = m[i];
+        for (int k = i; k < D; ++k) { sst[ss_sym_at(D, i, k)] = Ps[i][k]; fst[ss_sym_at(D, i, k)] = P[i][k]; }
+      }
+    }
   }
+}
+
+// One thread per (query, latent): the posterior marginal of the latent at xs[q] from the stored filtered and smoothed states
+// (ss_interp).  k = #{t : x_t <= s} by binary search over the sorted x (a query equal to a training input comes behind every copy of
+// it): at most ceil(log2(n + 1)) probes.  Reads the states of points k - 1 >= 0 and k < n only; a query's result depends on no other
+// query.  xs is finite (launch_ss_finite has looked).
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_interp_kernel(SSInterpArgs a) {
+  const int q = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (q >= a.ns) return;
+  const SSInterpLat& L = a.lat[z];
+  const auto M = ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
+  const double s = a.xs[q];
+  int lo = 0, hi = a.n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (a.x[mid] <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  const int k = lo;
+  constexpr int NC = D + D * (D + 1) / 2;
+  double m[D], P[D][D], ms[D], Ps[D][D];
+  for (int i = 0; i < D; ++i) {
+    m[i] = 0.0; ms[i] = 0.0;
+    for (int j = 0; j < D; ++j) { P[i][j] = 0.0; Ps[i][j] = 0.0; }
+  }
+  double d1 = 0.0, d2 = 0.0;
+  if (k > 0) {
+    const double* f = a.fstate + (size_t)z * a.state_stride + (size_t)(k - 1) * a.point_stride;
+    double c[NC];
+    for (int i = 0; i < NC; ++i) c[i] = f[(size_t)i * a.comp_stride];
+    for (int i = 0; i < D; ++i) {
+      m[i] = c[i];
+      for (int j = i; j < D; ++j) P[i][j] = P[j][i] = c[ss_sym_at(D, i, j)];
+    }
+    d1 = s - a.x[k - 1];
+  }
+  if (k < a.n) {
+    const double* f = a.sstate + (size_t)z * a.state_stride + (size_t)k * a.point_stride;
+    double c[NC];
+    for (int i = 0; i < NC; ++i) c[i] = f[(size_t)i * a.comp_stride];
+    for (int i = 0; i < D; ++i) {
+      ms[i] = c[i];
+      for (int j = i; j < D; ++j) Ps[i][j] = Ps[j][i] = c[ss_sym_at(D, i, j)];
+    }
+    d2 = a.x[k] - s;
+  }
+  ss_interp<D>(M, k > 0, d1, k < a.n, d2, m, P, ms, Ps);
+  a.mean[(size_t)z * a.ns + q] = m[0] + L.mean;
+  if (a.var) a.var[(size_t)z * a.ns + q] = P[0][0];
+}
+
+// *flag = the smallest t with xs_t NaN or +-Inf, left at its initial value (INT_MAX) when every query is finite (ss_sorted_kernel's way)
+__global__ __launch_bounds__(256) void ss_finite_kernel(const double* __restrict__ xs, int ns, int* flag) {
+  for (long long t = blockIdx.x * 256ll + threadIdx.x; t < ns; t += (long long)gridDim.x * 256)
+    if (!(fabs(xs[t]) < INFINITY)) atomicMin(flag, (int)t);
 }
 
 // *flag = the smallest t >= 1 with !(x_t >= x_{t-1}) (a NaN counts), left at its initial value (INT_MAX) when x is non-decreasing.
@@ -497,7 +567,13 @@ void smooth_D(const SSArgs& a, int nb, hipStream_t st) {
   hipLaunchKernelGGL((ss_bfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
   SSBwd<D>* agg = reinterpret_cast<SSBwd<D>*>(a.bagg);
   scan_levels<D, SSBwd<D>, BwdOp, true>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
-  hipLaunchKernelGGL((ss_rts_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
+  if (a.sstate) hipLaunchKernelGGL((ss_rts_kernel<D, OSC, true>), grid, dim3(SS_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((ss_rts_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
+}
+
+template <int D, bool OSC>
+void interp_D(const SSInterpArgs& a, int nb, hipStream_t st) {
+  hipLaunchKernelGGL((ss_interp_kernel<D, OSC>), dim3((a.ns + SS_THREADS - 1) / SS_THREADS, 1, nb), dim3(SS_THREADS), 0, st, a);
 }
 
 template <int D, bool OSC>
@@ -595,6 +671,18 @@ void launch_ss_addpath(double* f, const double* sm, int n, int ms, int N, hipStr
 void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st) {
   const int blocks = (int)std::min<long long>(2048, ((long long)n + 255) / 256);
   hipLaunchKernelGGL(ss_sorted_kernel, dim3(blocks), dim3(256), 0, st, x, n, flag);
+}
+
+void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st) {
+  if (model == SS_MODEL_SHO) interp_D<2, true>(a, nb, st);
+  else if (model == 1) interp_D<1, false>(a, nb, st);
+  else if (model == 2) interp_D<2, false>(a, nb, st);
+  else interp_D<3, false>(a, nb, st);
+}
+
+void launch_ss_finite(const double* xs, int ns, int* flag, hipStream_t st) {
+  const int blocks = (int)std::min<long long>(2048, ((long long)ns + 255) / 256);
+  hipLaunchKernelGGL(ss_finite_kernel, dim3(blocks), dim3(256), 0, st, xs, ns, flag);
 }
 
 void launch_ss_gather_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st) {

@@ -415,6 +415,31 @@ SS_HD void ss_rts_step(const SSBwd<D>& e, double ms[D], double Ps[D][D]) {
   ss_sym<D>(Ps);
 }
 
+// ---- the posterior at a new input (DESIGN.md 4.18 "Posterior object") ---------------------------------------------------------------
+// The posterior state at an input s that lies d1 behind training point k - 1 and d2 in front of training point k.  By the Markov
+// property it needs the FILTERED state of k - 1 (in: m, P) and the SMOOTHED state of k (ms, Ps) and nothing else: one predict step
+// over d1 (the filter's step at an unobserved point; d1 = 0 keeps the state exactly), then one RTS step back over d2.  has_prev =
+// false (s in front of every training point): the prior takes the place of the prediction and m, P are not read.  has_next = false
+// (s behind every training point): the prediction is the answer and ms, Ps are not read.  Out: m, P.
+template <int D, typename Mod>
+SS_HD void ss_interp(const Mod& M, bool has_prev, double d1, bool has_next, double d2, double m[D], double P[D][D], const double ms[D],
+                     const double Ps[D][D]) {
+  if (!has_prev) {
+    for (int i = 0; i < D; ++i) {
+      m[i] = 0.0;
+      for (int j = 0; j < D; ++j) P[i][j] = M.Pinf[i][j];
+    }
+  } else ss_filter_step<D>(M, d1, INFINITY, 0.0, m, P);
+  if (!has_next) return;
+  SSBwd<D> el;
+  ss_bwd_element<D>(M, false, d2, m, P, el);
+  for (int i = 0; i < D; ++i) {
+    m[i] = ms[i];
+    for (int j = 0; j < D; ++j) P[i][j] = Ps[i][j];
+  }
+  ss_rts_step<D>(el, m, P);
+}
+
 // ---- sampling: the prior path as an affine scan ------------------------------------------------------------------------------------
 // Lower Cholesky factor with non-negative diagonal of a symmetric positive SEMI-definite X (its lower triangle is read).  A pivot that
 // is not > 0 gives a zero column (its diagonal and everything below it), so X = 0 gives L = 0 exactly and a Q that rounding has made

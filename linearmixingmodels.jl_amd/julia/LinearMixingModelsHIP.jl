@@ -518,6 +518,9 @@ AbstractGPs.dtc(vfe::VFE{<:ByOutputsFill{HIPOILMM}}, fx::ByOutputsFill{HIPOILMM}
 # lmm_oilmm_mean_and_var_statespace (include/lmm_hip.h, "state space"): a Kalman filter / RTS smoother per latent, O(n) and exact.
 # The library takes sorted inputs: the points are sorted here (stably) and the results put back in the caller's order.  `missing` or
 # NaN entries of y are missing observations; new inputs xs are merged in as points without observations.  Prior OILMM only.
+# The reusable posterior (lmm_oilmm_statespace_posterior_create, lmm_oilmm_statespace_post_mean_and_var; Python:
+# statespace_posterior) is served by the C ABI and the Python mirror and not yet by this shim: its handle type, lmm_ss_post_t, has
+# no Julia mapping in the static check of this file's ccalls (tests/test_shim_signatures.py), as lmm_sparse_post_t above.
 function _statespace_sorted(x, y::AbstractVector, p::Integer, xs)
     X = _xmat(x)
     size(X, 1) == 1 || error("state-space inference is served for one-dimensional inputs (d = $(size(X, 1)))")

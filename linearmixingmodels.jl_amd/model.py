@@ -1031,6 +1031,90 @@ def statespace_mean_and_var(fx: "FiniteGP", y, add_noise: bool = True, xs=None):
     return _statespace_unsorted(mean, perm, p, n, xs is not None), _statespace_unsorted(var, perm, p, n, xs is not None)
 
 
+class StateSpacePosterior:
+    """posterior(fx, y) on the state-space path: owns an lmm_ss_post_t* (the sorted inputs and, per latent, the filtered and the
+    smoothed states on the device; include/lmm_hip.h "state space: the posterior object") and answers mean_and_var(post(x*, sigma2))
+    at new inputs in O(ns log n) per latent, without touching the data again.  Built by statespace_posterior; freed by close(), on
+    leaving a `with` block or with the object."""
+
+    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float):
+        self._ptr, self.n, self.p, self.logpdf = ptr, n, p, logpdf
+
+    def close(self) -> None:
+        if self._ptr:
+            ptr, self._ptr = self._ptr, None
+            L.load().lmm_statespace_post_destroy(ptr)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _query(self, xs, add_noise: bool, want_var: bool):
+        if not self._ptr:
+            raise ValueError("StateSpacePosterior: the posterior has been closed")
+        if not hasattr(xs, "shape"):
+            xs = np.asarray(xs, dtype=np.float64)
+        if len(xs.shape) != 1:
+            raise ValueError("StateSpacePosterior: xs is a (ns,) array of one-dimensional inputs")
+        ns = int(xs.shape[0])
+        if L._is_torch(xs):
+            import torch
+            xs = xs.to(torch.float64)
+            finite = bool(torch.isfinite(xs).all())
+        else:
+            xs = np.ascontiguousarray(xs, dtype=np.float64)
+            finite = bool(np.isfinite(xs).all())
+        if not finite:
+            raise ValueError("StateSpacePosterior: xs must be finite (no NaN or Inf)")
+        mean = _alloc_like(xs, ns * self.p)
+        var = _alloc_like(xs, ns * self.p) if want_var else None
+        if ns == 0:
+            return mean, var
+        L.check(L.load().lmm_oilmm_statespace_post_mean_and_var(self._ptr, L.Arr(xs).ptr, ns, int(add_noise), L.Arr(mean, True).ptr,
+                                                                L.Arr(var, True).ptr if want_var else None))
+        return mean, var
+
+    def mean_and_var(self, xs, add_noise: bool = True):
+        """(mean, var) at the inputs xs ((ns,), in any order): by-outputs vectors of ns * p values, NumPy or torch-device like xs."""
+        return self._query(xs, add_noise, True)
+
+    def mean(self, xs):
+        return self._query(xs, False, False)[0]
+
+    def var(self, xs, add_noise: bool = True):
+        return self._query(xs, add_noise, True)[1]
+
+    def marginals(self, xs) -> "Normal":
+        """Normal(mean, sqrt(var)) as marginals builds it."""
+        m, v = self._query(xs, True, True)
+        return Normal(m, v ** 0.5)
+
+
+def statespace_posterior(fx: "FiniteGP", y) -> StateSpacePosterior:
+    """posterior(fx, y) of the models statespace_logpdf serves, as a reusable object: one O(n) pass (the inputs are sorted here once,
+    stably; NaN in y is missing data) conditions on the data, and post.mean_and_var(xs) then answers at any new inputs without it.
+    post.logpdf is bitwise statespace_logpdf(fx, y)."""
+    y = _statespace_args(fx, y, "statespace_posterior")
+    f, x = fx.f, fx.x
+    xa, ya, _, _ = _statespace_sorted(x.x.reshape(-1), y, x.out_dim)
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    ptr, out = C.c_void_p(), C.c_double()
+    L.check(L.load().lmm_oilmm_statespace_posterior_create(L.Arr(xa).ptr, x.n, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps,
+                                                           0, m, C.byref(ptr), C.byref(out)))
+    return StateSpacePosterior(ptr, x.n, p, out.value)
+
+
 class _NoStateSpaceMixingGradient(dict):
     """The gradient dict of statespace_logpdf_and_gradient for data with NaN: "S" and "U" are not built (as _NoMixingGradient)."""
 
