@@ -836,6 +836,35 @@ int lmm_dev_statespace_interp(const double* x, int n, const lmm_gp_t* gp, const 
 int lmm_dev_statespace_interp_layout(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate,
                                      int point_major, const double* xs, int ns, double* mean, double* var);
 
+/* ---- state space: sampling from the posterior object ------------------------------------------------
+ * Joint samples of post(xs, sigma2) from the handle, without touching the data again (DESIGN.md 4.18 "Sampling from the posterior
+ * object"): what lmm_oilmm_rand_statespace with y draws at new inputs, in O(ns + training points between the smallest and the largest
+ * query) per latent and sample.  Given the data the states are a Markov chain that runs backwards, s_j | s_{j+1}, y = N(g_j + E_j
+ * s_{j+1}, L_j) with (E_j, g_j, L_j) the smoother's element of the FILTERED state of point j, so a path is an affine scan from the right
+ * over the WINDOW of the sorted queries q_0 <= ... <= q_{ns-1}: the queries and the training points first .. first + count - 1, first =
+ * #{t : x_t <= q_0}, count = #{t : x_t <= q_{ns-1}} - first, ordered by input (a training point before an equal query, equal queries in
+ * their order); W = ns + count.  The last window point is q_{ns-1} and starts the chain at its posterior state (the state
+ * lmm_oilmm_statespace_post_mean_and_var reads its marginal from).  Factors are upper triangular (the highest derivative is eliminated
+ * first), which keeps the law exact where queries lie 1e-12 lengthscales from a training input.  No atomics: results are bitwise
+ * reproducible, and sample q of a call is bitwise the one-sample call on its normals.
+ *   lmm_statespace_post_window : *first and *count for q_0 = lo and q_{ns-1} = hi (host scalars), so that a caller can size z.  lo > hi,
+ *                    a NaN or +-Inf, or a NULL pointer -> LMM_ERR_ARG.
+ *   lmm_oilmm_statespace_post_rand : nsamples joint samples at xs (ns values, NON-DECREASING and finite, host or device; otherwise
+ *                    LMM_ERR_ARG with the first offending index in lmm_last_error_detail's `info`).  z: per sample, for each latent l
+ *                    of the handle's shard in order, D_l W standard normals, component-major over window positions (component i of
+ *                    window point j at i W + j).  eps: per sample ns p standard normals by outputs, read only when add_noise (and then
+ *                    required).  out: per sample ns x p by outputs, H f + sqrt(sigma2) eps, mixed exactly as lmm_oilmm_rand_statespace
+ *                    mixes; partial sums over the handle's shard.  z, eps, out: host or device.  post, xs, z or out NULL, ns < 1 or
+ *                    nsamples < 1 -> LMM_ERR_ARG; the fp32 compute mode -> LMM_ERR_UNSUPPORTED ("Float64 only").
+ *   lmm_dev_statespace_post_sample : building block exported for tests (DEVICE pointers; one latent, gp on the host, its mean is not
+ *                    read): the zero-mean paths f ([sample][ns], in the order of the sorted xs) from given states in the layout of
+ *                    lmm_dev_statespace_states and z ([sample][D W]); chunk: window points per thread, 0 = the library's default. */
+int lmm_statespace_post_window(const lmm_ss_post_t* post, double lo, double hi, int* first, int* count);
+int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, int ns, const double* z, const double* eps,
+                                   int nsamples, int add_noise, double* out);
+int lmm_dev_statespace_post_sample(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate,
+                                   const double* xs, int ns, const double* z, int nsamples, int chunk, double* f);
+
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard
  * normals in the reference's draw order: z_lat = m blocks of ns (latent order), eps = ns*p (by-outputs),

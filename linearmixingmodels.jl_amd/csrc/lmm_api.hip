@@ -5802,6 +5802,152 @@ int lmm_dev_statespace_sample_posterior(const double* x, int n, const lmm_gp_t* 
   LMM_CATCH
 }
 
+// ---- sampling from the posterior object (DESIGN.md 4.18 "Sampling from the posterior object") ------------------------------------
+// first = #{t : x_t <= lo}, count = #{t : x_t <= hi} - first; xsd != nullptr: (lo, hi) = (xsd[0], xsd[ns - 1]), read on the device
+static void ss_window_bounds(const double* xd, int n, const double* xsd, int ns, double lo, double hi, int* first, int* count) {
+  hipStream_t st0 = g.streams[0];
+  Buf<int> ab(2);
+  int h[2] = {0, 0};
+  launch_ss_window_bounds(xd, n, xsd, ns, lo, hi, ab.p, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h, ab.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  *first = h[0]; *count = h[1] - h[0];
+}
+
+// The window of the queries xsd (device, ns values): they must be finite and non-decreasing (LMM_ERR_ARG with the first offending
+// index in the error detail's `info`).  src: W = ns + count entries (launch_ss_window).
+struct SSWindow { int first = 0, count = 0, W = 0; Buf<int> src; };
+static int ss_window(const double* xd, int n, const double* xsd, int ns, SSWindow& w) {
+  if (int rc = ss_check_finite(xsd, ns)) return rc;
+  if (int rc = ss_check_sorted(xsd, ns)) return rc;
+  ss_window_bounds(xd, n, xsd, ns, 0.0, 0.0, &w.first, &w.count);
+  if ((long long)ns + w.count > INT_MAX) return fail(LMM_ERR_ARG, "state-space posterior: the window of %d queries and %d points is too long", ns, w.count);
+  w.W = ns + w.count;
+  w.src = Buf<int>((size_t)w.W);
+  launch_ss_window(xd, n, xsd, ns, w.first, w.count, w.src.p, g.streams[0]);
+  HIPCHK(hipGetLastError());
+  return LMM_OK;
+}
+
+// Posterior paths of the ms latents lts[0 .. ms) at the sorted queries for N samples from their stored states (latent k's block
+// off[k] doubles into fstate / sstate): f[sample][latent][ns] on the device, with the latent's mean when add_mean.  z: sample 0's
+// normals of lts[0] on the device, the latents one after the other (D_l W values each, component-major over window positions), the
+// samples z_stride doubles apart.  The (latent, sample) pairs run in launches of one model.  Returns with streams[0] drained.
+static int ss_post_paths(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
+                         const double* xsd, int ns, const SSWindow& w, int N, const double* z, size_t z_stride, int chunk, bool add_mean,
+                         double* f) {
+  hipStream_t st0 = g.streams[0];
+  const int W = w.W;
+  if (chunk <= 0) chunk = ss_default_chunk(W);
+  if (chunk > W) chunk = W;
+  const int nch = (W + chunk - 1) / chunk;
+  std::vector<size_t> zoff(std::max(ms, 1), 0);
+  for (int k = 1; k < ms; ++k) zoff[k] = zoff[k - 1] + (size_t)ss_state_dim(lts[k - 1].kind) * W;
+  const long long ne = (long long)ms * N;
+  for (long long e0 = 0; e0 < ne;) {
+    const int model = ss_model_of(lts[e0 / N].kind), D = ss_model_dim(model);
+    const size_t per = ss_aff_agg_elems(D, nch) * sizeof(double);
+    const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / per));
+    int nb = 1;
+    while (e0 + nb < ne && nb < nbmax && ss_model_of(lts[(e0 + nb) / N].kind) == model) ++nb;
+    Buf<double> agg((size_t)nb * ss_aff_agg_elems(D, nch));
+    SSPostArgs a{};
+    a.x = xd; a.n = n; a.xs = xsd; a.ns = ns; a.src = w.src.p; a.first = w.first; a.W = W; a.chunk = chunk; a.nch = nch; a.agg = agg.p;
+    for (int j = 0; j < nb; ++j) {
+      const int k = (int)((e0 + j) / N), q = (int)((e0 + j) % N);
+      const Latent& L = lts[k];
+      a.lat[j] = SSPostLat{L.terms[0].ev.var, L.terms[0].ev.inv_ls, add_mean ? L.mean : 0.0, L.quality, fstate + off[k], sstate + off[k],
+                           z + (size_t)q * z_stride + zoff[k], f + ((size_t)q * ms + k) * ns};
+    }
+    launch_ss_post_path(a, model, nb, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));          // agg goes back to the pool
+    e0 += nb;
+  }
+  return LMM_OK;
+}
+
+int lmm_statespace_post_window(const lmm_ss_post_t* post, double lo, double hi, int* first, int* count) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !first || !count) return fail(LMM_ERR_ARG, "bad arguments");
+  if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi)
+    return fail(LMM_ERR_ARG, "state-space posterior: a window needs finite lo <= hi (lo = %g, hi = %g)", lo, hi);
+  ss_window_bounds(post->x.p, post->n, nullptr, 0, lo, hi, first, count);
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, int ns, const double* z, const double* eps, int nsamples,
+                                   int add_noise, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !xs || !out || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
+  if (!z) return fail(LMM_ERR_ARG, "z is NULL");
+  if (add_noise && !eps) return fail(LMM_ERR_ARG, "eps is NULL");
+  const lmm_ss_post* P = post;
+  const int p = P->p, ms = P->l1 - P->l0, mk = std::max(ms, 1);
+  const Latent* lts = P->ls->lat.data() + P->l0;
+  hipStream_t st0 = g.streams[0];
+  DevIn xsd(xs, (size_t)ns, st0);
+  SSWindow w;
+  if (int rc = ss_window(P->x.p, P->n, xsd.p, ns, w)) return rc;
+  size_t zshard = 0;                               // doubles of one sample's z
+  for (int k = 0; k < ms; ++k) zshard += (size_t)ss_state_dim(lts[k].kind) * w.W;
+  DevOut od(out, (size_t)ns * p * nsamples);
+  const int group = ss_sample_group(std::max(w.W, ns), ms, nsamples);
+  for (int q0 = 0; q0 < nsamples; q0 += group) {
+    const int ng = std::min(group, nsamples - q0);
+    SSNormals zd(z, zshard, 0, zshard, q0, ng, st0), epsd(add_noise ? eps : nullptr, (size_t)ns * p, 0, (size_t)ns * p, q0, ng, st0);
+    Buf<double> f((size_t)ng * mk * ns);           // [sample][latent of the shard][ns]
+    if (int rc = ss_post_paths(P->x.p, P->n, lts, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, w, ng, zd.p, zd.stride, 0, true,
+                               f.p))
+      return rc;
+    // the mixing of lmm_oilmm_rand_statespace: H f + sqrt(sigma2) eps
+    for (int q = 0; q < ng; ++q)
+      launch_mix(f.p + (size_t)q * ms * ns, ns, ms, P->H.p, p, 1, 0.0, 0.0, add_noise ? epsd.p + (size_t)q * epsd.stride : nullptr,
+                 std::sqrt(P->sigma2), od.p + (size_t)(q0 + q) * ns * p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));            // the group's buffers go back to the pool
+  }
+  od.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Building block for tests beside lmm_dev_statespace_interp: ONE latent from DEVICE pointers and given states, its mean not read.
+// z: [sample][D W], f: [sample][ns].
+int lmm_dev_statespace_post_sample(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate, const double* xs,
+                                   int ns, const double* z, int nsamples, int chunk, double* f) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!x || !gp || !fstate || !sstate || !xs || !z || !f || n <= 0 || ns < 1 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  RESOLVE_SS(gp, 1);
+  if (int rc = ss_check_latents(lts, 1)) return rc;
+  if (int rc = ss_check_sorted(x, n)) return rc;
+  SSWindow w;
+  if (int rc = ss_window(x, n, xs, ns, w)) return rc;
+  const size_t zs = (size_t)ss_state_dim(lts[0].kind) * w.W, off = 0;
+  const int group = ss_sample_group(std::max(w.W, ns), 1, nsamples);
+  for (int q0 = 0; q0 < nsamples; q0 += group) {
+    const int ng = std::min(group, nsamples - q0);
+    if (int rc = ss_post_paths(x, n, lts, 1, fstate, sstate, &off, xs, ns, w, ng, z + (size_t)q0 * zs, zs, chunk, false,
+                               f + (size_t)q0 * ns))
+      return rc;
+  }
+  return LMM_OK;
+  LMM_CATCH
+}
+
 // Standard normals on the device (Philox4x32-10 + Box-Muller, Float64): out[j], j < count, reproducible for (seed, stream).
 // out may be a host or a device pointer.  Optional companion of lmm_lmm_rand / lmm_lmm_rand_multi, whose normals are
 // caller-supplied: the Julia shim draws them from the reference's rng on the host; this generator serves callers that do not

@@ -394,6 +394,28 @@ struct SSInterpArgs {
 void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st);
 // *flag (preset to INT_MAX) = the first t with xs_t NaN or +-Inf
 void launch_ss_finite(const double* xs, int ns, int* flag, hipStream_t st);
+// Sampling from the posterior object (DESIGN.md 4.18 "Sampling from the posterior object").  The window of the sorted queries xs: the
+// ns queries and the training points first .. first + count - 1 that lie between the smallest and the largest of them, W = ns + count
+// points ordered by input (a training point before an equal query, equal queries in their order).
+// out[0] = #{t : x_t <= lo}, out[1] = #{t : x_t <= hi} (device); xs != nullptr: lo = xs[0], hi = xs[ns - 1] are read on the device
+void launch_ss_window_bounds(const double* x, int n, const double* xs, int ns, double lo, double hi, int* out, hipStream_t st);
+// src[W] (device): window position j holds training point src[j] >= 0, or query -1 - src[j]; one thread per point, no atomics
+void launch_ss_window(const double* x, int n, const double* xs, int ns, int first, int count, int* src, hipStream_t st);
+// One (latent, sample) pair of a launch: the latent's parameters, its stored states (device, point-major n x ss_state_comps(D)), the
+// pair's standard normals z (device, D W values, component i of window point j at z[i W + j]) and the path it writes (device, ns values
+// in the order of the sorted queries: the first component of the state + mean).
+struct SSPostLat { double var, inv_ls, mean, quality; const double* fstate; const double* sstate; const double* z; double* f; };
+struct SSPostArgs {
+  const double* x; int n;                     // sorted training inputs (device)
+  const double* xs; int ns;                   // sorted queries (device)
+  const int* src; int first, W;               // the window (launch_ss_window)
+  int chunk, nch;                             // window points per thread; nch = ceil(W / chunk) threads per pair
+  double* agg;                                // nb * ss_aff_agg_elems(D, nch) doubles: the affine aggregates and the scan's levels
+  SSPostLat lat[LMM_MAX_BATCH];
+};
+static_assert(sizeof(SSPostArgs) <= 4096, "SSPostArgs is passed by value: kernel arguments are limited to 4096 bytes");
+// fold from the right, suffix scan and restart of the backward recursion for nb pairs of one model
+void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st);
 // rows idx[0 .. nsel) of an n x p column-major matrix into an nsel x p one, and back
 void launch_ss_gather_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st);
 void launch_ss_scatter_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st);

@@ -20,6 +20,10 @@
 // The posterior object (launch_ss_interp): ss_rts_kernel<D, OSC, true> keeps the full smoothed and the filtered states point-major, and
 // ss_interp_kernel answers a query at a new input from the two stored states that bracket it, one thread per (query, latent): a binary
 // search over x, one predict step, one RTS step (ss_interp); no LDS, no atomics, a query's result depends on no other query.
+// Sampling from the posterior object (launch_ss_post_path): given the data the states at the sorted queries and the training points
+// between them are a Markov chain that runs backwards, an affine recursion in the caller's normals again, so phases 1 - 3 run from the
+// right on SSAff<D> elements built from the stored states (ss_window_kernel, ss_pfold_kernel, the suffix scan with AffRevOp,
+// ss_ppath_kernel); nothing outside the queries' span is read.
 #include "lmm_internal.h"
 #include "lmm_statespace.h"
 
@@ -544,6 +548,166 @@ __global__ __launch_bounds__(256) void ss_addpath_kernel(double* __restrict__ f,
   f[i] = f[i] + sm[((size_t)k * N + q) * n + t];
 }
 
+// ---- sampling from the posterior object --------------------------------------------------------------------------------------------
+// Given the data, the states at the window's points (SSPostArgs: the sorted queries and the training points between the smallest and
+// the largest of them) form a Markov chain that runs BACKWARDS: s_j = E_j s_{j+1} + g_j + U(L_j) zeta_j from the posterior state at the
+// last point (ss_post_element).  That is an affine recursion again, so the three phases of the prior path serve it from the right:
+// ss_pfold_kernel, the suffix scan with AffRevOp, ss_ppath_kernel.  Nothing outside the window is read but the states next to its ends.
+
+// out[0] = #{t : x_t <= lo}, out[1] = #{t : x_t <= hi}; xs != nullptr: (lo, hi) = (xs[0], xs[ns - 1])
+__global__ void ss_window_bounds_kernel(const double* __restrict__ x, int n, const double* __restrict__ xs, int ns, double lo, double hi,
+                                        int* __restrict__ out) {
+  if (threadIdx.x > 1 || blockIdx.x > 0) return;
+  const double s = xs ? (threadIdx.x ? xs[ns - 1] : xs[0]) : (threadIdx.x ? hi : lo);
+  int l = 0, h = n;
+  while (l < h) {
+    const int mid = l + ((h - l) >> 1);
+    if (x[mid] <= s) l = mid + 1;
+    else h = mid;
+  }
+  out[threadIdx.x] = l;
+}
+
+// One thread per window point.  Thread u < count is training point t = first + u, at (t - first) + #{i : q_i < x_t}; thread count + i
+// is query i, at i + #{t : x_t <= q_i} - first.  Both counts are binary searches; the positions are a permutation of 0 .. W - 1 (a
+// stable merge with training points in front of equal queries), so every entry of src is written once.
+__global__ __launch_bounds__(256) void ss_window_kernel(const double* __restrict__ x, int n, const double* __restrict__ xs, int ns,
+                                                        int first, int count, int* __restrict__ src) {
+  const long long u = blockIdx.x * 256ll + threadIdx.x;
+  if (u >= (long long)count + ns) return;
+  if (u < count) {
+    const int t = first + (int)u;
+    const double xt = x[t];
+    int l = 0, h = ns;
+    while (l < h) {
+      const int mid = l + ((h - l) >> 1);
+      if (xs[mid] < xt) l = mid + 1;
+      else h = mid;
+    }
+    src[(long long)u + l] = t;
+  } else {
+    const int i = (int)(u - count);
+    const double s = xs[i];
+    int l = first, h = first + count;       // first <= #{t : x_t <= q_i} <= first + count: q_0 <= q_i <= q_{ns-1}
+    while (l < h) {
+      const int mid = l + ((h - l) >> 1);
+      if (x[mid] <= s) l = mid + 1;
+      else h = mid;
+    }
+    src[(long long)i + (l - first)] = -1 - i;
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void ss_load_point_state(const double* __restrict__ st, long long t, double m[D], double P[D][D]) {
+  constexpr int NC = D + D * (D + 1) / 2;
+  const double* f = st + (size_t)t * NC;
+  for (int i = 0; i < D; ++i) {
+    m[i] = f[i];
+    for (int k = i; k < D; ++k) P[i][k] = P[k][i] = f[ss_sym_at(D, i, k)];
+  }
+}
+
+__device__ __forceinline__ double ss_window_input(const SSPostArgs& a, long long j) {
+  const int s = a.src[j];
+  return s >= 0 ? a.x[s] : a.xs[-1 - s];
+}
+
+// The element of window point j (input xj, its successor's input xn; xn is not read at the last point).  The filtered state of a
+// training point is the stored one; that of a query is the stored one of training point k - 1, k = #{t : x_t <= q} = first + (j - its
+// index among the queries), predicted over q - x_{k-1} (the filter's step at an unobserved point), and (0, Pinf) when k = 0.
+// Reads fstate of points first - 1 .. first + count - 1 (>= 0) and sstate of point first + count (< n) only.
+template <int D, typename Mod>
+__device__ __forceinline__ void ss_window_element(const SSPostArgs& a, const SSPostLat& L, const Mod& M, long long j, double xj, double xn,
+                                                  SSAff<D>& e) {
+  const int s = a.src[j];
+  double m[D], P[D][D], ms[D], Ps[D][D], zeta[D];
+  int k;
+  if (s >= 0) {
+    ss_load_point_state<D>(L.fstate, s, m, P);
+    k = s + 1;
+  } else {
+    k = a.first + (int)(j - (-1 - s));
+    if (k > 0) {
+      ss_load_point_state<D>(L.fstate, k - 1, m, P);
+      ss_filter_step<D>(M, xj - a.x[k - 1], INFINITY, 0.0, m, P);
+    } else {
+      for (int i = 0; i < D; ++i) {
+        m[i] = 0.0;
+        for (int c = 0; c < D; ++c) P[i][c] = M.Pinf[i][c];
+      }
+    }
+  }
+  const bool last = j == a.W - 1, has_next = k < a.n;
+  double dt = xn - xj;
+  for (int i = 0; i < D; ++i) {
+    ms[i] = 0.0;
+    for (int c = 0; c < D; ++c) Ps[i][c] = 0.0;
+  }
+  if (last) {
+    dt = 0.0;
+    if (has_next) {
+      ss_load_point_state<D>(L.sstate, k, ms, Ps);
+      dt = a.x[k] - xj;
+    }
+  }
+  for (int i = 0; i < D; ++i) zeta[i] = L.z[(size_t)i * a.W + j];
+  ss_post_element<D>(M, last, has_next, dt, m, P, ms, Ps, zeta, e);
+}
+
+// the scan's REV hands over (item, what lies to its right): the right operand is applied first
+struct AffRevOp {
+  template <int D> static __device__ __forceinline__ void combine(const SSAff<D>& a, const SSAff<D>& b, SSAff<D>& o) { ss_aff_combine<D>(b, a, o); }
+};
+
+// one thread per run of `chunk` window points, folded from the right: the aggregate maps the state behind the run to the run's first
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_pfold_kernel(SSPostArgs a) {
+  const int c = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (c >= a.nch) return;
+  const SSPostLat& L = a.lat[z];
+  const auto M = ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
+  const long long j0 = (long long)c * a.chunk;
+  const long long j1 = j0 + a.chunk < a.W ? j0 + a.chunk : a.W;
+  SSAff<D> acc, el;
+  double xn = j1 < a.W ? ss_window_input(a, j1) : 0.0;
+  for (long long j = j1 - 1; j >= j0; --j) {
+    const double xj = ss_window_input(a, j);
+    ss_window_element<D>(a, L, M, j, xj, xn, j == j1 - 1 ? acc : el);
+    if (j < j1 - 1) ss_aff_combine<D>(acc, el, acc);
+    xn = xj;
+  }
+  reinterpret_cast<SSAff<D>*>(a.agg)[(size_t)z * a.nch + c] = acc;
+}
+
+// each thread restarts the recursion from the state behind its run (the c of the scanned aggregate of the run to its right) and writes
+// the query rows f[i] = (s_j)_1 + lat.mean
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_ppath_kernel(SSPostArgs a) {
+  const int c = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (c >= a.nch) return;
+  const SSPostLat& L = a.lat[z];
+  const auto M = ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
+  const long long j0 = (long long)c * a.chunk;
+  const long long j1 = j0 + a.chunk < a.W ? j0 + a.chunk : a.W;
+  double s[D];
+  for (int i = 0; i < D; ++i) s[i] = 0.0;           // the last element has A = 0 and ignores this state
+  if (c + 1 < a.nch) {
+    const SSAff<D>& suf = reinterpret_cast<const SSAff<D>*>(a.agg)[(size_t)z * a.nch + c + 1];
+    for (int i = 0; i < D; ++i) s[i] = suf.c[i];
+  }
+  SSAff<D> el;
+  double xn = j1 < a.W ? ss_window_input(a, j1) : 0.0;
+  for (long long j = j1 - 1; j >= j0; --j) {
+    const double xj = ss_window_input(a, j);
+    ss_window_element<D>(a, L, M, j, xj, xn, el);
+    ss_aff_step<D>(el, s);
+    xn = xj;
+    const int q = a.src[j];
+    if (q < 0) L.f[-1 - q] = s[0] + L.mean;
+  }
+}
+
 size_t scan_items(int nch, int W = SS_SCAN) {         // items of every level below the first
   size_t tot = 0;
   int N = nch;
@@ -595,6 +759,15 @@ void path_D(const SSPathArgs& a, int nb, hipStream_t st) {
   SSAff<D>* agg = reinterpret_cast<SSAff<D>*>(a.agg);
   scan_levels<D, SSAff<D>, AffOp, false>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
   hipLaunchKernelGGL((ss_path_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
+}
+
+template <int D, bool OSC>
+void post_path_D(const SSPostArgs& a, int nb, hipStream_t st) {
+  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
+  hipLaunchKernelGGL((ss_pfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
+  SSAff<D>* agg = reinterpret_cast<SSAff<D>*>(a.agg);
+  scan_levels<D, SSAff<D>, AffRevOp, true>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
+  hipLaunchKernelGGL((ss_ppath_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
 }
 
 }  // namespace
@@ -678,6 +851,22 @@ void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st) 
   else if (model == 1) interp_D<1, false>(a, nb, st);
   else if (model == 2) interp_D<2, false>(a, nb, st);
   else interp_D<3, false>(a, nb, st);
+}
+
+void launch_ss_window_bounds(const double* x, int n, const double* xs, int ns, double lo, double hi, int* out, hipStream_t st) {
+  hipLaunchKernelGGL(ss_window_bounds_kernel, dim3(1), dim3(64), 0, st, x, n, xs, ns, lo, hi, out);
+}
+
+void launch_ss_window(const double* x, int n, const double* xs, int ns, int first, int count, int* src, hipStream_t st) {
+  const long long W = (long long)ns + count;
+  hipLaunchKernelGGL(ss_window_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, x, n, xs, ns, first, count, src);
+}
+
+void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st) {
+  if (model == SS_MODEL_SHO) post_path_D<2, true>(a, nb, st);
+  else if (model == 1) post_path_D<1, false>(a, nb, st);
+  else if (model == 2) post_path_D<2, false>(a, nb, st);
+  else post_path_D<3, false>(a, nb, st);
 }
 
 void launch_ss_finite(const double* xs, int ns, int* flag, hipStream_t st) {

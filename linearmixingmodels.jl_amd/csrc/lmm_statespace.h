@@ -462,6 +462,29 @@ SS_HD void ss_chol_psd(const double X[D][D], double L[D][D]) {
   }
 }
 
+// UPPER triangular factor with non-negative diagonal, U U' = X, of a symmetric positive semi-definite X (its upper triangle is read):
+// the elimination runs from component D down to component 1, the highest derivative first.  A pivot that is not > 0 gives a zero
+// column (its diagonal and everything above it), ss_chol_psd's rule.  For the differences L = P - E A P and Q = Pinf - A Pinf A' at a
+// small spacing the (1, 1) entry (~ dt^5 for Matern52) is pure rounding: ss_chol_psd pivots on it first and spoils the whole factor,
+// this order takes it last, where nothing depends on it (DESIGN.md 4.18 "Sampling from the posterior object").
+template <int D>
+SS_HD void ss_chol_upper(const double X[D][D], double U[D][D]) {
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) U[i][j] = 0.0;
+  for (int j = D - 1; j >= 0; --j) {
+    double s = X[j][j];
+    for (int k = j + 1; k < D; ++k) s -= U[j][k] * U[j][k];
+    if (!(s > 0.0)) continue;
+    const double dj = sqrt(s);
+    U[j][j] = dj;
+    for (int i = 0; i < j; ++i) {
+      double t = X[i][j];
+      for (int k = j + 1; k < D; ++k) t -= U[i][k] * U[j][k];
+      U[i][j] = t / dj;
+    }
+  }
+}
+
 // s -> A s + c
 template <int D>
 struct SSAff { double A[D][D], c[D]; };
@@ -505,4 +528,42 @@ SS_HD void ss_aff_step(const SSAff<D>& e, double s[D]) {
     t[i] = v;
   }
   for (int i = 0; i < D; ++i) s[i] = t[i];
+}
+
+// ---- sampling from the posterior object (DESIGN.md 4.18 "Sampling from the posterior object") ---------------------------------------
+// Given the data the states of a window of inputs are a Markov chain that runs backwards: s_j | s_{j+1}, y = N(g_j + E_j s_{j+1}, L_j)
+// with (E_j, g_j, L_j) the smoother's element of point j (ss_bwd_element on its FILTERED state (m, P) and the spacing dt to its
+// successor).  The element of the affine recursion s_j = E_j s_{j+1} + g_j + U(L_j) zeta_j, U = ss_chol_upper.  last: the window's
+// final point, which starts the chain: A = 0 and c = m* + U(P*) zeta with (m*, P*) the posterior state there -- has_next: one RTS step
+// back from (ms, Ps), the smoothed state of the training point dt further (the second half of ss_interp); else (m, P) itself (a
+// forecast behind the last training point), and dt, ms, Ps are not read.
+template <int D, typename Mod>
+SS_HD void ss_post_element(const Mod& M, bool last, bool has_next, double dt, const double m[D], const double P[D][D], const double ms[D],
+                           const double Ps[D][D], const double zeta[D], SSAff<D>& e) {
+  SSBwd<D> el;
+  ss_bwd_element<D>(M, last && !has_next, dt, m, P, el);
+  if (last) {
+    if (has_next) {
+      double mm[D], PP[D][D];
+      for (int i = 0; i < D; ++i) {
+        mm[i] = ms[i];
+        for (int j = 0; j < D; ++j) PP[i][j] = Ps[i][j];
+      }
+      ss_rts_step<D>(el, mm, PP);
+      for (int i = 0; i < D; ++i) {
+        el.g[i] = mm[i];
+        for (int j = 0; j < D; ++j) el.L[i][j] = PP[i][j];
+      }
+    }
+    for (int i = 0; i < D; ++i)
+      for (int j = 0; j < D; ++j) el.E[i][j] = 0.0;
+  }
+  double U[D][D];
+  ss_chol_upper<D>(el.L, U);
+  for (int i = 0; i < D; ++i) {
+    double s = el.g[i];
+    for (int k = i; k < D; ++k) s += U[i][k] * zeta[k];
+    e.c[i] = s;
+    for (int j = 0; j < D; ++j) e.A[i][j] = el.E[i][j];
+  }
 }

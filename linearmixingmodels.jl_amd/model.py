@@ -1034,11 +1034,12 @@ def statespace_mean_and_var(fx: "FiniteGP", y, add_noise: bool = True, xs=None):
 class StateSpacePosterior:
     """posterior(fx, y) on the state-space path: owns an lmm_ss_post_t* (the sorted inputs and, per latent, the filtered and the
     smoothed states on the device; include/lmm_hip.h "state space: the posterior object") and answers mean_and_var(post(x*, sigma2))
-    at new inputs in O(ns log n) per latent, without touching the data again.  Built by statespace_posterior; freed by close(), on
-    leaving a `with` block or with the object."""
+    at new inputs in O(ns log n) per latent, without touching the data again; rand draws joint samples there from the same states.
+    Built by statespace_posterior; freed by close(), on leaving a `with` block or with the object."""
 
-    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float):
+    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float, dims: Optional[Sequence[int]] = None):
         self._ptr, self.n, self.p, self.logpdf = ptr, n, p, logpdf
+        self._dims = None if dims is None else [int(D) for D in dims]       # the latents' state dimensions: what rand draws per point
 
     def close(self) -> None:
         if self._ptr:
@@ -1058,14 +1059,14 @@ class StateSpacePosterior:
         except Exception:
             pass
 
-    def _query(self, xs, add_noise: bool, want_var: bool):
+    def _queries(self, xs):
+        """xs as a (ns,) float64 array, checked: every refusal comes before any library call."""
         if not self._ptr:
             raise ValueError("StateSpacePosterior: the posterior has been closed")
         if not hasattr(xs, "shape"):
             xs = np.asarray(xs, dtype=np.float64)
         if len(xs.shape) != 1:
             raise ValueError("StateSpacePosterior: xs is a (ns,) array of one-dimensional inputs")
-        ns = int(xs.shape[0])
         if L._is_torch(xs):
             import torch
             xs = xs.to(torch.float64)
@@ -1075,6 +1076,11 @@ class StateSpacePosterior:
             finite = bool(np.isfinite(xs).all())
         if not finite:
             raise ValueError("StateSpacePosterior: xs must be finite (no NaN or Inf)")
+        return xs
+
+    def _query(self, xs, add_noise: bool, want_var: bool):
+        xs = self._queries(xs)
+        ns = int(xs.shape[0])
         mean = _alloc_like(xs, ns * self.p)
         var = _alloc_like(xs, ns * self.p) if want_var else None
         if ns == 0:
@@ -1098,6 +1104,75 @@ class StateSpacePosterior:
         m, v = self._query(xs, True, True)
         return Normal(m, v ** 0.5)
 
+    def _window(self, lo: float, hi: float):
+        first, count = C.c_int(), C.c_int()
+        L.check(L.load().lmm_statespace_post_window(self._ptr, float(lo), float(hi), C.byref(first), C.byref(count)))
+        return first.value, count.value
+
+    def window(self, xs):
+        """(first, count): the training points (of the sorted inputs) that lie between the smallest and the largest of the queries xs,
+        first = #{t : x_t <= min xs}.  rand touches these and the queries, W = ns + count points per latent and sample, and nothing
+        else.  No queries: (0, 0)."""
+        xs = self._queries(xs)
+        if int(xs.shape[0]) == 0:
+            return 0, 0
+        L.ensure_init()
+        return self._window(float(xs.min()), float(xs.max()))
+
+    def rand(self, rng, xs, N: Optional[int] = None, add_noise: bool = True):
+        """Joint samples of post(xs, sigma2) at the inputs xs ((ns,), in any order; NumPy or a torch device tensor), exact, without
+        touching the data again: rand(rng, posterior(fx, y)(x*, sigma2)) in O(ns + count) per latent and sample (window(xs)), by
+        sampling the posterior's Markov chain backwards from the largest query (include/lmm_hip.h "state space: sampling from the
+        posterior object").  `rng` is a NumPy Generator or a DeviceNormals; buffers and the result live where the normals do.  The
+        queries are sorted here, stably.  Draw order, per sample, with W = ns + count window points (the sorted queries merged with the
+        training points between them, a training point before an equal query):
+          for each latent l in order, standard_normal(D_l * W)     (component-major: component i of window point j at i * W + j);
+          then, if add_noise, standard_normal(ns * p)               (by outputs, over the SORTED queries).
+        Returns the by-outputs vector (ns * p,) for N=None, else (ns * p, N), in the callers' order of queries; column q of an N-sample
+        call is bitwise the one-sample call on the same normals."""
+        xs = self._queries(xs)
+        if N is not None and (int(N) != N or N < 1):
+            raise ValueError("StateSpacePosterior.rand: N is None or a number of samples >= 1")
+        if self._dims is None:
+            raise ValueError("StateSpacePosterior.rand: the handle was built without its latents' state dimensions")
+        ns, Ns, p = int(xs.shape[0]), 1 if N is None else int(N), self.p
+        if ns == 0:
+            return _empty_for(rng, 0) if N is None else _empty_for(rng, 0, Ns)
+        if L._is_torch(xs):
+            import torch
+            xq, perm = torch.sort(xs, stable=True)
+            xq = xq.contiguous()
+        else:
+            perm = np.argsort(xs, kind="stable")
+            xq = np.ascontiguousarray(xs[perm])
+        L.ensure_init()
+        _, count = self._window(float(xq[0]), float(xq[-1]))
+        W = ns + count
+        z = _empty_for(rng, Ns, sum(self._dims) * W)
+        eps = _empty_for(rng, Ns, ns * p) if add_noise else None
+        for q in range(Ns):
+            off = 0
+            for D in self._dims:
+                z[q, off:off + D * W] = rng.standard_normal(D * W)
+                off += D * W
+            if eps is not None:
+                eps[q] = rng.standard_normal(ns * p)
+        out = _empty_for(rng, Ns, ns * p)
+        L.check(L.load().lmm_oilmm_statespace_post_rand(self._ptr, L.Arr(xq).ptr, ns, L.Arr(z).ptr, None if eps is None else L.Arr(eps).ptr,
+                                                        Ns, int(add_noise), L.Arr(out, True).ptr))
+        if L._is_torch(out) and not L._is_torch(perm):        # the un-permuting happens where the result lives
+            import torch
+            perm = torch.as_tensor(perm, device=out.device)
+        elif L._is_torch(perm) and not L._is_torch(out):
+            perm = perm.cpu().numpy()
+        cols = [_statespace_unsorted(out[q], perm, p, ns, False) for q in range(Ns)]
+        if N is None:
+            return cols[0]
+        if L._is_torch(out):
+            import torch
+            return torch.stack(cols, dim=1)
+        return np.stack(cols, axis=1)
+
 
 def statespace_posterior(fx: "FiniteGP", y) -> StateSpacePosterior:
     """posterior(fx, y) of the models statespace_logpdf serves, as a reusable object: one O(n) pass (the inputs are sorted here once,
@@ -1112,7 +1187,7 @@ def statespace_posterior(fx: "FiniteGP", y) -> StateSpacePosterior:
     ptr, out = C.c_void_p(), C.c_double()
     L.check(L.load().lmm_oilmm_statespace_posterior_create(L.Arr(xa).ptr, x.n, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps,
                                                            0, m, C.byref(ptr), C.byref(out)))
-    return StateSpacePosterior(ptr, x.n, p, out.value)
+    return StateSpacePosterior(ptr, x.n, p, out.value, [_STATESPACE_DIM[g.kernel.kind] for g in f.f.fs])
 
 
 class _NoStateSpaceMixingGradient(dict):
