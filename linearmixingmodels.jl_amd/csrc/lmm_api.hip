@@ -624,11 +624,6 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
   std::shared_ptr<LatentSet> ls;                            \
   if (int rc_ = resolve(gps, m, d, ls)) return rc_;         \
   const Latent* lts = ls->lat.data()
-// the state-space entry points' (d = 1)
-#define RESOLVE_SS(gps, m)                                  \
-  std::shared_ptr<LatentSet> ls;                            \
-  if (int rc_ = resolve(gps, m, 1, ls)) return rc_;         \
-  const Latent* lts = ls->lat.data()
 // An entry point that does not serve SHO latents names the first one (what: the entry point's service, for the message).
 int refuse_sho(const LatentSet& S, const char* what) {
   for (size_t l = 0; l < S.lat.size(); ++l)
@@ -4971,6 +4966,8 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
   LMM_CATCH
 }
 
+}  // extern "C": the entry points below have C linkage from their declarations in include/lmm_hip.h
+
 // ------------------------------------------------------------------------------------------------
 // State-space inference for Matern12 / 32 / 52 and SHO latents over a one-dimensional input (include/lmm_hip.h "state space"):
 // the Kalman filter and the RTS smoother as parallel scans over the points (lmm_kernels_ss.hip), linear in n and exact.
@@ -4991,20 +4988,62 @@ static int ss_check_latents(const Latent* lts, int m) {
   return LMM_OK;
 }
 
-// x (device, n values) must be non-decreasing: LMM_ERR_ARG with the first offending index in the error detail's `info`.
-static int ss_check_sorted(const double* xd, int n) {
+static int ss_refuse_f32() { return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))"); }
+
+// The first index a device check (launch_ss_sorted, launch_ss_finite) flags among the n values at xd, INT_MAX when it flags none: the
+// flag goes up as INT_MAX, the kernel lowers it, the flag comes down.  A flagged index is left in the error detail's `info`.
+static int ss_first_flagged(void (*launch)(const double*, int, int*, hipStream_t), const double* xd, int n) {
   hipStream_t st0 = g.streams[0];
   Buf<int> flag(1);
   int h = INT_MAX;
   HIPCHK(hipMemcpyAsync(flag.p, &h, sizeof(int), hipMemcpyHostToDevice, st0));
-  launch_ss_sorted(xd, n, flag.p, st0);
+  launch(xd, n, flag.p, st0);
   HIPCHK(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipStreamSynchronize(st0));
-  if (h != INT_MAX) {
-    g.err_latent = -1; g.err_info = h;
-    return fail(LMM_ERR_ARG, "state-space inference needs non-decreasing inputs: x[%d] is not >= x[%d] (sort the points first)", h, h - 1);
+  if (h != INT_MAX) { g.err_latent = -1; g.err_info = h; }
+  return h;
+}
+// x (device, n values) must be non-decreasing: LMM_ERR_ARG with the first offending index in the error detail's `info`.
+static int ss_check_sorted(const double* xd, int n) {
+  const int h = ss_first_flagged(launch_ss_sorted, xd, n);
+  if (h == INT_MAX) return LMM_OK;
+  return fail(LMM_ERR_ARG, "state-space inference needs non-decreasing inputs: x[%d] is not >= x[%d] (sort the points first)", h, h - 1);
+}
+// xs (device, ns values) must be finite: LMM_ERR_ARG with the first offending index in the error detail's `info`.
+static int ss_check_finite(const double* xsd, int ns) {
+  const int h = ss_first_flagged(launch_ss_finite, xsd, ns);
+  if (h == INT_MAX) return LMM_OK;
+  return fail(LMM_ERR_ARG, "state-space posterior: xs[%d] is not finite", h);
+}
+
+// The plan of a scan over n items: `chunk` items per thread (<= 0: the library's choice, a function of n alone) and the threads it takes
+struct SSChunks { int chunk, nch; };
+static SSChunks ss_plan_chunks(int n, int chunk) {
+  if (chunk <= 0) chunk = ss_default_chunk(n);
+  if (chunk > n) chunk = n;
+  return SSChunks{chunk, (n + chunk - 1) / chunk};
+}
+
+// The launches of ne entries (latents, or (latent, sample) pairs), entry e belonging to latent lat_of(e): consecutive entries share a
+// launch while their model is the same (ss_model_of: Matern32 and SHO share a state dimension, not a launch), up to LMM_MAX_BATCH and
+// to the LMM_SS_BATCH_BYTES / bytes_per_entry(model, D, nch) entries whose buffers the launch may hold, and at least one.
+// body(e0, nb, model, D) runs the launch of entries [e0, e0 + nb).
+template <typename LatOf, typename Bytes, typename Body>
+static void ss_for_launches(long long ne, int nch, LatOf&& lat_of, Bytes&& bytes_per_entry, Body&& body) {
+  for (long long e0 = 0; e0 < ne;) {
+    const int model = ss_model_of(lat_of(e0).kind), D = ss_model_dim(model);
+    const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / bytes_per_entry(model, D, nch)));
+    int nb = 1;
+    while (e0 + nb < ne && nb < nbmax && ss_model_of(lat_of(e0 + nb).kind) == model) ++nb;
+    body(e0, nb, model, D);
+    e0 += nb;
   }
-  return LMM_OK;
+}
+
+// the kernel parameters every *Lat struct of a launch takes from its latent
+template <typename Lat>
+static void ss_fill_lat(Lat& o, const Latent& L, bool add_mean) {
+  o.var = L.terms[0].ev.var; o.inv_ls = L.terms[0].ev.inv_ls; o.mean = add_mean ? L.mean : 0.0; o.quality = L.quality;
 }
 
 // The filter (and, smean != nullptr, the smoother) of the ms latents lts[0 .. ms): w, r, fmean, fvar, smean, svar are [latent][n] on
@@ -5031,19 +5070,17 @@ static size_t ss_keep_offset(const SSEntry* es, int k, int n) {
 static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, int chunk, double* lml, double* fmean, double* fvar,
                            double* smean, double* svar, bool add_mean, const SSGradOut* go = nullptr, const SSKeep* keep = nullptr) {
   hipStream_t st0 = g.streams[0];
-  if (chunk <= 0) chunk = ss_default_chunk(n);
-  if (chunk > n) chunk = n;
-  const int nch = (n + chunk - 1) / chunk;
+  const SSChunks plan = ss_plan_chunks(n, chunk);
+  const int nch = plan.nch, npb = ss_point_blocks(n);
   const bool smooth = smean != nullptr || keep != nullptr;
-  for (int k0 = 0; k0 < ms;) {
-    const int model = ss_model_of(es[k0].L->kind), D = ss_model_dim(model), NS = ss_model_seeds(model);
+  const auto bytes = [&](int model, int D, int nch) {       // a latent's aggregates, partials and filtered states
+    const int NS = ss_model_seeds(model);
+    return (ss_fwd_agg_elems(D, nch) + (size_t)nch + (smooth ? (size_t)ss_state_comps(D) * n + ss_bwd_agg_elems(D, nch) : 0) +
+            (go ? ss_dual_agg_elems(D, nch, NS) + NS * (size_t)nch + 4 * (size_t)npb : 0)) * sizeof(double);
+  };
+  ss_for_launches(ms, nch, [&](long long k) -> const Latent& { return *es[k].L; }, bytes, [&](long long e0, int nb, int model, int D) {
+    const int k0 = (int)e0, NS = ss_model_seeds(model);
     const size_t comps = (size_t)ss_state_comps(D);
-    const int npb = ss_point_blocks(n);
-    const size_t per = (ss_fwd_agg_elems(D, nch) + (size_t)nch + (smooth ? comps * n + ss_bwd_agg_elems(D, nch) : 0) +
-                        (go ? ss_dual_agg_elems(D, nch, NS) + NS * (size_t)nch + 4 * (size_t)npb : 0)) * sizeof(double);
-    const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / per));
-    int nb = 1;
-    while (k0 + nb < ms && nb < nbmax && ss_model_of(es[k0 + nb].L->kind) == model) ++nb;
     Buf<double> agg((size_t)nb * ss_fwd_agg_elems(D, nch)), part((size_t)nb * nch), lmld(nb), state, bagg;
     if (smooth) { state = Buf<double>((size_t)nb * comps * n); bagg = Buf<double>((size_t)nb * ss_bwd_agg_elems(D, nch)); }
     Buf<double> dagg, dpart, ppart, gsum;
@@ -5053,7 +5090,7 @@ static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, i
       ppart = Buf<double>((size_t)nb * 4 * npb); gsum = Buf<double>((size_t)nb * (4 + NS));
     }
     SSArgs a{};
-    a.x = xd; a.n = n; a.chunk = chunk; a.nch = nch;
+    a.x = xd; a.n = n; a.chunk = plan.chunk; a.nch = nch;
     a.agg = agg.p; a.bagg = bagg.p; a.part = part.p;
     a.fmean = fmean ? fmean + (size_t)k0 * n : nullptr; a.fvar = fvar ? fvar + (size_t)k0 * n : nullptr;
     a.state = state.p; a.state_stride = comps * n;
@@ -5061,9 +5098,8 @@ static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, i
     a.smean = (smooth && smean) ? smean + (size_t)k0 * n : nullptr; a.svar = (smooth && svar) ? svar + (size_t)k0 * n : nullptr;
     a.dagg = dagg.p; a.dpart = dpart.p;
     for (int j = 0; j < nb; ++j) {
-      const Latent& L = *es[k0 + j].L;
-      a.lat[j].var = L.terms[0].ev.var; a.lat[j].inv_ls = L.terms[0].ev.inv_ls; a.lat[j].mean = add_mean ? L.mean : 0.0;
-      a.lat[j].w = es[k0 + j].w; a.lat[j].r = es[k0 + j].r; a.lat[j].quality = L.quality;
+      ss_fill_lat(a.lat[j], *es[k0 + j].L, add_mean);
+      a.lat[j].w = es[k0 + j].w; a.lat[j].r = es[k0 + j].r;
     }
     launch_ss_filter(a, model, nb, lmld.p, st0);
     if (smooth) launch_ss_smooth(a, model, nb, st0);
@@ -5081,8 +5117,7 @@ static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, i
     if (go)
       for (int j = 0; j < nb; ++j)
         for (int s = 0; s < 3; ++s) go->gtheta[(size_t)(k0 + j) * 3 + s] = s < NS ? gth[(size_t)j * NS + s] : 0.0;
-    k0 += nb;
-  }
+  });
   return LMM_OK;
 }
 
@@ -5184,30 +5219,56 @@ static int ss_front(const double* yd, int n, int p, const double* U, const doubl
   return LMM_OK;
 }
 
-#define LMM_SS_ARGCHECK(extra)                                                                                                   \
-  LMM_MISSING_ARGCHECK(!x || (extra));                                                                                            \
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");             \
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))")
+// The preamble of the entry points that take training data, in the order the error codes are pinned in: the argument checks (missing:
+// x, y where the entry point needs it, or an output of its own is NULL), the Float64-only refusal, after_args (the entry point's own
+// checks, if any), then the latents resolved and checked, x and y on the device, x checked, the shard's bounds and, with y, the front end.
+struct SSTrain {
+  std::shared_ptr<LatentSet> ls;
+  const Latent* lts = nullptr;         // all m latents
+  DevIn xd{nullptr, 0, nullptr}, yd{nullptr, 0, nullptr};
+  int l0 = 0, l1 = 0, ms = 0, mk = 1;  // the shard, its latents, max(ms, 1)
+  SSFront Fr;                          // left empty without y
+};
+static int ss_train(bool missing, const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                    const lmm_gp_t* gps, int l0, int l1, SSTrain& T, bool want_resid = false, const std::function<int()>& after_args = nullptr) {
+  if (missing || !x || !U || !S || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
+  if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
+  for (int l = 0; l < m; ++l)
+    if (!(S[l] > 0.0) || !std::isfinite(S[l])) return fail(LMM_ERR_ARG, "S must be finite and > 0 (S[%d] = %g)", l, S[l]);
+  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
+  if (g_f32) return ss_refuse_f32();
+  if (after_args)
+    if (int rc = after_args()) return rc;
+  if (int rc = resolve(gps, m, 1, T.ls)) return rc;
+  T.lts = T.ls->lat.data();
+  if (int rc = ss_check_latents(T.lts, m)) return rc;
+  T.xd = DevIn(x, (size_t)n, g.streams[0]); T.yd = DevIn(y, (size_t)n * p, g.streams[0]);
+  if (int rc = ss_check_sorted(T.xd.p, n)) return rc;
+  T.l0 = l0; T.l1 = l1; T.ms = l1 - l0; T.mk = std::max(T.ms, 1);
+  return y ? ss_front(T.yd.p, n, p, U, S, m, sigma2, T.lts, l0, l1, T.Fr, want_resid) : (int)LMM_OK;
+}
+
+// H = U sqrt(S) of the shard's ms latents from l0 on, p x max(ms, 1) column-major
+static std::vector<double> ss_shard_H(const double* U, const double* S, int p, int l0, int ms) {
+  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
+  for (int k = 0; k < ms; ++k)
+    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
+  return Hs;
+}
 
 int lmm_oilmm_logpdf_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
                                 const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  LMM_SS_ARGCHECK(!out);
-  RESOLVE_SS(gps, m);
-  if (int rc = ss_check_latents(lts, m)) return rc;
-  hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
-  if (int rc = ss_check_sorted(xd.p, n)) return rc;
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
-  SSFront Fr;
-  if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr)) return rc;
-  std::vector<double> lml(std::max(ms, 1), 0.0);
-  if (int rc = ss_core(xd.p, n, lts + l0, ms, Fr.w.p, Fr.r.p, 0, lml.data(), nullptr, nullptr, nullptr, nullptr, false)) return rc;
+  SSTrain T;
+  if (int rc = ss_train(!y || !out, x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, T)) return rc;
+  std::vector<double> lml(T.mk, 0.0);
+  if (int rc = ss_core(T.xd.p, n, T.lts + T.l0, T.ms, T.Fr.w.p, T.Fr.r.p, 0, lml.data(), nullptr, nullptr, nullptr, nullptr, false)) return rc;
   double total = 0.0;
-  for (int k = 0; k < ms; ++k) total += lml[k];
-  if (with_regulariser) total += Fr.reg;
+  for (int k = 0; k < T.ms; ++k) total += lml[k];
+  if (with_regulariser) total += T.Fr.reg;
   *out = total;
   return LMM_OK;
   LMM_CATCH
@@ -5219,21 +5280,13 @@ int lmm_oilmm_mean_and_var_statespace(const double* x, int n, const double* y, i
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  LMM_SS_ARGCHECK(!mean_out);
-  RESOLVE_SS(gps, m);
-  if (int rc = ss_check_latents(lts, m)) return rc;
+  SSTrain T;
+  if (int rc = ss_train(!y || !mean_out, x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, T)) return rc;
   hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
-  if (int rc = ss_check_sorted(xd.p, n)) return rc;
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
-  SSFront Fr;
-  if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr)) return rc;
-  Buf<double> ml((size_t)n * std::max(ms, 1)), vl((size_t)n * std::max(ms, 1));
-  if (int rc = ss_core(xd.p, n, lts + l0, ms, Fr.w.p, Fr.r.p, 0, nullptr, nullptr, nullptr, ml.p, vl.p, true)) return rc;
-  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
-  for (int k = 0; k < ms; ++k)
-    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
-  Uploaded Hd(Hs, st0);
+  const int ms = T.ms;
+  Buf<double> ml((size_t)n * T.mk), vl((size_t)n * T.mk);
+  if (int rc = ss_core(T.xd.p, n, T.lts + T.l0, ms, T.Fr.w.p, T.Fr.r.p, 0, nullptr, nullptr, nullptr, ml.p, vl.p, true)) return rc;
+  Uploaded Hd(ss_shard_H(U, S, p, T.l0, ms), st0);
   DevOut mo(mean_out, (size_t)n * p), vo(var_out, (size_t)n * p);
   // the mixing of lmm_oilmm_mean_and_var (reference src/oilmm.jl:69,72)
   mix_marginals(ml.p, n, ms, Hd.buf.p, p, 1, 0.0, 0.0, mo.p, st0);
@@ -5256,15 +5309,10 @@ int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, in
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  LMM_SS_ARGCHECK(false);
-  RESOLVE_SS(gps, m);
-  if (int rc = ss_check_latents(lts, m)) return rc;
+  SSTrain T;
+  if (int rc = ss_train(!y, x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, T, grad_y && with_regulariser)) return rc;
   hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
-  if (int rc = ss_check_sorted(xd.p, n)) return rc;
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0, msa = std::max(ms, 1);
-  SSFront Fr;
-  if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr, grad_y && with_regulariser)) return rc;
+  const auto& [ls, lts, xd, yd, l0, l1, ms, msa, Fr] = T;
   if (Fr.has_nan && (grad_S || grad_U))
     return fail(LMM_ERR_UNSUPPORTED, "state-space gradients with respect to S and U are not built for data with NaN (pass NULL for grad_S and grad_U)");
   DevOut gy(grad_y, (size_t)n * p);
@@ -5366,13 +5414,22 @@ int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, in
 
 // Building blocks for tests: ONE latent from device pointers, per-point noise w (+Inf: unobserved) and data r; the latent's mean is
 // not read (r is the residual).  chunk: points per thread (0: the library's plan).
+// The preamble of these one-latent entry points: `bad` (a NULL pointer or a size out of range) refuses the arguments, then nsamples
+// (given by the entry points that draw samples), the Float64-only refusal, the latent resolved and checked, x (device) checked.
+static int ss_dev_prepare(bool bad, const double* x, int n, const lmm_gp_t* gp, std::shared_ptr<LatentSet>& ls, int nsamples = 1) {
+  if (bad) return fail(LMM_ERR_ARG, "bad arguments");
+  if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
+  if (g_f32) return ss_refuse_f32();
+  if (int rc = resolve(gp, 1, 1, ls)) return rc;
+  if (int rc = ss_check_latents(ls->lat.data(), 1)) return rc;
+  return ss_check_sorted(x, n);
+}
+
 static int ss_dev_block(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* fmean,
                         double* fvar, double* lml_dev, double* smean, double* svar) {
-  if (n <= 0 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  RESOLVE_SS(gp, 1);
-  if (int rc = ss_check_latents(lts, 1)) return rc;
-  if (int rc = ss_check_sorted(x, n)) return rc;
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = ss_dev_prepare(n <= 0 || chunk < 0, x, n, gp, ls)) return rc;
+  const Latent* lts = ls->lat.data();
   double lml = 0.0;
   if (int rc = ss_core(x, n, lts, 1, w, r, chunk, &lml, fmean, fvar, smean, svar, false)) return rc;
   if (lml_dev) {
@@ -5409,11 +5466,10 @@ static int ss_dev_grad(const double* x, int n, const lmm_gp_t* gp, const double*
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !gp || !w || !r || !lml || !grad_r || !grad_w || !grad_theta || n <= 0 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  RESOLVE_SS(gp, 1);
-  if (int rc = ss_check_latents(lts, 1)) return rc;
-  if (int rc = ss_check_sorted(x, n)) return rc;
+  std::shared_ptr<LatentSet> ls;
+  const bool bad = !x || !gp || !w || !r || !lml || !grad_r || !grad_w || !grad_theta || n <= 0 || chunk < 0;
+  if (int rc = ss_dev_prepare(bad, x, n, gp, ls)) return rc;
+  const Latent* lts = ls->lat.data();
   hipStream_t st0 = g.streams[0];
   Buf<double> sm(n), sv(n);
   double hl = 0.0, sums[4], gth[3];
@@ -5441,8 +5497,6 @@ int lmm_dev_statespace_grad_sho(const double* x, int n, const lmm_gp_t* gp, cons
 // ---- the posterior object (DESIGN.md 4.18 "Posterior object") --------------------------------------------------------------------
 // One O(n) conditioning pass keeps, per latent of the shard, the filtered and the full smoothed states; a query at new inputs is then
 // one thread per (query, latent) (ss_interp_kernel) and the mixing of lmm_oilmm_mean_and_var_statespace.
-}  // extern "C"
-
 struct lmm_ss_post {
   int n = 0, p = 0, m = 0, l0 = 0, l1 = 0;
   double sigma2 = 0.0;
@@ -5453,53 +5507,26 @@ struct lmm_ss_post {
   std::vector<size_t> off;            // latent l0 + k's offset into fstate / sstate
 };
 
-namespace {
-
-// xs (device, ns values) must be finite: LMM_ERR_ARG with the first offending index in the error detail's `info`.
-int ss_check_finite(const double* xsd, int ns) {
-  hipStream_t st0 = g.streams[0];
-  Buf<int> flag(1);
-  int h = INT_MAX;
-  HIPCHK(hipMemcpyAsync(flag.p, &h, sizeof(int), hipMemcpyHostToDevice, st0));
-  launch_ss_finite(xsd, ns, flag.p, st0);
-  HIPCHK(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  if (h != INT_MAX) {
-    g.err_latent = -1; g.err_info = h;
-    return fail(LMM_ERR_ARG, "state-space posterior: xs[%d] is not finite", h);
-  }
-  return LMM_OK;
-}
-
 // The zero-mean (add_mean: plus the latent's mean) marginals of the ms latents lts[0 .. ms) at the ns queries xsd from their stored
 // states (latent k's block off[k] doubles into fstate / sstate): ml, vl [latent][ns] on the device (vl may be nullptr).  Launches
 // group consecutive latents of one model, LMM_MAX_BATCH at the most.  Queues on streams[0] and does not wait.
-void ss_interp_latents(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
+static void ss_interp_latents(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
                        const double* xsd, int ns, bool add_mean, double* ml, double* vl, bool point_major = true) {
   hipStream_t st0 = g.streams[0];
-  for (int k0 = 0; k0 < ms;) {
-    const int model = ss_model_of(lts[k0].kind), D = ss_model_dim(model);
-    int nb = 1;
-    while (k0 + nb < ms && nb < LMM_MAX_BATCH && ss_model_of(lts[k0 + nb].kind) == model) ++nb;
+  const auto no_buffers = [](int, int, int) { return size_t(1); };       // a launch allocates nothing: LMM_MAX_BATCH alone limits it
+  ss_for_launches(ms, 0, [&](long long k) -> const Latent& { return lts[k]; }, no_buffers, [&](long long e0, int nb, int model, int D) {
+    const int k0 = (int)e0;
     SSInterpArgs a{};
     a.x = xd; a.n = n; a.xs = xsd; a.ns = ns;
     a.fstate = fstate + off[k0]; a.sstate = sstate + off[k0];
     a.state_stride = (size_t)ss_state_comps(D) * n;
     a.comp_stride = point_major ? 1 : (size_t)n; a.point_stride = point_major ? (size_t)ss_state_comps(D) : 1;
     a.mean = ml + (size_t)k0 * ns; a.var = vl ? vl + (size_t)k0 * ns : nullptr;
-    for (int j = 0; j < nb; ++j) {
-      const Latent& L = lts[k0 + j];
-      a.lat[j] = SSInterpLat{L.terms[0].ev.var, L.terms[0].ev.inv_ls, add_mean ? L.mean : 0.0, L.quality};
-    }
+    for (int j = 0; j < nb; ++j) ss_fill_lat(a.lat[j], lts[k0 + j], add_mean);
     launch_ss_interp(a, model, nb, st0);
-    k0 += nb;
-  }
+  });
   HIPCHK(hipGetLastError());
 }
-
-}  // namespace
-
-extern "C" {
 
 int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
                                           double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_ss_post_t** out,
@@ -5507,16 +5534,10 @@ int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* 
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  LMM_SS_ARGCHECK(!out);
-  *out = nullptr;
-  RESOLVE_SS(gps, m);
-  if (int rc = ss_check_latents(lts, m)) return rc;
+  SSTrain T;
+  if (int rc = ss_train(!y || !out, x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, T, false, [&] { *out = nullptr; return 0; })) return rc;
   hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
-  if (int rc = ss_check_sorted(xd.p, n)) return rc;
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
-  SSFront Fr;
-  if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr)) return rc;
+  const auto& [ls, lts, xd, yd, l0, l1, ms, mk, Fr] = T;
   std::unique_ptr<lmm_ss_post> P(new lmm_ss_post());      // a throw below (a failed allocation) frees what it holds
   P->n = n; P->p = p; P->m = m; P->l0 = l0; P->l1 = l1; P->sigma2 = sigma2; P->ls = ls;
   std::vector<SSEntry> es(ms);
@@ -5529,12 +5550,10 @@ int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* 
   P->x = Buf<double>((size_t)n);
   P->fstate = Buf<double>(std::max<size_t>(total, 1)); P->sstate = Buf<double>(std::max<size_t>(total, 1));
   HIPCHK(hipMemcpyAsync(P->x.p, xd.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
-  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
-  for (int k = 0; k < ms; ++k)
-    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
+  const std::vector<double> Hs = ss_shard_H(U, S, p, l0, ms);
   P->H = Buf<double>(Hs.size());
   HIPCHK(hipMemcpyAsync(P->H.p, Hs.data(), Hs.size() * sizeof(double), hipMemcpyHostToDevice, st0));
-  std::vector<double> lml(std::max(ms, 1), 0.0);
+  std::vector<double> lml(mk, 0.0);
   const SSKeep keep{P->fstate.p, P->sstate.p};
   if (int rc = ss_core_entries(P->x.p, n, es.data(), ms, 0, lml.data(), nullptr, nullptr, nullptr, nullptr, false, nullptr, &keep)) return rc;
   HIPCHK(hipStreamSynchronize(st0));
@@ -5562,7 +5581,7 @@ int lmm_oilmm_statespace_post_mean_and_var(const lmm_ss_post_t* post, const doub
   REQUIRE_INIT();
   LMM_TRY
   if (!post || !xs || !mean_out || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  if (g_f32) return ss_refuse_f32();
   const lmm_ss_post* P = post;
   const int p = P->p, ms = P->l1 - P->l0;
   hipStream_t st0 = g.streams[0];
@@ -5586,11 +5605,9 @@ int lmm_dev_statespace_states(const double* x, int n, const lmm_gp_t* gp, const 
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !gp || !w || !r || !fstate || !sstate || n <= 0 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  RESOLVE_SS(gp, 1);
-  if (int rc = ss_check_latents(lts, 1)) return rc;
-  if (int rc = ss_check_sorted(x, n)) return rc;
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = ss_dev_prepare(!x || !gp || !w || !r || !fstate || !sstate || n <= 0 || chunk < 0, x, n, gp, ls)) return rc;
+  const Latent* lts = ls->lat.data();
   const SSEntry e{lts, w, r};
   const SSKeep keep{fstate, sstate};
   return ss_core_entries(x, n, &e, 1, chunk, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, &keep);
@@ -5604,11 +5621,10 @@ int lmm_dev_statespace_interp_layout(const double* x, int n, const lmm_gp_t* gp,
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !gp || !fstate || !sstate || !xs || !mean || !var || n <= 0 || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  RESOLVE_SS(gp, 1);
-  if (int rc = ss_check_latents(lts, 1)) return rc;
-  if (int rc = ss_check_sorted(x, n)) return rc;
+  std::shared_ptr<LatentSet> ls;
+  const bool bad = !x || !gp || !fstate || !sstate || !xs || !mean || !var || n <= 0 || ns < 1;
+  if (int rc = ss_dev_prepare(bad, x, n, gp, ls)) return rc;
+  const Latent* lts = ls->lat.data();
   if (int rc = ss_check_finite(xs, ns)) return rc;
   const size_t off = 0;
   ss_interp_latents(x, n, lts, 1, fstate, sstate, &off, xs, ns, false, mean, var, point_major != 0);
@@ -5623,39 +5639,44 @@ int lmm_dev_statespace_interp(const double* x, int n, const lmm_gp_t* gp, const 
 }
 
 // ---- sampling (DESIGN.md 4.18 "Sampling") ----------------------------------------------------------------------------------------
-// Prior paths of the ms latents lts[0 .. ms) for N samples: f[sample][latent][n] on the device, with the latent's mean when add_mean.
-// z: sample 0's normals of lts[0] on the device, the latents one after the other (D_l n values each, component-major), the samples
-// z_stride doubles apart.  The (latent, sample) pairs run in launches of one model.  Returns with streams[0] drained.
-static int ss_paths(const double* xd, int n, const Latent* lts, int ms, int N, const double* z, size_t z_stride, int chunk, bool add_mean,
-                    double* f) {
+// The affine-scan launches of the (latent, sample) pairs of the ms latents lts[0 .. ms) and N samples, `rows` points per pair: pair e
+// is (latent e / N, sample e % N), and the pairs run in launches of one model.  a: the launch's arguments but chunk, nch, agg and lat;
+// fill(lat, k, q, zoff) sets the pointers of pair (k, q), whose normals lie zoff doubles into a sample's (the latents one after the
+// other, D_l rows values each).  Returns with streams[0] drained.
+template <typename Args, typename Fill>
+static void ss_pair_launches(const Latent* lts, int ms, int N, int rows, int chunk, bool add_mean, const Args& a0,
+                             void (*launch)(const Args&, int, int, hipStream_t), Fill&& fill) {
   hipStream_t st0 = g.streams[0];
-  if (chunk <= 0) chunk = ss_default_chunk(n);
-  if (chunk > n) chunk = n;
-  const int nch = (n + chunk - 1) / chunk;
+  const SSChunks plan = ss_plan_chunks(rows, chunk);
   std::vector<size_t> zoff(std::max(ms, 1), 0);
-  for (int k = 1; k < ms; ++k) zoff[k] = zoff[k - 1] + (size_t)ss_state_dim(lts[k - 1].kind) * n;
-  const long long ne = (long long)ms * N;
-  for (long long e0 = 0; e0 < ne;) {
-    const int model = ss_model_of(lts[e0 / N].kind), D = ss_model_dim(model);
-    const size_t per = ss_aff_agg_elems(D, nch) * sizeof(double);
-    const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / per));
-    int nb = 1;
-    while (e0 + nb < ne && nb < nbmax && ss_model_of(lts[(e0 + nb) / N].kind) == model) ++nb;
-    Buf<double> agg((size_t)nb * ss_aff_agg_elems(D, nch));
-    SSPathArgs a{};
-    a.x = xd; a.n = n; a.chunk = chunk; a.nch = nch; a.agg = agg.p;
+  for (int k = 1; k < ms; ++k) zoff[k] = zoff[k - 1] + (size_t)ss_state_dim(lts[k - 1].kind) * rows;
+  const auto bytes = [](int, int D, int nch) { return ss_aff_agg_elems(D, nch) * sizeof(double); };
+  ss_for_launches((long long)ms * N, plan.nch, [&](long long e) -> const Latent& { return lts[e / N]; }, bytes,
+                  [&](long long e0, int nb, int model, int D) {
+    Buf<double> agg((size_t)nb * ss_aff_agg_elems(D, plan.nch));
+    Args a = a0;
+    a.chunk = plan.chunk; a.nch = plan.nch; a.agg = agg.p;
     for (int j = 0; j < nb; ++j) {
       const int k = (int)((e0 + j) / N), q = (int)((e0 + j) % N);
-      const Latent& L = lts[k];
-      a.lat[j].var = L.terms[0].ev.var; a.lat[j].inv_ls = L.terms[0].ev.inv_ls; a.lat[j].mean = add_mean ? L.mean : 0.0;
-      a.lat[j].z = z + (size_t)q * z_stride + zoff[k];
-      a.lat[j].f = f + ((size_t)q * ms + k) * n; a.lat[j].quality = L.quality;
+      ss_fill_lat(a.lat[j], lts[k], add_mean);
+      fill(a.lat[j], k, q, zoff[k]);
     }
-    launch_ss_path(a, model, nb, st0);
+    launch(a, model, nb, st0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st0));          // agg goes back to the pool
-    e0 += nb;
-  }
+  });
+}
+
+// Prior paths of the ms latents lts[0 .. ms) for N samples: f[sample][latent][n] on the device, with the latent's mean when add_mean.
+// z: sample 0's normals of lts[0] on the device, the latents one after the other (D_l n values each, component-major), the samples
+// z_stride doubles apart.  Returns with streams[0] drained.
+static int ss_paths(const double* xd, int n, const Latent* lts, int ms, int N, const double* z, size_t z_stride, int chunk, bool add_mean,
+                    double* f) {
+  SSPathArgs a{};
+  a.x = xd; a.n = n;
+  ss_pair_launches(lts, ms, N, n, chunk, add_mean, a, launch_ss_path, [&](SSPathLat& o, int k, int q, size_t zoff) {
+    o.z = z + (size_t)q * z_stride + zoff; o.f = f + ((size_t)q * ms + k) * n;
+  });
   return LMM_OK;
 }
 
@@ -5702,32 +5723,52 @@ struct SSNormals {
   }
 };
 
+// body(q0, ng) for the samples [q0, q0 + ng) of every group (ss_sample_group over `rows` points per sample and latent)
+template <typename Body>
+static int ss_for_sample_groups(int rows, int ms, int nsamples, Body&& body) {
+  const int group = ss_sample_group(rows, ms, nsamples);
+  for (int q0 = 0; q0 < nsamples; q0 += group)
+    if (int rc = body(q0, std::min(group, nsamples - q0))) return rc;
+  return LMM_OK;
+}
+
+// The sampling entry points' loop: per group, paths(q0, ng, f) leaves the latent paths of samples [q0, q0 + ng) in f[sample][latent
+// of the shard][rows] on the device, and the mixing of lmm_lmm_rand (reference src/oilmm.jl:50-53), H f + sqrt(sigma2) eps, writes
+// rows x p per sample to od (device).  eps: host or device, rows x p per sample (nullptr: no noise); Hd: p x ms on the device.
+template <typename Paths>
+static int ss_sample_mix(int rows, int group_rows, int ms, int p, const double* Hd, double sigma2, const double* eps, int nsamples,
+                         double* od, Paths&& paths) {
+  hipStream_t st0 = g.streams[0];
+  return ss_for_sample_groups(group_rows, ms, nsamples, [&](int q0, int ng) {
+    SSNormals epsd(eps, (size_t)rows * p, 0, (size_t)rows * p, q0, ng, st0);
+    Buf<double> f((size_t)ng * std::max(ms, 1) * rows);
+    if (int rc = paths(q0, ng, f.p)) return rc;
+    for (int q = 0; q < ng; ++q)
+      launch_mix(f.p + (size_t)q * ms * rows, rows, ms, Hd, p, 1, 0.0, 0.0, eps ? epsd.p + (size_t)q * epsd.stride : nullptr,
+                 std::sqrt(sigma2), od + (size_t)(q0 + q) * rows * p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));            // the group's buffers go back to the pool
+    return (int)LMM_OK;
+  });
+}
+
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples, const double* z,
                               const double* xi, const double* eps, double* out) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !U || !S || !out || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
-  for (int l = 0; l < m; ++l)
-    if (!(S[l] > 0.0) || !std::isfinite(S[l])) return fail(LMM_ERR_ARG, "S must be finite and > 0 (S[%d] = %g)", l, S[l]);
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
-  if (!z) return fail(LMM_ERR_ARG, "z is NULL");
-  if (y && !xi) return fail(LMM_ERR_ARG, "xi is NULL (a posterior sample needs it)");
-  if (add_noise && !eps) return fail(LMM_ERR_ARG, "eps is NULL");
-  RESOLVE_SS(gps, m);
-  if (int rc = ss_check_latents(lts, m)) return rc;
+  SSTrain T;
+  const int rc0 = ss_train(!out, x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, T, false, [&] {      // y may be NULL: the prior
+    if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
+    if (!z) return fail(LMM_ERR_ARG, "z is NULL");
+    if (y && !xi) return fail(LMM_ERR_ARG, "xi is NULL (a posterior sample needs it)");
+    return add_noise && !eps ? fail(LMM_ERR_ARG, "eps is NULL") : (int)LMM_OK;
+  });
+  if (rc0) return rc0;
   hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)n, st0), yd(y, (size_t)n * p, st0);
-  if (int rc = ss_check_sorted(xd.p, n)) return rc;
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0, mk = std::max(ms, 1);
-  SSFront Fr;
-  if (y)
-    if (int rc = ss_front(yd.p, n, p, U, S, m, sigma2, lts, l0, l1, Fr)) return rc;
+  const Latent* lts = T.lts;
+  const int l0 = T.l0, l1 = T.l1, ms = T.ms;
   size_t zall = 0, zbefore = 0, zshard = 0;        // doubles of one sample's z: every latent, those before the shard, the shard's
   for (int l = 0; l < m; ++l) {
     const size_t c = (size_t)ss_state_dim(lts[l].kind) * n;
@@ -5735,27 +5776,15 @@ int lmm_oilmm_rand_statespace(const double* x, int n, const double* y, int p, co
     if (l < l0) zbefore += c;
     else if (l < l1) zshard += c;
   }
-  std::vector<double> Hs((size_t)p * mk, 0.0);
-  for (int k = 0; k < ms; ++k)
-    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
-  Uploaded Hd(Hs, st0);
+  Uploaded Hd(ss_shard_H(U, S, p, l0, ms), st0);
   DevOut od(out, (size_t)n * p * nsamples);
-  const int group = ss_sample_group(n, ms, nsamples);
-  for (int q0 = 0; q0 < nsamples; q0 += group) {
-    const int ng = std::min(group, nsamples - q0);
+  const int rc = ss_sample_mix(n, n, ms, p, Hd.buf.p, sigma2, add_noise ? eps : nullptr, nsamples, od.p, [&](int q0, int ng, double* f) {
     SSNormals zd(z, zall, zbefore, zshard, q0, ng, st0), xid(y ? xi : nullptr, (size_t)m * n, (size_t)l0 * n, (size_t)ms * n, q0, ng, st0);
-    SSNormals epsd(add_noise ? eps : nullptr, (size_t)n * p, 0, (size_t)n * p, q0, ng, st0);
-    Buf<double> f((size_t)ng * mk * n);            // [sample][latent of the shard][n]
-    if (int rc = ss_paths(xd.p, n, lts + l0, ms, ng, zd.p, zd.stride, 0, y == nullptr, f.p)) return rc;
-    if (y)
-      if (int rc = ss_condition(xd.p, n, lts + l0, ms, ng, Fr.w.p, Fr.r.p, xid.p, xid.stride, 0, true, f.p)) return rc;
-    // the mixing of lmm_lmm_rand (reference src/oilmm.jl:50-53): H X + sqrt(sigma2) eps
-    for (int q = 0; q < ng; ++q)
-      launch_mix(f.p + (size_t)q * ms * n, n, ms, Hd.buf.p, p, 1, 0.0, 0.0, add_noise ? epsd.p + (size_t)q * epsd.stride : nullptr,
-                 std::sqrt(sigma2), od.p + (size_t)(q0 + q) * n * p, st0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st0));            // the group's buffers go back to the pool
-  }
+    if (int rc = ss_paths(T.xd.p, n, lts + l0, ms, ng, zd.p, zd.stride, 0, y == nullptr, f)) return rc;
+    if (y == nullptr) return (int)LMM_OK;
+    return ss_condition(T.xd.p, n, lts + l0, ms, ng, T.Fr.w.p, T.Fr.r.p, xid.p, xid.stride, 0, true, f);
+  });
+  if (rc) return rc;
   od.finish(st0);
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
@@ -5765,22 +5794,16 @@ int lmm_oilmm_rand_statespace(const double* x, int n, const double* y, int p, co
 // Building blocks for tests beside lmm_dev_statespace_smooth: ONE latent from DEVICE pointers, its mean not read.  f: [sample][n].
 static int ss_dev_sample(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, const double* z, const double* xi,
                          int nsamples, int chunk, double* f) {
-  if (n <= 0 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  RESOLVE_SS(gp, 1);
-  if (int rc = ss_check_latents(lts, 1)) return rc;
-  if (int rc = ss_check_sorted(x, n)) return rc;
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = ss_dev_prepare(n <= 0 || chunk < 0, x, n, gp, ls, nsamples)) return rc;
+  const Latent* lts = ls->lat.data();
   const size_t zs = (size_t)ss_state_dim(lts[0].kind) * n;
-  const int group = ss_sample_group(n, 1, nsamples);
-  for (int q0 = 0; q0 < nsamples; q0 += group) {
-    const int ng = std::min(group, nsamples - q0);
+  return ss_for_sample_groups(n, 1, nsamples, [&](int q0, int ng) {
     double* fq = f + (size_t)q0 * n;
     if (int rc = ss_paths(x, n, lts, 1, ng, z + (size_t)q0 * zs, zs, chunk, false, fq)) return rc;
-    if (w)
-      if (int rc = ss_condition(x, n, lts, 1, ng, w, r, xi + (size_t)q0 * n, (size_t)n, chunk, false, fq)) return rc;
-  }
-  return LMM_OK;
+    if (w == nullptr) return (int)LMM_OK;
+    return ss_condition(x, n, lts, 1, ng, w, r, xi + (size_t)q0 * n, (size_t)n, chunk, false, fq);
+  });
 }
 
 int lmm_dev_statespace_sample(const double* x, int n, const lmm_gp_t* gp, const double* z, int nsamples, int chunk, double* f) {
@@ -5833,38 +5856,15 @@ static int ss_window(const double* xd, int n, const double* xsd, int ns, SSWindo
 // Posterior paths of the ms latents lts[0 .. ms) at the sorted queries for N samples from their stored states (latent k's block
 // off[k] doubles into fstate / sstate): f[sample][latent][ns] on the device, with the latent's mean when add_mean.  z: sample 0's
 // normals of lts[0] on the device, the latents one after the other (D_l W values each, component-major over window positions), the
-// samples z_stride doubles apart.  The (latent, sample) pairs run in launches of one model.  Returns with streams[0] drained.
+// samples z_stride doubles apart.  Returns with streams[0] drained.
 static int ss_post_paths(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
                          const double* xsd, int ns, const SSWindow& w, int N, const double* z, size_t z_stride, int chunk, bool add_mean,
                          double* f) {
-  hipStream_t st0 = g.streams[0];
-  const int W = w.W;
-  if (chunk <= 0) chunk = ss_default_chunk(W);
-  if (chunk > W) chunk = W;
-  const int nch = (W + chunk - 1) / chunk;
-  std::vector<size_t> zoff(std::max(ms, 1), 0);
-  for (int k = 1; k < ms; ++k) zoff[k] = zoff[k - 1] + (size_t)ss_state_dim(lts[k - 1].kind) * W;
-  const long long ne = (long long)ms * N;
-  for (long long e0 = 0; e0 < ne;) {
-    const int model = ss_model_of(lts[e0 / N].kind), D = ss_model_dim(model);
-    const size_t per = ss_aff_agg_elems(D, nch) * sizeof(double);
-    const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / per));
-    int nb = 1;
-    while (e0 + nb < ne && nb < nbmax && ss_model_of(lts[(e0 + nb) / N].kind) == model) ++nb;
-    Buf<double> agg((size_t)nb * ss_aff_agg_elems(D, nch));
-    SSPostArgs a{};
-    a.x = xd; a.n = n; a.xs = xsd; a.ns = ns; a.src = w.src.p; a.first = w.first; a.W = W; a.chunk = chunk; a.nch = nch; a.agg = agg.p;
-    for (int j = 0; j < nb; ++j) {
-      const int k = (int)((e0 + j) / N), q = (int)((e0 + j) % N);
-      const Latent& L = lts[k];
-      a.lat[j] = SSPostLat{L.terms[0].ev.var, L.terms[0].ev.inv_ls, add_mean ? L.mean : 0.0, L.quality, fstate + off[k], sstate + off[k],
-                           z + (size_t)q * z_stride + zoff[k], f + ((size_t)q * ms + k) * ns};
-    }
-    launch_ss_post_path(a, model, nb, st0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st0));          // agg goes back to the pool
-    e0 += nb;
-  }
+  SSPostArgs a{};
+  a.x = xd; a.n = n; a.xs = xsd; a.ns = ns; a.src = w.src.p; a.first = w.first; a.W = w.W;
+  ss_pair_launches(lts, ms, N, w.W, chunk, add_mean, a, launch_ss_post_path, [&](SSPostLat& o, int k, int q, size_t zoff) {
+    o.fstate = fstate + off[k]; o.sstate = sstate + off[k]; o.z = z + (size_t)q * z_stride + zoff; o.f = f + ((size_t)q * ms + k) * ns;
+  });
   return LMM_OK;
 }
 
@@ -5886,12 +5886,12 @@ int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, 
   REQUIRE_INIT();
   LMM_TRY
   if (!post || !xs || !out || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  if (g_f32) return ss_refuse_f32();
   if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
   if (!z) return fail(LMM_ERR_ARG, "z is NULL");
   if (add_noise && !eps) return fail(LMM_ERR_ARG, "eps is NULL");
   const lmm_ss_post* P = post;
-  const int p = P->p, ms = P->l1 - P->l0, mk = std::max(ms, 1);
+  const int p = P->p, ms = P->l1 - P->l0;
   const Latent* lts = P->ls->lat.data() + P->l0;
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)ns, st0);
@@ -5900,21 +5900,12 @@ int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, 
   size_t zshard = 0;                               // doubles of one sample's z
   for (int k = 0; k < ms; ++k) zshard += (size_t)ss_state_dim(lts[k].kind) * w.W;
   DevOut od(out, (size_t)ns * p * nsamples);
-  const int group = ss_sample_group(std::max(w.W, ns), ms, nsamples);
-  for (int q0 = 0; q0 < nsamples; q0 += group) {
-    const int ng = std::min(group, nsamples - q0);
-    SSNormals zd(z, zshard, 0, zshard, q0, ng, st0), epsd(add_noise ? eps : nullptr, (size_t)ns * p, 0, (size_t)ns * p, q0, ng, st0);
-    Buf<double> f((size_t)ng * mk * ns);           // [sample][latent of the shard][ns]
-    if (int rc = ss_post_paths(P->x.p, P->n, lts, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, w, ng, zd.p, zd.stride, 0, true,
-                               f.p))
-      return rc;
-    // the mixing of lmm_oilmm_rand_statespace: H f + sqrt(sigma2) eps
-    for (int q = 0; q < ng; ++q)
-      launch_mix(f.p + (size_t)q * ms * ns, ns, ms, P->H.p, p, 1, 0.0, 0.0, add_noise ? epsd.p + (size_t)q * epsd.stride : nullptr,
-                 std::sqrt(P->sigma2), od.p + (size_t)(q0 + q) * ns * p, st0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st0));            // the group's buffers go back to the pool
-  }
+  const int rc = ss_sample_mix(ns, std::max(w.W, ns), ms, p, P->H.p, P->sigma2, add_noise ? eps : nullptr, nsamples, od.p,
+                               [&](int q0, int ng, double* f) {
+    SSNormals zd(z, zshard, 0, zshard, q0, ng, st0);
+    return ss_post_paths(P->x.p, P->n, lts, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, w, ng, zd.p, zd.stride, 0, true, f);
+  });
+  if (rc) return rc;
   od.finish(st0);
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
@@ -5928,25 +5919,20 @@ int lmm_dev_statespace_post_sample(const double* x, int n, const lmm_gp_t* gp, c
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !gp || !fstate || !sstate || !xs || !z || !f || n <= 0 || ns < 1 || chunk < 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
-  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "state-space inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  RESOLVE_SS(gp, 1);
-  if (int rc = ss_check_latents(lts, 1)) return rc;
-  if (int rc = ss_check_sorted(x, n)) return rc;
+  std::shared_ptr<LatentSet> ls;
+  const bool bad = !x || !gp || !fstate || !sstate || !xs || !z || !f || n <= 0 || ns < 1 || chunk < 0;
+  if (int rc = ss_dev_prepare(bad, x, n, gp, ls, nsamples)) return rc;
+  const Latent* lts = ls->lat.data();
   SSWindow w;
   if (int rc = ss_window(x, n, xs, ns, w)) return rc;
   const size_t zs = (size_t)ss_state_dim(lts[0].kind) * w.W, off = 0;
-  const int group = ss_sample_group(std::max(w.W, ns), 1, nsamples);
-  for (int q0 = 0; q0 < nsamples; q0 += group) {
-    const int ng = std::min(group, nsamples - q0);
-    if (int rc = ss_post_paths(x, n, lts, 1, fstate, sstate, &off, xs, ns, w, ng, z + (size_t)q0 * zs, zs, chunk, false,
-                               f + (size_t)q0 * ns))
-      return rc;
-  }
-  return LMM_OK;
+  return ss_for_sample_groups(std::max(w.W, ns), 1, nsamples, [&](int q0, int ng) {
+    return ss_post_paths(x, n, lts, 1, fstate, sstate, &off, xs, ns, w, ng, z + (size_t)q0 * zs, zs, chunk, false, f + (size_t)q0 * ns);
+  });
   LMM_CATCH
 }
+
+extern "C" {
 
 // Standard normals on the device (Philox4x32-10 + Box-Muller, Float64): out[j], j < count, reproducible for (seed, stream).
 // out may be a host or a device pointer.  Optional companion of lmm_lmm_rand / lmm_lmm_rand_multi, whose normals are

@@ -10,9 +10,9 @@
 // (the template arguments D and OSC: Matern12 / 32 / 52, or the damped oscillator of an SHO latent, which shares D = 2 with Matern32
 // but not its A(dt)); the scans see elements only and are shared between models of equal D.
 // Gradients (launch_ss_grad): d lml / d variance and d lml / d lengthscale (and an SHO latent's d lml / d quality) are the forward-mode
-// derivative of phases 1 - 3 of the filter, the same text instantiated with SSDual (lmm_statespace.h): ss_dfold_kernel, the scan over
-// SSFwd<D, SSDual> and ss_dfilter_kernel, with blockIdx.y the seeded parameter (2 per Matern latent, 3 per SHO latent), so a thread
-// carries one tangent.  d lml / d r_t and d lml / d w_t come from the smoothed
+// derivative of phases 1 - 3 of the filter, the same text instantiated with SSDual (lmm_statespace.h): ss_fold_kernel<D, OSC, SSDual>,
+// the scan over SSFwd<D, SSDual> and ss_filter_kernel<D, OSC, SSDual>, with blockIdx.y the seeded parameter (2 per Matern latent, 3 per
+// SHO latent), so a thread carries one tangent.  d lml / d r_t and d lml / d w_t come from the smoothed
 // marginals (ss_point_kernel), with fixed-order sums of what the OILMM chain rule needs.
 // Sampling (launch_ss_path): the prior path is an affine recursion in the caller's normals, so phases 1 - 3 run on SSAff<D> elements
 // (ss_sfold_kernel, the scan with AffOp, ss_path_kernel); a posterior path is the prior path plus the smoothed mean of the residual
@@ -24,10 +24,14 @@
 // between them are a Markov chain that runs backwards, an affine recursion in the caller's normals again, so phases 1 - 3 run from the
 // right on SSAff<D> elements built from the stored states (ss_window_kernel, ss_pfold_kernel, the suffix scan with AffRevOp,
 // ss_ppath_kernel); nothing outside the queries' span is read.
+// Shared by the kernels (lmm_statespace.h): ss_chunk_range (a thread's run), ss_count_le / ss_count_lt (the binary searches) and
+// ss_load_state (a stored state in either layout); ss_lat_model makes the model of any *Lat struct.  On the host, ss_dispatch hands a
+// launch's model to a generic lambda as compile-time (D, OSC), and ss_phases is the fold - scan - restart sequence of every direction.
 #include "lmm_internal.h"
 #include "lmm_statespace.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -50,36 +54,42 @@ __device__ __forceinline__ typename SSModelOf<D, OSC, Sc>::type ss_make_model(Sc
   return M;
 }
 
-template <int D, bool OSC>
-__device__ __forceinline__ typename SSModelOf<D, OSC>::type ss_lat_model(const SSLat& L) {
-  return ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
+// The model of a latent's (var, inv_ls, quality), of any of the *Lat structs.  Sc = SSDual: with the tangent of parameter `seed` set: 0 =
+// variance, 1 = lengthscale (d (1 / l) = -1 / l^2; an oscillator's period), 2 = an oscillator's quality
+template <int D, bool OSC, typename Sc = double, typename Lat>
+__device__ __forceinline__ typename SSModelOf<D, OSC, Sc>::type ss_lat_model(const Lat& L, int seed = 0) {
+  if constexpr (std::is_same<Sc, SSDual>::value)
+    return ss_make_model<D, OSC, SSDual>(SSDual(L.var, seed == 0 ? 1.0 : 0.0), SSDual(L.inv_ls, seed == 1 ? -L.inv_ls * L.inv_ls : 0.0),
+                                         SSDual(L.quality, seed == 2 ? 1.0 : 0.0));
+  else return ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
 }
 
-template <int D, bool OSC>
+// Fold and filter in both scalar types.  Sc = double: the value; the aggregates of latent z = blockIdx.z are item z of a.agg.
+// Sc = SSDual: (value, tangent) with blockIdx.y the seeded parameter (NS = ss_seeds<OSC>() of them), so a thread carries one tangent;
+// the aggregates of (latent z, seed s) are item NS z + s of a.dagg.
+template <int D, bool OSC, typename Sc>
 __global__ __launch_bounds__(SS_THREADS) void ss_fold_kernel(SSArgs a) {
-  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  constexpr bool DUAL = std::is_same<Sc, SSDual>::value;
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = DUAL ? blockIdx.y : 0;
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
-  const auto M = ss_lat_model<D, OSC>(L);
-  const long long t0 = (long long)j * a.chunk;
-  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
-  SSFwd<D> acc, el;
+  const auto M = ss_lat_model<D, OSC, Sc>(L, s);
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
+  SSFwd<D, Sc> acc, el;
   double xp = a.x[t0];
-  ss_fwd_element<D>(M, t0 == 0, t0 == 0 ? 0.0 : xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
+  ss_fwd_element<D, Sc>(M, t0 == 0, t0 == 0 ? 0.0 : xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
   for (long long t = t0 + 1; t < t1; ++t) {
     const double xt = a.x[t];
-    ss_fwd_element<D>(M, false, xt - xp, L.w[t], L.r[t], el);
-    ss_fwd_combine<D>(acc, el, acc);
+    ss_fwd_element<D, Sc>(M, false, xt - xp, L.w[t], L.r[t], el);
+    ss_fwd_combine<D, Sc>(acc, el, acc);
     xp = xt;
   }
-  reinterpret_cast<SSFwd<D>*>(a.agg)[(size_t)z * a.nch + j] = acc;
+  reinterpret_cast<SSFwd<D, Sc>*>(DUAL ? a.dagg : a.agg)[(size_t)(DUAL ? ss_seeds<OSC>() * z + s : z) * a.nch + j] = acc;
 }
 
 struct FwdOp {
-  template <int D> static __device__ __forceinline__ void combine(const SSFwd<D>& a, const SSFwd<D>& b, SSFwd<D>& o) { ss_fwd_combine<D>(a, b, o); }
-  template <int D> static __device__ __forceinline__ void combine(const SSFwd<D, SSDual>& a, const SSFwd<D, SSDual>& b, SSFwd<D, SSDual>& o) {
-    ss_fwd_combine<D, SSDual>(a, b, o);
-  }
+  template <int D, typename Sc>
+  static __device__ __forceinline__ void combine(const SSFwd<D, Sc>& a, const SSFwd<D, Sc>& b, SSFwd<D, Sc>& o) { ss_fwd_combine<D, Sc>(a, b, o); }
 };
 struct BwdOp {
   template <int D> static __device__ __forceinline__ void combine(const SSBwd<D>& a, const SSBwd<D>& b, SSBwd<D>& o) { ss_bwd_combine<D>(a, b, o); }
@@ -146,25 +156,23 @@ void scan_levels(T* items, int N, int nb, T* scratch, hipStream_t st) {
   hipLaunchKernelGGL((ss_addprefix_kernel<D, T, Op, REV>), dim3(nblk - 1, 1, nb), dim3(W), 0, st, items, N, (const T*)scratch);
 }
 
-// packed index of the symmetric entry (i, j), i <= j, behind the D mean components of a filtered state
-__host__ __device__ constexpr int ss_sym_at(int D, int i, int j) { return D + i * D - i * (i - 1) / 2 + (j - i); }
-
-template <int D, bool OSC>
+// Sc = double writes the marginals, the states and its log-density partial; Sc = SSDual only the tangent of its partial
+template <int D, bool OSC, typename Sc>
 __global__ __launch_bounds__(SS_THREADS) void ss_filter_kernel(SSArgs a) {
-  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  constexpr bool DUAL = std::is_same<Sc, SSDual>::value;
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = DUAL ? blockIdx.y : 0;
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
-  const auto M = ss_lat_model<D, OSC>(L);
-  const long long t0 = (long long)j * a.chunk;
-  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
-  double m[D], P[D][D];
+  const auto M = ss_lat_model<D, OSC, Sc>(L, s);
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
+  Sc m[D], P[D][D];
   if (j == 0) {
     for (int i = 0; i < D; ++i) {
       m[i] = 0.0;
       for (int k = 0; k < D; ++k) P[i][k] = M.Pinf[i][k];
     }
   } else {
-    const SSFwd<D>& pre = reinterpret_cast<const SSFwd<D>*>(a.agg)[(size_t)z * a.nch + j - 1];
+    const SSFwd<D, Sc>& pre = reinterpret_cast<const SSFwd<D, Sc>*>(DUAL ? a.dagg : a.agg)[(size_t)(DUAL ? ss_seeds<OSC>() * z + s : z) * a.nch + j - 1];
     for (int i = 0; i < D; ++i) {
       m[i] = pre.b[i];
       for (int k = 0; k < D; ++k) P[i][k] = pre.C[i][k];
@@ -173,22 +181,25 @@ __global__ __launch_bounds__(SS_THREADS) void ss_filter_kernel(SSArgs a) {
   double* fm = a.fmean ? a.fmean + (size_t)z * a.n : nullptr;
   double* fv = a.fvar ? a.fvar + (size_t)z * a.n : nullptr;
   double* stt = a.state ? a.state + (size_t)z * a.state_stride : nullptr;
-  double lp = 0.0;
+  Sc lp = 0.0;
   double xp = t0 == 0 ? a.x[0] : a.x[t0 - 1];
   for (long long t = t0; t < t1; ++t) {
     const double xt = a.x[t];
-    lp += ss_filter_step<D>(M, xt - xp, L.w[t], L.r[t], m, P);
+    lp += ss_filter_step<D, Sc>(M, xt - xp, L.w[t], L.r[t], m, P);
     xp = xt;
-    if (fm) fm[t] = m[0];
-    if (fv) fv[t] = P[0][0];
-    if (stt) {
-      for (int i = 0; i < D; ++i) {
-        stt[(size_t)i * a.n + t] = m[i];
-        for (int k = i; k < D; ++k) stt[(size_t)ss_sym_at(D, i, k) * a.n + t] = P[i][k];
+    if constexpr (!DUAL) {
+      if (fm) fm[t] = m[0];
+      if (fv) fv[t] = P[0][0];
+      if (stt) {
+        for (int i = 0; i < D; ++i) {
+          stt[(size_t)i * a.n + t] = m[i];
+          for (int k = i; k < D; ++k) stt[(size_t)ss_sym_at(D, i, k) * a.n + t] = P[i][k];
+        }
       }
     }
   }
-  a.part[(size_t)z * a.nch + j] = lp;
+  if constexpr (DUAL) a.dpart[(size_t)(ss_seeds<OSC>() * z + s) * a.nch + j] = lp.t;
+  else a.part[(size_t)z * a.nch + j] = lp;
 }
 
 // lml[z] = the nch partials of latent z: each thread adds a contiguous strip in order, thread 0 adds the strips in thread order
@@ -207,70 +218,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_finish_kernel(const double* __r
   }
 }
 
-
-// ---- gradients ---------------------------------------------------------------------------------------------------------------
-// The model of latent L with the tangent of parameter `seed` set: 0 = variance, 1 = lengthscale (d (1 / l) = -1 / l^2; an oscillator's
-// period), 2 = an oscillator's quality
-template <int D, bool OSC>
-__device__ __forceinline__ typename SSModelOf<D, OSC, SSDual>::type ss_lat_dmodel(const SSLat& L, int seed) {
-  return ss_make_model<D, OSC, SSDual>(SSDual(L.var, seed == 0 ? 1.0 : 0.0), SSDual(L.inv_ls, seed == 1 ? -L.inv_ls * L.inv_ls : 0.0),
-                                       SSDual(L.quality, seed == 2 ? 1.0 : 0.0));
-}
-
-// ss_fold_kernel on (value, tangent): blockIdx.y is the seeded parameter (NS = ss_seeds<OSC>() of them), the aggregates of (latent z,
-// seed s) are item NS z + s
-template <int D, bool OSC>
-__global__ __launch_bounds__(SS_THREADS) void ss_dfold_kernel(SSArgs a) {
-  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = blockIdx.y;
-  if (j >= a.nch) return;
-  const SSLat& L = a.lat[z];
-  const auto M = ss_lat_dmodel<D, OSC>(L, s);
-  const long long t0 = (long long)j * a.chunk;
-  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
-  SSFwd<D, SSDual> acc, el;
-  double xp = a.x[t0];
-  ss_fwd_element<D, SSDual>(M, t0 == 0, t0 == 0 ? 0.0 : xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
-  for (long long t = t0 + 1; t < t1; ++t) {
-    const double xt = a.x[t];
-    ss_fwd_element<D, SSDual>(M, false, xt - xp, L.w[t], L.r[t], el);
-    ss_fwd_combine<D, SSDual>(acc, el, acc);
-    xp = xt;
-  }
-  reinterpret_cast<SSFwd<D, SSDual>*>(a.dagg)[(size_t)(ss_seeds<OSC>() * z + s) * a.nch + j] = acc;
-}
-
-// ss_filter_kernel on (value, tangent): writes only the tangent of its log-density partial
-template <int D, bool OSC>
-__global__ __launch_bounds__(SS_THREADS) void ss_dfilter_kernel(SSArgs a) {
-  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = blockIdx.y;
-  if (j >= a.nch) return;
-  const SSLat& L = a.lat[z];
-  const auto M = ss_lat_dmodel<D, OSC>(L, s);
-  const long long t0 = (long long)j * a.chunk;
-  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
-  SSDual m[D], P[D][D];
-  if (j == 0) {
-    for (int i = 0; i < D; ++i) {
-      m[i] = 0.0;
-      for (int k = 0; k < D; ++k) P[i][k] = M.Pinf[i][k];
-    }
-  } else {
-    const SSFwd<D, SSDual>& pre = reinterpret_cast<const SSFwd<D, SSDual>*>(a.dagg)[(size_t)(ss_seeds<OSC>() * z + s) * a.nch + j - 1];
-    for (int i = 0; i < D; ++i) {
-      m[i] = pre.b[i];
-      for (int k = 0; k < D; ++k) P[i][k] = pre.C[i][k];
-    }
-  }
-  SSDual lp = 0.0;
-  double xp = t0 == 0 ? a.x[0] : a.x[t0 - 1];
-  for (long long t = t0; t < t1; ++t) {
-    const double xt = a.x[t];
-    lp += ss_filter_step<D, SSDual>(M, xt - xp, L.w[t], L.r[t], m, P);
-    xp = xt;
-  }
-  a.dpart[(size_t)(ss_seeds<OSC>() * z + s) * a.nch + j] = lp.t;
-}
-
+// ---- gradients: the pointwise part (the forward-mode part is ss_fold_kernel / ss_filter_kernel with Sc = SSDual) -----------------------
 constexpr int SS_POINT_PER = 8;      // points per thread of ss_point_kernel
 
 // Per point, from the smoothed first-component mean mu and variance Ps (without the latent's mean): alpha_t = (r_t - mu_t) / w_t and
@@ -309,27 +257,18 @@ __global__ __launch_bounds__(SS_THREADS) void ss_point_kernel(SSArgs a, double* 
   if (threadIdx.x < 4) ppart[((size_t)z * 4 + threadIdx.x) * nblk + blockIdx.x] = sh[threadIdx.x][0];
 }
 
-template <int D>
-__device__ __forceinline__ void ss_load_state(const double* stt, int n, long long t, double m[D], double P[D][D]) {
-  for (int i = 0; i < D; ++i) {
-    m[i] = stt[(size_t)i * n + t];
-    for (int k = i; k < D; ++k) P[i][k] = P[k][i] = stt[(size_t)ss_sym_at(D, i, k) * n + t];
-  }
-}
-
 template <int D, bool OSC>
 __global__ __launch_bounds__(SS_THREADS) void ss_bfold_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const auto M = ss_lat_model<D, OSC>(a.lat[z]);
-  const long long t0 = (long long)j * a.chunk;
-  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
   const double* stt = a.state + (size_t)z * a.state_stride;
   SSBwd<D> acc, el;
   double m[D], P[D][D];
   for (long long t = t0; t < t1; ++t) {
     const bool last = t == a.n - 1;
-    ss_load_state<D>(stt, a.n, t, m, P);
+    ss_load_state<D>(stt, a.n, 1, t, m, P);                   // component-major
     ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, t == t0 ? acc : el);
     if (t > t0) ss_bwd_combine<D>(acc, el, acc);
   }
@@ -344,8 +283,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
   const auto M = ss_lat_model<D, OSC>(L);
-  const long long t0 = (long long)j * a.chunk;
-  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
   const double* stt = a.state + (size_t)z * a.state_stride;
   double ms[D], Ps[D][D];
   for (int i = 0; i < D; ++i) {       // the last chunk has no successor: its first element has E = 0 and ignores this state
@@ -365,7 +303,7 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
   double m[D], P[D][D];
   for (long long t = t1 - 1; t >= t0; --t) {
     const bool last = t == a.n - 1;
-    ss_load_state<D>(stt, a.n, t, m, P);
+    ss_load_state<D>(stt, a.n, 1, t, m, P);                   // component-major
     ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, el);
     ss_rts_step<D>(el, ms, Ps);
     if (!FULL || sm) sm[t] = ms[0] + L.mean;
@@ -391,16 +329,9 @@ __global__ __launch_bounds__(SS_THREADS) void ss_interp_kernel(SSInterpArgs a) {
   const int q = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (q >= a.ns) return;
   const SSInterpLat& L = a.lat[z];
-  const auto M = ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
+  const auto M = ss_lat_model<D, OSC>(L);
   const double s = a.xs[q];
-  int lo = 0, hi = a.n;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (a.x[mid] <= s) lo = mid + 1;
-    else hi = mid;
-  }
-  const int k = lo;
-  constexpr int NC = D + D * (D + 1) / 2;
+  const int k = ss_count_le(a.x, 0, a.n, s);
   double m[D], P[D][D], ms[D], Ps[D][D];
   for (int i = 0; i < D; ++i) {
     m[i] = 0.0; ms[i] = 0.0;
@@ -408,23 +339,11 @@ __global__ __launch_bounds__(SS_THREADS) void ss_interp_kernel(SSInterpArgs a) {
   }
   double d1 = 0.0, d2 = 0.0;
   if (k > 0) {
-    const double* f = a.fstate + (size_t)z * a.state_stride + (size_t)(k - 1) * a.point_stride;
-    double c[NC];
-    for (int i = 0; i < NC; ++i) c[i] = f[(size_t)i * a.comp_stride];
-    for (int i = 0; i < D; ++i) {
-      m[i] = c[i];
-      for (int j = i; j < D; ++j) P[i][j] = P[j][i] = c[ss_sym_at(D, i, j)];
-    }
+    ss_load_state<D>(a.fstate + (size_t)z * a.state_stride, a.comp_stride, a.point_stride, k - 1, m, P);
     d1 = s - a.x[k - 1];
   }
   if (k < a.n) {
-    const double* f = a.sstate + (size_t)z * a.state_stride + (size_t)k * a.point_stride;
-    double c[NC];
-    for (int i = 0; i < NC; ++i) c[i] = f[(size_t)i * a.comp_stride];
-    for (int i = 0; i < D; ++i) {
-      ms[i] = c[i];
-      for (int j = i; j < D; ++j) Ps[i][j] = Ps[j][i] = c[ss_sym_at(D, i, j)];
-    }
+    ss_load_state<D>(a.sstate + (size_t)z * a.state_stride, a.comp_stride, a.point_stride, k, ms, Ps);
     d2 = a.x[k] - s;
   }
   ss_interp<D>(M, k > 0, d1, k < a.n, d2, m, P, ms, Ps);
@@ -462,11 +381,6 @@ __global__ __launch_bounds__(256) void ss_scatter_rows_kernel(const double* __re
 // The prior path s_t = A(dt_t) s_{t-1} + chol(Q(dt_t)) zeta_t, s_0 = chol(Pinf) zeta_0, is an affine recursion, so the same three
 // phases serve it with SSAff<D> elements (D^2 + D doubles): ss_sfold_kernel, the scan with AffOp, ss_path_kernel.  blockIdx.z runs over
 // the (latent, sample) pairs of a launch; zeta is read straight from the caller's buffer, component i of point t at z[i n + t].
-template <int D, bool OSC>
-__device__ __forceinline__ typename SSModelOf<D, OSC>::type ss_path_model(const SSPathLat& L) {
-  return ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
-}
-
 template <int D>
 __device__ __forceinline__ void ss_load_zeta(const double* __restrict__ z, int n, long long t, double zeta[D]) {
   for (int i = 0; i < D; ++i) zeta[i] = z[(size_t)i * n + t];
@@ -477,9 +391,8 @@ __global__ __launch_bounds__(SS_THREADS) void ss_sfold_kernel(SSPathArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const SSPathLat& L = a.lat[z];
-  const auto M = ss_path_model<D, OSC>(L);
-  const long long t0 = (long long)j * a.chunk;
-  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  const auto M = ss_lat_model<D, OSC>(L);
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
   SSAff<D> acc, el;
   double zeta[D];
   double xp = a.x[t0];
@@ -505,9 +418,8 @@ __global__ __launch_bounds__(SS_THREADS) void ss_path_kernel(SSPathArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const SSPathLat& L = a.lat[z];
-  const auto M = ss_path_model<D, OSC>(L);
-  const long long t0 = (long long)j * a.chunk;
-  const long long t1 = t0 + a.chunk < a.n ? t0 + a.chunk : a.n;
+  const auto M = ss_lat_model<D, OSC>(L);
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
   double s[D], zeta[D];
   for (int i = 0; i < D; ++i) s[i] = 0.0;           // the first element has A = 0 and ignores this state
   if (j > 0) {
@@ -559,13 +471,7 @@ __global__ void ss_window_bounds_kernel(const double* __restrict__ x, int n, con
                                         int* __restrict__ out) {
   if (threadIdx.x > 1 || blockIdx.x > 0) return;
   const double s = xs ? (threadIdx.x ? xs[ns - 1] : xs[0]) : (threadIdx.x ? hi : lo);
-  int l = 0, h = n;
-  while (l < h) {
-    const int mid = l + ((h - l) >> 1);
-    if (x[mid] <= s) l = mid + 1;
-    else h = mid;
-  }
-  out[threadIdx.x] = l;
+  out[threadIdx.x] = ss_count_le(x, 0, n, s);
 }
 
 // One thread per window point.  Thread u < count is training point t = first + u, at (t - first) + #{i : q_i < x_t}; thread count + i
@@ -578,33 +484,12 @@ __global__ __launch_bounds__(256) void ss_window_kernel(const double* __restrict
   if (u < count) {
     const int t = first + (int)u;
     const double xt = x[t];
-    int l = 0, h = ns;
-    while (l < h) {
-      const int mid = l + ((h - l) >> 1);
-      if (xs[mid] < xt) l = mid + 1;
-      else h = mid;
-    }
-    src[(long long)u + l] = t;
+    src[(long long)u + ss_count_lt(xs, 0, ns, xt)] = t;
   } else {
     const int i = (int)(u - count);
     const double s = xs[i];
-    int l = first, h = first + count;       // first <= #{t : x_t <= q_i} <= first + count: q_0 <= q_i <= q_{ns-1}
-    while (l < h) {
-      const int mid = l + ((h - l) >> 1);
-      if (x[mid] <= s) l = mid + 1;
-      else h = mid;
-    }
-    src[(long long)i + (l - first)] = -1 - i;
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void ss_load_point_state(const double* __restrict__ st, long long t, double m[D], double P[D][D]) {
-  constexpr int NC = D + D * (D + 1) / 2;
-  const double* f = st + (size_t)t * NC;
-  for (int i = 0; i < D; ++i) {
-    m[i] = f[i];
-    for (int k = i; k < D; ++k) P[i][k] = P[k][i] = f[ss_sym_at(D, i, k)];
+    // first <= #{t : x_t <= q_i} <= first + count: q_0 <= q_i <= q_{ns-1}
+    src[(long long)i + (ss_count_le(x, first, first + count, s) - first)] = -1 - i;
   }
 }
 
@@ -620,16 +505,17 @@ __device__ __forceinline__ double ss_window_input(const SSPostArgs& a, long long
 template <int D, typename Mod>
 __device__ __forceinline__ void ss_window_element(const SSPostArgs& a, const SSPostLat& L, const Mod& M, long long j, double xj, double xn,
                                                   SSAff<D>& e) {
+  constexpr int NC = D + D * (D + 1) / 2;       // the stored states are point-major
   const int s = a.src[j];
   double m[D], P[D][D], ms[D], Ps[D][D], zeta[D];
   int k;
   if (s >= 0) {
-    ss_load_point_state<D>(L.fstate, s, m, P);
+    ss_load_state<D>(L.fstate, 1, NC, s, m, P);
     k = s + 1;
   } else {
     k = a.first + (int)(j - (-1 - s));
     if (k > 0) {
-      ss_load_point_state<D>(L.fstate, k - 1, m, P);
+      ss_load_state<D>(L.fstate, 1, NC, k - 1, m, P);
       ss_filter_step<D>(M, xj - a.x[k - 1], INFINITY, 0.0, m, P);
     } else {
       for (int i = 0; i < D; ++i) {
@@ -647,7 +533,7 @@ __device__ __forceinline__ void ss_window_element(const SSPostArgs& a, const SSP
   if (last) {
     dt = 0.0;
     if (has_next) {
-      ss_load_point_state<D>(L.sstate, k, ms, Ps);
+      ss_load_state<D>(L.sstate, 1, NC, k, ms, Ps);
       dt = a.x[k] - xj;
     }
   }
@@ -666,7 +552,9 @@ __global__ __launch_bounds__(SS_THREADS) void ss_pfold_kernel(SSPostArgs a) {
   const int c = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (c >= a.nch) return;
   const SSPostLat& L = a.lat[z];
-  const auto M = ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
+  const auto M = ss_lat_model<D, OSC>(L);
+  // ss_chunk_range's text, written out here and in ss_ppath_kernel: `j1 < a.W` below shares its comparison only when the compiler sees
+  // both in the kernel before it inlines, and through the helper these two kernels come out with other code (SHO: 4 more VGPRs)
   const long long j0 = (long long)c * a.chunk;
   const long long j1 = j0 + a.chunk < a.W ? j0 + a.chunk : a.W;
   SSAff<D> acc, el;
@@ -687,8 +575,8 @@ __global__ __launch_bounds__(SS_THREADS) void ss_ppath_kernel(SSPostArgs a) {
   const int c = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (c >= a.nch) return;
   const SSPostLat& L = a.lat[z];
-  const auto M = ss_make_model<D, OSC, double>(L.var, L.inv_ls, L.quality);
-  const long long j0 = (long long)c * a.chunk;
+  const auto M = ss_lat_model<D, OSC>(L);
+  const long long j0 = (long long)c * a.chunk;           // as in ss_pfold_kernel
   const long long j1 = j0 + a.chunk < a.W ? j0 + a.chunk : a.W;
   double s[D];
   for (int i = 0; i < D; ++i) s[i] = 0.0;           // the last element has A = 0 and ignores this state
@@ -715,59 +603,30 @@ size_t scan_items(int nch, int W = SS_SCAN) {         // items of every level be
   return tot;
 }
 
-template <int D, bool OSC>
-void filter_D(const SSArgs& a, int nb, double* lml, hipStream_t st) {
-  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
-  hipLaunchKernelGGL((ss_fold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-  SSFwd<D>* agg = reinterpret_cast<SSFwd<D>*>(a.agg);
-  scan_levels<D, SSFwd<D>, FwdOp, false>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
-  hipLaunchKernelGGL((ss_filter_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-  if (lml) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
+// doubles of one item's aggregates of type E and of its share of the scan's levels
+template <typename E>
+size_t agg_elems(int nch) { return ((size_t)nch + scan_items(nch, ss_scan_width<E>())) * (sizeof(E) / sizeof(double)); }
+
+// f(SSModelTag<D, OSC>()) for the model of a launch, so that D and OSC reach the generic lambda f as compile-time constants.  A state
+// dimension 1 / 2 / 3 is the number of its Matern model, which is how the element sizes below dispatch on D.
+static_assert(SS_MODEL_SHO > 3, "ss_dispatch takes a state dimension 1 / 2 / 3 for its Matern model: none may be the oscillator's number");
+template <int D_, bool OSC_> struct SSModelTag { static constexpr int D = D_; static constexpr bool OSC = OSC_; };
+template <typename F>
+auto ss_dispatch(int model, F&& f) {
+  if (model == SS_MODEL_SHO) return f(SSModelTag<2, true>());
+  if (model == 1) return f(SSModelTag<1, false>());
+  if (model == 2) return f(SSModelTag<2, false>());
+  return f(SSModelTag<3, false>());
 }
 
-template <int D, bool OSC>
-void smooth_D(const SSArgs& a, int nb, hipStream_t st) {
-  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
-  hipLaunchKernelGGL((ss_bfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-  SSBwd<D>* agg = reinterpret_cast<SSBwd<D>*>(a.bagg);
-  scan_levels<D, SSBwd<D>, BwdOp, true>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
-  if (a.sstate) hipLaunchKernelGGL((ss_rts_kernel<D, OSC, true>), grid, dim3(SS_THREADS), 0, st, a);
-  else hipLaunchKernelGGL((ss_rts_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-}
-
-template <int D, bool OSC>
-void interp_D(const SSInterpArgs& a, int nb, hipStream_t st) {
-  hipLaunchKernelGGL((ss_interp_kernel<D, OSC>), dim3((a.ns + SS_THREADS - 1) / SS_THREADS, 1, nb), dim3(SS_THREADS), 0, st, a);
-}
-
-template <int D, bool OSC>
-void grad_D(const SSArgs& a, int nb, double* gtheta, hipStream_t st) {
-  constexpr int NS = ss_seeds<OSC>();
-  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, NS, nb);
-  hipLaunchKernelGGL((ss_dfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-  typedef SSFwd<D, SSDual> E;
-  E* agg = reinterpret_cast<E*>(a.dagg);
-  scan_levels<D, E, FwdOp, false>(agg, a.nch, NS * nb, agg + (size_t)NS * nb * a.nch, st);
-  hipLaunchKernelGGL((ss_dfilter_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-  hipLaunchKernelGGL(ss_finish_kernel, dim3(NS * nb), dim3(SS_THREADS), 0, st, (const double*)a.dpart, a.nch, gtheta);
-}
-
-template <int D, bool OSC>
-void path_D(const SSPathArgs& a, int nb, hipStream_t st) {
-  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
-  hipLaunchKernelGGL((ss_sfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-  SSAff<D>* agg = reinterpret_cast<SSAff<D>*>(a.agg);
-  scan_levels<D, SSAff<D>, AffOp, false>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
-  hipLaunchKernelGGL((ss_path_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-}
-
-template <int D, bool OSC>
-void post_path_D(const SSPostArgs& a, int nb, hipStream_t st) {
-  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, 1, nb);
-  hipLaunchKernelGGL((ss_pfold_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
-  SSAff<D>* agg = reinterpret_cast<SSAff<D>*>(a.agg);
-  scan_levels<D, SSAff<D>, AffRevOp, true>(agg, a.nch, nb, agg + (size_t)nb * a.nch, st);
-  hipLaunchKernelGGL((ss_ppath_kernel<D, OSC>), grid, dim3(SS_THREADS), 0, st, a);
+// Phases 1 - 3 with nch threads per item and ny * nb items (grid (., ny, nb)): fold, the scan of the items' aggregates E at agg, restart
+template <int D, typename E, typename Op, bool REV, typename Args>
+void ss_phases(void (*fold)(Args), void (*restart)(Args), const Args& a, int ny, int nb, double* agg, hipStream_t st) {
+  const dim3 grid((a.nch + SS_THREADS - 1) / SS_THREADS, ny, nb);
+  hipLaunchKernelGGL(fold, grid, dim3(SS_THREADS), 0, st, a);
+  E* e = reinterpret_cast<E*>(agg);
+  scan_levels<D, E, Op, REV>(e, a.nch, ny * nb, e + (size_t)ny * nb * a.nch, st);
+  hipLaunchKernelGGL(restart, grid, dim3(SS_THREADS), 0, st, a);
 }
 
 }  // namespace
@@ -780,27 +639,38 @@ int ss_model_seeds(int model) { return model == SS_MODEL_SHO ? ss_seeds<true>() 
 int ss_state_dim(int kind) { return ss_model_dim(ss_model_of(kind)); }
 int ss_state_comps(int D) { return D + D * (D + 1) / 2; }
 int ss_default_chunk(int n) { return n <= 4096 ? 16 : 64; }
-size_t ss_fwd_agg_elems(int D, int nch) {
-  const size_t e = D == 1 ? sizeof(SSFwd<1>) : D == 2 ? sizeof(SSFwd<2>) : sizeof(SSFwd<3>);
-  return ((size_t)nch + scan_items(nch)) * (e / sizeof(double));
-}
-size_t ss_bwd_agg_elems(int D, int nch) {
-  const size_t e = D == 1 ? sizeof(SSBwd<1>) : D == 2 ? sizeof(SSBwd<2>) : sizeof(SSBwd<3>);
-  return ((size_t)nch + scan_items(nch)) * (e / sizeof(double));
-}
-
+size_t ss_fwd_agg_elems(int D, int nch) { return ss_dispatch(D, [&](auto t) { return agg_elems<SSFwd<decltype(t)::D>>(nch); }); }
+size_t ss_bwd_agg_elems(int D, int nch) { return ss_dispatch(D, [&](auto t) { return agg_elems<SSBwd<decltype(t)::D>>(nch); }); }
+size_t ss_aff_agg_elems(int D, int nch) { return ss_dispatch(D, [&](auto t) { return agg_elems<SSAff<decltype(t)::D>>(nch); }); }
 size_t ss_dual_agg_elems(int D, int nch, int nseeds) {
-  const size_t e = D == 1 ? sizeof(SSFwd<1, SSDual>) : D == 2 ? sizeof(SSFwd<2, SSDual>) : sizeof(SSFwd<3, SSDual>);
-  const int W = D == 1 ? ss_scan_width<SSFwd<1, SSDual>>() : D == 2 ? ss_scan_width<SSFwd<2, SSDual>>() : ss_scan_width<SSFwd<3, SSDual>>();
-  return nseeds * ((size_t)nch + scan_items(nch, W)) * (e / sizeof(double));
+  return nseeds * ss_dispatch(D, [&](auto t) { return agg_elems<SSFwd<decltype(t)::D, SSDual>>(nch); });
 }
 int ss_point_blocks(int n) { return (n + SS_THREADS * SS_POINT_PER - 1) / (SS_THREADS * SS_POINT_PER); }
 
+void launch_ss_filter(const SSArgs& a, int model, int nb, double* lml, hipStream_t st) {
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    ss_phases<T::D, SSFwd<T::D>, FwdOp, false>(ss_fold_kernel<T::D, T::OSC, double>, ss_filter_kernel<T::D, T::OSC, double>, a, 1, nb, a.agg, st);
+  });
+  if (lml) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
+}
+
+void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st) {
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    ss_phases<T::D, SSBwd<T::D>, BwdOp, true>(ss_bfold_kernel<T::D, T::OSC>, a.sstate ? ss_rts_kernel<T::D, T::OSC, true> : ss_rts_kernel<T::D, T::OSC>,
+                                              a, 1, nb, a.bagg, st);
+  });
+}
+
 void launch_ss_grad(const SSArgs& a, int model, int nb, double* gtheta, hipStream_t st) {
-  if (model == SS_MODEL_SHO) grad_D<2, true>(a, nb, gtheta, st);
-  else if (model == 1) grad_D<1, false>(a, nb, gtheta, st);
-  else if (model == 2) grad_D<2, false>(a, nb, gtheta, st);
-  else grad_D<3, false>(a, nb, gtheta, st);
+  const int NS = ss_model_seeds(model);
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    ss_phases<T::D, SSFwd<T::D, SSDual>, FwdOp, false>(ss_fold_kernel<T::D, T::OSC, SSDual>, ss_filter_kernel<T::D, T::OSC, SSDual>, a, NS, nb,
+                                                       a.dagg, st);
+  });
+  hipLaunchKernelGGL(ss_finish_kernel, dim3(NS * nb), dim3(SS_THREADS), 0, st, (const double*)a.dpart, a.nch, gtheta);
 }
 
 void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, double* ppart, double* sums, hipStream_t st) {
@@ -809,27 +679,25 @@ void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, dou
   hipLaunchKernelGGL(ss_finish_kernel, dim3(4 * nb), dim3(SS_THREADS), 0, st, (const double*)ppart, nblk, sums);
 }
 
-void launch_ss_filter(const SSArgs& a, int model, int nb, double* lml, hipStream_t st) {
-  if (model == SS_MODEL_SHO) filter_D<2, true>(a, nb, lml, st);
-  else if (model == 1) filter_D<1, false>(a, nb, lml, st);
-  else if (model == 2) filter_D<2, false>(a, nb, lml, st);
-  else filter_D<3, false>(a, nb, lml, st);
-}
-
-void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st) {
-  if (model == SS_MODEL_SHO) smooth_D<2, true>(a, nb, st);
-  else if (model == 1) smooth_D<1, false>(a, nb, st);
-  else if (model == 2) smooth_D<2, false>(a, nb, st);
-  else smooth_D<3, false>(a, nb, st);
-}
-
-size_t ss_aff_agg_elems(int D, int nch) { return ((size_t)nch + scan_items(nch)) * (size_t)(D * D + D); }
-
 void launch_ss_path(const SSPathArgs& a, int model, int nb, hipStream_t st) {
-  if (model == SS_MODEL_SHO) path_D<2, true>(a, nb, st);
-  else if (model == 1) path_D<1, false>(a, nb, st);
-  else if (model == 2) path_D<2, false>(a, nb, st);
-  else path_D<3, false>(a, nb, st);
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    ss_phases<T::D, SSAff<T::D>, AffOp, false>(ss_sfold_kernel<T::D, T::OSC>, ss_path_kernel<T::D, T::OSC>, a, 1, nb, a.agg, st);
+  });
+}
+
+void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st) {
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    ss_phases<T::D, SSAff<T::D>, AffRevOp, true>(ss_pfold_kernel<T::D, T::OSC>, ss_ppath_kernel<T::D, T::OSC>, a, 1, nb, a.agg, st);
+  });
+}
+
+void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st) {
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((ss_interp_kernel<T::D, T::OSC>), dim3((a.ns + SS_THREADS - 1) / SS_THREADS, 1, nb), dim3(SS_THREADS), 0, st, a);
+  });
 }
 
 void launch_ss_pathwise(const double* r, const double* w, const double* f, const double* xi, size_t xi_stride, int n, int ms, int N,
@@ -846,11 +714,9 @@ void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st) {
   hipLaunchKernelGGL(ss_sorted_kernel, dim3(blocks), dim3(256), 0, st, x, n, flag);
 }
 
-void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st) {
-  if (model == SS_MODEL_SHO) interp_D<2, true>(a, nb, st);
-  else if (model == 1) interp_D<1, false>(a, nb, st);
-  else if (model == 2) interp_D<2, false>(a, nb, st);
-  else interp_D<3, false>(a, nb, st);
+void launch_ss_finite(const double* xs, int ns, int* flag, hipStream_t st) {
+  const int blocks = (int)std::min<long long>(2048, ((long long)ns + 255) / 256);
+  hipLaunchKernelGGL(ss_finite_kernel, dim3(blocks), dim3(256), 0, st, xs, ns, flag);
 }
 
 void launch_ss_window_bounds(const double* x, int n, const double* xs, int ns, double lo, double hi, int* out, hipStream_t st) {
@@ -860,18 +726,6 @@ void launch_ss_window_bounds(const double* x, int n, const double* xs, int ns, d
 void launch_ss_window(const double* x, int n, const double* xs, int ns, int first, int count, int* src, hipStream_t st) {
   const long long W = (long long)ns + count;
   hipLaunchKernelGGL(ss_window_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, x, n, xs, ns, first, count, src);
-}
-
-void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st) {
-  if (model == SS_MODEL_SHO) post_path_D<2, true>(a, nb, st);
-  else if (model == 1) post_path_D<1, false>(a, nb, st);
-  else if (model == 2) post_path_D<2, false>(a, nb, st);
-  else post_path_D<3, false>(a, nb, st);
-}
-
-void launch_ss_finite(const double* xs, int ns, int* flag, hipStream_t st) {
-  const int blocks = (int)std::min<long long>(2048, ((long long)ns + 255) / 256);
-  hipLaunchKernelGGL(ss_finite_kernel, dim3(blocks), dim3(256), 0, st, xs, ns, flag);
 }
 
 void launch_ss_gather_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st) {

@@ -61,6 +61,46 @@ SS_HD bool operator>=(SSDual a, SSDual b) { return a.v >= b.v; }
 SS_HD bool operator==(SSDual a, SSDual b) { return a.v == b.v; }
 SS_HD bool operator!=(SSDual a, SSDual b) { return a.v != b.v; }
 
+// ---- index arithmetic shared by the kernels of lmm_kernels_ss.hip ------------------------------------------------------------------
+// [t0, t1): the run of thread j over n items, `chunk` per thread
+struct SSRange { long long t0, t1; };
+SS_HD SSRange ss_chunk_range(long long j, int chunk, int n) {
+  const long long t0 = j * chunk;
+  return SSRange{t0, t0 + chunk < n ? t0 + chunk : n};
+}
+
+// lo + #{t in [lo, hi) : x_t <= s} (ss_count_lt: x_t < s) for non-decreasing x, by binary search: at most ceil(log2(hi - lo + 1)) probes
+SS_HD int ss_count_le(const double* x, int lo, int hi, double s) {
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (x[mid] <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+SS_HD int ss_count_lt(const double* x, int lo, int hi, double s) {
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (x[mid] < s) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// packed index of the symmetric entry (i, j), i <= j, behind the D mean components of a stored state
+__host__ __device__ constexpr int ss_sym_at(int D, int i, int j) { return D + i * D - i * (i - 1) / 2 + (j - i); }
+
+// The stored state of point t (mean, then the packed upper triangle of the covariance) into m, P: component c lies at
+// st[c comp_stride + t point_stride] ((n, 1): component-major; (1, D + D (D + 1) / 2): point-major)
+template <int D>
+SS_HD void ss_load_state(const double* st, size_t comp_stride, size_t point_stride, long long t, double m[D], double P[D][D]) {
+  const double* f = st + (size_t)t * point_stride;
+  for (int i = 0; i < D; ++i) {
+    m[i] = f[(size_t)i * comp_stride];
+    for (int k = i; k < D; ++k) P[i][k] = P[k][i] = f[(size_t)ss_sym_at(D, i, k) * comp_stride];
+  }
+}
+
 template <int D, typename Sc = double>
 struct SSModel {
   Sc lam;

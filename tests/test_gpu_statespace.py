@@ -239,6 +239,49 @@ def test_latents_of_one_kind_share_a_launch_and_shards_sum_to_the_whole(lmm, tol
     close(ms, gm, tol); close(vs, gv, tol)
 
 
+def test_launch_grouping_is_invisible_in_the_bits(lmm):
+    """33 Matern32 latents, then 2 SHO: more entries of one model than a launch takes (LMM_MAX_BATCH = 32), and a model change between
+    two kinds that share D = 2 but not a launch.  A launch is independent per latent, so however the entries are grouped the whole
+    logpdf is bitwise the left-to-right sum of the 35 one-latent shards, and 12 posterior samples of the 3-latent shard [31, 34)
+    (36 (latent, sample) entries across the model change) are bitwise the 12 one-sample calls on their slices of z, xi and eps."""
+    from lmm_amd import _lib as L
+    n, m = 63, 35
+    p, N, l0, l1 = m, 12, 31, 34
+    rng = np.random.default_rng(35)
+    gps = [{"kind": "matern32", "variance": rng.uniform(0.5, 2.0), "lengthscale": rng.uniform(0.4, 1.6), "mean": rng.normal()} for _ in range(33)]
+    gps += [{"kind": "sho", "variance": 1.1, "lengthscale": 1.7, "mean": 0.3, "quality": 2.0},
+            {"kind": "sho", "variance": 0.8, "lengthscale": 0.9, "mean": -0.1, "quality": 0.7}]
+    x = np.sort(rng.uniform(0.0, 8.0, n))
+    U, S = np.linalg.qr(rng.standard_normal((p, m)))[0], rng.uniform(0.5, 2.0, m)
+    y = rng.standard_normal(p * n)
+    lib, arr, Ua, Sa = lmm.load(), L.gps_array(gps), L.Arr(L.colmajor(U)), L.Arr(S)
+
+    def logpdf(a, b):
+        out = C.c_double()
+        L.check(lib.lmm_oilmm_logpdf_statespace(L.Arr(x).ptr, n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, S2, arr, a, b, 0, C.byref(out)))
+        return out.value
+
+    whole, val = logpdf(0, m), 0.0
+    for l in range(m):
+        val += logpdf(l, l + 1)
+    assert np.isfinite(whole) and val == whole, (val, whole)
+
+    zl = 2 * n * m                                                                       # every latent has D = 2
+    z, xi, eps = rng.standard_normal((N, zl)), rng.standard_normal((N, m * n)), rng.standard_normal((N, n * p))
+
+    def rand(q0, nq):
+        o = np.full((nq, n * p), np.nan)
+        L.check(lib.lmm_oilmm_rand_statespace(L.Arr(x).ptr, n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, S2, arr, l0, l1, 1, nq,
+                                              L.Arr(np.ascontiguousarray(z[q0:q0 + nq])).ptr, L.Arr(np.ascontiguousarray(xi[q0:q0 + nq])).ptr,
+                                              L.Arr(np.ascontiguousarray(eps[q0:q0 + nq])).ptr, L.Arr(o, True).ptr))
+        return o
+
+    together = rand(0, N)
+    assert np.isfinite(together).all()
+    for q in range(N):
+        assert np.array_equal(rand(q, 1)[0], together[q]), q
+
+
 def nan_problem(n, p=7):
     """The patterns of tests/test_gpu_missing.py: its well-conditioned U and, per point, up to (p - m) // 2 deleted outputs."""
     import test_gpu_missing as GM

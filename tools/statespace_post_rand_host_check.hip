@@ -129,8 +129,26 @@ template <int D> int check_matern(const char* name) {
   return bad;
 }
 
+// ss_count_le / ss_count_lt (the kernels' binary searches) against std::upper_bound / std::lower_bound on sorted arrays with ties,
+// n = 0, 1, 2, 7, queries on, between and outside the values, over the whole array and over every sub-range [lo, hi)
+int check_counts() {
+  int bad = 0;
+  const std::vector<double> all = {-1.0, 0.5, 0.5, 0.5, 2.0, 3.0, 3.0};
+  for (int n : {0, 1, 2, 7}) {
+    const std::vector<double> x(all.begin(), all.begin() + n);
+    for (double s : {-2.0, -1.0, 0.0, 0.5, 1.0, 2.0, 3.0, 4.0})
+      for (int lo = 0; lo <= n; ++lo)
+        for (int hi = lo; hi <= n; ++hi) {
+          if (ss_count_le(x.data(), lo, hi, s) != (int)(std::upper_bound(x.begin() + lo, x.begin() + hi, s) - x.begin())) ++bad;
+          if (ss_count_lt(x.data(), lo, hi, s) != (int)(std::lower_bound(x.begin() + lo, x.begin() + hi, s) - x.begin())) ++bad;
+        }
+  }
+  std::printf("ss_count_le / ss_count_lt %s\n", bad ? "BAD" : "ok");
+  return bad;
+}
+
 int main() {
-  int bad = check_matern<1>("matern12") + check_matern<2>("matern32") + check_matern<3>("matern52");
+  int bad = check_matern<1>("matern12") + check_matern<2>("matern32") + check_matern<3>("matern52") + check_counts();
   for (double Q : {0.51, 2.0, 50.0}) {
     SSOsc<double> M; ss_osc_model<double>(1.3, 1.0 / 0.7, Q, M);
     char name[32]; std::snprintf(name, sizeof name, "sho Q=%g", Q);
