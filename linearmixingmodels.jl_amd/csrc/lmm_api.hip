@@ -406,6 +406,17 @@ struct Latent {
   }
 };
 
+// The sum mode of the latents [l0, l1), which names the instantiation of the dense-H and inducing-point kernels that serves them
+// (mode_dispatch): 2 with a (locally) periodic latent or term, 1 with a sum latent, else 0.
+static int sum_mode(const Latent* lts, int l0, int l1) {
+  int mode = 0;
+  for (int l = l0; l < l1; ++l) {
+    if (lts[l].has_periodic()) return 2;
+    if (lts[l].is_sum()) mode = 1;
+  }
+  return mode;
+}
+
 struct LatentSet {
   int d = 0;
   std::vector<Latent> lat;
@@ -413,14 +424,7 @@ struct LatentSet {
   Buf<double> dev;                          // the same on the device
   std::vector<LatentDev> thost;             // the evaluation descriptors of every sum term (host, then `tdev`)
   Buf<LatentDev> tdev;
-  int any_sum() const {                     // the dense kernels' instantiation: 2 with a (locally) periodic latent or term, 1 with a sum latent
-    int r = 0;
-    for (const Latent& L : lat) {
-      if (L.has_periodic()) return 2;
-      if (L.is_sum()) r = 1;
-    }
-    return r;
-  }
+  int any_sum() const { return sum_mode(lat.data(), 0, (int)lat.size()); }      // the dense kernels' instantiation
   // d of the per-dimension gradient reduction (0: every term takes the isotropic one)
   int ard_grad_d() const {
     for (const Latent& L : lat)
@@ -624,6 +628,59 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
   std::shared_ptr<LatentSet> ls;                            \
   if (int rc_ = resolve(gps, m, d, ls)) return rc_;         \
   const Latent* lts = ls->lat.data()
+inline int shard_check(int l0, int l1, int m) {
+  return (l0 < 0 || l1 > m || l0 > l1) ? fail(LMM_ERR_ARG, "bad latent shard") : (int)LMM_OK;
+}
+inline std::vector<double> latent_means(const Latent* lts, int m) {
+  std::vector<double> means(m);
+  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  return means;
+}
+
+// The preamble of the per-latent entry points that take training data (x, y, [U, S, sigma2,] gps, shard), in three pieces in the order
+// the error codes are pinned in; train() is all three, and an entry point with checks of its own between two pieces calls the pieces.
+//   train_args     `bad` (the entry point's own NULL / size test), m > p, then with TRAIN_SIGMA2 / TRAIN_S the noise and S checks, the shard
+//   train_resolve  the latents resolved, the shard's bounds and the host means
+//   Train::upload  x and y on the device
+// An entry point that checks sigma2 elsewhere in its order (after its latents are resolved) does so itself, after train().
+enum { TRAIN_SIGMA2 = 1, TRAIN_S = 2 };
+struct Shard {
+  std::shared_ptr<LatentSet> ls;
+  const Latent* lts = nullptr;         // all m latents
+  int l0 = 0, l1 = 0, ms = 0, mk = 1;  // the shard, its latents, max(ms, 1)
+  void set(int l0_, int l1_) { lts = ls->lat.data(); l0 = l0_; l1 = l1_; ms = l1 - l0; mk = std::max(ms, 1); }
+};
+struct Train : Shard {
+  std::vector<double> means;           // of all m latents
+  DevIn xd{nullptr, 0, nullptr}, yd{nullptr, 0, nullptr};
+  void upload(const double* x, size_t nx, const double* y, size_t ny) {
+    xd = DevIn(x, nx, g.streams[0]); yd = DevIn(y, ny, g.streams[0]);
+  }
+};
+int train_args(bool bad, int p, int m, const double* S, double sigma2, int l0, int l1, int checks) {
+  if (bad) return fail(LMM_ERR_ARG, "bad arguments");
+  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
+  if ((checks & TRAIN_SIGMA2) && !(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
+  if (checks & TRAIN_S)
+    for (int l = 0; l < m; ++l)
+      if (!(S[l] > 0.0) || !std::isfinite(S[l])) return fail(LMM_ERR_ARG, "S must be finite and > 0 (S[%d] = %g)", l, S[l]);
+  return shard_check(l0, l1, m);
+}
+int train_resolve(const lmm_gp_t* gps, int m, int d, int l0, int l1, Train& T) {
+  if (int rc = resolve(gps, m, d, T.ls)) return rc;
+  T.set(l0, l1);
+  T.means = latent_means(T.lts, m);
+  return LMM_OK;
+}
+// x: d x n; y: ny values (n p, or n p ncol).  p = m and S = nullptr for an IndependentMOGP.
+int train(bool bad, const double* x, int d, int n, const double* y, size_t ny, int p, const double* S, int m, double sigma2,
+          const lmm_gp_t* gps, int l0, int l1, int checks, Train& T) {
+  if (int rc = train_args(bad, p, m, S, sigma2, l0, l1, checks)) return rc;
+  if (int rc = train_resolve(gps, m, d, l0, l1, T)) return rc;
+  T.upload(x, (size_t)d * n, y, ny);
+  return LMM_OK;
+}
+
 // An entry point that does not serve SHO latents names the first one (what: the entry point's service, for the message).
 int refuse_sho(const LatentSet& S, const char* what) {
   for (size_t l = 0; l < S.lat.size(); ++l)
@@ -1231,6 +1288,54 @@ void residual_on_device(const double* Y, int n, int p, const double* Ty_all, int
   residual_on_device(Y, n, p, Ty_all, m, Hd.p, partial, out1, st);
 }
 
+// The regulariser of reference src/oilmm.jl:101-113 for n points with noise s2 and resid = |(I - U U') Y|_F^2
+double oilmm_regulariser(double n, int p, int m, const double* S, double s2, double resid) {
+  double logdetS = 0.0;
+  for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
+  return -(n * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * s2)) + resid / s2) / 2.0;
+}
+
+// The projection front end of complete data (reference src/oilmm.jl:20-30): T, the projected noise ST and H on the host (the
+// constructor); T and the latent means on the device (upload); then, on streams[0], the shard's residual rows (delta) or the plain
+// rows of T y with the regulariser's residual (rows).
+struct OilmmFront {
+  int p, m;
+  std::vector<double> T, ST, H;
+  Uploaded Td, meansd, Hd;
+  Buf<double> Ty, resid_dev, partial;
+  OilmmFront(int p_, int m_) : p(p_), m(m_) {}
+  OilmmFront(const double* U, const double* S, int p_, int m_, double s2) : p(p_), m(m_) { project_orthogonal(U, S, p, m, s2, T, ST, H); }
+  static OilmmFront identity(int m) {      // an IndependentMOGP: T = I over its m outputs (no ST, no H)
+    OilmmFront F(m, m);
+    F.T.assign((size_t)m * m, 0.0);
+    for (int l = 0; l < m; ++l) F.T[l + (size_t)l * m] = 1.0;
+    return F;
+  }
+  void upload(const std::vector<double>& means) { Td = Uploaded(T, g.streams[0]); meansd = Uploaded(means, g.streams[0]); }
+  // delta_l = (T y)_l - mean_l for the ms latents from l0 on, [latent][n]
+  Buf<double> delta(const double* yd, int n, int l0, int ms) const {
+    Buf<double> out((size_t)n * std::max(ms, 1));
+    if (ms > 0) project_on_device(yd, n, p, Td.buf, m, l0, ms, meansd.buf.p + l0, out.p, g.streams[0]);
+    return out;
+  }
+  // (T y)_l of the shard without the means (returned, [latent][n]); with_regulariser: of every latent, and |Y - H T Y|_F^2 copied to
+  // *resid, which holds it once streams[0] has been synchronised
+  const double* rows(const double* yd, int n, int l0, int ms, bool with_regulariser, double* resid) {
+    hipStream_t st0 = g.streams[0];
+    const int c0 = with_regulariser ? 0 : l0, C = with_regulariser ? m : ms;
+    Ty = Buf<double>((size_t)n * std::max(C, 1));
+    if (C > 0) project_on_device(yd, n, p, Td.buf, m, c0, C, nullptr, Ty.p, st0);
+    if (with_regulariser) {
+      Hd = Uploaded(H, st0);
+      partial = Buf<double>(tall_skinny_partials(n, p));
+      resid_dev = Buf<double>(1);
+      residual_on_device(yd, n, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p, st0);
+      HIPCHK(hipMemcpyAsync(resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
+    }
+    return Ty.p + (size_t)(l0 - c0) * n;
+  }
+};
+
 // The training matrix of one latent as a factor matrix A (D.NR x D.NC, D.ld): K(x, x) + noise on the diagonal -- the scalar `noise`, or
 // the per-point values noisevec (device, n of them) when given -- the identity on the padding, and nrider rider rows (rider, n apart)
 // less rider_sub.  info_zero: the matrix's pivot-info word, zeroed by the launch.
@@ -1357,6 +1462,36 @@ struct lmm_post {
 };
 // the handle that owns the device state of a dense-H posterior (itself, or the base of a latent view)
 static inline const lmm_post* dense_state(const lmm_post* P) { return P->base ? P->base : P; }
+
+// The preamble of the prediction entry points, which take a posterior handle or (post == NULL) the prior's latents and a shard.
+// post_dtype_check comes first in an entry point; post_shard follows the entry point's own argument test: the handle's kind (refused
+// with the entry point's own text `other_kind`; nullptr: the entry point has checked it), its m and d (m_fmt: the entry point's wording;
+// d_who: nullptr no check here, "" the short message, else the name of the input in the long one), and the shard and latents from the
+// handle, or else from the caller's shard and resolve.  The shard's bounds (shard_check) are the caller's next step.
+static int post_dtype_check(const lmm_post* post) {
+  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  return LMM_OK;
+}
+static int post_shard(const lmm_post* P, const char* other_kind, const lmm_gp_t* gps, int m, int d, int latent_begin, int latent_end,
+                      Shard& Q, const char* d_who = "", const char* m_fmt = "posterior has %d latents, H has %d") {
+  if (P) {
+    if (other_kind && P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "%s", other_kind);
+    Q.ls = P->ls;
+    if (P->m != m) return fail(LMM_ERR_DIM, m_fmt, P->m, m);
+    if (d_who && P->d != d)
+      return *d_who ? fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, %s has d=%d", P->d, d_who, d)
+                    : fail(LMM_ERR_DIM, "input dimension mismatch");
+  } else if (int rc = resolve(gps, m, d, Q.ls)) return rc;
+  Q.set(P ? P->l0 : latent_begin, P ? P->l1 : latent_end);
+  return LMM_OK;
+}
+// H = U sqrt(S) (S == nullptr: U itself, a dense H) of the ms latents from l0 on, p x max(ms, 1) column-major
+static std::vector<double> shard_H(const double* U, const double* S, int p, int l0, int ms) {
+  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
+  for (int k = 0; k < ms; ++k)
+    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * (S ? std::sqrt(S[l0 + k]) : 1.0);
+  return Hs;
+}
 
 #define LMM_TRY try {
 // A throw unwinds through Buf destructors, which hand device blocks back to the caching pool while slot streams may still be
@@ -1767,21 +1902,20 @@ int lmm_oilmm_logpdf(const double* x, int d, int n, const double* y, int p, cons
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
+  // (this entry point is tuned to the microsecond at C0 size: it takes the preamble's pieces around its own staging, in its own order)
+  Train R;
+  if (int rc = train_args(!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0, p, m, S, sigma2, latent_begin, latent_end, 0)) return rc;
+  if (int rc = train_resolve(gps, m, d, latent_begin, latent_end, R)) return rc;
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
-  std::vector<double> T, ST, H;
+  OilmmFront F(p, m);
+  std::vector<double>&T = F.T, &ST = F.ST, &H = F.H;      // (T and H stay empty when the arena holds them)
   // [T | H] straight into the pinned arena when the regulariser path (which uploads both as one block) has room there
   double* packp = with_regulariser ? static_cast<double*>(pin_take(2 * (size_t)m * p * sizeof(double))) : nullptr;
   if (packp) { ST.resize(m); project_orthogonal_into(U, S, p, m, sigma2, packp, ST.data(), packp + (size_t)m * p); }
   else project_orthogonal(U, S, p, m, sigma2, T, ST, H);
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
+  R.upload(x, (size_t)d * n, y, (size_t)n * p);
+  const int l0 = R.l0, l1 = R.l1, ms = R.ms;
   double resid_pageable = 0.0;
   double* resid = static_cast<double*>(pin_take(sizeof(double)));      // pinned: the read-back below does not stall the host
   if (resid == nullptr) resid = &resid_pageable;
@@ -1798,26 +1932,20 @@ int lmm_oilmm_logpdf(const double* x, int d, int n, const double* y, int p, cons
     Buf<double> Ty((size_t)n * m), resid_dev(1), partial(tall_skinny_partials(n, p));
     double* resid_direct = (resid != &resid_pageable) ? pin_dev(resid) : nullptr;      // the reduction writes into host memory
     const std::function<void()> produce = [&]() {
-      project_on_device(yd.p, n, p, Tdev, m, 0, m, nullptr, Ty.p, st0);
+      project_on_device(R.yd.p, n, p, Tdev, m, 0, m, nullptr, Ty.p, st0);
       // reference src/oilmm.jl:112: sum(abs2, (I - U U') Y)  ==  |Y - H T Y|_F^2 since H T = U U'
-      residual_on_device(yd.p, n, p, Ty.p, m, Hdev, partial.p, resid_direct ? resid_direct : resid_dev.p, st0);
+      residual_on_device(R.yd.p, n, p, Ty.p, m, Hdev, partial.p, resid_direct ? resid_direct : resid_dev.p, st0);
       if (!resid_direct) HIPCHK(hipMemcpyAsync(resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));    // read after latent_lmls' sync
     };
-    if (int rc = latent_lmls(xd.p, d, n, lts, ST.data(), l0, l1, Ty.p + (size_t)l0 * n, lml, 1, nullptr, means.data(), &produce)) return rc;
+    if (int rc = latent_lmls(R.xd.p, d, n, R.lts, ST.data(), l0, l1, Ty.p + (size_t)l0 * n, lml, 1, nullptr, R.means.data(), &produce)) return rc;
   } else {
-    Uploaded Td(T, st0), meansd(means, st0);
-    Buf<double> delta((size_t)n * std::max(ms, 1));
-    if (ms > 0) project_on_device(yd.p, n, p, Td.buf, m, l0, ms, meansd.buf.p + l0, delta.p, st0);
-    if (int rc = latent_lmls(xd.p, d, n, lts, ST.data(), l0, l1, delta.p, lml)) return rc;
+    F.upload(R.means);
+    Buf<double> delta = F.delta(R.yd.p, n, l0, ms);
+    if (int rc = latent_lmls(R.xd.p, d, n, R.lts, ST.data(), l0, l1, delta.p, lml)) return rc;
   }
   double total = 0.0;
   for (int k = 0; k < ms; ++k) total += lml[k];
-  if (with_regulariser) {
-    // reference src/oilmm.jl:101-113
-    double logdetS = 0.0;
-    for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
-    total += -((double)n * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * sigma2)) + *resid / sigma2) / 2.0;
-  }
+  if (with_regulariser) total += oilmm_regulariser(n, p, m, S, sigma2, *resid);
   *out = total;
   return LMM_OK;
   LMM_CATCH
@@ -1882,8 +2010,6 @@ void oilmm_regulariser_grad(const double* U, const double* S, int p, int m, cons
     return Cc;
   };
   PtP = matmul(Pm, p, p, Pm, p);                               // P symmetric: P'P = P P
-  double logdetS = 0.0;
-  for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
   std::vector<double> Uv(U, U + (size_t)p * m);
   std::vector<double> PU = matmul(Pm, p, p, Uv, m);
   for (int blk = 0; blk < nblk; ++blk) {                        // reference src/oilmm.jl:101-113, once per noise block
@@ -1891,7 +2017,7 @@ void oilmm_regulariser_grad(const double* U, const double* S, int p, int m, cons
     const double s2 = NB.s2[blk], cnt = NB.count(blk);
     double Rn = 0.0;                                           // |P Y|_F^2 = tr(P'P Y Y')
     for (int a1 = 0; a1 < p; ++a1) for (int b1 = 0; b1 < p; ++b1) Rn += PtP[a1 + (size_t)b1 * p] * M2[b1 + (size_t)a1 * p];
-    total += -(cnt * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * s2)) + Rn / s2) / 2.0;
+    total += oilmm_regulariser(cnt, p, m, S, s2, Rn);
     for (int l = 0; l < m; ++l) G.gS[l] += -cnt / (2.0 * S[l]);
     G.gs2[blk] += -0.5 * (cnt * (double)(p - m) / s2 - Rn / (s2 * s2));
     std::vector<double> M2U = matmul(M2, p, p, Uv, m);
@@ -2039,10 +2165,8 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   std::vector<std::vector<double>> ST(nblk, std::vector<double>(m));      // projected noise s2[b] / S[l]
   for (int b = 0; b < nblk; ++b)
     for (int l = 0; l < m; ++l) ST[b][l] = NB.s2[b] / S[l];
-  Uploaded Td(T, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
-  Uploaded meansd(means, st0);
+  const std::vector<double> means = latent_means(lts, m);
+  Uploaded Td(T, st0), meansd(means, st0);
   // projections: Ty (all m, for dS), delta for the shard
   Buf<double> Ty((size_t)n * m), delta((size_t)n * mk);
   project_on_device(yd, n, p, Td.buf, m, 0, m, nullptr, Ty.p, st0);
@@ -2194,23 +2318,21 @@ int lmm_oilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int 
   LMM_TRY
   // fp32 compute mode (round 3): Float32 factor, triangular inverse and K^-1 = L^-T L^-1 (all on v_mfma_f32), Float64 reductions;
   // stated tolerance against the Float64 gradient: include/lmm_hip.h
-  if (!x || !y || !U || !S || !out_logpdf || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
+  Train R;
+  if (int rc = train(!x || !y || !U || !S || !out_logpdf || d <= 0 || n <= 0 || p <= 0 || m <= 0, x, d, n, y, (size_t)n * p, p, S, m, sigma2, gps,
+                     latent_begin, latent_end, 0, R)) return rc;
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   DevOut gy(grad_y, (size_t)n * p), gx(grad_x, (size_t)d * n);
-  if (int rc = ls->ard_grad_check()) return rc;
+  if (int rc = R.ls->ard_grad_check()) return rc;
   if (int rc = input_grad_check(d, grad_x != nullptr)) return rc;
-  if (grad_x) { if (int rc = refuse_sho(*ls, "gradients with respect to the inputs are")) return rc; }
+  if (grad_x) { if (int rc = refuse_sho(*R.ls, "gradients with respect to the inputs are")) return rc; }
   OilmmGrad G;
-  if (int rc = oilmm_grad_core(xd.p, d, n, one_noise_block(n, sigma2), yd.p, p, U, S, ls.get(), latent_begin, latent_end, with_regulariser,
+  if (int rc = oilmm_grad_core(R.xd.p, d, n, one_noise_block(n, sigma2), R.yd.p, p, U, S, R.ls.get(), latent_begin, latent_end, with_regulariser,
                                G, gy.p, gx.p))
     return rc;
   write_oilmm_grad(G, m, p, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
-  publish_grads(*ls, grad_gps ? &G.trec : nullptr, latent_begin, latent_end);
+  publish_grads(*R.ls, grad_gps ? &G.trec : nullptr, latent_begin, latent_end);
   if (grad_y) gy.finish(st0);
   if (grad_x) gx.finish(st0);
   if (grad_y || grad_x) HIPCHK(hipStreamSynchronize(st0));
@@ -2245,33 +2367,31 @@ int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* b
   REQUIRE_INIT();
   LMM_TRY
   // (the same core with one noise block per conditioning batch + one for the test points: served in the fp32 compute mode too)
-  if (!x || !y || !xs || !ys || !U || !S || !out_logpdf || d <= 0 || n <= 0 || ns <= 0 || p <= 0 || m <= 0)
-    return fail(LMM_ERR_ARG, "bad arguments");
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
+  Train R;
+  if (int rc = train(!x || !y || !xs || !ys || !U || !S || !out_logpdf || d <= 0 || n <= 0 || ns <= 0 || p <= 0 || m <= 0, x, d, n, y, (size_t)n * p, p,
+                     S, m, sigma2_s, gps, latent_begin, latent_end, 0, R)) return rc;
   if (int rc = check_batches(batch_n, batch_sigma2, nbatch, n)) return rc;
   if (!(sigma2_s > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
   const int N = n + ns;
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0), xsd(xs, (size_t)d * ns, st0), ysd(ys, (size_t)ns * p, st0);
+  DevIn xsd(xs, (size_t)d * ns, st0), ysd(ys, (size_t)ns * p, st0);
   Buf<double> xj((size_t)d * N), yj((size_t)N * p), gj((size_t)N * p), gm((size_t)n * p);
-  HIPCHK(hipMemcpyAsync(xj.p, xd.p, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, st0));
+  HIPCHK(hipMemcpyAsync(xj.p, R.xd.p, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpyAsync(xj.p + (size_t)d * n, xsd.p, (size_t)d * ns * sizeof(double), hipMemcpyDeviceToDevice, st0));
-  HIPCHK(hipMemcpy2DAsync(yj.p, (size_t)N * sizeof(double), yd.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
+  HIPCHK(hipMemcpy2DAsync(yj.p, (size_t)N * sizeof(double), R.yd.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpy2DAsync(yj.p + n, (size_t)N * sizeof(double), ysd.p, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
-  if (int rc = ls->ard_grad_check()) return rc;
+  if (int rc = R.ls->ard_grad_check()) return rc;
   const bool want_gx = grad_x != nullptr || grad_xs != nullptr;
   if (int rc = input_grad_check(d, want_gx)) return rc;
-  if (want_gx) { if (int rc = refuse_sho(*ls, "gradients with respect to the inputs are")) return rc; }
+  if (want_gx) { if (int rc = refuse_sho(*R.ls, "gradients with respect to the inputs are")) return rc; }
   const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
   Buf<double> gxj, gxm;
   if (want_gx) gxj = Buf<double>((size_t)d * N);
   if (grad_x) gxm = Buf<double>((size_t)d * n);
   OilmmGrad GJ, GM;
-  if (int rc = oilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, U, S, ls.get(),
+  if (int rc = oilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, U, S, R.ls.get(),
                                latent_begin, latent_end, with_regulariser, GJ, want_gy ? gj.p : nullptr, gxj.p)) return rc;
-  if (int rc = oilmm_grad_core(xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd.p, p, U, S, ls.get(),
+  if (int rc = oilmm_grad_core(R.xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), R.yd.p, p, U, S, R.ls.get(),
                                latent_begin, latent_end, with_regulariser, GM, grad_y ? gm.p : nullptr, gxm.p)) return rc;
   if (int rc = finish_input_grads(gxj.p, gxm.p, d, n, ns, grad_x, grad_xs)) return rc;
   *out_logpdf = GJ.value - GM.value;
@@ -2287,7 +2407,7 @@ int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* b
   }
   if (grad_U) for (size_t q = 0; q < (size_t)p * m; ++q) grad_U[q] = GJ.gU[q] - GM.gU[q];
   for (size_t q = 0; q < GJ.trec.size(); ++q) GJ.trec[q] -= GM.trec[q];
-  publish_grads(*ls, grad_gps ? &GJ.trec : nullptr, latent_begin, latent_end);
+  publish_grads(*R.ls, grad_gps ? &GJ.trec : nullptr, latent_begin, latent_end);
   if (grad_y) {
     DevOut gy(grad_y, (size_t)n * p);
     Buf<double> top((size_t)n * p);
@@ -2335,40 +2455,33 @@ int lmm_oilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !Y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0 || ncol <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
+  Train R;
+  if (int rc = train(!x || !Y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0 || ncol <= 0, x, d, n, Y, (size_t)n * p * ncol, p, S, m, sigma2,
+                     gps, latent_begin, latent_end, 0, R)) return rc;
   hipStream_t st0 = g.streams[0];
-  std::vector<double> T, ST, H;
-  project_orthogonal(U, S, p, m, sigma2, T, ST, H);
-  DevIn xd(x, (size_t)d * n, st0), yd(Y, (size_t)n * p * ncol, st0);
-  Uploaded Td(T, st0), Hd(H, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
-  Uploaded meansd(means, st0);
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
-  Buf<double> delta((size_t)n * std::max(ms, 1) * ncol), Ty((size_t)n * m), partial(tall_skinny_partials(n, p)), resid_dev(ncol);
+  OilmmFront F(U, S, p, m, sigma2);
+  F.upload(R.means);
+  Uploaded Hd(F.H, st0);
+  const int l0 = R.l0, l1 = R.l1, ms = R.ms;
+  Buf<double> delta((size_t)n * R.mk * ncol), Ty((size_t)n * m), partial(tall_skinny_partials(n, p)), resid_dev(ncol);
   std::vector<double> resid(ncol, 0.0);
   for (int c = 0; c < ncol; ++c) {
-    const double* yc = yd.p + (size_t)c * n * p;
+    const double* yc = R.yd.p + (size_t)c * n * p;
     // rider [latent k][column c]: delta + (k ncol + c) n  ==  output column stride ncol*n
-    if (ms > 0) launch_tall_skinny(yc, n, n, p, Td.buf.p + l0, m, ms, delta.p + (size_t)c * n, ncol * n, meansd.buf.p + l0, nullptr, 0,
+    if (ms > 0) launch_tall_skinny(yc, n, n, p, F.Td.buf.p + l0, m, ms, delta.p + (size_t)c * n, ncol * n, F.meansd.buf.p + l0, nullptr, 0,
                                    nullptr, 0, st0);
     if (with_regulariser) {
-      project_on_device(yc, n, p, Td.buf, m, 0, m, nullptr, Ty.p, st0);
+      project_on_device(yc, n, p, F.Td.buf, m, 0, m, nullptr, Ty.p, st0);
       residual_on_device(yc, n, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p + c, st0);
     }
   }
   if (with_regulariser) HIPCHK(hipMemcpyAsync(resid.data(), resid_dev.p, ncol * sizeof(double), hipMemcpyDeviceToHost, st0));
   std::vector<double> lml;
-  if (int rc = latent_lmls(xd.p, d, n, lts, ST.data(), l0, l1, delta.p, lml, ncol)) return rc;
-  double logdetS = 0.0;
-  for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
+  if (int rc = latent_lmls(R.xd.p, d, n, R.lts, F.ST.data(), l0, l1, delta.p, lml, ncol)) return rc;
   for (int c = 0; c < ncol; ++c) {
     double total = 0.0;
     for (int k = 0; k < ms; ++k) total += lml[(size_t)k * ncol + c];
-    if (with_regulariser) total += -((double)n * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * sigma2)) + resid[c] / sigma2) / 2.0;
+    if (with_regulariser) total += oilmm_regulariser(n, p, m, S, sigma2, resid[c]);
     out[c] = total;
   }
   return LMM_OK;
@@ -2397,22 +2510,18 @@ int lmm_mogp_logpdf(const double* x, int d, int n, const double* y, int m, doubl
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !y || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
-  hipStream_t st0 = g.streams[0];
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0);
+  Train R;
+  if (int rc = train(!x || !y || !out || d <= 0 || n <= 0 || m <= 0, x, d, n, y, (size_t)n * m, m, nullptr, m, sigma2, gps, latent_begin, latent_end, 0, R))
+    return rc;
   // delta_l = y_l - mean_l  via the projection kernel with T = I restricted to the shard
-  std::vector<double> T((size_t)m * m, 0.0), means(m), noise(m, sigma2);
-  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = lts[l].mean; }
-  Uploaded Td(T, st0), meansd(means, st0);
-  Buf<double> delta((size_t)n * std::max(ms, 1));
-  if (ms > 0) project_on_device(yd.p, n, m, Td.buf, m, l0, ms, meansd.buf.p + l0, delta.p, st0);
+  OilmmFront F = OilmmFront::identity(m);
+  F.upload(R.means);
+  Buf<double> delta = F.delta(R.yd.p, n, R.l0, R.ms);
+  const std::vector<double> noise(m, sigma2);
   std::vector<double> lml;
-  if (int rc = latent_lmls(xd.p, d, n, lts, noise.data(), l0, l1, delta.p, lml)) return rc;
+  if (int rc = latent_lmls(R.xd.p, d, n, R.lts, noise.data(), R.l0, R.l1, delta.p, lml)) return rc;
   double total = 0.0;
-  for (int k = 0; k < ms; ++k) total += lml[k];
+  for (int k = 0; k < R.ms; ++k) total += lml[k];
   *out = total;
   return LMM_OK;
   LMM_CATCH
@@ -2423,21 +2532,18 @@ int lmm_mogp_logpdf_diag(const double* x, int d, int n, const double* y, int m, 
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !y || !noise_diag || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
-  hipStream_t st0 = g.streams[0];
-  const int l0 = latent_begin, l1 = latent_end, ms = l1 - l0;
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0), nd(noise_diag, (size_t)n * m, st0);
-  std::vector<double> T((size_t)m * m, 0.0), means(m), noise(m, 0.0);
-  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = lts[l].mean; }
-  Uploaded Td(T, st0), meansd(means, st0);
-  Buf<double> delta((size_t)n * std::max(ms, 1));
-  if (ms > 0) project_on_device(yd.p, n, m, Td.buf, m, l0, ms, meansd.buf.p + l0, delta.p, st0);
+  Train R;
+  if (int rc = train(!x || !y || !noise_diag || !out || d <= 0 || n <= 0 || m <= 0, x, d, n, y, (size_t)n * m, m, nullptr, m, 0.0, gps, latent_begin,
+                     latent_end, 0, R)) return rc;
+  DevIn nd(noise_diag, (size_t)n * m, g.streams[0]);
+  OilmmFront F = OilmmFront::identity(m);
+  F.upload(R.means);
+  Buf<double> delta = F.delta(R.yd.p, n, R.l0, R.ms);
+  const std::vector<double> noise(m, 0.0);
   std::vector<double> lml;
-  if (int rc = latent_lmls(xd.p, d, n, lts, noise.data(), l0, l1, delta.p, lml, 1, nd.p + (size_t)l0 * n)) return rc;
+  if (int rc = latent_lmls(R.xd.p, d, n, R.lts, noise.data(), R.l0, R.l1, delta.p, lml, 1, nd.p + (size_t)R.l0 * n)) return rc;
   double total = 0.0;
-  for (int k = 0; k < ms; ++k) total += lml[k];
+  for (int k = 0; k < R.ms; ++k) total += lml[k];
   *out = total;
   return LMM_OK;
   LMM_CATCH
@@ -2458,9 +2564,9 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   if (int rc = project_dense(H, p, m, sigma2, jit->project_jitter, T, ST, &logdetST)) return rc;
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   Uploaded Td(T, st0), STd(ST, st0);
-  std::vector<double> Hv(H, H + (size_t)p * m), means(m);
+  const std::vector<double> Hv(H, H + (size_t)p * m), means = latent_means(lts, m);
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) { means[l] = lts[l].mean; lat[l] = lts[l].dense_dev(); }
+  for (int l = 0; l < m; ++l) lat[l] = lts[l].dense_dev();
   Uploaded Hd(Hv, st0), meansd(means, st0);
   Buf<LatentDev> latd(m);
   HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
@@ -2553,9 +2659,9 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   if (int rc = project_dense(H, p, m, sigma2, jit->project_jitter, T, ST, &logdetST)) return rc;
   DevIn xd(x, (size_t)d * n, st0), yd(Y, (size_t)n * p * ncol, st0);
   Uploaded Td(T, st0), STd(ST, st0);
-  std::vector<double> Hv(H, H + (size_t)p * m), means(m);
+  const std::vector<double> Hv(H, H + (size_t)p * m), means = latent_means(lts, m);
   std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) { means[l] = lts[l].mean; lat[l] = lts[l].dense_dev(); }
+  for (int l = 0; l < m; ++l) lat[l] = lts[l].dense_dev();
   Uploaded Hd(Hv, st0), meansd(means, st0);
   Buf<LatentDev> latd(m);
   HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
@@ -2627,7 +2733,8 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   for (int b = 0; b < nblk; ++b)
     if (int rc = project_dense(Hq[b], p, m, s2[b], jit->project_jitter, T[b], ST[b], &logdetST[b])) return rc;
   // host copies in the layouts the kernels read: Tt = T' (p x m), Ht = H' (m x p); the blocks' T, T', H and H' back to back
-  std::vector<double> Hv, Ht, means(m), STall, Tall, Ttall;
+  std::vector<double> Hv, Ht, STall, Tall, Ttall;
+  const std::vector<double> means = latent_means(lts, m);
   for (int b = 0; b < nblk; ++b) {
     std::vector<double> Ttb((size_t)p * m), Htb((size_t)m * p);
     for (int l = 0; l < m; ++l) for (int o = 0; o < p; ++o) { Ttb[o + (size_t)l * p] = T[b][l + (size_t)o * m]; Htb[l + (size_t)o * m] = Hq[b][o + (size_t)l * p]; }
@@ -2637,7 +2744,6 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
     Hv.insert(Hv.end(), Hq[b], Hq[b] + (size_t)p * m);
     Ht.insert(Ht.end(), Htb.begin(), Htb.end());
   }
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   std::vector<LatentDev> lat(m);
   for (int l = 0; l < m; ++l) lat[l] = lts[l].dense_dev();
   std::vector<int> sidx(n);
@@ -3094,22 +3200,13 @@ int lmm_oilmm_posterior_create(const double* x, int d, int n, const double* y, i
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
-  hipStream_t st0 = g.streams[0];
-  std::vector<double> T, ST, H;
-  project_orthogonal(U, S, p, m, sigma2, T, ST, H);
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
-  Uploaded Td(T, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
-  Uploaded meansd(means, st0);
-  const int ms = latent_end - latent_begin;
-  Buf<double> delta((size_t)n * std::max(ms, 1));
-  if (ms > 0) project_on_device(yd.p, n, p, Td.buf, m, latent_begin, ms, meansd.buf.p + latent_begin, delta.p, st0);
-  return posterior_create_common(xd.p, d, n, ls, ST.data(), latent_begin, latent_end, delta.p, out);
+  Train R;
+  if (int rc = train(!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0, x, d, n, y, (size_t)n * p, p, S, m, sigma2, gps, latent_begin,
+                     latent_end, 0, R)) return rc;
+  OilmmFront F(U, S, p, m, sigma2);
+  F.upload(R.means);
+  Buf<double> delta = F.delta(R.yd.p, n, R.l0, R.ms);
+  return posterior_create_common(R.xd.p, d, n, R.ls, F.ST.data(), latent_begin, latent_end, delta.p, out);
   LMM_CATCH
 }
 
@@ -3123,26 +3220,23 @@ int lmm_post_condition(const lmm_post_t* post, const double* U, const double* S,
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!post || !U || !S || !x2 || !y2 || !out || d <= 0 || n2 <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
-  if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "sequential conditioning of the dense-H posterior is not built");
-  if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", P->m, m);
-  if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
+  Shard Q;
+  if (int rc = post_shard(P, "sequential conditioning of the dense-H posterior is not built", nullptr, m, d, 0, 0, Q)) return rc;
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   hipStream_t st0 = g.streams[0];
-  const int l0 = P->l0, l1 = P->l1, ms = l1 - l0, n1 = P->n, n = n1 + n2;
-  std::vector<double> T, ST, H;
-  project_orthogonal(U, S, p, m, sigma2, T, ST, H);
+  const int l0 = Q.l0, l1 = Q.l1, ms = Q.ms, n1 = P->n, n = n1 + n2;
+  OilmmFront F(U, S, p, m, sigma2);
+  const std::vector<double>& ST = F.ST;
   DevIn x2d(x2, (size_t)d * n2, st0), y2d(y2, (size_t)n2 * p, st0);
-  Uploaded Td(T, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = P->ls->lat[l].mean;
-  Uploaded meansd(means, st0);
-  Buf<double> xall((size_t)d * n), delta((size_t)n * std::max(ms, 1)), nv((size_t)n * std::max(ms, 1)), d2buf((size_t)n2 * std::max(ms, 1));
+  const std::vector<double> means = latent_means(Q.lts, m);
+  F.upload(means);
+  Buf<double> xall((size_t)d * n), delta((size_t)n * Q.mk), nv((size_t)n * Q.mk);
   HIPCHK(hipMemcpyAsync(xall.p, P->x.p, (size_t)d * n1 * sizeof(double), hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpyAsync(xall.p + (size_t)d * n1, x2d.p, (size_t)d * n2 * sizeof(double), hipMemcpyDeviceToDevice, st0));
-  if (ms > 0) project_on_device(y2d.p, n2, p, Td.buf, m, l0, ms, meansd.buf.p + l0, d2buf.p, st0);
+  Buf<double> d2buf = F.delta(y2d.p, n2, l0, ms);
   for (int k = 0; k < ms; ++k) {
     HIPCHK(hipMemcpyAsync(delta.p + (size_t)k * n, P->delta_all.p + (size_t)k * n1, (size_t)n1 * sizeof(double), hipMemcpyDeviceToDevice, st0));
     HIPCHK(hipMemcpyAsync(delta.p + (size_t)k * n + n1, d2buf.p + (size_t)k * n2, (size_t)n2 * sizeof(double), hipMemcpyDeviceToDevice, st0));
@@ -3239,11 +3333,7 @@ static int missing_front(const double* yd, int n, int p, const double* U, const 
   F.pat_of = Buf<int>(n); F.pmask = Buf<unsigned long long>(pmask.size());
   HIPCHK(hipMemcpyAsync(F.pat_of.p, pat_of.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st0));
   HIPCHK(hipMemcpyAsync(F.pmask.p, pmask.data(), pmask.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st0));
-  std::vector<double> Hh((size_t)p * m);
-  for (int l = 0; l < m; ++l) {
-    const double rs = std::sqrt(S[l]);
-    for (int o = 0; o < p; ++o) Hh[o + (size_t)l * p] = U[o + (size_t)l * p] * rs;          // reference src/orthogonal_matrix.jl:27-30
-  }
+  const std::vector<double> Hh = shard_H(U, S, p, 0, m);          // reference src/orthogonal_matrix.jl:27-30
   F.Hd = Buf<double>(Hh.size());
   HIPCHK(hipMemcpyAsync(F.Hd.p, Hh.data(), Hh.size() * sizeof(double), hipMemcpyHostToDevice, st0));
   Buf<double> meansd(m);
@@ -3271,19 +3361,12 @@ static int missing_front(const double* yd, int n, int p, const double* U, const 
   return LMM_OK;
 }
 
-#define LMM_MISSING_ARGCHECK(extra)                                                                                              \
-  if (!y || !U || !S || (extra) || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");                        \
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");                                                          \
-  if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");                                                          \
-  for (int l_ = 0; l_ < m; ++l_)                                                                                                 \
-    if (!(S[l_] > 0.0) || !std::isfinite(S[l_])) return fail(LMM_ERR_ARG, "S must be finite and > 0 (S[%d] = %g)", l_, S[l_])
-
 int lmm_oilmm_project_missing(const double* y, int n, int p, const double* U, const double* S, int m, double sigma2,
                               const double* means, double* z_out, double* noise_out, double* reg_out, int* npatterns_out) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  LMM_MISSING_ARGCHECK(false);
+  if (int rc = train_args(!y || !U || !S || n <= 0 || p <= 0 || m <= 0, p, m, S, sigma2, 0, m, TRAIN_SIGMA2 | TRAIN_S)) return rc;
   hipStream_t st0 = g.streams[0];
   DevIn yd(y, (size_t)n * p, st0);
   MissingFront F;
@@ -3304,17 +3387,13 @@ int lmm_oilmm_logpdf_missing(const double* x, int d, int n, const double* y, int
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  LMM_MISSING_ARGCHECK(!x || !out || d <= 0);
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
-  hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  Train R;
+  if (int rc = train(!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0, x, d, n, y, (size_t)n * p, p, S, m, sigma2, gps, latent_begin,
+                     latent_end, TRAIN_SIGMA2 | TRAIN_S, R)) return rc;
   MissingFront F;
-  if (int rc = missing_front(yd.p, n, p, U, S, m, sigma2, means.data(), latent_begin, latent_end, false, F)) return rc;
+  if (int rc = missing_front(R.yd.p, n, p, U, S, m, sigma2, R.means.data(), latent_begin, latent_end, false, F)) return rc;
   std::vector<double> lml;
-  if (int rc = latent_lmls(xd.p, d, n, lts, nullptr, latent_begin, latent_end, F.z.p, lml, 1, F.nv.p)) return rc;
+  if (int rc = latent_lmls(R.xd.p, d, n, R.lts, nullptr, latent_begin, latent_end, F.z.p, lml, 1, F.nv.p)) return rc;
   double total = 0.0;
   for (double v : lml) total += v;
   if (with_regulariser) total += F.reg(n, m, sigma2);
@@ -3328,16 +3407,12 @@ int lmm_oilmm_posterior_create_missing(const double* x, int d, int n, const doub
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  LMM_MISSING_ARGCHECK(!x || !out || d <= 0);
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
-  hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  Train R;
+  if (int rc = train(!x || !y || !U || !S || !out || d <= 0 || n <= 0 || p <= 0 || m <= 0, x, d, n, y, (size_t)n * p, p, S, m, sigma2, gps, latent_begin,
+                     latent_end, TRAIN_SIGMA2 | TRAIN_S, R)) return rc;
   MissingFront F;
-  if (int rc = missing_front(yd.p, n, p, U, S, m, sigma2, means.data(), latent_begin, latent_end, false, F)) return rc;
-  return posterior_create_common(xd.p, d, n, ls, nullptr, latent_begin, latent_end, F.z.p, out, F.nv.p);
+  if (int rc = missing_front(R.yd.p, n, p, U, S, m, sigma2, R.means.data(), latent_begin, latent_end, false, F)) return rc;
+  return posterior_create_common(R.xd.p, d, n, R.ls, nullptr, latent_begin, latent_end, F.z.p, out, F.nv.p);
   LMM_CATCH
 }
 
@@ -3386,27 +3461,24 @@ int lmm_oilmm_logpdf_grad_missing(const double* x, int d, int n, const double* y
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  LMM_MISSING_ARGCHECK(!x || !out_logpdf || d <= 0);
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
-  if (int rc = ls->ard_grad_check()) return rc;
+  Train R;
+  if (int rc = train(!x || !y || !U || !S || !out_logpdf || d <= 0 || n <= 0 || p <= 0 || m <= 0, x, d, n, y, (size_t)n * p, p, S, m, sigma2, gps, latent_begin,
+                     latent_end, TRAIN_SIGMA2 | TRAIN_S, R)) return rc;
+  if (int rc = R.ls->ard_grad_check()) return rc;
   hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   DevOut gy(grad_y, (size_t)n * p);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
   MissingFront F;
-  if (int rc = missing_front(yd.p, n, p, U, S, m, sigma2, means.data(), latent_begin, latent_end, grad_y && with_regulariser, F)) return rc;
+  if (int rc = missing_front(R.yd.p, n, p, U, S, m, sigma2, R.means.data(), latent_begin, latent_end, grad_y && with_regulariser, F)) return rc;
   double value = 0.0, gs2 = 0.0;
   std::vector<lmm_gp_grad_t> ggps;
   std::vector<double> trec;
-  if (int rc = oilmm_grad_missing_core(xd.p, d, n, p, sigma2, ls.get(), latent_begin, latent_end, with_regulariser, F, &value, &gs2,
+  if (int rc = oilmm_grad_missing_core(R.xd.p, d, n, p, sigma2, R.ls.get(), latent_begin, latent_end, with_regulariser, F, &value, &gs2,
                                        ggps, trec, gy.p))
     return rc;
   *out_logpdf = value;
   if (grad_sigma2) *grad_sigma2 = gs2;
   if (grad_gps) std::copy(ggps.begin(), ggps.end(), grad_gps);
-  publish_grads(*ls, grad_gps ? &trec : nullptr, latent_begin, latent_end);
+  publish_grads(*R.ls, grad_gps ? &trec : nullptr, latent_begin, latent_end);
   if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
   return LMM_OK;
   LMM_CATCH
@@ -3417,18 +3489,14 @@ int lmm_mogp_posterior_create(const double* x, int d, int n, const double* y, in
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!x || !y || !out || d <= 0 || n <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (latent_begin < 0 || latent_end > m || latent_begin > latent_end) return fail(LMM_ERR_ARG, "bad latent shard");
-  RESOLVE(gps, m, d);
-  hipStream_t st0 = g.streams[0];
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * m, st0);
-  std::vector<double> T((size_t)m * m, 0.0), means(m), noise(m, sigma2);
-  for (int l = 0; l < m; ++l) { T[l + (size_t)l * m] = 1.0; means[l] = lts[l].mean; }
-  Uploaded Td(T, st0), meansd(means, st0);
-  const int ms = latent_end - latent_begin;
-  Buf<double> delta((size_t)n * std::max(ms, 1));
-  if (ms > 0) project_on_device(yd.p, n, m, Td.buf, m, latent_begin, ms, meansd.buf.p + latent_begin, delta.p, st0);
-  return posterior_create_common(xd.p, d, n, ls, noise.data(), latent_begin, latent_end, delta.p, out);
+  Train R;
+  if (int rc = train(!x || !y || !out || d <= 0 || n <= 0 || m <= 0, x, d, n, y, (size_t)n * m, m, nullptr, m, sigma2, gps, latent_begin, latent_end, 0, R))
+    return rc;
+  OilmmFront F = OilmmFront::identity(m);
+  F.upload(R.means);
+  Buf<double> delta = F.delta(R.yd.p, n, R.l0, R.ms);
+  const std::vector<double> noise(m, sigma2);
+  return posterior_create_common(R.xd.p, d, n, R.ls, noise.data(), latent_begin, latent_end, delta.p, out);
   LMM_CATCH
 }
 
@@ -3501,8 +3569,7 @@ int lmm_ilmm_posterior_create(const double* x, int d, int n, const double* y, in
   if (int rc = project_dense(H, p, m, sigma2, jit->project_jitter, T, ST, nullptr)) return rc;
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   Uploaded Td(T, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  const std::vector<double> means = latent_means(lts, m);
   Uploaded meansd(means, st0);
   Buf<double> delta((size_t)n * m);
   project_on_device(yd.p, n, p, Td.buf, m, 0, m, meansd.buf.p, delta.p, st0);
@@ -3518,7 +3585,7 @@ int lmm_ilmm_post_condition(const lmm_post_t* post, double sigma2, const double*
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!post || !x2 || !y2 || !out || d <= 0 || n2 <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
   if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
@@ -3531,8 +3598,7 @@ int lmm_ilmm_post_condition(const lmm_post_t* post, double sigma2, const double*
   if (int rc = project_dense(P->H.data(), p, m, sigma2, jit->project_jitter, T, ST, nullptr)) return rc;
   DevIn x2d(x2, (size_t)d * n2, st0), y2d(y2, (size_t)n2 * p, st0);
   Uploaded Td(T, st0);
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = P->ls->lat[l].mean;
+  const std::vector<double> means = latent_means(P->ls->lat.data(), m);
   Uploaded meansd(means, st0);
   Buf<double> d2((size_t)n2 * m), delta((size_t)n * m), xall((size_t)d * n);
   project_on_device(y2d.p, n2, p, Td.buf, m, 0, m, meansd.buf.p, d2.p, st0);
@@ -3558,7 +3624,7 @@ int lmm_ilmm_post_mean_and_var(const lmm_post_t* post, double sigma2, const doub
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!post || !xs || !mean_out || !var_out || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
   if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
@@ -3637,7 +3703,7 @@ int lmm_ilmm_post_mean_and_cov(const lmm_post_t* post, double sigma2, const doub
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!post || !xs || !mean_out || !cov_out || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
   if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
@@ -3672,7 +3738,7 @@ int lmm_ilmm_post_logpdf(const lmm_post_t* post, double sigma2, const double* xs
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!post || !xs || !ys || !out || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
   if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
@@ -3718,7 +3784,7 @@ int lmm_ilmm_post_rand(const lmm_post_t* post, double sigma2, int add_noise, con
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!post || !xs || !z_lat || !out || d <= 0 || ns <= 0 || (add_noise && !eps)) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
   if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
@@ -3879,7 +3945,7 @@ int lmm_latent_marginals(const lmm_post_t* post, const lmm_gp_t* gps, int m_shar
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!xs || !mean_lat || !var_lat || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (post && post->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "per-latent marginals of the dense-H posterior (coupled latents): use lmm_ilmm_post_mean_and_var");
   const int ms = post ? (post->l1 - post->l0) : m_shard;
@@ -3901,22 +3967,16 @@ int lmm_oilmm_mean_and_var(const lmm_post_t* post, const lmm_gp_t* gps, const do
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!U || !xs || !mean_out || d <= 0 || ns <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (post && post->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "dense-H posterior handle: use lmm_ilmm_post_mean_and_var");
   if (!jit) jit = &kDefaultJit;
-  int l0 = latent_begin, l1 = latent_end;
-  std::shared_ptr<LatentSet> ls;
-  if (post) { l0 = post->l0; l1 = post->l1; ls = post->ls; if (post->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", post->m, m); }
-  else if (int rc = resolve(gps, m, d, ls)) return rc;
-  const Latent* lts = ls->lat.data();
-  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
-  const int ms = l1 - l0;
+  Shard Q;      // (d is checked on the mean-only path below, and by the cross solve)
+  if (int rc = post_shard(post, "dense-H posterior handle: use lmm_ilmm_post_mean_and_var", gps, m, d, latent_begin, latent_end, Q, nullptr)) return rc;
+  if (int rc = shard_check(Q.l0, Q.l1, m)) return rc;
+  const Latent* lts = Q.lts;
+  const int l0 = Q.l0, ms = Q.ms;
   hipStream_t st0 = g.streams[0];
-  // H columns of the shard (p x ms)
-  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
-  for (int k = 0; k < ms; ++k)
-    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * (S ? std::sqrt(S[l0 + k]) : 1.0);
+  const std::vector<double> Hs = shard_H(U, S, p, l0, ms);      // H columns of the shard (p x ms)
   Uploaded Hd(Hs, st0);
   DevIn xsd(xs, (size_t)d * ns, st0);
   Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
@@ -4009,16 +4069,11 @@ int lmm_oilmm_mean_and_var_grad_xs(const lmm_post_t* post, const lmm_gp_t* gps, 
   if (post && post->kind != 0)
     return fail(LMM_ERR_UNSUPPORTED, "gradients of the predictive marginals of a dense-H posterior (coupled latents) are not served");
   if (int rc = input_grad_check(d, true)) return rc;
-  int l0 = latent_begin, l1 = latent_end;
-  std::shared_ptr<LatentSet> ls;
-  if (post) {
-    l0 = post->l0; l1 = post->l1;
-    if (post->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", post->m, m);
-    if (post->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, xs has d=%d", post->d, d);
-  } else if (int rc = resolve(gps, m, d, ls)) return rc;
-  if (int rc = refuse_sho(post ? *post->ls : *ls, "gradients of the predictive marginals are")) return rc;
-  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
-  const int ms = l1 - l0;
+  Shard Q;
+  if (int rc = post_shard(post, nullptr, gps, m, d, latent_begin, latent_end, Q, "xs")) return rc;
+  if (int rc = refuse_sho(*Q.ls, "gradients of the predictive marginals are")) return rc;
+  if (int rc = shard_check(Q.l0, Q.l1, m)) return rc;
+  const int l0 = Q.l0, ms = Q.ms;
   hipStream_t st0 = g.streams[0];
   const size_t count = (size_t)d * ns;
   DevOut go(grad_xs, count);
@@ -4030,10 +4085,11 @@ int lmm_oilmm_mean_and_var_grad_xs(const lmm_post_t* post, const lmm_gp_t* gps, 
     return LMM_OK;
   }
   // latent cotangents on the device: mbar = dmean H_s, vbar = dvar (H_s .* H_s)   (ns x ms; H_s the shard's columns of U sqrt(S))
+  const std::vector<double> Hs = shard_H(U, S, p, l0, ms);
   std::vector<double> HT((size_t)ms * p), H2T((size_t)ms * p);
   for (int k = 0; k < ms; ++k)
     for (int o = 0; o < p; ++o) {
-      const double h = U[o + (size_t)(l0 + k) * p] * (S ? std::sqrt(S[l0 + k]) : 1.0);
+      const double h = Hs[o + (size_t)k * p];
       HT[k + (size_t)o * ms] = h; H2T[k + (size_t)o * ms] = h * h;
     }
   Uploaded HTd(HT, st0), H2Td(H2T, st0);
@@ -4121,26 +4177,18 @@ extern "C" int lmm_lmm_mean_and_cov(const lmm_post_t* post, const lmm_gp_t* gps,
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!U || !xs || !mean_out || !cov_out || d <= 0 || ns <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if ((double)p * ns * (double)p * ns > 4e8) return fail(LMM_ERR_UNSUPPORTED, "full covariance (p*ns)^2 too large");
   if (!jit) jit = &kDefaultJit;
   const lmm_post* P = post;
-  int l0 = latent_begin, l1 = latent_end;
-  std::shared_ptr<LatentSet> ls;
-  if (P) {
-    if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "full covariance of the dense-H posterior is not built");
-    l0 = P->l0; l1 = P->l1; ls = P->ls;
-    if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", P->m, m);
-    if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  } else if (int rc = resolve(gps, m, d, ls)) return rc;
-  const Latent* lts = ls->lat.data();
-  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
-  const int ms = l1 - l0;
+  Shard Q;
+  if (int rc = post_shard(P, "full covariance of the dense-H posterior is not built", gps, m, d, latent_begin, latent_end, Q)) return rc;
+  if (int rc = shard_check(Q.l0, Q.l1, m)) return rc;
+  const Latent* lts = Q.lts;
+  const int l0 = Q.l0, ms = Q.ms;
   hipStream_t st0 = g.streams[0];
-  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
-  for (int k = 0; k < ms; ++k)
-    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * (S ? std::sqrt(S[l0 + k]) : 1.0);
+  const std::vector<double> Hs = shard_H(U, S, p, l0, ms);
   Uploaded Hd(Hs, st0);
   DevIn xsd(xs, (size_t)d * ns, st0);
   DevOut mo(mean_out, (size_t)ns * p), co(cov_out, (size_t)ns * p * ns * p);
@@ -4188,20 +4236,16 @@ extern "C" int lmm_mogp_cross_cov(const lmm_post_t* post, const lmm_gp_t* gps, i
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!x || !y || !cov_out || d <= 0 || n <= 0 || n2 <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if ((double)m * n * (double)m * n2 > 4e8) return fail(LMM_ERR_UNSUPPORTED, "cross-covariance (m n) x (m n2) too large");
   const lmm_post* P = post;
-  int l0 = latent_begin, l1 = latent_end;
-  std::shared_ptr<LatentSet> ls;
-  if (P) {
-    if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "cross-covariance of the coupled latents of a dense-H posterior is not built");
-    l0 = P->l0; l1 = P->l1; ls = P->ls;
-    if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, m = %d", P->m, m);
-    if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch: posterior has d=%d, x has d=%d", P->d, d);
-  } else if (int rc = resolve(gps, m, d, ls)) return rc;
-  const Latent* lts = ls->lat.data();
-  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
+  Shard Q;
+  if (int rc = post_shard(P, "cross-covariance of the coupled latents of a dense-H posterior is not built", gps, m, d, latent_begin, latent_end, Q, "x",
+                          "posterior has %d latents, m = %d")) return rc;
+  if (int rc = shard_check(Q.l0, Q.l1, m)) return rc;
+  const Latent* lts = Q.lts;
+  const int l0 = Q.l0, l1 = Q.l1;
   hipStream_t st0 = g.streams[0];
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)d * n2, st0);
   const size_t R = (size_t)m * n, Ccols = (size_t)m * n2;
@@ -4241,32 +4285,22 @@ int lmm_oilmm_post_logpdf(const lmm_post_t* post, const double* U, const double*
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!post || !U || !S || !xs || !ys || !out || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
-  if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "dense-H posterior handle: use lmm_ilmm_post_logpdf");
-  if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", P->m, m);
-  if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
+  Shard Q;
+  if (int rc = post_shard(P, "dense-H posterior handle: use lmm_ilmm_post_logpdf", nullptr, m, d, 0, 0, Q)) return rc;
   if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   hipStream_t st0 = g.streams[0];
-  const int l0 = P->l0, l1 = P->l1, ms = l1 - l0;
-  std::vector<double> T, ST, H;
-  project_orthogonal(U, S, p, m, sigma2, T, ST, H);
+  const int l0 = Q.l0, ms = Q.ms;
+  OilmmFront F(U, S, p, m, sigma2);
+  const std::vector<double>& ST = F.ST;
   DevIn xsd(xs, (size_t)d * ns, st0), ysd(ys, (size_t)ns * p, st0);
-  Uploaded Td(T, st0);
-  const int C = with_regulariser ? m : ms, c0 = with_regulariser ? 0 : l0;
-  Buf<double> Ty((size_t)ns * std::max(C, 1)), resid_dev(1);
+  F.Td = Uploaded(F.T, st0);      // (the handle's vectors carry the means)
   double resid = 0.0;
-  if (C > 0) project_on_device(ysd.p, ns, p, Td.buf, m, c0, C, nullptr, Ty.p, st0);
-  if (with_regulariser) {
-    Uploaded Hd(H, st0);
-    Buf<double> partial(tall_skinny_partials(ns, p));
-    residual_on_device(ysd.p, ns, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p, st0);
-    HIPCHK(hipMemcpyAsync(&resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
-    HIPCHK(hipStreamSynchronize(st0));
-  }
-  const double* Ty_shard = Ty.p + (size_t)(l0 - c0) * ns;
+  const double* Ty_shard = F.rows(ysd.p, ns, l0, ms, with_regulariser != 0, &resid);
+  if (with_regulariser) HIPCHK(hipStreamSynchronize(st0));
   Dims Ds(ns, 1);
   XsSlots X(P, ms, ns, Ds);
   const int mk = X.F.mk;
@@ -4294,11 +4328,7 @@ int lmm_oilmm_post_logpdf(const lmm_post_t* post, const double* U, const double*
   if (int rc = X.F.check(l0)) return rc;
   double total = 0.0;
   for (int k = 0; k < ms; ++k) total += lml[k];
-  if (with_regulariser) {
-    double logdetS = 0.0;
-    for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
-    total += -((double)ns * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * sigma2)) + resid / sigma2) / 2.0;
-  }
+  if (with_regulariser) total += oilmm_regulariser(ns, p, m, S, sigma2, resid);
   *out = total;
   return LMM_OK;
   LMM_CATCH
@@ -4310,28 +4340,20 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps, const double
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  if (int rc = post_dtype_check(post)) return rc;
   if (!U || !xs || !z_lat || !out || d <= 0 || ns <= 0 || p <= 0 || m <= 0 || nsamples <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (add_noise && !eps) return fail(LMM_ERR_ARG, "eps is NULL");
   if (!jit) jit = &kDefaultJit;
   const lmm_post* P = post;
-  int l0 = latent_begin, l1 = latent_end;
-  std::shared_ptr<LatentSet> ls;
-  if (P) {
-    if (P->kind != 0) return fail(LMM_ERR_UNSUPPORTED, "dense-H posterior handle: use lmm_ilmm_post_rand");
-    l0 = P->l0; l1 = P->l1; ls = P->ls;
-    if (P->m != m) return fail(LMM_ERR_DIM, "posterior has %d latents, H has %d", P->m, m);
-    if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  } else if (int rc = resolve(gps, m, d, ls)) return rc;
-  const Latent* lts = ls->lat.data();
-  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
-  const int ms = l1 - l0, mk = std::max(ms, 1);
+  Shard Q;
+  if (int rc = post_shard(P, "dense-H posterior handle: use lmm_ilmm_post_rand", gps, m, d, latent_begin, latent_end, Q)) return rc;
+  if (int rc = shard_check(Q.l0, Q.l1, m)) return rc;
+  const Latent* lts = Q.lts;
+  const int l0 = Q.l0, ms = Q.ms, mk = Q.mk;
   // OILMM: f(x) default jitter 1e-18 (reference src/oilmm.jl:47); dense-H ILMM: 1e-12 (src/ilmm.jl:84)
   const double jitter = S ? jit->default_jitter : jit->ilmm_rand_jitter;
   hipStream_t st0 = g.streams[0];
-  std::vector<double> Hs((size_t)p * mk, 0.0);
-  for (int k = 0; k < ms; ++k)
-    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * (S ? std::sqrt(S[l0 + k]) : 1.0);
+  const std::vector<double> Hs = shard_H(U, S, p, l0, ms);
   Uploaded Hd(Hs, st0);
   // z_lat: [sample][m][ns], eps: [sample][p][ns], out: [sample][p][ns]
   DevIn xsd(xs, (size_t)d * ns, st0), zd(z_lat, (size_t)ns * m * nsamples, st0);
@@ -4472,7 +4494,7 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
       Bu.add(out.Lu[k].p, out.Wu[k].p, info + k);
       Bb.add(out.LB[k].p, out.WB[k].p, info + ms + k);
     }
-    launch_sparse_moments(a, nb, st);
+    launch_sparse_moments(a, nb, sum_mode(lts, l0 + k0, l0 + k0 + nb), st);
     launch_sparse_finish(scratch.p, nch, nz, Pb, D.ld, true, bb, sb, nb, st);
     // L_u = chol(K_uu + jitter I), with b as the rider row: it becomes c0 = L_u^-1 b
     gram_batch_g(ga, nb, st, "inducing Gram assembly");
@@ -4520,15 +4542,6 @@ struct SparseGradOut {
   double* gz_dev = nullptr;                 // d x nz (device) or nullptr
 };
 
-static int sparse_grad_mode(const Latent* lts, int l0, int l1) {
-  int mode = 0;
-  for (int l = l0; l < l1; ++l) {
-    if (lts[l].has_periodic()) return 2;
-    if (lts[l].is_sum()) mode = 1;
-  }
-  return mode;
-}
-
 static void sparse_grad_fill_lat(SparseGradLat& s, const Latent& gp, const LatentDev* gd, const double* w, double wconst, const double* r,
                                  double rsub, const double* PhiBar, const double* beta, double* grad_r) {
   s.g = gp.dev(); s.gd = gd; s.nterms = gp.nt();
@@ -4574,7 +4587,7 @@ static int sparse_grad_core(const double* xd, int d, int n, const double* zd, in
   if (int rc = sparse_plan(n, nz, nb_per, 0, &chunk, &nch)) return rc;
   const int tm = (nz + 63) / 64;
   Buf<double> scratch((size_t)nb_per * nch * tm * sparse_grad_partial_stride(d));
-  const int mode = sparse_grad_mode(lts, l0, l1);
+  const int mode = sum_mode(lts, l0, l1);
   bool gz_first = true;
   fan.run([&](const FanBatch& fb) {
     const int k0 = fb.k0, nb = fb.nb;
@@ -4647,51 +4660,42 @@ static int sparse_oilmm(const double* x, int d, int n, const double* y, int p, c
                         const lmm_gp_t* gps, int l0, int l1, const double* z, int nz, double jitter, int with_regulariser,
                         SparseState& out, double* reg, std::shared_ptr<LatentSet>* ls_out, Buf<double>* z_keep,
                         SparseGradOut* grad = nullptr) {
-  if (!x || !y || !U || !S || !z || d <= 0 || n <= 0 || p <= 0 || m <= 0 || nz <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
+  if (int rc = train_args(!x || !y || !U || !S || !z || d <= 0 || n <= 0 || p <= 0 || m <= 0 || nz <= 0, p, m, S, sigma2, l0, l1, 0)) return rc;
   if (int rc = sparse_shape_check(d, nz, jitter)) return rc;
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
-  RESOLVE(gps, m, d);
+  Train R;
+  if (int rc = train_resolve(gps, m, d, l0, l1, R)) return rc;
+  const std::shared_ptr<LatentSet>& ls = R.ls;
+  const Latent* lts = R.lts;
+  const std::vector<double>& means = R.means;
   if (int rc = refuse_sho(*ls, "inducing-point inference is")) return rc;
   if (grad) { if (int rc = ls->ard_grad_check()) return rc; }
   out.keep_grad = grad != nullptr;
   hipStream_t st0 = g.streams[0];
-  std::vector<double> T, ST, H;
-  project_orthogonal(U, S, p, m, sigma2, T, ST, H);
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
+  OilmmFront F(U, S, p, m, sigma2);
+  const std::vector<double>& ST = F.ST;
+  R.upload(x, (size_t)d * n, y, (size_t)n * p);
+  const DevIn &xd = R.xd, &yd = R.yd;
   Buf<double> zown((size_t)d * nz);
   HIPCHK(hipMemcpyAsync(zown.p, z, (size_t)d * nz * sizeof(double), hipMemcpyDefault, st0));
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  F.Td = Uploaded(F.T, st0);      // (sparse_core subtracts the means)
   // (T y) of every latent when the regulariser needs the residual, else of the shard
-  const int c0 = with_regulariser ? 0 : l0, C = with_regulariser ? m : std::max(l1 - l0, 1);
-  Uploaded Td(T, st0), Hd(H, st0);
-  Buf<double> Ty((size_t)n * C), resid_dev(1), partial(tall_skinny_partials(n, p));
-  if (with_regulariser || l1 > l0) project_on_device(yd.p, n, p, Td.buf, m, c0, with_regulariser ? m : l1 - l0, nullptr, Ty.p, st0);
   double resid = 0.0;
-  if (with_regulariser) {
-    residual_on_device(yd.p, n, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p, st0);
-    HIPCHK(hipMemcpyAsync(&resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
-  }
-  if (int rc = sparse_core(xd.p, d, n, zown.p, nz, jitter, lts, l0, l1, Ty.p + (size_t)(l0 - c0) * n, means.data(), ST.data(), out)) {
+  const double* Ty_shard = F.rows(yd.p, n, l0, l1 - l0, with_regulariser != 0, &resid);
+  if (int rc = sparse_core(xd.p, d, n, zown.p, nz, jitter, lts, l0, l1, Ty_shard, means.data(), ST.data(), out)) {
     (void)hipStreamSynchronize(st0);      // the residual's copy targets this frame
     return rc;
   }
   HIPCHK(hipStreamSynchronize(st0));
   *reg = 0.0;
-  if (with_regulariser) {        // reference src/oilmm.jl:101-113, as lmm_oilmm_logpdf
-    double logdetS = 0.0;
-    for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
-    *reg = -((double)n * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * sigma2)) + resid / sigma2) / 2.0;
-  }
+  if (with_regulariser) *reg = oilmm_regulariser(n, p, m, S, sigma2, resid);        // as lmm_oilmm_logpdf
   if (grad) {
     // host chain rule, as oilmm_grad_core's: a_l = -d elbo_l / d r in the place of alpha, d elbo_l / d w in the place of d lml / d noise
     const int ms = l1 - l0, NGR = LMM_NGRAD;
     OilmmGrad& G = grad->G;
     std::vector<double> hred, hard, gksum;
     Buf<double> gr((size_t)n * std::max(ms, 1)), ones(n);
-    const double* rvs = Ty.p + (size_t)(l0 - c0) * n;
+    const double* rvs = Ty_shard;
     if (int rc = sparse_grad_core(xd.p, d, n, zown.p, nz, ls.get(), l0, l1, rvs, means.data(), ST.data(), out, hred, hard, gksum, gr.p,
                                   grad->gz_dev)) return rc;
     const size_t pp = (size_t)p * p;
@@ -4743,7 +4747,7 @@ static int sparse_oilmm(const double* x, int d, int n, const double* y, int p, c
     if (grad->gy_dev) {
       // d/dY[o, i] = sum_l T[l, o] (d elbo_l / d r)[i] - (P'P Y)[o, i] / sigma2
       std::vector<double> Tt((size_t)p * std::max(ms, 1), 0.0);
-      for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) Tt[o + (size_t)k * p] = T[(l0 + k) + (size_t)o * m];
+      for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) Tt[o + (size_t)k * p] = F.T[(l0 + k) + (size_t)o * m];
       Uploaded Ttd(Tt, st0);
       Buf<double> ga((size_t)n * p);
       launch_mix(gr.p, n, ms, Ttd.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, with_regulariser ? ga.p : grad->gy_dev, st0);
@@ -4863,9 +4867,7 @@ int lmm_oilmm_sparse_mean_and_var(const lmm_sparse_post_t* post, const lmm_gp_t*
   const lmm_sparse_post* P = post;
   const int l0 = P->l0, l1 = P->l1, ms = l1 - l0, M = P->nz;
   hipStream_t st0 = g.streams[0];
-  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
-  for (int k = 0; k < ms; ++k)
-    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
+  const std::vector<double> Hs = shard_H(U, S, p, l0, ms);
   Uploaded Hd(Hs, st0);
   DevIn xsd(xs, (size_t)d * ns, st0);
   Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1)), v1(ns), v2(ns), tmp(ns);
@@ -4917,7 +4919,7 @@ int lmm_dev_sparse_moments(const double* x, int d, int n, const double* z, int n
   sparse_fill_lat(a.lat[0], lts[0], w, 0.0, r, 0.0);
   BatchPtr Pb{}, bb{}, sb{};
   Pb.p[0] = Phi; bb.p[0] = b; sb.p[0] = scalars;
-  launch_sparse_moments(a, 1, st0);
+  launch_sparse_moments(a, 1, sum_mode(lts, 0, 1), st0);
   launch_sparse_finish(scratch.p, nch, nz, Pb, ld, false, bb, sb, 1, st0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st0));
@@ -4958,7 +4960,7 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
   a.x = x; a.z = z; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.ld = ld; a.scratch = scratch.p; a.lat = dl.p;
   BatchPtr rb{}, zb{};
   rb.p[0] = term_records; zb.p[0] = grad_z;
-  launch_sparse_grad(a, 1, sparse_grad_mode(lts, 0, 1), st0);
+  launch_sparse_grad(a, 1, sum_mode(lts, 0, 1), st0);
   launch_sparse_grad_finish(scratch.p, nch, nz, d, rb, zb, 1, st0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st0));
@@ -5181,8 +5183,7 @@ static int ss_front(const double* yd, int n, int p, const double* U, const doubl
   }
   const int nobs = (int)idx.size();
   Fr.nobs = nobs;
-  std::vector<double> means(m);
-  for (int l = 0; l < m; ++l) means[l] = lts[l].mean;
+  const std::vector<double> means = latent_means(lts, m);
   if (nobs == n) {
     if (int rc = missing_front(yd, n, p, U, S, m, s2, means.data(), l0, l1, want_resid, F)) return rc;
     Fr.w = std::move(F.nv); Fr.r = std::move(F.z);
@@ -5231,12 +5232,7 @@ struct SSTrain {
 };
 static int ss_train(bool missing, const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
                     const lmm_gp_t* gps, int l0, int l1, SSTrain& T, bool want_resid = false, const std::function<int()>& after_args = nullptr) {
-  if (missing || !x || !U || !S || n <= 0 || p <= 0 || m <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (m > p) return fail(LMM_ERR_DIM, "out dim of x != out dim of f.");
-  if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
-  for (int l = 0; l < m; ++l)
-    if (!(S[l] > 0.0) || !std::isfinite(S[l])) return fail(LMM_ERR_ARG, "S must be finite and > 0 (S[%d] = %g)", l, S[l]);
-  if (l0 < 0 || l1 > m || l0 > l1) return fail(LMM_ERR_ARG, "bad latent shard");
+  if (int rc = train_args(missing || !x || !U || !S || n <= 0 || p <= 0 || m <= 0, p, m, S, sigma2, l0, l1, TRAIN_SIGMA2 | TRAIN_S)) return rc;
   if (g_f32) return ss_refuse_f32();
   if (after_args)
     if (int rc = after_args()) return rc;
@@ -5247,14 +5243,6 @@ static int ss_train(bool missing, const double* x, int n, const double* y, int p
   if (int rc = ss_check_sorted(T.xd.p, n)) return rc;
   T.l0 = l0; T.l1 = l1; T.ms = l1 - l0; T.mk = std::max(T.ms, 1);
   return y ? ss_front(T.yd.p, n, p, U, S, m, sigma2, T.lts, l0, l1, T.Fr, want_resid) : (int)LMM_OK;
-}
-
-// H = U sqrt(S) of the shard's ms latents from l0 on, p x max(ms, 1) column-major
-static std::vector<double> ss_shard_H(const double* U, const double* S, int p, int l0, int ms) {
-  std::vector<double> Hs((size_t)p * std::max(ms, 1), 0.0);
-  for (int k = 0; k < ms; ++k)
-    for (int o = 0; o < p; ++o) Hs[o + (size_t)k * p] = U[o + (size_t)(l0 + k) * p] * std::sqrt(S[l0 + k]);
-  return Hs;
 }
 
 int lmm_oilmm_logpdf_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
@@ -5286,7 +5274,7 @@ int lmm_oilmm_mean_and_var_statespace(const double* x, int n, const double* y, i
   const int ms = T.ms;
   Buf<double> ml((size_t)n * T.mk), vl((size_t)n * T.mk);
   if (int rc = ss_core(T.xd.p, n, T.lts + T.l0, ms, T.Fr.w.p, T.Fr.r.p, 0, nullptr, nullptr, nullptr, ml.p, vl.p, true)) return rc;
-  Uploaded Hd(ss_shard_H(U, S, p, T.l0, ms), st0);
+  Uploaded Hd(shard_H(U, S, p, T.l0, ms), st0);
   DevOut mo(mean_out, (size_t)n * p), vo(var_out, (size_t)n * p);
   // the mixing of lmm_oilmm_mean_and_var (reference src/oilmm.jl:69,72)
   mix_marginals(ml.p, n, ms, Hd.buf.p, p, 1, 0.0, 0.0, mo.p, st0);
@@ -5550,7 +5538,7 @@ int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* 
   P->x = Buf<double>((size_t)n);
   P->fstate = Buf<double>(std::max<size_t>(total, 1)); P->sstate = Buf<double>(std::max<size_t>(total, 1));
   HIPCHK(hipMemcpyAsync(P->x.p, xd.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
-  const std::vector<double> Hs = ss_shard_H(U, S, p, l0, ms);
+  const std::vector<double> Hs = shard_H(U, S, p, l0, ms);
   P->H = Buf<double>(Hs.size());
   HIPCHK(hipMemcpyAsync(P->H.p, Hs.data(), Hs.size() * sizeof(double), hipMemcpyHostToDevice, st0));
   std::vector<double> lml(mk, 0.0);
@@ -5776,7 +5764,7 @@ int lmm_oilmm_rand_statespace(const double* x, int n, const double* y, int p, co
     if (l < l0) zbefore += c;
     else if (l < l1) zshard += c;
   }
-  Uploaded Hd(ss_shard_H(U, S, p, l0, ms), st0);
+  Uploaded Hd(shard_H(U, S, p, l0, ms), st0);
   DevOut od(out, (size_t)n * p * nsamples);
   const int rc = ss_sample_mix(n, n, ms, p, Hd.buf.p, sigma2, add_noise ? eps : nullptr, nsamples, od.p, [&](int q0, int ng, double* f) {
     SSNormals zd(z, zall, zbefore, zshard, q0, ng, st0), xid(y ? xi : nullptr, (size_t)m * n, (size_t)l0 * n, (size_t)ms * n, q0, ng, st0);

@@ -282,8 +282,8 @@ static_assert(sizeof(SparseMomArgs) <= 4096, "SparseMomArgs is passed by value: 
 size_t sparse_partial_stride(int nz);         // doubles of one (latent, chunk) partial: the 64 x 64 tiles of Phi's lower triangle, b, 3 scalars
 int sparse_default_chunk(int n, int nz, int nb);
 // Phi (the lower 64 x 64 tiles with nz padded to 64, zero rows beyond nz), b, (s, kappa, lambda) of nb latents in one launch
-// (blockIdx.z = latent) into a.scratch, one partial per chunk; no atomics.
-void launch_sparse_moments(const SparseMomArgs& a, int nb, hipStream_t st);
+// (blockIdx.z = latent) into a.scratch, one partial per chunk; no atomics.  mode: as launch_sparse_grad's, of these nb latents.
+void launch_sparse_moments(const SparseMomArgs& a, int nb, int mode, hipStream_t st);
 // The partials added in chunk order: Phi.p[l] (nz x nz, column-major ld; the lower triangle, mirror: also the upper), b.p[l] (nz),
 // scal.p[l] (3).
 void launch_sparse_finish(const double* scratch, int nch, int nz, const BatchPtr& Phi, int ld, bool mirror, const BatchPtr& b,

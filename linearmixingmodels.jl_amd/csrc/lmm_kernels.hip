@@ -5109,27 +5109,61 @@ int g_f32 = 0;
 static int gram_cpw(int row_tiles, int col_tiles, int nmat) {
   return (long long)row_tiles * ((col_tiles + 3) / 4) * nmat < 2048 ? 1 : 4;
 }
+// Tag dispatchers: each hands one axis of a launch's template arguments to a generic lambda as a compile-time value, so every kernel's
+// argument list is written once.  A dispatcher names exactly the values its axis has instantiations for (none builds a cross product
+// the kernels do not have: ND exists for the eight non-sum kinds only, and each kernel family names its own DK buckets).
+template <int V> using IntTag = std::integral_constant<int, V>;
+template <int K_, bool ND_> struct GramTag { static constexpr int K = K_; static constexpr bool ND = ND_; };
+// kernel kind of a Gram assembly: a sum latent by whether a term is (locally) periodic, the others by ND (1 < d <= 8)
+template <typename F>
+void gram_dispatch(const GramArgs& a, F&& f) {
+  const bool nd = (a.d > 1 && a.d <= 8);
+  auto plain = [&](auto k) { if (nd) f(GramTag<decltype(k)::value, true>()); else f(GramTag<decltype(k)::value, false>()); };
+  if (a.kind == LMM_KERNEL_SUM && a.sum_per) f(GramTag<LMM_KERNEL_SUM_PER, false>());
+  else if (a.kind == LMM_KERNEL_SUM) f(GramTag<LMM_KERNEL_SUM, false>());
+  else if (a.kind == LMM_KERNEL_SE) plain(IntTag<LMM_KERNEL_SE>());
+  else if (a.kind == LMM_KERNEL_MATERN32) plain(IntTag<LMM_KERNEL_MATERN32>());
+  else if (a.kind == LMM_KERNEL_MATERN12) plain(IntTag<LMM_KERNEL_MATERN12>());
+  else if (a.kind == LMM_KERNEL_RQ) plain(IntTag<LMM_KERNEL_RQ>());
+  else if (a.kind == LMM_KERNEL_SHO) plain(IntTag<LMM_KERNEL_SHO>());
+  else if (a.kind == LMM_KERNEL_PERIODIC) plain(IntTag<LMM_KERNEL_PERIODIC>());
+  else if (a.kind == LMM_KERNEL_LOCALLY_PERIODIC) plain(IntTag<LMM_KERNEL_LOCALLY_PERIODIC>());
+  else plain(IntTag<LMM_KERNEL_MATERN52>());
+}
+// EXT of the gradient and prediction kernels: 1 Matern12 / RQ / SHO, 2 periodic, 3 locally periodic
+static int grad_ext(int kind) {
+  if (kind == LMM_KERNEL_LOCALLY_PERIODIC) return 3;
+  if (kind == LMM_KERNEL_PERIODIC) return 2;
+  return kind >= LMM_KERNEL_MATERN12 ? 1 : 0;
+}
+template <typename F>
+void ext_dispatch(int ext, F&& f) {
+  if (ext == 3) f(IntTag<3>());
+  else if (ext == 2) f(IntTag<2>());
+  else if (ext) f(IntTag<1>());
+  else f(IntTag<0>());
+}
+// DK, the per-dimension registers of a kernel: 1 (where the kernel has it: ONE), 4, 8, or the family's widest input
+template <bool ONE, int DMAX, typename F>
+void dk_dispatch(int d, F&& f) {
+  if constexpr (ONE) { if (d == 1) return f(IntTag<1>()); }
+  if (d <= 4) f(IntTag<4>());
+  else if (d <= 8) f(IntTag<8>());
+  else f(IntTag<DMAX>());
+}
+// sum mode of the dense and inducing-point kernels (sum_mode of lmm_api.hip): 0 plain latents, 1 some sum latent, 2 some (locally) periodic latent or term
+template <typename F>
+void mode_dispatch(int mode, F&& f) {
+  if (mode == 2) f(IntTag<2>());
+  else if (mode) f(IntTag<1>());
+  else f(IntTag<0>());
+}
+
 void launch_gram(const GramArgs& a0, hipStream_t st) {
   GramArgs a = a0;
   a.cpw = gram_cpw(a.nrows / 64 - a.row_tile0, a.ncols / 64, 1);
   dim3 grid(a.nrows / 64 - a.row_tile0, (a.ncols / 64 + a.cpw - 1) / a.cpw);
-  const bool nd = (a.d > 1 && a.d <= 8);
-#define LMM_GRAM_LAUNCH(K)                                                                          \
-  do {                                                                                              \
-    if (nd) LMM_TS_LAUNCH((gram_kernel<K, true, TS>), grid, dim3(256), 0, st, a);                   \
-    else LMM_TS_LAUNCH((gram_kernel<K, false, TS>), grid, dim3(256), 0, st, a);                     \
-  } while (0)
-  if (a.kind == LMM_KERNEL_SUM && a.sum_per) LMM_TS_LAUNCH((gram_kernel<LMM_KERNEL_SUM_PER, false, TS>), grid, dim3(256), 0, st, a);
-  else if (a.kind == LMM_KERNEL_SUM) LMM_TS_LAUNCH((gram_kernel<LMM_KERNEL_SUM, false, TS>), grid, dim3(256), 0, st, a);
-  else if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
-  else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
-  else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
-  else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
-  else if (a.kind == LMM_KERNEL_SHO) LMM_GRAM_LAUNCH(LMM_KERNEL_SHO);
-  else if (a.kind == LMM_KERNEL_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_PERIODIC);
-  else if (a.kind == LMM_KERNEL_LOCALLY_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_LOCALLY_PERIODIC);
-  else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
-#undef LMM_GRAM_LAUNCH
+  gram_dispatch(a, [&](auto t) { typedef decltype(t) T; LMM_TS_LAUNCH((gram_kernel<T::K, T::ND, TS>), grid, dim3(256), 0, st, a); });
 }
 
 void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
@@ -5151,23 +5185,7 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     b.base.cpw = gram_cpw(b.base.nrows / 64 - b.base.row_tile0, b.base.ncols / 64, j1 - j0);
     const GramArgs& a = b.base;
     dim3 grid(a.nrows / 64 - a.row_tile0, (a.ncols / 64 + a.cpw - 1) / a.cpw, j1 - j0);
-    const bool nd = (a.d > 1 && a.d <= 8);
-#define LMM_GRAM_LAUNCH(K)                                                                          \
-    do {                                                                                            \
-      if (nd) LMM_TS_LAUNCH((gram_batch_kernel<K, true, TS>), grid, dim3(256), 0, st, b);           \
-      else LMM_TS_LAUNCH((gram_batch_kernel<K, false, TS>), grid, dim3(256), 0, st, b);             \
-    } while (0)
-    if (a.kind == LMM_KERNEL_SUM && a.sum_per) LMM_TS_LAUNCH((gram_batch_kernel<LMM_KERNEL_SUM_PER, false, TS>), grid, dim3(256), 0, st, b);
-    else if (a.kind == LMM_KERNEL_SUM) LMM_TS_LAUNCH((gram_batch_kernel<LMM_KERNEL_SUM, false, TS>), grid, dim3(256), 0, st, b);
-    else if (a.kind == LMM_KERNEL_SE) LMM_GRAM_LAUNCH(LMM_KERNEL_SE);
-    else if (a.kind == LMM_KERNEL_MATERN32) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN32);
-    else if (a.kind == LMM_KERNEL_MATERN12) LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN12);
-    else if (a.kind == LMM_KERNEL_RQ) LMM_GRAM_LAUNCH(LMM_KERNEL_RQ);
-    else if (a.kind == LMM_KERNEL_SHO) LMM_GRAM_LAUNCH(LMM_KERNEL_SHO);
-    else if (a.kind == LMM_KERNEL_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_PERIODIC);
-    else if (a.kind == LMM_KERNEL_LOCALLY_PERIODIC) LMM_GRAM_LAUNCH(LMM_KERNEL_LOCALLY_PERIODIC);
-    else LMM_GRAM_LAUNCH(LMM_KERNEL_MATERN52);
-#undef LMM_GRAM_LAUNCH
+    gram_dispatch(a, [&](auto t) { typedef decltype(t) T; LMM_TS_LAUNCH((gram_batch_kernel<T::K, T::ND, TS>), grid, dim3(256), 0, st, b); });
     j0 = j1;
   }
 }
@@ -5175,9 +5193,9 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
 void launch_dense_cross(double* R, int ldr, int nrows, int ncols, const double* xs, int ns, const double* x, int n, int d,
                         int m, const LatentDev* lat, int has_sum, hipStream_t st) {
   dim3 grid((nrows + 255) / 256, ncols);
-  if (has_sum == 2) LMM_TS_LAUNCH((dense_cross_kernel<TS, 2>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
-  else if (has_sum) LMM_TS_LAUNCH((dense_cross_kernel<TS, 1>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
-  else LMM_TS_LAUNCH((dense_cross_kernel<TS, 0>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
+  mode_dispatch(has_sum, [&](auto md) {
+    LMM_TS_LAUNCH((dense_cross_kernel<TS, decltype(md)::value>), grid, dim3(256), 0, st, (void*)R, ldr, nrows, ncols, xs, ns, x, n, d, m, lat);
+  });
 }
 
 int dense_var_kc(int Ncols) { int kc = ((Ncols + 127) / 128 + 63) / 64 * 64; return kc < 64 ? 64 : kc; }   // <= 128 chunks
@@ -5204,9 +5222,8 @@ void launch_dense_cov(const double* S, int lds, int ns, int m, const double* Hm,
 
 void launch_dense_assemble(const DenseArgs& a, hipStream_t st) {
   dim3 grid(a.nrows / 64, a.ncols / 64);
-  if (a.has_sum == 2) LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, 2>), grid, dim3(256), 0, st, a);
-  else if (a.has_sum) LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, 1>), grid, dim3(256), 0, st, a);
-  else LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, 0>), grid, dim3(256), 0, st, a);      // fp32 compute mode: Float32 matrix (the dense logpdf paths)
+  // fp32 compute mode: Float32 matrix (the dense logpdf paths)
+  mode_dispatch(a.has_sum, [&](auto md) { LMM_TS_LAUNCH((ilmm_dense_assemble_kernel<TS, decltype(md)::value>), grid, dim3(256), 0, st, a); });
 }
 
 // ---- round 3: 128-column panels (leaf128 / bulk) and the update fused with the next panel's leaf (K2c) ----
@@ -5706,10 +5723,9 @@ void launch_post_mean(const double* xs, int ns, const double* x, int n, int d, c
     return;
   }
   const int ic = post_mean_ichunk(n), nch = (n + ic - 1) / ic, nsp = (ns + 255) / 256 * 256;
-  if (g.kind == LMM_KERNEL_LOCALLY_PERIODIC) hipLaunchKernelGGL(post_mean_kernel<3>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
-  else if (g.kind == LMM_KERNEL_PERIODIC) hipLaunchKernelGGL(post_mean_kernel<2>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
-  else if (g.kind >= LMM_KERNEL_MATERN12) hipLaunchKernelGGL(post_mean_kernel<1>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
-  else hipLaunchKernelGGL(post_mean_kernel<0>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  ext_dispatch(grad_ext(g.kind), [&](auto e) {
+    hipLaunchKernelGGL(post_mean_kernel<decltype(e)::value>, dim3(nsp / 256, nch), dim3(256), 0, st, xs, ns, x, n, d, ic, alpha, g, partial);
+  });
   hipLaunchKernelGGL(strip_finish_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, partial, nsp, nch, 1, ns, 0, g.mean, 0.0,
                      out, (double*)nullptr);
 }
@@ -5749,13 +5765,6 @@ void launch_set_identity(double* R, int ld, int nc, hipStream_t st) {
 
 int grad_partials(int n, int d_ard) { const int nt = (n + 63) / 64; return (LMM_NG + 1 + d_ard) * nt * nt; }      // + 1: a locally periodic latent's decay sum
 
-// The EXT instantiation of the gradient kernels: 1 Matern12 / RQ, 2 periodic, 3 locally periodic
-static int grad_ext(int kind) {
-  if (kind == LMM_KERNEL_LOCALLY_PERIODIC) return 3;
-  if (kind == LMM_KERNEL_PERIODIC) return 2;
-  return kind >= LMM_KERNEL_MATERN12 ? 1 : 0;
-}
-
 // out (LMM_NGRAD values): [dl/d ell, tr Kinv (rows < nsplit), a.a (rows < nsplit), a.delta, sum a, tr Kinv (rows >= nsplit),
 //        a.a (rows >= nsplit), sum_{i>j} (a_i a_j - Kinv_ij) K_ij, dl/d alpha (RQ), dl/d quality (SHO) or dl/d rho (periodic kinds; 0 otherwise),
 //        dl/d decay (written for a locally periodic latent only)]
@@ -5765,24 +5774,15 @@ void launch_grad_reduce(const double* Kinv, int ld, int n, int nsplit, const dou
   const int ext = grad_ext(g.kind);
   const int nout = ext == 3 ? LMM_NG + 1 : LMM_NG;
   if (g.ils != nullptr) {          // ARD latent (the caller guarantees 1 < d <= LMM_ARD_GRAD_DMAX and out_ard != nullptr)
-#define LMM_ARD_LAUNCH(DK)                                                                                                      \
-    do {                                                                                                                        \
-      if (ext == 3) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 3>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
-      else if (ext == 2) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 2>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
-      else if (ext) LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 1>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
-      else LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, DK, 0>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial); \
-    } while (0)
-    if (d <= 4) LMM_ARD_LAUNCH(4);
-    else if (d <= 8) LMM_ARD_LAUNCH(8);
-    else LMM_ARD_LAUNCH(LMM_ARD_GRAD_DMAX);
-#undef LMM_ARD_LAUNCH
+    dk_dispatch<false, LMM_ARD_GRAD_DMAX>(d, [&](auto dk) { ext_dispatch(ext, [&](auto e) {
+      LMM_TS_LAUNCH((grad_reduce_ard_kernel<TS, decltype(dk)::value, decltype(e)::value>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+    }); });
     hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, nout + d, out_ard, nout);
     return;
   }
-  if (ext == 3) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 3>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
-  else if (ext == 2) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 2>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
-  else if (ext) LMM_TS_LAUNCH((grad_reduce_kernel<TS, 1>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
-  else LMM_TS_LAUNCH((grad_reduce_kernel<TS, 0>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  ext_dispatch(ext, [&](auto e) {
+    LMM_TS_LAUNCH((grad_reduce_kernel<TS, decltype(e)::value>), dim3(nt, nt), dim3(256), 0, st, (const void*)Kinv, ld, n, nsplit, alpha, delta, x, d, g, nt, partial);
+  });
   hipLaunchKernelGGL(grad_finish_kernel, dim3(1), dim3(256), 0, st, partial, nt, out7, nout, (double*)nullptr, nout);
 }
 
@@ -5792,18 +5792,9 @@ void launch_grad_x(const double* Kinv, int ld, int n, const double* alpha, const
                    double* gx, bool accumulate, hipStream_t st) {
   const int nt = (n + 63) / 64, nch = (nt + LMM_GX_CHUNK - 1) / LMM_GX_CHUNK;
   const int ext = grad_ext(g.kind);
-#define LMM_GX_LAUNCH(DK)                                                                                                      \
-  do {                                                                                                                        \
-    if (ext == 3) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 3>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
-    else if (ext == 2) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 2>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
-    else if (ext) LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 1>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
-    else LMM_TS_LAUNCH((grad_x_kernel<TS, DK, 0>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial); \
-  } while (0)
-  if (d == 1) LMM_GX_LAUNCH(1);
-  else if (d <= 4) LMM_GX_LAUNCH(4);
-  else if (d <= 8) LMM_GX_LAUNCH(8);
-  else LMM_GX_LAUNCH(LMM_ARD_GRAD_DMAX);
-#undef LMM_GX_LAUNCH
+  dk_dispatch<true, LMM_ARD_GRAD_DMAX>(d, [&](auto dk) { ext_dispatch(ext, [&](auto e) {
+    LMM_TS_LAUNCH((grad_x_kernel<TS, decltype(dk)::value, decltype(e)::value>), dim3(nt, nch), dim3(256), 0, st, (const void*)Kinv, ld, n, alpha, x, d, g, partial);
+  }); });
   const size_t count = (size_t)n * d;
   hipLaunchKernelGGL(grad_x_finish_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, partial, nch, count, accumulate ? 1 : 0, gx);
 }
@@ -5913,20 +5904,13 @@ void launch_pred_grad_x(const double* xs, int ns, const double* x, int n, int d,
   const int ext = grad_ext(g.kind);
   const bool var = W != nullptr;
   const dim3 grid((ns + 255) / 256, nch);
-#define LMM_PGX_LAUNCH(DK, EXT)                                                                                                   \
-  do {                                                                                                                            \
-    if (var) hipLaunchKernelGGL((pred_grad_x_kernel<DK, EXT, true>), grid, dim3(256), 0, st, xs, ns, x, n, d, chunk, alpha, mbar,  \
-                                vbar, W, ldw, g, partial);                                                                        \
-    else hipLaunchKernelGGL((pred_grad_x_kernel<DK, EXT, false>), grid, dim3(256), 0, st, xs, ns, x, n, d, chunk, alpha, mbar,    \
-                            vbar, W, ldw, g, partial);                                                                            \
-  } while (0)
-#define LMM_PGX_DK(DK) do { if (ext == 3) LMM_PGX_LAUNCH(DK, 3); else if (ext == 2) LMM_PGX_LAUNCH(DK, 2); else if (ext) LMM_PGX_LAUNCH(DK, 1); else LMM_PGX_LAUNCH(DK, 0); } while (0)
-  if (d == 1) LMM_PGX_DK(1);
-  else if (d <= 4) LMM_PGX_DK(4);
-  else if (d <= 8) LMM_PGX_DK(8);
-  else LMM_PGX_DK(LMM_ARD_GRAD_DMAX);
-#undef LMM_PGX_DK
-#undef LMM_PGX_LAUNCH
+  auto launch = [&](auto dk, auto e, auto v) {
+    hipLaunchKernelGGL((pred_grad_x_kernel<decltype(dk)::value, decltype(e)::value, decltype(v)::value>), grid, dim3(256), 0, st, xs, ns, x, n, d, chunk,
+                       alpha, mbar, vbar, W, ldw, g, partial);
+  };
+  dk_dispatch<true, LMM_ARD_GRAD_DMAX>(d, [&](auto dk) { ext_dispatch(ext, [&](auto e) {
+    if (var) launch(dk, e, std::true_type()); else launch(dk, e, std::false_type());
+  }); });
   const size_t count = (size_t)ns * d;
   hipLaunchKernelGGL(grad_x_finish_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, partial, nch, count, accumulate ? 1 : 0, gx);
 }
@@ -5948,19 +5932,11 @@ int sparse_default_chunk(int n, int nz, int nb) {
   chunk = (chunk + SPM_KT - 1) / SPM_KT * SPM_KT;
   return (int)chunk;
 }
-void launch_sparse_moments(const SparseMomArgs& a, int nb, hipStream_t st) {
+void launch_sparse_moments(const SparseMomArgs& a, int nb, int mode, hipStream_t st) {
   const int tm = (a.nz + 63) / 64;
   const dim3 grid(tm * (tm + 1) / 2, a.nch, nb);
   const size_t stride = sparse_partial_stride(a.nz);
-  int mode = 0;
-  for (int l = 0; l < nb; ++l) {
-    const LatentDev& g = a.lat[l].g;
-    if (g.kind == LMM_KERNEL_PERIODIC || g.kind == LMM_KERNEL_LOCALLY_PERIODIC || a.lat[l].sum_per) mode = 2;
-    else if (g.kind == LMM_KERNEL_SUM && mode < 1) mode = 1;
-  }
-  if (mode == 2) hipLaunchKernelGGL(sparse_moments_kernel<2>, grid, dim3(256), 0, st, a, stride);
-  else if (mode == 1) hipLaunchKernelGGL(sparse_moments_kernel<1>, grid, dim3(256), 0, st, a, stride);
-  else hipLaunchKernelGGL(sparse_moments_kernel<0>, grid, dim3(256), 0, st, a, stride);
+  mode_dispatch(mode, [&](auto md) { hipLaunchKernelGGL(sparse_moments_kernel<decltype(md)::value>, grid, dim3(256), 0, st, a, stride); });
 }
 void launch_sparse_finish(const double* scratch, int nch, int nz, const BatchPtr& Phi, int ld, bool mirror, const BatchPtr& b,
                           const BatchPtr& scal, int nb, hipStream_t st) {
@@ -5981,17 +5957,9 @@ size_t sparse_grad_partial_stride(int d) { return (size_t)LMM_SUM_MAX_TERMS * (4
 void launch_sparse_grad(const SparseGradArgs& a, int nb, int mode, hipStream_t st) {
   const dim3 grid((a.nz + 63) / 64, a.nch, nb);
   const size_t stride = sparse_grad_partial_stride(a.d);
-#define LMM_SPG_LAUNCH(DK)                                                                                       \
-  do {                                                                                                          \
-    if (mode == 2) hipLaunchKernelGGL((sparse_grad_kernel<2, DK>), grid, dim3(256), 0, st, a, stride);           \
-    else if (mode == 1) hipLaunchKernelGGL((sparse_grad_kernel<1, DK>), grid, dim3(256), 0, st, a, stride);      \
-    else hipLaunchKernelGGL((sparse_grad_kernel<0, DK>), grid, dim3(256), 0, st, a, stride);                     \
-  } while (0)
-  if (a.d == 1) LMM_SPG_LAUNCH(1);
-  else if (a.d <= 4) LMM_SPG_LAUNCH(4);
-  else if (a.d <= 8) LMM_SPG_LAUNCH(8);
-  else LMM_SPG_LAUNCH(LMM_SPARSE_DMAX);
-#undef LMM_SPG_LAUNCH
+  dk_dispatch<true, LMM_SPARSE_DMAX>(a.d, [&](auto dk) { mode_dispatch(mode, [&](auto md) {
+    hipLaunchKernelGGL((sparse_grad_kernel<decltype(md)::value, decltype(dk)::value>), grid, dim3(256), 0, st, a, stride);
+  }); });
 }
 void launch_sparse_grad_finish(const double* scratch, int nch, int nz, int d, const BatchPtr& recs, const BatchPtr& gz, int nb,
                                hipStream_t st) {

@@ -149,6 +149,12 @@ def test_prior_input_gradient_vs_finite_differences(lmm, model, d, ard, n):
     _close(G["x"], _fd_x(F, x), 1e-5)
 
 
+# the 4 < d <= 8 and d > 8 instantiations of grad_x_kernel (d = 1 and d <= 4 are above): the same comparison, same tolerance
+@pytest.mark.parametrize("d,ard", [(6, False), (12, True)])
+def test_prior_input_gradient_wide_inputs(lmm, d, ard):
+    test_prior_input_gradient_vs_finite_differences(lmm, "oilmm", d, ard, 37)
+
+
 # ---------------------------------------------------------------------------------------------------
 # 2. analytic host reference at size: 47 ragged tiles (3 chunks), and 128 tiles (8 chunks) on one latent
 # ---------------------------------------------------------------------------------------------------

@@ -168,6 +168,21 @@ def test_analytic_oilmm_n1000(lmm, d):
     _close(got_m, _oilmm_ref(gps, U, S, x, s2, y, xs, dmean, None), 1e-9)
 
 
+# the 4 < d <= 8 and d > 8 instantiations of pred_grad_x_kernel, with and without the variance cotangent: the analytic reference and
+# tolerance of test_analytic_oilmm_n1000 at n = 130, ns = 70
+@pytest.mark.parametrize("d", [6, 12])
+def test_analytic_oilmm_wide_inputs(lmm, d):
+    rng = np.random.default_rng(50 + d)
+    n, ns, p, s2 = 130, 70, 4, 0.05
+    gps = [_gp(rng, k, d) for k in ["matern52", "se", "rq"]]
+    U, S = _orth(rng, p, len(gps))
+    x, xs, y = _inputs(rng, n, d), _inputs(rng, ns, d), rng.standard_normal(n * p)
+    fx = _oilmm_post(lmm, gps, U, S, x, s2, y)(lmm.MOInputIsotopicByOutputs(xs, p), s2)
+    dmean, dvar = rng.standard_normal(ns * p), rng.standard_normal(ns * p)
+    _close(lmm.mean_and_var_vjp(fx, dmean, dvar)["x"], _oilmm_ref(gps, U, S, x, s2, y, xs, dmean, dvar), 1e-9)
+    _close(lmm.mean_and_var_vjp(fx, dmean)["x"], _oilmm_ref(gps, U, S, x, s2, y, xs, dmean, None), 1e-9)
+
+
 def test_analytic_mogp_n8192_deep_recursion(lmm):
     rng = np.random.default_rng(3)
     n, ns, m, s2 = 8192, 1024, 2, 0.1

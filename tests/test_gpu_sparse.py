@@ -271,6 +271,12 @@ def test_moments(lmm, n, M, d):
         assert np.array_equal(u[low] if u.ndim == 2 else u, v[low] if v.ndim == 2 else v)
 
 
+# a sum latent without a periodic term (sparse_moments_kernel's own instantiation; the d = 3 kernel above has one): the same checks
+def test_moments_sum_latent(lmm, monkeypatch):
+    monkeypatch.setitem(MOMENT_KERNELS, 2, ("sum", 1.3, 1.1, [("matern52", 0.8, [0.6, 0.9]), ("se", 0.5, 1.4)]))
+    test_moments(lmm, 63, 16, 2)
+
+
 # ---------------------------------------------------------------------------------------------------
 # elbo, dtc, the bound, the exact limit
 # ---------------------------------------------------------------------------------------------------

@@ -97,6 +97,13 @@ def test_second_pass(lmm, case):
         assert np.array_equal(a, b)
 
 
+# the 4 < d <= 8 (a sum latent) and d > 8 (a plain latent) instantiations of sparse_grad_kernel: the same checks, same tolerance
+@pytest.mark.parametrize("case", [(130, 70, 6, "m12+se+m32", 4.0, True), (130, 70, 12, "m52", 4.0, True)], ids=lambda c: "-".join(map(str, c)))
+def test_second_pass_wide_inputs(lmm, case, monkeypatch):
+    monkeypatch.setattr(R, "ARD", np.concatenate([R.ARD, 1.0 + 0.1 * np.arange(9)]))      # per-dimension factors for d up to 12
+    test_second_pass(lmm, case)
+
+
 # ---------------------------------------------------------------------------------------------------
 # elbo_and_gradient
 # ---------------------------------------------------------------------------------------------------

@@ -1,0 +1,186 @@
+"""Outputs of the dense per-latent path under two builds of liblmm_hip.so, byte for byte, on one GPU.
+
+    python tools/bitwise_vs_parent.py PARENT.so NEW.so > bitwise_vs_parent.txt
+
+Three child processes, one after the other and never two at once, each under a time limit and with LMM_DETERMINISTIC=1 (no split-K
+atomics): PARENT, PARENT again (the control) and NEW, all on the same inputs.  The tool stops at the first child that exits non-zero.
+Every output array of NEW is compared with PARENT's bytes, one line per operation (its output arrays back to back); an operation the
+two PARENT runs disagree on is listed as `not comparable` and is no evidence either way.  Exit status 0 when no comparable array differs.
+
+The inputs reach every branch of the launch dispatchers and every entry-point preamble: n = 200 (two 128-column panels), ns = 70, p = 9,
+m = 7 latents (SE, Matern-5/2, RQ, periodic, locally periodic, SHO -- Matern-1/2 in its place for d > 1 and where SHO is not served -- and
+a sum with a periodic term), shards [0, 7) and [2, 5), d = 1, 3 (isotropic and ARD), 6 and 12 (ARD), y complete and with single outputs
+NaN, Float64 and (logpdf and posterior paths) the Float32 compute dtype, lmm_oilmm_logpdf_multi with ncol = 3, the inducing-point bound and
+its gradient at nz = 70, the IndependentMOGP entry points, and the building blocks lmm_dev_gram / lmm_dev_sparse_moments / _grad per kind."""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N, NS, P, M, NZ = 200, 70, 9, 7, 70
+CHILD_SECONDS = 420
+
+
+def kernels(lmm, d, ard, sho):
+    ls = (lambda s: list(s * (1.0 + 0.1 * np.arange(d)))) if ard else (lambda s: s)
+    per = lmm.PeriodicKernel(0.8, ls(1.3), r=0.9)
+    return [lmm.SEKernel(1.1, ls(0.7)), lmm.Matern52Kernel(0.9, ls(0.9)), lmm.RationalQuadraticKernel(1.2, ls(0.8), alpha=1.7), per,
+            lmm.LocallyPeriodicKernel(0.7, ls(1.1), r=1.2, decay=2.0), lmm.SHOKernel(1.0, 0.6, quality=2.5) if sho else lmm.Matern12Kernel(1.0, ls(0.6)),
+            lmm.KernelSum(lmm.SEKernel(0.6, ls(0.5)), lmm.PeriodicKernel(0.4, ls(1.7), r=1.1), variance=1.3, lengthscale=1.1)]
+
+
+def child(out_path):
+    sys.path.insert(0, ROOT)
+    import ctypes as C
+    import torch
+    import lmm_amd as lmm
+    from lmm_amd import _lib as L, model as Mo
+    lmm.init(0)
+    out = {}
+
+    def leaves(v):
+        if isinstance(v, dict):
+            return [e for k in sorted(v, key=str) for e in leaves(v[k])]
+        if isinstance(v, (list, tuple)):
+            return [e for w in v for e in leaves(w)]
+        if v is None or isinstance(v, str):
+            return []
+        return [np.asarray(v.cpu() if hasattr(v, "cpu") else v, dtype=np.float64).reshape(-1)]
+
+    def rec(name, v):      # one record per operation: all its output arrays back to back, and their number
+        if callable(v):
+            try:
+                v = v()
+            except (NotImplementedError, ValueError, TypeError) as e:      # a refusal (made before any launch) is an output too
+                name, v = name + " [refused]", np.frombuffer(str(e).encode(), dtype=np.uint8)
+        ls = leaves(v)
+        out[name] = np.concatenate(ls + [np.array([float(len(ls))])])
+
+    rng = np.random.default_rng(7)
+    U = np.linalg.qr(rng.standard_normal((P, M)))[0]
+    S = rng.uniform(0.5, 2.0, M)
+    means = list(rng.standard_normal(M) * 0.3)
+    for d, ard, sho in [(1, False, True), (1, False, False), (3, False, False), (3, True, False), (6, False, False), (12, True, False)]:
+        x = np.sort(rng.uniform(0.0, 4.0, N)) if d == 1 else rng.uniform(0.0, 2.0, (d, N))
+        xs = np.sort(rng.uniform(0.0, 4.0, NS)) if d == 1 else rng.uniform(0.0, 2.0, (d, NS))
+        x2 = xs[:40] + 0.013 if d == 1 else xs[:, :40] + 0.013
+        z = np.linspace(0.05, 3.95, NZ) if d == 1 else rng.uniform(0.0, 2.0, (d, NZ))
+        y, ys, Y3 = rng.standard_normal(N * P), rng.standard_normal(NS * P), rng.standard_normal((N * P, 3))
+        ynan = y.copy()
+        ynan[rng.integers(0, P, 60) * N + rng.choice(N, 60, replace=False)] = np.nan      # 60 points miss one output each
+        fs = lmm.independent_mogp([lmm.GP(mu, k) for mu, k in zip(means, kernels(lmm, d, ard, sho))])
+        for shard in [(0, M), (2, 5)]:
+            tag = f"d={d}{' ard' if ard else ''}{' sho' if sho else ''} [{shard[0]},{shard[1]})"
+            f = lmm.ILMM(fs, lmm.Orthogonal(U, S), shard=shard)
+            fx, fxs, fx2 = (f(lmm.MOInputIsotopicByOutputs(a, P), 0.1) for a in (x, xs, x2))
+            xr = lmm.MOInputIsotopicByOutputs(xs[..., ::6], P)      # 12 points: a joint sample factors their covariance with a jitter of 1e-18
+            for f32 in (0, 1):
+                lmm.set_compute_dtype("f32" if f32 else "f64")
+                t = tag + (" f32" if f32 else "")
+                rec(f"{t} logpdf", lambda: lmm.logpdf(fx, y))
+                rec(f"{t} logpdf no regulariser", lambda: lmm.logpdf(fx, y, with_regulariser=False))
+                rec(f"{t} logpdf multi", lambda: Mo._logpdf_matrix(fx, Y3))
+                rec(f"{t} logpdf missing", lambda: lmm.logpdf(fx, ynan))
+                po = lmm.posterior(fx, y)
+                rec(f"{t} post mean_and_var", lambda: lmm.mean_and_var(po(fxs.x, 0.1)))
+                rec(f"{t} post logpdf", lambda: lmm.logpdf(po(fxs.x, 0.1), ys))
+                rec(f"{t} post missing mean_and_var", lambda: lmm.mean_and_var(lmm.posterior(fx, ynan)(fxs.x, 0.1)))
+            lmm.set_compute_dtype("f64")
+            po = lmm.posterior(fx, y)
+            rec(f"{tag} grad", lambda: lmm.logpdf_and_gradient(fx, y, inputs=not sho))
+            rec(f"{tag} grad missing", lambda: lmm.logpdf_and_gradient(fx, ynan))
+            rec(f"{tag} prior mean_and_var", lambda: lmm.mean_and_var(fxs))
+            rec(f"{tag} prior rand", lambda: lmm.rand(np.random.default_rng(3), f(xr, 0.1), 2))
+            rec(f"{tag} post mean", lambda: lmm.mean(po(fxs.x, 0.1)))
+            rec(f"{tag} post mean_and_cov", lambda: lmm.mean_and_cov(po(fxs.x, 0.1)))
+            rec(f"{tag} post rand", lambda: lmm.rand(np.random.default_rng(3), po(xr, 0.1), 2))
+            po2 = lmm.posterior(po(fx2.x, 0.2), ys[:40 * P])
+            rec(f"{tag} post post mean_and_var", lambda: lmm.mean_and_var(po2(fxs.x, 0.1)))
+            if not sho:
+                rec(f"{tag} post logpdf grad", lambda: lmm.logpdf_and_gradient(po(fxs.x, 0.1), ys, inputs=True))
+                rec(f"{tag} post vjp", lambda: lmm.mean_and_var_vjp(po(fxs.x, 0.1), dmean=ys, dvar=np.abs(ys)))
+                rec(f"{tag} post vjp mean only", lambda: lmm.mean_and_var_vjp(po(fxs.x, 0.1), dmean=ys))
+            if shard == (0, M):
+                lat = lmm.get_latent_gp(po)
+                rec(f"{tag} latent marginals", lambda: lmm.mean_and_var(lat(lmm.MOInputIsotopicByOutputs(xs, M), 1e-9)))
+                rec(f"{tag} latent cross cov", lambda: Mo._mogp_cross_cov(lat, lmm.MOInputIsotopicByOutputs(xs[..., :20], M), lmm.MOInputIsotopicByOutputs(x2[..., :24], M)))
+                if not sho:
+                    vfe = lmm.VFE(z, 1e-6)
+                    rec(f"{tag} elbo", lambda: lmm.elbo(vfe, fx, y))
+                    rec(f"{tag} dtc no regulariser", lambda: lmm.dtc(vfe, fx, y, with_regulariser=False))
+                    rec(f"{tag} elbo grad", lambda: lmm.elbo_and_gradient(vfe, fx, y))
+        # the IndependentMOGP entry points
+        tag = f"d={d}{' ard' if ard else ''}{' sho' if sho else ''} mogp"
+        ym = y[:N * M]
+        gx = fs(lmm.MOInputIsotopicByOutputs(x, M), 0.1)
+        rec(f"{tag} logpdf", lambda: lmm.logpdf(gx, ym))
+        rec(f"{tag} logpdf diag", lambda: lmm.logpdf(fs(lmm.MOInputIsotopicByOutputs(x, M), rng.uniform(0.05, 0.2, N * M)), ym))
+        rec(f"{tag} post mean_and_var", lambda: lmm.mean_and_var(lmm.posterior(gx, ym)(lmm.MOInputIsotopicByOutputs(xs, M), 0.1)))
+        # the building blocks, one latent kind at a time
+        dev = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device="cuda")
+        xd, zd = dev(np.atleast_2d(x).T), dev(np.atleast_2d(z).T)
+        w, r, beta = dev(rng.uniform(0.05, 0.5, N)), dev(rng.standard_normal(N)), dev(rng.standard_normal(NZ))
+        A = rng.standard_normal((NZ, NZ))
+        PhiBar = dev(0.5 * (A + A.T))
+        for l, k in enumerate(kernels(lmm, d, ard, sho)):
+            gp = L.gps_array([dict(k.desc(), mean=0.0)])
+            G = torch.zeros((256, 256), dtype=torch.float64, device="cuda")
+            L.check(L.load().lmm_dev_gram(C.c_void_p(G.data_ptr()), 256, 256, 256, C.c_void_p(xd.data_ptr()), d, N, gp, C.c_double(0.25)))
+            torch.cuda.synchronize()
+            rec(f"{tag} dev_gram latent {l}", lambda: G)
+            if k.kind == "sho":
+                continue
+            Phi, b, sc = torch.zeros((NZ, NZ), dtype=torch.float64, device="cuda"), torch.zeros(NZ, dtype=torch.float64, device="cuda"), torch.zeros(3, dtype=torch.float64, device="cuda")
+            L.check(L.load().lmm_dev_sparse_moments(xd.data_ptr(), d, N, zd.data_ptr(), NZ, gp, w.data_ptr(), r.data_ptr(), 64, Phi.data_ptr(), NZ, b.data_ptr(), sc.data_ptr()))
+            recs = torch.zeros(L.SUM_MAX_TERMS * (16 + d), dtype=torch.float64, device="cuda")
+            gz, gr = torch.zeros((NZ, d), dtype=torch.float64, device="cuda"), torch.zeros(N, dtype=torch.float64, device="cuda")
+            L.check(L.load().lmm_dev_sparse_grad(xd.data_ptr(), d, N, zd.data_ptr(), NZ, gp, w.data_ptr(), r.data_ptr(), PhiBar.data_ptr(), NZ, beta.data_ptr(), 64,
+                                                 recs.data_ptr(), gz.data_ptr(), gr.data_ptr()))
+            torch.cuda.synchronize()
+            rec(f"{tag} dev_sparse_moments latent {l}", [torch.tril(Phi.T), b, sc])
+            rec(f"{tag} dev_sparse_grad latent {l}", [recs, gz, gr])
+    np.savez(out_path, **out)
+
+
+def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--child":
+        return child(sys.argv[2])
+    parent, new = sys.argv[1], sys.argv[2]
+    with tempfile.TemporaryDirectory() as tmp:
+        runs = []
+        for i, lib in enumerate([parent, parent, new]):
+            path = os.path.join(tmp, f"run{i}.npz")
+            env = dict(os.environ, LMM_HIP_LIB=os.path.abspath(lib), LMM_DETERMINISTIC="1")
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=env, timeout=CHILD_SECONDS).returncode
+            if rc != 0:
+                print(f"child {i} ({lib}) exited with {rc}: stopping")
+                return 3
+            with np.load(path) as zf:
+                runs.append({k: zf[k] for k in zf.files})
+    a, c, b = runs
+    print(f"# {parent} and {new}, each in its own process on one GPU, LMM_DETERMINISTIC=1, same inputs; every output compared byte for byte.")
+    print(f"# n = {N}, ns = {NS}, p = {P}, m = {M}, nz = {NZ}; control: {parent} twice.")
+    differ = unsure = 0
+    for k in a:
+        if k not in b or a[k].shape != b[k].shape:
+            print(f"MISSING OR RESHAPED  {k}")
+            differ += 1
+            continue
+        nd = int(np.sum(a[k].view(np.uint64) != b[k].view(np.uint64)))
+        control = a[k].tobytes() == c[k].tobytes()
+        word = "not comparable" if not control else "identical" if nd == 0 else "DIFFERENT"
+        differ += word == "DIFFERENT"
+        unsure += not control
+        print(f"{word:<14} {int(a[k][-1]):>3} arrays {a[k].size - 1:>7} values, {nd} differ  nan={int(np.isnan(a[k]).sum())}  {k}")
+    extra = [k for k in b if k not in a]
+    for k in extra:
+        print(f"ONLY IN NEW  {k}")
+    print(f"# {len(a)} operations, {int(sum(v[-1] for v in a.values()))} arrays, {differ + len(extra)} operations differ, {unsure} not comparable (the control differs)")
+    return 1 if differ or extra else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
