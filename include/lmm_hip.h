@@ -961,6 +961,17 @@ int lmm_dev_potrf_plan(int NR, int NC, int nb, int rows_real, int in_flight, int
 /* Test hook: the emulation's GEMM is a persistent kernel of min(work items, CUs) workgroups; wgs >= 1 caps that grid (a small shape
  * then makes one workgroup walk several tiles), 0 goes back to the default.  Results do not depend on it. */
 int lmm_dev_set_emul_gemm_workgroups(int wgs);
+/* Switch of the emulation GEMM's zero skip.  The convert records, per 256 rows of a panel, which 128-wide K blocks hold a non-zero
+ * truncated integer; on != 0 (the default; the environment's LMM_EMUL_ZERO_SKIP=0 turns it off) the GEMM's tiles walk only the
+ * blocks that are live in both operands, on = 0 walks every block with the same kernel, on < 0 goes back to the environment's
+ * default.  A skipped block multiplies exact zeros: results do not depend on it. */
+int lmm_dev_set_emul_zero_skip(int on);
+/* Host-only (no GPU, no lmm_init needed): the K blocks a GEMM tile of the emulation walks when its two operands have the live masks
+ * (a0, a1) and (b0, b1) (bit k / 128 of a0 for k < 8192, of a1 above) and K = 128 nk, 1 <= nk <= 128, by the helpers the kernel
+ * uses: out[0 .. min(cap, length)) = the blocks in walk order, *count (may be NULL) = the number of K steps the kernel's MFMA loop
+ * runs.  An empty intersection walks block 0 alone.  Returns the length of the walk, or -LMM_ERR_ARG. */
+int lmm_dev_emul_stage_list(unsigned long long a0, unsigned long long a1, unsigned long long b0, unsigned long long b1, int nk, int* out,
+                            int cap, int* count);
 /* C[MxN] -= A[MxK] * A[0:N, :]^T for i >= j only (column-major, device pointers, one matrix) through the emulation kernels.
  * M >= N, K a multiple of 128, K <= 16384.  |error_ij| <= 4 K 2^-b amax_i amax_j + rounding of C, b = the bit budget for K. */
 int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N, int K, int nmod);

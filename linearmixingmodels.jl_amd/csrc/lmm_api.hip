@@ -872,6 +872,9 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
   std::vector<unsigned long long*> amax_kept(P.steps.size(), nullptr);
   for (size_t i = 0; i < P.steps.size(); ++i)
     if (P.steps[i].kind == POTRF_EMUL_UPDATE_LEAF) amax_kept[i] = reinterpret_cast<unsigned long long*>(call_scratch((size_t)B.nb * NR));
+  // live K blocks of the emulated updates' panels (lmm_emul.h): a few KB, rewritten by every group of every update in stream order
+  unsigned long long* emul_masks = nullptr;
+  if (P.emul_bytes > 0) emul_masks = reinterpret_cast<unsigned long long*>(call_scratch(emul_mask_bytes(NR, B.nb) / 8));
   auto leaf128 = [&](int c) { launch_leaf128(B.A, (size_t)c * ld + c, ld, B.W, (size_t)(c / 64) * 4096, W2, (size_t)(c / 128) * 16384, c, n_real, B.info, B.nb, st); };
   for (const PotrfStep& s : P.steps) {
     const bool named = s.named();
@@ -896,7 +899,7 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
           EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0};
           for (int q = 0; q < cov.n; ++q) keep.src[q] = amax_kept[cov.step[q]];
           if (r0 + s.M > NR) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's rows %d + %d exceed %d", r0, s.M, NR);
-          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, st, &keep));
+          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_masks, st, &keep));
         }
         leaf128(r0);
         break;
@@ -6073,6 +6076,28 @@ int lmm_dev_set_emul_gemm_workgroups(int wgs) {
   emul_set_gemm_workgroups(wgs);
   return LMM_OK;
 }
+// Switch of the emulation GEMM's zero skip: 1 (the default, or LMM_EMUL_ZERO_SKIP unset) walks only the K blocks that are live in
+// both operands of a tile, 0 (LMM_EMUL_ZERO_SKIP=0) walks all of them with the same kernel; on < 0 goes back to the env default.
+// Results do not depend on it.
+int lmm_dev_set_emul_zero_skip(int on) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  emul_set_zero_skip(on);
+  return LMM_OK;
+}
+// Host-only (no GPU, no lmm_init needed): the stage list of a GEMM tile whose operands have the live masks a (a0: K blocks 0 .. 63, a1:
+// 64 .. 127) and b, at depth nk = K / 128 blocks, walked with the helpers the kernel's staging cursor uses (lmm_emul.h).  out[0 .. min(
+// cap, length)) = the K blocks in walk order; *count (may be NULL) = what the kernel's MFMA loop takes for the length.  Returns the
+// length of the walk, or -LMM_ERR_ARG.
+int lmm_dev_emul_stage_list(unsigned long long a0, unsigned long long a1, unsigned long long b0, unsigned long long b1, int nk, int* out, int cap, int* count) {
+  g.err.clear();
+  if (nk < 1 || nk > 128 || cap < 0 || (cap > 0 && !out)) return -fail(LMM_ERR_ARG, "lmm_dev_emul_stage_list: 1 <= nk <= 128, cap >= 0");
+  EmulMask m = emul_live_stages(EmulMask{a0, a1}, EmulMask{b0, b1}, nk);
+  if (count) *count = emul_mask_count(m);
+  int n = 0;
+  for (; !emul_mask_empty(m); m = emul_mask_pop(m), ++n)
+    if (n < cap) out[n] = emul_mask_first(m);
+  return n;
+}
 // C (M x N, lower trapezoid i >= j) -= A A[0:N]' through the emulation kernels: one matrix, device pointers.
 int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N, int K, int nmod) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -6084,7 +6109,8 @@ int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N
   double* scratch = call_scratch((bytes + 7) / 8);
   BatchPtr Cb{}, Pb{};
   Cb.p[0] = C; Pb.p[0] = const_cast<double*>(A);
-  HIPCHK(launch_emul_update(Cb, 0, ldc, Pb, 0, lda, M, N, K, 1, 1, nmod, scratch, g.streams[0]));
+  unsigned long long* masks = reinterpret_cast<unsigned long long*>(call_scratch(emul_mask_bytes(M, 1) / 8));
+  HIPCHK(launch_emul_update(Cb, 0, ldc, Pb, 0, lda, M, N, K, 1, 1, nmod, scratch, masks, g.streams[0]));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(g.streams[0]));
   return LMM_OK;

@@ -86,6 +86,32 @@ inline EmulLayout emul_layout(int M, int N, int K, int G, int nmod) {
 }
 inline size_t emul_scratch_bytes(int M, int N, int K, int G, int nmod) { return emul_layout(M, N, K, G, nmod).total; }
 
+// ---- live K blocks (zero skip) ----
+// Per matrix and per 256-row tile row of the panel, one bit per 128-wide K block (K <= 16384: 128 bits, bit = k / 128, two 64-bit
+// words): set by the convert when any truncated integer of that block of rows is non-zero.  A block whose bit is clear holds zero
+// residues for every modulus and adds exactly zero to every integer dot product, so the GEMM may leave its stage out.  The stage list
+// of a tile is the set bits of (mask of its A rows) & (mask of its B rows) below K / 128, in increasing k; an empty intersection is
+// replaced by bit 0 alone (one stage of zeros), so that every tile has at least one stage.  Both sides of the GEMM's pipeline take
+// the list from here: the staging cursor walks it (emul_mask_first, emul_mask_pop), the MFMA loop counts it (emul_mask_count).
+#define LMM_EMUL_MASK_WORDS 2
+struct EmulMask { unsigned long long w0, w1; };
+inline size_t emul_mask_bytes(int M, int G) { return (size_t)G * ((M + LMM_EMUL_TILE - 1) / LMM_EMUL_TILE) * LMM_EMUL_MASK_WORDS * 8; }
+LMM_HD inline EmulMask emul_live_stages(EmulMask a, EmulMask b, int nk) {      // 1 <= nk <= 128
+  const unsigned long long ones = ~0ull;
+  EmulMask m;
+  m.w0 = a.w0 & b.w0 & (nk >= 64 ? ones : ones >> (64 - nk));
+  m.w1 = nk > 64 ? (a.w1 & b.w1 & (ones >> (128 - nk))) : 0ull;
+  if ((m.w0 | m.w1) == 0ull) m.w0 = 1ull;
+  return m;
+}
+LMM_HD inline bool emul_mask_empty(EmulMask m) { return (m.w0 | m.w1) == 0ull; }
+LMM_HD inline int emul_mask_count(EmulMask m) { return __builtin_popcountll(m.w0) + __builtin_popcountll(m.w1); }
+LMM_HD inline int emul_mask_first(EmulMask m) { return m.w0 != 0ull ? __builtin_ctzll(m.w0) : 64 + __builtin_ctzll(m.w1); }      // m not empty
+LMM_HD inline EmulMask emul_mask_pop(EmulMask m) {      // m without its first bit; m not empty
+  if (m.w0 != 0ull) m.w0 &= m.w0 - 1ull; else m.w1 &= m.w1 - 1ull;
+  return m;
+}
+
 // ceil(log2 amax) for a finite amax > 0
 LMM_HD inline int emul_row_exp(double amax) {
   int q;

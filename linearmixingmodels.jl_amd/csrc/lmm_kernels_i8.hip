@@ -4,14 +4,16 @@
 //      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows (inside a factorisation
 //      the maxima outlive the update, and a later update reads them for the columns it shares: emul_amax_fold_kernel);
 //   2. emul_gemm_kernel: one int8 SYRK-shaped GEMM per (matrix, modulus) on 256 x 256 tiles of the lower trapezoid, int32
-//      accumulators, reduced mod p to one byte per output, as a persistent kernel (tools/i8_gemm_probe.hip holds a copy,
-//      i8_syrk_mod_kernel_ps with ABL = 6, beside the loops and kernels this one replaced; the probe stands alone: a change here
-//      has to be made there too before its numbers speak for this kernel);
+//      accumulators, reduced mod p to one byte per output, as a persistent kernel whose tiles walk only the K blocks that are live
+//      (not all zeros) in both operands (tools/i8_gemm_probe.hip holds a copy of the kernel without that skip,
+//      i8_syrk_mod_kernel_ps with ABL = 6, beside the loops and kernels this one replaced; the probe stands alone: its numbers
+//      speak for a K step and a tile's fixed cost, not for a level's time);
 //   3. emul_combine_kernel: CRT reconstruction in Float64 (lmm_emul.h) and C_ij -= X 2^(e_i + e_j - 2b) for i >= j.
 // Integer sums are exact in any order: the result is bitwise reproducible.
 #include "lmm_internal.h"
 #include "lmm_emul.h"
 #include <algorithm>
+#include <cstdlib>
 #include <map>
 #include <utility>
 #include <vector>
@@ -53,10 +55,15 @@ __global__ __launch_bounds__(256) void emul_amax_fold_kernel(EmulAmaxKeep k, int
 // of 130 (16.6 KB: nine workgroups fit on a CU).  It then takes 4 consecutive k of two rows from LDS, forms the residues
 // (emul_residues: constants folded into the instructions) and stores one dword per modulus straight to the K-contiguous int8 rows
 // R[(z NMOD + t) Mp + i][k]: 32 lanes write 128 contiguous bytes.  Rows M .. Mp - 1 (padding up to the GEMM tile) get zero residues.
+// The barrier between the two halves also ORs "one of my integers is not zero" over the workgroup, and one thread then sets the bit of
+// this K block in the live mask of its 256-row tile row (lmm_emul.h; zeroed, or filled with ones, on the stream before this kernel).
+// The bit follows the truncated integers: a row with a NaN or an infinity and the padding rows are zeros here.  Every residue is still
+// written: a live block of 256 rows may hold dead pieces of 16, which the GEMM reads.
 constexpr int CV_ROWS = 16, CV_K = 128, CV_PITCH = 130;
 template <int NMOD>
 __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
-                                                           const unsigned long long* __restrict__ amax, int as, int8_t* __restrict__ R, double* sc, int* ex) {
+                                                           const unsigned long long* __restrict__ amax, int as, int8_t* __restrict__ R, double* sc, int* ex,
+                                                           unsigned long long* masks) {
   __shared__ long long lds[CV_ROWS * CV_PITCH];
   const int tid = threadIdx.x, ti = tid & 15, tk = tid >> 4, z = blockIdx.z;
   const int i = blockIdx.x * CV_ROWS + ti, k0 = blockIdx.y * CV_K;
@@ -73,9 +80,15 @@ __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, s
   double a[CV_K / 16];
 #pragma unroll
   for (int s = 0; s < CV_K / 16; ++s) a[s] = live ? P[(size_t)(16 * s) * ld] : 0.0;
+  long long any = 0;
 #pragma unroll
-  for (int s = 0; s < CV_K / 16; ++s) lds[ti * CV_PITCH + tk + 16 * s] = emul_trunc(a[s], bits - e);
-  __syncthreads();
+  for (int s = 0; s < CV_K / 16; ++s) {
+    const long long v = emul_trunc(a[s], bits - e);
+    lds[ti * CV_PITCH + tk + 16 * s] = v;
+    any |= v;
+  }
+  if (__syncthreads_or(any != 0) && tid == 0)
+    atomicOr(&masks[((size_t)z * (Mp / TILE) + blockIdx.x / (TILE / CV_ROWS)) * LMM_EMUL_MASK_WORDS + (blockIdx.y >> 6)], 1ull << (blockIdx.y & 63));
   const int kg = tid & 31;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -97,11 +110,11 @@ __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, s
 }
 template <int NMOD>
 void launch_convert(int nmod, dim3 grid, hipStream_t st, const BatchPtr& P, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
-                    const unsigned long long* amax, int as, int8_t* R, double* sc, int* ex) {
+                    const unsigned long long* amax, int as, int8_t* R, double* sc, int* ex, unsigned long long* masks) {
   if constexpr (NMOD > LMM_EMUL_MINMOD) {
-    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex);
+    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks);
   }
-  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex);
+  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks);
 }
 
 // lower-trapezoid tiles in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles share at most 12 operand panels
@@ -205,8 +218,15 @@ __device__ __forceinline__ void emul_transpose4(unsigned (&w)[4]) {
 //   too and nothing here relies on how stores retire relative to loads: the first Y after an epilogue waits for vmcnt(0), once per
 //   tile.  A load is 3 (A) or 4 (B) phases old when it is waited for, and Y never empties the queue inside a tile.
 //   The prologue (once per workgroup) stages 0, waits, and stages 1 if the walk has a second stage at all.
+//
+// Zero skip: a tile's K steps are not all K / 128 blocks but the blocks that are live in both of its operands (the convert's masks,
+// emul_live_stages in lmm_emul.h), in increasing k: a block of 256 rows x 128 k whose truncated integers are all zero adds exactly
+// zero to every accumulator.  The cursor's k offset is the next set bit of its tile's list and the MFMA loop runs popcount(list)
+// times, both from the same helper on the same two mask words, which are loaded with the tile coordinates, one tile ahead.  Nothing
+// above asks which k a stage holds or how many stages a tile has (>= 1 is kept: an empty list becomes block 0), so the phase table, the
+// barriers and the counts stand as they are.  All-ones masks (lmm_dev_set_emul_zero_skip(0)) give the full walk.
 __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
-                                                           int nids, int Mp, int Np, int K, EmulConst c) {
+                                                           int nids, int Mp, int Np, int K, EmulConst c, const unsigned long long* __restrict__ masks) {
   __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
   // the walk of this workgroup: ids first, first + step, .. (cnt of them) of its XCD's range; fewer than 8 workgroups split the ids
@@ -226,18 +246,30 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
   }
   // the staging cursor: operand panels of the cn-th work id of the walk, next k offset ck; (pitem, pt) is the (cn + 1)-th work id,
   // loaded one tile ahead so that stepping into it waits for no load
+  // The stages of a tile are the live K blocks of both its operands (emul_live_stages, lmm_emul.h): cm holds the ones the cursor has
+  // not issued yet, ck is the first of them; pm is the list of the (cn + 1)-th work id, loaded with its coordinates.
   const int8_t* cA = nullptr;
   const int8_t* cB = nullptr;
   int cn = 0, ck = 0, pitem = 0;
   int2 pt = make_int2(0, 0);
+  EmulMask cm{0, 0}, pm{0, 0};
+  const int tr = Mp / TILE, nkb = K / BK;
+  auto live_of = [&](int item, int2 t) {
+    const unsigned long long* mz = masks + (size_t)(item / c.nmod) * tr * LMM_EMUL_MASK_WORDS;
+    const EmulMask a{mz[t.x * LMM_EMUL_MASK_WORDS], mz[t.x * LMM_EMUL_MASK_WORDS + 1]}, b{mz[t.y * LMM_EMUL_MASK_WORDS], mz[t.y * LMM_EMUL_MASK_WORDS + 1]};
+    return emul_live_stages(a, b, nkb);
+  };
   auto cursor_peek = [&](int idn) {
     pitem = idn / ntiles;
     pt = tiles[idn - pitem * ntiles];
+    pm = live_of(pitem, pt);
   };
   auto cursor_tile = [&]() {
     const int8_t* Rb = R + (size_t)pitem * Mp * K;
     cA = Rb + (size_t)pt.x * TILE * K;
     cB = Rb + (size_t)pt.y * TILE * K;
+    cm = pm;
+    ck = emul_mask_first(cm) * BK;
     if (cn + 1 < cnt) cursor_peek(first + (cn + 1) * step);
   };
   // piece q (0..3: A, 4..7: B) of the cursor's stage into buffer buf; the cursor moves on after piece 3, the last one issued
@@ -246,11 +278,11 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
     if (q < 4) glds16(cA + ck + roff[q], base + q * 1024);
     else glds16(cB + ck + roff[q - 4], base + TILE * BK + (q - 4) * 1024);
     if (q == 3) {
-      ck += BK;
-      if (ck == K) {
-        ck = 0; ++cn;
+      cm = emul_mask_pop(cm);
+      if (emul_mask_empty(cm)) {
+        ++cn;
         if (cn < cnt) cursor_tile();
-      }
+      } else ck = emul_mask_first(cm) * BK;
     }
   };
   auto stage_next = [&](int buf) {      // cn < cnt: a whole stage at once (the prologue)
@@ -259,7 +291,7 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
 #pragma unroll
     for (int q = 0; q < 4; ++q) piece(buf, q);
   };
-  const int nk = K / BK, frow = lane & 15, fk = lane >> 4;
+  const int frow = lane & 15, fk = lane >> 4;
   // byte offset of a fragment in its stage: (row 128) + ((ks 4 + fk) ^ (row >> 1) & 7) 16 with row = 16 m + frow (+ the wave's first
   // row, a multiple of 64): the swizzle is (frow >> 1), and ks = 1 flips bit 6 of the offset
   const int offA = (wr * 128 + frow) * BK + ((fk ^ (frow >> 1)) << 4), offB = TILE * BK + (wc * 64 + frow) * BK + ((fk ^ (frow >> 1)) << 4);
@@ -288,11 +320,20 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
 #define EMUL_PIN() __builtin_amdgcn_sched_barrier(0)
   int par = 0;      // s & 1
   bool stored = false;      // an epilogue's stores have been issued since the last wait for vmcnt
+  // the MFMA side: coordinates and stage count of the next work id, loaded one tile ahead like the cursor's
+  int nitem = first / ntiles;
+  int2 nt = tiles[first - nitem * ntiles];
+  int nnk = emul_mask_count(live_of(nitem, nt));
   for (int n = 0, id = first; n < cnt; ++n, id += step) {
-    // what the epilogue of this work id needs, loaded above its K loop
-    const int item = id / ntiles;
-    const int2 t = tiles[id - item * ntiles];
+    // what this work id's K loop and epilogue need
+    const int item = nitem, nk = nnk;
+    const int2 t = nt;
     const int p = c.p[item % c.nmod];
+    if (n + 1 < cnt) {
+      nitem = (id + step) / ntiles;
+      nt = tiles[id + step - nitem * ntiles];
+      nnk = emul_mask_count(live_of(nitem, nt));
+    }
     for (int kt = 0; kt < nk; ++kt, par ^= 1) {
       const int8_t* cur = lds + par * STAGE_BYTES;
       const int8_t* nxt = lds + (par ^ 1) * STAGE_BYTES;
@@ -423,17 +464,29 @@ void launch_combine(int nmod, dim3 grid, hipStream_t st, const BatchPtr& C, int 
 }
 
 int g_emul_gemm_wgs = 0;      // emul_set_gemm_workgroups: 0 = one workgroup per CU
+int g_emul_zero_skip = -1;    // emul_set_zero_skip: -1 = LMM_EMUL_ZERO_SKIP (read once; default on)
+
+bool emul_zero_skip_on() {
+  if (g_emul_zero_skip < 0) {
+    const char* e = getenv("LMM_EMUL_ZERO_SKIP");
+    g_emul_zero_skip = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_emul_zero_skip != 0;
+}
 
 }  // namespace
 
 void emul_set_gemm_workgroups(int wgs) { g_emul_gemm_wgs = wgs; }
+void emul_set_zero_skip(int on) { g_emul_zero_skip = on < 0 ? -1 : (on ? 1 : 0); }
 
 // C_m (M x N at C.p[m] + offC, ldc) -= P_m P_m[0:N]' for the panels P_m (M x K at P.p[m] + offP, ldp), m < nb, lower trapezoid
 // (i >= j) only, in groups of G matrices through `scratch` (emul_scratch_bytes(M, N, K, G, nmod) bytes).  Returns the first HIP
 // error of its host-side calls (nothing is launched after one).  keep: the row maxima go to an array of the caller's, for all nb matrices
-// before the first group, and start from what earlier updates found (EmulAmaxKeep, lmm_internal.h).
+// before the first group, and start from what earlier updates found (EmulAmaxKeep, lmm_internal.h).  masks: emul_mask_bytes(M, G) bytes
+// for the live K blocks of a group's panels (lmm_emul.h), set on the stream before each convert: to zero, or to ones with the zero
+// skip switched off.
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
-                              int G, int nmod, void* scratch, hipStream_t st, const EmulAmaxKeep* keep) {
+                              int G, int nmod, void* scratch, unsigned long long* masks, hipStream_t st, const EmulAmaxKeep* keep) {
   static EmulConst consts[LMM_EMUL_MAXMOD + 1];
   if (consts[nmod].nmod != nmod) consts[nmod] = emul_make_const(nmod);
   const EmulConst& c = consts[nmod];
@@ -465,9 +518,11 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
       if (err != hipSuccess) return err;
       emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, K, amax);
     }
-    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, am, as, R, sc, ex);
+    err = hipMemsetAsync(masks, emul_zero_skip_on() ? 0 : 0xFF, emul_mask_bytes(M, gc), st);
+    if (err != hipSuccess) return err;
+    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, am, as, R, sc, ex, masks);
     const int nids = ntiles * gc * nmod;
-    emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, ntiles, nids, L.Mp, L.Np, K, c);
+    emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, ntiles, nids, L.Mp, L.Np, K, c, masks);
     launch_combine<LMM_EMUL_MAXMOD>(nmod, dim3((M + 1023) / 1024, N, gc), st, C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);
   }
   return hipSuccess;

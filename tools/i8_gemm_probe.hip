@@ -11,6 +11,9 @@
 // Both operands are fragment-loaded the same way (lane l: row l & 31 or l & 15, 16 consecutive k), so the k order inside an
 // MFMA is the same permutation for A and B whatever the hardware's k map is; the row/column map is checked with exact
 // asymmetric integer data (full check at a small shape, sampled check at every timed shape).
+// NOTE: i8_syrk_mod_kernel_ps here is the library's emul_gemm_kernel as it was BEFORE the zero skip: every tile walks
+// all K / 128 blocks, on dense random operands.  It still speaks for the cost of a K step and for the fixed cost of a tile, which the
+// skip leaves alone; it no longer speaks for the library's time at a level, which depends on how many blocks of its panels are live.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
