@@ -736,6 +736,19 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
  *   lmm_dev_statespace_grad_sho : the same block with grad_theta = {d lml / d variance, d lml / d lengthscale, d lml / d quality} (3
  *                    values; the third is 0 for a Matern latent): lmm_dev_statespace_grad keeps its two-value output, which cannot
  *                    carry an SHO latent's quality.
+ *   lmm_oilmm_logpdf_grad_statespace_x : lmm_oilmm_logpdf_grad_statespace with one more output, grad_x (n values in the order of the
+ *                    sorted x, host or device; may be NULL): d logpdf / d x_t, in O(n).  The value depends on x through the spacings
+ *                    dt_t = x_t - x_{t-1} alone, and spacing t through the predicted state (mp, Pp) of point t alone: with the
+ *                    smoothed state (ms, Ps) of point t, delta = ms - mp and F the drift of the latent's SDE (dA / dt = F A),
+ *                      g_t = (Pp^-1 delta)' F mp + tr(Pp^-1 (delta delta' + Ps - Pp) Pp^-1 F (Pp - Pinf)),   g_0 = g_n = 0,
+ *                    is d lml_l / d dt_t, and d lml_l / d x_t = g_t - g_{t+1}.  The smoother evaluates g_t when it steps from point t
+ *                    to point t - 1 (nothing is stored but the n values per latent); the latents are added in their order, no
+ *                    atomics.  grad_x is exactly 0 at a point without any observation.  Every other output is bitwise that of
+ *                    lmm_oilmm_logpdf_grad_statespace, whose refusals apply in their order; NaN in y is served (x does not enter
+ *                    the projection, so unlike grad_S and grad_U nothing is refused).  Partial sums over the shard.
+ *   lmm_dev_statespace_grad_x : the building block beside lmm_dev_statespace_grad (DEVICE pointers throughout; gp on the host, its mean
+ *                    not read; a Matern or an SHO latent, whose tag carries its quality): grad_x (n) = d lml / d x_t of one latent
+ *                    with noise w (+Inf: unobserved, where grad_x is exactly 0) and data r.  chunk as for lmm_dev_statespace_filter.
  *   lmm_oilmm_rand_statespace : rand in O(n), exact: joint samples of the prior (y == NULL) or of the posterior given y, at the n inputs,
  *                    from caller-supplied standard normals.  The prior path of a latent is the recursion s_0 = chol(Pinf) zeta_0,
  *                    s_t = A(dt_t) s_{t-1} + chol(Q(dt_t)) zeta_t, f_t = (s_t)_1 (chol: the lower factor with non-negative diagonal;
@@ -778,6 +791,13 @@ int lmm_dev_statespace_grad(const double* x, int n, const lmm_gp_t* gp, const do
                             double* lml, double* grad_r, double* grad_w, double* grad_theta);
 int lmm_dev_statespace_grad_sho(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
                                 double* lml, double* grad_r, double* grad_w, double* grad_theta);
+int lmm_oilmm_logpdf_grad_statespace_x(const double* x, int n, const double* y, int p,
+                                       const double* U, const double* S, int m, double sigma2,
+                                       const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                       double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                                       lmm_gp_grad_t* grad_gps, double* grad_x);
+int lmm_dev_statespace_grad_x(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
+                              double* grad_x);
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
                               const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,
@@ -815,6 +835,15 @@ int lmm_dev_statespace_sample_posterior(const double* x, int n, const lmm_gp_t* 
  *                    ns x p by outputs, host or device; var may be NULL.  Partial sums over the handle's shard.  post, xs or mean NULL
  *                    or ns < 1 -> LMM_ERR_ARG; a NaN or +-Inf in xs -> LMM_ERR_ARG with the first such index in lmm_last_error_detail's
  *                    `info`, before the search runs; the fp32 compute mode -> LMM_ERR_UNSUPPORTED.
+ *   lmm_oilmm_statespace_post_mean_and_var_grad_xs : the pullback of lmm_oilmm_statespace_post_mean_and_var to the queries: grad_xs[q]
+ *                    (ns values, host or device) = d / d xs_q of sum(dmean * mean) + sum(dvar * var) for cotangents dmean, dvar (ns x p
+ *                    by outputs, host or device; either may be NULL, both NULL -> LMM_ERR_ARG).  A Matern32, Matern52 or SHO latent
+ *                    carries f' as its second state component, so d mean_l / d s = m[1] and d var_l / d s = 2 P[0][1] of the state
+ *                    the query computes anyway; Matern12 differentiates its predict-then-smooth step in closed form (at a query
+ *                    equal to a training input its mean has a kink: the derivative is that of the side the search sorts the query
+ *                    to, behind every copy).  grad_xs[q] = sum_l (sum_o dmean[o, q] H[o, l]) d mean_l + (sum_o dvar[o, q] H[o, l]^2)
+ *                    d var_l, latents in order; a query's entry depends on no other query (bitwise).  The added sigma2 does not
+ *                    depend on xs.  post, xs or grad_xs NULL or ns < 1 -> LMM_ERR_ARG; xs checked as there.
  *   lmm_dev_statespace_states, lmm_dev_statespace_interp : building blocks exported for tests (DEVICE pointers; one latent, gp on the
  *                    host, its mean is not read; chunk as for lmm_dev_statespace_filter).  states: fstate, sstate, each
  *                    n x (D + D (D + 1) / 2) in the layout above, from per-point noise w and data r.  interp: mean, var (ns each), the
@@ -829,6 +858,8 @@ int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* 
 int lmm_statespace_post_destroy(lmm_ss_post_t* post);
 int lmm_oilmm_statespace_post_mean_and_var(const lmm_ss_post_t* post, const double* xs, int ns, int add_noise,
                                            double* mean, double* var);
+int lmm_oilmm_statespace_post_mean_and_var_grad_xs(const lmm_ss_post_t* post, const double* xs, int ns,
+                                                   const double* dmean, const double* dvar, double* grad_xs);
 int lmm_dev_statespace_states(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
                               double* fstate, double* sstate);
 int lmm_dev_statespace_interp(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate,

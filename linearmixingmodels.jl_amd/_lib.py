@@ -36,6 +36,7 @@ SYMBOLS = [
     "lmm_oilmm_elbo_grad", "lmm_dev_sparse_grad",
     "lmm_oilmm_logpdf_statespace", "lmm_oilmm_mean_and_var_statespace", "lmm_dev_statespace_filter", "lmm_dev_statespace_smooth",
     "lmm_oilmm_logpdf_grad_statespace", "lmm_dev_statespace_grad", "lmm_dev_statespace_grad_sho",
+    "lmm_oilmm_logpdf_grad_statespace_x", "lmm_dev_statespace_grad_x", "lmm_oilmm_statespace_post_mean_and_var_grad_xs",
     "lmm_oilmm_rand_statespace", "lmm_dev_statespace_sample", "lmm_dev_statespace_sample_posterior",
     "lmm_oilmm_statespace_posterior_create", "lmm_statespace_post_destroy", "lmm_oilmm_statespace_post_mean_and_var",
     "lmm_dev_statespace_states", "lmm_dev_statespace_interp", "lmm_dev_statespace_interp_layout",
@@ -69,6 +70,9 @@ STATESPACE_ARGTYPES = {
     "lmm_oilmm_logpdf_grad_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "lmm_dev_statespace_grad": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
     "lmm_dev_statespace_grad_sho": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "lmm_oilmm_logpdf_grad_statespace_x": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "lmm_dev_statespace_grad_x": [_P, _I, _P, _P, _P, _I, _P],
+    "lmm_oilmm_statespace_post_mean_and_var_grad_xs": [_P, _P, _I, _P, _P, _P],
     "lmm_oilmm_rand_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "lmm_dev_statespace_sample": [_P, _I, _P, _P, _I, _I, _P],
     "lmm_dev_statespace_sample_posterior": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P],

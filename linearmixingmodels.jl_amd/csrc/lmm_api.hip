@@ -5060,6 +5060,7 @@ struct SSGradOut {
   double* alpha; double* grad_w;       // device, [latent][n]: alpha_t = -d lml / d r_t, d lml / d w_t
   double* sums;                        // host, 4 per latent: sum_t alpha_t, w_t alpha_t^2, w_t c_t, d lml / d w_t
   double* gtheta;                      // host, 3 per latent: d lml / d variance, d lml / d lengthscale, d lml / d quality (SHO; else 0)
+  double* gdt = nullptr;               // device, [latent][n] (nullptr: not computed): d lml / d (x_t - x_{t-1}), 0 at t = 0
 };
 // One entry of the latent dimension of a launch: a latent with its own noise and data (n values each, on the device).  Samples ride
 // through the filter and smoother as several entries of one latent, with the same w and their own r.
@@ -5102,6 +5103,7 @@ static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, i
     if (keep) { const size_t off = ss_keep_offset(es, k0, n); a.fkeep = keep->fstate + off; a.sstate = keep->sstate + off; }
     a.smean = (smooth && smean) ? smean + (size_t)k0 * n : nullptr; a.svar = (smooth && svar) ? svar + (size_t)k0 * n : nullptr;
     a.dagg = dagg.p; a.dpart = dpart.p;
+    a.gdt = (go && go->gdt) ? go->gdt + (size_t)k0 * n : nullptr;
     for (int j = 0; j < nb; ++j) {
       ss_fill_lat(a.lat[j], *es[k0 + j].L, add_mean);
       a.lat[j].w = es[k0 + j].w; a.lat[j].r = es[k0 + j].r;
@@ -5293,10 +5295,12 @@ int lmm_oilmm_mean_and_var_statespace(const double* x, int n, const double* y, i
 // forward-mode pass d lml / d variance and d lml / d lengthscale (ss_core with SSGradOut); the front end's chain rule is that of
 // lmm_oilmm_elbo_grad for complete data and that of oilmm_grad_missing_core for data with NaN (then without S and U).  *out_logpdf is
 // the sum of lmm_oilmm_logpdf_statespace in its order.  Partial sums over the shard; any output may be NULL.
-int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
-                                     double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
-                                     double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
-                                     lmm_gp_grad_t* grad_gps) {
+// grad_x (lmm_oilmm_logpdf_grad_statespace_x; n values in the order of x, host or device; may be nullptr): the smoother's launches also
+// write every spacing's d lml_l / d dt (SSGradOut::gdt), and launch_ss_grad_x adds the latents' d lml_l / d x_t = g_t - g_{t+1} in
+// latent order.  The regulariser and the projection do not depend on x.
+static int ss_logpdf_grad(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                          const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out_logpdf, double* grad_y,
+                          double* grad_sigma2, double* grad_S, double* grad_U, lmm_gp_grad_t* grad_gps, double* grad_x) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
@@ -5309,8 +5313,17 @@ int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, in
   DevOut gy(grad_y, (size_t)n * p);
   std::vector<double> lml(msa, 0.0), sums(4 * (size_t)msa, 0.0), gth(3 * (size_t)msa, 0.0);
   Buf<double> sm((size_t)n * msa), sv((size_t)n * msa), al((size_t)n * msa), gw((size_t)n * msa);
-  const SSGradOut go{al.p, gw.p, sums.data(), gth.data()};
+  DevOut gx(grad_x, (size_t)n);
+  Buf<double> gd;
+  if (grad_x) gd = Buf<double>((size_t)n * msa);
+  const SSGradOut go{al.p, gw.p, sums.data(), gth.data(), gd.p};
   if (int rc = ss_core(xd.p, n, lts + l0, ms, Fr.w.p, Fr.r.p, 0, lml.data(), nullptr, nullptr, sm.p, sv.p, false, &go)) return rc;
+  if (grad_x) {
+    launch_ss_grad_x(gd.p, Fr.w.p, n, ms, gx.p, st0);
+    HIPCHK(hipGetLastError());
+    gx.finish(st0);
+    HIPCHK(hipStreamSynchronize(st0));
+  }
   double total = 0.0;
   for (int k = 0; k < ms; ++k) total += lml[k];
   if (with_regulariser) total += Fr.reg;
@@ -5403,6 +5416,22 @@ int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, in
   LMM_CATCH
 }
 
+int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                     double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                     double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                                     lmm_gp_grad_t* grad_gps) {
+  return ss_logpdf_grad(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, out_logpdf, grad_y, grad_sigma2,
+                        grad_S, grad_U, grad_gps, nullptr);
+}
+
+int lmm_oilmm_logpdf_grad_statespace_x(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                       double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                       double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                                       lmm_gp_grad_t* grad_gps, double* grad_x) {
+  return ss_logpdf_grad(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, out_logpdf, grad_y, grad_sigma2,
+                        grad_S, grad_U, grad_gps, grad_x);
+}
+
 // Building blocks for tests: ONE latent from device pointers, per-point noise w (+Inf: unobserved) and data r; the latent's mean is
 // not read (r is the residual).  chunk: points per thread (0: the library's plan).
 // The preamble of these one-latent entry points: `bad` (a NULL pointer or a size out of range) refuses the arguments, then nsamples
@@ -5485,6 +5514,27 @@ int lmm_dev_statespace_grad_sho(const double* x, int n, const lmm_gp_t* gp, cons
   return ss_dev_grad(x, n, gp, w, r, chunk, lml, grad_r, grad_w, grad_theta, 3);
 }
 
+// Building block for tests beside lmm_dev_statespace_grad: grad_x (n values, device) = d lml / d x_t of ONE latent, Matern or SHO (the
+// tag carries an SHO latent's quality, as in lmm_dev_statespace_grad_sho); exactly 0 where w = +Inf.
+int lmm_dev_statespace_grad_x(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* grad_x) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = ss_dev_prepare(!x || !gp || !w || !r || !grad_x || n <= 0 || chunk < 0, x, n, gp, ls)) return rc;
+  const Latent* lts = ls->lat.data();
+  hipStream_t st0 = g.streams[0];
+  Buf<double> sm(n), sv(n), al(n), gw(n), gd(n);
+  double hl = 0.0, sums[4], gth[3];
+  const SSGradOut go{al.p, gw.p, sums, gth, gd.p};
+  if (int rc = ss_core(x, n, lts, 1, w, r, chunk, &hl, nullptr, nullptr, sm.p, sv.p, false, &go)) return rc;
+  launch_ss_grad_x(gd.p, w, n, 1, grad_x, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
 // ---- the posterior object (DESIGN.md 4.18 "Posterior object") --------------------------------------------------------------------
 // One O(n) conditioning pass keeps, per latent of the shard, the filtered and the full smoothed states; a query at new inputs is then
 // one thread per (query, latent) (ss_interp_kernel) and the mixing of lmm_oilmm_mean_and_var_statespace.
@@ -5501,8 +5551,9 @@ struct lmm_ss_post {
 // The zero-mean (add_mean: plus the latent's mean) marginals of the ms latents lts[0 .. ms) at the ns queries xsd from their stored
 // states (latent k's block off[k] doubles into fstate / sstate): ml, vl [latent][ns] on the device (vl may be nullptr).  Launches
 // group consecutive latents of one model, LMM_MAX_BATCH at the most.  Queues on streams[0] and does not wait.
+// dx: ml, vl (both given) take the derivatives of the two with respect to the query instead (launch_ss_interp_dx).
 static void ss_interp_latents(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
-                       const double* xsd, int ns, bool add_mean, double* ml, double* vl, bool point_major = true) {
+                       const double* xsd, int ns, bool add_mean, double* ml, double* vl, bool point_major = true, bool dx = false) {
   hipStream_t st0 = g.streams[0];
   const auto no_buffers = [](int, int, int) { return size_t(1); };       // a launch allocates nothing: LMM_MAX_BATCH alone limits it
   ss_for_launches(ms, 0, [&](long long k) -> const Latent& { return lts[k]; }, no_buffers, [&](long long e0, int nb, int model, int D) {
@@ -5513,8 +5564,10 @@ static void ss_interp_latents(const double* xd, int n, const Latent* lts, int ms
     a.state_stride = (size_t)ss_state_comps(D) * n;
     a.comp_stride = point_major ? 1 : (size_t)n; a.point_stride = point_major ? (size_t)ss_state_comps(D) : 1;
     a.mean = ml + (size_t)k0 * ns; a.var = vl ? vl + (size_t)k0 * ns : nullptr;
+    if (dx) { a.dmean = a.mean; a.dvar = a.var; a.mean = nullptr; a.var = nullptr; }
     for (int j = 0; j < nb; ++j) ss_fill_lat(a.lat[j], lts[k0 + j], add_mean);
-    launch_ss_interp(a, model, nb, st0);
+    if (dx) launch_ss_interp_dx(a, model, nb, st0);
+    else launch_ss_interp(a, model, nb, st0);
   });
   HIPCHK(hipGetLastError());
 }
@@ -5585,6 +5638,35 @@ int lmm_oilmm_statespace_post_mean_and_var(const lmm_ss_post_t* post, const doub
   mix_marginals(ml.p, ns, ms, P->H.p, p, 1, 0.0, 0.0, mo.p, st0);
   if (var_out) mix_marginals(vl.p, ns, ms, P->H.p, p, 2, kDefaultJit.default_jitter, add_noise ? P->sigma2 : 0.0, vo.p, st0);
   mo.finish(st0); vo.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// The pullback of lmm_oilmm_statespace_post_mean_and_var to the queries: per (query, latent) the derivatives of the latent's mean and
+// variance (ss_interp_dx_kernel), contracted with H and the cotangents in latent order (launch_ss_contract_dx).  The added sigma2 does
+// not depend on xs.
+int lmm_oilmm_statespace_post_mean_and_var_grad_xs(const lmm_ss_post_t* post, const double* xs, int ns, const double* dmean,
+                                                   const double* dvar, double* grad_xs) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !xs || !grad_xs || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
+  if (!dmean && !dvar) return fail(LMM_ERR_ARG, "state-space posterior: dmean and dvar are both NULL (one cotangent is needed)");
+  if (g_f32) return ss_refuse_f32();
+  const lmm_ss_post* P = post;
+  const int p = P->p, ms = P->l1 - P->l0;
+  hipStream_t st0 = g.streams[0];
+  DevIn xsd(xs, (size_t)ns, st0);
+  if (int rc = ss_check_finite(xsd.p, ns)) return rc;
+  DevIn dm(dmean, (size_t)ns * p, st0), dv(dvar, (size_t)ns * p, st0);
+  Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
+  ss_interp_latents(P->x.p, P->n, P->ls->lat.data() + P->l0, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, false, ml.p, vl.p, true,
+                    true);
+  DevOut go(grad_xs, (size_t)ns);
+  launch_ss_contract_dx(dm.p, dv.p, P->H.p, p, ms, ml.p, vl.p, ns, go.p, st0);
+  HIPCHK(hipGetLastError());
+  go.finish(st0);
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
   LMM_CATCH

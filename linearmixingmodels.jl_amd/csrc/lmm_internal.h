@@ -337,6 +337,8 @@ struct SSArgs {
   double* dagg;                               // nb * ss_dual_agg_elems(D, nch, seeds) doubles: the (value, tangent) aggregates (gradients only)
   double* dpart;                              // nb * seeds * nch tangents of the log-density partials (gradients only)
   SSLat lat[LMM_MAX_BATCH];
+  double* gdt;                                // d lml / d (x_t - x_{t-1}), [latent][n] with 0 at t = 0 (nullptr: not written; behind lat, so that
+                                              // the kernels from before it read their arguments where they did)
 };
 static_assert(sizeof(SSArgs) <= 4096, "SSArgs is passed by value: kernel arguments are limited to 4096 bytes");
 // The model of a launch: 1 / 2 / 3 = Matern12 / 32 / 52 (the state dimension), SS_MODEL_SHO = the damped oscillator (state dimension 2)
@@ -352,7 +354,11 @@ size_t ss_bwd_agg_elems(int D, int nch);
 // fold, scan, filter (and, lml != nullptr, lml[l] = latent l's log density) of nb latents of one model
 void launch_ss_filter(const SSArgs& a, int model, int nb, double* lml, hipStream_t st);
 // the same in reverse over the filtered states a.state: smoothed marginals into a.smean / a.svar
+// a.gdt != nullptr: and every spacing's d lml / d dt into a.gdt, from what the backward recursion holds when it steps from t + 1 to t
 void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st);
+// grad_x[t] = sum over the ms latents, in their order, of g_l[t] - g_l[t + 1] (g_l[n] = 0) where w_l[t] < +Inf, and exactly 0 where
+// it is not: d lml / d x_t from the spacings' derivatives g ([latent][n], SSArgs::gdt) and the noise w ([latent][n])
+void launch_ss_grad_x(const double* g, const double* w, int n, int ms, double* grad_x, hipStream_t st);
 // Gradients.  gtheta[NS l + s], NS = ss_model_seeds(model): d lml_l / d variance (s = 0), d lml_l / d lengthscale (s = 1) and, SHO,
 // d lml_l / d quality (s = 2) by the forward-mode (dual number) instantiation of fold, scan and filter; a.dagg and a.dpart are its workspace
 size_t ss_dual_agg_elems(int D, int nch, int nseeds);     // per latent, all seeds
@@ -391,9 +397,16 @@ struct SSInterpArgs {
   const double* fstate; const double* sstate; size_t state_stride, comp_stride, point_stride;
   double* mean; double* var;                  // [latent][ns]: first-component mean (+ lat.mean) and variance
   SSInterpLat lat[LMM_MAX_BATCH];
+  double* dmean; double* dvar;                // launch_ss_interp_dx only, [latent][ns]: their derivatives with respect to the query
 };
 // one thread per (query, latent) of nb latents of one model
 void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st);
+// the same threads write a.dmean, a.dvar (not nullptr) instead: d mean / d xs and d var / d xs per (query, latent); a.mean, a.var not read
+void launch_ss_interp_dx(const SSInterpArgs& a, int model, int nb, hipStream_t st);
+// grad_xs[q] = sum over the ms latents, in their order, of (sum_o dmean[q + o ns] H[o + l p]) dmu[l ns + q] + (sum_o dvar[q + o ns]
+// H[o + l p]^2) dv[l ns + q]; dmean or dvar may be nullptr (its term is left out), H is p x ms column-major; one thread per query
+void launch_ss_contract_dx(const double* dmean, const double* dvar, const double* H, int p, int ms, const double* dmu, const double* dv,
+                           int ns, double* grad_xs, hipStream_t st);
 // *flag (preset to INT_MAX) = the first t with xs_t NaN or +-Inf
 void launch_ss_finite(const double* xs, int ns, int* flag, hipStream_t st);
 // Sampling from the posterior object (DESIGN.md 4.18 "Sampling from the posterior object").  The window of the sorted queries xs: the

@@ -24,6 +24,10 @@
 // between them are a Markov chain that runs backwards, an affine recursion in the caller's normals again, so phases 1 - 3 run from the
 // right on SSAff<D> elements built from the stored states (ss_window_kernel, ss_pfold_kernel, the suffix scan with AffRevOp,
 // ss_ppath_kernel); nothing outside the queries' span is read.
+// Gradients with respect to locations: d lml / d x_t = g_t - g_{t+1} with g_t = d lml / d (x_t - x_{t-1}) local to one
+// transition (ss_input_grad); ss_rts_kernel<D, OSC, false, true> writes g while it steps through the points, ss_grad_x_kernel adds the
+// latents in order.  For the posterior object ss_interp_dx_kernel writes d mean / d s and d var / d s per (query, latent) and
+// ss_contract_dx_kernel contracts them with H and the cotangents, one thread per query, latents in order.  No atomics, no LDS.
 // Shared by the kernels (lmm_statespace.h): ss_chunk_range (a thread's run), ss_count_le / ss_count_lt (the binary searches) and
 // ss_load_state (a stored state in either layout); ss_lat_model makes the model of any *Lat struct.  On the host, ss_dispatch hands a
 // launch's model to a generic lambda as compile-time (D, OSC), and ss_phases is the fold - scan - restart sequence of every direction.
@@ -277,7 +281,10 @@ __global__ __launch_bounds__(SS_THREADS) void ss_bfold_kernel(SSArgs a) {
 
 // FULL: the whole smoothed state (without the latent's mean) goes to a.sstate as well, and the filtered state it was computed from to
 // a.fkeep, both point-major; a.smean may be nullptr.  A second instantiation, so that the code of the first is what it was.
-template <int D, bool OSC, bool FULL = false>
+// GX (a third, for the same reason): when the recursion steps from point t + 1 to point t it holds the filtered state of t and the
+// smoothed state of t + 1, which is all ss_input_grad takes: a.gdt[t + 1] = d lml / d (x_{t+1} - x_t), and a.gdt[0] = 0.  No state is
+// stored for it, and every entry of a.gdt is written by exactly one thread.
+template <int D, bool OSC, bool FULL = false, bool GX = false>
 __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
@@ -305,6 +312,11 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
     const bool last = t == a.n - 1;
     ss_load_state<D>(stt, a.n, 1, t, m, P);                   // component-major
     ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, el);
+    if constexpr (GX) {
+      double* gd = a.gdt + (size_t)z * a.n;
+      if (!last) gd[t + 1] = ss_input_grad<D>(M, a.x[t + 1] - a.x[t], m, P, ms, Ps);
+      if (t == 0) gd[0] = 0.0;
+    }
     ss_rts_step<D>(el, ms, Ps);
     if (!FULL || sm) sm[t] = ms[0] + L.mean;
     if (sv) sv[t] = Ps[0][0];
@@ -349,6 +361,73 @@ __global__ __launch_bounds__(SS_THREADS) void ss_interp_kernel(SSInterpArgs a) {
   ss_interp<D>(M, k > 0, d1, k < a.n, d2, m, P, ms, Ps);
   a.mean[(size_t)z * a.ns + q] = m[0] + L.mean;
   if (a.var) a.var[(size_t)z * a.ns + q] = P[0][0];
+}
+
+// ss_interp_kernel's threads, writing the derivatives of its two outputs with respect to the query instead (ss_interp_dx_state; Matern12:
+// ss_interp_dx_ou on ss_interp's inputs).  At a query equal to a training input they are those of the side the search sorts it to
+// (behind every copy), which matters for Matern12 alone: its posterior mean has a kink there.
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_interp_dx_kernel(SSInterpArgs a) {
+  const int q = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (q >= a.ns) return;
+  const SSInterpLat& L = a.lat[z];
+  const auto M = ss_lat_model<D, OSC>(L);
+  const double s = a.xs[q];
+  const int k = ss_count_le(a.x, 0, a.n, s);
+  double m[D], P[D][D], ms[D], Ps[D][D];
+  for (int i = 0; i < D; ++i) {
+    m[i] = 0.0; ms[i] = 0.0;
+    for (int j = 0; j < D; ++j) { P[i][j] = 0.0; Ps[i][j] = 0.0; }
+  }
+  double d1 = 0.0, d2 = 0.0;
+  if (k > 0) {
+    ss_load_state<D>(a.fstate + (size_t)z * a.state_stride, a.comp_stride, a.point_stride, k - 1, m, P);
+    d1 = s - a.x[k - 1];
+  }
+  if (k < a.n) {
+    ss_load_state<D>(a.sstate + (size_t)z * a.state_stride, a.comp_stride, a.point_stride, k, ms, Ps);
+    d2 = a.x[k] - s;
+  }
+  double dmu, dv;
+  if constexpr (D == 1) ss_interp_dx_ou(M, k > 0, d1, k < a.n, d2, m[0], P[0][0], ms[0], Ps[0][0], dmu, dv);
+  else {
+    ss_interp<D>(M, k > 0, d1, k < a.n, d2, m, P, ms, Ps);
+    ss_interp_dx_state<D>(m, P, dmu, dv);
+  }
+  a.dmean[(size_t)z * a.ns + q] = dmu;
+  a.dvar[(size_t)z * a.ns + q] = dv;
+}
+
+// one thread per query: the latents' derivatives contracted with H and the cotangents, latents in order (launch_ss_contract_dx)
+__global__ __launch_bounds__(256) void ss_contract_dx_kernel(const double* __restrict__ dmean, const double* __restrict__ dvar,
+                                                             const double* __restrict__ H, int p, int ms, const double* __restrict__ dmu,
+                                                             const double* __restrict__ dv, int ns, double* __restrict__ grad_xs) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= ns) return;
+  double acc = 0.0;
+  for (int l = 0; l < ms; ++l) {
+    double cm = 0.0, cv = 0.0;
+    for (int o = 0; o < p; ++o) {
+      const double h = H[o + (size_t)l * p];
+      if (dmean) cm += dmean[q + (size_t)o * ns] * h;
+      if (dvar) cv += dvar[q + (size_t)o * ns] * (h * h);
+    }
+    acc += cm * dmu[(size_t)l * ns + q] + cv * dv[(size_t)l * ns + q];
+  }
+  grad_xs[q] = acc;
+}
+
+// one thread per point: d lml / d x_t from the spacings' derivatives, latents in order (launch_ss_grad_x)
+__global__ __launch_bounds__(256) void ss_grad_x_kernel(const double* __restrict__ g, const double* __restrict__ w, int n, int ms,
+                                                        double* __restrict__ grad_x) {
+  const long long t = blockIdx.x * 256ll + threadIdx.x;
+  if (t >= n) return;
+  double acc = 0.0;
+  for (int l = 0; l < ms; ++l) {
+    const double* gl = g + (size_t)l * n;
+    if (w[(size_t)l * n + t] < INFINITY) acc += gl[t] - (t + 1 < n ? gl[t + 1] : 0.0);
+  }
+  grad_x[t] = acc;
 }
 
 // *flag = the smallest t with xs_t NaN or +-Inf, left at its initial value (INT_MAX) when every query is finite (ss_sorted_kernel's way)
@@ -658,7 +737,9 @@ void launch_ss_filter(const SSArgs& a, int model, int nb, double* lml, hipStream
 void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st) {
   ss_dispatch(model, [&](auto t) {
     typedef decltype(t) T;
-    ss_phases<T::D, SSBwd<T::D>, BwdOp, true>(ss_bfold_kernel<T::D, T::OSC>, a.sstate ? ss_rts_kernel<T::D, T::OSC, true> : ss_rts_kernel<T::D, T::OSC>,
+    ss_phases<T::D, SSBwd<T::D>, BwdOp, true>(ss_bfold_kernel<T::D, T::OSC>,
+                                              a.sstate ? ss_rts_kernel<T::D, T::OSC, true>
+                                                       : a.gdt ? ss_rts_kernel<T::D, T::OSC, false, true> : ss_rts_kernel<T::D, T::OSC>,
                                               a, 1, nb, a.bagg, st);
   });
 }
@@ -698,6 +779,22 @@ void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st) 
     typedef decltype(t) T;
     hipLaunchKernelGGL((ss_interp_kernel<T::D, T::OSC>), dim3((a.ns + SS_THREADS - 1) / SS_THREADS, 1, nb), dim3(SS_THREADS), 0, st, a);
   });
+}
+
+void launch_ss_interp_dx(const SSInterpArgs& a, int model, int nb, hipStream_t st) {
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    hipLaunchKernelGGL((ss_interp_dx_kernel<T::D, T::OSC>), dim3((a.ns + SS_THREADS - 1) / SS_THREADS, 1, nb), dim3(SS_THREADS), 0, st, a);
+  });
+}
+
+void launch_ss_contract_dx(const double* dmean, const double* dvar, const double* H, int p, int ms, const double* dmu, const double* dv,
+                           int ns, double* grad_xs, hipStream_t st) {
+  hipLaunchKernelGGL(ss_contract_dx_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, dmean, dvar, H, p, ms, dmu, dv, ns, grad_xs);
+}
+
+void launch_ss_grad_x(const double* g, const double* w, int n, int ms, double* grad_x, hipStream_t st) {
+  hipLaunchKernelGGL(ss_grad_x_kernel, dim3((n + 255) / 256), dim3(256), 0, st, g, w, n, ms, grad_x);
 }
 
 void launch_ss_pathwise(const double* r, const double* w, const double* f, const double* xi, size_t xi_stride, int n, int ms, int N,

@@ -480,6 +480,97 @@ SS_HD void ss_interp(const Mod& M, bool has_prev, double d1, bool has_next, doub
   ss_rts_step<D>(el, m, P);
 }
 
+// ---- gradients with respect to locations (DESIGN.md 4.18 "Gradients with respect to locations") --------------------------------------
+// The drift F of the model's SDE, dA / dt = F A: N - lam I (Matern), N - a I (oscillator)
+template <int D>
+SS_HD void ss_drift(const SSModel<D>& M, double F[D][D]) {
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) F[i][j] = M.N[i][j] - (i == j ? M.lam : 0.0);
+}
+template <int D>
+SS_HD void ss_drift(const SSOsc<double>& M, double F[D][D]) {
+  static_assert(D == 2, "the oscillator has a two-dimensional state");
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) F[i][j] = M.N[i][j] - (i == j ? M.a : 0.0);
+}
+
+// g = d lml / d dt of ONE transition: the spacing dt between point t - 1, with FILTERED state (m, P), and point t, with SMOOTHED state
+// (ms, Ps).  lml depends on dt only through the predicted state mp = A m, Pp = A P A' + Q of point t, with d mp / d dt = F mp and
+// d Pp / d dt = F (Pp - Pinf) + (Pp - Pinf) F' (dA / dt = F A and dQ / dt = -F (A Pinf A') - (A Pinf A') F'), and
+// d lml / d mp = Pp^-1 delta, d lml / d Pp = Pp^-1 (delta delta' + Ps - Pp) Pp^-1 / 2 with delta = ms - mp (Fisher's identity), so
+//   g = (Pp^-1 delta)' F mp + tr(Pp^-1 (delta delta' + Ps - Pp) Pp^-1 F (Pp - Pinf)).
+// The first lines are those of ss_bwd_element, which the smoother evaluates beside this for the same transition.
+template <int D, typename Mod>
+SS_HD double ss_input_grad(const Mod& M, double dt, const double m[D], const double P[D][D], const double ms[D], const double Ps[D][D]) {
+  double A[D][D], Q[D][D], T[D][D], Pp[D][D], Pi[D][D], F[D][D], G[D][D], X[D][D], Y[D][D], mp[D];
+  ss_AQ<D>(M, dt, A, Q);
+  ss_mm<D>(A, P, T);                          // A P
+  for (int i = 0; i < D; ++i)
+    for (int j = i; j < D; ++j) {
+      double q = Q[i][j];
+      for (int k = 0; k < D; ++k) q += T[i][k] * A[j][k];
+      Pp[i][j] = Pp[j][i] = q;
+    }
+  ss_inv_spd<D>(Pp, Pi);
+  ss_drift<D>(M, F);
+  for (int i = 0; i < D; ++i) {
+    double s = 0.0;
+    for (int k = 0; k < D; ++k) s += A[i][k] * m[k];
+    mp[i] = s;
+  }
+  for (int i = 0; i < D; ++i)                 // G = delta delta' + Ps - Pp
+    for (int j = 0; j < D; ++j) G[i][j] = (ms[i] - mp[i]) * (ms[j] - mp[j]) + (Ps[i][j] - Pp[i][j]);
+  double g = 0.0;
+  for (int i = 0; i < D; ++i) {
+    double s = 0.0, f = 0.0;
+    for (int k = 0; k < D; ++k) { s += Pi[i][k] * (ms[k] - mp[k]); f += F[i][k] * mp[k]; }
+    g += s * f;
+  }
+  ss_mm<D>(Pi, G, X);
+  ss_mm<D>(X, Pi, Y);                         // Pp^-1 G Pp^-1
+  for (int i = 0; i < D; ++i)                 // X = F (Pp - Pinf)
+    for (int j = 0; j < D; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < D; ++k) s += F[i][k] * (Pp[k][j] - M.Pinf[k][j]);
+      X[i][j] = s;
+    }
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) g += Y[i][j] * X[j][i];
+  return g;
+}
+
+// The derivative with respect to s of ss_interp's first-component mean and variance at the query s (d d1 / ds = 1, d d2 / ds = -1),
+// given ss_interp's OUTPUT (m, P) there.  A mean-square differentiable latent (D >= 2) carries f' as its second state component:
+// d E[f(s) | y] / ds = m[1] and d Var[f(s) | y] / ds = 2 P[0][1].
+template <int D>
+SS_HD void ss_interp_dx_state(const double m[D], const double P[D][D], double& dmu, double& dv) {
+  static_assert(D >= 2, "Matern12 has no derivative component: ss_interp_dx_ou");
+  dmu = m[D >= 2 ? 1 : 0];
+  dv = 2.0 * P[0][D >= 2 ? 1 : 0];
+}
+// Matern12 (D = 1, the Ornstein-Uhlenbeck process) has no such component; its predict-then-RTS step is differentiated in closed form.
+// In: ss_interp's INPUTS (the filtered state (m, P) of point k - 1, the smoothed state (ms, Ps) of point k).  With e1 = exp(-lam d1),
+// e2 = exp(-lam d2) and v = Pinf: mp = e1 m, Pp = v + e1^2 (P - v), so d mp = -lam mp and d Pp = -2 lam (Pp - v) (both 0 in front of
+// every training point, where the prior stands).  The prediction (mn, Pn) of point k does not depend on s, so with E = Pp e2 / Pn,
+// d E = (d Pp + lam Pp) e2 / Pn: d mean = d mp + d E (ms - mn) and d var = d Pp + 2 E d E (Ps - Pn).
+SS_HD void ss_interp_dx_ou(const SSModel<1>& M, bool has_prev, double d1, bool has_next, double d2, double m, double P, double ms,
+                           double Ps, double& dmu, double& dv) {
+  const double v = M.Pinf[0][0], lam = M.lam;
+  double mp = 0.0, Pp = v;
+  if (has_prev) {
+    const double e1 = exp(-lam * d1);
+    mp = e1 * m;
+    Pp = v + e1 * e1 * (P - v);
+  }
+  const double dmp = -lam * mp, dPp = -2.0 * lam * (Pp - v);
+  if (!has_next) { dmu = dmp; dv = dPp; return; }
+  const double e2 = exp(-lam * d2);
+  const double mn = e2 * mp, Pn = v + e2 * e2 * (Pp - v);
+  const double E = Pp * e2 / Pn, dE = (dPp + lam * Pp) * e2 / Pn;
+  dmu = dmp + dE * (ms - mn);
+  dv = dPp + 2.0 * E * dE * (Ps - Pn);
+}
+
 // ---- sampling: the prior path as an affine scan ------------------------------------------------------------------------------------
 // Lower Cholesky factor with non-negative diagonal of a symmetric positive SEMI-definite X (its lower triangle is read).  A pivot that
 // is not > 0 gives a zero column (its diagonal and everything below it), so X = 0 gives L = 0 exactly and a Q that rounding has made

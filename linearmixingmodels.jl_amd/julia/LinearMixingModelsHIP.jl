@@ -1126,10 +1126,11 @@ function ChainRulesCore.rrule(::typeof(AbstractGPs.elbo), vfe::VFE{<:ByOutputsFi
     return val[], elbo_pullback
 end
 
-# statespace_logpdf(fx, y) (lmm_oilmm_logpdf_grad_statespace; include/lmm_hip.h "state space"): cotangents for the latent GPs' variances,
+# statespace_logpdf(fx, y) (lmm_oilmm_logpdf_grad_statespace_x; include/lmm_hip.h "state space"): cotangents for the latent GPs' variances,
 # lengthscales and means, σ², y (0 at missing entries, in the caller's order of points) and, for complete data, H = (U, S), in the way
 # the logpdf rrules above are written and in O(n).  With `missing` or NaN in y the library builds no derivative through the per-point
-# projection, so H gets ZeroTangent, as in _logpdf_missing_rrule.  The inputs get no cotangent.
+# projection, so H gets ZeroTangent, as in _logpdf_missing_rrule.  The inputs fx.x get the library's d logpdf / d x (O(n) as well, in
+# the caller's order of points, 0 at points without observations; NaN in y is served), unless INPUT_GRADIENTS[] = false.
 function ChainRulesCore.rrule(::typeof(statespace_logpdf), fx::ByOutputsFill{HIPOILMM}, y::AbstractVector; with_regulariser::Bool=true)
     fs, H, σ², x = unpack(fx)
     isposterior(fs) && error("state-space inference is served on a prior OILMM only")
@@ -1139,19 +1140,23 @@ function ChainRulesCore.rrule(::typeof(statespace_logpdf), fx::ByOutputsFill{HIP
     val = Ref{Cdouble}(0.0); gσ = Ref{Cdouble}(0.0)
     gy = Vector{Float64}(undef, n * p); gS = Vector{Float64}(undef, m); gU = Matrix{Float64}(undef, p, m)
     gg = Vector{LmmGpGrad}(undef, m); gard = nothing
+    gx = INPUT_GRADIENTS[] ? Vector{Float64}(undef, n) : nothing
     _gps(fs.fs) do gps, tags
-        GC.@preserve xv yv U S gps gy gS gU gg check(ccall((:lmm_oilmm_logpdf_grad_statespace, liblmm), Cint,
+        GC.@preserve xv yv U S gps gy gS gU gg gx check(ccall((:lmm_oilmm_logpdf_grad_statespace_x, liblmm), Cint,
             (Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{LmmGp}, Cint, Cint, Cint,
-             Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}),
+             Ref{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{LmmGpGrad}, Ptr{Cdouble}),
             xv, n, yv, p, U, S, m, σ², gps, 0, m, Cint(with_regulariser), val, gy, gσ,
-            complete ? pointer(gS) : Ptr{Cdouble}(C_NULL), complete ? pointer(gU) : Ptr{Cdouble}(C_NULL), gg))
+            complete ? pointer(gS) : Ptr{Cdouble}(C_NULL), complete ? pointer(gU) : Ptr{Cdouble}(C_NULL), gg,
+            gx === nothing ? Ptr{Cdouble}(C_NULL) : pointer(gx)))
         gard = _ard_grads(tags, 1)
     end
     gfull = similar(reshape(gy, n, p)); gfull[perm, :] = reshape(gy, n, p)      # back in the caller's order
+    gxfull = gx === nothing ? nothing : (g = similar(gx); g[perm] = gx; g)
     function statespace_logpdf_pullback(Δ)
         dlat = Tangent{typeof(fs)}(; fs=_fstangent(fs.fs, gg, Δ, gard))
         dH = complete ? _htangent(H, Δ .* gU, Δ .* gS) : ZeroTangent()
-        dfx = Tangent{typeof(fx)}(; x=NoTangent(), f=Tangent{typeof(fx.f)}(; f=dlat, H=dH), Σy=_noise_tangent(fx, Δ * gσ[]))
+        dx = _motangent(fx.x, gxfull === nothing ? nothing : Δ .* gxfull)
+        dfx = Tangent{typeof(fx)}(; x=dx, f=Tangent{typeof(fx.f)}(; f=dlat, H=dH), Σy=_noise_tangent(fx, Δ * gσ[]))
         return NoTangent(), dfx, Δ .* vec(gfull)
     end
     return val[], statespace_logpdf_pullback

@@ -1104,6 +1104,37 @@ class StateSpacePosterior:
         m, v = self._query(xs, True, True)
         return Normal(m, v ** 0.5)
 
+    def mean_and_var_vjp(self, xs, dmean=None, dvar=None) -> dict:
+        """Pullback of mean_and_var to the queries: {"x": d/d xs of sum(dmean * mean) + sum(dvar * var)} with mean, var =
+        self.mean_and_var(xs), shaped and typed like xs and in the callers' order, in O(ns log n) per latent from the stored states
+        (include/lmm_hip.h, lmm_oilmm_statespace_post_mean_and_var_grad_xs).  dmean, dvar: by-outputs cotangents of ns * p values, NumPy
+        or torch; dvar=None is the pullback of the mean alone, dmean=None that of the variance.  The sigma2 that add_noise adds does not
+        depend on xs, so there is no add_noise argument and no "sigma2" entry.  A query's entry depends on no other query.
+        Matern12 latents only: at a query equal to a training input the mean has a kink, and the derivative returned is that of the
+        side the query is sorted to (behind the training point); Matern32, Matern52 and SHO latents are differentiable there."""
+        xs = self._queries(xs)
+        ns = int(xs.shape[0])
+        if dmean is None and dvar is None:
+            raise ValueError("StateSpacePosterior.mean_and_var_vjp: dmean and dvar are both None")
+        cot = []
+        for name, d in (("dmean", dmean), ("dvar", dvar)):
+            if d is not None:
+                if not hasattr(d, "shape"):
+                    d = np.asarray(d, dtype=np.float64)
+                if len(d.shape) != 1 or int(d.shape[0]) != ns * self.p:
+                    raise ValueError(f"StateSpacePosterior.mean_and_var_vjp: {name} holds ns * p = {ns * self.p} values by outputs")
+                if L._is_torch(d):
+                    import torch
+                    d = d.to(torch.float64)
+            cot.append(d)
+        gx = _alloc_like(xs, ns)
+        if ns == 0:
+            return {"x": gx}
+        L.check(L.load().lmm_oilmm_statespace_post_mean_and_var_grad_xs(self._ptr, L.Arr(xs).ptr, ns,
+                                                                        None if cot[0] is None else L.Arr(cot[0]).ptr,
+                                                                        None if cot[1] is None else L.Arr(cot[1]).ptr, L.Arr(gx, True).ptr))
+        return {"x": gx}
+
     def _window(self, lo: float, hi: float):
         first, count = C.c_int(), C.c_int()
         L.check(L.load().lmm_statespace_post_window(self._ptr, float(lo), float(hi), C.byref(first), C.byref(count)))
@@ -1199,12 +1230,14 @@ class _NoStateSpaceMixingGradient(dict):
         raise KeyError(key)
 
 
-def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = True) -> dict:
+def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = True, inputs: bool = False) -> dict:
     """Value and gradient of statespace_logpdf(fx, y) in O(n): {"value", "y", "sigma2", "S", "U", "gps"}, as logpdf_and_gradient returns
     them for a prior OILMM.  "value" is bitwise statespace_logpdf(fx, y, with_regulariser); "y" is shaped and typed like y, in the
     callers' order of points whatever the order of the inputs, and exactly 0 at NaN entries; "gps" (through _gps_grads) holds every
     latent's "variance", "lengthscale" and "mean", and an SHO latent's "quality" ("lengthscale" is then d / d period).  With NaN in y (points whose outputs are all NaN included) "S" and "U" raise
-    NotImplementedError, as after logpdf_and_gradient.  There is no gradient with respect to the inputs."""
+    NotImplementedError, as after logpdf_and_gradient.  inputs=True adds "x", the gradient with respect to the input locations in O(n)
+    (include/lmm_hip.h, lmm_oilmm_logpdf_grad_statespace_x): shaped and typed like fx.x.x, in the callers' order of points, exactly 0
+    at points whose outputs are all NaN; every other entry is bitwise that of inputs=False."""
     y = _statespace_args(fx, y, "statespace_logpdf_and_gradient")
     f, x = fx.f, fx.x
     nan = _has_nan(y)
@@ -1214,13 +1247,23 @@ def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = T
     val, gs2 = C.c_double(), C.c_double()
     gy, gS, gU = _alloc_like(ya, n * p), np.empty(m), np.empty(p * m)
     gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.f.fs])
-    L.check(L.load().lmm_oilmm_logpdf_grad_statespace(L.Arr(xa).ptr, n, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), ga, 0, m,
-                                                      int(with_regulariser), C.byref(val), L.Arr(gy, True).ptr, C.byref(gs2),
-                                                      None if nan else L.Arr(gS, True).ptr, None if nan else L.Arr(gU, True).ptr, gg))
+    args = (L.Arr(xa).ptr, n, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), ga, 0, m, int(with_regulariser), C.byref(val),
+            L.Arr(gy, True).ptr, C.byref(gs2), None if nan else L.Arr(gS, True).ptr, None if nan else L.Arr(gU, True).ptr, gg)
+    gx = None
+    if inputs:
+        gx = _alloc_like(xa, n)
+        L.check(L.load().lmm_oilmm_logpdf_grad_statespace_x(*args, L.Arr(gx, True).ptr))
+        gx = _statespace_unsorted(gx, perm, 1, n, False).reshape(x.x.shape)
+        if L._is_torch(gx) and not L._is_torch(x.x):      # NumPy inputs x with a torch y
+            gx = gx.cpu().numpy()
+    else:
+        L.check(L.load().lmm_oilmm_logpdf_grad_statespace(*args))
     gy = _statespace_unsorted(gy, perm, p, n, False)
     if L._is_torch(gy) and not L._is_torch(y):        # torch inputs x with a NumPy y
         gy = gy.cpu().numpy()
     out = {"value": val.value, "y": gy, "sigma2": gs2.value, "gps": _gps_grads(gg, ga, m, 1)}
+    if inputs:
+        out["x"] = gx
     if nan:
         return _NoStateSpaceMixingGradient(out)
     out.update(S=gS, U=gU.reshape(m, p).T.copy())
