@@ -997,6 +997,10 @@ int lmm_dev_set_emul_gemm_workgroups(int wgs);
  * blocks that are live in both operands, on = 0 walks every block with the same kernel, on < 0 goes back to the environment's
  * default.  A skipped block multiplies exact zeros: results do not depend on it. */
 int lmm_dev_set_emul_zero_skip(int on);
+/* Test hook, default 0, never set outside tests: on != 0 makes every emulated update fill the residue scratch of a group with a
+ * non-zero byte before its convert.  With the zero skip on the convert stores nothing into a dead K block (block 0 excepted), so the
+ * fill stands in for whatever an earlier update left there.  Results do not depend on it. */
+int lmm_dev_set_emul_scratch_poison(int on);
 /* Host-only (no GPU, no lmm_init needed): the K blocks a GEMM tile of the emulation walks when its two operands have the live masks
  * (a0, a1) and (b0, b1) (bit k / 128 of a0 for k < 8192, of a1 above) and K = 128 nk, 1 <= nk <= 128, by the helpers the kernel
  * uses: out[0 .. min(cap, length)) = the blocks in walk order, *count (may be NULL) = the number of K steps the kernel's MFMA loop

@@ -872,9 +872,15 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
   std::vector<unsigned long long*> amax_kept(P.steps.size(), nullptr);
   for (size_t i = 0; i < P.steps.size(); ++i)
     if (P.steps[i].kind == POTRF_EMUL_UPDATE_LEAF) amax_kept[i] = reinterpret_cast<unsigned long long*>(call_scratch((size_t)B.nb * NR));
-  // live K blocks of the emulated updates' panels (lmm_emul.h): a few KB, rewritten by every group of every update in stream order
-  unsigned long long* emul_masks = nullptr;
-  if (P.emul_bytes > 0) emul_masks = reinterpret_cast<unsigned long long*>(call_scratch(emul_mask_bytes(NR, B.nb) / 8));
+  // live K blocks and unwritten pieces of the emulated updates' panels (lmm_emul.h): sized for the deepest update, rewritten by every
+  // group of every update in stream order
+  void* emul_aux_blk = nullptr;
+  if (P.emul_bytes > 0) {
+    int kmax = 128;
+    for (const PotrfStep& s : P.steps)
+      if (s.kind == POTRF_EMUL_UPDATE_LEAF) kmax = std::max(kmax, s.h);
+    emul_aux_blk = call_scratch(emul_aux(NR, B.nb, kmax).total / 8);
+  }
   auto leaf128 = [&](int c) { launch_leaf128(B.A, (size_t)c * ld + c, ld, B.W, (size_t)(c / 64) * 4096, W2, (size_t)(c / 128) * 16384, c, n_real, B.info, B.nb, st); };
   for (const PotrfStep& s : P.steps) {
     const bool named = s.named();
@@ -899,7 +905,7 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
           EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0};
           for (int q = 0; q < cov.n; ++q) keep.src[q] = amax_kept[cov.step[q]];
           if (r0 + s.M > NR) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's rows %d + %d exceed %d", r0, s.M, NR);
-          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_masks, st, &keep));
+          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, st, &keep));
         }
         leaf128(r0);
         break;
@@ -6166,6 +6172,13 @@ int lmm_dev_set_emul_zero_skip(int on) {
   emul_set_zero_skip(on);
   return LMM_OK;
 }
+// Test hook (default 0, never set outside tests): on != 0 fills the residue scratch of every group of an emulated update with a
+// non-zero byte before its convert, in place of whatever an earlier update left in the blocks the convert no longer writes.
+int lmm_dev_set_emul_scratch_poison(int on) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  emul_set_scratch_poison(on);
+  return LMM_OK;
+}
 // Host-only (no GPU, no lmm_init needed): the stage list of a GEMM tile whose operands have the live masks a (a0: K blocks 0 .. 63, a1:
 // 64 .. 127) and b, at depth nk = K / 128 blocks, walked with the helpers the kernel's staging cursor uses (lmm_emul.h).  out[0 .. min(
 // cap, length)) = the K blocks in walk order; *count (may be NULL) = what the kernel's MFMA loop takes for the length.  Returns the
@@ -6191,8 +6204,8 @@ int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N
   double* scratch = call_scratch((bytes + 7) / 8);
   BatchPtr Cb{}, Pb{};
   Cb.p[0] = C; Pb.p[0] = const_cast<double*>(A);
-  unsigned long long* masks = reinterpret_cast<unsigned long long*>(call_scratch(emul_mask_bytes(M, 1) / 8));
-  HIPCHK(launch_emul_update(Cb, 0, ldc, Pb, 0, lda, M, N, K, 1, 1, nmod, scratch, masks, g.streams[0]));
+  void* aux = call_scratch(emul_aux(M, 1, K).total / 8);
+  HIPCHK(launch_emul_update(Cb, 0, ldc, Pb, 0, lda, M, N, K, 1, 1, nmod, scratch, aux, g.streams[0]));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(g.streams[0]));
   return LMM_OK;

@@ -112,6 +112,42 @@ LMM_HD inline EmulMask emul_mask_pop(EmulMask m) {      // m without its first b
   return m;
 }
 
+// ---- the GEMM's walk: work ids per XCD ----
+// Workgroups b and b + 8 share an XCD.  The nids work ids are cut into min(nwg, 8) contiguous ranges, as equal as they can be (the
+// first nids % parts ranges hold one more); range x belongs to the workgroups b with b % 8 == x, emul_range_wgs of them.  The ranges
+// tile [0, nids) exactly, whatever nids and nwg >= 1.
+struct EmulRange { int start, len; };
+LMM_HD inline int emul_range_parts(int nwg) { return nwg < 8 ? nwg : 8; }
+LMM_HD inline EmulRange emul_xcd_range(int nids, int nwg, int x) {      // 0 <= x < emul_range_parts(nwg)
+  const int parts = emul_range_parts(nwg), q = nids / parts, r = nids - q * parts;
+  return EmulRange{x * q + (x < r ? x : r), q + (x < r ? 1 : 0)};
+}
+LMM_HD inline int emul_range_wgs(int nwg, int x) { return (nwg >> 3) + (x < (nwg & 7) ? 1 : 0); }
+
+// ---- unwritten pieces (dead blocks are never written) ----
+// The convert works on pieces of 16 rows x 128 k, 16 per block.  A piece whose truncated integers are all zero is not turned into
+// residues and not stored: the convert sets its bit here instead, 16 bits per (matrix, tile row, K block), two blocks per 32-bit word
+// (cleared on the stream with the masks).  emul_zero_fill_kernel then writes zero residues into the unwritten pieces of the blocks the
+// GEMM may stage -- the live ones, and block 0 for the empty-intersection fallback of emul_live_stages -- and into no other block.
+#define LMM_EMUL_PIECE_ROWS 16
+#define LMM_EMUL_PIECES (LMM_EMUL_TILE / LMM_EMUL_PIECE_ROWS)
+LMM_HD inline size_t emul_piece_block(int tile_rows, int nkb, int z, int trow, int kb) { return ((size_t)z * tile_rows + trow) * nkb + kb; }
+LMM_HD inline size_t emul_piece_word(size_t block) { return block >> 1; }
+LMM_HD inline unsigned emul_piece_shift(size_t block) { return (unsigned)(block & 1) * LMM_EMUL_PIECES; }
+inline size_t emul_piece_bytes(int M, int G, int K) {
+  const size_t blocks = (size_t)G * ((M + LMM_EMUL_TILE - 1) / LMM_EMUL_TILE) * (K / 128);
+  return (blocks + 1) / 2 * 4;
+}
+// The small arrays of one group beside its residues: the live masks, then the unwritten-piece bitmap (byte offsets; a multiple of 8 each)
+struct EmulAux { size_t masks, pieces, total; };
+inline EmulAux emul_aux(int M, int G, int K) {
+  EmulAux a{};
+  a.masks = 0;
+  a.pieces = emul_mask_bytes(M, G);
+  a.total = a.pieces + ((emul_piece_bytes(M, G, K) + 7) & ~size_t(7));
+  return a;
+}
+
 // ceil(log2 amax) for a finite amax > 0
 LMM_HD inline int emul_row_exp(double amax) {
   int q;

@@ -167,15 +167,16 @@ bool launch_gemm32w(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
 // M >= N, K a multiple of 128 within the int32 accumulator bound.  Matrices go through `scratch` (emul_scratch_bytes) in groups of G.
 // (emul_shape_ok, emul_scratch_bytes: lmm_emul.h)
 void emul_set_gemm_workgroups(int wgs);      // cap of the persistent GEMM grid (tests); 0: one workgroup per CU
+void emul_set_scratch_poison(int on);        // tests: != 0 fills a group's residue scratch with a non-zero byte before its convert
 void emul_set_zero_skip(int on);             // 0: the GEMM walks every K block (all-ones live masks); 1: only the live ones; < 0: LMM_EMUL_ZERO_SKIP (default 1)
 // Row maxima that outlive the update (potrf_batch; emul_amax_cover of lmm_potrf_plan.h): out = this update's array, out[m ld + r] for
 // matrix m and the ABSOLUTE row r of the matrix (the panel's row i is row row0 + i), written for all nb matrices; src[0 .. n) = arrays
 // of the same layout that earlier updates wrote, which together hold the maxima over the panel's columns [0, scan0), so that only
 // the columns [scan0, K) are read.  nullptr: the maxima live in the scratch, per group, and the whole panel is read.
-// masks: emul_mask_bytes(M, G) bytes (lmm_emul.h) for the live K blocks of one group's panels.
+// aux: emul_aux(M, G, K).total bytes (lmm_emul.h) for the live K blocks and the unwritten pieces of one group's panels.
 struct EmulAmaxKeep { unsigned long long* out; int ld, row0, n; const unsigned long long* src[LMM_EMUL_COVER_MAX]; int scan0; };
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
-                              int G, int nmod, void* scratch, unsigned long long* masks, hipStream_t st, const EmulAmaxKeep* keep = nullptr);      // the first HIP error of its host-side calls
+                              int G, int nmod, void* scratch, void* aux, hipStream_t st, const EmulAmaxKeep* keep = nullptr);      // the first HIP error of its host-side calls
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,
                    const BatchInfo& info, int nb, hipStream_t st);
 // no_splitk: never split the last round's tiles along K (their f64 atomics make the sum order run-dependent): bitwise reproducible

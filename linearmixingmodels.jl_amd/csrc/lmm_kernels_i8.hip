@@ -2,7 +2,9 @@
 // Built WITHOUT -amdgpu-mfma-vgpr-form=1.  Three steps per update, for groups of matrices:
 //   1. emul_rowmax_kernel + emul_convert_kernel: per panel row the exponent e_i = ceil(log2 max_k |a_ik|), the integers
 //      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows (inside a factorisation
-//      the maxima outlive the update, and a later update reads them for the columns it shares: emul_amax_fold_kernel);
+//      the maxima outlive the update, and a later update reads them for the columns it shares: emul_amax_fold_kernel); a piece of
+//      16 rows x 128 k that is all zeros is read and neither converted nor stored, and emul_zero_fill_kernel writes zeros into
+//      such pieces only where the GEMM may stage them;
 //   2. emul_gemm_kernel: one int8 SYRK-shaped GEMM per (matrix, modulus) on 256 x 256 tiles of the lower trapezoid, int32
 //      accumulators, reduced mod p to one byte per output, as a persistent kernel whose tiles walk only the K blocks that are live
 //      (not all zeros) in both operands (tools/i8_gemm_probe.hip holds a copy of the kernel without that skip,
@@ -57,13 +59,15 @@ __global__ __launch_bounds__(256) void emul_amax_fold_kernel(EmulAmaxKeep k, int
 // R[(z NMOD + t) Mp + i][k]: 32 lanes write 128 contiguous bytes.  Rows M .. Mp - 1 (padding up to the GEMM tile) get zero residues.
 // The barrier between the two halves also ORs "one of my integers is not zero" over the workgroup, and one thread then sets the bit of
 // this K block in the live mask of its 256-row tile row (lmm_emul.h; zeroed, or filled with ones, on the stream before this kernel).
-// The bit follows the truncated integers: a row with a NaN or an infinity and the padding rows are zeros here.  Every residue is still
-// written: a live block of 256 rows may hold dead pieces of 16, which the GEMM reads.
+// The bit follows the truncated integers: a row with a NaN or an infinity and the padding rows are zeros here.
+// A workgroup whose piece is all zeros stops at that barrier (pieces != nullptr: the zero skip is on): it forms no residues and
+// stores nothing, and sets its bit in the unwritten-piece bitmap (lmm_emul.h) instead.  A live block of 256 rows may hold such dead
+// pieces of 16, which the GEMM reads: emul_zero_fill_kernel writes them.  pieces == nullptr: every residue is written here.
 constexpr int CV_ROWS = 16, CV_K = 128, CV_PITCH = 130;
 template <int NMOD>
 __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
                                                            const unsigned long long* __restrict__ amax, int as, int8_t* __restrict__ R, double* sc, int* ex,
-                                                           unsigned long long* masks) {
+                                                           unsigned long long* masks, unsigned* pieces) {
   __shared__ long long lds[CV_ROWS * CV_PITCH];
   const int tid = threadIdx.x, ti = tid & 15, tk = tid >> 4, z = blockIdx.z;
   const int i = blockIdx.x * CV_ROWS + ti, k0 = blockIdx.y * CV_K;
@@ -87,8 +91,14 @@ __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, s
     lds[ti * CV_PITCH + tk + 16 * s] = v;
     any |= v;
   }
-  if (__syncthreads_or(any != 0) && tid == 0)
-    atomicOr(&masks[((size_t)z * (Mp / TILE) + blockIdx.x / (TILE / CV_ROWS)) * LMM_EMUL_MASK_WORDS + (blockIdx.y >> 6)], 1ull << (blockIdx.y & 63));
+  const int trow = blockIdx.x / LMM_EMUL_PIECES;
+  if (__syncthreads_or(any != 0)) {
+    if (tid == 0) atomicOr(&masks[((size_t)z * (Mp / TILE) + trow) * LMM_EMUL_MASK_WORDS + (blockIdx.y >> 6)], 1ull << (blockIdx.y & 63));
+  } else if (pieces != nullptr) {
+    const size_t blk = emul_piece_block(Mp / TILE, K / CV_K, z, trow, blockIdx.y);
+    if (tid == 0) atomicOr(&pieces[emul_piece_word(blk)], 1u << (emul_piece_shift(blk) + blockIdx.x % LMM_EMUL_PIECES));
+    return;
+  }
   const int kg = tid & 31;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -108,13 +118,33 @@ __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, s
     for (int t = 0; t < NMOD; ++t) *reinterpret_cast<unsigned*>(dst + (size_t)t * Mp * K) = w[t];
   }
 }
+// One workgroup per (K block, tile row, matrix): zero residues, for all nmod planes, into the pieces the convert left unwritten, if
+// the block is one the GEMM may stage: a live one, or block 0 (two tile rows that share no live block stage block 0 of both:
+// emul_live_stages).  A piece is 16 rows x 128 B per plane: 8 lanes of 16 B per row.  Dead blocks other than block 0 get no store.
+__global__ __launch_bounds__(256) void emul_zero_fill_kernel(int8_t* __restrict__ R, int Mp, int K, int nmod, const unsigned long long* __restrict__ masks,
+                                                             const unsigned* __restrict__ pieces) {
+  const int kb = blockIdx.x, trow = blockIdx.y, z = blockIdx.z, tr = Mp / TILE;
+  const unsigned long long mw = masks[((size_t)z * tr + trow) * LMM_EMUL_MASK_WORDS + (kb >> 6)];
+  if (kb != 0 && ((mw >> (kb & 63)) & 1ull) == 0ull) return;
+  const size_t blk = emul_piece_block(tr, K / BK, z, trow, kb);
+  const unsigned u = (pieces[emul_piece_word(blk)] >> emul_piece_shift(blk)) & ((1u << LMM_EMUL_PIECES) - 1u);
+  if (u == 0u) return;
+  for (int pc = 0; pc < LMM_EMUL_PIECES; ++pc) {
+    if (((u >> pc) & 1u) == 0u) continue;
+    for (int q = threadIdx.x; q < nmod * CV_ROWS * 8; q += 256) {
+      const int t = q / (CV_ROWS * 8), row = (q >> 3) % CV_ROWS, col = q & 7;
+      int8_t* dst = R + (((size_t)z * nmod + t) * Mp + trow * TILE + pc * CV_ROWS + row) * K + kb * BK + col * 16;
+      *reinterpret_cast<v4u*>(dst) = (v4u){0u, 0u, 0u, 0u};
+    }
+  }
+}
 template <int NMOD>
 void launch_convert(int nmod, dim3 grid, hipStream_t st, const BatchPtr& P, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
-                    const unsigned long long* amax, int as, int8_t* R, double* sc, int* ex, unsigned long long* masks) {
+                    const unsigned long long* amax, int as, int8_t* R, double* sc, int* ex, unsigned long long* masks, unsigned* pieces) {
   if constexpr (NMOD > LMM_EMUL_MINMOD) {
-    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks);
+    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks, pieces);
   }
-  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks);
+  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks, pieces);
 }
 
 // lower-trapezoid tiles in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles share at most 12 operand panels
@@ -231,10 +261,10 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
   // the walk of this workgroup: ids first, first + step, .. (cnt of them) of its XCD's range; fewer than 8 workgroups split the ids
   // among themselves
-  const int nwg = gridDim.x, parts = nwg < 8 ? nwg : 8, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int step = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
-  const int qi = nids / parts, ri = nids - qi * parts;
-  const int first = xcd * qi + (xcd < ri ? xcd : ri) + slot, span = qi + (xcd < ri ? 1 : 0) - slot;
+  const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int step = emul_range_wgs(nwg, xcd);
+  const EmulRange rg = emul_xcd_range(nids, nwg, xcd);
+  const int first = rg.start + slot, span = rg.len - slot;
   const int cnt = span > 0 ? (span + step - 1) / step : 0;
   if (cnt == 0) return;
   // source offsets of a lane's four 16-byte loads of one operand, from the tile's first row at k = 0
@@ -465,6 +495,7 @@ void launch_combine(int nmod, dim3 grid, hipStream_t st, const BatchPtr& C, int 
 
 int g_emul_gemm_wgs = 0;      // emul_set_gemm_workgroups: 0 = one workgroup per CU
 int g_emul_zero_skip = -1;    // emul_set_zero_skip: -1 = LMM_EMUL_ZERO_SKIP (read once; default on)
+int g_emul_poison = 0;        // emul_set_scratch_poison (tests): the residue scratch of a group is filled with a non-zero byte before its convert
 
 bool emul_zero_skip_on() {
   if (g_emul_zero_skip < 0) {
@@ -478,15 +509,18 @@ bool emul_zero_skip_on() {
 
 void emul_set_gemm_workgroups(int wgs) { g_emul_gemm_wgs = wgs; }
 void emul_set_zero_skip(int on) { g_emul_zero_skip = on < 0 ? -1 : (on ? 1 : 0); }
+void emul_set_scratch_poison(int on) { g_emul_poison = on ? 1 : 0; }
 
 // C_m (M x N at C.p[m] + offC, ldc) -= P_m P_m[0:N]' for the panels P_m (M x K at P.p[m] + offP, ldp), m < nb, lower trapezoid
 // (i >= j) only, in groups of G matrices through `scratch` (emul_scratch_bytes(M, N, K, G, nmod) bytes).  Returns the first HIP
 // error of its host-side calls (nothing is launched after one).  keep: the row maxima go to an array of the caller's, for all nb matrices
-// before the first group, and start from what earlier updates found (EmulAmaxKeep, lmm_internal.h).  masks: emul_mask_bytes(M, G) bytes
-// for the live K blocks of a group's panels (lmm_emul.h), set on the stream before each convert: to zero, or to ones with the zero
-// skip switched off.
+// before the first group, and start from what earlier updates found (EmulAmaxKeep, lmm_internal.h).  aux: emul_aux(M, G, K).total bytes
+// for the live K blocks of a group's panels and its unwritten pieces (lmm_emul.h), set on the stream before each convert: the masks to
+// zero, or to ones with the zero skip switched off; the bitmap to zero.  The residues R are shared by the groups and the updates that
+// go through one scratch block and a dead block is never written, so it holds whatever was there: R is read through
+// emul_live_stages only.
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
-                              int G, int nmod, void* scratch, unsigned long long* masks, hipStream_t st, const EmulAmaxKeep* keep) {
+                              int G, int nmod, void* scratch, void* aux, hipStream_t st, const EmulAmaxKeep* keep) {
   static EmulConst consts[LMM_EMUL_MAXMOD + 1];
   if (consts[nmod].nmod != nmod) consts[nmod] = emul_make_const(nmod);
   const EmulConst& c = consts[nmod];
@@ -502,6 +536,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
   unsigned long long* amax = reinterpret_cast<unsigned long long*>(s + L.amax);
   double* sc = reinterpret_cast<double*>(s + L.sc);
   int* ex = reinterpret_cast<int*>(s + L.ex);
+  const bool skip = emul_zero_skip_on();
   const int wgs = g_emul_gemm_wgs > 0 ? g_emul_gemm_wgs : device_cus();      // one 128-KiB workgroup fits on a CU
   if (keep) {      // every row of every matrix gets its first write from the fold: no memset
     emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(*keep, M);
@@ -518,9 +553,18 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
       if (err != hipSuccess) return err;
       emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, K, amax);
     }
-    err = hipMemsetAsync(masks, emul_zero_skip_on() ? 0 : 0xFF, emul_mask_bytes(M, gc), st);
+    // skip on: masks and bitmap are one run of bytes, one fill of zeros; skip off: ones for the masks, and no bitmap
+    const EmulAux X = emul_aux(M, gc, K);
+    unsigned long long* masks = reinterpret_cast<unsigned long long*>(static_cast<char*>(aux) + X.masks);
+    unsigned* pieces = skip ? reinterpret_cast<unsigned*>(static_cast<char*>(aux) + X.pieces) : nullptr;
+    err = skip ? hipMemsetAsync(aux, 0, X.total, st) : hipMemsetAsync(masks, 0xFF, emul_mask_bytes(M, gc), st);
     if (err != hipSuccess) return err;
-    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, am, as, R, sc, ex, masks);
+    if (g_emul_poison) {
+      err = hipMemsetAsync(R, 0x5A, (size_t)gc * nmod * L.Mp * K, st);
+      if (err != hipSuccess) return err;
+    }
+    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, am, as, R, sc, ex, masks, pieces);
+    if (skip) emul_zero_fill_kernel<<<dim3(K / BK, L.Mp / TILE, gc), 256, 0, st>>>(R, L.Mp, K, nmod, masks, pieces);
     const int nids = ntiles * gc * nmod;
     emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, ntiles, nids, L.Mp, L.Np, K, c, masks);
     launch_combine<LMM_EMUL_MAXMOD>(nmod, dim3((M + 1023) / 1024, N, gc), st, C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);

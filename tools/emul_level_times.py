@@ -6,7 +6,9 @@
 A level is recognised by the K of the update's emul_convert_kernel launches (grid y = K / 128): the row-maximum kernels that open
 an update scan only the columns no earlier update has scanned (emul_amax_fold_kernel, counted with emul_rowmax, starts them from the
 kept maxima), so their grid does not tell.  Prints ms summed over the launches of a level, per kernel, and the totals of every other
-kernel.
+kernel.  emul_zero_fill is the kernel behind a convert that writes zero residues into the pieces the convert left unwritten (dead blocks
+are never written); a trace from before it has zeros there.  `fill` is the stream's memsets inside an update: the masks and the
+unwritten-piece bitmap of a group are one of them.
 
 Then one line per emulated UPDATE, in launch order: an update is a maximal run of emulation kernels and the fills between them
 (two emulated updates are never neighbours: the factorisation of the columns between them lies in between).  Its key is (K, Mp,
@@ -19,7 +21,7 @@ import collections
 import csv
 import sys
 
-EMUL = ("emul_rowmax", "emul_convert", "emul_gemm", "emul_combine")
+EMUL = ("emul_rowmax", "emul_convert", "emul_zero_fill", "emul_gemm", "emul_combine")
 ALIAS = {"emul_amax_fold": "emul_rowmax"}
 
 
@@ -88,7 +90,7 @@ def main(argv):
     print("emulated total: " + str({k: round(sum(per[kern][k] for kern in per), 2) for k in levels}))
     print("other kernels ms: " + str({k: round(v, 2) for k, v in sorted(other.items(), key=lambda kv: -kv[1])[:10]}))
     if runs:
-        print("emulated updates in launch order: K Mp nb groups | rowmax convert gemm combine fill leaf | kernel sum, span (ms)")
+        print("emulated updates in launch order: K Mp nb groups | rowmax convert zero_fill gemm combine fill leaf | kernel sum, span (ms)")
     for u in runs:
         tot = sum(u[k] for k in EMUL) + u["fill"] + u["leaf"]
         print(f"  K={u['K']:5d} Mp={int(u['Mp']):5d} nb={u['nb']:2d} groups={u['groups']:2d} | " + " ".join(f"{u[k]:7.3f}" for k in EMUL)
