@@ -1211,39 +1211,49 @@ void host_jacobi_eig(std::vector<double> A, int m, std::vector<double>& lam, std
   for (int i = 0; i < m; ++i) lam[i] = A[i + (size_t)i * m];
 }
 
-// reference src/ilmm.jl:61-68.  T m x p, ST m x m (column-major); also logdet(ST) for src/ilmm.jl:179.
-int project_dense(const double* H, int p, int m, double s2, double jitter, std::vector<double>& T,
-                  std::vector<double>& ST, double* logdetST) {
-  std::vector<double> G((size_t)m * m, 0.0);
-  for (int a = 0; a < m; ++a)
-    for (int b = 0; b < m; ++b) {
-      double s = 0.0;
-      for (int o = 0; o < p; ++o) s += H[o + (size_t)a * p] * H[o + (size_t)b * p];
-      G[a + (size_t)b * m] = s / s2 + (a == b ? jitter : 0.0);
+// C (r x c) = op(A) op(B), column-major, op(A) r x k and op(B) k x c; ta / tb: the operand is stored transposed.  Every element is the
+// sum over the inner index in ascending order from 0.0: the order the callers' values are pinned in, bit for bit.
+std::vector<double> host_matmul(const double* A, bool ta, const double* B, bool tb, int r, int k, int c) {
+  std::vector<double> Cm((size_t)r * c, 0.0);
+  for (int j = 0; j < c; ++j)
+    for (int q = 0; q < k; ++q) {
+      const double b = tb ? B[j + (size_t)q * c] : B[q + (size_t)j * k];
+      for (int i = 0; i < r; ++i) Cm[i + (size_t)j * r] += (ta ? A[q + (size_t)i * k] : A[i + (size_t)q * r]) * b;
     }
-  if (!host_cholesky(G, m)) return fail(LMM_ERR_NOT_PD, "PosDefException in project(H, sigma2): H'H/sigma2 + 1e-9 I not PD");
-  T.assign((size_t)m * p, 0.0);
-  for (int o = 0; o < p; ++o) {     // solve (L L') t = H[o,:]' / s2
-    std::vector<double> v(m);
+  return Cm;
+}
+
+// B (m x nrhs, column-major) <- (L L')^-1 B in place, L the lower factor host_cholesky leaves: forward, then backward substitution
+void host_chol_solve(const std::vector<double>& L, int m, double* B, int nrhs) {
+  for (int c = 0; c < nrhs; ++c) {
+    double* v = B + (size_t)c * m;
     for (int a = 0; a < m; ++a) {
-      double s = H[o + (size_t)a * p] / s2;
-      for (int k = 0; k < a; ++k) s -= G[a + (size_t)k * m] * v[k];
-      v[a] = s / G[a + (size_t)a * m];
+      double s = v[a];
+      for (int k = 0; k < a; ++k) s -= L[a + (size_t)k * m] * v[k];
+      v[a] = s / L[a + (size_t)a * m];
     }
     for (int a = m - 1; a >= 0; --a) {
       double s = v[a];
-      for (int k = a + 1; k < m; ++k) s -= G[k + (size_t)a * m] * v[k];
-      v[a] = s / G[a + (size_t)a * m];
+      for (int k = a + 1; k < m; ++k) s -= L[k + (size_t)a * m] * v[k];
+      v[a] = s / L[a + (size_t)a * m];
     }
-    for (int a = 0; a < m; ++a) T[a + (size_t)o * m] = v[a];
   }
-  ST.assign((size_t)m * m, 0.0);
+}
+
+// reference src/ilmm.jl:61-68: P = H'H / s2 + jitter I, T = P^-1 H' / s2 (m x p), ST = s2 T T' (m x m; all column-major); also
+// logdet(ST) for src/ilmm.jl:179.
+int project_dense(const double* H, int p, int m, double s2, double jitter, std::vector<double>& T,
+                  std::vector<double>& ST, double* logdetST) {
+  std::vector<double> G = host_matmul(H, true, H, false, m, p, m);
   for (int a = 0; a < m; ++a)
-    for (int b = 0; b < m; ++b) {
-      double s = 0.0;
-      for (int o = 0; o < p; ++o) s += T[a + (size_t)o * m] * T[b + (size_t)o * m];
-      ST[a + (size_t)b * m] = s2 * s;
-    }
+    for (int b = 0; b < m; ++b) G[a + (size_t)b * m] = G[a + (size_t)b * m] / s2 + (a == b ? jitter : 0.0);
+  if (!host_cholesky(G, m)) return fail(LMM_ERR_NOT_PD, "PosDefException in project(H, sigma2): H'H/sigma2 + 1e-9 I not PD");
+  T.assign((size_t)m * p, 0.0);
+  for (int o = 0; o < p; ++o)
+    for (int a = 0; a < m; ++a) T[a + (size_t)o * m] = H[o + (size_t)a * p] / s2;
+  host_chol_solve(G, m, T.data(), p);
+  ST = host_matmul(T.data(), false, T.data(), true, m, p, m);
+  for (double& v : ST) v = s2 * v;
   if (logdetST) {
     std::vector<double> C = ST;
     if (!host_cholesky(C, m)) return fail(LMM_ERR_NOT_PD, "PosDefException: SigmaT not PD");
@@ -1251,6 +1261,48 @@ int project_dense(const double* H, int p, int m, double s2, double jitter, std::
     for (int a = 0; a < m; ++a) ld += std::log(C[a + (size_t)a * m]);
     *logdetST = 2.0 * ld;
   }
+  return LMM_OK;
+}
+
+// project_dense differentiated, host algebra only: from the cotangents Tb of T and Gs of ST, ADD the cotangent of H (p x m) to Hb and
+// that of s2 to s2g.  The caller's own terms are in Hb and s2g before the call, and every sum runs in the order written here: the
+// dense-H gradients are pinned bit for bit (tools/bitwise_vs_parent.py).
+int project_dense_backward(const double* H, int p, int m, double s2, double jitter, const std::vector<double>& T, std::vector<double> Tb,
+                           const std::vector<double>& Gs, std::vector<double>& Hb, double& s2g) {
+  const size_t mm = (size_t)m * m;
+  const double s = 1.0 / s2;
+  const std::vector<double> HtH = host_matmul(H, true, H, false, m, p, m);
+  // ST = s2 T T':  Tb += s2 (Gs + Gs') T;  s2g += <Gs, T T'>
+  std::vector<double> Gsym(mm), Psym(mm);
+  for (int a = 0; a < m; ++a)
+    for (int b = 0; b < m; ++b) Gsym[a + (size_t)b * m] = Gs[a + (size_t)b * m] + Gs[b + (size_t)a * m];
+  const std::vector<double> GT = host_matmul(Gsym.data(), false, T.data(), false, m, m, p);
+  const std::vector<double> TTt = host_matmul(T.data(), false, T.data(), true, m, p, m);
+  for (size_t q = 0; q < Tb.size(); ++q) Tb[q] += s2 * GT[q];
+  for (int a = 0; a < m; ++a)
+    for (int b = 0; b < m; ++b) s2g += Gs[a + (size_t)b * m] * TTt[a + (size_t)b * m];
+  // T = P^-1 H' s with P = s H'H + jitter I:  Mb = P^-1 Tb (m x p, in Tb's place);  Pb = -Mb T'
+  std::vector<double> P(mm);
+  for (int a = 0; a < m; ++a)
+    for (int b = 0; b < m; ++b) P[a + (size_t)b * m] = s * HtH[a + (size_t)b * m] + (a == b ? jitter : 0.0);
+  if (!host_cholesky(P, m)) return fail(LMM_ERR_NOT_PD, "PosDefException in project(H, sigma2)");
+  const std::vector<double>& Mb = Tb;
+  host_chol_solve(P, m, Tb.data(), p);
+  std::vector<double> Pb = host_matmul(Mb.data(), false, T.data(), true, m, p, m);
+  for (double& v : Pb) v = -v;
+  for (int a = 0; a < m; ++a)
+    for (int b = 0; b < m; ++b) Psym[a + (size_t)b * m] = Pb[a + (size_t)b * m] + Pb[b + (size_t)a * m];
+  const std::vector<double> HP = host_matmul(H, false, Psym.data(), false, p, m, m);      // P = s H'H:  Hb += s H (Pb + Pb')
+  double sb = 0.0;       // cotangent of s = 1 / s2
+  for (int o = 0; o < p; ++o)
+    for (int l = 0; l < m; ++l) {
+      Hb[o + (size_t)l * p] += s * Mb[l + (size_t)o * m];                        // M = H' s
+      sb += Mb[l + (size_t)o * m] * H[o + (size_t)l * p];
+      Hb[o + (size_t)l * p] += s * HP[o + (size_t)l * p];
+    }
+  for (int a = 0; a < m; ++a)
+    for (int b = 0; b < m; ++b) sb += Pb[a + (size_t)b * m] * HtH[a + (size_t)b * m];
+  s2g += -sb * s * s;
   return LMM_OK;
 }
 
@@ -1303,6 +1355,10 @@ double oilmm_regulariser(double n, int p, int m, const double* S, double s2, dou
   for (int l = 0; l < m; ++l) logdetS += std::log(S[l]);
   return -(n * (logdetS + (double)(p - m) * std::log(2.0 * M_PI * s2)) + resid / s2) / 2.0;
 }
+// The dense-H one, reference src/ilmm.jl:171-181, for cnt points with noise s2 and resid = |Y - H T Y|_F^2
+double ilmm_regulariser(double cnt, int p, int m, double s2, double logdetST, double resid) {
+  return -(cnt * ((double)(p - m) * kLog2Pi + ((double)p * std::log(s2) - logdetST)) + resid / s2) / 2.0;
+}
 
 // The projection front end of complete data (reference src/oilmm.jl:20-30): T, the projected noise ST and H on the host (the
 // constructor); T and the latent means on the device (upload); then, on streams[0], the shard's residual rows (delta) or the plain
@@ -1342,6 +1398,85 @@ struct OilmmFront {
       HIPCHK(hipMemcpyAsync(resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
     }
     return Ty.p + (size_t)(l0 - c0) * n;
+  }
+};
+
+// The front end of the dense-H ILMM for one (H, s2, jitter): project(H, s2) on the host (reference src/ilmm.jl:61-68); T on the device
+// and, with n_noise > 0 (the points whose residual is taken), SigmaT, H and the residual's buffers (upload); given the latents, also
+// their means and, with n_noise > 0, the LatentDev array of a training matrix; then, on streams[0], the projected residuals T y - mean
+// (delta) and the regulariser's |Y - H T Y|_F^2 (residual, which leaves T y in Ty).
+struct DenseFront {
+  const double* H;
+  int p, m;
+  std::vector<double> T, ST, Hv, means;      // (the host sides of the uploads live as long as the front end)
+  std::vector<LatentDev> lat;
+  double logdetST = 0.0;
+  Uploaded Td, STd, Hd, meansd;
+  Buf<LatentDev> latd;
+  Buf<double> Ty, partial;
+  DenseFront(const double* H_, int p_, int m_) : H(H_), p(p_), m(m_) {}
+  int project(double s2, double jitter, bool logdet) { return project_dense(H, p, m, s2, jitter, T, ST, logdet ? &logdetST : nullptr); }
+  void upload(const Latent* lts, int n_noise) {
+    hipStream_t st0 = g.streams[0];
+    const bool noise = n_noise > 0;
+    Td = Uploaded(T, st0);
+    if (noise) {
+      Hv.assign(H, H + (size_t)p * m); STd = Uploaded(ST, st0); Hd = Uploaded(Hv, st0);
+      Ty = Buf<double>((size_t)n_noise * m); partial = Buf<double>(tall_skinny_partials(n_noise, p));
+    }
+    if (!lts) return;
+    means = latent_means(lts, m);
+    meansd = Uploaded(means, st0);
+    if (!noise) return;
+    lat.resize(m);
+    for (int l = 0; l < m; ++l) lat[l] = lts[l].dense_dev();
+    latd = Buf<LatentDev>(m);
+    HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  }
+  void delta(const double* yd, int n, double* out) const { project_on_device(yd, n, p, Td.buf, m, 0, m, meansd.buf.p, out, g.streams[0]); }
+  void residual(const double* yd, int n, double* resid_dev) {      // n: the n_noise of upload
+    project_on_device(yd, n, p, Td.buf, m, 0, m, nullptr, Ty.p, g.streams[0]);
+    residual_on_device(yd, n, p, Ty.p, m, Hd.buf, partial.p, resid_dev, g.streams[0]);
+  }
+};
+
+// The training matrix of the dense-H ILMM as a factor matrix A (D.NR x D.NC, D.ld): blockdiag(K_l(x, x)) + sigmaT (x) I over n points
+// and m latents -- sig_idx (device, n of them, or NULL for one block) picks each point's m x m block of sigmaT -- with nrider rider rows,
+// m n apart.  The one place that fills a DenseArgs.
+void dense_assemble(double* A, const Dims& D, const double* xd, int d, int n, int m, const LatentDev* lat, int has_sum, const double* sigmaT,
+                    const int* sig_idx, const double* rider, int nrider, hipStream_t st) {
+  DenseArgs a{};
+  a.A = A; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n; a.m = m;
+  a.lat = lat; a.sigmaT = sigmaT; a.sig_idx = sig_idx; a.rider = rider; a.rider_ld = m * n; a.nrider = nrider; a.has_sum = has_sum;
+  launch_dense_assemble(a, st);
+}
+
+// One (N x N) factorisation with nrider rider rows, N = m n: the factor matrix A and the inverse diagonal blocks W (its own, or the
+// caller's where the factor is kept), the pivot-info word (zeroed on st by the constructor), the Cholesky and, asked for, every rider's log
+// marginal likelihood (factor), and at the end of the caller's launches the values back, the stream synchronised and the pivot
+// checked (finish).  The caller assembles A in between: dense_assemble, or dense_post_cov_factor.
+struct DenseFactor {
+  int N;
+  Dims D;
+  double *A, *W;
+  Buf<double> Aown, Wown, lml_dev;
+  Buf<int> info;
+  DenseFactor(int N_, int nrider, hipStream_t st, double* A_ = nullptr, double* W_ = nullptr)
+      : N(N_), D(N_, nrider), A(A_), W(W_), lml_dev(std::max(nrider, 1)), info(1) {
+    if (!A) { Aown = Buf<double>(mat_count(D.elems())); A = Aown.p; }
+    if (!W) { Wown = Buf<double>(mat_count((size_t)(D.NC / 64) * 4096)); W = Wown.p; }
+    HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st));
+  }
+  void factor(bool lml, hipStream_t st) {
+    potrf_one(A, D.ld, D.NR, D.NC, W, N, info.p, st);
+    if (lml) launch_lml_reduce(A, D.ld, N, D.NC, (int)lml_dev.n, lml_dev.p, st);
+  }
+  int finish(double* lml, hipStream_t st) {
+    int hinfo = 0;
+    if (lml) HIPCHK(hipMemcpyAsync(lml, lml_dev.p, lml_dev.n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return check_info(std::vector<int>{hinfo}, 0);
   }
 };
 
@@ -1479,6 +1614,17 @@ static inline const lmm_post* dense_state(const lmm_post* P) { return P->base ? 
 // handle, or else from the caller's shard and resolve.  The shard's bounds (shard_check) are the caller's next step.
 static int post_dtype_check(const lmm_post* post) {
   if (post && post->f32 != g_f32) return fail(LMM_ERR_ARG, "posterior handle was built in the other compute dtype (lmm_set_compute_dtype)");
+  return LMM_OK;
+}
+// The preamble of the dense-H handle's own entry points (lmm_ilmm_post_*): the dtype, `bad` (the entry point's NULL / size test), the
+// handle's kind and d, then D, the handle that owns the device state, and the default jitters.
+static int dense_post_args(const lmm_post* post, bool bad, int d, const lmm_post*& D, const lmm_jitters_t*& jit) {
+  if (int rc = post_dtype_check(post)) return rc;
+  if (!post || bad) return fail(LMM_ERR_ARG, "bad arguments");
+  if (post->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
+  D = dense_state(post);
+  if (post->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
+  if (!jit) jit = &kDefaultJit;
   return LMM_OK;
 }
 static int post_shard(const lmm_post* P, const char* other_kind, const lmm_gp_t* gps, int m, int d, int latent_begin, int latent_end,
@@ -2013,24 +2159,18 @@ void oilmm_regulariser_grad(const double* U, const double* S, int p, int m, cons
       for (int l = 0; l < m; ++l) s -= U[a1 + (size_t)l * p] * U[b1 + (size_t)l * p];
       Pm[a1 + (size_t)b1 * p] = s;
     }
-  auto matmul = [&](const std::vector<double>& A1, int r, int c, const std::vector<double>& B1, int c2) {
-    std::vector<double> Cc((size_t)r * c2, 0.0);
-    for (int j = 0; j < c2; ++j) for (int kk = 0; kk < c; ++kk) { const double b = B1[kk + (size_t)j * c]; for (int i = 0; i < r; ++i) Cc[i + (size_t)j * r] += A1[i + (size_t)kk * r] * b; }
-    return Cc;
-  };
-  PtP = matmul(Pm, p, p, Pm, p);                               // P symmetric: P'P = P P
-  std::vector<double> Uv(U, U + (size_t)p * m);
-  std::vector<double> PU = matmul(Pm, p, p, Uv, m);
+  PtP = host_matmul(Pm.data(), false, Pm.data(), false, p, p, p);      // P symmetric: P'P = P P
+  const std::vector<double> PU = host_matmul(Pm.data(), false, U, false, p, p, m);
   for (int blk = 0; blk < nblk; ++blk) {                        // reference src/oilmm.jl:101-113, once per noise block
-    const std::vector<double> M2(M2all.begin() + pp * blk, M2all.begin() + pp * (blk + 1));
+    const double* M2 = M2all.data() + pp * blk;
     const double s2 = NB.s2[blk], cnt = NB.count(blk);
     double Rn = 0.0;                                           // |P Y|_F^2 = tr(P'P Y Y')
     for (int a1 = 0; a1 < p; ++a1) for (int b1 = 0; b1 < p; ++b1) Rn += PtP[a1 + (size_t)b1 * p] * M2[b1 + (size_t)a1 * p];
     total += oilmm_regulariser(cnt, p, m, S, s2, Rn);
     for (int l = 0; l < m; ++l) G.gS[l] += -cnt / (2.0 * S[l]);
     G.gs2[blk] += -0.5 * (cnt * (double)(p - m) / s2 - Rn / (s2 * s2));
-    std::vector<double> M2U = matmul(M2, p, p, Uv, m);
-    std::vector<double> t1 = matmul(Pm, p, p, M2U, m), t2 = matmul(M2, p, p, PU, m);
+    const std::vector<double> M2U = host_matmul(M2, false, U, false, p, p, m);
+    const std::vector<double> t1 = host_matmul(Pm.data(), false, M2U.data(), false, p, p, m), t2 = host_matmul(M2, false, PU.data(), false, p, p, m);
     for (size_t q = 0; q < G.gU.size(); ++q) G.gU[q] += (t1[q] + t2[q]) / s2;
   }
 }
@@ -2301,6 +2441,63 @@ int finish_input_grads(const double* gxj, const double* gxm, int d, int n, int n
   return LMM_OK;
 }
 
+// The driver of the predictive gradients, log p(ys | y) = log p(y, ys) - log p(y): `core(joint, x, n, NB, y, G, gy, gx)` is the model's
+// prior-gradient core (oilmm_grad_core, ilmm_grad_core), run on the joint [x; xs], [y; ys] with one noise block per conditioning batch
+// and one for the test points, then on the conditioning data alone.  xd (d x n), yd (n x p by outputs): device; xs, ys: the caller's.  ys
+// has pt <= p columns (the dense-H latent view observes m of the p outputs): the joint's other test columns are zero.  Leaves the two
+// results in GJ and GM for the model's own outputs, with GJ.ggps and GJ.trec already the differences (published, and written to
+// grad_gps), and writes every output the models share: grad_y, grad_ys (ns x pt), grad_batch_sigma2, grad_x, grad_xs.
+template <class Grad, class Core>
+int predictive_grad(const LatentSet& ls, int l0, int l1, const double* xd, const double* yd, int d, int n, const int* batch_n,
+                    const double* batch_sigma2, int nbatch, const double* xs, int ns, const double* ys, int p, int pt, double sigma2_s,
+                    Core core, Grad& GJ, Grad& GM, double* grad_y, double* grad_ys, double* grad_batch_sigma2, lmm_gp_grad_t* grad_gps,
+                    double* grad_x, double* grad_xs) {
+  hipStream_t st0 = g.streams[0];
+  const int N = n + ns;
+  const size_t col = sizeof(double);
+  DevIn xsd(xs, (size_t)d * ns, st0), ysd(ys, (size_t)ns * pt, st0);
+  Buf<double> xj((size_t)d * N), yj((size_t)N * p), gj((size_t)N * p), gm((size_t)n * p);
+  HIPCHK(hipMemcpyAsync(xj.p, xd, (size_t)d * n * col, hipMemcpyDeviceToDevice, st0));
+  HIPCHK(hipMemcpyAsync(xj.p + (size_t)d * n, xsd.p, (size_t)d * ns * col, hipMemcpyDeviceToDevice, st0));
+  if (pt < p) HIPCHK(hipMemsetAsync(yj.p, 0, (size_t)N * p * col, st0));
+  HIPCHK(hipMemcpy2DAsync(yj.p, N * col, yd, n * col, n * col, p, hipMemcpyDeviceToDevice, st0));
+  HIPCHK(hipMemcpy2DAsync(yj.p + n, N * col, ysd.p, ns * col, ns * col, pt, hipMemcpyDeviceToDevice, st0));
+  if (int rc = ls.ard_grad_check()) return rc;
+  const bool want_gx = grad_x != nullptr || grad_xs != nullptr, want_gy = grad_y != nullptr || grad_ys != nullptr;
+  if (int rc = input_grad_check(d, want_gx)) return rc;
+  if (want_gx) { if (int rc = refuse_sho(ls, "gradients with respect to the inputs are")) return rc; }
+  Buf<double> gxj, gxm;
+  if (want_gx) gxj = Buf<double>((size_t)d * N);
+  if (grad_x) gxm = Buf<double>((size_t)d * n);
+  if (int rc = core(true, xj.p, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, GJ, want_gy ? gj.p : nullptr, gxj.p)) return rc;
+  if (int rc = core(false, xd, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd, GM, grad_y ? gm.p : nullptr, gxm.p)) return rc;
+  if (int rc = finish_input_grads(gxj.p, gxm.p, d, n, ns, grad_x, grad_xs)) return rc;
+  if (grad_batch_sigma2) for (int b = 0; b < nbatch; ++b) grad_batch_sigma2[b] = GJ.gs2[b] - GM.gs2[b];
+  for (size_t l = 0; l < GJ.ggps.size(); ++l) {
+    GJ.ggps[l].variance -= GM.ggps[l].variance;
+    GJ.ggps[l].lengthscale -= GM.ggps[l].lengthscale;
+    GJ.ggps[l].mean -= GM.ggps[l].mean;
+  }
+  for (size_t q = 0; q < GJ.trec.size(); ++q) GJ.trec[q] -= GM.trec[q];
+  publish_grads(ls, grad_gps ? &GJ.trec : nullptr, l0, l1);
+  if (grad_gps) std::copy(GJ.ggps.begin(), GJ.ggps.end(), grad_gps);
+  if (grad_y) {
+    DevOut gy(grad_y, (size_t)n * p);
+    Buf<double> top((size_t)n * p);
+    HIPCHK(hipMemcpy2DAsync(top.p, n * col, gj.p, N * col, n * col, p, hipMemcpyDeviceToDevice, st0));
+    launch_vec_lin(top.p, gm.p, -1.0, n * p, gy.p, st0);
+    gy.finish(st0);
+    HIPCHK(hipStreamSynchronize(st0));
+  }
+  if (grad_ys) {
+    DevOut gys(grad_ys, (size_t)ns * pt);
+    HIPCHK(hipMemcpy2DAsync(gys.p, ns * col, gj.p + n, N * col, ns * col, pt, hipMemcpyDeviceToDevice, st0));
+    gys.finish(st0);
+    HIPCHK(hipStreamSynchronize(st0));
+  }
+  return LMM_OK;
+}
+
 void write_oilmm_grad(const OilmmGrad& G, int m, int p, double* out_logpdf, double* grad_sigma2, double* grad_S, double* grad_U,
                       lmm_gp_grad_t* grad_gps) {
   *out_logpdf = G.value;
@@ -2381,56 +2578,16 @@ int lmm_oilmm_post_logpdf_grad_seq_x(const double* x, int d, int n, const int* b
                      S, m, sigma2_s, gps, latent_begin, latent_end, 0, R)) return rc;
   if (int rc = check_batches(batch_n, batch_sigma2, nbatch, n)) return rc;
   if (!(sigma2_s > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
-  hipStream_t st0 = g.streams[0];
-  const int N = n + ns;
-  DevIn xsd(xs, (size_t)d * ns, st0), ysd(ys, (size_t)ns * p, st0);
-  Buf<double> xj((size_t)d * N), yj((size_t)N * p), gj((size_t)N * p), gm((size_t)n * p);
-  HIPCHK(hipMemcpyAsync(xj.p, R.xd.p, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, st0));
-  HIPCHK(hipMemcpyAsync(xj.p + (size_t)d * n, xsd.p, (size_t)d * ns * sizeof(double), hipMemcpyDeviceToDevice, st0));
-  HIPCHK(hipMemcpy2DAsync(yj.p, (size_t)N * sizeof(double), R.yd.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
-  HIPCHK(hipMemcpy2DAsync(yj.p + n, (size_t)N * sizeof(double), ysd.p, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
-  if (int rc = R.ls->ard_grad_check()) return rc;
-  const bool want_gx = grad_x != nullptr || grad_xs != nullptr;
-  if (int rc = input_grad_check(d, want_gx)) return rc;
-  if (want_gx) { if (int rc = refuse_sho(*R.ls, "gradients with respect to the inputs are")) return rc; }
-  const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
-  Buf<double> gxj, gxm;
-  if (want_gx) gxj = Buf<double>((size_t)d * N);
-  if (grad_x) gxm = Buf<double>((size_t)d * n);
   OilmmGrad GJ, GM;
-  if (int rc = oilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, U, S, R.ls.get(),
-                               latent_begin, latent_end, with_regulariser, GJ, want_gy ? gj.p : nullptr, gxj.p)) return rc;
-  if (int rc = oilmm_grad_core(R.xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), R.yd.p, p, U, S, R.ls.get(),
-                               latent_begin, latent_end, with_regulariser, GM, grad_y ? gm.p : nullptr, gxm.p)) return rc;
-  if (int rc = finish_input_grads(gxj.p, gxm.p, d, n, ns, grad_x, grad_xs)) return rc;
+  auto core = [&](bool, const double* xq, int nq, const NoiseBlocks& NB, const double* yq, OilmmGrad& G, double* gy, double* gx) {
+    return oilmm_grad_core(xq, d, nq, NB, yq, p, U, S, R.ls.get(), latent_begin, latent_end, with_regulariser, G, gy, gx);
+  };
+  if (int rc = predictive_grad(*R.ls, latent_begin, latent_end, R.xd.p, R.yd.p, d, n, batch_n, batch_sigma2, nbatch, xs, ns, ys, p, p, sigma2_s,
+                               core, GJ, GM, grad_y, grad_ys, grad_batch_sigma2, grad_gps, grad_x, grad_xs)) return rc;
   *out_logpdf = GJ.value - GM.value;
-  if (grad_batch_sigma2) for (int b = 0; b < nbatch; ++b) grad_batch_sigma2[b] = GJ.gs2[b] - GM.gs2[b];
   if (grad_sigma2_s) *grad_sigma2_s = GJ.gs2[nbatch];
-  for (int l = 0; l < m; ++l) {
-    if (grad_S) grad_S[l] = GJ.gS[l] - GM.gS[l];
-    if (grad_gps) {
-      grad_gps[l].variance = GJ.ggps[l].variance - GM.ggps[l].variance;
-      grad_gps[l].lengthscale = GJ.ggps[l].lengthscale - GM.ggps[l].lengthscale;
-      grad_gps[l].mean = GJ.ggps[l].mean - GM.ggps[l].mean;
-    }
-  }
+  if (grad_S) for (int l = 0; l < m; ++l) grad_S[l] = GJ.gS[l] - GM.gS[l];
   if (grad_U) for (size_t q = 0; q < (size_t)p * m; ++q) grad_U[q] = GJ.gU[q] - GM.gU[q];
-  for (size_t q = 0; q < GJ.trec.size(); ++q) GJ.trec[q] -= GM.trec[q];
-  publish_grads(*R.ls, grad_gps ? &GJ.trec : nullptr, latent_begin, latent_end);
-  if (grad_y) {
-    DevOut gy(grad_y, (size_t)n * p);
-    Buf<double> top((size_t)n * p);
-    HIPCHK(hipMemcpy2DAsync(top.p, (size_t)n * sizeof(double), gj.p, (size_t)N * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
-    launch_vec_lin(top.p, gm.p, -1.0, n * p, gy.p, st0);
-    gy.finish(st0);
-    HIPCHK(hipStreamSynchronize(st0));
-  }
-  if (grad_ys) {
-    DevOut gys(grad_ys, (size_t)ns * p);
-    HIPCHK(hipMemcpy2DAsync(gys.p, (size_t)ns * sizeof(double), gj.p + n, (size_t)N * sizeof(double), (size_t)ns * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
-    gys.finish(st0);
-    HIPCHK(hipStreamSynchronize(st0));
-  }
   return LMM_OK;
   LMM_CATCH
 }
@@ -2568,25 +2725,13 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
   if (!jit) jit = &kDefaultJit;
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
   hipStream_t st0 = g.streams[0];
-  std::vector<double> T, ST;
-  double logdetST = 0.0;
-  if (int rc = project_dense(H, p, m, sigma2, jit->project_jitter, T, ST, &logdetST)) return rc;
+  DenseFront F(H, p, m);
+  if (int rc = F.project(sigma2, jit->project_jitter, true)) return rc;
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
-  Uploaded Td(T, st0), STd(ST, st0);
-  const std::vector<double> Hv(H, H + (size_t)p * m), means = latent_means(lts, m);
-  std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) lat[l] = lts[l].dense_dev();
-  Uploaded Hd(Hv, st0), meansd(means, st0);
-  Buf<LatentDev> latd(m);
-  HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
-  // projection, residual, rider = vec(T Y) - mean
-  Buf<double> Ty((size_t)n * m), delta((size_t)n * m), partial(tall_skinny_partials(n, p)), resid_dev(1);
-  project_on_device(yd.p, n, p, Td.buf, m, 0, m, nullptr, Ty.p, st0);
-  residual_on_device(yd.p, n, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p, st0);
-  // reference src/ilmm.jl:171-181 (scalar part; the residual comes from the device below)
-  auto regulariser = [&](double resid) {
-    return -((double)n * ((double)(p - m) * kLog2Pi + ((double)p * std::log(sigma2) - logdetST)) + resid / sigma2) / 2.0;
-  };
+  F.upload(lts, n);
+  // the regulariser's residual (reference src/ilmm.jl:171-181), then the rider vec(T Y) - mean
+  Buf<double> delta((size_t)n * m), resid_dev(1);
+  F.residual(yd.p, n, resid_dev.p);
   bool identical = allow_decoupled != 0;
   for (int l = 1; l < m && identical; ++l)
     identical = lts[l].same_kernel(lts[0]);        // two tags with one alpha: one kernel
@@ -2596,14 +2741,10 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
     // SigmaT = Q Lam Q' rotates it to blockdiag(K + lam_a I), so the (mn)^3/3 factorisation becomes m independent n^3/3
     // ones on the rotated projections (Q'T) Y - Q' mu.  Same value up to rounding; not the reference's operation count.
     std::vector<double> lam, Q;
-    host_jacobi_eig(ST, m, lam, Q);
-    std::vector<double> T2((size_t)m * p, 0.0), mu2(m, 0.0);
+    host_jacobi_eig(F.ST, m, lam, Q);
+    const std::vector<double> T2 = host_matmul(Q.data(), true, F.T.data(), false, m, m, p);      // Q' T
+    std::vector<double> mu2(m, 0.0);
     for (int aI = 0; aI < m; ++aI) {
-      for (int o = 0; o < p; ++o) {
-        double s = 0.0;
-        for (int b = 0; b < m; ++b) s += Q[b + (size_t)aI * m] * T[b + (size_t)o * m];
-        T2[aI + (size_t)o * m] = s;
-      }
       for (int b = 0; b < m; ++b) mu2[aI] += Q[b + (size_t)aI * m] * lts[b].mean;
       if (!(lam[aI] > 0.0)) return fail(LMM_ERR_NOT_PD, "PosDefException: SigmaT has a non-positive eigenvalue");
     }
@@ -2616,30 +2757,18 @@ int lmm_ilmm_logpdf_ex(const double* x, int d, int n, const double* y, int p, co
     if (int rc = latent_lmls(xd.p, d, n, g2.data(), lam.data(), 0, m, delta.p, lml)) return rc;   // synchronises st0
     double total = 0.0;
     for (int l = 0; l < m; ++l) total += lml[l];
-    *out = total + regulariser(resid);
+    *out = total + ilmm_regulariser(n, p, m, sigma2, F.logdetST, resid);
     return LMM_OK;
   }
-  project_on_device(yd.p, n, p, Td.buf, m, 0, m, meansd.buf.p, delta.p, st0);
+  F.delta(yd.p, n, delta.p);
   // one dense (mn) x (mn) factorisation: reference src/ilmm.jl:160-162 (fp32 compute mode: a Float32 matrix, as the per-latent paths)
-  const int N = m * n;
-  Dims D(N, 1);
-  Buf<double> A(mat_count(D.elems())), W(mat_count((size_t)(D.NC / 64) * 4096)), lml_dev(1);
-  Buf<int> info(1);
-  HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
-  DenseArgs a{};
-  a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd.p; a.d = d; a.n = n; a.m = m;
-  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = 1; a.has_sum = ls->any_sum();
-  launch_dense_assemble(a, st0);
-  potrf_one(A.p, D.ld, D.NR, D.NC, W.p, N, info.p, st0);
-  launch_lml_reduce(A.p, D.ld, N, D.NC, 1, lml_dev.p, st0);
+  DenseFactor C(m * n, 1, st0);
+  dense_assemble(C.A, C.D, xd.p, d, n, m, F.latd.p, ls->any_sum(), F.STd.buf.p, nullptr, delta.p, 1, st0);
+  C.factor(true, st0);
   double lml = 0.0, resid = 0.0;
-  int hinfo = 0;
-  HIPCHK(hipMemcpyAsync(&lml, lml_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(&resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  if (int rc = check_info(std::vector<int>{hinfo}, 0)) return rc;
-  *out = lml + regulariser(resid);
+  if (int rc = C.finish(&lml, st0)) return rc;
+  *out = lml + ilmm_regulariser(n, p, m, sigma2, F.logdetST, resid);
   return LMM_OK;
   LMM_CATCH
 }
@@ -2663,44 +2792,24 @@ int lmm_ilmm_logpdf_multi(const double* x, int d, int n, const double* Y, int p,
   if (!jit) jit = &kDefaultJit;
   if ((long long)m * n > 2000000000LL / 64) return fail(LMM_ERR_UNSUPPORTED, "m*n too large for the dense path");
   hipStream_t st0 = g.streams[0];
-  std::vector<double> T, ST;
-  double logdetST = 0.0;
-  if (int rc = project_dense(H, p, m, sigma2, jit->project_jitter, T, ST, &logdetST)) return rc;
+  DenseFront F(H, p, m);
+  if (int rc = F.project(sigma2, jit->project_jitter, true)) return rc;
   DevIn xd(x, (size_t)d * n, st0), yd(Y, (size_t)n * p * ncol, st0);
-  Uploaded Td(T, st0), STd(ST, st0);
-  const std::vector<double> Hv(H, H + (size_t)p * m), means = latent_means(lts, m);
-  std::vector<LatentDev> lat(m);
-  for (int l = 0; l < m; ++l) lat[l] = lts[l].dense_dev();
-  Uploaded Hd(Hv, st0), meansd(means, st0);
-  Buf<LatentDev> latd(m);
-  HIPCHK(hipMemcpyAsync(latd.p, lat.data(), m * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  F.upload(lts, n);
   const int N = m * n;
-  Buf<double> Ty((size_t)N), delta((size_t)N * ncol), partial(tall_skinny_partials(n, p)), resid_dev(ncol), lml_dev(ncol);
+  Buf<double> delta((size_t)N * ncol), resid_dev(ncol);
   for (int c = 0; c < ncol; ++c) {
     const double* yc = yd.p + (size_t)c * n * p;
-    project_on_device(yc, n, p, Td.buf, m, 0, m, nullptr, Ty.p, st0);
-    residual_on_device(yc, n, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p + c, st0);
-    project_on_device(yc, n, p, Td.buf, m, 0, m, meansd.buf.p, delta.p + (size_t)c * N, st0);      // rider c: [latent][point]
+    F.residual(yc, n, resid_dev.p + c);
+    F.delta(yc, n, delta.p + (size_t)c * N);      // rider c: [latent][point]
   }
-  Dims D(N, ncol);
-  Buf<double> A(mat_count(D.elems())), W(mat_count((size_t)(D.NC / 64) * 4096));
-  Buf<int> info(1);
-  HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
-  DenseArgs a{};
-  a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd.p; a.d = d; a.n = n; a.m = m;
-  a.lat = latd.p; a.sigmaT = STd.buf.p; a.rider = delta.p; a.rider_ld = N; a.nrider = ncol; a.has_sum = ls->any_sum();
-  launch_dense_assemble(a, st0);
-  potrf_one(A.p, D.ld, D.NR, D.NC, W.p, N, info.p, st0);
-  launch_lml_reduce(A.p, D.ld, N, D.NC, ncol, lml_dev.p, st0);
+  DenseFactor C(N, ncol, st0);
+  dense_assemble(C.A, C.D, xd.p, d, n, m, F.latd.p, ls->any_sum(), F.STd.buf.p, nullptr, delta.p, ncol, st0);
+  C.factor(true, st0);
   std::vector<double> lml(ncol), resid(ncol);
-  int hinfo = 0;
-  HIPCHK(hipMemcpyAsync(lml.data(), lml_dev.p, ncol * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(resid.data(), resid_dev.p, ncol * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  if (int rc = check_info(std::vector<int>{hinfo}, 0)) return rc;
-  for (int c = 0; c < ncol; ++c)      // reference src/ilmm.jl:171-181
-    out[c] = lml[c] - ((double)n * ((double)(p - m) * kLog2Pi + ((double)p * std::log(sigma2) - logdetST)) + resid[c] / sigma2) / 2.0;
+  if (int rc = C.finish(lml.data(), st0)) return rc;
+  for (int c = 0; c < ncol; ++c) out[c] = lml[c] + ilmm_regulariser(n, p, m, sigma2, F.logdetST, resid[c]);
   return LMM_OK;
   LMM_CATCH
 }
@@ -2781,23 +2890,17 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
     launch_tall_skinny(Ty.p + i0, n, nb_, m, Hdv[b], p, p, nullptr, 0, nullptr, yd + i0, n, partial.p, 1, st0);
     launch_sum_partials(partial.p, tall_skinny_partials(nb_, p), resid_dev.p + b, st0);
   }
-  Dims D(N, 1);
-  Buf<double> A(mat_count(D.elems())), W(mat_count((size_t)(D.NC / 64) * 4096)), R(mat_count((size_t)D.ld * D.NC)), alpha((size_t)D.NC), lml_dev(1);
-  Buf<int> info(1);
-  HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
+  DenseFactor C(N, 1, st0);
+  const Dims& D = C.D;
+  Buf<double> R(mat_count((size_t)D.ld * D.NC)), alpha((size_t)D.NC);
   HIPCHK(hipMemsetAsync(alpha.p, 0, (size_t)D.NC * sizeof(double), st0));
-  DenseArgs a{};
-  a.A = A.p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = xd; a.d = d; a.n = n; a.m = m;
-  a.lat = latd.p; a.sigmaT = STd.buf.p; a.sig_idx = nblk > 1 ? sidxd.p : nullptr; a.rider = delta.p; a.rider_ld = N; a.nrider = 1;
-  a.has_sum = ls->any_sum();
-  launch_dense_assemble(a, st0);
-  potrf_one(A.p, D.ld, D.NR, D.NC, W.p, N, info.p, st0);
-  launch_lml_reduce(A.p, D.ld, N, D.NC, 1, lml_dev.p, st0);
-  launch_extract_row(A.p, D.ld, D.NC, N, alpha.p, st0);
-  backsolve1(A.p, D.ld, W.p, D.NC / 64, alpha.p, st0);
+  dense_assemble(C.A, D, xd, d, n, m, latd.p, ls->any_sum(), STd.buf.p, nblk > 1 ? sidxd.p : nullptr, delta.p, 1, st0);
+  C.factor(true, st0);
+  launch_extract_row(C.A, D.ld, D.NC, N, alpha.p, st0);
+  backsolve1(C.A, D.ld, C.W, D.NC / 64, alpha.p, st0);
   launch_set_identity(R.p, D.ld, D.NC, st0);
-  trsm_rec(R.p, D.ld, D.NC, A.p, D.ld, W.p, 0, D.NC, st0, true);                 // R = L^-T
-  launch_syrk_upper_set(A.p, D.ld, R.p, D.ld, D.NC, st0);                         // lower(A) = Sigma^-1
+  trsm_rec(R.p, D.ld, D.NC, C.A, D.ld, C.W, 0, D.NC, st0, true);                   // R = L^-T
+  launch_syrk_upper_set(C.A, D.ld, R.p, D.ld, D.NC, st0);                           // lower(A) = Sigma^-1
   const int NGR = LMM_NGRAD;
   const size_t mm = (size_t)m * m, mp = (size_t)m * p;
   const std::vector<int> toff = ls->term_offsets(0, m);       // one reduction per term of every latent
@@ -2806,7 +2909,7 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   Buf<double> ardred((size_t)d * nterm), gxpart;
   if (gx_dev) gxpart = Buf<double>(grad_x_partial_elems(n, d));
   for (int l = 0; l < m; ++l) {
-    const double* Kl = mat_at(A.p, (size_t)l * n * D.ld + (size_t)l * n);
+    const double* Kl = mat_at(C.A, (size_t)l * n * D.ld + (size_t)l * n);
     for (int c = 0; c < lts[l].nt(); ++c) {
       const LatentDev& gd = lts[l].terms[c].gd;
       const size_t t = (size_t)toff[l] + c;
@@ -2824,7 +2927,7 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
     launch_tall_skinny(Rm.p + bi0[b], n, bn[b], p, Htdv[b], m, m, RH.p + bi0[b], n, nullptr, nullptr, 0, nullptr, 0, st0);
   for (int b = 0; b < nblk; ++b) {
     const int i0 = bi0[b], nb_ = bn[b];
-    launch_block_trace(A.p, D.ld, n, m, i0, i0 + nb_, Btr.p + b * mm, st0);
+    launch_block_trace(C.A, D.ld, n, m, i0, i0 + nb_, Btr.p + b * mm, st0);
     launch_atb(alpha.p + i0, n, alpha.p + i0, n, nb_, m, m, AAt.p + b * mm, st0);      // (alpha_l . alpha_l') over the block
     launch_atb(alpha.p + i0, n, yd + i0, n, nb_, m, p, AY.p + b * mp, st0);            // sum_i alpha_l[i] Y[i, o]   (m x p)
     launch_atb(Rm.p + i0, n, Ty.p + i0, n, nb_, p, m, RtTy.p + b * mp, st0);
@@ -2832,10 +2935,7 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   }
   std::vector<double> hred((size_t)NGR * nterm), hB(KB * mm), hAAt(KB * mm), hAY(KB * mp), hRtTy(KB * mp), hRHtY(KB * mp);
   double lml = 0.0, resid[KB] = {};
-  int hinfo = 0;
-  HIPCHK(hipMemcpyAsync(&lml, lml_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(resid, resid_dev.p, nblk * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hred.data(), red.p, hred.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   std::vector<double> hard(ard_d ? (size_t)d * nterm : 0, 0.0);
   if (!hard.empty()) HIPCHK(hipMemcpyAsync(hard.data(), ardred.p, hard.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
@@ -2844,12 +2944,11 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
   HIPCHK(hipMemcpyAsync(hAY.data(), AY.p, nblk * mp * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hRtTy.data(), RtTy.p, nblk * mp * sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(hRHtY.data(), RHtY.p, nblk * mp * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  if (int rc = check_info(std::vector<int>{hinfo}, 0)) return rc;
+  if (int rc = C.finish(&lml, st0)) return rc;
   // value: reference src/ilmm.jl:150-163 + :171-181
   G.value = lml;
   for (int b = 0; b < nblk; ++b)
-    G.value -= ((double)bn[b] * ((double)(p - m) * kLog2Pi + ((double)p * std::log(s2[b]) - logdetST[b])) + resid[b] / s2[b]) / 2.0;
+    G.value += ilmm_regulariser(bn[b], p, m, s2[b], logdetST[b], resid[b]);
   // ---- kernel-parameter gradients: 1/2 tr((aa' - Sigma^-1) dSigma/dtheta_l), dSigma = E_ll (x) dK_l ----
   G.ggps.assign(m, lmm_gp_grad_t{});
   G.trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
@@ -2859,87 +2958,28 @@ int ilmm_grad_core(const double* xd, int d, int n, const NoiseBlocks& NB, const 
                                         &G.trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)], &G.ggps[l].variance);
     G.ggps[l].mean = r[4];
   }
-  std::vector<double> Hacc((size_t)p * m, 0.0), HtH(mm, 0.0);
+  // ---- per block: the cotangents of its T (m x p) and SigmaT (m x m), then backward through project(H_b, sigma2_b) ----
+  G.gH.assign(mp, 0.0);
   for (int b = 0; b < nblk; ++b) {
-    const double* H = Hq[b];                        // (shadows the argument: everything below differentiates through THIS block's mixing matrix)
-    std::vector<double> Hb((size_t)p * m, 0.0);     // its cotangent; kept only for the blocks observed through the model's H
-    for (int aI = 0; aI < m; ++aI)
-      for (int bb = 0; bb < m; ++bb) {
-        double acc = 0.0;
-        for (int o = 0; o < p; ++o) acc += H[o + (size_t)aI * p] * H[o + (size_t)bb * p];
-        HtH[aI + (size_t)bb * m] = acc;
-      }
-    const double sigma2 = s2[b], s = 1.0 / sigma2;
-    const std::vector<double>& Tq = T[b];
+    const double s = 1.0 / s2[b];
     const double* bAY = &hAY[b * mp]; const double* bRHtY = &hRHtY[b * mp]; const double* bRtTy = &hRtTy[b * mp];
     const double* bAAt = &hAAt[b * mm]; const double* bB = &hB[b * mm];
-    // ---- cotangents of T (m x p) and SigmaT (m x m) of this block ----
-    std::vector<double> Tb((size_t)m * p, 0.0), Gs(mm, 0.0);
-    double s2g = 0.0;
-    for (int l = 0; l < m; ++l)
-      for (int o = 0; o < p; ++o) Tb[l + (size_t)o * m] = -bAY[l + (size_t)o * m] + s * bRHtY[l + (size_t)o * m];   // lml + regulariser (residual)
+    std::vector<double> Tb(mp), Gs(mm), Hb(mp, 0.0);      // Hb: kept only for the blocks observed through the model's H
+    for (size_t q = 0; q < mp; ++q) Tb[q] = -bAY[q] + s * bRHtY[q];            // lml + regulariser (residual)
     // SigmaT^-1 for the +n/2 logdet SigmaT term of the regulariser
     std::vector<double> STc = ST[b], STinv(mm, 0.0);
     if (!host_cholesky(STc, m)) return fail(LMM_ERR_NOT_PD, "PosDefException: SigmaT not PD");
-    for (int c = 0; c < m; ++c) {       // solve (L L') col = e_c
-      std::vector<double> v(m, 0.0);
-      for (int aI = 0; aI < m; ++aI) { double t = (aI == c) ? 1.0 : 0.0; for (int k = 0; k < aI; ++k) t -= STc[aI + (size_t)k * m] * v[k]; v[aI] = t / STc[aI + (size_t)aI * m]; }
-      for (int aI = m - 1; aI >= 0; --aI) { double t = v[aI]; for (int k = aI + 1; k < m; ++k) t -= STc[k + (size_t)aI * m] * v[k]; v[aI] = t / STc[aI + (size_t)aI * m]; }
-      for (int aI = 0; aI < m; ++aI) STinv[aI + (size_t)c * m] = v[aI];
-    }
-    for (int aI = 0; aI < m; ++aI)
-      for (int bb = 0; bb < m; ++bb) Gs[aI + (size_t)bb * m] = 0.5 * (bAAt[aI + (size_t)bb * m] - bB[aI + (size_t)bb * m]) + 0.5 * (double)bn[b] * STinv[aI + (size_t)bb * m];
+    for (int l = 0; l < m; ++l) STinv[l + (size_t)l * m] = 1.0;
+    host_chol_solve(STc, m, STinv.data(), m);
+    for (size_t q = 0; q < mm; ++q) Gs[q] = 0.5 * (bAAt[q] - bB[q]) + 0.5 * (double)bn[b] * STinv[q];
     // explicit sigma2 of the regulariser and explicit H of the residual
-    s2g += -0.5 * ((double)bn[b] * (double)p / sigma2 - resid[b] / (sigma2 * sigma2));
-    for (int o = 0; o < p; ++o) for (int l = 0; l < m; ++l) Hb[o + (size_t)l * p] += s * bRtTy[o + (size_t)l * p];
-    // ---- backward through project(H, sigma2): P = s H'H + eps I,  T = P^-1 H' s,  SigmaT = sigma2 T T' ----
-    // SigmaT = sigma2 T T':  Tb += sigma2 (Gs + Gs') T;  s2g += <Gs, T T'>
-    for (int aI = 0; aI < m; ++aI)
-      for (int o = 0; o < p; ++o) {
-        double acc = 0.0;
-        for (int bb = 0; bb < m; ++bb) acc += (Gs[aI + (size_t)bb * m] + Gs[bb + (size_t)aI * m]) * Tq[bb + (size_t)o * m];
-        Tb[aI + (size_t)o * m] += sigma2 * acc;
-      }
-    for (int aI = 0; aI < m; ++aI)
-      for (int bb = 0; bb < m; ++bb) {
-        double tt = 0.0;
-        for (int o = 0; o < p; ++o) tt += Tq[aI + (size_t)o * m] * Tq[bb + (size_t)o * m];
-        s2g += Gs[aI + (size_t)bb * m] * tt;
-      }
-    // P and its Cholesky
-    std::vector<double> P(mm, 0.0);
-    for (int aI = 0; aI < m; ++aI)
-      for (int bb = 0; bb < m; ++bb) P[aI + (size_t)bb * m] = s * HtH[aI + (size_t)bb * m] + (aI == bb ? jit->project_jitter : 0.0);
-    if (!host_cholesky(P, m)) return fail(LMM_ERR_NOT_PD, "PosDefException in project(H, sigma2)");
-    // Mb = P^-1 Tb (m x p);  Pb = -Mb T'
-    std::vector<double> Mb((size_t)m * p, 0.0), Pb(mm, 0.0);
-    for (int o = 0; o < p; ++o) {
-      std::vector<double> v(m);
-      for (int aI = 0; aI < m; ++aI) { double t = Tb[aI + (size_t)o * m]; for (int k = 0; k < aI; ++k) t -= P[aI + (size_t)k * m] * v[k]; v[aI] = t / P[aI + (size_t)aI * m]; }
-      for (int aI = m - 1; aI >= 0; --aI) { double t = v[aI]; for (int k = aI + 1; k < m; ++k) t -= P[k + (size_t)aI * m] * v[k]; v[aI] = t / P[aI + (size_t)aI * m]; }
-      for (int aI = 0; aI < m; ++aI) Mb[aI + (size_t)o * m] = v[aI];
-    }
-    for (int aI = 0; aI < m; ++aI)
-      for (int bb = 0; bb < m; ++bb) {
-        double acc = 0.0;
-        for (int o = 0; o < p; ++o) acc += Mb[aI + (size_t)o * m] * Tq[bb + (size_t)o * m];
-        Pb[aI + (size_t)bb * m] = -acc;
-      }
-    double sb = 0.0;       // cotangent of s = 1 / sigma2
-    for (int o = 0; o < p; ++o)
-      for (int l = 0; l < m; ++l) {
-        Hb[o + (size_t)l * p] += s * Mb[l + (size_t)o * m];                      // M = H' s
-        sb += Mb[l + (size_t)o * m] * H[o + (size_t)l * p];
-        double acc = 0.0;                                                        // P = s H'H: Hb += s H (Pb + Pb')
-        for (int bb = 0; bb < m; ++bb) acc += H[o + (size_t)bb * p] * (Pb[bb + (size_t)l * m] + Pb[l + (size_t)bb * m]);
-        Hb[o + (size_t)l * p] += s * acc;
-      }
-    for (int aI = 0; aI < m; ++aI) for (int bb = 0; bb < m; ++bb) sb += Pb[aI + (size_t)bb * m] * HtH[aI + (size_t)bb * m];
-    s2g += -sb * s * s;
+    double s2g = 0.0;
+    s2g += -0.5 * ((double)bn[b] * (double)p / s2[b] - resid[b] / (s2[b] * s2[b]));
+    for (size_t q = 0; q < mp; ++q) Hb[q] += s * bRtTy[q];
+    if (int rc = project_dense_backward(Hq[b], p, m, s2[b], jit->project_jitter, T[b], Tb, Gs, Hb, s2g)) return rc;
     G.gs2[b] = s2g;
-    if (!(Hblk && Hblk[b])) for (size_t q = 0; q < Hacc.size(); ++q) Hacc[q] += Hb[q];
+    if (!(Hblk && Hblk[b])) for (size_t q = 0; q < mp; ++q) G.gH[q] += Hb[q];
   }
-  G.gH = Hacc;
   if (gy_dev) {
     // dL/dY (n x p) = -((alpha - RH / sigma2_i) T_i) - Rm / sigma2_i     (alpha as the n x m matrix [point][latent])
     Buf<double> Z((size_t)N), ZT((size_t)n * p);
@@ -3019,14 +3059,7 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
   if (!(sigma2_s > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
   if (!jit) jit = &kDefaultJit;
   hipStream_t st0 = g.streams[0];
-  const int N = n + ns, pt = latent_test ? m : p;          // columns of ys
-  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0), xsd(xs, (size_t)d * ns, st0), ysd(ys, (size_t)ns * pt, st0);
-  Buf<double> xj((size_t)d * N), yj((size_t)N * p), gj((size_t)N * p), gm((size_t)n * p);
-  HIPCHK(hipMemcpyAsync(xj.p, xd.p, (size_t)d * n * sizeof(double), hipMemcpyDeviceToDevice, st0));
-  HIPCHK(hipMemcpyAsync(xj.p + (size_t)d * n, xsd.p, (size_t)d * ns * sizeof(double), hipMemcpyDeviceToDevice, st0));
-  if (pt < p) HIPCHK(hipMemsetAsync(yj.p, 0, (size_t)N * p * sizeof(double), st0));        // the test block's columns m .. p-1 stay 0
-  HIPCHK(hipMemcpy2DAsync(yj.p, (size_t)N * sizeof(double), yd.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
-  HIPCHK(hipMemcpy2DAsync(yj.p + n, (size_t)N * sizeof(double), ysd.p, (size_t)ns * sizeof(double), (size_t)ns * sizeof(double), pt, hipMemcpyDeviceToDevice, st0));
+  DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
   // The latent view observes its test points through H* = [I_m; 0] (p x m): z embedded in the first m of p output columns.  project(H*,
   // s) gives T = [I 0], SigmaT = s I (src/ilmm.jl:61-68) -- the latent FiniteGP's own noise -- and a residual of 0; what the p - m
   // padded columns add to the regulariser, -ns (p - m) log(2 pi s) / 2, is taken out again below.
@@ -3037,47 +3070,16 @@ int ilmm_post_logpdf_grad_impl(bool latent_test, const double* x, int d, int n, 
     for (int l = 0; l < m; ++l) Hlat[l + (size_t)l * p] = 1.0;
     Hblk[nbatch] = Hlat.data();
   }
-  if (int rc = ls->ard_grad_check()) return rc;
-  const bool want_gx = grad_x != nullptr || grad_xs != nullptr;
-  if (int rc = input_grad_check(d, want_gx)) return rc;
-  if (want_gx) { if (int rc = refuse_sho(*ls, "gradients with respect to the inputs are")) return rc; }
-  const bool want_gy = grad_y != nullptr || grad_ys != nullptr;
-  Buf<double> gxj, gxm;
-  if (want_gx) gxj = Buf<double>((size_t)d * N);
-  if (grad_x) gxm = Buf<double>((size_t)d * n);
   IlmmGrad GJ, GM;
-  if (int rc = ilmm_grad_core(xj.p, d, N, batch_noise_blocks(batch_n, batch_sigma2, nbatch, ns, sigma2_s), yj.p, p, H, m, ls.get(), jit, GJ,
-                              want_gy ? gj.p : nullptr, latent_test ? Hblk : nullptr, gxj.p)) return rc;
-  if (int rc = ilmm_grad_core(xd.p, d, n, batch_noise_blocks(batch_n, batch_sigma2, nbatch, 0, 0.0), yd.p, p, H, m, ls.get(), jit, GM,
-                              grad_y ? gm.p : nullptr, nullptr, gxm.p)) return rc;
-  if (int rc = finish_input_grads(gxj.p, gxm.p, d, n, ns, grad_x, grad_xs)) return rc;
+  auto core = [&](bool joint, const double* xq, int nq, const NoiseBlocks& NB, const double* yq, IlmmGrad& G, double* gy, double* gx) {
+    return ilmm_grad_core(xq, d, nq, NB, yq, p, H, m, ls.get(), jit, G, gy, joint && latent_test ? Hblk : nullptr, gx);
+  };
+  if (int rc = predictive_grad(*ls, 0, m, xd.p, yd.p, d, n, batch_n, batch_sigma2, nbatch, xs, ns, ys, p, latent_test ? m : p, sigma2_s, core,
+                               GJ, GM, grad_y, grad_ys, grad_batch_sigma2, grad_gps, grad_x, grad_xs)) return rc;
   const double pad = latent_test ? 0.5 * (double)ns * (double)(p - m) : 0.0;
   *out_logpdf = GJ.value - GM.value + pad * (kLog2Pi + std::log(sigma2_s));
-  if (grad_batch_sigma2) for (int b = 0; b < nbatch; ++b) grad_batch_sigma2[b] = GJ.gs2[b] - GM.gs2[b];
   if (grad_sigma2_s) *grad_sigma2_s = GJ.gs2[nbatch] + pad / sigma2_s;
   if (grad_H) for (size_t q = 0; q < (size_t)p * m; ++q) grad_H[q] = GJ.gH[q] - GM.gH[q];
-  if (grad_gps)
-    for (int l = 0; l < m; ++l) {
-      grad_gps[l].variance = GJ.ggps[l].variance - GM.ggps[l].variance;
-      grad_gps[l].lengthscale = GJ.ggps[l].lengthscale - GM.ggps[l].lengthscale;
-      grad_gps[l].mean = GJ.ggps[l].mean - GM.ggps[l].mean;
-    }
-  for (size_t q = 0; q < GJ.trec.size(); ++q) GJ.trec[q] -= GM.trec[q];
-  publish_grads(*ls, grad_gps ? &GJ.trec : nullptr, 0, m);
-  if (grad_y) {
-    DevOut gy(grad_y, (size_t)n * p);
-    Buf<double> top((size_t)n * p);
-    HIPCHK(hipMemcpy2DAsync(top.p, (size_t)n * sizeof(double), gj.p, (size_t)N * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyDeviceToDevice, st0));
-    launch_vec_lin(top.p, gm.p, -1.0, n * p, gy.p, st0);
-    gy.finish(st0);
-    HIPCHK(hipStreamSynchronize(st0));
-  }
-  if (grad_ys) {
-    DevOut gys(grad_ys, (size_t)ns * pt);
-    HIPCHK(hipMemcpy2DAsync(gys.p, (size_t)ns * sizeof(double), gj.p + n, (size_t)N * sizeof(double), (size_t)ns * sizeof(double), pt, hipMemcpyDeviceToDevice, st0));
-    gys.finish(st0);
-    HIPCHK(hipStreamSynchronize(st0));
-  }
   return LMM_OK;
 }
 }  // namespace
@@ -3542,22 +3544,14 @@ static int dense_posterior_build(const double* xd, int d, int n, const double* H
     P->W.emplace_back(mat_count((size_t)(D.NC / 64) * 4096));
     P->alpha.emplace_back((size_t)D.NC);
     P->z.emplace_back((size_t)D.NC);          // z = L^-1 delta (the rider row): the fp32 mode's means are mu + R' z, not mu + K(x*, x) alpha
-    Buf<int> info(1);
-    HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
-    DenseArgs a{};
-    a.A = P->L[0].p; a.ld = D.ld; a.nrows = D.NR; a.ncols = D.NC; a.x = P->x.p; a.d = d; a.n = n; a.m = m;
-    a.lat = P->latd.p; a.sigmaT = STd.buf.p; a.sig_idx = idxd.p; a.rider = P->ddelta.p; a.rider_ld = N; a.nrider = 1;
-    a.has_sum = P->ls->any_sum();
-    launch_dense_assemble(a, st0);
-    potrf_one(P->L[0].p, D.ld, D.NR, D.NC, P->W[0].p, N, info.p, st0);
+    DenseFactor C(N, 1, st0, P->L[0].p, P->W[0].p);      // the handle keeps the factor
+    dense_assemble(C.A, D, P->x.p, d, n, m, P->latd.p, P->ls->any_sum(), STd.buf.p, idxd.p, P->ddelta.p, 1, st0);
+    C.factor(false, st0);
     HIPCHK(hipMemsetAsync(P->alpha[0].p, 0, (size_t)D.NC * sizeof(double), st0));
-    launch_extract_row(P->L[0].p, D.ld, D.NC, N, P->alpha[0].p, st0);
+    launch_extract_row(C.A, D.ld, D.NC, N, P->alpha[0].p, st0);
     HIPCHK(hipMemcpyAsync(P->z[0].p, P->alpha[0].p, (size_t)D.NC * sizeof(double), hipMemcpyDeviceToDevice, st0));
-    backsolve1(P->L[0].p, D.ld, P->W[0].p, D.NC / 64, P->alpha[0].p, st0);
-    int hinfo = 0;
-    HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
-    HIPCHK(hipStreamSynchronize(st0));
-    if (int rc = check_info(std::vector<int>{hinfo}, 0)) { delete P; return rc; }
+    backsolve1(C.A, D.ld, C.W, D.NC / 64, P->alpha[0].p, st0);
+    if (int rc = C.finish(nullptr, st0)) { delete P; return rc; }
   } catch (int code) { drain_after_error(); delete P; return code; }
   *out = P;
   return LMM_OK;
@@ -3574,15 +3568,13 @@ int lmm_ilmm_posterior_create(const double* x, int d, int n, const double* y, in
   RESOLVE(gps, m, d);
   if (!jit) jit = &kDefaultJit;
   hipStream_t st0 = g.streams[0];
-  std::vector<double> T, ST;
-  if (int rc = project_dense(H, p, m, sigma2, jit->project_jitter, T, ST, nullptr)) return rc;
+  DenseFront F(H, p, m);
+  if (int rc = F.project(sigma2, jit->project_jitter, false)) return rc;
   DevIn xd(x, (size_t)d * n, st0), yd(y, (size_t)n * p, st0);
-  Uploaded Td(T, st0);
-  const std::vector<double> means = latent_means(lts, m);
-  Uploaded meansd(means, st0);
+  F.upload(lts, 0);
   Buf<double> delta((size_t)n * m);
-  project_on_device(yd.p, n, p, Td.buf, m, 0, m, meansd.buf.p, delta.p, st0);
-  return dense_posterior_build(xd.p, d, n, H, p, ls, delta.p, ST, std::vector<int>(n, 0), out);
+  F.delta(yd.p, n, delta.p);
+  return dense_posterior_build(xd.p, d, n, H, p, ls, delta.p, F.ST, std::vector<int>(n, 0), out);
   LMM_CATCH
 }
 
@@ -3594,23 +3586,17 @@ int lmm_ilmm_post_condition(const lmm_post_t* post, double sigma2, const double*
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (int rc = post_dtype_check(post)) return rc;
-  if (!post || !x2 || !y2 || !out || d <= 0 || n2 <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
-  if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
-  const lmm_post* D = dense_state(P);
-  if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  if (!jit) jit = &kDefaultJit;
+  const lmm_post* D = nullptr;
+  if (int rc = dense_post_args(post, !x2 || !y2 || !out || d <= 0 || n2 <= 0, d, D, jit)) return rc;
   hipStream_t st0 = g.streams[0];
   const int m = P->m, p = P->p, n1 = P->n, n = n1 + n2;
-  std::vector<double> T, ST;
-  if (int rc = project_dense(P->H.data(), p, m, sigma2, jit->project_jitter, T, ST, nullptr)) return rc;
+  DenseFront F(P->H.data(), p, m);
+  if (int rc = F.project(sigma2, jit->project_jitter, false)) return rc;
   DevIn x2d(x2, (size_t)d * n2, st0), y2d(y2, (size_t)n2 * p, st0);
-  Uploaded Td(T, st0);
-  const std::vector<double> means = latent_means(P->ls->lat.data(), m);
-  Uploaded meansd(means, st0);
+  F.upload(P->ls->lat.data(), 0);
   Buf<double> d2((size_t)n2 * m), delta((size_t)n * m), xall((size_t)d * n);
-  project_on_device(y2d.p, n2, p, Td.buf, m, 0, m, meansd.buf.p, d2.p, st0);
+  F.delta(y2d.p, n2, d2.p);
   HIPCHK(hipMemcpyAsync(xall.p, D->x.p, (size_t)d * n1 * sizeof(double), hipMemcpyDeviceToDevice, st0));
   HIPCHK(hipMemcpyAsync(xall.p + (size_t)d * n1, x2d.p, (size_t)d * n2 * sizeof(double), hipMemcpyDeviceToDevice, st0));
   for (int l = 0; l < m; ++l) {
@@ -3618,7 +3604,7 @@ int lmm_ilmm_post_condition(const lmm_post_t* post, double sigma2, const double*
     HIPCHK(hipMemcpyAsync(delta.p + (size_t)l * n + n1, d2.p + (size_t)l * n2, (size_t)n2 * sizeof(double), hipMemcpyDeviceToDevice, st0));
   }
   std::vector<double> sigs = P->sigs;
-  sigs.insert(sigs.end(), ST.begin(), ST.end());
+  sigs.insert(sigs.end(), F.ST.begin(), F.ST.end());
   std::vector<int> idx = P->sigidx;
   idx.resize(n, (int)(P->sigs.size() / ((size_t)m * m)));
   return dense_posterior_build(xall.p, d, n, P->H.data(), p, P->ls, delta.p, sigs, idx, out);
@@ -3633,13 +3619,9 @@ int lmm_ilmm_post_mean_and_var(const lmm_post_t* post, double sigma2, const doub
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (int rc = post_dtype_check(post)) return rc;
-  if (!post || !xs || !mean_out || !var_out || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
-  if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
-  const lmm_post* D = dense_state(P);
-  if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  if (!jit) jit = &kDefaultJit;
+  const lmm_post* D = nullptr;
+  if (int rc = dense_post_args(post, !xs || !mean_out || !var_out || d <= 0 || ns <= 0, d, D, jit)) return rc;
   hipStream_t st0 = g.streams[0];
   const int m = P->m, p = P->p, n = P->n, N = m * n;
   DevIn xsd(xs, (size_t)d * ns, st0);
@@ -3688,20 +3670,13 @@ static void dense_post_means(const lmm_post* P, const double* xsd, int d, int ns
   HIPCHK(hipStreamSynchronize(st));
 }
 // Latent joint covariance at xs as a factor matrix,  blockdiag(K_l(xs,xs)) + SigAdd (x) I_ns - R R'  (R from dense_post_cross with
-// nr = Ds.NC rows), optional rider row, then its Cholesky.
+// nr = Ds.NC rows), optional rider row; a caller that wants its Cholesky gives the A of a DenseFactor and factors that.
 static void dense_post_cov_factor(const lmm_post* P, const double* xsd, int d, int ns, const double* sigadd_dev,
-                                  const double* rider, const Dims& Ds, double* A, double* WA, const double* R, int ldr, int* info,
-                                  hipStream_t st, bool factor = true) {
-  const int m = P->m;
+                                  const double* rider, const Dims& Ds, double* A, const double* R, int ldr, hipStream_t st) {
   const lmm_post* D = dense_state(P);
-  DenseArgs a{};
-  a.A = A; a.ld = Ds.ld; a.nrows = Ds.NR; a.ncols = Ds.NC; a.x = xsd; a.d = d; a.n = ns; a.m = m;
-  a.lat = D->latd.p; a.sigmaT = sigadd_dev; a.rider = rider; a.rider_ld = m * ns; a.nrider = rider ? 1 : 0;
-  a.has_sum = D->ls->any_sum();
   guard_extent(A, Ds.NR, Ds.ld, Ds.NC, true, "dense-H posterior covariance");
-  launch_dense_assemble(a, st);
+  dense_assemble(A, Ds, xsd, d, ns, P->m, D->latd.p, D->ls->any_sum(), sigadd_dev, nullptr, rider, rider ? 1 : 0, st);
   gemm_nt_g(A, Ds.ld, R, ldr, R, ldr, Ds.NC, Ds.NC, P->NC, 1, false, st, "Schur complement (dense-H posterior covariance)");
-  if (factor) potrf_one(A, Ds.ld, Ds.NR, Ds.NC, WA, m * ns, info, st);
 }
 
 // mean_and_cov(pi(xs, sigma2)) / cov on the dense-H posterior ILMM (reference src/ilmm.jl:132-147 with the PosteriorGP latent
@@ -3712,14 +3687,10 @@ int lmm_ilmm_post_mean_and_cov(const lmm_post_t* post, double sigma2, const doub
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (int rc = post_dtype_check(post)) return rc;
-  if (!post || !xs || !mean_out || !cov_out || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
-  if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
-  const lmm_post* D = dense_state(P);
-  if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  if (!jit) jit = &kDefaultJit;
-  const int m = P->m, p = P->p, n = P->n, Ns = m * ns;
+  const lmm_post* D = nullptr;
+  if (int rc = dense_post_args(post, !xs || !mean_out || !cov_out || d <= 0 || ns <= 0, d, D, jit)) return rc;
+  const int m = P->m, p = P->p, Ns = m * ns;
   if ((double)p * ns * (double)p * ns > 4e8) return fail(LMM_ERR_UNSUPPORTED, "full covariance (p*ns)^2 too large");
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)d * ns, st0);
@@ -3730,7 +3701,7 @@ int lmm_ilmm_post_mean_and_cov(const lmm_post_t* post, double sigma2, const doub
   Buf<double> A(mat_count(Ds.elems())), R(mat_count((size_t)ldr * P->NC)), T((size_t)p * ns * Ns);
   dense_post_cross(P, xsd.p, d, ns, Ds.NC, R.p, ldr, st0);
   dense_post_means(P, xsd.p, d, ns, R.p, ldr, ml.p, st0);
-  dense_post_cov_factor(P, xsd.p, d, ns, Zd.buf.p, nullptr, Ds, A.p, nullptr, R.p, ldr, nullptr, st0, false);
+  dense_post_cov_factor(P, xsd.p, d, ns, Zd.buf.p, nullptr, Ds, A.p, R.p, ldr, st0);
   DevOut mo(mean_out, (size_t)ns * p), co(cov_out, (size_t)ns * p * ns * p);
   launch_mix(ml.p, ns, m, Hd.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, mo.p, st0);
   launch_dense_cov(A.p, Ds.ld, ns, m, Hd.buf.p, p, jit->default_jitter, sigma2, T.p, co.p, st0);
@@ -3747,41 +3718,30 @@ int lmm_ilmm_post_logpdf(const lmm_post_t* post, double sigma2, const double* xs
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (int rc = post_dtype_check(post)) return rc;
-  if (!post || !xs || !ys || !out || d <= 0 || ns <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
-  if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
-  const lmm_post* D = dense_state(P);
-  if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  if (!jit) jit = &kDefaultJit;
+  const lmm_post* D = nullptr;
+  if (int rc = dense_post_args(post, !xs || !ys || !out || d <= 0 || ns <= 0, d, D, jit)) return rc;
   hipStream_t st0 = g.streams[0];
-  const int m = P->m, p = P->p, n = P->n, Ns = m * ns;
-  std::vector<double> T, ST;
-  double logdetST = 0.0;
-  if (int rc = project_dense(P->H.data(), p, m, sigma2, jit->project_jitter, T, ST, &logdetST)) return rc;
+  const int m = P->m, p = P->p, Ns = m * ns;
+  DenseFront F(P->H.data(), p, m);
+  if (int rc = F.project(sigma2, jit->project_jitter, true)) return rc;
   DevIn xsd(xs, (size_t)d * ns, st0), ysd(ys, (size_t)ns * p, st0);
-  Uploaded Td(T, st0), STd(ST, st0), Hd(P->H, st0);
-  Buf<double> Ty((size_t)ns * m), ml((size_t)ns * m), delta((size_t)ns * m), partial(tall_skinny_partials(ns, p)), resid_dev(1);
-  project_on_device(ysd.p, ns, p, Td.buf, m, 0, m, nullptr, Ty.p, st0);
-  residual_on_device(ysd.p, ns, p, Ty.p, m, Hd.buf, partial.p, resid_dev.p, st0);
-  Dims Ds(Ns, 1);
+  F.upload(nullptr, ns);                           // (the handle has the latents; their posterior means come below)
+  Buf<double> ml((size_t)ns * m), delta((size_t)ns * m), resid_dev(1);
+  F.residual(ysd.p, ns, resid_dev.p);
+  const Dims Ds(Ns, 1);
   const int ldr = pad_ld(Ds.NC);
-  Buf<double> A(mat_count(Ds.elems())), WA(mat_count((size_t)(Ds.NC / 64) * 4096)), R(mat_count((size_t)ldr * P->NC)), lml_dev(1);
+  Buf<double> R(mat_count((size_t)ldr * P->NC));
   dense_post_cross(P, xsd.p, d, ns, Ds.NC, R.p, ldr, st0);
   dense_post_means(P, xsd.p, d, ns, R.p, ldr, ml.p, st0);
-  launch_vec_lin(Ty.p, ml.p, -1.0, Ns, delta.p, st0);
-  Buf<int> info(1);
-  HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
-  dense_post_cov_factor(P, xsd.p, d, ns, STd.buf.p, delta.p, Ds, A.p, WA.p, R.p, ldr, info.p, st0);
-  launch_lml_reduce(A.p, Ds.ld, Ns, Ds.NC, 1, lml_dev.p, st0);
+  launch_vec_lin(F.Ty.p, ml.p, -1.0, Ns, delta.p, st0);
+  DenseFactor C(Ns, 1, st0);
+  dense_post_cov_factor(P, xsd.p, d, ns, F.STd.buf.p, delta.p, C.D, C.A, R.p, ldr, st0);
+  C.factor(true, st0);
   double lml = 0.0, resid = 0.0;
-  int hinfo = 0;
-  HIPCHK(hipMemcpyAsync(&lml, lml_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
   HIPCHK(hipMemcpyAsync(&resid, resid_dev.p, sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  if (int rc = check_info(std::vector<int>{hinfo}, 0)) return rc;
-  *out = lml - ((double)ns * ((double)(p - m) * kLog2Pi + ((double)p * std::log(sigma2) - logdetST)) + resid / sigma2) / 2.0;
+  if (int rc = C.finish(&lml, st0)) return rc;
+  *out = lml + ilmm_regulariser(ns, p, m, sigma2, F.logdetST, resid);
   return LMM_OK;
   LMM_CATCH
 }
@@ -3793,37 +3753,30 @@ int lmm_ilmm_post_rand(const lmm_post_t* post, double sigma2, int add_noise, con
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (int rc = post_dtype_check(post)) return rc;
-  if (!post || !xs || !z_lat || !out || d <= 0 || ns <= 0 || (add_noise && !eps)) return fail(LMM_ERR_ARG, "bad arguments");
   const lmm_post* P = post;
-  if (P->kind != 1) return fail(LMM_ERR_ARG, "not a dense-H ILMM posterior");
-  const lmm_post* D = dense_state(P);
-  if (P->d != d) return fail(LMM_ERR_DIM, "input dimension mismatch");
-  if (!jit) jit = &kDefaultJit;
+  const lmm_post* D = nullptr;
+  if (int rc = dense_post_args(post, !xs || !z_lat || !out || d <= 0 || ns <= 0 || (add_noise && !eps), d, D, jit)) return rc;
   hipStream_t st0 = g.streams[0];
-  const int m = P->m, p = P->p, n = P->n, Ns = m * ns;
+  const int m = P->m, p = P->p, Ns = m * ns;
   std::vector<double> J((size_t)m * m, 0.0);
   for (int l = 0; l < m; ++l) J[l + (size_t)l * m] = jit->ilmm_rand_jitter;
   DevIn xsd(xs, (size_t)d * ns, st0), zd(z_lat, (size_t)Ns, st0), epsd(add_noise ? eps : nullptr, (size_t)ns * p, st0);
   Uploaded Jd(J, st0), Hd(P->H, st0);
   Buf<double> ml((size_t)Ns), X((size_t)Ns);
-  Dims Ds(Ns, 0);
+  const Dims Ds(Ns, 0);
   const int ldr = pad_ld(Ds.NC);
-  Buf<double> A(mat_count(Ds.elems())), WA(mat_count((size_t)(Ds.NC / 64) * 4096)), R(mat_count((size_t)ldr * P->NC)), part(strip_partial_elems(Ns, Ns, 1));
+  Buf<double> R(mat_count((size_t)ldr * P->NC)), part(strip_partial_elems(Ns, Ns, 1));
   dense_post_cross(P, xsd.p, d, ns, Ds.NC, R.p, ldr, st0);
   dense_post_means(P, xsd.p, d, ns, R.p, ldr, ml.p, st0);
-  Buf<int> info(1);
-  HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st0));
-  dense_post_cov_factor(P, xsd.p, d, ns, Jd.buf.p, nullptr, Ds, A.p, WA.p, R.p, ldr, info.p, st0);
-  launch_trmv_lower(A.p, Ds.ld, Ns, zd.p, 0.0, part.p, X.p, st0);
+  DenseFactor C(Ns, 0, st0);
+  dense_post_cov_factor(P, xsd.p, d, ns, Jd.buf.p, nullptr, C.D, C.A, R.p, ldr, st0);
+  C.factor(false, st0);
+  launch_trmv_lower(C.A, C.D.ld, Ns, zd.p, 0.0, part.p, X.p, st0);
   launch_vec_lin(X.p, ml.p, 1.0, Ns, X.p, st0);
   DevOut od(out, (size_t)ns * p);
   launch_mix(X.p, ns, m, Hd.buf.p, p, 1, 0.0, 0.0, add_noise ? epsd.p : nullptr, std::sqrt(sigma2), od.p, st0);
   od.finish(st0);
-  int hinfo = 0;
-  HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipStreamSynchronize(st0));
-  return check_info(std::vector<int>{hinfo}, 0);
+  return C.finish(nullptr, st0);
   LMM_CATCH
 }
 

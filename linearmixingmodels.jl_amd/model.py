@@ -1467,6 +1467,32 @@ def _gps_grads(gg, ga, m: int, d: int) -> list:
     return out
 
 
+def _dense_post_gradient(symbol: str, post, H, fs, x, s2, y, latent: bool, inputs: bool) -> dict:
+    """The predictive logpdf gradient of a dense-H posterior through `symbol` (`symbol + "_x"` with inputs): the ILMM itself (y has
+    p columns) or, with `latent`, its latent view (m columns).  H is the p x m matrix the conditioning batches were observed through."""
+    lib = L.load()
+    Ha, _, p, m = _H_args(H)
+    n = x.n
+    x0, s2b, y0, sizes = _merged_train(post.train, p)
+    bn, bs, gb = _batch_args(s2b, sizes)
+    val, gs2 = C.c_double(), C.c_double()
+    gy, gH = _alloc_like(y if L._is_torch(y) else x.x, n * (m if latent else p)), np.empty(p * m)
+    gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
+    gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in fs])
+    gx0, gxs = (_x_buf(x0), _x_buf(x)) if inputs else (None, None)
+    fn = getattr(lib, symbol + "_x" if inputs else symbol)
+    L.check(fn(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
+               L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
+               None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
+               L.Arr(gH, True).ptr, gg, *((L.Arr(gx0, True).ptr, L.Arr(gxs, True).ptr) if inputs else ())))
+    out = {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
+           "sigma2_train": _train_noise_grad(gb, s2b), "H": gH.reshape(m, p).T.copy(),
+           "gps": _gps_grads(gg, ga, m, x.dim)}
+    if inputs:
+        out.update(x=_x_grad(gxs, x.x), x_train=_split_train_x(gx0, post.train, sizes))
+    return out
+
+
 def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True, inputs: bool = False) -> dict:
     """Value and gradient of logpdf(fx, y) -- what `Zygote.gradient(logpdf, fx, y)` differentiates in the reference's tests
     (test/oilmm.jl:31-32, test/ilmm.jl:31-32, test/independent_mogp.jl:65-66).
@@ -1508,50 +1534,16 @@ def logpdf_and_gradient(fx: FiniteGP, y, with_regulariser: bool = True, inputs: 
         m = len(f.fs)
         if x.out_dim != m:
             raise RuntimeError("out dim of x != out dim of f.")
-        Ha, _, p, _m = _H_args(post.mix)
-        n = x.n
-        x0, s2b, y0, sizes = _merged_train(post.train, p)
-        bn, bs, gb = _batch_args(s2b, sizes)
-        val, gs2 = C.c_double(), C.c_double()
-        gy, gH = _alloc_like(y if L._is_torch(y) else x.x, n * m), np.empty(p * m)
-        gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
-        gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.fs])
-        gx0, gxs = (_x_buf(x0), _x_buf(x)) if inputs else (None, None)
-        fn = lib.lmm_ilmm_post_latent_logpdf_grad_seq_x if inputs else lib.lmm_ilmm_post_latent_logpdf_grad_seq
-        L.check(fn(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
-                   L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
-                   None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
-                   L.Arr(gH, True).ptr, gg, *((L.Arr(gx0, True).ptr, L.Arr(gxs, True).ptr) if inputs else ())))
-        out = {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
-               "sigma2_train": _train_noise_grad(gb, s2b), "H": gH.reshape(m, p).T.copy(),
-               "gps": _gps_grads(gg, ga, m, x.dim)}
-        if inputs:
-            out.update(x=_x_grad(gxs, x.x), x_train=_split_train_x(gx0, post.train, sizes))
-        return out
+        return _dense_post_gradient("lmm_ilmm_post_latent_logpdf_grad_seq", post, post.mix, f.fs, x, s2, y, True, inputs)
     if not mogp and not f.is_oilmm:
         unpack(fx)
+        if post is not None:          # reference test/ilmm.jl:32: gradient(logpdf, pi, y_test) on the dense-H posterior
+            return _dense_post_gradient("lmm_ilmm_post_logpdf_grad_seq", post, f.H, f.f.fs, x, s2, y, False, inputs)
         Ha, _, p, m = _H_args(f.H)
         n = x.n
         val, gs2 = C.c_double(), C.c_double()
         gy, gH = _alloc_like(y if L._is_torch(y) else x.x, n * p), np.empty(p * m)
         gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.f.fs])
-        if post is not None:          # reference test/ilmm.jl:32: gradient(logpdf, pi, y_test) on the dense-H posterior
-            x0, s2b, y0, sizes = _merged_train(post.train, p)
-            bn, bs, gb = _batch_args(s2b, sizes)
-            gy0 = _alloc_like(y0 if L._is_torch(y0) else x0.x, x0.n * p)
-            gx0, gxs = (_x_buf(x0), _x_buf(x)) if inputs else (None, None)
-            fn = lib.lmm_ilmm_post_logpdf_grad_seq_x if inputs else lib.lmm_ilmm_post_logpdf_grad_seq
-            L.check(fn(x0.carr().ptr, x0.dim, x0.n, bn, bs, len(sizes), L.Arr(y0).ptr, x.carr().ptr, n,
-                       L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2), ga,
-                       None, C.byref(val), L.Arr(gy0, True).ptr, L.Arr(gy, True).ptr, gb, C.byref(gs2),
-                       L.Arr(gH, True).ptr, gg, *((L.Arr(gx0, True).ptr, L.Arr(gxs, True).ptr) if inputs else ())))
-            out = {"value": val.value, "y": gy, "y_train": _split_train_grad(gy0, sizes, p), "sigma2": gs2.value,
-                   "sigma2_train": _train_noise_grad(gb, s2b),
-                   "H": gH.reshape(m, p).T.copy(),
-                   "gps": _gps_grads(gg, ga, m, x.dim)}
-            if inputs:
-                out.update(x=_x_grad(gxs, x.x), x_train=_split_train_x(gx0, post.train, sizes))
-            return out
         gx = _x_buf(x) if inputs else None
         fn = lib.lmm_ilmm_logpdf_grad_x if inputs else lib.lmm_ilmm_logpdf_grad
         L.check(fn(x.carr().ptr, x.dim, n, L.Arr(y).ptr, p, Ha.ptr, m, C.c_double(s2),

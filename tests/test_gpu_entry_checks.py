@@ -3,7 +3,8 @@ table of defective calls with the code and a piece of lmm_last_error_string() ea
 the order of the checks in each entry point; the rows with two defects pin that order (the first failing check wins).  A defect an
 entry point does not check (sigma2 = 0 in lmm_oilmm_logpdf_multi, lmm_oilmm_posterior_create and the MOGP entry points; S outside the
 missing-data entry points; m > p where no p is taken; the shard where a handle brings it) has no row: such a call would run.  Every
-call here returns before any launch.
+call here returns before any launch.  The dense-H training entry points (lmm_ilmm_*) have rows of the same form; theirs were recorded
+from the build before their shared front end (profiles/dense_h_refactor/entry_checks_parent.txt).
 
 Shapes: n = 8, p = 3, m = 2, d = 1; one per-latent posterior handle at n = 64 and one dense-H handle (the "other kind") at n = 8.
 The argument lists are built from the declarations in include/lmm_hip.h; a row names the arguments it spoils."""
@@ -16,17 +17,18 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIM, ARG, UNSUP = 1, 5, 6          # LMM_ERR_DIM, LMM_ERR_ARG, LMM_ERR_UNSUPPORTED
+DIM, NOT_PD, ARG, UNSUP = 1, 3, 5, 6          # LMM_ERR_DIM, LMM_ERR_NOT_PD, LMM_ERR_ARG, LMM_ERR_UNSUPPORTED
 N, P, M, D, NS, NZ = 8, 3, 2, 1, 4, 4
 
 # messages
 BAD, OUTDIM, SHARD, SIGMA2, SBAD, GPS = "bad arguments", "out dim of x != out dim of f.", "bad latent shard", "sigma2 must be > 0", "S must be finite and > 0 (S[1] = ", "gps is NULL"
 DTYPE = "posterior handle was built in the other compute dtype"
 HM, HD = "posterior has 2 latents, H has 3", "input dimension mismatch"
+PROJECT = "PosDefException in project(H, sigma2)"
 HDXS = "input dimension mismatch: posterior has d=1, xs has d=2"
 
 # spoiled arguments
-NULLX, NULLU, NULLXS = {"x": None}, {"U": None}, {"xs": None}
+NULLX, NULLU, NULLXS, NULLH = {"x": None}, {"U": None}, {"xs": None}, {"H": None}
 MP = {"m": 4}                       # m > p; the shard [0, 2) stays inside [0, m]
 SH = {"latent_end": 3}              # shard outside [0, m]
 S0 = {"sigma2": 0.0}
@@ -44,6 +46,7 @@ def both(*ds):
     return out
 
 
+DENSE = [("NULL x", NULLX, ARG, BAD), ("NULL H", NULLH, ARG, BAD), ("no gps", NOGPS, ARG, GPS), ("NULL x and no gps", both(NULLX, NOGPS), ARG, BAD)]
 TRAIN = [("NULL x", NULLX, ARG, BAD), ("m > p", MP, DIM, OUTDIM), ("shard", SH, ARG, SHARD)]
 TABLE = {
     # ---- training data: args, m > p, shard, resolve, then sigma2 (S is not checked)
@@ -99,6 +102,19 @@ TABLE = {
     # the dense-H handle's own entry points: the dtype check comes first
     **{name: [("other dtype", both(OTHER, F32), ARG, DTYPE), ("other dtype and NULL input", both(OTHER, F32, {"xs": None, "x2": None}), ARG, DTYPE)]
        for name in ("lmm_ilmm_post_mean_and_var", "lmm_ilmm_post_mean_and_cov", "lmm_ilmm_post_condition", "lmm_ilmm_post_logpdf", "lmm_ilmm_post_rand")},
+    # ---- dense-H training data (no shard, no m > p): args, resolve, then sigma2 where the entry point tests it; lmm_ilmm_logpdf_ex and
+    # lmm_ilmm_posterior_create do not, and project(H, sigma2) refuses sigma2 = 0 on the host
+    "lmm_ilmm_logpdf_ex": DENSE + [("sigma2 = 0", S0, NOT_PD, PROJECT), ("no gps and sigma2 = 0", both(NOGPS, S0), ARG, GPS)],
+    "lmm_ilmm_logpdf_multi": DENSE + [("NULL Y", {"Y": None}, ARG, BAD), ("ncol = 0", {"ncol": 0}, ARG, BAD), ("sigma2 = 0", S0, ARG, SIGMA2),
+                                      ("no gps and sigma2 = 0", both(NOGPS, S0), ARG, GPS), ("ncol = 0 and sigma2 = 0", both({"ncol": 0}, S0), ARG, BAD)],
+    "lmm_ilmm_logpdf_grad_x": DENSE + [("sigma2 = 0", S0, ARG, SIGMA2), ("no gps and sigma2 = 0", both(NOGPS, S0), ARG, GPS),
+                                       ("NULL H and sigma2 = 0", both(NULLH, S0), ARG, BAD)],
+    # args, resolve, the batches, then the test points' sigma2
+    "lmm_ilmm_post_logpdf_grad_seq_x": DENSE + [("NULL ys", {"ys": None}, ARG, BAD), ("sigma2_s = 0", {"sigma2_s": 0.0}, ARG, SIGMA2),
+                                                ("batches", {"batch_n": "batch_bad"}, ARG, "batch sizes do not add up to n"),
+                                                ("no gps and batches", both(NOGPS, {"batch_n": "batch_bad"}), ARG, GPS),
+                                                ("batches and sigma2_s = 0", {"batch_n": "batch_bad", "sigma2_s": 0.0}, ARG, "batch sizes do not add up to n")],
+    "lmm_ilmm_posterior_create": DENSE + [("sigma2 = 0", S0, NOT_PD, PROJECT), ("no gps and sigma2 = 0", both(NOGPS, S0), ARG, GPS)],
 }
 CASES = [(name, label, spoil, code, msg) for name, rows in TABLE.items() for label, spoil, code, msg in rows]
 
@@ -144,8 +160,8 @@ def env():
 
 # what a sound call passes, by argument name; any other pointer is an output (or an optional input) and gets the scratch block
 VALUES = {"d": D, "n": N, "p": P, "m": M, "ncol": 2, "ns": NS, "nz": NZ, "n2": NS, "nbatch": 1, "nsamples": 1, "m_shard": M, "latent_begin": 0, "latent_end": M,
-          "with_regulariser": 1, "add_noise": 0, "x_by_features": 0, "y_by_features": 0, "sigma2": 0.1, "sigma2_s": 0.1, "jitter": 1e-6}
-INPUTS = {"x": "x", "y": "y", "Y": "y", "U": "U", "S": "S", "gps": "gps", "xs": "xs", "ys": "y", "z": "z", "batch_n": "batch_n", "batch_sigma2": "batch_sigma2",
+          "with_regulariser": 1, "add_noise": 0, "allow_decoupled": 1, "x_by_features": 0, "y_by_features": 0, "sigma2": 0.1, "sigma2_s": 0.1, "jitter": 1e-6}
+INPUTS = {"x": "x", "y": "y", "Y": "y", "U": "U", "H": "U", "S": "S", "gps": "gps", "xs": "xs", "ys": "y", "z": "z", "batch_n": "batch_n", "batch_sigma2": "batch_sigma2",
           "noise_diag": "noise_diag", "post": "post", "x2": "xs", "y2": "y", "z_lat": "y", "dmean": "y", "dvar": "y"}
 NULLS = {"jit", "eps", "grad_y", "grad_ys", "grad_sigma2", "grad_S", "grad_U", "grad_gps", "grad_x", "grad_batch_sigma2", "grad_sigma2_s", "dtc"}
 
