@@ -992,8 +992,8 @@ int lmm_dev_potrf_plan(int NR, int NC, int nb, int rows_real, int in_flight, int
 /* Test hook: the emulation's GEMM is a persistent kernel of min(work items, CUs) workgroups; wgs >= 1 caps that grid (a small shape
  * then makes one workgroup walk several tiles), 0 goes back to the default.  Results do not depend on it. */
 int lmm_dev_set_emul_gemm_workgroups(int wgs);
-/* Switch of the emulation GEMM's zero skip.  The convert records, per 256 rows of a panel, which 128-wide K blocks hold a non-zero
- * truncated integer; on != 0 (the default; the environment's LMM_EMUL_ZERO_SKIP=0 turns it off) the GEMM's tiles walk only the
+/* Switch of the emulation GEMM's zero skip.  A pass before the convert records, per 256 rows of a panel, which 128-wide K blocks hold
+ * a non-zero truncated integer (from the block maxima the row scan keeps); on != 0 (the default; the environment's LMM_EMUL_ZERO_SKIP=0 turns it off) the GEMM's tiles walk only the
  * blocks that are live in both operands, on = 0 walks every block with the same kernel, on < 0 goes back to the environment's
  * default.  A skipped block multiplies exact zeros: results do not depend on it. */
 int lmm_dev_set_emul_zero_skip(int on);
@@ -1020,6 +1020,11 @@ int lmm_dev_emul_host(const double* A, int lda, const double* B, int ldb, int M,
  * out[i * nmod + t] = v[i] modulo the t-th modulus as an int8 (congruent, inside the symmetric range).  exhaustive (may be NULL, 2
  * words): the reduction behind it run on every input it can see, every odd modulus, both signs: [0] cases, [1] failures. */
 int lmm_dev_emul_residues(const long long* v, int count, int nmod, signed char* out, long long* exhaustive);
+/* Host-only (no GPU, no lmm_init needed): the liveness decision of the emulation's convert, which reads a 16-row piece of a 128-wide
+ * K block only when the block maxima kept by the row scan say it holds a non-zero truncated integer.  For `count` (row, K block)
+ * pairs at the bit budget 1 <= bits <= 58: out[i] = 1 when trunc(|blockmax[i]| 2^(bits - e)) != 0, e = ceil(log2 |rowmax[i]|), for a
+ * finite non-zero rowmax[i]; 0 otherwise (a row of zeros, or one with a NaN or an infinity, is all zeros to the GEMM). */
+int lmm_dev_emul_block_live(const double* rowmax, const double* blockmax, int count, int bits, int* out);
 /* Host-only (no GPU, no lmm_init needed): the reduction of the emulation's GEMM epilogue on `count` int32 accumulators |x| <= 2^28:
  * out[i * nmod + t] = x[i] modulo the t-th modulus as an int8 (congruent, inside the symmetric range).  exhaustive (may be NULL, 2
  * words): its float step run on every folded value it can see, every modulus: [0] cases, [1] failures. */

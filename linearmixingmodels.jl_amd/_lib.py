@@ -44,7 +44,7 @@ SYMBOLS = [
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
     "lmm_dev_set_f64_emul", "lmm_dev_syrk_emul", "lmm_dev_emul_host", "lmm_dev_emul_residues", "lmm_dev_set_emul_gemm_workgroups", "lmm_dev_emul_acc_residues",
     "lmm_dev_set_f64_emul_rule", "lmm_dev_set_emul_group", "lmm_dev_set_emul_amax_reuse", "lmm_dev_emul_plan", "lmm_dev_potrf_plan",
-    "lmm_dev_set_emul_zero_skip", "lmm_dev_emul_stage_list", "lmm_dev_set_emul_scratch_poison",
+    "lmm_dev_set_emul_zero_skip", "lmm_dev_emul_stage_list", "lmm_dev_set_emul_scratch_poison", "lmm_dev_emul_block_live",
 ]
 
 

@@ -872,14 +872,20 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
   std::vector<unsigned long long*> amax_kept(P.steps.size(), nullptr);
   for (size_t i = 0; i < P.steps.size(); ++i)
     if (P.steps[i].kind == POTRF_EMUL_UPDATE_LEAF) amax_kept[i] = reinterpret_cast<unsigned long long*>(call_scratch((size_t)B.nb * NR));
-  // live K blocks and unwritten pieces of the emulated updates' panels (lmm_emul.h): sized for the deepest update, rewritten by every
-  // group of every update in stream order
+  // live K blocks and dead pieces of the emulated updates' panels (lmm_emul.h): sized for the deepest update, rewritten by every
+  // group of every update in stream order.  Block maxima: ONE array for the factorisation, [matrix][128-column block][NR], up to the
+  // last column an emulated panel holds; the scan of an update writes the blocks it reads, a later update that covers them
+  // (emul_amax_cover) decides its live blocks and pieces from them without reading those columns (emul_block_max_bytes: batch_plan
+  // counts them)
   void* emul_aux_blk = nullptr;
+  unsigned long long* emul_bmax = nullptr;
+  int emul_ncb = 0;
   if (P.emul_bytes > 0) {
     int kmax = 128;
     for (const PotrfStep& s : P.steps)
-      if (s.kind == POTRF_EMUL_UPDATE_LEAF) kmax = std::max(kmax, s.h);
+      if (s.kind == POTRF_EMUL_UPDATE_LEAF) { kmax = std::max(kmax, s.h); emul_ncb = std::max(emul_ncb, (s.j0 + s.h) / 128); }
     emul_aux_blk = call_scratch(emul_aux(NR, B.nb, kmax).total / 8);
+    if (emul_ncb > 0) emul_bmax = reinterpret_cast<unsigned long long*>(call_scratch(emul_block_max_bytes(NR, emul_ncb, B.nb) / 8));
   }
   auto leaf128 = [&](int c) { launch_leaf128(B.A, (size_t)c * ld + c, ld, B.W, (size_t)(c / 64) * 4096, W2, (size_t)(c / 128) * 16384, c, n_real, B.info, B.nb, st); };
   for (const PotrfStep& s : P.steps) {
@@ -902,9 +908,11 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
         {
           const int si = (int)(&s - P.steps.data());
           const EmulCover cov = emul_amax_cover(P.steps, si, g_emul_amax_reuse != 0);
-          EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0};
+          EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0, emul_bmax, j0 / 128, emul_ncb};
           for (int q = 0; q < cov.n; ++q) keep.src[q] = amax_kept[cov.step[q]];
           if (r0 + s.M > NR) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's rows %d + %d exceed %d", r0, s.M, NR);
+          if ((j0 % 128) != 0 || (s.h % 128) != 0 || ((cov.scan0 - j0) % 128) != 0 || (j0 + s.h) / 128 > emul_ncb)
+            throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's panel [%d, %d) is not whole 128-column blocks below %d", j0, j0 + s.h, 128 * emul_ncb);
           HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, st, &keep));
         }
         leaf128(r0);
@@ -1017,7 +1025,8 @@ void batch_plan(int ms, int* nb_per, int* nstreams_used, double bytes_per_latent
       // have an emulated level at the batch size the plan starts from (emul_view: the plan potrf_batch makes; the shape is the
       // square one of this working set, n = sqrt(bytes / 8) rounded up to whole panels, with one 64-row block of riders)
       const int nce = (int)rup((size_t)std::sqrt(bytes_per_latent / 8.0), 128);
-      const double per_stream = (!g_f32 && emul_view(nce + 64, nce, b).emul_bytes > 0) ? 12e9 : 0.0;
+      // and that batch's block maxima (8 bytes per row and 128-column block of every matrix, at most all nce columns)
+      const double per_stream = (!g_f32 && emul_view(nce + 64, nce, b).emul_bytes > 0) ? 12e9 + (double)emul_block_max_bytes(nce + 64, nce / 128, b) : 0.0;
       while ((double)b * ns * bytes_per_latent + ns * per_stream > budget && (b > 1 || ns > 1)) {
         if (b > 1) b = (b + 1) / 2; else --ns;
         nbatches = (ms + b - 1) / b;
@@ -6157,7 +6166,7 @@ int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N
   double* scratch = call_scratch((bytes + 7) / 8);
   BatchPtr Cb{}, Pb{};
   Cb.p[0] = C; Pb.p[0] = const_cast<double*>(A);
-  void* aux = call_scratch(emul_aux(M, 1, K).total / 8);
+  void* aux = call_scratch(emul_aux(M, 1, K).total_bmax / 8);      // no factorisation around it: the block maxima live there too
   HIPCHK(launch_emul_update(Cb, 0, ldc, Pb, 0, lda, M, N, K, 1, 1, nmod, scratch, aux, g.streams[0]));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(g.streams[0]));
@@ -6232,6 +6241,19 @@ int lmm_dev_emul_residues(const long long* v, int count, int nmod, signed char* 
       }
     }
     exhaustive[0] = cases; exhaustive[1] = bad;
+  }
+  return LMM_OK;
+}
+// Host-only (no GPU, no lmm_init needed): the convert's liveness decision (emul_block_live, lmm_emul.h) for `count` (row, K block)
+// pairs at the bit budget `bits`: out[i] = 1 when a block whose largest |entry| is blockmax[i], in a row whose largest |entry| is
+// rowmax[i], holds a truncated integer that is not zero, else 0.  Signs are ignored; a NaN counts as above everything, as in the scan.
+int lmm_dev_emul_block_live(const double* rowmax, const double* blockmax, int count, int bits, int* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (count < 0 || (count > 0 && (!rowmax || !blockmax || !out)) || bits < 1 || bits > LMM_EMUL_MAXBITS) return fail(LMM_ERR_ARG, "lmm_dev_emul_block_live: bad arguments");
+  for (int i = 0; i < count; ++i) {
+    unsigned long long r, b;
+    memcpy(&r, &rowmax[i], 8); memcpy(&b, &blockmax[i], 8);
+    out[i] = emul_block_live(r & 0x7FFFFFFFFFFFFFFFull, b & 0x7FFFFFFFFFFFFFFFull, bits) ? 1 : 0;
   }
   return LMM_OK;
 }

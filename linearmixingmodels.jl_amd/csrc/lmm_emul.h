@@ -124,10 +124,11 @@ LMM_HD inline EmulRange emul_xcd_range(int nids, int nwg, int x) {      // 0 <= 
 }
 LMM_HD inline int emul_range_wgs(int nwg, int x) { return (nwg >> 3) + (x < (nwg & 7) ? 1 : 0); }
 
-// ---- unwritten pieces (dead blocks are never written) ----
-// The convert works on pieces of 16 rows x 128 k, 16 per block.  A piece whose truncated integers are all zero is not turned into
-// residues and not stored: the convert sets its bit here instead, 16 bits per (matrix, tile row, K block), two blocks per 32-bit word
-// (cleared on the stream with the masks).  emul_zero_fill_kernel then writes zero residues into the unwritten pieces of the blocks the
+// ---- dead pieces (dead blocks are never written) ----
+// The convert works on pieces of 16 rows x 128 k, 16 per block.  A piece whose truncated integers are all zero is dead: it is neither
+// read nor turned into residues.  emul_live_kernel finds the dead pieces from the block maxima (below) before the convert starts and
+// sets their bits here, 16 bits per (matrix, tile row, K block), two blocks per 32-bit word -- one 16-bit store per block, every
+// block of a group written, so nothing is cleared beforehand.  The convert writes zero residues into the dead pieces of the blocks the
 // GEMM may stage -- the live ones, and block 0 for the empty-intersection fallback of emul_live_stages -- and into no other block.
 #define LMM_EMUL_PIECE_ROWS 16
 #define LMM_EMUL_PIECES (LMM_EMUL_TILE / LMM_EMUL_PIECE_ROWS)
@@ -138,13 +139,17 @@ inline size_t emul_piece_bytes(int M, int G, int K) {
   const size_t blocks = (size_t)G * ((M + LMM_EMUL_TILE - 1) / LMM_EMUL_TILE) * (K / 128);
   return (blocks + 1) / 2 * 4;
 }
-// The small arrays of one group beside its residues: the live masks, then the unwritten-piece bitmap (byte offsets; a multiple of 8 each)
-struct EmulAux { size_t masks, pieces, total; };
+// The small arrays of one group beside its residues: the live masks, then the dead-piece bitmap (byte offsets; a multiple of 8 each;
+// `total` bytes for a caller that keeps the block maxima elsewhere: a factorisation).  An update on its own keeps the block maxima of
+// its group behind them, [matrix][K block][row] with M rows per block, and needs `total_bmax` bytes.
+struct EmulAux { size_t masks, pieces, total, bmax, total_bmax; };
 inline EmulAux emul_aux(int M, int G, int K) {
   EmulAux a{};
   a.masks = 0;
   a.pieces = emul_mask_bytes(M, G);
   a.total = a.pieces + ((emul_piece_bytes(M, G, K) + 7) & ~size_t(7));
+  a.bmax = a.total;
+  a.total_bmax = a.bmax + (size_t)G * (K / 128) * M * 8;
   return a;
 }
 
@@ -156,6 +161,29 @@ LMM_HD inline int emul_row_exp(double amax) {
 }
 // a' = trunc(a 2^sh), sh = b - e_row: an exact power-of-two scaling, |a'| <= 2^b
 LMM_HD inline long long emul_trunc(double a, int sh) { return (long long)ldexp(a, sh); }
+// ---- block maxima: liveness without reading the panel ----
+// The scan that finds a row's maximum keeps, per row and 128-wide K block, the largest |a| of the block as a bit pattern (order-
+// preserving for non-negative doubles).  |trunc(a 2^sh)| does not decrease with |a|, so the truncated integers of a (row, block) pair
+// are all zero exactly when the block maximum's is: the pair is live iff emul_trunc(block maximum, b - e_row) != 0, for a row whose
+// own maximum is finite and not zero (any other row is all zeros to the GEMM).  The very functions of the convert decide, so a
+// subnormal scale or a maximum that is an exact power of two cannot fall on the other side.
+// bytes of a factorisation's block maxima: nb matrices of NR rows, the first ncb 128-column blocks (all 8 bytes of a maximum are kept:
+// the upper half would decide only where the threshold 2^(e_row - b) is a normal number)
+inline size_t emul_block_max_bytes(int NR, int ncb, int nb) { return (size_t)nb * ncb * NR * 8; }
+LMM_HD inline double emul_bits_as_double(unsigned long long u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __longlong_as_double((long long)u);
+#else
+  double d;
+  __builtin_memcpy(&d, &u, 8);
+  return d;
+#endif
+}
+// row: bit pattern of the row's max |a| (a NaN is above everything); returns false for an all-zero row and for one with a NaN or an infinity
+LMM_HD inline bool emul_row_live(unsigned long long row) { return row != 0ull && row < 0x7FF0000000000000ull; }
+LMM_HD inline bool emul_block_live(unsigned long long row, unsigned long long blk, int bits) {
+  return emul_row_live(row) && emul_trunc(emul_bits_as_double(blk), bits - emul_row_exp(emul_bits_as_double(row))) != 0;
+}
 // ---- the convert kernel's residue step: no branch, no division, no 32-bit multiply per modulus ----
 // |v| <= 2^58 is cut into its 8 bytes d_i.  For an odd modulus p, x = sum_i d_i (256^i mod p) <= 8 255 (p - 1) < 2^19 is congruent
 // to |v|; the eight products are two 4-byte dot products against the packed constants lo and hi.  q = rint(x fl(1 / p)) is THE

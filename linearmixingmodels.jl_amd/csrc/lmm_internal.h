@@ -172,9 +172,14 @@ void emul_set_zero_skip(int on);             // 0: the GEMM walks every K block 
 // Row maxima that outlive the update (potrf_batch; emul_amax_cover of lmm_potrf_plan.h): out = this update's array, out[m ld + r] for
 // matrix m and the ABSOLUTE row r of the matrix (the panel's row i is row row0 + i), written for all nb matrices; src[0 .. n) = arrays
 // of the same layout that earlier updates wrote, which together hold the maxima over the panel's columns [0, scan0), so that only
-// the columns [scan0, K) are read.  nullptr: the maxima live in the scratch, per group, and the whole panel is read.
-// aux: emul_aux(M, G, K).total bytes (lmm_emul.h) for the live K blocks and the unwritten pieces of one group's panels.
-struct EmulAmaxKeep { unsigned long long* out; int ld, row0, n; const unsigned long long* src[LMM_EMUL_COVER_MAX]; int scan0; };
+// the columns [scan0, K) are read.  bmax: the factorisation's block maxima (lmm_emul.h), bmax[(m ncb + c) ld + r] for matrix m, the
+// ABSOLUTE 128-column block c < ncb and row r; the panel begins at column block cb0.  The scan writes the blocks it reads, and the
+// blocks of the columns [0, scan0) are there from the updates that scanned them, whose rows began no later than row0 (the entries
+// below a factored block column never change).  nullptr: the maxima live in the scratch and in aux, per group, and the whole panel
+// is read.
+// aux: emul_aux(M, G, K).total bytes (lmm_emul.h) for the live K blocks and the dead pieces of one group's panels; without a keep,
+// .total_bmax bytes: the group's block maxima follow them.
+struct EmulAmaxKeep { unsigned long long* out; int ld, row0, n; const unsigned long long* src[LMM_EMUL_COVER_MAX]; int scan0; unsigned long long* bmax; int cb0, ncb; };
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
                               int G, int nmod, void* scratch, void* aux, hipStream_t st, const EmulAmaxKeep* keep = nullptr);      // the first HIP error of its host-side calls
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,

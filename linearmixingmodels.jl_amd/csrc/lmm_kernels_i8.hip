@@ -1,10 +1,11 @@
 // lmm_kernels_i8.hip -- the large Float64 trailing updates C -= A B' of the factorisation as exact int8 modular GEMMs.
 // Built WITHOUT -amdgpu-mfma-vgpr-form=1.  Three steps per update, for groups of matrices:
-//   1. emul_rowmax_kernel + emul_convert_kernel: per panel row the exponent e_i = ceil(log2 max_k |a_ik|), the integers
-//      a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows (inside a factorisation
-//      the maxima outlive the update, and a later update reads them for the columns it shares: emul_amax_fold_kernel); a piece of
-//      16 rows x 128 k that is all zeros is read and neither converted nor stored, and emul_zero_fill_kernel writes zeros into
-//      such pieces only where the GEMM may stage them;
+//   1. emul_rowmax_kernel + emul_live_kernel + emul_convert_kernel: per panel row the exponent e_i = ceil(log2 max_k |a_ik|), the
+//      integers a' = trunc(a 2^(b - e_i)) and their residues modulo nmod small coprime moduli as K-contiguous int8 rows (inside a
+//      factorisation the maxima outlive the update, and a later update reads them for the columns it shares: emul_amax_fold_kernel).
+//      The scan keeps the maximum of every row and 128-wide K block too; from those emul_live_kernel decides, before the convert
+//      starts, which 256-row blocks and which of their pieces of 16 rows x 128 k hold a non-zero integer.  The convert loads live
+//      pieces only; a dead piece gets zeros, without a load, where the GEMM may stage it, and no store anywhere else;
 //   2. emul_gemm_kernel: one int8 SYRK-shaped GEMM per (matrix, modulus) on 256 x 256 tiles of the lower trapezoid, int32
 //      accumulators, reduced mod p to one byte per output, as a persistent kernel whose tiles walk only the K blocks that are live
 //      (not all zeros) in both operands (tools/i8_gemm_probe.hip holds a copy of the kernel without that skip,
@@ -29,15 +30,23 @@ constexpr int TILE = LMM_EMUL_TILE, BK = 128;
 constexpr int STAGE_BYTES = 2 * TILE * BK;      // A tile + B tile of one K step
 constexpr unsigned long long ABS_MASK = 0x7FFFFFFFFFFFFFFFull, INF_BITS = 0x7FF0000000000000ull;
 
-// amax[z as + i] = max(what is there, max_k |a_ik| over the columns k = kb .. K - 1) as a bit pattern (order-preserving for
-// non-negative doubles; a NaN is above everything).  as: entries per matrix of amax.
-__global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int as, int kb, int K, unsigned long long* amax) {
+// Block maxima of a group's panels (lmm_emul.h): p[z zs + kblock ld + i] = max |a_ik| over the 128 columns of K block `kblock` of
+// the panel, for its row i of matrix z, as a bit pattern.  p points at (first matrix, K block 0, row 0) of the panel inside whatever
+// array holds it: the one of a factorisation (absolute column blocks and rows, ld = its rows) or the aux block of a single update.
+struct EmulBlockMax { unsigned long long* p; size_t zs, ld; };
+
+// One thread per row and K block of 128 columns, for the blocks kb / 128 .. K / 128 - 1 (kb, K multiples of 128): the block's maximum
+// |a_ik| as a bit pattern (order-preserving for non-negative doubles; a NaN is above everything) goes to bm -- one plain store per
+// entry, coalesced over the rows -- and amax[z as + i] = max(what is there, that maximum).  as: entries per matrix of amax.
+__global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int as, int kb, unsigned long long* amax, EmulBlockMax bm) {
   const int i = blockIdx.x * 256 + threadIdx.x, z = blockIdx.z;
   if (i >= M) return;
-  const double* P = A.p[g0 + z] + off + i;
-  const int k0 = kb + blockIdx.y * 64, k1 = min(K, k0 + 64);
+  const int k0 = kb + blockIdx.y * BK;
+  const double* P = A.p[g0 + z] + off + i + (size_t)k0 * ld;
   unsigned long long m = 0;
-  for (int k = k0; k < k1; ++k) m = max(m, (unsigned long long)__double_as_longlong(P[(size_t)k * ld]) & ABS_MASK);
+#pragma unroll 8
+  for (int k = 0; k < BK; ++k) m = max(m, (unsigned long long)__double_as_longlong(P[(size_t)k * ld]) & ABS_MASK);
+  bm.p[(size_t)z * bm.zs + (size_t)(k0 / BK) * bm.ld + i] = m;
   atomicMax(&amax[(size_t)z * as + i], m);
 }
 // The first write of an update's kept row maxima: per row the largest of the maxima that earlier updates kept for parts of its panel
@@ -52,99 +61,144 @@ __global__ __launch_bounds__(256) void emul_amax_fold_kernel(EmulAmaxKeep k, int
   k.out[at] = m;
 }
 
-// 16 rows x 128 k per workgroup of 256 threads, NMOD moduli.  Each thread first issues its 8 loads (8 k of one row; 16 lanes cover
-// 128 contiguous bytes of a column of the column-major panel), truncates them and writes the integers to LDS, [row][k] with a pitch
-// of 130 (16.6 KB: nine workgroups fit on a CU).  It then takes 4 consecutive k of two rows from LDS, forms the residues
-// (emul_residues: constants folded into the instructions) and stores one dword per modulus straight to the K-contiguous int8 rows
-// R[(z NMOD + t) Mp + i][k]: 32 lanes write 128 contiguous bytes.  Rows M .. Mp - 1 (padding up to the GEMM tile) get zero residues.
-// The barrier between the two halves also ORs "one of my integers is not zero" over the workgroup, and one thread then sets the bit of
-// this K block in the live mask of its 256-row tile row (lmm_emul.h; zeroed, or filled with ones, on the stream before this kernel).
-// The bit follows the truncated integers: a row with a NaN or an infinity and the padding rows are zeros here.
-// A workgroup whose piece is all zeros stops at that barrier (pieces != nullptr: the zero skip is on): it forms no residues and
-// stores nothing, and sets its bit in the unwritten-piece bitmap (lmm_emul.h) instead.  A live block of 256 rows may hold such dead
-// pieces of 16, which the GEMM reads: emul_zero_fill_kernel writes them.  pieces == nullptr: every residue is written here.
 constexpr int CV_ROWS = 16, CV_K = 128, CV_PITCH = 130;
+constexpr int CV_NO_ROW = -0x7FFFFFFF - 1;      // in place of a row's shift b - e_i: the row is all zeros to the GEMM
+constexpr int CV_SPLIT = 4;                     // workgroups of the convert per (tile row, K block): each walks 16 / CV_SPLIT of the pieces
+constexpr int CV_WG_ROWS = TILE / CV_SPLIT;     // (per batch of C2: 5.34 ms with 1, 4.94 with 2, 4.78 with 4, 4.76 with 16 = one per piece)
+
+// Liveness of a group's panels from the block maxima, before the convert reads anything of the panel (zero skip on).  One workgroup
+// per (256-row tile row, matrix), one thread per row: for every K block, emul_block_live (lmm_emul.h) of the row's maximum and the
+// block's, ORed over the 16 rows of a piece by a wave ballot (a wave holds 4 pieces).  Thread k < K / 128 then stores the 16 dead-piece
+// bits of K block k, and the first two waves store the tile row's two live-mask words (a block is live iff one of its pieces is):
+// plain stores, every word of the group written, nothing cleared beforehand.  Padding rows and rows with a NaN, an infinity or only
+// zeros are dead, as their truncated integers are zeros.
+__global__ __launch_bounds__(256) void emul_live_kernel(int M, int Mp, int K, int bits, const unsigned long long* __restrict__ amax, int as, EmulBlockMax bm,
+                                                        unsigned long long* masks, unsigned short* dead) {
+  __shared__ unsigned char nib[LMM_EMUL_MASK_WORDS * 64][4];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, trow = blockIdx.x, z = blockIdx.y, nkb = K / BK, tr = Mp / TILE;
+  const int i = trow * TILE + tid;
+  const unsigned long long row = i < M ? amax[(size_t)z * as + i] : 0ull;
+  const bool ok = emul_row_live(row);
+  const unsigned long long* b = bm.p + (size_t)z * bm.zs + i;
+  for (int kb = 0; kb < nkb; ++kb) {
+    const bool lv = ok && emul_block_live(row, b[(size_t)kb * bm.ld], bits);
+    const unsigned long long bal = __ballot(lv);
+    if (lane == 0) {
+      unsigned n = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) n |= ((bal >> (16 * q)) & 0xFFFFull) != 0ull ? 1u << q : 0u;
+      nib[kb][w] = (unsigned char)n;
+    }
+  }
+  __syncthreads();
+  if (tid < LMM_EMUL_MASK_WORDS * 64) {      // K block tid: waves 0 and 1 hold the two mask words
+    unsigned lp = 0;
+    if (tid < nkb) {
+      lp = (unsigned)nib[tid][0] | (unsigned)nib[tid][1] << 4 | (unsigned)nib[tid][2] << 8 | (unsigned)nib[tid][3] << 12;
+      dead[emul_piece_block(tr, nkb, z, trow, tid)] = (unsigned short)(~lp & 0xFFFFu);      // 16-bit field emul_piece_word / emul_piece_shift
+    }
+    const unsigned long long word = __ballot(lp != 0u);
+    if (lane == 0) masks[((size_t)z * tr + trow) * LMM_EMUL_MASK_WORDS + w] = word;
+  }
+}
+
+// CV_SPLIT workgroups of 256 threads per (256-row tile row, K block, matrix), NMOD moduli; each walks 16 / CV_SPLIT of the block's 16
+// pieces of 16 rows x 128 k (blockIdx.x = tile row * CV_SPLIT + part).
+// With the zero skip on (dead != nullptr) it first reads its live bit and its dead-piece bits (emul_live_kernel): a dead block other
+// than block 0 returns at once, having read nothing of the panel and stored nothing; the dead pieces of a live block, and all of a
+// dead block 0 (which emul_live_stages stages for an empty intersection), get zero residues for all planes -- 8 lanes of 16 B per row
+// and plane -- without a panel load.  dead == nullptr: every piece is converted.
+// A live piece: each thread issues its 8 loads (8 k of one row; 16 lanes cover 128 contiguous bytes of a column of the column-major
+// panel), truncates them and writes the integers to LDS, [row][k] with a pitch of 130.  It then takes 4 consecutive k of two rows
+// from LDS, forms the residues (emul_residues: constants folded into the instructions) and stores one dword per modulus straight to
+// the K-contiguous int8 rows R[(z NMOD + t) Mp + i][k]: 32 lanes write 128 contiguous bytes.  The loads of the next live piece are
+// issued before the current one is truncated, so they fly while its residues are formed.  Rows M .. Mp - 1 (padding up to the GEMM
+// tile), all-zero rows and rows with a NaN or an infinity are not loaded and get zero residues.  The workgroups of K block 0 also write the row scales and exponents.
 template <int NMOD>
 __global__ __launch_bounds__(256) void emul_convert_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
                                                            const unsigned long long* __restrict__ amax, int as, int8_t* __restrict__ R, double* sc, int* ex,
-                                                           unsigned long long* masks, unsigned* pieces) {
+                                                           const unsigned long long* __restrict__ masks, const unsigned short* __restrict__ dead) {
   __shared__ long long lds[CV_ROWS * CV_PITCH];
-  const int tid = threadIdx.x, ti = tid & 15, tk = tid >> 4, z = blockIdx.z;
-  const int i = blockIdx.x * CV_ROWS + ti, k0 = blockIdx.y * CV_K;
-  unsigned long long mb = 0;
-  if (i < M) mb = amax[(size_t)z * as + i];      // as: entries per matrix of amax
-  const bool finite = mb < INF_BITS, live = mb != 0 && finite;
-  int e = 0;
-  if (live) e = emul_row_exp(__longlong_as_double((long long)mb));
-  if (blockIdx.y == 0 && tk == 0) {      // row scale: 0 for an all-zero (or padding) row, NaN for a row with a non-finite entry
-    sc[(size_t)z * Mp + i] = live ? 1.0 : (finite ? 0.0 : __longlong_as_double(0x7FF8000000000000ll));
-    ex[(size_t)z * Mp + i] = live ? e - bits : 0;
+  __shared__ int shift[TILE];
+  const int tid = threadIdx.x, ti = tid & 15, tk = tid >> 4, trow = blockIdx.x / CV_SPLIT, part = blockIdx.x % CV_SPLIT, kbi = blockIdx.y, z = blockIdx.z, k0 = kbi * CV_K;
+  const unsigned mine = ((1u << (LMM_EMUL_PIECES / CV_SPLIT)) - 1u) << (part * (LMM_EMUL_PIECES / CV_SPLIT));      // this workgroup's pieces
+  unsigned dm = 0;      // the dead pieces
+  if (dead != nullptr) {
+    const unsigned long long mw = masks[((size_t)z * (Mp / TILE) + trow) * LMM_EMUL_MASK_WORDS + (kbi >> 6)];
+    if (kbi != 0 && ((mw >> (kbi & 63)) & 1ull) == 0ull) return;
+    dm = dead[emul_piece_block(Mp / TILE, K / CV_K, z, trow, kbi)] & mine;
   }
-  const double* P = A.p[g0 + z] + off + i + (size_t)(k0 + tk) * ld;
-  double a[CV_K / 16];
-#pragma unroll
-  for (int s = 0; s < CV_K / 16; ++s) a[s] = live ? P[(size_t)(16 * s) * ld] : 0.0;
-  long long any = 0;
-#pragma unroll
-  for (int s = 0; s < CV_K / 16; ++s) {
-    const long long v = emul_trunc(a[s], bits - e);
-    lds[ti * CV_PITCH + tk + 16 * s] = v;
-    any |= v;
-  }
-  const int trow = blockIdx.x / LMM_EMUL_PIECES;
-  if (__syncthreads_or(any != 0)) {
-    if (tid == 0) atomicOr(&masks[((size_t)z * (Mp / TILE) + trow) * LMM_EMUL_MASK_WORDS + (blockIdx.y >> 6)], 1ull << (blockIdx.y & 63));
-  } else if (pieces != nullptr) {
-    const size_t blk = emul_piece_block(Mp / TILE, K / CV_K, z, trow, blockIdx.y);
-    if (tid == 0) atomicOr(&pieces[emul_piece_word(blk)], 1u << (emul_piece_shift(blk) + blockIdx.x % LMM_EMUL_PIECES));
-    return;
-  }
-  const int kg = tid & 31;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int row = (tid >> 5) + 8 * h;
-    unsigned w[NMOD];
-#pragma unroll
-    for (int t = 0; t < NMOD; ++t) w[t] = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int r[NMOD];
-      emul_residues<NMOD>(lds[row * CV_PITCH + 4 * kg + j], r);
-#pragma unroll
-      for (int t = 0; t < NMOD; ++t) w[t] |= (unsigned)r[t] << (8 * j);
+  if (tid / CV_WG_ROWS == part) {
+    const int i = trow * TILE + tid;
+    unsigned long long mb = 0;
+    if (i < M) mb = amax[(size_t)z * as + i];      // as: entries per matrix of amax
+    const bool finite = mb < INF_BITS, live = emul_row_live(mb);
+    int e = 0;
+    if (live) e = emul_row_exp(__longlong_as_double((long long)mb));
+    shift[tid] = live ? bits - e : CV_NO_ROW;
+    if (kbi == 0) {      // row scale: 0 for an all-zero (or padding) row, NaN for a row with a non-finite entry
+      sc[(size_t)z * Mp + i] = live ? 1.0 : (finite ? 0.0 : __longlong_as_double(0x7FF8000000000000ll));
+      ex[(size_t)z * Mp + i] = live ? e - bits : 0;
     }
-    int8_t* dst = R + ((size_t)z * NMOD * Mp + blockIdx.x * CV_ROWS + row) * K + k0 + 4 * kg;
-#pragma unroll
-    for (int t = 0; t < NMOD; ++t) *reinterpret_cast<unsigned*>(dst + (size_t)t * Mp * K) = w[t];
   }
-}
-// One workgroup per (K block, tile row, matrix): zero residues, for all nmod planes, into the pieces the convert left unwritten, if
-// the block is one the GEMM may stage: a live one, or block 0 (two tile rows that share no live block stage block 0 of both:
-// emul_live_stages).  A piece is 16 rows x 128 B per plane: 8 lanes of 16 B per row.  Dead blocks other than block 0 get no store.
-__global__ __launch_bounds__(256) void emul_zero_fill_kernel(int8_t* __restrict__ R, int Mp, int K, int nmod, const unsigned long long* __restrict__ masks,
-                                                             const unsigned* __restrict__ pieces) {
-  const int kb = blockIdx.x, trow = blockIdx.y, z = blockIdx.z, tr = Mp / TILE;
-  const unsigned long long mw = masks[((size_t)z * tr + trow) * LMM_EMUL_MASK_WORDS + (kb >> 6)];
-  if (kb != 0 && ((mw >> (kb & 63)) & 1ull) == 0ull) return;
-  const size_t blk = emul_piece_block(tr, K / BK, z, trow, kb);
-  const unsigned u = (pieces[emul_piece_word(blk)] >> emul_piece_shift(blk)) & ((1u << LMM_EMUL_PIECES) - 1u);
-  if (u == 0u) return;
-  for (int pc = 0; pc < LMM_EMUL_PIECES; ++pc) {
-    if (((u >> pc) & 1u) == 0u) continue;
-    for (int q = threadIdx.x; q < nmod * CV_ROWS * 8; q += 256) {
+  __syncthreads();
+  for (unsigned u = dm; u != 0u; u &= u - 1u) {
+    const int pc = __builtin_ctz(u);
+    for (int q = tid; q < NMOD * CV_ROWS * 8; q += 256) {
       const int t = q / (CV_ROWS * 8), row = (q >> 3) % CV_ROWS, col = q & 7;
-      int8_t* dst = R + (((size_t)z * nmod + t) * Mp + trow * TILE + pc * CV_ROWS + row) * K + kb * BK + col * 16;
+      int8_t* dst = R + (((size_t)z * NMOD + t) * Mp + trow * TILE + pc * CV_ROWS + row) * K + k0 + col * 16;
       *reinterpret_cast<v4u*>(dst) = (v4u){0u, 0u, 0u, 0u};
+    }
+  }
+  const double* P = A.p[g0 + z] + off + (size_t)(k0 + tk) * ld + trow * TILE + ti;
+  auto load = [&](int pc, double (&a)[CV_K / 16]) {
+    const bool live = shift[pc * CV_ROWS + ti] != CV_NO_ROW;
+#pragma unroll
+    for (int s = 0; s < CV_K / 16; ++s) a[s] = live ? P[pc * CV_ROWS + (size_t)(16 * s) * ld] : 0.0;
+  };
+  unsigned rest = ~dm & mine;
+  double a[CV_K / 16], an[CV_K / 16];
+  if (rest != 0u) load(__builtin_ctz(rest), a);
+  const int kg = tid & 31;
+  while (rest != 0u) {
+    const int pc = __builtin_ctz(rest);
+    rest &= rest - 1u;
+    if (rest != 0u) load(__builtin_ctz(rest), an);
+    const int sh = shift[pc * CV_ROWS + ti];
+#pragma unroll
+    for (int s = 0; s < CV_K / 16; ++s) lds[ti * CV_PITCH + tk + 16 * s] = sh != CV_NO_ROW ? emul_trunc(a[s], sh) : 0ll;
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int row = (tid >> 5) + 8 * h;
+      unsigned w[NMOD];
+#pragma unroll
+      for (int t = 0; t < NMOD; ++t) w[t] = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int r[NMOD];
+        emul_residues<NMOD>(lds[row * CV_PITCH + 4 * kg + j], r);
+#pragma unroll
+        for (int t = 0; t < NMOD; ++t) w[t] |= (unsigned)r[t] << (8 * j);
+      }
+      int8_t* dst = R + ((size_t)z * NMOD * Mp + trow * TILE + pc * CV_ROWS + row) * K + k0 + 4 * kg;
+#pragma unroll
+      for (int t = 0; t < NMOD; ++t) *reinterpret_cast<unsigned*>(dst + (size_t)t * Mp * K) = w[t];
+    }
+    __syncthreads();      // the next piece overwrites the integers
+    if (rest != 0u) {
+#pragma unroll
+      for (int s = 0; s < CV_K / 16; ++s) a[s] = an[s];
     }
   }
 }
 template <int NMOD>
 void launch_convert(int nmod, dim3 grid, hipStream_t st, const BatchPtr& P, int g0, size_t off, int ld, int M, int Mp, int K, int bits,
-                    const unsigned long long* amax, int as, int8_t* R, double* sc, int* ex, unsigned long long* masks, unsigned* pieces) {
+                    const unsigned long long* amax, int as, int8_t* R, double* sc, int* ex, const unsigned long long* masks, const unsigned short* dead) {
   if constexpr (NMOD > LMM_EMUL_MINMOD) {
-    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks, pieces);
+    if (nmod != NMOD) return launch_convert<NMOD - 1>(nmod, grid, st, P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks, dead);
   }
-  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks, pieces);
+  emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks, dead);
 }
 
 // lower-trapezoid tiles in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles share at most 12 operand panels
@@ -513,12 +567,13 @@ void emul_set_scratch_poison(int on) { g_emul_poison = on ? 1 : 0; }
 
 // C_m (M x N at C.p[m] + offC, ldc) -= P_m P_m[0:N]' for the panels P_m (M x K at P.p[m] + offP, ldp), m < nb, lower trapezoid
 // (i >= j) only, in groups of G matrices through `scratch` (emul_scratch_bytes(M, N, K, G, nmod) bytes).  Returns the first HIP
-// error of its host-side calls (nothing is launched after one).  keep: the row maxima go to an array of the caller's, for all nb matrices
-// before the first group, and start from what earlier updates found (EmulAmaxKeep, lmm_internal.h).  aux: emul_aux(M, G, K).total bytes
-// for the live K blocks of a group's panels and its unwritten pieces (lmm_emul.h), set on the stream before each convert: the masks to
-// zero, or to ones with the zero skip switched off; the bitmap to zero.  The residues R are shared by the groups and the updates that
-// go through one scratch block and a dead block is never written, so it holds whatever was there: R is read through
-// emul_live_stages only.
+// error of its host-side calls (nothing is launched after one).  keep: the row maxima and the block maxima go to arrays of the
+// caller's, for all nb matrices before the first group, and start from what earlier updates found (EmulAmaxKeep, lmm_internal.h);
+// aux is then emul_aux(M, G, K).total bytes.  Without keep the block maxima of a group live in aux too: emul_aux(M, G, K).total_bmax
+// bytes.  aux holds the live K blocks of a group's panels and its dead pieces (lmm_emul.h): written in full by emul_live_kernel
+// before each convert, or, with the zero skip switched off, the masks set to ones on the stream and no bitmap.  The residues R are
+// shared by the groups and the updates that go through one scratch block and a dead block is never written, so it holds whatever
+// was there: R is read through emul_live_stages only.
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
                               int G, int nmod, void* scratch, void* aux, hipStream_t st, const EmulAmaxKeep* keep) {
   static EmulConst consts[LMM_EMUL_MAXMOD + 1];
@@ -538,33 +593,37 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
   int* ex = reinterpret_cast<int*>(s + L.ex);
   const bool skip = emul_zero_skip_on();
   const int wgs = g_emul_gemm_wgs > 0 ? g_emul_gemm_wgs : device_cus();      // one 128-KiB workgroup fits on a CU
+  EmulBlockMax bm{};
   if (keep) {      // every row of every matrix gets its first write from the fold: no memset
+    bm = EmulBlockMax{keep->bmax + (size_t)keep->cb0 * keep->ld + keep->row0, (size_t)keep->ncb * keep->ld, (size_t)keep->ld};
     emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(*keep, M);
     if (keep->scan0 < K)
-      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep->scan0 + 63) / 64, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep->ld, keep->scan0, K, keep->out + keep->row0);
+      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep->scan0) / BK, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep->ld, keep->scan0, keep->out + keep->row0, bm);
   }
   for (int g0 = 0; g0 < nb; g0 += G) {
     const int gc = std::min(G, nb - g0);
+    const EmulAux X = emul_aux(M, gc, K);
     const unsigned long long* am = amax;
     int as = L.Mp;
-    if (keep) { am = keep->out + (size_t)g0 * keep->ld + keep->row0; as = keep->ld; }
+    EmulBlockMax gbm{reinterpret_cast<unsigned long long*>(static_cast<char*>(aux) + X.bmax), (size_t)(K / BK) * M, (size_t)M};
+    if (keep) { am = keep->out + (size_t)g0 * keep->ld + keep->row0; as = keep->ld; gbm = bm; gbm.p += (size_t)g0 * bm.zs; }
     else {
       err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
       if (err != hipSuccess) return err;
-      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K + 63) / 64, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, K, amax);
+      emul_rowmax_kernel<<<dim3((M + 255) / 256, K / BK, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, amax, gbm);
     }
-    // skip on: masks and bitmap are one run of bytes, one fill of zeros; skip off: ones for the masks, and no bitmap
-    const EmulAux X = emul_aux(M, gc, K);
     unsigned long long* masks = reinterpret_cast<unsigned long long*>(static_cast<char*>(aux) + X.masks);
-    unsigned* pieces = skip ? reinterpret_cast<unsigned*>(static_cast<char*>(aux) + X.pieces) : nullptr;
-    err = skip ? hipMemsetAsync(aux, 0, X.total, st) : hipMemsetAsync(masks, 0xFF, emul_mask_bytes(M, gc), st);
-    if (err != hipSuccess) return err;
+    unsigned short* dead = skip ? reinterpret_cast<unsigned short*>(static_cast<char*>(aux) + X.pieces) : nullptr;
+    if (skip) emul_live_kernel<<<dim3(L.Mp / TILE, gc), 256, 0, st>>>(M, L.Mp, K, bits, am, as, gbm, masks, dead);
+    else {
+      err = hipMemsetAsync(masks, 0xFF, emul_mask_bytes(M, gc), st);
+      if (err != hipSuccess) return err;
+    }
     if (g_emul_poison) {
       err = hipMemsetAsync(R, 0x5A, (size_t)gc * nmod * L.Mp * K, st);
       if (err != hipSuccess) return err;
     }
-    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / CV_ROWS, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, am, as, R, sc, ex, masks, pieces);
-    if (skip) emul_zero_fill_kernel<<<dim3(K / BK, L.Mp / TILE, gc), 256, 0, st>>>(R, L.Mp, K, nmod, masks, pieces);
+    launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / TILE * CV_SPLIT, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, am, as, R, sc, ex, masks, dead);
     const int nids = ntiles * gc * nmod;
     emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, ntiles, nids, L.Mp, L.Np, K, c, masks);
     launch_combine<LMM_EMUL_MAXMOD>(nmod, dim3((M + 1023) / 1024, N, gc), st, C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);

@@ -6,9 +6,10 @@
 A level is recognised by the K of the update's emul_convert_kernel launches (grid y = K / 128): the row-maximum kernels that open
 an update scan only the columns no earlier update has scanned (emul_amax_fold_kernel, counted with emul_rowmax, starts them from the
 kept maxima), so their grid does not tell.  Prints ms summed over the launches of a level, per kernel, and the totals of every other
-kernel.  emul_zero_fill is the kernel behind a convert that writes zero residues into the pieces the convert left unwritten (dead blocks
-are never written); a trace from before it has zeros there.  `fill` is the stream's memsets inside an update: the masks and the
-unwritten-piece bitmap of a group are one of them.
+kernel.  emul_live is the kernel in front of a convert that decides the live blocks and pieces of a group from the block maxima; a
+trace from before it has zeros there, and the kernel it made unnecessary, emul_zero_fill (zero residues into the pieces the convert left
+unwritten), has zeros in a trace with it.  `fill` is the stream's memsets inside an update: before emul_live, the masks and the
+unwritten-piece bitmap of a group were one of them.
 
 Then one line per emulated UPDATE, in launch order: an update is a maximal run of emulation kernels and the fills between them
 (two emulated updates are never neighbours: the factorisation of the columns between them lies in between).  Its key is (K, Mp,
@@ -21,7 +22,7 @@ import collections
 import csv
 import sys
 
-EMUL = ("emul_rowmax", "emul_convert", "emul_zero_fill", "emul_gemm", "emul_combine")
+EMUL = ("emul_rowmax", "emul_live", "emul_convert", "emul_zero_fill", "emul_gemm", "emul_combine")
 ALIAS = {"emul_amax_fold": "emul_rowmax"}
 
 
@@ -48,6 +49,7 @@ def main(argv):
     path = argv[0]
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    cv_rows = 64 if any("emul_live_kernel" in r["Kernel_Name"] for r in rows) else 16      # panel rows per workgroup of the convert
     per = collections.defaultdict(lambda: collections.defaultdict(float))
     other = collections.defaultdict(float)
     runs, cur, last_k = [], None, 0      # last_k: a run cut in two by another kernel continues the level of its first part
@@ -77,7 +79,7 @@ def main(argv):
             cur = collections.defaultdict(float, t0=t0, K=last_k, nb=0, groups=0)
         if hit == "emul_convert":
             cur["K"] = last_k = 128 * grid(r, "Y")
-            cur["Mp"] = 16 * grid(r, "X")
+            cur["Mp"] = cv_rows * grid(r, "X")
             cur["nb"] += grid(r, "Z")
             cur["groups"] += 1
         cur[hit] += ms
@@ -90,7 +92,7 @@ def main(argv):
     print("emulated total: " + str({k: round(sum(per[kern][k] for kern in per), 2) for k in levels}))
     print("other kernels ms: " + str({k: round(v, 2) for k, v in sorted(other.items(), key=lambda kv: -kv[1])[:10]}))
     if runs:
-        print("emulated updates in launch order: K Mp nb groups | rowmax convert zero_fill gemm combine fill leaf | kernel sum, span (ms)")
+        print("emulated updates in launch order: K Mp nb groups | rowmax live convert zero_fill gemm combine fill leaf | kernel sum, span (ms)")
     for u in runs:
         tot = sum(u[k] for k in EMUL) + u["fill"] + u["leaf"]
         print(f"  K={u['K']:5d} Mp={int(u['Mp']):5d} nb={u['nb']:2d} groups={u['groups']:2d} | " + " ".join(f"{u[k]:7.3f}" for k in EMUL)
