@@ -1025,6 +1025,19 @@ int lmm_dev_emul_residues(const long long* v, int count, int nmod, signed char* 
  * pairs at the bit budget 1 <= bits <= 58: out[i] = 1 when trunc(|blockmax[i]| 2^(bits - e)) != 0, e = ceil(log2 |rowmax[i]|), for a
  * finite non-zero rowmax[i]; 0 otherwise (a row of zeros, or one with a NaN or an infinity, is all zeros to the GEMM). */
 int lmm_dev_emul_block_live(const double* rowmax, const double* blockmax, int count, int bits, int* out);
+/* Switch of the emulation's screen.  Once the row maxima of a panel exist, a pass over C marks the 256 x 256 tiles of the update in
+ * which every output is negligible (lmm_dev_emul_negligible); on != 0 (the default; the environment's LMM_EMUL_SCREEN=0 turns it off)
+ * the GEMM and the combine leave those tiles out, on = 0 treats every tile as live with the same kernels, on < 0 goes back to the
+ * environment's default.  A skipped tile's update would not have changed a bit of C: results do not depend on it. */
+int lmm_dev_set_emul_screen(int on);
+/* Test hook: the number of tiles of the last lmm_dev_syrk_emul call that were not skipped by the screen (all of the lower
+ * trapezoid's 256 x 256 tiles with the screen off), -1 before the first call. */
+int lmm_dev_emul_last_live_tiles(void);
+/* Host-only (no GPU, no lmm_init needed): the screen's predicate.  For `count` outputs of an update of depth 1 <= K <= 16384:
+ * out[i] = 1 when c[i] is finite and not zero, rowmax_i[i] and rowmax_j[i] (the largest |entry| of the output's two panel rows) are
+ * finite, and one of them is zero or ceil(log2 K) + e_i + e_j + 56 <= ilogb(c[i]) with e = ceil(log2 |rowmax|); 0 otherwise.  Then
+ * the update the emulation would subtract is below a quarter of the spacing of the doubles under |c[i]|, and c[i] keeps its bits. */
+int lmm_dev_emul_negligible(int K, const double* rowmax_i, const double* rowmax_j, const double* c, int count, int* out);
 /* Host-only (no GPU, no lmm_init needed): the reduction of the emulation's GEMM epilogue on `count` int32 accumulators |x| <= 2^28:
  * out[i * nmod + t] = x[i] modulo the t-th modulus as an int8 (congruent, inside the symmetric range).  exhaustive (may be NULL, 2
  * words): its float step run on every folded value it can see, every modulus: [0] cases, [1] failures. */

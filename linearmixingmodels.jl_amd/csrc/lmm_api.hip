@@ -877,14 +877,22 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
   // last column an emulated panel holds; the scan of an update writes the blocks it reads, a later update that covers them
   // (emul_amax_cover) decides its live blocks and pieces from them without reading those columns (emul_block_max_bytes: batch_plan
   // counts them)
+  // The screen's tile flags, live id list and counts (lmm_emul.h): a block of their own, sized for the update that needs most,
+  // rewritten by every group of every update in stream order like the aux block.
   void* emul_aux_blk = nullptr;
+  void* emul_screen_blk = nullptr;
+  size_t emul_screen_bytes = 0;
   unsigned long long* emul_bmax = nullptr;
   int emul_ncb = 0;
   if (P.emul_bytes > 0) {
     int kmax = 128;
     for (const PotrfStep& s : P.steps)
-      if (s.kind == POTRF_EMUL_UPDATE_LEAF) { kmax = std::max(kmax, s.h); emul_ncb = std::max(emul_ncb, (s.j0 + s.h) / 128); }
+      if (s.kind == POTRF_EMUL_UPDATE_LEAF) {
+        kmax = std::max(kmax, s.h); emul_ncb = std::max(emul_ncb, (s.j0 + s.h) / 128);
+        emul_screen_bytes = std::max(emul_screen_bytes, emul_screen_layout(s.M, s.N, std::min(s.group, B.nb), P.emul_nmod).total);
+      }
     emul_aux_blk = call_scratch(emul_aux(NR, B.nb, kmax).total / 8);
+    if (emul_screen_bytes > 0) emul_screen_blk = call_scratch(emul_screen_bytes / 8);
     if (emul_ncb > 0) emul_bmax = reinterpret_cast<unsigned long long*>(call_scratch(emul_block_max_bytes(NR, emul_ncb, B.nb) / 8));
   }
   auto leaf128 = [&](int c) { launch_leaf128(B.A, (size_t)c * ld + c, ld, B.W, (size_t)(c / 64) * 4096, W2, (size_t)(c / 128) * 16384, c, n_real, B.info, B.nb, st); };
@@ -906,6 +914,11 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
         if (s.scratch > P.emul_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", s.scratch, P.emul_bytes);
         guard_extent(emul_blk, s.scratch / 8, s.scratch / 8, 1, false, "emulated update (scratch)");
         {
+          const size_t sb = emul_screen_layout(s.M, s.N, std::min(s.group, B.nb), P.emul_nmod).total;
+          if (sb > emul_screen_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's screen needs %zu bytes, has %zu", sb, emul_screen_bytes);
+          guard_extent(emul_screen_blk, sb / 8, sb / 8, 1, false, "emulated update (screen)");
+        }
+        {
           const int si = (int)(&s - P.steps.data());
           const EmulCover cov = emul_amax_cover(P.steps, si, g_emul_amax_reuse != 0);
           EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0, emul_bmax, j0 / 128, emul_ncb};
@@ -913,7 +926,7 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
           if (r0 + s.M > NR) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's rows %d + %d exceed %d", r0, s.M, NR);
           if ((j0 % 128) != 0 || (s.h % 128) != 0 || ((cov.scan0 - j0) % 128) != 0 || (j0 + s.h) / 128 > emul_ncb)
             throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's panel [%d, %d) is not whole 128-column blocks below %d", j0, j0 + s.h, 128 * emul_ncb);
-          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, st, &keep));
+          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, emul_screen_blk, st, &keep));
         }
         leaf128(r0);
         break;
@@ -6155,6 +6168,33 @@ int lmm_dev_emul_stage_list(unsigned long long a0, unsigned long long a1, unsign
     if (n < cap) out[n] = emul_mask_first(m);
   return n;
 }
+// Switch of the emulation's screen (lmm_emul.h, negligible updates): 1 (the default, or LMM_EMUL_SCREEN unset) skips, in the GEMM and
+// the combine, the tiles whose update cannot change a bit of C; 0 (LMM_EMUL_SCREEN=0) makes every tile live and the live id list the
+// identity, with the same kernels; on < 0 goes back to the env default.  Results do not depend on it.
+int lmm_dev_set_emul_screen(int on) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  emul_set_screen(on);
+  return LMM_OK;
+}
+// Test hook: the number of live tiles (of the trapezoid's tile list) in the last lmm_dev_syrk_emul call, -1 before the first.
+static int g_emul_last_live_tiles = -1;
+int lmm_dev_emul_last_live_tiles(void) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return g_emul_last_live_tiles;
+}
+// Host-only (no GPU, no lmm_init needed): the screen's predicate (emul_negligible, lmm_emul.h) for `count` outputs of an update of
+// depth K: out[i] = 1 when an output with the value c[i], whose two panel rows have the largest |entry| rowmax_i[i] and rowmax_j[i],
+// is negligible -- the update cannot change a bit of it -- else 0.  Signs of the maxima are ignored; a NaN counts as above everything.
+int lmm_dev_emul_negligible(int K, const double* rowmax_i, const double* rowmax_j, const double* c, int count, int* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (count < 0 || (count > 0 && (!rowmax_i || !rowmax_j || !c || !out)) || K < 1 || K > 16384) return fail(LMM_ERR_ARG, "lmm_dev_emul_negligible: bad arguments");
+  for (int i = 0; i < count; ++i) {
+    unsigned long long ri, rj;
+    memcpy(&ri, &rowmax_i[i], 8); memcpy(&rj, &rowmax_j[i], 8);
+    out[i] = emul_negligible(K, ri & 0x7FFFFFFFFFFFFFFFull, rj & 0x7FFFFFFFFFFFFFFFull, c[i]) ? 1 : 0;
+  }
+  return LMM_OK;
+}
 // C (M x N, lower trapezoid i >= j) -= A A[0:N]' through the emulation kernels: one matrix, device pointers.
 int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N, int K, int nmod) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -6167,9 +6207,15 @@ int lmm_dev_syrk_emul(double* C, int ldc, const double* A, int lda, int M, int N
   BatchPtr Cb{}, Pb{};
   Cb.p[0] = C; Pb.p[0] = const_cast<double*>(A);
   void* aux = call_scratch(emul_aux(M, 1, K).total_bmax / 8);      // no factorisation around it: the block maxima live there too
-  HIPCHK(launch_emul_update(Cb, 0, ldc, Pb, 0, lda, M, N, K, 1, 1, nmod, scratch, aux, g.streams[0]));
+  const EmulScreen S = emul_screen_layout(M, N, 1, nmod);
+  char* screen = reinterpret_cast<char*>(call_scratch(S.total / 8));
+  guard_extent(screen, S.total / 8, S.total / 8, 1, false, "lmm_dev_syrk_emul (screen)");
+  HIPCHK(launch_emul_update(Cb, 0, ldc, Pb, 0, lda, M, N, K, 1, 1, nmod, scratch, aux, screen, g.streams[0]));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(g.streams[0]));
+  int counts[2] = {0, 0};
+  HIPCHK(hipMemcpy(counts, screen + S.count, sizeof(counts), hipMemcpyDeviceToHost));
+  g_emul_last_live_tiles = counts[1];
   return LMM_OK;
   LMM_CATCH
 }

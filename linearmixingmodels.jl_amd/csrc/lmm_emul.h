@@ -184,6 +184,110 @@ LMM_HD inline bool emul_row_live(unsigned long long row) { return row != 0ull &&
 LMM_HD inline bool emul_block_live(unsigned long long row, unsigned long long blk, int bits) {
   return emul_row_live(row) && emul_trunc(emul_bits_as_double(blk), bits - emul_row_exp(emul_bits_as_double(row))) != 0;
 }
+// ---- negligible updates: tiles whose update cannot change a bit of C (the screen) ----
+// Output (i, j) of an update of depth K is NEGLIGIBLE when C_ij is finite and not zero, both rows' maxima are finite, and either one
+// of the rows is all zeros or
+//     ceil(log2 K) + e_i + e_j + LMM_EMUL_NEG_MARGIN <= ilogb(C_ij),      e = emul_row_exp(row maximum), the convert's own exponent.
+// Then fl(C_ij - T_ij) has the bits of C_ij, T_ij being the update the GEMM and the combine would form.  Proof, from the code: the
+// convert makes |a'| <= 2^b (emul_trunc), so the integer X = sum_k a'_ik a'_jk has |X| <= K 2^(2b); the CRT returns X rounded once
+// to Float64, |X~| <= K 2^(2b) (1 + 2^-53).  Both rows being live, sc = 1 and ex = e - b, so the combine subtracts
+// T = ldexp(X~, e_i + e_j - 2b): an exact scaling, or a rounding to the subnormal grid, which gives 0 or at most doubles |T| (see
+// the margin's spare binade below).  With L = ceil(log2 K), |T| <= 2^(L + e_i + e_j) (1 + 2^-52) <= 2^(q - 56) (1 + 2^-52) for q = ilogb(C_ij).
+// The spacing of the doubles just BELOW |C_ij| is at least 2^(q - 53) (at a power of two; 2^(q - 52) elsewhere; the fixed 2^-1074 of
+// the subnormals is no smaller than either, and ilogb is taken of the value, not of the exponent field), so |T| is below a quarter
+// of the smaller of the two gaps around C_ij: the exact C_ij - T is strictly closer to C_ij than to either neighbour, and round-to-
+// nearest returns C_ij.  (With an exact ldexp the derivation closes at a margin of 55 already -- |T| < half the lower gap; the 56th
+// bit is the binade that a rounding of ldexp into the subnormals may use up, so 56 is what the code as written needs.)  An all-zero row gives X = 0 and
+// T = 0 exactly.  A row with a NaN or an infinity is never negligible: its scale is NaN and must reach row i and column j of C.
+// C_ij = +-0 counts as live (0 - T = -T), and so do an infinite or NaN C_ij (kept out of the argument, they cost nothing).
+// The kernel's screen and the host entry lmm_dev_emul_negligible both decide through emul_negligible.
+#define LMM_EMUL_NEG_MARGIN 56
+#define LMM_EMUL_NEG_NEVER 0x7FFFFFFF
+#define LMM_EMUL_NEG_ALWAYS (-0x7FFFFFFF - 1)
+LMM_HD inline int emul_ceil_log2(int K) {      // K >= 1
+  int l = 0;
+  while ((1 << l) < K) ++l;
+  return l;
+}
+LMM_HD inline unsigned long long emul_double_bits(double d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (unsigned long long)__double_as_longlong(d);
+#else
+  unsigned long long u;
+  __builtin_memcpy(&u, &d, 8);
+  return u;
+#endif
+}
+// ri, rj: bit patterns of the two rows' max |a| (as the scan keeps them); lgk = emul_ceil_log2(K).  The least ilogb(C_ij) at which the
+// output is negligible; NEVER for a row with a NaN or an infinity, ALWAYS for an all-zero row
+LMM_HD inline int emul_neg_bound(int lgk, unsigned long long ri, unsigned long long rj) {
+  if (ri >= 0x7FF0000000000000ull || rj >= 0x7FF0000000000000ull) return LMM_EMUL_NEG_NEVER;
+  if (ri == 0ull || rj == 0ull) return LMM_EMUL_NEG_ALWAYS;
+  return lgk + emul_row_exp(emul_bits_as_double(ri)) + emul_row_exp(emul_bits_as_double(rj)) + LMM_EMUL_NEG_MARGIN;
+}
+LMM_HD inline bool emul_neg_at(int bound, double c) {
+  const unsigned long long u = emul_double_bits(c) & 0x7FFFFFFFFFFFFFFFull;
+  if (u == 0ull || u >= 0x7FF0000000000000ull || bound == LMM_EMUL_NEG_NEVER) return false;
+  int q;
+  (void)frexp(c, &q);      // |c| = f 2^q, 0.5 <= f < 1, subnormals included: ilogb(c) = q - 1
+  return bound <= q - 1;
+}
+LMM_HD inline bool emul_negligible(int K, unsigned long long ri, unsigned long long rj, double c) {
+  return emul_neg_at(emul_neg_bound(emul_ceil_log2(K), ri, rj), c);
+}
+
+// ---- the trapezoid's tile list, the live flags and the live id list ----
+// Lower-trapezoid tiles (tm tile rows, tn tile columns, j <= i) in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles
+// share at most 12 operand panels.  xy (may be nullptr): 2 ints per tile, (tile row, tile column).  Returns the number of tiles.
+inline int emul_tile_list(int tm, int tn, int* xy) {
+  int n = 0;
+  for (int I = 0; I < tm; I += 8)
+    for (int J = 0; J < tn; J += 4)
+      for (int i = I; i < (I + 8 < tm ? I + 8 : tm); ++i)
+        for (int j = J; j < (J + 4 < tn ? J + 4 : tn); ++j)
+          if (j <= i) {
+            if (xy) { xy[2 * n] = i; xy[2 * n + 1] = j; }
+            ++n;
+          }
+  return n;
+}
+// The screen leaves one byte per (matrix, tile): flags[(z tm + tile row) tn + tile column] != 0 when some entry the combine would write
+// is not negligible (the bytes above the diagonal are never written or read).  The GEMM's work ids -- item-major, item = (matrix,
+// modulus), the tile list inside -- are then compacted IN ORDER into the live id list: with `before` live tiles in the matrices
+// before z and lc live tiles in z, the r-th live tile of z (in tile-list order) under modulus t sits at emul_live_slot, so the list
+// is the increasing sequence of the live ids and an XCD's consecutive entries stay on one item's supertiles.  count[0] = entries
+// (live ids), count[1] = live (matrix, tile) pairs.  emul_compact_host is the same arithmetic in plain C++ (tests/c).
+LMM_HD inline size_t emul_flag_at(int tm, int tn, int z, int ti, int tj) { return ((size_t)z * tm + ti) * tn + tj; }
+LMM_HD inline size_t emul_live_slot(int nmod, int before, int lc, int t, int r) { return (size_t)nmod * before + (size_t)t * lc + r; }
+inline int emul_compact_host(const unsigned char* flags, const int* xy, int ntiles, int tm, int tn, int gc, int nmod, int* list) {
+  int before = 0;
+  for (int z = 0; z < gc; ++z) {
+    int lc = 0;
+    for (int k = 0; k < ntiles; ++k) lc += flags[emul_flag_at(tm, tn, z, xy[2 * k], xy[2 * k + 1])] != 0;
+    int r = 0;
+    for (int k = 0; k < ntiles; ++k) {
+      if (flags[emul_flag_at(tm, tn, z, xy[2 * k], xy[2 * k + 1])] == 0) continue;
+      for (int t = 0; t < nmod; ++t) list[emul_live_slot(nmod, before, lc, t, r)] = (z * nmod + t) * ntiles + k;
+      ++r;
+    }
+    before += lc;
+  }
+  return nmod * before;
+}
+// byte offsets in the screen's own block for groups of G matrices (beside the scratch and the aux block, whose layouts stand)
+struct EmulScreen { size_t flags, count, list, total; int ntiles; };
+inline EmulScreen emul_screen_layout(int M, int N, int G, int nmod) {
+  const int tm = (M + LMM_EMUL_TILE - 1) / LMM_EMUL_TILE, tn = (N + LMM_EMUL_TILE - 1) / LMM_EMUL_TILE;
+  EmulScreen s{};
+  s.ntiles = emul_tile_list(tm, tn, nullptr);
+  s.flags = 0;
+  s.count = ((size_t)G * tm * tn + 15) & ~size_t(15);
+  s.list = s.count + 16;
+  s.total = s.list + (size_t)G * nmod * s.ntiles * 4;
+  s.total = (s.total + 7) & ~size_t(7);
+  return s;
+}
+
 // ---- the convert kernel's residue step: no branch, no division, no 32-bit multiply per modulus ----
 // |v| <= 2^58 is cut into its 8 bytes d_i.  For an odd modulus p, x = sum_i d_i (256^i mod p) <= 8 255 (p - 1) < 2^19 is congruent
 // to |v|; the eight products are two 4-byte dot products against the packed constants lo and hi.  q = rint(x fl(1 / p)) is THE

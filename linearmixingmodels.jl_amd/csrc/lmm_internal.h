@@ -168,6 +168,7 @@ bool launch_gemm32w(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, 
 // (emul_shape_ok, emul_scratch_bytes: lmm_emul.h)
 void emul_set_gemm_workgroups(int wgs);      // cap of the persistent GEMM grid (tests); 0: one workgroup per CU
 void emul_set_scratch_poison(int on);        // tests: != 0 fills a group's residue scratch with a non-zero byte before its convert
+void emul_set_screen(int on);                // 0: every tile counts as live (the live id list is the identity); 1: tiles whose update cannot change a bit of C are skipped; < 0: LMM_EMUL_SCREEN (default 1)
 void emul_set_zero_skip(int on);             // 0: the GEMM walks every K block (all-ones live masks); 1: only the live ones; < 0: LMM_EMUL_ZERO_SKIP (default 1)
 // Row maxima that outlive the update (potrf_batch; emul_amax_cover of lmm_potrf_plan.h): out = this update's array, out[m ld + r] for
 // matrix m and the ABSOLUTE row r of the matrix (the panel's row i is row row0 + i), written for all nb matrices; src[0 .. n) = arrays
@@ -178,10 +179,11 @@ void emul_set_zero_skip(int on);             // 0: the GEMM walks every K block 
 // below a factored block column never change).  nullptr: the maxima live in the scratch and in aux, per group, and the whole panel
 // is read.
 // aux: emul_aux(M, G, K).total bytes (lmm_emul.h) for the live K blocks and the dead pieces of one group's panels; without a keep,
-// .total_bmax bytes: the group's block maxima follow them.
+// .total_bmax bytes: the group's block maxima follow them.  screen: emul_screen_layout(M, N, G, nmod).total bytes for the tile flags,
+// the live id list and its counts.
 struct EmulAmaxKeep { unsigned long long* out; int ld, row0, n; const unsigned long long* src[LMM_EMUL_COVER_MAX]; int scan0; unsigned long long* bmax; int cb0, ncb; };
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
-                              int G, int nmod, void* scratch, void* aux, hipStream_t st, const EmulAmaxKeep* keep = nullptr);      // the first HIP error of its host-side calls
+                              int G, int nmod, void* scratch, void* aux, void* screen, hipStream_t st, const EmulAmaxKeep* keep = nullptr);      // the first HIP error of its host-side calls
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,
                    const BatchInfo& info, int nb, hipStream_t st);
 // no_splitk: never split the last round's tiles along K (their f64 atomics make the sum order run-dependent): bitwise reproducible

@@ -12,6 +12,9 @@
 //      i8_syrk_mod_kernel_ps with ABL = 6, beside the loops and kernels this one replaced; the probe stands alone: its numbers
 //      speak for a K step and a tile's fixed cost, not for a level's time);
 //   3. emul_combine_kernel: CRT reconstruction in Float64 (lmm_emul.h) and C_ij -= X 2^(e_i + e_j - 2b) for i >= j.
+// Between 1 and 2, emul_screen_kernel marks the tiles in which no output can change by a bit (from the row maxima of 1 and C itself:
+// emul_negligible, lmm_emul.h) and emul_compact_kernel lists the work ids of the others; 2 walks that list and 3 returns on a dead
+// tile's flag.
 // Integer sums are exact in any order: the result is bitwise reproducible.
 #include "lmm_internal.h"
 #include "lmm_emul.h"
@@ -201,24 +204,14 @@ void launch_convert(int nmod, dim3 grid, hipStream_t st, const BatchPtr& P, int 
   emul_convert_kernel<NMOD><<<grid, 256, 0, st>>>(P, g0, off, ld, M, Mp, K, bits, amax, as, R, sc, ex, masks, dead);
 }
 
-// lower-trapezoid tiles in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles share at most 12 operand panels
-inline int emul_tile_count(int tm, int tn) {
-  int n = 0;
-  for (int i = 0; i < tm; ++i) n += (i + 1 < tn) ? i + 1 : tn;
-  return n;
-}
-// The list is built on the host once per (tile rows, tile columns) and kept on the device for the life of the process (a few KB per
-// shape; one process drives one GPU).  nullptr: the allocation or the copy failed (*err says why).
+// The tile list (emul_tile_list, lmm_emul.h) is built on the host once per (tile rows, tile columns) and kept on the device for the
+// life of the process (a few KB per shape; one process drives one GPU).  nullptr: the allocation or the copy failed (*err says why).
 const int2* emul_tiles(int tm, int tn, hipError_t* err) {
   static std::map<std::pair<int, int>, int2*> cache;
   auto it = cache.find({tm, tn});
   if (it != cache.end()) return it->second;
-  std::vector<int2> v;
-  for (int I = 0; I < tm; I += 8)
-    for (int J = 0; J < tn; J += 4)
-      for (int i = I; i < std::min(I + 8, tm); ++i)
-        for (int j = J; j < std::min(J + 4, tn); ++j)
-          if (j <= i) v.push_back(make_int2(i, j));
+  std::vector<int2> v(emul_tile_list(tm, tn, nullptr));
+  emul_tile_list(tm, tn, reinterpret_cast<int*>(v.data()));
   int2* d = nullptr;
   *err = hipMalloc((void**)&d, v.size() * sizeof(int2));
   if (*err != hipSuccess) return nullptr;
@@ -226,6 +219,75 @@ const int2* emul_tiles(int tm, int tn, hipError_t* err) {
   if (*err != hipSuccess) { (void)hipFree(d); return nullptr; }
   cache[{tm, tn}] = d;
   return d;
+}
+
+// The screen (lmm_emul.h, negligible updates): one workgroup per (tile of the trapezoid's list, matrix), one thread per row of the
+// tile.  It tests the entries the combine would write -- i >= j, i < M, j < N -- with emul_negligible against the row maxima the
+// convert takes its exponents from, SCR_COLS columns at a time (all loads of a chunk issued before the first is used), and stops at
+// the first chunk that holds an entry that is not negligible: a live tile, and any tile of data that does not decay, reads one
+// chunk; a dead tile reads its C once.  Thread 0 stores the tile's byte: a plain store, every byte the compaction and the combine
+// read is written by each group.
+constexpr int SCR_COLS = 16;
+__global__ __launch_bounds__(256) void emul_screen_kernel(BatchPtr A, int g0, size_t offC, int ldc, int M, int N, int K, const unsigned long long* __restrict__ amax, int as,
+                                                          const int2* __restrict__ tiles, int tm, int tn, unsigned char* flags) {
+  const int tid = threadIdx.x, z = blockIdx.y;
+  const int2 t = tiles[blockIdx.x];
+  const int i = t.x * TILE + tid, j0 = t.y * TILE, jn = min(N, j0 + TILE), lgk = emul_ceil_log2(K);
+  const unsigned long long* az = amax + (size_t)z * as;
+  const unsigned long long ri = i < M ? az[i] : 0ull;
+  const double* C = A.p[g0 + z] + offC + i;
+  bool live = false;
+  for (int jc = j0; jc < jn && !live; jc += SCR_COLS) {
+    double cv[SCR_COLS];
+    bool on[SCR_COLS];
+#pragma unroll
+    for (int q = 0; q < SCR_COLS; ++q) {
+      const int j = jc + q;
+      on[q] = j < jn && i >= j && i < M;
+      cv[q] = on[q] ? C[(size_t)j * ldc] : 0.0;
+    }
+    bool lv = false;
+#pragma unroll
+    for (int q = 0; q < SCR_COLS; ++q)
+      if (on[q]) lv |= !emul_neg_at(emul_neg_bound(lgk, ri, az[jc + q]), cv[q]);      // j < N <= M: the row maximum of column j's panel row exists
+    live = __syncthreads_or(lv ? 1 : 0) != 0;
+  }
+  if (tid == 0) flags[emul_flag_at(tm, tn, z, t.x, t.y)] = live ? 1 : 0;
+}
+// The live id list (lmm_emul.h): one workgroup per matrix of the group, no workgroup reads what another writes.  Workgroup z counts
+// the live tiles of the matrices before it and its own (ballots, tile-list order), then walks its tiles again and stores, for the
+// r-th live one, its nmod ids at emul_live_slot -- consecutive r in consecutive lanes.  The last workgroup stores the two counts.
+__global__ __launch_bounds__(256) void emul_compact_kernel(const unsigned char* __restrict__ flags, const int2* __restrict__ tiles, int ntiles, int tm, int tn, int nmod,
+                                                           int* __restrict__ list, int* __restrict__ count) {
+  __shared__ int part[2][4], woff[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, z = blockIdx.x;
+  auto flag = [&](int zz, int k) {
+    const int2 t = tiles[k];
+    return flags[emul_flag_at(tm, tn, zz, t.x, t.y)] != 0;
+  };
+  int nb = 0, nl = 0;      // wave-uniform: live tiles this wave saw in the matrices before z, and in z
+  for (int q0 = 0; q0 < z * ntiles; q0 += 256) {
+    const int q = q0 + tid;
+    nb += __popcll(__ballot(q < z * ntiles && flag(q / ntiles, q % ntiles)));
+  }
+  for (int k0 = 0; k0 < ntiles; k0 += 256) nl += __popcll(__ballot(k0 + tid < ntiles && flag(z, k0 + tid)));
+  if (lane == 0) { part[0][w] = nb; part[1][w] = nl; }
+  __syncthreads();
+  const int before = part[0][0] + part[0][1] + part[0][2] + part[0][3], lc = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+  int run = 0;      // live tiles of z before this chunk
+  for (int k0 = 0, it = 0; k0 < ntiles; k0 += 256, ++it) {
+    const int k = k0 + tid;
+    const bool f = k < ntiles && flag(z, k);
+    const unsigned long long bal = __ballot(f);
+    if (lane == 0) woff[it & 1][w] = __popcll(bal);
+    __syncthreads();      // woff[it & 1] is next written two chunks on, with a barrier in between
+    int r = run + __popcll(bal & ((1ull << lane) - 1ull));
+    for (int v = 0; v < w; ++v) r += woff[it & 1][v];
+    if (f)
+      for (int t = 0; t < nmod; ++t) list[emul_live_slot(nmod, before, lc, t, r)] = (z * nmod + t) * ntiles + k;
+    run += woff[it & 1][0] + woff[it & 1][1] + woff[it & 1][2] + woff[it & 1][3];
+  }
+  if (z == (int)gridDim.x - 1 && tid == 0) { count[0] = nmod * (before + lc); count[1] = before + lc; }
 }
 
 __device__ __forceinline__ void glds16(const int8_t* src, int8_t* lds_wave_base) {
@@ -309,14 +371,22 @@ __device__ __forceinline__ void emul_transpose4(unsigned (&w)[4]) {
 // times, both from the same helper on the same two mask words, which are loaded with the tile coordinates, one tile ahead.  Nothing
 // above asks which k a stage holds or how many stages a tile has (>= 1 is kept: an empty list becomes block 0), so the phase table, the
 // barriers and the counts stand as they are.  All-ones masks (lmm_dev_set_emul_zero_skip(0)) give the full walk.
+//
+// Screen: the walk is not over all (item, tile) pairs but over the live id list (emul_compact_kernel): nlive[0] entries, read from
+// device memory at entry -- the XCD ranges and cnt come from it, and a workgroup whose range is empty returns -- and a position of
+// the walk maps to its work id through live[], one scalar load more where the tile coordinates are loaded, still one tile ahead.
+// The grid is sized by the host's upper bound, all ids.  A tile that is not in the list is never staged, multiplied or stored: its
+// part of U keeps whatever it held.  The K loop does not know: it sees tiles, as before.
 __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restrict__ R, int8_t* __restrict__ U, const int2* __restrict__ tiles, int ntiles,
-                                                           int nids, int Mp, int Np, int K, EmulConst c, const unsigned long long* __restrict__ masks) {
+                                                           const int* __restrict__ live, const int* __restrict__ nlive, int Mp, int Np, int K, EmulConst c,
+                                                           const unsigned long long* __restrict__ masks) {
   __shared__ __attribute__((aligned(1024))) int8_t lds[2 * STAGE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 2, wc = wid & 3;
   // the walk of this workgroup: ids first, first + step, .. (cnt of them) of its XCD's range; fewer than 8 workgroups split the ids
   // among themselves
   const int nwg = gridDim.x, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int step = emul_range_wgs(nwg, xcd);
+  const int nids = nlive[0];      // entries of the live id list: the walk is over list positions, live[position] is the work id
   const EmulRange rg = emul_xcd_range(nids, nwg, xcd);
   const int first = rg.start + slot, span = rg.len - slot;
   const int cnt = span > 0 ? (span + step - 1) / step : 0;
@@ -343,7 +413,8 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
     const EmulMask a{mz[t.x * LMM_EMUL_MASK_WORDS], mz[t.x * LMM_EMUL_MASK_WORDS + 1]}, b{mz[t.y * LMM_EMUL_MASK_WORDS], mz[t.y * LMM_EMUL_MASK_WORDS + 1]};
     return emul_live_stages(a, b, nkb);
   };
-  auto cursor_peek = [&](int idn) {
+  auto cursor_peek = [&](int pos) {
+    const int idn = live[pos];
     pitem = idn / ntiles;
     pt = tiles[idn - pitem * ntiles];
     pm = live_of(pitem, pt);
@@ -405,17 +476,19 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
   int par = 0;      // s & 1
   bool stored = false;      // an epilogue's stores have been issued since the last wait for vmcnt
   // the MFMA side: coordinates and stage count of the next work id, loaded one tile ahead like the cursor's
-  int nitem = first / ntiles;
-  int2 nt = tiles[first - nitem * ntiles];
+  int nid = live[first];
+  int nitem = nid / ntiles;
+  int2 nt = tiles[nid - nitem * ntiles];
   int nnk = emul_mask_count(live_of(nitem, nt));
-  for (int n = 0, id = first; n < cnt; ++n, id += step) {
+  for (int n = 0, pos = first; n < cnt; ++n, pos += step) {
     // what this work id's K loop and epilogue need
     const int item = nitem, nk = nnk;
     const int2 t = nt;
     const int p = c.p[item % c.nmod];
     if (n + 1 < cnt) {
-      nitem = (id + step) / ntiles;
-      nt = tiles[id + step - nitem * ntiles];
+      nid = live[pos + step];
+      nitem = nid / ntiles;
+      nt = tiles[nid - nitem * ntiles];
       nnk = emul_mask_count(live_of(nitem, nt));
     }
     for (int kt = 0; kt < nk; ++kt, par ^= 1) {
@@ -462,7 +535,7 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
       if (more) piece(par, 3);
       EMUL_PIN();
     }
-    // epilogue of work id `id`: reduce mod p (emul_acc_residue: |acc| <= K 128^2 <= 2^28) and pack the 4 consecutive rows a lane holds of
+    // epilogue of this work id: reduce mod p (emul_acc_residue: |acc| <= K 128^2 <= 2^28) and pack the 4 consecutive rows a lane holds of
     // a 16 x 16 block into one dword.  C/D map of 16x16: column = lane & 15, rows = 4 (lane >> 4) + e, so the dword of row fragment m
     // in lane (c, g) is rows 16 m + 4 g .. + 3 of column c, and storing it as it is makes a wave store 16 pieces of 16 bytes in 16
     // lines (the columns of U are Mp bytes apart).  Instead the four row groups of a column exchange the dwords of row fragments
@@ -501,11 +574,15 @@ __global__ __launch_bounds__(512, 2) void emul_gemm_kernel(const int8_t* __restr
 // The sums of emul_crt run modulus-outer over the thread's 4 outputs (each output sees the same operations in the same order), so a
 // CRT weight is a scalar operand that is dead after 4 FMAs: held for all 16 moduli at once, the 96 dwords of weights do not fit the
 // scalar registers.
+// A wave covers 256 consecutive rows of one column, which lie in ONE tile: it reads that tile's flag first (the screen's) and returns
+// for a dead tile, having loaded nothing else.  The GEMM never wrote U there, so the flag is the only guard against its stale bytes.
 template <int NMOD>
 __global__ __launch_bounds__(256) void emul_combine_kernel(BatchPtr A, int g0, size_t offC, int ldc, int M, int N, int Mp, int Np, EmulConst c,
-                                                           const int8_t* __restrict__ U, const double* __restrict__ sc, const int* __restrict__ ex) {
+                                                           const int8_t* __restrict__ U, const double* __restrict__ sc, const int* __restrict__ ex,
+                                                           const unsigned char* __restrict__ flags) {
   const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4, j = blockIdx.y, z = blockIdx.z;
   if (i0 + 3 < j || i0 >= M) return;
+  if (flags[emul_flag_at(Mp / TILE, Np / TILE, z, i0 / TILE, j / TILE)] == 0) return;
   unsigned w[NMOD];
 #pragma unroll
   for (int t = 0; t < NMOD; ++t) w[t] = *reinterpret_cast<const unsigned*>(U + (((size_t)z * NMOD + t) * Np + j) * Mp + i0);
@@ -540,16 +617,17 @@ __global__ __launch_bounds__(256) void emul_combine_kernel(BatchPtr A, int g0, s
 }
 template <int NMOD>
 void launch_combine(int nmod, dim3 grid, hipStream_t st, const BatchPtr& C, int g0, size_t offC, int ldc, int M, int N, int Mp, int Np, const EmulConst& c,
-                    const int8_t* U, const double* sc, const int* ex) {
+                    const int8_t* U, const double* sc, const int* ex, const unsigned char* flags) {
   if constexpr (NMOD > LMM_EMUL_MINMOD) {
-    if (nmod != NMOD) return launch_combine<NMOD - 1>(nmod, grid, st, C, g0, offC, ldc, M, N, Mp, Np, c, U, sc, ex);
+    if (nmod != NMOD) return launch_combine<NMOD - 1>(nmod, grid, st, C, g0, offC, ldc, M, N, Mp, Np, c, U, sc, ex, flags);
   }
-  emul_combine_kernel<NMOD><<<grid, 256, 0, st>>>(C, g0, offC, ldc, M, N, Mp, Np, c, U, sc, ex);
+  emul_combine_kernel<NMOD><<<grid, 256, 0, st>>>(C, g0, offC, ldc, M, N, Mp, Np, c, U, sc, ex, flags);
 }
 
 int g_emul_gemm_wgs = 0;      // emul_set_gemm_workgroups: 0 = one workgroup per CU
 int g_emul_zero_skip = -1;    // emul_set_zero_skip: -1 = LMM_EMUL_ZERO_SKIP (read once; default on)
 int g_emul_poison = 0;        // emul_set_scratch_poison (tests): the residue scratch of a group is filled with a non-zero byte before its convert
+int g_emul_screen = -1;       // emul_set_screen: -1 = LMM_EMUL_SCREEN (read once; default on)
 
 bool emul_zero_skip_on() {
   if (g_emul_zero_skip < 0) {
@@ -559,8 +637,17 @@ bool emul_zero_skip_on() {
   return g_emul_zero_skip != 0;
 }
 
+bool emul_screen_on() {
+  if (g_emul_screen < 0) {
+    const char* e = getenv("LMM_EMUL_SCREEN");
+    g_emul_screen = (e && e[0] == '0') ? 0 : 1;
+  }
+  return g_emul_screen != 0;
+}
+
 }  // namespace
 
+void emul_set_screen(int on) { g_emul_screen = on < 0 ? -1 : (on ? 1 : 0); }
 void emul_set_gemm_workgroups(int wgs) { g_emul_gemm_wgs = wgs; }
 void emul_set_zero_skip(int on) { g_emul_zero_skip = on < 0 ? -1 : (on ? 1 : 0); }
 void emul_set_scratch_poison(int on) { g_emul_poison = on ? 1 : 0; }
@@ -573,15 +660,18 @@ void emul_set_scratch_poison(int on) { g_emul_poison = on ? 1 : 0; }
 // bytes.  aux holds the live K blocks of a group's panels and its dead pieces (lmm_emul.h): written in full by emul_live_kernel
 // before each convert, or, with the zero skip switched off, the masks set to ones on the stream and no bitmap.  The residues R are
 // shared by the groups and the updates that go through one scratch block and a dead block is never written, so it holds whatever
-// was there: R is read through emul_live_stages only.
+// was there: R is read through emul_live_stages only.  screen: emul_screen_layout(M, N, G, nmod).total bytes for a group's tile
+// flags, its live id list and the two counts (lmm_emul.h), written in full by every group: by emul_screen_kernel once the row maxima
+// exist, or, with the screen switched off, the flags set to ones on the stream; emul_compact_kernel runs either way, and the list is
+// then the identity.  U is written for live tiles only and holds stale bytes elsewhere: U is read behind the flags only.
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
-                              int G, int nmod, void* scratch, void* aux, hipStream_t st, const EmulAmaxKeep* keep) {
+                              int G, int nmod, void* scratch, void* aux, void* screen, hipStream_t st, const EmulAmaxKeep* keep) {
   static EmulConst consts[LMM_EMUL_MAXMOD + 1];
   if (consts[nmod].nmod != nmod) consts[nmod] = emul_make_const(nmod);
   const EmulConst& c = consts[nmod];
   const int bits = emul_bits(nmod, K);
   const EmulLayout L = emul_layout(M, N, K, G, nmod);
-  const int ntiles = emul_tile_count(L.Mp / TILE, L.Np / TILE);
+  const int tm = L.Mp / TILE, tn = L.Np / TILE, ntiles = emul_tile_list(tm, tn, nullptr);
   hipError_t err = hipSuccess;
   const int2* tiles = emul_tiles(L.Mp / TILE, L.Np / TILE, &err);
   if (tiles == nullptr) return err;
@@ -591,7 +681,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
   unsigned long long* amax = reinterpret_cast<unsigned long long*>(s + L.amax);
   double* sc = reinterpret_cast<double*>(s + L.sc);
   int* ex = reinterpret_cast<int*>(s + L.ex);
-  const bool skip = emul_zero_skip_on();
+  const bool skip = emul_zero_skip_on(), screened = emul_screen_on();
   const int wgs = g_emul_gemm_wgs > 0 ? g_emul_gemm_wgs : device_cus();      // one 128-KiB workgroup fits on a CU
   EmulBlockMax bm{};
   if (keep) {      // every row of every matrix gets its first write from the fold: no memset
@@ -621,12 +711,23 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
     }
     if (g_emul_poison) {
       err = hipMemsetAsync(R, 0x5A, (size_t)gc * nmod * L.Mp * K, st);
+      if (err == hipSuccess) err = hipMemsetAsync(U, 0x5A, (size_t)gc * nmod * L.Np * L.Mp, st);
       if (err != hipSuccess) return err;
     }
+    const EmulScreen S = emul_screen_layout(M, N, gc, nmod);
+    unsigned char* flags = static_cast<unsigned char*>(screen) + S.flags;
+    int* nlive = reinterpret_cast<int*>(static_cast<char*>(screen) + S.count);
+    int* live = reinterpret_cast<int*>(static_cast<char*>(screen) + S.list);
+    if (screened) emul_screen_kernel<<<dim3(ntiles, gc), 256, 0, st>>>(C, g0, offC, ldc, M, N, K, am, as, tiles, tm, tn, flags);
+    else {
+      err = hipMemsetAsync(flags, 1, (size_t)gc * tm * tn, st);
+      if (err != hipSuccess) return err;
+    }
+    emul_compact_kernel<<<gc, 256, 0, st>>>(flags, tiles, ntiles, tm, tn, nmod, live, nlive);
     launch_convert<LMM_EMUL_MAXMOD>(nmod, dim3(L.Mp / TILE * CV_SPLIT, K / CV_K, gc), st, P, g0, offP, ldp, M, L.Mp, K, bits, am, as, R, sc, ex, masks, dead);
     const int nids = ntiles * gc * nmod;
-    emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, ntiles, nids, L.Mp, L.Np, K, c, masks);
-    launch_combine<LMM_EMUL_MAXMOD>(nmod, dim3((M + 1023) / 1024, N, gc), st, C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex);
+    emul_gemm_kernel<<<std::min(nids, wgs), 512, 0, st>>>(R, U, tiles, ntiles, live, nlive, L.Mp, L.Np, K, c, masks);
+    launch_combine<LMM_EMUL_MAXMOD>(nmod, dim3((M + 1023) / 1024, N, gc), st, C, g0, offC, ldc, M, N, L.Mp, L.Np, c, U, sc, ex, flags);
   }
   return hipSuccess;
 }

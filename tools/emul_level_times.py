@@ -9,7 +9,8 @@ kept maxima), so their grid does not tell.  Prints ms summed over the launches o
 kernel.  emul_live is the kernel in front of a convert that decides the live blocks and pieces of a group from the block maxima; a
 trace from before it has zeros there, and the kernel it made unnecessary, emul_zero_fill (zero residues into the pieces the convert left
 unwritten), has zeros in a trace with it.  `fill` is the stream's memsets inside an update: before emul_live, the masks and the
-unwritten-piece bitmap of a group were one of them.
+unwritten-piece bitmap of a group were one of them.  emul_screen marks the tiles whose update cannot change a bit of C and
+emul_compact lists the GEMM's work ids of the others; a trace from before them has zeros there.
 
 Then one line per emulated UPDATE, in launch order: an update is a maximal run of emulation kernels and the fills between them
 (two emulated updates are never neighbours: the factorisation of the columns between them lies in between).  Its key is (K, Mp,
@@ -22,7 +23,7 @@ import collections
 import csv
 import sys
 
-EMUL = ("emul_rowmax", "emul_live", "emul_convert", "emul_zero_fill", "emul_gemm", "emul_combine")
+EMUL = ("emul_rowmax", "emul_live", "emul_convert", "emul_zero_fill", "emul_screen", "emul_compact", "emul_gemm", "emul_combine")
 ALIAS = {"emul_amax_fold": "emul_rowmax"}
 
 
@@ -92,7 +93,7 @@ def main(argv):
     print("emulated total: " + str({k: round(sum(per[kern][k] for kern in per), 2) for k in levels}))
     print("other kernels ms: " + str({k: round(v, 2) for k, v in sorted(other.items(), key=lambda kv: -kv[1])[:10]}))
     if runs:
-        print("emulated updates in launch order: K Mp nb groups | rowmax live convert zero_fill gemm combine fill leaf | kernel sum, span (ms)")
+        print("emulated updates in launch order: K Mp nb groups | " + " ".join(k[5:] for k in EMUL) + " fill leaf | kernel sum, span (ms)")
     for u in runs:
         tot = sum(u[k] for k in EMUL) + u["fill"] + u["leaf"]
         print(f"  K={u['K']:5d} Mp={int(u['Mp']):5d} nb={u['nb']:2d} groups={u['groups']:2d} | " + " ".join(f"{u[k]:7.3f}" for k in EMUL)
