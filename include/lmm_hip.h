@@ -823,7 +823,7 @@ int lmm_dev_statespace_sample_posterior(const double* x, int n, const lmm_gp_t* 
  *                    lmm_oilmm_logpdf_statespace, in its order.  *out_logpdf (may be NULL) is bitwise the value of
  *                    lmm_oilmm_logpdf_statespace with the regulariser (the filter runs anyway).  The handle owns, on the device, the
  *                    sorted x, the states and H = U sqrt(S) of the shard, and on the host the latents' descriptors and means and sigma2
- *                    (they travel as kernel arguments): 2 (D_l + D_l (D_l + 1) / 2) n doubles per latent l of the shard (2 n, 10 n, 18 n
+ *                    (they travel as kernel arguments) and copies of U and S (lmm_oilmm_statespace_post_append projects with them): 2 (D_l + D_l (D_l + 1) / 2) n doubles per latent l of the shard (2 n, 10 n, 18 n
  *                    for Matern12, Matern32 and SHO, Matern52) + n doubles for x + p (l1 - l0) for H.  States are stored
  *                    point-major, [latent][n][component] (a query reads one or two lines per state; measured against
  *                    component-major in DESIGN.md 4.18), the D means first and then the upper triangle of the covariance by rows;
@@ -895,6 +895,47 @@ int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, 
                                    int nsamples, int add_noise, double* out);
 int lmm_dev_statespace_post_sample(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate,
                                    const double* xs, int ns, const double* z, int nsamples, int chunk, double* f);
+
+/* ---- state space: appending observations --------------------------------------------------------------
+ * Conditioning a live handle on LATER observations without starting over (DESIGN.md 4.18 "Appending observations").  The filtered state
+ * of the last training point is a sufficient statistic for everything in front of it, so k new points at or behind the last input cost
+ * one front end and one filter over those k points, started from that state: O(k), whatever n is.  The RTS recursion consumes filtered
+ * states and inputs only, never the data, so the smoothed states are rebuilt from the handle alone, in O(n), when they are needed.
+ * LAZINESS.  An append leaves the smoothed states behind (smoothed_n < n).  A query reads a smoothed state only when it lies in FRONT
+ * of the last input, so lmm_oilmm_statespace_post_mean_and_var, ..._grad_xs and ..._post_rand first decide on the device whether any of
+ * their queries does (one small kernel, a 4-byte download) and run the O(n) pass only then; lmm_statespace_post_window does when lo
+ * does.  A batch of pure forecasts (every query >= the last input; a query equal to it is a forecast) never triggers the pass, and
+ * its results are bitwise those of the same call after lmm_statespace_post_smooth.  The query entry points keep their const handle.
+ * CAPACITY.  The handle's buffers (x, and the filtered and smoothed states of every latent of the shard) have room for cap >= n points;
+ * a latent's block is cap x (D_l + D_l (D_l + 1) / 2), so the memory of lmm_oilmm_statespace_posterior_create reads with cap for n.
+ * Create leaves cap = n (its memory is what it was).  An append that needs more grows to max(2 cap, n + k) with one device-to-device
+ * copy of the filled rows; lmm_statespace_post_reserve grows once to a known size.  Results do not depend on cap (bitwise).
+ *   lmm_oilmm_statespace_post_append : x_new: k values, finite and non-decreasing, host or device, with x_new[0] >= the handle's last
+ *                    input (ties are served: a spacing of 0 is exact).  y_new: k x p by outputs (y_new[o k + t]), host or device, NaN =
+ *                    missing, with create's rules.  Projects the k points (create's front end, with the U, S and sigma2 the handle
+ *                    keeps), filters them from the stored last state and appends x and the filtered states: n += k, smoothed_n stays.
+ *                    *out_increment (may be NULL) = log p(y_new | all earlier data) with the regulariser terms of the new points, so
+ *                    that create's *out_logpdf plus the increments is the log density of all the data.  Refusals, all before the handle
+ *                    is touched (after a failed call it answers exactly as before): post NULL or k < 0 -> LMM_ERR_ARG; the fp32 compute
+ *                    mode -> LMM_ERR_UNSUPPORTED; a NaN or +-Inf in x_new, or x_new[t] < x_new[t - 1] -> LMM_ERR_ARG with the index in
+ *                    lmm_last_error_detail's `info`; x_new[0] in front of the last input -> LMM_ERR_ARG, `info` = 0 (appended points lie
+ *                    at or behind the last input); a point observing 0 < p_t < m outputs -> LMM_ERR_UNSUPPORTED naming it by its index
+ *                    in the handle's numbering, n + t (`info`); n + k > INT_MAX -> LMM_ERR_ARG.  k = 0 is LMM_OK and changes nothing.
+ *   lmm_statespace_post_smooth : runs the smoother over all n kept filtered states when smoothed_n < n (then smoothed_n = n); else nothing.
+ *   lmm_statespace_post_reserve : cap = n_total when that is larger than cap; else nothing.
+ *   lmm_statespace_post_size : *n, *smoothed_n, *cap (each may be NULL).
+ *   lmm_dev_statespace_filter_from : building block exported for tests beside lmm_dev_statespace_filter (DEVICE pointers; one latent, gp
+ *                    on the host, its mean is not read): the filter over the k points (x, w, r) whose predecessor is the packed state
+ *                    state0 (D + D (D + 1) / 2 values in the handle's layout) at the input x0 <= x[0] (a host scalar).  *lml = log p(r |
+ *                    state0), fmean, fvar (k each) the filtered first-component marginals, fstate (k x (D + D (D + 1) / 2),
+ *                    point-major) the filtered states.  chunk: points per thread, 0 = the library's default; one chunk (k <= chunk)
+ *                    is a single launch that runs the sequential filter. */
+int lmm_oilmm_statespace_post_append(lmm_ss_post_t* post, const double* x_new, int k, const double* y_new, double* out_increment);
+int lmm_statespace_post_smooth(lmm_ss_post_t* post);
+int lmm_statespace_post_reserve(lmm_ss_post_t* post, int n_total);
+int lmm_statespace_post_size(const lmm_ss_post_t* post, int* n, int* smoothed_n, int* cap);
+int lmm_dev_statespace_filter_from(const double* state0, double x0, const double* x, int k, const lmm_gp_t* gp, const double* w,
+                                   const double* r, int chunk, double* fmean, double* fvar, double* fstate, double* lml);
 
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard

@@ -41,6 +41,8 @@ SYMBOLS = [
     "lmm_oilmm_statespace_posterior_create", "lmm_statespace_post_destroy", "lmm_oilmm_statespace_post_mean_and_var",
     "lmm_dev_statespace_states", "lmm_dev_statespace_interp", "lmm_dev_statespace_interp_layout",
     "lmm_statespace_post_window", "lmm_oilmm_statespace_post_rand", "lmm_dev_statespace_post_sample",
+    "lmm_oilmm_statespace_post_append", "lmm_statespace_post_smooth", "lmm_statespace_post_reserve", "lmm_statespace_post_size",
+    "lmm_dev_statespace_filter_from",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
     "lmm_dev_set_f64_emul", "lmm_dev_syrk_emul", "lmm_dev_emul_host", "lmm_dev_emul_residues", "lmm_dev_set_emul_gemm_workgroups", "lmm_dev_emul_acc_residues",
     "lmm_dev_set_f64_emul_rule", "lmm_dev_set_emul_group", "lmm_dev_set_emul_amax_reuse", "lmm_dev_emul_plan", "lmm_dev_potrf_plan",
@@ -86,6 +88,11 @@ STATESPACE_ARGTYPES = {
     "lmm_statespace_post_window": [_P, _D, _D, _P, _P],
     "lmm_oilmm_statespace_post_rand": [_P, _P, _I, _P, _P, _I, _I, _P],
     "lmm_dev_statespace_post_sample": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P],
+    "lmm_oilmm_statespace_post_append": [_P, _P, _I, _P, _P],
+    "lmm_statespace_post_smooth": [_P],
+    "lmm_statespace_post_reserve": [_P, _I],
+    "lmm_statespace_post_size": [_P, _P, _P, _P],
+    "lmm_dev_statespace_filter_from": [_P, _D, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
 }
 
 # Argument types of the SHO tag entry points (include/lmm_hip.h, LMM_KERNEL_SHO), set on the library by load().

@@ -5146,7 +5146,7 @@ struct SSFront {
   MissingFront F;
 };
 static int ss_front(const double* yd, int n, int p, const double* U, const double* S, int m, double s2, const Latent* lts, int l0, int l1,
-                    SSFront& Fr, bool want_resid = false) {
+                    SSFront& Fr, bool want_resid = false, int point0 = 0) {      // point0: the caller's number of point 0 (an append: the handle's n)
   hipStream_t st0 = g.streams[0];
   const int nw = (p + 63) / 64, ms = l1 - l0;
   std::vector<int> hpt(n);
@@ -5161,8 +5161,8 @@ static int ss_front(const double* yd, int n, int p, const double* U, const doubl
   }
   for (int t = 0; t < n; ++t) {
     if (hpt[t] > 0 && hpt[t] < m) {
-      g.err_latent = -1; g.err_info = t;
-      return fail(LMM_ERR_UNSUPPORTED, "missing data: point %d observes %d outputs, fewer than the m = %d latent processes", t, hpt[t], m);
+      g.err_latent = -1; g.err_info = point0 + t;
+      return fail(LMM_ERR_UNSUPPORTED, "missing data: point %d observes %d outputs, fewer than the m = %d latent processes", point0 + t, hpt[t], m);
     }
     if (hpt[t] > 0) idx.push_back(t);
     if (hpt[t] != p) Fr.has_nan = true;
@@ -5189,7 +5189,7 @@ static int ss_front(const double* yd, int n, int p, const double* U, const doubl
     launch_ss_gather_rows(yd, n, p, idxd.p, nobs, yc.p, st0);
     if (int rc = missing_front(yc.p, nobs, p, U, S, m, s2, means.data(), l0, l1, want_resid, F)) {
       if (rc == LMM_ERR_NOT_PD && g.err_info >= 0 && g.err_info < nobs) {      // the front end numbered the points it saw
-        g.err_info = idx[g.err_info];
+        g.err_info = point0 + idx[g.err_info];
         return fail(LMM_ERR_NOT_PD, "PosDefException: H_t' H_t of point %d is not positive definite over its observed outputs", g.err_info);
       }
       return rc;
@@ -5523,18 +5523,40 @@ struct lmm_ss_post {
   int n = 0, p = 0, m = 0, l0 = 0, l1 = 0;
   double sigma2 = 0.0;
   std::shared_ptr<LatentSet> ls;      // all m latents as the handle was built with them
-  Buf<double> x;                      // the sorted inputs, n
-  Buf<double> fstate, sstate;         // per latent of the shard, one after the other: n x ss_state_comps(D_l), point-major
+  Buf<double> x;                      // the sorted inputs: n of cap
+  Buf<double> fstate;                 // per latent of the shard, one after the other: cap x ss_state_comps(D_l), point-major, n rows filled
   Buf<double> H;                      // p x (l1 - l0), column-major: H = U sqrt(S) of the shard
-  std::vector<size_t> off;            // latent l0 + k's offset into fstate / sstate
+  std::vector<size_t> off;            // latent l0 + k's offset into fstate / sstate: the blocks are strided by cap
+  // Appending (DESIGN.md 4.18 "Appending observations"): rows beyond n are room for later points; the smoothed states are current for
+  // the first smoothed_n points only (== n on a fresh handle) and are rebuilt from the filtered ones, without the data, when a query
+  // in front of the last input needs them -- which a query entry point does through its const handle, hence `mutable`.
+  int cap = 0;
+  mutable int smoothed_n = 0;
+  mutable Buf<double> sstate;         // laid out as fstate
+  std::vector<double> U, S;           // host copies of the mixing matrix's factors (p x m, m): the front end projects new data with them
+  double xlast = 0.0;                 // x[n - 1]
+  double logpdf = 0.0;                // log p(all data so far), regulariser included
 };
+
+// latent k's offset into a state buffer whose blocks hold `cap` points
+static std::vector<size_t> ss_post_offsets(const Latent* lts, int ms, int cap) {
+  std::vector<size_t> off;
+  size_t total = 0;
+  for (int k = 0; k < ms; ++k) {
+    off.push_back(total);
+    total += (size_t)ss_state_comps(ss_state_dim(lts[k].kind)) * cap;
+  }
+  off.push_back(total);               // one behind the last: the buffer's size
+  return off;
+}
 
 // The zero-mean (add_mean: plus the latent's mean) marginals of the ms latents lts[0 .. ms) at the ns queries xsd from their stored
 // states (latent k's block off[k] doubles into fstate / sstate): ml, vl [latent][ns] on the device (vl may be nullptr).  Launches
 // group consecutive latents of one model, LMM_MAX_BATCH at the most.  Queues on streams[0] and does not wait.
 // dx: ml, vl (both given) take the derivatives of the two with respect to the query instead (launch_ss_interp_dx).
 static void ss_interp_latents(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
-                       const double* xsd, int ns, bool add_mean, double* ml, double* vl, bool point_major = true, bool dx = false) {
+                       const double* xsd, int ns, bool add_mean, double* ml, double* vl, bool point_major = true, bool dx = false,
+                       int cap = 0) {       // cap: the points a latent's block has room for (0: n)
   hipStream_t st0 = g.streams[0];
   const auto no_buffers = [](int, int, int) { return size_t(1); };       // a launch allocates nothing: LMM_MAX_BATCH alone limits it
   ss_for_launches(ms, 0, [&](long long k) -> const Latent& { return lts[k]; }, no_buffers, [&](long long e0, int nb, int model, int D) {
@@ -5542,7 +5564,7 @@ static void ss_interp_latents(const double* xd, int n, const Latent* lts, int ms
     SSInterpArgs a{};
     a.x = xd; a.n = n; a.xs = xsd; a.ns = ns;
     a.fstate = fstate + off[k0]; a.sstate = sstate + off[k0];
-    a.state_stride = (size_t)ss_state_comps(D) * n;
+    a.state_stride = (size_t)ss_state_comps(D) * (cap ? cap : n);
     a.comp_stride = point_major ? 1 : (size_t)n; a.point_stride = point_major ? (size_t)ss_state_comps(D) : 1;
     a.mean = ml + (size_t)k0 * ns; a.var = vl ? vl + (size_t)k0 * ns : nullptr;
     if (dx) { a.dmean = a.mean; a.dvar = a.var; a.mean = nullptr; a.var = nullptr; }
@@ -5565,13 +5587,12 @@ int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* 
   const auto& [ls, lts, xd, yd, l0, l1, ms, mk, Fr] = T;
   std::unique_ptr<lmm_ss_post> P(new lmm_ss_post());      // a throw below (a failed allocation) frees what it holds
   P->n = n; P->p = p; P->m = m; P->l0 = l0; P->l1 = l1; P->sigma2 = sigma2; P->ls = ls;
+  P->cap = n; P->smoothed_n = n;
+  P->U.assign(U, U + (size_t)p * m); P->S.assign(S, S + m);
   std::vector<SSEntry> es(ms);
-  size_t total = 0;
-  for (int k = 0; k < ms; ++k) {
-    es[k] = SSEntry{lts + l0 + k, Fr.w.p + (size_t)k * n, Fr.r.p + (size_t)k * n};
-    P->off.push_back(total);
-    total += (size_t)ss_state_comps(ss_state_dim(lts[l0 + k].kind)) * n;
-  }
+  for (int k = 0; k < ms; ++k) es[k] = SSEntry{lts + l0 + k, Fr.w.p + (size_t)k * n, Fr.r.p + (size_t)k * n};
+  P->off = ss_post_offsets(lts + l0, ms, n);
+  const size_t total = P->off[ms];
   P->x = Buf<double>((size_t)n);
   P->fstate = Buf<double>(std::max<size_t>(total, 1)); P->sstate = Buf<double>(std::max<size_t>(total, 1));
   HIPCHK(hipMemcpyAsync(P->x.p, xd.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
@@ -5586,6 +5607,8 @@ int lmm_oilmm_statespace_posterior_create(const double* x, int n, const double* 
   for (int k = 0; k < ms; ++k) value += lml[k];
   value += Fr.reg;
   if (out_logpdf) *out_logpdf = value;
+  P->logpdf = value;
+  HIPCHK(hipMemcpy(&P->xlast, P->x.p + (n - 1), sizeof(double), hipMemcpyDeviceToHost));
   *out = P.release();
   return LMM_OK;
   LMM_CATCH
@@ -5600,6 +5623,202 @@ int lmm_statespace_post_destroy(lmm_ss_post_t* post) {
   return LMM_OK;
 }
 
+// ---- appending observations (DESIGN.md 4.18 "Appending observations") ------------------------------------------------------------
+// The RTS pass over all n kept filtered states (launch_ss_smooth_kept): O(n), without the data.  Returns with streams[0] drained.
+static int ss_post_smooth(const lmm_ss_post* P) {
+  if (P->smoothed_n == P->n) return LMM_OK;
+  hipStream_t st0 = g.streams[0];
+  const int n = P->n, ms = P->l1 - P->l0;
+  const Latent* lts = P->ls->lat.data() + P->l0;
+  const SSChunks plan = ss_plan_chunks(n, 0);
+  const auto bytes = [&](int, int D, int nch) { return ss_bwd_agg_elems(D, nch) * sizeof(double); };
+  ss_for_launches(ms, plan.nch, [&](long long k) -> const Latent& { return lts[k]; }, bytes, [&](long long e0, int nb, int model, int D) {
+    const int k0 = (int)e0;
+    Buf<double> bagg((size_t)nb * ss_bwd_agg_elems(D, plan.nch));
+    SSArgs a{};
+    a.x = P->x.p; a.n = n; a.chunk = plan.chunk; a.nch = plan.nch;
+    a.bagg = bagg.p;
+    a.fkeep = P->fstate.p + P->off[k0]; a.sstate = P->sstate.p + P->off[k0];
+    a.state_stride = (size_t)ss_state_comps(D) * P->cap;
+    for (int j = 0; j < nb; ++j) ss_fill_lat(a.lat[j], lts[k0 + j], false);
+    launch_ss_smooth_kept(a, model, nb, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));          // bagg goes back to the pool
+  });
+  P->smoothed_n = n;
+  return LMM_OK;
+}
+
+// What a query entry point does with a handle whose smoothed states are behind: a query reads one only when it lies in front of the
+// last input (ss_interp's has_next), so one small kernel and a 4-byte download decide (ss_first_flagged's pattern) and a batch of pure
+// forecasts -- a query equal to the last input is one -- never pays the O(n) pass.
+static int ss_post_ensure_smoothed(const lmm_ss_post* P, const double* xsd, int ns) {
+  if (P->smoothed_n == P->n) return LMM_OK;
+  hipStream_t st0 = g.streams[0];
+  Buf<int> flag(1);
+  int h = 0;
+  launch_ss_any_below(xsd, ns, P->xlast, flag.p, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  return h ? ss_post_smooth(P) : (int)LMM_OK;
+}
+
+// Room for n_total points: new buffers, one device-to-device copy of the n filled rows of every block, then the handle takes them (a
+// failed allocation throws before the handle is touched).  The smoothed states are copied too: they stay current for smoothed_n points.
+static void ss_post_grow(lmm_ss_post* P, int n_total) {
+  if (n_total <= P->cap) return;
+  hipStream_t st0 = g.streams[0];
+  const int ms = P->l1 - P->l0, n = P->n;
+  const Latent* lts = P->ls->lat.data() + P->l0;
+  const std::vector<size_t> off = ss_post_offsets(lts, ms, n_total);
+  Buf<double> x((size_t)n_total), fs(std::max<size_t>(off[ms], 1)), ss(std::max<size_t>(off[ms], 1));
+  HIPCHK(hipMemcpyAsync(x.p, P->x.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
+  for (int k = 0; k < ms; ++k) {
+    const size_t bytes = (size_t)ss_state_comps(ss_state_dim(lts[k].kind)) * n * sizeof(double);
+    HIPCHK(hipMemcpyAsync(fs.p + off[k], P->fstate.p + P->off[k], bytes, hipMemcpyDeviceToDevice, st0));
+    HIPCHK(hipMemcpyAsync(ss.p + off[k], P->sstate.p + P->off[k], bytes, hipMemcpyDeviceToDevice, st0));
+  }
+  HIPCHK(hipStreamSynchronize(st0));            // the old buffers go back to the pool below
+  P->x = std::move(x); P->fstate = std::move(fs); P->sstate = std::move(ss);
+  P->off = off; P->cap = n_total;
+}
+
+// The filter over k new points from a stored state, per launch group of the ms latents: latent j reads init[j] (device, packed) at
+// input x0 and writes its k states to out[j] (device, point-major); w, r: [latent][k] on the device; lml: ms host values.
+static int ss_filter_from(const double* xd, int k, double x0, const Latent* lts, int ms, const double* w, const double* r, int chunk,
+                          const double* const* init, double* const* out, double* fmean, double* fvar, double* lml) {
+  hipStream_t st0 = g.streams[0];
+  const SSChunks plan = ss_plan_chunks(k, chunk);
+  const int nch = plan.nch;
+  const auto bytes = [&](int, int D, int nch) { return (ss_fwd_agg_elems(D, nch) + (size_t)nch) * sizeof(double); };
+  ss_for_launches(ms, nch, [&](long long j) -> const Latent& { return lts[j]; }, bytes, [&](long long e0, int nb, int model, int D) {
+    const int k0 = (int)e0;
+    Buf<double> agg, part, lmld(nb);
+    if (nch > 1) { agg = Buf<double>((size_t)nb * ss_fwd_agg_elems(D, nch)); part = Buf<double>((size_t)nb * nch); }
+    SSFromArgs a{};
+    a.x = xd; a.n = k; a.chunk = plan.chunk; a.nch = nch; a.x0 = x0;
+    a.agg = agg.p; a.part = part.p;
+    a.fmean = fmean ? fmean + (size_t)k0 * k : nullptr; a.fvar = fvar ? fvar + (size_t)k0 * k : nullptr;
+    for (int j = 0; j < nb; ++j) {
+      const Latent& L = lts[k0 + j];
+      a.lat[j].var = L.terms[0].ev.var; a.lat[j].inv_ls = L.terms[0].ev.inv_ls; a.lat[j].quality = L.quality;
+      a.lat[j].w = w + (size_t)(k0 + j) * k; a.lat[j].r = r + (size_t)(k0 + j) * k;
+      a.lat[j].init = init[k0 + j]; a.lat[j].out = out[k0 + j];
+    }
+    launch_ss_filter_from(a, model, nb, lmld.p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(lml + k0, lmld.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));          // the buffers above go back to the pool
+  });
+  return LMM_OK;
+}
+
+int lmm_oilmm_statespace_post_append(lmm_ss_post_t* post, const double* x_new, int k, const double* y_new, double* out_increment) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || k < 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return ss_refuse_f32();
+  if (k == 0) {
+    if (out_increment) *out_increment = 0.0;
+    return LMM_OK;
+  }
+  if (!x_new || !y_new) return fail(LMM_ERR_ARG, "bad arguments");
+  lmm_ss_post* P = post;
+  const int n = P->n, p = P->p, m = P->m, ms = P->l1 - P->l0;
+  if ((long long)n + k > INT_MAX) return fail(LMM_ERR_ARG, "state-space posterior: %d points and %d more are too many", n, k);
+  hipStream_t st0 = g.streams[0];
+  const Latent* lts = P->ls->lat.data();
+  DevIn xd(x_new, (size_t)k, st0), yd(y_new, (size_t)k * p, st0);
+  // every refusal comes before the handle is touched
+  if (ss_first_flagged(launch_ss_finite, xd.p, k) != INT_MAX)
+    return fail(LMM_ERR_ARG, "state-space posterior: x_new[%d] is not finite", g.err_info);
+  if (int rc = ss_check_sorted(xd.p, k)) return rc;
+  double ends[2];
+  HIPCHK(hipMemcpyAsync(&ends[0], xd.p, sizeof(double), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipMemcpyAsync(&ends[1], xd.p + (k - 1), sizeof(double), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  if (ends[0] < P->xlast) {
+    g.err_latent = -1; g.err_info = 0;
+    return fail(LMM_ERR_ARG, "state-space posterior: appended points lie at or behind the last input (x_new[0] = %g is in front of %g)",
+                ends[0], P->xlast);
+  }
+  SSFront Fr;
+  if (int rc = ss_front(yd.p, k, p, P->U.data(), P->S.data(), m, P->sigma2, lts, P->l0, P->l1, Fr, false, n)) return rc;
+  if (n + k > P->cap) ss_post_grow(P, (int)std::min<long long>(INT_MAX, std::max<long long>(2ll * P->cap, (long long)n + k)));      // geometric
+  HIPCHK(hipMemcpyAsync(P->x.p + n, xd.p, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, st0));
+  std::vector<const double*> init(ms);
+  std::vector<double*> outp(ms);
+  for (int j = 0; j < ms; ++j) {
+    const size_t comps = (size_t)ss_state_comps(ss_state_dim(lts[P->l0 + j].kind));
+    init[j] = P->fstate.p + P->off[j] + (size_t)(n - 1) * comps;
+    outp[j] = P->fstate.p + P->off[j] + (size_t)n * comps;
+  }
+  std::vector<double> lml(std::max(ms, 1), 0.0);
+  if (int rc = ss_filter_from(P->x.p + n, k, P->xlast, lts + P->l0, ms, Fr.w.p, Fr.r.p, 0, init.data(), outp.data(), nullptr, nullptr,
+                              lml.data())) return rc;
+  HIPCHK(hipStreamSynchronize(st0));
+  double inc = 0.0;
+  for (int j = 0; j < ms; ++j) inc += lml[j];
+  inc += Fr.reg;
+  P->n = n + k; P->xlast = ends[1]; P->logpdf += inc;       // smoothed_n stays: the smoothed states are now behind
+  if (out_increment) *out_increment = inc;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_statespace_post_smooth(lmm_ss_post_t* post) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return ss_refuse_f32();
+  return ss_post_smooth(post);
+  LMM_CATCH
+}
+
+int lmm_statespace_post_reserve(lmm_ss_post_t* post, int n_total) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post) return fail(LMM_ERR_ARG, "bad arguments");
+  ss_post_grow(post, n_total);
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_statespace_post_size(const lmm_ss_post_t* post, int* n, int* smoothed_n, int* cap) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!post) return fail(LMM_ERR_ARG, "bad arguments");
+  if (n) *n = post->n;
+  if (smoothed_n) *smoothed_n = post->smoothed_n;
+  if (cap) *cap = post->cap;
+  return LMM_OK;
+}
+
+// Building block for tests beside lmm_dev_statespace_filter: the filter of ONE latent over k points from the packed state `state0`
+// (device) at input x0 <= x[0].  fstate: k x ss_state_comps(D), point-major.
+int lmm_dev_statespace_filter_from(const double* state0, double x0, const double* x, int k, const lmm_gp_t* gp, const double* w,
+                                   const double* r, int chunk, double* fmean, double* fvar, double* fstate, double* lml) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  std::shared_ptr<LatentSet> ls;
+  const bool bad = !state0 || !x || !gp || !w || !r || !fmean || !fvar || !fstate || !lml || k <= 0 || chunk < 0 || !std::isfinite(x0);
+  if (int rc = ss_dev_prepare(bad, x, k, gp, ls)) return rc;
+  hipStream_t st0 = g.streams[0];
+  double first = 0.0;
+  HIPCHK(hipMemcpy(&first, x, sizeof(double), hipMemcpyDeviceToHost));
+  if (!(first >= x0)) return fail(LMM_ERR_ARG, "state-space filter: x[0] = %g lies in front of the given state's input x0 = %g", first, x0);
+  double h = 0.0;
+  if (int rc = ss_filter_from(x, k, x0, ls->lat.data(), 1, w, r, chunk, &state0, &fstate, fmean, fvar, &h)) return rc;
+  HIPCHK(hipMemcpyAsync(lml, &h, sizeof(double), hipMemcpyHostToDevice, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
 int lmm_oilmm_statespace_post_mean_and_var(const lmm_ss_post_t* post, const double* xs, int ns, int add_noise, double* mean_out,
                                            double* var_out) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -5612,9 +5831,10 @@ int lmm_oilmm_statespace_post_mean_and_var(const lmm_ss_post_t* post, const doub
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)ns, st0);
   if (int rc = ss_check_finite(xsd.p, ns)) return rc;
+  if (int rc = ss_post_ensure_smoothed(P, xsd.p, ns)) return rc;
   Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
   ss_interp_latents(P->x.p, P->n, P->ls->lat.data() + P->l0, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, true, ml.p,
-                    var_out ? vl.p : nullptr);
+                    var_out ? vl.p : nullptr, true, false, P->cap);
   DevOut mo(mean_out, (size_t)ns * p), vo(var_out, (size_t)ns * p);
   mix_marginals(ml.p, ns, ms, P->H.p, p, 1, 0.0, 0.0, mo.p, st0);
   if (var_out) mix_marginals(vl.p, ns, ms, P->H.p, p, 2, kDefaultJit.default_jitter, add_noise ? P->sigma2 : 0.0, vo.p, st0);
@@ -5640,10 +5860,11 @@ int lmm_oilmm_statespace_post_mean_and_var_grad_xs(const lmm_ss_post_t* post, co
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)ns, st0);
   if (int rc = ss_check_finite(xsd.p, ns)) return rc;
+  if (int rc = ss_post_ensure_smoothed(P, xsd.p, ns)) return rc;
   DevIn dm(dmean, (size_t)ns * p, st0), dv(dvar, (size_t)ns * p, st0);
   Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
   ss_interp_latents(P->x.p, P->n, P->ls->lat.data() + P->l0, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, false, ml.p, vl.p, true,
-                    true);
+                    true, P->cap);
   DevOut go(grad_xs, (size_t)ns);
   launch_ss_contract_dx(dm.p, dv.p, P->H.p, p, ms, ml.p, vl.p, ns, go.p, st0);
   HIPCHK(hipGetLastError());
@@ -5929,6 +6150,8 @@ int lmm_statespace_post_window(const lmm_ss_post_t* post, double lo, double hi, 
   if (!post || !first || !count) return fail(LMM_ERR_ARG, "bad arguments");
   if (!std::isfinite(lo) || !std::isfinite(hi) || lo > hi)
     return fail(LMM_ERR_ARG, "state-space posterior: a window needs finite lo <= hi (lo = %g, hi = %g)", lo, hi);
+  if (post->smoothed_n < post->n && lo < post->xlast)       // a sampler over this window reads a smoothed state
+    if (int rc = ss_post_smooth(post)) return rc;
   ss_window_bounds(post->x.p, post->n, nullptr, 0, lo, hi, first, count);
   return LMM_OK;
   LMM_CATCH
@@ -5951,6 +6174,7 @@ int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, 
   DevIn xsd(xs, (size_t)ns, st0);
   SSWindow w;
   if (int rc = ss_window(P->x.p, P->n, xsd.p, ns, w)) return rc;
+  if (int rc = ss_post_ensure_smoothed(P, xsd.p, ns)) return rc;
   size_t zshard = 0;                               // doubles of one sample's z
   for (int k = 0; k < ms; ++k) zshard += (size_t)ss_state_dim(lts[k].kind) * w.W;
   DevOut od(out, (size_t)ns * p * nsamples);

@@ -439,6 +439,29 @@ struct SSPostArgs {
 static_assert(sizeof(SSPostArgs) <= 4096, "SSPostArgs is passed by value: kernel arguments are limited to 4096 bytes");
 // fold from the right, suffix scan and restart of the backward recursion for nb pairs of one model
 void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st);
+// Appending observations (DESIGN.md 4.18 "Appending observations").  The filter over k new points whose predecessor is a stored state.
+// One latent of a launch: its parameters, the noise w and data r of the k points (device), the packed state `init` (device,
+// ss_state_comps(D) values: mean, then the upper triangle of the covariance) of the point in front of them, and `out` (device), where
+// the k filtered states go point-major, k x ss_state_comps(D): row n of the latent's block of the posterior object.
+struct SSFromLat { double var, inv_ls, quality; const double* w; const double* r; const double* init; double* out; };
+struct SSFromArgs {
+  const double* x; int n, chunk, nch;         // the k = n new inputs, sorted (device); points per thread; threads per latent
+  double x0;                                  // the input of the stored state, <= x[0]
+  double* agg;                                // nb * ss_fwd_agg_elems(D, nch) doubles (not read when nch == 1)
+  double* fmean; double* fvar;                // filtered first-component mean / variance, [latent][k] (nullptr: not written)
+  double* part;                               // nb * nch log-density partials
+  SSFromLat lat[LMM_MAX_BATCH];
+};
+static_assert(sizeof(SSFromArgs) <= 4096, "SSFromArgs is passed by value: kernel arguments are limited to 4096 bytes");
+// fold, scan, restart from the stored state (nch == 1: the restart alone, which is then the sequential filter) and lml[l] = the log
+// density of latent l's new points given everything in front of them
+void launch_ss_filter_from(const SSFromArgs& a, int model, int nb, double* lml, hipStream_t st);
+// The smoother over kept states: reads the filtered states point-major from a.fkeep and writes the full smoothed states point-major
+// to a.sstate, latent z's block z * a.state_stride doubles in (the stride is the capacity's, not n's).  a.state, a.smean, a.svar,
+// lat.w and lat.r are not read: the recursion consumes filtered states and inputs only.
+void launch_ss_smooth_kept(const SSArgs& a, int model, int nb, hipStream_t st);
+// *flag (device) = 1 when some xs_t < bound, else 0; one workgroup, no atomics
+void launch_ss_any_below(const double* xs, int ns, double bound, int* flag, hipStream_t st);
 // rows idx[0 .. nsel) of an n x p column-major matrix into an nsel x p one, and back
 void launch_ss_gather_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st);
 void launch_ss_scatter_rows(const double* in, int n, int p, const int* idx, int nsel, double* out, hipStream_t st);

@@ -332,6 +332,143 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
   }
 }
 
+// ---- appending observations (DESIGN.md 4.18 "Appending observations") -------------------------------------------------------------
+// Phases 1 and 3 of the filter over k new points whose predecessor is a stored state (L.init at input a.x0) instead of the prior: the
+// element of the first new point is ss_fwd_element_from, every other element and the scan are the filter's.  Kernels of their own, so
+// that the code of ss_fold_kernel and ss_filter_kernel is what it was.
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_fold_from_kernel(SSFromArgs a) {
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const SSFromLat& L = a.lat[z];
+  const auto M = ss_lat_model<D, OSC>(L);
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
+  SSFwd<D> acc, el;
+  double xp = a.x[t0];
+  if (t0 == 0) {
+    double m0[D], P0[D][D];
+    ss_load_state<D>(L.init, 1, 0, 0, m0, P0);
+    ss_fwd_element_from<D>(M, xp - a.x0, m0, P0, L.w[0], L.r[0], acc);
+  } else ss_fwd_element<D>(M, false, xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
+  for (long long t = t0 + 1; t < t1; ++t) {
+    const double xt = a.x[t];
+    ss_fwd_element<D>(M, false, xt - xp, L.w[t], L.r[t], el);
+    ss_fwd_combine<D>(acc, el, acc);
+    xp = xt;
+  }
+  reinterpret_cast<SSFwd<D>*>(a.agg)[(size_t)z * a.nch + j] = acc;
+}
+
+// Thread 0 starts the ordinary recursion from the stored state over x[0] - x0, every other thread from its prefix; the filtered states
+// go point-major to L.out (rows n .. n + k - 1 of the posterior object's block).  With one chunk this kernel alone is the filter.
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_filter_from_kernel(SSFromArgs a) {
+  constexpr int NC = D + D * (D + 1) / 2;
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const SSFromLat& L = a.lat[z];
+  const auto M = ss_lat_model<D, OSC>(L);
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
+  double m[D], P[D][D];
+  if (j == 0) ss_load_state<D>(L.init, 1, 0, 0, m, P);
+  else {
+    const SSFwd<D>& pre = reinterpret_cast<const SSFwd<D>*>(a.agg)[(size_t)z * a.nch + j - 1];
+    for (int i = 0; i < D; ++i) {
+      m[i] = pre.b[i];
+      for (int k = 0; k < D; ++k) P[i][k] = pre.C[i][k];
+    }
+  }
+  double* fm = a.fmean ? a.fmean + (size_t)z * a.n : nullptr;
+  double* fv = a.fvar ? a.fvar + (size_t)z * a.n : nullptr;
+  double lp = 0.0;
+  double xp = t0 == 0 ? a.x0 : a.x[t0 - 1];
+  for (long long t = t0; t < t1; ++t) {
+    const double xt = a.x[t];
+    lp += ss_filter_step<D>(M, xt - xp, L.w[t], L.r[t], m, P);
+    xp = xt;
+    if (fm) fm[t] = m[0];
+    if (fv) fv[t] = P[0][0];
+    double* fst = L.out + (size_t)t * NC;
+    for (int i = 0; i < D; ++i) {
+      fst[i] = m[i];
+      for (int k = i; k < D; ++k) fst[ss_sym_at(D, i, k)] = P[i][k];
+    }
+  }
+  a.part[(size_t)z * a.nch + j] = lp;
+}
+
+// ss_bfold_kernel and ss_rts_kernel<.., FULL> over KEPT states: the filtered states are read point-major from a.fkeep (the posterior
+// object's buffer, latent z's block z * a.state_stride doubles in) and the full smoothed states go point-major to a.sstate; neither
+// the data nor the component-major a.state is read, and no marginal is written.  Kernels of their own, for the reason above.
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_bfold_kept_kernel(SSArgs a) {
+  constexpr int NC = D + D * (D + 1) / 2;
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const auto M = ss_lat_model<D, OSC>(a.lat[z]);
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
+  const double* fst = a.fkeep + (size_t)z * a.state_stride;
+  SSBwd<D> acc, el;
+  double m[D], P[D][D];
+  for (long long t = t0; t < t1; ++t) {
+    const bool last = t == a.n - 1;
+    ss_load_state<D>(fst, 1, NC, t, m, P);                    // point-major
+    ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, t == t0 ? acc : el);
+    if (t > t0) ss_bwd_combine<D>(acc, el, acc);
+  }
+  reinterpret_cast<SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j] = acc;
+}
+
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_rts_kept_kernel(SSArgs a) {
+  constexpr int NC = D + D * (D + 1) / 2;
+  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (j >= a.nch) return;
+  const auto M = ss_lat_model<D, OSC>(a.lat[z]);
+  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
+  const double* fst = a.fkeep + (size_t)z * a.state_stride;
+  double* sst = a.sstate + (size_t)z * a.state_stride;
+  double ms[D], Ps[D][D];
+  for (int i = 0; i < D; ++i) {       // the last chunk has no successor: its first element has E = 0 and ignores this state
+    ms[i] = 0.0;
+    for (int k = 0; k < D; ++k) Ps[i][k] = 0.0;
+  }
+  if (j + 1 < a.nch) {
+    const SSBwd<D>& suf = reinterpret_cast<const SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j + 1];
+    for (int i = 0; i < D; ++i) {
+      ms[i] = suf.g[i];
+      for (int k = 0; k < D; ++k) Ps[i][k] = suf.L[i][k];
+    }
+  }
+  SSBwd<D> el;
+  double m[D], P[D][D];
+  for (long long t = t1 - 1; t >= t0; --t) {
+    const bool last = t == a.n - 1;
+    ss_load_state<D>(fst, 1, NC, t, m, P);                    // point-major
+    ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, el);
+    ss_rts_step<D>(el, ms, Ps);
+    double* o = sst + (size_t)t * NC;
+    for (int i = 0; i < D; ++i) {
+      o[i] = ms[i];
+      for (int k = i; k < D; ++k) o[ss_sym_at(D, i, k)] = Ps[i][k];
+    }
+  }
+}
+
+// *flag = 1 when some xs_t < bound, else 0: one workgroup strides over the queries, an OR through LDS, thread 0 writes (no atomics)
+__global__ __launch_bounds__(SS_THREADS) void ss_any_below_kernel(const double* __restrict__ xs, int ns, double bound, int* __restrict__ flag) {
+  __shared__ int sh[SS_THREADS];
+  int any = 0;
+  for (int t = threadIdx.x; t < ns; t += SS_THREADS) any |= xs[t] < bound ? 1 : 0;
+  sh[threadIdx.x] = any;
+  __syncthreads();
+  for (int off = SS_THREADS / 2; off > 0; off >>= 1) {
+    if (threadIdx.x < off) sh[threadIdx.x] |= sh[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *flag = sh[0];
+}
+
 // One thread per (query, latent): the posterior marginal of the latent at xs[q] from the stored filtered and smoothed states
 // (ss_interp).  k = #{t : x_t <= s} by binary search over the sorted x (a query equal to a training input comes behind every copy of
 // it): at most ceil(log2(n + 1)) probes.  Reads the states of points k - 1 >= 0 and k < n only; a query's result depends on no other
@@ -742,6 +879,30 @@ void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st) {
                                                        : a.gdt ? ss_rts_kernel<T::D, T::OSC, false, true> : ss_rts_kernel<T::D, T::OSC>,
                                               a, 1, nb, a.bagg, st);
   });
+}
+
+void launch_ss_filter_from(const SSFromArgs& a, int model, int nb, double* lml, hipStream_t st) {
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    if (a.nch == 1) {     // one chunk: thread 0 of the restart is the whole sequential filter, no aggregate is read, and a latent's
+      SSFromArgs b = a;   // one partial is its log density: one launch in all
+      if (lml) b.part = lml;
+      hipLaunchKernelGGL((ss_filter_from_kernel<T::D, T::OSC>), dim3(1, 1, nb), dim3(SS_THREADS), 0, st, b);
+    } else
+      ss_phases<T::D, SSFwd<T::D>, FwdOp, false>(ss_fold_from_kernel<T::D, T::OSC>, ss_filter_from_kernel<T::D, T::OSC>, a, 1, nb, a.agg, st);
+  });
+  if (lml && a.nch > 1) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
+}
+
+void launch_ss_smooth_kept(const SSArgs& a, int model, int nb, hipStream_t st) {
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    ss_phases<T::D, SSBwd<T::D>, BwdOp, true>(ss_bfold_kept_kernel<T::D, T::OSC>, ss_rts_kept_kernel<T::D, T::OSC>, a, 1, nb, a.bagg, st);
+  });
+}
+
+void launch_ss_any_below(const double* xs, int ns, double bound, int* flag, hipStream_t st) {
+  hipLaunchKernelGGL(ss_any_below_kernel, dim3(1), dim3(SS_THREADS), 0, st, xs, ns, bound, flag);
 }
 
 void launch_ss_grad(const SSArgs& a, int model, int nb, double* gtheta, hipStream_t st) {

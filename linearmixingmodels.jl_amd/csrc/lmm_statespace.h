@@ -373,6 +373,24 @@ SS_HD Sc ss_filter_step(const Mod& M, double dt, double w, double r, Sc m[D], Sc
   return -0.5 * (log(6.283185307179586 * S) + e * e * Sinv);
 }
 
+// The element of the first of a run of points whose predecessor is not the prior but a given state (m0, P0) lying dt in front of it
+// (DESIGN.md 4.18 "Appending observations"): ss_fwd_element's `first` with the prediction m- = A m0, P- = A P0 A' + Q in the prior's
+// place, i.e. A = 0, b = m- + K (r - m-[0]), C = P- - K P-[0, :], eta = 0, J = 0; w = +Inf: b = m-, C = P-.  (b, C) is what
+// ss_filter_step makes of (m0, P0), in its arithmetic; dt = 0 keeps (m0, P0) exactly through the prediction.
+template <int D, typename Mod>
+SS_HD void ss_fwd_element_from(const Mod& M, double dt, const double m0[D], const double P0[D][D], double w, double r, SSFwd<D>& e) {
+  double m[D], P[D][D];
+  for (int i = 0; i < D; ++i) {
+    m[i] = m0[i];
+    for (int j = 0; j < D; ++j) P[i][j] = P0[i][j];
+  }
+  ss_filter_step<D>(M, dt, w, r, m, P);
+  for (int i = 0; i < D; ++i) {
+    e.b[i] = m[i]; e.eta[i] = 0.0;
+    for (int j = 0; j < D; ++j) { e.A[i][j] = 0.0; e.C[i][j] = P[i][j]; e.J[i][j] = 0.0; }
+  }
+}
+
 // ---- backward (smoothing) elements -----------------------------------------------------------------------------------------------
 template <int D>
 struct SSBwd { double E[D][D], g[D], L[D][D]; };

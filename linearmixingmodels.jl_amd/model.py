@@ -1037,9 +1037,11 @@ class StateSpacePosterior:
     at new inputs in O(ns log n) per latent, without touching the data again; rand draws joint samples there from the same states.
     Built by statespace_posterior; freed by close(), on leaving a `with` block or with the object."""
 
-    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float, dims: Optional[Sequence[int]] = None):
+    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float, dims: Optional[Sequence[int]] = None,
+                 x_last: Optional[float] = None):
         self._ptr, self.n, self.p, self.logpdf = ptr, n, p, logpdf
         self._dims = None if dims is None else [int(D) for D in dims]       # the latents' state dimensions: what rand draws per point
+        self._x_last = None if x_last is None else float(x_last)            # the last input, kept on the host for append's check
 
     def close(self) -> None:
         if self._ptr:
@@ -1058,6 +1060,81 @@ class StateSpacePosterior:
             self.close()
         except Exception:
             pass
+
+    def append(self, x_new, y_new) -> float:
+        """Conditions the posterior on k LATER observations in O(k), without starting over (include/lmm_hip.h "state space: appending
+        observations").  x_new: (k,) inputs in any order (sorted here, stably), NumPy or a torch device tensor, none in front of the
+        last input so far (equal to it is served); y_new: (k * p,) by outputs in the caller's order, NaN = missing.  Returns the
+        increment log p(y_new | all earlier data) and updates n and logpdf.  The smoothed states fall behind (`smoothed`): forecasts
+        stay O(1) per query, and the first query in front of the last input (or smooth()) pays one O(n) pass that does not need the
+        data.  Every refusal below comes before any library call."""
+        if not self._ptr:
+            raise ValueError("StateSpacePosterior: the posterior has been closed")
+        if not hasattr(x_new, "shape"):
+            x_new = np.asarray(x_new, dtype=np.float64)
+        if not hasattr(y_new, "shape"):
+            y_new = np.asarray(y_new, dtype=np.float64)
+        if len(x_new.shape) != 1:
+            raise ValueError("StateSpacePosterior.append: x_new is a (k,) array of one-dimensional inputs")
+        k = int(x_new.shape[0])
+        if len(y_new.shape) != 1 or int(y_new.shape[0]) != k * self.p:
+            raise ValueError(f"StateSpacePosterior.append: y_new holds k * p = {k * self.p} values by outputs")
+        if self._x_last is None:
+            raise ValueError("StateSpacePosterior.append: the handle was built without its last input")
+        if k == 0:
+            return 0.0
+        if L._is_torch(x_new):
+            import torch
+            x_new = x_new.to(torch.float64)
+            finite, lo, hi = bool(torch.isfinite(x_new).all()), float(x_new.min()), float(x_new.max())
+        else:
+            x_new = np.ascontiguousarray(x_new, dtype=np.float64)
+            finite, lo, hi = bool(np.isfinite(x_new).all()), float(x_new.min()), float(x_new.max())
+        if not finite:
+            raise ValueError("StateSpacePosterior.append: x_new must be finite (no NaN or Inf)")
+        if lo < self._x_last:
+            raise ValueError(f"StateSpacePosterior.append: appended points lie at or behind the last input ({lo} is in front of "
+                             f"{self._x_last})")
+        xa, ya, _, _ = _statespace_sorted(x_new, y_new, self.p)
+        out = C.c_double()
+        L.check(L.load().lmm_oilmm_statespace_post_append(self._ptr, L.Arr(xa).ptr, k, L.Arr(ya).ptr, C.byref(out)))
+        self.n += k
+        self.logpdf += out.value
+        self._x_last = hi
+        return out.value
+
+    def smooth(self) -> None:
+        """Brings the smoothed states up to date after appends (one O(n) pass over the kept filtered states); else nothing."""
+        if not self._ptr:
+            raise ValueError("StateSpacePosterior: the posterior has been closed")
+        L.check(L.load().lmm_statespace_post_smooth(self._ptr))
+
+    def reserve(self, n_total: int) -> None:
+        """Room for n_total points in all, so that appends up to there do not grow the buffers; smaller than the capacity: nothing."""
+        if not self._ptr:
+            raise ValueError("StateSpacePosterior: the posterior has been closed")
+        if int(n_total) != n_total or n_total < 0 or n_total > 2 ** 31 - 1:
+            raise ValueError("StateSpacePosterior.reserve: n_total is a number of points in 0 .. 2^31 - 1")
+        L.check(L.load().lmm_statespace_post_reserve(self._ptr, int(n_total)))
+
+    def _size(self):
+        n, sn, cap = C.c_int(), C.c_int(), C.c_int()
+        L.check(L.load().lmm_statespace_post_size(self._ptr, C.byref(n), C.byref(sn), C.byref(cap)))
+        return n.value, sn.value, cap.value
+
+    @property
+    def smoothed(self) -> bool:
+        """Whether the smoothed states are current (False between an append and the next smooth, explicit or on demand)."""
+        if not self._ptr:
+            raise ValueError("StateSpacePosterior: the posterior has been closed")
+        n, sn, _ = self._size()
+        return sn == n
+
+    @property
+    def capacity(self) -> int:
+        if not self._ptr:
+            raise ValueError("StateSpacePosterior: the posterior has been closed")
+        return self._size()[2]
 
     def _queries(self, xs):
         """xs as a (ns,) float64 array, checked: every refusal comes before any library call."""
@@ -1218,7 +1295,7 @@ def statespace_posterior(fx: "FiniteGP", y) -> StateSpacePosterior:
     ptr, out = C.c_void_p(), C.c_double()
     L.check(L.load().lmm_oilmm_statespace_posterior_create(L.Arr(xa).ptr, x.n, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps,
                                                            0, m, C.byref(ptr), C.byref(out)))
-    return StateSpacePosterior(ptr, x.n, p, out.value, [_STATESPACE_DIM[g.kernel.kind] for g in f.f.fs])
+    return StateSpacePosterior(ptr, x.n, p, out.value, [_STATESPACE_DIM[g.kernel.kind] for g in f.f.fs], float(xa[-1]))
 
 
 class _NoStateSpaceMixingGradient(dict):
