@@ -965,6 +965,17 @@ int lmm_lmm_rand_multi(const lmm_post_t* post, const lmm_gp_t* gps,
  * rows >= ncols ride along (become A21 * L11^-T).  nrows, ncols multiples of 64.  Winv: ncols/64 dense
  * 64x64 inverse diagonal blocks (scratch / output).  info: device int (0 = ok, k = pivot k failed). */
 int lmm_dev_potrf(double* A, int nrows, int ncols, int ld, double* Winv, int n_real, int* info_dev);
+/* The back substitution behind every dense gradient and posterior, on its own: z_j <- L_j^-T z_j (64 nblk values each) for the nb <= 32
+ * matrices of a batch, from the factors and inverse diagonal blocks lmm_dev_potrf leaves.  Matrix j is at L + j l_stride, its inverse
+ * blocks at W + j w_stride, its vector at z + j z_stride (strides in Float64 elements; l_stride = w_stride = 0 lets all the solves
+ * share one factor).  Words of z from 64 nblk on are not touched. */
+int lmm_dev_backsolve(const double* L, size_t l_stride, int ld, const double* W, size_t w_stride, int nblk,
+                      double* z, size_t z_stride, int nb);
+/* The inverse behind every dense gradient, on its own, for a batch of nb <= 32 factored NC x NC matrices (ld; matrix j at
+ * A + j a_stride, inverse blocks at W + j w_stride): R_j (NC columns of ld, at R + j r_stride) becomes L_j^-T -- upper triangular, its
+ * strict lower triangle exactly 0 -- and the lower triangle of A_j, diagonal included, becomes (L_j L_j')^-1. */
+int lmm_dev_factor_inverse(double* A, size_t a_stride, int ld, int NC, const double* W, size_t w_stride,
+                           double* R, size_t r_stride, int nb);
 /* Host-only (no GPU needed): the status the library derives from `count` pivot-info words of a batch -- LMM_OK; LMM_ERR_NOT_PD for
  * the first non-zero word (lmm_last_error_detail: latent_begin + index, pivot; reference: `cholesky` throwing PosDefException inside
  * src/oilmm.jl:90 / AbstractGPs logpdf); LMM_ERR_HIP when ANY word carries -7777, the marker potrf_region_kernel leaves when one of

@@ -48,6 +48,7 @@ SYMBOLS = [
     "lmm_dev_set_f64_emul_rule", "lmm_dev_set_emul_group", "lmm_dev_set_emul_amax_reuse", "lmm_dev_emul_plan", "lmm_dev_potrf_plan",
     "lmm_dev_set_emul_zero_skip", "lmm_dev_emul_stage_list", "lmm_dev_set_emul_scratch_poison", "lmm_dev_emul_block_live",
     "lmm_dev_set_emul_screen", "lmm_dev_emul_last_live_tiles", "lmm_dev_emul_negligible",
+    "lmm_dev_backsolve", "lmm_dev_factor_inverse",
 ]
 
 
@@ -93,6 +94,13 @@ STATESPACE_ARGTYPES = {
     "lmm_statespace_post_reserve": [_P, _I],
     "lmm_statespace_post_size": [_P, _P, _P, _P],
     "lmm_dev_statespace_filter_from": [_P, _D, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+}
+
+# Argument types of the solve-chain building blocks (include/lmm_hip.h, "building blocks"), set on the library by load().
+_Z = C.c_size_t
+SOLVE_CHAIN_ARGTYPES = {
+    "lmm_dev_backsolve": [_P, _Z, _I, _P, _Z, _I, _P, _Z, _I],
+    "lmm_dev_factor_inverse": [_P, _Z, _I, _I, _P, _Z, _P, _Z, _I],
 }
 
 # Argument types of the SHO tag entry points (include/lmm_hip.h, LMM_KERNEL_SHO), set on the library by load().
@@ -153,7 +161,7 @@ def load() -> C.CDLL:
             pass
         _lib = C.CDLL(LIB_PATH)
         _lib.lmm_last_error_string.restype = C.c_char_p
-        for name, types in list(SPARSE_ARGTYPES.items()) + list(STATESPACE_ARGTYPES.items()) + list(SHO_ARGTYPES.items()):
+        for name, types in list(SPARSE_ARGTYPES.items()) + list(STATESPACE_ARGTYPES.items()) + list(SHO_ARGTYPES.items()) + list(SOLVE_CHAIN_ARGTYPES.items()):
             fn = getattr(_lib, name)
             fn.argtypes, fn.restype = types, C.c_int
     return _lib

@@ -6249,6 +6249,52 @@ int lmm_dev_potrf(double* A, int nrows, int ncols, int ld, double* Winv, int n_r
   LMM_CATCH
 }
 
+// The back substitution of a gradient or posterior pass on its own: exactly launch_backsolve, on the main stream.
+int lmm_dev_backsolve(const double* L, size_t l_stride, int ld, const double* W, size_t w_stride, int nblk, double* z, size_t z_stride,
+                      int nb) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!L || !W || !z || nblk < 1 || nb < 1 || nb > LMM_MAX_BATCH || ld < nblk * 64 || (ld & 1) || (l_stride & 1) ||
+      (nb > 1 && z_stride < (size_t)nblk * 64))
+    return fail(LMM_ERR_ARG, "lmm_dev_backsolve: bad arguments");
+  BatchPtr Lb{}, Wb{}, zb{};
+  for (int j = 0; j < nb; ++j) {
+    Lb.p[j] = const_cast<double*>(L) + (size_t)j * l_stride; Wb.p[j] = const_cast<double*>(W) + (size_t)j * w_stride;
+    zb.p[j] = z + (size_t)j * z_stride;
+  }
+  launch_backsolve(Lb, ld, Wb, nblk, zb, nb, g.streams[0]);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(g.streams[0]));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// The inverse of a gradient pass on its own, as KernelGradPass::launch queues it: R = identity, R <- L^-T (upper triangular), then
+// lower(A) = R R' = Kt^-1 over the factor.
+int lmm_dev_factor_inverse(double* A, size_t a_stride, int ld, int NC, const double* W, size_t w_stride, double* R, size_t r_stride,
+                           int nb) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  const size_t mat = (size_t)ld * (NC > 0 ? NC : 0);
+  if (!A || !W || !R || NC < 64 || NC % 64 || nb < 1 || nb > LMM_MAX_BATCH || ld < NC || (ld & 1) || (a_stride & 1) || (r_stride & 1) ||
+      (nb > 1 && (a_stride < mat || r_stride < mat || w_stride < (size_t)NC * 64)))
+    return fail(LMM_ERR_ARG, "lmm_dev_factor_inverse: bad arguments");
+  hipStream_t st = g.streams[0];
+  BatchPtr Ab{}, Wb{}, Rb{};
+  for (int j = 0; j < nb; ++j) {
+    Ab.p[j] = A + (size_t)j * a_stride; Wb.p[j] = const_cast<double*>(W) + (size_t)j * w_stride; Rb.p[j] = R + (size_t)j * r_stride;
+    launch_set_identity(Rb.p[j], ld, NC, st);
+  }
+  trsm_rec(Rb, ld, NC, Ab, ld, Wb, nb, 0, NC, st, true);
+  launch_syrk_upper_set(Ab, ld, Rb, ld, NC, nb, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(g.streams[0]));
+  return LMM_OK;
+  LMM_CATCH
+}
+
 // The region kernel's row-task plan for one block column (host arithmetic only; no device, no lmm_init needed).
 int lmm_dev_region_plan(int P, int nb, int rows_below, int rows_real, int cus, int assistants, int out[3]) {
   std::lock_guard<std::mutex> lk(g_mu);

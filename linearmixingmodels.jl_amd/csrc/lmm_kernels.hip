@@ -3295,21 +3295,49 @@ __global__ void strip_finish_kernel(const double* __restrict__ partial, int nrp,
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Back substitution  L' alpha = z  (alpha = C \ delta second half), one launch per 64-block from the last block to the
-// first, for every matrix of the batch (blockIdx.y).  Step b: alpha_b = W_bb' z_b (every workgroup recomputes it from an
-// LDS copy of the 64x64 inverse block), then z_i -= sum_{j in b} L[j, i] alpha_j for the 256 columns i < 64 b of this
-// workgroup: 16 lanes share a column (4 consecutive rows each, so a wave load covers 4 whole 512-byte column segments).
+// Back substitution  L' alpha = z  (alpha = C \ delta second half) for every matrix of the batch (blockIdx.y): one step launch per
+// 64-block from the last block down to block 1, then one finishing launch.
+// Step b: alpha_b = W_bb' z_b (every workgroup recomputes it from an LDS copy of the 64x64 inverse block), then
+// z_i -= sum_{j in b} L[j, i] alpha_j for the 256 columns i < 64 b of this workgroup: 16 lanes share a column (4 consecutive rows
+// each, so a wave load covers 4 whole 512-byte column segments).  A step launch only READS block b of z -- every workgroup of the
+// launch loads it, whenever it happens to start -- and each workgroup writes its own 256 columns below it.  z_b is final once step
+// b + 1 has run, so the finishing launch turns every z_b into alpha_b = W_bb' z_b, one workgroup per block on its own 64 words, by
+// the same arithmetic.  No word is written by one workgroup of a launch and read by another.
 // ---------------------------------------------------------------------------------------------------
+struct BacksolveLds {
+  double Ws[64 * 65];
+  double zb[64];
+  double ps[4][64];
+  double ab[64];
+};
+
+// S.ab = W_bb' z_b from block b's inverse block and z_b (all 256 threads; S.ab is complete on return)
+template <typename TS>
+__device__ __forceinline__ void backsolve_block_alpha(BacksolveLds& S, const void* __restrict__ Wb, int b, const double* __restrict__ z) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const size_t woff = (size_t)b * 4096;
+  for (int e = t; e < 4096; e += 256) S.Ws[(e >> 6) * 65 + (e & 63)] = MatIO<TS>::ld1(Wb, woff + e);     // Wb[c*64 + j] = W[j, c]
+  if (t < 64) S.zb[t] = z[b * 64 + t];
+  __syncthreads();
+  {
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int j = w * 16 + u;
+      if (j >= lane) s = __builtin_fma(S.Ws[lane * 65 + j], S.zb[j], s);          // (W')[t, j] = W[j, t], j >= t
+    }
+    S.ps[w][lane] = s;
+  }
+  __syncthreads();
+  if (t < 64) S.ab[t] = (S.ps[0][t] + S.ps[1][t]) + (S.ps[2][t] + S.ps[3][t]);
+  __syncthreads();
+}
+
 template <typename TS>
 __global__ __launch_bounds__(256) void backsolve_step_kernel(BatchPtr Lb, int ld, BatchPtr Wb_, int b, BatchPtr zb_) {
-  __shared__ double Ws[64 * 65];
-  __shared__ double zb[64];
-  __shared__ double ps[4][64];
-  __shared__ double ab[64];
+  __shared__ BacksolveLds S;
   const void* __restrict__ L = Lb.p[blockIdx.y];
-  const void* __restrict__ Wb = Wb_.p[blockIdx.y];
-  const size_t woff = (size_t)b * 4096;
-  double* __restrict__ z = zb_.p[blockIdx.y];
+  double* z = zb_.p[blockIdx.y];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   // issue this workgroup's 32 panel loads first: they do not depend on alpha_b
   const int c0 = blockIdx.x * 256 + w * 64;
@@ -3324,23 +3352,8 @@ __global__ __launch_bounds__(256) void backsolve_step_kernel(BatchPtr Lb, int ld
       pa[gI] = make_double2(q4[0], q4[1]); pb[gI] = make_double2(q4[2], q4[3]);
     } else { pa[gI] = make_double2(0.0, 0.0); pb[gI] = pa[gI]; }
   }
-  for (int e = t; e < 4096; e += 256) Ws[(e >> 6) * 65 + (e & 63)] = MatIO<TS>::ld1(Wb, woff + e);     // Wb[c*64 + j] = W[j, c]
-  if (t < 64) zb[t] = z[b * 64 + t];
-  __syncthreads();
-  {
-    double s = 0.0;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int j = w * 16 + u;
-      if (j >= lane) s = __builtin_fma(Ws[lane * 65 + j], zb[j], s);          // (W')[t, j] = W[j, t], j >= t
-    }
-    ps[w][lane] = s;
-  }
-  __syncthreads();
-  if (t < 64) ab[t] = (ps[0][t] + ps[1][t]) + (ps[2][t] + ps[3][t]);
-  __syncthreads();
-  if (blockIdx.x == 0 && t < 64) z[b * 64 + t] = ab[t];
-  const double a0 = ab[jq * 4], a1 = ab[jq * 4 + 1], a2 = ab[jq * 4 + 2], a3 = ab[jq * 4 + 3];
+  backsolve_block_alpha<TS>(S, Wb_.p[blockIdx.y], b, z);
+  const double a0 = S.ab[jq * 4], a1 = S.ab[jq * 4 + 1], a2 = S.ab[jq * 4 + 2], a3 = S.ab[jq * 4 + 3];
 #pragma unroll
   for (int gI = 0; gI < 16; ++gI) {
     double s = __builtin_fma(pa[gI].x, a0, __builtin_fma(pa[gI].y, a1, __builtin_fma(pb[gI].x, a2, pb[gI].y * a3)));
@@ -3348,6 +3361,16 @@ __global__ __launch_bounds__(256) void backsolve_step_kernel(BatchPtr Lb, int ld
     const int col = c0 + gI * 4 + cq;
     if (jq == 0 && col < b * 64) z[col] -= s;
   }
+}
+
+// z_b <- alpha_b = W_bb' z_b for block b = blockIdx.x, after the last step launch
+template <typename TS>
+__global__ __launch_bounds__(256) void backsolve_finish_kernel(BatchPtr Wb_, BatchPtr zb_) {
+  __shared__ BacksolveLds S;
+  double* z = zb_.p[blockIdx.y];
+  const int b = blockIdx.x, t = threadIdx.x;
+  backsolve_block_alpha<TS>(S, Wb_.p[blockIdx.y], b, z);
+  if (t < 64) z[b * 64 + t] = S.ab[t];
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -5686,10 +5709,10 @@ void launch_rider_stats(const double* R, int ld, int nr, int nk, const double* z
 }
 
 void launch_backsolve(const BatchPtr& L, int ld, const BatchPtr& W, int nblk, const BatchPtr& z, int nb, hipStream_t st) {
-  for (int b = nblk - 1; b >= 0; --b) {
-    int grid = (b * 64 + 255) / 256; if (grid < 1) grid = 1;
-    LMM_TS_LAUNCH((backsolve_step_kernel<TS>), dim3(grid, nb), dim3(256), 0, st, L, ld, W, b, z);
-  }
+  if (nblk <= 0 || nb <= 0) return;
+  for (int b = nblk - 1; b >= 1; --b)
+    LMM_TS_LAUNCH((backsolve_step_kernel<TS>), dim3((b * 64 + 255) / 256, nb), dim3(256), 0, st, L, ld, W, b, z);
+  LMM_TS_LAUNCH((backsolve_finish_kernel<TS>), dim3(nblk, nb), dim3(256), 0, st, W, z);
 }
 
 void launch_tall_skinny(const double* In, int ldi, int n, int K, const double* Mx, int ldm, int C, double* Out, int ldo,

@@ -145,3 +145,49 @@ def test_c4_shape_rand_marginals(lmm):
     z0 = np.random.default_rng(0).standard_normal(m * ns)[:ns]                     # latent 0's block of the reference's draw order
     ref0 = O.gp_rand(po0, xs, 1e-8, z0)
     np.testing.assert_allclose(s0.reshape(p, ns), Hs[:, :1] * ref0[None, :], rtol=1e-6, atol=1e-8)
+
+
+def test_c2_gradient_matches_state_space(lmm):
+    """configs[2]'s whole shape on one GPU through the gradient: 32 Matern52 latents, p = 64, n = 16384 (the problem of
+    tools/statespace_bench.py: two batches of 16 latents on two streams, 256 back-substitution steps of up to 64 x 16 workgroups each),
+    one logpdf_and_gradient call against statespace_logpdf_and_gradient, which shares no kernel with it, every key; and latent 0's
+    d / d mean = sum(alpha) against host LAPACK.
+
+    Bound: 1e-8 of max|reference| per key (the three per-latent keys as arrays over the latents).  The two paths agree to 1e-13 or
+    better on 3 latents of this size (profiles/statespace_grad_bench.json); the build whose back substitution let one workgroup
+    overwrite z_b with alpha_b while others of the same launch were still to read it differed by 7e-4 in its best key (sigma2) and by
+    0.2 to 1.0 in the others (profiles/solve_chain/parent.txt).  1e-8 lies between, five orders from the failing side.  Host check:
+    1e-8 of sum|alpha|."""
+    import importlib.util
+    import os
+    import scipy.linalg as sla
+    spec = importlib.util.spec_from_file_location("statespace_bench", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                                                  "tools", "statespace_bench.py"))
+    SB = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(SB)
+    BOUND, n = 1e-8, 16384
+    f, x, y = SB.make_problem(lmm, n)
+    fx = f(lmm.MOInputIsotopicByOutputs(x, SB.P_OUT), SB.S2)
+    got = lmm.logpdf_and_gradient(fx, y)
+    ref = lmm.statespace_logpdf_and_gradient(fx, y)
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a, dtype=np.float64)
+    pairs = {k: (host(got[k]), host(ref[k])) for k in ("value", "y", "sigma2", "S", "U")}
+    assert len(got["gps"]) == len(ref["gps"]) == SB.M_LAT
+    for key in ("variance", "lengthscale", "mean"):
+        pairs["gps." + key] = (np.array([g[key] for g in got["gps"]]), np.array([g[key] for g in ref["gps"]]))
+    errs = {}
+    for k, (a, b) in pairs.items():
+        assert a.shape == b.shape and np.isfinite(a).all(), k
+        errs[k] = float(np.abs(a - b).max() / np.abs(b).max())
+        print(f"c2 gradient, Cholesky path against state space, {k}: {errs[k]:.3e} of max|reference|")
+    # latent 0 on the host: alpha = (K + (sigma2 / S_0) I)^-1 T_0 Y  (mean 0)
+    T, ST = O.project_orthogonal(f.H.U, f.H.S, SB.S2)
+    xh = host(x)
+    delta = T[0] @ O.reshape_y(host(y), n)
+    Kt = O.kernelmatrix({"kind": "matern52", "variance": 0.5, "lengthscale": 0.8}, xh)
+    Kt[np.diag_indices(n)] += ST[0]
+    alpha = sla.cho_solve(sla.cho_factor(Kt, lower=True, overwrite_a=True, check_finite=False), delta)
+    e0 = abs(got["gps"][0]["mean"] - alpha.sum()) / np.abs(alpha).sum()
+    print(f"c2 gradient, latent 0's sum(alpha): {got['gps'][0]['mean']:.10g} (host {alpha.sum():.10g}), {e0:.3e} of sum|alpha|")
+    assert all(e <= BOUND for e in errs.values()), errs
+    assert e0 <= BOUND, (got["gps"][0]["mean"], alpha.sum())

@@ -138,7 +138,8 @@ def child(out_path):
         for f32 in (0, 1):
             lmm.set_compute_dtype("f32" if f32 else "f64")
             t = tag + (" f32" if f32 else "")
-            # The Float32 back substitution (backsolve_step_kernel<float>) is not a function of its inputs: every workgroup of step b reads
+            # Builds before backsolve_finish_kernel (a parent this tool may be given): the Float32 back substitution
+            # (backsolve_step_kernel<float>) is not a function of its inputs there: every workgroup of step b reads
             # z[64 b .. 64 b + 63] while workgroup 0 of the same launch overwrites them with alpha_b, so the weights alpha = L^-T z of the
             # dense-H gradient, and all it computes from them, come out in several versions (profiles/dense_h_refactor/
             # f32_gradient_reproducibility.txt).  Each Float32 dense-H gradient is therefore called F32_GRAD_CALLS times in every child, and a
