@@ -937,6 +937,37 @@ int lmm_statespace_post_size(const lmm_ss_post_t* post, int* n, int* smoothed_n,
 int lmm_dev_statespace_filter_from(const double* state0, double x0, const double* x, int k, const lmm_gp_t* gp, const double* w,
                                    const double* r, int chunk, double* fmean, double* fvar, double* fstate, double* lml);
 
+/* ---- state space: predictive log density -----------------------------------------------------------------
+ * logpdf(post(xs, sigma2), ys): the joint log density of held-out observations given the training data, from the handle alone
+ * (DESIGN.md 4.18 "Predictive log density from the posterior object").  Given the data the states over the window of the sorted queries
+ * ("sampling from the posterior object" above: the same window, the same backward chain s_j | s_{j+1}, y = N(g_j + E_j s_{j+1}, L_j))
+ * are Markov, so observing ys at the queries is a Kalman filter over the window with affine transitions, run from the largest query
+ * down to the smallest; its marginal likelihood is log p(ys | y) per latent, exactly.  Cost O(ns + count) per latent; a held-out
+ * block behind the data touches no training point.  Training points inside the window are unobserved steps.  No atomics: the value
+ * depends only on the handle and the queries, bitwise.  The handle is const and answers exactly as before after any call, refused or
+ * not.  Served by the C ABI and the Python mirror (StateSpacePosterior.predictive_logpdf); the Julia shim has no state-space posterior
+ * yet, hence no method there.
+ *   lmm_oilmm_statespace_post_logpdf : xs: ns values, finite and NON-DECREASING, host or device (otherwise LMM_ERR_ARG with the first
+ *                    offending index in lmm_last_error_detail's `info`); ties among the queries and with training inputs are served.
+ *                    ys: ns x p by outputs (ys[o ns + t]), host or device, NaN = missing, with create's rules: a row without any
+ *                    observed output is an unobserved query and contributes 0; a row observing 0 < p_t < m outputs ->
+ *                    LMM_ERR_UNSUPPORTED naming the query by its index t (`info`); a singular G_t -> LMM_ERR_NOT_PD.  sigma2: the noise
+ *                    at the queries, finite and > 0; exactly 0 means the handle's own; anything else -> LMM_ERR_ARG.  *out = the sum
+ *                    over the shard's latents of the window filter's value plus the regulariser terms of the queries, i.e. what
+ *                    lmm_oilmm_logpdf_statespace gives on all n + ns points minus what it gives on the n training points, and for
+ *                    queries at or behind the last input what lmm_oilmm_statespace_post_append would return.  LAZINESS as for the
+ *                    other query entry points: the O(n) pass runs only when a query lies in front of the last input.  ns = 0 ->
+ *                    *out = 0.  post or out NULL, ns < 0, or xs or ys NULL with ns > 0 -> LMM_ERR_ARG; the fp32 compute mode ->
+ *                    LMM_ERR_UNSUPPORTED ("Float64 only").
+ *   lmm_dev_statespace_post_logpdf : building block exported for tests beside lmm_dev_statespace_post_sample (DEVICE pointers; one
+ *                    latent, gp on the host, its mean is not read): *out (device) = the window filter's value from given states in the
+ *                    layout of lmm_dev_statespace_states, with noise w and data r of the ns sorted queries (w = +Inf: unobserved).
+ *                    chunk: window points per thread, 0 = the library's default; one chunk (W <= chunk) is a single launch that runs
+ *                    the sequential filter. */
+int lmm_oilmm_statespace_post_logpdf(const lmm_ss_post_t* post, const double* xs, int ns, const double* ys, double sigma2, double* out);
+int lmm_dev_statespace_post_logpdf(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate,
+                                   const double* xs, int ns, const double* w, const double* r, int chunk, double* out);
+
 /* ---- rand ----------------------------------------------------------------------------------- */
 /* rand(rng, fx::FiniteGP{<:OILMM}): reference src/oilmm.jl:40-54.  The caller supplies the standard
  * normals in the reference's draw order: z_lat = m blocks of ns (latent order), eps = ns*p (by-outputs),

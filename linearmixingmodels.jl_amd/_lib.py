@@ -43,6 +43,7 @@ SYMBOLS = [
     "lmm_statespace_post_window", "lmm_oilmm_statespace_post_rand", "lmm_dev_statespace_post_sample",
     "lmm_oilmm_statespace_post_append", "lmm_statespace_post_smooth", "lmm_statespace_post_reserve", "lmm_statespace_post_size",
     "lmm_dev_statespace_filter_from",
+    "lmm_oilmm_statespace_post_logpdf", "lmm_dev_statespace_post_logpdf",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
     "lmm_dev_set_f64_emul", "lmm_dev_syrk_emul", "lmm_dev_emul_host", "lmm_dev_emul_residues", "lmm_dev_set_emul_gemm_workgroups", "lmm_dev_emul_acc_residues",
     "lmm_dev_set_f64_emul_rule", "lmm_dev_set_emul_group", "lmm_dev_set_emul_amax_reuse", "lmm_dev_emul_plan", "lmm_dev_potrf_plan",
@@ -94,6 +95,8 @@ STATESPACE_ARGTYPES = {
     "lmm_statespace_post_reserve": [_P, _I],
     "lmm_statespace_post_size": [_P, _P, _P, _P],
     "lmm_dev_statespace_filter_from": [_P, _D, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "lmm_oilmm_statespace_post_logpdf": [_P, _P, _I, _P, _D, _P],
+    "lmm_dev_statespace_post_logpdf": [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P],
 }
 
 # Argument types of the solve-chain building blocks (include/lmm_hip.h, "building blocks"), set on the library by load().

@@ -6210,6 +6210,93 @@ int lmm_dev_statespace_post_sample(const double* x, int n, const lmm_gp_t* gp, c
   LMM_CATCH
 }
 
+// ---- predictive log density from the posterior object (DESIGN.md 4.18 "Predictive log density from the posterior object") --------
+// log p(the queries' data | the training data) of the ms latents lts[0 .. ms) from their stored states (latent k's block off[k]
+// doubles into fstate / sstate): the filter over the window's backward chain.  w, r: [latent][ns] on the device, over the sorted
+// queries (+Inf: unobserved); lml: ms host values.  Returns with streams[0] drained.
+static int ss_post_logpdf(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
+                          const double* xsd, int ns, const SSWindow& win, const double* w, const double* r, int chunk, double* lml) {
+  hipStream_t st0 = g.streams[0];
+  const SSChunks plan = ss_plan_chunks(win.W, chunk);
+  const int nch = plan.nch;
+  const auto bytes = [&](int, int D, int nch) { return (ss_fwd_agg_elems(D, nch) + (size_t)nch) * sizeof(double); };
+  ss_for_launches(ms, nch, [&](long long j) -> const Latent& { return lts[j]; }, bytes, [&](long long e0, int nb, int model, int D) {
+    const int k0 = (int)e0;
+    Buf<double> agg, part, lmld(nb);
+    if (nch > 1) { agg = Buf<double>((size_t)nb * ss_fwd_agg_elems(D, nch)); part = Buf<double>((size_t)nb * nch); }
+    SSLpdfArgs a{};
+    a.x = xd; a.n = n; a.xs = xsd; a.ns = ns; a.src = win.src.p; a.first = win.first; a.W = win.W;
+    a.chunk = plan.chunk; a.nch = nch; a.agg = agg.p; a.part = part.p;
+    for (int j = 0; j < nb; ++j) {
+      ss_fill_lat(a.lat[j], lts[k0 + j], false);
+      a.lat[j].fstate = fstate + off[k0 + j]; a.lat[j].sstate = sstate + off[k0 + j];
+      a.lat[j].w = w + (size_t)(k0 + j) * ns; a.lat[j].r = r + (size_t)(k0 + j) * ns;
+    }
+    launch_ss_post_logpdf(a, model, nb, lmld.p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(lml + k0, lmld.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));          // the buffers above go back to the pool
+  });
+  return LMM_OK;
+}
+
+int lmm_oilmm_statespace_post_logpdf(const lmm_ss_post_t* post, const double* xs, int ns, const double* ys, double sigma2, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !out || ns < 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return ss_refuse_f32();
+  if (!(sigma2 >= 0.0) || !std::isfinite(sigma2))
+    return fail(LMM_ERR_ARG, "state-space posterior: sigma2 must be finite and > 0, or exactly 0 for the handle's own (sigma2 = %g)", sigma2);
+  if (ns == 0) {
+    *out = 0.0;
+    return LMM_OK;
+  }
+  if (!xs || !ys) return fail(LMM_ERR_ARG, "bad arguments");
+  const lmm_ss_post* P = post;
+  const int p = P->p, m = P->m, ms = P->l1 - P->l0;
+  const double s2 = sigma2 == 0.0 ? P->sigma2 : sigma2;
+  const Latent* lts = P->ls->lat.data();
+  hipStream_t st0 = g.streams[0];
+  DevIn xsd(xs, (size_t)ns, st0), ysd(ys, (size_t)ns * p, st0);
+  // every refusal comes before the smoothed states are touched
+  SSWindow w;
+  if (int rc = ss_window(P->x.p, P->n, xsd.p, ns, w)) return rc;
+  SSFront Fr;
+  if (int rc = ss_front(ysd.p, ns, p, P->U.data(), P->S.data(), m, s2, lts, P->l0, P->l1, Fr)) return rc;
+  if (int rc = ss_post_ensure_smoothed(P, xsd.p, ns)) return rc;
+  std::vector<double> lml(std::max(ms, 1), 0.0);
+  if (int rc = ss_post_logpdf(P->x.p, P->n, lts + P->l0, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, w, Fr.w.p, Fr.r.p, 0,
+                              lml.data())) return rc;
+  double value = 0.0;
+  for (int j = 0; j < ms; ++j) value += lml[j];
+  value += Fr.reg;
+  *out = value;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Building block for tests beside lmm_dev_statespace_post_sample: ONE latent from DEVICE pointers and given states, its mean not read
+// (r is the residual).  w, r: ns values over the sorted queries (+Inf: unobserved); out: one value on the device.
+int lmm_dev_statespace_post_logpdf(const double* x, int n, const lmm_gp_t* gp, const double* fstate, const double* sstate, const double* xs,
+                                   int ns, const double* w, const double* r, int chunk, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  std::shared_ptr<LatentSet> ls;
+  const bool bad = !x || !gp || !fstate || !sstate || !xs || !w || !r || !out || n <= 0 || ns < 1 || chunk < 0;
+  if (int rc = ss_dev_prepare(bad, x, n, gp, ls)) return rc;
+  SSWindow win;
+  if (int rc = ss_window(x, n, xs, ns, win)) return rc;
+  const size_t off = 0;
+  double h = 0.0;
+  if (int rc = ss_post_logpdf(x, n, ls->lat.data(), 1, fstate, sstate, &off, xs, ns, win, w, r, chunk, &h)) return rc;
+  HIPCHK(hipMemcpyAsync(out, &h, sizeof(double), hipMemcpyHostToDevice, g.streams[0]));
+  HIPCHK(hipStreamSynchronize(g.streams[0]));
+  return LMM_OK;
+  LMM_CATCH
+}
+
 extern "C" {
 
 // Standard normals on the device (Philox4x32-10 + Box-Muller, Float64): out[j], j < count, reproducible for (seed, stream).

@@ -439,6 +439,24 @@ struct SSPostArgs {
 static_assert(sizeof(SSPostArgs) <= 4096, "SSPostArgs is passed by value: kernel arguments are limited to 4096 bytes");
 // fold from the right, suffix scan and restart of the backward recursion for nb pairs of one model
 void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st);
+// Predictive log density from the posterior object (DESIGN.md 4.18 "Predictive log density from the posterior object"): the Kalman
+// filter over the window's backward chain, from its last point down to its first.  One latent of a launch: its parameters, its stored
+// states (as SSPostLat) and the noise w and data r of the ns sorted queries (device; +Inf: an unobserved query).  Training points of
+// the window are unobserved steps.
+struct SSLpdfLat { double var, inv_ls, mean, quality; const double* fstate; const double* sstate; const double* w; const double* r; };
+struct SSLpdfArgs {
+  const double* x; int n;                     // sorted training inputs (device)
+  const double* xs; int ns;                   // sorted queries (device)
+  const int* src; int first, W;               // the window (launch_ss_window)
+  int chunk, nch;                             // window points per thread; nch = ceil(W / chunk) threads per latent
+  double* agg;                                // nb * ss_fwd_agg_elems(D, nch) doubles (not read when nch == 1)
+  double* part;                               // nb * nch log-density partials
+  SSLpdfLat lat[LMM_MAX_BATCH];
+};
+static_assert(sizeof(SSLpdfArgs) <= 4096, "SSLpdfArgs is passed by value: kernel arguments are limited to 4096 bytes");
+// fold from the right, suffix scan and restart (nch == 1: the restart alone, which is then the sequential filter) and lml[l] = latent
+// l's log p(queries' data | training data)
+void launch_ss_post_logpdf(const SSLpdfArgs& a, int model, int nb, double* lml, hipStream_t st);
 // Appending observations (DESIGN.md 4.18 "Appending observations").  The filter over k new points whose predecessor is a stored state.
 // One latent of a launch: its parameters, the noise w and data r of the k points (device), the packed state `init` (device,
 // ss_state_comps(D) values: mean, then the upper triangle of the covariance) of the point in front of them, and `out` (device), where

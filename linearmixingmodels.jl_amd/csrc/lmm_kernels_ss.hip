@@ -24,6 +24,9 @@
 // between them are a Markov chain that runs backwards, an affine recursion in the caller's normals again, so phases 1 - 3 run from the
 // right on SSAff<D> elements built from the stored states (ss_window_kernel, ss_pfold_kernel, the suffix scan with AffRevOp,
 // ss_ppath_kernel); nothing outside the queries' span is read.
+// Predictive log density from the posterior object (launch_ss_post_logpdf): held-out data at the queries are observations of that same
+// backward chain, so its marginal likelihood is a Kalman filter over the window from the right with affine transitions: phases 1 - 3
+// on SSFwd<D> elements (ss_lfold_kernel, the suffix scan with FwdRevOp, ss_lfilter_kernel, ss_finish_kernel).
 // Gradients with respect to locations: d lml / d x_t = g_t - g_{t+1} with g_t = d lml / d (x_t - x_{t-1}) local to one
 // transition (ss_input_grad); ss_rts_kernel<D, OSC, false, true> writes g while it steps through the points, ss_grad_x_kernel adds the
 // latents in order.  For the posterior object ss_interp_dx_kernel writes d mean / d s and d var / d s per (query, latent) and
@@ -812,6 +815,125 @@ __global__ __launch_bounds__(SS_THREADS) void ss_ppath_kernel(SSPostArgs a) {
   }
 }
 
+// ---- predictive log density from the posterior object ------------------------------------------------------------------------------
+// Observing data at the queries of the window's backward chain is a Kalman filter that runs from the window's last point down to its
+// first, with the affine transitions (E_j, g_j, L_j) (ss_fwd_element_affine, ss_chain_step).  The three phases of the filter serve it
+// from the right: ss_lfold_kernel, the suffix scan of SSFwd<D> with FwdRevOp, ss_lfilter_kernel, and ss_finish_kernel adds the
+// partials.  A training point of the window is an unobserved step; a query carries (w, r) of the front end, indexed through src.
+
+__device__ __forceinline__ double ss_lwindow_input(const SSLpdfArgs& a, long long j) {
+  const int s = a.src[j];
+  return s >= 0 ? a.x[s] : a.xs[-1 - s];
+}
+
+// The backward element of window point j (input xj, its successor's input xn; xn is not read at the last point) and the point's noise
+// and data.  The filtered state is taken as ss_window_element takes it; the last point's element is ss_chain_start.  Reads fstate of
+// points first - 1 .. first + count - 1 (>= 0) and sstate of point first + count (< n) only, and w, r of the queries.
+template <int D, typename Mod>
+__device__ __forceinline__ void ss_lwindow_element(const SSLpdfArgs& a, const SSLpdfLat& L, const Mod& M, long long j, double xj, double xn,
+                                                   SSBwd<D>& el, double& w, double& r) {
+  constexpr int NC = D + D * (D + 1) / 2;       // the stored states are point-major
+  const int s = a.src[j];
+  double m[D], P[D][D];
+  int k;
+  if (s >= 0) {
+    ss_load_state<D>(L.fstate, 1, NC, s, m, P);
+    k = s + 1;
+    w = INFINITY; r = 0.0;
+  } else {
+    k = a.first + (int)(j - (-1 - s));
+    if (k > 0) {
+      ss_load_state<D>(L.fstate, 1, NC, k - 1, m, P);
+      ss_filter_step<D>(M, xj - a.x[k - 1], INFINITY, 0.0, m, P);
+    } else {
+      for (int i = 0; i < D; ++i) {
+        m[i] = 0.0;
+        for (int c = 0; c < D; ++c) P[i][c] = M.Pinf[i][c];
+      }
+    }
+    w = L.w[-1 - s]; r = L.r[-1 - s];
+  }
+  if (j < a.W - 1) {
+    ss_bwd_element<D>(M, false, xn - xj, m, P, el);
+    return;
+  }
+  const bool has_next = k < a.n;
+  double ms[D], Ps[D][D], dt = 0.0;
+  for (int i = 0; i < D; ++i) {
+    ms[i] = 0.0;
+    for (int c = 0; c < D; ++c) Ps[i][c] = 0.0;
+  }
+  if (has_next) {
+    ss_load_state<D>(L.sstate, 1, NC, k, ms, Ps);
+    dt = a.x[k] - xj;
+  }
+  ss_chain_start<D>(M, has_next, dt, m, P, ms, Ps, el);
+}
+
+// the scan's REV hands over (item, what lies to its right); the run to the right is the earlier one in filter order
+struct FwdRevOp {
+  template <int D> static __device__ __forceinline__ void combine(const SSFwd<D>& a, const SSFwd<D>& b, SSFwd<D>& o) { ss_fwd_combine<D>(b, a, o); }
+};
+
+// one thread per run of `chunk` window points, folded from the right: the aggregate takes the filtered state behind the run to the one
+// at the run's first point
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_lfold_kernel(SSLpdfArgs a) {
+  const int c = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (c >= a.nch) return;
+  const SSLpdfLat& L = a.lat[z];
+  const auto M = ss_lat_model<D, OSC>(L);
+  const long long j0 = (long long)c * a.chunk;
+  const long long j1 = j0 + a.chunk < a.W ? j0 + a.chunk : a.W;
+  SSFwd<D> acc, fe;
+  SSBwd<D> el;
+  double xn = j1 < a.W ? ss_lwindow_input(a, j1) : 0.0;
+  for (long long j = j1 - 1; j >= j0; --j) {
+    const double xj = ss_lwindow_input(a, j);
+    double w, r;
+    ss_lwindow_element<D>(a, L, M, j, xj, xn, el, w, r);
+    ss_fwd_element_affine<D>(el.E, el.g, el.L, w, r, j == j1 - 1 ? acc : fe);
+    if (j < j1 - 1) ss_fwd_combine<D>(acc, fe, acc);
+    xn = xj;
+  }
+  reinterpret_cast<SSFwd<D>*>(a.agg)[(size_t)z * a.nch + c] = acc;
+}
+
+// each thread restarts the sequential filter from the state behind its run ((b, C) of the scanned aggregate of the run to its right;
+// the last run starts the chain and reads none) and writes its log-density partial.  With one chunk this kernel alone is the filter.
+template <int D, bool OSC>
+__global__ __launch_bounds__(SS_THREADS) void ss_lfilter_kernel(SSLpdfArgs a) {
+  const int c = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
+  if (c >= a.nch) return;
+  const SSLpdfLat& L = a.lat[z];
+  const auto M = ss_lat_model<D, OSC>(L);
+  const long long j0 = (long long)c * a.chunk;
+  const long long j1 = j0 + a.chunk < a.W ? j0 + a.chunk : a.W;
+  double m[D], P[D][D];
+  for (int i = 0; i < D; ++i) {                     // the start element has E = 0 and ignores this state
+    m[i] = 0.0;
+    for (int k = 0; k < D; ++k) P[i][k] = 0.0;
+  }
+  if (c + 1 < a.nch) {
+    const SSFwd<D>& suf = reinterpret_cast<const SSFwd<D>*>(a.agg)[(size_t)z * a.nch + c + 1];
+    for (int i = 0; i < D; ++i) {
+      m[i] = suf.b[i];
+      for (int k = 0; k < D; ++k) P[i][k] = suf.C[i][k];
+    }
+  }
+  SSBwd<D> el;
+  double lp = 0.0;
+  double xn = j1 < a.W ? ss_lwindow_input(a, j1) : 0.0;
+  for (long long j = j1 - 1; j >= j0; --j) {
+    const double xj = ss_lwindow_input(a, j);
+    double w, r;
+    ss_lwindow_element<D>(a, L, M, j, xj, xn, el, w, r);
+    lp += ss_chain_step<D>(el, w, r, m, P);
+    xn = xj;
+  }
+  a.part[(size_t)z * a.nch + c] = lp;
+}
+
 size_t scan_items(int nch, int W = SS_SCAN) {         // items of every level below the first
   size_t tot = 0;
   int N = nch;
@@ -933,6 +1055,19 @@ void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st)
     typedef decltype(t) T;
     ss_phases<T::D, SSAff<T::D>, AffRevOp, true>(ss_pfold_kernel<T::D, T::OSC>, ss_ppath_kernel<T::D, T::OSC>, a, 1, nb, a.agg, st);
   });
+}
+
+void launch_ss_post_logpdf(const SSLpdfArgs& a, int model, int nb, double* lml, hipStream_t st) {
+  ss_dispatch(model, [&](auto t) {
+    typedef decltype(t) T;
+    if (a.nch == 1) {     // one chunk: thread 0 of the restart is the whole sequential filter, no aggregate is read, and a latent's
+      SSLpdfArgs b = a;   // one partial is its log density: one launch in all
+      b.part = lml;
+      hipLaunchKernelGGL((ss_lfilter_kernel<T::D, T::OSC>), dim3(1, 1, nb), dim3(SS_THREADS), 0, st, b);
+    } else
+      ss_phases<T::D, SSFwd<T::D>, FwdRevOp, true>(ss_lfold_kernel<T::D, T::OSC>, ss_lfilter_kernel<T::D, T::OSC>, a, 1, nb, a.agg, st);
+  });
+  if (a.nch > 1) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
 }
 
 void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st) {

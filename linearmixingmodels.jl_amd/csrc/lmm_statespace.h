@@ -716,3 +716,86 @@ SS_HD void ss_post_element(const Mod& M, bool last, bool has_next, double dt, co
     for (int j = 0; j < D; ++j) e.A[i][j] = el.E[i][j];
   }
 }
+
+// ---- predictive log density from the posterior object (DESIGN.md 4.18 "Predictive log density from the posterior object") -----------
+// Observing held-out data at the queries of the backward chain above is a Kalman filter over the window that runs from its last point
+// down to its first, with the AFFINE transitions s_j = E_j s_{j+1} + g_j + N(0, L_j) in the place of s_t = A(dt) s_{t-1} + N(0, Q(dt)).
+// The forward element of one such step, observed through h = e_1' with noise w and data r: with S = L_00 + w and K = L[:, 0] / S,
+// A = E - K E[0, :], b = g + K (r - g_0), C = L - K L[0, :], eta = E[0, :]' (r - g_0) / S, J = E[0, :]' E[0, :] / S; w = +Inf
+// (unobserved): (E, g, L, 0, 0).  ss_fwd_element is the case g = 0.  The window's last point starts the chain with E = 0 and (g, L)
+// the posterior state (m*, P*) there, which gives A = 0, eta = 0, J = 0 and (b, C) that state after its own update.
+template <int D>
+SS_HD void ss_fwd_element_affine(const double E[D][D], const double g[D], const double L[D][D], double w, double r, SSFwd<D>& e) {
+  if (!(w < INFINITY)) {
+    for (int i = 0; i < D; ++i) {
+      e.b[i] = g[i]; e.eta[i] = 0.0;
+      for (int j = 0; j < D; ++j) { e.A[i][j] = E[i][j]; e.C[i][j] = L[i][j]; e.J[i][j] = 0.0; }
+    }
+    return;
+  }
+  const double Sinv = 1.0 / (L[0][0] + w), d = r - g[0];
+  for (int i = 0; i < D; ++i) {
+    const double K = L[i][0] * Sinv;
+    e.b[i] = g[i] + K * d;
+    e.eta[i] = E[0][i] * d * Sinv;
+    for (int j = 0; j < D; ++j) {
+      e.A[i][j] = E[i][j] - K * E[0][j];
+      e.C[i][j] = L[i][j] - K * L[0][j];
+      e.J[i][j] = E[0][i] * E[0][j] * Sinv;
+    }
+  }
+}
+
+// The backward element of the window's last point: E = 0 and (g, L) = (m*, P*), the posterior state there as ss_post_element takes it
+// -- has_next: one RTS step back from (ms, Ps), the smoothed state of the training point dt further; else the filtered (m, P) itself.
+template <int D, typename Mod>
+SS_HD void ss_chain_start(const Mod& M, bool has_next, double dt, const double m[D], const double P[D][D], const double ms[D],
+                          const double Ps[D][D], SSBwd<D>& el) {
+  ss_bwd_element<D>(M, !has_next, dt, m, P, el);
+  if (has_next) {
+    double mm[D], PP[D][D];
+    for (int i = 0; i < D; ++i) {
+      mm[i] = ms[i];
+      for (int j = 0; j < D; ++j) PP[i][j] = Ps[i][j];
+    }
+    ss_rts_step<D>(el, mm, PP);
+    for (int i = 0; i < D; ++i) {
+      el.g[i] = mm[i];
+      for (int j = 0; j < D; ++j) el.L[i][j] = PP[i][j];
+    }
+  }
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) el.E[i][j] = 0.0;
+}
+
+// One step of the sequential filter along the chain: (m, P) at window point j + 1 -> (m, P) at point j with element el, m <- E m + g
+// and P <- E P E' + L, then ss_filter_step's update.  Returns the point's log-density term, 0 for an unobserved point.  The start
+// element (E = 0) makes (m*, P*) of any finite (m, P).
+template <int D>
+SS_HD double ss_chain_step(const SSBwd<D>& el, double w, double r, double m[D], double P[D][D]) {
+  double X[D][D], mp[D];
+  ss_mm<D>(el.E, P, X);
+  for (int i = 0; i < D; ++i) {
+    double s = el.g[i];
+    for (int k = 0; k < D; ++k) s += el.E[i][k] * m[k];
+    mp[i] = s;
+  }
+  for (int i = 0; i < D; ++i) {
+    m[i] = mp[i];
+    for (int j = i; j < D; ++j) {
+      double q = el.L[i][j];
+      for (int k = 0; k < D; ++k) q += X[i][k] * el.E[j][k];
+      P[i][j] = P[j][i] = q;
+    }
+  }
+  if (!(w < INFINITY)) return 0.0;
+  const double S = P[0][0] + w, Sinv = 1.0 / S, e = r - m[0];
+  double K[D], p0[D];
+  for (int i = 0; i < D; ++i) { p0[i] = P[0][i]; K[i] = P[i][0] * Sinv; }
+  for (int i = 0; i < D; ++i) {
+    m[i] += K[i] * e;
+    for (int j = 0; j < D; ++j) P[i][j] -= K[i] * p0[j];
+  }
+  ss_sym<D>(P);
+  return -0.5 * (log(6.283185307179586 * S) + e * e * Sinv);
+}

@@ -1034,7 +1034,8 @@ def statespace_mean_and_var(fx: "FiniteGP", y, add_noise: bool = True, xs=None):
 class StateSpacePosterior:
     """posterior(fx, y) on the state-space path: owns an lmm_ss_post_t* (the sorted inputs and, per latent, the filtered and the
     smoothed states on the device; include/lmm_hip.h "state space: the posterior object") and answers mean_and_var(post(x*, sigma2))
-    at new inputs in O(ns log n) per latent, without touching the data again; rand draws joint samples there from the same states.
+    at new inputs in O(ns log n) per latent, without touching the data again; rand draws joint samples there from the same states,
+    and predictive_logpdf scores held-out observations there.
     Built by statespace_posterior; freed by close(), on leaving a `with` block or with the object."""
 
     def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float, dims: Optional[Sequence[int]] = None,
@@ -1280,6 +1281,33 @@ class StateSpacePosterior:
             import torch
             return torch.stack(cols, dim=1)
         return np.stack(cols, axis=1)
+
+    def predictive_logpdf(self, xs, ys, sigma2: Optional[float] = None) -> float:
+        """logpdf(post(xs, sigma2), ys): the joint log density of the held-out observations ys at the inputs xs given the training
+        data, from the stored states alone, in O(ns + count) per latent (window(xs)) -- a Kalman filter over the posterior's backward
+        Markov chain, run from the largest query (include/lmm_hip.h "state space: predictive log density").  (`logpdf` is the
+        attribute that holds the training data's value, hence the name.)  xs: (ns,) in any order (sorted here, stably, with ys
+        carried along), NumPy or a torch device tensor; ys: (ns * p,) by outputs in the caller's order, NaN = missing (a query
+        without any observed output contributes 0; one observing fewer than m outputs is refused by the library, which names it by
+        its index among the sorted queries); sigma2: the noise at the queries, None = the handle's own.  The handle is left
+        as it was: n, logpdf and every later answer are unchanged.  Every refusal below comes before any library call."""
+        xs = self._queries(xs)
+        ns = int(xs.shape[0])
+        if not hasattr(ys, "shape"):
+            ys = np.asarray(ys, dtype=np.float64)
+        if len(ys.shape) != 1 or int(ys.shape[0]) != ns * self.p:
+            raise ValueError(f"StateSpacePosterior.predictive_logpdf: ys holds ns * p = {ns * self.p} values by outputs")
+        if sigma2 is not None:
+            sigma2 = float(sigma2)
+            if not np.isfinite(sigma2) or not sigma2 > 0.0:
+                raise ValueError("StateSpacePosterior.predictive_logpdf: sigma2 must be finite and > 0 (None: the handle's own)")
+        if ns == 0:
+            return 0.0
+        xa, ya, _, _ = _statespace_sorted(xs, ys, self.p)
+        out = C.c_double()
+        L.check(L.load().lmm_oilmm_statespace_post_logpdf(self._ptr, L.Arr(xa).ptr, ns, L.Arr(ya).ptr, 0.0 if sigma2 is None else sigma2,
+                                                          C.byref(out)))
+        return out.value
 
 
 def statespace_posterior(fx: "FiniteGP", y) -> StateSpacePosterior:
