@@ -5550,27 +5550,36 @@ static std::vector<size_t> ss_post_offsets(const Latent* lts, int ms, int cap) {
   return off;
 }
 
-// The zero-mean (add_mean: plus the latent's mean) marginals of the ms latents lts[0 .. ms) at the ns queries xsd from their stored
-// states (latent k's block off[k] doubles into fstate / sstate): ml, vl [latent][ns] on the device (vl may be nullptr).  Launches
-// group consecutive latents of one model, LMM_MAX_BATCH at the most.  Queues on streams[0] and does not wait.
-// dx: ml, vl (both given) take the derivatives of the two with respect to the query instead (launch_ss_interp_dx).
-static void ss_interp_latents(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
-                       const double* xsd, int ns, bool add_mean, double* ml, double* vl, bool point_major = true, bool dx = false,
-                       int cap = 0) {       // cap: the points a latent's block has room for (0: n)
+// The stored states of ms latents over n sorted inputs, as every reader takes them (device pointers but off): latent k's filtered and
+// smoothed states lie off[k] doubles into fstate / sstate, in a block with room for cap >= n points, [point][component] or transposed.
+enum SSLayout { SS_POINT_MAJOR, SS_COMPONENT_MAJOR };
+struct SSStored { const double* x; int n, cap; const Latent* lts; int ms; const double* fstate; const double* sstate; const size_t* off; SSLayout layout; };
+static SSStored ss_stored(const lmm_ss_post* P) {
+  return {P->x.p, P->n, P->cap, P->ls->lat.data() + P->l0, P->l1 - P->l0, P->fstate.p, P->sstate.p, P->off.data(), SS_POINT_MAJOR};
+}
+static const size_t kNoOffset = 0;       // one latent's own buffers, as the lmm_dev_statespace_* building blocks are handed them
+static SSStored ss_stored(const double* x, int n, const Latent* lt, const double* fstate, const double* sstate, SSLayout layout = SS_POINT_MAJOR) {
+  return {x, n, n, lt, 1, fstate, sstate, &kNoOffset, layout};
+}
+
+// The zero-mean (add_mean: plus the latent's mean) marginals of the stored latents at the ns queries xsd: ml, vl [latent][ns] on the
+// device (vl may be nullptr); SS_INTERP_DX: their derivatives with respect to the query instead (both given; launch_ss_interp_dx).
+// Launches group consecutive latents of one model, LMM_MAX_BATCH at the most.  Queues on streams[0] and does not wait.
+enum SSInterpWhat { SS_INTERP_MARGINALS, SS_INTERP_DX };
+static void ss_interp_latents(const SSStored& S, const double* xsd, int ns, SSInterpWhat what, bool add_mean, double* ml, double* vl) {
   hipStream_t st0 = g.streams[0];
+  const bool point_major = S.layout == SS_POINT_MAJOR, dx = what == SS_INTERP_DX;
   const auto no_buffers = [](int, int, int) { return size_t(1); };       // a launch allocates nothing: LMM_MAX_BATCH alone limits it
-  ss_for_launches(ms, 0, [&](long long k) -> const Latent& { return lts[k]; }, no_buffers, [&](long long e0, int nb, int model, int D) {
+  ss_for_launches(S.ms, 0, [&](long long k) -> const Latent& { return S.lts[k]; }, no_buffers, [&](long long e0, int nb, int model, int D) {
     const int k0 = (int)e0;
     SSInterpArgs a{};
-    a.x = xd; a.n = n; a.xs = xsd; a.ns = ns;
-    a.fstate = fstate + off[k0]; a.sstate = sstate + off[k0];
-    a.state_stride = (size_t)ss_state_comps(D) * (cap ? cap : n);
-    a.comp_stride = point_major ? 1 : (size_t)n; a.point_stride = point_major ? (size_t)ss_state_comps(D) : 1;
-    a.mean = ml + (size_t)k0 * ns; a.var = vl ? vl + (size_t)k0 * ns : nullptr;
-    if (dx) { a.dmean = a.mean; a.dvar = a.var; a.mean = nullptr; a.var = nullptr; }
-    for (int j = 0; j < nb; ++j) ss_fill_lat(a.lat[j], lts[k0 + j], add_mean);
-    if (dx) launch_ss_interp_dx(a, model, nb, st0);
-    else launch_ss_interp(a, model, nb, st0);
+    a.x = S.x; a.n = S.n; a.xs = xsd; a.ns = ns;
+    a.fstate = S.fstate + S.off[k0]; a.sstate = S.sstate + S.off[k0];
+    a.state_stride = (size_t)ss_state_comps(D) * S.cap;
+    a.comp_stride = point_major ? 1 : (size_t)S.n; a.point_stride = point_major ? (size_t)ss_state_comps(D) : 1;
+    (dx ? a.dmean : a.mean) = ml + (size_t)k0 * ns; (dx ? a.dvar : a.var) = vl ? vl + (size_t)k0 * ns : nullptr;
+    for (int j = 0; j < nb; ++j) ss_fill_lat(a.lat[j], S.lts[k0 + j], add_mean);
+    (dx ? launch_ss_interp_dx : launch_ss_interp)(a, model, nb, st0);
   });
   HIPCHK(hipGetLastError());
 }
@@ -5684,21 +5693,37 @@ static void ss_post_grow(lmm_ss_post* P, int n_total) {
   P->off = off; P->cap = n_total;
 }
 
-// The filter over k new points from a stored state, per launch group of the ms latents: latent j reads init[j] (device, packed) at
-// input x0 and writes its k states to out[j] (device, point-major); w, r: [latent][k] on the device; lml: ms host values.
-static int ss_filter_from(const double* xd, int k, double x0, const Latent* lts, int ms, const double* w, const double* r, int chunk,
-                          const double* const* init, double* const* out, double* fmean, double* fvar, double* lml) {
+// The launch loop of a scored scan, a filter over `items` points per latent that ends in lml[k] (host, ms values): from a stored state
+// (SSFromArgs) or over a window's backward chain (SSLpdfArgs).  It holds the plan, the launch groups within the byte budget and their
+// buffers (none with one chunk: the single launch); a0 is the launch's arguments but chunk, nch, agg, part and lat, and fill(a, k0, nb)
+// sets what belongs to the latents [k0, k0 + nb) of a launch.  Returns with streams[0] drained.
+template <typename Args, typename Fill>
+static void ss_scored_scan(const Latent* lts, int ms, int items, int chunk, const Args& a0,
+                           void (*launch)(const Args&, int, int, double*, hipStream_t), double* lml, Fill&& fill) {
   hipStream_t st0 = g.streams[0];
-  const SSChunks plan = ss_plan_chunks(k, chunk);
-  const int nch = plan.nch;
+  const SSChunks plan = ss_plan_chunks(items, chunk);
   const auto bytes = [&](int, int D, int nch) { return (ss_fwd_agg_elems(D, nch) + (size_t)nch) * sizeof(double); };
-  ss_for_launches(ms, nch, [&](long long j) -> const Latent& { return lts[j]; }, bytes, [&](long long e0, int nb, int model, int D) {
-    const int k0 = (int)e0;
+  ss_for_launches(ms, plan.nch, [&](long long j) -> const Latent& { return lts[j]; }, bytes, [&](long long e0, int nb, int model, int D) {
+    const int k0 = (int)e0, nch = plan.nch;
     Buf<double> agg, part, lmld(nb);
     if (nch > 1) { agg = Buf<double>((size_t)nb * ss_fwd_agg_elems(D, nch)); part = Buf<double>((size_t)nb * nch); }
-    SSFromArgs a{};
-    a.x = xd; a.n = k; a.chunk = plan.chunk; a.nch = nch; a.x0 = x0;
-    a.agg = agg.p; a.part = part.p;
+    Args a = a0;
+    a.chunk = plan.chunk; a.nch = nch; a.agg = agg.p; a.part = part.p;
+    fill(a, k0, nb);
+    launch(a, model, nb, lmld.p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(lml + k0, lmld.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));          // the buffers above go back to the pool
+  });
+}
+
+// The filter over k new points from a stored state, per launch group of the ms latents: latent j reads init[j] (device, packed) at
+// input x0 and writes its k states to out[j] (device, point-major); w, r: [latent][k] on the device; lml: ms host values.
+static void ss_filter_from(const double* xd, int k, double x0, const Latent* lts, int ms, const double* w, const double* r, int chunk,
+                           const double* const* init, double* const* out, double* fmean, double* fvar, double* lml) {
+  SSFromArgs a0{};
+  a0.x = xd; a0.n = k; a0.x0 = x0;
+  ss_scored_scan(lts, ms, k, chunk, a0, launch_ss_filter_from, lml, [&](SSFromArgs& a, int k0, int nb) {
     a.fmean = fmean ? fmean + (size_t)k0 * k : nullptr; a.fvar = fvar ? fvar + (size_t)k0 * k : nullptr;
     for (int j = 0; j < nb; ++j) {
       const Latent& L = lts[k0 + j];
@@ -5706,12 +5731,7 @@ static int ss_filter_from(const double* xd, int k, double x0, const Latent* lts,
       a.lat[j].w = w + (size_t)(k0 + j) * k; a.lat[j].r = r + (size_t)(k0 + j) * k;
       a.lat[j].init = init[k0 + j]; a.lat[j].out = out[k0 + j];
     }
-    launch_ss_filter_from(a, model, nb, lmld.p, st0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(lml + k0, lmld.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st0));
-    HIPCHK(hipStreamSynchronize(st0));          // the buffers above go back to the pool
   });
-  return LMM_OK;
 }
 
 int lmm_oilmm_statespace_post_append(lmm_ss_post_t* post, const double* x_new, int k, const double* y_new, double* out_increment) {
@@ -5756,8 +5776,7 @@ int lmm_oilmm_statespace_post_append(lmm_ss_post_t* post, const double* x_new, i
     outp[j] = P->fstate.p + P->off[j] + (size_t)n * comps;
   }
   std::vector<double> lml(std::max(ms, 1), 0.0);
-  if (int rc = ss_filter_from(P->x.p + n, k, P->xlast, lts + P->l0, ms, Fr.w.p, Fr.r.p, 0, init.data(), outp.data(), nullptr, nullptr,
-                              lml.data())) return rc;
+  ss_filter_from(P->x.p + n, k, P->xlast, lts + P->l0, ms, Fr.w.p, Fr.r.p, 0, init.data(), outp.data(), nullptr, nullptr, lml.data());
   HIPCHK(hipStreamSynchronize(st0));
   double inc = 0.0;
   for (int j = 0; j < ms; ++j) inc += lml[j];
@@ -5812,7 +5831,7 @@ int lmm_dev_statespace_filter_from(const double* state0, double x0, const double
   HIPCHK(hipMemcpy(&first, x, sizeof(double), hipMemcpyDeviceToHost));
   if (!(first >= x0)) return fail(LMM_ERR_ARG, "state-space filter: x[0] = %g lies in front of the given state's input x0 = %g", first, x0);
   double h = 0.0;
-  if (int rc = ss_filter_from(x, k, x0, ls->lat.data(), 1, w, r, chunk, &state0, &fstate, fmean, fvar, &h)) return rc;
+  ss_filter_from(x, k, x0, ls->lat.data(), 1, w, r, chunk, &state0, &fstate, fmean, fvar, &h);
   HIPCHK(hipMemcpyAsync(lml, &h, sizeof(double), hipMemcpyHostToDevice, st0));
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
@@ -5833,8 +5852,7 @@ int lmm_oilmm_statespace_post_mean_and_var(const lmm_ss_post_t* post, const doub
   if (int rc = ss_check_finite(xsd.p, ns)) return rc;
   if (int rc = ss_post_ensure_smoothed(P, xsd.p, ns)) return rc;
   Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
-  ss_interp_latents(P->x.p, P->n, P->ls->lat.data() + P->l0, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, true, ml.p,
-                    var_out ? vl.p : nullptr, true, false, P->cap);
+  ss_interp_latents(ss_stored(P), xsd.p, ns, SS_INTERP_MARGINALS, true, ml.p, var_out ? vl.p : nullptr);
   DevOut mo(mean_out, (size_t)ns * p), vo(var_out, (size_t)ns * p);
   mix_marginals(ml.p, ns, ms, P->H.p, p, 1, 0.0, 0.0, mo.p, st0);
   if (var_out) mix_marginals(vl.p, ns, ms, P->H.p, p, 2, kDefaultJit.default_jitter, add_noise ? P->sigma2 : 0.0, vo.p, st0);
@@ -5863,8 +5881,7 @@ int lmm_oilmm_statespace_post_mean_and_var_grad_xs(const lmm_ss_post_t* post, co
   if (int rc = ss_post_ensure_smoothed(P, xsd.p, ns)) return rc;
   DevIn dm(dmean, (size_t)ns * p, st0), dv(dvar, (size_t)ns * p, st0);
   Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
-  ss_interp_latents(P->x.p, P->n, P->ls->lat.data() + P->l0, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, false, ml.p, vl.p, true,
-                    true, P->cap);
+  ss_interp_latents(ss_stored(P), xsd.p, ns, SS_INTERP_DX, false, ml.p, vl.p);
   DevOut go(grad_xs, (size_t)ns);
   launch_ss_contract_dx(dm.p, dv.p, P->H.p, p, ms, ml.p, vl.p, ns, go.p, st0);
   HIPCHK(hipGetLastError());
@@ -5901,8 +5918,8 @@ int lmm_dev_statespace_interp_layout(const double* x, int n, const lmm_gp_t* gp,
   if (int rc = ss_dev_prepare(bad, x, n, gp, ls)) return rc;
   const Latent* lts = ls->lat.data();
   if (int rc = ss_check_finite(xs, ns)) return rc;
-  const size_t off = 0;
-  ss_interp_latents(x, n, lts, 1, fstate, sstate, &off, xs, ns, false, mean, var, point_major != 0);
+  const SSLayout layout = point_major ? SS_POINT_MAJOR : SS_COMPONENT_MAJOR;
+  ss_interp_latents(ss_stored(x, n, lts, fstate, sstate, layout), xs, ns, SS_INTERP_MARGINALS, false, mean, var);
   HIPCHK(hipStreamSynchronize(g.streams[0]));
   return LMM_OK;
   LMM_CATCH
@@ -6128,17 +6145,15 @@ static int ss_window(const double* xd, int n, const double* xsd, int ns, SSWindo
   return LMM_OK;
 }
 
-// Posterior paths of the ms latents lts[0 .. ms) at the sorted queries for N samples from their stored states (latent k's block
-// off[k] doubles into fstate / sstate): f[sample][latent][ns] on the device, with the latent's mean when add_mean.  z: sample 0's
-// normals of lts[0] on the device, the latents one after the other (D_l W values each, component-major over window positions), the
-// samples z_stride doubles apart.  Returns with streams[0] drained.
-static int ss_post_paths(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
-                         const double* xsd, int ns, const SSWindow& w, int N, const double* z, size_t z_stride, int chunk, bool add_mean,
-                         double* f) {
+// Posterior paths of the stored latents at the sorted queries for N samples: f[sample][latent][ns] on the device, with the latent's
+// mean when add_mean.  z: sample 0's normals of S.lts[0] on the device, the latents one after the other (D_l W values each,
+// component-major over window positions), the samples z_stride doubles apart.  Returns with streams[0] drained.
+static int ss_post_paths(const SSStored& S, const double* xsd, int ns, const SSWindow& w, int N, const double* z, size_t z_stride, int chunk,
+                         bool add_mean, double* f) {
   SSPostArgs a{};
-  a.x = xd; a.n = n; a.xs = xsd; a.ns = ns; a.src = w.src.p; a.first = w.first; a.W = w.W;
-  ss_pair_launches(lts, ms, N, w.W, chunk, add_mean, a, launch_ss_post_path, [&](SSPostLat& o, int k, int q, size_t zoff) {
-    o.fstate = fstate + off[k]; o.sstate = sstate + off[k]; o.z = z + (size_t)q * z_stride + zoff; o.f = f + ((size_t)q * ms + k) * ns;
+  a.x = S.x; a.n = S.n; a.xs = xsd; a.ns = ns; a.src = w.src.p; a.first = w.first; a.W = w.W;
+  ss_pair_launches(S.lts, S.ms, N, w.W, chunk, add_mean, a, launch_ss_post_path, [&](SSPostLat& o, int k, int q, size_t zoff) {
+    o.fstate = S.fstate + S.off[k]; o.sstate = S.sstate + S.off[k]; o.z = z + (size_t)q * z_stride + zoff; o.f = f + ((size_t)q * S.ms + k) * ns;
   });
   return LMM_OK;
 }
@@ -6181,7 +6196,7 @@ int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, 
   const int rc = ss_sample_mix(ns, std::max(w.W, ns), ms, p, P->H.p, P->sigma2, add_noise ? eps : nullptr, nsamples, od.p,
                                [&](int q0, int ng, double* f) {
     SSNormals zd(z, zshard, 0, zshard, q0, ng, st0);
-    return ss_post_paths(P->x.p, P->n, lts, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, w, ng, zd.p, zd.stride, 0, true, f);
+    return ss_post_paths(ss_stored(P), xsd.p, ns, w, ng, zd.p, zd.stride, 0, true, f);
   });
   if (rc) return rc;
   od.finish(st0);
@@ -6203,41 +6218,27 @@ int lmm_dev_statespace_post_sample(const double* x, int n, const lmm_gp_t* gp, c
   const Latent* lts = ls->lat.data();
   SSWindow w;
   if (int rc = ss_window(x, n, xs, ns, w)) return rc;
-  const size_t zs = (size_t)ss_state_dim(lts[0].kind) * w.W, off = 0;
+  const size_t zs = (size_t)ss_state_dim(lts[0].kind) * w.W;
   return ss_for_sample_groups(std::max(w.W, ns), 1, nsamples, [&](int q0, int ng) {
-    return ss_post_paths(x, n, lts, 1, fstate, sstate, &off, xs, ns, w, ng, z + (size_t)q0 * zs, zs, chunk, false, f + (size_t)q0 * ns);
+    return ss_post_paths(ss_stored(x, n, lts, fstate, sstate), xs, ns, w, ng, z + (size_t)q0 * zs, zs, chunk, false, f + (size_t)q0 * ns);
   });
   LMM_CATCH
 }
 
 // ---- predictive log density from the posterior object (DESIGN.md 4.18 "Predictive log density from the posterior object") --------
-// log p(the queries' data | the training data) of the ms latents lts[0 .. ms) from their stored states (latent k's block off[k]
-// doubles into fstate / sstate): the filter over the window's backward chain.  w, r: [latent][ns] on the device, over the sorted
-// queries (+Inf: unobserved); lml: ms host values.  Returns with streams[0] drained.
-static int ss_post_logpdf(const double* xd, int n, const Latent* lts, int ms, const double* fstate, const double* sstate, const size_t* off,
-                          const double* xsd, int ns, const SSWindow& win, const double* w, const double* r, int chunk, double* lml) {
-  hipStream_t st0 = g.streams[0];
-  const SSChunks plan = ss_plan_chunks(win.W, chunk);
-  const int nch = plan.nch;
-  const auto bytes = [&](int, int D, int nch) { return (ss_fwd_agg_elems(D, nch) + (size_t)nch) * sizeof(double); };
-  ss_for_launches(ms, nch, [&](long long j) -> const Latent& { return lts[j]; }, bytes, [&](long long e0, int nb, int model, int D) {
-    const int k0 = (int)e0;
-    Buf<double> agg, part, lmld(nb);
-    if (nch > 1) { agg = Buf<double>((size_t)nb * ss_fwd_agg_elems(D, nch)); part = Buf<double>((size_t)nb * nch); }
-    SSLpdfArgs a{};
-    a.x = xd; a.n = n; a.xs = xsd; a.ns = ns; a.src = win.src.p; a.first = win.first; a.W = win.W;
-    a.chunk = plan.chunk; a.nch = nch; a.agg = agg.p; a.part = part.p;
+// log p(the queries' data | the training data) of the stored latents: the filter over the window's backward chain.  w, r: [latent][ns]
+// on the device, over the sorted queries (+Inf: unobserved); lml: S.ms host values.  Returns with streams[0] drained.
+static void ss_post_logpdf(const SSStored& S, const double* xsd, int ns, const SSWindow& win, const double* w, const double* r, int chunk,
+                           double* lml) {
+  SSLpdfArgs a0{};
+  a0.x = S.x; a0.n = S.n; a0.xs = xsd; a0.ns = ns; a0.src = win.src.p; a0.first = win.first; a0.W = win.W;
+  ss_scored_scan(S.lts, S.ms, win.W, chunk, a0, launch_ss_post_logpdf, lml, [&](SSLpdfArgs& a, int k0, int nb) {
     for (int j = 0; j < nb; ++j) {
-      ss_fill_lat(a.lat[j], lts[k0 + j], false);
-      a.lat[j].fstate = fstate + off[k0 + j]; a.lat[j].sstate = sstate + off[k0 + j];
+      ss_fill_lat(a.lat[j], S.lts[k0 + j], false);
+      a.lat[j].fstate = S.fstate + S.off[k0 + j]; a.lat[j].sstate = S.sstate + S.off[k0 + j];
       a.lat[j].w = w + (size_t)(k0 + j) * ns; a.lat[j].r = r + (size_t)(k0 + j) * ns;
     }
-    launch_ss_post_logpdf(a, model, nb, lmld.p, st0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(lml + k0, lmld.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st0));
-    HIPCHK(hipStreamSynchronize(st0));          // the buffers above go back to the pool
   });
-  return LMM_OK;
 }
 
 int lmm_oilmm_statespace_post_logpdf(const lmm_ss_post_t* post, const double* xs, int ns, const double* ys, double sigma2, double* out) {
@@ -6266,8 +6267,7 @@ int lmm_oilmm_statespace_post_logpdf(const lmm_ss_post_t* post, const double* xs
   if (int rc = ss_front(ysd.p, ns, p, P->U.data(), P->S.data(), m, s2, lts, P->l0, P->l1, Fr)) return rc;
   if (int rc = ss_post_ensure_smoothed(P, xsd.p, ns)) return rc;
   std::vector<double> lml(std::max(ms, 1), 0.0);
-  if (int rc = ss_post_logpdf(P->x.p, P->n, lts + P->l0, ms, P->fstate.p, P->sstate.p, P->off.data(), xsd.p, ns, w, Fr.w.p, Fr.r.p, 0,
-                              lml.data())) return rc;
+  ss_post_logpdf(ss_stored(P), xsd.p, ns, w, Fr.w.p, Fr.r.p, 0, lml.data());
   double value = 0.0;
   for (int j = 0; j < ms; ++j) value += lml[j];
   value += Fr.reg;
@@ -6288,9 +6288,8 @@ int lmm_dev_statespace_post_logpdf(const double* x, int n, const lmm_gp_t* gp, c
   if (int rc = ss_dev_prepare(bad, x, n, gp, ls)) return rc;
   SSWindow win;
   if (int rc = ss_window(x, n, xs, ns, win)) return rc;
-  const size_t off = 0;
   double h = 0.0;
-  if (int rc = ss_post_logpdf(x, n, ls->lat.data(), 1, fstate, sstate, &off, xs, ns, win, w, r, chunk, &h)) return rc;
+  ss_post_logpdf(ss_stored(x, n, ls->lat.data(), fstate, sstate), xs, ns, win, w, r, chunk, &h);
   HIPCHK(hipMemcpyAsync(out, &h, sizeof(double), hipMemcpyHostToDevice, g.streams[0]));
   HIPCHK(hipStreamSynchronize(g.streams[0]));
   return LMM_OK;

@@ -428,12 +428,16 @@ void launch_ss_window(const double* x, int n, const double* xs, int ns, int firs
 // pair's standard normals z (device, D W values, component i of window point j at z[i W + j]) and the path it writes (device, ns values
 // in the order of the sorted queries: the first component of the state + mean).
 struct SSPostLat { double var, inv_ls, mean, quality; const double* fstate; const double* sstate; const double* z; double* f; };
-struct SSPostArgs {
+// what every scan over a window takes, in front of its own fields (the kernels read their arguments by offset)
+struct SSWindowArgs {
   const double* x; int n;                     // sorted training inputs (device)
   const double* xs; int ns;                   // sorted queries (device)
   const int* src; int first, W;               // the window (launch_ss_window)
-  int chunk, nch;                             // window points per thread; nch = ceil(W / chunk) threads per pair
-  double* agg;                                // nb * ss_aff_agg_elems(D, nch) doubles: the affine aggregates and the scan's levels
+  int chunk, nch;                             // window points per thread; nch = ceil(W / chunk) threads per entry
+  double* agg;                                // nb * ss_aff_agg_elems(D, nch) (SSLpdfArgs: ss_fwd_agg_elems, not read when nch == 1) doubles:
+                                              // the aggregates and the scan's levels
+};
+struct SSPostArgs : SSWindowArgs {
   SSPostLat lat[LMM_MAX_BATCH];
 };
 static_assert(sizeof(SSPostArgs) <= 4096, "SSPostArgs is passed by value: kernel arguments are limited to 4096 bytes");
@@ -444,12 +448,7 @@ void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st)
 // states (as SSPostLat) and the noise w and data r of the ns sorted queries (device; +Inf: an unobserved query).  Training points of
 // the window are unobserved steps.
 struct SSLpdfLat { double var, inv_ls, mean, quality; const double* fstate; const double* sstate; const double* w; const double* r; };
-struct SSLpdfArgs {
-  const double* x; int n;                     // sorted training inputs (device)
-  const double* xs; int ns;                   // sorted queries (device)
-  const int* src; int first, W;               // the window (launch_ss_window)
-  int chunk, nch;                             // window points per thread; nch = ceil(W / chunk) threads per latent
-  double* agg;                                // nb * ss_fwd_agg_elems(D, nch) doubles (not read when nch == 1)
+struct SSLpdfArgs : SSWindowArgs {
   double* part;                               // nb * nch log-density partials
   SSLpdfLat lat[LMM_MAX_BATCH];
 };

@@ -17,7 +17,7 @@
 // Sampling (launch_ss_path): the prior path is an affine recursion in the caller's normals, so phases 1 - 3 run on SSAff<D> elements
 // (ss_sfold_kernel, the scan with AffOp, ss_path_kernel); a posterior path is the prior path plus the smoothed mean of the residual
 // data r - f - sqrt(w) xi (ss_pathwise_kernel, then the filter and smoother above, then ss_addpath_kernel).
-// The posterior object (launch_ss_interp): ss_rts_kernel<D, OSC, true> keeps the full smoothed and the filtered states point-major, and
+// The posterior object (launch_ss_interp): ss_rts_kernel<D, OSC, SS_RTS_FULL> keeps the full smoothed and the filtered states point-major, and
 // ss_interp_kernel answers a query at a new input from the two stored states that bracket it, one thread per (query, latent): a binary
 // search over x, one predict step, one RTS step (ss_interp); no LDS, no atomics, a query's result depends on no other query.
 // Sampling from the posterior object (launch_ss_post_path): given the data the states at the sorted queries and the training points
@@ -28,12 +28,15 @@
 // backward chain, so its marginal likelihood is a Kalman filter over the window from the right with affine transitions: phases 1 - 3
 // on SSFwd<D> elements (ss_lfold_kernel, the suffix scan with FwdRevOp, ss_lfilter_kernel, ss_finish_kernel).
 // Gradients with respect to locations: d lml / d x_t = g_t - g_{t+1} with g_t = d lml / d (x_t - x_{t-1}) local to one
-// transition (ss_input_grad); ss_rts_kernel<D, OSC, false, true> writes g while it steps through the points, ss_grad_x_kernel adds the
+// transition (ss_input_grad); ss_rts_kernel<D, OSC, SS_RTS_GX> writes g while it steps through the points, ss_grad_x_kernel adds the
 // latents in order.  For the posterior object ss_interp_dx_kernel writes d mean / d s and d var / d s per (query, latent) and
 // ss_contract_dx_kernel contracts them with H and the cotangents, one thread per query, latents in order.  No atomics, no LDS.
+// Appending observations (launch_ss_filter_from, launch_ss_smooth_kept) adds no kernel: ss_fold_kernel / ss_filter_kernel on SSFromArgs
+// start from a stored state instead of the prior, and ss_bfold_kernel<.., true> / ss_rts_kernel<.., SS_RTS_KEPT> smooth over kept states.
 // Shared by the kernels (lmm_statespace.h): ss_chunk_range (a thread's run), ss_count_le / ss_count_lt (the binary searches) and
-// ss_load_state (a stored state in either layout); ss_lat_model makes the model of any *Lat struct.  On the host, ss_dispatch hands a
-// launch's model to a generic lambda as compile-time (D, OSC), and ss_phases is the fold - scan - restart sequence of every direction.
+// ss_load_state / ss_store_state (a stored state in either layout); ss_lat_model makes the model of any *Lat struct.  On the host, ss_dispatch hands a
+// launch's model to a generic lambda as compile-time (D, OSC), and ss_phases is the fold - scan - restart sequence of every direction
+// (ss_scored_phases: with the log-density finish, and the single launch when there is one chunk).
 #include "lmm_internal.h"
 #include "lmm_statespace.h"
 
@@ -74,24 +77,40 @@ __device__ __forceinline__ typename SSModelOf<D, OSC, Sc>::type ss_lat_model(con
 // Fold and filter in both scalar types.  Sc = double: the value; the aggregates of latent z = blockIdx.z are item z of a.agg.
 // Sc = SSDual: (value, tangent) with blockIdx.y the seeded parameter (NS = ss_seeds<OSC>() of them), so a thread carries one tangent;
 // the aggregates of (latent z, seed s) are item NS z + s of a.dagg.
-template <int D, bool OSC, typename Sc>
-__global__ __launch_bounds__(SS_THREADS) void ss_fold_kernel(SSArgs a) {
-  constexpr bool DUAL = std::is_same<Sc, SSDual>::value;
+// And from both starts (Args).  SSArgs: the prior in front of point 0.  SSFromArgs (Sc = double; DESIGN.md 4.18 "Appending
+// observations"): a stored state, L.init at input a.x0 -- the element of point 0 is ss_fwd_element_from, thread 0 restarts from L.init
+// over x[0] - x0, and the filtered states go point-major to L.out (rows n .. n + k - 1 of the posterior object's block); every other
+// element and the scan are the same.
+template <int D, bool OSC, typename Sc, typename Args>
+__device__ __forceinline__ SSFwd<D, Sc>& ss_fwd_agg(const Args& a, int z, int s, size_t j) {       // aggregate j of (latent z, seed s)
+  if constexpr (std::is_same<Sc, SSDual>::value) return reinterpret_cast<SSFwd<D, Sc>*>(a.dagg)[(size_t)(ss_seeds<OSC>() * z + s) * a.nch + j];
+  else return reinterpret_cast<SSFwd<D, Sc>*>(a.agg)[(size_t)z * a.nch + j];
+}
+
+template <int D, bool OSC, typename Sc, typename Args = SSArgs>
+__global__ __launch_bounds__(SS_THREADS) void ss_fold_kernel(Args a) {
+  constexpr bool DUAL = std::is_same<Sc, SSDual>::value, FROM = std::is_same<Args, SSFromArgs>::value;
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = DUAL ? blockIdx.y : 0;
   if (j >= a.nch) return;
-  const SSLat& L = a.lat[z];
+  const auto& L = a.lat[z];
   const auto M = ss_lat_model<D, OSC, Sc>(L, s);
   const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
   SSFwd<D, Sc> acc, el;
   double xp = a.x[t0];
-  ss_fwd_element<D, Sc>(M, t0 == 0, t0 == 0 ? 0.0 : xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
+  if constexpr (FROM) {
+    if (t0 == 0) {
+      double m0[D], P0[D][D];
+      ss_load_state<D>(L.init, 1, 0, 0, m0, P0);
+      ss_fwd_element_from<D>(M, xp - a.x0, m0, P0, L.w[0], L.r[0], acc);
+    } else ss_fwd_element<D>(M, false, xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
+  } else ss_fwd_element<D, Sc>(M, t0 == 0, t0 == 0 ? 0.0 : xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
   for (long long t = t0 + 1; t < t1; ++t) {
     const double xt = a.x[t];
     ss_fwd_element<D, Sc>(M, false, xt - xp, L.w[t], L.r[t], el);
     ss_fwd_combine<D, Sc>(acc, el, acc);
     xp = xt;
   }
-  reinterpret_cast<SSFwd<D, Sc>*>(DUAL ? a.dagg : a.agg)[(size_t)(DUAL ? ss_seeds<OSC>() * z + s : z) * a.nch + j] = acc;
+  ss_fwd_agg<D, OSC, Sc>(a, z, s, j) = acc;
 }
 
 struct FwdOp {
@@ -163,23 +182,27 @@ void scan_levels(T* items, int N, int nb, T* scratch, hipStream_t st) {
   hipLaunchKernelGGL((ss_addprefix_kernel<D, T, Op, REV>), dim3(nblk - 1, 1, nb), dim3(W), 0, st, items, N, (const T*)scratch);
 }
 
-// Sc = double writes the marginals, the states and its log-density partial; Sc = SSDual only the tangent of its partial
-template <int D, bool OSC, typename Sc>
-__global__ __launch_bounds__(SS_THREADS) void ss_filter_kernel(SSArgs a) {
-  constexpr bool DUAL = std::is_same<Sc, SSDual>::value;
+// Sc = double writes the marginals, the states and its log-density partial; Sc = SSDual only the tangent of its partial.  With one
+// chunk this kernel alone is the filter (ss_scored_phases).
+template <int D, bool OSC, typename Sc, typename Args = SSArgs>
+__global__ __launch_bounds__(SS_THREADS) void ss_filter_kernel(Args a) {
+  constexpr bool DUAL = std::is_same<Sc, SSDual>::value, FROM = std::is_same<Args, SSFromArgs>::value;
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z, s = DUAL ? blockIdx.y : 0;
   if (j >= a.nch) return;
-  const SSLat& L = a.lat[z];
+  const auto& L = a.lat[z];
   const auto M = ss_lat_model<D, OSC, Sc>(L, s);
   const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
   Sc m[D], P[D][D];
   if (j == 0) {
-    for (int i = 0; i < D; ++i) {
-      m[i] = 0.0;
-      for (int k = 0; k < D; ++k) P[i][k] = M.Pinf[i][k];
+    if constexpr (FROM) ss_load_state<D>(L.init, 1, 0, 0, m, P);
+    else {
+      for (int i = 0; i < D; ++i) {
+        m[i] = 0.0;
+        for (int k = 0; k < D; ++k) P[i][k] = M.Pinf[i][k];
+      }
     }
-  } else {
-    const SSFwd<D, Sc>& pre = reinterpret_cast<const SSFwd<D, Sc>*>(DUAL ? a.dagg : a.agg)[(size_t)(DUAL ? ss_seeds<OSC>() * z + s : z) * a.nch + j - 1];
+  } else {       // (b, C) of the prefix, written out: through a loader the SSFromArgs instantiation of Matern32 takes 110 VGPRs, not 96
+    const SSFwd<D, Sc>& pre = ss_fwd_agg<D, OSC, Sc>(a, z, s, (size_t)j - 1);
     for (int i = 0; i < D; ++i) {
       m[i] = pre.b[i];
       for (int k = 0; k < D; ++k) P[i][k] = pre.C[i][k];
@@ -187,9 +210,12 @@ __global__ __launch_bounds__(SS_THREADS) void ss_filter_kernel(SSArgs a) {
   }
   double* fm = a.fmean ? a.fmean + (size_t)z * a.n : nullptr;
   double* fv = a.fvar ? a.fvar + (size_t)z * a.n : nullptr;
-  double* stt = a.state ? a.state + (size_t)z * a.state_stride : nullptr;
+  double* stt = nullptr;
+  if constexpr (!FROM) stt = a.state ? a.state + (size_t)z * a.state_stride : nullptr;
   Sc lp = 0.0;
-  double xp = t0 == 0 ? a.x[0] : a.x[t0 - 1];
+  double xp;
+  if constexpr (FROM) xp = t0 == 0 ? a.x0 : a.x[t0 - 1];
+  else xp = t0 == 0 ? a.x[0] : a.x[t0 - 1];
   for (long long t = t0; t < t1; ++t) {
     const double xt = a.x[t];
     lp += ss_filter_step<D, Sc>(M, xt - xp, L.w[t], L.r[t], m, P);
@@ -197,7 +223,8 @@ __global__ __launch_bounds__(SS_THREADS) void ss_filter_kernel(SSArgs a) {
     if constexpr (!DUAL) {
       if (fm) fm[t] = m[0];
       if (fv) fv[t] = P[0][0];
-      if (stt) {
+      if constexpr (FROM) ss_store_state<D>(L.out, 1, D + D * (D + 1) / 2, t, m, P);       // point-major
+      else if (stt) {                                                                      // component-major
         for (int i = 0; i < D; ++i) {
           stt[(size_t)i * a.n + t] = m[i];
           for (int k = i; k < D; ++k) stt[(size_t)ss_sym_at(D, i, k) * a.n + t] = P[i][k];
@@ -264,40 +291,49 @@ __global__ __launch_bounds__(SS_THREADS) void ss_point_kernel(SSArgs a, double* 
   if (threadIdx.x < 4) ppart[((size_t)z * 4 + threadIdx.x) * nblk + blockIdx.x] = sh[threadIdx.x][0];
 }
 
-template <int D, bool OSC>
+// The backward recursion reads the filtered states from a.state, component-major, as the filter of the same call left them; KEPT: from
+// a.fkeep, point-major -- the posterior object's buffer, whose blocks a.state_stride strides as well.
+template <int D, bool OSC, bool KEPT = false>
 __global__ __launch_bounds__(SS_THREADS) void ss_bfold_kernel(SSArgs a) {
+  constexpr int NC = D + D * (D + 1) / 2;
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const auto M = ss_lat_model<D, OSC>(a.lat[z]);
   const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
-  const double* stt = a.state + (size_t)z * a.state_stride;
+  const double* fst = (KEPT ? a.fkeep : a.state) + (size_t)z * a.state_stride;
   SSBwd<D> acc, el;
   double m[D], P[D][D];
   for (long long t = t0; t < t1; ++t) {
     const bool last = t == a.n - 1;
-    ss_load_state<D>(stt, a.n, 1, t, m, P);                   // component-major
+    ss_load_state<D>(fst, KEPT ? 1 : a.n, KEPT ? NC : 1, t, m, P);
     ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, t == t0 ? acc : el);
     if (t > t0) ss_bwd_combine<D>(acc, el, acc);
   }
   reinterpret_cast<SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j] = acc;
 }
 
-// FULL: the whole smoothed state (without the latent's mean) goes to a.sstate as well, and the filtered state it was computed from to
-// a.fkeep, both point-major; a.smean may be nullptr.  A second instantiation, so that the code of the first is what it was.
-// GX (a third, for the same reason): when the recursion steps from point t + 1 to point t it holds the filtered state of t and the
-// smoothed state of t + 1, which is all ss_input_grad takes: a.gdt[t + 1] = d lml / d (x_{t+1} - x_t), and a.gdt[0] = 0.  No state is
-// stored for it, and every entry of a.gdt is written by exactly one thread.
-template <int D, bool OSC, bool FULL = false, bool GX = false>
+// What the RTS replay writes.  MARGINALS: a.smean (+ the latent's mean) and a.svar.  FULL: the whole smoothed state (without the
+// latent's mean) goes to a.sstate as well, and the filtered state it was computed from to a.fkeep, both point-major (a point's
+// components side by side, which is how ss_interp_kernel reads them); a.smean may be nullptr.  GX: when the recursion steps from point
+// t + 1 to point t it holds the filtered state of t and the smoothed state of t + 1, which is all ss_input_grad takes: a.gdt[t + 1] =
+// d lml / d (x_{t+1} - x_t), and a.gdt[0] = 0; no state is stored for it, and every entry of a.gdt is written by exactly one thread.
+// KEPT (with ss_bfold_kernel<.., true>; DESIGN.md 4.18 "Appending observations"): the smoother over kept states -- the filtered states
+// are read from a.fkeep and only a.sstate is written; neither the data nor a.state is read, and no marginal is written.
+enum SSRts { SS_RTS_MARGINALS, SS_RTS_FULL, SS_RTS_GX, SS_RTS_KEPT };
+template <int D, bool OSC, SSRts V = SS_RTS_MARGINALS>
 __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
+  constexpr bool FULL = V == SS_RTS_FULL, GX = V == SS_RTS_GX, KEPT = V == SS_RTS_KEPT;
+  constexpr int NC = D + D * (D + 1) / 2;
   const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
   if (j >= a.nch) return;
   const SSLat& L = a.lat[z];
   const auto M = ss_lat_model<D, OSC>(L);
   const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
-  const double* stt = a.state + (size_t)z * a.state_stride;
+  const double* fst = (KEPT ? a.fkeep : a.state) + (size_t)z * a.state_stride;
+  double* sst = KEPT ? a.sstate + (size_t)z * a.state_stride : nullptr;
   double ms[D], Ps[D][D];
-  for (int i = 0; i < D; ++i) {       // the last chunk has no successor: its first element has E = 0 and ignores this state
-    ms[i] = 0.0;
+  for (int i = 0; i < D; ++i) {       // the last chunk has no successor: its first element has E = 0 and ignores this state.  (Written
+    ms[i] = 0.0;                      // out, as the prefix is in ss_filter_kernel: a loader changes the code of all twelve instantiations.)
     for (int k = 0; k < D; ++k) Ps[i][k] = 0.0;
   }
   if (j + 1 < a.nch) {
@@ -307,13 +343,13 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
       for (int k = 0; k < D; ++k) Ps[i][k] = suf.L[i][k];
     }
   }
-  double* sm = (!FULL || a.smean) ? a.smean + (size_t)z * a.n : nullptr;
-  double* sv = a.svar ? a.svar + (size_t)z * a.n : nullptr;
+  double* sm = (!KEPT && (!FULL || a.smean)) ? a.smean + (size_t)z * a.n : nullptr;
+  double* sv = (!KEPT && a.svar) ? a.svar + (size_t)z * a.n : nullptr;
   SSBwd<D> el;
   double m[D], P[D][D];
   for (long long t = t1 - 1; t >= t0; --t) {
     const bool last = t == a.n - 1;
-    ss_load_state<D>(stt, a.n, 1, t, m, P);                   // component-major
+    ss_load_state<D>(fst, KEPT ? 1 : a.n, KEPT ? NC : 1, t, m, P);
     ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, el);
     if constexpr (GX) {
       double* gd = a.gdt + (size_t)z * a.n;
@@ -321,139 +357,18 @@ __global__ __launch_bounds__(SS_THREADS) void ss_rts_kernel(SSArgs a) {
       if (t == 0) gd[0] = 0.0;
     }
     ss_rts_step<D>(el, ms, Ps);
-    if (!FULL || sm) sm[t] = ms[0] + L.mean;
-    if (sv) sv[t] = Ps[0][0];
-    if constexpr (FULL) {       // point-major: a point's components side by side, which is how ss_interp_kernel reads them
-      constexpr int NC = D + D * (D + 1) / 2;
-      double* sst = a.sstate + (size_t)z * a.state_stride + (size_t)t * NC;
-      double* fst = a.fkeep + (size_t)z * a.state_stride + (size_t)t * NC;
+    if constexpr (!KEPT) {
+      if (!FULL || sm) sm[t] = ms[0] + L.mean;
+      if (sv) sv[t] = Ps[0][0];
+    }
+    if constexpr (KEPT) ss_store_state<D>(sst, 1, NC, t, ms, Ps);
+    if constexpr (FULL) {       // both states entry by entry: two ss_store_state calls issue the stores in another order (other code)
+      double* so = a.sstate + (size_t)z * a.state_stride + (size_t)t * NC;
+      double* fo = a.fkeep + (size_t)z * a.state_stride + (size_t)t * NC;
       for (int i = 0; i < D; ++i) {
-        sst[i] = ms[i]; fst[i] = m[i];
-        for (int k = i; k < D; ++k) { sst[ss_sym_at(D, i, k)] = Ps[i][k]; fst[ss_sym_at(D, i, k)] = P[i][k]; }
+        so[i] = ms[i]; fo[i] = m[i];
+        for (int k = i; k < D; ++k) { so[ss_sym_at(D, i, k)] = Ps[i][k]; fo[ss_sym_at(D, i, k)] = P[i][k]; }
       }
-    }
-  }
-}
-
-// ---- appending observations (DESIGN.md 4.18 "Appending observations") -------------------------------------------------------------
-// Phases 1 and 3 of the filter over k new points whose predecessor is a stored state (L.init at input a.x0) instead of the prior: the
-// element of the first new point is ss_fwd_element_from, every other element and the scan are the filter's.  Kernels of their own, so
-// that the code of ss_fold_kernel and ss_filter_kernel is what it was.
-template <int D, bool OSC>
-__global__ __launch_bounds__(SS_THREADS) void ss_fold_from_kernel(SSFromArgs a) {
-  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
-  if (j >= a.nch) return;
-  const SSFromLat& L = a.lat[z];
-  const auto M = ss_lat_model<D, OSC>(L);
-  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
-  SSFwd<D> acc, el;
-  double xp = a.x[t0];
-  if (t0 == 0) {
-    double m0[D], P0[D][D];
-    ss_load_state<D>(L.init, 1, 0, 0, m0, P0);
-    ss_fwd_element_from<D>(M, xp - a.x0, m0, P0, L.w[0], L.r[0], acc);
-  } else ss_fwd_element<D>(M, false, xp - a.x[t0 - 1], L.w[t0], L.r[t0], acc);
-  for (long long t = t0 + 1; t < t1; ++t) {
-    const double xt = a.x[t];
-    ss_fwd_element<D>(M, false, xt - xp, L.w[t], L.r[t], el);
-    ss_fwd_combine<D>(acc, el, acc);
-    xp = xt;
-  }
-  reinterpret_cast<SSFwd<D>*>(a.agg)[(size_t)z * a.nch + j] = acc;
-}
-
-// Thread 0 starts the ordinary recursion from the stored state over x[0] - x0, every other thread from its prefix; the filtered states
-// go point-major to L.out (rows n .. n + k - 1 of the posterior object's block).  With one chunk this kernel alone is the filter.
-template <int D, bool OSC>
-__global__ __launch_bounds__(SS_THREADS) void ss_filter_from_kernel(SSFromArgs a) {
-  constexpr int NC = D + D * (D + 1) / 2;
-  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
-  if (j >= a.nch) return;
-  const SSFromLat& L = a.lat[z];
-  const auto M = ss_lat_model<D, OSC>(L);
-  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
-  double m[D], P[D][D];
-  if (j == 0) ss_load_state<D>(L.init, 1, 0, 0, m, P);
-  else {
-    const SSFwd<D>& pre = reinterpret_cast<const SSFwd<D>*>(a.agg)[(size_t)z * a.nch + j - 1];
-    for (int i = 0; i < D; ++i) {
-      m[i] = pre.b[i];
-      for (int k = 0; k < D; ++k) P[i][k] = pre.C[i][k];
-    }
-  }
-  double* fm = a.fmean ? a.fmean + (size_t)z * a.n : nullptr;
-  double* fv = a.fvar ? a.fvar + (size_t)z * a.n : nullptr;
-  double lp = 0.0;
-  double xp = t0 == 0 ? a.x0 : a.x[t0 - 1];
-  for (long long t = t0; t < t1; ++t) {
-    const double xt = a.x[t];
-    lp += ss_filter_step<D>(M, xt - xp, L.w[t], L.r[t], m, P);
-    xp = xt;
-    if (fm) fm[t] = m[0];
-    if (fv) fv[t] = P[0][0];
-    double* fst = L.out + (size_t)t * NC;
-    for (int i = 0; i < D; ++i) {
-      fst[i] = m[i];
-      for (int k = i; k < D; ++k) fst[ss_sym_at(D, i, k)] = P[i][k];
-    }
-  }
-  a.part[(size_t)z * a.nch + j] = lp;
-}
-
-// ss_bfold_kernel and ss_rts_kernel<.., FULL> over KEPT states: the filtered states are read point-major from a.fkeep (the posterior
-// object's buffer, latent z's block z * a.state_stride doubles in) and the full smoothed states go point-major to a.sstate; neither
-// the data nor the component-major a.state is read, and no marginal is written.  Kernels of their own, for the reason above.
-template <int D, bool OSC>
-__global__ __launch_bounds__(SS_THREADS) void ss_bfold_kept_kernel(SSArgs a) {
-  constexpr int NC = D + D * (D + 1) / 2;
-  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
-  if (j >= a.nch) return;
-  const auto M = ss_lat_model<D, OSC>(a.lat[z]);
-  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
-  const double* fst = a.fkeep + (size_t)z * a.state_stride;
-  SSBwd<D> acc, el;
-  double m[D], P[D][D];
-  for (long long t = t0; t < t1; ++t) {
-    const bool last = t == a.n - 1;
-    ss_load_state<D>(fst, 1, NC, t, m, P);                    // point-major
-    ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, t == t0 ? acc : el);
-    if (t > t0) ss_bwd_combine<D>(acc, el, acc);
-  }
-  reinterpret_cast<SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j] = acc;
-}
-
-template <int D, bool OSC>
-__global__ __launch_bounds__(SS_THREADS) void ss_rts_kept_kernel(SSArgs a) {
-  constexpr int NC = D + D * (D + 1) / 2;
-  const int j = blockIdx.x * SS_THREADS + threadIdx.x, z = blockIdx.z;
-  if (j >= a.nch) return;
-  const auto M = ss_lat_model<D, OSC>(a.lat[z]);
-  const auto [t0, t1] = ss_chunk_range(j, a.chunk, a.n);
-  const double* fst = a.fkeep + (size_t)z * a.state_stride;
-  double* sst = a.sstate + (size_t)z * a.state_stride;
-  double ms[D], Ps[D][D];
-  for (int i = 0; i < D; ++i) {       // the last chunk has no successor: its first element has E = 0 and ignores this state
-    ms[i] = 0.0;
-    for (int k = 0; k < D; ++k) Ps[i][k] = 0.0;
-  }
-  if (j + 1 < a.nch) {
-    const SSBwd<D>& suf = reinterpret_cast<const SSBwd<D>*>(a.bagg)[(size_t)z * a.nch + j + 1];
-    for (int i = 0; i < D; ++i) {
-      ms[i] = suf.g[i];
-      for (int k = 0; k < D; ++k) Ps[i][k] = suf.L[i][k];
-    }
-  }
-  SSBwd<D> el;
-  double m[D], P[D][D];
-  for (long long t = t1 - 1; t >= t0; --t) {
-    const bool last = t == a.n - 1;
-    ss_load_state<D>(fst, 1, NC, t, m, P);                    // point-major
-    ss_bwd_element<D>(M, last, last ? 0.0 : a.x[t + 1] - a.x[t], m, P, el);
-    ss_rts_step<D>(el, ms, Ps);
-    double* o = sst + (size_t)t * NC;
-    for (int i = 0; i < D; ++i) {
-      o[i] = ms[i];
-      for (int k = i; k < D; ++k) o[ss_sym_at(D, i, k)] = Ps[i][k];
     }
   }
 }
@@ -712,7 +627,7 @@ __global__ __launch_bounds__(256) void ss_window_kernel(const double* __restrict
   }
 }
 
-__device__ __forceinline__ double ss_window_input(const SSPostArgs& a, long long j) {
+__device__ __forceinline__ double ss_window_input(const SSWindowArgs& a, long long j) {
   const int s = a.src[j];
   return s >= 0 ? a.x[s] : a.xs[-1 - s];
 }
@@ -721,6 +636,10 @@ __device__ __forceinline__ double ss_window_input(const SSPostArgs& a, long long
 // training point is the stored one; that of a query is the stored one of training point k - 1, k = #{t : x_t <= q} = first + (j - its
 // index among the queries), predicted over q - x_{k-1} (the filter's step at an unobserved point), and (0, Pinf) when k = 0.
 // Reads fstate of points first - 1 .. first + count - 1 (>= 0) and sstate of point first + count (< n) only.
+// ss_lwindow_element below repeats the filtered state of a window point, and the four window kernels their walk over a run, on
+// purpose.  One window-point helper (a struct it fills, arrays it fills, or the shared text outside and the element in a lambda) costs
+// every window kernel 2 - 8 SGPRs (ss_ppath_kernel<3>: 51 -> 58, ss_lfilter_kernel<1>: 66 -> 74), and one walk taking the body as a
+// lambda costs ss_pfold_kernel 2 - 4 VGPRs besides (Matern52: 208 -> 212).
 template <int D, typename Mod>
 __device__ __forceinline__ void ss_window_element(const SSPostArgs& a, const SSPostLat& L, const Mod& M, long long j, double xj, double xn,
                                                   SSAff<D>& e) {
@@ -821,11 +740,6 @@ __global__ __launch_bounds__(SS_THREADS) void ss_ppath_kernel(SSPostArgs a) {
 // from the right: ss_lfold_kernel, the suffix scan of SSFwd<D> with FwdRevOp, ss_lfilter_kernel, and ss_finish_kernel adds the
 // partials.  A training point of the window is an unobserved step; a query carries (w, r) of the front end, indexed through src.
 
-__device__ __forceinline__ double ss_lwindow_input(const SSLpdfArgs& a, long long j) {
-  const int s = a.src[j];
-  return s >= 0 ? a.x[s] : a.xs[-1 - s];
-}
-
 // The backward element of window point j (input xj, its successor's input xn; xn is not read at the last point) and the point's noise
 // and data.  The filtered state is taken as ss_window_element takes it; the last point's element is ss_chain_start.  Reads fstate of
 // points first - 1 .. first + count - 1 (>= 0) and sstate of point first + count (< n) only, and w, r of the queries.
@@ -887,9 +801,9 @@ __global__ __launch_bounds__(SS_THREADS) void ss_lfold_kernel(SSLpdfArgs a) {
   const long long j1 = j0 + a.chunk < a.W ? j0 + a.chunk : a.W;
   SSFwd<D> acc, fe;
   SSBwd<D> el;
-  double xn = j1 < a.W ? ss_lwindow_input(a, j1) : 0.0;
+  double xn = j1 < a.W ? ss_window_input(a, j1) : 0.0;
   for (long long j = j1 - 1; j >= j0; --j) {
-    const double xj = ss_lwindow_input(a, j);
+    const double xj = ss_window_input(a, j);
     double w, r;
     ss_lwindow_element<D>(a, L, M, j, xj, xn, el, w, r);
     ss_fwd_element_affine<D>(el.E, el.g, el.L, w, r, j == j1 - 1 ? acc : fe);
@@ -923,9 +837,9 @@ __global__ __launch_bounds__(SS_THREADS) void ss_lfilter_kernel(SSLpdfArgs a) {
   }
   SSBwd<D> el;
   double lp = 0.0;
-  double xn = j1 < a.W ? ss_lwindow_input(a, j1) : 0.0;
+  double xn = j1 < a.W ? ss_window_input(a, j1) : 0.0;
   for (long long j = j1 - 1; j >= j0; --j) {
-    const double xj = ss_lwindow_input(a, j);
+    const double xj = ss_window_input(a, j);
     double w, r;
     ss_lwindow_element<D>(a, L, M, j, xj, xn, el, w, r);
     lp += ss_chain_step<D>(el, w, r, m, P);
@@ -967,6 +881,21 @@ void ss_phases(void (*fold)(Args), void (*restart)(Args), const Args& a, int ny,
   hipLaunchKernelGGL(restart, grid, dim3(SS_THREADS), 0, st, a);
 }
 
+// Filter-shaped phases over SSFwd<D> with a log-density finish: lml[l] (device, nullptr: none) = the sum of latent l's partials.  One
+// chunk: thread 0 of the restart is the whole sequential filter, no aggregate is read, and a latent's one partial is its log density:
+// one launch in all.  (launch_ss_filter does not come here: its launch sequence is fold, scan, filter, finish whatever nch is.)
+template <int D, typename Op, bool REV, typename Args>
+void ss_scored_phases(void (*fold)(Args), void (*restart)(Args), const Args& a, int nb, double* lml, hipStream_t st) {
+  if (a.nch == 1) {
+    Args b = a;
+    if (lml) b.part = lml;
+    hipLaunchKernelGGL(restart, dim3(1, 1, nb), dim3(SS_THREADS), 0, st, b);
+    return;
+  }
+  ss_phases<D, SSFwd<D>, Op, REV>(fold, restart, a, 1, nb, a.agg, st);
+  if (lml) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
+}
+
 }  // namespace
 
 int ss_model_of(int kind) {
@@ -997,8 +926,8 @@ void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st) {
   ss_dispatch(model, [&](auto t) {
     typedef decltype(t) T;
     ss_phases<T::D, SSBwd<T::D>, BwdOp, true>(ss_bfold_kernel<T::D, T::OSC>,
-                                              a.sstate ? ss_rts_kernel<T::D, T::OSC, true>
-                                                       : a.gdt ? ss_rts_kernel<T::D, T::OSC, false, true> : ss_rts_kernel<T::D, T::OSC>,
+                                              a.sstate ? ss_rts_kernel<T::D, T::OSC, SS_RTS_FULL>
+                                                       : a.gdt ? ss_rts_kernel<T::D, T::OSC, SS_RTS_GX> : ss_rts_kernel<T::D, T::OSC>,
                                               a, 1, nb, a.bagg, st);
   });
 }
@@ -1006,20 +935,15 @@ void launch_ss_smooth(const SSArgs& a, int model, int nb, hipStream_t st) {
 void launch_ss_filter_from(const SSFromArgs& a, int model, int nb, double* lml, hipStream_t st) {
   ss_dispatch(model, [&](auto t) {
     typedef decltype(t) T;
-    if (a.nch == 1) {     // one chunk: thread 0 of the restart is the whole sequential filter, no aggregate is read, and a latent's
-      SSFromArgs b = a;   // one partial is its log density: one launch in all
-      if (lml) b.part = lml;
-      hipLaunchKernelGGL((ss_filter_from_kernel<T::D, T::OSC>), dim3(1, 1, nb), dim3(SS_THREADS), 0, st, b);
-    } else
-      ss_phases<T::D, SSFwd<T::D>, FwdOp, false>(ss_fold_from_kernel<T::D, T::OSC>, ss_filter_from_kernel<T::D, T::OSC>, a, 1, nb, a.agg, st);
+    ss_scored_phases<T::D, FwdOp, false>(ss_fold_kernel<T::D, T::OSC, double, SSFromArgs>, ss_filter_kernel<T::D, T::OSC, double, SSFromArgs>,
+                                         a, nb, lml, st);
   });
-  if (lml && a.nch > 1) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
 }
 
 void launch_ss_smooth_kept(const SSArgs& a, int model, int nb, hipStream_t st) {
   ss_dispatch(model, [&](auto t) {
     typedef decltype(t) T;
-    ss_phases<T::D, SSBwd<T::D>, BwdOp, true>(ss_bfold_kept_kernel<T::D, T::OSC>, ss_rts_kept_kernel<T::D, T::OSC>, a, 1, nb, a.bagg, st);
+    ss_phases<T::D, SSBwd<T::D>, BwdOp, true>(ss_bfold_kernel<T::D, T::OSC, true>, ss_rts_kernel<T::D, T::OSC, SS_RTS_KEPT>, a, 1, nb, a.bagg, st);
   });
 }
 
@@ -1060,14 +984,8 @@ void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st)
 void launch_ss_post_logpdf(const SSLpdfArgs& a, int model, int nb, double* lml, hipStream_t st) {
   ss_dispatch(model, [&](auto t) {
     typedef decltype(t) T;
-    if (a.nch == 1) {     // one chunk: thread 0 of the restart is the whole sequential filter, no aggregate is read, and a latent's
-      SSLpdfArgs b = a;   // one partial is its log density: one launch in all
-      b.part = lml;
-      hipLaunchKernelGGL((ss_lfilter_kernel<T::D, T::OSC>), dim3(1, 1, nb), dim3(SS_THREADS), 0, st, b);
-    } else
-      ss_phases<T::D, SSFwd<T::D>, FwdRevOp, true>(ss_lfold_kernel<T::D, T::OSC>, ss_lfilter_kernel<T::D, T::OSC>, a, 1, nb, a.agg, st);
+    ss_scored_phases<T::D, FwdRevOp, true>(ss_lfold_kernel<T::D, T::OSC>, ss_lfilter_kernel<T::D, T::OSC>, a, nb, lml, st);
   });
-  if (a.nch > 1) hipLaunchKernelGGL(ss_finish_kernel, dim3(nb), dim3(SS_THREADS), 0, st, (const double*)a.part, a.nch, lml);
 }
 
 void launch_ss_interp(const SSInterpArgs& a, int model, int nb, hipStream_t st) {

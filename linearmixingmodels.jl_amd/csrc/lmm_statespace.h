@@ -100,6 +100,15 @@ SS_HD void ss_load_state(const double* st, size_t comp_stride, size_t point_stri
     for (int k = i; k < D; ++k) P[i][k] = P[k][i] = f[(size_t)ss_sym_at(D, i, k) * comp_stride];
   }
 }
+// its counterpart: m and the upper triangle of P become the stored state of point t
+template <int D>
+SS_HD void ss_store_state(double* st, size_t comp_stride, size_t point_stride, long long t, const double m[D], const double P[D][D]) {
+  double* f = st + (size_t)t * point_stride;
+  for (int i = 0; i < D; ++i) {
+    f[(size_t)i * comp_stride] = m[i];
+    for (int k = i; k < D; ++k) f[(size_t)ss_sym_at(D, i, k) * comp_stride] = P[i][k];
+  }
+}
 
 template <int D, typename Sc = double>
 struct SSModel {

@@ -1,6 +1,12 @@
 """Compare the rocprofv3 --kernel-trace CSVs under two output directories: python tools/compare_kernel_traces.py DIR_A DIR_B
-Equal means the same multiset of (kernel, grid, workgroup, LDS bytes) and, queue by queue, the same sequence of them."""
-import collections, csv, glob, sys
+Equal means the same multiset of (kernel, grid, workgroup, LDS bytes) and, queue by queue, the same sequence of them.
+--rename REGEX=REPL (repeatable, behind the directories): a kernel name of DIR_A is read as re.sub(REGEX, REPL, name), for kernels
+that DIR_B's build renamed or merged.  --ignore REGEX: dispatches whose kernel name matches are counted and left out of both
+comparisons (the HIP runtime's own copy kernels, __amd_rocclr_*: how it splits a copy from pageable host memory is not the library's doing)."""
+import collections, csv, glob, re, sys
+
+RENAMES = [tuple(sys.argv[i + 1].split("=", 1)) for i in range(3, len(sys.argv) - 1) if sys.argv[i] == "--rename"]
+IGNORE = [sys.argv[i + 1] for i in range(3, len(sys.argv) - 1) if sys.argv[i] == "--ignore"]
 
 
 def load(d):
@@ -17,6 +23,13 @@ def key(r):
 
 
 a, fa = load(sys.argv[1]); b, fb = load(sys.argv[2])
+for r in a:
+    for rx, repl in RENAMES:
+        r["Kernel_Name"] = re.sub(rx, repl, r["Kernel_Name"])
+for rx in IGNORE:
+    na, nb = len(a), len(b)
+    a, b = [r for r in a if not re.search(rx, r["Kernel_Name"])], [r for r in b if not re.search(rx, r["Kernel_Name"])]
+    print(f"ignored {rx}: {na - len(a)} dispatches of the parent, {nb - len(b)} of this build")
 print("columns:", ", ".join(a[0].keys()))
 ok = True
 ca, cb = collections.Counter(map(key, a)), collections.Counter(map(key, b))

@@ -11,7 +11,10 @@ The inputs are those of the existing tests (tests/test_gpu_statespace.py `proble
 `complete_problem` with the SHO latent) at n = 1, 63, 333 and 5000 (two plans of the scan: 16 and 64 points per thread): statespace_logpdf with
 and without the regulariser, statespace_mean_and_var at the training inputs and at new ones, statespace_posterior with its logpdf,
 mean_and_var, mean_and_var_vjp, window and rand at the queries of the tests, statespace_logpdf_and_gradient without and with the
-inputs, and statespace_rand of the prior and of the posterior."""
+inputs, and statespace_rand of the prior and of the posterior.  Where the build has them: predictive_logpdf at those queries (ys with
+NaN holes; the handle's sigma2 and an explicit one); append in three steps (k = 1, the single launch; k = 17, two chunks of the default
+plan; one more point than the capacity holds, which grows the buffers) with every query taken again afterwards, smoothed lazily and
+after an explicit smooth(); and the building blocks that take `chunk` at chunk = 1 (`blocks`)."""
 import os
 import subprocess
 import sys
@@ -78,7 +81,76 @@ def child(out_path):
             rec(f"{t} rand prior", lmm.statespace_rand(np.random.default_rng(n + 1), fx, None, 2))
             rec(f"{t} rand posterior", lmm.statespace_rand(np.random.default_rng(n + 2), fx, y, 2))
             rec(f"{t} rand posterior xs", lmm.statespace_rand(np.random.default_rng(n + 3), fx, y, None, True, Q))
+            if not hasattr(probe, "lmm_oilmm_statespace_post_logpdf"):
+                continue
+            rng = np.random.default_rng([n, 11])
+            Yq = rng.standard_normal((p, len(Q)))
+            Yq[0, ::3] = np.nan
+            Yq[:, 1] = np.nan                                    # one query with nothing observed
+            yq = np.ascontiguousarray(Yq).reshape(-1)
+
+            def answers(post, label):
+                rec(f"{t} {label} mean_and_var", post.mean_and_var(Q))
+                rec(f"{t} {label} vjp", post.mean_and_var_vjp(Q, np.ones(len(Q) * p), np.linspace(-1.0, 1.0, len(Q) * p)))
+                rec(f"{t} {label} rand", post.rand(np.random.default_rng(n), Q, 3))
+                rec(f"{t} {label} predictive_logpdf", post.predictive_logpdf(Q, yq))
+                rec(f"{t} {label} predictive_logpdf sigma2", post.predictive_logpdf(Q, yq, sigma2=0.37))
+
+            for explicit in (False, True):                       # the same appends; the queries smooth lazily, or after post.smooth()
+                with lmm.statespace_posterior(fx, y) as post:
+                    if not explicit:
+                        answers(post, "posterior")
+                    for step, k in enumerate((1, 17, None)):     # one chunk (the single launch); two chunks of the default plan; a growth
+                        k = post.capacity - post.n + 1 if k is None else k
+                        xn = float(np.max(x)) + step * 100.0 + np.cumsum(rng.uniform(0.05, 0.4, k))     # behind everything so far
+                        Yn = rng.standard_normal((p, k))
+                        Yn[0, ::4] = np.nan
+                        cap = post.capacity
+                        rec(f"{t} append {step} smooth={explicit}", [post.append(xn, np.ascontiguousarray(Yn).reshape(-1)), post.logpdf])
+                        if step == 2:
+                            assert post.capacity > cap, (post.capacity, cap)
+                    if explicit:
+                        post.smooth()
+                    answers(post, f"appended smooth={explicit}")
+    blocks(lmm, probe, rec)
     np.savez(out_path, **out)
+
+
+def blocks(lmm, probe, rec):
+    """The building blocks that take `chunk`, one latent of each model at chunk = 1: lengths 1 (one chunk), 2 (a prefix, one workgroup
+    of the scan) and 130 (two workgroups at 128 aggregates each, three at 64, so ss_addprefix_kernel runs).  For the two blocks over a
+    window the length is the window's: W = 1, 2 and 129 over the states of 130 points."""
+    import test_gpu_statespace_append as GA
+    import test_gpu_statespace_post_rand as GR
+    import test_gpu_statespace_posterior as PP
+    import test_gpu_statespace_predictive_logpdf as GL
+    import test_sho_abi as S
+    import test_statespace_abi as T
+    import test_statespace_posterior_abi as PA
+    have = lambda name: hasattr(probe, name)
+    for lat in tuple(T.KINDS) + (("sho", S.QS[0]),):
+        model = PA.model_of(lat, 0.9, 1.3) if lat in T.KINDS else S.sho(0.9, 1.7, lat[1])
+        D = model.D
+        for n in (1, 2, 130):
+            rng = np.random.default_rng([n, 13])
+            x, w, r = np.cumsum(rng.uniform(0.05, 0.6, n)), rng.uniform(0.1, 0.5, n), rng.standard_normal(n)
+            if n > 2:
+                w[n // 2] = np.inf
+            t = f"block {lat} n={n} chunk=1"
+            if have("lmm_dev_statespace_filter_from"):
+                rec(f"{t} filter_from", list(GA.gpu_filter_from(lmm, model, np.full(D, 0.3), 0.5 * np.eye(D), x[0] - 0.2, x, w, r, 1)))
+            fs, ss = PP.gpu_states(lmm, model, x, w, r, 1)
+            rec(f"{t} states", [fs, ss])
+        mid = 0.5 * (x[:-1] + x[1:])                             # x, fs, ss: the 130 points
+        for W, q in ((1, mid[40:41]), (2, np.array([mid[40], mid[40] + 1e-3])), (129, mid[:65])):
+            rng = np.random.default_rng([W, 17])
+            t = f"block {lat} W={W} chunk=1"
+            if have("lmm_dev_statespace_post_sample"):
+                rec(f"{t} post_sample", GR.gpu_post_sample(lmm, model, x, fs, ss, q, rng.standard_normal((2, D * W)), 1))
+            if have("lmm_dev_statespace_post_logpdf"):
+                ws = rng.uniform(0.1, 0.5, len(q))
+                ws[len(q) // 2] = np.inf if len(q) > 2 else ws[len(q) // 2]
+                rec(f"{t} post_logpdf", GL.gpu_window_logpdf(lmm, model, x, fs, ss, q, ws, rng.standard_normal(len(q)), 1))
 
 
 def main():
