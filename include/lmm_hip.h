@@ -1067,7 +1067,9 @@ int lmm_dev_emul_plan(int NR, int NC, int nb, long long* out, int cap);
  *           names the step's (M, N, K) = ([4], [3], [2]); [7] work and [8] bytes booked for the class, as the bits of a double;
  *           [9] first_done (region: its first diagonal block is already factored); [10] fused_bulk (update + leaf: the next panel's
  *           bulk rows ride in the launch); [11] a ragged last 64 rows: 0 none, 1 as items of the launch, 2 as a launch of their own;
- *           [12] matrices per group and [13] scratch bytes of an emulated update.
+ *           [12] matrices per group and [13] scratch bytes of an emulated update; of an update + leaf (kind 5), [12] is 1 when the
+ *           step is screened (lmm_dev_set_f64_screen): its panel's row maxima are scanned and kept, and its launch leaves out the
+ *           128 x 128 tiles, from tile column 1 on, whose update cannot change a bit of C.
  * Returns the number of steps (those beyond cap are counted, not written), or -LMM_ERR_ARG. */
 #define LMM_POTRF_PLAN_HEADER 8
 #define LMM_POTRF_PLAN_STEP 14
@@ -1121,6 +1123,24 @@ int lmm_dev_emul_last_live_tiles(void);
  * finite, and one of them is zero or ceil(log2 K) + e_i + e_j + 56 <= ilogb(c[i]) with e = ceil(log2 |rowmax|); 0 otherwise.  Then
  * the update the emulation would subtract is below a quarter of the spacing of the doubles under |c[i]|, and c[i] keeps its bits. */
 int lmm_dev_emul_negligible(int K, const double* rowmax_i, const double* rowmax_j, const double* c, int count, int* out);
+/* The same screen in front of the f64 update launches (switches LMM_F64_SCREEN, LMM_F64_SCREEN_MINK, LMM_F64_SCREEN_VOTE,
+ * LMM_F64_SCREEN_ROUNDS, read once).  By default an update on the f64 kernel is screened when K >= 512, it has more than one tile
+ * column and its launch has more work items than one round of two workgroups per CU.  Test hook: on = 0 / 1; EVERY update on the f64
+ * kernel with K >= min_k >= 128 and more than one tile column is screened, whatever its size; on < 0 goes back to the defaults.  A
+ * skipped tile's update would not have changed a bit of C: results do not depend on it. */
+int lmm_dev_set_f64_screen(int on, int min_k);
+/* Test hook: LMM_DETERMINISTIC (read once) -- on != 0: no split-K atomics in the update launches, so sums are bitwise reproducible. */
+int lmm_dev_set_deterministic(int on);
+/* Test hook: on != 0 makes every later factorisation copy its screened updates' counters to the host (this synchronises its stream).
+ * out (cap records of 5 ints; may be NULL with cap = 0): for every screened update of the last factorisation of the process, in
+ * launch order: M, N, K, the dead tiles its screen counted, 1 when the screen did its work (0: the first screened update found no
+ * dead tile and this one returned at entry).  Returns the number of records (those beyond cap are counted, not written), or -LMM_ERR_ARG. */
+int lmm_dev_f64_screen_stats(int on, int* out, int cap);
+/* The scan and the screen of ONE f64 update C[MxN] -= A[MxK] A[0:N, :]^T (column-major, device pointers; M >= N > 128, M >= 256, K a
+ * multiple of 128), as a screened step of a factorisation runs them.  flags (host, ceil(M / 128) x ceil(N / 128) bytes, row-major over
+ * (tile row, tile column)): for 1 <= tile column <= tile row, 1 when some entry i >= j of the tile is not negligible
+ * (lmm_dev_emul_negligible), 0 when the tile is dead; 0xFF elsewhere (never written).  *dead = the dead tiles the screen counted. */
+int lmm_dev_f64_screen_flags(const double* C, int ldc, const double* A, int lda, int M, int N, int K, unsigned char* flags, int* dead);
 /* Host-only (no GPU, no lmm_init needed): the reduction of the emulation's GEMM epilogue on `count` int32 accumulators |x| <= 2^28:
  * out[i * nmod + t] = x[i] modulo the t-th modulus as an int8 (congruent, inside the symmetric range).  exhaustive (may be NULL, 2
  * words): its float step run on every folded value it can see, every modulus: [0] cases, [1] failures. */

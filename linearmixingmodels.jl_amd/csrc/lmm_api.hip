@@ -802,6 +802,9 @@ struct Batch {
 
 static int g_in_flight = 1;       // batches that run concurrently on the slot streams (fork_slots / join_slots)
 static int g_emul_amax_reuse = 1; // lmm_dev_set_emul_amax_reuse: 0 = every emulated update scans its whole panel for the row maxima
+// lmm_dev_f64_screen_stats: with g_f64_screen_stats on, every factorisation ends by copying its screened steps' counters here (M, N, K, dead tiles, ran)
+static int g_f64_screen_stats = 0;
+static std::vector<int> g_f64_screen_last;
 // The emulation side of a Float64 factorisation's plan, whatever path and base case the other switches choose (lmm_dev_emul_plan, batch_plan)
 static PotrfPlan emul_view(int NR, int NC, int nb) {
   FactorSwitches sw = factor_switches();
@@ -870,8 +873,29 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
   // Row maxima of the emulated updates: one array per emulated step, [matrix][NR], kept until the API call ends like W2 -- a later
   // update whose panel contains an earlier one's reads its maxima there instead of scanning those columns again (emul_amax_cover)
   std::vector<unsigned long long*> amax_kept(P.steps.size(), nullptr);
-  for (size_t i = 0; i < P.steps.size(); ++i)
-    if (P.steps[i].kind == POTRF_EMUL_UPDATE_LEAF) amax_kept[i] = reinterpret_cast<unsigned long long*>(call_scratch((size_t)B.nb * NR));
+  // A screened f64 update (PotrfStep.screened) scans its panel the same way and keeps its array too; its screen leaves
+  // one flag byte per 128 x 128 tile in a block of this batch's own, sized for the step that needs most and rewritten by every
+  // screened step in stream order, and two counters per step (dead tiles; 1 when the screen ran), zeroed here.  The dead count of
+  // the first screened step with at least LMM_F64_SCREEN_VOTE_NT tile columns is the vote: zero there and the later scans and
+  // screens of this factorisation return at entry (decaying data has dead tiles from the third or fourth tile column on; a
+  // narrower update finds none either way and says nothing).
+  size_t scr_bytes = 0;
+  int scr_vote = -1;
+  for (size_t i = 0; i < P.steps.size(); ++i) {
+    const PotrfStep& s = P.steps[i];
+    if (s.kind == POTRF_EMUL_UPDATE_LEAF || (s.kind == POTRF_UPDATE_LEAF && s.screened)) amax_kept[i] = reinterpret_cast<unsigned long long*>(call_scratch((size_t)B.nb * NR));
+    if (s.kind == POTRF_UPDATE_LEAF && s.screened) {
+      scr_bytes = std::max(scr_bytes, f64_screen_flag_bytes(s.M, s.N, s.strip, B.nb));
+      if (scr_vote < 0 && (s.N + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE >= LMM_F64_SCREEN_VOTE_NT) scr_vote = (int)i;
+    }
+  }
+  unsigned char* scr_flags = nullptr;
+  int* scr_stat = nullptr;
+  if (scr_bytes > 0) {
+    scr_flags = reinterpret_cast<unsigned char*>(call_scratch(scr_bytes / 8));
+    scr_stat = reinterpret_cast<int*>(call_scratch(P.steps.size()));
+    HIPCHK(hipMemsetAsync(scr_stat, 0, P.steps.size() * 2 * sizeof(int), st));
+  }
   // live K blocks and dead pieces of the emulated updates' panels (lmm_emul.h): sized for the deepest update, rewritten by every
   // group of every update in stream order.  Block maxima: ONE array for the factorisation, [matrix][128-column block][NR], up to the
   // last column an emulated panel holds; the scan of an update writes the blocks it reads, a later update that covers them
@@ -907,9 +931,25 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
       case POTRF_UPDATE: launch_gemm_nt(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, B.A, offA, ld, s.M, s.N, s.h, 1, false, B.nb, st); break;
       case POTRF_LEAF128: leaf128(j0); break;
       case POTRF_PANEL_BULK: launch_panel_bulk(B.A, W2, ld, NR, j0, B.nb, st); break;
-      case POTRF_UPDATE_LEAF:
-        launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, s.h, s.N, n_real, B.nb, st, s.strip, s.fused_bulk ? nflags : nullptr, (int)P.node_flag_ints);
+      case POTRF_UPDATE_LEAF: {
+        const unsigned char* scr = nullptr;
+        if (s.screened) {
+          const int si = (int)(&s - P.steps.data());
+          const size_t fb = f64_screen_flag_bytes(s.M, s.N, s.strip, B.nb);
+          if (fb > scr_bytes || r0 + s.M > NR || s.N > f64_screen_rows(s.M, s.strip))
+            throw fail(LMM_ERR_ARG, "internal extent check failed: screened update %d x %d at row %d needs %zu flag bytes, has %zu, of %d rows", s.M, s.N, r0, fb, scr_bytes, NR);
+          guard_extent(scr_flags, fb / 8, fb / 8, 1, false, "screened update (tile flags)");
+          guard_extent(scr_stat, P.steps.size(), P.steps.size(), 1, false, "screened update (counters)");
+          const EmulCover cov = emul_amax_cover(P.steps, si, g_emul_amax_reuse != 0, true);
+          EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0, nullptr, j0 / 128, 0};
+          for (int q = 0; q < cov.n; ++q) keep.src[q] = amax_kept[cov.step[q]];
+          const int* vote = (sw.f64_screen_vote && scr_vote >= 0 && si > scr_vote) ? scr_stat + 2 * scr_vote : nullptr;
+          HIPCHK(launch_f64_screen(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, s.strip, B.nb, keep, scr_flags, scr_stat + 2 * si, vote, st));
+          scr = scr_flags;
+        }
+        launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, s.h, s.N, n_real, B.nb, st, s.strip, s.fused_bulk ? nflags : nullptr, (int)P.node_flag_ints, scr);
         break;
+      }
       case POTRF_EMUL_UPDATE_LEAF:
         if (s.scratch > P.emul_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", s.scratch, P.emul_bytes);
         guard_extent(emul_blk, s.scratch / 8, s.scratch / 8, 1, false, "emulated update (scratch)");
@@ -931,6 +971,17 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
         leaf128(r0);
         break;
       case POTRF_REGION: launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst); break;
+    }
+  }
+  if (g_f64_screen_stats) {      // test hook only: synchronises the stream
+    g_f64_screen_last.clear();
+    if (scr_stat != nullptr) {
+      std::vector<int> h(P.steps.size() * 2);
+      HIPCHK(hipMemcpyAsync(h.data(), scr_stat, h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (size_t i = 0; i < P.steps.size(); ++i)
+        if (P.steps[i].kind == POTRF_UPDATE_LEAF && P.steps[i].screened)
+          for (int v : {P.steps[i].M, P.steps[i].N, P.steps[i].h, h[2 * i], h[2 * i + 1]}) g_f64_screen_last.push_back(v);
     }
   }
 }
@@ -6428,6 +6479,68 @@ int lmm_dev_set_f64_emul(int on, int min_k, int nmod) {
   g_switches.emul_on = on ? 1 : 0; g_switches.emul_mink = min_k; g_switches.emul_nmod = nmod;
   return LMM_OK;
 }
+// Test hook of the f64 updates' screen (the env values LMM_F64_SCREEN, LMM_F64_SCREEN_MINK, LMM_F64_SCREEN_ROUNDS are read once):
+// on = 0 / 1; every update on the f64 kernel with K >= min_k >= 128 and more than one tile column is screened, whatever its size
+// (f64_screen_pays is off, as with an explicit LMM_F64_SCREEN_MINK); on < 0 goes back to the defaults (on, K >= 512, launches of more
+// than one round).
+int lmm_dev_set_f64_screen(int on, int min_k) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  (void)factor_switches();      // the environment first, so that a later first read does not undo this
+  if (on < 0) { const FactorSwitches d; g_switches.f64_screen = d.f64_screen; g_switches.f64_screen_mink = d.f64_screen_mink; g_switches.f64_screen_rounds = d.f64_screen_rounds; return LMM_OK; }
+  if (min_k < 128) return fail(LMM_ERR_ARG, "lmm_dev_set_f64_screen: min_k >= 128");
+  g_switches.f64_screen = on ? 1 : 0; g_switches.f64_screen_mink = min_k; g_switches.f64_screen_rounds = 0;
+  return LMM_OK;
+}
+// Test hook: FactorSwitches.deterministic (LMM_DETERMINISTIC, read once): no split-K atomics in the update launches.
+int lmm_dev_set_deterministic(int on) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  (void)factor_switches();
+  g_switches.deterministic = on ? 1 : 0;
+  return LMM_OK;
+}
+// Test hook: on != 0 makes every factorisation copy its screened updates' counters to the host when its launches are issued (that
+// synchronises its stream).  out (may be NULL when cap = 0): 5 ints per screened update of the LAST factorisation of this process, in
+// launch order: M, N, K, dead tiles the screen counted, 1 when the screen did its work (0: the vote made it return at entry).
+// Returns the number of screened updates (those beyond cap are counted, not written).
+int lmm_dev_f64_screen_stats(int on, int* out, int cap) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (cap < 0 || (cap > 0 && !out)) return -fail(LMM_ERR_ARG, "lmm_dev_f64_screen_stats: bad arguments");
+  g_f64_screen_stats = on ? 1 : 0;
+  const int n = (int)(g_f64_screen_last.size() / 5);
+  for (int i = 0; i < n && i < cap; ++i)
+    for (int q = 0; q < 5; ++q) out[5 * i + q] = g_f64_screen_last[5 * i + q];
+  return n;
+}
+// Scan + screen of ONE f64 update shape on the caller's device memory, as a screened step of a factorisation runs them: C (M x N, ldc;
+// the region), A (M x K, lda; its panel, whose first N rows are the B operand).  flags (host, MT x NT bytes, MT = ceil(M / 128), NT =
+// ceil(N / 128); row-major over (tile row, tile column)): the bytes of the rest tiles 1 <= tj <= ti as the screen stored them, 0xFF
+// elsewhere.  *dead = the count the screen kept.
+int lmm_dev_f64_screen_flags(const double* C, int ldc, const double* A, int lda, int M, int N, int K, unsigned char* flags, int* dead) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!C || !A || !flags || !dead || ldc < M || lda < M || M < N || N <= 128 || M < 256 || K < 128 || (K % 128) != 0 || K > 16384) return fail(LMM_ERR_ARG, "bad arguments");
+  guard_extent(C, M, ldc, N, false, "lmm_dev_f64_screen_flags (C)"); guard_extent(A, M, lda, K, false, "lmm_dev_f64_screen_flags (A)");
+  const size_t fb = f64_screen_flag_bytes(M, N, POTRF_STRIP_NONE, 1);
+  unsigned char* dflags = reinterpret_cast<unsigned char*>(call_scratch(fb / 8));
+  int* stat = reinterpret_cast<int*>(call_scratch(1));
+  unsigned long long* amax = reinterpret_cast<unsigned long long*>(call_scratch((size_t)M));
+  hipStream_t st = g.streams[0];
+  HIPCHK(hipMemsetAsync(dflags, 0xFF, fb, st));
+  HIPCHK(hipMemsetAsync(stat, 0, 2 * sizeof(int), st));
+  BatchPtr Cb{}, Pb{};
+  Cb.p[0] = const_cast<double*>(C); Pb.p[0] = const_cast<double*>(A);
+  EmulAmaxKeep keep{amax, M, 0, 0, {}, 0, nullptr, 0, 0};
+  HIPCHK(launch_f64_screen(Cb, 0, ldc, Pb, 0, lda, M, N, K, POTRF_STRIP_NONE, 1, keep, dflags, stat, nullptr, st));
+  const int MT = (M + 127) / 128, NT = (N + 127) / 128;
+  HIPCHK(hipMemcpyAsync(flags, dflags, (size_t)MT * NT, hipMemcpyDeviceToHost, st));
+  int hs[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(hs, stat, sizeof(hs), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  *dead = hs[0];
+  return LMM_OK;
+  LMM_CATCH
+}
 // Test hook of the shape rule that decides when nothing explicit is set (emul_pays): updates with K >= min_k_always are emulated, those
 // with min_k_shape <= K < min_k_always when nb * outputs >= min_outputs; min_k_always < 0 goes back to the defaults.
 int lmm_dev_set_f64_emul_rule(int min_k_always, int min_k_shape, double min_outputs) {
@@ -6483,7 +6596,7 @@ int lmm_dev_potrf_plan(int NR, int NC, int nb, int rows_real, int in_flight, int
     long long* r = out + LMM_POTRF_PLAN_HEADER + LMM_POTRF_PLAN_STEP * i;
     r[0] = s.kind; r[1] = s.j0; r[2] = s.h; r[3] = s.N; r[4] = s.M; r[5] = s.cls; r[6] = s.named();
     memcpy(&r[7], &s.work, 8); memcpy(&r[8], &s.bytes, 8);
-    r[9] = s.first_done; r[10] = s.fused_bulk; r[11] = s.strip; r[12] = s.group; r[13] = (long long)s.scratch;
+    r[9] = s.first_done; r[10] = s.fused_bulk; r[11] = s.strip; r[12] = s.kind == POTRF_UPDATE_LEAF ? (long long)s.screened : s.group; r[13] = (long long)s.scratch;
   }
   return (int)P.steps.size();
 }

@@ -200,7 +200,17 @@ LMM_HD inline bool emul_block_live(unsigned long long row, unsigned long long bl
 // bit is the binade that a rounding of ldexp into the subnormals may use up, so 56 is what the code as written needs.)  An all-zero row gives X = 0 and
 // T = 0 exactly.  A row with a NaN or an infinity is never negligible: its scale is NaN and must reach row i and column j of C.
 // C_ij = +-0 counts as live (0 - T = -T), and so do an infinite or NaN C_ij (kept out of the argument, they cost nothing).
-// The kernel's screen and the host entry lmm_dev_emul_negligible both decide through emul_negligible.
+// The f64 kernel (potrf_node_kernel, screened by f64_screen_kernel with the same predicate and margin).  It forms acc = sum_k a_ik a_jk
+// by f64 MFMAs -- fused multiply-adds, one rounding per term, in some order -- over the K columns of the panel or, with split-K, over
+// a part of them, and stores fl(C_ij - acc), or adds -acc to C_ij atomically once per part.  |a_ik| <= 2^e_i, so every partial sum
+// is at most K 2^(e_i + e_j) <= B = 2^(q - 56) in exact arithmetic, and, while the roundings are relative ones of 2^-53 each,
+// |acc| <= B (1 + 2^-53)^K <= B (1 + 2^-38) for K <= 16384.  Roundings into the subnormal grid are absolute, at most 2^-1075 each:
+// if q >= L - 1019 their sum K 2^-1075 <= 2^(L - 1075) <= B, so |acc| <= 2 B (1 + 2^-38) < 2^(q - 54), still below HALF the smaller
+// gap 2^(q - 53) around C_ij -- the spare binade again; if q < L - 1019 every product is below 2^-1075, each fused add returns the
+// zero it started from, and acc = 0.  Either way the exact C_ij - acc is strictly closer to C_ij than to a neighbour: the store keeps
+// the bits of C_ij, and so does each atomic add of a part, whose bound is the same with fewer terms (C_ij is C_ij again before the
+// next part arrives).  The cases kept live above stay live here; an all-zero row gives acc = 0 exactly.
+// The kernels' screens and the host entry lmm_dev_emul_negligible all decide through emul_negligible.
 #define LMM_EMUL_NEG_MARGIN 56
 #define LMM_EMUL_NEG_NEVER 0x7FFFFFFF
 #define LMM_EMUL_NEG_ALWAYS (-0x7FFFFFFF - 1)

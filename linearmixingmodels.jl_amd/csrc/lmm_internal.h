@@ -110,6 +110,8 @@ struct NodeArgs {
   int* nflags; int nf_stride, epoch;
   int strip_n, strip0;    // column tiles of the ragged last 64 rows run as work items of this launch (0: none / separate launch); their first item
   int Mb, MTb, bulk0;     // rows / 128-row tiles the bulk items cover (a ragged last 64 rows included); index of the first bulk item
+  // the screen's flag bytes (lmm_potrf_plan.h, f64_screen_flag_at with MT and scr_nt): a "rest" item whose tile's byte is 0 returns at once; nullptr: no screen
+  const unsigned char* scr; int scr_nt;
 };
 // Arguments of potrf_region_kernel (lmm_kernels.hip K2d): the columns [c0, c0 + 128 P) of every matrix of the batch, rows c0 .. c0 + M - 1.
 struct RegionArgs {
@@ -159,7 +161,7 @@ void launch_panel_bulk(const BatchPtr& A, const BatchPtr& W2, int ld, int NR, in
 // strip (POTRF_STRIP_*): where the plan puts a ragged last 64 rows; nflags != nullptr (the plan's fused_bulk): also the bulk rows of that
 // panel, in the same launch (NODE_FUSE, flags of nf_stride ints per matrix)
 void launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, int ld, int NR, int j0, int h,
-                        int N, int n_real, int nb, hipStream_t st, int strip, int* nflags = nullptr, int nf_stride = 0);
+                        int N, int n_real, int nb, hipStream_t st, int strip, int* nflags = nullptr, int nf_stride = 0, const unsigned char* scr = nullptr);
 // lmm_kernels_f32w.hip: fp32 C -= A B' on 256 x 256 tiles (one workgroup per CU); false: not launched (shape / switch), use the 128-tile kernel
 bool launch_gemm32w(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B, size_t offB, int ldb,
                     int M, int N, int K, int lower, int nb, int cus, bool deterministic, hipStream_t st);
@@ -184,6 +186,12 @@ void emul_set_zero_skip(int on);             // 0: the GEMM walks every K block 
 struct EmulAmaxKeep { unsigned long long* out; int ld, row0, n; const unsigned long long* src[LMM_EMUL_COVER_MAX]; int scan0; unsigned long long* bmax; int cb0, ncb; };
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
                               int G, int nmod, void* scratch, void* aux, void* screen, hipStream_t st, const EmulAmaxKeep* keep = nullptr);      // the first HIP error of its host-side calls
+// lmm_kernels_i8.hip: the scan and the screen in front of a screened f64 update launch.  keep: as for an emulated
+// update (bmax may be nullptr: no block maxima are kept).  flags: f64_screen_flag_bytes; stat[0] += dead rest tiles, stat[1] = 1 when
+// the screen did its work; vote (may be nullptr): a word an earlier screen of the factorisation left its dead count in -- when it is
+// zero the scan and the screen return at entry and the flags say "live".  M, strip: the step's; the screen covers the rows the node launch takes.
+hipError_t launch_f64_screen(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int strip, int nb,
+                             const EmulAmaxKeep& keep, unsigned char* flags, int* stat, const int* vote, hipStream_t st);
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,
                    const BatchInfo& info, int nb, hipStream_t st);
 // no_splitk: never split the last round's tiles along K (their f64 atomics make the sum order run-dependent): bitwise reproducible

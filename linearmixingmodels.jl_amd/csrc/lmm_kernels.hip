@@ -2269,6 +2269,9 @@ __global__ __launch_bounds__(256, 2) void potrf_node_kernel(NodeArgs a) {
           bidx = a.nb - 1;
           gemm_work_item_from(q - bidx * a.rest_items, 1, BM, BN, a.N, 1, a.MT, a.full_items_last, a.splitk_last, part, nparts, ti, tj);
         }
+        // The screen found that no entry of this tile can change by a bit: all parts of a split tile read the same byte
+        // and leave.  Uniform over the workgroup and ahead of every barrier; a rest item publishes nothing and nobody waits for it.
+        if (a.scr != nullptr && a.scr[f64_screen_flag_at(a.MT, a.scr_nt, bidx, ti, tj)] == 0) return;
       }
     } else { bulk = true; bidx = item / (a.MT - 1); ti = item - bidx * (a.MT - 1) + 1; }
   }
@@ -5353,13 +5356,17 @@ const FactorSwitches& factor_switches() {
     g_switches.region_occ = num("LMM_REGION_OCC", 0);
     g_switches.region_th = num("LMM_REGION_TH", 0);
     g_switches.region_trace = num("LMM_REGION_TRACE", 0);
+    g_switches.f64_screen = num("LMM_F64_SCREEN", 1) != 0;
+    g_switches.f64_screen_mink = std::max(128, num("LMM_F64_SCREEN_MINK", 512));
+    g_switches.f64_screen_rounds = getenv("LMM_F64_SCREEN_MINK") ? 0 : std::max(0, num("LMM_F64_SCREEN_ROUNDS", 1));      // an explicit threshold screens every update it admits
+    g_switches.f64_screen_vote = num("LMM_F64_SCREEN_VOTE", 1) != 0;
   }
   if (g_switches.emul_on < 0) g_switches.emul_on = num("LMM_F64_EMUL", 1) != 0;
   if (g_switches.emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_switches.emul_mink = e ? std::max(128, atoi(e)) : 0; }
   return g_switches;
 }
 void launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, int ld, int NR, int j0, int h,
-                        int N, int n_real, int nb, hipStream_t st, int strip_mode, int* nflags, int nf_stride) {
+                        int N, int n_real, int nb, hipStream_t st, int strip_mode, int* nflags, int nf_stride, const unsigned char* scr) {
   const int r0 = j0 + h, NT = (N + 127) / 128;     // N may end in a 64-column half tile
   if (nb <= 0 || N <= 0 || h <= 0) return;
   node_lds_attr();
@@ -5418,6 +5425,7 @@ void launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2
   a.strip_n = strip_in ? N / 128 : 0; a.strip0 = nb * MT;
   long long items = nb * MT + (long long)nb * a.strip_n + (T > 0 ? (long long)(nb - 1) * a.rest_items + rest_last : 0);
   a.Mb = Mfull; a.MTb = MTb; a.bulk0 = (int)items;
+  a.scr = scr; a.scr_nt = NT;
   if (fuse) {
     a.mode |= NODE_FUSE; a.nflags = nflags; a.nf_stride = nf_stride; a.epoch = next_flag_epoch();
     items += (long long)nb * (MTb - 1);

@@ -41,7 +41,11 @@ struct EmulBlockMax { unsigned long long* p; size_t zs, ld; };
 // One thread per row and K block of 128 columns, for the blocks kb / 128 .. K / 128 - 1 (kb, K multiples of 128): the block's maximum
 // |a_ik| as a bit pattern (order-preserving for non-negative doubles; a NaN is above everything) goes to bm -- one plain store per
 // entry, coalesced over the rows -- and amax[z as + i] = max(what is there, that maximum).  as: entries per matrix of amax.
-__global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int as, int kb, unsigned long long* amax, EmulBlockMax bm) {
+// The scans of the f64 updates' screen keep no block maxima (bm.p == nullptr) and obey that screen's vote: a zero there means the
+// factorisation's data does not decay, and the scan returns at entry (uniform over the grid; nobody reads its array then).
+__global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int as, int kb, unsigned long long* amax, EmulBlockMax bm,
+                                                          const int* __restrict__ vote) {
+  if (vote != nullptr && *vote == 0) return;
   const int i = blockIdx.x * 256 + threadIdx.x, z = blockIdx.z;
   if (i >= M) return;
   const int k0 = kb + blockIdx.y * BK;
@@ -49,7 +53,7 @@ __global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, si
   unsigned long long m = 0;
 #pragma unroll 8
   for (int k = 0; k < BK; ++k) m = max(m, (unsigned long long)__double_as_longlong(P[(size_t)k * ld]) & ABS_MASK);
-  bm.p[(size_t)z * bm.zs + (size_t)(k0 / BK) * bm.ld + i] = m;
+  if (bm.p != nullptr) bm.p[(size_t)z * bm.zs + (size_t)(k0 / BK) * bm.ld + i] = m;
   atomicMax(&amax[(size_t)z * as + i], m);
 }
 // The first write of an update's kept row maxima: per row the largest of the maxima that earlier updates kept for parts of its panel
@@ -253,6 +257,50 @@ __global__ __launch_bounds__(256) void emul_screen_kernel(BatchPtr A, int g0, si
     live = __syncthreads_or(lv ? 1 : 0) != 0;
   }
   if (tid == 0) flags[emul_flag_at(tm, tn, z, t.x, t.y)] = live ? 1 : 0;
+}
+// The same screen in front of an f64 update launch (potrf_node_kernel, lmm_kernels.hip), over that launch's 128 x 128 tiles with tile
+// column >= 1 -- its "rest" items; column 0 carries the leaf and what fused bulk tiles wait for, and is never screened.  One workgroup
+// of 128 threads per (tile row, tile column - 1, matrix), one thread per row; the entries tested are the ones the kernel would write
+// below or on the diagonal: i >= j, i < M, j < N.  Depth K of f64 MFMAs in any order: |acc| <= K 2^(e_i + e_j) (1 + 2^-52)^K, within
+// the bound the predicate was proved for (lmm_emul.h, "the f64 kernel").  amax: the kept row maxima, row 0 = the region's first row.
+// Thread 0 stores the tile's byte (f64_screen_flag_at): a plain store, every byte the node launch reads is written by every launch.
+// stat[0] counts the dead tiles, stat[1] says that the screen ran.  vote: a zero there (the first screened update of this
+// factorisation found no dead tile) makes every workgroup store "live" and return without reading C.
+__global__ __launch_bounds__(128) void f64_screen_kernel(BatchPtr A, size_t offC, int ldc, int M, int N, int K, const unsigned long long* __restrict__ amax, int as,
+                                                         int MT, int NT, unsigned char* flags, int* stat, const int* __restrict__ vote) {
+  constexpr int T = LMM_F64_SCREEN_TILE;
+  const int tid = threadIdx.x, ti = blockIdx.x, tj = blockIdx.y + 1, z = blockIdx.z;
+  if (ti < tj) return;                                  // above the diagonal: no such item, the byte is never read
+  unsigned char* flag = flags + f64_screen_flag_at(MT, NT, z, ti, tj);
+  if (vote != nullptr && *vote == 0) {
+    if (tid == 0) *flag = 1;
+    return;
+  }
+  const int i = ti * T + tid, j0 = tj * T, jn = min(N, j0 + T), lgk = emul_ceil_log2(K);
+  const unsigned long long* az = amax + (size_t)z * as;
+  const unsigned long long ri = i < M ? az[i] : 0ull;
+  const double* C = A.p[z] + offC + i;
+  bool live = false;
+  for (int jc = j0; jc < jn && !live; jc += SCR_COLS) {
+    double cv[SCR_COLS];
+    bool on[SCR_COLS];
+#pragma unroll
+    for (int q = 0; q < SCR_COLS; ++q) {
+      const int j = jc + q;
+      on[q] = j < jn && i >= j && i < M;
+      cv[q] = on[q] ? C[(size_t)j * ldc] : 0.0;
+    }
+    bool lv = false;
+#pragma unroll
+    for (int q = 0; q < SCR_COLS; ++q)
+      if (on[q]) lv |= !emul_neg_at(emul_neg_bound(lgk, ri, az[jc + q]), cv[q]);      // j < N <= M: the row maximum of column j's panel row exists
+    live = __syncthreads_or(lv ? 1 : 0) != 0;
+  }
+  if (tid == 0) {
+    *flag = live ? 1 : 0;
+    if (!live) atomicAdd(&stat[0], 1);
+    if (ti == MT - 1 && tj == 1 && z == 0) stat[1] = 1;
+  }
 }
 // The live id list (lmm_emul.h): one workgroup per matrix of the group, no workgroup reads what another writes.  Workgroup z counts
 // the live tiles of the matrices before it and its own (ballots, tile-list order), then walks its tiles again and stores, for the
@@ -652,6 +700,20 @@ void emul_set_gemm_workgroups(int wgs) { g_emul_gemm_wgs = wgs; }
 void emul_set_zero_skip(int on) { g_emul_zero_skip = on < 0 ? -1 : (on ? 1 : 0); }
 void emul_set_scratch_poison(int on) { g_emul_poison = on ? 1 : 0; }
 
+hipError_t launch_f64_screen(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int strip, int nb,
+                             const EmulAmaxKeep& keep, unsigned char* flags, int* stat, const int* vote, hipStream_t st) {
+  const int Mn = f64_screen_rows(M, strip);
+  const int MT = (Mn + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE, NT = (N + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE;
+  if (nb <= 0 || MT < 2 || NT < 2 || N > Mn || (K % BK) != 0 || (keep.scan0 % BK) != 0) return hipErrorInvalidValue;
+  EmulBlockMax bm{};
+  if (keep.bmax != nullptr) bm = EmulBlockMax{keep.bmax + (size_t)keep.cb0 * keep.ld + keep.row0, (size_t)keep.ncb * keep.ld, (size_t)keep.ld};
+  emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(keep, M);      // every row's first write: no memset
+  if (keep.scan0 < K)
+    emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep.scan0) / BK, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep.ld, keep.scan0, keep.out + keep.row0, bm, vote);
+  f64_screen_kernel<<<dim3(MT, NT - 1, nb), LMM_F64_SCREEN_TILE, 0, st>>>(C, offC, ldc, Mn, N, K, keep.out + keep.row0, keep.ld, MT, NT, flags, stat, vote);
+  return hipGetLastError();
+}
+
 // C_m (M x N at C.p[m] + offC, ldc) -= P_m P_m[0:N]' for the panels P_m (M x K at P.p[m] + offP, ldp), m < nb, lower trapezoid
 // (i >= j) only, in groups of G matrices through `scratch` (emul_scratch_bytes(M, N, K, G, nmod) bytes).  Returns the first HIP
 // error of its host-side calls (nothing is launched after one).  keep: the row maxima and the block maxima go to arrays of the
@@ -688,7 +750,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
     bm = EmulBlockMax{keep->bmax + (size_t)keep->cb0 * keep->ld + keep->row0, (size_t)keep->ncb * keep->ld, (size_t)keep->ld};
     emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(*keep, M);
     if (keep->scan0 < K)
-      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep->scan0) / BK, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep->ld, keep->scan0, keep->out + keep->row0, bm);
+      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep->scan0) / BK, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep->ld, keep->scan0, keep->out + keep->row0, bm, nullptr);
   }
   for (int g0 = 0; g0 < nb; g0 += G) {
     const int gc = std::min(G, nb - g0);
@@ -700,7 +762,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
     else {
       err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
       if (err != hipSuccess) return err;
-      emul_rowmax_kernel<<<dim3((M + 255) / 256, K / BK, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, amax, gbm);
+      emul_rowmax_kernel<<<dim3((M + 255) / 256, K / BK, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, amax, gbm, nullptr);
     }
     unsigned long long* masks = reinterpret_cast<unsigned long long*>(static_cast<char*>(aux) + X.masks);
     unsigned short* dead = skip ? reinterpret_cast<unsigned short*>(static_cast<char*>(aux) + X.pieces) : nullptr;

@@ -40,6 +40,11 @@ struct FactorSwitches {
   int rule_always = kRuleAlways, rule_shape = kRuleShape;      // lmm_dev_set_f64_emul_rule
   double rule_outs = kRuleOuts;
   int emul_group_cap = 0;    // lmm_dev_set_emul_group: at most this many matrices per group of an emulated update (0: no cap)
+  // The f64 update launches leave out the 128 x 128 tiles whose update cannot change a bit of C (DESIGN.md 4.17 "the same screen on
+  // the f64 kernel"): LMM_F64_SCREEN=0 turns that off, LMM_F64_SCREEN_MINK is the least K that earns its scan;
+  // lmm_dev_set_f64_screen(on, min_k) writes both.  LMM_F64_SCREEN_VOTE=0: every screened update scans and screens, whatever the first one found.
+  int f64_screen = 1, f64_screen_mink = 512, f64_screen_vote = 1;
+  int f64_screen_rounds = 1; // f64_screen_pays: a screened launch has more work items than this many rounds of 2 per CU (0: no such rule; LMM_F64_SCREEN_ROUNDS)
 };
 
 enum PotrfStepKind {
@@ -64,6 +69,7 @@ struct PotrfStep {
   double work, bytes;        // what ProfScope books for the step
   bool first_done = false, fused_bulk = false;
   int strip = POTRF_STRIP_NONE;      // UPDATE_LEAF: where a ragged last 64 rows of a K >= 1024 update go
+  bool screened = false;             // UPDATE_LEAF: its panel's row maxima are scanned and kept, and the tiles of the column tiles 1.. are screened
   int update = -1;                   // UPDATE_LEAF, EMUL_UPDATE_LEAF: the step's entry in PotrfPlan.updates
   int group = 0; size_t scratch = 0; // EMUL_UPDATE_LEAF: matrices per group, scratch bytes at that group size (that entry's)
   // the (M, N, K) ProfScope names: the 64-column path's diagonal blocks and solves go unnamed
@@ -121,6 +127,36 @@ inline int emul_group(int M, int N, int K, int nb, const PotrfPlan& P, const Fac
   return gs;
 }
 
+// ---- the f64 update launches' screen: flag bytes of one launch ----
+// potrf_node_kernel's tiles are 128 x 128; the screen leaves one byte per (matrix, tile row, tile column) of the launch's MT x NT
+// tile grid, flags[f64_screen_flag_at(MT, NT, z, ti, tj)] != 0 when some entry of the tile that the kernel would write -- i >= j,
+// i < M, j < N -- is not negligible (emul_negligible, lmm_emul.h).  Only the bytes of the "rest" tiles, 1 <= tj <= ti < MT, are
+// written and read.  MT counts the rows the node launch takes: a ragged last 64 rows that go to the strip are not among them.
+#define LMM_F64_SCREEN_TILE 128
+#define LMM_F64_SCREEN_VOTE_NT 4      // the vote is taken by the first screened update with at least this many tile columns (potrf_batch)
+LMM_HD inline size_t f64_screen_flag_at(int MT, int NT, int z, int ti, int tj) { return ((size_t)z * MT + ti) * NT + tj; }
+inline int f64_screen_rows(int M, int strip) { return strip != POTRF_STRIP_NONE ? M - 64 : M; }
+inline size_t f64_screen_flag_bytes(int M, int N, int strip, int nb) {
+  const int MT = (f64_screen_rows(M, strip) + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE, NT = (N + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE;
+  return ((size_t)nb * MT * NT + 7) & ~size_t(7);
+}
+// rest tiles of one matrix: sum over tj = 1 .. NT - 1 of (MT - tj)
+inline long long f64_screen_rest_tiles(int MT, int NT) {
+  long long T = 0;
+  for (int tj = 1; tj < NT && tj < MT; ++tj) T += MT - tj;
+  return T;
+}
+// Does screening the M x N (x K) update of nb matrices pay?  Only a launch of more than `rounds` rounds of workgroups (two resident per
+// CU) can get shorter by leaving tiles out: one that fits the device at once takes a tile time whatever is skipped, and the scan, the
+// screen and their launches are pure cost (8 x 2048, one K = 1024 update of 288 work items: 1.16 -> 1.20 ms per evaluation with it
+// screened).  An explicit threshold (LMM_F64_SCREEN_MINK, lmm_dev_set_f64_screen) sets rounds to 0: every update with K >= min_k and
+// more than one tile column is screened, as the tests' small shapes need.
+inline bool f64_screen_pays(int M, int N, int strip, int nb, int cus, const FactorSwitches& sw) {
+  if (sw.f64_screen_rounds <= 0) return true;
+  const int MT = (f64_screen_rows(M, strip) + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE, NT = (N + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE;
+  return (long long)nb * (MT + f64_screen_rest_tiles(MT, NT)) > 2LL * cus * sw.f64_screen_rounds;
+}
+
 // The walk over the columns [0, NC) of nb matrices of NR rows.  rows_real: rows that hold data (the Gram rows + the real rider rows; -1:
 // all NR) -- the work figures count those, not the 64-row padding of the riders.
 struct PotrfPlanner {
@@ -128,6 +164,7 @@ struct PotrfPlanner {
   const FactorSwitches& sw;
   int NR, nbi, rows; double nb;
   bool emul, node_fuse = false; int in_flight;
+  int cus = 256;
 
   PotrfStep& add(int kind, int cls, int j0, int h, int N, int M, double work, double bytes = 0.0) {
     PotrfStep s{}; s.kind = kind; s.cls = cls; s.j0 = j0; s.h = h; s.N = N; s.M = M; s.work = work; s.bytes = bytes;
@@ -211,6 +248,7 @@ struct PotrfPlanner {
                        nb * (2.0 * h * outs + 2.0 * 128.0 * 128.0 * 128.0 / 3.0 + Mb * 128.0 * 128.0), nb * (16.0 * outs + 8.0 * Mr * h + 16.0 * Mb * 128.0));
     s.update = (int)P.updates.size() - 1;
     if (!emulated) {
+      s.screened = sw.f64_screen != 0 && h >= sw.f64_screen_mink && (h % 128) == 0 && (j0 % 128) == 0 && Nc > 128;
       s.fused_bulk = fuse_k && (M + 127) / 128 > 1;
       // ragged last row tile (the rider rows make the row count an odd multiple of 64): on the long products the node kernel takes the
       // full 128-row tiles and gemm16h_kernel the last 64 rows (two idle waves for a whole tile time otherwise) -- as work items of the
@@ -218,6 +256,7 @@ struct PotrfPlanner {
       // kernels fill the CUs a separate launch leaves idle, and the in-launch items measured slower (687.2 -> 689.9 ms per step)
       if ((M % 128) == 64 && M - 64 >= Nc && (Nc % 128) == 0 && h >= 1024)
         s.strip = sw.strip_items && (in_flight <= 1 || sw.strip_items == 2) ? POTRF_STRIP_IN_LAUNCH : POTRF_STRIP_SEPARATE;
+      s.screened = s.screened && f64_screen_pays(M, Nc, s.strip, nbi, cus, sw);
     }
     const bool fused = s.fused_bulk;
     panels(r0, Nc, true, fused);
@@ -228,12 +267,19 @@ struct PotrfPlanner {
 // [j0, j0 + h), rows from j0 + h -- for the largest |entry| of every row, and potrf_batch keeps that array until the factorisation
 // ends.  The entries below a factored block column never change again, so a later update whose panel contains those columns, and
 // whose rows begin at or below the kept array's first row, finds the exact maximum of that column range in it.  emul_amax_cover
-// covers a prefix [j0, scan0) of the panel of steps[si] with the kept arrays of earlier emulated steps: from c = j0, the widest
+// covers a prefix [j0, scan0) of the panel of steps[si] with the kept arrays of earlier scanning steps: from c = j0, the widest
 // earlier panel that begins at c and ends at or before j0 + h (so its rows begin no later than ours, at j0 + h), then on from its
 // end.  The columns [scan0, j0 + h) are left to scan.  It reads the step list only: no shape of the recursion is assumed.
+// A scanning step is an emulated update or, with f64_too, a screened f64 update (PotrfStep.screened), which keeps the same array.
+// (An f64 step's array holds maxima only while the vote of the f64 screen has not switched its scans off -- potrf_batch passes
+// f64_too to f64 steps, which the same vote switches off, and to emulated steps only when there is no vote -- and an f64 step keeps no
+// block maxima unless told to: emul_step_scans says which steps of a plan an emulated step may take from.)
 #define LMM_EMUL_COVER_MAX 8
 struct EmulCover { int n = 0; int step[LMM_EMUL_COVER_MAX] = {}; int scan0 = 0; };
-inline EmulCover emul_amax_cover(const std::vector<PotrfStep>& steps, int si, bool reuse) {
+inline bool emul_step_scans(const PotrfStep& e, bool f64_too) {
+  return e.kind == POTRF_EMUL_UPDATE_LEAF || (f64_too && e.kind == POTRF_UPDATE_LEAF && e.screened);
+}
+inline EmulCover emul_amax_cover(const std::vector<PotrfStep>& steps, int si, bool reuse, bool f64_too = false) {
   const PotrfStep& s = steps[si];
   EmulCover c;
   c.scan0 = s.j0;
@@ -242,7 +288,7 @@ inline EmulCover emul_amax_cover(const std::vector<PotrfStep>& steps, int si, bo
     int best = -1;
     for (int t = 0; t < si; ++t) {
       const PotrfStep& e = steps[t];
-      if (e.kind == POTRF_EMUL_UPDATE_LEAF && e.j0 == c.scan0 && e.j0 + e.h <= end && (best < 0 || e.h > steps[best].h)) best = t;
+      if (emul_step_scans(e, f64_too) && e.j0 == c.scan0 && e.j0 + e.h <= end && (best < 0 || e.h > steps[best].h)) best = t;
     }
     if (best < 0) break;
     c.step[c.n++] = best;
@@ -258,6 +304,7 @@ inline PotrfPlan plan_potrf(int NR, int NC, int nb, int rows_real, int in_flight
                             const FactorSwitches& sw) {
   PotrfPlanner W{PotrfPlan{}, sw, NR, nb, rows_real >= 0 ? std::min(NR, rows_real) : NR, (double)nb, false, false, in_flight};
   PotrfPlan& P = W.P;
+  W.cus = cus;
   // Float64 batches take the 128-column panel path; its W2 scratch -- one 128 x 128 inverse per panel and matrix -- lives until the API call ends
   P.panel128 = !(f32 || !sw.panel128 || NC < 128 || ld_odd);
   if (!P.panel128) { W.cols64(0, NC); return P; }
@@ -303,3 +350,4 @@ inline PotrfPlan plan_potrf(int NR, int NC, int nb, int rows_real, int in_flight
     if (s.kind == POTRF_EMUL_UPDATE_LEAF) { s.group = P.updates[s.update].group; s.scratch = P.updates[s.update].scratch; }
   return P;
 }
+

@@ -17,6 +17,11 @@ Then one line per emulated UPDATE, in launch order: an update is a maximal run o
 nb): Mp = the rows padded to the GEMM tile (convert's grid), nb = the matrices of all its groups.  `span` is first start to last end,
 the leaf128_kernel launch that follows an emulated update included (the f64 update runs that leaf inside its own launch).
 
+A screened f64 update ("the same screen on the f64 kernel") opens with the same scan kernels, then f64_screen_kernel
+and its potrf_node_kernel launch: those are kept apart from the emulated updates and listed after them, one line per update in launch
+order -- the node launch's template arguments, grid and ms, the scan's and the screen's ms, and the screen's grid (tile rows x tile
+columns - 1 x matrices).
+
 --f64 NR NC: the trace is of the f64 path (LMM_F64_EMUL=0) of matrices with NR rows and NC columns; the potrf_node_kernel<2>
 launches (the updates with K >= 1024) are named by walking the factorisation's recursion, evaluation after evaluation."""
 import collections
@@ -54,6 +59,7 @@ def main(argv):
     per = collections.defaultdict(lambda: collections.defaultdict(float))
     other = collections.defaultdict(float)
     runs, cur, last_k = [], None, 0      # last_k: a run cut in two by another kernel continues the level of its first part
+    screened, scr = [], None             # screened f64 updates: scan ms, screen ms and grid, then the node launch
 
     def close(u):
         for k in EMUL:
@@ -64,6 +70,14 @@ def main(argv):
         t0, t1 = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
         ms = (t1 - t0) * 1e-6
         hit = next((ALIAS.get(k, k) for k in EMUL + tuple(ALIAS) if k + "_kernel" in name), None)
+        if "f64_screen_kernel" in name:      # the run so far was this update's scan, not an emulated update
+            scr = dict(scan=cur["emul_rowmax"] if cur is not None else 0.0, screen=ms, grid=f"{grid(r, 'X')} x {grid(r, 'Y')} x {grid(r, 'Z')}")
+            cur = None
+            continue
+        if scr is not None and "potrf_node_kernel" in name:
+            scr.update(node=ms, kind=name[name.index("<"):name.index(">") + 1] if "<" in name else "", items=grid(r, "X"))
+            screened.append(scr)
+            scr = None
         if hit is None:
             other[name.split("(")[0][:60]] += ms
             if cur is not None and "fillBuffer" in name:
@@ -98,6 +112,11 @@ def main(argv):
         tot = sum(u[k] for k in EMUL) + u["fill"] + u["leaf"]
         print(f"  K={u['K']:5d} Mp={int(u['Mp']):5d} nb={u['nb']:2d} groups={u['groups']:2d} | " + " ".join(f"{u[k]:7.3f}" for k in EMUL)
               + f" {u['fill']:6.3f} {u['leaf']:6.3f} | {tot:8.3f} {(u['t1'] - u['t0']) * 1e-6:8.3f}")
+    if screened:
+        print(f"screened f64 updates in launch order ({len(screened)}): node kernel, items | node ms, scan ms, screen ms | screen grid")
+        for u in screened:
+            print(f"  {u['kind']:10s} {u['items']:7d} | {u['node']:8.3f} {u['scan']:7.3f} {u['screen']:7.3f} | {u['grid']}")
+        print("screened f64 updates, totals: node %.2f ms, scan %.2f ms, screen %.2f ms" % tuple(sum(u[k] for u in screened) for k in ("node", "scan", "screen")))
     if "--f64" in argv:
         NR, NC = int(argv[argv.index("--f64") + 1]), int(argv[argv.index("--f64") + 2])
         seq = []

@@ -11,6 +11,11 @@
         convert's rule applied to every emulated update's panel (a 256-row block is live in a 128-wide K block when one of its
         truncated integers is not zero), and per tile (I, J) of the update the number of blocks live in both operands -- the K steps
         the kernel runs for it -- beside K / 128, the K steps without the skip.  Rider rows (y) are left out: they are one tile row.
+
+    python tools/emul_zero_skip_probe.py screen [--lengthscale L]
+        one logpdf, then the counters the screen of the f64 update launches kept on the device (lmm_dev_f64_screen_stats): per
+        screened update of the last batch, the dead 128 x 128 tiles of its rest tiles, and whether its screen ran or returned at
+        entry after the vote.
 """
 import argparse
 import ctypes as C
@@ -65,6 +70,38 @@ def timed(args):
                       "ms_per_step": 1e3 * dt / max(args.steps, 1), "logpdf": val, "lib": os.environ.get("LMM_HIP_LIB", "in-tree")}))
 
 
+def screen(args):
+    """The f64 update launches' screen on the device: per screened update of the last batch's factorisation, the dead
+    tiles its screen counted of the rest tiles of one matrix x the batch"""
+    import torch
+    import lmm_amd
+    from lmm_amd.workloads import synthetic_problem
+    lmm_amd.init(0)
+    lib = lmm_amd.load()
+    lib.lmm_dev_f64_screen_stats.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int]
+    lib.lmm_dev_f64_screen_stats.restype = C.c_int
+    P = synthetic_problem(M_LAT, P_OUT, N, "matern52", True, s2=0.1, seed=0)
+    fs = lmm_amd.independent_mogp([lmm_amd.GP(0.0, lmm_amd.Matern52Kernel(1.0, args.lengthscale)) for _ in range(M_LAT)])
+    f = lmm_amd.ILMM(fs, lmm_amd.Orthogonal(P["U"], P["S"]), shard=lmm_amd.latent_shard(M_LAT, 0, 1))
+    xd, yd = torch.from_numpy(P["x"]).cuda(), torch.from_numpy(P["y"]).cuda()
+    fx = f(lmm_amd.MOInputIsotopicByOutputs(xd, P_OUT), 0.1)
+    assert lib.lmm_dev_f64_screen_stats(1, None, 0) >= 0
+    val = lmm_amd.logpdf(fx, yd, True)
+    out = (C.c_int * (5 * 256))()
+    n = lib.lmm_dev_f64_screen_stats(0, out, 256)
+    print(f"lengthscale {args.lengthscale}: logpdf {val!r}; screened f64 updates of the last batch ({M_LAT // 2} matrices), in launch order: M N K | dead tiles of rest tiles | screen ran")
+    tot = {}
+    for i in range(n):
+        M, Nc, K, dead, ran = out[5 * i:5 * i + 5]
+        mt, nt = (M - (64 if M % 128 == 64 and K >= 1024 else 0) + 127) // 128, (Nc + 127) // 128
+        rest = (M_LAT // 2) * sum(mt - tj for tj in range(1, nt))
+        tot.setdefault(K, [0, 0])
+        tot[K][0] += dead
+        tot[K][1] += rest
+        print(f"  {M:6d} {Nc:5d} {K:5d} | {dead:6d} of {rest:6d} | {ran}")
+    print("per K (dead, rest tiles): " + str({k: tuple(v) for k, v in sorted(tot.items())}))
+
+
 def live(args):
     import torch
     import lmm_amd
@@ -114,10 +151,10 @@ def live(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["time", "live"])
+    ap.add_argument("mode", choices=["time", "live", "screen"])
     ap.add_argument("--lengthscale", type=float, default=1.0)
     ap.add_argument("--noise", type=float, default=0.1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args()
-    timed(a) if a.mode == "time" else live(a)
+    {"time": timed, "live": live, "screen": screen}[a.mode](a)
