@@ -1141,6 +1141,38 @@ int lmm_dev_f64_screen_stats(int on, int* out, int cap);
  * (tile row, tile column)): for 1 <= tile column <= tile row, 1 when some entry i >= j of the tile is not negligible
  * (lmm_dev_emul_negligible), 0 when the tile is dead; 0xFF elsewhere (never written).  *dead = the dead tiles the screen counted. */
 int lmm_dev_f64_screen_flags(const double* C, int ldc, const double* A, int lda, int M, int N, int K, unsigned char* flags, int* dead);
+/* Zero extents (DESIGN.md 4.17 "rows whose panel is exactly zero"; switch LMM_ZERO_EXTENTS, read once, default 1).  The Gram launch of
+ * a Float64 per-latent logpdf keeps, per block of 64 rows of each factor matrix, the number of leading columns (whole 64-column blocks
+ * of the lower triangle) in which every entry of those rows was stored as +0; a row block that is all zeros keeps 0x7F7F7F7F.  The
+ * factorisation leaves out the region row tasks, the f64 update items and the emulated update tiles whose rows are zero across the
+ * whole panel: for a finite factor they would only rewrite the zeros that are there, so results do not depend on the switch, bit
+ * for bit.  LMM_ZERO_EXTENTS=0: no extents are kept.  None are kept either for matrices of at most LMM_REGION (1024) columns, which one
+ * region launch factors whole: no item of theirs can be void.  With LMM_REGION_OCC=2 the region launches leave nothing out (the
+ * two-per-CU build has no void test; its counters stay 0) -- updates and screens still do.  Test hook: on = 0 / 1, on < 0 goes
+ * back to the default. */
+int lmm_dev_set_zero_extents(int on);
+/* The size gate of the zero extents (LMM_ZERO_EXTENTS_MINCOLS, read once; default 2048): a per-latent logpdf keeps them only for
+ * matrices of more than this many columns -- at 2048 columns they cost more than the little that is void there gains.  Test hook:
+ * cols >= 0 sets the gate, cols < 0 goes back to the default. */
+int lmm_dev_set_zero_extents_min_cols(int cols);
+/* Test hook: on != 0 makes every later factorisation that has zero extents count the work items it leaves out and copy the counters to
+ * the host (this synchronises its stream).  out (cap records of 7 ints; may be NULL with cap = 0): for every region, update + leaf
+ * and emulated update + leaf step of the last factorisation of the process, in launch order: the step kind (as in
+ * lmm_dev_potrf_plan), j0, h, N, M, the count over all matrices of the batch, and a shape word (a region launch: how many of its
+ * row tasks are 128 rows high, the rest 64; an update: 1 when the bulk rows ride along + 2 x the strip mode of the plan).  The count: row tasks of a region launch that returned at
+ * entry; rest and column-0 items of an f64 update launch that did (a split tile counts once); 256 x 256 tiles the emulation's
+ * screen marked dead without reading C.  No records when that factorisation had no extents.  Returns the number of records (those
+ * beyond cap are counted, not written), or -LMM_ERR_ARG. */
+int lmm_dev_zero_extent_stats(int on, int* out, int cap);
+/* lmm_dev_potrf with the caller's zero extents: zext (device, nrows / 64 ints) holds, per block of 64 rows, a number of leading
+ * columns in which all entries of those rows are +0 -- the true extents or any smaller values.  NULL: exactly lmm_dev_potrf. */
+int lmm_dev_potrf_zext(double* A, int nrows, int ncols, int ld, double* Winv, int n_real, int* info_dev, const int* zext);
+/* The training Gram launch of the per-latent logpdf for nb latents on device memory: matrix j (nrows x ncols, leading dimension ld,
+ * nrows and ncols multiples of 64, ncols >= n) at A + j * ld * ncols = K_j(x, x) + noise[j] I (or + diag(noisevec[j][.]), device,
+ * when noisevec is given), the identity on the padding, rows ncols .. ncols + nrider - 1 = rider[j][r][.] (device).  zext (host,
+ * nb x nrows / 64 ints): the zero extents the launch kept, -1 everywhere when none are kept (switch off, Float32). */
+int lmm_dev_train_gram(double* A, int ld, int nrows, int ncols, const double* x, int d, int n, const lmm_gp_t* gp, int nb,
+                       const double* noise, const double* noisevec, const double* rider, int nrider, int* zext);
 /* Host-only (no GPU, no lmm_init needed): the reduction of the emulation's GEMM epilogue on `count` int32 accumulators |x| <= 2^28:
  * out[i * nmod + t] = x[i] modulo the t-th modulus as an int8 (congruent, inside the symmetric range).  exhaustive (may be NULL, 2
  * words): its float step run on every folded value it can see, every modulus: [0] cases, [1] failures. */

@@ -50,6 +50,7 @@ SYMBOLS = [
     "lmm_dev_set_emul_zero_skip", "lmm_dev_emul_stage_list", "lmm_dev_set_emul_scratch_poison", "lmm_dev_emul_block_live",
     "lmm_dev_set_emul_screen", "lmm_dev_emul_last_live_tiles", "lmm_dev_emul_negligible",
     "lmm_dev_set_f64_screen", "lmm_dev_set_deterministic", "lmm_dev_f64_screen_stats", "lmm_dev_f64_screen_flags",
+    "lmm_dev_set_zero_extents", "lmm_dev_set_zero_extents_min_cols", "lmm_dev_zero_extent_stats", "lmm_dev_potrf_zext", "lmm_dev_train_gram",
     "lmm_dev_backsolve", "lmm_dev_factor_inverse",
 ]
 

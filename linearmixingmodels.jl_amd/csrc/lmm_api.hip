@@ -805,6 +805,21 @@ static int g_emul_amax_reuse = 1; // lmm_dev_set_emul_amax_reuse: 0 = every emul
 // lmm_dev_f64_screen_stats: with g_f64_screen_stats on, every factorisation ends by copying its screened steps' counters here (M, N, K, dead tiles, ran)
 static int g_f64_screen_stats = 0;
 static std::vector<int> g_f64_screen_last;
+// lmm_dev_zero_extent_stats: likewise, the void work items of every step that takes the zero extents (kind, j0, h, N, M, count, shape word)
+static int g_zero_ext_stats = 0;
+static std::vector<int> g_zero_ext_last;
+// The zero extents of a batch (lmm_emul.h): [matrix][zero_ext_ld(NR)] ints in call scratch, set to LMM_ZERO_EXT_NONE on the stream; the
+// Gram launch that assembles the batch lowers them (GramArgs.zext).  nullptr when the switch is off or the matrices are not Float64.
+inline int zero_ext_ld(int NR) { return NR / 64 + LMM_ZERO_EXT_PAD; }
+inline int sw_region_cols() { return factor_switches().region; }      // widest block column of one region launch (LMM_REGION; 0: off)
+int* zero_ext_scratch(int NR, int nb, hipStream_t st) {
+  if (g_f32 || !factor_switches().zero_extents) return nullptr;
+  const size_t ints = (size_t)zero_ext_ld(NR) * nb;
+  int* p = reinterpret_cast<int*>(call_scratch((ints + 1) / 2));
+  guard_extent(p, (ints + 1) / 2, (ints + 1) / 2, 1, false, "zero extents");
+  HIPCHK(hipMemsetAsync(p, 0x7F, ints * sizeof(int), st));
+  return p;
+}
 // The emulation side of a Float64 factorisation's plan, whatever path and base case the other switches choose (lmm_dev_emul_plan, batch_plan)
 static PotrfPlan emul_view(int NR, int NC, int nb) {
   FactorSwitches sw = factor_switches();
@@ -815,7 +830,9 @@ static PotrfPlan emul_view(int NR, int NC, int nb) {
 // Entry point of the factorisation of a batch: columns [0, NC) of every matrix (rows 0 .. NR - 1 participate; W: NC / 64 inverse
 // diagonal blocks).  plan_potrf decides what is launched; this function takes the scratch the plan asks for -- all of it lives until
 // the API call ends -- and launches the steps.
-void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t st, int rows_real = -1) {
+// zext (may be nullptr: nothing is left out): the batch's zero extents, matrix j's at zext + j * zero_ext_ld(NR) -- valid only if the
+// launch that wrote them is the only writer of the factor matrices so far.
+void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t st, int rows_real = -1, const int* zext = nullptr) {
   for (int j = 0; j < B.nb; ++j) {
     guard_extent(B.A.p[j], NR, ld, NC, true, "factorisation (factor matrix)");
     guard_extent(B.W.p[j], 64, 64, (size_t)(NC / 64) * 64, true, "factorisation (inverse diagonal blocks)");
@@ -919,6 +936,16 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
     if (emul_screen_bytes > 0) emul_screen_blk = call_scratch(emul_screen_bytes / 8);
     if (emul_ncb > 0) emul_bmax = reinterpret_cast<unsigned long long*>(call_scratch(emul_block_max_bytes(NR, emul_ncb, B.nb) / 8));
   }
+  // counters of the void work items, one per step, zeroed here (the test hook reads them)
+  int* zx_stat = nullptr;
+  if (zext != nullptr && (g_f32 || !sw.zero_extents)) zext = nullptr;
+  if (zext != nullptr) guard_extent(zext, ((size_t)zero_ext_ld(NR) * B.nb + 1) / 2, ((size_t)zero_ext_ld(NR) * B.nb + 1) / 2, 1, false, "factorisation (zero extents)");
+  if (zext != nullptr && g_zero_ext_stats) {
+    zx_stat = reinterpret_cast<int*>(call_scratch((P.steps.size() + 1) / 2));
+    HIPCHK(hipMemsetAsync(zx_stat, 0, P.steps.size() * sizeof(int), st));
+  }
+  std::vector<int> region_n128(P.steps.size(), 0);
+  auto zx_of = [&](const PotrfStep& s) { ZeroExt z; z.p = zext; z.ld = zero_ext_ld(NR); z.stat = zx_stat ? zx_stat + (&s - P.steps.data()) : nullptr; return z; };
   auto leaf128 = [&](int c) { launch_leaf128(B.A, (size_t)c * ld + c, ld, B.W, (size_t)(c / 64) * 4096, W2, (size_t)(c / 128) * 16384, c, n_real, B.info, B.nb, st); };
   for (const PotrfStep& s : P.steps) {
     const bool named = s.named();
@@ -944,10 +971,10 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
           EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0, nullptr, j0 / 128, 0};
           for (int q = 0; q < cov.n; ++q) keep.src[q] = amax_kept[cov.step[q]];
           const int* vote = (sw.f64_screen_vote && scr_vote >= 0 && si > scr_vote) ? scr_stat + 2 * scr_vote : nullptr;
-          HIPCHK(launch_f64_screen(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, s.strip, B.nb, keep, scr_flags, scr_stat + 2 * si, vote, st));
+          HIPCHK(launch_f64_screen(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, s.strip, B.nb, keep, scr_flags, scr_stat + 2 * si, vote, st, zx_of(s), r0));
           scr = scr_flags;
         }
-        launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, s.h, s.N, n_real, B.nb, st, s.strip, s.fused_bulk ? nflags : nullptr, (int)P.node_flag_ints, scr);
+        launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, s.h, s.N, n_real, B.nb, st, s.strip, s.fused_bulk ? nflags : nullptr, (int)P.node_flag_ints, scr, zx_of(s));
         break;
       }
       case POTRF_EMUL_UPDATE_LEAF:
@@ -966,11 +993,11 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
           if (r0 + s.M > NR) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's rows %d + %d exceed %d", r0, s.M, NR);
           if ((j0 % 128) != 0 || (s.h % 128) != 0 || ((cov.scan0 - j0) % 128) != 0 || (j0 + s.h) / 128 > emul_ncb)
             throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's panel [%d, %d) is not whole 128-column blocks below %d", j0, j0 + s.h, 128 * emul_ncb);
-          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, emul_screen_blk, st, &keep));
+          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, emul_screen_blk, st, &keep, zx_of(s), r0));
         }
         leaf128(r0);
         break;
-      case POTRF_REGION: launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst); break;
+      case POTRF_REGION: region_n128[&s - P.steps.data()] = launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst, zx_of(s)); break;
     }
   }
   if (g_f64_screen_stats) {      // test hook only: synchronises the stream
@@ -982,6 +1009,20 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
       for (size_t i = 0; i < P.steps.size(); ++i)
         if (P.steps[i].kind == POTRF_UPDATE_LEAF && P.steps[i].screened)
           for (int v : {P.steps[i].M, P.steps[i].N, P.steps[i].h, h[2 * i], h[2 * i + 1]}) g_f64_screen_last.push_back(v);
+    }
+  }
+  if (g_zero_ext_stats) {        // test hook only: synchronises the stream
+    g_zero_ext_last.clear();
+    if (zx_stat != nullptr) {
+      std::vector<int> h(P.steps.size());
+      HIPCHK(hipMemcpyAsync(h.data(), zx_stat, h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (size_t i = 0; i < P.steps.size(); ++i) {
+        const PotrfStep& s = P.steps[i];
+        if (s.kind == POTRF_UPDATE_LEAF || s.kind == POTRF_EMUL_UPDATE_LEAF || s.kind == POTRF_REGION)
+          for (int v : {(int)s.kind, s.j0, s.h, s.N, s.M, h[i], s.kind == POTRF_REGION ? region_n128[i] : (s.fused_bulk ? 1 : 0) + 2 * (int)s.strip})
+            g_zero_ext_last.push_back(v);
+      }
     }
   }
 }
@@ -1608,21 +1649,29 @@ int latent_lmls(const double* xd, int d, int n, const Latent* lts, const double*
   F.run([&](const FanBatch& b) {
     Slot& s = slots[b.s];
     Batch B;
+    int* zext = nullptr;
     {
     // the batch's Gram launches share one event pair (back-to-back launches: the event overhead is not charged per launch)
     const double gb = train_gram_bytes(n);
     ProfScope ps(LMM_PROF_GRAM, b.nb * gb, s.st, 0, 0, 0, b.nb * gb, b.nb);
     GramArgs ga[LMM_MAX_BATCH];
+    // zero extents (lmm_emul.h): this Gram launch writes every entry of the lower triangle of every matrix of the batch, rider and padding
+    // rows included, and nothing else writes them before the factorisation
+    // (a matrix of at most one region launch's columns is factored by that launch alone: its row tasks are the rider rows, nothing can be
+    // void, and the memset and the per-tile reduction would be pure cost on the small shapes)
+    // and the size gate: FactorSwitches.zero_extents_min_cols
+    if (!(sw_region_cols() > 0 && D.NC <= sw_region_cols()) && D.NC > factor_switches().zero_extents_min_cols) zext = zero_ext_scratch(D.NR, b.nb, s.st);
     for (int j = 0; j < b.nb; ++j) {
       const int k = b.k0 + j;
       // (noisevec: per-point noise of latent k, n device values)
       ga[j] = train_gram_args(lts[l0 + k], xd, d, n, D, s.A[j].p, noisevec ? 0.0 : noise[l0 + k], noisevec ? noisevec + (size_t)k * n : nullptr,
                               delta + (size_t)k * nrhs * n, nrhs, rider_sub ? rider_sub[l0 + k] : 0.0, F.info + k);
+      if (zext != nullptr) { ga[j].zext = zext + (size_t)j * zero_ext_ld(D.NR); ga[j].zext_ld = zero_ext_ld(D.NR); }
       B.add(s.A[j].p, s.W[j].p, F.info + k);
     }
     gram_batch_g(ga, b.nb, s.st);       // one launch per run of equal kernel kinds (blockIdx.z = latent)
     }
-    potrf_batch(B, D.ld, D.NR, D.NC, n, s.st, D.NC + nrhs);      // the rider rows NC + nrhs .. NR - 1 are zero padding
+    potrf_batch(B, D.ld, D.NR, D.NC, n, s.st, D.NC + nrhs, zext);      // the rider rows NC + nrhs .. NR - 1 are zero padding
     if (pk_dev) launch_lml_reduce(B.A, b.nb, D.ld, n, D.NC, nrhs, reinterpret_cast<double*>(pk_dev) + (size_t)b.k0 * nrhs, s.st, &B.info,
                                   reinterpret_cast<int*>(pk_dev + nout * sizeof(double)) + b.k0);
     else launch_lml_reduce(B.A, b.nb, D.ld, n, D.NC, nrhs, out.p + (size_t)b.k0 * nrhs, s.st);
@@ -6386,6 +6435,65 @@ int lmm_dev_potrf(double* A, int nrows, int ncols, int ld, double* Winv, int n_r
   LMM_CATCH
 }
 
+// lmm_dev_potrf with the caller's zero extents (lmm_emul.h; device, nrows / 64 ints: per 64-row block the number of leading columns
+// that hold +0 in all of its rows -- any lower bound of the true extents is valid, 0 everywhere leaves nothing out); zext = NULL is
+// lmm_dev_potrf.  With LMM_ZERO_EXTENTS=0 / lmm_dev_set_zero_extents(0) the extents are ignored.
+int lmm_dev_potrf_zext(double* A, int nrows, int ncols, int ld, double* Winv, int n_real, int* info_dev, const int* zext) {
+  if (!zext) return lmm_dev_potrf(A, nrows, ncols, ld, Winv, n_real, info_dev);
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!A || !Winv || !info_dev || nrows % 64 || ncols % 64 || nrows < ncols || ld < nrows || (ld & 1))
+    return fail(LMM_ERR_ARG, "bad arguments");
+  hipStream_t st = g.streams[0];
+  int* zx = zero_ext_scratch(nrows, 1, st);      // the padded layout potrf_batch takes; nullptr: switched off or fp32
+  if (zx) HIPCHK(hipMemcpyAsync(zx, zext, (size_t)(nrows / 64) * sizeof(int), hipMemcpyDeviceToDevice, st));
+  Batch B; B.add(A, Winv, info_dev);
+  potrf_batch(B, ld, nrows, ncols, n_real, st, -1, zx);
+  int hinfo = 0;
+  HIPCHK(hipMemcpyAsync(&hinfo, info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (hinfo == LMM_INFO_SYNC_TIMEOUT) return check_info(&hinfo, 1, 0);
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// The training Gram launch of the per-latent path (latent_lmls: train_gram_args, one batched launch per run of equal kinds) for nb
+// latents gp[0 .. nb) on the caller's device memory: matrix j (nrows x ncols, ld; nrows, ncols multiples of 64, ncols >= n) at
+// A + j * ld * ncols with the diagonal term noise[j] -- or noisevec (device, [nb][n]) -- and the nrider rider rows rider[j] (device,
+// [nb][nrider][n]).  zext (host, [nb][nrows / 64]): the zero extents the launch kept (LMM_ZERO_EXT_NONE = 0x7F7F7F7F for a row block
+// that is all zeros); all -1 when the switch is off or the compute dtype is Float32 (no extents are kept).
+int lmm_dev_train_gram(double* A, int ld, int nrows, int ncols, const double* x, int d, int n, const lmm_gp_t* gp, int nb, const double* noise,
+                       const double* noisevec, const double* rider, int nrider, int* zext) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!A || !x || !gp || !zext || (!noise && !noisevec) || nb < 1 || nb > LMM_MAX_BATCH || nrows % 64 || ncols % 64 || (ld & 1) || ld < nrows || ncols < n || n < 1 ||
+      nrows < ncols || nrider < 0 || nrows - ncols < nrider || (nrider > 0 && !rider))
+    return fail(LMM_ERR_ARG, "bad arguments");
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = resolve(gp, nb, d, ls)) return rc;
+  hipStream_t st = g.streams[0];
+  Dims D(n, nrider);
+  D.NC = ncols; D.NR = nrows; D.ld = ld;
+  int* zx = zero_ext_scratch(nrows, nb, st);
+  const int zld = zero_ext_ld(nrows);
+  GramArgs ga[LMM_MAX_BATCH];
+  for (int j = 0; j < nb; ++j) {
+    ga[j] = train_gram_args(ls->lat[j], x, d, n, D, A + (size_t)j * ld * ncols, noisevec ? 0.0 : noise[j], noisevec ? noisevec + (size_t)j * n : nullptr,
+                            rider ? rider + (size_t)j * nrider * n : nullptr, nrider);
+    if (zx) { ga[j].zext = zx + (size_t)j * zld; ga[j].zext_ld = zld; }
+  }
+  gram_batch_g(ga, nb, st);
+  std::vector<int> h((size_t)nb * zld, -1);
+  if (zx) HIPCHK(hipMemcpyAsync(h.data(), zx, h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int j = 0; j < nb; ++j)
+    for (int r = 0; r < nrows / 64; ++r) zext[(size_t)j * (nrows / 64) + r] = h[(size_t)j * zld + r];
+  return LMM_OK;
+  LMM_CATCH
+}
+
 // The back substitution of a gradient or posterior pass on its own: exactly launch_backsolve, on the main stream.
 int lmm_dev_backsolve(const double* L, size_t l_stride, int ld, const double* W, size_t w_stride, int nblk, double* z, size_t z_stride,
                       int nb) {
@@ -6490,6 +6598,36 @@ int lmm_dev_set_f64_screen(int on, int min_k) {
   if (min_k < 128) return fail(LMM_ERR_ARG, "lmm_dev_set_f64_screen: min_k >= 128");
   g_switches.f64_screen = on ? 1 : 0; g_switches.f64_screen_mink = min_k; g_switches.f64_screen_rounds = 0;
   return LMM_OK;
+}
+// Test hook of the zero extents (LMM_ZERO_EXTENTS, read once): on = 0 / 1; on < 0 goes back to the default (on).
+int lmm_dev_set_zero_extents(int on) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  (void)factor_switches();
+  g_switches.zero_extents = on < 0 ? FactorSwitches().zero_extents : (on ? 1 : 0);
+  return LMM_OK;
+}
+// Test hook of the size gate (LMM_ZERO_EXTENTS_MINCOLS, read once): a per-latent logpdf keeps extents for matrices of more than `cols`
+// columns; cols < 0 goes back to the default (2048).
+int lmm_dev_set_zero_extents_min_cols(int cols) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  (void)factor_switches();
+  g_switches.zero_extents_min_cols = cols < 0 ? FactorSwitches().zero_extents_min_cols : cols;
+  return LMM_OK;
+}
+// Test hook: on != 0 makes every factorisation that was given zero extents count its void work items and copy the counters to the
+// host when its launches are issued (that synchronises its stream).  out (may be NULL when cap = 0): 7 ints per region, update + leaf
+// and emulated update + leaf step of the LAST factorisation of this process, in launch order: step kind (PotrfStepKind), j0, h, N, M,
+// the count, and a shape word (region: its 128-row row tasks; update: 1 fused bulk rows + 2 x its strip mode).  The count: row tasks of a region launch that returned at entry; rest and column-0 items of an f64 update launch that did
+// (a split tile once); 256 x 256 tiles the emulation's screen marked without reading C, all matrices of the batch together.  Empty
+// when that factorisation had no extents.  Returns the number of steps (those beyond cap are counted, not written).
+int lmm_dev_zero_extent_stats(int on, int* out, int cap) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (cap < 0 || (cap > 0 && !out)) return -fail(LMM_ERR_ARG, "lmm_dev_zero_extent_stats: bad arguments");
+  g_zero_ext_stats = on ? 1 : 0;
+  const int n = (int)(g_zero_ext_last.size() / 7);
+  for (int i = 0; i < n && i < cap; ++i)
+    for (int q = 0; q < 7; ++q) out[7 * i + q] = g_zero_ext_last[7 * i + q];
+  return n;
 }
 // Test hook: FactorSwitches.deterministic (LMM_DETERMINISTIC, read once): no split-K atomics in the update launches.
 int lmm_dev_set_deterministic(int on) {

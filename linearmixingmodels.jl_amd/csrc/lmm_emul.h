@@ -246,6 +246,39 @@ LMM_HD inline bool emul_negligible(int K, unsigned long long ri, unsigned long l
   return emul_neg_at(emul_neg_bound(emul_ceil_log2(K), ri, rj), c);
 }
 
+// ---- zero extents: rows whose panel is exactly zero (void work) ----
+// The ZERO EXTENT of a block of 64 rows of a factor matrix is the number of leading columns, in whole 64-column blocks of the lower
+// triangle, in which every entry of those rows was stored as +0 by the launch that assembled the matrix.  The Gram launch keeps one
+// int per 64-row block and matrix (gram_body: every thread ORs the bits of what it stores, one __syncthreads_or per tile, atomicMin
+// of the tile's first column for a tile with a set bit; a row block that is all zeros keeps the memset's LMM_ZERO_EXT_NONE, larger
+// than any column).  The test is on all 64 bits: a stored -0 counts as an entry.  An update would keep it (-0 - (+0) = -0), but the
+// solve REPLACES the entry by its sum, +0, so leaving a solve out under a -0 would change a sign bit.  The kernels store products of
+// non-negative factors, so only a rider value of -0 or a negative variance can put one there, and such a tile is simply live.
+// Claim.  If every entry of the factor is finite, then L[i, p] = +0 for every row i of the block and every p < ext, at every point of
+// the factorisation, whatever the schedule.  Induction on p: C[i, p] starts as +0.  Every update of it subtracts
+// acc = sum_q L[i, q] L[p, q] over some q < p < ext, where L[i, q] = +0 by hypothesis: the accumulators start at +0 and every term is
+// fma(+0, finite, +0) = +0 (the product may be -0; +0 + -0 = +0 in round-to-nearest), so acc = +0 and +0 - (+0) = +0: the store
+// writes the bits that are there.  The solve multiplies the row's zeros by the finite inverse block, again sums of +-0 from +0: +0.
+// Consequences, for rows [r, r + 64 k) with ext = the minimum over their blocks:
+//   * an update item with the panel [j0, j0 + h) has acc = +0 in every entry when ext >= j0 + h, and stores what it loaded -- whatever
+//     C is there, zero or not (C - (+0) = C for every C, -0 and NaN included);
+//   * the atomic split-K form adds -acc = -0 once per part: C + (-0) = C for every C (+0 + -0 = +0, -0 + -0 = -0);
+//   * the emulation: the rows' maxima are 0, the convert's integers are 0, X = 0 and the CRT returns +0 (emul_crt_finish: sums of
+//     0 w_t from +0, q = +0), the combine subtracts ldexp(+0 sc_i sc_j, ..) = +0 for finite scales: T = +0, C - T = C bit for bit;
+//   * a region row task over the block column [c0, c0 + 128 P) reads only +0 of its own row and writes only +0 when ext >= c0 + 128 P.
+// A non-finite factor: the parent spreads 0 NaN into such rows, a build that leaves the work out does not.  A non-finite entry of a
+// square reaches a diagonal entry of its block column or the next (d - sum l^2 is NaN or -Inf), whose pivot test !(d > 0) fails and
+// records the pivot (diag_info_of / atomicCAS(info, 0, ..)): the status and the first failing pivot are the parent's; what lies
+// below and right of a failed pivot is unspecified in either build.
+#define LMM_ZERO_EXT_NONE 0x7F7F7F7F      // the value of a 0x7F memset: "no stored bit in this row block"
+#define LMM_ZERO_EXT_PAD 4                // entries past the last row block that a 256-row tile may read; they hold LMM_ZERO_EXT_NONE
+// zx: one matrix's extents.  True when the nblk 64-row blocks from row `row` are zero in every column below `need`.
+LMM_HD inline bool zero_ext_void(const int* zx, int row, int nblk, int need) {
+  int m = LMM_ZERO_EXT_NONE;
+  for (int q = 0; q < nblk; ++q) { const int e = zx[row / 64 + q]; m = e < m ? e : m; }
+  return m >= need;
+}
+
 // ---- the trapezoid's tile list, the live flags and the live id list ----
 // Lower-trapezoid tiles (tm tile rows, tn tile columns, j <= i) in supertiles of 8 tile rows x 4 tile columns: 32 consecutive tiles
 // share at most 12 operand panels.  xy (may be nullptr): 2 ints per tile, (tile row, tile column).  Returns the number of tiles.

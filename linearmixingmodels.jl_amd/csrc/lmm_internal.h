@@ -52,6 +52,9 @@ struct GramArgs {
   const LatentDev* terms; int nterms;          // kind LMM_KERNEL_SUM: the resolved terms (device; see LatentDev)
   int sum_per;                                 // kind LMM_KERNEL_SUM: some term is periodic or locally periodic (the instantiation that evaluates one)
   double inv_decay;                            // locally periodic: 1 / decay (unused by the other kinds)
+  // optional (Float64 storage only; row_shift = 0): this matrix's zero extents (lmm_emul.h), one int per 64-row block of the matrix,
+  // set to LMM_ZERO_EXT_NONE on the stream ahead of the launch; args[j] of a batched launch has zext = args[0].zext + j * zext_ld
+  int* zext; int zext_ld;
 };
 
 // The same assembly for up to LMM_MAX_BATCH same-shaped matrices in ONE launch (blockIdx.z = matrix): everything in `base`
@@ -112,6 +115,9 @@ struct NodeArgs {
   int Mb, MTb, bulk0;     // rows / 128-row tiles the bulk items cover (a ragged last 64 rows included); index of the first bulk item
   // the screen's flag bytes (lmm_potrf_plan.h, f64_screen_flag_at with MT and scr_nt): a "rest" item whose tile's byte is 0 returns at once; nullptr: no screen
   const unsigned char* scr; int scr_nt;
+  // zero extents (lmm_emul.h; matrix b at zext + b * zext_ld, nullptr: none): a rest item, or a column-0 item ti >= 1 of a launch without
+  // NODE_FUSE, whose rows are zero across the panel returns at entry; zstat (may be nullptr) counts them, split parts once
+  const int* zext; int zext_ld; int* zstat;
 };
 // Arguments of potrf_region_kernel (lmm_kernels.hip K2d): the columns [c0, c0 + 128 P) of every matrix of the batch, rows c0 .. c0 + M - 1.
 struct RegionArgs {
@@ -126,7 +132,12 @@ struct RegionArgs {
   long long* trace;       // optional (LMM_REGION_TRACE=1, tools/region_trace.py): start / end wall-clock ticks of every workgroup
   unsigned* claim; unsigned* claim_next;      // strict-progress build: this launch's claim counters, and the set it zeroes for the next one
   int claim_scramble;     // test hook (lmm_dev_claim_scramble): workgroups ask for the indices in REVERSE order, as if dispatched last-first
+  // zero extents (as in NodeArgs): a row task whose rows are zero across the block column returns before its first wait; zstat counts them
+  const int* zext; int zext_ld; int* zstat;
 };
+// The zero extents of a batch as the launchers take them (lmm_emul.h): matrix b's at p + b * ld, one int per 64-row block from matrix
+// row 0 and LMM_ZERO_EXT_PAD more; stat (may be nullptr): this step's counter of void work items.  p == nullptr: none, nothing is left out.
+struct ZeroExt { const int* p = nullptr; int ld = 0; int* stat = nullptr; };
 // Strict forward progress (lmm_set_strict_progress, default on): potrf_region_kernel's workgroups take their task INDEX in turn from a
 // per-matrix counter (region_claim) instead of reading it from blockIdx.x, and the fused update launches (NODE_FUSE: bulk items that wait for earlier items of the same launch)
 // are not used -- no kernel then relies on the order in which workgroups are dispatched.
@@ -151,8 +162,10 @@ const FactorSwitches& factor_switches();  // ... which fills it from the environ
 void region_plan_probe(int P, int nb, int Mb, int Mb_real, int cus, int na_full, int out[3]);   // lmm_dev_region_plan
 int region_flag_epoch(int set_to);                       // lmm_dev_flag_epoch: returns the current launch epoch; set_to >= 0 replaces it
 size_t region_flag_ints(int NR);          // ints per matrix that the flags of any region of a matrix with NR rows need
-void launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, const BatchInfo& flags, int ld, int NR,
-                   int c0, int width, int n_real, int nb, bool first_done, hipStream_t st, int rows_real = -1, const BatchPtr* S = nullptr);
+// returns the number of 128-row row tasks of the launch (the following row tasks are 64 rows high)
+int launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, const BatchInfo& flags, int ld, int NR,
+                   int c0, int width, int n_real, int nb, bool first_done, hipStream_t st, int rows_real = -1, const BatchPtr* S = nullptr,
+                   const ZeroExt& zx = ZeroExt());
 void launch_leaf128(const BatchPtr& A, size_t offD, int ld, const BatchPtr& W, size_t offW, const BatchPtr& W2, size_t offW2,
                     int gcol0, int n_real, const BatchInfo& info, int nb, hipStream_t st);
 // bulk rows of the panel at column r0 (its diagonal block factored, its inverse in W2): X = P Dinv' in place
@@ -161,7 +174,8 @@ void launch_panel_bulk(const BatchPtr& A, const BatchPtr& W2, int ld, int NR, in
 // strip (POTRF_STRIP_*): where the plan puts a ragged last 64 rows; nflags != nullptr (the plan's fused_bulk): also the bulk rows of that
 // panel, in the same launch (NODE_FUSE, flags of nf_stride ints per matrix)
 void launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, int ld, int NR, int j0, int h,
-                        int N, int n_real, int nb, hipStream_t st, int strip, int* nflags = nullptr, int nf_stride = 0, const unsigned char* scr = nullptr);
+                        int N, int n_real, int nb, hipStream_t st, int strip, int* nflags = nullptr, int nf_stride = 0, const unsigned char* scr = nullptr,
+                        const ZeroExt& zx = ZeroExt());
 // lmm_kernels_f32w.hip: fp32 C -= A B' on 256 x 256 tiles (one workgroup per CU); false: not launched (shape / switch), use the 128-tile kernel
 bool launch_gemm32w(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& A, size_t offA, int lda, const BatchPtr& B, size_t offB, int ldb,
                     int M, int N, int K, int lower, int nb, int cus, bool deterministic, hipStream_t st);
@@ -185,13 +199,16 @@ void emul_set_zero_skip(int on);             // 0: the GEMM walks every K block 
 // the live id list and its counts.
 struct EmulAmaxKeep { unsigned long long* out; int ld, row0, n; const unsigned long long* src[LMM_EMUL_COVER_MAX]; int scan0; unsigned long long* bmax; int cb0, ncb; };
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
-                              int G, int nmod, void* scratch, void* aux, void* screen, hipStream_t st, const EmulAmaxKeep* keep = nullptr);      // the first HIP error of its host-side calls
+                              int G, int nmod, void* scratch, void* aux, void* screen, hipStream_t st, const EmulAmaxKeep* keep = nullptr,
+                              const ZeroExt& zx = ZeroExt(), int zrow0 = 0);      // the first HIP error of its host-side calls
+// zx, zrow0 (both screens): the zero extents and the matrix row of the region's first row, which is also the panel's end: a tile whose
+// row blocks are zero there is stored as not live without reading C (and counted in zx.stat by the emulation's screen, in stat[0] by the f64 one)
 // lmm_kernels_i8.hip: the scan and the screen in front of a screened f64 update launch.  keep: as for an emulated
 // update (bmax may be nullptr: no block maxima are kept).  flags: f64_screen_flag_bytes; stat[0] += dead rest tiles, stat[1] = 1 when
 // the screen did its work; vote (may be nullptr): a word an earlier screen of the factorisation left its dead count in -- when it is
 // zero the scan and the screen return at entry and the flags say "live".  M, strip: the step's; the screen covers the rows the node launch takes.
 hipError_t launch_f64_screen(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int strip, int nb,
-                             const EmulAmaxKeep& keep, unsigned char* flags, int* stat, const int* vote, hipStream_t st);
+                             const EmulAmaxKeep& keep, unsigned char* flags, int* stat, const int* vote, hipStream_t st, const ZeroExt& zx = ZeroExt(), int zrow0 = 0);
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,
                    const BatchInfo& info, int nb, hipStream_t st);
 // no_splitk: never split the last round's tiles along K (their f64 atomics make the sum order run-dependent): bitwise reproducible

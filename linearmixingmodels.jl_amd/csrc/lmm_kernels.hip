@@ -273,6 +273,17 @@ __device__ __forceinline__ double kappa_sum(const LatentDev* __restrict__ T, int
 // 16-byte store of two consecutive rows of a Gram column (non-temporal stores measured no different: 4.7-4.9 TB/s either way, round 2)
 template <typename TS>
 __device__ __forceinline__ void gram_store(void* base, size_t idx, d2 v) { MatIO<TS>::st2(base, idx, v); }
+// Zero extents (lmm_emul.h): nz |= all the bits of the two stored values, for the tile's "some entry is not +0".  Two v_or3_b32 pinned
+// behind the store: left to the compiler, the OR chain regroups the eight column iterations of a tile and costs 23-26 registers
+// (an occupancy step in every plain kernel; profiles/zero_extents/kernel_resources.txt).
+__device__ __forceinline__ void gram_acc(unsigned& nz, d2 v) {
+  asm volatile("v_or3_b32 %0, %1, %2, %0\n\tv_or3_b32 %0, %3, %4, %0"
+               : "+v"(nz) : "v"(__double2loint(v.x)), "v"(__double2hiint(v.x)), "v"(__double2loint(v.y)), "v"(__double2hiint(v.y)));
+}
+// The tile's report: one __syncthreads_or, then thread 0 lowers the row block's extent to the tile's first column.  All 256 threads, a.zext != nullptr.
+__device__ __forceinline__ void gram_zext_report(const GramArgs& a, int ti, int tj, unsigned nz) {
+  if (__syncthreads_or(nz != 0u ? 1 : 0) != 0 && threadIdx.x == 0) atomicMin(a.zext + ti, tj * 64);
+}
 
 template <int KIND>
 __device__ __forceinline__ double kappa_t(double var, double r, double r2, double alpha) {
@@ -289,7 +300,7 @@ __device__ __forceinline__ double kappa_t(double var, double r, double r2, doubl
 }
 
 template <int KIND, typename TS>      // the three original kinds evaluate kappa on a.kind at run time, as they always have
-__device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int tj) {
+__device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int tj, unsigned* nz = nullptr) {
   const int t = threadIdx.x;
   const int i0 = ti * 64 + 2 * (t & 31);
   const int cg = t >> 5;
@@ -347,6 +358,7 @@ __device__ __forceinline__ void gram_tile_generic(const GramArgs& a, int ti, int
       v.x = out[0]; v.y = out[1];
     }
     MatIO<TS>::st2(a.A, (size_t)j * a.ld + (i0 - a.row_shift), v);
+    if (nz != nullptr) gram_acc(*nz, v);
   }
 }
 
@@ -381,7 +393,9 @@ __device__ __forceinline__ double exp_any(double x) {
 // 2 x 64 column exponentials are amortised over 64 elements per thread.  Guard: |a (x - c)| <= 40 inside the strip (else
 // the direct per-element exp is used, e.g. for unsorted inputs).  Relative error of the product form <= ~1e-14.  Matern12 takes the
 // same path with a = 1 / lengthscale and polynomial factor 1; RQ, like SE, is not separable and evaluates every element.
-template <int KIND, bool ND, typename TS>      // ND: the 1 < d <= 8 fast path is compiled in (kept out of the d == 1 kernel's register budget)
+// ZX: the launch keeps the zero extents of its matrices (a.zext, Float64 storage; lmm_emul.h) -- an instantiation of its own, so that
+// every other Gram launch runs the code it always ran
+template <int KIND, bool ND, typename TS, bool ZX>      // ND: the 1 < d <= 8 fast path is compiled in (kept out of the d == 1 kernel's register budget)
 __device__ __forceinline__ void gram_body(const GramArgs& a) {
   constexpr int DMAX = 8;                                     // input dimensions with a fast path (d > DMAX: generic tiles)
   __shared__ double colE[64], colF[64], colX[64];
@@ -425,6 +439,7 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
     if (!a.full && ti < tj) break;                          // lower tiles only
     const bool cols_in = (tj * 64 + 63 < a.n);
     const size_t out = (size_t)(tj * 64 + cg) * a.ld + (i0 - a.row_shift);      // element index of this thread's first store
+    unsigned nz = 0u;                                       // zero extents: bits of this thread's stores into the tile (ZX: Float64 storage)
     if (ND && rows_nd && cols_in) {                         // d > 1 interior tile: column points staged (pre-scaled) in LDS
       __syncthreads();
       if (a.ils == nullptr) { for (int e = t; e < 64 * a.d; e += 256) colP[e] = a.x[(size_t)tj * 64 * a.d + e] * a.inv_ls; }
@@ -454,13 +469,28 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
           if (i0 + 1 == j) v.y += da;
         }
         gram_store<TS>(a.A, out + (size_t)(8 * q) * a.ld, v);
+        if (ZX) gram_acc(nz, v);
       }
+      if (ZX) gram_zext_report(a, ti, tj, nz);
       continue;
     }
     const bool interior = rows_interior && cols_in;
-    if (!interior) { gram_tile_generic<KIND, TS>(a, ti, tj); continue; }
-    bool sep = false;
+    if (!interior) {
+      gram_tile_generic<KIND, TS>(a, ti, tj, ZX ? &nz : nullptr);
+      if (ZX) gram_zext_report(a, ti, tj, nz);
+      continue;
+    }
+    bool sep = false, far = false, far_zero = false;
     if (SEP) {
+      // The product form holds while D = a (c_r - c_c) can be exponentiated: it is clamped to +-700 below, so beyond that every
+      // element would come out as exp(-700 -+ ..) ~ 1e-304 whatever its distance -- where kappa is subnormal or has underflowed to 0.
+      // Such a tile takes the direct per-element form like any other tile outside the guards; from |D| = 830 on every element has
+      // a |xi - xj| >= 830 - 40 - 40, exp_nonpos returns 0 there (p 2^k with k <= -1082) and the direct form's value is var poly 0:
+      // stored as var 0 without the arithmetic (var poly finite: |var|, |D| <= 1e100).  Zeros as the direct form stores them are what
+      // the zero extents (lmm_emul.h) see.
+      const double Dt = aS * (cr - a.x[tj * 64]);           // uniform over the workgroup
+      far = !(fabs(Dt) <= 700.0);
+      far_zero = fabs(Dt) >= 830.0 && fabs(Dt) <= 1e100 && fabs(a.var) <= 1e100;
       __syncthreads();                                      // previous tile's readers are done with colE/colF/colX
       bool ok = true;
       if (t < 64) {
@@ -477,7 +507,15 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
       }
       sep = __syncthreads_and(ok && rows_ok) != 0;
     }
-    if (SEP && sep) {
+    if (SEP && sep && far_zero) {
+      d2 v;
+      v.x = a.var * 0.0; v.y = v.x;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        gram_store<TS>(a.A, out + (size_t)(8 * q) * a.ld, v);
+        if (ZX) gram_acc(nz, v);
+      }
+    } else if (SEP && sep && !far) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const int jl = cg + 8 * q;
@@ -498,6 +536,7 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
           if (i0 + 1 == j) v.y += da;
         }
         gram_store<TS>(a.A, out + (size_t)(8 * q) * a.ld, v);
+        if (ZX) gram_acc(nz, v);
       }
     } else {
       const double* xc = a.x + tj * 64 + cg;
@@ -515,8 +554,10 @@ __device__ __forceinline__ void gram_body(const GramArgs& a) {
           if (i0 + 1 == j) v.y += da;
         }
         gram_store<TS>(a.A, out + (size_t)(8 * q) * a.ld, v);
+        if (ZX) gram_acc(nz, v);
       }
     }
+    if (ZX) gram_zext_report(a, ti, tj, nz);
   }
 }
 
@@ -625,20 +666,21 @@ __device__ __forceinline__ void gram_body_per(const GramArgs& a) {
   }
 }
 
-template <int KIND, bool ND, typename TS>
+template <int KIND, bool ND, typename TS, bool ZX = false>
 __global__ __launch_bounds__(256) void gram_kernel(GramArgs a) {
   if (a.info_zero && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.info_zero = 0;
   if constexpr (KIND == LMM_KERNEL_SUM || KIND == LMM_KERNEL_SUM_PER) gram_body_sum<KIND, TS>(a);
   else if constexpr (KIND == LMM_KERNEL_PERIODIC || KIND == LMM_KERNEL_LOCALLY_PERIODIC) gram_body_per<KIND == LMM_KERNEL_LOCALLY_PERIODIC, ND, TS>(a);
-  else gram_body<KIND, ND, TS>(a);
+  else gram_body<KIND, ND, TS, ZX>(a);
 }
 
-template <int KIND, bool ND, typename TS>
+template <int KIND, bool ND, typename TS, bool ZX = false>
 __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
   GramArgs a = b.base;
   const int z = blockIdx.z;
   a.A = b.A[z]; a.var = b.var[z]; a.inv_ls = b.inv_ls[z]; a.ils = b.ils[z]; a.alpha = b.alpha[z]; a.diag_add = b.diag_add[z]; a.diag_vec = b.diag_vec[z]; a.rider = b.rider[z]; a.rider_sub = b.rider_sub[z];
   if (b.info_zero[z] && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *b.info_zero[z] = 0;
+  if constexpr (ZX) a.zext += (size_t)z * a.zext_ld;
   if constexpr (KIND == LMM_KERNEL_SUM || KIND == LMM_KERNEL_SUM_PER) {
     a.terms = b.terms[z]; a.nterms = b.nterms[z];
     gram_body_sum<KIND, TS>(a);
@@ -648,7 +690,7 @@ __global__ __launch_bounds__(256) void gram_batch_kernel(GramBatchArgs b) {
     a.inv_decay = b.inv_decay[z];
     gram_body_per<true, ND, TS>(a);
   } else {
-    gram_body<KIND, ND, TS>(a);
+    gram_body<KIND, ND, TS, ZX>(a);
   }
 }
 
@@ -2220,7 +2262,14 @@ __global__ __launch_bounds__(256, 2) void potrf_node_kernel(NodeArgs a) {
     const int item = blockIdx.x;
     if (a.mode & NODE_UPDATE) {
       const int n0 = a.nb * a.MT;
-      if (item < n0) { ti = item / a.nb; bidx = item - ti * a.nb; col0 = true; }
+      if (item < n0) {
+        ti = item / a.nb; bidx = item - ti * a.nb; col0 = true;
+        // zero extents (lmm_emul.h): rows that are zero across the panel; item (0, 0) carries the leaf, and a fused launch's bulk tiles wait for column 0
+        if (!fuse && ti >= 1 && a.zext != nullptr && zero_ext_void(a.zext + (size_t)bidx * a.zext_ld, a.j0 + a.h + ti * BM, BM / 64, a.j0 + a.h)) {
+          if (a.zstat != nullptr && threadIdx.x == 0) atomicAdd(a.zstat, 1);
+          return;
+        }
+      }
       else if (item >= a.strip0 && item < a.strip0 + a.nb * a.strip_n) {
         // the ragged last 64 rows of the region (rows a.M .. a.M + 63 below every column), one item per column tile: the 64 x 128 pipeline
         // (a separate gemm16h_kernel launch behind this one until round 4: N / 128 workgroups per matrix alone on the device for half
@@ -2268,6 +2317,12 @@ __global__ __launch_bounds__(256, 2) void potrf_node_kernel(NodeArgs a) {
         else {                                                     // the last matrix carries the launch's split-K tail
           bidx = a.nb - 1;
           gemm_work_item_from(q - bidx * a.rest_items, 1, BM, BN, a.N, 1, a.MT, a.full_items_last, a.splitk_last, part, nparts, ti, tj);
+        }
+        // Zero extents (lmm_emul.h): the tile's rows are zero across the panel, acc = +0: all parts of a split tile leave.  Uniform over
+        // the workgroup, ahead of the screen's byte and of every barrier.
+        if (a.zext != nullptr && zero_ext_void(a.zext + (size_t)bidx * a.zext_ld, a.j0 + a.h + ti * BM, BM / 64, a.j0 + a.h)) {
+          if (a.zstat != nullptr && part == 0 && threadIdx.x == 0) atomicAdd(a.zstat, 1);
+          return;
         }
         // The screen found that no entry of this tile can change by a bit: all parts of a split tile read the same byte
         // and leave.  Uniform over the workgroup and ahead of every barrier; a rest item publishes nothing and nobody waits for it.
@@ -3000,6 +3055,19 @@ __global__ __launch_bounds__(256, OCC) void potrf_region_kernel(RegionArgs a) {
     const bool tall = k < a.n128;
     const int roff = tall ? 128 * (a.P + k) : 128 * (a.P + a.n128) + 64 * (k - a.n128);
     const int real = a.M_real - roff;                    // rows of this tile that hold data (the rest is zero padding, before and after)
+    // zero extents (lmm_emul.h): the task's rows are +0 in every column of the block column and stay so: it leaves before its first wait
+    // or barrier (a row task signals nothing; under strict progress it has taken its index in turn above).  zero_ext_void spelled out on
+    // scalar values, and in the one-per-CU build only: any other form, and any form in the two-per-CU build, moved the register or scratch
+    // figures of the kernel (profiles/zero_extents/kernel_resources.txt), and LMM_REGION_OCC=2 is the slower build at every size
+    bool zvoid = false;
+    if (OCC == 1 && a.zext != nullptr) {
+      const int* zx = a.zext + (size_t)b * a.zext_ld + ((a.c0 + roff) >> 6);
+      const int e0 = __builtin_amdgcn_readfirstlane(zx[0]), e1 = tall ? __builtin_amdgcn_readfirstlane(zx[1]) : LMM_ZERO_EXT_NONE;
+      zvoid = real > 0 && min(e0, e1) >= a.c0 + 128 * a.P;
+    }
+    if (zvoid) {
+      if (a.zstat != nullptr && threadIdx.x == 0) atomicAdd(a.zstat, 1);
+    } else
     if (real > 16) { if (tall) potrf_region_row(a, node_lds, Am, b, a.P + k); else potrf_region_row64(a, node_lds, Am, b, roff); }
     else if (real > 0) potrf_region_row_thin(a, node_lds, Am, b, roff);
   }
@@ -5185,11 +5253,27 @@ void mode_dispatch(int mode, F&& f) {
   else f(IntTag<0>());
 }
 
+// Zero extents (GramArgs.zext, lmm_emul.h): the plain body keeps them, in an instantiation of its own; the sum, periodic and locally
+// periodic bodies do not, and neither does Float32 storage: a caller that asked gets 0 for every row block -- nothing is void.
+constexpr bool gram_keeps_zext(int kind) {
+  return kind != LMM_KERNEL_SUM && kind != LMM_KERNEL_SUM_PER && kind != LMM_KERNEL_PERIODIC && kind != LMM_KERNEL_LOCALLY_PERIODIC;
+}
+static void gram_no_zext(const GramArgs& a, int nmat, hipStream_t st) {
+  if (a.zext == nullptr) return;
+  for (int z = 0; z < nmat; ++z) (void)hipMemsetAsync(a.zext + (size_t)z * a.zext_ld, 0, (size_t)(a.nrows / 64) * sizeof(int), st);
+}
 void launch_gram(const GramArgs& a0, hipStream_t st) {
   GramArgs a = a0;
   a.cpw = gram_cpw(a.nrows / 64 - a.row_tile0, a.ncols / 64, 1);
   dim3 grid(a.nrows / 64 - a.row_tile0, (a.ncols / 64 + a.cpw - 1) / a.cpw);
-  gram_dispatch(a, [&](auto t) { typedef decltype(t) T; LMM_TS_LAUNCH((gram_kernel<T::K, T::ND, TS>), grid, dim3(256), 0, st, a); });
+  gram_dispatch(a, [&](auto t) {
+    typedef decltype(t) T;
+    if constexpr (gram_keeps_zext(T::K)) {
+      if (a.zext != nullptr && !g_f32) { hipLaunchKernelGGL((gram_kernel<T::K, T::ND, double, true>), grid, dim3(256), 0, st, a); return; }
+    }
+    gram_no_zext(a, 1, st);
+    LMM_TS_LAUNCH((gram_kernel<T::K, T::ND, TS>), grid, dim3(256), 0, st, a);
+  });
 }
 
 void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
@@ -5211,7 +5295,14 @@ void launch_gram_batch(const GramArgs* args, int nb, hipStream_t st) {
     b.base.cpw = gram_cpw(b.base.nrows / 64 - b.base.row_tile0, b.base.ncols / 64, j1 - j0);
     const GramArgs& a = b.base;
     dim3 grid(a.nrows / 64 - a.row_tile0, (a.ncols / 64 + a.cpw - 1) / a.cpw, j1 - j0);
-    gram_dispatch(a, [&](auto t) { typedef decltype(t) T; LMM_TS_LAUNCH((gram_batch_kernel<T::K, T::ND, TS>), grid, dim3(256), 0, st, b); });
+    gram_dispatch(a, [&](auto t) {
+      typedef decltype(t) T;
+      if constexpr (gram_keeps_zext(T::K)) {
+        if (a.zext != nullptr && !g_f32) { hipLaunchKernelGGL((gram_batch_kernel<T::K, T::ND, double, true>), grid, dim3(256), 0, st, b); return; }
+      }
+      gram_no_zext(a, j1 - j0, st);
+      LMM_TS_LAUNCH((gram_batch_kernel<T::K, T::ND, TS>), grid, dim3(256), 0, st, b);
+    });
     j0 = j1;
   }
 }
@@ -5360,13 +5451,15 @@ const FactorSwitches& factor_switches() {
     g_switches.f64_screen_mink = std::max(128, num("LMM_F64_SCREEN_MINK", 512));
     g_switches.f64_screen_rounds = getenv("LMM_F64_SCREEN_MINK") ? 0 : std::max(0, num("LMM_F64_SCREEN_ROUNDS", 1));      // an explicit threshold screens every update it admits
     g_switches.f64_screen_vote = num("LMM_F64_SCREEN_VOTE", 1) != 0;
+    g_switches.zero_extents = num("LMM_ZERO_EXTENTS", 1) != 0;
+    g_switches.zero_extents_min_cols = std::max(0, num("LMM_ZERO_EXTENTS_MINCOLS", 2048));
   }
   if (g_switches.emul_on < 0) g_switches.emul_on = num("LMM_F64_EMUL", 1) != 0;
   if (g_switches.emul_mink < 0) { const char* e = getenv("LMM_F64_EMUL_MINK"); g_switches.emul_mink = e ? std::max(128, atoi(e)) : 0; }
   return g_switches;
 }
 void launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, int ld, int NR, int j0, int h,
-                        int N, int n_real, int nb, hipStream_t st, int strip_mode, int* nflags, int nf_stride, const unsigned char* scr) {
+                        int N, int n_real, int nb, hipStream_t st, int strip_mode, int* nflags, int nf_stride, const unsigned char* scr, const ZeroExt& zx) {
   const int r0 = j0 + h, NT = (N + 127) / 128;     // N may end in a 64-column half tile
   if (nb <= 0 || N <= 0 || h <= 0) return;
   node_lds_attr();
@@ -5426,6 +5519,7 @@ void launch_update_leaf(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2
   long long items = nb * MT + (long long)nb * a.strip_n + (T > 0 ? (long long)(nb - 1) * a.rest_items + rest_last : 0);
   a.Mb = Mfull; a.MTb = MTb; a.bulk0 = (int)items;
   a.scr = scr; a.scr_nt = NT;
+  a.zext = zx.p; a.zext_ld = zx.ld; a.zstat = zx.stat;
   if (fuse) {
     a.mode |= NODE_FUSE; a.nflags = nflags; a.nf_stride = nf_stride; a.epoch = next_flag_epoch();
     items += (long long)nb * (MTb - 1);
@@ -5508,10 +5602,10 @@ void region_plan_probe(int P, int nb, int Mb, int Mb_real, int cus, int na_full,
   out[0] = r.n128; out[1] = r.row_tasks; out[2] = r.na;
 }
 size_t region_flag_ints(int) { return REGION_FLAG_INTS; }
-void launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, const BatchInfo& flags, int ld, int NR,
-                   int c0, int width, int n_real, int nb, bool first_done, hipStream_t st, int rows_real, const BatchPtr* S) {
+int launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, const BatchInfo& flags, int ld, int NR,
+                   int c0, int width, int n_real, int nb, bool first_done, hipStream_t st, int rows_real, const BatchPtr* S, const ZeroExt& zx) {
   const int P = width / 128, M = NR - c0, R = (M + 127) / 128;
-  if (nb <= 0 || P <= 0) return;
+  if (nb <= 0 || P <= 0) return 0;
   node_lds_attr();
   RegionArgs a{};
   a.A = A; a.W = W; a.W2 = W2; a.info = info; a.flags = flags; a.ld = ld; a.M = M; a.c0 = c0; a.P = P; a.R = R; a.n_real = n_real; a.nb = nb;
@@ -5546,6 +5640,7 @@ void launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, con
   if (trace_env) { if (hipMalloc((void**)&tr, ((size_t)tasks * nb * 2 + 64 * (size_t)nb) * sizeof(long long)) != hipSuccess) tr = nullptr; }
   a.trace = tr; a.ntasks = (int)tasks;
   a.claim_scramble = g_claim_scramble;
+  a.zext = zx.p; a.zext_ld = zx.ld; a.zstat = zx.stat;
   if (g_strict_progress && strict_claim_sets(st, &a.claim, &a.claim_next)) {
     if (occ == 1) hipLaunchKernelGGL((potrf_region_kernel<1, true>), dim3((unsigned)(tasks * nb)), dim3(256), LEAF_LDS_DOUBLES * 8, st, a);
     else hipLaunchKernelGGL((potrf_region_kernel<2, true>), dim3((unsigned)(tasks * nb)), dim3(256), LEAF_LDS_DOUBLES * 8, st, a);
@@ -5568,6 +5663,7 @@ void launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, con
     }
     (void)hipFree(tr);
   }
+  return a.n128;
 }
 
 void launch_diag64(const BatchPtr& A, size_t offA, int ld, const BatchPtr& W, size_t offW, int gcol0, int n_real,

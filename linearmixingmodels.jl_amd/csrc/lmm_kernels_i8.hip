@@ -233,9 +233,15 @@ const int2* emul_tiles(int tm, int tn, hipError_t* err) {
 // read is written by each group.
 constexpr int SCR_COLS = 16;
 __global__ __launch_bounds__(256) void emul_screen_kernel(BatchPtr A, int g0, size_t offC, int ldc, int M, int N, int K, const unsigned long long* __restrict__ amax, int as,
-                                                          const int2* __restrict__ tiles, int tm, int tn, unsigned char* flags) {
+                                                          const int2* __restrict__ tiles, int tm, int tn, unsigned char* flags,
+                                                          const int* __restrict__ zext, int zext_ld, int zrow0, int* zstat) {
   const int tid = threadIdx.x, z = blockIdx.y;
   const int2 t = tiles[blockIdx.x];
+  // zero extents (lmm_emul.h): the tile's four row blocks are zero across the panel, T = 0: not live, C unread.  Uniform, ahead of the barriers
+  if (zext != nullptr && zero_ext_void(zext + (size_t)(g0 + z) * zext_ld, zrow0 + t.x * TILE, TILE / 64, zrow0)) {
+    if (tid == 0) { flags[emul_flag_at(tm, tn, z, t.x, t.y)] = 0; if (zstat != nullptr) atomicAdd(zstat, 1); }
+    return;
+  }
   const int i = t.x * TILE + tid, j0 = t.y * TILE, jn = min(N, j0 + TILE), lgk = emul_ceil_log2(K);
   const unsigned long long* az = amax + (size_t)z * as;
   const unsigned long long ri = i < M ? az[i] : 0ull;
@@ -267,13 +273,23 @@ __global__ __launch_bounds__(256) void emul_screen_kernel(BatchPtr A, int g0, si
 // stat[0] counts the dead tiles, stat[1] says that the screen ran.  vote: a zero there (the first screened update of this
 // factorisation found no dead tile) makes every workgroup store "live" and return without reading C.
 __global__ __launch_bounds__(128) void f64_screen_kernel(BatchPtr A, size_t offC, int ldc, int M, int N, int K, const unsigned long long* __restrict__ amax, int as,
-                                                         int MT, int NT, unsigned char* flags, int* stat, const int* __restrict__ vote) {
+                                                         int MT, int NT, unsigned char* flags, int* stat, const int* __restrict__ vote,
+                                                         const int* __restrict__ zext, int zext_ld, int zrow0) {
   constexpr int T = LMM_F64_SCREEN_TILE;
   const int tid = threadIdx.x, ti = blockIdx.x, tj = blockIdx.y + 1, z = blockIdx.z;
   if (ti < tj) return;                                  // above the diagonal: no such item, the byte is never read
   unsigned char* flag = flags + f64_screen_flag_at(MT, NT, z, ti, tj);
   if (vote != nullptr && *vote == 0) {
     if (tid == 0) *flag = 1;
+    return;
+  }
+  // zero extents (lmm_emul.h): the node kernel leaves this item out whatever the byte says; dead, C unread.  Uniform, ahead of the barriers
+  if (zext != nullptr && zero_ext_void(zext + (size_t)z * zext_ld, zrow0 + ti * T, T / 64, zrow0)) {
+    if (tid == 0) {
+      *flag = 0;
+      atomicAdd(&stat[0], 1);
+      if (ti == MT - 1 && tj == 1 && z == 0) stat[1] = 1;
+    }
     return;
   }
   const int i = ti * T + tid, j0 = tj * T, jn = min(N, j0 + T), lgk = emul_ceil_log2(K);
@@ -701,7 +717,7 @@ void emul_set_zero_skip(int on) { g_emul_zero_skip = on < 0 ? -1 : (on ? 1 : 0);
 void emul_set_scratch_poison(int on) { g_emul_poison = on ? 1 : 0; }
 
 hipError_t launch_f64_screen(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int strip, int nb,
-                             const EmulAmaxKeep& keep, unsigned char* flags, int* stat, const int* vote, hipStream_t st) {
+                             const EmulAmaxKeep& keep, unsigned char* flags, int* stat, const int* vote, hipStream_t st, const ZeroExt& zx, int zrow0) {
   const int Mn = f64_screen_rows(M, strip);
   const int MT = (Mn + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE, NT = (N + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE;
   if (nb <= 0 || MT < 2 || NT < 2 || N > Mn || (K % BK) != 0 || (keep.scan0 % BK) != 0) return hipErrorInvalidValue;
@@ -710,7 +726,7 @@ hipError_t launch_f64_screen(const BatchPtr& C, size_t offC, int ldc, const Batc
   emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(keep, M);      // every row's first write: no memset
   if (keep.scan0 < K)
     emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep.scan0) / BK, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep.ld, keep.scan0, keep.out + keep.row0, bm, vote);
-  f64_screen_kernel<<<dim3(MT, NT - 1, nb), LMM_F64_SCREEN_TILE, 0, st>>>(C, offC, ldc, Mn, N, K, keep.out + keep.row0, keep.ld, MT, NT, flags, stat, vote);
+  f64_screen_kernel<<<dim3(MT, NT - 1, nb), LMM_F64_SCREEN_TILE, 0, st>>>(C, offC, ldc, Mn, N, K, keep.out + keep.row0, keep.ld, MT, NT, flags, stat, vote, zx.p, zx.ld, zrow0);
   return hipGetLastError();
 }
 
@@ -727,7 +743,7 @@ hipError_t launch_f64_screen(const BatchPtr& C, size_t offC, int ldc, const Batc
 // exist, or, with the screen switched off, the flags set to ones on the stream; emul_compact_kernel runs either way, and the list is
 // then the identity.  U is written for live tiles only and holds stale bytes elsewhere: U is read behind the flags only.
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
-                              int G, int nmod, void* scratch, void* aux, void* screen, hipStream_t st, const EmulAmaxKeep* keep) {
+                              int G, int nmod, void* scratch, void* aux, void* screen, hipStream_t st, const EmulAmaxKeep* keep, const ZeroExt& zx, int zrow0) {
   static EmulConst consts[LMM_EMUL_MAXMOD + 1];
   if (consts[nmod].nmod != nmod) consts[nmod] = emul_make_const(nmod);
   const EmulConst& c = consts[nmod];
@@ -780,7 +796,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
     unsigned char* flags = static_cast<unsigned char*>(screen) + S.flags;
     int* nlive = reinterpret_cast<int*>(static_cast<char*>(screen) + S.count);
     int* live = reinterpret_cast<int*>(static_cast<char*>(screen) + S.list);
-    if (screened) emul_screen_kernel<<<dim3(ntiles, gc), 256, 0, st>>>(C, g0, offC, ldc, M, N, K, am, as, tiles, tm, tn, flags);
+    if (screened) emul_screen_kernel<<<dim3(ntiles, gc), 256, 0, st>>>(C, g0, offC, ldc, M, N, K, am, as, tiles, tm, tn, flags, zx.p, zx.ld, zrow0, zx.stat);
     else {
       err = hipMemsetAsync(flags, 1, (size_t)gc * tm * tn, st);
       if (err != hipSuccess) return err;

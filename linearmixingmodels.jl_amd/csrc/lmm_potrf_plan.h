@@ -44,6 +44,14 @@ struct FactorSwitches {
   // the f64 kernel"): LMM_F64_SCREEN=0 turns that off, LMM_F64_SCREEN_MINK is the least K that earns its scan;
   // lmm_dev_set_f64_screen(on, min_k) writes both.  LMM_F64_SCREEN_VOTE=0: every screened update scans and screens, whatever the first one found.
   int f64_screen = 1, f64_screen_mink = 512, f64_screen_vote = 1;
+  // Zero extents (lmm_emul.h): the Gram launch of a per-latent logpdf keeps, per 64-row block, how many leading columns it stored as +0, and
+  // the region row tasks, update items and screens leave out work on rows that are zero across their panel.  LMM_ZERO_EXTENTS=0 (or
+  // lmm_dev_set_zero_extents(0)): no extents are kept and every launch does what it did without them.
+  int zero_extents = 1;
+  // ... and only for matrices of more than this many columns (LMM_ZERO_EXTENTS_MINCOLS, lmm_dev_set_zero_extents_min_cols): at 2048
+  // columns (`small`) the memset and the per-tile reduction cost 0.3 % and next to nothing is void, at 4096 (C1) the extents gain 17 %
+  // (profiles/zero_extents/ab_summary.txt).  A matrix one region launch factors whole has no item that can be void at any setting.
+  int zero_extents_min_cols = 2048;
   int f64_screen_rounds = 1; // f64_screen_pays: a screened launch has more work items than this many rounds of 2 per CU (0: no such rule; LMM_F64_SCREEN_ROUNDS)
 };
 

@@ -16,6 +16,11 @@
         one logpdf, then the counters the screen of the f64 update launches kept on the device (lmm_dev_f64_screen_stats): per
         screened update of the last batch, the dead 128 x 128 tiles of its rest tiles, and whether its screen ran or returned at
         entry after the vote.
+
+    python tools/emul_zero_skip_probe.py void [--lengthscale L]
+        one logpdf, then the work items the zero extents ("Rows whose panel is exactly zero") left out in the last
+        batch's factorisation (lmm_dev_zero_extent_stats): per region launch its void row tasks, per f64 update its void items, per
+        emulated update its void 256 x 256 tiles, all matrices of the batch together.
 """
 import argparse
 import ctypes as C
@@ -102,6 +107,36 @@ def screen(args):
     print("per K (dead, rest tiles): " + str({k: tuple(v) for k, v in sorted(tot.items())}))
 
 
+def void(args):
+    """The zero extents on the device: per step of the last batch's factorisation, the work items left out"""
+    import torch
+    import lmm_amd
+    from lmm_amd.workloads import synthetic_problem
+    lmm_amd.init(0)
+    lib = lmm_amd.load()
+    lib.lmm_dev_zero_extent_stats.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int]
+    lib.lmm_dev_zero_extent_stats.restype = C.c_int
+    P = synthetic_problem(M_LAT, P_OUT, N, "matern52", True, s2=0.1, seed=0)
+    fs = lmm_amd.independent_mogp([lmm_amd.GP(0.0, lmm_amd.Matern52Kernel(1.0, args.lengthscale)) for _ in range(M_LAT)])
+    f = lmm_amd.ILMM(fs, lmm_amd.Orthogonal(P["U"], P["S"]), shard=lmm_amd.latent_shard(M_LAT, 0, 1))
+    xd, yd = torch.from_numpy(P["x"]).cuda(), torch.from_numpy(P["y"]).cuda()
+    fx = f(lmm_amd.MOInputIsotopicByOutputs(xd, P_OUT), 0.1)
+    assert lib.lmm_dev_zero_extent_stats(1, None, 0) >= 0
+    val = lmm_amd.logpdf(fx, yd, True)
+    out = (C.c_int * (7 * 512))()
+    n = lib.lmm_dev_zero_extent_stats(0, out, 512)
+    names = {5: "f64 update", 6: "emulated update", 7: "region"}
+    print(f"lengthscale {args.lengthscale}: logpdf {val!r}; steps of the last batch ({M_LAT // 2} matrices) that take the zero extents, in launch order: "
+          "step | j0 h N M | void items | shape word (region: 128-row row tasks; update: fused + 2 strip mode)")
+    tot = {}
+    for i in range(min(n, 512)):
+        kind, j0, h, Nc, M, cnt, word = out[7 * i:7 * i + 7]
+        key = (names.get(kind, str(kind)), h)
+        tot[key] = tot.get(key, 0) + cnt
+        print(f"  {names.get(kind, kind):15s} | {j0:6d} {h:5d} {Nc:6d} {M:6d} | {cnt:6d} | {word}")
+    print("void items per (step, K): " + str({f"{k[0]} K={k[1]}": v for k, v in sorted(tot.items())}))
+
+
 def live(args):
     import torch
     import lmm_amd
@@ -151,10 +186,10 @@ def live(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["time", "live", "screen"])
+    ap.add_argument("mode", choices=["time", "live", "screen", "void"])
     ap.add_argument("--lengthscale", type=float, default=1.0)
     ap.add_argument("--noise", type=float, default=0.1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args()
-    {"time": timed, "live": live, "screen": screen}[a.mode](a)
+    {"time": timed, "live": live, "screen": screen, "void": void}[a.mode](a)
