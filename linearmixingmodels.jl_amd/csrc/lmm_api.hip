@@ -801,35 +801,41 @@ struct Batch {
 };
 
 static int g_in_flight = 1;       // batches that run concurrently on the slot streams (fork_slots / join_slots)
-static int g_emul_amax_reuse = 1; // lmm_dev_set_emul_amax_reuse: 0 = every emulated update scans its whole panel for the row maxima
 // lmm_dev_f64_screen_stats: with g_f64_screen_stats on, every factorisation ends by copying its screened steps' counters here (M, N, K, dead tiles, ran)
 static int g_f64_screen_stats = 0;
 static std::vector<int> g_f64_screen_last;
 // lmm_dev_zero_extent_stats: likewise, the void work items of every step that takes the zero extents (kind, j0, h, N, M, count, shape word)
 static int g_zero_ext_stats = 0;
 static std::vector<int> g_zero_ext_last;
+inline int sw_region_cols() { return factor_switches().region; }      // widest block column of one region launch (LMM_REGION; 0: off)
+// `bytes` of call scratch, a multiple of 8 as scratch_round makes them (lmm_potrf_plan.h); nullptr for none
+template <class T> T* scratch_bytes(size_t bytes) { return bytes ? reinterpret_cast<T*>(call_scratch(bytes / 8)) : nullptr; }
 // The zero extents of a batch (lmm_emul.h): [matrix][zero_ext_ld(NR)] ints in call scratch, set to LMM_ZERO_EXT_NONE on the stream; the
 // Gram launch that assembles the batch lowers them (GramArgs.zext).  nullptr when the switch is off or the matrices are not Float64.
-inline int zero_ext_ld(int NR) { return NR / 64 + LMM_ZERO_EXT_PAD; }
-inline int sw_region_cols() { return factor_switches().region; }      // widest block column of one region launch (LMM_REGION; 0: off)
 int* zero_ext_scratch(int NR, int nb, hipStream_t st) {
   if (g_f32 || !factor_switches().zero_extents) return nullptr;
   const size_t ints = (size_t)zero_ext_ld(NR) * nb;
-  int* p = reinterpret_cast<int*>(call_scratch((ints + 1) / 2));
-  guard_extent(p, (ints + 1) / 2, (ints + 1) / 2, 1, false, "zero extents");
+  int* p = scratch_bytes<int>(scratch_ints(ints));
+  guard_extent(p, scratch_ints(ints) / 8, scratch_ints(ints) / 8, 1, false, "zero extents");
   HIPCHK(hipMemsetAsync(p, 0x7F, ints * sizeof(int), st));
   return p;
 }
-// The emulation side of a Float64 factorisation's plan, whatever path and base case the other switches choose (lmm_dev_emul_plan, batch_plan)
-static PotrfPlan emul_view(int NR, int NC, int nb) {
-  FactorSwitches sw = factor_switches();
-  sw.panel128 = 1;
-  return plan_potrf(NR, NC, nb, -1, 1, 256, false, false, true, true, sw);
+static PotrfPlan emul_view(int NR, int NC, int nb) { return plan_potrf_emul_view(NR, NC, nb, factor_switches()); }
+// The test hooks' read-back of a per-step counter array (n ints; nullptr: the factorisation kept none): copied to the host, which
+// synchronises the stream, and handed to fmt step by step, which appends what the hook reports to `last`.
+template <class F>
+void read_step_counters(const int* dev, size_t n, const PotrfPlan& P, hipStream_t st, std::vector<int>& last, F fmt) {
+  last.clear();
+  if (dev == nullptr) return;
+  std::vector<int> h(n);
+  HIPCHK(hipMemcpyAsync(h.data(), dev, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t i = 0; i < P.steps.size(); ++i) fmt(P.steps[i], i, h, last);
 }
 
 // Entry point of the factorisation of a batch: columns [0, NC) of every matrix (rows 0 .. NR - 1 participate; W: NC / 64 inverse
-// diagonal blocks).  plan_potrf decides what is launched; this function takes the scratch the plan asks for -- all of it lives until
-// the API call ends -- and launches the steps.
+// diagonal blocks).  plan_potrf decides what is launched, which scratch it needs and how the steps are wired to it; this function
+// checks the plan once, takes the scratch it lists -- all of it lives until the API call ends -- and launches the steps.
 // zext (may be nullptr: nothing is left out): the batch's zero extents, matrix j's at zext + j * zero_ext_ld(NR) -- valid only if the
 // launch that wrote them is the only writer of the factor matrices so far.
 void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t st, int rows_real = -1, const int* zext = nullptr) {
@@ -837,37 +843,11 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
     guard_extent(B.A.p[j], NR, ld, NC, true, "factorisation (factor matrix)");
     guard_extent(B.W.p[j], 64, 64, (size_t)(NC / 64) * 64, true, "factorisation (inverse diagonal blocks)");
   }
-  const FactorSwitches& sw = factor_switches();
-  auto make_plan = [&]() { return plan_potrf(NR, NC, B.nb, rows_real, g_in_flight, device_cus(), g_f32 != 0, (ld & 1) != 0, g_strict_progress != 0, !g.emul_denied, sw); };
-  PotrfPlan P = make_plan();
-  auto per_matrix = [&](size_t doubles) {
-    BatchPtr S{};
-    double* base = call_scratch(doubles * B.nb);
-    for (int j = 0; j < B.nb; ++j) S.p[j] = base + doubles * j;
-    return S;
+  auto make_plan = [&]() {
+    return plan_potrf(NR, NC, B.nb, rows_real, g_in_flight, device_cus(), g_f32 != 0, (ld & 1) != 0, g_strict_progress != 0, !g.emul_denied, factor_switches(),
+                      zext != nullptr, g_zero_ext_stats != 0);
   };
-  BatchPtr W2{}, asst{};
-  BatchInfo flags{};
-  int* nflags = nullptr;
-  if (P.w2_doubles) W2 = per_matrix(P.w2_doubles);
-  if (P.region_cols > 0) {                 // dependency flags of the region launches: this stream's slice of the persistent, once-zeroed
-    int si = -1;                           // array (launches are told apart by epoch); an unknown stream gets a zeroed scratch
-    for (int s = 0; s < kMaxStreams; ++s) if (g.streams[s] == st) si = s;
-    const size_t fi = region_flag_ints(NR);
-    int* fl;
-    if (si >= 0 && g.region_flags) fl = g.region_flags + (size_t)si * LMM_MAX_BATCH * fi;
-    else {
-      fl = reinterpret_cast<int*>(call_scratch((fi * B.nb + 1) / 2));
-      HIPCHK(hipMemsetAsync(fl, 0, fi * sizeof(int) * B.nb, st));
-    }
-    for (int j = 0; j < B.nb; ++j) flags.p[j] = fl + fi * j;
-  }
-  if (P.node_flag_ints) {
-    const size_t ints = P.node_flag_ints * B.nb;
-    nflags = reinterpret_cast<int*>(call_scratch((ints + 1) / 2));
-    HIPCHK(hipMemsetAsync(nflags, 0, ints * sizeof(int), st));
-  }
-  if (P.asst_doubles) asst = per_matrix(P.asst_doubles);
+  PotrfPlan P = make_plan();
   // Scratch of the emulated updates: ONE block per stream per API call (g.emul_blocks): the batches a stream factors one after the
   // other share it (stream order keeps them apart), so an API call holds at most one block per stream it uses however many batches it
   // has -- plus the smaller ones a stream outgrew, if its batches differ in shape.  If a block cannot be had the f64 path runs, for the
@@ -887,67 +867,61 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
       }
     }
   }
-  // Row maxima of the emulated updates: one array per emulated step, [matrix][NR], kept until the API call ends like W2 -- a later
-  // update whose panel contains an earlier one's reads its maxima there instead of scanning those columns again (emul_amax_cover)
-  std::vector<unsigned long long*> amax_kept(P.steps.size(), nullptr);
-  // A screened f64 update (PotrfStep.screened) scans its panel the same way and keeps its array too; its screen leaves
-  // one flag byte per 128 x 128 tile in a block of this batch's own, sized for the step that needs most and rewritten by every
-  // screened step in stream order, and two counters per step (dead tiles; 1 when the screen ran), zeroed here.  The dead count of
-  // the first screened step with at least LMM_F64_SCREEN_VOTE_NT tile columns is the vote: zero there and the later scans and
-  // screens of this factorisation return at entry (decaying data has dead tiles from the third or fourth tile column on; a
-  // narrower update finds none either way and says nothing).
-  size_t scr_bytes = 0;
-  int scr_vote = -1;
-  for (size_t i = 0; i < P.steps.size(); ++i) {
-    const PotrfStep& s = P.steps[i];
-    if (s.kind == POTRF_EMUL_UPDATE_LEAF || (s.kind == POTRF_UPDATE_LEAF && s.screened)) amax_kept[i] = reinterpret_cast<unsigned long long*>(call_scratch((size_t)B.nb * NR));
-    if (s.kind == POTRF_UPDATE_LEAF && s.screened) {
-      scr_bytes = std::max(scr_bytes, f64_screen_flag_bytes(s.M, s.N, s.strip, B.nb));
-      if (scr_vote < 0 && (s.N + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE >= LMM_F64_SCREEN_VOTE_NT) scr_vote = (int)i;
+  if (const PotrfViolation v = plan_potrf_check(P, NR)) {
+    const PotrfStep& s = P.steps[v.step];
+    throw fail(LMM_ERR_ARG, "internal extent check failed: step %d (kind %d, %d x %d x %d at column %d of %d rows): %s: %lld against %lld", v.step, s.kind, s.M, s.N,
+               s.h, s.j0, NR, potrf_invariant_text(v.which), v.needs, v.has);
+  }
+  if (!P.zext) zext = nullptr;
+  guard_extent(zext, P.zext_bytes / 8, P.zext_bytes / 8, 1, false, "factorisation (zero extents)");
+  const size_t nsteps = P.steps.size();
+  auto per_matrix = [&](size_t doubles) {
+    BatchPtr S{};
+    double* base = call_scratch(doubles * B.nb);
+    for (int j = 0; j < B.nb; ++j) S.p[j] = base + doubles * j;
+    return S;
+  };
+  BatchPtr W2{}, asst{};
+  BatchInfo flags{};
+  if (P.w2_doubles) W2 = per_matrix(P.w2_doubles);
+  if (P.region_cols > 0) {                 // dependency flags of the region launches: this stream's slice of the persistent, once-zeroed
+    int si = -1;                           // array (launches are told apart by epoch); an unknown stream gets a zeroed scratch
+    for (int s = 0; s < kMaxStreams; ++s) if (g.streams[s] == st) si = s;
+    const size_t fi = region_flag_ints(NR);
+    int* fl;
+    if (si >= 0 && g.region_flags) fl = g.region_flags + (size_t)si * LMM_MAX_BATCH * fi;
+    else {
+      fl = scratch_bytes<int>(scratch_ints(fi * B.nb));
+      HIPCHK(hipMemsetAsync(fl, 0, fi * sizeof(int) * B.nb, st));
     }
+    for (int j = 0; j < B.nb; ++j) flags.p[j] = fl + fi * j;
   }
-  unsigned char* scr_flags = nullptr;
-  int* scr_stat = nullptr;
-  if (scr_bytes > 0) {
-    scr_flags = reinterpret_cast<unsigned char*>(call_scratch(scr_bytes / 8));
-    scr_stat = reinterpret_cast<int*>(call_scratch(P.steps.size()));
-    HIPCHK(hipMemsetAsync(scr_stat, 0, P.steps.size() * 2 * sizeof(int), st));
-  }
-  // live K blocks and dead pieces of the emulated updates' panels (lmm_emul.h): sized for the deepest update, rewritten by every
-  // group of every update in stream order.  Block maxima: ONE array for the factorisation, [matrix][128-column block][NR], up to the
-  // last column an emulated panel holds; the scan of an update writes the blocks it reads, a later update that covers them
-  // (emul_amax_cover) decides its live blocks and pieces from them without reading those columns (emul_block_max_bytes: batch_plan
-  // counts them)
-  // The screen's tile flags, live id list and counts (lmm_emul.h): a block of their own, sized for the update that needs most,
-  // rewritten by every group of every update in stream order like the aux block.
-  void* emul_aux_blk = nullptr;
-  void* emul_screen_blk = nullptr;
-  size_t emul_screen_bytes = 0;
-  unsigned long long* emul_bmax = nullptr;
-  int emul_ncb = 0;
-  if (P.emul_bytes > 0) {
-    int kmax = 128;
-    for (const PotrfStep& s : P.steps)
-      if (s.kind == POTRF_EMUL_UPDATE_LEAF) {
-        kmax = std::max(kmax, s.h); emul_ncb = std::max(emul_ncb, (s.j0 + s.h) / 128);
-        emul_screen_bytes = std::max(emul_screen_bytes, emul_screen_layout(s.M, s.N, std::min(s.group, B.nb), P.emul_nmod).total);
-      }
-    emul_aux_blk = call_scratch(emul_aux(NR, B.nb, kmax).total / 8);
-    if (emul_screen_bytes > 0) emul_screen_blk = call_scratch(emul_screen_bytes / 8);
-    if (emul_ncb > 0) emul_bmax = reinterpret_cast<unsigned long long*>(call_scratch(emul_block_max_bytes(NR, emul_ncb, B.nb) / 8));
-  }
-  // counters of the void work items, one per step, zeroed here (the test hook reads them)
-  int* zx_stat = nullptr;
-  if (zext != nullptr && (g_f32 || !sw.zero_extents)) zext = nullptr;
-  if (zext != nullptr) guard_extent(zext, ((size_t)zero_ext_ld(NR) * B.nb + 1) / 2, ((size_t)zero_ext_ld(NR) * B.nb + 1) / 2, 1, false, "factorisation (zero extents)");
-  if (zext != nullptr && g_zero_ext_stats) {
-    zx_stat = reinterpret_cast<int*>(call_scratch((P.steps.size() + 1) / 2));
-    HIPCHK(hipMemsetAsync(zx_stat, 0, P.steps.size() * sizeof(int), st));
-  }
-  std::vector<int> region_n128(P.steps.size(), 0);
-  auto zx_of = [&](const PotrfStep& s) { ZeroExt z; z.p = zext; z.ld = zero_ext_ld(NR); z.stat = zx_stat ? zx_stat + (&s - P.steps.data()) : nullptr; return z; };
+  int* nflags = scratch_bytes<int>(scratch_ints(P.node_flag_ints * B.nb));
+  if (nflags) HIPCHK(hipMemsetAsync(nflags, 0, P.node_flag_ints * B.nb * sizeof(int), st));
+  if (P.asst_doubles) asst = per_matrix(P.asst_doubles);
+  std::vector<unsigned long long*> amax_kept(nsteps, nullptr);
+  for (size_t i = 0; i < nsteps; ++i)
+    if (P.steps[i].keeps_amax) amax_kept[i] = scratch_bytes<unsigned long long>(P.amax_bytes);
+  unsigned char* scr_flags = scratch_bytes<unsigned char>(P.f64_flag_bytes);
+  int* scr_stat = scratch_bytes<int>(P.f64_stat_bytes);
+  if (scr_stat) HIPCHK(hipMemsetAsync(scr_stat, 0, nsteps * 2 * sizeof(int), st));
+  void* emul_aux_blk = scratch_bytes<void>(P.emul_aux_bytes);
+  void* emul_screen_blk = scratch_bytes<void>(P.emul_screen_bytes);
+  unsigned long long* emul_bmax = scratch_bytes<unsigned long long>(P.emul_bmax_bytes);
+  int* zx_stat = scratch_bytes<int>(P.zext_stat_bytes);
+  if (zx_stat) HIPCHK(hipMemsetAsync(zx_stat, 0, nsteps * sizeof(int), st));
+  std::vector<int> region_n128(nsteps, 0);
+  auto zx_of = [&](int si) { ZeroExt z; z.p = zext; z.ld = zero_ext_ld(NR); z.stat = zx_stat ? zx_stat + si : nullptr; return z; };
+  // the step's kept array, and the earlier steps' arrays its cover reads
+  auto keep_of = [&](int si, unsigned long long* bmax, int ncb) {
+    const PotrfStep& s = P.steps[si];
+    EmulAmaxKeep keep{amax_kept[si], NR, s.j0 + s.h, s.cover.n, {}, s.cover.scan0 - s.j0, bmax, s.j0 / 128, ncb};
+    for (int q = 0; q < s.cover.n; ++q) keep.src[q] = amax_kept[s.cover.step[q]];
+    return keep;
+  };
   auto leaf128 = [&](int c) { launch_leaf128(B.A, (size_t)c * ld + c, ld, B.W, (size_t)(c / 64) * 4096, W2, (size_t)(c / 128) * 16384, c, n_real, B.info, B.nb, st); };
-  for (const PotrfStep& s : P.steps) {
+  for (int si = 0; si < (int)nsteps; ++si) {
+    const PotrfStep& s = P.steps[si];
     const bool named = s.named();
     ProfScope ps(s.cls, s.work, st, named ? s.M : 0, named ? s.N : 0, named ? s.h : 0, s.bytes);
     const int j0 = s.j0, r0 = s.j0 + s.h;
@@ -958,73 +932,36 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
       case POTRF_UPDATE: launch_gemm_nt(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, B.A, offA, ld, s.M, s.N, s.h, 1, false, B.nb, st); break;
       case POTRF_LEAF128: leaf128(j0); break;
       case POTRF_PANEL_BULK: launch_panel_bulk(B.A, W2, ld, NR, j0, B.nb, st); break;
-      case POTRF_UPDATE_LEAF: {
-        const unsigned char* scr = nullptr;
+      case POTRF_UPDATE_LEAF:
         if (s.screened) {
-          const int si = (int)(&s - P.steps.data());
-          const size_t fb = f64_screen_flag_bytes(s.M, s.N, s.strip, B.nb);
-          if (fb > scr_bytes || r0 + s.M > NR || s.N > f64_screen_rows(s.M, s.strip))
-            throw fail(LMM_ERR_ARG, "internal extent check failed: screened update %d x %d at row %d needs %zu flag bytes, has %zu, of %d rows", s.M, s.N, r0, fb, scr_bytes, NR);
-          guard_extent(scr_flags, fb / 8, fb / 8, 1, false, "screened update (tile flags)");
-          guard_extent(scr_stat, P.steps.size(), P.steps.size(), 1, false, "screened update (counters)");
-          const EmulCover cov = emul_amax_cover(P.steps, si, g_emul_amax_reuse != 0, true);
-          EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0, nullptr, j0 / 128, 0};
-          for (int q = 0; q < cov.n; ++q) keep.src[q] = amax_kept[cov.step[q]];
-          const int* vote = (sw.f64_screen_vote && scr_vote >= 0 && si > scr_vote) ? scr_stat + 2 * scr_vote : nullptr;
-          HIPCHK(launch_f64_screen(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, s.strip, B.nb, keep, scr_flags, scr_stat + 2 * si, vote, st, zx_of(s), r0));
-          scr = scr_flags;
+          guard_extent(scr_flags, s.flag_bytes / 8, s.flag_bytes / 8, 1, false, "screened update (tile flags)");
+          guard_extent(scr_stat, nsteps, nsteps, 1, false, "screened update (counters)");
+          HIPCHK(launch_f64_screen(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, s.strip, B.nb, keep_of(si, nullptr, 0), scr_flags, scr_stat + 2 * si,
+                                   s.vote_from >= 0 ? scr_stat + 2 * s.vote_from : nullptr, st, zx_of(si), r0));
         }
-        launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, s.h, s.N, n_real, B.nb, st, s.strip, s.fused_bulk ? nflags : nullptr, (int)P.node_flag_ints, scr, zx_of(s));
+        launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, s.h, s.N, n_real, B.nb, st, s.strip, s.fused_bulk ? nflags : nullptr, (int)P.node_flag_ints,
+                           s.screened ? scr_flags : nullptr, zx_of(si));
         break;
-      }
-      case POTRF_EMUL_UPDATE_LEAF:
-        if (s.scratch > P.emul_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update needs %zu bytes of scratch, has %zu", s.scratch, P.emul_bytes);
+      case POTRF_EMUL_UPDATE_LEAF: {
         guard_extent(emul_blk, s.scratch / 8, s.scratch / 8, 1, false, "emulated update (scratch)");
-        {
-          const size_t sb = emul_screen_layout(s.M, s.N, std::min(s.group, B.nb), P.emul_nmod).total;
-          if (sb > emul_screen_bytes) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's screen needs %zu bytes, has %zu", sb, emul_screen_bytes);
-          guard_extent(emul_screen_blk, sb / 8, sb / 8, 1, false, "emulated update (screen)");
-        }
-        {
-          const int si = (int)(&s - P.steps.data());
-          const EmulCover cov = emul_amax_cover(P.steps, si, g_emul_amax_reuse != 0);
-          EmulAmaxKeep keep{amax_kept[si], NR, r0, cov.n, {}, cov.scan0 - j0, emul_bmax, j0 / 128, emul_ncb};
-          for (int q = 0; q < cov.n; ++q) keep.src[q] = amax_kept[cov.step[q]];
-          if (r0 + s.M > NR) throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's rows %d + %d exceed %d", r0, s.M, NR);
-          if ((j0 % 128) != 0 || (s.h % 128) != 0 || ((cov.scan0 - j0) % 128) != 0 || (j0 + s.h) / 128 > emul_ncb)
-            throw fail(LMM_ERR_ARG, "internal extent check failed: emulated update's panel [%d, %d) is not whole 128-column blocks below %d", j0, j0 + s.h, 128 * emul_ncb);
-          HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, emul_screen_blk, st, &keep, zx_of(s), r0));
-        }
+        guard_extent(emul_screen_blk, s.screen_bytes / 8, s.screen_bytes / 8, 1, false, "emulated update (screen)");
+        const EmulAmaxKeep keep = keep_of(si, emul_bmax, P.emul_ncb);
+        HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, emul_screen_blk, st, &keep, zx_of(si), r0));
         leaf128(r0);
         break;
-      case POTRF_REGION: region_n128[&s - P.steps.data()] = launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst, zx_of(s)); break;
-    }
-  }
-  if (g_f64_screen_stats) {      // test hook only: synchronises the stream
-    g_f64_screen_last.clear();
-    if (scr_stat != nullptr) {
-      std::vector<int> h(P.steps.size() * 2);
-      HIPCHK(hipMemcpyAsync(h.data(), scr_stat, h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      for (size_t i = 0; i < P.steps.size(); ++i)
-        if (P.steps[i].kind == POTRF_UPDATE_LEAF && P.steps[i].screened)
-          for (int v : {P.steps[i].M, P.steps[i].N, P.steps[i].h, h[2 * i], h[2 * i + 1]}) g_f64_screen_last.push_back(v);
-    }
-  }
-  if (g_zero_ext_stats) {        // test hook only: synchronises the stream
-    g_zero_ext_last.clear();
-    if (zx_stat != nullptr) {
-      std::vector<int> h(P.steps.size());
-      HIPCHK(hipMemcpyAsync(h.data(), zx_stat, h.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      for (size_t i = 0; i < P.steps.size(); ++i) {
-        const PotrfStep& s = P.steps[i];
-        if (s.kind == POTRF_UPDATE_LEAF || s.kind == POTRF_EMUL_UPDATE_LEAF || s.kind == POTRF_REGION)
-          for (int v : {(int)s.kind, s.j0, s.h, s.N, s.M, h[i], s.kind == POTRF_REGION ? region_n128[i] : (s.fused_bulk ? 1 : 0) + 2 * (int)s.strip})
-            g_zero_ext_last.push_back(v);
       }
+      case POTRF_REGION: region_n128[si] = launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst, zx_of(si)); break;
     }
   }
+  if (g_f64_screen_stats)        // test hook only
+    read_step_counters(scr_stat, nsteps * 2, P, st, g_f64_screen_last, [](const PotrfStep& s, size_t i, const std::vector<int>& h, std::vector<int>& last) {
+      if (s.kind == POTRF_UPDATE_LEAF && s.screened) last.insert(last.end(), {s.M, s.N, s.h, h[2 * i], h[2 * i + 1]});
+    });
+  if (g_zero_ext_stats)          // test hook only
+    read_step_counters(zx_stat, nsteps, P, st, g_zero_ext_last, [&](const PotrfStep& s, size_t i, const std::vector<int>& h, std::vector<int>& last) {
+      if (s.kind == POTRF_UPDATE_LEAF || s.kind == POTRF_EMUL_UPDATE_LEAF || s.kind == POTRF_REGION)
+        last.insert(last.end(), {(int)s.kind, s.j0, s.h, s.N, s.M, h[i], s.kind == POTRF_REGION ? region_n128[i] : (s.fused_bulk ? 1 : 0) + 2 * (int)s.strip});
+    });
 }
 
 // One matrix: the batch of one
@@ -1126,12 +1063,12 @@ void batch_plan(int ms, int* nb_per, int* nstreams_used, double bytes_per_latent
       double avail = (double)fr;
       for (const auto& kv : g.pool) avail += (double)kv.first;
       const double budget = 0.8 * avail;
-      // + one scratch block of the emulated updates per stream (potrf_batch: at most ~12 GB each), for working sets whose matrices
-      // have an emulated level at the batch size the plan starts from (emul_view: the plan potrf_batch makes; the shape is the
-      // square one of this working set, n = sqrt(bytes / 8) rounded up to whole panels, with one 64-row block of riders)
+      // + per stream what the plan's emul_stream_budget sets aside (the emulation block at its cap and the block maxima of all nce
+      // columns), for working sets whose matrices have an emulated level at the batch size the plan starts from (emul_view: the plan
+      // potrf_batch makes; the shape is the square one of this working set, n = sqrt(bytes / 8) rounded up to whole panels, with one
+      // 64-row block of riders)
       const int nce = (int)rup((size_t)std::sqrt(bytes_per_latent / 8.0), 128);
-      // and that batch's block maxima (8 bytes per row and 128-column block of every matrix, at most all nce columns)
-      const double per_stream = (!g_f32 && emul_view(nce + 64, nce, b).emul_bytes > 0) ? 12e9 + (double)emul_block_max_bytes(nce + 64, nce / 128, b) : 0.0;
+      const double per_stream = g_f32 ? 0.0 : emul_stream_budget(emul_view(nce + 64, nce, b), nce + 64, nce, b);
       while ((double)b * ns * bytes_per_latent + ns * per_stream > budget && (b > 1 || ns > 1)) {
         if (b > 1) b = (b + 1) / 2; else --ns;
         nbatches = (ms + b - 1) / b;
@@ -6699,7 +6636,7 @@ int lmm_dev_set_emul_group(int gcap) {
 // had kept any; the default, 1, reads what earlier updates kept (emul_amax_cover).  Results do not depend on it.
 int lmm_dev_set_emul_amax_reuse(int on) {
   g.err.clear();
-  g_emul_amax_reuse = on ? 1 : 0;
+  g_switches.emul_amax_reuse = on ? 1 : 0;
   return LMM_OK;
 }
 // Host-only (no GPU, no lmm_init needed): the emulation side of the plan potrf_batch makes for nb matrices of NR rows and NC columns.

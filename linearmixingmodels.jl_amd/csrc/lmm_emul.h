@@ -272,6 +272,8 @@ LMM_HD inline bool emul_negligible(int K, unsigned long long ri, unsigned long l
 // below and right of a failed pivot is unspecified in either build.
 #define LMM_ZERO_EXT_NONE 0x7F7F7F7F      // the value of a 0x7F memset: "no stored bit in this row block"
 #define LMM_ZERO_EXT_PAD 4                // entries past the last row block that a 256-row tile may read; they hold LMM_ZERO_EXT_NONE
+// ints per matrix of a batch's extents, [matrix][zero_ext_ld(NR)]: one per 64-row block and the pad
+inline int zero_ext_ld(int NR) { return NR / 64 + LMM_ZERO_EXT_PAD; }
 // zx: one matrix's extents.  True when the nblk 64-row blocks from row `row` are zero in every column below `need`.
 LMM_HD inline bool zero_ext_void(const int* zx, int row, int nblk, int need) {
   int m = LMM_ZERO_EXT_NONE;

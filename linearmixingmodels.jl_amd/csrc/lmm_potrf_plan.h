@@ -1,6 +1,9 @@
 // lmm_potrf_plan.h -- what the batched blocked Cholesky launches for a shape (DESIGN.md "what is launched for a shape").  Plain C++17,
 // no HIP: plan_potrf is a pure function of the shape, the batch, the device's CU count and the switches, so the schedule can be read
-// and tested without a GPU (lmm_dev_potrf_plan, tests/test_potrf_plan_host.py).  potrf_batch (lmm_api.hip) executes the step list.
+// and tested without a GPU (lmm_dev_potrf_plan, tests/test_potrf_plan_host.py).  The plan also owns the factorisation's scratch list,
+// every step's wiring to it (kept row maxima and their covers, the f64 screen's flags and vote) and the extent invariants between
+// them (plan_potrf_finish, plan_potrf_check; tests/c/potrf_scratch_check.cpp).  potrf_batch (lmm_api.hip) allocates what the plan
+// lists and launches the step list.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -40,6 +43,7 @@ struct FactorSwitches {
   int rule_always = kRuleAlways, rule_shape = kRuleShape;      // lmm_dev_set_f64_emul_rule
   double rule_outs = kRuleOuts;
   int emul_group_cap = 0;    // lmm_dev_set_emul_group: at most this many matrices per group of an emulated update (0: no cap)
+  int emul_amax_reuse = 1;   // lmm_dev_set_emul_amax_reuse: 0 = every scanning update reads its whole panel for the row maxima (emul_amax_cover)
   // The f64 update launches leave out the 128 x 128 tiles whose update cannot change a bit of C (DESIGN.md 4.17 "the same screen on
   // the f64 kernel"): LMM_F64_SCREEN=0 turns that off, LMM_F64_SCREEN_MINK is the least K that earns its scan;
   // lmm_dev_set_f64_screen(on, min_k) writes both.  LMM_F64_SCREEN_VOTE=0: every screened update scans and screens, whatever the first one found.
@@ -70,6 +74,11 @@ enum { POTRF_STRIP_NONE = 0, POTRF_STRIP_IN_LAUNCH = 1, POTRF_STRIP_SEPARATE = 2
 // Profile classes: the lmm_prof_class values of include/lmm_hip.h, which this header does not see (lmm_internal.h asserts they agree)
 enum { POTRF_CLS_UPDATE = 1, POTRF_CLS_UPDATE_NARROW = 2, POTRF_CLS_TRSM = 3, POTRF_CLS_DIAG = 4, POTRF_CLS_REGION = 5, POTRF_CLS_UPDATE_SHORT = 6 };
 
+// The kept row-maximum arrays a scanning step reads instead of scanning (emul_amax_cover, below): those of step[0 .. n), which hold
+// the maxima over the columns [j0, scan0) of its panel; the columns [scan0, j0 + h) are left to scan.
+#define LMM_EMUL_COVER_MAX 8
+struct EmulCover { int n = 0; int step[LMM_EMUL_COVER_MAX] = {}; int scan0 = 0; };
+
 struct PotrfStep {
   int kind;
   int j0, h, N, M;           // first column; depth K of the product (the block's width for the other kinds); columns; rows (from row j0 + h of an update)
@@ -80,6 +89,12 @@ struct PotrfStep {
   bool screened = false;             // UPDATE_LEAF: its panel's row maxima are scanned and kept, and the tiles of the column tiles 1.. are screened
   int update = -1;                   // UPDATE_LEAF, EMUL_UPDATE_LEAF: the step's entry in PotrfPlan.updates
   int group = 0; size_t scratch = 0; // EMUL_UPDATE_LEAF: matrices per group, scratch bytes at that group size (that entry's)
+  // The step's wiring to the plan's scratch (plan_potrf_finish):
+  bool keeps_amax = false;           // an emulated or screened update: it scans its panel's row maxima into a kept array of its own
+  EmulCover cover;                   // ... reading these earlier steps' kept arrays for the columns [j0, cover.scan0) instead
+  size_t flag_bytes = 0;             // screened: the bytes of the flag block its screen writes (f64_screen_flag_bytes)
+  int vote_from = -1;                // screened: the step whose counters carry the vote it listens to (-1: it scans and screens whatever was found)
+  size_t screen_bytes = 0;           // EMUL_UPDATE_LEAF: the bytes of the emulation's screen block one of its groups uses (emul_screen_layout)
   // the (M, N, K) ProfScope names: the 64-column path's diagonal blocks and solves go unnamed
   bool named() const { return kind != POTRF_DIAG64 && kind != POTRF_SOLVE64; }
 };
@@ -94,6 +109,29 @@ struct PotrfPlan {
   // The scratch block of the emulated updates: sized for the widest emulated level at G = min(4, nb, 12 GB / that level) matrices.  The
   // sizing also counts updates that end up inside a region launch, which only makes it generous.
   size_t emul_bytes = 0; int emul_G = 0, emul_nmod = 0;
+  // ---- what plan_potrf_finish adds: every other array of the factorisation, in the bytes potrf_batch requests (scratch_round) ----
+  // Each is an allocation of its own, so that the extent guard checks an access against the array it belongs to; all live until
+  // the API call ends, like W2.
+  // Row maxima: one array per step with keeps_amax, [matrix][NR] 8-byte words -- a later update whose panel contains an earlier one's
+  // reads its maxima there instead of scanning those columns again (PotrfStep.cover).
+  int amax_arrays = 0; size_t amax_bytes = 0;      // how many; bytes of each
+  // The f64 screen: one flag byte per 128 x 128 tile in ONE block, sized for the screened step that needs most and
+  // rewritten by every screened step in stream order, and two counters per step of the plan (dead tiles; 1 when the screen ran), zeroed
+  // before the first launch.  The dead count of the first screened step with at least LMM_F64_SCREEN_VOTE_NT tile columns is the vote:
+  // zero there and the later scans and screens of this factorisation return at entry (decaying data has dead tiles from the third or
+  // fourth tile column on; a narrower update finds none either way and says nothing).  vote_step is that step whether or not
+  // FactorSwitches.f64_screen_vote lets the later ones listen (PotrfStep.vote_from).
+  size_t f64_flag_bytes = 0, f64_stat_bytes = 0; int vote_step = -1;
+  // The emulated updates' small arrays, each rewritten by every group of every update in stream order.  Aux: live K blocks and dead
+  // pieces of the panels (emul_aux), sized for the deepest emulated step, emul_kmax.  Screen: tile flags, live id list and counts
+  // (emul_screen_layout), sized for the step that needs most.  Block maxima: ONE array for the factorisation, [matrix][128-column
+  // block][NR], up to the last column block an emulated step's panel holds, emul_ncb; the scan of an update writes the blocks it reads,
+  // a later update that covers them decides its live blocks and pieces from them without reading those columns.  batch_plan budgets
+  // the block maxima by emul_stream_budget, which counts all NC / 128 blocks.
+  int emul_kmax = 0, emul_ncb = 0; size_t emul_aux_bytes = 0, emul_screen_bytes = 0, emul_bmax_bytes = 0;
+  // Zero extents (lmm_emul.h): taken when the caller has them, the matrices are Float64 and FactorSwitches.zero_extents is on; then
+  // the caller's array holds zext_bytes, and, when the test hook asks, one counter of void work items per step, zeroed likewise.
+  bool zext = false; size_t zext_bytes = 0, zext_stat_bytes = 0;
   std::vector<PotrfStep> steps;        // in launch order
   std::vector<PotrfUpdate> updates;    // in the order of the recursion
 };
@@ -114,7 +152,8 @@ inline bool emul_pays(int M, int N, int K, int nb, const FactorSwitches& sw) {
   return nb * outs >= sw.rule_outs;
 }
 inline bool emul_takes(int M, int N, int K, int nb, const FactorSwitches& sw) { return emul_shape_ok(M, N, K) && emul_pays(M, N, K, nb, sw); }
-// The block for a factorisation's emulated updates (PotrfPlan.emul_bytes, .emul_G)
+// The block for a factorisation's emulated updates (PotrfPlan.emul_bytes, .emul_G); kEmulBlockCap: what G is cut to fit
+constexpr double kEmulBlockCap = 12e9;
 inline void emul_block_plan(PotrfPlan& P, int nb) {
   auto need = [&](int G) {
     size_t n = 0;
@@ -123,7 +162,7 @@ inline void emul_block_plan(PotrfPlan& P, int nb) {
   };
   const size_t one = need(1);
   if (one == 0) return;
-  P.emul_G = (int)std::max<size_t>(1, std::min<size_t>(std::min(4, nb), (size_t)12e9 / one));
+  P.emul_G = (int)std::max<size_t>(1, std::min<size_t>(std::min(4, nb), (size_t)kEmulBlockCap / one));
   P.emul_bytes = need(P.emul_G);
 }
 // Matrices per group of ONE update inside that block: as many as fit (a level below the widest needs less per matrix, so fewer groups
@@ -141,7 +180,7 @@ inline int emul_group(int M, int N, int K, int nb, const PotrfPlan& P, const Fac
 // i < M, j < N -- is not negligible (emul_negligible, lmm_emul.h).  Only the bytes of the "rest" tiles, 1 <= tj <= ti < MT, are
 // written and read.  MT counts the rows the node launch takes: a ragged last 64 rows that go to the strip are not among them.
 #define LMM_F64_SCREEN_TILE 128
-#define LMM_F64_SCREEN_VOTE_NT 4      // the vote is taken by the first screened update with at least this many tile columns (potrf_batch)
+#define LMM_F64_SCREEN_VOTE_NT 4      // the vote is taken by the first screened update with at least this many tile columns (PotrfPlan.vote_step)
 LMM_HD inline size_t f64_screen_flag_at(int MT, int NT, int z, int ti, int tj) { return ((size_t)z * MT + ti) * NT + tj; }
 inline int f64_screen_rows(int M, int strip) { return strip != POTRF_STRIP_NONE ? M - 64 : M; }
 inline size_t f64_screen_flag_bytes(int M, int N, int strip, int nb) {
@@ -272,18 +311,16 @@ struct PotrfPlanner {
 };
 
 // Row maxima kept across the emulated updates of one factorisation.  An emulated update scans its panel -- columns
-// [j0, j0 + h), rows from j0 + h -- for the largest |entry| of every row, and potrf_batch keeps that array until the factorisation
-// ends.  The entries below a factored block column never change again, so a later update whose panel contains those columns, and
+// [j0, j0 + h), rows from j0 + h -- for the largest |entry| of every row, and that array is kept until the factorisation ends
+// (PotrfStep.keeps_amax).  The entries below a factored block column never change again, so a later update whose panel contains those columns, and
 // whose rows begin at or below the kept array's first row, finds the exact maximum of that column range in it.  emul_amax_cover
 // covers a prefix [j0, scan0) of the panel of steps[si] with the kept arrays of earlier scanning steps: from c = j0, the widest
 // earlier panel that begins at c and ends at or before j0 + h (so its rows begin no later than ours, at j0 + h), then on from its
 // end.  The columns [scan0, j0 + h) are left to scan.  It reads the step list only: no shape of the recursion is assumed.
 // A scanning step is an emulated update or, with f64_too, a screened f64 update (PotrfStep.screened), which keeps the same array.
-// (An f64 step's array holds maxima only while the vote of the f64 screen has not switched its scans off -- potrf_batch passes
-// f64_too to f64 steps, which the same vote switches off, and to emulated steps only when there is no vote -- and an f64 step keeps no
-// block maxima unless told to: emul_step_scans says which steps of a plan an emulated step may take from.)
-#define LMM_EMUL_COVER_MAX 8
-struct EmulCover { int n = 0; int step[LMM_EMUL_COVER_MAX] = {}; int scan0 = 0; };
+// An f64 step's array holds maxima only while the vote of the f64 screen has not switched its scans off, and an f64 step keeps no
+// block maxima.  So plan_potrf_finish passes f64_too for the cover of a screened f64 step, which the same vote switches off and
+// which reads no block maxima, and never for the cover of an emulated step: that one takes from emulated steps' arrays only.
 inline bool emul_step_scans(const PotrfStep& e, bool f64_too) {
   return e.kind == POTRF_EMUL_UPDATE_LEAF || (f64_too && e.kind == POTRF_UPDATE_LEAF && e.screened);
 }
@@ -305,17 +342,110 @@ inline EmulCover emul_amax_cover(const std::vector<PotrfStep>& steps, int si, bo
   return c;
 }
 
+// ---- the factorisation's scratch and the steps' wiring to it ----
+// The scratch allocator counts in doubles, so every array is requested in whole doubles.  scratch_round is the ONE place that rounds:
+// a *_bytes field of the plan is the bytes actually requested, a multiple of 8, and potrf_batch asks for bytes / 8 doubles.
+inline size_t scratch_round(size_t bytes) { return (bytes + 7) & ~size_t(7); }
+inline size_t scratch_ints(size_t ints) { return scratch_round(ints * sizeof(int)); }
+// The last pass of plan_potrf, pure like the rest: reads the step list, NR, nb and the switches.  zext: the caller has zero extents
+// for this factorisation; zext_counters: the test hook wants the void work items counted.
+inline void plan_potrf_finish(PotrfPlan& P, int NR, int nb, bool f32, bool zext, bool zext_counters, const FactorSwitches& sw) {
+  const int n = (int)P.steps.size();
+  P.amax_bytes = scratch_round((size_t)nb * NR * 8);
+  if (P.emul_bytes > 0) P.emul_kmax = 128;
+  for (int i = 0; i < n; ++i) {
+    PotrfStep& s = P.steps[i];
+    const bool screened = s.kind == POTRF_UPDATE_LEAF && s.screened, emulated = s.kind == POTRF_EMUL_UPDATE_LEAF;
+    s.keeps_amax = screened || emulated;
+    if (!s.keeps_amax) continue;
+    ++P.amax_arrays;
+    s.cover = emul_amax_cover(P.steps, i, sw.emul_amax_reuse != 0, screened);
+    if (screened) {
+      s.flag_bytes = scratch_round(f64_screen_flag_bytes(s.M, s.N, s.strip, nb));
+      P.f64_flag_bytes = std::max(P.f64_flag_bytes, s.flag_bytes);
+      if (P.vote_step >= 0) s.vote_from = sw.f64_screen_vote ? P.vote_step : -1;
+      else if ((s.N + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE >= LMM_F64_SCREEN_VOTE_NT) P.vote_step = i;
+    } else {
+      s.screen_bytes = scratch_round(emul_screen_layout(s.M, s.N, std::min(s.group, nb), P.emul_nmod).total);
+      P.emul_screen_bytes = std::max(P.emul_screen_bytes, s.screen_bytes);
+      P.emul_kmax = std::max(P.emul_kmax, s.h);
+      P.emul_ncb = std::max(P.emul_ncb, (s.j0 + s.h) / 128);
+    }
+  }
+  if (P.f64_flag_bytes > 0) P.f64_stat_bytes = scratch_ints(2 * (size_t)n);
+  if (P.emul_bytes > 0) {
+    P.emul_aux_bytes = scratch_round(emul_aux(NR, nb, P.emul_kmax).total);
+    P.emul_bmax_bytes = scratch_round(emul_block_max_bytes(NR, P.emul_ncb, nb));
+  }
+  P.zext = zext && !f32 && sw.zero_extents != 0;
+  if (P.zext) P.zext_bytes = scratch_ints((size_t)zero_ext_ld(NR) * nb);
+  if (P.zext && zext_counters) P.zext_stat_bytes = scratch_ints((size_t)n);
+}
+// What batch_plan sets aside per stream for a batch with this plan, in bytes: upper bounds that need no second plan when the batch
+// is halved -- the emulation block at its cap, and block maxima for all NC / 128 column blocks (PotrfPlan.emul_bmax_bytes stops at
+// emul_ncb <= NC / 128, the same formula).  0 when nothing is emulated.
+inline double emul_stream_budget(const PotrfPlan& P, int NR, int NC, int nb) {
+  return P.emul_bytes > 0 ? kEmulBlockCap + (double)emul_block_max_bytes(NR, NC / 128, nb) : 0.0;
+}
+
+// ---- the extent invariants of a finished plan ----
+// Every one compares a step's figure with the plan's (or with NR); potrf_batch checks them once, before its first allocation.
+enum PotrfInvariant {
+  POTRF_INV_NONE = 0,
+  POTRF_INV_FLAG_BYTES,      // screened: its flag bytes fit the flag block
+  POTRF_INV_ROWS,            // screened, emulated: the update's rows j0 + h + M end within the NR rows of the matrix (and of a kept array)
+  POTRF_INV_SCREEN_COLS,     // screened: its N columns lie within the rows the screen covers (f64_screen_rows)
+  POTRF_INV_EMUL_SCRATCH,    // emulated: its scratch fits the emulation block
+  POTRF_INV_EMUL_SCREEN,     // emulated: its screen bytes fit the emulation's screen block
+  POTRF_INV_PANEL_BLOCKS,    // emulated: j0, h and scan0 - j0 are whole 128-column blocks (the block maxima are kept per block)
+  POTRF_INV_BMAX_BLOCKS,     // emulated: its panel ends within the emul_ncb column blocks of the block maxima
+  POTRF_INVARIANTS
+};
+struct PotrfViolation {
+  int which = POTRF_INV_NONE, step = -1;
+  long long needs = 0, has = 0;      // the two numbers of the relation (PANEL_BLOCKS: the offending column count and 128)
+  explicit operator bool() const { return which != POTRF_INV_NONE; }
+};
+inline const char* potrf_invariant_text(int which) {
+  static const char* const text[POTRF_INVARIANTS] = {"", "flag bytes of the screened update", "last row of the update against the matrix rows",
+    "columns of the screened update against the rows its screen covers", "scratch bytes of the emulated update", "screen bytes of the emulated update",
+    "columns of the emulated update's panel that are not whole 128-column blocks", "last column block of the emulated update's panel against the block maxima"};
+  return which > POTRF_INV_NONE && which < POTRF_INVARIANTS ? text[which] : "";
+}
+// The first violated invariant in step order (nothing: all hold)
+inline PotrfViolation plan_potrf_check(const PotrfPlan& P, int NR) {
+  for (int i = 0; i < (int)P.steps.size(); ++i) {
+    const PotrfStep& s = P.steps[i];
+    const int r0 = s.j0 + s.h;
+    auto bad = [&](int which, long long needs, long long has) { return PotrfViolation{which, i, needs, has}; };
+    if (s.kind == POTRF_UPDATE_LEAF && s.screened) {
+      if (s.flag_bytes > P.f64_flag_bytes) return bad(POTRF_INV_FLAG_BYTES, (long long)s.flag_bytes, (long long)P.f64_flag_bytes);
+      if (r0 + s.M > NR) return bad(POTRF_INV_ROWS, r0 + s.M, NR);
+      if (s.N > f64_screen_rows(s.M, s.strip)) return bad(POTRF_INV_SCREEN_COLS, s.N, f64_screen_rows(s.M, s.strip));
+    }
+    if (s.kind == POTRF_EMUL_UPDATE_LEAF) {
+      if (s.scratch > P.emul_bytes) return bad(POTRF_INV_EMUL_SCRATCH, (long long)s.scratch, (long long)P.emul_bytes);
+      if (s.screen_bytes > P.emul_screen_bytes) return bad(POTRF_INV_EMUL_SCREEN, (long long)s.screen_bytes, (long long)P.emul_screen_bytes);
+      if (r0 + s.M > NR) return bad(POTRF_INV_ROWS, r0 + s.M, NR);
+      for (int v : {s.j0, s.h, s.cover.scan0 - s.j0})
+        if ((v % 128) != 0) return bad(POTRF_INV_PANEL_BLOCKS, v, 128);
+      if (r0 / 128 > P.emul_ncb) return bad(POTRF_INV_BMAX_BLOCKS, r0 / 128, P.emul_ncb);
+    }
+  }
+  return PotrfViolation{};
+}
+
 // in_flight: batches that run concurrently on the slot streams; ld_odd: the leading dimension is odd (the panel kernels' 16-byte
 // accesses need an even one); emul_allowed: false once the API call could not get an emulation block (its remaining batches take the
-// f64 path without asking again)
+// f64 path without asking again); zext, zext_counters: plan_potrf_finish
 inline PotrfPlan plan_potrf(int NR, int NC, int nb, int rows_real, int in_flight, int cus, bool f32, bool ld_odd, bool strict, bool emul_allowed,
-                            const FactorSwitches& sw) {
+                            const FactorSwitches& sw, bool zext = false, bool zext_counters = false) {
   PotrfPlanner W{PotrfPlan{}, sw, NR, nb, rows_real >= 0 ? std::min(NR, rows_real) : NR, (double)nb, false, false, in_flight};
   PotrfPlan& P = W.P;
   W.cus = cus;
   // Float64 batches take the 128-column panel path; its W2 scratch -- one 128 x 128 inverse per panel and matrix -- lives until the API call ends
   P.panel128 = !(f32 || !sw.panel128 || NC < 128 || ld_odd);
-  if (!P.panel128) { W.cols64(0, NC); return P; }
+  if (!P.panel128) { W.cols64(0, NC); plan_potrf_finish(P, NR, nb, f32, zext, zext_counters, sw); return P; }
   P.w2_doubles = (size_t)(NC / 128) * 16384;
   // Default: the region kernel serves matrices that are ONE region (NC <= 1024: the whole factorisation in one launch, the small-n
   // path); larger matrices take it as the base case of the panel recursion where the rule below says so.
@@ -356,6 +486,12 @@ inline PotrfPlan plan_potrf(int NR, int NC, int nb, int rows_real, int in_flight
     if (u.emulated) { u.group = emul_group(u.M, u.N, u.K, nb, P, sw); u.scratch = emul_scratch_bytes(u.M, u.N, u.K, u.group, P.emul_nmod); }
   for (PotrfStep& s : P.steps)
     if (s.kind == POTRF_EMUL_UPDATE_LEAF) { s.group = P.updates[s.update].group; s.scratch = P.updates[s.update].scratch; }
+  plan_potrf_finish(P, NR, nb, f32, zext, zext_counters, sw);
   return P;
+}
+// The emulation side of a Float64 factorisation's plan, whatever path and base case the other switches choose (lmm_dev_emul_plan, batch_plan)
+inline PotrfPlan plan_potrf_emul_view(int NR, int NC, int nb, FactorSwitches sw) {
+  sw.panel128 = 1;
+  return plan_potrf(NR, NC, nb, -1, 1, 256, false, false, true, true, sw);
 }
 

@@ -319,5 +319,16 @@ def test_plan_check_program(tmp_path):
     assert out.returncode == 0 and out.stdout.strip().endswith(" 0 failures"), out.stdout[-500:] + out.stderr[-3000:]
 
 
+def test_scratch_check_program(tmp_path):
+    """tests/c/potrf_scratch_check.cpp: the plan's scratch sizes, covers, vote and listeners equal what the executor derived from the
+    step list while it sized its own scratch, on the whole grid; batch_plan's per-stream term is its former expression; and each of
+    the seven extent invariants of plan_potrf_check fails, naming its step, on a plan edited to violate exactly that one."""
+    exe = str(tmp_path / "potrf_scratch_check")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "linearmixingmodels.jl_amd", "csrc"),
+                           os.path.join(HERE, "c", "potrf_scratch_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip().endswith(" 0 failures"), out.stdout[-500:] + out.stderr[-3000:]
+
+
 if __name__ == "__main__":
     child(sys.argv[1])

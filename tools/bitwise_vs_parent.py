@@ -1,6 +1,7 @@
 """Outputs of the dense per-latent path and of the dense-H ILMM path under two builds of liblmm_hip.so, byte for byte, on one GPU.
 
     python tools/bitwise_vs_parent.py PARENT.so NEW.so > bitwise_vs_parent.txt
+    python tools/bitwise_vs_parent.py factor PARENT.so NEW.so >> bitwise_vs_parent.txt      (the factorisation alone, below)
 
 Three child processes, one after the other and never two at once, each under a time limit and with LMM_DETERMINISTIC=1 (no split-K
 atomics): PARENT, PARENT again (the control) and NEW, all on the same inputs.  The tool stops at the first child that exits non-zero.
@@ -18,7 +19,15 @@ The dense-H ILMM (one (mn) x (mn) factorisation, n m = 1400: eleven 128-column p
 loop with a dense 9 x 7 mixing matrix, in both compute dtypes: the prior logpdf with ILMM_ALLOW_DECOUPLED off and on (mixed kernels, seven
 identical kernels -- the decoupled branch -- and a Y of 3 columns), logpdf_and_gradient without and with inputs, the posterior's
 mean_and_var, mean_and_cov, logpdf and rand, a second conditioning batch with its own noise (mean_and_var, logpdf), the predictive
-gradient with inputs after one and after two batches (joint 1890), and the latent view's logpdf, rand and gradient."""
+gradient with inputs after one and after two batches (joint 1890), and the latent view's logpdf, rand and gradient.
+
+`factor`: n = 200 never reaches the region, panel, 64-column-tail, emulated or screened paths of the blocked Cholesky, so this mode
+factors (NR, NC) = (320, 256), (1088, 1024), (1280, 1216) and (2368, 2304) -- the smallest shapes at which each of them runs -- under
+the default switches, lmm_dev_set_f64_emul(1, 256, 16), lmm_dev_set_f64_screen(1, 256) and lmm_dev_set_zero_extents_min_cols(0):
+one matrix assembled by lmm_dev_train_gram (Matern-5/2, sorted inputs a lengthscale of 0.6 spacings apart, three rider rows) through
+lmm_dev_potrf and through lmm_dev_potrf_zext with the extents that launch kept -- factor, rider rows, inverse diagonal blocks and info
+word are the record -- and, as those entry points factor one matrix, a batch of three through lmm.logpdf and the posterior's
+mean_and_var of a three-latent OILMM with n = NC."""
 import os
 import subprocess
 import sys
@@ -204,16 +213,79 @@ def child(out_path):
     np.savez(out_path, **out)
 
 
+FACTOR_SHAPES = [(320, 256), (1088, 1024), (1280, 1216), (2368, 2304)]
+FACTOR_RIDERS = 3
+
+
+def child_factor(out_path):
+    sys.path.insert(0, ROOT)
+    import ctypes as C
+    import torch
+    import lmm_amd as lmm
+    from lmm_amd import _lib as L
+    lmm.init(0)
+    lib = lmm.load()
+    lib.lmm_dev_set_f64_emul.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.lmm_dev_set_f64_screen.argtypes = [C.c_int, C.c_int]
+    lib.lmm_dev_set_zero_extents_min_cols.argtypes = [C.c_int]
+    lib.lmm_dev_potrf_zext.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.lmm_dev_train_gram.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(L.GpT), C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    settings = {"default": lambda: 0, "emul from 256": lambda: lib.lmm_dev_set_f64_emul(1, 256, 16), "f64 screen from 256": lambda: lib.lmm_dev_set_f64_screen(1, 256),
+                "zero extents at every width": lambda: lib.lmm_dev_set_zero_extents_min_cols(0)}
+    out = {}
+
+    def rec(name, arrays):
+        ls = [np.asarray(a.cpu() if hasattr(a, "cpu") else a, dtype=np.float64).reshape(-1) for a in arrays]
+        out[name] = np.concatenate(ls + [np.array([float(len(ls))])])
+
+    for sname, apply in settings.items():
+        assert lib.lmm_dev_set_f64_emul(-1, 0, 0) == 0 and lib.lmm_dev_set_f64_screen(-1, 0) == 0 and lib.lmm_dev_set_zero_extents_min_cols(-1) == 0
+        assert apply() == 0, lib.lmm_last_error_string()
+        for NR, NC in FACTOR_SHAPES:
+            rng = np.random.default_rng(NC)
+            xd = torch.arange(NC, dtype=torch.float64, device="cuda")
+            rid = torch.from_numpy(rng.standard_normal(FACTOR_RIDERS * NC)).cuda()
+            noise = np.full(1, 0.1)
+            ext = np.full(NR // 64, -7, dtype=np.int32)
+            G = torch.zeros(NC * NR, dtype=torch.float64, device="cuda")
+            gps = L.gps_array([{"kind": "matern52", "variance": 1.0, "lengthscale": 0.6, "mean": 0.0}])
+            torch.cuda.synchronize()
+            L.check(lib.lmm_dev_train_gram(C.c_void_p(G.data_ptr()), NR, NR, NC, C.c_void_p(xd.data_ptr()), 1, NC, gps, 1, C.c_void_p(noise.ctypes.data), None,
+                                           C.c_void_p(rid.data_ptr()), FACTOR_RIDERS, C.c_void_p(ext.ctypes.data)))
+            zx = torch.from_numpy(ext).cuda()
+            for how, z in (("potrf", None), ("potrf_zext", zx)):
+                A = G.clone()
+                W = torch.zeros(NC // 64 * 4096, dtype=torch.float64, device="cuda")
+                info = torch.zeros(1, dtype=torch.int32, device="cuda")
+                torch.cuda.synchronize()
+                L.check(lib.lmm_dev_potrf_zext(C.c_void_p(A.data_ptr()), NR, NC, NR, C.c_void_p(W.data_ptr()), NC, C.c_void_p(info.data_ptr()),
+                                               None if z is None else C.c_void_p(z.data_ptr())))
+                torch.cuda.synchronize()
+                rec(f"{sname}: {how} {NR} x {NC}, {int((ext > 0).sum())} of {ext.size} row blocks with zeros", [A, W, info])
+            # a batch of three through the per-latent path
+            n, p, m = NC, 3, 3
+            x = np.arange(n, dtype=np.float64)
+            U = np.linalg.qr(rng.standard_normal((p, m)))[0]
+            f = lmm.ILMM(lmm.independent_mogp([lmm.GP(lmm.Matern52Kernel(1.0 + 0.1 * l, 0.6 + 0.7 * l)) for l in range(m)]), lmm.Orthogonal(U, np.linspace(2.0, 1.0, m)))
+            fx = f(lmm.MOInputIsotopicByOutputs(x, p), 0.1)
+            y = rng.standard_normal(n * p)
+            rec(f"{sname}: logpdf, 3 latents, n = {n}", [lmm.logpdf(fx, y)])
+            rec(f"{sname}: posterior mean_and_var, 3 latents, n = {n}", list(lmm.mean_and_var(lmm.posterior(fx, y)(lmm.MOInputIsotopicByOutputs(x[:40] + 0.3, p), 0.1))))
+    np.savez(out_path, **out)
+
+
 def main():
-    if len(sys.argv) == 3 and sys.argv[1] == "--child":
-        return child(sys.argv[2])
-    parent, new = sys.argv[1], sys.argv[2]
+    if len(sys.argv) == 3 and sys.argv[1] in ("--child", "--child-factor"):
+        return (child if sys.argv[1] == "--child" else child_factor)(sys.argv[2])
+    factor = sys.argv[1] == "factor"
+    parent, new = sys.argv[-2], sys.argv[-1]
     with tempfile.TemporaryDirectory() as tmp:
         runs = []
         for i, lib in enumerate([parent, parent, new]):
             path = os.path.join(tmp, f"run{i}.npz")
             env = dict(os.environ, LMM_HIP_LIB=os.path.abspath(lib), LMM_DETERMINISTIC="1")
-            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=env, timeout=CHILD_SECONDS).returncode
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-factor" if factor else "--child", path], env=env, timeout=CHILD_SECONDS).returncode
             if rc != 0:
                 print(f"child {i} ({lib}) exited with {rc}: stopping")
                 return 3
@@ -222,7 +294,7 @@ def main():
     unstable = {k[len("unstable::"):] for r in runs for k in r if k.startswith("unstable::")}
     a, c, b = ({k: v for k, v in r.items() if not k.startswith("unstable::")} for r in runs)
     print(f"# {parent} and {new}, each in its own process on one GPU, LMM_DETERMINISTIC=1, same inputs; every output compared byte for byte.")
-    print(f"# n = {N}, ns = {NS}, p = {P}, m = {M}, nz = {NZ}; control: {parent} twice.")
+    print(f"# factor mode: (NR, NC) in {FACTOR_SHAPES}; control: {parent} twice." if factor else f"# n = {N}, ns = {NS}, p = {P}, m = {M}, nz = {NZ}; control: {parent} twice.")
     differ = unsure = 0
     for k in a:
         if k not in b or k not in c or a[k].shape != b[k].shape:      # (a record that ends [refused] or [FAILED PIVOT] in one run only is missing in the others)
