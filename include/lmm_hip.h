@@ -222,6 +222,24 @@ int lmm_kernel_tag_quality_grad(int tag, double* out);
  * their gradients; the decoupled shortcut requires equal term lists). */
 int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag);
 int lmm_kernel_sum_grad(int tag, lmm_gp_grad_t* out);
+/* State space: sum latents.  The state-space entry points ("state space" below) serve a latent of kind LMM_KERNEL_SUM | (tag << 8)
+ * whose sum has exactly two terms, each a plain Matern12 / 32 / 52 with a scalar lengthscale (no tag) or an SHO (kind 12; its tag, if
+ * any, carries its quality), with state dimensions (1 / 2 / 3, SHO 2) adding up to at most 4: Matern12 + Matern12 / Matern32 / SHO /
+ * Matern52, Matern32 + Matern32 / SHO, SHO + SHO, in either order of the terms.  The sum's own variance v0 and lengthscale s0 fold
+ * into the terms: v = v0 v_c, l = s0 l_c, and an SHO term's period is s0 P.  Every other sum (three or more terms, Matern32 +
+ * Matern52 and other state dimensions above 4, another term kind, a term with per-dimension lengthscales) is refused there with
+ * LMM_ERR_UNSUPPORTED naming the latent, as before.  The tag comes from either creator:
+ *   lmm_kernel_sum_create            : Matern-only sums; the same gps run on every other entry point too.
+ *   lmm_kernel_sum_create_statespace : as above, and admits kind-12 terms (with a quality tag of lmm_kernel_tag_create_sho, or none:
+ *                    Q = 1).  nterms < 1 or a NULL -> LMM_ERR_ARG; nterms != 2, a term of another kind, a tag on a Matern term, or
+ *                    state dimensions adding up to more than 4 -> LMM_ERR_UNSUPPORTED; a bad term value, or an SHO term's tag that is
+ *                    not a live quality tag -> LMM_ERR_ARG.  Every entry point that is not a state-space one refuses a latent with such a
+ *                    tag with LMM_ERR_UNSUPPORTED naming the latent, before any device work.
+ * Per-term gradients come back through lmm_kernel_sum_grad, an SHO term's d/d quality through lmm_kernel_tag_quality_grad on the
+ * term's tag, and grad_gps[l].variance / .lengthscale are d/dv0 and d/ds0, as on the dense path.  The gradients with respect to
+ * locations (lmm_oilmm_logpdf_grad_statespace_x, lmm_dev_statespace_grad_x, lmm_oilmm_statespace_post_mean_and_var_grad_xs) refuse a
+ * sum latent with LMM_ERR_UNSUPPORTED naming it: the second component of its state is not f'. */
+int lmm_kernel_sum_create_statespace(int nterms, const lmm_gp_t* terms, int* tag);
 
 /* ---- lifetime -------------------------------------------------------------------------- */
 int lmm_init(int device);                 /* bind this process to HIP device `device`, create streams */
@@ -736,6 +754,12 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
  *   lmm_dev_statespace_grad_sho : the same block with grad_theta = {d lml / d variance, d lml / d lengthscale, d lml / d quality} (3
  *                    values; the third is 0 for a Matern latent): lmm_dev_statespace_grad keeps its two-value output, which cannot
  *                    carry an SHO latent's quality.
+ *   lmm_dev_statespace_grad_sum : the same block for a sum latent ("State space: sum latents" above; a plain latent is served too):
+ *                    grad_theta holds 6 values, the seeds of the sum's first term in the library's order of the terms (Matern12,
+ *                    Matern32, SHO, Matern52; two terms of one kind keep the caller's order), then those of its second: d lml / d V_c, d lml / d E_c and, for an SHO term,
+ *                    d lml / d quality, with V_c = v0 v_c and E_c = s0 l_c the term's own variance and lengthscale (period); the
+ *                    slots behind the last seed are 0.  lmm_dev_statespace_grad and lmm_dev_statespace_grad_sho refuse a sum latent with
+ *                    LMM_ERR_UNSUPPORTED naming it (latent 0): their two or three values cannot carry its seeds.
  *   lmm_oilmm_logpdf_grad_statespace_x : lmm_oilmm_logpdf_grad_statespace with one more output, grad_x (n values in the order of the
  *                    sorted x, host or device; may be NULL): d logpdf / d x_t, in O(n).  The value depends on x through the spacings
  *                    dt_t = x_t - x_{t-1} alone, and spacing t through the predicted state (mp, Pp) of point t alone: with the
@@ -790,6 +814,8 @@ int lmm_oilmm_logpdf_grad_statespace(const double* x, int n, const double* y, in
 int lmm_dev_statespace_grad(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
                             double* lml, double* grad_r, double* grad_w, double* grad_theta);
 int lmm_dev_statespace_grad_sho(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
+                                double* lml, double* grad_r, double* grad_w, double* grad_theta);
+int lmm_dev_statespace_grad_sum(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
                                 double* lml, double* grad_r, double* grad_w, double* grad_theta);
 int lmm_oilmm_logpdf_grad_statespace_x(const double* x, int n, const double* y, int p,
                                        const double* U, const double* S, int m, double sigma2,

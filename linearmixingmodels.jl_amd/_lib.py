@@ -24,7 +24,7 @@ KERNEL_SHO = 12             # LMM_KERNEL_SHO: the damped oscillator, a base kind
 # Every symbol include/lmm_hip.h declares (tests/test_abi.py checks the library exports each one).
 SYMBOLS = [
     "lmm_init", "lmm_shutdown", "lmm_last_error_string", "lmm_last_error_detail", "lmm_device_synchronize", "lmm_release_cached_memory",
-    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_kernel_tag_create_periodic", "lmm_kernel_tag_rho_grad", "lmm_kernel_tag_create_locally_periodic", "lmm_kernel_tag_decay_grad", "lmm_kernel_tag_create_sho", "lmm_kernel_tag_quality_grad", "lmm_kernel_sum_create", "lmm_kernel_sum_grad", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
+    "lmm_stream_wait_caller", "lmm_ard_create", "lmm_ard_destroy", "lmm_ard_grad", "lmm_kernel_tag_create", "lmm_kernel_tag_alpha_grad", "lmm_kernel_tag_create_periodic", "lmm_kernel_tag_rho_grad", "lmm_kernel_tag_create_locally_periodic", "lmm_kernel_tag_decay_grad", "lmm_kernel_tag_create_sho", "lmm_kernel_tag_quality_grad", "lmm_kernel_sum_create", "lmm_kernel_sum_grad", "lmm_kernel_sum_create_statespace", "lmm_set_compute_dtype", "lmm_get_compute_dtype", "lmm_set_projection_dtype", "lmm_get_projection_dtype", "lmm_comm_get_unique_id", "lmm_comm_init_rank", "lmm_comm_info", "lmm_allreduce_sum_f64", "lmm_allreduce_max_f64",
     "lmm_comm_destroy",
     "lmm_set_strict_progress", "lmm_get_strict_progress", "lmm_dev_claim_scramble", "lmm_orthogonal_validate", "lmm_oilmm_logpdf", "lmm_oilmm_logpdf_grad", "lmm_oilmm_post_logpdf_grad", "lmm_oilmm_post_logpdf_grad_seq", "lmm_ilmm_logpdf_grad", "lmm_ilmm_post_logpdf_grad", "lmm_ilmm_post_logpdf_grad_seq", "lmm_ilmm_post_latent_logpdf_grad_seq", "lmm_oilmm_logpdf_grad_x", "lmm_oilmm_post_logpdf_grad_seq_x", "lmm_ilmm_logpdf_grad_x",
     "lmm_ilmm_post_logpdf_grad_seq_x", "lmm_ilmm_post_latent_logpdf_grad_seq_x", "lmm_oilmm_logpdf_multi", "lmm_reorder", "lmm_ilmm_logpdf", "lmm_ilmm_logpdf_ex", "lmm_ilmm_logpdf_multi", "lmm_mogp_logpdf", "lmm_mogp_logpdf_diag",
@@ -35,7 +35,7 @@ SYMBOLS = [
     "lmm_oilmm_elbo", "lmm_oilmm_sparse_posterior_create", "lmm_sparse_post_destroy", "lmm_oilmm_sparse_mean_and_var", "lmm_dev_sparse_moments",
     "lmm_oilmm_elbo_grad", "lmm_dev_sparse_grad",
     "lmm_oilmm_logpdf_statespace", "lmm_oilmm_mean_and_var_statespace", "lmm_dev_statespace_filter", "lmm_dev_statespace_smooth",
-    "lmm_oilmm_logpdf_grad_statespace", "lmm_dev_statespace_grad", "lmm_dev_statespace_grad_sho",
+    "lmm_oilmm_logpdf_grad_statespace", "lmm_dev_statespace_grad", "lmm_dev_statespace_grad_sho", "lmm_dev_statespace_grad_sum",
     "lmm_oilmm_logpdf_grad_statespace_x", "lmm_dev_statespace_grad_x", "lmm_oilmm_statespace_post_mean_and_var_grad_xs",
     "lmm_oilmm_rand_statespace", "lmm_dev_statespace_sample", "lmm_dev_statespace_sample_posterior",
     "lmm_oilmm_statespace_posterior_create", "lmm_statespace_post_destroy", "lmm_oilmm_statespace_post_mean_and_var",
@@ -77,6 +77,7 @@ STATESPACE_ARGTYPES = {
     "lmm_oilmm_logpdf_grad_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "lmm_dev_statespace_grad": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
     "lmm_dev_statespace_grad_sho": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "lmm_dev_statespace_grad_sum": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
     "lmm_oilmm_logpdf_grad_statespace_x": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "lmm_dev_statespace_grad_x": [_P, _I, _P, _P, _P, _I, _P],
     "lmm_oilmm_statespace_post_mean_and_var_grad_xs": [_P, _P, _I, _P, _P, _P],
@@ -413,25 +414,29 @@ class ArdTags:
         self.terms = [None] * m
         self._lib = None
 
-    def create_sum(self, l: int, terms: Sequence[dict]) -> int:
-        """latent l's sum tag over the term descriptors `terms` (their own factor / alpha tags are created first)."""
-        self._lib = self._lib or load()
+    def create_sum(self, l: int, terms: Sequence[dict], statespace: bool = False) -> int:
+        """latent l's sum tag over the term descriptors `terms` (their own factor / alpha tags are created first).  statespace (the
+        state-space functions' arrays, statespace_gps_array): a sum with an SHO term is registered with
+        lmm_kernel_sum_create_statespace, which admits it; every other sum, and every sum of another caller, with
+        lmm_kernel_sum_create, which the dense entry points serve too."""
         n = len(terms)
         if not 1 <= n <= SUM_MAX_TERMS:
             raise ValueError(f"a sum kernel has 1..{SUM_MAX_TERMS} terms, got {n}")
-        for c, t in enumerate(terms):
-            if t["kind"] == "sho":
-                raise NotImplementedError(f"latent {l}: an SHO term inside a sum kernel is not served (term {c})")
+        sho = [c for c, t in enumerate(terms) if t["kind"] == "sho"]
+        if sho and not statespace:
+            raise NotImplementedError(f"latent {l}: an SHO term inside a sum kernel is not served (term {sho[0]})")
+        self._lib = self._lib or load()
         tarr = gps_array(terms)
         self.terms[l] = tarr.ard
         t = C.c_int()
-        check(self._lib.lmm_kernel_sum_create(n, tarr, C.byref(t)))
+        check((self._lib.lmm_kernel_sum_create_statespace if sho else self._lib.lmm_kernel_sum_create)(n, tarr, C.byref(t)))
         self.tags[l] = t.value
         return t.value
 
     def sum_grad(self, l: int, d: int) -> list:
         """Per-term gradients of sum latent l after a gradient call: [{"variance", "lengthscale" (float, or the length-d array
-        d logpdf / d lengthscale_k of a term with per-dimension lengthscales), "alpha" (RQ terms), "r" (periodic and locally periodic terms), "decay" (locally periodic terms)}, ...]."""
+        d logpdf / d lengthscale_k of a term with per-dimension lengthscales), "alpha" (RQ terms), "r" (periodic and locally periodic terms), "decay" (locally periodic terms),
+        "quality" (SHO terms of a state-space sum whose descriptor has one; "lengthscale" is then d / d period)}, ...]."""
         ta = self.terms[l]
         n = len(ta.tags)
         out = (GpGradT * n)()
@@ -445,6 +450,8 @@ class ArdTags:
                 e["r"] = ta.rho_grad(c)
             if ta.has_decay[c]:
                 e["decay"] = ta.decay_grad(c)
+            if ta.has_quality[c]:
+                e["quality"] = ta.quality_grad(c)
             res.append(e)
         return res
 
@@ -544,7 +551,7 @@ def sho_quality(q) -> float:
     return q
 
 
-def gps_array(gps: Sequence[dict]):
+def gps_array(gps: Sequence[dict], statespace: bool = False):
     """lmm_gp_t array of latent descriptors.  A vector "lengthscale" (length d) becomes an ARD latent: a tag holding the vector, kind
     = base | tag << 8 and lengthscale (the common multiplier) 1.  An "rq" latent's "alpha" (default 2.0) goes into its tag too (one
     tag holds both).  A "periodic" latent's "lengthscale" is its period and its "r" (default 1.0) goes into a tag
@@ -553,8 +560,8 @@ def gps_array(gps: Sequence[dict]):
     when the descriptor has "r", "decay" or a vector period.  A "sum" latent's "terms" (descriptors as above, mean 0) get their own tags and then one sum tag
     (lmm_kernel_sum_create); its "variance" and scalar "lengthscale" scale the whole sum.  An "sho" latent's "lengthscale" is its period
     (a scalar: the kernel is defined for d = 1) and its "quality" (default 1.0) goes into a tag (lmm_kernel_tag_create_sho) when the
-    descriptor has one.  An "sho" term of a sum raises NotImplementedError naming the latent, before any library call.  The tags live
-    as long as the returned array (its `.ard`)."""
+    descriptor has one.  An "sho" term of a sum raises NotImplementedError naming the latent, before any library call -- unless
+    `statespace` (statespace_gps_array below).  The tags live as long as the returned array (its `.ard`)."""
     arr = (GpT * max(len(gps), 1))()
     arr.ard = ArdTags(len(gps))
     for l, g in enumerate(gps):
@@ -566,7 +573,7 @@ def gps_array(gps: Sequence[dict]):
             if np.ndim(ls) != 0:
                 raise ValueError("per-dimension lengthscales around a whole sum kernel are not supported")
             a.lengthscale = float(ls)
-            a.kind |= arr.ard.create_sum(l, g["terms"]) << 8
+            a.kind |= arr.ard.create_sum(l, g["terms"], statespace) << 8
             a.mean = float(g.get("mean", 0.0))
             continue
         if g["kind"] == "sho":
@@ -617,6 +624,13 @@ def gps_array(gps: Sequence[dict]):
             a.kind |= arr.ard.create(l, vec, alpha, rho, decay) << 8
         a.mean = float(g.get("mean", 0.0))
     return arr
+
+
+def statespace_gps_array(gps: Sequence[dict]):
+    """gps_array for the state-space functions: a "sum" latent with an "sho" term gets its tag from lmm_kernel_sum_create_statespace (the
+    term's "quality" in a tag of its own, as an "sho" latent's), which only the state-space entry points take; every other latent is
+    built as gps_array builds it, so a Matern-only sum runs on the dense verbs with the same array."""
+    return gps_array(gps, statespace=True)
 
 
 def jitters(j: Optional[Tuple[float, float, float]]):

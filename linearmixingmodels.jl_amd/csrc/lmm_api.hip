@@ -336,6 +336,7 @@ struct ArdTag {           // d = 0: no factors; alpha = 0: no shape; terms non-e
   double quality = 0.0, gquality = 0.0; // an SHO latent's quality factor (lmm_kernel_tag_create_sho; 0: none) and its latest gradient
   std::vector<lmm_gp_t> terms;
   std::vector<lmm_gp_grad_t> tgrad;     // a sum tag's latest per-term (d/dv_c, d/dl_c, 0)
+  bool statespace = false;              // a sum tag of lmm_kernel_sum_create_statespace: its terms may be SHO; the state-space entry points alone take it
 };
 std::mutex g_ard_mu;
 std::map<int, ArdTag> g_ard_tags;
@@ -503,7 +504,9 @@ inline bool base_kind_ok(int base) { return base <= LMM_KERNEL_RQ || base == LMM
 // An SHO latent (LMM_KERNEL_SHO) is served over a one-dimensional input only: d > 1 is refused here, before any device work.  Its
 // descriptor carries the quality in the alpha slot (as RQ its shape).  The entry points that do not serve it (input gradients, the
 // inducing-point bound) refuse it right after this (refuse_sho), so no route evaluates another kernel in its place.
-int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) {
+// statespace: the caller is a state-space entry point, which alone takes a sum tag of lmm_kernel_sum_create_statespace (its terms may be
+// SHO, with their quality tags); everywhere else such a latent is refused by name here, before any device work.
+int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out, bool statespace = false) {
   if (!gps) return fail(LMM_ERR_ARG, "gps is NULL");
   for (int l = 0; l < m; ++l) {
     const int base = gps[l].kind & LMM_KERNEL_BASE_MASK;
@@ -533,7 +536,7 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
     double alpha, rho, decay, quality;
     std::vector<lmm_gp_t> terms;
     std::vector<std::vector<double>> tard;
-    std::vector<double> talpha, trho, tdecay;
+    std::vector<double> talpha, trho, tdecay, tquality;
     {
       std::lock_guard<std::mutex> lk(g_ard_mu);
       auto it = g_ard_tags.find(tag);
@@ -542,6 +545,10 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
         return fail(LMM_ERR_ARG, "latent %d: tag %d is %sa sum tag but the kernel kind is %d", l, tag, L.is_sum() ? "not " : "", L.kind);
       if (it->second.d != 0 && it->second.d != d)
         return fail(LMM_ERR_DIM, "latent %d: ARD tag %d has %d dimensions, the inputs have %d", l, tag, it->second.d, d);
+      if (it->second.statespace && !statespace) {
+        g.err_latent = l; g.err_info = 0;
+        return fail(LMM_ERR_UNSUPPORTED, "latent %d: sum tag %d comes from lmm_kernel_sum_create_statespace, which the state-space entry points alone serve", l, tag);
+      }
       ard = it->second.ard;
       alpha = it->second.alpha;
       rho = it->second.rho;
@@ -554,6 +561,7 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
         talpha.push_back(0.0);
         trho.push_back(0.0);
         tdecay.push_back(0.0);
+        tquality.push_back(0.0);
         if (tt == 0) continue;
         auto jt = g_ard_tags.find(tt);
         if (jt == g_ard_tags.end() || !jt->second.terms.empty())
@@ -564,8 +572,9 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
         talpha.back() = jt->second.alpha;
         trho.back() = jt->second.rho;
         tdecay.back() = jt->second.decay;
+        tquality.back() = jt->second.quality;
         const int tb = terms[c].kind & LMM_KERNEL_BASE_MASK;
-        if (!tag_shape_fits(tb, talpha.back(), trho.back(), tdecay.back()) || jt->second.quality > 0.0)
+        if (!tag_shape_fits(tb, talpha.back(), trho.back(), tdecay.back()) || (jt->second.quality > 0.0) != (tb == LMM_KERNEL_SHO))
           return fail(LMM_ERR_ARG, "latent %d: term %d: tag %d carries a shape its kernel kind %d does not take", l, (int)c, tt, tb);
       }
     }
@@ -587,6 +596,11 @@ int resolve(const lmm_gp_t* gps, int m, int d, std::shared_ptr<LatentSet>& out) 
         T.tag = terms[c].kind >> 8; T.v = terms[c].variance; T.ls = terms[c].lengthscale;
         resolve_term(*S, T, terms[c].kind & LMM_KERNEL_BASE_MASK, L.variance * T.v, L.lengthscale * T.ls, tard[c], talpha[c], trho[c], tdecay[c],
                      L.lengthscale, entry_of);
+        if (T.ev.kind == LMM_KERNEL_SHO) {      // an SHO term (a state-space sum tag): its quality in the alpha slot, as an SHO latent's (Q = 1 without a tag)
+          T.quality = tquality[c];
+          T.ev.alpha = T.quality > 0.0 ? T.quality : 1.0;
+          T.gd = T.ev;
+        }
       }
       continue;
     }
@@ -1845,6 +1859,21 @@ int lmm_kernel_tag_create_sho(double quality, int* tag) {
   return tag_register(0, nullptr, 0.0, tag, "lmm_kernel_tag_create_sho: too many live tags", 0.0, 0.0, quality);
 }
 
+// Registers a validated sum tag; the caller holds g_ard_mu.
+static int sum_register(int nterms, const lmm_gp_t* terms, int* tag, bool statespace, const char* full_msg) {
+  if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, full_msg);
+  while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
+  const int t = g_ard_next;
+  g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
+  ArdTag& a = g_ard_tags[t];
+  a.d = 0;
+  a.terms.assign(terms, terms + nterms);
+  a.tgrad.assign(nterms, lmm_gp_grad_t{0.0, 0.0, 0.0});
+  a.statespace = statespace;
+  *tag = t;
+  return LMM_OK;
+}
+
 int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag) {
   if (nterms < 1 || nterms > LMM_SUM_MAX_TERMS || !terms || !tag)
     return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: nterms must be 1..4, terms and tag non-NULL");
@@ -1870,16 +1899,36 @@ int lmm_kernel_sum_create(int nterms, const lmm_gp_t* terms, int* tag) {
     if (it->second.quality > 0.0)
       return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create: a term's tag carries an SHO quality, which no term kind takes");
   }
-  if (g_ard_tags.size() >= LMM_ARD_MAX_TAGS) return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create: too many live tags");
-  while (g_ard_tags.count(g_ard_next)) g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
-  const int t = g_ard_next;
-  g_ard_next = g_ard_next % ((1 << 23) - 1) + 1;
-  ArdTag& a = g_ard_tags[t];
-  a.d = 0;
-  a.terms.assign(terms, terms + nterms);
-  a.tgrad.assign(nterms, lmm_gp_grad_t{0.0, 0.0, 0.0});
-  *tag = t;
-  return LMM_OK;
+  return sum_register(nterms, terms, tag, false, "lmm_kernel_sum_create: too many live tags");
+}
+
+// The sum tag of a latent the state-space entry points serve (include/lmm_hip.h "state space: sum latents"): exactly two terms, each a
+// plain Matern12 / 32 / 52 (no tag) or an SHO (kind 12; its tag, if any, a quality tag), with state dimensions adding up to at most 4.
+int lmm_kernel_sum_create_statespace(int nterms, const lmm_gp_t* terms, int* tag) {
+  if (nterms < 1 || !terms || !tag) return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create_statespace: nterms must be >= 1, terms and tag non-NULL");
+  if (nterms != 2) return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create_statespace: the state-space path serves sums of exactly two terms");
+  int model[2];
+  for (int c = 0; c < nterms; ++c) {
+    model[c] = terms[c].kind < 0 ? 0 : ss_model_of(terms[c].kind & LMM_KERNEL_BASE_MASK);
+    if (model[c] == 0)
+      return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create_statespace: a term must be Matern12, Matern32, Matern52 or SHO (kinds 3, 1, 2, 12)");
+    if ((terms[c].kind >> 8) != 0 && model[c] != SS_MODEL_SHO)
+      return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create_statespace: a Matern term takes no tag (per-dimension lengthscales are not served)");
+    if (!(terms[c].variance > 0.0) || !std::isfinite(terms[c].variance) || !(terms[c].lengthscale > 0.0) ||
+        !std::isfinite(terms[c].lengthscale) || terms[c].mean != 0.0)
+      return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create_statespace: a term needs finite variance > 0, lengthscale > 0 and mean 0");
+  }
+  if (ss_pair_model(model[0], model[1], nullptr) == 0)
+    return ard_fail(LMM_ERR_UNSUPPORTED, "lmm_kernel_sum_create_statespace: the terms' state dimensions add up to more than 4");
+  std::lock_guard<std::mutex> lk(g_ard_mu);
+  for (int c = 0; c < nterms; ++c) {
+    const int tt = terms[c].kind >> 8;
+    if (tt == 0) continue;
+    auto it = g_ard_tags.find(tt);
+    if (it == g_ard_tags.end() || !(it->second.quality > 0.0))
+      return ard_fail(LMM_ERR_ARG, "lmm_kernel_sum_create_statespace: an SHO term's tag must be a live quality tag (lmm_kernel_tag_create_sho)");
+  }
+  return sum_register(nterms, terms, tag, true, "lmm_kernel_sum_create_statespace: too many live tags");
 }
 
 int lmm_kernel_sum_grad(int tag, lmm_gp_grad_t* out) {
@@ -4997,12 +5046,29 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
 // ------------------------------------------------------------------------------------------------
 #define LMM_SS_BATCH_BYTES (size_t(1) << 30)       // device memory one launch's latents may take (aggregates, filtered states)
 
-// Every latent must be a plain Matern12 / 32 / 52 (no tag: per-dimension factors; no sum) or an SHO latent (whose tag, if any, carries
-// its quality: resolve has checked it).  Names the first that is not.
-static int ss_check_latents(const Latent* lts, int m) {
+// The model of a latent's launches (lmm_internal.h): that of its kind, or of the sum of its two terms (*swapped: the second term comes
+// first in the library's order of the terms); 0: not served.  A term is served as a plain latent is: no factors, a tag only for an SHO
+// term's quality.
+static int ss_latent_model(const Latent& L, int* swapped = nullptr) {
+  if (swapped) *swapped = 0;
+  for (const KernelTerm& T : L.terms)
+    if (T.has_ard || T.ev.ils != nullptr || (T.tag != 0 && T.ev.kind != LMM_KERNEL_SHO)) return 0;
+  if (!L.is_sum()) return L.nt() == 1 ? ss_model_of(L.kind) : 0;
+  return L.nt() == 2 ? ss_pair_model(ss_model_of(L.terms[0].ev.kind), ss_model_of(L.terms[1].ev.kind), swapped) : 0;
+}
+static int ss_latent_dim(const Latent& L) { return ss_model_dim(ss_latent_model(L)); }
+
+// Every latent must be a plain Matern12 / 32 / 52 (no tag: per-dimension factors) or an SHO latent (whose tag, if any, carries its
+// quality: resolve has checked it), or the sum of two such terms with a state dimension of at most 4 (DESIGN.md 4.18 "Sum latents").
+// Names the first that is not.  refuse_sums: the entry point serves no sum latent (the gradients with respect to locations).
+static int ss_check_latents(const Latent* lts, int m, bool refuse_sums = false) {
   for (int l = 0; l < m; ++l) {
     const Latent& L = lts[l];
-    if (L.is_sum() || (L.tag != 0 && L.kind != LMM_KERNEL_SHO) || ss_model_of(L.kind) == 0 || L.terms.size() != 1 || L.terms[0].ev.ils != nullptr) {
+    if (refuse_sums && L.is_sum()) {
+      g.err_latent = l; g.err_info = 0;
+      return fail(LMM_ERR_UNSUPPORTED, "latent %d: gradients with respect to locations are not served for a sum latent on the state-space path", l);
+    }
+    if (ss_latent_model(L) == 0) {
       g.err_latent = l; g.err_info = 0;
       // (the wording is pinned by tests from before SHO latents were admitted: it stays word for word)
       return fail(LMM_ERR_UNSUPPORTED, "state-space inference is served for plain Matern12, Matern32 and Matern52 latents: latent %d is not one", l);
@@ -5054,20 +5120,35 @@ static SSChunks ss_plan_chunks(int n, int chunk) {
 template <typename LatOf, typename Bytes, typename Body>
 static void ss_for_launches(long long ne, int nch, LatOf&& lat_of, Bytes&& bytes_per_entry, Body&& body) {
   for (long long e0 = 0; e0 < ne;) {
-    const int model = ss_model_of(lat_of(e0).kind), D = ss_model_dim(model);
+    const int model = ss_latent_model(lat_of(e0)), D = ss_model_dim(model);
     const int nbmax = (int)std::max<size_t>(1, std::min<size_t>(LMM_MAX_BATCH, LMM_SS_BATCH_BYTES / bytes_per_entry(model, D, nch)));
     int nb = 1;
-    while (e0 + nb < ne && nb < nbmax && ss_model_of(lat_of(e0 + nb).kind) == model) ++nb;
+    while (e0 + nb < ne && nb < nbmax && ss_latent_model(lat_of(e0 + nb)) == model) ++nb;
     body(e0, nb, model, D);
     e0 += nb;
   }
 }
 
-// the kernel parameters every *Lat struct of a launch takes from its latent
+// the kernel parameters every *Lat struct of a launch takes from its latent; a sum latent's terms go in the library's order, with the
+// sum's own variance and lengthscale folded in (KernelTerm::ev) and an SHO term's quality from the alpha slot of its descriptor
+template <typename Lat>
+static void ss_fill_kernel(Lat& o, const Latent& L) {
+  int sw = 0;
+  ss_latent_model(L, &sw);
+  const KernelTerm& A = L.terms[sw ? 1 : 0];
+  o.var = A.ev.var; o.inv_ls = A.ev.inv_ls; o.quality = L.is_sum() ? A.ev.alpha : L.quality;
+  o.var2 = 0.0; o.inv_ls2 = 0.0; o.quality2 = 0.0;
+  if (L.is_sum()) {
+    const KernelTerm& B = L.terms[sw ? 0 : 1];
+    o.var2 = B.ev.var; o.inv_ls2 = B.ev.inv_ls; o.quality2 = B.ev.alpha;
+  }
+}
 template <typename Lat>
 static void ss_fill_lat(Lat& o, const Latent& L, bool add_mean) {
-  o.var = L.terms[0].ev.var; o.inv_ls = L.terms[0].ev.inv_ls; o.mean = add_mean ? L.mean : 0.0; o.quality = L.quality;
+  ss_fill_kernel(o, L);
+  o.mean = add_mean ? L.mean : 0.0;
 }
+#define SS_NTHETA 6                    // kernel parameters a latent's forward-mode gradient seeds at the most (an SHO + SHO sum: 3 + 3)
 
 // The filter (and, smean != nullptr, the smoother) of the ms latents lts[0 .. ms): w, r, fmean, fvar, smean, svar are [latent][n] on
 // the device (outputs may be nullptr); lml: ms host values or nullptr; add_mean: the smoothed means get the latent's mean added.
@@ -5077,7 +5158,8 @@ static void ss_fill_lat(Lat& o, const Latent& L, bool add_mean) {
 struct SSGradOut {
   double* alpha; double* grad_w;       // device, [latent][n]: alpha_t = -d lml / d r_t, d lml / d w_t
   double* sums;                        // host, 4 per latent: sum_t alpha_t, w_t alpha_t^2, w_t c_t, d lml / d w_t
-  double* gtheta;                      // host, 3 per latent: d lml / d variance, d lml / d lengthscale, d lml / d quality (SHO; else 0)
+  double* gtheta;                      // host, SS_NTHETA per latent: d lml / d variance, d lml / d lengthscale, d lml / d quality (SHO; else 0); a sum
+                                       // latent: its first term's (in the library's order), then its second's, each with a quality only when SHO
   double* gdt = nullptr;               // device, [latent][n] (nullptr: not computed): d lml / d (x_t - x_{t-1}), 0 at t = 0
 };
 // One entry of the latent dimension of a launch: a latent with its own noise and data (n values each, on the device).  Samples ride
@@ -5088,7 +5170,7 @@ struct SSEntry { const Latent* L; const double* w; const double* r; };
 struct SSKeep { double* fstate; double* sstate; };
 static size_t ss_keep_offset(const SSEntry* es, int k, int n) {
   size_t off = 0;
-  for (int j = 0; j < k; ++j) off += (size_t)ss_state_comps(ss_state_dim(es[j].L->kind)) * n;
+  for (int j = 0; j < k; ++j) off += (size_t)ss_state_comps(ss_latent_dim(*es[j].L)) * n;
   return off;
 }
 static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, int chunk, double* lml, double* fmean, double* fvar,
@@ -5108,7 +5190,7 @@ static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, i
     Buf<double> agg((size_t)nb * ss_fwd_agg_elems(D, nch)), part((size_t)nb * nch), lmld(nb), state, bagg;
     if (smooth) { state = Buf<double>((size_t)nb * comps * n); bagg = Buf<double>((size_t)nb * ss_bwd_agg_elems(D, nch)); }
     Buf<double> dagg, dpart, ppart, gsum;
-    std::vector<double> gth((size_t)nb * 3);      // the launch's NS values per latent
+    std::vector<double> gth((size_t)nb * NS);     // the launch's NS values per latent
     if (go) {
       dagg = Buf<double>((size_t)nb * ss_dual_agg_elems(D, nch, NS)); dpart = Buf<double>((size_t)nb * NS * nch);
       ppart = Buf<double>((size_t)nb * 4 * npb); gsum = Buf<double>((size_t)nb * (4 + NS));
@@ -5141,7 +5223,7 @@ static int ss_core_entries(const double* xd, int n, const SSEntry* es, int ms, i
     HIPCHK(hipStreamSynchronize(st0));          // the buffers above go back to the pool
     if (go)
       for (int j = 0; j < nb; ++j)
-        for (int s = 0; s < 3; ++s) go->gtheta[(size_t)(k0 + j) * 3 + s] = s < NS ? gth[(size_t)j * NS + s] : 0.0;
+        for (int s = 0; s < SS_NTHETA; ++s) go->gtheta[(size_t)(k0 + j) * SS_NTHETA + s] = s < NS ? gth[(size_t)j * NS + s] : 0.0;
   });
   return LMM_OK;
 }
@@ -5153,19 +5235,39 @@ static int ss_core(const double* xd, int n, const Latent* lts, int ms, const dou
   return ss_core_entries(xd, n, es.data(), ms, chunk, lml, fmean, fvar, smean, svar, add_mean, go);
 }
 
-// d lml / d quality of the SHO latents to their tags (lmm_kernel_tag_quality_grad): every tag the call named is reset; then, over the
-// shard [l0, l1), a tag gets the sum over the latents carrying it.  gth: 3 values per latent of the shard (nullptr, grad_gps NULL: zeros).
-static void ss_publish_quality(const Latent* lts, int m, int l0, int l1, const double* gth) {
-  std::lock_guard<std::mutex> lk(g_ard_mu);
-  for (int l = 0; l < m; ++l) {
-    auto it = g_ard_tags.find(lts[l].tag);
-    if (lts[l].tag != 0 && it != g_ard_tags.end()) it->second.gquality = 0.0;
-  }
-  if (!gth) return;
+// The latents' kernel-parameter gradients from the forward-mode values gth (SS_NTHETA per latent of the shard [l0, l1), in the order of
+// SSGradOut::gtheta): grad_gps[l] (m entries; nullptr: not wanted) gets d lml / d variance and d lml / d lengthscale, and the registry
+// (publish_grads) an SHO latent's d lml / d quality (lmm_kernel_tag_quality_grad) and a sum latent's per-term values
+// (lmm_kernel_sum_grad; an SHO term's quality through its own tag).  A sum's terms are V_c kappa_c(. / E_c) with V_c = v0 v_c and
+// E_c = s0 l_c (an SHO term's period), which is what the kernels seed: d/dv_c = v0 d/dV_c, d/dl_c = s0 d/dE_c, d/dv0 = sum_c v_c d/dV_c
+// and d/ds0 = sum_c l_c d/dE_c, the dense path's semantics (grad_finish).  gth == nullptr (grad_gps NULL): the tags are reset to zeros.
+static void ss_publish_grads(const LatentSet& S, int l0, int l1, const double* gth, lmm_gp_grad_t* ggps) {
+  if (!gth) { publish_grads(S, nullptr, l0, l1); return; }
+  const size_t sw = term_grad_stride(S.d);
+  std::vector<double> trec(S.lat.size() * LMM_SUM_MAX_TERMS * sw, 0.0);
   for (int l = l0; l < l1; ++l) {
-    auto it = g_ard_tags.find(lts[l].tag);
-    if (lts[l].tag != 0 && it != g_ard_tags.end() && lts[l].kind == LMM_KERNEL_SHO) it->second.gquality += gth[3 * (size_t)(l - l0) + 2];
+    const Latent& L = S.lat[l];
+    const double* gl = gth + (size_t)SS_NTHETA * (l - l0);
+    double* rec = &trec[(size_t)l * LMM_SUM_MAX_TERMS * sw];
+    if (!L.is_sum()) {
+      if (ggps) { ggps[l].variance = gl[0]; ggps[l].lengthscale = gl[1]; }
+      rec[0] = gl[0]; rec[1] = gl[1]; rec[2] = gl[2];
+      continue;
+    }
+    int swapped = 0;
+    const int model = ss_latent_model(L, &swapped);
+    const int na = ss_model_seeds(model / SS_PAIR(1, 0));
+    double dv0 = 0.0, ds0 = 0.0;
+    for (int c = 0; c < 2; ++c) {
+      const KernelTerm& T = L.terms[c];
+      const double* gc = gl + ((c == 0) == (swapped == 0) ? 0 : na);      // the term's seeds: first in the library's order, or behind the first's
+      double* o = rec + sw * c;
+      o[0] = L.variance * gc[0]; o[1] = L.lengthscale * gc[1]; o[2] = T.ev.kind == LMM_KERNEL_SHO ? gc[2] : 0.0;
+      dv0 += T.v * gc[0]; ds0 += T.ls * gc[1];
+    }
+    if (ggps) { ggps[l].variance = dv0; ggps[l].lengthscale = ds0; }
   }
+  publish_grads(S, &trec, l0, l1);
 }
 
 // The OILMM front end of the state-space path: per latent of the shard and point, the pseudo-observation r = z_t[l] - mean_l and its
@@ -5254,14 +5356,15 @@ struct SSTrain {
   SSFront Fr;                          // left empty without y
 };
 static int ss_train(bool missing, const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
-                    const lmm_gp_t* gps, int l0, int l1, SSTrain& T, bool want_resid = false, const std::function<int()>& after_args = nullptr) {
+                    const lmm_gp_t* gps, int l0, int l1, SSTrain& T, bool want_resid = false, const std::function<int()>& after_args = nullptr,
+                    bool refuse_sums = false) {
   if (int rc = train_args(missing || !x || !U || !S || n <= 0 || p <= 0 || m <= 0, p, m, S, sigma2, l0, l1, TRAIN_SIGMA2 | TRAIN_S)) return rc;
   if (g_f32) return ss_refuse_f32();
   if (after_args)
     if (int rc = after_args()) return rc;
-  if (int rc = resolve(gps, m, 1, T.ls)) return rc;
+  if (int rc = resolve(gps, m, 1, T.ls, true)) return rc;
   T.lts = T.ls->lat.data();
-  if (int rc = ss_check_latents(T.lts, m)) return rc;
+  if (int rc = ss_check_latents(T.lts, m, refuse_sums)) return rc;
   T.xd = DevIn(x, (size_t)n, g.streams[0]); T.yd = DevIn(y, (size_t)n * p, g.streams[0]);
   if (int rc = ss_check_sorted(T.xd.p, n)) return rc;
   T.l0 = l0; T.l1 = l1; T.ms = l1 - l0; T.mk = std::max(T.ms, 1);
@@ -5323,13 +5426,13 @@ static int ss_logpdf_grad(const double* x, int n, const double* y, int p, const 
   REQUIRE_INIT();
   LMM_TRY
   SSTrain T;
-  if (int rc = ss_train(!y, x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, T, grad_y && with_regulariser)) return rc;
+  if (int rc = ss_train(!y, x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, T, grad_y && with_regulariser, nullptr, grad_x != nullptr)) return rc;
   hipStream_t st0 = g.streams[0];
   const auto& [ls, lts, xd, yd, l0, l1, ms, msa, Fr] = T;
   if (Fr.has_nan && (grad_S || grad_U))
     return fail(LMM_ERR_UNSUPPORTED, "state-space gradients with respect to S and U are not built for data with NaN (pass NULL for grad_S and grad_U)");
   DevOut gy(grad_y, (size_t)n * p);
-  std::vector<double> lml(msa, 0.0), sums(4 * (size_t)msa, 0.0), gth(3 * (size_t)msa, 0.0);
+  std::vector<double> lml(msa, 0.0), sums(4 * (size_t)msa, 0.0), gth(SS_NTHETA * (size_t)msa, 0.0);
   Buf<double> sm((size_t)n * msa), sv((size_t)n * msa), al((size_t)n * msa), gw((size_t)n * msa);
   DevOut gx(grad_x, (size_t)n);
   Buf<double> gd;
@@ -5350,10 +5453,7 @@ static int ss_logpdf_grad(const double* x, int n, const double* y, int p, const 
   G.gs2.assign(1, 0.0);
   G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
   G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
-  for (int k = 0; k < ms; ++k) {
-    G.ggps[l0 + k].variance = gth[3 * (size_t)k]; G.ggps[l0 + k].lengthscale = gth[3 * (size_t)k + 1];
-    G.ggps[l0 + k].mean = sums[4 * (size_t)k];                 // sum_t alpha_t
-  }
+  for (int k = 0; k < ms; ++k) G.ggps[l0 + k].mean = sums[4 * (size_t)k];      // sum_t alpha_t
   if (Fr.has_nan) {
     const MissingFront& F = Fr.F;
     const int nobs = Fr.nobs;
@@ -5426,8 +5526,8 @@ static int ss_logpdf_grad(const double* x, int n, const double* y, int p, const 
     }
   }
   double value = 0.0;
+  ss_publish_grads(*ls, l0, l1, grad_gps ? gth.data() : nullptr, G.ggps.data());
   write_oilmm_grad(G, m, p, &value, grad_sigma2, grad_S, grad_U, grad_gps);
-  ss_publish_quality(lts, m, l0, l1, grad_gps ? gth.data() : nullptr);
   if (out_logpdf) *out_logpdf = value;
   if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
   return LMM_OK;
@@ -5454,12 +5554,13 @@ int lmm_oilmm_logpdf_grad_statespace_x(const double* x, int n, const double* y, 
 // not read (r is the residual).  chunk: points per thread (0: the library's plan).
 // The preamble of these one-latent entry points: `bad` (a NULL pointer or a size out of range) refuses the arguments, then nsamples
 // (given by the entry points that draw samples), the Float64-only refusal, the latent resolved and checked, x (device) checked.
-static int ss_dev_prepare(bool bad, const double* x, int n, const lmm_gp_t* gp, std::shared_ptr<LatentSet>& ls, int nsamples = 1) {
+static int ss_dev_prepare(bool bad, const double* x, int n, const lmm_gp_t* gp, std::shared_ptr<LatentSet>& ls, int nsamples = 1,
+                          bool refuse_sums = false) {
   if (bad) return fail(LMM_ERR_ARG, "bad arguments");
   if (nsamples < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", nsamples);
   if (g_f32) return ss_refuse_f32();
-  if (int rc = resolve(gp, 1, 1, ls)) return rc;
-  if (int rc = ss_check_latents(ls->lat.data(), 1)) return rc;
+  if (int rc = resolve(gp, 1, 1, ls, true)) return rc;
+  if (int rc = ss_check_latents(ls->lat.data(), 1, refuse_sums)) return rc;
   return ss_check_sorted(x, n);
 }
 
@@ -5508,9 +5609,13 @@ static int ss_dev_grad(const double* x, int n, const lmm_gp_t* gp, const double*
   const bool bad = !x || !gp || !w || !r || !lml || !grad_r || !grad_w || !grad_theta || n <= 0 || chunk < 0;
   if (int rc = ss_dev_prepare(bad, x, n, gp, ls)) return rc;
   const Latent* lts = ls->lat.data();
+  if (lts[0].is_sum() && ntheta < SS_NTHETA) {      // two or three values cannot carry a sum's seeds: lmm_dev_statespace_grad_sum does
+    g.err_latent = 0; g.err_info = 0;
+    return fail(LMM_ERR_UNSUPPORTED, "latent 0: a sum latent's gradient has up to %d kernel parameters (lmm_dev_statespace_grad_sum)", SS_NTHETA);
+  }
   hipStream_t st0 = g.streams[0];
   Buf<double> sm(n), sv(n);
-  double hl = 0.0, sums[4], gth[3];
+  double hl = 0.0, sums[4], gth[SS_NTHETA];
   const SSGradOut go{grad_r, grad_w, sums, gth};
   if (int rc = ss_core(x, n, lts, 1, w, r, chunk, &hl, nullptr, nullptr, sm.p, sv.p, false, &go)) return rc;
   launch_vec_lin(grad_r, grad_r, -2.0, n, grad_r, st0);      // ss_core left alpha there: d lml / d r = -alpha
@@ -5532,6 +5637,14 @@ int lmm_dev_statespace_grad_sho(const double* x, int n, const lmm_gp_t* gp, cons
   return ss_dev_grad(x, n, gp, w, r, chunk, lml, grad_r, grad_w, grad_theta, 3);
 }
 
+// The same for a sum latent: grad_theta holds 6 values, the seeds of its first term in the library's order of the terms (Matern12,
+// Matern32, SHO, Matern52), then those of its second: d lml / d V_c, d lml / d E_c and, SHO, d lml / d quality, with V_c = v0 v_c and
+// E_c = s0 l_c the term's own variance and lengthscale (period); the slots behind the last seed are 0.
+int lmm_dev_statespace_grad_sum(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* lml,
+                                double* grad_r, double* grad_w, double* grad_theta) {
+  return ss_dev_grad(x, n, gp, w, r, chunk, lml, grad_r, grad_w, grad_theta, SS_NTHETA);
+}
+
 // Building block for tests beside lmm_dev_statespace_grad: grad_x (n values, device) = d lml / d x_t of ONE latent, Matern or SHO (the
 // tag carries an SHO latent's quality, as in lmm_dev_statespace_grad_sho); exactly 0 where w = +Inf.
 int lmm_dev_statespace_grad_x(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk, double* grad_x) {
@@ -5539,11 +5652,11 @@ int lmm_dev_statespace_grad_x(const double* x, int n, const lmm_gp_t* gp, const 
   REQUIRE_INIT();
   LMM_TRY
   std::shared_ptr<LatentSet> ls;
-  if (int rc = ss_dev_prepare(!x || !gp || !w || !r || !grad_x || n <= 0 || chunk < 0, x, n, gp, ls)) return rc;
+  if (int rc = ss_dev_prepare(!x || !gp || !w || !r || !grad_x || n <= 0 || chunk < 0, x, n, gp, ls, 1, true)) return rc;
   const Latent* lts = ls->lat.data();
   hipStream_t st0 = g.streams[0];
   Buf<double> sm(n), sv(n), al(n), gw(n), gd(n);
-  double hl = 0.0, sums[4], gth[3];
+  double hl = 0.0, sums[4], gth[SS_NTHETA];
   const SSGradOut go{al.p, gw.p, sums, gth, gd.p};
   if (int rc = ss_core(x, n, lts, 1, w, r, chunk, &hl, nullptr, nullptr, sm.p, sv.p, false, &go)) return rc;
   launch_ss_grad_x(gd.p, w, n, 1, grad_x, st0);
@@ -5581,7 +5694,7 @@ static std::vector<size_t> ss_post_offsets(const Latent* lts, int ms, int cap) {
   size_t total = 0;
   for (int k = 0; k < ms; ++k) {
     off.push_back(total);
-    total += (size_t)ss_state_comps(ss_state_dim(lts[k].kind)) * cap;
+    total += (size_t)ss_state_comps(ss_latent_dim(lts[k])) * cap;
   }
   off.push_back(total);               // one behind the last: the buffer's size
   return off;
@@ -5721,7 +5834,7 @@ static void ss_post_grow(lmm_ss_post* P, int n_total) {
   Buf<double> x((size_t)n_total), fs(std::max<size_t>(off[ms], 1)), ss(std::max<size_t>(off[ms], 1));
   HIPCHK(hipMemcpyAsync(x.p, P->x.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
   for (int k = 0; k < ms; ++k) {
-    const size_t bytes = (size_t)ss_state_comps(ss_state_dim(lts[k].kind)) * n * sizeof(double);
+    const size_t bytes = (size_t)ss_state_comps(ss_latent_dim(lts[k])) * n * sizeof(double);
     HIPCHK(hipMemcpyAsync(fs.p + off[k], P->fstate.p + P->off[k], bytes, hipMemcpyDeviceToDevice, st0));
     HIPCHK(hipMemcpyAsync(ss.p + off[k], P->sstate.p + P->off[k], bytes, hipMemcpyDeviceToDevice, st0));
   }
@@ -5764,7 +5877,7 @@ static void ss_filter_from(const double* xd, int k, double x0, const Latent* lts
     a.fmean = fmean ? fmean + (size_t)k0 * k : nullptr; a.fvar = fvar ? fvar + (size_t)k0 * k : nullptr;
     for (int j = 0; j < nb; ++j) {
       const Latent& L = lts[k0 + j];
-      a.lat[j].var = L.terms[0].ev.var; a.lat[j].inv_ls = L.terms[0].ev.inv_ls; a.lat[j].quality = L.quality;
+      ss_fill_kernel(a.lat[j], L);
       a.lat[j].w = w + (size_t)(k0 + j) * k; a.lat[j].r = r + (size_t)(k0 + j) * k;
       a.lat[j].init = init[k0 + j]; a.lat[j].out = out[k0 + j];
     }
@@ -5808,7 +5921,7 @@ int lmm_oilmm_statespace_post_append(lmm_ss_post_t* post, const double* x_new, i
   std::vector<const double*> init(ms);
   std::vector<double*> outp(ms);
   for (int j = 0; j < ms; ++j) {
-    const size_t comps = (size_t)ss_state_comps(ss_state_dim(lts[P->l0 + j].kind));
+    const size_t comps = (size_t)ss_state_comps(ss_latent_dim(lts[P->l0 + j]));
     init[j] = P->fstate.p + P->off[j] + (size_t)(n - 1) * comps;
     outp[j] = P->fstate.p + P->off[j] + (size_t)n * comps;
   }
@@ -5911,6 +6024,7 @@ int lmm_oilmm_statespace_post_mean_and_var_grad_xs(const lmm_ss_post_t* post, co
   if (!dmean && !dvar) return fail(LMM_ERR_ARG, "state-space posterior: dmean and dvar are both NULL (one cotangent is needed)");
   if (g_f32) return ss_refuse_f32();
   const lmm_ss_post* P = post;
+  if (int rc = ss_check_latents(P->ls->lat.data(), P->m, true)) return rc;       // component 2 of a sum latent's state is not f'
   const int p = P->p, ms = P->l1 - P->l0;
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)ns, st0);
@@ -5978,7 +6092,7 @@ static void ss_pair_launches(const Latent* lts, int ms, int N, int rows, int chu
   hipStream_t st0 = g.streams[0];
   const SSChunks plan = ss_plan_chunks(rows, chunk);
   std::vector<size_t> zoff(std::max(ms, 1), 0);
-  for (int k = 1; k < ms; ++k) zoff[k] = zoff[k - 1] + (size_t)ss_state_dim(lts[k - 1].kind) * rows;
+  for (int k = 1; k < ms; ++k) zoff[k] = zoff[k - 1] + (size_t)ss_latent_dim(lts[k - 1]) * rows;
   const auto bytes = [](int, int D, int nch) { return ss_aff_agg_elems(D, nch) * sizeof(double); };
   ss_for_launches((long long)ms * N, plan.nch, [&](long long e) -> const Latent& { return lts[e / N]; }, bytes,
                   [&](long long e0, int nb, int model, int D) {
@@ -6100,7 +6214,7 @@ int lmm_oilmm_rand_statespace(const double* x, int n, const double* y, int p, co
   const int l0 = T.l0, l1 = T.l1, ms = T.ms;
   size_t zall = 0, zbefore = 0, zshard = 0;        // doubles of one sample's z: every latent, those before the shard, the shard's
   for (int l = 0; l < m; ++l) {
-    const size_t c = (size_t)ss_state_dim(lts[l].kind) * n;
+    const size_t c = (size_t)ss_latent_dim(lts[l]) * n;
     zall += c;
     if (l < l0) zbefore += c;
     else if (l < l1) zshard += c;
@@ -6126,7 +6240,7 @@ static int ss_dev_sample(const double* x, int n, const lmm_gp_t* gp, const doubl
   std::shared_ptr<LatentSet> ls;
   if (int rc = ss_dev_prepare(n <= 0 || chunk < 0, x, n, gp, ls, nsamples)) return rc;
   const Latent* lts = ls->lat.data();
-  const size_t zs = (size_t)ss_state_dim(lts[0].kind) * n;
+  const size_t zs = (size_t)ss_latent_dim(lts[0]) * n;
   return ss_for_sample_groups(n, 1, nsamples, [&](int q0, int ng) {
     double* fq = f + (size_t)q0 * n;
     if (int rc = ss_paths(x, n, lts, 1, ng, z + (size_t)q0 * zs, zs, chunk, false, fq)) return rc;
@@ -6228,7 +6342,7 @@ int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, 
   if (int rc = ss_window(P->x.p, P->n, xsd.p, ns, w)) return rc;
   if (int rc = ss_post_ensure_smoothed(P, xsd.p, ns)) return rc;
   size_t zshard = 0;                               // doubles of one sample's z
-  for (int k = 0; k < ms; ++k) zshard += (size_t)ss_state_dim(lts[k].kind) * w.W;
+  for (int k = 0; k < ms; ++k) zshard += (size_t)ss_latent_dim(lts[k]) * w.W;
   DevOut od(out, (size_t)ns * p * nsamples);
   const int rc = ss_sample_mix(ns, std::max(w.W, ns), ms, p, P->H.p, P->sigma2, add_noise ? eps : nullptr, nsamples, od.p,
                                [&](int q0, int ng, double* f) {
@@ -6255,7 +6369,7 @@ int lmm_dev_statespace_post_sample(const double* x, int n, const lmm_gp_t* gp, c
   const Latent* lts = ls->lat.data();
   SSWindow w;
   if (int rc = ss_window(x, n, xs, ns, w)) return rc;
-  const size_t zs = (size_t)ss_state_dim(lts[0].kind) * w.W;
+  const size_t zs = (size_t)ss_latent_dim(lts[0]) * w.W;
   return ss_for_sample_groups(std::max(w.W, ns), 1, nsamples, [&](int q0, int ng) {
     return ss_post_paths(ss_stored(x, n, lts, fstate, sstate), xs, ns, w, ng, z + (size_t)q0 * zs, zs, chunk, false, f + (size_t)q0 * ns);
   });

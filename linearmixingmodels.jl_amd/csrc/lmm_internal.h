@@ -356,7 +356,7 @@ void launch_sparse_phibar(const BatchPtr& Ki, const BatchPtr& Si, const BatchPtr
 // State-space inference for Matern and SHO latents over a one-dimensional input (lmm_kernels_ss.hip).  All Float64.
 // One latent of a launch: variance, 1 / lengthscale (an SHO latent's 1 / period), the constant added to the smoothed means, per-point
 // noise w (device, n values; +Inf: unobserved), data r (device, n values) and an SHO latent's quality factor (unused by the Matern models).
-struct SSLat { double var, inv_ls, mean; const double* w; const double* r; double quality; };
+struct SSLat { double var, inv_ls, mean; const double* w; const double* r; double quality; double var2, inv_ls2, quality2; };
 struct SSArgs {
   const double* x; int n, chunk, nch;         // sorted inputs (device); points per thread; nch = ceil(n / chunk) threads per latent
   double* agg;                                // nb * ss_fwd_agg_elems(D, nch) doubles: the forward aggregates and the scan's levels
@@ -376,9 +376,14 @@ struct SSArgs {
 static_assert(sizeof(SSArgs) <= 4096, "SSArgs is passed by value: kernel arguments are limited to 4096 bytes");
 // The model of a launch: 1 / 2 / 3 = Matern12 / 32 / 52 (the state dimension), SS_MODEL_SHO = the damped oscillator (state dimension 2)
 #define SS_MODEL_SHO 4
+// The model of a sum of two terms inside one latent (DESIGN.md 4.18 "Sum latents"): SS_PAIR(a, b) of the term models a, b above, in the
+// library's one order of the terms (Matern12, Matern32, SHO, Matern52) and with a state dimension D_a + D_b <= 4.  Every *Lat struct
+// carries the second term's (var2, inv_ls2, quality2) behind its own fields, which the one-term models do not read.
+#define SS_PAIR(a, b) (16 * (a) + (b))
 int ss_model_of(int kind);                    // the model of a base kind, 0 for a kind without one
+int ss_pair_model(int a, int b, int* swapped);// the model of the sum of the term models a, b (*swapped: b comes first in it); 0: not served
 int ss_model_dim(int model);                  // its state dimension
-int ss_model_seeds(int model);                // parameters its forward-mode gradient seeds: 2 (variance, lengthscale), SHO 3 (+ quality)
+int ss_model_seeds(int model);                // parameters its forward-mode gradient seeds: 2 (variance, lengthscale), SHO 3 (+ quality); a sum: its terms' together
 int ss_state_dim(int kind);                   // 1 / 2 / 3 for Matern12 / 32 / 52, 2 for SHO, 0 for every other kind
 int ss_state_comps(int D);                    // doubles of one filtered state: D + D (D + 1) / 2
 int ss_default_chunk(int n);                  // the library's plan: a function of n alone
@@ -403,7 +408,7 @@ void launch_ss_point(const SSArgs& a, int nb, double* alpha, double* grad_w, dou
 // Sampling.  One (latent, sample) pair of a launch: variance, 1 / lengthscale, its standard normals z (device, D n values, component i
 // of point t at z[i n + t]), the constant added to the path, the path it writes (device, n values: the first component of the state)
 // and an SHO latent's quality factor.
-struct SSPathLat { double var, inv_ls, mean; const double* z; double* f; double quality; };
+struct SSPathLat { double var, inv_ls, mean; const double* z; double* f; double quality; double var2, inv_ls2, quality2; };
 struct SSPathArgs {
   const double* x; int n, chunk, nch;         // as SSArgs
   double* agg;                                // nb * ss_aff_agg_elems(D, nch) doubles: the affine aggregates and the scan's levels
@@ -423,7 +428,7 @@ void launch_ss_sorted(const double* x, int n, int* flag, hipStream_t st);
 // the constant added to the means and an SHO latent's quality.  Component c of point t of latent z's filtered (smoothed) state is
 // fstate (sstate)[z state_stride + c comp_stride + t point_stride]: comp_stride = 1, point_stride = ss_state_comps(D) is the point-major
 // layout the posterior object keeps (SSArgs::sstate, fkeep); comp_stride = n, point_stride = 1 the component-major one of SSArgs::state.
-struct SSInterpLat { double var, inv_ls, mean, quality; };
+struct SSInterpLat { double var, inv_ls, mean, quality; double var2, inv_ls2, quality2; };
 struct SSInterpArgs {
   const double* x; int n;                     // sorted training inputs (device)
   const double* xs; int ns;                   // the queries (device), in any order
@@ -452,7 +457,7 @@ void launch_ss_window(const double* x, int n, const double* xs, int ns, int firs
 // One (latent, sample) pair of a launch: the latent's parameters, its stored states (device, point-major n x ss_state_comps(D)), the
 // pair's standard normals z (device, D W values, component i of window point j at z[i W + j]) and the path it writes (device, ns values
 // in the order of the sorted queries: the first component of the state + mean).
-struct SSPostLat { double var, inv_ls, mean, quality; const double* fstate; const double* sstate; const double* z; double* f; };
+struct SSPostLat { double var, inv_ls, mean, quality; const double* fstate; const double* sstate; const double* z; double* f; double var2, inv_ls2, quality2; };
 // what every scan over a window takes, in front of its own fields (the kernels read their arguments by offset)
 struct SSWindowArgs {
   const double* x; int n;                     // sorted training inputs (device)
@@ -472,7 +477,7 @@ void launch_ss_post_path(const SSPostArgs& a, int model, int nb, hipStream_t st)
 // filter over the window's backward chain, from its last point down to its first.  One latent of a launch: its parameters, its stored
 // states (as SSPostLat) and the noise w and data r of the ns sorted queries (device; +Inf: an unobserved query).  Training points of
 // the window are unobserved steps.
-struct SSLpdfLat { double var, inv_ls, mean, quality; const double* fstate; const double* sstate; const double* w; const double* r; };
+struct SSLpdfLat { double var, inv_ls, mean, quality; const double* fstate; const double* sstate; const double* w; const double* r; double var2, inv_ls2, quality2; };
 struct SSLpdfArgs : SSWindowArgs {
   double* part;                               // nb * nch log-density partials
   SSLpdfLat lat[LMM_MAX_BATCH];
@@ -485,7 +490,7 @@ void launch_ss_post_logpdf(const SSLpdfArgs& a, int model, int nb, double* lml, 
 // One latent of a launch: its parameters, the noise w and data r of the k points (device), the packed state `init` (device,
 // ss_state_comps(D) values: mean, then the upper triangle of the covariance) of the point in front of them, and `out` (device), where
 // the k filtered states go point-major, k x ss_state_comps(D): row n of the latent's block of the posterior object.
-struct SSFromLat { double var, inv_ls, quality; const double* w; const double* r; const double* init; double* out; };
+struct SSFromLat { double var, inv_ls, quality; const double* w; const double* r; const double* init; double* out; double var2, inv_ls2, quality2; };
 struct SSFromArgs {
   const double* x; int n, chunk, nch;         // the k = n new inputs, sorted (device); points per thread; threads per latent
   double x0;                                  // the input of the stored state, <= x[0]

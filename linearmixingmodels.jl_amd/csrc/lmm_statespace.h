@@ -206,6 +206,61 @@ SS_HD void ss_AQ(const SSOsc<Sc>& M, double dt, Sc A[D][D], Sc Q[D][D]) {
   ss_stationary_Q<D, Sc>(M.Pinf, A, Q);
 }
 
+// ---- the sum of two models inside one latent (DESIGN.md 4.18 "Sum latents") --------------------------------------------------------
+// f = f_a + f_b with independent f_a, f_b of models MA, MB is again a state-space model: the state s = (s_a, s_b) has dimension
+// D = D_a + D_b, block-diagonal A, Q, Pinf and F, and the observation e_1' s_a + e_1' s_b.  Everything below ss_fwd_element is written
+// against h = e_1', so the state is held in the basis s' = T s with T = I + e_1 e_{D_a+1}': its first component is f_a + f_b and every
+// other component is the one of s.  T and T^-1 = I - e_1 e_{D_a+1}' differ from I in one entry: T X adds row D_a + 1 of X to row 1,
+// X T' adds column D_a + 1 to column 1, and X T^-1 takes column 1 off column D_a + 1.
+template <typename M> struct SSDimOf;
+template <int D, typename Sc> struct SSDimOf<SSModel<D, Sc>> { static constexpr int value = D; };
+template <typename Sc> struct SSDimOf<SSOsc<Sc>> { static constexpr int value = 2; };
+
+template <typename MA, typename MB, typename Sc = double>
+struct SSSum {
+  static constexpr int DA = SSDimOf<MA>::value, DB = SSDimOf<MB>::value;
+  MA a;
+  MB b;
+  Sc Pinf[DA + DB][DA + DB];
+};
+
+// X = T blkdiag(Xa, Xb) T' (COV: a covariance) or T blkdiag(Xa, Xb) T^-1 (a transition)
+template <int DA, int DB, bool COV, typename Sc>
+SS_HD void ss_sum_basis(const Sc Xa[DA][DA], const Sc Xb[DB][DB], Sc X[DA + DB][DA + DB]) {
+  constexpr int D = DA + DB;
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      if (i < DA && j < DA) X[i][j] = Xa[i][j];
+      else if (i >= DA && j >= DA) X[i][j] = Xb[i - DA][j - DA];
+      else X[i][j] = 0.0;
+    }
+  for (int j = 0; j < D; ++j) X[0][j] += X[DA][j];
+  for (int i = 0; i < D; ++i) {
+    if (COV) X[i][0] += X[i][DA];
+    else X[i][DA] -= X[i][0];
+  }
+}
+
+template <typename MA, typename MB, typename Sc>
+SS_HD void ss_sum_model(const MA& a, const MB& b, SSSum<MA, MB, Sc>& M) {
+  M.a = a; M.b = b;
+  ss_sum_basis<SSSum<MA, MB, Sc>::DA, SSSum<MA, MB, Sc>::DB, true, Sc>(a.Pinf, b.Pinf, M.Pinf);
+}
+
+// A(dt) and Q(dt) of the sum from its terms' own: A' = T blkdiag(A_a, A_b) T^-1, and Q' = Pinf' - A' Pinf' A'' taken block by block,
+// T blkdiag(Q_a, Q_b) T' with Q_c = Pinf_c - A_c Pinf_c A_c' (the same matrix; the blocks' zeros stay exact and the products are
+// those of the terms).  dt = 0: A_a = A_b = I and Q_a = Q_b = 0 exactly, so A' = I (its entry (1, D_a + 1) is 1 - 1) and Q' = 0 exactly.
+template <int D, typename Sc = double, typename MA, typename MB>
+SS_HD void ss_AQ(const SSSum<MA, MB, Sc>& M, double dt, Sc A[D][D], Sc Q[D][D]) {
+  constexpr int DA = SSSum<MA, MB, Sc>::DA, DB = SSSum<MA, MB, Sc>::DB;
+  static_assert(D == DA + DB, "the sum's state dimension is that of its terms together");
+  Sc Aa[DA][DA], Qa[DA][DA], Ab[DB][DB], Qb[DB][DB];
+  ss_AQ<DA, Sc>(M.a, dt, Aa, Qa);
+  ss_AQ<DB, Sc>(M.b, dt, Ab, Qb);
+  ss_sum_basis<DA, DB, false, Sc>(Aa, Ab, A);
+  ss_sum_basis<DA, DB, true, Sc>(Qa, Qb, Q);
+}
+
 template <int D, typename Sc = double>
 SS_HD void ss_mm(const Sc X[D][D], const Sc Y[D][D], Sc Z[D][D]) {      // Z = X Y
   for (int i = 0; i < D; ++i)
@@ -230,9 +285,39 @@ SS_HD void ss_sym(Sc X[D][D]) {
     for (int j = i + 1; j < D; ++j) X[i][j] = X[j][i] = 0.5 * (X[i][j] + X[j][i]);
 }
 
-// X^-1 of a general D x D matrix by cofactors (relative accuracy is invariant under the diagonal scalings that separate f, f', f'')
+// X^-1 of a general D x D matrix by cofactors (relative accuracy is invariant under the diagonal scalings that separate f, f', f'').
+// D = 4 (a sum model): the adjugate through the twelve 2 x 2 minors of rows (0, 1) and rows (2, 3), not a block inverse.  The
+// matrices inverted here are I + C J with C, J positive semi-definite, whose entries scale like X_ij ~ s_i / s_j with s = (1, lam,
+// lam^2, ..) per block.  Every product in a minor, in a cofactor and in the determinant takes one entry from each of its rows and
+// columns, so all the terms of one sum carry the same power of the s_i: the scalings factor out of every sum and the rounding is
+// that of the well-scaled matrix.  A block inverse divides by a Schur complement of the leading block instead, which is exact in
+// the same sense only while that block stays well conditioned, and costs a second 2 x 2 inverse on the critical path.
 template <int D, typename Sc = double>
 SS_HD void ss_inv(const Sc X[D][D], Sc Y[D][D]) {
+  if constexpr (D == 4) {
+    const Sc s0 = X[0][0] * X[1][1] - X[1][0] * X[0][1], s1 = X[0][0] * X[1][2] - X[1][0] * X[0][2], s2 = X[0][0] * X[1][3] - X[1][0] * X[0][3];
+    const Sc s3 = X[0][1] * X[1][2] - X[1][1] * X[0][2], s4 = X[0][1] * X[1][3] - X[1][1] * X[0][3], s5 = X[0][2] * X[1][3] - X[1][2] * X[0][3];
+    const Sc c5 = X[2][2] * X[3][3] - X[3][2] * X[2][3], c4 = X[2][1] * X[3][3] - X[3][1] * X[2][3], c3 = X[2][1] * X[3][2] - X[3][1] * X[2][2];
+    const Sc c2 = X[2][0] * X[3][3] - X[3][0] * X[2][3], c1 = X[2][0] * X[3][2] - X[3][0] * X[2][2], c0 = X[2][0] * X[3][1] - X[3][0] * X[2][1];
+    const Sc r = 1.0 / (s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0);
+    Y[0][0] = (X[1][1] * c5 - X[1][2] * c4 + X[1][3] * c3) * r;
+    Y[0][1] = (X[0][2] * c4 - X[0][1] * c5 - X[0][3] * c3) * r;
+    Y[0][2] = (X[3][1] * s5 - X[3][2] * s4 + X[3][3] * s3) * r;
+    Y[0][3] = (X[2][2] * s4 - X[2][1] * s5 - X[2][3] * s3) * r;
+    Y[1][0] = (X[1][2] * c2 - X[1][0] * c5 - X[1][3] * c1) * r;
+    Y[1][1] = (X[0][0] * c5 - X[0][2] * c2 + X[0][3] * c1) * r;
+    Y[1][2] = (X[3][2] * s2 - X[3][0] * s5 - X[3][3] * s1) * r;
+    Y[1][3] = (X[2][0] * s5 - X[2][2] * s2 + X[2][3] * s1) * r;
+    Y[2][0] = (X[1][0] * c4 - X[1][1] * c2 + X[1][3] * c0) * r;
+    Y[2][1] = (X[0][1] * c2 - X[0][0] * c4 - X[0][3] * c0) * r;
+    Y[2][2] = (X[3][0] * s4 - X[3][1] * s2 + X[3][3] * s0) * r;
+    Y[2][3] = (X[2][1] * s2 - X[2][0] * s4 - X[2][3] * s0) * r;
+    Y[3][0] = (X[1][1] * c1 - X[1][0] * c3 - X[1][2] * c0) * r;
+    Y[3][1] = (X[0][0] * c3 - X[0][1] * c1 + X[0][2] * c0) * r;
+    Y[3][2] = (X[3][1] * s1 - X[3][0] * s3 - X[3][2] * s0) * r;
+    Y[3][3] = (X[2][0] * s3 - X[2][1] * s1 + X[2][2] * s0) * r;
+    return;
+  }
   if (D == 1) { Y[0][0] = 1.0 / X[0][0]; return; }
   if (D == 2) {
     const Sc a = X[0][0], b = X[0][D - 1], c = X[D - 1][0], d = X[D - 1][D - 1];
@@ -520,6 +605,7 @@ SS_HD void ss_drift(const SSOsc<double>& M, double F[D][D]) {
   for (int i = 0; i < D; ++i)
     for (int j = 0; j < D; ++j) F[i][j] = M.N[i][j] - (i == j ? M.a : 0.0);
 }
+// (A sum, SSSum, has none yet: its drift would be T blkdiag(F_a, F_b) T^-1, and gradients with respect to locations refuse sum latents.)
 
 // g = d lml / d dt of ONE transition: the spacing dt between point t - 1, with FILTERED state (m, P), and point t, with SMOOTHED state
 // (ms, Ps).  lml depends on dt only through the predicted state mp = A m, Pp = A P A' + Q of point t, with d mp / d dt = F mp and

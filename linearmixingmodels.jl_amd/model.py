@@ -190,7 +190,9 @@ class SHOKernel(_Kernel):
     1/2 (critically damped and overdamped) is not served.  It is exactly a two-dimensional linear SDE: the state-space functions
     (statespace_logpdf, statespace_mean_and_var, statespace_logpdf_and_gradient, statespace_rand) serve it alone or mixed with Matern
     latents, in O(n).  The dense verbs serve it too (logpdf, posterior and what is asked of it, logpdf_and_gradient with "quality", NaN
-    data; OILMM, IndependentMOGP and dense-H); inputs=True, mean_and_var_vjp, the VFE functions and sum kernels refuse it."""
+    data; OILMM, IndependentMOGP and dense-H); inputs=True, mean_and_var_vjp, the VFE functions and sum kernels refuse it.  (The C ABI's state-space
+    entry points take a two-term sum with an SHO term, through lmm_kernel_sum_create_statespace; the state-space functions here serve
+    Matern-only sums.)"""
     kind = "sho"
 
     def __init__(self, variance: float = 1.0, lengthscale=1.0, quality: float = 1.0):
@@ -905,7 +907,31 @@ def _sparse_mean_and_var(fx: "FiniteGP", add_noise: bool, want_var: bool):
 # Matern12 / 32 / 52 latents over a one-dimensional input are finite-dimensional linear SDEs, so a Kalman filter gives logpdf and an RTS
 # smoother the posterior marginals in O(n), exactly (include/lmm_hip.h, "state space").  The library takes sorted
 # inputs; the sorting, and the merging of new inputs as points without observations, happen here.
-_STATESPACE_KINDS = ("matern12", "matern32", "matern52", "sho")
+_STATESPACE_DIM = {"matern12": 1, "matern32": 2, "matern52": 3, "sho": 2}
+_STATESPACE_MAX_DIM = 4      # the largest state the kernels are built for: a sum of two terms whose dimensions add up to it
+
+
+def _statespace_dim(k) -> Optional[int]:
+    """The state dimension of a latent kernel the state-space functions serve, None for any other: a plain Matern12 / 32 / 52 or SHO
+    with a scalar lengthscale, or a KernelSum of exactly two plain Matern terms whose dimensions add up to at most 4 (the sum's own
+    variance and lengthscale fold into the terms; the library has one order of the terms, so either order is served).  An SHO term
+    inside a KernelSum stays refused here, as on the dense verbs: the library serves it (lmm_kernel_sum_create_statespace,
+    L.statespace_gps_array), these functions do not yet."""
+    if k.kind in _STATESPACE_DIM:
+        return _STATESPACE_DIM[k.kind] if np.ndim(k.lengthscale) == 0 else None
+    if k.kind == "sum" and len(k.kernels) == 2:
+        dims = [None if t.kind in ("sum", "sho") else _statespace_dim(t) for t in k.kernels]
+        if None not in dims and sum(dims) <= _STATESPACE_MAX_DIM:
+            return sum(dims)
+    return None
+
+
+def _statespace_refuse_sums(fx: "FiniteGP", what: str) -> None:
+    """Gradients with respect to locations are not served for a sum latent: the second component of its state is not f'."""
+    for l, gp in enumerate(fx.f.f.fs):
+        if gp.kernel.kind == "sum":
+            raise NotImplementedError(f"{what}: gradients with respect to locations are not served for a sum latent on the state-space "
+                                      f"path; latent {l} is {gp.kernel!r}")
 
 
 def _statespace_sorted(xv, y, p: int, xs=None):
@@ -977,7 +1003,7 @@ def _statespace_args(fx: "FiniteGP", y, what: str):
         raise NotImplementedError(f"{what}: state-space inference is served for one-dimensional inputs (d = {x.dim})")
     for l, gp in enumerate(f.f.fs):
         k = gp.kernel
-        if k.kind not in _STATESPACE_KINDS or np.ndim(k.lengthscale) != 0:
+        if _statespace_dim(k) is None:
             raise NotImplementedError(f"{what}: state-space inference is served for plain Matern12, Matern32 and Matern52 latents; "
                                       f"latent {l} is {k!r}")
     if not hasattr(y, "shape"):
@@ -992,7 +1018,8 @@ def _statespace_args(fx: "FiniteGP", y, what: str):
 
 def statespace_logpdf(fx: "FiniteGP", y, with_regulariser: bool = True) -> float:
     """logpdf(fx, y) of a prior OILMM whose latents are Matern12 / 32 / 52 or SHO (in any mixture and order) over one-dimensional inputs, by a
-    Kalman filter per latent:
+    Kalman filter per latent; a latent may also be a KernelSum of two plain Matern terms whose state dimensions (1 / 2 / 3) add up to
+    at most 4 -- "short + long lengthscale" in one latent (_statespace_dim; DESIGN.md 4.18 "Sum latents"):
     the value of logpdf (NaN in y included: the missing-data approximation of logpdf) in O(n).  Points may come in any order (they are
     sorted here, stably); a point whose outputs are all NaN is a predict-only step and leaves the value unchanged."""
     y = _statespace_args(fx, y, "statespace_logpdf")
@@ -1039,8 +1066,9 @@ class StateSpacePosterior:
     Built by statespace_posterior; freed by close(), on leaving a `with` block or with the object."""
 
     def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float, dims: Optional[Sequence[int]] = None,
-                 x_last: Optional[float] = None):
+                 x_last: Optional[float] = None, sums: Sequence[int] = ()):
         self._ptr, self.n, self.p, self.logpdf = ptr, n, p, logpdf
+        self._sums = [int(l) for l in sums]                                  # the sum latents: mean_and_var_vjp refuses them
         self._dims = None if dims is None else [int(D) for D in dims]       # the latents' state dimensions: what rand draws per point
         self._x_last = None if x_last is None else float(x_last)            # the last input, kept on the host for append's check
 
@@ -1190,6 +1218,9 @@ class StateSpacePosterior:
         depend on xs, so there is no add_noise argument and no "sigma2" entry.  A query's entry depends on no other query.
         Matern12 latents only: at a query equal to a training input the mean has a kink, and the derivative returned is that of the
         side the query is sorted to (behind the training point); Matern32, Matern52 and SHO latents are differentiable there."""
+        if self._sums:
+            raise NotImplementedError("StateSpacePosterior.mean_and_var_vjp: gradients with respect to locations are not served for a "
+                                      f"sum latent on the state-space path (latent {self._sums[0]})")
         xs = self._queries(xs)
         ns = int(xs.shape[0])
         if dmean is None and dvar is None:
@@ -1323,7 +1354,8 @@ def statespace_posterior(fx: "FiniteGP", y) -> StateSpacePosterior:
     ptr, out = C.c_void_p(), C.c_double()
     L.check(L.load().lmm_oilmm_statespace_posterior_create(L.Arr(xa).ptr, x.n, L.Arr(ya).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps,
                                                            0, m, C.byref(ptr), C.byref(out)))
-    return StateSpacePosterior(ptr, x.n, p, out.value, [_STATESPACE_DIM[g.kernel.kind] for g in f.f.fs], float(xa[-1]))
+    return StateSpacePosterior(ptr, x.n, p, out.value, [_statespace_dim(g.kernel) for g in f.f.fs], float(xa[-1]),
+                               [l for l, g in enumerate(f.f.fs) if g.kernel.kind == "sum"])
 
 
 class _NoStateSpaceMixingGradient(dict):
@@ -1344,6 +1376,8 @@ def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = T
     (include/lmm_hip.h, lmm_oilmm_logpdf_grad_statespace_x): shaped and typed like fx.x.x, in the callers' order of points, exactly 0
     at points whose outputs are all NaN; every other entry is bitwise that of inputs=False."""
     y = _statespace_args(fx, y, "statespace_logpdf_and_gradient")
+    if inputs:
+        _statespace_refuse_sums(fx, "statespace_logpdf_and_gradient(inputs=True)")
     f, x = fx.f, fx.x
     nan = _has_nan(y)
     xa, ya, perm, n = _statespace_sorted(x.x.reshape(-1), y, x.out_dim)
@@ -1373,9 +1407,6 @@ def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = T
         return _NoStateSpaceMixingGradient(out)
     out.update(S=gS, U=gU.reshape(m, p).T.copy())
     return out
-
-
-_STATESPACE_DIM = {"matern12": 1, "matern32": 2, "matern52": 3, "sho": 2}
 
 
 def statespace_rand(rng, fx: "FiniteGP", y=None, N: Optional[int] = None, add_noise: bool = True, xs=None):
@@ -1409,7 +1440,7 @@ def statespace_rand(rng, fx: "FiniteGP", y=None, N: Optional[int] = None, add_no
     L.ensure_init()
     _, gps = _gps_arg(f.f)
     Ua, Sa, p, m = _H_args(f.H)
-    dims = [_STATESPACE_DIM[g.kernel.kind] for g in f.f.fs]
+    dims = [_statespace_dim(g.kernel) for g in f.f.fs]
     z = _empty_for(rng, Ns, sum(dims) * na)
     xi = _empty_for(rng, Ns, m * na) if y is not None else None
     eps = _empty_for(rng, Ns, na * p) if add_noise else None
