@@ -2246,12 +2246,18 @@ int check_batches(const int* batch_n, const double* batch_s2, int nbatch, int n)
   return LMM_OK;
 }
 
-struct OilmmGrad {          // host results of oilmm_grad_core (partial sums over the latent shard)
+struct OilmmGrad {          // host results of an OILMM gradient (partial sums over the latent shard)
   double value = 0.0;
   std::vector<double> gs2;    // one per noise block
   std::vector<double> gS, gU;
   std::vector<lmm_gp_grad_t> ggps;
   std::vector<double> trec;   // m x LMM_SUM_MAX_TERMS records per latent and term (grad_finish), zeros elsewhere
+  void size(int m, int p, int nblk, int d) {      // every sum at zero
+    gs2.assign(nblk, 0.0);
+    gS.assign(m, 0.0); gU.assign((size_t)p * m, 0.0);
+    ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
+    trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
+  }
 };
 
 // The regulariser of reference src/oilmm.jl:101-113, once per noise block: its value (added to `total`), its share of d/dS, d/dU and
@@ -2282,6 +2288,89 @@ void oilmm_regulariser_grad(const double* U, const double* S, int p, int m, cons
     for (size_t q = 0; q < G.gU.size(); ++q) G.gU[q] += (t1[q] + t2[q]) / s2;
   }
 }
+
+// The back end of the OILMM gradients for complete data (oilmm_grad_core, sparse_oilmm_grad, ss_logpdf_grad): the chain rule from a
+// path's per-latent sensitivities back through r_l = (T y)_l - mean_l with T = S^-1/2 U', the projected noise s2[b] / S_l and the
+// regulariser, into G.gs2 / gS / gU and d/dY.  The latents' own (variance, lengthscale, mean) gradients stay with the paths.
+struct OilmmGradIn {      // what a path hands it; the first row is set by position, the rest by name
+  const double* yd; int n, p; const double *U, *S; int m; NoiseBlocks NB; int l0, l1, with_regulariser;
+  // a (device, latent k of the shard at a + k lda): sgn * (-d value / d r_l), so sgn = 1 for alpha = -d lml / d r (exact, state space)
+  // and -1 for d elbo / d r itself; negation is exact, so one sign serves them bit for bit.  dot (device, n per latent): what
+  // aTy_k = a_k . dot_k is taken with, T y of all m latents (dot_all: ONE ms x m launch, [k, l0 + k] read) or a row per latent of the
+  // shard (a launch each; atb_kernel computes each output element in a block of its own, so its bits do not depend on the launch).
+  const double* a = nullptr; int lda = 0; double sgn = 1.0; const double* dot = nullptr; bool dot_all = false;
+  bool want_sum = false;      // asum[k] = sum_t a_t too, for a path with no other source of the mean's gradient (the inducing-point one)
+};
+// The constructor queues the products on streams[0] with their read-backs: YA = Y'a (p x ms), aTy and, with the regulariser,
+// M2 = Y Y' (p x p) per noise block.  finish() is host work for once streams[0] has drained.
+struct OilmmGradBackEnd : OilmmGradIn {
+  const int ms, mk;
+  Buf<double> YAd, aTyd, M2d, ones, asumd;
+  std::vector<double> YA, aTy, M2all, asum;
+  explicit OilmmGradBackEnd(const OilmmGradIn& in)
+      : OilmmGradIn(in), ms(l1 - l0), mk(std::max(ms, 1)), YAd((size_t)p * mk), aTyd((size_t)mk * (dot_all ? m : 1)), M2d((size_t)p * p * NB.nblk),
+        YA(YAd.n, 0.0), aTy(aTyd.n, 0.0), M2all(M2d.n, 0.0), asum(mk, 0.0) {
+    hipStream_t st0 = g.streams[0];
+    if (ms > 0) {
+      if (want_sum) { ones = Buf<double>(n); asumd = Buf<double>(mk); launch_fill(ones.p, n, 1.0, st0); }
+      launch_atb(yd, n, a, lda, n, p, ms, YAd.p, st0);
+      if (want_sum) launch_atb(a, lda, ones.p, n, n, ms, 1, asumd.p, st0);
+      if (dot_all) launch_atb(a, lda, dot, n, n, ms, m, aTyd.p, st0);
+      else for (int k = 0; k < ms; ++k) launch_atb(a + (size_t)k * lda, lda, dot + (size_t)k * n, n, n, 1, 1, aTyd.p + k, st0);
+      HIPCHK(hipMemcpyAsync(YA.data(), YAd.p, YA.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+      HIPCHK(hipMemcpyAsync(aTy.data(), aTyd.p, aTy.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+      if (want_sum) HIPCHK(hipMemcpyAsync(asum.data(), asumd.p, (size_t)ms * sizeof(double), hipMemcpyDeviceToHost, st0));
+    }
+    if (with_regulariser) {
+      for (int b = 0; b < NB.nblk; ++b) launch_atb(yd + NB.off[b], n, yd + NB.off[b], n, NB.count(b), p, p, M2d.p + (size_t)p * p * b, st0);
+      HIPCHK(hipMemcpyAsync(M2all.data(), M2d.p, M2all.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+    }
+  }
+  // dnoise[k * nblk + b]: d value / d (projected noise of latent k of the shard in block b); dot_add[k] (or nullptr): what aTy_k lacks
+  // (the state-space path dots with r, the mean taken off: mean_l * sum_t a_t); T: m x p.  Adds the shard's share to G.gs2 / gS / gU,
+  // then the regulariser's to them and its value to `value`, and writes gy_dev (n x p, device) when given.
+  void finish(const double* dnoise, const double* dot_add, const std::vector<double>& T, double& value, OilmmGrad& G, double* gy_dev) const {
+    hipStream_t st0 = g.streams[0];
+    const int nblk = NB.nblk;
+    for (int k = 0; k < ms; ++k) {
+      const int l = l0 + k;
+      double g_s2 = 0.0;                                   // sum_b s2[b] d value / d noise_b
+      for (int b = 0; b < nblk; ++b) {
+        const double gb = dnoise[(size_t)k * nblk + b];
+        G.gs2[b] += gb / S[l];
+        g_s2 += gb * NB.s2[b];
+      }
+      double aTyl = dot_all ? aTy[k + (size_t)l * ms] : aTy[k];
+      if (dot_add) aTyl += dot_add[k];
+      G.gS[l] += -g_s2 / (S[l] * S[l]) + 0.5 * (sgn * aTyl) / S[l];
+      for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] += -(sgn * YA[o + (size_t)k * p]) / std::sqrt(S[l]);
+    }
+    std::vector<double> PtP;       // P'P for the regulariser's dY
+    if (with_regulariser) oilmm_regulariser_grad(U, S, p, m, NB, M2all, value, G, PtP);
+    if (!gy_dev) return;
+    // d value / dY[o, i] = -sgn sum_l T[l, o] a_l[i] - (P'P Y)[o, i] / sigma2(i)
+    std::vector<double> Tt((size_t)p * mk, 0.0);
+    for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) Tt[o + (size_t)k * p] = -(sgn * T[(l0 + k) + (size_t)o * m]);
+    Uploaded Ttd(Tt, st0);
+    Buf<double> ga((size_t)n * p), ac;
+    const double* lat = a;
+    if (lda != n) {      // mix reads lat[l * n + i]: a compact copy first
+      ac = Buf<double>((size_t)n * mk);
+      for (int k = 0; k < ms; ++k) HIPCHK(hipMemcpyAsync(ac.p + (size_t)k * n, a + (size_t)k * lda, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
+      lat = ac.p;
+    }
+    launch_mix(lat, n, ms, Ttd.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, with_regulariser ? ga.p : gy_dev, st0);
+    Uploaded Qd;
+    Buf<double> gq;
+    if (with_regulariser) {
+      Qd = Uploaded(PtP, st0);
+      gq = Buf<double>((size_t)n * p);
+      launch_tall_skinny(yd, n, n, p, Qd.buf.p, p, p, gq.p, n, nullptr, nullptr, 0, nullptr, 0, st0);   // (Y' (P'P)')' rows
+      launch_vec_lin_blocks(ga.p, gq.p, NB, -1.0, n, (size_t)n * p, gy_dev, st0);
+    }
+    HIPCHK(hipStreamSynchronize(st0));         // Ttd, ga, ac, gq and Qd are released on return
+  }
+};
 
 // What oilmm_grad_core and oilmm_grad_missing_core share, per latent of the shard: the training matrix with the residual as its rider,
 // its factor, alpha = Kt^-1 delta, Kt^-1 = L^-T L^-1 (triangular solve of identity riders + an upper-triangular SYRK, over the factor's
@@ -2364,10 +2453,6 @@ struct KernelGradPass {
   }
 
   // ---- host, once the main stream has drained ----
-  void init_outputs(int m, std::vector<lmm_gp_grad_t>& ggps, std::vector<double>& trec) const {
-    ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
-    trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
-  }
   // the sums of latent k's first term: [1] tr Kt^-1 and [2] alpha.alpha over the rows below nsplit ([5], [6]: from nsplit on),
   // [3] alpha.delta, [4] sum(alpha)
   const double* sums(int k) const { return &hred[(size_t)LMM_NGRAD * toff[k]]; }
@@ -2463,70 +2548,34 @@ int oilmm_grad_core(const double* xd, int d, int N, const NoiseBlocks& NB, const
   std::vector<double> hblk(nblk > 2 ? (size_t)2 * nblk * mk : 0, 0.0);
   if (!hblk.empty() && ms > 0) HIPCHK(hipMemcpyAsync(hblk.data(), blksum.p, hblk.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   K.F.fetch_info();
-  // small dense products needed by the chain rule: YA = Y' alpha (p x ms), aTy = alpha_l . (T y)_l, M2 = Y Y' (p x p) per noise block
-  const size_t pp = (size_t)p * p;
-  Buf<double> YAd((size_t)p * mk), aTyd((size_t)mk * m), M2d(pp * nblk);
-  if (ms > 0) {
-    launch_atb(yd, n, alpha.p, D.NC, n, p, ms, YAd.p, st0);
-    launch_atb(alpha.p, D.NC, Ty.p, n, n, ms, m, aTyd.p, st0);       // [k, l]; only l = l0 + k is used
-  }
-  std::vector<double> YA((size_t)p * mk, 0.0), aTy((size_t)mk * m, 0.0), M2all(pp * nblk, 0.0);
-  if (with_regulariser) {
-    for (int b = 0; b < nblk; ++b) launch_atb(yd + NB.off[b], n, yd + NB.off[b], n, NB.count(b), p, p, M2d.p + pp * b, st0);
-    HIPCHK(hipMemcpyAsync(M2all.data(), M2d.p, M2all.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  }
-  HIPCHK(hipMemcpyAsync(YA.data(), YAd.p, YA.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(aTy.data(), aTyd.p, aTy.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  // the back end's products are queued ahead of the wait for the pivots; alpha = -d lml / d delta, dotted with T y itself
+  OilmmGradIn in{yd, n, p, U, S, m, NB, l0, l1, with_regulariser};
+  in.a = alpha.p; in.lda = D.NC; in.dot = Ty.p; in.dot_all = true;
+  OilmmGradBackEnd B(in);
   if (int rc = K.F.check(l0)) return rc;
 
-  // ---- host chain rule ----
+  // ---- host: the latents' own gradients and d lml / d (projected noise) per block ----
   double total = 0.0;
-  G.gs2.assign(nblk, 0.0);
-  G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
-  K.init_outputs(m, G.ggps, G.trec);
+  G.size(m, p, nblk, d);
+  std::vector<double> dnoise((size_t)mk * nblk, 0.0);
   for (int k = 0; k < ms; ++k) {
     const int l = l0 + k;
     total += K.lml[k];
     const double* r = K.sums(k);
     double aa_all = 0.0, tr_all = 0.0;
-    double D_aa = 0.0, D_tr = 0.0, g_s2 = 0.0;       // a'Da, tr(Kt^-1 D) with D the projected noise; sum_b s2[b] dlml/dnoise_b
+    double D_aa = 0.0, D_tr = 0.0;       // a'Da, tr(Kt^-1 D) with D the projected noise
     for (int b = 0; b < nblk; ++b) {
       // tr Kinv and alpha.alpha over the block's rows
       const double tr = nblk > 2 ? hblk[((size_t)k * nblk + b) * 2] : r[b ? 5 : 1];
       const double aa = nblk > 2 ? hblk[((size_t)k * nblk + b) * 2 + 1] : r[b ? 6 : 2];
-      const double gb = 0.5 * (aa - tr);                                       // d lml / d (projected noise of block b)
+      dnoise[(size_t)k * nblk + b] = 0.5 * (aa - tr);
       D_aa += ST[b][l] * aa; D_tr += ST[b][l] * tr;
       aa_all += aa; tr_all += tr;
-      G.gs2[b] += gb / S[l];
-      g_s2 += gb * NB.s2[b];
     }
     K.finish(k, D_aa, D_tr, aa_all, tr_all, G.ggps, G.trec);
-    G.gS[l] += -g_s2 / (S[l] * S[l]) + 0.5 * aTy[k + (size_t)l * ms] / S[l];
-    for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] += -YA[o + (size_t)k * p] / std::sqrt(S[l]);
   }
-  std::vector<double> PtP;       // P'P for the regulariser's dY
-  if (with_regulariser) oilmm_regulariser_grad(U, S, p, m, NB, M2all, total, G, PtP);
+  B.finish(dnoise.data(), nullptr, T, total, G, gy_dev);
   G.value = total;
-  if (gy_dev) {
-    // dL/dY[o, i] = - sum_l T[l, o] alpha_l[i]  - (P'P Y)[o, i] / sigma2(i)
-    std::vector<double> negTt((size_t)p * mk, 0.0);
-    for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) negTt[o + (size_t)k * p] = -T[(l0 + k) + (size_t)o * m];
-    Uploaded nT(negTt, st0);
-    Buf<double> ga((size_t)n * p);
-    // mix reads lat[l*ns + s] with ns = n: alpha is stored with stride NC -> compact copy first
-    Buf<double> ac((size_t)n * mk);
-    for (int k = 0; k < ms; ++k) HIPCHK(hipMemcpyAsync(ac.p + (size_t)k * n, alpha.p + (size_t)k * D.NC, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st0));
-    launch_mix(ac.p, n, ms, nT.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, with_regulariser ? ga.p : gy_dev, st0);
-    if (with_regulariser) {
-      Uploaded Qd(PtP, st0);
-      Buf<double> gr((size_t)n * p);
-      launch_tall_skinny(yd, n, n, p, Qd.buf.p, p, p, gr.p, n, nullptr, nullptr, 0, nullptr, 0, st0);   // (Y' (P'P)')' rows
-      launch_vec_lin_blocks(ga.p, gr.p, NB, -1.0, n, (size_t)n * p, gy_dev, st0);
-      HIPCHK(hipStreamSynchronize(st0));       // ga, gr, Qd are released on return
-    } else {
-      HIPCHK(hipStreamSynchronize(st0));
-    }
-  }
   return LMM_OK;
 }
 
@@ -2606,14 +2655,12 @@ int predictive_grad(const LatentSet& ls, int l0, int l1, const double* xd, const
   return LMM_OK;
 }
 
-void write_oilmm_grad(const OilmmGrad& G, int m, int p, double* out_logpdf, double* grad_sigma2, double* grad_S, double* grad_U,
-                      lmm_gp_grad_t* grad_gps) {
-  *out_logpdf = G.value;
+void write_oilmm_grad(const OilmmGrad& G, double* out_value, double* grad_sigma2, double* grad_S, double* grad_U, lmm_gp_grad_t* grad_gps) {
+  if (out_value) *out_value = G.value;
   if (grad_sigma2) { *grad_sigma2 = 0.0; for (double v : G.gs2) *grad_sigma2 += v; }
   if (grad_S) std::copy(G.gS.begin(), G.gS.end(), grad_S);
   if (grad_U) std::copy(G.gU.begin(), G.gU.end(), grad_U);
   if (grad_gps) std::copy(G.ggps.begin(), G.ggps.end(), grad_gps);
-  (void)m; (void)p;
 }
 
 }  // namespace
@@ -2645,7 +2692,7 @@ int lmm_oilmm_logpdf_grad_x(const double* x, int d, int n, const double* y, int 
   if (int rc = oilmm_grad_core(R.xd.p, d, n, one_noise_block(n, sigma2), R.yd.p, p, U, S, R.ls.get(), latent_begin, latent_end, with_regulariser,
                                G, gy.p, gx.p))
     return rc;
-  write_oilmm_grad(G, m, p, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
+  write_oilmm_grad(G, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
   publish_grads(*R.ls, grad_gps ? &G.trec : nullptr, latent_begin, latent_end);
   if (grad_y) gy.finish(st0);
   if (grad_x) gx.finish(st0);
@@ -3535,12 +3582,22 @@ int lmm_oilmm_posterior_create_missing(const double* x, int d, int n, const doub
   LMM_CATCH
 }
 
+// The back end of the OILMM gradients for data with NaN (oilmm_grad_missing_core, ss_logpdf_grad), over the n points the front end F
+// numbered: the regulariser's share of d/dsigma2 (added to G.gs2[0]) and d/dY through the per-point projections (gy_dev: n x p, device,
+// or nullptr) from a = -d value / d r (device, latent k of the shard at a + k lda).  The latents' share of d/dsigma2 stays with the paths.
+static void missing_grad_back_end(const MissingFront& F, int n, int p, int m, double s2, int with_regulariser, const double* a, int lda,
+                                  int l0, int ms, OilmmGrad& G, double* gy_dev) {
+  if (with_regulariser) G.gs2[0] += -0.5 * ((F.sum_pt - (double)n * m) / s2 - F.rss / (s2 * s2));
+  if (gy_dev)
+    launch_missing_grad_y(n, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, a, lda, l0, ms, with_regulariser ? F.resid.p : nullptr, s2, gy_dev,
+                          g.streams[0]);
+}
+
 // The path beside oilmm_grad_core for precomputed per-latent residuals and per-point noise (F.z, F.nv): the same per-latent factor,
 // alpha, Kt^-1 and launch_grad_reduce; the chain rule runs through the per-point noise (missing_wdiag_kernel) instead of s2 / S, and
 // d/dy through the per-point projection (missing_grad_y_kernel).  No derivatives with respect to S, U or x.
 static int oilmm_grad_missing_core(const double* xd, int d, int n, int p, double s2, const LatentSet* ls, int l0, int l1,
-                                   int with_regulariser, const MissingFront& F, double* value, double* gs2_out,
-                                   std::vector<lmm_gp_grad_t>& ggps, std::vector<double>& trec, double* gy_dev) {
+                                   int with_regulariser, const MissingFront& F, OilmmGrad& G, double* gy_dev) {
   hipStream_t st0 = g.streams[0];
   const int m = (int)ls->lat.size(), ms = l1 - l0;
   KernelGradPass K(ls, l0, l1, n, d);
@@ -3553,24 +3610,20 @@ static int oilmm_grad_missing_core(const double* xd, int d, int n, int p, double
   std::vector<double> hwd(2 * (size_t)K.F.mk, 0.0);
   if (ms > 0) HIPCHK(hipMemcpyAsync(hwd.data(), wd.p, hwd.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
   K.F.fetch_info();
-  if (gy_dev)
-    launch_missing_grad_y(n, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, K.alpha.p, K.D.NC, l0, ms, with_regulariser ? F.resid.p : nullptr, s2,
-                          gy_dev, st0);
+  G.size(m, p, 1, d);
+  missing_grad_back_end(F, n, p, m, s2, with_regulariser, K.alpha.p, K.D.NC, l0, ms, G, gy_dev);      // d/dY is queued ahead of the wait for the pivots
   if (int rc = K.F.check(l0)) return rc;
   double total = 0.0, gs2 = 0.0;
-  K.init_outputs(m, ggps, trec);
   for (int k = 0; k < ms; ++k) {
     total += K.lml[k];
     const double* r = K.sums(k);
     const double D_aa = hwd[2 * (size_t)k], D_tr = hwd[2 * (size_t)k + 1];      // alpha' D alpha, tr(Kt^-1 D), D = diag(s2 (G_t^-1)_ll)
-    K.finish(k, D_aa, D_tr, r[2], r[1], ggps, trec);
+    K.finish(k, D_aa, D_tr, r[2], r[1], G.ggps, G.trec);
     gs2 += 0.5 * (D_aa - D_tr) / s2;            // sum_t c_lt (alpha_t^2 - (Kt^-1)_tt) / 2, c_lt = (G_t^-1)_ll
   }
-  if (with_regulariser) {
-    total += F.reg(n, m, s2);
-    gs2 += -0.5 * ((F.sum_pt - (double)n * m) / s2 - F.rss / (s2 * s2));
-  }
-  *value = total; *gs2_out = gs2;
+  if (with_regulariser) total += F.reg(n, m, s2);
+  G.value = total;
+  G.gs2[0] += gs2;                              // (the latents' sum + the regulariser's term: addition commutes)
   return LMM_OK;
 }
 
@@ -3588,16 +3641,10 @@ int lmm_oilmm_logpdf_grad_missing(const double* x, int d, int n, const double* y
   DevOut gy(grad_y, (size_t)n * p);
   MissingFront F;
   if (int rc = missing_front(R.yd.p, n, p, U, S, m, sigma2, R.means.data(), latent_begin, latent_end, grad_y && with_regulariser, F)) return rc;
-  double value = 0.0, gs2 = 0.0;
-  std::vector<lmm_gp_grad_t> ggps;
-  std::vector<double> trec;
-  if (int rc = oilmm_grad_missing_core(R.xd.p, d, n, p, sigma2, R.ls.get(), latent_begin, latent_end, with_regulariser, F, &value, &gs2,
-                                       ggps, trec, gy.p))
-    return rc;
-  *out_logpdf = value;
-  if (grad_sigma2) *grad_sigma2 = gs2;
-  if (grad_gps) std::copy(ggps.begin(), ggps.end(), grad_gps);
-  publish_grads(*R.ls, grad_gps ? &trec : nullptr, latent_begin, latent_end);
+  OilmmGrad G;
+  if (int rc = oilmm_grad_missing_core(R.xd.p, d, n, p, sigma2, R.ls.get(), latent_begin, latent_end, with_regulariser, F, G, gy.p)) return rc;
+  write_oilmm_grad(G, out_logpdf, grad_sigma2, nullptr, nullptr, grad_gps);
+  publish_grads(*R.ls, grad_gps ? &G.trec : nullptr, latent_begin, latent_end);
   if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
   return LMM_OK;
   LMM_CATCH
@@ -4495,9 +4542,13 @@ struct SparseState {
   std::vector<double> s, kappa, ctc;
 };
 
-static int sparse_shape_check(int d, int nz, double jitter) {
+static int sparse_size_check(int d, int nz) {      // what the kernels are built for; all the one-latent building blocks check
   if (nz > LMM_SPARSE_MMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for at most %d inducing points (nz = %d)", LMM_SPARSE_MMAX, nz);
   if (d > LMM_SPARSE_DMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for d <= %d (d = %d)", LMM_SPARSE_DMAX, d);
+  return LMM_OK;
+}
+static int sparse_shape_check(int d, int nz, double jitter) {
+  if (int rc = sparse_size_check(d, nz)) return rc;
   if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is Float64 only (lmm_set_compute_dtype(LMM_F64))");
   if (!(jitter > 0.0) || !std::isfinite(jitter)) return fail(LMM_ERR_ARG, "jitter must be finite and > 0");
   return LMM_OK;
@@ -4517,6 +4568,26 @@ static int sparse_plan(int n, int nz, int nb, int chunk, int* chunk_out, int* nc
     return fail(LMM_ERR_ARG, "chunk = %d gives %lld partials for n = %d: too many (raise chunk, or pass 0)", chunk, nch, n);
   *chunk_out = chunk; *nch_out = (int)nch;
   return LMM_OK;
+}
+struct SparsePoints { const double* x; int d, n; const double* z; int nz, chunk, nch; };      // what a pass over the points walks (sparse_plan)
+
+// The first pass over the points for nb latents (a.lat[0 .. nb), sparse_fill_lat): the moments per chunk, then their sums into Phi
+// (ld; zero_pad: its pad rows and columns too), b and the scalars.
+static void sparse_moments_pass(SparseMomArgs& a, const SparsePoints& P, double* scratch, int nb, int mode, const BatchPtr& Phi, int ld,
+                                bool zero_pad, const BatchPtr& b, const BatchPtr& scalars, hipStream_t st) {
+  a.x = P.x; a.z = P.z; a.d = P.d; a.n = P.n; a.nz = P.nz; a.chunk = P.chunk; a.nch = P.nch; a.scratch = scratch;
+  launch_sparse_moments(a, nb, mode, st);
+  launch_sparse_finish(scratch, P.nch, P.nz, Phi, ld, zero_pad, b, scalars, nb, st);
+}
+// The second pass for nb latents (hlat[0 .. nb), sparse_grad_fill_lat; dlat: their device copy, the caller's): the K_uf sums per chunk,
+// then the term records and d/dz (gz entries may be nullptr).
+static void sparse_grad_pass(const SparseGradLat* hlat, SparseGradLat* dlat, const SparsePoints& P, int ld, double* scratch, int nb, int mode,
+                             const BatchPtr& records, const BatchPtr& gz, hipStream_t st) {
+  HIPCHK(hipMemcpyAsync(dlat, hlat, (size_t)nb * sizeof(SparseGradLat), hipMemcpyHostToDevice, st));
+  SparseGradArgs a{};
+  a.x = P.x; a.z = P.z; a.d = P.d; a.n = P.n; a.nz = P.nz; a.chunk = P.chunk; a.nch = P.nch; a.ld = ld; a.scratch = scratch; a.lat = dlat;
+  launch_sparse_grad(a, nb, mode, st);
+  launch_sparse_grad_finish(scratch, P.nch, P.nz, P.d, records, gz, nb, st);
 }
 
 // rv: device, the projected data of latent l0 + k at rv + k * n (its mean rsub[l0 + k] is subtracted by the kernel); wconst[l0 + k]: its
@@ -4546,7 +4617,6 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
   F.run([&](const FanBatch& fb) {
     const int k0 = fb.k0, nb = fb.nb;
     SparseMomArgs a{};
-    a.x = xd; a.z = zd; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.scratch = scratch.p;
     BatchPtr Pb{}, Qb{}, bb{}, sb{};
     Batch Bu, Bb;
     GramArgs ga[LMM_MAX_BATCH];
@@ -4564,8 +4634,7 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
       Bu.add(out.Lu[k].p, out.Wu[k].p, info + k);
       Bb.add(out.LB[k].p, out.WB[k].p, info + ms + k);
     }
-    launch_sparse_moments(a, nb, sum_mode(lts, l0 + k0, l0 + k0 + nb), st);
-    launch_sparse_finish(scratch.p, nch, nz, Pb, D.ld, true, bb, sb, nb, st);
+    sparse_moments_pass(a, SparsePoints{xd, d, n, zd, nz, chunk, nch}, scratch.p, nb, sum_mode(lts, l0 + k0, l0 + k0 + nb), Pb, D.ld, true, bb, sb, st);
     // L_u = chol(K_uu + jitter I), with b as the rider row: it becomes c0 = L_u^-1 b
     gram_batch_g(ga, nb, st, "inducing Gram assembly");
     potrf_batch(Bu, D.ld, D.NR, D.NC, M, st, D.NC + 1);
@@ -4606,12 +4675,6 @@ static int sparse_core(const double* xd, int d, int n, const double* zd, int nz,
 // from the forward pass's factors: X' = L_u^-T (identity riders through trsm_rec), Y' = X' L_B^-T, K^-1 = X'X, Sigma^-1 = Y'Y,
 // beta = Y' c, K^-1 Phi K^-1 = X' Q X.  The second pass over the points (sparse_grad_kernel) contracts g = (2 PhiBar K_uf + beta r') / w with
 // d k; the K_uu terms are the gradient reductions of the exact path over x = z with alpha = 0 and -2 KuuBar as the inverse.
-struct SparseGradOut {
-  OilmmGrad G;
-  double* gy_dev = nullptr;                 // n x p (device) or nullptr
-  double* gz_dev = nullptr;                 // d x nz (device) or nullptr
-};
-
 static void sparse_grad_fill_lat(SparseGradLat& s, const Latent& gp, const LatentDev* gd, const double* w, double wconst, const double* r,
                                  double rsub, const double* PhiBar, const double* beta, double* grad_r) {
   s.g = gp.dev(); s.gd = gd; s.nterms = gp.nt();
@@ -4680,16 +4743,12 @@ static int sparse_grad_core(const double* xd, int d, int n, const double* zd, in
     launch_syrk_upper_set(Sib, D.ld, Rub, D.ld, D.NC, nb, st);                             // lower(Si) = Y'Y = Sigma^-1
     launch_sparse_beta(Rub, D.ld, M, cb, betab, nb, st);
     launch_sparse_phibar(Kib, Sib, T2b, betab, T1b, D.ld, M, nb, st);                      // T1 <- PhiBar, lower(Si) <- -2 KuuBar
-    SparseGradArgs a{};
-    a.x = xd; a.z = zd; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.ld = D.ld; a.scratch = scratch.p; a.lat = dlat.p;
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
       sparse_grad_fill_lat(hlat[j], lts[l0 + k], gdd.p + toff[k], nullptr, wconst[l0 + k], rv + (size_t)k * n, rsub[l0 + k], T1[j].p,
                            betab.p[j], gr_dev + (size_t)k * n);
     }
-    HIPCHK(hipMemcpyAsync(dlat.p, hlat.data(), (size_t)nb * sizeof(SparseGradLat), hipMemcpyHostToDevice, st));
-    launch_sparse_grad(a, nb, mode, st);
-    launch_sparse_grad_finish(scratch.p, nch, nz, d, recb, gzb, nb, st);
+    sparse_grad_pass(hlat.data(), dlat.p, SparsePoints{xd, d, n, zd, nz, chunk, nch}, D.ld, scratch.p, nb, mode, recb, gzb, st);
     for (int j = 0; j < nb; ++j) {
       const int k = k0 + j;
       for (int c = 0; c < lts[l0 + k].nt(); ++c) {
@@ -4725,113 +4784,90 @@ static int sparse_grad_core(const double* xd, int d, int n, const double* zd, in
   return LMM_OK;
 }
 
-// The per-latent residual rows (T y)_l, the projected noise and (with_regulariser) the regulariser of lmm_oilmm_logpdf, then sparse_core.
-static int sparse_oilmm(const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
-                        const lmm_gp_t* gps, int l0, int l1, const double* z, int nz, double jitter, int with_regulariser,
-                        SparseState& out, double* reg, std::shared_ptr<LatentSet>* ls_out, Buf<double>* z_keep,
-                        SparseGradOut* grad = nullptr) {
-  if (int rc = train_args(!x || !y || !U || !S || !z || d <= 0 || n <= 0 || p <= 0 || m <= 0 || nz <= 0, p, m, S, sigma2, l0, l1, 0)) return rc;
+// The front end of the inducing-point entry points.  sparse_resolve, in the order the error codes are pinned in: `bad` (the entry
+// point's own NULL test, or a NULL / size defect of the shared arguments), m > p and the shard, the shape (nz, d, dtype, jitter),
+// sigma2, the latents resolved, SHO refused; no device work.  sparse_upload: x, y and z on the device, T = S^-1/2 U' and, on
+// streams[0], the shard's rows of T y (Ty; sparse_core subtracts the means) with the regulariser's residual.
+struct SparseTrain : Train {
+  int d = 0, n = 0, p = 0, m = 0, nz = 0, with_regulariser = 0;
+  const double *U = nullptr, *S = nullptr; double sigma2 = 0.0, jitter = 0.0;
+  OilmmFront F{0, 0};
+  Buf<double> z;                  // d x nz: the library's own copy (a posterior handle keeps it)
+  const double* Ty = nullptr;     // [latent of the shard][n], in F
+  double resid = 0.0, reg = 0.0;  // the copy queued by F.rows lands in resid; reg: sparse_value
+};
+static int sparse_resolve(bool bad, const double* x, int d, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                          const lmm_gp_t* gps, int l0, int l1, const double* z, int nz, double jitter, int with_regulariser, SparseTrain& T) {
+  bad = bad || !x || !y || !U || !S || !z || d <= 0 || n <= 0 || p <= 0 || m <= 0 || nz <= 0;
+  if (int rc = train_args(bad, p, m, S, sigma2, l0, l1, 0)) return rc;
   if (int rc = sparse_shape_check(d, nz, jitter)) return rc;
   if (!(sigma2 > 0.0)) return fail(LMM_ERR_ARG, "sigma2 must be > 0");
-  Train R;
-  if (int rc = train_resolve(gps, m, d, l0, l1, R)) return rc;
-  const std::shared_ptr<LatentSet>& ls = R.ls;
-  const Latent* lts = R.lts;
-  const std::vector<double>& means = R.means;
-  if (int rc = refuse_sho(*ls, "inducing-point inference is")) return rc;
-  if (grad) { if (int rc = ls->ard_grad_check()) return rc; }
-  out.keep_grad = grad != nullptr;
+  if (int rc = train_resolve(gps, m, d, l0, l1, T)) return rc;
+  T.d = d; T.n = n; T.p = p; T.m = m; T.nz = nz; T.with_regulariser = with_regulariser;
+  T.U = U; T.S = S; T.sigma2 = sigma2; T.jitter = jitter;
+  return refuse_sho(*T.ls, "inducing-point inference is");
+}
+static void sparse_upload(const double* x, const double* y, const double* z, SparseTrain& T) {
   hipStream_t st0 = g.streams[0];
-  OilmmFront F(U, S, p, m, sigma2);
-  const std::vector<double>& ST = F.ST;
-  R.upload(x, (size_t)d * n, y, (size_t)n * p);
-  const DevIn &xd = R.xd, &yd = R.yd;
-  Buf<double> zown((size_t)d * nz);
-  HIPCHK(hipMemcpyAsync(zown.p, z, (size_t)d * nz * sizeof(double), hipMemcpyDefault, st0));
-  F.Td = Uploaded(F.T, st0);      // (sparse_core subtracts the means)
+  T.F = OilmmFront(T.U, T.S, T.p, T.m, T.sigma2);
+  T.upload(x, (size_t)T.d * T.n, y, (size_t)T.n * T.p);
+  T.z = Buf<double>((size_t)T.d * T.nz);
+  HIPCHK(hipMemcpyAsync(T.z.p, z, (size_t)T.d * T.nz * sizeof(double), hipMemcpyDefault, st0));
+  T.F.Td = Uploaded(T.F.T, st0);
   // (T y) of every latent when the regulariser needs the residual, else of the shard
-  double resid = 0.0;
-  const double* Ty_shard = F.rows(yd.p, n, l0, l1 - l0, with_regulariser != 0, &resid);
-  if (int rc = sparse_core(xd.p, d, n, zown.p, nz, jitter, lts, l0, l1, Ty_shard, means.data(), ST.data(), out)) {
-    (void)hipStreamSynchronize(st0);      // the residual's copy targets this frame
+  T.Ty = T.F.rows(T.yd.p, T.n, T.l0, T.ms, T.with_regulariser != 0, &T.resid);
+}
+
+// The value: sparse_core on the front end's rows (out.keep_grad: the gradient's inputs stay in `out`), streams[0] drained, and the
+// regulariser of lmm_oilmm_logpdf in T.reg.
+static int sparse_value(SparseTrain& T, SparseState& out) {
+  hipStream_t st0 = g.streams[0];
+  if (int rc = sparse_core(T.xd.p, T.d, T.n, T.z.p, T.nz, T.jitter, T.lts, T.l0, T.l1, T.Ty, T.means.data(), T.F.ST.data(), out)) {
+    (void)hipStreamSynchronize(st0);      // the residual's copy targets T
     return rc;
   }
   HIPCHK(hipStreamSynchronize(st0));
-  *reg = 0.0;
-  if (with_regulariser) *reg = oilmm_regulariser(n, p, m, S, sigma2, resid);        // as lmm_oilmm_logpdf
-  if (grad) {
-    // host chain rule, as oilmm_grad_core's: a_l = -d elbo_l / d r in the place of alpha, d elbo_l / d w in the place of d lml / d noise
-    const int ms = l1 - l0, NGR = LMM_NGRAD;
-    OilmmGrad& G = grad->G;
-    std::vector<double> hred, hard, gksum;
-    Buf<double> gr((size_t)n * std::max(ms, 1)), ones(n);
-    const double* rvs = Ty_shard;
-    if (int rc = sparse_grad_core(xd.p, d, n, zown.p, nz, ls.get(), l0, l1, rvs, means.data(), ST.data(), out, hred, hard, gksum, gr.p,
-                                  grad->gz_dev)) return rc;
-    const size_t pp = (size_t)p * p;
-    Buf<double> YAd((size_t)p * std::max(ms, 1)), aTyd(std::max(ms, 1)), sad(std::max(ms, 1)), M2d(pp);
-    std::vector<double> YA((size_t)p * std::max(ms, 1), 0.0), aTy(std::max(ms, 1), 0.0), sa(std::max(ms, 1), 0.0), M2all(pp, 0.0);
-    if (ms > 0) {
-      launch_fill(ones.p, n, 1.0, st0);
-      launch_atb(yd.p, n, gr.p, n, n, p, ms, YAd.p, st0);                   // Y' (d elbo / d r_l), p x ms
-      launch_atb(gr.p, n, ones.p, n, n, ms, 1, sad.p, st0);
-      for (int k = 0; k < ms; ++k) launch_atb(gr.p + (size_t)k * n, n, rvs + (size_t)k * n, n, n, 1, 1, aTyd.p + k, st0);
-      HIPCHK(hipMemcpyAsync(YA.data(), YAd.p, YA.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-      HIPCHK(hipMemcpyAsync(aTy.data(), aTyd.p, (size_t)ms * sizeof(double), hipMemcpyDeviceToHost, st0));
-      HIPCHK(hipMemcpyAsync(sa.data(), sad.p, (size_t)ms * sizeof(double), hipMemcpyDeviceToHost, st0));
-    }
-    if (with_regulariser) {
-      launch_atb(yd.p, n, yd.p, n, n, p, p, M2d.p, st0);
-      HIPCHK(hipMemcpyAsync(M2all.data(), M2d.p, pp * sizeof(double), hipMemcpyDeviceToHost, st0));
-    }
-    HIPCHK(hipStreamSynchronize(st0));
-    const std::vector<int> toff = ls->term_offsets(l0, l1);
-    G.gs2.assign(1, 0.0);
-    G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
-    G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
-    G.trec.assign((size_t)m * LMM_SUM_MAX_TERMS * term_grad_stride(d), 0.0);
-    for (int k = 0; k < ms; ++k) {
-      const int l = l0 + k;
-      const double w = ST[l];
-      double* r = &hred[(size_t)NGR * toff[k]];
-      const double gk = gksum[k];                          // sum_{i,t} g_it k_it = 2 tr(PhiBar Phi) + beta'b
-      const double trK = -0.5 * r[1];                      // tr KuuBar
-      const double dw = -(0.5 * gk + 0.5 * out.ctc[k] - 0.5 * out.s[k] - 0.5 * out.kappa[k]) / w - (double)n / (2.0 * w);
-      // [7] of a term: + the diagonal of K_uu and the kappa term, both linear in V_c
-      for (int c = 0; c < lts[l].nt(); ++c) r[NGR * c + 7] += lts[l].terms[c].ev.var * (trK - 0.5 * (double)n / w);
-      double dv0 = 0.0;
-      G.ggps[l].lengthscale = grad_finish(lts[l], d, r, &hard[(size_t)d * toff[k]], 0.0, 0.0,
-                                          &G.trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)], &dv0);
-      G.ggps[l].variance = dv0;
-      G.ggps[l].mean = -sa[k];
-      G.gs2[0] += dw / S[l];
-      G.gS[l] += -dw * sigma2 / (S[l] * S[l]) - 0.5 * aTy[k] / S[l];
-      for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] += YA[o + (size_t)k * p] / std::sqrt(S[l]);
-    }
-    double total = 0.0;
-    std::vector<double> PtP;
-    const NoiseBlocks NB1 = one_noise_block(n, sigma2);
-    if (with_regulariser) oilmm_regulariser_grad(U, S, p, m, NB1, M2all, total, G, PtP);
-    G.value = *reg;                                        // the sum of lmm_oilmm_elbo, in its order
-    for (int k = 0; k < ms; ++k) G.value += out.elbo[k];
-    if (grad->gy_dev) {
-      // d/dY[o, i] = sum_l T[l, o] (d elbo_l / d r)[i] - (P'P Y)[o, i] / sigma2
-      std::vector<double> Tt((size_t)p * std::max(ms, 1), 0.0);
-      for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) Tt[o + (size_t)k * p] = F.T[(l0 + k) + (size_t)o * m];
-      Uploaded Ttd(Tt, st0);
-      Buf<double> ga((size_t)n * p);
-      launch_mix(gr.p, n, ms, Ttd.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, with_regulariser ? ga.p : grad->gy_dev, st0);
-      if (with_regulariser) {
-        Uploaded Qd(PtP, st0);
-        Buf<double> gq((size_t)n * p);
-        launch_tall_skinny(yd.p, n, n, p, Qd.buf.p, p, p, gq.p, n, nullptr, nullptr, 0, nullptr, 0, st0);
-        launch_vec_lin_blocks(ga.p, gq.p, NB1, -1.0, n, (size_t)n * p, grad->gy_dev, st0);
-      }
-      HIPCHK(hipStreamSynchronize(st0));
-    }
+  T.reg = T.with_regulariser ? oilmm_regulariser(T.n, T.p, T.m, T.S, T.sigma2, T.resid) : 0.0;
+  return LMM_OK;
+}
+
+// The gradient of the bound from the value's factors (`out`, kept with keep_grad): the second pass over the points, the latents' own
+// gradients (grad_finish with the K_uu diagonal and the kappa term in [7]), then the complete-data back end with d elbo_l / d r in the
+// place of -alpha and d elbo_l / d w in the place of d lml / d noise.  gy_dev (n x p), gz_dev (d x nz): device outputs or nullptr.
+static int sparse_oilmm_grad(const SparseTrain& T, const SparseState& out, OilmmGrad& G, double* gy_dev, double* gz_dev) {
+  hipStream_t st0 = g.streams[0];
+  const int d = T.d, n = T.n, l0 = T.l0, l1 = T.l1, ms = T.ms, mk = T.mk, NGR = LMM_NGRAD;
+  const Latent* lts = T.lts;
+  std::vector<double> hred, hard, gksum;
+  Buf<double> gr((size_t)n * mk);
+  if (int rc = sparse_grad_core(T.xd.p, d, n, T.z.p, T.nz, T.ls.get(), l0, l1, T.Ty, T.means.data(), T.F.ST.data(), out, hred, hard, gksum, gr.p,
+                                gz_dev)) return rc;
+  std::vector<double> dw(mk, 0.0);
+  OilmmGradIn in{T.yd.p, n, T.p, T.U, T.S, T.m, one_noise_block(n, T.sigma2), l0, l1, T.with_regulariser};
+  in.a = gr.p; in.lda = n; in.sgn = -1.0; in.dot = T.Ty; in.want_sum = true;      // sum_t d elbo_l / d r_t: minus the mean's gradient
+  OilmmGradBackEnd B(in);
+  HIPCHK(hipStreamSynchronize(st0));
+  const std::vector<int> toff = T.ls->term_offsets(l0, l1);
+  G.size(T.m, T.p, 1, d);
+  for (int k = 0; k < ms; ++k) {
+    const int l = l0 + k;
+    const double w = T.F.ST[l];
+    double* r = &hred[(size_t)NGR * toff[k]];
+    const double gk = gksum[k];                          // sum_{i,t} g_it k_it = 2 tr(PhiBar Phi) + beta'b
+    const double trK = -0.5 * r[1];                      // tr KuuBar
+    dw[k] = -(0.5 * gk + 0.5 * out.ctc[k] - 0.5 * out.s[k] - 0.5 * out.kappa[k]) / w - (double)n / (2.0 * w);
+    // [7] of a term: + the diagonal of K_uu and the kappa term, both linear in V_c
+    for (int c = 0; c < lts[l].nt(); ++c) r[NGR * c + 7] += lts[l].terms[c].ev.var * (trK - 0.5 * (double)n / w);
+    double dv0 = 0.0;
+    G.ggps[l].lengthscale = grad_finish(lts[l], d, r, &hard[(size_t)d * toff[k]], 0.0, 0.0,
+                                        &G.trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(d)], &dv0);
+    G.ggps[l].variance = dv0;
+    G.ggps[l].mean = -B.asum[k];
   }
-  if (ls_out) *ls_out = ls;
-  if (z_keep) *z_keep = std::move(zown);
+  G.value = T.reg;                                       // the sum of lmm_oilmm_elbo, in its order
+  for (int k = 0; k < ms; ++k) G.value += out.elbo[k];
+  double reg_value = 0.0;                                // (the regulariser's value is T.reg)
+  B.finish(dw.data(), nullptr, T.F.T, reg_value, G, gy_dev);
   return LMM_OK;
 }
 
@@ -4843,12 +4879,13 @@ int lmm_oilmm_elbo(const double* x, int d, int n, const double* y, int p, const 
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!elbo && !dtc) return fail(LMM_ERR_ARG, "bad arguments");
+  SparseTrain T;
+  if (int rc = sparse_resolve(!elbo && !dtc, x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, with_regulariser, T))
+    return rc;
+  sparse_upload(x, y, z, T);
   SparseState st;
-  double reg = 0.0;
-  if (int rc = sparse_oilmm(x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, with_regulariser, st, &reg,
-                            nullptr, nullptr)) return rc;
-  double e = reg, t = reg;
+  if (int rc = sparse_value(T, st)) return rc;
+  double e = T.reg, t = T.reg;
   for (size_t k = 0; k < st.elbo.size(); ++k) { e += st.elbo[k]; t += st.dtc[k]; }
   if (elbo) *elbo = e;
   if (dtc) *dtc = t;
@@ -4866,21 +4903,22 @@ int lmm_oilmm_elbo_grad(const double* x, int d, int n, const double* y, int p, c
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
+  // its own arguments and the shape are reported ahead of the front end's m > p and shard (the pinned order), the ARD width after it
   if (!x || !y || !U || !S || !z || d <= 0 || n <= 0 || p <= 0 || m <= 0 || nz <= 0) return fail(LMM_ERR_ARG, "bad arguments");
   if (int rc = sparse_shape_check(d, nz, jitter)) return rc;
   hipStream_t st0 = g.streams[0];
   DevOut gy(grad_y, (size_t)n * p), gz(grad_z, (size_t)d * nz);
+  SparseTrain T;
+  if (int rc = sparse_resolve(false, x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, with_regulariser, T)) return rc;
+  if (int rc = T.ls->ard_grad_check()) return rc;
+  sparse_upload(x, y, z, T);
   SparseState st;
-  SparseGradOut GO;
-  GO.gy_dev = gy.p; GO.gz_dev = gz.p;
-  double reg = 0.0;
-  std::shared_ptr<LatentSet> ls;
-  if (int rc = sparse_oilmm(x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, with_regulariser, st, &reg,
-                            &ls, nullptr, &GO)) return rc;
-  double value = 0.0;
-  write_oilmm_grad(GO.G, m, p, &value, grad_sigma2, grad_S, grad_U, grad_gps);
-  if (out_elbo) *out_elbo = value;
-  publish_grads(*ls, grad_gps ? &GO.G.trec : nullptr, latent_begin, latent_end);
+  st.keep_grad = true;
+  if (int rc = sparse_value(T, st)) return rc;
+  OilmmGrad G;
+  if (int rc = sparse_oilmm_grad(T, st, G, gy.p, gz.p)) return rc;
+  write_oilmm_grad(G, out_elbo, grad_sigma2, grad_S, grad_U, grad_gps);
+  publish_grads(*T.ls, grad_gps ? &G.trec : nullptr, latent_begin, latent_end);
   if (grad_y) gy.finish(st0);
   if (grad_z) gz.finish(st0);
   if (grad_y || grad_z) HIPCHK(hipStreamSynchronize(st0));
@@ -4895,14 +4933,15 @@ int lmm_oilmm_sparse_posterior_create(const double* x, int d, int n, const doubl
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
-  if (!out) return fail(LMM_ERR_ARG, "bad arguments");
+  SparseTrain T;
+  if (int rc = sparse_resolve(!out, x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, 0, T)) return rc;
+  sparse_upload(x, y, z, T);
   SparseState st;
-  double reg = 0.0;
+  if (int rc = sparse_value(T, st)) return rc;
   auto P = std::make_unique<lmm_sparse_post>();
-  if (int rc = sparse_oilmm(x, d, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, z, nz, jitter, 0, st, &reg, &P->ls, &P->z))
-    return rc;
   Dims D(nz, 1);
   P->d = d; P->nz = nz; P->l0 = latent_begin; P->l1 = latent_end; P->m = m; P->NC = D.NC; P->NR = D.NR; P->ld = D.ld;
+  P->ls = T.ls; P->z = std::move(T.z);
   P->Lu = std::move(st.Lu); P->Wu = std::move(st.Wu); P->LB = std::move(st.LB); P->WB = std::move(st.WB); P->c = std::move(st.c);
   *out = P.release();
   return LMM_OK;
@@ -4976,8 +5015,7 @@ int lmm_dev_sparse_moments(const double* x, int d, int n, const double* z, int n
   REQUIRE_INIT();
   LMM_TRY
   if (!x || !z || !gp || !w || !r || !Phi || !b || !scalars || d <= 0 || n <= 0 || nz <= 0 || ld < nz) return fail(LMM_ERR_ARG, "bad arguments");
-  if (nz > LMM_SPARSE_MMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for at most %d inducing points (nz = %d)", LMM_SPARSE_MMAX, nz);
-  if (d > LMM_SPARSE_DMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for d <= %d (d = %d)", LMM_SPARSE_DMAX, d);
+  if (int rc = sparse_size_check(d, nz)) return rc;
   RESOLVE(gp, 1, d);
   if (int rc = refuse_sho(*ls, "inducing-point inference is")) return rc;
   int nch = 0;
@@ -4985,12 +5023,10 @@ int lmm_dev_sparse_moments(const double* x, int d, int n, const double* z, int n
   hipStream_t st0 = g.streams[0];
   Buf<double> scratch((size_t)nch * sparse_partial_stride(nz));
   SparseMomArgs a{};
-  a.x = x; a.z = z; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.scratch = scratch.p;
   sparse_fill_lat(a.lat[0], lts[0], w, 0.0, r, 0.0);
   BatchPtr Pb{}, bb{}, sb{};
   Pb.p[0] = Phi; bb.p[0] = b; sb.p[0] = scalars;
-  launch_sparse_moments(a, 1, sum_mode(lts, 0, 1), st0);
-  launch_sparse_finish(scratch.p, nch, nz, Pb, ld, false, bb, sb, 1, st0);
+  sparse_moments_pass(a, SparsePoints{x, d, n, z, nz, chunk, nch}, scratch.p, 1, sum_mode(lts, 0, 1), Pb, ld, false, bb, sb, st0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
@@ -5009,8 +5045,7 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
   LMM_TRY
   if (!x || !z || !gp || !w || !r || !PhiBar || !beta || !term_records || d <= 0 || n <= 0 || nz <= 0 || ld < nz)
     return fail(LMM_ERR_ARG, "bad arguments");
-  if (nz > LMM_SPARSE_MMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for at most %d inducing points (nz = %d)", LMM_SPARSE_MMAX, nz);
-  if (d > LMM_SPARSE_DMAX) return fail(LMM_ERR_UNSUPPORTED, "inducing-point inference is served for d <= %d (d = %d)", LMM_SPARSE_DMAX, d);
+  if (int rc = sparse_size_check(d, nz)) return rc;
   RESOLVE(gp, 1, d);
   if (int rc = refuse_sho(*ls, "inducing-point inference is")) return rc;
   int nch = 0;
@@ -5025,13 +5060,9 @@ int lmm_dev_sparse_grad(const double* x, int d, int n, const double* z, int nz, 
   SparseGradLat hl{};
   sparse_grad_fill_lat(hl, lts[0], gdd.p, w, 0.0, r, 0.0, PhiBar, beta, grad_r);
   Buf<SparseGradLat> dl(1);
-  HIPCHK(hipMemcpyAsync(dl.p, &hl, sizeof(SparseGradLat), hipMemcpyHostToDevice, st0));
-  SparseGradArgs a{};
-  a.x = x; a.z = z; a.d = d; a.n = n; a.nz = nz; a.chunk = chunk; a.nch = nch; a.ld = ld; a.scratch = scratch.p; a.lat = dl.p;
   BatchPtr rb{}, zb{};
   rb.p[0] = term_records; zb.p[0] = grad_z;
-  launch_sparse_grad(a, 1, sum_mode(lts, 0, 1), st0);
-  launch_sparse_grad_finish(scratch.p, nch, nz, d, rb, zb, 1, st0);
+  sparse_grad_pass(&hl, dl.p, SparsePoints{x, d, n, z, nz, chunk, nch}, ld, scratch.p, 1, sum_mode(lts, 0, 1), rb, zb, st0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
@@ -5449,29 +5480,27 @@ static int ss_logpdf_grad(const double* x, int n, const double* y, int p, const 
   for (int k = 0; k < ms; ++k) total += lml[k];
   if (with_regulariser) total += Fr.reg;
   OilmmGrad G;
+  G.size(m, p, 1, 1);
   G.value = total;
-  G.gs2.assign(1, 0.0);
-  G.gS.assign(m, 0.0); G.gU.assign((size_t)p * m, 0.0);
-  G.ggps.assign(m, lmm_gp_grad_t{0.0, 0.0, 0.0});
   for (int k = 0; k < ms; ++k) G.ggps[l0 + k].mean = sums[4 * (size_t)k];      // sum_t alpha_t
   if (Fr.has_nan) {
     const MissingFront& F = Fr.F;
     const int nobs = Fr.nobs;
     // w_t = sigma2 (G_t^-1)_ll: sum_t (d lml / d w_t) w_t / sigma2, as oilmm_grad_missing_core
     for (int k = 0; k < ms; ++k) G.gs2[0] += 0.5 * (sums[4 * (size_t)k + 1] - sums[4 * (size_t)k + 2]) / sigma2;
-    if (with_regulariser && nobs > 0) G.gs2[0] += -0.5 * ((F.sum_pt - (double)nobs * m) / sigma2 - F.rss / (sigma2 * sigma2));
-    if (grad_y) {
-      if (nobs == n) {
-        launch_missing_grad_y(n, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, al.p, n, l0, ms, with_regulariser ? F.resid.p : nullptr, sigma2,
-                              gy.p, st0);
-      } else {
-        // the front end numbered the nobs points with observations: alpha in that numbering, the rows of grad_y scattered back
-        for (int o = 0; o < p; ++o) launch_fill(gy.p + (size_t)o * n, n, 0.0, st0);
-        if (nobs > 0) {
-          Buf<double> ac((size_t)nobs * msa), gyc((size_t)nobs * p);
+    if (nobs == n) {
+      missing_grad_back_end(F, n, p, m, sigma2, with_regulariser, al.p, n, l0, ms, G, gy.p);
+    } else {
+      // the front end numbered the nobs points with observations: alpha in that numbering, the rows of grad_y scattered back
+      if (grad_y) for (int o = 0; o < p; ++o) launch_fill(gy.p + (size_t)o * n, n, 0.0, st0);
+      if (nobs > 0) {
+        Buf<double> ac, gyc;
+        if (grad_y) {
+          ac = Buf<double>((size_t)nobs * msa); gyc = Buf<double>((size_t)nobs * p);
           if (ms > 0) launch_ss_gather_rows(al.p, n, ms, Fr.idxd.p, nobs, ac.p, st0);
-          launch_missing_grad_y(nobs, p, m, F.pat_of.p, F.pmask.p, F.Tpat.p, ac.p, nobs, l0, ms, with_regulariser ? F.resid.p : nullptr,
-                                sigma2, gyc.p, st0);
+        }
+        missing_grad_back_end(F, nobs, p, m, sigma2, with_regulariser, ac.p, nobs, l0, ms, G, gyc.p);
+        if (grad_y) {
           launch_ss_scatter_rows(gyc.p, n, p, Fr.idxd.p, nobs, gy.p, st0);
           HIPCHK(hipGetLastError());
           HIPCHK(hipStreamSynchronize(st0));      // ac and gyc go back to the pool
@@ -5479,56 +5508,24 @@ static int ss_logpdf_grad(const double* x, int n, const double* y, int p, const 
       }
     }
   } else {
-    // complete data: r = (T y)_l - mean_l with T = S^-1/2 U' and w = sigma2 / S_l; the host chain rule of lmm_oilmm_elbo_grad
-    std::vector<double> T, ST, H;
+    // complete data: r = (T y)_l - mean_l with T = S^-1/2 U' and w = sigma2 / S_l.  alpha = -d lml / d r is dotted with r, so the back
+    // end adds mean_l * sum_t alpha_t; the regulariser's value is in G.value already (Fr.reg)
+    std::vector<double> T, ST, H, dw(msa, 0.0), mean_sum(msa, 0.0);
     project_orthogonal(U, S, p, m, sigma2, T, ST, H);
-    const size_t pp = (size_t)p * p;
-    Buf<double> YAd((size_t)p * msa), aTyd(msa), M2d(pp);
-    std::vector<double> YA((size_t)p * msa, 0.0), aTy(msa, 0.0), M2all(pp, 0.0);
-    if (ms > 0) {
-      launch_atb(yd.p, n, al.p, n, n, p, ms, YAd.p, st0);                   // Y' alpha_l, p x ms
-      for (int k = 0; k < ms; ++k) launch_atb(al.p + (size_t)k * n, n, Fr.r.p + (size_t)k * n, n, n, 1, 1, aTyd.p + k, st0);
-      HIPCHK(hipMemcpyAsync(YA.data(), YAd.p, YA.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
-      HIPCHK(hipMemcpyAsync(aTy.data(), aTyd.p, (size_t)ms * sizeof(double), hipMemcpyDeviceToHost, st0));
-    }
-    if (with_regulariser) {
-      launch_atb(yd.p, n, yd.p, n, n, p, p, M2d.p, st0);
-      HIPCHK(hipMemcpyAsync(M2all.data(), M2d.p, pp * sizeof(double), hipMemcpyDeviceToHost, st0));
-    }
+    OilmmGradIn in{yd.p, n, p, U, S, m, one_noise_block(n, sigma2), l0, l1, with_regulariser};
+    in.a = al.p; in.lda = n; in.dot = Fr.r.p;
+    OilmmGradBackEnd B(in);
     HIPCHK(hipStreamSynchronize(st0));
     for (int k = 0; k < ms; ++k) {
-      const int l = l0 + k;
-      const double dw = sums[4 * (size_t)k + 3];                            // sum_t d lml / d w_t
-      const double aTyl = aTy[k] + lts[l].mean * sums[4 * (size_t)k];       // alpha' (T y)_l: r has the mean taken off
-      G.gs2[0] += dw / S[l];
-      G.gS[l] += -dw * sigma2 / (S[l] * S[l]) + 0.5 * aTyl / S[l];          // d lml / d r = -alpha
-      for (int o = 0; o < p; ++o) G.gU[o + (size_t)l * p] -= YA[o + (size_t)k * p] / std::sqrt(S[l]);
+      dw[k] = sums[4 * (size_t)k + 3];                                      // sum_t d lml / d w_t
+      mean_sum[k] = lts[l0 + k].mean * sums[4 * (size_t)k];
     }
-    double reg_value = 0.0;                  // the regulariser's value is in G.value already (Fr.reg)
-    std::vector<double> PtP;
-    const NoiseBlocks NB1 = one_noise_block(n, sigma2);
-    if (with_regulariser) oilmm_regulariser_grad(U, S, p, m, NB1, M2all, reg_value, G, PtP);
-    if (grad_y) {
-      // d/dY[o, i] = -sum_l T[l, o] alpha_l[i] - (P'P Y)[o, i] / sigma2
-      std::vector<double> Tt((size_t)p * msa, 0.0);
-      for (int k = 0; k < ms; ++k) for (int o = 0; o < p; ++o) Tt[o + (size_t)k * p] = -T[(l0 + k) + (size_t)o * m];
-      Uploaded Ttd(Tt, st0);
-      Buf<double> ga((size_t)n * p);
-      launch_mix(al.p, n, ms, Ttd.buf.p, p, 1, 0.0, 0.0, nullptr, 0.0, with_regulariser ? ga.p : gy.p, st0);
-      if (with_regulariser) {
-        Uploaded Qd(PtP, st0);
-        Buf<double> gq((size_t)n * p);
-        launch_tall_skinny(yd.p, n, n, p, Qd.buf.p, p, p, gq.p, n, nullptr, nullptr, 0, nullptr, 0, st0);
-        launch_vec_lin_blocks(ga.p, gq.p, NB1, -1.0, n, (size_t)n * p, gy.p, st0);
-      }
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(st0));
-    }
+    double reg_value = 0.0;
+    B.finish(dw.data(), mean_sum.data(), T, reg_value, G, gy.p);
+    if (grad_y) HIPCHK(hipGetLastError());
   }
-  double value = 0.0;
   ss_publish_grads(*ls, l0, l1, grad_gps ? gth.data() : nullptr, G.ggps.data());
-  write_oilmm_grad(G, m, p, &value, grad_sigma2, grad_S, grad_U, grad_gps);
-  if (out_logpdf) *out_logpdf = value;
+  write_oilmm_grad(G, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
   if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
   return LMM_OK;
   LMM_CATCH

@@ -7,6 +7,8 @@ call here returns before any launch.  The dense-H training entry points (lmm_ilm
 from the build before their shared front end (profiles/dense_h_refactor/entry_checks_parent.txt).
 
 Shapes: n = 8, p = 3, m = 2, d = 1; one per-latent posterior handle at n = 64 and one dense-H handle (the "other kind") at n = 8.
+The inducing-point entry points (the bound's gradient, the sparse posterior handle and its mean_and_var at nz = 4, the two one-latent
+building blocks) have rows recorded from the build before their shared front end (profiles/oilmm_grad_backend/entry_checks_parent.txt).
 The argument lists are built from the declarations in include/lmm_hip.h; a row names the arguments it spoils."""
 import ctypes as C
 import functools
@@ -36,6 +38,9 @@ SNAN = {"S": "S_nan"}
 NOGPS = {"gps": None}
 OTHER, PRIOR = {"post": "dense"}, {"post": None}
 M3, D2 = {"m": 3}, {"d": 2}
+NZBIG, J0 = {"nz": 1025}, {"jitter": 0.0}          # one inducing point more than LMM_SPARSE_MMAX
+NZMSG, JITTER = "inducing-point inference is served for at most 1024 inducing points (nz = 1025)", "jitter must be finite and > 0"
+SPARSE, NOTSPARSE = {"post": "sparse"}, "not a handle of lmm_oilmm_sparse_posterior_create"
 F32 = {"f32": 1}                    # the call is made in the other compute dtype than the handles were built in
 
 
@@ -71,6 +76,28 @@ TABLE = {
     "lmm_oilmm_elbo": TRAIN + [("NULL z", {"z": None}, ARG, BAD), ("sigma2 = 0", S0, ARG, SIGMA2), ("shard and jitter = 0", both(SH, {"jitter": 0.0}), ARG, SHARD),
                                ("jitter = 0 and sigma2 = 0", both({"jitter": 0.0}, S0), ARG, "jitter must be finite and > 0"),
                                ("sigma2 = 0 and no gps", both(S0, NOGPS), ARG, SIGMA2)],
+    # its gradient tests its own arguments and the shape (nz, d, dtype, jitter) ahead of the shared front end: those come before m > p and the shard
+    "lmm_oilmm_elbo_grad": TRAIN + [("NULL z", {"z": None}, ARG, BAD), ("nz above the limit", NZBIG, UNSUP, NZMSG), ("jitter = 0", J0, ARG, JITTER), ("sigma2 = 0", S0, ARG, SIGMA2),
+                                    ("NULL z and nz above the limit", both({"z": None}, NZBIG), ARG, BAD), ("nz above the limit and jitter = 0", both(NZBIG, J0), UNSUP, NZMSG),
+                                    ("jitter = 0 and m > p", both(J0, MP), ARG, JITTER), ("jitter = 0 and shard", both(J0, SH), ARG, JITTER),
+                                    ("nz above the limit and shard", both(NZBIG, SH), UNSUP, NZMSG), ("m > p and shard", both(MP, {"latent_end": 5}), DIM, OUTDIM),
+                                    ("shard and sigma2 = 0", both(SH, S0), ARG, SHARD), ("jitter = 0 and sigma2 = 0", both(J0, S0), ARG, JITTER),
+                                    ("sigma2 = 0 and no gps", both(S0, NOGPS), ARG, SIGMA2), ("no gps", NOGPS, ARG, GPS)],
+    # the handle: its own output, then the bound's order
+    "lmm_oilmm_sparse_posterior_create": TRAIN + [("NULL out", {"out": None}, ARG, BAD), ("NULL z", {"z": None}, ARG, BAD), ("nz above the limit", NZBIG, UNSUP, NZMSG),
+                                                  ("jitter = 0", J0, ARG, JITTER), ("sigma2 = 0", S0, ARG, SIGMA2), ("m > p and nz above the limit", both(MP, NZBIG), DIM, OUTDIM),
+                                                  ("shard and jitter = 0", both(SH, J0), ARG, SHARD), ("jitter = 0 and sigma2 = 0", both(J0, S0), ARG, JITTER),
+                                                  ("sigma2 = 0 and no gps", both(S0, NOGPS), ARG, SIGMA2), ("no gps", NOGPS, ARG, GPS)],
+    # args, dtype, handle kind, m, d (every row names its handle: the table's `post` is a per-latent one, another kind here)
+    "lmm_oilmm_sparse_mean_and_var": [("NULL U", both(SPARSE, NULLU), ARG, BAD), ("no handle", PRIOR, ARG, BAD), ("other kind", {}, ARG, NOTSPARSE), ("other kind (dense-H)", OTHER, ARG, NOTSPARSE),
+                                      ("other m", both(SPARSE, M3), DIM, HM), ("other d", both(SPARSE, D2), DIM, HDXS), ("other dtype", both(SPARSE, F32), UNSUP, "inducing-point inference is Float64 only"),
+                                      ("NULL U and other kind", NULLU, ARG, BAD), ("other dtype and other kind", F32, UNSUP, "inducing-point inference is Float64 only"),
+                                      ("other kind and other m", M3, ARG, NOTSPARSE), ("other m and other d", both(SPARSE, M3, D2), DIM, HM)],
+    # the one-latent building blocks: args (ld < nz among them), then the sizes; no dtype and no jitter check
+    **{name: [("NULL x", NULLX, ARG, BAD), ("ld < nz", {"ld": NZ - 1}, ARG, BAD), ("nz above the limit", both(NZBIG, {"ld": 1025}), UNSUP, NZMSG),
+              ("d above the limit", {"d": 33}, UNSUP, "inducing-point inference is served for d <= 32 (d = 33)"),
+              ("ld < nz and nz above the limit", NZBIG, ARG, BAD), ("nz and d above the limit", both(NZBIG, {"ld": 1025, "d": 33}), UNSUP, NZMSG)]
+       for name in ("lmm_dev_sparse_moments", "lmm_dev_sparse_grad")},
     # IndependentMOGP: args, shard, resolve
     **{name: [("NULL x", NULLX, ARG, BAD), ("shard", SH, ARG, SHARD), ("NULL x and shard", both(NULLX, SH), ARG, BAD), ("shard and no gps", both(SH, NOGPS), ARG, SHARD)]
        for name in ("lmm_mogp_logpdf", "lmm_mogp_logpdf_diag", "lmm_mogp_posterior_create")},
@@ -151,8 +178,12 @@ def env():
     L.check(lib.lmm_oilmm_posterior_create(ptr["x"], C.c_int(D), C.c_int(64), ptr["y"], C.c_int(P), ptr["U"], ptr["S"], C.c_int(M), C.c_double(0.1), ptr["gps"],
                                            C.c_int(0), C.c_int(M), C.byref(post)))
     L.check(lib.lmm_ilmm_posterior_create(ptr["x"], C.c_int(D), C.c_int(N), ptr["y"], C.c_int(P), ptr["U"], C.c_int(M), C.c_double(0.1), ptr["gps"], None, C.byref(dense)))
-    ptr["post"], ptr["dense"] = post, dense
+    sparse = C.c_void_p()
+    L.check(lib.lmm_oilmm_sparse_posterior_create(ptr["x"], C.c_int(D), C.c_int(64), ptr["y"], C.c_int(P), ptr["U"], ptr["S"], C.c_int(M), C.c_double(0.1), ptr["gps"],
+                                                  C.c_int(0), C.c_int(M), ptr["z"], C.c_int(NZ), C.c_double(1e-6), C.byref(sparse)))
+    ptr["post"], ptr["dense"], ptr["sparse"] = post, dense, sparse
     yield lib, ptr, (keep, gps)
+    lib.lmm_sparse_post_destroy(sparse)
     lib.lmm_set_compute_dtype(C.c_int(0))
     lib.lmm_post_destroy(post)
     lib.lmm_post_destroy(dense)
@@ -160,7 +191,8 @@ def env():
 
 # what a sound call passes, by argument name; any other pointer is an output (or an optional input) and gets the scratch block
 VALUES = {"d": D, "n": N, "p": P, "m": M, "ncol": 2, "ns": NS, "nz": NZ, "n2": NS, "nbatch": 1, "nsamples": 1, "m_shard": M, "latent_begin": 0, "latent_end": M,
-          "with_regulariser": 1, "add_noise": 0, "allow_decoupled": 1, "x_by_features": 0, "y_by_features": 0, "sigma2": 0.1, "sigma2_s": 0.1, "jitter": 1e-6}
+          "with_regulariser": 1, "add_noise": 0, "allow_decoupled": 1, "x_by_features": 0, "y_by_features": 0, "sigma2": 0.1, "sigma2_s": 0.1, "jitter": 1e-6,
+          "ld": NZ, "chunk": 0}
 INPUTS = {"x": "x", "y": "y", "Y": "y", "U": "U", "H": "U", "S": "S", "gps": "gps", "xs": "xs", "ys": "y", "z": "z", "batch_n": "batch_n", "batch_sigma2": "batch_sigma2",
           "noise_diag": "noise_diag", "post": "post", "x2": "xs", "y2": "y", "z_lat": "y", "dmean": "y", "dvar": "y"}
 NULLS = {"jit", "eps", "grad_y", "grad_ys", "grad_sigma2", "grad_S", "grad_U", "grad_gps", "grad_x", "grad_batch_sigma2", "grad_sigma2_s", "dtc"}

@@ -12,8 +12,9 @@ and is no evidence either way.  Exit status 0 when no comparable array differs.
 The inputs reach every branch of the launch dispatchers and every entry-point preamble: n = 200 (two 128-column panels), ns = 70, p = 9,
 m = 7 latents (SE, Matern-5/2, RQ, periodic, locally periodic, SHO -- Matern-1/2 in its place for d > 1 and where SHO is not served -- and
 a sum with a periodic term), shards [0, 7) and [2, 5), d = 1, 3 (isotropic and ARD), 6 and 12 (ARD), y complete and with single outputs
-NaN, Float64 and (logpdf and posterior paths) the Float32 compute dtype, lmm_oilmm_logpdf_multi with ncol = 3, the inducing-point bound and
-its gradient at nz = 70, the IndependentMOGP entry points, and the building blocks lmm_dev_gram / lmm_dev_sparse_moments / _grad per kind.
+NaN, Float64 and (logpdf and posterior paths) the Float32 compute dtype, lmm_oilmm_logpdf_multi with ncol = 3, the inducing-point bound, its
+gradient (with and without the regulariser; on the shard [2, 5) through the entry point, as the model refuses a sharded bound) and its
+posterior's mean_and_var at nz = 70, the IndependentMOGP entry points, and the building blocks lmm_dev_gram / lmm_dev_sparse_moments / _grad per kind.
 
 The dense-H ILMM (one (mn) x (mn) factorisation, n m = 1400: eleven 128-column panels) runs on the same inputs and the same (d, ARD, SHO)
 loop with a dense 9 x 7 mixing matrix, in both compute dtypes: the prior logpdf with ILMM_ALLOW_DECOUPLED off and on (mixed kernels, seven
@@ -83,6 +84,16 @@ def child(out_path):
         ls = leaves(v)
         out[name] = np.concatenate(ls + [np.array([float(len(ls))])])
 
+    def elbo_grad_entry(vfe, fx, y, shard):      # lmm_oilmm_elbo_grad on a shard, every output
+        xi, (Ua, Sa, p, m) = fx.x, Mo._H_args(fx.f.H)
+        val, gs2 = C.c_double(), C.c_double()
+        gy, gS, gU, gz = np.empty(xi.n * p), np.empty(m), np.empty(p * m), np.empty(xi.dim * vfe.nz)
+        gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in fx.f.f.fs])
+        L.check(L.load().lmm_oilmm_elbo_grad(xi.carr().ptr, xi.dim, xi.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), ga, shard[0], shard[1],
+                                             vfe.carr().ptr, vfe.nz, vfe.jitter, 1, C.byref(val), L.Arr(gy, True).ptr, C.byref(gs2), L.Arr(gS, True).ptr,
+                                             L.Arr(gU, True).ptr, gg, L.Arr(gz, True).ptr))
+        return [val.value, gy, gs2.value, gS, gU, [[g.variance, g.lengthscale, g.mean] for g in gg], gz]
+
     rng = np.random.default_rng(7)
     U = np.linalg.qr(rng.standard_normal((P, M)))[0]
     S = rng.uniform(0.5, 2.0, M)
@@ -138,6 +149,10 @@ def child(out_path):
                     rec(f"{tag} elbo", lambda: lmm.elbo(vfe, fx, y))
                     rec(f"{tag} dtc no regulariser", lambda: lmm.dtc(vfe, fx, y, with_regulariser=False))
                     rec(f"{tag} elbo grad", lambda: lmm.elbo_and_gradient(vfe, fx, y))
+                    rec(f"{tag} elbo grad no regulariser", lambda: lmm.elbo_and_gradient(vfe, fx, y, with_regulariser=False))
+                    rec(f"{tag} approx post mean_and_var", lambda: lmm.mean_and_var(lmm.approx_posterior(vfe, fx, y)(fxs.x, 0.1)))
+            elif not sho:      # the model refuses a sharded bound: the entry point itself
+                rec(f"{tag} elbo grad", lambda: elbo_grad_entry(lmm.VFE(z, 1e-6), fx, y, shard))
         # the dense-H ILMM: one (mn) x (mn) factorisation, n m = 1400 (eleven 128-column panels); the joint of a predictive gradient is 1890
         tag = f"d={d}{' ard' if ard else ''}{' sho' if sho else ''} dense-H"
         g = lmm.ILMM(fs, Hd)
