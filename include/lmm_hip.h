@@ -824,6 +824,34 @@ int lmm_oilmm_logpdf_grad_statespace_x(const double* x, int n, const double* y, 
                                        lmm_gp_grad_t* grad_gps, double* grad_x);
 int lmm_dev_statespace_grad_x(const double* x, int n, const lmm_gp_t* gp, const double* w, const double* r, int chunk,
                               double* grad_x);
+/* Toeplitz: stationary latents over an evenly spaced one-dimensional input, complete data.  Every base kind and
+ * sums of them are served, exactly, in O(n^2) time and O(n) memory per latent: on such a grid K_l + (sigma2 / S_l) I is symmetric
+ * Toeplitz and the Schur recursion factors it inside one workgroup.  Float64, no atomics, bitwise reproducible.
+ *   lmm_toeplitz_max_n : the largest n the path serves (8192).
+ *   lmm_oilmm_logpdf_toeplitz : the value of lmm_oilmm_logpdf for d = 1 (part of the signature).  x: n values, host or device,
+ *                    ascending and evenly spaced: with h = (x[n-1] - x[0]) / (n - 1), every |x[t] - (x[0] + t h)| <= 8 eps
+ *                    max(|x[0]|, |x[n-1]|); otherwise LMM_ERR_ARG with the first offending index in lmm_last_error_detail's `info`.
+ *                    n = 1 is served.  The kernels are evaluated at the actual x[t] - x[0].  Refused before any launch of the path's
+ *                    kernels: the fp32 compute mode, n > lmm_toeplitz_max_n(), a latent whose tag carries per-dimension factors
+ *                    (LMM_ERR_UNSUPPORTED, the latter naming the latent), a NaN in y (LMM_ERR_UNSUPPORTED with the first such point in
+ *                    `info`: per-point noise is not Toeplitz).  A matrix that is not positive definite is LMM_ERR_NOT_PD with the latent
+ *                    and 1 + the step of the recursion in the error detail.  Partial sums over the shard.
+ *   lmm_oilmm_logpdf_grad_toeplitz : value and gradient, the outputs of lmm_oilmm_logpdf_grad_statespace with its semantics for
+ *                    grad_gps, tags and sum terms (those of lmm_oilmm_logpdf_grad); *out_logpdf is bitwise the value call.  Any
+ *                    output may be NULL.
+ *   lmm_dev_toeplitz_factor, lmm_dev_toeplitz_solve : building blocks for tests, DEVICE pointers, one matrix: the recursion on the
+ *                    first column t and right-hand side r (n values each) gives log det, r' K^-1 r (host; may be NULL) and the
+ *                    Gohberg-Semencul generators p, q (n values each) with K^-1 = L(q) L(q)' - L(p) L(p)'; the solve gives
+ *                    alpha = K^-1 r from them.  Not positive definite: LMM_ERR_NOT_PD naming latent 0 and the step. */
+int lmm_toeplitz_max_n(void);
+int lmm_oilmm_logpdf_toeplitz(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                              const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out);
+int lmm_oilmm_logpdf_grad_toeplitz(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                   double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                   double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                                   lmm_gp_grad_t* grad_gps);
+int lmm_dev_toeplitz_factor(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q);
+int lmm_dev_toeplitz_solve(const double* p, const double* q, const double* r, int n, double* alpha);
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
                               const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,

@@ -44,6 +44,7 @@ SYMBOLS = [
     "lmm_oilmm_statespace_post_append", "lmm_statespace_post_smooth", "lmm_statespace_post_reserve", "lmm_statespace_post_size",
     "lmm_dev_statespace_filter_from",
     "lmm_oilmm_statespace_post_logpdf", "lmm_dev_statespace_post_logpdf",
+    "lmm_toeplitz_max_n", "lmm_oilmm_logpdf_toeplitz", "lmm_oilmm_logpdf_grad_toeplitz", "lmm_dev_toeplitz_factor", "lmm_dev_toeplitz_solve",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
     "lmm_dev_set_f64_emul", "lmm_dev_syrk_emul", "lmm_dev_emul_host", "lmm_dev_emul_residues", "lmm_dev_set_emul_gemm_workgroups", "lmm_dev_emul_acc_residues",
     "lmm_dev_set_f64_emul_rule", "lmm_dev_set_emul_group", "lmm_dev_set_emul_amax_reuse", "lmm_dev_emul_plan", "lmm_dev_potrf_plan",
@@ -79,6 +80,12 @@ STATESPACE_ARGTYPES = {
     "lmm_dev_statespace_grad_sho": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
     "lmm_dev_statespace_grad_sum": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
     "lmm_oilmm_logpdf_grad_statespace_x": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    # the Toeplitz path (include/lmm_hip.h, "Toeplitz"): same conventions
+    "lmm_toeplitz_max_n": [],
+    "lmm_oilmm_logpdf_toeplitz": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P],
+    "lmm_oilmm_logpdf_grad_toeplitz": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "lmm_dev_toeplitz_factor": [_P, _P, _I, _P, _P, _P, _P],
+    "lmm_dev_toeplitz_solve": [_P, _P, _P, _I, _P],
     "lmm_dev_statespace_grad_x": [_P, _I, _P, _P, _P, _I, _P],
     "lmm_oilmm_statespace_post_mean_and_var_grad_xs": [_P, _P, _I, _P, _P, _P],
     "lmm_oilmm_rand_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _I, _P, _P, _P, _P],

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "lmm_internal.h"
+#include "lmm_toeplitz.h"
 #include "lmm_emul.h"
 
 namespace {
@@ -5545,6 +5546,232 @@ int lmm_oilmm_logpdf_grad_statespace_x(const double* x, int n, const double* y, 
                                        lmm_gp_grad_t* grad_gps, double* grad_x) {
   return ss_logpdf_grad(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, out_logpdf, grad_y, grad_sigma2,
                         grad_S, grad_U, grad_gps, grad_x);
+}
+
+// ---- Toeplitz path: stationary latents over an evenly spaced one-dimensional input, complete data ----
+// Every stationary kernel gives a symmetric Toeplitz Gram matrix there, and complete data adds the same noise sigma2 / S_l at every
+// point, so K_l + w_l I is factored by the Schur recursion in O(n^2) (lmm_kernels_toeplitz.hip), one workgroup per latent.
+int lmm_toeplitz_max_n(void) { return TOEP_MAX_N; }
+
+// The device work of a call over the shard's ms latents: first columns, recursion, and what the gradient needs on top.
+struct ToepWork {
+  Buf<double> t, p, q, out2;
+  Buf<int> info;
+  std::vector<double> lml;             // per latent of the shard
+};
+// lml[k] of the shard's latents from the noise w and data r ([latent][n], device); a failed step is LMM_ERR_NOT_PD naming latent and step
+static int toep_factor(const double* xd, int n, const Latent* lts, int l0, int ms, const double* w, const double* r, ToepWork& W) {
+  hipStream_t st0 = g.streams[0];
+  const int mk = std::max(ms, 1);
+  W.t = Buf<double>((size_t)n * mk); W.p = Buf<double>((size_t)n * mk); W.q = Buf<double>((size_t)n * mk);
+  W.out2 = Buf<double>(2 * (size_t)mk); W.info = Buf<int>(mk);
+  W.lml.assign(mk, 0.0);
+  if (ms == 0) return LMM_OK;
+  std::vector<LatentDev> hd(ms);
+  for (int k = 0; k < ms; ++k) hd[k] = lts[l0 + k].dev();
+  Buf<LatentDev> dd(ms);
+  HIPCHK(hipMemcpyAsync(dd.p, hd.data(), (size_t)ms * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  launch_toep_row(xd, n, dd.p, w, ms, sum_mode(lts, l0, l0 + ms), W.t.p, st0);
+  launch_toep_schur(W.t.p, r, n, ms, W.out2.p, W.p.p, W.q.p, W.info.p, st0);
+  HIPCHK(hipGetLastError());
+  std::vector<double> h2(2 * (size_t)ms);
+  std::vector<int> hinfo(ms);
+  HIPCHK(hipMemcpyAsync(h2.data(), W.out2.p, h2.size() * sizeof(double), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipMemcpyAsync(hinfo.data(), W.info.p, (size_t)ms * sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  for (int k = 0; k < ms; ++k)
+    if (hinfo[k] != 0) {
+      g.err_latent = l0 + k; g.err_info = hinfo[k];
+      return fail(LMM_ERR_NOT_PD, "PosDefException: the Toeplitz matrix is not positive definite; the Schur recursion failed (latent %d, step %d)",
+                  g.err_latent, hinfo[k] - 1);
+    }
+  for (int k = 0; k < ms; ++k) W.lml[k] = -0.5 * (h2[2 * k + 1] + h2[2 * k] + (double)n * std::log(2.0 * M_PI));
+  return LMM_OK;
+}
+
+// The preamble of the two entry points, refusals first and all of them before any launch of the path's own kernels: arguments, the
+// fp32 mode, n beyond the cap, the latents (per-dimension lengthscales are refused), the grid rule on x, NaN in y; then the front end.
+struct ToepTrain {
+  std::shared_ptr<LatentSet> ls;
+  const Latent* lts = nullptr;
+  DevIn xd{nullptr, 0, nullptr}, yd{nullptr, 0, nullptr};
+  int l0 = 0, l1 = 0, ms = 0, mk = 1;
+  MissingFront F;                      // complete data: z = r, nv = the constant noise
+};
+static int toep_train(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                      const lmm_gp_t* gps, int l0, int l1, bool want_resid, ToepTrain& T) {
+  if (int rc = train_args(!x || !y || !U || !S || n <= 0 || p <= 0 || m <= 0, p, m, S, sigma2, l0, l1, TRAIN_SIGMA2 | TRAIN_S)) return rc;
+  if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path is Float64 only (lmm_set_compute_dtype(LMM_F64))");
+  if (n > TOEP_MAX_N) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves n <= %d points (lmm_toeplitz_max_n; n = %d)", TOEP_MAX_N, n);
+  if (int rc = resolve(gps, m, 1, T.ls)) return rc;
+  T.lts = T.ls->lat.data();
+  for (int l = 0; l < m; ++l)
+    for (const KernelTerm& K : T.lts[l].terms)
+      if (K.has_ard) {
+        g.err_latent = l; g.err_info = 0;
+        return fail(LMM_ERR_UNSUPPORTED, "latent %d: per-dimension lengthscales (an ARD tag) are not served on the Toeplitz path", l);
+      }
+  hipStream_t st0 = g.streams[0];
+  // the grid rule, on the host: a host x is checked before anything goes to the device, a device x is copied back (n <= the cap)
+  std::vector<double> hx(n);
+  const bool xdev = is_device_ptr(x);
+  if (xdev) { HIPCHK(hipMemcpyAsync(hx.data(), x, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st0)); HIPCHK(hipStreamSynchronize(st0)); }
+  else std::copy(x, x + n, hx.begin());
+  if (n > 1) {
+    const double h = (hx[n - 1] - hx[0]) / (double)(n - 1);
+    const double tol = 8.0 * 2.220446049250313e-16 * std::max(std::fabs(hx[0]), std::fabs(hx[n - 1]));
+    int off = h > 0.0 ? 0 : 1;          // not ascending (or not finite): the first step already is off
+    for (int t = 1; t < n && !off; ++t)
+      if (!(std::fabs(hx[t] - (hx[0] + (double)t * h)) <= tol)) off = t;
+    if (off) {
+      g.err_latent = -1; g.err_info = off;
+      return fail(LMM_ERR_ARG, "the Toeplitz path needs ascending, evenly spaced inputs: x[%d] is off the grid from x[0] to x[%d]", off, n - 1);
+    }
+  }
+  T.xd = DevIn(x, (size_t)n, st0);
+  T.yd = DevIn(y, (size_t)n * p, st0);
+  {
+    Buf<unsigned long long> masks((size_t)n * ((p + 63) / 64));
+    Buf<int> pt(n);
+    std::vector<int> hpt(n);
+    launch_missing_masks(T.yd.p, n, p, masks.p, pt.p, st0);
+    HIPCHK(hipMemcpyAsync(hpt.data(), pt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));
+    for (int t = 0; t < n; ++t)
+      if (hpt[t] != p) {
+        g.err_latent = -1; g.err_info = t;
+        return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path needs complete data: point %d has a NaN in y (per-point noise is not Toeplitz)", t);
+      }
+  }
+  T.l0 = l0; T.l1 = l1; T.ms = l1 - l0; T.mk = std::max(T.ms, 1);
+  const std::vector<double> means = latent_means(T.lts, m);
+  return missing_front(T.yd.p, n, p, U, S, m, sigma2, means.data(), l0, l1, want_resid, T.F);
+}
+
+int lmm_oilmm_logpdf_toeplitz(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                              const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!out) return fail(LMM_ERR_ARG, "bad arguments");
+  ToepTrain T;
+  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, false, T)) return rc;
+  ToepWork W;
+  if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, T.ms, T.F.nv.p, T.F.z.p, W)) return rc;
+  double total = 0.0;
+  for (int k = 0; k < T.ms; ++k) total += W.lml[k];
+  if (with_regulariser) total += T.F.reg(n, m, sigma2);
+  *out = total;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Value and gradient of lmm_oilmm_logpdf_toeplitz with respect to y, sigma2, S, U and every latent's kernel parameters and mean.  Per
+// latent: alpha = K^-1 r by the Gohberg-Semencul products, the diagonal sums of K^-1 and the autocorrelation of alpha, and their
+// contraction with the kernel's derivatives along the lags (launch_toep_contract), which gives the sums of the dense reduction: the
+// host formulas are those of KernelGradPass::finish, the chain rule OilmmGradBackEnd with a = alpha.
+int lmm_oilmm_logpdf_grad_toeplitz(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                                   const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out_logpdf,
+                                   double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U, lmm_gp_grad_t* grad_gps) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  ToepTrain T;
+  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, grad_y && with_regulariser, T)) return rc;
+  hipStream_t st0 = g.streams[0];
+  const int l0 = T.l0, l1 = T.l1, ms = T.ms, mk = T.mk;
+  const Latent* lts = T.lts;
+  ToepWork W;
+  if (int rc = toep_factor(T.xd.p, n, lts, l0, ms, T.F.nv.p, T.F.z.p, W)) return rc;
+  DevOut gy(grad_y, (size_t)n * p);
+  Buf<double> al((size_t)n * mk), u(2 * (size_t)n * mk), sd((size_t)n * mk), ad((size_t)n * mk), red((size_t)LMM_SUM_MAX_TERMS * LMM_NGRAD * mk);
+  std::vector<double> hred(red.n, 0.0);
+  std::vector<ToepGradLat> hg(mk);
+  Buf<ToepGradLat> dg(mk);
+  if (ms > 0) {
+    for (int k = 0; k < ms; ++k) {
+      hg[k].nterms = lts[l0 + k].nt();
+      for (int c = 0; c < hg[k].nterms; ++c) hg[k].gd[c] = lts[l0 + k].terms[c].gd;
+    }
+    HIPCHK(hipMemcpyAsync(dg.p, hg.data(), (size_t)ms * sizeof(ToepGradLat), hipMemcpyHostToDevice, st0));
+    launch_toep_solve(W.p.p, W.q.p, T.F.z.p, n, ms, u.p, al.p, st0);
+    launch_toep_lags(W.p.p, W.q.p, al.p, n, ms, sd.p, ad.p, st0);
+    launch_toep_contract(T.xd.p, n, dg.p, sd.p, ad.p, al.p, T.F.z.p, ms, sum_mode(lts, l0, l1), red.p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hred.data(), red.p, (size_t)LMM_SUM_MAX_TERMS * LMM_NGRAD * ms * sizeof(double), hipMemcpyDeviceToHost, st0));
+  }
+  OilmmGrad G;
+  G.size(m, p, 1, 1);
+  double total = 0.0;
+  for (int k = 0; k < ms; ++k) total += W.lml[k];
+  if (with_regulariser) total += T.F.reg(n, m, sigma2);
+  G.value = total;
+  std::vector<double> Tm, ST, H, dw(mk, 0.0), mean_sum(mk, 0.0);
+  project_orthogonal(U, S, p, m, sigma2, Tm, ST, H);
+  OilmmGradIn in{T.yd.p, n, p, U, S, m, one_noise_block(n, sigma2), l0, l1, with_regulariser};
+  in.a = al.p; in.lda = n; in.dot = T.F.z.p;
+  OilmmGradBackEnd B(in);
+  HIPCHK(hipStreamSynchronize(st0));
+  for (int k = 0; k < ms; ++k) {
+    const int l = l0 + k;
+    const double* r = &hred[(size_t)LMM_SUM_MAX_TERMS * LMM_NGRAD * k];      // [1] tr K^-1, [2] alpha.alpha, [3] alpha.r, [4] sum alpha
+    const double tr = r[1], aa = r[2], wl = ST[l];
+    dw[k] = 0.5 * (aa - tr);
+    mean_sum[k] = lts[l].mean * r[4];
+    G.ggps[l].variance = 0.5 * ((r[3] - wl * aa) - ((double)n - wl * tr)) / lts[l].variance;
+    G.ggps[l].lengthscale = grad_finish(lts[l], 1, r, nullptr, aa, tr, &G.trec[(size_t)l * LMM_SUM_MAX_TERMS * term_grad_stride(1)]);
+    G.ggps[l].mean = r[4];
+  }
+  double reg_value = 0.0;
+  B.finish(dw.data(), mean_sum.data(), Tm, reg_value, G, gy.p);
+  if (grad_y) HIPCHK(hipGetLastError());
+  publish_grads(*T.ls, grad_gps ? &G.trec : nullptr, l0, l1);
+  write_oilmm_grad(G, out_logpdf, grad_sigma2, grad_S, grad_U, grad_gps);
+  if (grad_y) { gy.finish(st0); HIPCHK(hipStreamSynchronize(st0)); }
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// Building blocks for tests (DEVICE pointers, one matrix): the recursion on a given first column t and right-hand side r, and the
+// Gohberg-Semencul solve from its generators.
+int lmm_dev_toeplitz_factor(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!t || !r || !p || !q || n <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  if (n > TOEP_MAX_N) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves n <= %d points (lmm_toeplitz_max_n; n = %d)", TOEP_MAX_N, n);
+  hipStream_t st0 = g.streams[0];
+  Buf<double> out2(2);
+  Buf<int> info(1);
+  launch_toep_schur(t, r, n, 1, out2.p, p, q, info.p, st0);
+  HIPCHK(hipGetLastError());
+  double h2[2] = {0.0, 0.0};
+  int hinfo = 0;
+  HIPCHK(hipMemcpyAsync(h2, out2.p, sizeof h2, hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  if (hinfo != 0) {
+    g.err_latent = 0; g.err_info = hinfo;
+    return fail(LMM_ERR_NOT_PD, "PosDefException: the Toeplitz matrix is not positive definite; the Schur recursion failed (latent 0, step %d)", hinfo - 1);
+  }
+  if (logdet) *logdet = h2[0];
+  if (quad) *quad = h2[1];
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_dev_toeplitz_solve(const double* p, const double* q, const double* r, int n, double* alpha) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!p || !q || !r || !alpha || n <= 0) return fail(LMM_ERR_ARG, "bad arguments");
+  hipStream_t st0 = g.streams[0];
+  Buf<double> u(2 * (size_t)n);
+  launch_toep_solve(p, q, r, n, 1, u.p, alpha, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
 }
 
 // Building blocks for tests: ONE latent from device pointers, per-point noise w (+Inf: unobserved) and data r; the latent's mean is

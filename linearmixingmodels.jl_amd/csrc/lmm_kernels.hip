@@ -26,6 +26,7 @@
 #include <type_traits>
 #include <cstdlib>
 #include "lmm_internal.h"
+#include "lmm_toeplitz.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -6098,4 +6099,88 @@ void launch_sparse_beta(const BatchPtr& R, int ld, int M, const BatchPtr& c, con
 void launch_sparse_phibar(const BatchPtr& Ki, const BatchPtr& Si, const BatchPtr& T2, const BatchPtr& beta, const BatchPtr& PB, int ld,
                           int M, int nb, hipStream_t st) {
   hipLaunchKernelGGL(sparse_phibar_kernel, dim3((M + 255) / 256, M, nb), dim3(256), 0, st, Ki, Si, T2, beta, PB, ld, M);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Toeplitz path (lmm_toeplitz.h): the two kernels that evaluate a latent's kernel, beside the evaluators they call.
+// ---------------------------------------------------------------------------------------------------
+// The first column of K + w I over an evenly spaced input: t[j] = kappa(x_j, x_0) through kappa_lat, the noise added at j = 0.
+template <int SUM>
+__global__ __launch_bounds__(256) void toep_row_kernel(const double* __restrict__ x, int n, const LatentDev* __restrict__ lat,
+                                                       const double* __restrict__ w, double* __restrict__ t) {
+  const int j = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (j >= n) return;
+  const LatentDev g = lat[l];
+  double v = kappa_lat<SUM>(g, x + j, x, 1);
+  if (j == 0 && w) v += w[(size_t)l * n];
+  t[(size_t)l * n + j] = v;
+}
+
+// The kernel-parameter contractions of one latent per workgroup: sum over the lags d >= 1 of (ad[d] - sd[d]) d t_d / d theta, which is
+// sum_{i > j} (alpha_i alpha_j - (K^-1)_ij) d K_ij / d theta of grad_reduce_kernel taken along the diagonals.  Per term the pair
+// (x_d, x_0) goes through the pair evaluators of the dense and inducing-point reductions (sparse_grad_pair; ext_pair for an SHO term,
+// which the former does not serve) with that weight, and the sums get the same closing factors.  A thread takes every 256th lag in
+// ascending order, block_sum_256 adds the threads: a fixed order.  Term 0's record also carries tr K^-1 = sd[0], alpha.alpha = ad[0],
+// alpha.r and sum alpha, where grad_reduce_kernel puts them.
+template <bool PER>
+__global__ __launch_bounds__(256) void toep_contract_kernel(const double* __restrict__ x, int n, const ToepGradLat* __restrict__ lat,
+                                                            const double* __restrict__ sd, const double* __restrict__ ad,
+                                                            const double* __restrict__ alpha, const double* __restrict__ r,
+                                                            double* __restrict__ red) {
+  __shared__ double sh[4];
+  const int l = blockIdx.x, t = threadIdx.x;
+  const size_t off = (size_t)l * n;
+  sd += off; ad += off; alpha += off; r += off;
+  double* out = red + (size_t)l * LMM_SUM_MAX_TERMS * LMM_NGRAD;
+  const int nterms = lat[l].nterms;
+  for (int c = 0; c < LMM_SUM_MAX_TERMS; ++c) {
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    if (c < nterms) {
+      const LatentDev g = lat[l].gd[c];
+      const bool per = g.kind == LMM_KERNEL_PERIODIC || g.kind == LMM_KERNEL_LOCALLY_PERIODIC;
+      const double sils = g.inv_ls, sdec = g.kind == LMM_KERNEL_LOCALLY_PERIODIC ? g.inv_decay * g.inv_decay / g.inv_ls : 0.0;
+      double rec[4] = {0.0, 0.0, 0.0, 0.0}, ard[1] = {0.0}, gz[1] = {0.0};
+      for (int d = 1 + t; d < n; d += 256) {
+        const double w = ad[d] - sd[d];
+        if (g.kind == LMM_KERNEL_SHO) {
+          const double rs = fabs(x[d] - x[0]) * g.inv_ls;
+          double kap, dell, dq;
+          ext_pair(g, rs, rs * rs, kap, dell, dq);
+          rec[0] = __builtin_fma(w, dell, rec[0]);
+          rec[1] = __builtin_fma(w, kap, rec[1]);
+          rec[2] = __builtin_fma(w, dq, rec[2]);
+        } else {
+          sparse_grad_pair<1, PER>(g, &sils, &sdec, x + d, x, 1, w, rec, ard, gz);
+        }
+      }
+      const double pc = per ? LMM_PI * g.alpha : 1.0;
+      v[0] = g.kind == LMM_KERNEL_SHO ? rec[0] : rec[0] * g.inv_ls * pc;
+      v[1] = rec[1];
+      v[2] = per ? rec[2] * per_rho3(g.alpha) : rec[2];
+      v[3] = rec[3] * (g.inv_decay * g.inv_decay * g.inv_decay);
+    }
+    const double s0 = block_sum_256(v[0], sh), s1 = block_sum_256(v[1], sh), s2 = block_sum_256(v[2], sh), s3 = block_sum_256(v[3], sh);
+    if (t == 0) {
+      double* o = out + (size_t)LMM_NGRAD * c;
+      for (int e = 0; e < LMM_NGRAD; ++e) o[e] = 0.0;
+      o[0] = s0; o[7] = s1; o[8] = s2; o[9] = s3;
+    }
+  }
+  double ar = 0.0, sa = 0.0;
+  for (int i = t; i < n; i += 256) { ar = __builtin_fma(alpha[i], r[i], ar); sa += alpha[i]; }
+  const double tar = block_sum_256(ar, sh), tsa = block_sum_256(sa, sh);
+  if (t == 0) { out[1] = sd[0]; out[2] = ad[0]; out[3] = tar; out[4] = tsa; }
+}
+
+void launch_toep_row(const double* x, int n, const LatentDev* lat, const double* w, int nb, int mode, double* t, hipStream_t st) {
+  if (nb <= 0) return;
+  mode_dispatch(mode, [&](auto md) {
+    hipLaunchKernelGGL((toep_row_kernel<decltype(md)::value>), dim3((n + 255) / 256, nb), dim3(256), 0, st, x, n, lat, w, t);
+  });
+}
+void launch_toep_contract(const double* x, int n, const ToepGradLat* lat, const double* sd, const double* ad, const double* alpha,
+                          const double* r, int nb, int mode, double* red, hipStream_t st) {
+  if (nb <= 0) return;
+  if (mode == 2) hipLaunchKernelGGL((toep_contract_kernel<true>), dim3(nb), dim3(256), 0, st, x, n, lat, sd, ad, alpha, r, red);
+  else hipLaunchKernelGGL((toep_contract_kernel<false>), dim3(nb), dim3(256), 0, st, x, n, lat, sd, ad, alpha, r, red);
 }

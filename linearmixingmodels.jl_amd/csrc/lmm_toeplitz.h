@@ -1,0 +1,28 @@
+// lmm_toeplitz.h -- the Toeplitz path for stationary latents over an evenly spaced one-dimensional input.  All Float64.
+// lmm_kernels_toeplitz.hip holds the factorisation and the products; the two kernels that evaluate a latent's kernel (the first column
+// and the gradient contraction) stand beside the per-kind evaluators they call, in lmm_kernels.hip.
+#pragma once
+#include "lmm_internal.h"
+
+#define TOEP_THREADS 1024                     // threads of the one workgroup that factors a latent
+#define TOEP_MAX_EPT 8                        // most rows a thread owns
+#define TOEP_MAX_N (TOEP_THREADS * TOEP_MAX_EPT)      // 8192: a and p (n doubles each) stay in LDS, 128 KB of the CU's 160
+
+// t[l n + j] = kappa_l(x_j, x_0) (+ w[l n] at j = 0) for the nb latents lat[0 .. nb) (device descriptors as the dense kernels take them:
+// Latent::dev()); w: [latent][n] noise, of which element 0 is read, or nullptr; mode: the kernel instantiation (0, 1 sums, 2 periodic)
+void launch_toep_row(const double* x, int n, const LatentDev* lat, const double* w, int nb, int mode, double* t, hipStream_t st);
+// The Schur recursion of nb symmetric positive definite Toeplitz matrices with first columns t[l n ..] and right-hand sides r[l n ..]:
+// out2[2 l] = log det, out2[2 l + 1] = r' K^-1 r, p / q [l n ..] the Gohberg-Semencul generators of K^-1, info[l] = 0 or 1 + the step
+// whose pivot was not > 0 (or whose reflection coefficient was not inside (-1, 1)).  n <= TOEP_MAX_N.
+void launch_toep_schur(const double* t, const double* r, int n, int nb, double* out2, double* p, double* q, int* info, hipStream_t st);
+// alpha[l n ..] = K_l^-1 r_l = L(q) L(q)' r - L(p) L(p)' r; u: 2 nb n doubles of scratch
+void launch_toep_solve(const double* p, const double* q, const double* r, int n, int nb, double* u, double* alpha, hipStream_t st);
+// sd[l n + d] = sum_i (K_l^-1)_{i, i + d} and ad[l n + d] = sum_i alpha_i alpha_{i + d}
+void launch_toep_lags(const double* p, const double* q, const double* alpha, int n, int nb, double* sd, double* ad, hipStream_t st);
+// One latent of the gradient contraction: its nterms gradient descriptors (KernelTerm::gd)
+struct ToepGradLat { LatentDev gd[LMM_SUM_MAX_TERMS]; int nterms; int pad; };
+// red[(LMM_SUM_MAX_TERMS l + c) LMM_NGRAD ..]: term c's record in the layout of grad_reduce_kernel -- [0] d/d lengthscale, [7] sum w K_c,
+// [8] d/d alpha, rho or quality, [9] d/d decay over the pairs i > j, w_ij = alpha_i alpha_j - (K^-1)_ij summed along the diagonals
+// (ad - sd); term 0's also [1] tr K^-1, [2] alpha.alpha, [3] alpha.r, [4] sum alpha.  mode as launch_toep_row's.
+void launch_toep_contract(const double* x, int n, const ToepGradLat* lat, const double* sd, const double* ad, const double* alpha,
+                          const double* r, int nb, int mode, double* red, hipStream_t st);

@@ -1409,6 +1409,76 @@ def statespace_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = T
     return out
 
 
+def _toeplitz_args(fx: "FiniteGP", y, what: str):
+    """Checks of toeplitz_logpdf / toeplitz_logpdf_and_gradient, all before any library call (they mirror _statespace_args)."""
+    f, x = fx.f, fx.x
+    if isinstance(f, IndependentMOGP):
+        raise NotImplementedError(f"{what}: the Toeplitz path is not served for an IndependentMOGP (wrap it in an OILMM)")
+    if not isinstance(f, ILMM) or not f.is_oilmm:
+        raise NotImplementedError(f"{what}: the Toeplitz path is not served for a dense-H ILMM (OILMM only)")
+    if f.f._post is not None:
+        raise NotImplementedError(f"{what}: the Toeplitz path is not served on a posterior model (prior OILMM only)")
+    if f.shard != (0, len(f.f.fs)):
+        raise NotImplementedError(f"{what}: the Toeplitz path is not served with latents sharded across processes")
+    if not isinstance(x, MOInputIsotopicByOutputs):
+        raise NotImplementedError(f"{what}: the Toeplitz path takes MOInputIsotopicByOutputs inputs")
+    if fx.heteroscedastic:
+        raise NotImplementedError(f"{what}: the Toeplitz path takes a scalar noise variance (no per-point noise)")
+    if x.dim != 1:
+        raise NotImplementedError(f"{what}: the Toeplitz path is served for one-dimensional inputs (d = {x.dim})")
+    if not hasattr(y, "shape"):
+        y = np.asarray(y, dtype=np.float64)
+    if len(y.shape) != 1:
+        raise NotImplementedError(f"{what}: the Toeplitz path is not served for a matrix Y (one vector y)")
+    unpack(fx)
+    if y.shape[0] != x.n * x.out_dim:
+        raise ValueError("length(y) != n * out_dim")
+    xs = x.x.reshape(-1)
+    xh = xs.detach().cpu().numpy() if L._is_torch(xs) else np.asarray(xs, dtype=np.float64)
+    n = xh.shape[0]
+    if n > 1:
+        h = (xh[-1] - xh[0]) / (n - 1)
+        off = np.abs(xh - (xh[0] + np.arange(n) * h)) <= 8.0 * np.finfo(np.float64).eps * max(abs(xh[0]), abs(xh[-1]))
+        if not h > 0.0 or not off.all():
+            bad = 1 if not h > 0.0 else int(np.argmin(off))
+            raise ValueError(f"{what}: the Toeplitz path needs ascending, evenly spaced inputs (x[{bad}] is off the grid)")
+    return y
+
+
+def toeplitz_logpdf(fx: "FiniteGP", y, with_regulariser: bool = True) -> float:
+    """logpdf(fx, y) of a prior OILMM with stationary latents of ANY kind (SE, RQ, periodic, locally periodic, Matern, SHO, KernelSum)
+    over ascending, evenly spaced one-dimensional inputs and complete data, exactly, in O(n^2) time and O(n) memory per latent: there
+    every K_l + (sigma2 / S_l) I is symmetric Toeplitz, and the Schur recursion factors it.  x and y: NumPy arrays or
+    torch device tensors.  A NaN in y, n beyond the cap (lmm_toeplitz_max_n) and ARD tags are refused by the library."""
+    y = _toeplitz_args(fx, y, "toeplitz_logpdf")
+    f, x = fx.f, fx.x
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    out = C.c_double()
+    L.check(L.load().lmm_oilmm_logpdf_toeplitz(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps, 0, m,
+                                               int(with_regulariser), C.byref(out)))
+    return out.value
+
+
+def toeplitz_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = True) -> dict:
+    """Value and gradient of toeplitz_logpdf(fx, y): {"value", "y", "sigma2", "S", "U", "gps"}, as logpdf_and_gradient returns them for
+    a prior OILMM ("gps" through _gps_grads: every latent's kernel parameters, tags and sum terms included, and its mean).  "value" is
+    bitwise toeplitz_logpdf(fx, y, with_regulariser); "y" is shaped and typed like y."""
+    y = _toeplitz_args(fx, y, "toeplitz_logpdf_and_gradient")
+    f, x = fx.f, fx.x
+    n = x.n
+    L.ensure_init()
+    Ua, Sa, p, m = _H_args(f.H)
+    val, gs2 = C.c_double(), C.c_double()
+    gy, gS, gU = _alloc_like(y, n * p), np.empty(m), np.empty(p * m)
+    gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.f.fs])
+    L.check(L.load().lmm_oilmm_logpdf_grad_toeplitz(L.Arr(x.x.reshape(-1)).ptr, n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), ga, 0, m,
+                                                    int(with_regulariser), C.byref(val), L.Arr(gy, True).ptr, C.byref(gs2),
+                                                    L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg))
+    return {"value": val.value, "y": gy, "sigma2": gs2.value, "S": gS, "U": gU.reshape(m, p).T.copy(), "gps": _gps_grads(gg, ga, m, 1)}
+
+
 def statespace_rand(rng, fx: "FiniteGP", y=None, N: Optional[int] = None, add_noise: bool = True, xs=None):
     """Joint samples of the same models in O(n), exact: of the prior fx (y=None: rand(rng, fx)), or of the posterior given y
     (rand(rng, posterior(fx, y)(x*, sigma2))) at the training inputs (xs=None) or at the new inputs xs ((ns,); merged into the inputs
