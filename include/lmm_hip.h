@@ -852,6 +852,35 @@ int lmm_oilmm_logpdf_grad_toeplitz(const double* x, int n, const double* y, int 
                                    lmm_gp_grad_t* grad_gps);
 int lmm_dev_toeplitz_factor(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q);
 int lmm_dev_toeplitz_solve(const double* p, const double* q, const double* r, int n, double* alpha);
+/* Toeplitz: the posterior object (DESIGN.md 4.22 "Posterior handle").  What posterior(fx, y) followed by mean_and_var(post(x*, sigma2))
+ * is on the dense path, from ONE Schur recursion per latent: the handle keeps the Gohberg-Semencul generators p, q of
+ * (K_l + (sigma2 / S_l) I)^-1 and alpha_l = (K_l + (sigma2 / S_l) I)^-1 r_l, and a query at any new inputs is
+ *   mean_l(s) = mu_l + k*(s)' alpha_l,     var_l(s) = kappa_l(0) - (|L(q)' k*(s)|^2 - |L(p)' k*(s)|^2),     k*(s)[t] = kappa_l(x_0 + t h, s),
+ * the variance as a GEMM on v_mfma_f64_16x16x4_f64 whose two operands are generated on the fly (toep_predict_kernel): O(n^2 ns) flops,
+ * O(n + ns) memory, no atomics, bitwise reproducible; a query's result depends on no other query.  The error of var is relative to
+ * the PRIOR variance kappa_l(0) (it grows with |L(q)' k*|^2 / kappa_l(0) and with n), not to a small posterior variance.
+ *   lmm_oilmm_toeplitz_posterior_create : conditions on (x, y).  Arguments, data rules and every refusal of lmm_oilmm_logpdf_toeplitz,
+ *                    in its order.  *out_logpdf (may be NULL) is bitwise the value of lmm_oilmm_logpdf_toeplitz with the regulariser.
+ *                    The handle owns, on the device, 3 n doubles per latent of the shard (p, q, alpha) and H = U sqrt(S) of the shard,
+ *                    and on the host x_0, h = (x[n-1] - x[0]) / (n - 1), n, sigma2 and the resolved latents.  On any failure *out is NULL.
+ *   lmm_toeplitz_post_destroy : frees the handle; NULL is accepted.
+ *   lmm_oilmm_toeplitz_post_mean_and_var : the latent marginals at xs (ns values in any order, host or device) mixed through H exactly
+ *                    as lmm_oilmm_statespace_post_mean_and_var mixes (the default jitter on the latent variances, + sigma2 when
+ *                    add_noise).  mean, var: ns x p by outputs, host or device; var may be NULL, and then no GEMM runs.  Large ns is
+ *                    served in chunks of queries (bounded scratch).  Partial sums over the handle's shard.  post, xs or mean NULL or
+ *                    ns < 1 -> LMM_ERR_ARG; a NaN or +-Inf in xs -> LMM_ERR_ARG with the first such index in lmm_last_error_detail's
+ *                    `info`, before any kernel of the path runs; the fp32 compute mode -> LMM_ERR_UNSUPPORTED.
+ *   lmm_dev_toeplitz_predict : building block for tests, DEVICE pointers, ONE latent (gp on the host; its mean is not read): from the
+ *                    generators p, q and alpha (n values each) over the grid x0 + t h, t < n, the zero-mean latent marginals mean, var
+ *                    (ns values each) at xs.  n <= lmm_toeplitz_max_n(). */
+typedef struct lmm_toep_post lmm_toep_post_t;
+int lmm_oilmm_toeplitz_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                        double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_toep_post_t** out,
+                                        double* out_logpdf);
+int lmm_toeplitz_post_destroy(lmm_toep_post_t* post);
+int lmm_oilmm_toeplitz_post_mean_and_var(const lmm_toep_post_t* post, const double* xs, int ns, int add_noise, double* mean, double* var);
+int lmm_dev_toeplitz_predict(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* alpha,
+                             const double* xs, int ns, double* mean, double* var);
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
                               const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,

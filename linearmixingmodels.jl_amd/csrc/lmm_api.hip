@@ -5774,6 +5774,151 @@ int lmm_dev_toeplitz_solve(const double* p, const double* q, const double* r, in
   LMM_CATCH
 }
 
+// ---- the Toeplitz posterior object (DESIGN.md 4.22 "Posterior handle") -------------------------------------------------------------
+// One recursion per latent keeps the generators p, q of (K_l + w_l I)^-1 and alpha_l; a query at new inputs is the latent mean
+// mu + K(xs, x) alpha (post_mean_g), the latent variance kappa(0) - |L(q)' k*|^2 + |L(p)' k*|^2 (launch_toep_predict) and the mixing
+// of lmm_oilmm_statespace_post_mean_and_var.
+struct lmm_toep_post {
+  int n = 0, p = 0, m = 0, l0 = 0, l1 = 0;
+  double sigma2 = 0.0, x0 = 0.0, h = 0.0;
+  std::shared_ptr<LatentSet> ls;      // all m latents as the handle was built with them
+  Buf<double> pg, qg, alpha;          // per latent of the shard, [latent][n]
+  Buf<double> H;                      // p x (l1 - l0), column-major: H = U sqrt(S) of the shard
+};
+
+static const size_t kToepPredictScratch = size_t(1) << 23;      // doubles of partials a query chunk may take (64 MB)
+
+// The marginals of the ms latents lts[0 .. ms) at the ns queries xsd (device, finite) from their generators and alpha ([latent][n],
+// device) over the grid x0 + t h: ml, vl [latent][ns] on the device; vl == nullptr: the means alone, no GEMM.  add_mean: plus the
+// latent's mean.  The variance runs in chunks of queries whose partials fit kToepPredictScratch.  Returns with streams[0] drained.
+static int toep_predict_latents(double x0, double h, int n, const Latent* lts, int ms, const double* pg, const double* qg,
+                                const double* alpha, const double* xsd, int ns, bool add_mean, double* ml, double* vl) {
+  if (ms == 0) return LMM_OK;
+  hipStream_t st0 = g.streams[0];
+  Buf<double> xg((size_t)n), pm_part(post_mean_partial_elems(ns, n));
+  launch_toep_grid(x0, h, n, xg.p, st0);
+  for (int k = 0; k < ms; ++k) {
+    Latent L = lts[k];
+    if (!add_mean) L.mean = 0.0;
+    post_mean_g(xsd, ns, xg.p, n, 1, alpha + (size_t)k * n, L, pm_part.p, ml + (size_t)k * ns, st0);
+  }
+  HIPCHK(hipGetLastError());
+  if (!vl) { HIPCHK(hipStreamSynchronize(st0)); return LMM_OK; }
+  std::vector<LatentDev> hd(ms);
+  std::vector<double> hk0(ms);
+  for (int k = 0; k < ms; ++k) { hd[k] = lts[k].dev(); hk0[k] = lts[k].prior_var(); }
+  Buf<LatentDev> dd(ms);
+  Buf<double> k0(ms);
+  HIPCHK(hipMemcpyAsync(dd.p, hd.data(), (size_t)ms * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  HIPCHK(hipMemcpyAsync(k0.p, hk0.data(), (size_t)ms * sizeof(double), hipMemcpyHostToDevice, st0));
+  const size_t per_block = toep_predict_scratch(n, TOEP_PRED_Q, ms);      // the partials of one block of queries
+  const int chunk = (int)std::min<size_t>((size_t)rup(ns, TOEP_PRED_Q), std::max<size_t>(1, std::min<size_t>(kToepPredictScratch / per_block, 32768)) * TOEP_PRED_Q);
+  Buf<double> part(toep_predict_scratch(n, chunk, ms));
+  const int mode = sum_mode(lts, 0, ms);
+  for (int c0 = 0; c0 < ns; c0 += chunk)
+    launch_toep_predict(x0, h, n, dd.p, k0.p, pg, qg, xsd + c0, std::min(chunk, ns - c0), ms, mode, part.p, vl + c0, (size_t)ns, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+}
+
+// xs (device, ns values) must be finite: LMM_ERR_ARG with the first offending index in the error detail's `info`.
+static int toep_check_finite(const double* xsd, int ns) {
+  const int h = ss_first_flagged(launch_ss_finite, xsd, ns);
+  if (h == INT_MAX) return LMM_OK;
+  return fail(LMM_ERR_ARG, "Toeplitz posterior: xs[%d] is not finite", h);
+}
+static int toep_refuse_f32() { return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path is Float64 only (lmm_set_compute_dtype(LMM_F64))"); }
+
+int lmm_oilmm_toeplitz_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                        double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_toep_post_t** out,
+                                        double* out_logpdf) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!out) return fail(LMM_ERR_ARG, "bad arguments");
+  *out = nullptr;
+  ToepTrain T;
+  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, false, T)) return rc;
+  ToepWork W;
+  if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, T.ms, T.F.nv.p, T.F.z.p, W)) return rc;
+  hipStream_t st0 = g.streams[0];
+  double total = 0.0;                       // the sum of lmm_oilmm_logpdf_toeplitz, in its order
+  for (int k = 0; k < T.ms; ++k) total += W.lml[k];
+  total += T.F.reg(n, m, sigma2);
+  std::unique_ptr<lmm_toep_post> P(new lmm_toep_post());      // a throw below (a failed allocation) frees what it holds
+  P->n = n; P->p = p; P->m = m; P->l0 = T.l0; P->l1 = T.l1; P->sigma2 = sigma2; P->ls = T.ls;
+  double ends[2] = {0.0, 0.0};
+  HIPCHK(hipMemcpyAsync(&ends[0], T.xd.p, sizeof(double), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipMemcpyAsync(&ends[1], T.xd.p + (n - 1), sizeof(double), hipMemcpyDeviceToHost, st0));
+  P->alpha = Buf<double>((size_t)n * T.mk);
+  {
+    Buf<double> u(2 * (size_t)n * T.mk);
+    launch_toep_solve(W.p.p, W.q.p, T.F.z.p, n, T.ms, u.p, P->alpha.p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));
+  }
+  P->x0 = ends[0]; P->h = n > 1 ? (ends[1] - ends[0]) / (double)(n - 1) : 0.0;
+  P->pg = std::move(W.p); P->qg = std::move(W.q);
+  const std::vector<double> Hs = shard_H(U, S, p, T.l0, T.ms);
+  P->H = Buf<double>(std::max<size_t>(Hs.size(), 1));
+  HIPCHK(hipMemcpyAsync(P->H.p, Hs.data(), Hs.size() * sizeof(double), hipMemcpyHostToDevice, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  if (out_logpdf) *out_logpdf = total;
+  *out = P.release();
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_toeplitz_post_destroy(lmm_toep_post_t* post) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (post) {
+    if (g.init) (void)hipDeviceSynchronize();
+    delete post;
+  }
+  return LMM_OK;
+}
+
+int lmm_oilmm_toeplitz_post_mean_and_var(const lmm_toep_post_t* post, const double* xs, int ns, int add_noise, double* mean_out,
+                                         double* var_out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !xs || !mean_out || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return toep_refuse_f32();
+  const lmm_toep_post* P = post;
+  const int p = P->p, ms = P->l1 - P->l0;
+  hipStream_t st0 = g.streams[0];
+  DevIn xsd(xs, (size_t)ns, st0);
+  if (int rc = toep_check_finite(xsd.p, ns)) return rc;
+  Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
+  if (int rc = toep_predict_latents(P->x0, P->h, P->n, P->ls->lat.data() + P->l0, ms, P->pg.p, P->qg.p, P->alpha.p, xsd.p, ns, true,
+                                    ml.p, var_out ? vl.p : nullptr)) return rc;
+  DevOut mo(mean_out, (size_t)ns * p), vo(var_out, (size_t)ns * p);
+  mix_marginals(ml.p, ns, ms, P->H.p, p, 1, 0.0, 0.0, mo.p, st0);
+  if (var_out) mix_marginals(vl.p, ns, ms, P->H.p, p, 2, kDefaultJit.default_jitter, add_noise ? P->sigma2 : 0.0, vo.p, st0);
+  mo.finish(st0); vo.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_dev_toeplitz_predict(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* alpha,
+                             const double* xs, int ns, double* mean, double* var) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!gp || !p || !q || !alpha || !xs || !mean || !var || n <= 0 || ns <= 0 || !std::isfinite(x0) || !std::isfinite(h))
+    return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return toep_refuse_f32();
+  if (n > TOEP_MAX_N) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves n <= %d points (lmm_toeplitz_max_n; n = %d)", TOEP_MAX_N, n);
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = resolve(gp, 1, 1, ls)) return rc;
+  if (int rc = toep_check_finite(xs, ns)) return rc;
+  return toep_predict_latents(x0, h, n, ls->lat.data(), 1, p, q, alpha, xs, ns, false, mean, var);
+  LMM_CATCH
+}
+
 // Building blocks for tests: ONE latent from device pointers, per-point noise w (+Inf: unobserved) and data r; the latent's mean is
 // not read (r is the residual).  chunk: points per thread (0: the library's plan).
 // The preamble of these one-latent entry points: `bad` (a NULL pointer or a size out of range) refuses the arguments, then nsamples

@@ -6184,3 +6184,140 @@ void launch_toep_contract(const double* x, int n, const ToepGradLat* lat, const 
   if (mode == 2) hipLaunchKernelGGL((toep_contract_kernel<true>), dim3(nb), dim3(256), 0, st, x, n, lat, sd, ad, alpha, r, red);
   else hipLaunchKernelGGL((toep_contract_kernel<false>), dim3(nb), dim3(256), 0, st, x, n, lat, sd, ad, alpha, r, red);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Toeplitz posterior (DESIGN.md 4.22 "Posterior handle"): the latent variance reduction at ns new inputs,
+//     red_c = k*_c' K^-1 k*_c = |L(q)' k*_c|^2 - |L(p)' k*_c|^2,      k*_c[s] = kappa(x_0 + s h, xs_c),
+// as a GEMM on v_mfma_f64_16x16x4_f64 whose operands are both generated on the fly: A[o][s] = q[s - o] (and p[s - o]), s >= o, upper
+// triangular Toeplitz, and B[s][c] = k*_c[s].  Neither an n x n nor an n x ns matrix exists: memory is O(n + ns).
+// Workgroup (pair of row blocks, block of TOEP_PRED_Q queries, latent), 4 waves.  For a row block of TOEP_PRED_R rows o it walks s in
+// tiles of TPR_T from the block's first row to n.  Per tile the 256 threads stage the TOEP_PRED_R + TPR_T - 1 lags of q and p the
+// tile pair spans (zeros outside [0, n), as toep_tri_kernel stages them) and evaluate the TPR_T x TOEP_PRED_Q tile of B through
+// kappa_lat ONCE (4 evaluations per thread; zeros from s = n and from query ns on); all 16 row tiles of 16 rows and both generators
+// then read it: one evaluation feeds 2 TOEP_PRED_R FMAs.  Wave w owns the row tiles 4 j + w, j < 4 (interleaved, so the waves share
+// the diagonal tiles' triangle evenly) for both generators: 4 x 2 x 2 accumulators of 16 x 16, 128 VGPRs.  Per k-step of 4 values of
+// s a lane reads 2 B fragments and, per row tile, one fragment of q and one of p from the windows (lane (i, k) of a row tile takes
+// lag s - o, 19 consecutive doubles per fragment), for 4 MFMAs.  A k-step that lies wholly in front of a row tile (s < o) is not
+// issued.  At the end a lane adds (u_q - u_p)(u_q + u_p) over its rows (the form the NumPy restatement shows to lose less than two
+// sums of squares: tests/test_toeplitz_posterior_abi.py), the lanes and waves are added through LDS in a fixed order, and the block's
+// partial per query goes to part[latent][row block][query].  Row block i is paired with row block nrb - 1 - i, which evens out the
+// triangle's work among workgroups.  toep_predict_finish_kernel adds the partials in row-block order: no atomics, results are
+// bitwise reproducible, and a query's result depends on no other query.
+// ---------------------------------------------------------------------------------------------------
+constexpr int TPR_T = 32;                                  // values of s per tile of B
+constexpr int TPR_SB = TOEP_PRED_Q + 16;                   // LDS stride of a row of B: the k-lanes of a half-wave on distinct banks
+constexpr int TPR_W = TOEP_PRED_R + TPR_T;                 // the lag windows (TOEP_PRED_R + TPR_T - 1 lags are used)
+static_assert(TOEP_PRED_R == 256 && TOEP_PRED_Q == 32 && TPR_T * TOEP_PRED_Q == 4 * 256, "toep_predict_kernel's thread maps");
+
+template <int SUM>
+__global__ __launch_bounds__(256) void toep_predict_kernel(double x0, double h, int n, const LatentDev* __restrict__ lat,
+                                                           const double* __restrict__ p, const double* __restrict__ q,
+                                                           const double* __restrict__ xs, int ns, int nrb, double* __restrict__ part) {
+  __shared__ double Bt[TPR_T * TPR_SB];
+  __shared__ double wq[TPR_W], wp[TPR_W];
+  __shared__ double red[4][4][TOEP_PRED_Q];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, l15 = lane & 15, lk = lane >> 4;
+  const int l = blockIdx.z, c0 = blockIdx.y * TOEP_PRED_Q, nsp = gridDim.y * TOEP_PRED_Q;
+  const LatentDev g = lat[l];
+  p += (size_t)l * n; q += (size_t)l * n;
+  part += (size_t)l * nrb * nsp;
+  const int ec = t & (TOEP_PRED_Q - 1), ek = t >> 5;       // the thread evaluates B[ek + 8 e][ec], e < 4
+  const bool qlive = c0 + ec < ns;
+  const double xq = qlive ? xs[c0 + ec] : 0.0;
+  for (int half = 0; half < 2; ++half) {
+    const int rbk = half == 0 ? (int)blockIdx.x : nrb - 1 - (int)blockIdx.x;
+    if (half == 1 && rbk <= (int)blockIdx.x) break;        // the middle block of an odd count has no partner
+    const int o0 = rbk * TOEP_PRED_R;
+    d4 aq[4][2], ap[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) { aq[j][cb] = (d4){0.0, 0.0, 0.0, 0.0}; ap[j][cb] = (d4){0.0, 0.0, 0.0, 0.0}; }
+    for (int s0 = o0; s0 < n; s0 += TPR_T) {
+      __syncthreads();
+      for (int w = t; w < TPR_W; w += 256) {
+        const int lag = s0 - o0 - (TOEP_PRED_R - 1) + w;
+        const bool ok = lag >= 0 && lag < n;
+        wq[w] = ok ? q[lag] : 0.0; wp[w] = ok ? p[lag] : 0.0;
+      }
+#pragma unroll 1
+      for (int e = 0; e < 4; ++e) {
+        const int ks = ek + 8 * e, s = s0 + ks;
+        double v = 0.0;
+        if (qlive && s < n) {
+          const double xc = __builtin_fma((double)s, h, x0);
+          v = kappa_lat<SUM>(g, &xq, &xc, 1);
+        }
+        Bt[ks * TPR_SB + ec] = v;
+      }
+      __syncthreads();
+#pragma unroll 2
+      for (int k4 = 0; k4 < TPR_T / 4; ++k4) {      // two k-steps in flight: the 128 accumulator VGPRs leave room for two waves per SIMD
+        const int ks = 4 * k4 + lk;
+        const double b0 = Bt[ks * TPR_SB + l15], b1 = Bt[ks * TPR_SB + 16 + l15];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int ro = 16 * (4 * j + wv);
+          if (s0 + 4 * k4 + 3 >= o0 + ro) {                // else every s of the k-step lies in front of every row of the tile
+            const int w = ks - (ro + l15) + TOEP_PRED_R - 1;
+            const double fq = wq[w], fp = wp[w];
+            aq[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fq, b0, aq[j][0], 0, 0, 0);
+            aq[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fq, b1, aq[j][1], 0, 0, 0);
+            ap[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fp, b0, ap[j][0], 0, 0, 0);
+            ap[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fp, b1, ap[j][1], 0, 0, 0);
+          }
+        }
+      }
+    }
+    double sum[2] = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sum[cb] = __builtin_fma(aq[j][cb][r] - ap[j][cb][r], aq[j][cb][r] + ap[j][cb][r], sum[cb]);
+    __syncthreads();
+    red[wv][lk][l15] = sum[0]; red[wv][lk][16 + l15] = sum[1];
+    __syncthreads();
+    if (t < TOEP_PRED_Q) {
+      double v = 0.0;
+      for (int w = 0; w < 4; ++w)
+        for (int k = 0; k < 4; ++k) v += red[w][k][t];
+      part[(size_t)rbk * nsp + c0 + t] = v;
+    }
+  }
+}
+
+// var[l ldv + c] = k0[l] - sum over the row blocks, in their order, of part[l][row block][c]
+__global__ __launch_bounds__(256) void toep_predict_finish_kernel(const double* __restrict__ part, int nrb, int nsp, int ns,
+                                                                  const double* __restrict__ k0, double* __restrict__ var, size_t ldv) {
+  const int c = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (c >= ns) return;
+  double s = 0.0;
+  for (int b = 0; b < nrb; ++b) s += part[((size_t)l * nrb + b) * nsp + c];
+  var[(size_t)l * ldv + c] = k0[l] - s;
+}
+
+// x[i] = x0 + i h, the grid as toep_predict_kernel forms it
+__global__ __launch_bounds__(256) void toep_grid_kernel(double x0, double h, int n, double* __restrict__ x) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = __builtin_fma((double)i, h, x0);
+}
+
+void launch_toep_grid(double x0, double h, int n, double* x, hipStream_t st) {
+  hipLaunchKernelGGL(toep_grid_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x0, h, n, x);
+}
+size_t toep_predict_scratch(int n, int ns, int nb) {
+  return (size_t)nb * ((n + TOEP_PRED_R - 1) / TOEP_PRED_R) * ((ns + TOEP_PRED_Q - 1) / TOEP_PRED_Q * TOEP_PRED_Q);
+}
+void launch_toep_predict(double x0, double h, int n, const LatentDev* lat, const double* k0, const double* p, const double* q,
+                         const double* xs, int ns, int nb, int mode, double* part, double* var, size_t ldv, hipStream_t st) {
+  if (nb <= 0 || ns <= 0) return;
+  const int nrb = (n + TOEP_PRED_R - 1) / TOEP_PRED_R, nqb = (ns + TOEP_PRED_Q - 1) / TOEP_PRED_Q;
+  mode_dispatch(mode, [&](auto md) {
+    hipLaunchKernelGGL((toep_predict_kernel<decltype(md)::value>), dim3((nrb + 1) / 2, nqb, nb), dim3(256), 0, st, x0, h, n, lat, p, q,
+                       xs, ns, nrb, part);
+  });
+  hipLaunchKernelGGL(toep_predict_finish_kernel, dim3((ns + 255) / 256, nb), dim3(256), 0, st, (const double*)part, nrb,
+                     nqb * TOEP_PRED_Q, ns, k0, var, ldv);
+}

@@ -26,3 +26,15 @@ struct ToepGradLat { LatentDev gd[LMM_SUM_MAX_TERMS]; int nterms; int pad; };
 // (ad - sd); term 0's also [1] tr K^-1, [2] alpha.alpha, [3] alpha.r, [4] sum alpha.  mode as launch_toep_row's.
 void launch_toep_contract(const double* x, int n, const ToepGradLat* lat, const double* sd, const double* ad, const double* alpha,
                           const double* r, int nb, int mode, double* red, hipStream_t st);
+
+// ---- the posterior at new inputs (DESIGN.md 4.22 "Posterior handle") ----
+#define TOEP_PRED_R 256                       // rows of a row block of toep_predict_kernel
+#define TOEP_PRED_Q 32                        // queries of a query block
+// x[i] = x0 + i h, i < n: the grid as the predict kernel forms it
+void launch_toep_grid(double x0, double h, int n, double* x, hipStream_t st);
+// var[l ldv + c] = k0[l] - k*_c' K_l^-1 k*_c for the ns queries xs and the nb latents lat[0 .. nb) with generators p, q [l n ..] over the
+// grid x0 + s h, s < n; k0[l] = kappa_l(0) (device); part: toep_predict_scratch(n, ns, nb) doubles; mode as launch_toep_row's.
+// ns <= 65535 TOEP_PRED_Q.
+size_t toep_predict_scratch(int n, int ns, int nb);
+void launch_toep_predict(double x0, double h, int n, const LatentDev* lat, const double* k0, const double* p, const double* q,
+                         const double* xs, int ns, int nb, int mode, double* part, double* var, size_t ldv, hipStream_t st);

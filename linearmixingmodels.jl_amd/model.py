@@ -1479,6 +1479,90 @@ def toeplitz_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = Tru
     return {"value": val.value, "y": gy, "sigma2": gs2.value, "S": gS, "U": gU.reshape(m, p).T.copy(), "gps": _gps_grads(gg, ga, m, 1)}
 
 
+class ToeplitzPosterior:
+    """posterior(fx, y) on the Toeplitz path: owns an lmm_toep_post_t* (per latent the Gohberg-Semencul generators p, q and alpha on the
+    device, 3 n doubles; include/lmm_hip.h "Toeplitz: the posterior object") and answers mean_and_var(post(x*, sigma2)) at new inputs
+    without touching the data again: the means in O(n ns), the variances by one GEMM on the matrix cores whose operands are generated
+    on the fly, in O(n + ns) memory.  The error of var is relative to the prior variance, not to a small posterior variance.
+    Built by toeplitz_posterior; freed by close(), on leaving a `with` block or with the object."""
+
+    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float):
+        self._ptr, self.n, self.p, self.logpdf = ptr, n, p, logpdf
+
+    def close(self) -> None:
+        if self._ptr:
+            ptr, self._ptr = self._ptr, None
+            L.load().lmm_toeplitz_post_destroy(ptr)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _query(self, xs, add_noise: bool, want_var: bool):
+        """Every refusal comes before any library call."""
+        if not self._ptr:
+            raise ValueError("ToeplitzPosterior: the posterior has been closed")
+        if not hasattr(xs, "shape"):
+            xs = np.asarray(xs, dtype=np.float64)
+        if len(xs.shape) != 1:
+            raise ValueError("ToeplitzPosterior: xs is a (ns,) array of one-dimensional inputs")
+        if L._is_torch(xs):
+            import torch
+            xs = xs.to(torch.float64)
+            finite = bool(torch.isfinite(xs).all())
+        else:
+            xs = np.ascontiguousarray(xs, dtype=np.float64)
+            finite = bool(np.isfinite(xs).all())
+        if not finite:
+            raise ValueError("ToeplitzPosterior: xs must be finite (no NaN or Inf)")
+        ns = int(xs.shape[0])
+        mean = _alloc_like(xs, ns * self.p)
+        var = _alloc_like(xs, ns * self.p) if want_var else None
+        if ns == 0:
+            return mean, var
+        L.check(L.load().lmm_oilmm_toeplitz_post_mean_and_var(self._ptr, L.Arr(xs).ptr, ns, int(add_noise), L.Arr(mean, True).ptr,
+                                                              L.Arr(var, True).ptr if want_var else None))
+        return mean, var
+
+    def mean_and_var(self, xs, add_noise: bool = True):
+        """(mean, var) at the inputs xs ((ns,), in any order): by-outputs vectors of ns * p values, NumPy or torch-device like xs."""
+        return self._query(xs, add_noise, True)
+
+    def mean(self, xs):
+        return self._query(xs, False, False)[0]
+
+    def var(self, xs, add_noise: bool = True):
+        return self._query(xs, add_noise, True)[1]
+
+    def marginals(self, xs) -> "Normal":
+        """Normal(mean, sqrt(var)) as marginals builds it."""
+        m, v = self._query(xs, True, True)
+        return Normal(m, v ** 0.5)
+
+
+def toeplitz_posterior(fx: "FiniteGP", y) -> ToeplitzPosterior:
+    """posterior(fx, y) of the models toeplitz_logpdf serves, as a reusable object: one Schur recursion per latent conditions on the
+    data, and post.mean_and_var(xs) then answers at any new inputs without it.  post.logpdf is bitwise toeplitz_logpdf(fx, y)."""
+    y = _toeplitz_args(fx, y, "toeplitz_posterior")
+    f, x = fx.f, fx.x
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    ptr, out = C.c_void_p(), C.c_double()
+    L.check(L.load().lmm_oilmm_toeplitz_posterior_create(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2),
+                                                         gps, 0, m, C.byref(ptr), C.byref(out)))
+    return ToeplitzPosterior(ptr, x.n, p, out.value)
+
+
 def statespace_rand(rng, fx: "FiniteGP", y=None, N: Optional[int] = None, add_noise: bool = True, xs=None):
     """Joint samples of the same models in O(n), exact: of the prior fx (y=None: rand(rng, fx)), or of the posterior given y
     (rand(rng, posterior(fx, y)(x*, sigma2))) at the training inputs (xs=None) or at the new inputs xs ((ns,); merged into the inputs
