@@ -1157,6 +1157,26 @@ int lmm_dev_emul_plan(int NR, int NC, int nb, long long* out, int cap);
 #define LMM_POTRF_PLAN_HEADER 8
 #define LMM_POTRF_PLAN_STEP 14
 int lmm_dev_potrf_plan(int NR, int NC, int nb, int rows_real, int in_flight, int cus, int f32, int strict, long long* out, int cap);
+/* Test hook: where the row maxima of the screened f64 updates and the emulated updates of a factorisation come from.  source != 0, the
+ * default: one array of block maxima per factorisation -- max |L[r, 128 c .. 128 c + 127]| per row r and 128-column block c -- that the
+ * region launches' row tasks write as they store their panels and a scan fills for any other block, once; an update's row maxima are
+ * a fold over the blocks of its panel.  source = 0: every update scans its panel (what earlier updates kept apart,
+ * lmm_dev_set_emul_amax_reuse) and the region launches store nothing.  Results do not depend on it. */
+int lmm_dev_set_bmax_source(int source);
+/* Test hook: on != 0 makes every factorisation copy its block-maximum array to the host when its launches are issued (that synchronises
+ * its stream); on = 0 stops that and drops the copy after this call.  dims (may be NULL): matrices, 128-column blocks and rows of the
+ * array of the LAST factorisation of this process (0 blocks: it had none); out (may be NULL when cap = 0): its words,
+ * out[(m blocks + c) rows + r] = max |L[r, 128 c .. 128 c + 127]| of matrix m as the bit pattern of a double, for every (c, r) that
+ * lmm_dev_potrf_block_writers lists with a writer whose first row is at most r; unspecified elsewhere.  Returns the number of words
+ * (those beyond cap are counted, not written), or -LMM_ERR_ARG. */
+long long lmm_dev_potrf_block_maxima(int on, unsigned long long* out, long long cap, int dims[3]);
+/* Host-only (no GPU, no lmm_init needed): who writes the block maxima in the plan that lmm_dev_potrf_plan describes (the same first
+ * eight arguments), under the current switches.  5 words per record, in step order: [0] the step's index in that plan, [1] the 128-column
+ * block, [2] the index of the step that writes the block's words -- the step itself when it scans the block, or stores it as a region
+ * launch -- [3] the first row the writer's words cover, [4] the first row the step reads (= [3] in a writer's own record).  One record
+ * per block of the panel of every step that folds block maxima, and per block a region launch stores.  Returns the number of records
+ * (those beyond cap are counted, not written), or -LMM_ERR_ARG. */
+int lmm_dev_potrf_block_writers(int NR, int NC, int nb, int rows_real, int in_flight, int cus, int f32, int strict, long long* out, int cap);
 /* Test hook: the emulation's GEMM is a persistent kernel of min(work items, CUs) workgroups; wgs >= 1 caps that grid (a small shape
  * then makes one workgroup walk several tiles), 0 goes back to the default.  Results do not depend on it. */
 int lmm_dev_set_emul_gemm_workgroups(int wgs);
@@ -1250,6 +1270,10 @@ int lmm_dev_zero_extent_stats(int on, int* out, int cap);
 /* lmm_dev_potrf with the caller's zero extents: zext (device, nrows / 64 ints) holds, per block of 64 rows, a number of leading
  * columns in which all entries of those rows are +0 -- the true extents or any smaller values.  NULL: exactly lmm_dev_potrf. */
 int lmm_dev_potrf_zext(double* A, int nrows, int ncols, int ld, double* Winv, int n_real, int* info_dev, const int* zext);
+/* lmm_dev_potrf_zext for nb (1 .. the batch limit) matrices factored by the same launches, as the per-latent paths factor a batch:
+ * matrix j at A + j * ld * ncols, its inverse diagonal blocks at Winv + j * (ncols / 64) * 4096, its info at info_dev + j, its zero
+ * extents at zext + j * (nrows / 64) (zext may be NULL: nothing is left out).  A non-positive pivot stays in info_dev[j]. */
+int lmm_dev_potrf_batch(double* A, int nb, int nrows, int ncols, int ld, double* Winv, int n_real, int* info_dev, const int* zext);
 /* The training Gram launch of the per-latent logpdf for nb latents on device memory: matrix j (nrows x ncols, leading dimension ld,
  * nrows and ncols multiples of 64, ncols >= n) at A + j * ld * ncols = K_j(x, x) + noise[j] I (or + diag(noisevec[j][.]), device,
  * when noisevec is given), the identity on the padding, rows ncols .. ncols + nrider - 1 = rider[j][r][.] (device).  zext (host,

@@ -822,6 +822,10 @@ static std::vector<int> g_f64_screen_last;
 // lmm_dev_zero_extent_stats: likewise, the void work items of every step that takes the zero extents (kind, j0, h, N, M, count, shape word)
 static int g_zero_ext_stats = 0;
 static std::vector<int> g_zero_ext_last;
+// lmm_dev_potrf_block_maxima: with g_bmax_readback on, every factorisation ends by copying its block maxima here ([matrix][block][NR]; dims: matrices, blocks, NR)
+static int g_bmax_readback = 0;
+static std::vector<unsigned long long> g_bmax_last;
+static int g_bmax_dims[3] = {0, 0, 0};
 inline int sw_region_cols() { return factor_switches().region; }      // widest block column of one region launch (LMM_REGION; 0: off)
 // `bytes` of call scratch, a multiple of 8 as scratch_round makes them (lmm_potrf_plan.h); nullptr for none
 template <class T> T* scratch_bytes(size_t bytes) { return bytes ? reinterpret_cast<T*>(call_scratch(bytes / 8)) : nullptr; }
@@ -922,7 +926,8 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
   if (scr_stat) HIPCHK(hipMemsetAsync(scr_stat, 0, nsteps * 2 * sizeof(int), st));
   void* emul_aux_blk = scratch_bytes<void>(P.emul_aux_bytes);
   void* emul_screen_blk = scratch_bytes<void>(P.emul_screen_bytes);
-  unsigned long long* emul_bmax = scratch_bytes<unsigned long long>(P.emul_bmax_bytes);
+  unsigned long long* emul_bmax = scratch_bytes<unsigned long long>(P.bmax_bytes);      // the factorisation's block maxima (plan_block_maxima)
+  guard_extent(emul_bmax, P.bmax_bytes / 8, P.bmax_bytes / 8, 1, false, "factorisation (block maxima)");
   int* zx_stat = scratch_bytes<int>(P.zext_stat_bytes);
   if (zx_stat) HIPCHK(hipMemsetAsync(zx_stat, 0, nsteps * sizeof(int), st));
   std::vector<int> region_n128(nsteps, 0);
@@ -930,7 +935,7 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
   // the step's kept array, and the earlier steps' arrays its cover reads
   auto keep_of = [&](int si, unsigned long long* bmax, int ncb) {
     const PotrfStep& s = P.steps[si];
-    EmulAmaxKeep keep{amax_kept[si], NR, s.j0 + s.h, s.cover.n, {}, s.cover.scan0 - s.j0, bmax, s.j0 / 128, ncb};
+    EmulAmaxKeep keep{amax_kept[si], NR, s.j0 + s.h, s.cover.n, {}, s.cover.scan0 - s.j0, bmax, s.j0 / 128, ncb, s.bmax_from.empty() ? nullptr : s.bmax_from.data()};
     for (int q = 0; q < s.cover.n; ++q) keep.src[q] = amax_kept[s.cover.step[q]];
     return keep;
   };
@@ -951,7 +956,7 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
         if (s.screened) {
           guard_extent(scr_flags, s.flag_bytes / 8, s.flag_bytes / 8, 1, false, "screened update (tile flags)");
           guard_extent(scr_stat, nsteps, nsteps, 1, false, "screened update (counters)");
-          HIPCHK(launch_f64_screen(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, s.strip, B.nb, keep_of(si, nullptr, 0), scr_flags, scr_stat + 2 * si,
+          HIPCHK(launch_f64_screen(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, s.strip, B.nb, s.bmax_from.empty() ? keep_of(si, nullptr, 0) : keep_of(si, emul_bmax, P.bmax_ncb), scr_flags, scr_stat + 2 * si,
                                    s.vote_from >= 0 ? scr_stat + 2 * s.vote_from : nullptr, st, zx_of(si), r0));
         }
         launch_update_leaf(B.A, B.W, W2, B.info, ld, NR, j0, s.h, s.N, n_real, B.nb, st, s.strip, s.fused_bulk ? nflags : nullptr, (int)P.node_flag_ints,
@@ -960,12 +965,21 @@ void potrf_batch(const Batch& B, int ld, int NR, int NC, int n_real, hipStream_t
       case POTRF_EMUL_UPDATE_LEAF: {
         guard_extent(emul_blk, s.scratch / 8, s.scratch / 8, 1, false, "emulated update (scratch)");
         guard_extent(emul_screen_blk, s.screen_bytes / 8, s.screen_bytes / 8, 1, false, "emulated update (screen)");
-        const EmulAmaxKeep keep = keep_of(si, emul_bmax, P.emul_ncb);
+        const EmulAmaxKeep keep = keep_of(si, emul_bmax, P.bmax_ncb);
         HIPCHK(launch_emul_update(B.A, (size_t)r0 * ld + r0, ld, B.A, offA, ld, s.M, s.N, s.h, B.nb, s.group, P.emul_nmod, emul_blk, emul_aux_blk, emul_screen_blk, st, &keep, zx_of(si), r0));
         leaf128(r0);
         break;
       }
-      case POTRF_REGION: region_n128[si] = launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst, zx_of(si)); break;
+      case POTRF_REGION: region_n128[si] = launch_region(B.A, B.W, W2, B.info, flags, ld, NR, j0, s.N, n_real, B.nb, s.first_done, st, rows_real, &asst, zx_of(si),
+                                                       s.emits_bmax ? emul_bmax : nullptr, P.bmax_ncb); break;
+    }
+  }
+  if (g_bmax_readback) {         // test hook only: the block maxima as the launches left them
+    g_bmax_last.assign(P.bmax_bytes / 8, 0ull);
+    g_bmax_dims[0] = B.nb; g_bmax_dims[1] = P.bmax_ncb; g_bmax_dims[2] = NR;
+    if (emul_bmax) {
+      HIPCHK(hipMemcpyAsync(g_bmax_last.data(), emul_bmax, P.bmax_bytes, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
     }
   }
   if (g_f64_screen_stats)        // test hook only
@@ -1083,7 +1097,9 @@ void batch_plan(int ms, int* nb_per, int* nstreams_used, double bytes_per_latent
       // potrf_batch makes; the shape is the square one of this working set, n = sqrt(bytes / 8) rounded up to whole panels, with one
       // 64-row block of riders)
       const int nce = (int)rup((size_t)std::sqrt(bytes_per_latent / 8.0), 128);
-      const double per_stream = g_f32 ? 0.0 : emul_stream_budget(emul_view(nce + 64, nce, b), nce + 64, nce, b);
+      // -- or, when only screened f64 steps scan, the block maxima alone (bmax_stream_budget)
+      const PotrfPlan view = emul_view(nce + 64, nce, b);
+      const double per_stream = g_f32 ? 0.0 : emul_stream_budget(view, nce + 64, nce, b) + bmax_stream_budget(view, nce + 64, nce, b);
       while ((double)b * ns * bytes_per_latent + ns * per_stream > budget && (b > 1 || ns > 1)) {
         if (b > 1) b = (b + 1) / 2; else --ns;
         nbatches = (ms + b - 1) / b;
@@ -6878,6 +6894,31 @@ int lmm_dev_potrf_zext(double* A, int nrows, int ncols, int ld, double* Winv, in
   LMM_CATCH
 }
 
+// lmm_dev_potrf_zext for a batch: nb matrices in lock-step through the same launches (matrix j at A + j * ld * ncols, W, info and the
+// extents likewise), so that the per-matrix strides of the scratch arrays -- block maxima, row maxima, tile flags -- are reached the
+// way the per-latent paths reach them.
+int lmm_dev_potrf_batch(double* A, int nb, int nrows, int ncols, int ld, double* Winv, int n_real, int* info_dev, const int* zext) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!A || !Winv || !info_dev || nb < 1 || nb > LMM_MAX_BATCH || nrows % 64 || ncols % 64 || nrows < ncols || ld < nrows || (ld & 1))
+    return fail(LMM_ERR_ARG, "bad arguments");
+  hipStream_t st = g.streams[0];
+  int* zx = zext ? zero_ext_scratch(nrows, nb, st) : nullptr;
+  for (int j = 0; zx && j < nb; ++j)
+    HIPCHK(hipMemcpyAsync(zx + (size_t)j * zero_ext_ld(nrows), zext + (size_t)j * (nrows / 64), (size_t)(nrows / 64) * sizeof(int), hipMemcpyDeviceToDevice, st));
+  Batch B;
+  for (int j = 0; j < nb; ++j) B.add(A + (size_t)j * ld * ncols, Winv + (size_t)j * (ncols / 64) * 4096, info_dev + j);
+  potrf_batch(B, ld, nrows, ncols, n_real, st, -1, zx);
+  std::vector<int> hinfo(nb, 0);
+  HIPCHK(hipMemcpyAsync(hinfo.data(), info_dev, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int j = 0; j < nb; ++j)
+    if (hinfo[j] == LMM_INFO_SYNC_TIMEOUT) return check_info(&hinfo[j], 1, 0);
+  return LMM_OK;
+  LMM_CATCH
+}
+
 // The training Gram launch of the per-latent path (latent_lmls: train_gram_args, one batched launch per run of equal kinds) for nb
 // latents gp[0 .. nb) on the caller's device memory: matrix j (nrows x ncols, ld; nrows, ncols multiples of 64, ncols >= n) at
 // A + j * ld * ncols with the diagonal term noise[j] -- or noisevec (device, [nb][n]) -- and the nrider rider rows rider[j] (device,
@@ -7121,6 +7162,60 @@ int lmm_dev_set_emul_amax_reuse(int on) {
   g.err.clear();
   g_switches.emul_amax_reuse = on ? 1 : 0;
   return LMM_OK;
+}
+// Test hook: where the scanning updates' row maxima come from (FactorSwitches.bmax_source).  0: every update scans its panel as its
+// cover says and the region launches store nothing; 1, the default: the region launches' row tasks store the block maxima of what
+// they write, any other block is scanned once, and an update's row maxima are a fold over its blocks.  Results do not depend on it.
+int lmm_dev_set_bmax_source(int source) {
+  g.err.clear();
+  (void)factor_switches();
+  g_switches.bmax_source = source ? 1 : 0;
+  return LMM_OK;
+}
+// Test hook: on != 0 makes every factorisation copy its block-maximum array to the host when its launches are issued (that
+// synchronises its stream).  dims (may be NULL): matrices, 128-column blocks and rows of the LAST factorisation's array; out (may be
+// NULL when cap = 0): its words, out[(m blocks + c) rows + r] = the bit pattern of max |L[r, 128 c .. 128 c + 127]| of matrix m where
+// lmm_dev_potrf_block_writers names a writer whose rows reach r, unspecified elsewhere.  Returns the number of words (those beyond
+// cap are counted, not written).
+long long lmm_dev_potrf_block_maxima(int on, unsigned long long* out, long long cap, int dims[3]) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (cap < 0 || (cap > 0 && !out)) return -fail(LMM_ERR_ARG, "lmm_dev_potrf_block_maxima: bad arguments");
+  g_bmax_readback = on ? 1 : 0;
+  if (dims) for (int q = 0; q < 3; ++q) dims[q] = g_bmax_dims[q];
+  const long long n = (long long)g_bmax_last.size();
+  for (long long i = 0; i < n && i < cap; ++i) out[i] = g_bmax_last[i];
+  if (!on) { g_bmax_last.clear(); g_bmax_last.shrink_to_fit(); }
+  return n;
+}
+// Host-only (no GPU, no lmm_init needed): who writes the block maxima, for the plan lmm_dev_potrf_plan describes (same arguments).
+// 5 words per (step, block): for every step that folds block maxima and every 128-column block of its panel -- the step's index, the
+// block, the writer's step index (the step's own: it scans the block), the first row the writer's words cover, the first row the
+// step reads; and for every region launch that stores block maxima one record per block it holds, with itself as the writer and
+// the reader's row = the writer's.  In step order.  Returns the number of records (those beyond cap are counted, not written), or
+// -LMM_ERR_ARG; a plan that violates an invariant of plan_potrf_check returns -LMM_ERR_ARG too.
+int lmm_dev_potrf_block_writers(int NR, int NC, int nb, int rows_real, int in_flight, int cus, int f32, int strict, long long* out, int cap) {
+  g.err.clear();
+  if ((cap > 0 && !out) || cap < 0 || nb < 1 || nb > LMM_MAX_BATCH || NC < 64 || (NC % 64) != 0 || (NR % 64) != 0 || NR < NC || rows_real > NR || rows_real < -1 ||
+      (rows_real >= 0 && rows_real < NC) || in_flight < 1 || cus < 1)
+    return -fail(LMM_ERR_ARG, "lmm_dev_potrf_block_writers: bad arguments");
+  const PotrfPlan P = plan_potrf(NR, NC, nb, rows_real, in_flight, cus, f32 != 0, false, strict != 0, true, factor_switches());
+  if (const PotrfViolation v = plan_potrf_check(P, NR)) return -fail(LMM_ERR_ARG, "lmm_dev_potrf_block_writers: step %d: %s", v.step, potrf_invariant_text(v.which));
+  int n = 0;
+  auto put = [&](long long step, long long cb, long long writer, long long wrow, long long rrow) {
+    if (n < cap) { long long* r = out + 5 * (size_t)n; r[0] = step; r[1] = cb; r[2] = writer; r[3] = wrow; r[4] = rrow; }
+    ++n;
+  };
+  for (int i = 0; i < (int)P.steps.size(); ++i) {
+    const PotrfStep& s = P.steps[i];
+    if (s.kind == POTRF_REGION && s.emits_bmax)
+      for (int cb = s.j0 / 128; cb < std::min(P.bmax_ncb, (s.j0 + s.N) / 128); ++cb) put(i, cb, i, s.j0 + s.N, s.j0 + s.N);
+    for (int q = 0; q < (int)s.bmax_from.size(); ++q) {
+      const int t = s.bmax_from[q] < 0 ? i : s.bmax_from[q];
+      const PotrfStep& e = P.steps[t];
+      put(i, s.j0 / 128 + q, t, e.kind == POTRF_REGION ? e.j0 + e.N : e.j0 + e.h, s.j0 + s.h);
+    }
+  }
+  return n;
 }
 // Host-only (no GPU, no lmm_init needed): the emulation side of the plan potrf_batch makes for nb matrices of NR rows and NC columns.
 // out[0] = bytes of the scratch block it asks for (0: nothing is emulated), out[1] = the G that block is sized for; then 6 words per

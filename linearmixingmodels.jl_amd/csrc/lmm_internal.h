@@ -134,6 +134,9 @@ struct RegionArgs {
   int claim_scramble;     // test hook (lmm_dev_claim_scramble): workgroups ask for the indices in REVERSE order, as if dispatched last-first
   // zero extents (as in NodeArgs): a row task whose rows are zero across the block column returns before its first wait; zstat counts them
   const int* zext; int zext_ld; int* zstat;
+  // block maxima (lmm_potrf_plan.h, plan_block_maxima; nullptr: none are stored): bmax[((size_t)b bmax_ncb + c) (c0 + M) + r] = max |X[r, 128 c .. + 127]|
+  // as a bit pattern, stored by the row task that owns row r for every panel of the block column, void and padding tasks included
+  unsigned long long* bmax; int bmax_ncb;
 };
 // The zero extents of a batch as the launchers take them (lmm_emul.h): matrix b's at p + b * ld, one int per 64-row block from matrix
 // row 0 and LMM_ZERO_EXT_PAD more; stat (may be nullptr): this step's counter of void work items.  p == nullptr: none, nothing is left out.
@@ -165,7 +168,7 @@ size_t region_flag_ints(int NR);          // ints per matrix that the flags of a
 // returns the number of 128-row row tasks of the launch (the following row tasks are 64 rows high)
 int launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, const BatchInfo& flags, int ld, int NR,
                    int c0, int width, int n_real, int nb, bool first_done, hipStream_t st, int rows_real = -1, const BatchPtr* S = nullptr,
-                   const ZeroExt& zx = ZeroExt());
+                   const ZeroExt& zx = ZeroExt(), unsigned long long* bmax = nullptr, int bmax_ncb = 0);
 void launch_leaf128(const BatchPtr& A, size_t offD, int ld, const BatchPtr& W, size_t offW, const BatchPtr& W2, size_t offW2,
                     int gcol0, int n_real, const BatchInfo& info, int nb, hipStream_t st);
 // bulk rows of the panel at column r0 (its diagonal block factored, its inverse in W2): X = P Dinv' in place
@@ -197,7 +200,10 @@ void emul_set_zero_skip(int on);             // 0: the GEMM walks every K block 
 // aux: emul_aux(M, G, K).total bytes (lmm_emul.h) for the live K blocks and the dead pieces of one group's panels; without a keep,
 // .total_bmax bytes: the group's block maxima follow them.  screen: emul_screen_layout(M, N, G, nmod).total bytes for the tile flags,
 // the live id list and its counts.
-struct EmulAmaxKeep { unsigned long long* out; int ld, row0, n; const unsigned long long* src[LMM_EMUL_COVER_MAX]; int scan0; unsigned long long* bmax; int cb0, ncb; };
+// bfrom (host side only; nullptr: src and scan0 decide): the plan's PotrfStep.bmax_from, one entry per 128-column block of the panel --
+// the blocks marked -1 are scanned into bmax, the others are there already (a region launch's row tasks or an earlier scan wrote them,
+// over rows that contain this step's), and `out` becomes the fold over all of them.
+struct EmulAmaxKeep { unsigned long long* out; int ld, row0, n; const unsigned long long* src[LMM_EMUL_COVER_MAX]; int scan0; unsigned long long* bmax; int cb0, ncb; const int* bfrom; };
 hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int nb,
                               int G, int nmod, void* scratch, void* aux, void* screen, hipStream_t st, const EmulAmaxKeep* keep = nullptr,
                               const ZeroExt& zx = ZeroExt(), int zrow0 = 0);      // the first HIP error of its host-side calls

@@ -2803,13 +2803,38 @@ __device__ __forceinline__ void potrf_region_assistant(const RegionArgs& a, doub
   }
 }
 
+// Block maxima of a row task's outputs (RegionArgs.bmax; lmm_potrf_plan.h, plan_block_maxima).  A row task owns its rows, and a
+// 128-column panel of the block column is one block of the array, so the word of (row, panel) is one plain store by the task that
+// holds the panel's tile in registers: |x| as a bit pattern, compared as an integer (a NaN orders above everything, which v_max_f64
+// would drop), reduced over the registers of a lane, over the lanes that share a row (16 and 32 apart) and, through bmx, over the
+// waves that share it.  Only in the one-workgroup-per-CU build (EMIT), behind a branch that is uniform over the launch.
+__device__ __forceinline__ unsigned long long region_abs_bits(double x) { return (unsigned long long)__double_as_longlong(x) & 0x7FFFFFFFFFFFFFFFull; }
+__device__ __forceinline__ unsigned long long region_max_lk(unsigned long long m) {      // over the four lanes l15 + 16 lk
+  m = max(m, __shfl_xor(m, 16));
+  return max(m, __shfl_xor(m, 32));
+}
+__device__ __forceinline__ unsigned long long* region_bmax_at(const RegionArgs& a, int b, size_t row_j, size_t row) {
+  return a.bmax + ((size_t)b * a.bmax_ncb + row_j / 128) * (size_t)(a.c0 + a.M) + row;
+}
+// A task that computes nothing -- its rows are zero padding, or void by the zero extents -- stores the zeros its rows hold
+__device__ __forceinline__ void region_row_zero_bmax(const RegionArgs& a, int b, int roff, int height) {
+  if (a.bmax == nullptr) return;
+  const int t = threadIdx.x;
+  if (t >= height || roff + t >= a.M) return;
+  for (int tj = 0; tj < a.P; ++tj) {
+    const size_t row_j = (size_t)a.c0 + 128 * (size_t)tj;
+    if ((int)(row_j / 128) < a.bmax_ncb) *region_bmax_at(a, b, row_j, (size_t)a.c0 + roff + t) = 0ull;
+  }
+}
+
 // ROW task of potrf_region_kernel: row tile i >= P of matrix b (128 rows below the square, riders included), columns j = 0 .. P-1
 // left to right.  It consumes only the square's rows 2j, 2j+1 (final through block column 2j - 1) and the panel inverses, produces
 // only its own row -- which nobody else reads inside this launch -- so it signals nothing: no release fence, no flag traffic beyond
 // 3 P waits.
 //   column j:  acc = X[i, 0:j] X[j, 0:j]'  as ONE pass over K = 128 j (own earlier outputs + the square's rows);  C[i, j] -= acc;
 //              wait Dinv_j;  X[i, j] = C[i, j] Dinv_j'.
-__device__ __forceinline__ void potrf_region_row(const RegionArgs& a, double* __restrict__ lds, double* __restrict__ Am, int b, int ti) {
+template <bool EMIT>
+__device__ __forceinline__ void potrf_region_row(const RegionArgs& a, double* __restrict__ lds, double* __restrict__ Am, int b, int ti, unsigned long long* __restrict__ bmx) {
   int* abort_word = a.flags.p[b];
   int* wk = abort_word + 1; int* trs = abort_word + 2; int* dinv = abort_word + 34;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -2864,13 +2889,32 @@ __device__ __forceinline__ void potrf_region_row(const RegionArgs& a, double* __
           for (int r = 0; r < 4; ++r) cpv[(size_t)(4 * r) * a.ld + 16 * u] = acc[v][u][r];
       }
     }
+    const bool emit = EMIT && a.bmax != nullptr && (int)(row_j / 128) < a.bmax_ncb;      // uniform
+    unsigned long long bm[4] = {0ull, 0ull, 0ull, 0ull};
+    if (emit && active) {      // rows wr + l15 + 16 u; this lane holds the columns wc + 16 v + lk + 4 r, the waves wc = 0 and 64 a half each
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) bm[u] = max(bm[u], region_abs_bits(acc[v][u][r]));
+        bm[u] = region_max_lk(bm[u]);
+        if (wc != 0 && lk == 0) bmx[wr + l15 + 16 * u] = bm[u];
+      }
+    }
     __syncthreads();                                               // X[i, j] is in memory for this workgroup's own later passes
+    if (emit && active && wc == 0 && lk == 0) {
+      unsigned long long* bp = region_bmax_at(a, b, row_j, row_i + wr + l15);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) bp[16 * u] = max(bm[u], bmx[wr + l15 + 16 * u]);      // (the next write of bmx lies behind the barriers of the next pass)
+    }
   }
 }
 
 // The same row task on a 64-row tile (rows c0 + roff .. + 63 of matrix b): half the work per workgroup, twice the workgroups -- for
 // launches whose 128-row tiles leave CUs idle or come to a little more than a whole number of waves (launch_region's rule).
-__device__ __forceinline__ void potrf_region_row64(const RegionArgs& a, double* __restrict__ lds, double* __restrict__ Am, int b, int roff) {
+template <bool EMIT>
+__device__ __forceinline__ void potrf_region_row64(const RegionArgs& a, double* __restrict__ lds, double* __restrict__ Am, int b, int roff, unsigned long long* __restrict__ bmx) {
   int* abort_word = a.flags.p[b];
   int* wk = abort_word + 1; int* trs = abort_word + 2; int* dinv = abort_word + 34;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -2918,7 +2962,21 @@ __device__ __forceinline__ void potrf_region_row64(const RegionArgs& a, double* 
 #pragma unroll
         for (int r = 0; r < 4; ++r) cpv[(size_t)(4 * r) * a.ld + 16 * u] = acc[v][u][r];
     }
+    const bool emit = EMIT && a.bmax != nullptr && (int)(row_j / 128) < a.bmax_ncb;      // uniform
+    if (emit) {                // rows l15 + 16 u; wave w holds the columns 32 w .. 32 w + 31: a quarter each
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        unsigned long long m = 0ull;
+#pragma unroll
+        for (int v = 0; v < 2; ++v)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) m = max(m, region_abs_bits(acc[v][u][r]));
+        m = region_max_lk(m);
+        if (lk == 0) bmx[64 * w + l15 + 16 * u] = m;
+      }
+    }
     __syncthreads();                                               // X[i, j] is in memory for this workgroup's own later passes
+    if (emit && t < 64) *region_bmax_at(a, b, row_j, row_i + t) = max(max(bmx[t], bmx[64 + t]), max(bmx[128 + t], bmx[192 + t]));
   }
 }
 
@@ -2933,7 +2991,9 @@ __device__ __forceinline__ void potrf_region_row64(const RegionArgs& a, double* 
 //                                                    Dinv is lower triangular: wave w stops at k = 32 (w + 1).
 // Rows 16 .. of the tile are padding (zeros before and after).  Nothing is published: nobody reads a row stream inside the launch.
 struct ThinChunk { double fb[8], fa[8][2]; };
-__device__ __forceinline__ void potrf_region_row_thin(const RegionArgs& a, double* __restrict__ lds, double* __restrict__ Am, int b, int roff) {
+template <bool EMIT>
+__device__ __forceinline__ void potrf_region_row_thin(const RegionArgs& a, double* __restrict__ lds, double* __restrict__ Am, int b, int roff, int height,
+                                                      unsigned long long* __restrict__ bmx) {
   int* abort_word = a.flags.p[b];
   int* wk = abort_word + 1; int* trs = abort_word + 2; int* dinv = abort_word + 34;
   int* info = a.info.p[b];
@@ -3012,7 +3072,19 @@ __device__ __forceinline__ void potrf_region_row_thin(const RegionArgs& a, doubl
     for (int v = 0; v < 2; ++v)
 #pragma unroll
       for (int r = 0; r < 4; ++r) Am[(row_j + 32 * w + 16 * v + 4 * r + lk) * a.ld + row_i + l15] = xo[v][r];
+    const bool emit = EMIT && a.bmax != nullptr && (int)(row_j / 128) < a.bmax_ncb;      // uniform
+    if (emit) {                // row l15; wave w holds the panel columns 32 w .. 32 w + 31
+      unsigned long long m = 0ull;
+#pragma unroll
+      for (int v = 0; v < 2; ++v)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m = max(m, region_abs_bits(xo[v][r]));
+      m = region_max_lk(m);
+      if (lk == 0) bmx[16 * w + l15] = m;
+    }
     __syncthreads();                                     // X[i, j] is in memory for this workgroup's own later passes
+    if (emit && t < height && roff + t < a.M)            // the tile's rows 16 .. are zero padding
+      *region_bmax_at(a, b, row_j, row_i + t) = t < 16 ? max(max(bmx[t], bmx[16 + t]), max(bmx[32 + t], bmx[48 + t])) : 0ull;
   }
 }
 
@@ -3028,6 +3100,7 @@ template <int OCC, bool STRICT = false>
 __global__ __launch_bounds__(256, OCC) void potrf_region_kernel(RegionArgs a) {
   extern __shared__ __attribute__((aligned(16))) double node_lds[];
   __shared__ int dflags[3];                  // the walker's two-wave diagonal-block factorisation (zero before the walker's first barrier)
+  __shared__ unsigned long long bmx[256];    // the row tasks' block maxima, between the waves that share a row
   if (threadIdx.x == 0) { dflags[0] = 0; dflags[1] = 0; dflags[2] = 0; }
   const int b = blockIdx.x % a.nb;
   int idx = blockIdx.x / a.nb;
@@ -3068,9 +3141,11 @@ __global__ __launch_bounds__(256, OCC) void potrf_region_kernel(RegionArgs a) {
     }
     if (zvoid) {
       if (a.zstat != nullptr && threadIdx.x == 0) atomicAdd(a.zstat, 1);
+      region_row_zero_bmax(a, b, roff, tall ? 128 : 64);
     } else
-    if (real > 16) { if (tall) potrf_region_row(a, node_lds, Am, b, a.P + k); else potrf_region_row64(a, node_lds, Am, b, roff); }
-    else if (real > 0) potrf_region_row_thin(a, node_lds, Am, b, roff);
+    if (real > 16) { if (tall) potrf_region_row<OCC == 1>(a, node_lds, Am, b, a.P + k, bmx); else potrf_region_row64<OCC == 1>(a, node_lds, Am, b, roff, bmx); }
+    else if (real > 0) potrf_region_row_thin<OCC == 1>(a, node_lds, Am, b, roff, tall ? 128 : 64, bmx);
+    else if (OCC == 1) region_row_zero_bmax(a, b, roff, tall ? 128 : 64);
   }
   if (a.trace && threadIdx.x == 0) a.trace[2 * task + 1] = wall_clock64();
 }
@@ -5604,7 +5679,8 @@ void region_plan_probe(int P, int nb, int Mb, int Mb_real, int cus, int na_full,
 }
 size_t region_flag_ints(int) { return REGION_FLAG_INTS; }
 int launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, const BatchInfo& info, const BatchInfo& flags, int ld, int NR,
-                   int c0, int width, int n_real, int nb, bool first_done, hipStream_t st, int rows_real, const BatchPtr* S, const ZeroExt& zx) {
+                   int c0, int width, int n_real, int nb, bool first_done, hipStream_t st, int rows_real, const BatchPtr* S, const ZeroExt& zx,
+                   unsigned long long* bmax, int bmax_ncb) {
   const int P = width / 128, M = NR - c0, R = (M + 127) / 128;
   if (nb <= 0 || P <= 0) return 0;
   node_lds_attr();
@@ -5642,6 +5718,7 @@ int launch_region(const BatchPtr& A, const BatchPtr& W, const BatchPtr& W2, cons
   a.trace = tr; a.ntasks = (int)tasks;
   a.claim_scramble = g_claim_scramble;
   a.zext = zx.p; a.zext_ld = zx.ld; a.zstat = zx.stat;
+  a.bmax = occ == 1 ? bmax : nullptr; a.bmax_ncb = bmax_ncb;      // the plan never asks the two-per-CU build for them (region_emits_bmax)
   if (g_strict_progress && strict_claim_sets(st, &a.claim, &a.claim_next)) {
     if (occ == 1) hipLaunchKernelGGL((potrf_region_kernel<1, true>), dim3((unsigned)(tasks * nb)), dim3(256), LEAF_LDS_DOUBLES * 8, st, a);
     else hipLaunchKernelGGL((potrf_region_kernel<2, true>), dim3((unsigned)(tasks * nb)), dim3(256), LEAF_LDS_DOUBLES * 8, st, a);

@@ -40,21 +40,39 @@ struct EmulBlockMax { unsigned long long* p; size_t zs, ld; };
 
 // One thread per row and K block of 128 columns, for the blocks kb / 128 .. K / 128 - 1 (kb, K multiples of 128): the block's maximum
 // |a_ik| as a bit pattern (order-preserving for non-negative doubles; a NaN is above everything) goes to bm -- one plain store per
-// entry, coalesced over the rows -- and amax[z as + i] = max(what is there, that maximum).  as: entries per matrix of amax.
-// The scans of the f64 updates' screen keep no block maxima (bm.p == nullptr) and obey that screen's vote: a zero there means the
+// entry, coalesced over the rows -- and, with amax != nullptr, amax[z as + i] = max(what is there, that maximum).  as: entries per
+// matrix of amax.  amax == nullptr: the block maxima are all it leaves (emul_bmax_fold_kernel forms the row maxima from them).
+// The scans of the f64 updates' screen that keep no block maxima (bm.p == nullptr) obey that screen's vote: a zero there means the
 // factorisation's data does not decay, and the scan returns at entry (uniform over the grid; nobody reads its array then).
+// zext (may be nullptr; matrix z's extents at zext + z zext_ld, lmm_emul.h): a row whose 64-row block is +0 in every column up to the
+// block's last one -- zrow0 is the matrix row of the panel's row 0, col0 the matrix column of its column 0 -- gets 0 without a load.
 __global__ __launch_bounds__(256) void emul_rowmax_kernel(BatchPtr A, int g0, size_t off, int ld, int M, int as, int kb, unsigned long long* amax, EmulBlockMax bm,
-                                                          const int* __restrict__ vote) {
+                                                          const int* __restrict__ vote, const int* __restrict__ zext, int zext_ld, int zrow0, int col0) {
   if (vote != nullptr && *vote == 0) return;
   const int i = blockIdx.x * 256 + threadIdx.x, z = blockIdx.z;
   if (i >= M) return;
   const int k0 = kb + blockIdx.y * BK;
   const double* P = A.p[g0 + z] + off + i + (size_t)k0 * ld;
   unsigned long long m = 0;
+  if (zext == nullptr || zext[(size_t)(g0 + z) * zext_ld + ((zrow0 + i) >> 6)] < col0 + k0 + BK) {
 #pragma unroll 8
-  for (int k = 0; k < BK; ++k) m = max(m, (unsigned long long)__double_as_longlong(P[(size_t)k * ld]) & ABS_MASK);
+    for (int k = 0; k < BK; ++k) m = max(m, (unsigned long long)__double_as_longlong(P[(size_t)k * ld]) & ABS_MASK);
+  }
   if (bm.p != nullptr) bm.p[(size_t)z * bm.zs + (size_t)(k0 / BK) * bm.ld + i] = m;
-  atomicMax(&amax[(size_t)z * as + i], m);
+  if (amax != nullptr) atomicMax(&amax[(size_t)z * as + i], m);
+}
+// A step's row maxima from the factorisation's block maxima (lmm_potrf_plan.h, plan_block_maxima): out[z as + i] = the largest of the
+// nkb words of row i, bit patterns compared as integers (a NaN or an infinity stays on top).  One thread per row, coalesced over the
+// rows: K = 8192 reads 64 words per row.  vote: as for the scan above -- only the folds of f64 steps are given one.
+__global__ __launch_bounds__(256) void emul_bmax_fold_kernel(EmulBlockMax bm, int nkb, unsigned long long* out, int as, int M, const int* __restrict__ vote) {
+  if (vote != nullptr && *vote == 0) return;
+  const int i = blockIdx.x * 256 + threadIdx.x, z = blockIdx.y;
+  if (i >= M) return;
+  const unsigned long long* b = bm.p + (size_t)z * bm.zs + i;
+  unsigned long long m = 0;
+#pragma unroll 4
+  for (int kb = 0; kb < nkb; ++kb) m = max(m, b[(size_t)kb * bm.ld]);
+  out[(size_t)z * as + i] = m;
 }
 // The first write of an update's kept row maxima: per row the largest of the maxima that earlier updates kept for parts of its panel
 // (bit patterns again, so a NaN or an infinity found then is still there), 0 when there are none.  emul_rowmax_kernel adds the
@@ -716,16 +734,37 @@ void emul_set_gemm_workgroups(int wgs) { g_emul_gemm_wgs = wgs; }
 void emul_set_zero_skip(int on) { g_emul_zero_skip = on < 0 ? -1 : (on ? 1 : 0); }
 void emul_set_scratch_poison(int on) { g_emul_poison = on ? 1 : 0; }
 
+// The row maxima of a step inside a factorisation, into keep.out, and the block maxima it owes to keep.bmax.  keep.bfrom (the plan's
+// PotrfStep.bmax_from): the blocks marked -1 are scanned, run by run, and the row maxima are a fold over all K / 128 blocks; vote
+// switches off that fold only (an f64 step's: its screen is the only reader).  keep.bfrom == nullptr: the fold of the kept arrays of
+// keep.src and a scan of the columns [scan0, K), which obeys the vote when it keeps no block maxima.
+static void launch_row_maxima(const BatchPtr& P, size_t offP, int ldp, int M, int K, int nb, const EmulAmaxKeep& keep, const EmulBlockMax& bm, const int* vote,
+                              hipStream_t st, const ZeroExt& zx, int zrow0) {
+  if (keep.bfrom == nullptr) {
+    emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(keep, M);      // every row's first write: no memset
+    if (keep.scan0 < K)
+      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep.scan0) / BK, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep.ld, keep.scan0, keep.out + keep.row0, bm,
+                                                                                          bm.p == nullptr ? vote : nullptr, nullptr, 0, 0, 0);
+    return;
+  }
+  for (int q = 0; q < K / BK;) {
+    if (keep.bfrom[q] >= 0) { ++q; continue; }
+    int e = q;
+    while (e < K / BK && keep.bfrom[e] < 0) ++e;
+    emul_rowmax_kernel<<<dim3((M + 255) / 256, e - q, nb), 256, 0, st>>>(P, 0, offP, ldp, M, 0, q * BK, nullptr, bm, nullptr, zx.p, zx.ld, zrow0, keep.cb0 * BK);
+    q = e;
+  }
+  emul_bmax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(bm, K / BK, keep.out + keep.row0, keep.ld, M, vote);
+}
+
 hipError_t launch_f64_screen(const BatchPtr& C, size_t offC, int ldc, const BatchPtr& P, size_t offP, int ldp, int M, int N, int K, int strip, int nb,
                              const EmulAmaxKeep& keep, unsigned char* flags, int* stat, const int* vote, hipStream_t st, const ZeroExt& zx, int zrow0) {
   const int Mn = f64_screen_rows(M, strip);
   const int MT = (Mn + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE, NT = (N + LMM_F64_SCREEN_TILE - 1) / LMM_F64_SCREEN_TILE;
-  if (nb <= 0 || MT < 2 || NT < 2 || N > Mn || (K % BK) != 0 || (keep.scan0 % BK) != 0) return hipErrorInvalidValue;
+  if (nb <= 0 || MT < 2 || NT < 2 || N > Mn || (K % BK) != 0 || (keep.scan0 % BK) != 0 || (keep.bfrom != nullptr && keep.bmax == nullptr)) return hipErrorInvalidValue;
   EmulBlockMax bm{};
   if (keep.bmax != nullptr) bm = EmulBlockMax{keep.bmax + (size_t)keep.cb0 * keep.ld + keep.row0, (size_t)keep.ncb * keep.ld, (size_t)keep.ld};
-  emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(keep, M);      // every row's first write: no memset
-  if (keep.scan0 < K)
-    emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep.scan0) / BK, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep.ld, keep.scan0, keep.out + keep.row0, bm, vote);
+  launch_row_maxima(P, offP, ldp, M, K, nb, keep, bm, vote, st, zx, zrow0);
   f64_screen_kernel<<<dim3(MT, NT - 1, nb), LMM_F64_SCREEN_TILE, 0, st>>>(C, offC, ldc, Mn, N, K, keep.out + keep.row0, keep.ld, MT, NT, flags, stat, vote, zx.p, zx.ld, zrow0);
   return hipGetLastError();
 }
@@ -764,9 +803,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
   EmulBlockMax bm{};
   if (keep) {      // every row of every matrix gets its first write from the fold: no memset
     bm = EmulBlockMax{keep->bmax + (size_t)keep->cb0 * keep->ld + keep->row0, (size_t)keep->ncb * keep->ld, (size_t)keep->ld};
-    emul_amax_fold_kernel<<<dim3((M + 255) / 256, nb), 256, 0, st>>>(*keep, M);
-    if (keep->scan0 < K)
-      emul_rowmax_kernel<<<dim3((M + 255) / 256, (K - keep->scan0) / BK, nb), 256, 0, st>>>(P, 0, offP, ldp, M, keep->ld, keep->scan0, keep->out + keep->row0, bm, nullptr);
+    launch_row_maxima(P, offP, ldp, M, K, nb, *keep, bm, nullptr, st, zx, zrow0);
   }
   for (int g0 = 0; g0 < nb; g0 += G) {
     const int gc = std::min(G, nb - g0);
@@ -778,7 +815,7 @@ hipError_t launch_emul_update(const BatchPtr& C, size_t offC, int ldc, const Bat
     else {
       err = hipMemsetAsync(amax, 0, (size_t)gc * L.Mp * 8, st);      // stale row maxima would give wrong scales: stop here
       if (err != hipSuccess) return err;
-      emul_rowmax_kernel<<<dim3((M + 255) / 256, K / BK, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, amax, gbm, nullptr);
+      emul_rowmax_kernel<<<dim3((M + 255) / 256, K / BK, gc), 256, 0, st>>>(P, g0, offP, ldp, M, L.Mp, 0, amax, gbm, nullptr, nullptr, 0, 0, 0);
     }
     unsigned long long* masks = reinterpret_cast<unsigned long long*>(static_cast<char*>(aux) + X.masks);
     unsigned short* dead = skip ? reinterpret_cast<unsigned short*>(static_cast<char*>(aux) + X.pieces) : nullptr;

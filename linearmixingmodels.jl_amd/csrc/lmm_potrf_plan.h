@@ -56,6 +56,11 @@ struct FactorSwitches {
   // columns (`small`) the memset and the per-tile reduction cost 0.3 % and next to nothing is void, at 4096 (C1) the extents gain 17 %
   // (profiles/zero_extents/ab_summary.txt).  A matrix one region launch factors whole has no item that can be void at any setting.
   int zero_extents_min_cols = 2048;
+  // Where the row maxima of the scanning updates come from (plan_block_maxima): 1, the default -- the region launches' row tasks store
+  // the block maxima of what they write, every other block is scanned once, by the first update that needs it, and an update's row
+  // maxima are a fold over its panel's blocks; 0 (lmm_dev_set_bmax_source) -- every update scans as PotrfStep.cover says and the
+  // region launches store nothing.  Results do not depend on it.
+  int bmax_source = 1;
   int f64_screen_rounds = 1; // f64_screen_pays: a screened launch has more work items than this many rounds of 2 per CU (0: no such rule; LMM_F64_SCREEN_ROUNDS)
 };
 
@@ -95,6 +100,9 @@ struct PotrfStep {
   size_t flag_bytes = 0;             // screened: the bytes of the flag block its screen writes (f64_screen_flag_bytes)
   int vote_from = -1;                // screened: the step whose counters carry the vote it listens to (-1: it scans and screens whatever was found)
   size_t screen_bytes = 0;           // EMUL_UPDATE_LEAF: the bytes of the emulation's screen block one of its groups uses (emul_screen_layout)
+  // Block maxima as the only source of row maxima (FactorSwitches.bmax_source, plan_block_maxima):
+  bool emits_bmax = false;           // REGION: its row tasks store the block maxima of the rows below the square, for every panel of the block column
+  std::vector<int> bmax_from;        // keeps_amax: per 128-column block of its panel, the earlier step that wrote it (-1: this step scans it); empty: the cover decides
   // the (M, N, K) ProfScope names: the 64-column path's diagonal blocks and solves go unnamed
   bool named() const { return kind != POTRF_DIAG64 && kind != POTRF_SOLVE64; }
 };
@@ -129,6 +137,9 @@ struct PotrfPlan {
   // a later update that covers them decides its live blocks and pieces from them without reading those columns.  batch_plan budgets
   // the block maxima by emul_stream_budget, which counts all NC / 128 blocks.
   int emul_kmax = 0, emul_ncb = 0; size_t emul_aux_bytes = 0, emul_screen_bytes = 0, emul_bmax_bytes = 0;
+  // The block-maximum array potrf_batch takes: with FactorSwitches.bmax_source on, up to the last column block that the panel of any
+  // scanning step holds, screened f64 steps included (plan_block_maxima); else the emulated steps' array above.
+  int bmax_ncb = 0; size_t bmax_bytes = 0;
   // Zero extents (lmm_emul.h): taken when the caller has them, the matrices are Float64 and FactorSwitches.zero_extents is on; then
   // the caller's array holds zext_bytes, and, when the test hook asks, one counter of void work items per step, zeroed likewise.
   bool zext = false; size_t zext_bytes = 0, zext_stat_bytes = 0;
@@ -342,6 +353,45 @@ inline EmulCover emul_amax_cover(const std::vector<PotrfStep>& steps, int si, bo
   return c;
 }
 
+// ---- block maxima as the only source of row maxima ----
+// ONE array per factorisation, [matrix][128-column block][NR]: word (m, c, r) = max |L[r, 128 c .. 128 c + 127]| of matrix m as a bit
+// pattern, final once the block column that holds block c is factored.  Who writes a block is decided here, once, in step order:
+//   - a region launch writes the blocks of its block column for all rows below its square: its row tasks own those rows and store
+//     one word per row and panel beside the panel itself (PotrfStep.emits_bmax; not in the two-workgroups-per-CU build, LMM_REGION_OCC=2);
+//   - a block no launch has written is scanned by the first scanning step -- a screened f64 update or an emulated one -- whose panel
+//     holds it (bmax_from = -1), for that step's rows;
+//   - every later step takes it (bmax_from = the writer) if the writer's rows begin no later than its own, and scans it again
+//     otherwise (the recursion never asks for that: an update's panel contains the earlier panels it overlaps, so its rows begin lower).
+// A step's row maxima are then a fold over the h / 128 words of each of its rows.  Invariant (POTRF_INV_BMAX_WRITER, plan_potrf_check):
+// NO STEP EVER FOLDS A WORD THAT NOBODY WROTE -- every writer writes whatever the f64 screen's vote says: the vote switches off folds and
+// screens, which only f64 steps read, never a scan or a region launch's stores, so an emulated step always finds its maxima.
+// (region_occ: 0 = the default, 1 = forced; launch_region stores only in that build, so any other value means no emission)
+inline bool region_emits_bmax(const FactorSwitches& sw) { return sw.bmax_source != 0 && (sw.region_occ == 0 || sw.region_occ == 1); }
+inline void plan_block_maxima(PotrfPlan& P, int NR, int nb, const FactorSwitches& sw) {
+  int ncb = 0;
+  for (const PotrfStep& s : P.steps)
+    if (s.keeps_amax) ncb = std::max(ncb, (s.j0 + s.h) / 128);
+  P.bmax_ncb = ncb;
+  P.bmax_bytes = emul_block_max_bytes(NR, ncb, nb);      // 8-byte words: whole doubles as it is
+  if (ncb == 0) return;
+  std::vector<int> writer(ncb, -1), wrow(ncb, 0);
+  for (int i = 0; i < (int)P.steps.size(); ++i) {
+    PotrfStep& s = P.steps[i];
+    if (s.kind == POTRF_REGION && region_emits_bmax(sw) && (s.j0 % 128) == 0 && (NR % 64) == 0 && s.j0 / 128 < ncb && s.M > s.N) {
+      s.emits_bmax = true;
+      for (int cb = s.j0 / 128; cb < std::min(ncb, (s.j0 + s.N) / 128); ++cb) { writer[cb] = i; wrow[cb] = s.j0 + s.N; }
+    } else if (s.keeps_amax) {
+      s.bmax_from.assign(s.h / 128, -1);
+      for (int q = 0; q < s.h / 128; ++q) {
+        const int cb = s.j0 / 128 + q;
+        if (cb >= ncb) continue;
+        if (writer[cb] >= 0 && wrow[cb] <= s.j0 + s.h) s.bmax_from[q] = writer[cb];
+        else { writer[cb] = i; wrow[cb] = s.j0 + s.h; }
+      }
+    }
+  }
+}
+
 // ---- the factorisation's scratch and the steps' wiring to it ----
 // The scratch allocator counts in doubles, so every array is requested in whole doubles.  scratch_round is the ONE place that rounds:
 // a *_bytes field of the plan is the bytes actually requested, a multiple of 8, and potrf_batch asks for bytes / 8 doubles.
@@ -377,6 +427,8 @@ inline void plan_potrf_finish(PotrfPlan& P, int NR, int nb, bool f32, bool zext,
     P.emul_aux_bytes = scratch_round(emul_aux(NR, nb, P.emul_kmax).total);
     P.emul_bmax_bytes = scratch_round(emul_block_max_bytes(NR, P.emul_ncb, nb));
   }
+  if (sw.bmax_source != 0) plan_block_maxima(P, NR, nb, sw);
+  else { P.bmax_ncb = P.emul_ncb; P.bmax_bytes = P.emul_bmax_bytes; }
   P.zext = zext && !f32 && sw.zero_extents != 0;
   if (P.zext) P.zext_bytes = scratch_ints((size_t)zero_ext_ld(NR) * nb);
   if (P.zext && zext_counters) P.zext_stat_bytes = scratch_ints((size_t)n);
@@ -386,6 +438,11 @@ inline void plan_potrf_finish(PotrfPlan& P, int NR, int nb, bool f32, bool zext,
 // emul_ncb <= NC / 128, the same formula).  0 when nothing is emulated.
 inline double emul_stream_budget(const PotrfPlan& P, int NR, int NC, int nb) {
   return P.emul_bytes > 0 ? kEmulBlockCap + (double)emul_block_max_bytes(NR, NC / 128, nb) : 0.0;
+}
+// ... and for a plan that emulates nothing but has screened f64 steps, whose folds need the block maxima all the same
+// (plan_block_maxima): the same upper bound, all NC / 128 column blocks.  0 when the term above already holds them, or nothing scans.
+inline double bmax_stream_budget(const PotrfPlan& P, int NR, int NC, int nb) {
+  return P.emul_bytes == 0 && P.bmax_bytes > 0 ? (double)emul_block_max_bytes(NR, NC / 128, nb) : 0.0;
 }
 
 // ---- the extent invariants of a finished plan ----
@@ -399,6 +456,8 @@ enum PotrfInvariant {
   POTRF_INV_EMUL_SCREEN,     // emulated: its screen bytes fit the emulation's screen block
   POTRF_INV_PANEL_BLOCKS,    // emulated: j0, h and scan0 - j0 are whole 128-column blocks (the block maxima are kept per block)
   POTRF_INV_BMAX_BLOCKS,     // emulated: its panel ends within the emul_ncb column blocks of the block maxima
+  POTRF_INV_BMAX_WRITER,     // a step that folds block maxima: every block of its panel lies within bmax_ncb and is scanned here or was written by
+                             // an EARLIER step -- a region launch that emits and holds the block, or a step that scanned it -- whose rows begin no later
   POTRF_INVARIANTS
 };
 struct PotrfViolation {
@@ -409,7 +468,8 @@ struct PotrfViolation {
 inline const char* potrf_invariant_text(int which) {
   static const char* const text[POTRF_INVARIANTS] = {"", "flag bytes of the screened update", "last row of the update against the matrix rows",
     "columns of the screened update against the rows its screen covers", "scratch bytes of the emulated update", "screen bytes of the emulated update",
-    "columns of the emulated update's panel that are not whole 128-column blocks", "last column block of the emulated update's panel against the block maxima"};
+    "columns of the emulated update's panel that are not whole 128-column blocks", "last column block of the emulated update's panel against the block maxima",
+    "writer of a folded block maximum (needs: the block, has: the writer's step, -1 for none that wrote it over these rows)"};
   return which > POTRF_INV_NONE && which < POTRF_INVARIANTS ? text[which] : "";
 }
 // The first violated invariant in step order (nothing: all hold)
@@ -430,6 +490,21 @@ inline PotrfViolation plan_potrf_check(const PotrfPlan& P, int NR) {
       for (int v : {s.j0, s.h, s.cover.scan0 - s.j0})
         if ((v % 128) != 0) return bad(POTRF_INV_PANEL_BLOCKS, v, 128);
       if (r0 / 128 > P.emul_ncb) return bad(POTRF_INV_BMAX_BLOCKS, r0 / 128, P.emul_ncb);
+    }
+    if (!s.bmax_from.empty()) {
+      if ((s.j0 % 128) != 0 || (int)s.bmax_from.size() != s.h / 128 || (s.h % 128) != 0 || r0 / 128 > P.bmax_ncb) return bad(POTRF_INV_BMAX_WRITER, r0 / 128, -1);
+      for (int q = 0; q < (int)s.bmax_from.size(); ++q) {
+        const int t = s.bmax_from[q], cb = s.j0 / 128 + q;
+        if (t < 0) continue;
+        bool ok = t < i;
+        if (ok) {
+          const PotrfStep& e = P.steps[t];
+          const bool holds = e.j0 <= 128 * cb && 128 * cb + 128 <= e.j0 + (e.kind == POTRF_REGION ? e.N : e.h);
+          if (e.kind == POTRF_REGION) ok = e.emits_bmax && holds && e.j0 + e.N <= r0;
+          else ok = !e.bmax_from.empty() && holds && e.bmax_from[cb - e.j0 / 128] < 0 && e.j0 + e.h <= r0;
+        }
+        if (!ok) return bad(POTRF_INV_BMAX_WRITER, cb, t);
+      }
     }
   }
   return PotrfViolation{};
