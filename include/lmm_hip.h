@@ -852,6 +852,23 @@ int lmm_oilmm_logpdf_grad_toeplitz(const double* x, int n, const double* y, int 
                                    lmm_gp_grad_t* grad_gps);
 int lmm_dev_toeplitz_factor(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q);
 int lmm_dev_toeplitz_solve(const double* p, const double* q, const double* r, int n, double* alpha);
+/* Toeplitz, the blocked schedule (DESIGN.md 4.22 "Blocked schedule"): the same recursion with every latent spread over many
+ * workgroups, a fixed number of steps per kernel launch and launches ordered by the stream alone, which serves any
+ * n <= lmm_toeplitz_blocked_max_n() (131072: nothing beyond it has been run; memory is O(n), 9 n doubles of workspace per latent).
+ * Float64, no atomics, bitwise reproducible.  Each *_blocked entry point takes the arguments of the entry point it is named after and
+ * has its outputs, rules and refusals, except that n is held against lmm_toeplitz_blocked_max_n (LMM_ERR_UNSUPPORTED naming it).
+ *   lmm_toeplitz_blocked_shape : the steps of a launch and the rows a workgroup stores (either may be NULL), so that a test can place
+ *                    its sizes on the kernel's boundaries. */
+int lmm_toeplitz_blocked_max_n(void);
+int lmm_toeplitz_blocked_shape(int* steps, int* rows_per_workgroup);
+int lmm_oilmm_logpdf_toeplitz_blocked(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                      double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                      double* out);
+int lmm_oilmm_logpdf_grad_toeplitz_blocked(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                           double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                           double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                                           lmm_gp_grad_t* grad_gps);
+int lmm_dev_toeplitz_factor_blocked(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q);
 /* Toeplitz: the posterior object (DESIGN.md 4.22 "Posterior handle").  What posterior(fx, y) followed by mean_and_var(post(x*, sigma2))
  * is on the dense path, from ONE Schur recursion per latent: the handle keeps the Gohberg-Semencul generators p, q of
  * (K_l + (sigma2 / S_l) I)^-1 and alpha_l = (K_l + (sigma2 / S_l) I)^-1 r_l, and a query at any new inputs is
@@ -877,6 +894,9 @@ typedef struct lmm_toep_post lmm_toep_post_t;
 int lmm_oilmm_toeplitz_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
                                         double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_toep_post_t** out,
                                         double* out_logpdf);
+int lmm_oilmm_toeplitz_posterior_create_blocked(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                                double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                                lmm_toep_post_t** out, double* out_logpdf);
 int lmm_toeplitz_post_destroy(lmm_toep_post_t* post);
 int lmm_oilmm_toeplitz_post_mean_and_var(const lmm_toep_post_t* post, const double* xs, int ns, int add_noise, double* mean, double* var);
 int lmm_dev_toeplitz_predict(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* alpha,

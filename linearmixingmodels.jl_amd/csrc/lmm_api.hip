@@ -5566,8 +5566,32 @@ int lmm_oilmm_logpdf_grad_statespace_x(const double* x, int n, const double* y, 
 
 // ---- Toeplitz path: stationary latents over an evenly spaced one-dimensional input, complete data ----
 // Every stationary kernel gives a symmetric Toeplitz Gram matrix there, and complete data adds the same noise sigma2 / S_l at every
-// point, so K_l + w_l I is factored by the Schur recursion in O(n^2) (lmm_kernels_toeplitz.hip), one workgroup per latent.
+// point, so K_l + w_l I is factored by the Schur recursion in O(n^2) (lmm_kernels_toeplitz.hip), one workgroup per latent, or
+// (`blocked`) many workgroups per latent and TOEPB_J steps per launch, which serves n up to TOEPB_MAX_N.
 int lmm_toeplitz_max_n(void) { return TOEP_MAX_N; }
+int lmm_toeplitz_blocked_max_n(void) { return TOEPB_MAX_N; }
+int lmm_toeplitz_blocked_shape(int* steps, int* rows_per_workgroup) {
+  const ToepBlockPlan P = toep_block_plan(1, 1);
+  if (steps) *steps = P.steps;
+  if (rows_per_workgroup) *rows_per_workgroup = P.rows;
+  return LMM_OK;
+}
+// n beyond the cap of the schedule in use
+static int toep_check_n(int n, bool blocked) {
+  if (blocked) {
+    if (n > TOEPB_MAX_N)
+      return fail(LMM_ERR_UNSUPPORTED, "the blocked Toeplitz path serves n <= %d points (lmm_toeplitz_blocked_max_n; n = %d)", TOEPB_MAX_N, n);
+  } else if (n > TOEP_MAX_N) {
+    return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves n <= %d points (lmm_toeplitz_max_n; n = %d)", TOEP_MAX_N, n);
+  }
+  return LMM_OK;
+}
+// The recursion by either schedule; the blocked one's workspace is scratch of the call
+static void toep_schur(const double* t, const double* r, int n, int nb, double* out2, double* p, double* q, int* info, bool blocked,
+                       hipStream_t st) {
+  if (!blocked) { launch_toep_schur(t, r, n, nb, out2, p, q, info, st); return; }
+  launch_toep_schur_blocked(t, r, n, nb, out2, p, q, info, call_scratch(toep_block_plan(n, nb).work), st);
+}
 
 // The device work of a call over the shard's ms latents: first columns, recursion, and what the gradient needs on top.
 struct ToepWork {
@@ -5576,7 +5600,8 @@ struct ToepWork {
   std::vector<double> lml;             // per latent of the shard
 };
 // lml[k] of the shard's latents from the noise w and data r ([latent][n], device); a failed step is LMM_ERR_NOT_PD naming latent and step
-static int toep_factor(const double* xd, int n, const Latent* lts, int l0, int ms, const double* w, const double* r, ToepWork& W) {
+static int toep_factor(const double* xd, int n, const Latent* lts, int l0, int ms, const double* w, const double* r, bool blocked,
+                       ToepWork& W) {
   hipStream_t st0 = g.streams[0];
   const int mk = std::max(ms, 1);
   W.t = Buf<double>((size_t)n * mk); W.p = Buf<double>((size_t)n * mk); W.q = Buf<double>((size_t)n * mk);
@@ -5588,7 +5613,7 @@ static int toep_factor(const double* xd, int n, const Latent* lts, int l0, int m
   Buf<LatentDev> dd(ms);
   HIPCHK(hipMemcpyAsync(dd.p, hd.data(), (size_t)ms * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
   launch_toep_row(xd, n, dd.p, w, ms, sum_mode(lts, l0, l0 + ms), W.t.p, st0);
-  launch_toep_schur(W.t.p, r, n, ms, W.out2.p, W.p.p, W.q.p, W.info.p, st0);
+  toep_schur(W.t.p, r, n, ms, W.out2.p, W.p.p, W.q.p, W.info.p, blocked, st0);
   HIPCHK(hipGetLastError());
   std::vector<double> h2(2 * (size_t)ms);
   std::vector<int> hinfo(ms);
@@ -5615,10 +5640,10 @@ struct ToepTrain {
   MissingFront F;                      // complete data: z = r, nv = the constant noise
 };
 static int toep_train(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
-                      const lmm_gp_t* gps, int l0, int l1, bool want_resid, ToepTrain& T) {
+                      const lmm_gp_t* gps, int l0, int l1, bool want_resid, bool blocked, ToepTrain& T) {
   if (int rc = train_args(!x || !y || !U || !S || n <= 0 || p <= 0 || m <= 0, p, m, S, sigma2, l0, l1, TRAIN_SIGMA2 | TRAIN_S)) return rc;
   if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  if (n > TOEP_MAX_N) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves n <= %d points (lmm_toeplitz_max_n; n = %d)", TOEP_MAX_N, n);
+  if (int rc = toep_check_n(n, blocked)) return rc;
   if (int rc = resolve(gps, m, 1, T.ls)) return rc;
   T.lts = T.ls->lat.data();
   for (int l = 0; l < m; ++l)
@@ -5664,16 +5689,16 @@ static int toep_train(const double* x, int n, const double* y, int p, const doub
   return missing_front(T.yd.p, n, p, U, S, m, sigma2, means.data(), l0, l1, want_resid, T.F);
 }
 
-int lmm_oilmm_logpdf_toeplitz(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
-                              const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out) {
+static int toep_logpdf(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                       const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out, bool blocked) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
   if (!out) return fail(LMM_ERR_ARG, "bad arguments");
   ToepTrain T;
-  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, false, T)) return rc;
+  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, false, blocked, T)) return rc;
   ToepWork W;
-  if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, T.ms, T.F.nv.p, T.F.z.p, W)) return rc;
+  if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, T.ms, T.F.nv.p, T.F.z.p, blocked, W)) return rc;
   double total = 0.0;
   for (int k = 0; k < T.ms; ++k) total += W.lml[k];
   if (with_regulariser) total += T.F.reg(n, m, sigma2);
@@ -5681,24 +5706,33 @@ int lmm_oilmm_logpdf_toeplitz(const double* x, int n, const double* y, int p, co
   return LMM_OK;
   LMM_CATCH
 }
+int lmm_oilmm_logpdf_toeplitz(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                              const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out) {
+  return toep_logpdf(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, out, false);
+}
+int lmm_oilmm_logpdf_toeplitz_blocked(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                      double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                      double* out) {
+  return toep_logpdf(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, out, true);
+}
 
 // Value and gradient of lmm_oilmm_logpdf_toeplitz with respect to y, sigma2, S, U and every latent's kernel parameters and mean.  Per
 // latent: alpha = K^-1 r by the Gohberg-Semencul products, the diagonal sums of K^-1 and the autocorrelation of alpha, and their
 // contraction with the kernel's derivatives along the lags (launch_toep_contract), which gives the sums of the dense reduction: the
 // host formulas are those of KernelGradPass::finish, the chain rule OilmmGradBackEnd with a = alpha.
-int lmm_oilmm_logpdf_grad_toeplitz(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
-                                   const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out_logpdf,
-                                   double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U, lmm_gp_grad_t* grad_gps) {
+static int toep_logpdf_grad(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                            const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out_logpdf,
+                            double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U, lmm_gp_grad_t* grad_gps, bool blocked) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
   ToepTrain T;
-  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, grad_y && with_regulariser, T)) return rc;
+  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, grad_y && with_regulariser, blocked, T)) return rc;
   hipStream_t st0 = g.streams[0];
   const int l0 = T.l0, l1 = T.l1, ms = T.ms, mk = T.mk;
   const Latent* lts = T.lts;
   ToepWork W;
-  if (int rc = toep_factor(T.xd.p, n, lts, l0, ms, T.F.nv.p, T.F.z.p, W)) return rc;
+  if (int rc = toep_factor(T.xd.p, n, lts, l0, ms, T.F.nv.p, T.F.z.p, blocked, W)) return rc;
   DevOut gy(grad_y, (size_t)n * p);
   Buf<double> al((size_t)n * mk), u(2 * (size_t)n * mk), sd((size_t)n * mk), ad((size_t)n * mk), red((size_t)LMM_SUM_MAX_TERMS * LMM_NGRAD * mk);
   std::vector<double> hred(red.n, 0.0);
@@ -5747,19 +5781,32 @@ int lmm_oilmm_logpdf_grad_toeplitz(const double* x, int n, const double* y, int 
   return LMM_OK;
   LMM_CATCH
 }
+int lmm_oilmm_logpdf_grad_toeplitz(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                                   const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, double* out_logpdf,
+                                   double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U, lmm_gp_grad_t* grad_gps) {
+  return toep_logpdf_grad(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, out_logpdf, grad_y, grad_sigma2,
+                          grad_S, grad_U, grad_gps, false);
+}
+int lmm_oilmm_logpdf_grad_toeplitz_blocked(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                           double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser,
+                                           double* out_logpdf, double* grad_y, double* grad_sigma2, double* grad_S, double* grad_U,
+                                           lmm_gp_grad_t* grad_gps) {
+  return toep_logpdf_grad(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, out_logpdf, grad_y, grad_sigma2,
+                          grad_S, grad_U, grad_gps, true);
+}
 
 // Building blocks for tests (DEVICE pointers, one matrix): the recursion on a given first column t and right-hand side r, and the
 // Gohberg-Semencul solve from its generators.
-int lmm_dev_toeplitz_factor(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q) {
+static int toep_dev_factor(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q, bool blocked) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
   if (!t || !r || !p || !q || n <= 0) return fail(LMM_ERR_ARG, "bad arguments");
-  if (n > TOEP_MAX_N) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves n <= %d points (lmm_toeplitz_max_n; n = %d)", TOEP_MAX_N, n);
+  if (int rc = toep_check_n(n, blocked)) return rc;
   hipStream_t st0 = g.streams[0];
   Buf<double> out2(2);
   Buf<int> info(1);
-  launch_toep_schur(t, r, n, 1, out2.p, p, q, info.p, st0);
+  toep_schur(t, r, n, 1, out2.p, p, q, info.p, blocked, st0);
   HIPCHK(hipGetLastError());
   double h2[2] = {0.0, 0.0};
   int hinfo = 0;
@@ -5774,6 +5821,12 @@ int lmm_dev_toeplitz_factor(const double* t, const double* r, int n, double* log
   if (quad) *quad = h2[1];
   return LMM_OK;
   LMM_CATCH
+}
+int lmm_dev_toeplitz_factor(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q) {
+  return toep_dev_factor(t, r, n, logdet, quad, p, q, false);
+}
+int lmm_dev_toeplitz_factor_blocked(const double* t, const double* r, int n, double* logdet, double* quad, double* p, double* q) {
+  return toep_dev_factor(t, r, n, logdet, quad, p, q, true);
 }
 
 int lmm_dev_toeplitz_solve(const double* p, const double* q, const double* r, int n, double* alpha) {
@@ -5846,18 +5899,18 @@ static int toep_check_finite(const double* xsd, int ns) {
 }
 static int toep_refuse_f32() { return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path is Float64 only (lmm_set_compute_dtype(LMM_F64))"); }
 
-int lmm_oilmm_toeplitz_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
-                                        double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_toep_post_t** out,
-                                        double* out_logpdf) {
+static int toep_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                                 const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_toep_post_t** out, double* out_logpdf,
+                                 bool blocked) {
   std::lock_guard<std::mutex> lk(g_mu);
   REQUIRE_INIT();
   LMM_TRY
   if (!out) return fail(LMM_ERR_ARG, "bad arguments");
   *out = nullptr;
   ToepTrain T;
-  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, false, T)) return rc;
+  if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, false, blocked, T)) return rc;
   ToepWork W;
-  if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, T.ms, T.F.nv.p, T.F.z.p, W)) return rc;
+  if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, T.ms, T.F.nv.p, T.F.z.p, blocked, W)) return rc;
   hipStream_t st0 = g.streams[0];
   double total = 0.0;                       // the sum of lmm_oilmm_logpdf_toeplitz, in its order
   for (int k = 0; k < T.ms; ++k) total += W.lml[k];
@@ -5884,6 +5937,16 @@ int lmm_oilmm_toeplitz_posterior_create(const double* x, int n, const double* y,
   *out = P.release();
   return LMM_OK;
   LMM_CATCH
+}
+int lmm_oilmm_toeplitz_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                        double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_toep_post_t** out,
+                                        double* out_logpdf) {
+  return toep_posterior_create(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, out, out_logpdf, false);
+}
+int lmm_oilmm_toeplitz_posterior_create_blocked(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                                double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                                lmm_toep_post_t** out, double* out_logpdf) {
+  return toep_posterior_create(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, out, out_logpdf, true);
 }
 
 int lmm_toeplitz_post_destroy(lmm_toep_post_t* post) {

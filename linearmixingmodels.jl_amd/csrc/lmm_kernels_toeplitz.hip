@@ -215,3 +215,202 @@ void launch_toep_lags(const double* p, const double* q, const double* alpha, int
   if (nb <= 0) return;
   hipLaunchKernelGGL(toep_lag_kernel, dim3((n + 255) / 256, nb), dim3(256), 0, st, p, q, alpha, n, sd, ad);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// The blocked schedule (DESIGN.md 4.22 "Blocked schedule"): the same recursion with one latent spread over many workgroups, TOEPB_J
+// steps per launch, for n beyond what one workgroup's LDS holds.  Between launches the state lives in global memory: a, b, p, q in two
+// copies each (a launch reads one and writes the other), r updated in place by its row's owner, and a four-double record per latent
+// (running product, sum z^2, exponent, info), also in two copies.  (p, q) are kept on every row: p_k and q_k are exactly 0 on the rows
+// > k, and the rotation of a zero pair is zero, so row k + 1 "enters" with q = 0 without a rule of its own.
+//
+// A launch at step k0 is (row windows x latents) workgroups of TOEPB_WAVES waves.  Wave 0 of every workgroup first replays the block on
+// its leading rows, one row per lane: lane j holds a[k0 + j], b[k0 + j + 1] and r[k0 + j]; step s reads pivot, b and r from lane s,
+// rotates, and moves a down one lane.  It leaves (rho, c, 1 / c, z) of the TOEPB_J steps in LDS; steps past n - 1 (and step n - 1,
+// which has no rotation) are the identity (0, 1, 1, 0).  Every workgroup of a latent computes the same numbers with the same code, so
+// nothing waits for a panel; workgroup 0 alone writes the latent's record.  After the one barrier each wave applies the steps to a
+// window of 64 TOEPB_EPT rows held in registers, lane j rows g0 + j TOEPB_EPT + e.  Per step: r -= a z (the a side), a (or p) moves
+// down one row, the rotation.  The move is a rename inside the lane -- the step loop is unrolled by TOEPB_EPT and row e of step s
+// lives in register (e - s) mod TOEPB_EPT -- plus one __shfl_up of the register that leaves the lane.  What comes in at the top of
+// the window is wrong, one row more per step: the first TOEPB_J rows are a halo that is loaded and never stored, and a wave stores the
+// TOEPB_V rows below it.  The (p, q) windows tile the rows [0, k0 + J], the (a, b) windows the rows [k0 + J, n); rows above 0 and
+// p, q above k0 load as 0.  In the last block only jr < J steps rotate; the identity steps still move p down, so p is stored J - jr
+// rows up.  No barrier but the one, no LDS but the coefficients, no atomics, no flags: launches are ordered by the stream.
+// A latent whose record already has info != 0, or whose replay meets a bad pivot, stores nothing but the record.
+// ---------------------------------------------------------------------------------------------------
+static_assert(TOEPB_J == 64, "the replay holds one row per lane");
+static_assert(TOEPB_J % TOEPB_EPT == 0, "the register rename closes after TOEPB_EPT steps");
+
+__device__ __forceinline__ double toepb_lane(double v, int lane) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
+// One wave's window.  ASIDE: x = a, y = b over the rows [0, n), r updated; else x = p, y = q over the rows [0, hi], x stored sh rows up.
+template <bool ASIDE>
+__device__ __forceinline__ void toepb_window(const double* __restrict__ xin, const double* __restrict__ yin, double* __restrict__ xout,
+                                             double* __restrict__ yout, double* r, const double4* coef, int n, int g0, int hi, int sh,
+                                             int lane) {
+  double P[TOEPB_EPT], B[TOEPB_EPT], R[TOEPB_EPT];
+  const int i0 = g0 + lane * TOEPB_EPT;
+  const bool own = lane * TOEPB_EPT >= TOEPB_J;      // below the halo (TOEPB_J is a multiple of TOEPB_EPT: a lane is all halo or none)
+#pragma unroll
+  for (int e = 0; e < TOEPB_EPT; ++e) {
+    const int i = i0 + e;
+    const bool ok = i >= 0 && i <= hi;
+    const int ii = ok ? i : 0;
+    const double xv = xin[ii], yv = yin[ii];
+    P[e] = ok ? xv : 0.0;
+    B[e] = ok ? yv : 0.0;
+    R[e] = 0.0;
+    if (ASIDE && ok && own) R[e] = r[i];      // r is read by its row's owner alone
+  }
+  for (int s0 = 0; s0 < TOEPB_J; s0 += TOEPB_EPT) {
+#pragma unroll
+    for (int s = 0; s < TOEPB_EPT; ++s) {
+      const double4 cf = coef[s0 + s];
+      const double rho = cf.x, c = cf.y, ic = cf.z, z = cf.w;
+      if (ASIDE) {
+#pragma unroll
+        for (int e = 0; e < TOEPB_EPT; ++e) R[e] = __builtin_fma(-P[(e - s + TOEPB_EPT) % TOEPB_EPT], z, R[e]);
+      }
+      const int ps = (2 * TOEPB_EPT - 1 - s) % TOEPB_EPT;      // the row that leaves the lane
+      P[ps] = __shfl_up(P[ps], 1);
+#pragma unroll
+      for (int e = 0; e < TOEPB_EPT; ++e) {
+        const int x = (e - s - 1 + 2 * TOEPB_EPT) % TOEPB_EPT;
+        const double an = (P[x] - rho * B[e]) * ic;
+        B[e] = c * B[e] - rho * an;
+        P[x] = an;
+      }
+    }
+  }
+  if (own) {
+#pragma unroll
+    for (int e = 0; e < TOEPB_EPT; ++e) {
+      const int i = i0 + e;
+      if (i < n) yout[i] = B[e];
+      if (i - sh >= 0 && i - sh < n) xout[i - sh] = P[e];
+      if (ASIDE && i < n) r[i] = R[e];
+    }
+  }
+}
+
+// work: see launch_toep_schur_blocked.  np: the workgroups on the (p, q) side (they come first).
+__global__ __launch_bounds__(64 * TOEPB_WAVES) void toep_schur_block_kernel(
+    const double* __restrict__ ain, const double* __restrict__ bin, const double* __restrict__ pin, const double* __restrict__ qin,
+    double* __restrict__ aout, double* __restrict__ bout, double* __restrict__ pout, double* __restrict__ qout, double* r,
+    const double* __restrict__ stin, double* __restrict__ stout, int n, int k0, int np) {
+  __shared__ double4 coef[TOEPB_J];
+  __shared__ int sbad;
+  const int l = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t off = (size_t)l * n;
+  stin += 4 * l; stout += 4 * l;
+  if (stin[3] != 0.0) {      // failed in an earlier block: pass the record on
+    if (blockIdx.x == 0 && tid < 4) stout[tid] = stin[tid];
+    return;
+  }
+  r += off;
+  const int js = min(TOEPB_J, n - k0);      // steps of this block, the last of the recursion (n - 1) included
+  const int jr = min(TOEPB_J, n - 1 - k0);  // of which rotate
+  if (wave == 0) {
+    const int i = k0 + lane;
+    const double av = ain[off + (i < n ? i : k0)], bv = bin[off + (i + 1 < n ? i + 1 : k0)], rv = r[i < n ? i : k0];
+    double X = i < n ? av : 0.0, Bq = i + 1 < n ? bv : 0.0, R = i < n ? rv : 0.0;
+    double prod = stin[0], quad = stin[1];
+    int ex = (int)stin[2], bad = 0, s = 0;
+    for (; s < js; ++s) {
+      const double pa = toepb_lane(X, s), pb = toepb_lane(Bq, s), num = toepb_lane(R, s);
+      const double ipa = 1.0 / pa, z = num * ipa, rho = pb * ipa;
+      const bool last = k0 + s == n - 1;
+      if (!(pa > 0.0) || (!last && !(fabs(rho) < 1.0))) { bad = k0 + s + 1; break; }
+      quad = __builtin_fma(z, z, quad);
+      prod *= pa;
+      const bool big = prod > 0x1p+500, small = prod < 0x1p-500;
+      prod *= big ? 0x1p-500 : small ? 0x1p+500 : 1.0;
+      ex += big ? 500 : small ? -500 : 0;
+      if (last) break;
+      const double c = sqrt((1.0 - rho) * (1.0 + rho)), ic = 1.0 / c;
+      if (lane == 0) coef[s] = make_double4(rho, c, ic, z);
+      R = lane > s ? __builtin_fma(-X, z, R) : R;
+      const double an = (X - rho * Bq) * ic;
+      Bq = c * Bq - rho * an;
+      X = __shfl_up(an, 1);
+    }
+    if (lane >= jr) coef[lane] = make_double4(0.0, 1.0, 1.0, 0.0);
+    if (lane == 0) sbad = bad;
+    if (blockIdx.x == 0 && lane == 0) { stout[0] = prod; stout[1] = quad; stout[2] = (double)ex; stout[3] = (double)bad; }
+  }
+  __syncthreads();
+  if (sbad) return;
+  const int v = ((int)blockIdx.x < np ? (int)blockIdx.x : (int)blockIdx.x - np) * TOEPB_WAVES + wave;
+  if ((int)blockIdx.x < np) {
+    const int g0 = v * TOEPB_V - TOEPB_J;
+    if (g0 > k0) return;                    // its rows lie above k0 + J
+    toepb_window<false>(pin + off, qin + off, pout + off, qout + off, nullptr, coef, n, g0, k0, TOEPB_J - jr, lane);
+  } else {
+    const int g0 = k0 + v * TOEPB_V;
+    if (g0 + TOEPB_J >= n) return;
+    toepb_window<true>(ain + off, bin + off, aout + off, bout + off, r, coef, n, g0, n - 1, 0, lane);
+  }
+}
+
+// Before the first block: a = t / sqrt(t0) (a[0] the square root itself), b = a, p[0] = q[0] = 1 / sqrt(t0), r copied, the record.
+__global__ __launch_bounds__(256) void toep_block_init_kernel(const double* __restrict__ t, const double* __restrict__ r, int n,
+                                                              double* __restrict__ a, double* __restrict__ b, double* __restrict__ p,
+                                                              double* __restrict__ q, double* __restrict__ rw, double* __restrict__ st) {
+  const int l = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  const size_t off = (size_t)l * n;
+  if (i >= n) return;
+  const double s = sqrt(t[off]), is = 1.0 / s, v = i ? t[off + i] * is : s;
+  a[off + i] = v; b[off + i] = v; rw[off + i] = r[off + i];
+  if (i == 0) {
+    p[off] = is; q[off] = is;
+    st[4 * l] = 1.0; st[4 * l + 1] = 0.0; st[4 * l + 2] = 0.0; st[4 * l + 3] = 0.0;
+  }
+}
+// After the last: the generators with p's last shift, log det, the sum, info.
+__global__ __launch_bounds__(256) void toep_block_finish_kernel(const double* __restrict__ p, const double* __restrict__ q,
+                                                                const double* __restrict__ st, int n, double* __restrict__ pg,
+                                                                double* __restrict__ qg, double* __restrict__ out2, int* __restrict__ info) {
+  const int l = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  const size_t off = (size_t)l * n;
+  if (i >= n) return;
+  pg[off + i] = i ? p[off + i - 1] : 0.0;
+  qg[off + i] = q[off + i];
+  if (i == 0) {
+    out2[2 * l] = 2.0 * (log(st[4 * l]) + st[4 * l + 2] * 0.6931471805599453);
+    out2[2 * l + 1] = st[4 * l + 1];
+    info[l] = (int)st[4 * l + 3];
+  }
+}
+
+ToepBlockPlan toep_block_plan(int n, int nb) {
+  ToepBlockPlan P;
+  P.steps = TOEPB_J; P.rows = TOEPB_ROWS;
+  P.launches = (n + TOEPB_J - 1) / TOEPB_J;
+  P.windows = (n - 1) / TOEPB_ROWS + 2;      // most workgroups a launch gives a latent (both sides)
+  P.work = 9 * (size_t)nb * n + 8 * (size_t)nb;
+  return P;
+}
+void launch_toep_schur_blocked(const double* t, const double* r, int n, int nb, double* out2, double* p, double* q, int* info,
+                               double* work, hipStream_t st) {
+  if (nb <= 0) return;
+  const size_t N = (size_t)nb * n;
+  double* a[2] = {work, work + N};
+  double* b[2] = {work + 2 * N, work + 3 * N};
+  double* pp[2] = {work + 4 * N, work + 5 * N};
+  double* qq[2] = {work + 6 * N, work + 7 * N};
+  double* rw = work + 8 * N;
+  double* rec[2] = {work + 9 * N, work + 9 * N + 4 * (size_t)nb};
+  const dim3 flat((n + 255) / 256, nb);
+  hipLaunchKernelGGL(toep_block_init_kernel, flat, dim3(256), 0, st, t, r, n, a[0], b[0], pp[0], qq[0], rw, rec[0]);
+  int cur = 0;
+  for (int k0 = 0; k0 < n; k0 += TOEPB_J, cur ^= 1) {
+    const int np = (k0 + TOEPB_J + TOEPB_ROWS) / TOEPB_ROWS;      // rows [0, k0 + J]
+    const int na = k0 + TOEPB_J < n ? (n - k0 - TOEPB_J + TOEPB_ROWS - 1) / TOEPB_ROWS : 0;
+    hipLaunchKernelGGL(toep_schur_block_kernel, dim3(np + na, nb), dim3(64 * TOEPB_WAVES), 0, st, (const double*)a[cur],
+                       (const double*)b[cur], (const double*)pp[cur], (const double*)qq[cur], a[cur ^ 1], b[cur ^ 1], pp[cur ^ 1],
+                       qq[cur ^ 1], rw, (const double*)rec[cur], rec[cur ^ 1], n, k0, np);
+  }
+  hipLaunchKernelGGL(toep_block_finish_kernel, flat, dim3(256), 0, st, (const double*)pp[cur], (const double*)qq[cur],
+                     (const double*)rec[cur], n, p, q, out2, info);
+}

@@ -15,6 +15,23 @@ void launch_toep_row(const double* x, int n, const LatentDev* lat, const double*
 // out2[2 l] = log det, out2[2 l + 1] = r' K^-1 r, p / q [l n ..] the Gohberg-Semencul generators of K^-1, info[l] = 0 or 1 + the step
 // whose pivot was not > 0 (or whose reflection coefficient was not inside (-1, 1)).  n <= TOEP_MAX_N.
 void launch_toep_schur(const double* t, const double* r, int n, int nb, double* out2, double* p, double* q, int* info, hipStream_t st);
+// The same recursion for any n <= TOEPB_MAX_N, a latent spread over many workgroups and TOEPB_J steps per launch (DESIGN.md 4.22
+// "Blocked schedule").  A wave holds 64 TOEPB_EPT rows in registers, of which the first TOEPB_J are the halo of the block's steps.
+#define TOEPB_J 64                            // steps of a block (a launch)
+#define TOEPB_EPT 8                           // rows a lane holds
+#define TOEPB_WAVES 4                         // waves of a workgroup
+#define TOEPB_V (64 * TOEPB_EPT - TOEPB_J)    // rows a wave stores: 448
+#define TOEPB_ROWS (TOEPB_WAVES * TOEPB_V)    // rows a workgroup stores: 1792
+#define TOEPB_MAX_N 131072                    // the largest n that has been run; memory is O(n)
+struct ToepBlockPlan {
+  int steps, rows;                            // TOEPB_J, TOEPB_ROWS
+  int windows, launches;                      // most workgroups per latent of a launch; block launches
+  size_t work;                                // doubles of workspace: a, b, p, q twice, r, the records twice
+};
+ToepBlockPlan toep_block_plan(int n, int nb);
+// Outputs as launch_toep_schur's; work: toep_block_plan(n, nb).work doubles.
+void launch_toep_schur_blocked(const double* t, const double* r, int n, int nb, double* out2, double* p, double* q, int* info,
+                               double* work, hipStream_t st);
 // alpha[l n ..] = K_l^-1 r_l = L(q) L(q)' r - L(p) L(p)' r; u: 2 nb n doubles of scratch
 void launch_toep_solve(const double* p, const double* q, const double* r, int n, int nb, double* u, double* alpha, hipStream_t st);
 // sd[l n + d] = sum_i (K_l^-1)_{i, i + d} and ad[l n + d] = sum_i alpha_i alpha_{i + d}

@@ -1445,26 +1445,29 @@ def _toeplitz_args(fx: "FiniteGP", y, what: str):
     return y
 
 
-def toeplitz_logpdf(fx: "FiniteGP", y, with_regulariser: bool = True) -> float:
+def toeplitz_logpdf(fx: "FiniteGP", y, with_regulariser: bool = True, blocked: bool = False) -> float:
     """logpdf(fx, y) of a prior OILMM with stationary latents of ANY kind (SE, RQ, periodic, locally periodic, Matern, SHO, KernelSum)
     over ascending, evenly spaced one-dimensional inputs and complete data, exactly, in O(n^2) time and O(n) memory per latent: there
     every K_l + (sigma2 / S_l) I is symmetric Toeplitz, and the Schur recursion factors it.  x and y: NumPy arrays or
-    torch device tensors.  A NaN in y, n beyond the cap (lmm_toeplitz_max_n) and ARD tags are refused by the library."""
+    torch device tensors.  A NaN in y, n beyond the cap (lmm_toeplitz_max_n) and ARD tags are refused by the library.
+    blocked=True runs the recursion's blocked schedule (DESIGN.md 4.22 "Blocked schedule"), which spreads a latent over the whole GPU
+    and serves any n up to lmm_toeplitz_blocked_max_n; every other rule is the same."""
     y = _toeplitz_args(fx, y, "toeplitz_logpdf")
     f, x = fx.f, fx.x
     L.ensure_init()
     _, gps = _gps_arg(f.f)
     Ua, Sa, p, m = _H_args(f.H)
     out = C.c_double()
-    L.check(L.load().lmm_oilmm_logpdf_toeplitz(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps, 0, m,
+    lib = L.load()
+    L.check((lib.lmm_oilmm_logpdf_toeplitz_blocked if blocked else lib.lmm_oilmm_logpdf_toeplitz)(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps, 0, m,
                                                int(with_regulariser), C.byref(out)))
     return out.value
 
 
-def toeplitz_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = True) -> dict:
+def toeplitz_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = True, blocked: bool = False) -> dict:
     """Value and gradient of toeplitz_logpdf(fx, y): {"value", "y", "sigma2", "S", "U", "gps"}, as logpdf_and_gradient returns them for
     a prior OILMM ("gps" through _gps_grads: every latent's kernel parameters, tags and sum terms included, and its mean).  "value" is
-    bitwise toeplitz_logpdf(fx, y, with_regulariser); "y" is shaped and typed like y."""
+    bitwise toeplitz_logpdf(fx, y, with_regulariser, blocked); "y" is shaped and typed like y.  blocked: as toeplitz_logpdf's."""
     y = _toeplitz_args(fx, y, "toeplitz_logpdf_and_gradient")
     f, x = fx.f, fx.x
     n = x.n
@@ -1473,7 +1476,8 @@ def toeplitz_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = Tru
     val, gs2 = C.c_double(), C.c_double()
     gy, gS, gU = _alloc_like(y, n * p), np.empty(m), np.empty(p * m)
     gg, ga = (L.GpGradT * m)(), L.gps_array([g.desc() for g in f.f.fs])
-    L.check(L.load().lmm_oilmm_logpdf_grad_toeplitz(L.Arr(x.x.reshape(-1)).ptr, n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), ga, 0, m,
+    lib = L.load()
+    L.check((lib.lmm_oilmm_logpdf_grad_toeplitz_blocked if blocked else lib.lmm_oilmm_logpdf_grad_toeplitz)(L.Arr(x.x.reshape(-1)).ptr, n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), ga, 0, m,
                                                     int(with_regulariser), C.byref(val), L.Arr(gy, True).ptr, C.byref(gs2),
                                                     L.Arr(gS, True).ptr, L.Arr(gU, True).ptr, gg))
     return {"value": val.value, "y": gy, "sigma2": gs2.value, "S": gS, "U": gU.reshape(m, p).T.copy(), "gps": _gps_grads(gg, ga, m, 1)}
@@ -1549,16 +1553,18 @@ class ToeplitzPosterior:
         return Normal(m, v ** 0.5)
 
 
-def toeplitz_posterior(fx: "FiniteGP", y) -> ToeplitzPosterior:
+def toeplitz_posterior(fx: "FiniteGP", y, blocked: bool = False) -> ToeplitzPosterior:
     """posterior(fx, y) of the models toeplitz_logpdf serves, as a reusable object: one Schur recursion per latent conditions on the
-    data, and post.mean_and_var(xs) then answers at any new inputs without it.  post.logpdf is bitwise toeplitz_logpdf(fx, y)."""
+    data, and post.mean_and_var(xs) then answers at any new inputs without it.  post.logpdf is bitwise toeplitz_logpdf(fx, y, True, blocked).
+    blocked: as toeplitz_logpdf's."""
     y = _toeplitz_args(fx, y, "toeplitz_posterior")
     f, x = fx.f, fx.x
     L.ensure_init()
     _, gps = _gps_arg(f.f)
     Ua, Sa, p, m = _H_args(f.H)
     ptr, out = C.c_void_p(), C.c_double()
-    L.check(L.load().lmm_oilmm_toeplitz_posterior_create(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2),
+    lib = L.load()
+    L.check((lib.lmm_oilmm_toeplitz_posterior_create_blocked if blocked else lib.lmm_oilmm_toeplitz_posterior_create)(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2),
                                                          gps, 0, m, C.byref(ptr), C.byref(out)))
     return ToeplitzPosterior(ptr, x.n, p, out.value)
 
