@@ -901,6 +901,34 @@ int lmm_toeplitz_post_destroy(lmm_toep_post_t* post);
 int lmm_oilmm_toeplitz_post_mean_and_var(const lmm_toep_post_t* post, const double* xs, int ns, int add_noise, double* mean, double* var);
 int lmm_dev_toeplitz_predict(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* alpha,
                              const double* xs, int ns, double* mean, double* var);
+/* Toeplitz: joint samples (DESIGN.md 4.22 "Sampling"), of the prior and of the posterior, over the training grid and its continuation
+ * x_0 + i h, i < nt = n + horizon, in O(nt^2) time and O(nt) memory per latent and pass of 4 samples.  A prior path is f = L zeta with
+ * L L' = Toeplitz(t0 + jitter e_0), t0 the latent kernel's first column over nt lags: step k of the blocked Schur recursion holds
+ * column k of L, and f += L[:, k] zeta_k rides on it (toep_schur_sample_kernel); L is never stored.  A posterior path is pathwise
+ * conditioning from the handle's generators and alpha, without the data: d = f[0:n] + sqrt(w_l) xi, beta = (K + w_l I)^-1 d,
+ * g = alpha - beta padded with zeros to nt, path = mu_l + f + T(t0) g (w_l = sigma2 / S_l).  No atomics: bitwise reproducible, and
+ * sample q of a call is bitwise the one-sample call on its normals.  All normals are the caller's; z, xi, eps, out: host or device.
+ *   lmm_oilmm_rand_toeplitz : nsamples prior samples.  z: per sample m nt standard normals, latent-major (the shard reads its
+ *                    latents'); eps: per sample nt p by outputs, read only when add_noise (and then required); out: per sample nt x p by
+ *                    outputs, H (mu + f) + sqrt(sigma2) eps, mixed exactly as lmm_oilmm_rand_statespace mixes; partial sums over the
+ *                    shard.  jitter < 0: the default jitter that lmm_lmm_rand adds to a latent prior (lmm_jitters_t.default_jitter).
+ *                    z or out NULL, horizon < 0, nsamples < 1, a jitter that is not finite, a horizon > 0 with n < 2
+ *                    -> LMM_ERR_ARG; then every refusal of lmm_oilmm_logpdf_toeplitz_blocked that does not read y, in its order, the
+ *                    cap held against n + horizon (LMM_ERR_UNSUPPORTED naming "n + horizon").  A prior matrix that the recursion
+ *                    cannot factor -> LMM_ERR_NOT_PD with latent and 1 + step in lmm_last_error_detail: raise jitter.
+ *   lmm_oilmm_toeplitz_post_rand : nsamples posterior samples from a handle of either schedule, which is not changed: every later
+ *                    answer of the handle is bitwise what it was, after a refusal too.  z: per sample, for each latent of the handle's
+ *                    shard, nt normals; xi: per sample, for each of them, n normals; eps, out, refusals and failures as above.
+ *   lmm_toeplitz_rand_last_ms : milliseconds of the last successful call of either, by events: the recursion, and the rest of the call.
+ *   lmm_dev_toeplitz_sample : building block for tests, DEVICE pointers, ONE matrix: f[q n ..] = L z[q n ..], L L' = Toeplitz(t), for
+ *                    q < nsamples and any n <= lmm_toeplitz_blocked_max_n().  LMM_ERR_NOT_PD with 1 + the step as `info`. */
+int lmm_oilmm_rand_toeplitz(const double* x, int n, int p, const double* U, const double* S, int m, double sigma2, const lmm_gp_t* gps,
+                            int latent_begin, int latent_end, int horizon, double jitter, int add_noise, int nsamples, const double* z,
+                            const double* eps /* iff add_noise */, double* out);
+int lmm_oilmm_toeplitz_post_rand(const lmm_toep_post_t* post, int horizon, double jitter, int add_noise, int nsamples, const double* z,
+                                 const double* xi, const double* eps /* iff add_noise */, double* out);
+int lmm_toeplitz_rand_last_ms(double* recursion_ms, double* rest_ms);
+int lmm_dev_toeplitz_sample(const double* t, const double* z, int n, int nsamples, double* f);
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
                               const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,

@@ -5577,8 +5577,11 @@ int lmm_toeplitz_blocked_shape(int* steps, int* rows_per_workgroup) {
   return LMM_OK;
 }
 // n beyond the cap of the schedule in use
-static int toep_check_n(int n, bool blocked) {
+static int toep_check_n(int n, bool blocked, int horizon = -1) {
   if (blocked) {
+    if (horizon >= 0 && (long long)n + horizon > TOEPB_MAX_N)      // the sampling entry points: the grid and its continuation
+      return fail(LMM_ERR_UNSUPPORTED, "the blocked Toeplitz path serves n <= %d points (lmm_toeplitz_blocked_max_n; n + horizon = %lld)",
+                  TOEPB_MAX_N, (long long)n + horizon);
     if (n > TOEPB_MAX_N)
       return fail(LMM_ERR_UNSUPPORTED, "the blocked Toeplitz path serves n <= %d points (lmm_toeplitz_blocked_max_n; n = %d)", TOEPB_MAX_N, n);
   } else if (n > TOEP_MAX_N) {
@@ -5637,13 +5640,15 @@ struct ToepTrain {
   const Latent* lts = nullptr;
   DevIn xd{nullptr, 0, nullptr}, yd{nullptr, 0, nullptr};
   int l0 = 0, l1 = 0, ms = 0, mk = 1;
+  double x0 = 0.0, h = 0.0;            // the grid: x[0] and (x[n-1] - x[0]) / (n - 1)
   MissingFront F;                      // complete data: z = r, nv = the constant noise
 };
-static int toep_train(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
-                      const lmm_gp_t* gps, int l0, int l1, bool want_resid, bool blocked, ToepTrain& T) {
-  if (int rc = train_args(!x || !y || !U || !S || n <= 0 || p <= 0 || m <= 0, p, m, S, sigma2, l0, l1, TRAIN_SIGMA2 | TRAIN_S)) return rc;
+// The refusals that do not read y, and x on the device.  horizon >= 0 (the sampling entry points): the cap is held against n + horizon.
+static int toep_inputs(bool bad, const double* x, int n, int p, const double* U, const double* S, int m, double sigma2, const lmm_gp_t* gps,
+                       int l0, int l1, bool blocked, int horizon, ToepTrain& T) {
+  if (int rc = train_args(bad || !x || !U || !S || n <= 0 || p <= 0 || m <= 0, p, m, S, sigma2, l0, l1, TRAIN_SIGMA2 | TRAIN_S)) return rc;
   if (g_f32) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path is Float64 only (lmm_set_compute_dtype(LMM_F64))");
-  if (int rc = toep_check_n(n, blocked)) return rc;
+  if (int rc = toep_check_n(n, blocked, horizon)) return rc;
   if (int rc = resolve(gps, m, 1, T.ls)) return rc;
   T.lts = T.ls->lat.data();
   for (int l = 0; l < m; ++l)
@@ -5669,7 +5674,15 @@ static int toep_train(const double* x, int n, const double* y, int p, const doub
       return fail(LMM_ERR_ARG, "the Toeplitz path needs ascending, evenly spaced inputs: x[%d] is off the grid from x[0] to x[%d]", off, n - 1);
     }
   }
+  T.x0 = hx[0]; T.h = n > 1 ? (hx[n - 1] - hx[0]) / (double)(n - 1) : 0.0;
   T.xd = DevIn(x, (size_t)n, st0);
+  T.l0 = l0; T.l1 = l1; T.ms = l1 - l0; T.mk = std::max(T.ms, 1);
+  return LMM_OK;
+}
+static int toep_train(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                      const lmm_gp_t* gps, int l0, int l1, bool want_resid, bool blocked, ToepTrain& T) {
+  if (int rc = toep_inputs(!y, x, n, p, U, S, m, sigma2, gps, l0, l1, blocked, -1, T)) return rc;
+  hipStream_t st0 = g.streams[0];
   T.yd = DevIn(y, (size_t)n * p, st0);
   {
     Buf<unsigned long long> masks((size_t)n * ((p + 63) / 64));
@@ -5684,7 +5697,6 @@ static int toep_train(const double* x, int n, const double* y, int p, const doub
         return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path needs complete data: point %d has a NaN in y (per-point noise is not Toeplitz)", t);
       }
   }
-  T.l0 = l0; T.l1 = l1; T.ms = l1 - l0; T.mk = std::max(T.ms, 1);
   const std::vector<double> means = latent_means(T.lts, m);
   return missing_front(T.yd.p, n, p, U, S, m, sigma2, means.data(), l0, l1, want_resid, T.F);
 }
@@ -5853,6 +5865,7 @@ struct lmm_toep_post {
   std::shared_ptr<LatentSet> ls;      // all m latents as the handle was built with them
   Buf<double> pg, qg, alpha;          // per latent of the shard, [latent][n]
   Buf<double> H;                      // p x (l1 - l0), column-major: H = U sqrt(S) of the shard
+  std::vector<double> w;              // per latent of the shard: its noise sigma2 / S_l (read by lmm_oilmm_toeplitz_post_rand)
 };
 
 static const size_t kToepPredictScratch = size_t(1) << 23;      // doubles of partials a query chunk may take (64 MB)
@@ -5929,6 +5942,7 @@ static int toep_posterior_create(const double* x, int n, const double* y, int p,
   }
   P->x0 = ends[0]; P->h = n > 1 ? (ends[1] - ends[0]) / (double)(n - 1) : 0.0;
   P->pg = std::move(W.p); P->qg = std::move(W.q);
+  for (int k = 0; k < T.ms; ++k) P->w.push_back(sigma2 / S[T.l0 + k]);
   const std::vector<double> Hs = shard_H(U, S, p, T.l0, T.ms);
   P->H = Buf<double>(std::max<size_t>(Hs.size(), 1));
   HIPCHK(hipMemcpyAsync(P->H.p, Hs.data(), Hs.size() * sizeof(double), hipMemcpyHostToDevice, st0));
@@ -6800,6 +6814,161 @@ int lmm_oilmm_statespace_post_rand(const lmm_ss_post_t* post, const double* xs, 
   if (rc) return rc;
   od.finish(st0);
   HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+// ---- sampling on the Toeplitz path (DESIGN.md 4.22 "Sampling") ---------------------------------------------------------------------
+// Joint samples over the grid x0 + i h, i < nt = n + horizon, of the ms latents lts[0 .. ms): per latent the prior path
+// f = L zeta with L L' = Toeplitz(t0 + jitter e0) (launch_toep_sample, t0 the first column of the latent's kernel over nt lags), and
+// with a handle P pathwise conditioning from its generators and alpha: d = f[0:n] + sqrt(w) xi, beta = (K + w I)^-1 d, g = alpha - beta
+// padded to nt, path = mu + f + T(t0) g.  The paths are mixed as lmm_oilmm_rand_statespace mixes (ss_sample_mix).
+// z: per sample zall doubles of which the shard's ms nt start at zoff; xi: per sample ms n (handle only); eps: per sample nt p.
+static double g_toep_rand_ms[2] = {0.0, 0.0};      // the last call's recursion and everything else of it, by events on streams[0]
+static int toep_rand(const Latent* lts, int l_first, int ms, double x0, double h, int n, int horizon, double jitter, const lmm_toep_post* P,
+                     int p, const double* Hd, double sigma2, int add_noise, int N, const double* z, size_t zall, size_t zoff,
+                     const double* xi, const double* eps, double* out) {
+  hipStream_t st0 = g.streams[0];
+  const int nt = n + horizon, mk = std::max(ms, 1);
+  hipEvent_t ev[4];
+  for (hipEvent_t& e : ev) HIPCHK(hipEventCreate(&e));
+  struct EvFree { hipEvent_t* e; ~EvFree() { for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e[i]); } } ev_free{ev};
+  HIPCHK(hipEventRecord(ev[0], st0));
+  Buf<double> xg((size_t)nt), t0((size_t)nt * mk), tj((size_t)nt * mk), e0(P ? (size_t)nt * mk : 1);
+  std::vector<double> hmu(mk, 0.0), hsw(mk, 0.0);
+  if (ms > 0) {
+    std::vector<LatentDev> hd(ms);
+    for (int k = 0; k < ms; ++k) { hd[k] = lts[k].dev(); hmu[k] = lts[k].mean; if (P) hsw[k] = std::sqrt(P->w[k]); }
+    Buf<LatentDev> dd(ms);
+    HIPCHK(hipMemcpyAsync(dd.p, hd.data(), (size_t)ms * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+    launch_toep_grid(x0, h, nt, xg.p, st0);
+    launch_toep_row(xg.p, nt, dd.p, nullptr, ms, sum_mode(lts, 0, ms), t0.p, st0);
+    launch_toep_prior(t0.p, jitter, nt, ms, tj.p, P ? e0.p : nullptr, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));            // dd goes back to the pool
+  }
+  Uploaded mu(hmu, st0), sw(hsw, st0);
+  DevOut od(out, (size_t)nt * p * N);
+  float rec_ms = 0.0f;
+  const int rc = ss_sample_mix(nt, nt, ms, p, Hd, sigma2, add_noise ? eps : nullptr, N, od.p, [&](int q0, int ng, double* f) {
+    if (ms == 0) return (int)LMM_OK;
+    SSNormals zd(z, zall, zoff, (size_t)ms * nt, q0, ng, st0), xid(P ? xi : nullptr, (size_t)ms * n, 0, (size_t)ms * n, q0, ng, st0);
+    Buf<double> zt((size_t)ms * ng * nt), fs((size_t)ms * ng * nt), work(toep_sample_work(nt, ms));
+    Buf<int> info(ms);
+    std::vector<int> hinfo(ms);
+    launch_toep_gather(zd.p, zd.stride, nt, ms, ng, zt.p, st0);
+    HIPCHK(hipEventRecord(ev[1], st0));
+    launch_toep_sample(tj.p, zt.p, nt, ms, ng, fs.p, info.p, work.p, st0);
+    HIPCHK(hipEventRecord(ev[2], st0));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hinfo.data(), info.p, (size_t)ms * sizeof(int), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));
+    float part = 0.0f;
+    HIPCHK(hipEventElapsedTime(&part, ev[1], ev[2]));
+    rec_ms += part;
+    for (int k = 0; k < ms; ++k)
+      if (hinfo[k] != 0) {
+        g.err_latent = l_first + k; g.err_info = hinfo[k];
+        return fail(LMM_ERR_NOT_PD, "PosDefException: the prior Toeplitz matrix plus jitter %g is not positive definite; the Schur recursion "
+                    "failed (latent %d, step %d): raise jitter", jitter, g.err_latent, hinfo[k] - 1);
+      }
+    if (!P) {
+      for (int q = 0; q < ng; ++q) launch_toep_path(fs.p, nt, ng, q, mu.buf.p, nullptr, nullptr, ms, f + (size_t)q * ms * nt, st0);
+    } else {
+      Buf<double> d((size_t)ms * n), beta((size_t)ms * n), u(2 * (size_t)ms * n), gp((size_t)ms * nt), lo((size_t)ms * nt), up((size_t)ms * nt),
+          waste((size_t)ms * nt);
+      for (int q = 0; q < ng; ++q) {
+        launch_toep_obs(fs.p, nt, ng, q, sw.buf.p, xid.p + (size_t)q * xid.stride, n, ms, d.p, st0);
+        launch_toep_solve(P->pg.p, P->qg.p, d.p, n, ms, u.p, beta.p, st0);
+        launch_toep_gap(P->alpha.p, beta.p, n, nt, ms, gp.p, st0);
+        launch_toep_sym(t0.p, e0.p, gp.p, nt, ms, lo.p, up.p, waste.p, st0);
+        launch_toep_path(fs.p, nt, ng, q, mu.buf.p, lo.p, up.p, ms, f + (size_t)q * ms * nt, st0);
+      }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));            // the group's buffers go back to the pool
+    return (int)LMM_OK;
+  });
+  if (rc) return rc;
+  od.finish(st0);
+  HIPCHK(hipEventRecord(ev[3], st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  float all_ms = 0.0f;
+  HIPCHK(hipEventElapsedTime(&all_ms, ev[0], ev[3]));
+  g_toep_rand_ms[0] = rec_ms; g_toep_rand_ms[1] = all_ms - rec_ms;
+  return LMM_OK;
+}
+// What the two entry points refuse alike, after their own arguments
+static int toep_rand_args(int n, int horizon, double& jitter, int add_noise, int N, const double* z, const double* eps, const double* out) {
+  if (!z || !out) return fail(LMM_ERR_ARG, "bad arguments");
+  if (horizon < 0) return fail(LMM_ERR_ARG, "horizon must be >= 0 (horizon = %d)", horizon);
+  if (N < 1) return fail(LMM_ERR_ARG, "nsamples must be >= 1 (nsamples = %d)", N);
+  if (!std::isfinite(jitter)) return fail(LMM_ERR_ARG, "jitter must be finite (jitter = %g)", jitter);
+  if (jitter < 0.0) jitter = kDefaultJit.default_jitter;      // what lmm_lmm_rand adds to a latent prior: both paths draw from one law
+  if (add_noise && !eps) return fail(LMM_ERR_ARG, "eps is NULL");
+  if (horizon > 0 && n < 2) return fail(LMM_ERR_ARG, "a horizon continues the grid, which needs n >= 2 points (n = %d)", n);
+  return LMM_OK;
+}
+
+int lmm_oilmm_rand_toeplitz(const double* x, int n, int p, const double* U, const double* S, int m, double sigma2, const lmm_gp_t* gps,
+                            int latent_begin, int latent_end, int horizon, double jitter, int add_noise, int nsamples, const double* z,
+                            const double* eps, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (int rc = toep_rand_args(n, horizon, jitter, add_noise, nsamples, z, eps, out)) return rc;
+  ToepTrain T;
+  if (int rc = toep_inputs(false, x, n, p, U, S, m, sigma2, gps, latent_begin, latent_end, true, horizon, T)) return rc;
+  Uploaded Hd(shard_H(U, S, p, T.l0, T.ms), g.streams[0]);
+  const size_t nt = (size_t)n + horizon;
+  return toep_rand(T.lts + T.l0, T.l0, T.ms, T.x0, T.h, n, horizon, jitter, nullptr, p, Hd.buf.p, sigma2, add_noise, nsamples, z, (size_t)m * nt,
+                   (size_t)T.l0 * nt, nullptr, eps, out);
+  LMM_CATCH
+}
+
+int lmm_oilmm_toeplitz_post_rand(const lmm_toep_post_t* post, int horizon, double jitter, int add_noise, int nsamples, const double* z,
+                                 const double* xi, const double* eps, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !xi) return fail(LMM_ERR_ARG, "bad arguments");
+  const lmm_toep_post* P = post;
+  if (int rc = toep_rand_args(P->n, horizon, jitter, add_noise, nsamples, z, eps, out)) return rc;
+  if (g_f32) return toep_refuse_f32();
+  if (int rc = toep_check_n(P->n, true, horizon)) return rc;
+  const int ms = P->l1 - P->l0;
+  return toep_rand(P->ls->lat.data() + P->l0, P->l0, ms, P->x0, P->h, P->n, horizon, jitter, P, P->p, P->H.p, P->sigma2, add_noise, nsamples,
+                   z, (size_t)ms * (P->n + horizon), 0, xi, eps, out);
+  LMM_CATCH
+}
+
+int lmm_toeplitz_rand_last_ms(double* recursion_ms, double* rest_ms) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (recursion_ms) *recursion_ms = g_toep_rand_ms[0];
+  if (rest_ms) *rest_ms = g_toep_rand_ms[1];
+  return LMM_OK;
+}
+
+// Building block for tests: ONE matrix from DEVICE pointers, f[q n ..] = L z[q n ..] with L L' = Toeplitz(t), q < nsamples.
+int lmm_dev_toeplitz_sample(const double* t, const double* z, int n, int nsamples, double* f) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!t || !z || !f || n <= 0 || nsamples < 1) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return toep_refuse_f32();
+  if (int rc = toep_check_n(n, true)) return rc;
+  hipStream_t st0 = g.streams[0];
+  Buf<double> work(toep_sample_work(n, 1));
+  Buf<int> info(1);
+  int hinfo = 0;
+  launch_toep_sample(t, z, n, 1, nsamples, f, info.p, work.p, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  if (hinfo != 0) {
+    g.err_latent = 0; g.err_info = hinfo;
+    return fail(LMM_ERR_NOT_PD, "PosDefException: the Toeplitz matrix is not positive definite; the Schur recursion failed (latent 0, step %d)", hinfo - 1);
+  }
   return LMM_OK;
   LMM_CATCH
 }

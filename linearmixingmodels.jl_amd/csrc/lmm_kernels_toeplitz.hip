@@ -414,3 +414,246 @@ void launch_toep_schur_blocked(const double* t, const double* r, int n, int nb, 
   hipLaunchKernelGGL(toep_block_finish_kernel, flat, dim3(256), 0, st, (const double*)pp[cur], (const double*)qq[cur],
                      (const double*)rec[cur], n, p, q, out2, info);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Sampling (DESIGN.md 4.22 "Sampling"): f = L zeta with L L' = Toeplitz(t), the factor never stored.  Before step k shifts it, a holds
+// column k of L on the rows >= k, so f[i] += a[i] zeta[k] rides on the recursion where r[i] -= a[i] z rides in the blocked schedule,
+// whose launches (TOEPB_J steps each, ordered by the stream), one-wave replay and register windows this kernel keeps.  Only the
+// (a, b) side exists: a launch is max(na, 1) workgroups per latent and the state between launches is a, b in two copies, the samples
+// (in f itself, a row read and written by its owner alone) and one int of record per latent, in two copies.
+// A pass carries TOEPS_NS samples: a lane keeps TOEPS_NS accumulators for each of its TOEPB_EPT rows, and the TOEPB_J x TOEPS_NS
+// normals of the block are staged once in LDS beside the coefficients and read as broadcasts.  The rows k0 .. k0 + J - 1 turn into
+// pivots inside the block: they are finished by the replay wave, lane j row k0 + j, diagonal term included, and stored by workgroup 0
+// alone, as the record is.  Sample slots past the call's N read zeros and are never stored, and every accumulator is one chain of
+// fmas in step order whatever its slot: column q of an N-sample call is bitwise the one-sample call on its normals.
+// A bad pivot (or |rho| >= 1) stores nothing but the record, which holds 1 + the step.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void toeps_window(const double* __restrict__ ain, const double* __restrict__ bin, double* __restrict__ aout,
+                                             double* __restrict__ bout, double* f, int nq, const double4* coef, const double* zeta, int n,
+                                             int g0, int lane) {
+  double P[TOEPB_EPT], B[TOEPB_EPT], F[TOEPS_NS][TOEPB_EPT];
+  const int i0 = g0 + lane * TOEPB_EPT;              // g0 >= 0: no row above 0
+  const bool own = lane * TOEPB_EPT >= TOEPB_J;      // below the halo
+#pragma unroll
+  for (int e = 0; e < TOEPB_EPT; ++e) {
+    const int i = i0 + e;
+    const bool ok = i < n;
+    const int ii = ok ? i : 0;
+    const double xv = ain[ii], yv = bin[ii];
+    P[e] = ok ? xv : 0.0;
+    B[e] = ok ? yv : 0.0;
+#pragma unroll
+    for (int q = 0; q < TOEPS_NS; ++q) {
+      F[q][e] = 0.0;
+      if (ok && own && q < nq) F[q][e] = f[(size_t)q * n + i];      // a row's samples are read by its owner alone
+    }
+  }
+  for (int s0 = 0; s0 < TOEPB_J; s0 += TOEPB_EPT) {
+#pragma unroll
+    for (int s = 0; s < TOEPB_EPT; ++s) {
+      const double4 cf = coef[s0 + s];
+      const double rho = cf.x, c = cf.y, ic = cf.z;
+      const double* zt = zeta + (s0 + s) * TOEPS_NS;
+#pragma unroll
+      for (int q = 0; q < TOEPS_NS; ++q) {
+        const double zq = zt[q];
+#pragma unroll
+        for (int e = 0; e < TOEPB_EPT; ++e) F[q][e] = __builtin_fma(P[(e - s + TOEPB_EPT) % TOEPB_EPT], zq, F[q][e]);
+      }
+      const int ps = (2 * TOEPB_EPT - 1 - s) % TOEPB_EPT;      // the row that leaves the lane
+      P[ps] = __shfl_up(P[ps], 1);
+#pragma unroll
+      for (int e = 0; e < TOEPB_EPT; ++e) {
+        const int x = (e - s - 1 + 2 * TOEPB_EPT) % TOEPB_EPT;
+        const double an = (P[x] - rho * B[e]) * ic;
+        B[e] = c * B[e] - rho * an;
+        P[x] = an;
+      }
+    }
+  }
+  if (own) {
+#pragma unroll
+    for (int e = 0; e < TOEPB_EPT; ++e) {
+      const int i = i0 + e;
+      if (i < n) {
+        bout[i] = B[e]; aout[i] = P[e];
+#pragma unroll
+        for (int q = 0; q < TOEPS_NS; ++q)
+          if (q < nq) f[(size_t)q * n + i] = F[q][e];
+      }
+    }
+  }
+}
+
+// z, f: [latent][N][n]; this pass serves the samples [q0, min(q0 + TOEPS_NS, N)).  stin, stout: the record, one int per latent.
+__global__ __launch_bounds__(64 * TOEPB_WAVES) void toep_schur_sample_kernel(
+    const double* __restrict__ ain, const double* __restrict__ bin, double* __restrict__ aout, double* __restrict__ bout,
+    const double* __restrict__ z, double* f, const int* __restrict__ stin, int* __restrict__ stout, int n, int k0, int N, int q0) {
+  __shared__ double4 coef[TOEPB_J];                  // (rho, c, 1 / c, -)
+  __shared__ double zeta[TOEPB_J * TOEPS_NS];        // zeta[s][q]: the normal of step k0 + s, sample q0 + q
+  __shared__ int sbad;
+  const int l = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t off = (size_t)l * n;
+  if (stin[l] != 0) {      // failed in an earlier block: pass the record on
+    if (blockIdx.x == 0 && tid == 0) stout[l] = stin[l];
+    return;
+  }
+  const int nq = min(TOEPS_NS, N - q0);
+  z += ((size_t)l * N + q0) * n; f += ((size_t)l * N + q0) * n;
+  const int js = min(TOEPB_J, n - k0);      // steps of this block, the last of the recursion (n - 1) included
+  const int jr = min(TOEPB_J, n - 1 - k0);  // of which rotate
+  for (int w = tid; w < TOEPB_J * TOEPS_NS; w += 64 * TOEPB_WAVES) {
+    const int s = w % TOEPB_J, q = w / TOEPB_J;
+    const bool ok = s < js && q < nq;
+    const double v = z[ok ? (size_t)q * n + k0 + s : 0];
+    zeta[s * TOEPS_NS + q] = ok ? v : 0.0;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const int i = k0 + lane;
+    const bool in = i < n;
+    const double av = ain[off + (in ? i : k0)], bv = bin[off + (i + 1 < n ? i + 1 : k0)];
+    double X = in ? av : 0.0, Bq = i + 1 < n ? bv : 0.0, F[TOEPS_NS];
+#pragma unroll
+    for (int q = 0; q < TOEPS_NS; ++q) {
+      F[q] = 0.0;
+      if (in && q < nq && blockIdx.x == 0) F[q] = f[(size_t)q * n + i];      // workgroup 0 alone keeps these rows
+    }
+    int bad = 0;
+    for (int s = 0; s < js; ++s) {
+      const double pa = toepb_lane(X, s), pb = toepb_lane(Bq, s);
+      const double ipa = 1.0 / pa, rho = pb * ipa;
+      const bool last = k0 + s == n - 1;
+      if (!(pa > 0.0) || (!last && !(fabs(rho) < 1.0))) { bad = k0 + s + 1; break; }
+#pragma unroll
+      for (int q = 0; q < TOEPS_NS; ++q) F[q] = lane >= s ? __builtin_fma(X, zeta[s * TOEPS_NS + q], F[q]) : F[q];
+      if (last) break;
+      const double c = sqrt((1.0 - rho) * (1.0 + rho)), ic = 1.0 / c;
+      if (lane == 0) coef[s] = make_double4(rho, c, ic, 0.0);
+      const double an = (X - rho * Bq) * ic;
+      Bq = c * Bq - rho * an;
+      X = __shfl_up(an, 1);
+    }
+    if (lane >= jr) coef[lane] = make_double4(0.0, 1.0, 1.0, 0.0);
+    if (lane == 0) sbad = bad;
+    if (blockIdx.x == 0) {
+      if (lane == 0) stout[l] = bad;
+      if (!bad && lane < js) {
+#pragma unroll
+        for (int q = 0; q < TOEPS_NS; ++q)
+          if (q < nq) f[(size_t)q * n + i] = F[q];
+      }
+    }
+  }
+  __syncthreads();
+  if (sbad) return;
+  const int g0 = k0 + ((int)blockIdx.x * TOEPB_WAVES + wave) * TOEPB_V;
+  if (g0 + TOEPB_J >= n) return;
+  toeps_window(ain + off, bin + off, aout + off, bout + off, f, nq, coef, zeta, n, g0, lane);
+}
+
+// Before a pass: a = t / sqrt(t0) (a[0] the square root itself), b = a, the pass's samples 0, the record 0
+__global__ __launch_bounds__(256) void toep_sample_init_kernel(const double* __restrict__ t, int n, int N, int q0, double* __restrict__ a,
+                                                               double* __restrict__ b, double* __restrict__ f, int* __restrict__ st) {
+  const int l = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  const size_t off = (size_t)l * n;
+  if (i >= n) return;
+  const double s = sqrt(t[off]), v = i ? t[off + i] / s : s;
+  a[off + i] = v; b[off + i] = v;
+  for (int q = q0; q < min(q0 + TOEPS_NS, N); ++q) f[((size_t)l * N + q) * n + i] = 0.0;
+  if (i == 0) st[l] = 0;
+}
+__global__ void toep_sample_info_kernel(const int* __restrict__ st, int nb, int* __restrict__ info) {
+  const int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l < nb) info[l] = st[l];
+}
+
+size_t toep_sample_work(int n, int nb) { return 4 * (size_t)nb * n + (size_t)nb; }
+void launch_toep_sample(const double* t, const double* z, int n, int nb, int N, double* f, int* info, double* work, hipStream_t st) {
+  if (nb <= 0 || N <= 0) return;
+  const size_t M = (size_t)nb * n;
+  double* a[2] = {work, work + M};
+  double* b[2] = {work + 2 * M, work + 3 * M};
+  int* rec[2] = {reinterpret_cast<int*>(work + 4 * M), reinterpret_cast<int*>(work + 4 * M) + nb};
+  int cur = 0;
+  for (int q0 = 0; q0 < N; q0 += TOEPS_NS) {
+    cur = 0;
+    hipLaunchKernelGGL(toep_sample_init_kernel, dim3((n + 255) / 256, nb), dim3(256), 0, st, t, n, N, q0, a[0], b[0], f, rec[0]);
+    for (int k0 = 0; k0 < n; k0 += TOEPB_J, cur ^= 1) {
+      const int na = k0 + TOEPB_J < n ? (n - k0 - TOEPB_J + TOEPB_ROWS - 1) / TOEPB_ROWS : 0;
+      hipLaunchKernelGGL(toep_schur_sample_kernel, dim3(std::max(na, 1), nb), dim3(64 * TOEPB_WAVES), 0, st, (const double*)a[cur],
+                         (const double*)b[cur], a[cur ^ 1], b[cur ^ 1], z, f, (const int*)rec[cur], rec[cur ^ 1], n, k0, N, q0);
+    }
+  }
+  hipLaunchKernelGGL(toep_sample_info_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, (const int*)rec[cur], nb, info);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Pathwise conditioning around the products (lmm_api.hip, toep_rand): elementwise kernels, a thread per point, blockIdx.y the latent.
+// ---------------------------------------------------------------------------------------------------
+// zt[l][q][i] = z[q zs + l n + i]: the callers' normals ([sample][latent][n], samples zs apart) in the layout of launch_toep_sample
+__global__ __launch_bounds__(256) void toep_gather_kernel(const double* __restrict__ z, size_t zs, int n, int N, double* __restrict__ zt) {
+  const int l = blockIdx.y, q = blockIdx.z, i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) zt[((size_t)l * N + q) * n + i] = z[(size_t)q * zs + (size_t)l * n + i];
+}
+// tj = t + jitter e0, and e = t[0] e0 (so that L(e) = t[0] I); e may be nullptr
+__global__ __launch_bounds__(256) void toep_prior_kernel(const double* __restrict__ t, double jitter, int n, double* __restrict__ tj,
+                                                         double* __restrict__ e) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const size_t off = (size_t)blockIdx.y * n;
+  if (i >= n) return;
+  const double v = t[off + i];
+  tj[off + i] = i ? v : v + jitter;
+  if (e) e[off + i] = i ? 0.0 : v;
+}
+// d[l][i] = f[l][q][i] + sw[l] xi[l n + i], i < n: the prior path's pseudo-observation (f: [latent][N][nt], sample q)
+__global__ __launch_bounds__(256) void toep_obs_kernel(const double* __restrict__ f, int nt, int N, int q, const double* __restrict__ sw,
+                                                       const double* __restrict__ xi, int n, double* __restrict__ d) {
+  const int l = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) d[(size_t)l * n + i] = __builtin_fma(sw[l], xi[(size_t)l * n + i], f[((size_t)l * N + q) * nt + i]);
+}
+// g[l][i] = alpha[l][i] - beta[l][i] for i < n, 0 for n <= i < nt
+__global__ __launch_bounds__(256) void toep_gap_kernel(const double* __restrict__ alpha, const double* __restrict__ beta, int n, int nt,
+                                                       double* __restrict__ gp) {
+  const int l = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i < nt) gp[(size_t)l * nt + i] = i < n ? alpha[(size_t)l * n + i] - beta[(size_t)l * n + i] : 0.0;
+}
+// out[l][i] = mu[l] + f[l][q][i] (+ lo[l][i] + up[l][i]): the latent paths of sample q, [latent][nt]
+__global__ __launch_bounds__(256) void toep_path_kernel(const double* __restrict__ f, int nt, int N, int q, const double* __restrict__ mu,
+                                                        const double* __restrict__ lo, const double* __restrict__ up,
+                                                        double* __restrict__ out) {
+  const int l = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nt) return;
+  const size_t o = (size_t)l * nt + i;
+  double v = mu[l] + f[((size_t)l * N + q) * nt + i];
+  if (lo) v += lo[o] + up[o];
+  out[o] = v;
+}
+
+void launch_toep_gather(const double* z, size_t zs, int n, int nb, int N, double* zt, hipStream_t st) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(toep_gather_kernel, dim3((n + 255) / 256, nb, N), dim3(256), 0, st, z, zs, n, N, zt);
+}
+void launch_toep_prior(const double* t, double jitter, int n, int nb, double* tj, double* e, hipStream_t st) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(toep_prior_kernel, dim3((n + 255) / 256, nb), dim3(256), 0, st, t, jitter, n, tj, e);
+}
+void launch_toep_obs(const double* f, int nt, int N, int q, const double* sw, const double* xi, int n, int nb, double* d, hipStream_t st) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(toep_obs_kernel, dim3((n + 255) / 256, nb), dim3(256), 0, st, f, nt, N, q, sw, xi, n, d);
+}
+void launch_toep_gap(const double* alpha, const double* beta, int n, int nt, int nb, double* gp, hipStream_t st) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(toep_gap_kernel, dim3((nt + 255) / 256, nb), dim3(256), 0, st, alpha, beta, n, nt, gp);
+}
+void launch_toep_sym(const double* t, const double* e, const double* v, int n, int nb, double* lo, double* up, double* waste, hipStream_t st) {
+  if (nb <= 0) return;
+  const dim3 grid((n + 255) / 256, nb);
+  hipLaunchKernelGGL(toep_tri_kernel<true>, grid, dim3(256), 0, st, e, t, v, v, n, lo, (double*)nullptr);      // L(t) v - t[0] v
+  hipLaunchKernelGGL(toep_tri_kernel<false>, grid, dim3(256), 0, st, e, t, v, v, n, up, waste);                // L(t)' v (and t[0] v)
+}
+void launch_toep_path(const double* f, int nt, int N, int q, const double* mu, const double* lo, const double* up, int nb, double* out,
+                      hipStream_t st) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(toep_path_kernel, dim3((nt + 255) / 256, nb), dim3(256), 0, st, f, nt, N, q, mu, lo, up, out);
+}

@@ -32,6 +32,22 @@ ToepBlockPlan toep_block_plan(int n, int nb);
 // Outputs as launch_toep_schur's; work: toep_block_plan(n, nb).work doubles.
 void launch_toep_schur_blocked(const double* t, const double* r, int n, int nb, double* out2, double* p, double* q, int* info,
                                double* work, hipStream_t st);
+// Joint samples (DESIGN.md 4.22 "Sampling"): f[l][q][..] = L_l z[l][q][..] with L_l L_l' = Toeplitz(t[l n ..]), for the N samples
+// q of each of the nb matrices, TOEPS_NS samples per pass of the blocked recursion; the factor is never stored.  Any n <= TOEPB_MAX_N.
+// info[l] = 0 or 1 + the failing step (f is then not a sample); work: toep_sample_work(n, nb) doubles.
+#define TOEPS_NS 4                            // samples of a pass: 4 x TOEPB_EPT accumulators (64 VGPRs) beside a and b (32)
+size_t toep_sample_work(int n, int nb);
+void launch_toep_sample(const double* t, const double* z, int n, int nb, int N, double* f, int* info, double* work, hipStream_t st);
+// out = T(t) v = L(t) v + L(t)' v - t[0] v in two parts on toep_tri_kernel: lo = L(t) v - t[0] v, up = L(t)' v; e = t[0] e0
+// (launch_toep_prior); v, lo, up, waste: [matrix][n]
+void launch_toep_sym(const double* t, const double* e, const double* v, int n, int nb, double* lo, double* up, double* waste, hipStream_t st);
+// The elementwise steps of pathwise conditioning (lmm_kernels_toeplitz.hip, above their kernels)
+void launch_toep_gather(const double* z, size_t zs, int n, int nb, int N, double* zt, hipStream_t st);
+void launch_toep_prior(const double* t, double jitter, int n, int nb, double* tj, double* e, hipStream_t st);
+void launch_toep_obs(const double* f, int nt, int N, int q, const double* sw, const double* xi, int n, int nb, double* d, hipStream_t st);
+void launch_toep_gap(const double* alpha, const double* beta, int n, int nt, int nb, double* gp, hipStream_t st);
+void launch_toep_path(const double* f, int nt, int N, int q, const double* mu, const double* lo, const double* up, int nb, double* out,
+                      hipStream_t st);
 // alpha[l n ..] = K_l^-1 r_l = L(q) L(q)' r - L(p) L(p)' r; u: 2 nb n doubles of scratch
 void launch_toep_solve(const double* p, const double* q, const double* r, int n, int nb, double* u, double* alpha, hipStream_t st);
 // sd[l n + d] = sum_i (K_l^-1)_{i, i + d} and ad[l n + d] = sum_i alpha_i alpha_{i + d}

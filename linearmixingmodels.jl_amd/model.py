@@ -1490,13 +1490,28 @@ class ToeplitzPosterior:
     on the fly, in O(n + ns) memory.  The error of var is relative to the prior variance, not to a small posterior variance.
     Built by toeplitz_posterior; freed by close(), on leaving a `with` block or with the object."""
 
-    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float):
-        self._ptr, self.n, self.p, self.logpdf = ptr, n, p, logpdf
+    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float, m: int = 0):
+        self._ptr, self.n, self.p, self.logpdf, self.m = ptr, n, p, logpdf, m
 
     def close(self) -> None:
         if self._ptr:
             ptr, self._ptr = self._ptr, None
             L.load().lmm_toeplitz_post_destroy(ptr)
+
+    def rand(self, rng, N: Optional[int] = None, add_noise: bool = True, horizon: int = 0, jitter: Optional[float] = None):
+        """Joint samples of post(x, sigma2) over the training grid and its continuation by `horizon` further points, from the handle
+        alone (pathwise conditioning; DESIGN.md 4.22 "Sampling"): (n_tot * p,) by outputs for N=None, else (n_tot * p, N), n_tot =
+        n + horizon, the first n points the training grid.  rng, the draw order and jitter as toeplitz_rand's.  The handle is not
+        changed.  Every refusal comes before any library call."""
+        if not self._ptr:
+            raise ValueError("ToeplitzPosterior: the posterior has been closed")
+        horizon, jit = _toeplitz_rand_args("ToeplitzPosterior.rand", self.n, N, horizon, jitter)
+        Ns = 1 if N is None else int(N)
+        z, xi, eps = _toeplitz_normals(rng, self.m, self.n, horizon, self.p, Ns, True, add_noise)
+        out = _empty_for(rng, Ns, (self.n + horizon) * self.p)
+        L.check(L.load().lmm_oilmm_toeplitz_post_rand(self._ptr, horizon, jit, int(add_noise), Ns, L.Arr(z).ptr, L.Arr(xi).ptr,
+                                                      None if eps is None else L.Arr(eps).ptr, L.Arr(out, True).ptr))
+        return out[0] if N is None else out.T
 
     def __enter__(self):
         return self
@@ -1566,7 +1581,74 @@ def toeplitz_posterior(fx: "FiniteGP", y, blocked: bool = False) -> ToeplitzPost
     lib = L.load()
     L.check((lib.lmm_oilmm_toeplitz_posterior_create_blocked if blocked else lib.lmm_oilmm_toeplitz_posterior_create)(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2),
                                                          gps, 0, m, C.byref(ptr), C.byref(out)))
-    return ToeplitzPosterior(ptr, x.n, p, out.value)
+    return ToeplitzPosterior(ptr, x.n, p, out.value, m)
+
+
+def _toeplitz_rand_args(what: str, n: int, N, horizon, jitter):
+    """What toeplitz_rand and ToeplitzPosterior.rand refuse alike; returns (horizon, the jitter argument of the library: < 0 is the
+    default that lmm_lmm_rand applies to a latent prior)."""
+    if L.get_compute_dtype() == "f32":
+        raise NotImplementedError(f"{what}: the Toeplitz path is Float64 only (set_compute_dtype('f64'))")
+    if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon < 0:
+        raise ValueError(f"{what}: horizon is an integer >= 0")
+    if N is not None and (int(N) != N or N < 1):
+        raise ValueError(f"{what}: N is None or a number of samples >= 1")
+    if jitter is not None and not (np.isfinite(jitter) and jitter >= 0.0):
+        raise ValueError(f"{what}: jitter is None or finite and >= 0")
+    cap = L.load().lmm_toeplitz_blocked_max_n()
+    if n + horizon > cap:
+        raise NotImplementedError(f"{what}: the Toeplitz path serves n + horizon <= {cap} points (lmm_toeplitz_blocked_max_n; n + horizon = {n + horizon})")
+    if horizon > 0 and n < 2:
+        raise ValueError(f"{what}: a horizon continues the grid, which needs n >= 2 points")
+    return int(horizon), -1.0 if jitter is None else float(jitter)
+
+
+def _toeplitz_normals(rng, m: int, n: int, horizon: int, p: int, Ns: int, with_data: bool, add_noise: bool):
+    """The normals of Ns samples in the draw order of toeplitz_rand, where rng's normals live"""
+    nt = n + horizon
+    z = _empty_for(rng, Ns, m * nt)
+    xi = _empty_for(rng, Ns, m * n) if with_data else None
+    eps = _empty_for(rng, Ns, nt * p) if add_noise else None
+    for q in range(Ns):
+        for l in range(m):
+            z[q, l * nt:(l + 1) * nt] = rng.standard_normal(nt)
+        if xi is not None:
+            xi[q] = rng.standard_normal(m * n)
+        if eps is not None:
+            eps[q] = rng.standard_normal(nt * p)
+    return z, xi, eps
+
+
+def toeplitz_rand(rng, fx: "FiniteGP", y=None, N: Optional[int] = None, add_noise: bool = True, horizon: int = 0,
+                  jitter: Optional[float] = None):
+    """Joint samples of the models toeplitz_logpdf serves, in O(n_tot^2) time and O(n_tot) memory per latent, n_tot = n + horizon: of
+    the prior fx (y=None), or of the posterior given y (toeplitz_posterior(fx, y, blocked=True) and that handle's rand), over the grid
+    of fx.x and `horizon` further points that continue it.  A latent's prior path is f = L zeta with L L' = K + jitter I, column by
+    column of L as the Schur recursion passes it, L never stored (DESIGN.md 4.22 "Sampling"); a posterior path is pathwise conditioning.
+    `rng` is a NumPy Generator or a DeviceNormals; buffers and the result live where the normals do.  Draw order, per sample:
+      for each latent in order, standard_normal(n_tot);
+      then, with y only, standard_normal(m * n)       (latent-major);
+      then, if add_noise, standard_normal(n_tot * p)  (by outputs).
+    Returns (n_tot * p,) by outputs for N=None, else (n_tot * p, N); the first n points are the training grid.  jitter is added to the
+    diagonal of each latent's prior Gram; None: what rand applies to a latent prior.  A prior the recursion cannot factor raises
+    PosDefException naming latent and step: raise jitter (periodic Grams have a numerical rank of a few dozen).  Every refusal comes
+    before any library call."""
+    f, x = fx.f, fx.x
+    yc = _toeplitz_args(fx, np.broadcast_to(0.0, (x.n * x.out_dim,)) if y is None else y, "toeplitz_rand")
+    horizon, jit = _toeplitz_rand_args("toeplitz_rand", x.n, N, horizon, jitter)
+    if y is not None:
+        with toeplitz_posterior(fx, yc, blocked=True) as post:
+            return post.rand(rng, N, add_noise, horizon, jitter)
+    Ns = 1 if N is None else int(N)
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    z, _, eps = _toeplitz_normals(rng, m, x.n, horizon, p, Ns, False, add_noise)
+    out = _empty_for(rng, Ns, (x.n + horizon) * p)
+    L.check(L.load().lmm_oilmm_rand_toeplitz(L.Arr(x.x.reshape(-1)).ptr, x.n, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps, 0, m, horizon, jit,
+                                             int(add_noise), Ns, L.Arr(z).ptr, None if eps is None else L.Arr(eps).ptr,
+                                             L.Arr(out, True).ptr))
+    return out[0] if N is None else out.T
 
 
 def statespace_rand(rng, fx: "FiniteGP", y=None, N: Optional[int] = None, add_noise: bool = True, xs=None):
