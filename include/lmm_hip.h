@@ -929,6 +929,41 @@ int lmm_oilmm_toeplitz_post_rand(const lmm_toep_post_t* post, int horizon, doubl
                                  const double* xi, const double* eps /* iff add_noise */, double* out);
 int lmm_toeplitz_rand_last_ms(double* recursion_ms, double* rest_ms);
 int lmm_dev_toeplitz_sample(const double* t, const double* z, int n, int nsamples, double* f);
+/* Toeplitz: the joint predictive at new inputs (DESIGN.md 4.22 "Joint predictive").  Per latent the ns x ns posterior covariance
+ *   C_l = K_l(xs, xs) - (Uq' Uq - Up' Up),  Uq = L(q)' K*, Up = L(p)' K*,
+ * from the handle's generators: the predict GEMM of lmm_oilmm_toeplitz_post_mean_and_var keeps its products in chunks of rows, a Gram
+ * kernel on v_mfma_f64_16x16x4_f64 contracts them (one owner per tile, a fixed order: bitwise reproducible, C[i][j] depends on xs_i and
+ * xs_j only and not on the chunking), and C_l + d_l I is factored by the dense path's batched Cholesky.  Memory is
+ * O(n + chunk ns + ns^2) per latent for any n the handle holds, on either schedule; ns <= lmm_toeplitz_joint_max_ns() (4096).  The
+ * error of C is relative to kappa(0), as var's.  The handle is const: every later answer is bitwise what it was, after a refusal too.
+ *   lmm_toeplitz_joint_shape : the cap on ns, the edge of the Gram kernel's tile and the rows of a chunk that the plan takes for ONE
+ *                    latent at ns = the cap (chunks are whole multiples of 256 rows and no shorter for fewer queries); any may be NULL.
+ *   lmm_oilmm_toeplitz_post_logpdf : *out = log p(ys | the training data), as logpdf(post(xs, sigma2), ys) on the dense path.  xs: ns
+ *                    values in any order; ys: ns x p by outputs, complete; xs, ys: host or device.  sigma2 < 0: the handle's own, else
+ *                    finite and > 0.  ys goes through the front end of lmm_oilmm_toeplitz_posterior_create, the latent means are those
+ *                    of lmm_oilmm_toeplitz_post_mean_and_var, and d_l = sigma2 / S_l.
+ *   lmm_oilmm_toeplitz_post_rand_at : nsamples joint samples at xs: per latent f_l = mu*_l + chol(C_l + jitter I) z_l, mixed and
+ *                    given noise as lmm_oilmm_toeplitz_post_rand does.  z: per sample, for each latent of the handle's shard, ns
+ *                    normals; eps: per sample ns p by outputs (iff add_noise); out: per sample ns x p by outputs; host or device.
+ *                    jitter < 0: the default of lmm_oilmm_toeplitz_post_rand.  Sample q is bitwise the one-sample call on its normals.
+ *                    A C_l + jitter I that cannot be factored -> LMM_ERR_NOT_PD with the latent in lmm_last_error_detail: raise jitter.
+ *   Refusals of both: a NULL handle, xs, ys / z or out, ns < 1, nsamples < 1, a jitter or sigma2 out of range, eps NULL with add_noise
+ *                    -> LMM_ERR_ARG; the fp32 mode and ns > the cap (naming lmm_toeplitz_joint_max_ns) -> LMM_ERR_UNSUPPORTED; a
+ *                    non-finite xs[i] -> LMM_ERR_ARG naming i; a NaN in ys -> LMM_ERR_UNSUPPORTED naming the point.
+ *   lmm_dev_toeplitz_predict_cov : building block for tests, DEVICE pointers, ONE latent (gp on the host): element (i, j), i >= j, of
+ *                    C + diag I at cov[j ldc + i] (ldc >= ns; nothing else of cov is written).  chunk_rows: 0 takes the plan's rows per
+ *                    chunk, any other multiple of 256 forces that chunking.  n <= lmm_toeplitz_blocked_max_n().
+ *   lmm_toeplitz_joint_last_ms : where the last of the three calls above that ran spent its device time, by events on its stream: the
+ *                    storing GEMM, the Gram kernel, and the finish kernel with the factorisation (0 for the building block); any may
+ *                    be NULL.  For tools/toeplitz_joint_bench.py. */
+int lmm_toeplitz_joint_max_ns(void);
+int lmm_toeplitz_joint_last_ms(double* gemm_ms, double* gram_ms, double* factor_ms);
+int lmm_toeplitz_joint_shape(int* max_ns, int* tile, int* chunk_rows);
+int lmm_oilmm_toeplitz_post_logpdf(const lmm_toep_post_t* post, const double* xs, int ns, const double* ys, double sigma2, double* out);
+int lmm_oilmm_toeplitz_post_rand_at(const lmm_toep_post_t* post, const double* xs, int ns, double jitter, int add_noise, int nsamples,
+                                    const double* z, const double* eps /* iff add_noise */, double* out);
+int lmm_dev_toeplitz_predict_cov(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* xs, int ns,
+                                 double diag, int chunk_rows, double* cov, int ldc);
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
                               const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,

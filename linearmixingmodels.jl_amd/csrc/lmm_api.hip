@@ -5866,6 +5866,7 @@ struct lmm_toep_post {
   Buf<double> pg, qg, alpha;          // per latent of the shard, [latent][n]
   Buf<double> H;                      // p x (l1 - l0), column-major: H = U sqrt(S) of the shard
   std::vector<double> w;              // per latent of the shard: its noise sigma2 / S_l (read by lmm_oilmm_toeplitz_post_rand)
+  std::vector<double> U, S;           // the mixing as the handle was built with it (p x m, m): the front end of lmm_oilmm_toeplitz_post_logpdf
 };
 
 static const size_t kToepPredictScratch = size_t(1) << 23;      // doubles of partials a query chunk may take (64 MB)
@@ -5943,6 +5944,7 @@ static int toep_posterior_create(const double* x, int n, const double* y, int p,
   P->x0 = ends[0]; P->h = n > 1 ? (ends[1] - ends[0]) / (double)(n - 1) : 0.0;
   P->pg = std::move(W.p); P->qg = std::move(W.q);
   for (int k = 0; k < T.ms; ++k) P->w.push_back(sigma2 / S[T.l0 + k]);
+  P->U.assign(U, U + (size_t)p * m); P->S.assign(S, S + m);
   const std::vector<double> Hs = shard_H(U, S, p, T.l0, T.ms);
   P->H = Buf<double>(std::max<size_t>(Hs.size(), 1));
   HIPCHK(hipMemcpyAsync(P->H.p, Hs.data(), Hs.size() * sizeof(double), hipMemcpyHostToDevice, st0));
@@ -6010,6 +6012,248 @@ int lmm_dev_toeplitz_predict(double x0, double h, int n, const lmm_gp_t* gp, con
   if (int rc = toep_check_finite(xs, ns)) return rc;
   return toep_predict_latents(x0, h, n, ls->lat.data(), 1, p, q, alpha, xs, ns, false, mean, var);
   LMM_CATCH
+}
+
+// ---- the joint predictive at new inputs (DESIGN.md 4.22 "Joint predictive") --------------------------------------------------------
+int lmm_toeplitz_joint_max_ns(void) { return TOEP_JOINT_MAX_NS; }
+int lmm_toeplitz_joint_shape(int* max_ns, int* tile, int* chunk_rows) {
+  if (max_ns) *max_ns = TOEP_JOINT_MAX_NS;
+  if (tile) *tile = TOEP_JOINT_T;
+  if (chunk_rows) *chunk_rows = toep_joint_plan(TOEPB_MAX_N, TOEP_JOINT_MAX_NS, 1).rows;
+  return LMM_OK;
+}
+static int toep_joint_check_ns(int ns) {
+  if (ns <= TOEP_JOINT_MAX_NS) return LMM_OK;
+  return fail(LMM_ERR_UNSUPPORTED, "the joint predictive of the Toeplitz path serves ns <= %d queries (lmm_toeplitz_joint_max_ns; ns = %d)",
+              TOEP_JOINT_MAX_NS, ns);
+}
+
+// Where the last joint call spent its time (lmm_toeplitz_joint_last_ms): the storing GEMM, the Gram kernel, the factorisation (the
+// finish kernel and potrf_batch), by events on the call's stream.  mark(stage, st) opens a stage (stage < 0: only closes the one
+// before); read() sums the intervals once the stream has drained.  The events come from the profiler's pool and go back to it.
+static double g_toep_joint_ms[3] = {0.0, 0.0, 0.0};
+struct ToepJointClock {
+  std::vector<std::pair<hipEvent_t, int>> marks;
+  void mark(int stage, hipStream_t st) {
+    hipEvent_t e;
+    if (!g.ev_pool.empty()) { e = g.ev_pool.back(); g.ev_pool.pop_back(); }
+    else HIPCHK(hipEventCreate(&e));
+    marks.emplace_back(e, stage);
+    HIPCHK(hipEventRecord(e, st));
+  }
+  void read() {
+    double ms[3] = {0.0, 0.0, 0.0};
+    for (size_t i = 0; i + 1 < marks.size(); ++i)
+      if (marks[i].second >= 0) {
+        float part = 0.0f;
+        HIPCHK(hipEventElapsedTime(&part, marks[i].first, marks[i + 1].first));
+        ms[marks[i].second] += part;
+      }
+    std::copy(ms, ms + 3, g_toep_joint_ms);
+  }
+  ~ToepJointClock() { for (auto& mk : marks) g.ev_pool.push_back(mk.first); }
+};
+
+// G_l = Uq' Uq - Up' Up at the queries xsd of the nb <= LMM_MAX_BATCH latents with descriptors dd (device) and generators pg, qg
+// ([latent][n], device), into G.p[l] (leading dimension ld; Dims(ns, .) holds the tiles that are written), on stream st: passes of
+// plan.lat latents, chunks of plan.rows rows, the storing GEMM and then the Gram kernel per chunk.  U is scratch of the call.
+static void toep_joint_gram(double x0, double h, int n, const LatentDev* dd, int nb, const double* pg, const double* qg, const double* xsd,
+                            int ns, int mode, int rows_forced, const BatchPtr& G, int ld, ToepJointClock& ck, hipStream_t st) {
+  const ToepJointPlan pl = toep_joint_plan(n, ns, nb, rows_forced);
+  const int top = rup(n, TOEP_PRED_R), NC = rup(ns, TOEP_JOINT_T);
+  double* U = call_scratch((size_t)pl.lat * 2 * pl.rows * toep_joint_nsp(ns));
+  for (int k0 = 0; k0 < nb; k0 += pl.lat) {
+    const int nl = std::min(pl.lat, nb - k0);
+    BatchPtr Gs{};
+    for (int j = 0; j < nl; ++j) {
+      Gs.p[j] = G.p[k0 + j];
+      guard_extent(Gs.p[j], NC, ld, NC, false, "joint predictive (Gram tiles)");
+    }
+    for (int row0 = 0; row0 < top; row0 += pl.rows) {
+      const int rows = std::min(pl.rows, top - row0);
+      ck.mark(0, st);
+      launch_toep_predict_store(x0, h, n, dd + k0, pg + (size_t)k0 * n, qg + (size_t)k0 * n, xsd, ns, nl, mode, row0, rows, U, st);
+      ck.mark(1, st);
+      launch_toep_gram(U, n, row0, rows, ns, Gs, ld, nl, row0 == 0, st);
+    }
+  }
+  ck.mark(-1, st);
+  HIPCHK(hipGetLastError());
+}
+
+// The factor matrices of the handle's latents at the queries: per batch of latents C_l + diag[k] I (and the rider row rider[k ns ..],
+// or none) in the layout Ds, factored by potrf_batch; after(batch, matrices) then reads the factors on the batch's stream.  A factor
+// that fails is LMM_ERR_NOT_PD naming the latent.  Returns with streams[0] drained.
+template <typename After>
+static int toep_joint_factor(const lmm_toep_post* P, const double* xsd, int ns, const std::vector<double>& diag, const double* rider,
+                             const Dims& Ds, After&& after) {
+  const int ms = P->l1 - P->l0;
+  if (ms == 0) return LMM_OK;
+  hipStream_t st0 = g.streams[0];
+  const Latent* lts = P->ls->lat.data() + P->l0;
+  std::vector<LatentDev> hd(ms);
+  for (int k = 0; k < ms; ++k) hd[k] = lts[k].dev();
+  Buf<LatentDev> dd(ms);
+  HIPCHK(hipMemcpyAsync(dd.p, hd.data(), (size_t)ms * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  Uploaded dg(diag, st0);
+  const int mode = sum_mode(lts, 0, ms);
+  FanOut F = FanOut::one_slot(ms);
+  int* info = F.alloc_info();
+  std::vector<Buf<double>> B, WB;
+  for (int j = 0; j < F.nb_per; ++j) { B.emplace_back(Ds.elems()); WB.emplace_back((size_t)(Ds.NC / 64) * 4096); }
+  ToepJointClock ck;
+  F.run([&](const FanBatch& b) {
+    Batch Bt;
+    for (int j = 0; j < b.nb; ++j) Bt.add(B[j].p, WB[j].p, info + b.k0 + j);
+    toep_joint_gram(P->x0, P->h, P->n, dd.p + b.k0, b.nb, P->pg.p + (size_t)b.k0 * P->n, P->qg.p + (size_t)b.k0 * P->n, xsd, ns, mode, 0,
+                    Bt.A, Ds.ld, ck, b.st);
+    ck.mark(2, b.st);
+    launch_toep_cov_finish(dd.p + b.k0, xsd, ns, Bt.A, Ds.ld, Bt.A, Ds.ld, Ds.NR, Ds.NC, dg.buf.p + b.k0,
+                           rider ? rider + (size_t)b.k0 * ns : nullptr, true, b.nb, mode, b.st);
+    potrf_batch(Bt, Ds.ld, Ds.NR, Ds.NC, ns, b.st);
+    ck.mark(-1, b.st);
+    after(b, Bt);
+  });
+  HIPCHK(hipGetLastError());
+  const int rc = F.check(P->l0);
+  ck.read();
+  return rc;
+}
+
+int lmm_oilmm_toeplitz_post_logpdf(const lmm_toep_post_t* post, const double* xs, int ns, const double* ys, double sigma2, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !xs || !ys || !out) return fail(LMM_ERR_ARG, "bad arguments");
+  if (ns < 1) return fail(LMM_ERR_ARG, "ns must be >= 1 (ns = %d)", ns);
+  if (g_f32) return toep_refuse_f32();
+  if (int rc = toep_joint_check_ns(ns)) return rc;
+  const lmm_toep_post* P = post;
+  if (!(sigma2 < 0.0) && (!std::isfinite(sigma2) || !(sigma2 > 0.0)))
+    return fail(LMM_ERR_ARG, "Toeplitz posterior: sigma2 must be finite and > 0, or < 0 for the handle's own (sigma2 = %g)", sigma2);
+  const double s2 = sigma2 < 0.0 ? P->sigma2 : sigma2;
+  const int p = P->p, m = P->m, ms = P->l1 - P->l0, mk = std::max(ms, 1);
+  hipStream_t st0 = g.streams[0];
+  DevIn xsd(xs, (size_t)ns, st0), ysd(ys, (size_t)ns * p, st0);
+  if (int rc = toep_check_finite(xsd.p, ns)) return rc;
+  {
+    Buf<unsigned long long> masks((size_t)ns * ((p + 63) / 64));
+    Buf<int> pt(ns);
+    std::vector<int> hpt(ns);
+    launch_missing_masks(ysd.p, ns, p, masks.p, pt.p, st0);
+    HIPCHK(hipMemcpyAsync(hpt.data(), pt.p, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));
+    for (int t = 0; t < ns; ++t)
+      if (hpt[t] != p) {
+        g.err_latent = -1; g.err_info = t;
+        return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path needs complete data: point %d has a NaN in ys (per-point noise is not served)", t);
+      }
+  }
+  const Latent* lts = P->ls->lat.data();
+  const std::vector<double> means = latent_means(lts, m);
+  MissingFront F;                     // z = (T ys)_l - mean_l
+  if (int rc = missing_front(ysd.p, ns, p, P->U.data(), P->S.data(), m, s2, means.data(), P->l0, P->l1, false, F)) return rc;
+  Buf<double> ml((size_t)ns * mk), rid((size_t)ns * mk), outd(mk);
+  if (int rc = toep_predict_latents(P->x0, P->h, P->n, lts + P->l0, ms, P->pg.p, P->qg.p, P->alpha.p, xsd.p, ns, false, ml.p, nullptr)) return rc;
+  std::vector<double> diag(mk, 0.0), lml(mk, 0.0);
+  for (int k = 0; k < ms; ++k) {
+    diag[k] = s2 / P->S[P->l0 + k];
+    launch_vec_lin(F.z.p + (size_t)k * ns, ml.p + (size_t)k * ns, -1.0, ns, rid.p + (size_t)k * ns, st0);
+  }
+  const Dims Ds(ns, 1);
+  if (int rc = toep_joint_factor(P, xsd.p, ns, diag, rid.p, Ds, [&](const FanBatch& b, const Batch& Bt) {
+        launch_lml_reduce(Bt.A, b.nb, Ds.ld, ns, Ds.NC, 1, outd.p + b.k0, b.st);
+        HIPCHK(hipMemcpyAsync(lml.data() + b.k0, outd.p + b.k0, (size_t)b.nb * sizeof(double), hipMemcpyDeviceToHost, b.st));
+      })) return rc;
+  double total = 0.0;
+  for (int k = 0; k < ms; ++k) total += lml[k];
+  *out = total + F.reg(ns, m, s2);
+  return LMM_OK;
+  LMM_CATCH
+}
+
+static int toep_rand_args(int n, int horizon, double& jitter, int add_noise, int N, const double* z, const double* eps, const double* out);
+int lmm_oilmm_toeplitz_post_rand_at(const lmm_toep_post_t* post, const double* xs, int ns, double jitter, int add_noise, int nsamples,
+                                    const double* z, const double* eps, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !xs) return fail(LMM_ERR_ARG, "bad arguments");
+  if (ns < 1) return fail(LMM_ERR_ARG, "ns must be >= 1 (ns = %d)", ns);
+  const lmm_toep_post* P = post;
+  if (int rc = toep_rand_args(P->n, 0, jitter, add_noise, nsamples, z, eps, out)) return rc;
+  if (g_f32) return toep_refuse_f32();
+  if (int rc = toep_joint_check_ns(ns)) return rc;
+  const int p = P->p, ms = P->l1 - P->l0, mk = std::max(ms, 1);
+  hipStream_t st0 = g.streams[0];
+  DevIn xsd(xs, (size_t)ns, st0), zd(z, (size_t)ns * ms * nsamples, st0), epsd(add_noise ? eps : nullptr, (size_t)ns * p * nsamples, st0);
+  if (int rc = toep_check_finite(xsd.p, ns)) return rc;
+  Buf<double> ml((size_t)ns * mk), X((size_t)ns * mk * nsamples), part(strip_partial_elems(ns, ns, 1));
+  if (int rc = toep_predict_latents(P->x0, P->h, P->n, P->ls->lat.data() + P->l0, ms, P->pg.p, P->qg.p, P->alpha.p, xsd.p, ns, true, ml.p,
+                                    nullptr)) return rc;
+  const Dims Ds(ns, 0);
+  const std::vector<double> diag(mk, jitter);
+  if (int rc = toep_joint_factor(P, xsd.p, ns, diag, nullptr, Ds, [&](const FanBatch& b, const Batch& Bt) {
+        for (int j = 0; j < b.nb; ++j)
+          for (int q = 0; q < nsamples; ++q) {      // sample q reads nothing of another sample: bitwise the one-sample call
+            double* Xq = X.p + ((size_t)q * ms + b.k0 + j) * ns;
+            launch_trmv_lower(Bt.A.p[j], Ds.ld, ns, zd.p + ((size_t)q * ms + b.k0 + j) * ns, 0.0, part.p, Xq, b.st);
+            launch_vec_lin(Xq, ml.p + (size_t)(b.k0 + j) * ns, 1.0, ns, Xq, b.st);
+          }
+      })) return rc;
+  DevOut od(out, (size_t)ns * p * nsamples);
+  for (int q = 0; q < nsamples; ++q)
+    launch_mix(X.p + (size_t)q * ms * ns, ns, ms, P->H.p, p, 1, 0.0, 0.0, add_noise ? epsd.p + (size_t)q * ns * p : nullptr, std::sqrt(P->sigma2),
+               od.p + (size_t)q * ns * p, st0);
+  HIPCHK(hipGetLastError());
+  od.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_dev_toeplitz_predict_cov(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* xs, int ns,
+                                 double diag, int chunk_rows, double* cov, int ldc) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!gp || !p || !q || !xs || !cov || n <= 0 || ns <= 0 || ldc < ns || !std::isfinite(x0) || !std::isfinite(h) || !std::isfinite(diag) ||
+      chunk_rows < 0 || chunk_rows % TOEP_PRED_R)
+    return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return toep_refuse_f32();
+  if (int rc = toep_check_n(n, true)) return rc;
+  if (int rc = toep_joint_check_ns(ns)) return rc;
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = resolve(gp, 1, 1, ls)) return rc;
+  if (int rc = toep_check_finite(xs, ns)) return rc;
+  hipStream_t st0 = g.streams[0];
+  const Latent* lts = ls->lat.data();
+  const LatentDev hd = lts[0].dev();
+  Buf<LatentDev> dd(1);
+  HIPCHK(hipMemcpyAsync(dd.p, &hd, sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  const std::vector<double> hdiag(1, diag);
+  Uploaded dg(hdiag, st0);
+  const Dims Ds(ns, 0);
+  Buf<double> G(Ds.elems());
+  BatchPtr Gb{}, Cb{};
+  Gb.p[0] = G.p; Cb.p[0] = cov;
+  const int mode = sum_mode(lts, 0, 1);
+  ToepJointClock ck;
+  toep_joint_gram(x0, h, n, dd.p, 1, p, q, xs, ns, mode, chunk_rows, Gb, Ds.ld, ck, st0);
+  launch_toep_cov_finish(dd.p, xs, ns, Gb, Ds.ld, Cb, ldc, Ds.NR, Ds.NC, dg.buf.p, nullptr, false, 1, mode, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  ck.read();
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_toeplitz_joint_last_ms(double* gemm_ms, double* gram_ms, double* factor_ms) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (gemm_ms) *gemm_ms = g_toep_joint_ms[0];
+  if (gram_ms) *gram_ms = g_toep_joint_ms[1];
+  if (factor_ms) *factor_ms = g_toep_joint_ms[2];
+  return LMM_OK;
 }
 
 // Building blocks for tests: ONE latent from device pointers, per-point noise w (+Inf: unobserved) and data r; the latent's mean is

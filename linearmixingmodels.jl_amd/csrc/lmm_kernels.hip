@@ -6375,6 +6375,199 @@ __global__ __launch_bounds__(256) void toep_predict_finish_kernel(const double* 
   var[(size_t)l * ldv + c] = k0[l] - s;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Joint predictive (DESIGN.md 4.22 "Joint predictive"): C = K(xs, xs) - (Uq' Uq - Up' Up) from the products toep_predict_kernel reduces.
+// ---------------------------------------------------------------------------------------------------
+// The storing variant of toep_predict_kernel over the nrbc row blocks from rb0 on: a sibling with that kernel's work split and tile
+// loop (a body shared by both changed the register allocation of the reducing instantiations), row block i of the chunk paired with
+// nrbc - 1 - i.  At the end a lane writes its 4 x 2 x 2 accumulator tiles to U[latent][generator][row of the chunk][nsp] -- D row
+// lk + 4 r of a tile is the lane's r-th value, D column l15 its query, so 16 lanes store 16 consecutive doubles -- with zeros for the
+// rows from n on and the padding queries.
+template <int SUM>
+__global__ __launch_bounds__(256) void toep_predict_store_kernel(double x0, double h, int n, const LatentDev* __restrict__ lat,
+                                                                 const double* __restrict__ p, const double* __restrict__ q,
+                                                                 const double* __restrict__ xs, int ns, int rb0, int nrbc,
+                                                                 double* __restrict__ U) {
+  __shared__ double Bt[TPR_T * TPR_SB];
+  __shared__ double wq[TPR_W], wp[TPR_W];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, l15 = lane & 15, lk = lane >> 4;
+  const int l = blockIdx.z, c0 = blockIdx.y * TOEP_PRED_Q, nsp = gridDim.y * TOEP_PRED_Q;
+  const size_t gen = (size_t)nrbc * TOEP_PRED_R * nsp;     // doubles of one generator's part of the chunk
+  const LatentDev g = lat[l];
+  p += (size_t)l * n; q += (size_t)l * n;
+  U += (size_t)l * 2 * gen;
+  const int ec = t & (TOEP_PRED_Q - 1), ek = t >> 5;
+  const bool qlive = c0 + ec < ns;
+  const double xq = qlive ? xs[c0 + ec] : 0.0;
+  for (int half = 0; half < 2; ++half) {
+    const int rbk = half == 0 ? (int)blockIdx.x : nrbc - 1 - (int)blockIdx.x;
+    if (half == 1 && rbk <= (int)blockIdx.x) break;
+    const int o0 = (rb0 + rbk) * TOEP_PRED_R;
+    d4 aq[4][2], ap[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) { aq[j][cb] = (d4){0.0, 0.0, 0.0, 0.0}; ap[j][cb] = (d4){0.0, 0.0, 0.0, 0.0}; }
+    for (int s0 = o0; s0 < n; s0 += TPR_T) {
+      __syncthreads();
+      for (int w = t; w < TPR_W; w += 256) {
+        const int lag = s0 - o0 - (TOEP_PRED_R - 1) + w;
+        const bool ok = lag >= 0 && lag < n;
+        wq[w] = ok ? q[lag] : 0.0; wp[w] = ok ? p[lag] : 0.0;
+      }
+#pragma unroll 1
+      for (int e = 0; e < 4; ++e) {
+        const int ks = ek + 8 * e, s = s0 + ks;
+        double v = 0.0;
+        if (qlive && s < n) {
+          const double xc = __builtin_fma((double)s, h, x0);
+          v = kappa_lat<SUM>(g, &xq, &xc, 1);
+        }
+        Bt[ks * TPR_SB + ec] = v;
+      }
+      __syncthreads();
+      // two k-steps in flight.  SUM = 0 fits 256 registers (two waves per SIMD); the sum modes take 255 + 9 and 256 + 15 (the compiler
+      // parks address arithmetic in AGPRs) and run at one wave per SIMD: held to two waves they would spill 20 / 68 B to scratch
+#pragma unroll 2
+      for (int k4 = 0; k4 < TPR_T / 4; ++k4) {
+        const int ks = 4 * k4 + lk;
+        const double b0 = Bt[ks * TPR_SB + l15], b1 = Bt[ks * TPR_SB + 16 + l15];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int ro = 16 * (4 * j + wv);
+          if (s0 + 4 * k4 + 3 >= o0 + ro) {                // else every s of the k-step lies in front of every row of the tile
+            const int w = ks - (ro + l15) + TOEP_PRED_R - 1;
+            const double fq = wq[w], fp = wp[w];
+            aq[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fq, b0, aq[j][0], 0, 0, 0);
+            aq[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fq, b1, aq[j][1], 0, 0, 0);
+            ap[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fp, b0, ap[j][0], 0, 0, 0);
+            ap[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fp, b1, ap[j][1], 0, 0, 0);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * (4 * j + wv) + lk + 4 * r, c = c0 + 16 * cb + l15;
+          const bool live = o0 + row < n && c < ns;
+          const size_t e = ((size_t)rbk * TOEP_PRED_R + row) * nsp + c;
+          U[e] = live ? aq[j][cb][r] : 0.0;
+          U[gen + e] = live ? ap[j][cb][r] : 0.0;
+        }
+  }
+}
+
+// The signed Gram of a chunk: workgroup (tile pair ti >= tj of TOEP_JOINT_T, latent) owns G[ti][tj] and no other workgroup touches it:
+// no split over the rows, no atomics.  4 waves in 2 x 2, each a 64 x 64 quarter as 4 x 4 accumulators of 16 x 16 (128 VGPRs), which
+// start at zero (first) or at G as the previous chunk left it, so the sum is one chain over the row blocks whatever the chunking:
+// per row block its rows of Uq in ascending order, then its rows of Up with the A operand negated.  A panel is TG_K rows of U, its
+// columns i0 .. i0 + T - 1 and, off the diagonal, j0 .. j0 + T - 1, in LDS at stride TG_S (the 4 k-lanes of a fragment on distinct
+// banks); the next panel's loads are in flight in registers while this one is multiplied.  U is row-major in the query, so a fragment
+// of either operand is 16 consecutive doubles of one row; per k-step of 4 rows a wave reads 4 fragments of the j side (A: D row
+// lk + 4 r is column j of G) and 4 of the i side (B: D column l15 is row i of G, contiguous in the column-major G) for 16 MFMAs: an
+// element read from LDS feeds 4.  Rows from n on are zeros in U; whole panels of them are not walked (live: the chunk's rows < n).
+constexpr int TG_K = 16;
+constexpr int TG_S = TOEP_JOINT_T + 16;
+static_assert(TOEP_JOINT_T == 128 && TG_K * TOEP_JOINT_T == 8 * 256 && TOEP_PRED_R % TG_K == 0, "toep_gram_kernel's thread maps");
+
+__global__ __launch_bounds__(256) void toep_gram_kernel(const double* __restrict__ U, int live, int rows, int nsp, BatchPtr G, int ld,
+                                                        int first) {
+  __shared__ double Pi[TG_K * TG_S], Pj[TG_K * TG_S];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, l15 = lane & 15, lk = lane >> 4, wr = wv >> 1, wc = wv & 1;
+  int ti = 0;
+  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
+  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2, l = blockIdx.y;
+  const int i0 = ti * TOEP_JOINT_T, j0 = tj * TOEP_JOINT_T;
+  const bool diag = ti == tj;
+  const double* Pa = diag ? Pi : Pj;                       // the j side: the same panel on the diagonal
+  const size_t gen = (size_t)rows * nsp;
+  U += (size_t)l * 2 * gen;
+  double* Gt = G.p[l] + (size_t)(j0 + 64 * wc + lk) * ld + i0 + 64 * wr + l15;
+  d4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = first ? 0.0 : Gt[(size_t)(16 * a + 4 * r) * ld + 16 * b];
+  const int cc = t & (TOEP_JOINT_T - 1), rr = t >> 7;      // the thread stages rows rr + 2 e, e < 8, of column cc
+  const bool ilive = i0 + cc < nsp, jlive = !diag && j0 + cc < nsp;
+  const int nrbl = (live + TOEP_PRED_R - 1) / TOEP_PRED_R;
+  auto panels = [&](int rb) { return (min(TOEP_PRED_R, live - rb * TOEP_PRED_R) + TG_K - 1) / TG_K; };
+  double ri[8], rj[8];
+  auto fetch = [&](int rb, int gn, int kp) {
+    const double* src = U + gn * gen + ((size_t)rb * TOEP_PRED_R + kp * TG_K + rr) * nsp;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      ri[e] = ilive ? src[(size_t)2 * e * nsp + i0 + cc] : 0.0;
+      rj[e] = jlive ? src[(size_t)2 * e * nsp + j0 + cc] : 0.0;
+    }
+  };
+  int rb = 0, gn = 0, kp = 0;
+  bool more = nrbl > 0;
+  if (more) fetch(0, 0, 0);
+  while (more) {
+    const bool neg = gn == 1;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      Pi[(rr + 2 * e) * TG_S + cc] = ri[e];
+      if (!diag) Pj[(rr + 2 * e) * TG_S + cc] = rj[e];
+    }
+    __syncthreads();
+    if (++kp == panels(rb)) { kp = 0; if (++gn == 2) { gn = 0; ++rb; } }
+    more = rb < nrbl;
+    if (more) fetch(rb, gn, kp);
+#pragma unroll
+    for (int k4 = 0; k4 < TG_K / 4; ++k4) {
+      const int ko = (4 * k4 + lk) * TG_S + l15;
+      double fa[4], fb[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const double v = Pa[ko + 64 * wc + 16 * a];
+        fa[a] = neg ? -v : v;
+        fb[a] = Pi[ko + 64 * wr + 16 * a];
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Gt[(size_t)(16 * a + 4 * r) * ld + 16 * b] = acc[a][b][r];
+}
+
+// C + d I from G, in place or into the caller's matrix (launch_toep_cov_finish in lmm_toeplitz.h): thread (row i, column j, latent).
+// kappa takes the larger input first, so that the value of a pair does not depend on which of the two is the row.
+template <int SUM>
+__global__ __launch_bounds__(256) void toep_cov_finish_kernel(const LatentDev* __restrict__ lat, const double* __restrict__ xs, int ns,
+                                                              BatchPtr G, int ldg, BatchPtr out, int ldo, int NR, int NC,
+                                                              const double* __restrict__ diag, const double* __restrict__ rider, int pad) {
+  const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, l = blockIdx.z;
+  if (pad ? (i >= NR || (i >> 6) < (j >> 6)) : (i >= ns || i < j)) return;
+  double v = 0.0;
+  if (i < ns && j < ns) {
+    const double xi = xs[i], xj = xs[j];
+    const double hi = fmax(xi, xj), lo = fmin(xi, xj);
+    v = kappa_lat<SUM>(lat[l], &hi, &lo, 1) - G.p[l][(size_t)j * ldg + i];
+    if (i == j) v += diag[l];
+  } else if (j >= ns) {
+    v = i == j ? 1.0 : 0.0;
+  } else if (i == NC && rider) {
+    v = rider[(size_t)l * ns + j];
+  }
+  out.p[l][(size_t)j * ldo + i] = v;
+}
+
 // x[i] = x0 + i h, the grid as toep_predict_kernel forms it
 __global__ __launch_bounds__(256) void toep_grid_kernel(double x0, double h, int n, double* __restrict__ x) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -6397,4 +6590,46 @@ void launch_toep_predict(double x0, double h, int n, const LatentDev* lat, const
   });
   hipLaunchKernelGGL(toep_predict_finish_kernel, dim3((ns + 255) / 256, nb), dim3(256), 0, st, (const double*)part, nrb,
                      nqb * TOEP_PRED_Q, ns, k0, var, ldv);
+}
+
+ToepJointPlan toep_joint_plan(int n, int ns, int nb, int rows_forced) {
+  const size_t per_block = (size_t)2 * TOEP_PRED_R * toep_joint_nsp(ns) * sizeof(double);      // one latent, one row block
+  const size_t blocks = std::max<size_t>(1, TOEP_JOINT_BUDGET / per_block);
+  const int nrb = (n + TOEP_PRED_R - 1) / TOEP_PRED_R;
+  ToepJointPlan P;
+  const size_t most = (size_t)std::min(std::max(nb, 1), LMM_MAX_BATCH);
+  if (rows_forced > 0) {
+    P.rows = std::min(rows_forced / TOEP_PRED_R, nrb) * TOEP_PRED_R;
+    P.lat = (int)std::min(most, std::max<size_t>(1, blocks / (P.rows / TOEP_PRED_R)));
+    return P;
+  }
+  // latents first: the Gram kernel's grid is tiles x latents of the pass, and few latents per pass leave most of the GPU idle at
+  // small ns.  Rows first (fewer round trips of G) was measured slower at every ns: 35 / 127 / 562 ms against 26 / 97 / 500 at n = 8192
+  P.lat = (int)std::min(most, blocks);
+  P.rows = (int)std::min<size_t>((size_t)nrb, blocks / P.lat) * TOEP_PRED_R;
+  return P;
+}
+void launch_toep_predict_store(double x0, double h, int n, const LatentDev* lat, const double* p, const double* q, const double* xs, int ns,
+                               int nb, int mode, int row0, int rows, double* U, hipStream_t st) {
+  if (nb <= 0 || ns <= 0 || rows <= 0) return;
+  const int nrbc = rows / TOEP_PRED_R, nqb = (ns + TOEP_PRED_Q - 1) / TOEP_PRED_Q;
+  mode_dispatch(mode, [&](auto md) {
+    hipLaunchKernelGGL((toep_predict_store_kernel<decltype(md)::value>), dim3((nrbc + 1) / 2, nqb, nb), dim3(256), 0, st, x0, h, n, lat, p,
+                       q, xs, ns, row0 / TOEP_PRED_R, nrbc, U);
+  });
+}
+void launch_toep_gram(const double* U, int n, int row0, int rows, int ns, const BatchPtr& G, int ld, int nb, bool first, hipStream_t st) {
+  if (nb <= 0 || ns <= 0 || rows <= 0) return;
+  const int nt = (ns + TOEP_JOINT_T - 1) / TOEP_JOINT_T;
+  hipLaunchKernelGGL(toep_gram_kernel, dim3(nt * (nt + 1) / 2, nb), dim3(256), 0, st, U, std::max(0, std::min(rows, n - row0)), rows,
+                     toep_joint_nsp(ns), G, ld, first ? 1 : 0);
+}
+void launch_toep_cov_finish(const LatentDev* lat, const double* xs, int ns, const BatchPtr& G, int ldg, const BatchPtr& out, int ldo, int NR,
+                            int NC, const double* diag, const double* rider, bool pad, int nb, int mode, hipStream_t st) {
+  if (nb <= 0 || ns <= 0) return;
+  const dim3 grid(((pad ? NR : ns) + 255) / 256, pad ? NC : ns, nb);
+  mode_dispatch(mode, [&](auto md) {
+    hipLaunchKernelGGL((toep_cov_finish_kernel<decltype(md)::value>), grid, dim3(256), 0, st, lat, xs, ns, G, ldg, out, ldo, NR, NC, diag,
+                       rider, pad ? 1 : 0);
+  });
 }

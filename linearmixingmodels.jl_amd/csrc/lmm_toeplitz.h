@@ -71,3 +71,32 @@ void launch_toep_grid(double x0, double h, int n, double* x, hipStream_t st);
 size_t toep_predict_scratch(int n, int ns, int nb);
 void launch_toep_predict(double x0, double h, int n, const LatentDev* lat, const double* k0, const double* p, const double* q,
                          const double* xs, int ns, int nb, int mode, double* part, double* var, size_t ldv, hipStream_t st);
+
+// ---- the joint predictive at new inputs (DESIGN.md 4.22 "Joint predictive") ----
+// C_l = K_l(xs, xs) - (Uq' Uq - Up' Up), Uq = L(q)' K*, Up = L(p)' K*: the storing variant of the predict GEMM leaves Uq and Up of a
+// chunk of whole row blocks in U[latent][generator][row of the chunk][nsp], nsp = toep_joint_nsp(ns); the Gram kernel folds the chunk
+// into G; the finish kernel turns G into C + d I in place, in the layout potrf_batch takes.
+#define TOEP_JOINT_T 128                      // edge of the tile of G a workgroup of toep_gram_kernel owns
+#define TOEP_JOINT_MAX_NS 4096                // 32 latents' C: 4.3 GB
+#define TOEP_JOINT_BUDGET (size_t(1) << 28)   // bytes of U a pass may hold: 256 MB
+inline int toep_joint_nsp(int ns) { return (ns + TOEP_PRED_Q - 1) / TOEP_PRED_Q * TOEP_PRED_Q; }
+// What a call over nb latents runs: `lat` latents per pass (<= LMM_MAX_BATCH) and chunks of `rows` rows (whole row blocks, at most the
+// row blocks of n), so that lat 2 rows nsp doubles stay within TOEP_JOINT_BUDGET -- but for one latent and one row block, the least a
+// pass can hold (16 MB at ns = 4096).  rows_forced (a multiple of TOEP_PRED_R; 0: none): chunks of that many rows, lat sized to them.
+struct ToepJointPlan { int lat, rows; };
+ToepJointPlan toep_joint_plan(int n, int ns, int nb, int rows_forced = 0);
+// U of the rows [row0, row0 + rows) (row0, rows: multiples of TOEP_PRED_R) for the nb latents lat[0 .. nb): rows >= n and the padding
+// queries ns .. nsp - 1 are zeros.  U: nb 2 rows nsp doubles.  Arguments otherwise as launch_toep_predict's.
+void launch_toep_predict_store(double x0, double h, int n, const LatentDev* lat, const double* p, const double* q, const double* xs, int ns,
+                               int nb, int mode, int row0, int rows, double* U, hipStream_t st);
+// G_l (+)= sum over the chunk's row blocks, in ascending order, of (Uq' Uq over the block's rows, then - Up' Up over them): element
+// (i, j) of latent l at G.p[l][j ld + i], the TOEP_JOINT_T tiles of the lower triangle (whole tiles: i, j < rup(ns, TOEP_JOINT_T), the
+// diagonal tiles on both sides).  first: the sum starts here (G is not read).  The sum is carried in the accumulators from chunk to
+// chunk, so G does not depend on how the rows are chunked.
+void launch_toep_gram(const double* U, int n, int row0, int rows, int ns, const BatchPtr& G, int ld, int nb, bool first, hipStream_t st);
+// out.p[l][j ldo + i] = kappa_l(xs_i - xs_j) - G.p[l][j ldg + i] + (i == j) diag[l] for ns > i >= j.  With pad (out as Dims(ns, 1) lays a
+// factor matrix out: NC columns, NR rows) the whole 64 x 64 tiles of the lower triangle are written: also i < j inside a diagonal tile,
+// the identity on the padding columns, rider[l ns + j] in row NC (rider == nullptr: zeros) and zeros in the other rows from ns on.
+// diag: nb values, rider: [latent][ns], both on the device.  out may be G.
+void launch_toep_cov_finish(const LatentDev* lat, const double* xs, int ns, const BatchPtr& G, int ldg, const BatchPtr& out, int ldo, int NR,
+                            int NC, const double* diag, const double* rider, bool pad, int nb, int mode, hipStream_t st);

@@ -1498,11 +1498,22 @@ class ToeplitzPosterior:
             ptr, self._ptr = self._ptr, None
             L.load().lmm_toeplitz_post_destroy(ptr)
 
-    def rand(self, rng, N: Optional[int] = None, add_noise: bool = True, horizon: int = 0, jitter: Optional[float] = None):
+    def rand(self, rng, N: Optional[int] = None, add_noise: bool = True, horizon: int = 0, jitter: Optional[float] = None, xs=None):
         """Joint samples of post(x, sigma2) over the training grid and its continuation by `horizon` further points, from the handle
         alone (pathwise conditioning; DESIGN.md 4.22 "Sampling"): (n_tot * p,) by outputs for N=None, else (n_tot * p, N), n_tot =
         n + horizon, the first n points the training grid.  rng, the draw order and jitter as toeplitz_rand's.  The handle is not
-        changed.  Every refusal comes before any library call."""
+        changed.  Every refusal comes before any library call.
+        With xs ((ns,) in any order, NumPy or a torch device tensor, ns <= lmm_toeplitz_joint_max_ns(); horizon must be 0): joint
+        samples of post(xs, sigma2) at those inputs, in the caller's order, (ns * p,) or (ns * p, N) by outputs: per latent
+        mu* + chol(C + jitter I) zeta with C the ns x ns posterior covariance (DESIGN.md 4.22 "Joint predictive").  Draw order per
+        sample: for each latent in order, standard_normal(ns); then, if add_noise, standard_normal(ns * p) (by outputs).  Column q
+        of an N-sample call is bitwise the one-sample call on the same normals; the samples share the factorisation but are not
+        batched beyond it (two small launches per latent and sample).  At the default jitter a C that is not positive definite to
+        rounding (queries closer than the data can resolve) is a PosDefException naming the latent: raise jitter."""
+        if xs is not None:
+            if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon != 0:
+                raise ValueError("ToeplitzPosterior.rand: horizon must be 0 when xs is given")
+            return self._rand_at(rng, xs, N, add_noise, jitter)
         if not self._ptr:
             raise ValueError("ToeplitzPosterior: the posterior has been closed")
         horizon, jit = _toeplitz_rand_args("ToeplitzPosterior.rand", self.n, N, horizon, jitter)
@@ -1526,8 +1537,8 @@ class ToeplitzPosterior:
         except Exception:
             pass
 
-    def _query(self, xs, add_noise: bool, want_var: bool):
-        """Every refusal comes before any library call."""
+    def _queries(self, xs):
+        """xs as the library takes it ((ns,) Float64, NumPy or torch); every refusal comes before any library call."""
         if not self._ptr:
             raise ValueError("ToeplitzPosterior: the posterior has been closed")
         if not hasattr(xs, "shape"):
@@ -1543,6 +1554,72 @@ class ToeplitzPosterior:
             finite = bool(np.isfinite(xs).all())
         if not finite:
             raise ValueError("ToeplitzPosterior: xs must be finite (no NaN or Inf)")
+        return xs
+
+    def _joint_ns(self, what: str, xs) -> int:
+        """What the two joint verbs refuse alike, after _queries"""
+        if L.get_compute_dtype() == "f32":
+            raise NotImplementedError(f"{what}: the Toeplitz path is Float64 only (set_compute_dtype('f64'))")
+        cap = L.load().lmm_toeplitz_joint_max_ns()
+        if int(xs.shape[0]) > cap:
+            raise NotImplementedError(f"{what}: the joint predictive serves ns <= {cap} queries (lmm_toeplitz_joint_max_ns; ns = {int(xs.shape[0])})")
+        return int(xs.shape[0])
+
+    def predictive_logpdf(self, xs, ys, sigma2: Optional[float] = None) -> float:
+        """logpdf(post(xs, sigma2), ys): the joint log density of the held-out observations ys at the inputs xs given the training
+        data, from the handle alone (DESIGN.md 4.22 "Joint predictive"): per latent the ns x ns posterior covariance from the
+        generators, in O(n^2 ns + n ns^2) time and O(n + ns^2) memory, factored by the dense path's Cholesky.  (`logpdf` is the
+        attribute that holds the training data's value, hence the name.)  xs: (ns,) in any order, NumPy or a torch device tensor,
+        ns <= lmm_toeplitz_joint_max_ns(); ys: (ns * p,) by outputs, complete (the library refuses a NaN and names its point);
+        sigma2: the noise at the queries, None = the handle's own.  The handle is not changed.  Every refusal below comes before
+        any library call that takes the handle (the cap on ns is read from the library)."""
+        xs = self._queries(xs)
+        ns = self._joint_ns("ToeplitzPosterior.predictive_logpdf", xs)
+        if not hasattr(ys, "shape"):
+            ys = np.asarray(ys, dtype=np.float64)
+        if len(ys.shape) != 1 or int(ys.shape[0]) != ns * self.p:
+            raise ValueError(f"ToeplitzPosterior.predictive_logpdf: ys holds ns * p = {ns * self.p} values by outputs")
+        if sigma2 is not None:
+            sigma2 = float(sigma2)
+            if not np.isfinite(sigma2) or not sigma2 > 0.0:
+                raise ValueError("ToeplitzPosterior.predictive_logpdf: sigma2 must be finite and > 0 (None: the handle's own)")
+        if ns == 0:
+            return 0.0
+        if L._is_torch(ys):
+            import torch
+            ys = ys.to(torch.float64)
+        else:
+            ys = np.ascontiguousarray(ys, dtype=np.float64)
+        out = C.c_double()
+        L.check(L.load().lmm_oilmm_toeplitz_post_logpdf(self._ptr, L.Arr(xs).ptr, ns, L.Arr(ys).ptr, -1.0 if sigma2 is None else sigma2,
+                                                        C.byref(out)))
+        return out.value
+
+    def _rand_at(self, rng, xs, N, add_noise: bool, jitter):
+        xs = self._queries(xs)
+        ns = self._joint_ns("ToeplitzPosterior.rand", xs)
+        if N is not None and (int(N) != N or N < 1):
+            raise ValueError("ToeplitzPosterior.rand: N is None or a number of samples >= 1")
+        if jitter is not None and not (np.isfinite(jitter) and jitter >= 0.0):
+            raise ValueError("ToeplitzPosterior.rand: jitter is None or finite and >= 0")
+        Ns, p, m = 1 if N is None else int(N), self.p, self.m
+        if ns == 0:
+            return _empty_for(rng, 0) if N is None else _empty_for(rng, 0, Ns)
+        z = _empty_for(rng, Ns, m * ns)
+        eps = _empty_for(rng, Ns, ns * p) if add_noise else None
+        for q in range(Ns):
+            for l in range(m):
+                z[q, l * ns:(l + 1) * ns] = rng.standard_normal(ns)
+            if eps is not None:
+                eps[q] = rng.standard_normal(ns * p)
+        out = _empty_for(rng, Ns, ns * p)
+        L.check(L.load().lmm_oilmm_toeplitz_post_rand_at(self._ptr, L.Arr(xs).ptr, ns, -1.0 if jitter is None else float(jitter), int(add_noise),
+                                                         Ns, L.Arr(z).ptr, None if eps is None else L.Arr(eps).ptr, L.Arr(out, True).ptr))
+        return out[0] if N is None else out.T
+
+    def _query(self, xs, add_noise: bool, want_var: bool):
+        """Every refusal comes before any library call."""
+        xs = self._queries(xs)
         ns = int(xs.shape[0])
         mean = _alloc_like(xs, ns * self.p)
         var = _alloc_like(xs, ns * self.p) if want_var else None
