@@ -901,6 +901,30 @@ int lmm_toeplitz_post_destroy(lmm_toep_post_t* post);
 int lmm_oilmm_toeplitz_post_mean_and_var(const lmm_toep_post_t* post, const double* xs, int ns, int add_noise, double* mean, double* var);
 int lmm_dev_toeplitz_predict(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* alpha,
                              const double* xs, int ns, double* mean, double* var);
+/* Toeplitz: gradients with respect to the queries (DESIGN.md 4.22 "Gradients with respect to the queries").  Per latent, with
+ * k*'(s)[t] = d kappa_l(x_0 + t h, s) / d s,
+ *   d mean_l / d s = k*'(s)' alpha_l,     d var_l / d s = -2 (L(q)' k*(s) . L(q)' k*'(s) - L(p)' k*(s) . L(p)' k*'(s)),
+ * the variance part as the predict GEMM with the derivative columns beside the values (toep_predict_grad_kernel, 16 queries per
+ * workgroup): O(n^2 ns) flops, twice those of the variance itself, O(n + ns) memory, no atomics, bitwise reproducible, and a query's
+ * entry depends on no other query.  A query that coincides with a grid point x_0 + t h, to within the tolerance of the grid rule of
+ * lmm_oilmm_logpdf_toeplitz (8 eps max(|x_0|, |x_{n-1}|)), gets 0 from that point for every kind: Matern12 has a cusp there (the dense
+ * path's convention), and the handle knows the training inputs to that tolerance only.  Every kind the path serves is served, SHO and
+ * sums included.
+ *   lmm_oilmm_toeplitz_post_mean_and_var_grad_xs : the pullback of lmm_oilmm_toeplitz_post_mean_and_var to the queries:
+ *                    grad_xs[c] = sum_l mbar_l[c] d mean_l / d xs_c + vbar_l[c] d var_l / d xs_c, mbar = H' dmean, vbar = (H o H)' dvar,
+ *                    mixed as lmm_oilmm_statespace_post_mean_and_var_grad_xs mixes.  The jitter and the sigma2 of add_noise do not
+ *                    depend on xs.  xs, grad_xs: ns values; dmean, dvar: ns x p by outputs; all host or device.  Either cotangent may
+ *                    be NULL (dvar NULL: no GEMM runs); both NULL -> LMM_ERR_ARG.  A handle of either schedule; partial sums over the
+ *                    handle's shard.  post, xs or grad_xs NULL or ns < 1 -> LMM_ERR_ARG; a NaN or +-Inf in xs -> LMM_ERR_ARG with the
+ *                    first such index in `info`; the fp32 compute mode -> LMM_ERR_UNSUPPORTED; all before any kernel of the path
+ *                    runs, and the handle answers bitwise as before.
+ *   lmm_dev_toeplitz_predict_grad : building block for tests, DEVICE pointers, ONE latent (gp on the host): d mean / d xs and
+ *                    d var / d xs (ns values each) of lmm_dev_toeplitz_predict's marginals.  dvar_dx may be NULL.
+ *                    n <= lmm_toeplitz_blocked_max_n(). */
+int lmm_oilmm_toeplitz_post_mean_and_var_grad_xs(const lmm_toep_post_t* post, const double* xs, int ns, const double* dmean,
+                                                 const double* dvar, double* grad_xs);
+int lmm_dev_toeplitz_predict_grad(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* alpha,
+                                  const double* xs, int ns, double* dmean_dx, double* dvar_dx);
 /* Toeplitz: joint samples (DESIGN.md 4.22 "Sampling"), of the prior and of the posterior, over the training grid and its continuation
  * x_0 + i h, i < nt = n + horizon, in O(nt^2) time and O(nt) memory per latent and pass of 4 samples.  A prior path is f = L zeta with
  * L L' = Toeplitz(t0 + jitter e_0), t0 the latent kernel's first column over nt lags: step k of the blocked Schur recursion holds

@@ -6014,6 +6014,83 @@ int lmm_dev_toeplitz_predict(double x0, double h, int n, const lmm_gp_t* gp, con
   LMM_CATCH
 }
 
+// ---- gradients with respect to the queries (DESIGN.md 4.22 "Gradients with respect to the queries") --------------------------------
+// d mean / d xs and d var / d xs of the ms latents lts[0 .. ms) at the ns queries xsd (device, finite): dml, dvl [latent][ns] on the
+// device, either nullptr: not computed (dvl == nullptr: no GEMM).  The variance part runs in chunks of queries whose partials fit
+// kToepPredictScratch.  Returns with streams[0] drained.
+static int toep_predict_grad_latents(double x0, double h, int n, const Latent* lts, int ms, const double* pg, const double* qg,
+                                     const double* alpha, const double* xsd, int ns, double* dml, double* dvl) {
+  if (ms == 0) return LMM_OK;
+  hipStream_t st0 = g.streams[0];
+  std::vector<LatentDev> hd(ms);
+  for (int k = 0; k < ms; ++k) hd[k] = lts[k].dev();
+  Buf<LatentDev> dd(ms);
+  HIPCHK(hipMemcpyAsync(dd.p, hd.data(), (size_t)ms * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  const int mode = sum_mode(lts, 0, ms);
+  // a query within the grid rule's tolerance of x0 + s h (toep_train) is that training input as far as the handle knows it: x_s itself
+  // may differ from the fused x0 + s h in its last bits, and Matern12 has a cusp there
+  const double ctol = 8.0 * 2.220446049250313e-16 * std::max(std::fabs(x0), std::fabs(x0 + (double)(n - 1) * h));
+  if (dml) launch_toep_mean_grad(x0, h, ctol, n, dd.p, alpha, xsd, ns, ms, mode, dml, (size_t)ns, st0);
+  HIPCHK(hipGetLastError());
+  if (!dvl) { HIPCHK(hipStreamSynchronize(st0)); return LMM_OK; }
+  const size_t per_block = toep_predict_grad_scratch(n, TOEP_GRAD_Q, ms);      // the partials of one block of queries
+  const int chunk = (int)std::min<size_t>((size_t)rup(ns, TOEP_GRAD_Q), std::max<size_t>(1, std::min<size_t>(kToepPredictScratch / per_block, 32768)) * TOEP_GRAD_Q);
+  Buf<double> part(toep_predict_grad_scratch(n, chunk, ms));
+  for (int c0 = 0; c0 < ns; c0 += chunk)
+    launch_toep_predict_grad(x0, h, ctol, n, dd.p, pg, qg, xsd + c0, std::min(chunk, ns - c0), ms, mode, part.p, dvl + c0, (size_t)ns, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+}
+
+// The pullback of lmm_oilmm_toeplitz_post_mean_and_var to the queries: the latents' derivatives contracted with H and the cotangents
+// as lmm_oilmm_statespace_post_mean_and_var_grad_xs contracts them (launch_ss_contract_dx); the side without a cotangent is not
+// computed and enters as zeros.  The jitter and the added sigma2 do not depend on xs.
+int lmm_oilmm_toeplitz_post_mean_and_var_grad_xs(const lmm_toep_post_t* post, const double* xs, int ns, const double* dmean,
+                                                 const double* dvar, double* grad_xs) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!post || !xs || !grad_xs || ns < 1) return fail(LMM_ERR_ARG, "bad arguments");
+  if (!dmean && !dvar) return fail(LMM_ERR_ARG, "Toeplitz posterior: dmean and dvar are both NULL (one cotangent is needed)");
+  if (g_f32) return toep_refuse_f32();
+  const lmm_toep_post* P = post;
+  const int p = P->p, ms = P->l1 - P->l0;
+  hipStream_t st0 = g.streams[0];
+  DevIn xsd(xs, (size_t)ns, st0);
+  if (int rc = toep_check_finite(xsd.p, ns)) return rc;
+  DevIn dm(dmean, (size_t)ns * p, st0), dv(dvar, (size_t)ns * p, st0);
+  const size_t cnt = (size_t)ns * std::max(ms, 1);
+  Buf<double> ml(cnt), vl(cnt);
+  if (!dmean) HIPCHK(hipMemsetAsync(ml.p, 0, cnt * sizeof(double), st0));
+  if (!dvar) HIPCHK(hipMemsetAsync(vl.p, 0, cnt * sizeof(double), st0));
+  if (int rc = toep_predict_grad_latents(P->x0, P->h, P->n, P->ls->lat.data() + P->l0, ms, P->pg.p, P->qg.p, P->alpha.p, xsd.p, ns,
+                                         dmean ? ml.p : nullptr, dvar ? vl.p : nullptr)) return rc;
+  DevOut go(grad_xs, (size_t)ns);
+  launch_ss_contract_dx(dm.p, dv.p, P->H.p, p, ms, ml.p, vl.p, ns, go.p, st0);
+  HIPCHK(hipGetLastError());
+  go.finish(st0);
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_dev_toeplitz_predict_grad(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* alpha,
+                                  const double* xs, int ns, double* dmean_dx, double* dvar_dx) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!gp || !p || !q || !alpha || !xs || !dmean_dx || n <= 0 || ns <= 0 || !std::isfinite(x0) || !std::isfinite(h))
+    return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return toep_refuse_f32();
+  if (n > TOEPB_MAX_N) return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves n <= %d points (lmm_toeplitz_blocked_max_n; n = %d)", TOEPB_MAX_N, n);
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = resolve(gp, 1, 1, ls)) return rc;
+  if (int rc = toep_check_finite(xs, ns)) return rc;
+  return toep_predict_grad_latents(x0, h, n, ls->lat.data(), 1, p, q, alpha, xs, ns, dmean_dx, dvar_dx);
+  LMM_CATCH
+}
+
 // ---- the joint predictive at new inputs (DESIGN.md 4.22 "Joint predictive") --------------------------------------------------------
 int lmm_toeplitz_joint_max_ns(void) { return TOEP_JOINT_MAX_NS; }
 int lmm_toeplitz_joint_shape(int* max_ns, int* tile, int* chunk_rows) {

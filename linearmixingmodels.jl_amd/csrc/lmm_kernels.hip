@@ -6376,6 +6376,215 @@ __global__ __launch_bounds__(256) void toep_predict_finish_kernel(const double* 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Gradients with respect to the queries (DESIGN.md 4.22 "Gradients with respect to the queries"): per latent and query c
+//     d mean_c / d xs_c = k*'_c . alpha,      d var_c / d xs_c = -2 (u_q . u'_q - u_p . u'_p),      u_g = L(g)' k*_c,  u'_g = L(g)' k*'_c,
+// with k*'_c[s] = d kappa(x_0 + s h, xs_c) / d xs_c.  The variance part is toep_predict_kernel's GEMM with the derivative columns in
+// the place of its second 16 queries; the mean part is a dot product per query.
+// ---------------------------------------------------------------------------------------------------
+// kappa and d kappa / d xs of one term at dl = xs - x (d = 1), every base kind; the exp and the sincospi are shared by the two.  A
+// coincident pair (dl = 0) has derivative exactly 0: the smooth kinds carry the factor dl or sin, Matern12 and SHO the sign, sign(0) = 0
+// (the dense path's convention at the cusp of Matern12).  The sign takes |dl| <= ctol for 0: the grid point is x0 + s h fused, which
+// may differ from the training input it stands for in the last bits (the grid rule's tolerance), and a query equal to that input must
+// not land on one side of the cusp.  PER: the term may be periodic or locally periodic, as kappa_sum's.
+template <bool PER>
+__device__ __forceinline__ void kappa_dx_term(const LatentDev& g, double dl, double ctol, double& kap, double& dk) {
+  if (PER && (g.kind == LMM_KERNEL_PERIODIC || g.kind == LMM_KERNEL_LOCALLY_PERIODIC)) {
+    const double ip = g.ils ? g.ils[0] : g.inv_ls;                               // 1 / period, where per_q reads it
+    const double id2 = g.kind == LMM_KERNEL_LOCALLY_PERIODIC ? g.inv_decay * g.inv_decay : 0.0;
+    double sn, cs;
+    sincospi(dl * ip, &sn, &cs);
+    kap = g.var * exp_nonpos(-0.5 * __builtin_fma(id2, dl * dl, g.alpha * (sn * sn)));
+    dk = -kap * __builtin_fma(LMM_PI * g.alpha * ip, sn * cs, dl * id2);         // pi sin(2 pi dl / P) / (2 P rho^2) + dl / decay^2
+    return;
+  }
+  const double r = fabs(dl) * g.inv_ls, r2 = r * r, td = dl * g.inv_ls * g.inv_ls;
+  const double sg = dl > ctol ? 1.0 : (dl < -ctol ? -1.0 : 0.0);
+  if (g.kind == LMM_KERNEL_SE) {
+    kap = g.var * exp_nonpos(-0.5 * r2);
+    dk = -kap * td;
+  } else if (g.kind == LMM_KERNEL_MATERN32) {
+    const double s = 1.7320508075688772 * r, ve = g.var * exp_nonpos(-s);
+    kap = (1.0 + s) * ve;
+    dk = -3.0 * ve * td;
+  } else if (g.kind == LMM_KERNEL_MATERN52) {
+    const double s = 2.23606797749979 * r, ve = g.var * exp_nonpos(-s);
+    kap = (1.0 + s + (5.0 / 3.0) * r2) * ve;
+    dk = -(5.0 / 3.0) * (1.0 + s) * ve * td;
+  } else if (g.kind == LMM_KERNEL_MATERN12) {
+    kap = g.var * exp_nonpos(-r);
+    dk = -sg * kap * g.inv_ls;
+  } else if (g.kind == LMM_KERNEL_RQ) {
+    double hr, dal;
+    rq_pair(g.var, g.alpha, r2, kap, hr, dal);
+    dk = -hr * td;
+  } else {                                                                       // SHO: d kap / d r = -2 pi v E s / h (sho_pair)
+    const double hh = sho_eta(g.alpha);
+    double sn, cs;
+    sincospi(2.0 * hh * r, &sn, &cs);
+    const double vE = g.var * exp_nonpos(-LMM_PI * r / g.alpha);
+    kap = vE * __builtin_fma(sn, 0.5 / (hh * g.alpha), cs);
+    dk = -sg * (2.0 * LMM_PI * g.inv_ls / hh) * vE * sn;
+  }
+}
+// The same of one latent: a sum is the sum of its terms.  SUM as kappa_lat's.
+template <int SUM>
+__device__ __forceinline__ void kappa_dx_lat(const LatentDev& g, double xq, double xc, double ctol, double& kap, double& dk) {
+  const double dl = xq - xc;
+  if (SUM && g.kind == LMM_KERNEL_SUM) {
+    kap = 0.0; dk = 0.0;
+    for (int c = 0; c < g.nterms; ++c) {
+      const LatentDev tm = g.terms[c];
+      double k1, d1;
+      kappa_dx_term<SUM == 2>(tm, dl, ctol, k1, d1);
+      kap += k1; dk += d1;
+    }
+    return;
+  }
+  kappa_dx_term<SUM == 2>(g, dl, ctol, kap, dk);
+}
+
+// toep_predict_kernel's sibling for d var / d xs (a sibling and no template flag: a shared body moved the register allocation of the
+// reducing instantiations).  Workgroup (pair of row blocks, block of TOEP_GRAD_Q = 16 queries, latent), 4 waves.  The B tile keeps the
+// predict kernel's geometry, TPR_T values of s by 32 columns at stride TPR_SB: columns 0 .. 15 hold kappa for the 16 queries, columns
+// 16 .. 31 d kappa / d xs for the same 16; a thread evaluates 2 (kappa, d kappa) pairs per tile through kappa_dx_lat.  The MFMA loop is
+// that kernel's, so accumulator set [j][0] is U = L(g)' K* and set [j][1] is U' = L(g)' K*' for the same rows and queries: a lane ends
+// with u_q, u'_q, u_p, u'_p of 16 (row, query) pairs and adds u_q u'_q - u_p u'_p over them (the three forms of the NumPy restatement,
+// tests/test_toeplitz_vjp_abi.py, lose the same: the one with the fewest operations), lanes and waves then through LDS in a fixed
+// order; the partial goes to part[latent][row block][query].  No atomics; a query's result depends on no other query.
+static_assert(TOEP_PRED_Q == 2 * TOEP_GRAD_Q && TPR_T * TOEP_GRAD_Q == 2 * 256, "toep_predict_grad_kernel's thread maps");
+
+template <int SUM>
+__global__ __launch_bounds__(256) void toep_predict_grad_kernel(double x0, double h, double ctol, int n,
+                                                                const LatentDev* __restrict__ lat, const double* __restrict__ p,
+                                                                const double* __restrict__ q,
+                                                                const double* __restrict__ xs, int ns, int nrb,
+                                                                double* __restrict__ part) {
+  __shared__ double Bt[TPR_T * TPR_SB];
+  __shared__ double wq[TPR_W], wp[TPR_W];
+  __shared__ double red[4][4][TOEP_GRAD_Q];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, l15 = lane & 15, lk = lane >> 4;
+  const int l = blockIdx.z, c0 = blockIdx.y * TOEP_GRAD_Q, nsp = gridDim.y * TOEP_GRAD_Q;
+  const LatentDev g = lat[l];
+  p += (size_t)l * n; q += (size_t)l * n;
+  part += (size_t)l * nrb * nsp;
+  const int ec = t & (TOEP_GRAD_Q - 1), ek = t >> 4;       // the thread evaluates B[ek + 16 e][ec] and [16 + ec], e < 2
+  const bool qlive = c0 + ec < ns;
+  const double xq = qlive ? xs[c0 + ec] : 0.0;
+  for (int half = 0; half < 2; ++half) {
+    const int rbk = half == 0 ? (int)blockIdx.x : nrb - 1 - (int)blockIdx.x;
+    if (half == 1 && rbk <= (int)blockIdx.x) break;        // the middle block of an odd count has no partner
+    const int o0 = rbk * TOEP_PRED_R;
+    d4 aq[4][2], ap[4][2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) { aq[j][cb] = (d4){0.0, 0.0, 0.0, 0.0}; ap[j][cb] = (d4){0.0, 0.0, 0.0, 0.0}; }
+    for (int s0 = o0; s0 < n; s0 += TPR_T) {
+      __syncthreads();
+      for (int w = t; w < TPR_W; w += 256) {
+        const int lag = s0 - o0 - (TOEP_PRED_R - 1) + w;
+        const bool ok = lag >= 0 && lag < n;
+        wq[w] = ok ? q[lag] : 0.0; wp[w] = ok ? p[lag] : 0.0;
+      }
+#pragma unroll 1
+      for (int e = 0; e < 2; ++e) {
+        const int ks = ek + 16 * e, s = s0 + ks;
+        double v = 0.0, dv = 0.0;
+        if (qlive && s < n) kappa_dx_lat<SUM>(g, xq, __builtin_fma((double)s, h, x0), ctol, v, dv);
+        Bt[ks * TPR_SB + ec] = v; Bt[ks * TPR_SB + TOEP_GRAD_Q + ec] = dv;
+      }
+      __syncthreads();
+#pragma unroll 2
+      for (int k4 = 0; k4 < TPR_T / 4; ++k4) {
+        const int ks = 4 * k4 + lk;
+        const double b0 = Bt[ks * TPR_SB + l15], b1 = Bt[ks * TPR_SB + TOEP_GRAD_Q + l15];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int ro = 16 * (4 * j + wv);
+          if (s0 + 4 * k4 + 3 >= o0 + ro) {                // else every s of the k-step lies in front of every row of the tile
+            const int w = ks - (ro + l15) + TOEP_PRED_R - 1;
+            const double fq = wq[w], fp = wp[w];
+            aq[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fq, b0, aq[j][0], 0, 0, 0);
+            aq[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fq, b1, aq[j][1], 0, 0, 0);
+            ap[j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fp, b0, ap[j][0], 0, 0, 0);
+            ap[j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fp, b1, ap[j][1], 0, 0, 0);
+          }
+        }
+      }
+    }
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        sum = __builtin_fma(aq[j][0][r], aq[j][1][r], sum);
+        sum = __builtin_fma(-ap[j][0][r], ap[j][1][r], sum);
+      }
+    __syncthreads();
+    red[wv][lk][l15] = sum;
+    __syncthreads();
+    if (t < TOEP_GRAD_Q) {
+      double v = 0.0;
+      for (int w = 0; w < 4; ++w)
+        for (int k = 0; k < 4; ++k) v += red[w][k][t];
+      part[(size_t)rbk * nsp + c0 + t] = v;
+    }
+  }
+}
+
+// dvar[l ldv + c] = -2 sum over the row blocks, in their order, of part[l][row block][c]
+__global__ __launch_bounds__(256) void toep_predict_grad_finish_kernel(const double* __restrict__ part, int nrb, int nsp, int ns,
+                                                                       double* __restrict__ dvar, size_t ldv) {
+  const int c = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (c >= ns) return;
+  double s = 0.0;
+  for (int b = 0; b < nrb; ++b) s += part[((size_t)l * nrb + b) * nsp + c];
+  dvar[(size_t)l * ldv + c] = -2.0 * s;
+}
+
+// dmean[l ldm + c] = sum_s d kappa(x_0 + s h, xs_c) / d xs_c alpha_l[s].  Workgroup (block of TOEP_GRAD_Q queries, latent): alpha goes
+// through LDS 256 values at a time, thread (query ec, lane ek of 16) takes s = s0 + ek + 16 e, e < 16, in ascending order into one
+// accumulator, and the 16 lanes of a query are added through LDS in their order: no atomics, and a query's sum does not depend on the
+// other queries of the call.
+template <int SUM>
+__global__ __launch_bounds__(256) void toep_mean_grad_kernel(double x0, double h, double ctol, int n,
+                                                             const LatentDev* __restrict__ lat, const double* __restrict__ alpha,
+                                                             const double* __restrict__ xs, int ns, double* __restrict__ dmean,
+                                                             size_t ldm) {
+  __shared__ double al[256];
+  __shared__ double red[16][TOEP_GRAD_Q];
+  const int t = threadIdx.x, ec = t & (TOEP_GRAD_Q - 1), ek = t >> 4, l = blockIdx.y, c0 = blockIdx.x * TOEP_GRAD_Q;
+  const LatentDev g = lat[l];
+  alpha += (size_t)l * n;
+  const bool qlive = c0 + ec < ns;
+  const double xq = qlive ? xs[c0 + ec] : 0.0;
+  double acc = 0.0;
+  for (int s0 = 0; s0 < n; s0 += 256) {
+    __syncthreads();
+    al[t] = s0 + t < n ? alpha[s0 + t] : 0.0;
+    __syncthreads();
+    if (qlive) {
+#pragma unroll 1
+      for (int e = 0; e < 16; ++e) {
+        const int ks = ek + 16 * e, s = s0 + ks;
+        if (s < n) {
+          double v, dv;
+          kappa_dx_lat<SUM>(g, xq, __builtin_fma((double)s, h, x0), ctol, v, dv);
+          acc = __builtin_fma(dv, al[ks], acc);
+        }
+      }
+    }
+  }
+  red[ek][ec] = acc;
+  __syncthreads();
+  if (t < TOEP_GRAD_Q && c0 + t < ns) {
+    double v = 0.0;
+    for (int k = 0; k < 16; ++k) v += red[k][t];
+    dmean[(size_t)l * ldm + c0 + t] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Joint predictive (DESIGN.md 4.22 "Joint predictive"): C = K(xs, xs) - (Uq' Uq - Up' Up) from the products toep_predict_kernel reduces.
 // ---------------------------------------------------------------------------------------------------
 // The storing variant of toep_predict_kernel over the nrbc row blocks from rb0 on: a sibling with that kernel's work split and tile
@@ -6590,6 +6799,28 @@ void launch_toep_predict(double x0, double h, int n, const LatentDev* lat, const
   });
   hipLaunchKernelGGL(toep_predict_finish_kernel, dim3((ns + 255) / 256, nb), dim3(256), 0, st, (const double*)part, nrb,
                      nqb * TOEP_PRED_Q, ns, k0, var, ldv);
+}
+size_t toep_predict_grad_scratch(int n, int ns, int nb) {
+  return (size_t)nb * ((n + TOEP_PRED_R - 1) / TOEP_PRED_R) * ((ns + TOEP_GRAD_Q - 1) / TOEP_GRAD_Q * TOEP_GRAD_Q);
+}
+void launch_toep_predict_grad(double x0, double h, double ctol, int n, const LatentDev* lat, const double* p, const double* q,
+                              const double* xs, int ns, int nb, int mode, double* part, double* dvar, size_t ldv, hipStream_t st) {
+  if (nb <= 0 || ns <= 0) return;
+  const int nrb = (n + TOEP_PRED_R - 1) / TOEP_PRED_R, nqb = (ns + TOEP_GRAD_Q - 1) / TOEP_GRAD_Q;
+  mode_dispatch(mode, [&](auto md) {
+    hipLaunchKernelGGL((toep_predict_grad_kernel<decltype(md)::value>), dim3((nrb + 1) / 2, nqb, nb), dim3(256), 0, st, x0, h, ctol, n, lat,
+                       p, q, xs, ns, nrb, part);
+  });
+  hipLaunchKernelGGL(toep_predict_grad_finish_kernel, dim3((ns + 255) / 256, nb), dim3(256), 0, st, (const double*)part, nrb,
+                     nqb * TOEP_GRAD_Q, ns, dvar, ldv);
+}
+void launch_toep_mean_grad(double x0, double h, double ctol, int n, const LatentDev* lat, const double* alpha, const double* xs, int ns,
+                           int nb, int mode, double* dmean, size_t ldm, hipStream_t st) {
+  if (nb <= 0 || ns <= 0) return;
+  mode_dispatch(mode, [&](auto md) {
+    hipLaunchKernelGGL((toep_mean_grad_kernel<decltype(md)::value>), dim3((ns + TOEP_GRAD_Q - 1) / TOEP_GRAD_Q, nb), dim3(256), 0, st, x0,
+                       h, ctol, n, lat, alpha, xs, ns, dmean, ldm);
+  });
 }
 
 ToepJointPlan toep_joint_plan(int n, int ns, int nb, int rows_forced) {

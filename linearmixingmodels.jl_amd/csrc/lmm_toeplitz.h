@@ -72,6 +72,18 @@ size_t toep_predict_scratch(int n, int ns, int nb);
 void launch_toep_predict(double x0, double h, int n, const LatentDev* lat, const double* k0, const double* p, const double* q,
                          const double* xs, int ns, int nb, int mode, double* part, double* var, size_t ldv, hipStream_t st);
 
+// ---- gradients with respect to the queries (DESIGN.md 4.22 "Gradients with respect to the queries") ----
+#define TOEP_GRAD_Q 16                        // queries of a query block of toep_predict_grad_kernel: kappa and d kappa / d xs share the B tile
+// dvar[l ldv + c] = d var_l(xs_c) / d xs_c = -2 (u_q . u'_q - u_p . u'_p); part: toep_predict_grad_scratch(n, ns, nb) doubles.
+// ctol: |xs_c - (x0 + s h)| <= ctol counts as a coincident pair, whose derivative is 0 for every kind (it matters at the cusp of
+// Matern12 only).  Arguments otherwise as launch_toep_predict's.  ns <= 65535 TOEP_GRAD_Q.
+size_t toep_predict_grad_scratch(int n, int ns, int nb);
+void launch_toep_predict_grad(double x0, double h, double ctol, int n, const LatentDev* lat, const double* p, const double* q,
+                              const double* xs, int ns, int nb, int mode, double* part, double* dvar, size_t ldv, hipStream_t st);
+// dmean[l ldm + c] = sum_s d kappa_l(x0 + s h, xs_c) / d xs_c alpha[l n + s]
+void launch_toep_mean_grad(double x0, double h, double ctol, int n, const LatentDev* lat, const double* alpha, const double* xs, int ns,
+                           int nb, int mode, double* dmean, size_t ldm, hipStream_t st);
+
 // ---- the joint predictive at new inputs (DESIGN.md 4.22 "Joint predictive") ----
 // C_l = K_l(xs, xs) - (Uq' Uq - Up' Up), Uq = L(q)' K*, Up = L(p)' K*: the storing variant of the predict GEMM leaves Uq and Up of a
 // chunk of whole row blocks in U[latent][generator][row of the chunk][nsp], nsp = toep_joint_nsp(ns); the Gram kernel folds the chunk

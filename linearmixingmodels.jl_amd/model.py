@@ -1644,6 +1644,40 @@ class ToeplitzPosterior:
         m, v = self._query(xs, True, True)
         return Normal(m, v ** 0.5)
 
+    def mean_and_var_vjp(self, xs, dmean=None, dvar=None) -> dict:
+        """Pullback of mean_and_var to the queries: {"x": d/d xs of sum(dmean * mean) + sum(dvar * var)} with mean, var =
+        self.mean_and_var(xs), shaped and typed like xs and in the caller's order (include/lmm_hip.h,
+        lmm_oilmm_toeplitz_post_mean_and_var_grad_xs): the variance part is one GEMM on the matrix cores, twice the flops of
+        mean_and_var's, in O(n + ns) memory.  dmean, dvar: by-outputs cotangents of ns * p values, NumPy or torch; dvar=None is the
+        pullback of the mean alone (no GEMM runs), dmean=None that of the variance.  The sigma2 that add_noise adds does not depend
+        on xs, so there is no add_noise argument and no "sigma2" entry.  A query's entry depends on no other query.  Every latent
+        kind of the path is served; where a query coincides with a grid point that point contributes 0 (Matern12 and SHO have a
+        kink there).  Every refusal below comes before any library call."""
+        xs = self._queries(xs)
+        ns = int(xs.shape[0])
+        if dmean is None and dvar is None:
+            raise ValueError("ToeplitzPosterior.mean_and_var_vjp: dmean and dvar are both None")
+        cot = []
+        for name, d in (("dmean", dmean), ("dvar", dvar)):
+            if d is not None:
+                if not hasattr(d, "shape"):
+                    d = np.asarray(d, dtype=np.float64)
+                if len(d.shape) != 1 or int(d.shape[0]) != ns * self.p:
+                    raise ValueError(f"ToeplitzPosterior.mean_and_var_vjp: {name} holds ns * p = {ns * self.p} values by outputs")
+                if L._is_torch(d):
+                    import torch
+                    d = d.to(torch.float64)
+                else:
+                    d = np.ascontiguousarray(d, dtype=np.float64)
+            cot.append(d)
+        gx = _alloc_like(xs, ns)
+        if ns == 0:
+            return {"x": gx}
+        L.check(L.load().lmm_oilmm_toeplitz_post_mean_and_var_grad_xs(self._ptr, L.Arr(xs).ptr, ns,
+                                                                      None if cot[0] is None else L.Arr(cot[0]).ptr,
+                                                                      None if cot[1] is None else L.Arr(cot[1]).ptr, L.Arr(gx, True).ptr))
+        return {"x": gx}
+
 
 def toeplitz_posterior(fx: "FiniteGP", y, blocked: bool = False) -> ToeplitzPosterior:
     """posterior(fx, y) of the models toeplitz_logpdf serves, as a reusable object: one Schur recursion per latent conditions on the
