@@ -988,6 +988,32 @@ int lmm_oilmm_toeplitz_post_rand_at(const lmm_toep_post_t* post, const double* x
                                     const double* z, const double* eps /* iff add_noise */, double* out);
 int lmm_dev_toeplitz_predict_cov(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const double* xs, int ns,
                                  double diag, int chunk_rows, double* cov, int ldc);
+/* Toeplitz: missing observations, NaN in y (DESIGN.md 4.22 "Missing observations").  With the k points S that have a NaN the covariance
+ * of a latent's pseudo-observations is the Toeplitz matrix T = K_l + (sigma2 / S_l) I plus a diagonal correction on S, restricted to the
+ * points with data.  One recursion and one Gohberg-Semencul solve as for complete data, the block B = (T^-1)[S, S] from the generators
+ * (a GEMM on v_mfma_f64_16x16x4_f64 over gathered windows of p and q: one owner per tile, a fixed order, no atomics, bitwise
+ * reproducible) and the k x k matrix M = D B D + F through the dense path's batched Cholesky give the value exactly:
+ *   log N = -1/2 [ z' alpha - a' M^-1 a + log det T + log det M + n_obs log 2 pi ],  a = d o alpha[S];
+ * a point without any observed output has d = 1, f = 0, z = 0 and stays in the grid; every other point of S has
+ * d = sqrt(max(w_t - sigma2 / S_l, 0)), f = 1 with the front end's w_t = sigma2 (G_t^-1)_ll.  O(n^2 + k^2 n + k^3) time, O(n + k^2) memory.
+ *   lmm_toeplitz_missing_max_k : the cap on k (4096, as lmm_toeplitz_joint_max_ns: the same Cholesky, the same k^2 memory).
+ *   lmm_oilmm_logpdf_toeplitz_missing : arguments, refusals and check order of lmm_oilmm_logpdf_toeplitz, with NaN in y served; blocked
+ *                    != 0 runs the blocked schedule and takes its cap on n.  Further refusals: a point that observes 0 < p_t < m
+ *                    outputs -> LMM_ERR_UNSUPPORTED, a singular G_t -> LMM_ERR_NOT_PD, both with the point in lmm_last_error_detail;
+ *                    no point with data -> LMM_ERR_ARG; k > the cap -> LMM_ERR_UNSUPPORTED naming k; an M that cannot be factored ->
+ *                    LMM_ERR_NOT_PD naming the latent.  Without NaN the value is bitwise lmm_oilmm_logpdf_toeplitz[_blocked]'s.  Partial
+ *                    sums over the shard, as its siblings give them.
+ *   lmm_dev_toeplitz_inverse_block : building block for tests, DEVICE pointers, one matrix: B[j ldb + i] = (T^-1)[idx[i], idx[j]] for
+ *                    k > i >= j from the generators of lmm_dev_toeplitz_factor; nothing else of B is written.  idx: k ascending,
+ *                    distinct values in [0, n), else LMM_ERR_ARG; ldb >= k; n <= lmm_toeplitz_blocked_max_n().
+ *   lmm_toeplitz_missing_last_ms : where the last lmm_oilmm_logpdf_toeplitz_missing spent its device time, by events on its stream: the
+ *                    recursion (first columns included), the inverse block, the finish kernel with the factorisation; any may be
+ *                    NULL.  For tools/toeplitz_missing_bench.py. */
+int lmm_toeplitz_missing_max_k(void);
+int lmm_oilmm_logpdf_toeplitz_missing(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                                      const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, int blocked, double* out);
+int lmm_dev_toeplitz_inverse_block(const double* p, const double* q, int n, const int* idx, int k, double* B, int ldb);
+int lmm_toeplitz_missing_last_ms(double* recursion_ms, double* block_ms, double* factor_ms);
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
                               const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,

@@ -6118,7 +6118,7 @@ struct ToepJointClock {
     marks.emplace_back(e, stage);
     HIPCHK(hipEventRecord(e, st));
   }
-  void read() {
+  void read(double* dst = g_toep_joint_ms) {
     double ms[3] = {0.0, 0.0, 0.0};
     for (size_t i = 0; i + 1 < marks.size(); ++i)
       if (marks[i].second >= 0) {
@@ -6126,7 +6126,7 @@ struct ToepJointClock {
         HIPCHK(hipEventElapsedTime(&part, marks[i].first, marks[i + 1].first));
         ms[marks[i].second] += part;
       }
-    std::copy(ms, ms + 3, g_toep_joint_ms);
+    std::copy(ms, ms + 3, dst);
   }
   ~ToepJointClock() { for (auto& mk : marks) g.ev_pool.push_back(mk.first); }
 };
@@ -6331,6 +6331,136 @@ int lmm_toeplitz_joint_last_ms(double* gemm_ms, double* gram_ms, double* factor_
   if (gram_ms) *gram_ms = g_toep_joint_ms[1];
   if (factor_ms) *factor_ms = g_toep_joint_ms[2];
   return LMM_OK;
+}
+
+// ---- Toeplitz path: missing observations (DESIGN.md 4.22 "Missing observations") ------------------------------------------------------
+// With the k points S that have a NaN, the covariance of a latent's pseudo-observations is T + diag(e) restricted to the points with
+// data, T = K_l + w0 I the Toeplitz matrix of complete data.  By the determinant lemma and the Woodbury identity over S alone,
+//   log N = -1/2 [ z' alpha - a' M^-1 a + log det T + log det M + n_obs log 2 pi ],   M = D B D + F,  B = (T^-1)[S, S],  a = d o alpha[S],
+// with z = 0 at the points without data: one recursion and one solve as for complete data, B from the generators
+// (toep_inverse_block_kernel), and M with two riders (a, and zeros: lml_reduce then gives log det M and a' M^-1 a apart) through the
+// dense path's batched Cholesky, as toep_joint_factor runs it.
+int lmm_toeplitz_missing_max_k(void) { return TOEP_MISSING_MAX_K; }
+static double g_toep_missing_ms[3] = {0.0, 0.0, 0.0};      // recursion, inverse block, finish + factorisation: of the last call
+int lmm_toeplitz_missing_last_ms(double* recursion_ms, double* block_ms, double* factor_ms) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (recursion_ms) *recursion_ms = g_toep_missing_ms[0];
+  if (block_ms) *block_ms = g_toep_missing_ms[1];
+  if (factor_ms) *factor_ms = g_toep_missing_ms[2];
+  return LMM_OK;
+}
+
+int lmm_oilmm_logpdf_toeplitz_missing(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                                      const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, int blocked, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!out) return fail(LMM_ERR_ARG, "bad arguments");
+  ToepTrain T;
+  if (int rc = toep_inputs(!y, x, n, p, U, S, m, sigma2, gps, latent_begin, latent_end, blocked != 0, -1, T)) return rc;
+  hipStream_t st0 = g.streams[0];
+  T.yd = DevIn(y, (size_t)n * p, st0);
+  std::vector<int> sidx;                // S: the points with a NaN, ascending
+  {
+    Buf<unsigned long long> masks((size_t)n * ((p + 63) / 64));
+    Buf<int> pt(n);
+    std::vector<int> hpt(n);
+    launch_missing_masks(T.yd.p, n, p, masks.p, pt.p, st0);
+    HIPCHK(hipMemcpyAsync(hpt.data(), pt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st0));
+    HIPCHK(hipStreamSynchronize(st0));
+    for (int t = 0; t < n; ++t)
+      if (hpt[t] != p) sidx.push_back(t);
+  }
+  const int k = (int)sidx.size(), ms = T.ms, mk = T.mk;
+  SSFront Fr;                           // w = +Inf and r = 0 at the points without data, which stay in the grid
+  if (int rc = ss_front(T.yd.p, n, p, U, S, m, sigma2, T.lts, T.l0, T.l1, Fr)) return rc;
+  if (Fr.nobs == 0) return fail(LMM_ERR_ARG, "missing data: no point has an observed output");
+  if (k > TOEP_MISSING_MAX_K)
+    return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves k <= %d points with a NaN in y (lmm_toeplitz_missing_max_k; k = %d)",
+                TOEP_MISSING_MAX_K, k);
+  const bool corr = k > 0 && ms > 0;
+  Buf<int> idxd(std::max(k, 1));
+  Buf<double> dv((size_t)std::max(k, 1) * mk), fv((size_t)std::max(k, 1) * mk);
+  if (corr) {
+    HIPCHK(hipMemcpyAsync(idxd.p, sidx.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st0));
+    std::vector<double> w0(ms);
+    for (int j = 0; j < ms; ++j) w0[j] = sigma2 / S[T.l0 + j];
+    Uploaded w0u(w0, st0);
+    launch_toep_missing_prep(Fr.w.p, n, idxd.p, k, w0u.buf.p, ms, dv.p, fv.p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));  // sidx and w0 have been read
+  }
+  ToepJointClock ck;
+  ck.mark(0, st0);
+  ToepWork W;
+  if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, ms, Fr.w.p, Fr.r.p, blocked != 0, W)) return rc;
+  ck.mark(-1, st0);
+  const double L2PI = std::log(2.0 * M_PI);
+  double total = 0.0;
+  for (int j = 0; j < ms; ++j) total += W.lml[j];
+  if (corr) {
+    Buf<double> al((size_t)n * mk), u(2 * (size_t)n * mk), outd(2 * (size_t)mk);
+    std::vector<double> ho(2 * (size_t)mk, 0.0);
+    launch_toep_solve(W.p.p, W.q.p, Fr.r.p, n, ms, u.p, al.p, st0);
+    const Dims Ds(k, 2);
+    FanOut F = FanOut::one_slot(ms);
+    int* info = F.alloc_info();
+    std::vector<Buf<double>> B, WB;
+    for (int j = 0; j < F.nb_per; ++j) { B.emplace_back(Ds.elems()); WB.emplace_back((size_t)(Ds.NC / 64) * 4096); }
+    F.run([&](const FanBatch& b) {
+      Batch Bt;
+      for (int j = 0; j < b.nb; ++j) {
+        Bt.add(B[j].p, WB[j].p, info + b.k0 + j);
+        guard_extent(B[j].p, Ds.NC, Ds.ld, Ds.NC, false, "Toeplitz missing data (inverse block tiles)");
+      }
+      ck.mark(1, b.st);
+      launch_toep_inverse_block(W.p.p + (size_t)b.k0 * n, W.q.p + (size_t)b.k0 * n, n, idxd.p, k, Bt.A, Ds.ld, b.nb, true, b.st);
+      ck.mark(2, b.st);
+      launch_toep_missing_finish(Bt.A, Ds.ld, Ds.NR, Ds.NC, k, idxd.p, dv.p + (size_t)b.k0 * k, fv.p + (size_t)b.k0 * k,
+                                 al.p + (size_t)b.k0 * n, n, b.nb, b.st);
+      potrf_batch(Bt, Ds.ld, Ds.NR, Ds.NC, k, b.st);
+      launch_lml_reduce(Bt.A, b.nb, Ds.ld, k, Ds.NC, 2, outd.p + 2 * (size_t)b.k0, b.st);
+      ck.mark(-1, b.st);
+      HIPCHK(hipMemcpyAsync(ho.data() + 2 * (size_t)b.k0, outd.p + 2 * (size_t)b.k0, 2 * (size_t)b.nb * sizeof(double), hipMemcpyDeviceToHost, b.st));
+    });
+    HIPCHK(hipGetLastError());
+    if (int rc = F.check(T.l0)) return rc;
+    // rider 0: -1/2 (k log 2 pi + log det M + a' M^-1 a), rider 1: the same without the quadratic form
+    for (int j = 0; j < ms; ++j) total += (ho[2 * j + 1] - ho[2 * j]) + (ho[2 * j + 1] + 0.5 * (double)k * L2PI);
+  }
+  if (Fr.nobs < n) total += 0.5 * (double)ms * (double)(n - Fr.nobs) * L2PI;      // the points without data leave the Gaussian
+  if (with_regulariser) total += Fr.reg;
+  HIPCHK(hipStreamSynchronize(st0));
+  ck.read(g_toep_missing_ms);
+  *out = total;
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_dev_toeplitz_inverse_block(const double* p, const double* q, int n, const int* idx, int k, double* B, int ldb) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!p || !q || !idx || !B || n <= 0 || k <= 0 || ldb < k) return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return toep_refuse_f32();
+  if (int rc = toep_check_n(n, true)) return rc;
+  if (k > TOEP_MISSING_MAX_K)
+    return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves k <= %d points with a NaN in y (lmm_toeplitz_missing_max_k; k = %d)",
+                TOEP_MISSING_MAX_K, k);
+  hipStream_t st0 = g.streams[0];
+  std::vector<int> h(k);
+  HIPCHK(hipMemcpyAsync(h.data(), idx, (size_t)k * sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  for (int i = 0; i < k; ++i)
+    if (h[i] < 0 || h[i] >= n || (i > 0 && h[i] <= h[i - 1]))
+      return fail(LMM_ERR_ARG, "idx must be ascending and distinct in [0, n): idx[%d] = %d", i, h[i]);
+  BatchPtr Bb{};
+  Bb.p[0] = B;
+  launch_toep_inverse_block(p, q, n, idx, k, Bb, ldb, 1, false, st0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
 }
 
 // Building blocks for tests: ONE latent from device pointers, per-point noise w (+Inf: unobserved) and data r; the latent's mean is

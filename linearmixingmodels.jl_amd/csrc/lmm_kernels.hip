@@ -6755,6 +6755,139 @@ __global__ __launch_bounds__(256) void toep_gram_kernel(const double* __restrict
       for (int r = 0; r < 4; ++r) Gt[(size_t)(16 * a + 4 * r) * ld + 16 * b] = acc[a][b][r];
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Missing observations (DESIGN.md 4.22 "Missing observations"): a block of the inverse from the generators,
+//     B[i][j] = (T^-1)[s_i, s_j] = sum_{c <= min(s_i, s_j)} q[s_i - c] q[s_j - c] - p[s_i - c] p[s_j - c],      s = idx, ascending,
+// as a GEMM over c whose operand rows are windows of the generators read backwards, A[i][c] = q[s_i - c] (0 for c > s_i): nothing of
+// size k x n exists anywhere.  Ownership, wave layout, accumulators and fragment reads are toep_gram_kernel's: workgroup (tile pair
+// ti >= tj of TOEP_JOINT_T, latent) owns B[ti][tj]; 4 waves in 2 x 2, each a 64 x 64 quarter as 4 x 4 accumulators of 16 x 16.  The sum
+// over c runs in chunks of TIB_K in ascending order, per chunk the q panel and then the p panel with the A operand negated, through the
+// same accumulators: one chain per element whatever the launch, no atomics.  The loop ends at the largest index of the tile's column
+// block (beyond it every window of the j side is zero).  Staging: thread (row = t & 127, half = t >> 7) reads the 8 consecutive
+// doubles q[s_row - c0 - 8 half - 7 .. s_row - c0 - 8 half] of its row's window (a window is one 128-byte piece of the generator; over
+// a run of consecutive points the 64 lanes of a wave read 64 consecutive doubles per load, so an outage needs no staging of its own)
+// and writes them k-major at stride TG_S, a wave's 64 rows on 64 distinct banks.  The next panel's loads are in flight in registers
+// while this one is multiplied.  Rows from k on carry the index -1: their windows are zeros.
+// whole: every tile on or below the diagonal is written whole (the layout of a factor matrix: rows and columns < rup(k, TOEP_JOINT_T),
+// the diagonal tiles on both sides, which are bitwise symmetric); else only i >= j, i < k.
+constexpr int TIB_K = 16;
+static_assert(TIB_K == TG_K && 2 * 8 == TIB_K && 256 == 2 * TOEP_JOINT_T, "toep_inverse_block_kernel's thread maps");
+
+__global__ __launch_bounds__(256) void toep_inverse_block_kernel(const double* __restrict__ p, const double* __restrict__ q, int n,
+                                                                 const int* __restrict__ idx, int k, BatchPtr B, int ld, int whole) {
+  __shared__ double Pi[TIB_K * TG_S], Pj[TIB_K * TG_S];
+  __shared__ int si[TOEP_JOINT_T], sj[TOEP_JOINT_T];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, l15 = lane & 15, lk = lane >> 4, wr = wv >> 1, wc = wv & 1;
+  int ti = 0;
+  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
+  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2, l = blockIdx.y;
+  const int i0 = ti * TOEP_JOINT_T, j0 = tj * TOEP_JOINT_T;
+  const bool diag = ti == tj;
+  const double* Pa = diag ? Pi : Pj;                       // the j side: the same panel on the diagonal
+  p += (size_t)l * n; q += (size_t)l * n;
+  if (t < TOEP_JOINT_T) {
+    si[t] = i0 + t < k ? idx[i0 + t] : -1;
+    sj[t] = j0 + t < k ? idx[j0 + t] : -1;
+  }
+  __syncthreads();
+  const int nch = sj[min(TOEP_JOINT_T, k - j0) - 1] / TIB_K + 1;      // chunks up to the column block's largest index
+  const int row = t & (TOEP_JOINT_T - 1), half = t >> 7;
+  const int srow_i = si[row], srow_j = diag ? -1 : sj[row];
+  d4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = d4{0.0, 0.0, 0.0, 0.0};
+  double ri[8], rj[8];
+  auto fetch = [&](int ch, int gn) {
+    const double* __restrict__ src = gn ? p : q;
+    const int c = ch * TIB_K + 8 * half;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int ai = srow_i - c - e, aj = srow_j - c - e;      // < n always; < 0: beyond the window's end
+      ri[e] = ai >= 0 ? src[ai] : 0.0;
+      rj[e] = aj >= 0 ? src[aj] : 0.0;
+    }
+  };
+  int ch = 0, gn = 0;
+  bool more = true;
+  fetch(0, 0);
+  while (more) {
+    const bool neg = gn == 1;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      Pi[(8 * half + e) * TG_S + row] = ri[e];
+      if (!diag) Pj[(8 * half + e) * TG_S + row] = rj[e];
+    }
+    __syncthreads();
+    if (++gn == 2) { gn = 0; ++ch; }
+    more = ch < nch;
+    if (more) fetch(ch, gn);
+#pragma unroll
+    for (int k4 = 0; k4 < TIB_K / 4; ++k4) {
+      const int ko = (4 * k4 + lk) * TG_S + l15;
+      double fa[4], fb[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const double v = Pa[ko + 64 * wc + 16 * a];
+        fa[a] = neg ? -v : v;
+        fb[a] = Pi[ko + 64 * wr + 16 * a];
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+    }
+  }
+  double* Bl = B.p[l];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = j0 + 64 * wc + 16 * a + 4 * r + lk, i = i0 + 64 * wr + 16 * b + l15;
+        if (whole || (i >= j && i < k)) Bl[(size_t)j * ld + i] = acc[a][b][r];
+      }
+}
+
+// Where a point of S stands (toep_missing_finish_kernel): d = 1, f = 0 at a point without any observed output (its noise is +Inf),
+// else d = sqrt(max(w_t - w0, 0)), f = 1; thread (i < k, latent).  w: [latent][n], the front end's per-point noise; its element 0, which
+// launch_toep_row reads, becomes the complete-data noise w0[l] (thread 0 alone reads and then writes it: idx is ascending).
+__global__ __launch_bounds__(256) void toep_missing_prep_kernel(double* w, int n, const int* __restrict__ idx, int k,
+                                                                const double* __restrict__ w0, double* __restrict__ d,
+                                                                double* __restrict__ f) {
+  const int i = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (i >= k) return;
+  const double wt = w[(size_t)l * n + idx[i]], base = w0[l];
+  const bool gone = wt == INFINITY;
+  d[(size_t)l * k + i] = gone ? 1.0 : sqrt(fmax(wt - base, 0.0));
+  f[(size_t)l * k + i] = gone ? 0.0 : 1.0;
+  if (i == 0) w[(size_t)l * n] = base;
+}
+
+// M = D B D + F in place, in the layout potrf_batch takes (Dims(k, 2)): thread (row i, column j, latent) over the whole 64 x 64 tiles
+// of the lower triangle; the identity on the padding columns, the rider a = d o alpha[S] in row NC, zeros in the other rows from k on.
+// d_i d_j is formed first, so the two sides of a diagonal tile stay bitwise symmetric.
+__global__ __launch_bounds__(256) void toep_missing_finish_kernel(BatchPtr M, int ld, int NR, int NC, int k, const int* __restrict__ idx,
+                                                                  const double* __restrict__ d, const double* __restrict__ f,
+                                                                  const double* __restrict__ alpha, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, l = blockIdx.z;
+  if (i >= NR || (i >> 6) < (j >> 6)) return;
+  d += (size_t)l * k; f += (size_t)l * k;
+  double v = 0.0;
+  if (i < k && j < k) {
+    v = M.p[l][(size_t)j * ld + i] * (d[i] * d[j]);
+    if (i == j) v += f[i];
+  } else if (j >= k) {
+    v = i == j ? 1.0 : 0.0;
+  } else if (i == NC) {
+    v = d[j] * alpha[(size_t)l * n + idx[j]];
+  }
+  M.p[l][(size_t)j * ld + i] = v;
+}
+
 // C + d I from G, in place or into the caller's matrix (launch_toep_cov_finish in lmm_toeplitz.h): thread (row i, column j, latent).
 // kappa takes the larger input first, so that the value of a pair does not depend on which of the two is the row.
 template <int SUM>
@@ -6863,4 +6996,19 @@ void launch_toep_cov_finish(const LatentDev* lat, const double* xs, int ns, cons
     hipLaunchKernelGGL((toep_cov_finish_kernel<decltype(md)::value>), grid, dim3(256), 0, st, lat, xs, ns, G, ldg, out, ldo, NR, NC, diag,
                        rider, pad ? 1 : 0);
   });
+}
+void launch_toep_inverse_block(const double* p, const double* q, int n, const int* idx, int k, const BatchPtr& B, int ld, int nb, bool whole,
+                               hipStream_t st) {
+  if (nb <= 0 || k <= 0) return;
+  const int nt = (k + TOEP_JOINT_T - 1) / TOEP_JOINT_T;
+  hipLaunchKernelGGL(toep_inverse_block_kernel, dim3(nt * (nt + 1) / 2, nb), dim3(256), 0, st, p, q, n, idx, k, B, ld, whole ? 1 : 0);
+}
+void launch_toep_missing_prep(double* w, int n, const int* idx, int k, const double* w0, int nb, double* d, double* f, hipStream_t st) {
+  if (nb <= 0 || k <= 0) return;
+  hipLaunchKernelGGL(toep_missing_prep_kernel, dim3((k + 255) / 256, nb), dim3(256), 0, st, w, n, idx, k, w0, d, f);
+}
+void launch_toep_missing_finish(const BatchPtr& M, int ld, int NR, int NC, int k, const int* idx, const double* d, const double* f,
+                                const double* alpha, int n, int nb, hipStream_t st) {
+  if (nb <= 0 || k <= 0) return;
+  hipLaunchKernelGGL(toep_missing_finish_kernel, dim3((NR + 255) / 256, NC, nb), dim3(256), 0, st, M, ld, NR, NC, k, idx, d, f, alpha, n);
 }

@@ -112,3 +112,18 @@ void launch_toep_gram(const double* U, int n, int row0, int rows, int ns, const 
 // diag: nb values, rider: [latent][ns], both on the device.  out may be G.
 void launch_toep_cov_finish(const LatentDev* lat, const double* xs, int ns, const BatchPtr& G, int ldg, const BatchPtr& out, int ldo, int NR,
                             int NC, const double* diag, const double* rider, bool pad, int nb, int mode, hipStream_t st);
+
+// ---- missing observations (DESIGN.md 4.22 "Missing observations") ----
+#define TOEP_MISSING_MAX_K TOEP_JOINT_MAX_NS  // the same Cholesky and the same k^2 memory as the joint predictive
+// B_l[i][j] = (T_l^-1)[idx[i], idx[j]] from the generators p, q [l n ..] of the nb latents, element (i, j) at B.p[l][j ld + i]; idx: k
+// ascending distinct points in [0, n) (device), the same for every latent.  whole: the TOEP_JOINT_T tiles on and below the diagonal
+// are written whole (i, j < rup(k, TOEP_JOINT_T); zeros from k on); else the lower triangle i >= j, i < k and nothing else.
+void launch_toep_inverse_block(const double* p, const double* q, int n, const int* idx, int k, const BatchPtr& B, int ld, int nb, bool whole,
+                               hipStream_t st);
+// d, f [l k ..] of the points idx from the per-point noise w ([latent][n]; +Inf: no observed output) and the complete-data noise w0[l];
+// w[l n] becomes w0[l], which launch_toep_row then reads
+void launch_toep_missing_prep(double* w, int n, const int* idx, int k, const double* w0, int nb, double* d, double* f, hipStream_t st);
+// M_l = D B_l D + F in place (B as launch_toep_inverse_block leaves it with `whole`), in the layout of Dims(k, 2): the identity on the
+// padding columns, the rider d o alpha_l[idx] in row NC, zeros in row NC + 1 and the other rows from k on
+void launch_toep_missing_finish(const BatchPtr& M, int ld, int NR, int NC, int k, const int* idx, const double* d, const double* f,
+                                const double* alpha, int n, int nb, hipStream_t st);

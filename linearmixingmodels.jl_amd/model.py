@@ -1464,6 +1464,24 @@ def toeplitz_logpdf(fx: "FiniteGP", y, with_regulariser: bool = True, blocked: b
     return out.value
 
 
+def toeplitz_logpdf_missing(fx: "FiniteGP", y, blocked: bool = False, *, with_regulariser: bool = True) -> float:
+    """toeplitz_logpdf(fx, y) for data with holes: NaN in y means missing (DESIGN.md 4.22 "Missing observations").  A point without
+    any observed output stays in the grid; every other point must observe at least m outputs, as logpdf's missing-data path asks.
+    With the k points that have a NaN the covariance is Toeplitz plus a correction on those points, and the k x k block of the
+    inverse that the exact value needs comes from the recursion's generators: O(n^2 + k^2 n + k^3) time, O(n + k^2) memory per latent,
+    k <= lmm_toeplitz_missing_max_k.  Without NaN the value is bitwise toeplitz_logpdf's.  x and y: NumPy arrays or torch device
+    tensors; blocked: as toeplitz_logpdf's.  Gradients and a posterior handle for such data are not served yet."""
+    y = _toeplitz_args(fx, y, "toeplitz_logpdf_missing")
+    f, x = fx.f, fx.x
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    out = C.c_double()
+    L.check(L.load().lmm_oilmm_logpdf_toeplitz_missing(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2), gps,
+                                                       0, m, int(with_regulariser), int(blocked), C.byref(out)))
+    return out.value
+
+
 def toeplitz_logpdf_and_gradient(fx: "FiniteGP", y, with_regulariser: bool = True, blocked: bool = False) -> dict:
     """Value and gradient of toeplitz_logpdf(fx, y): {"value", "y", "sigma2", "S", "U", "gps"}, as logpdf_and_gradient returns them for
     a prior OILMM ("gps" through _gps_grads: every latent's kernel parameters, tags and sum terms included, and its mean).  "value" is
