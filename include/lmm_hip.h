@@ -1014,6 +1014,35 @@ int lmm_oilmm_logpdf_toeplitz_missing(const double* x, int n, const double* y, i
                                       const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, int blocked, double* out);
 int lmm_dev_toeplitz_inverse_block(const double* p, const double* q, int n, const int* idx, int k, double* B, int ldb);
 int lmm_toeplitz_missing_last_ms(double* recursion_ms, double* block_ms, double* factor_ms);
+/* Toeplitz: the posterior handle for gappy grids (DESIGN.md 4.22 "Posterior handle for gappy grids").  The identity the value rests on,
+ *   J_O C^-1 J_O' = T^-1 - T^-1[:, S] D M^-1 D T^-1[S, :],
+ * gives the mean as k*' alpha-hat with alpha-hat = alpha - T^-1 J_S (d o M^-1 a), an n-vector formed once, and the variance as that of
+ * complete data plus |L_M^-1 (d o V[:, *])|^2 with V = (T^-1 K*)[S, :], a GEMM on v_mfma_f64_16x16x4_f64 of gathered windows of the
+ * generators with the stored products of the predict GEMM (one owner per tile, a fixed order, no atomics: bitwise reproducible).
+ *   lmm_oilmm_toeplitz_posterior_create_missing : lmm_oilmm_toeplitz_posterior_create with NaN in y served, by either schedule
+ *                    (blocked != 0: the blocked one and its cap on n).  Refusals and their order are those of
+ *                    lmm_oilmm_logpdf_toeplitz_missing; *out_logpdf (NULL: not wanted) is bitwise its value with the regulariser.
+ *                    Without NaN the handle has no gap state and every result is bitwise that of the complete-data handle.  With k
+ *                    points that have a NaN the handle holds, beyond its 3 n doubles per latent, the factored M: rup(k, 128)^2 doubles
+ *                    per latent (with two rider rows and the inverse diagonal blocks): 4.3 GB for 32 latents at the cap k = 4096.
+ *                    lmm_oilmm_toeplitz_post_mean_and_var serves such a handle (var == NULL: the correction does not run); a query's
+ *                    result does not depend on the other queries.  lmm_oilmm_toeplitz_post_rand, _rand_at, _post_logpdf and
+ *                    _post_mean_and_var_grad_xs refuse it with LMM_ERR_UNSUPPORTED.
+ *   lmm_toeplitz_post_gap_k : *k = the number of points with a NaN the handle was built with (0: no gap state).
+ *   lmm_dev_toeplitz_inverse_rows : building block for tests, DEVICE pointers, one latent: V[i ldv + j] = (T^-1 K*)[idx[i], j] for i < k,
+ *                    j < ns over the grid x0 + t h, t < n, from the generators of lmm_dev_toeplitz_factor; nothing else of V is
+ *                    written.  rows_forced: the rows of a chunk of the storing GEMM (a multiple of 256; 0: the library's plan); V does
+ *                    not depend on it.  Refusals: those of lmm_dev_toeplitz_inverse_block and lmm_dev_toeplitz_predict_cov; ldv >= ns.
+ *   lmm_toeplitz_missing_post_last_ms : where the last lmm_oilmm_toeplitz_post_mean_and_var on a handle with gap state spent its device
+ *                    time: the predict of complete data (means included), the storing GEMM, the inverse-rows kernel, the solve with the
+ *                    sums of squares; any may be NULL.  For tools/toeplitz_missing_posterior_bench.py. */
+int lmm_oilmm_toeplitz_posterior_create_missing(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                                double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                                lmm_toep_post_t** out, double* out_logpdf, int blocked);
+int lmm_toeplitz_post_gap_k(const lmm_toep_post_t* post, int* k);
+int lmm_dev_toeplitz_inverse_rows(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const int* idx, int k,
+                                  const double* xs, int ns, int rows_forced, double* V, int ldv);
+int lmm_toeplitz_missing_post_last_ms(double* predict_ms, double* gemm_ms, double* rows_ms, double* solve_ms);
 int lmm_oilmm_rand_statespace(const double* x, int n, const double* y /* NULL: prior sample */, int p,
                               const double* U, const double* S, int m, double sigma2,
                               const lmm_gp_t* gps, int latent_begin, int latent_end, int add_noise, int nsamples,

@@ -10,7 +10,8 @@ from .model import (GP, ILMM, OILMM, FiniteGP, IndependentMOGP, Matern12Kernel, 
                     marginals, mean, mean_and_cov, cov, mean_and_var, mean_and_var_vjp, noise_var, posterior, rand, reshape_y, unpack, var,
                     VFE, elbo, dtc, approx_posterior, elbo_and_gradient, statespace_logpdf, statespace_mean_and_var,
                     statespace_logpdf_and_gradient, statespace_rand, statespace_posterior, StateSpacePosterior,
-                    toeplitz_logpdf, toeplitz_logpdf_missing, toeplitz_logpdf_and_gradient, toeplitz_posterior, ToeplitzPosterior, toeplitz_rand)
+                    toeplitz_logpdf, toeplitz_logpdf_missing, toeplitz_logpdf_and_gradient, toeplitz_posterior, toeplitz_posterior_missing, ToeplitzPosterior,
+                    toeplitz_rand)
 from .parallel import select_collective, latent_shard, sharded_logpdf, sharded_mean_and_var, sharded_posterior, sharded_rand
 
 __all__ = [
@@ -20,6 +21,6 @@ __all__ = [
     "logpdf", "logpdf_and_gradient", "posterior", "rand", "marginals", "mean_and_var", "mean_and_var_vjp", "mean_and_cov", "mean", "var", "cov", "noise_var", "reshape_y", "unpack",
     "VFE", "elbo", "dtc", "approx_posterior", "elbo_and_gradient",   # AbstractGPs' inducing-point approximation on the latents of an OILMM
     "statespace_logpdf", "statespace_mean_and_var", "statespace_logpdf_and_gradient", "statespace_rand", "statespace_posterior", "StateSpacePosterior",   # Kalman filter / RTS smoother on Matern and SHO latents over one-dimensional inputs
-    "toeplitz_logpdf", "toeplitz_logpdf_missing", "toeplitz_logpdf_and_gradient", "toeplitz_posterior", "ToeplitzPosterior", "toeplitz_rand",   # Schur recursion on stationary latents over an evenly spaced one-dimensional grid
+    "toeplitz_logpdf", "toeplitz_logpdf_missing", "toeplitz_logpdf_and_gradient", "toeplitz_posterior", "toeplitz_posterior_missing", "ToeplitzPosterior", "toeplitz_rand",   # Schur recursion on stationary latents over an evenly spaced one-dimensional grid
     "select_collective", "latent_shard", "sharded_logpdf", "sharded_mean_and_var", "sharded_posterior", "sharded_rand", "init", "load", "PosDefException", "LMMError", "set_compute_dtype", "get_compute_dtype", "set_strict_progress", "get_strict_progress", "set_projection_dtype", "get_projection_dtype", "wait_stream",
 ]

@@ -53,6 +53,7 @@ SYMBOLS = [
     "lmm_dev_toeplitz_predict_cov", "lmm_toeplitz_joint_last_ms",
     "lmm_oilmm_toeplitz_post_mean_and_var_grad_xs", "lmm_dev_toeplitz_predict_grad",
     "lmm_toeplitz_missing_max_k", "lmm_oilmm_logpdf_toeplitz_missing", "lmm_dev_toeplitz_inverse_block", "lmm_toeplitz_missing_last_ms",
+    "lmm_oilmm_toeplitz_posterior_create_missing", "lmm_toeplitz_post_gap_k", "lmm_dev_toeplitz_inverse_rows", "lmm_toeplitz_missing_post_last_ms",
     "lmm_dev_potrf", "lmm_dev_check_info", "lmm_dev_extent_check", "lmm_dev_region_plan", "lmm_dev_flag_epoch", "lmm_dev_gemm_nt_sub", "lmm_dev_gram", "lmm_dev_write_rate", "lmm_dev_mfma_f64_peak",
     "lmm_dev_set_f64_emul", "lmm_dev_syrk_emul", "lmm_dev_emul_host", "lmm_dev_emul_residues", "lmm_dev_set_emul_gemm_workgroups", "lmm_dev_emul_acc_residues",
     "lmm_dev_set_f64_emul_rule", "lmm_dev_set_emul_group", "lmm_dev_set_emul_amax_reuse", "lmm_dev_emul_plan", "lmm_dev_potrf_plan",
@@ -123,6 +124,10 @@ STATESPACE_ARGTYPES = {
     "lmm_oilmm_logpdf_toeplitz_missing": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _I, _P],
     "lmm_dev_toeplitz_inverse_block": [_P, _P, _I, _P, _I, _P, _I],
     "lmm_toeplitz_missing_last_ms": [_P, _P, _P],
+    "lmm_oilmm_toeplitz_posterior_create_missing": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _P, _P, _I],
+    "lmm_toeplitz_post_gap_k": [_P, _P],
+    "lmm_dev_toeplitz_inverse_rows": [_D, _D, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _I],
+    "lmm_toeplitz_missing_post_last_ms": [_P, _P, _P, _P],
     "lmm_dev_statespace_grad_x": [_P, _I, _P, _P, _P, _I, _P],
     "lmm_oilmm_statespace_post_mean_and_var_grad_xs": [_P, _P, _I, _P, _P, _P],
     "lmm_oilmm_rand_statespace": [_P, _I, _P, _I, _P, _P, _I, _D, _P, _I, _I, _I, _I, _P, _P, _P, _P],

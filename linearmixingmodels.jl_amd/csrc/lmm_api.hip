@@ -5867,7 +5867,20 @@ struct lmm_toep_post {
   Buf<double> H;                      // p x (l1 - l0), column-major: H = U sqrt(S) of the shard
   std::vector<double> w;              // per latent of the shard: its noise sigma2 / S_l (read by lmm_oilmm_toeplitz_post_rand)
   std::vector<double> U, S;           // the mixing as the handle was built with it (p x m, m): the front end of lmm_oilmm_toeplitz_post_logpdf
+  // The gap state (lmm_oilmm_toeplitz_posterior_create_missing with NaN in y; k == 0: none, the handle is that of complete data): the
+  // k points S with a NaN, d per latent, and per latent the factor of M = D B D + F in the layout Dims(k, 2) with its inverse diagonal
+  // blocks.  alpha is then alpha-hat (DESIGN.md 4.22 "Posterior handle for gappy grids").
+  struct Gap {
+    int k = 0, last = 0, NC = 0, ld = 0;        // last: the largest point of S
+    Buf<int> idx;
+    Buf<double> d;                    // [latent][k]
+    std::vector<Buf<double>> L, W;
+  } gap;
 };
+static int toep_refuse_gap(const char* what) {
+  return fail(LMM_ERR_UNSUPPORTED, "%s is not served on a Toeplitz posterior with gap state (NaN in y; lmm_oilmm_toeplitz_posterior_create_missing): "
+                                   "mean_and_var is", what);
+}
 
 static const size_t kToepPredictScratch = size_t(1) << 23;      // doubles of partials a query chunk may take (64 MB)
 
@@ -5913,6 +5926,34 @@ static int toep_check_finite(const double* xsd, int ns) {
 }
 static int toep_refuse_f32() { return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path is Float64 only (lmm_set_compute_dtype(LMM_F64))"); }
 
+// The handle of a factored shard: the generators move out of W, alpha = T^-1 r from the right-hand sides r ([latent][n], device), the
+// grid from the ends of x on the device, the mixing.  A throw (a failed allocation) frees what the handle holds.
+static std::unique_ptr<lmm_toep_post> toep_post_fill(const ToepTrain& T, ToepWork& W, const double* r, int n, int p, const double* U,
+                                                     const double* S, int m, double sigma2) {
+  hipStream_t st0 = g.streams[0];
+  std::unique_ptr<lmm_toep_post> P(new lmm_toep_post());
+  P->n = n; P->p = p; P->m = m; P->l0 = T.l0; P->l1 = T.l1; P->sigma2 = sigma2; P->ls = T.ls;
+  double ends[2] = {0.0, 0.0};
+  HIPCHK(hipMemcpyAsync(&ends[0], T.xd.p, sizeof(double), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipMemcpyAsync(&ends[1], T.xd.p + (n - 1), sizeof(double), hipMemcpyDeviceToHost, st0));
+  P->alpha = Buf<double>((size_t)n * T.mk);
+  {
+    Buf<double> u(2 * (size_t)n * T.mk);
+    launch_toep_solve(W.p.p, W.q.p, r, n, T.ms, u.p, P->alpha.p, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));
+  }
+  P->x0 = ends[0]; P->h = n > 1 ? (ends[1] - ends[0]) / (double)(n - 1) : 0.0;
+  P->pg = std::move(W.p); P->qg = std::move(W.q);
+  for (int k = 0; k < T.ms; ++k) P->w.push_back(sigma2 / S[T.l0 + k]);
+  P->U.assign(U, U + (size_t)p * m); P->S.assign(S, S + m);
+  const std::vector<double> Hs = shard_H(U, S, p, T.l0, T.ms);
+  P->H = Buf<double>(std::max<size_t>(Hs.size(), 1));
+  HIPCHK(hipMemcpyAsync(P->H.p, Hs.data(), Hs.size() * sizeof(double), hipMemcpyHostToDevice, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  return P;
+}
+
 static int toep_posterior_create(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
                                  const lmm_gp_t* gps, int latent_begin, int latent_end, lmm_toep_post_t** out, double* out_logpdf,
                                  bool blocked) {
@@ -5925,30 +5966,10 @@ static int toep_posterior_create(const double* x, int n, const double* y, int p,
   if (int rc = toep_train(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, false, blocked, T)) return rc;
   ToepWork W;
   if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, T.ms, T.F.nv.p, T.F.z.p, blocked, W)) return rc;
-  hipStream_t st0 = g.streams[0];
   double total = 0.0;                       // the sum of lmm_oilmm_logpdf_toeplitz, in its order
   for (int k = 0; k < T.ms; ++k) total += W.lml[k];
   total += T.F.reg(n, m, sigma2);
-  std::unique_ptr<lmm_toep_post> P(new lmm_toep_post());      // a throw below (a failed allocation) frees what it holds
-  P->n = n; P->p = p; P->m = m; P->l0 = T.l0; P->l1 = T.l1; P->sigma2 = sigma2; P->ls = T.ls;
-  double ends[2] = {0.0, 0.0};
-  HIPCHK(hipMemcpyAsync(&ends[0], T.xd.p, sizeof(double), hipMemcpyDeviceToHost, st0));
-  HIPCHK(hipMemcpyAsync(&ends[1], T.xd.p + (n - 1), sizeof(double), hipMemcpyDeviceToHost, st0));
-  P->alpha = Buf<double>((size_t)n * T.mk);
-  {
-    Buf<double> u(2 * (size_t)n * T.mk);
-    launch_toep_solve(W.p.p, W.q.p, T.F.z.p, n, T.ms, u.p, P->alpha.p, st0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st0));
-  }
-  P->x0 = ends[0]; P->h = n > 1 ? (ends[1] - ends[0]) / (double)(n - 1) : 0.0;
-  P->pg = std::move(W.p); P->qg = std::move(W.q);
-  for (int k = 0; k < T.ms; ++k) P->w.push_back(sigma2 / S[T.l0 + k]);
-  P->U.assign(U, U + (size_t)p * m); P->S.assign(S, S + m);
-  const std::vector<double> Hs = shard_H(U, S, p, T.l0, T.ms);
-  P->H = Buf<double>(std::max<size_t>(Hs.size(), 1));
-  HIPCHK(hipMemcpyAsync(P->H.p, Hs.data(), Hs.size() * sizeof(double), hipMemcpyHostToDevice, st0));
-  HIPCHK(hipStreamSynchronize(st0));
+  std::unique_ptr<lmm_toep_post> P = toep_post_fill(T, W, T.F.z.p, n, p, U, S, m, sigma2);
   if (out_logpdf) *out_logpdf = total;
   *out = P.release();
   return LMM_OK;
@@ -5974,6 +5995,9 @@ int lmm_toeplitz_post_destroy(lmm_toep_post_t* post) {
   return LMM_OK;
 }
 
+// toep_predict_latents for a handle with gap state, plus the variance's correction (defined with the missing-data entry points below)
+static int toep_gap_latents(const lmm_toep_post* P, const double* xsd, int ns, double* ml, double* vl);
+
 int lmm_oilmm_toeplitz_post_mean_and_var(const lmm_toep_post_t* post, const double* xs, int ns, int add_noise, double* mean_out,
                                          double* var_out) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -5987,8 +6011,10 @@ int lmm_oilmm_toeplitz_post_mean_and_var(const lmm_toep_post_t* post, const doub
   DevIn xsd(xs, (size_t)ns, st0);
   if (int rc = toep_check_finite(xsd.p, ns)) return rc;
   Buf<double> ml((size_t)ns * std::max(ms, 1)), vl((size_t)ns * std::max(ms, 1));
-  if (int rc = toep_predict_latents(P->x0, P->h, P->n, P->ls->lat.data() + P->l0, ms, P->pg.p, P->qg.p, P->alpha.p, xsd.p, ns, true,
-                                    ml.p, var_out ? vl.p : nullptr)) return rc;
+  if (var_out && P->gap.k > 0 && ms > 0) {
+    if (int rc = toep_gap_latents(P, xsd.p, ns, ml.p, vl.p)) return rc;
+  } else if (int rc = toep_predict_latents(P->x0, P->h, P->n, P->ls->lat.data() + P->l0, ms, P->pg.p, P->qg.p, P->alpha.p, xsd.p, ns, true,
+                                           ml.p, var_out ? vl.p : nullptr)) return rc;
   DevOut mo(mean_out, (size_t)ns * p), vo(var_out, (size_t)ns * p);
   mix_marginals(ml.p, ns, ms, P->H.p, p, 1, 0.0, 0.0, mo.p, st0);
   if (var_out) mix_marginals(vl.p, ns, ms, P->H.p, p, 2, kDefaultJit.default_jitter, add_noise ? P->sigma2 : 0.0, vo.p, st0);
@@ -6055,6 +6081,7 @@ int lmm_oilmm_toeplitz_post_mean_and_var_grad_xs(const lmm_toep_post_t* post, co
   if (!dmean && !dvar) return fail(LMM_ERR_ARG, "Toeplitz posterior: dmean and dvar are both NULL (one cotangent is needed)");
   if (g_f32) return toep_refuse_f32();
   const lmm_toep_post* P = post;
+  if (P->gap.k > 0) return toep_refuse_gap("the gradient with respect to the queries");
   const int p = P->p, ms = P->l1 - P->l0;
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)ns, st0);
@@ -6118,15 +6145,15 @@ struct ToepJointClock {
     marks.emplace_back(e, stage);
     HIPCHK(hipEventRecord(e, st));
   }
-  void read(double* dst = g_toep_joint_ms) {
-    double ms[3] = {0.0, 0.0, 0.0};
+  void read(double* dst = g_toep_joint_ms, int stages = 3) {      // stages <= 4
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};
     for (size_t i = 0; i + 1 < marks.size(); ++i)
       if (marks[i].second >= 0) {
         float part = 0.0f;
         HIPCHK(hipEventElapsedTime(&part, marks[i].first, marks[i + 1].first));
         ms[marks[i].second] += part;
       }
-    std::copy(ms, ms + 3, dst);
+    std::copy(ms, ms + stages, dst);
   }
   ~ToepJointClock() { for (auto& mk : marks) g.ev_pool.push_back(mk.first); }
 };
@@ -6206,6 +6233,7 @@ int lmm_oilmm_toeplitz_post_logpdf(const lmm_toep_post_t* post, const double* xs
   if (g_f32) return toep_refuse_f32();
   if (int rc = toep_joint_check_ns(ns)) return rc;
   const lmm_toep_post* P = post;
+  if (P->gap.k > 0) return toep_refuse_gap("the joint predictive logpdf");
   if (!(sigma2 < 0.0) && (!std::isfinite(sigma2) || !(sigma2 > 0.0)))
     return fail(LMM_ERR_ARG, "Toeplitz posterior: sigma2 must be finite and > 0, or < 0 for the handle's own (sigma2 = %g)", sigma2);
   const double s2 = sigma2 < 0.0 ? P->sigma2 : sigma2;
@@ -6261,6 +6289,7 @@ int lmm_oilmm_toeplitz_post_rand_at(const lmm_toep_post_t* post, const double* x
   if (int rc = toep_rand_args(P->n, 0, jitter, add_noise, nsamples, z, eps, out)) return rc;
   if (g_f32) return toep_refuse_f32();
   if (int rc = toep_joint_check_ns(ns)) return rc;
+  if (P->gap.k > 0) return toep_refuse_gap("sampling at new inputs");
   const int p = P->p, ms = P->l1 - P->l0, mk = std::max(ms, 1);
   hipStream_t st0 = g.streams[0];
   DevIn xsd(xs, (size_t)ns, st0), zd(z, (size_t)ns * ms * nsamples, st0), epsd(add_noise ? eps : nullptr, (size_t)ns * p * nsamples, st0);
@@ -6350,17 +6379,32 @@ int lmm_toeplitz_missing_last_ms(double* recursion_ms, double* block_ms, double*
   return LMM_OK;
 }
 
-int lmm_oilmm_logpdf_toeplitz_missing(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
-                                      const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, int blocked, double* out) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  REQUIRE_INIT();
-  LMM_TRY
-  if (!out) return fail(LMM_ERR_ARG, "bad arguments");
+// What the value leaves behind for the handle: the front end, the recursion, S, d, alpha = T^-1 z and the factored M_l (keep: one
+// matrix per latent of the shard, which the handle takes over; else one per latent of a batch, reused from batch to batch).
+struct ToepMissing {
   ToepTrain T;
+  SSFront Fr;
+  ToepWork W;
+  std::vector<int> sidx;                // S: the points with a NaN, ascending
+  Buf<int> idxd;
+  Buf<double> dv, al;
+  std::vector<Buf<double>> B, WB;
+  double total = 0.0;
+};
+// The body of lmm_oilmm_logpdf_toeplitz_missing, which lmm_oilmm_toeplitz_posterior_create_missing shares: refusals, front end, prep,
+// recursion, inverse block, finish, factorisation.  Caller holds g_mu.
+static int toep_missing_value(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                              const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, int blocked, bool keep,
+                              ToepMissing& Q) {
+  ToepTrain& T = Q.T;
+  SSFront& Fr = Q.Fr;
+  ToepWork& W = Q.W;
+  std::vector<int>& sidx = Q.sidx;
+  Buf<int>& idxd = Q.idxd;
+  Buf<double>& dv = Q.dv;
   if (int rc = toep_inputs(!y, x, n, p, U, S, m, sigma2, gps, latent_begin, latent_end, blocked != 0, -1, T)) return rc;
   hipStream_t st0 = g.streams[0];
   T.yd = DevIn(y, (size_t)n * p, st0);
-  std::vector<int> sidx;                // S: the points with a NaN, ascending
   {
     Buf<unsigned long long> masks((size_t)n * ((p + 63) / 64));
     Buf<int> pt(n);
@@ -6372,15 +6416,16 @@ int lmm_oilmm_logpdf_toeplitz_missing(const double* x, int n, const double* y, i
       if (hpt[t] != p) sidx.push_back(t);
   }
   const int k = (int)sidx.size(), ms = T.ms, mk = T.mk;
-  SSFront Fr;                           // w = +Inf and r = 0 at the points without data, which stay in the grid
+  // Fr: w = +Inf and r = 0 at the points without data, which stay in the grid
   if (int rc = ss_front(T.yd.p, n, p, U, S, m, sigma2, T.lts, T.l0, T.l1, Fr)) return rc;
   if (Fr.nobs == 0) return fail(LMM_ERR_ARG, "missing data: no point has an observed output");
   if (k > TOEP_MISSING_MAX_K)
     return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves k <= %d points with a NaN in y (lmm_toeplitz_missing_max_k; k = %d)",
                 TOEP_MISSING_MAX_K, k);
   const bool corr = k > 0 && ms > 0;
-  Buf<int> idxd(std::max(k, 1));
-  Buf<double> dv((size_t)std::max(k, 1) * mk), fv((size_t)std::max(k, 1) * mk);
+  idxd = Buf<int>(std::max(k, 1));
+  dv = Buf<double>((size_t)std::max(k, 1) * mk);
+  Buf<double> fv((size_t)std::max(k, 1) * mk);
   if (corr) {
     HIPCHK(hipMemcpyAsync(idxd.p, sidx.data(), (size_t)k * sizeof(int), hipMemcpyHostToDevice, st0));
     std::vector<double> w0(ms);
@@ -6392,26 +6437,29 @@ int lmm_oilmm_logpdf_toeplitz_missing(const double* x, int n, const double* y, i
   }
   ToepJointClock ck;
   ck.mark(0, st0);
-  ToepWork W;
   if (int rc = toep_factor(T.xd.p, n, T.lts, T.l0, ms, Fr.w.p, Fr.r.p, blocked != 0, W)) return rc;
   ck.mark(-1, st0);
   const double L2PI = std::log(2.0 * M_PI);
   double total = 0.0;
   for (int j = 0; j < ms; ++j) total += W.lml[j];
   if (corr) {
-    Buf<double> al((size_t)n * mk), u(2 * (size_t)n * mk), outd(2 * (size_t)mk);
+    Buf<double>& al = Q.al;
+    al = Buf<double>((size_t)n * mk);
+    Buf<double> u(2 * (size_t)n * mk), outd(2 * (size_t)mk);
     std::vector<double> ho(2 * (size_t)mk, 0.0);
     launch_toep_solve(W.p.p, W.q.p, Fr.r.p, n, ms, u.p, al.p, st0);
     const Dims Ds(k, 2);
     FanOut F = FanOut::one_slot(ms);
     int* info = F.alloc_info();
-    std::vector<Buf<double>> B, WB;
-    for (int j = 0; j < F.nb_per; ++j) { B.emplace_back(Ds.elems()); WB.emplace_back((size_t)(Ds.NC / 64) * 4096); }
+    std::vector<Buf<double>>& B = Q.B;
+    std::vector<Buf<double>>& WB = Q.WB;
+    for (int j = 0; j < (keep ? ms : F.nb_per); ++j) { B.emplace_back(Ds.elems()); WB.emplace_back((size_t)(Ds.NC / 64) * 4096); }
     F.run([&](const FanBatch& b) {
       Batch Bt;
       for (int j = 0; j < b.nb; ++j) {
-        Bt.add(B[j].p, WB[j].p, info + b.k0 + j);
-        guard_extent(B[j].p, Ds.NC, Ds.ld, Ds.NC, false, "Toeplitz missing data (inverse block tiles)");
+        const int jb = keep ? b.k0 + j : j;
+        Bt.add(B[jb].p, WB[jb].p, info + b.k0 + j);
+        guard_extent(B[jb].p, Ds.NC, Ds.ld, Ds.NC, false, "Toeplitz missing data (inverse block tiles)");
       }
       ck.mark(1, b.st);
       launch_toep_inverse_block(W.p.p + (size_t)b.k0 * n, W.q.p + (size_t)b.k0 * n, n, idxd.p, k, Bt.A, Ds.ld, b.nb, true, b.st);
@@ -6432,9 +6480,156 @@ int lmm_oilmm_logpdf_toeplitz_missing(const double* x, int n, const double* y, i
   if (with_regulariser) total += Fr.reg;
   HIPCHK(hipStreamSynchronize(st0));
   ck.read(g_toep_missing_ms);
-  *out = total;
+  Q.total = total;
+  return LMM_OK;
+}
+
+int lmm_oilmm_logpdf_toeplitz_missing(const double* x, int n, const double* y, int p, const double* U, const double* S, int m, double sigma2,
+                                      const lmm_gp_t* gps, int latent_begin, int latent_end, int with_regulariser, int blocked, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!out) return fail(LMM_ERR_ARG, "bad arguments");
+  ToepMissing Q;
+  if (int rc = toep_missing_value(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, with_regulariser, blocked, false, Q)) return rc;
+  *out = Q.total;
   return LMM_OK;
   LMM_CATCH
+}
+
+// ---- the posterior handle for gappy grids (DESIGN.md 4.22 "Posterior handle for gappy grids") --------------------------------------
+// J_O C^-1 J_O' = T^-1 - T^-1[:, S] D M^-1 D T^-1[S, :] gives the mean as k*' alpha-hat, alpha-hat = alpha - T^-1 J_S (d o M^-1 a), and
+// the variance as that of complete data plus |L_M^-1 (d o V[:, *])|^2, V = (T^-1 K*)[S, :] (toep_inverse_rows_kernel).
+int lmm_oilmm_toeplitz_posterior_create_missing(const double* x, int n, const double* y, int p, const double* U, const double* S, int m,
+                                                double sigma2, const lmm_gp_t* gps, int latent_begin, int latent_end,
+                                                lmm_toep_post_t** out, double* out_logpdf, int blocked) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!out) return fail(LMM_ERR_ARG, "bad arguments");
+  *out = nullptr;
+  ToepMissing Q;
+  if (int rc = toep_missing_value(x, n, y, p, U, S, m, sigma2, gps, latent_begin, latent_end, 1, blocked, true, Q)) return rc;
+  std::unique_ptr<lmm_toep_post> P = toep_post_fill(Q.T, Q.W, Q.Fr.r.p, n, p, U, S, m, sigma2);
+  const int k = (int)Q.sidx.size(), ms = Q.T.ms;
+  if (k > 0 && ms > 0) {
+    hipStream_t st0 = g.streams[0];
+    const Dims Ds(k, 2);
+    lmm_toep_post::Gap& G = P->gap;
+    G.k = k; G.last = Q.sidx.back(); G.NC = Ds.NC; G.ld = Ds.ld;
+    G.idx = std::move(Q.idxd); G.d = std::move(Q.dv); G.L = std::move(Q.B); G.W = std::move(Q.WB);
+    // alpha-hat: M^-1 a from the rider row L_M^-1 a and a back substitution, scattered to the grid with d, one more solve
+    Buf<double> gv((size_t)Ds.NC * ms), g2((size_t)Ds.NC * ms), rhs((size_t)n * ms), u(2 * (size_t)n * ms), back((size_t)n * ms);
+    for (int k0 = 0; k0 < ms; k0 += LMM_MAX_BATCH) {
+      const int nl = std::min(LMM_MAX_BATCH, ms - k0);
+      BatchPtr Ab{}, Wb{}, gb{}, hb{};
+      for (int j = 0; j < nl; ++j) {
+        Ab.p[j] = G.L[k0 + j].p; Wb.p[j] = G.W[k0 + j].p;
+        gb.p[j] = gv.p + (size_t)(k0 + j) * Ds.NC; hb.p[j] = g2.p + (size_t)(k0 + j) * Ds.NC;
+        launch_fill(rhs.p + (size_t)(k0 + j) * n, n, 0.0, st0);
+      }
+      launch_extract_rows(Ab, nl, Ds.ld, Ds.NC, k, Ds.NC, gb, hb, st0);
+      launch_backsolve(Ab, Ds.ld, Wb, Ds.NC / 64, gb, nl, st0);
+      launch_toep_gap_scatter(gb, G.d.p + (size_t)k0 * k, G.idx.p, k, n, nl, rhs.p + (size_t)k0 * n, st0);
+    }
+    launch_toep_solve(P->pg.p, P->qg.p, rhs.p, n, ms, u.p, back.p, st0);
+    for (int j = 0; j < ms; ++j)
+      launch_vec_lin(P->alpha.p + (size_t)j * n, back.p + (size_t)j * n, -1.0, n, P->alpha.p + (size_t)j * n, st0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st0));
+  }
+  if (out_logpdf) *out_logpdf = Q.total;
+  *out = P.release();
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_toeplitz_post_gap_k(const lmm_toep_post_t* post, int* k) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!post || !k) return fail(LMM_ERR_ARG, "bad arguments");
+  *k = post->gap.k;
+  return LMM_OK;
+}
+
+// The correction's scratch: the rider rows of a pass (latents of the pass x rup(k, 128) x queries of a chunk doubles)
+static const size_t kToepGapBudget = size_t(1) << 30;
+static double g_toep_gap_ms[4] = {0.0, 0.0, 0.0, 0.0};     // predict, storing GEMM, inverse rows, solve + sums: of the last query on a gappy handle
+int lmm_toeplitz_missing_post_last_ms(double* predict_ms, double* gemm_ms, double* rows_ms, double* solve_ms) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (predict_ms) *predict_ms = g_toep_gap_ms[0];
+  if (gemm_ms) *gemm_ms = g_toep_gap_ms[1];
+  if (rows_ms) *rows_ms = g_toep_gap_ms[2];
+  if (solve_ms) *solve_ms = g_toep_gap_ms[3];
+  return LMM_OK;
+}
+
+// V (+ scaling) of nb <= pl.lat latents at the ns queries xsd into V.p[l] (leading dimension ld): the storing GEMM and then the
+// inverse-rows kernel per chunk of pl.rows rows, up to the row block of S's largest point `last` (beyond it every window is zero).
+// U: pl.lat 2 pl.rows toep_joint_nsp(ns) doubles of scratch.
+static void toep_gap_rows(double x0, double h, int n, const LatentDev* dd, int nb, const double* pg, const double* qg, const int* idx, int k,
+                          int last, const double* xsd, int ns, int mode, const ToepJointPlan& pl, double* U, const double* d,
+                          const BatchPtr& V, int ld, bool whole, ToepJointClock& ck, hipStream_t st) {
+  const int top = rup(std::min(n, last + 1), TOEP_PRED_R);
+  for (int row0 = 0; row0 < top; row0 += pl.rows) {
+    const int rows = std::min(pl.rows, top - row0);
+    ck.mark(1, st);
+    launch_toep_predict_store(x0, h, n, dd, pg, qg, xsd, ns, nb, mode, row0, rows, U, st);
+    ck.mark(2, st);
+    launch_toep_inverse_rows(pg, qg, n, idx, k, U, row0, rows, ns, d, V, ld, nb, row0 == 0, row0 + rows >= top, whole, st);
+  }
+  ck.mark(-1, st);
+  HIPCHK(hipGetLastError());
+}
+
+static int toep_gap_latents(const lmm_toep_post* P, const double* xsd, int ns, double* ml, double* vl) {
+  const lmm_toep_post::Gap& G = P->gap;
+  const int ms = P->l1 - P->l0, n = P->n, k = G.k;
+  hipStream_t st0 = g.streams[0];
+  const Latent* lts = P->ls->lat.data() + P->l0;
+  ToepJointClock ck;
+  ck.mark(0, st0);
+  if (int rc = toep_predict_latents(P->x0, P->h, n, lts, ms, P->pg.p, P->qg.p, P->alpha.p, xsd, ns, true, ml, vl)) return rc;
+  ck.mark(-1, st0);
+  std::vector<LatentDev> hd(ms);
+  for (int j = 0; j < ms; ++j) hd[j] = lts[j].dev();
+  Buf<LatentDev> dd(ms);
+  HIPCHK(hipMemcpyAsync(dd.p, hd.data(), (size_t)ms * sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  const int mode = sum_mode(lts, 0, ms);
+  // queries of a chunk: whole tiles, the rider rows of a pass's latents within the budget
+  const size_t per_tile = (size_t)std::min(ms, LMM_MAX_BATCH) * G.NC * TOEP_JOINT_T * sizeof(double);
+  const int chunk = (int)std::min<size_t>((size_t)rup(ns, TOEP_JOINT_T), std::max<size_t>(1, kToepGapBudget / per_tile) * TOEP_JOINT_T);
+  const ToepJointPlan pl = toep_joint_plan(n, std::min(chunk, ns), ms);
+  double* U = call_scratch((size_t)pl.lat * 2 * pl.rows * toep_joint_nsp(std::min(chunk, ns)));
+  const int ldr = pad_ld(chunk);
+  std::vector<Buf<double>> R;
+  for (int j = 0; j < pl.lat; ++j) R.emplace_back((size_t)ldr * G.NC);
+  Buf<double> zero((size_t)G.NC), neg((size_t)chunk), part(strip_partial_elems(chunk, G.NC, 2));
+  launch_fill(zero.p, G.NC, 0.0, st0);
+  for (int c0 = 0; c0 < ns; c0 += chunk) {
+    const int nsc = std::min(chunk, ns - c0);
+    for (int k0 = 0; k0 < ms; k0 += pl.lat) {
+      const int nl = std::min(pl.lat, ms - k0);
+      BatchPtr Rb{}, Lb{}, Wb{};
+      for (int j = 0; j < nl; ++j) {
+        Rb.p[j] = R[j].p; Lb.p[j] = G.L[k0 + j].p; Wb.p[j] = G.W[k0 + j].p;
+        guard_extent(R[j].p, rup(nsc, TOEP_JOINT_T), ldr, G.NC, false, "Toeplitz gap correction (rider rows)");
+      }
+      toep_gap_rows(P->x0, P->h, n, dd.p + k0, nl, P->pg.p + (size_t)k0 * n, P->qg.p + (size_t)k0 * n, G.idx.p, k, G.last, xsd + c0, nsc, mode,
+                    pl, U, G.d.p + (size_t)k0 * k, Rb, ldr, true, ck, st0);
+      ck.mark(3, st0);
+      trsm_rec(Rb, ldr, rup(nsc, 64), Lb, G.ld, Wb, nl, 0, G.NC, st0, false, true, true);      // rows (L_M^-1 (d o V[:, c]))'
+      for (int j = 0; j < nl; ++j) {
+        double* v = vl + (size_t)(k0 + j) * ns + c0;
+        rider_stats_g(R[j].p, ldr, nsc, G.NC, zero.p, 0.0, 0.0, part.p, nullptr, neg.p, st0);  // neg = -|row|^2
+        launch_vec_lin(v, neg.p, -1.0, nsc, v, st0);
+      }
+      ck.mark(-1, st0);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  ck.read(g_toep_gap_ms, 4);
+  return LMM_OK;
 }
 
 int lmm_dev_toeplitz_inverse_block(const double* p, const double* q, int n, const int* idx, int k, double* B, int ldb) {
@@ -6458,6 +6653,45 @@ int lmm_dev_toeplitz_inverse_block(const double* p, const double* q, int n, cons
   Bb.p[0] = B;
   launch_toep_inverse_block(p, q, n, idx, k, Bb, ldb, 1, false, st0);
   HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st0));
+  return LMM_OK;
+  LMM_CATCH
+}
+
+int lmm_dev_toeplitz_inverse_rows(double x0, double h, int n, const lmm_gp_t* gp, const double* p, const double* q, const int* idx, int k,
+                                  const double* xs, int ns, int rows_forced, double* V, int ldv) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  REQUIRE_INIT();
+  LMM_TRY
+  if (!gp || !p || !q || !idx || !xs || !V || n <= 0 || k <= 0 || ns <= 0 || ldv < ns || !std::isfinite(x0) || !std::isfinite(h) ||
+      rows_forced < 0 || rows_forced % TOEP_PRED_R)
+    return fail(LMM_ERR_ARG, "bad arguments");
+  if (g_f32) return toep_refuse_f32();
+  if (int rc = toep_check_n(n, true)) return rc;
+  if (int rc = toep_joint_check_ns(ns)) return rc;
+  if (k > TOEP_MISSING_MAX_K)
+    return fail(LMM_ERR_UNSUPPORTED, "the Toeplitz path serves k <= %d points with a NaN in y (lmm_toeplitz_missing_max_k; k = %d)",
+                TOEP_MISSING_MAX_K, k);
+  std::shared_ptr<LatentSet> ls;
+  if (int rc = resolve(gp, 1, 1, ls)) return rc;
+  if (int rc = toep_check_finite(xs, ns)) return rc;
+  hipStream_t st0 = g.streams[0];
+  std::vector<int> hi(k);
+  HIPCHK(hipMemcpyAsync(hi.data(), idx, (size_t)k * sizeof(int), hipMemcpyDeviceToHost, st0));
+  HIPCHK(hipStreamSynchronize(st0));
+  for (int i = 0; i < k; ++i)
+    if (hi[i] < 0 || hi[i] >= n || (i > 0 && hi[i] <= hi[i - 1]))
+      return fail(LMM_ERR_ARG, "idx must be ascending and distinct in [0, n): idx[%d] = %d", i, hi[i]);
+  const Latent* lts = ls->lat.data();
+  const LatentDev hd = lts[0].dev();
+  Buf<LatentDev> dd(1);
+  HIPCHK(hipMemcpyAsync(dd.p, &hd, sizeof(LatentDev), hipMemcpyHostToDevice, st0));
+  const ToepJointPlan pl = toep_joint_plan(n, ns, 1, rows_forced);
+  double* U = call_scratch((size_t)pl.lat * 2 * pl.rows * toep_joint_nsp(ns));
+  BatchPtr Vb{};
+  Vb.p[0] = V;
+  ToepJointClock ck;
+  toep_gap_rows(x0, h, n, dd.p, 1, p, q, idx, k, hi[k - 1], xs, ns, sum_mode(lts, 0, 1), pl, U, nullptr, Vb, ldv, false, ck, st0);
   HIPCHK(hipStreamSynchronize(st0));
   return LMM_OK;
   LMM_CATCH
@@ -7387,6 +7621,7 @@ int lmm_oilmm_toeplitz_post_rand(const lmm_toep_post_t* post, int horizon, doubl
   if (int rc = toep_rand_args(P->n, horizon, jitter, add_noise, nsamples, z, eps, out)) return rc;
   if (g_f32) return toep_refuse_f32();
   if (int rc = toep_check_n(P->n, true, horizon)) return rc;
+  if (P->gap.k > 0) return toep_refuse_gap("sampling");
   const int ms = P->l1 - P->l0;
   return toep_rand(P->ls->lat.data() + P->l0, P->l0, ms, P->x0, P->h, P->n, horizon, jitter, P, P->p, P->H.p, P->sigma2, add_noise, nsamples,
                    z, (size_t)ms * (P->n + horizon), 0, xi, eps, out);

@@ -6852,6 +6852,120 @@ __global__ __launch_bounds__(256) void toep_inverse_block_kernel(const double* _
       }
 }
 
+// Rows of T^-1 K* (DESIGN.md 4.22 "Posterior handle for gappy grids"): with Uq = L(q)' K* and Up = L(p)' K* as the storing GEMM leaves
+// them,
+//     V[i][j] = (T^-1 K*)[s_i, j] = sum_c q[s_i - c] Uq[c][j] - p[s_i - c] Up[c][j],
+// a GEMM over c whose A operand is toep_inverse_block_kernel's (windows of the generators read backwards, gathered k-major into LDS at
+// stride TG_S, rows from k on with index -1: zeros that cause no load) and whose B operand is a TIR_K-row x 128-query panel of U, which
+// is contiguous along the queries: thread (column = t & 127, rows t >> 7 + 2 e) stages it through LDS at the same stride, so both
+// fragments are 16 consecutive doubles of one panel row.  Workgroup (point tile, query tile, latent) owns its 128 x 128 tile of V and
+// no other workgroup touches it; 4 waves in 2 x 2, each a 64 x 64 quarter as 4 x 4 accumulators.  c ascends in chunks of TIR_K over the
+// launch's rows [row0, row0 + live): the q panel, then the p panel with the A operand negated, through the same accumulators; the next
+// panel's loads of both operands are in flight in registers while this one is multiplied.  A chunk wholly beyond the tile's largest
+// s_i is not walked (every window is zero there).  The sum is carried from launch to launch through the output (first: it starts here
+// and the output is not read), so an element is one chain over c whatever the chunking, without atomics; the last launch scales row i
+// by d[i] (nullptr: 1).  Element (i, j) goes to out.p[l][i ld + j] -- the query runs along the memory, as the rider rows of trsm_rec
+// want it (one row per query, one column per point of S) and as D column l15 of an accumulator gives it: 16 lanes store 16 consecutive
+// doubles.  whole: the tile is read and written whole (zeros from k and from ns on); else only i < k, j < ns.
+constexpr int TIR_K = 16;
+static_assert(TIR_K == TIB_K && TOEP_PRED_R % TIR_K == 0, "toep_inverse_rows_kernel's thread maps");
+
+__global__ __launch_bounds__(256) void toep_inverse_rows_kernel(const double* __restrict__ p, const double* __restrict__ q, int n,
+                                                                const int* __restrict__ idx, int k, const double* __restrict__ U, int row0,
+                                                                int live, int rows, int nsp, int ns, const double* __restrict__ d,
+                                                                BatchPtr out, int ld, int first, int last, int whole) {
+  __shared__ double Pa[TIR_K * TG_S], Pb[TIR_K * TG_S];
+  __shared__ int si[TOEP_JOINT_T];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, l15 = lane & 15, lk = lane >> 4, wr = wv >> 1, wc = wv & 1;
+  const int i0 = blockIdx.x * TOEP_JOINT_T, j0 = blockIdx.y * TOEP_JOINT_T, l = blockIdx.z;
+  p += (size_t)l * n; q += (size_t)l * n;
+  const size_t gen = (size_t)rows * nsp;
+  U += (size_t)l * 2 * gen;
+  if (t < TOEP_JOINT_T) si[t] = i0 + t < k ? idx[i0 + t] : -1;
+  __syncthreads();
+  const int smax = si[min(TOEP_JOINT_T, k - i0) - 1];      // idx ascends: the tile's largest point
+  const int nch = (min(live, smax + 1 - row0) + TIR_K - 1) / TIR_K;      // <= 0: the launch's rows lie beyond every window of the tile
+  if (nch <= 0 && !first && !last) return;
+  const int row = t & (TOEP_JOINT_T - 1), half = t >> 7;   // A: the thread stages 8 consecutive lags of point `row`
+  const int cc = row, rr = half;                           // B: rows rr + 2 e of query column cc
+  const int srow = si[row];
+  const bool jlive = j0 + cc < nsp;
+  double* ot = out.p[l] + (size_t)(i0 + 64 * wc + lk) * ld + j0 + 64 * wr + l15;
+  const int ib = i0 + 64 * wc + lk, jb = j0 + 64 * wr + l15;
+  d4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool cell = whole || (ib + 16 * a + 4 * r < k && jb + 16 * b < ns);
+        acc[a][b][r] = (first || !cell) ? 0.0 : ot[(size_t)(16 * a + 4 * r) * ld + 16 * b];
+      }
+  double ra[8], rb[8];
+  auto fetch = [&](int ch, int gn) {
+    const double* __restrict__ src = gn ? p : q;
+    const int c = row0 + ch * TIR_K + 8 * half;
+    const double* __restrict__ us = U + gn * gen + ((size_t)ch * TIR_K + rr) * nsp + j0 + cc;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int ai = srow - c - e;                           // < n always; < 0: beyond the window's end
+      ra[e] = ai >= 0 ? src[ai] : 0.0;
+      rb[e] = jlive ? us[(size_t)2 * e * nsp] : 0.0;
+    }
+  };
+  int ch = 0, gn = 0;
+  bool more = nch > 0;
+  if (more) fetch(0, 0);
+  while (more) {
+    const bool neg = gn == 1;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      Pa[(8 * half + e) * TG_S + row] = ra[e];
+      Pb[(rr + 2 * e) * TG_S + cc] = rb[e];
+    }
+    __syncthreads();
+    if (++gn == 2) { gn = 0; ++ch; }
+    more = ch < nch;
+    if (more) fetch(ch, gn);
+#pragma unroll
+    for (int k4 = 0; k4 < TIR_K / 4; ++k4) {
+      const int ko = (4 * k4 + lk) * TG_S + l15;
+      double fa[4], fb[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const double v = Pa[ko + 64 * wc + 16 * a];
+        fa[a] = neg ? -v : v;
+        fb[a] = Pb[ko + 64 * wr + 16 * a];
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+    }
+  }
+  if (d) d += (size_t)l * k;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = ib + 16 * a + 4 * r;
+      const double sc = (last && d && i < k) ? d[i] : 1.0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (whole || (i < k && jb + 16 * b < ns)) ot[(size_t)(16 * a + 4 * r) * ld + 16 * b] = acc[a][b][r] * sc;
+    }
+}
+
+// rhs[l n + idx[i]] = d[l k + i] g.p[l][i] at the k points of S (the rest of rhs is the caller's zeros): the right-hand side of the
+// second solve of alpha-hat = alpha - T^-1 J_S (d o M^-1 a); thread (i < k, latent)
+__global__ __launch_bounds__(256) void toep_gap_scatter_kernel(BatchPtr g, const double* __restrict__ d, const int* __restrict__ idx, int k,
+                                                               int n, double* __restrict__ rhs) {
+  const int i = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y;
+  if (i < k) rhs[(size_t)l * n + idx[i]] = d[(size_t)l * k + i] * g.p[l][i];
+}
+
 // Where a point of S stands (toep_missing_finish_kernel): d = 1, f = 0 at a point without any observed output (its noise is +Inf),
 // else d = sqrt(max(w_t - w0, 0)), f = 1; thread (i < k, latent).  w: [latent][n], the front end's per-point noise; its element 0, which
 // launch_toep_row reads, becomes the complete-data noise w0[l] (thread 0 alone reads and then writes it: idx is ascending).
@@ -7002,6 +7116,17 @@ void launch_toep_inverse_block(const double* p, const double* q, int n, const in
   if (nb <= 0 || k <= 0) return;
   const int nt = (k + TOEP_JOINT_T - 1) / TOEP_JOINT_T;
   hipLaunchKernelGGL(toep_inverse_block_kernel, dim3(nt * (nt + 1) / 2, nb), dim3(256), 0, st, p, q, n, idx, k, B, ld, whole ? 1 : 0);
+}
+void launch_toep_inverse_rows(const double* p, const double* q, int n, const int* idx, int k, const double* U, int row0, int rows, int ns,
+                              const double* d, const BatchPtr& V, int ld, int nb, bool first, bool last, bool whole, hipStream_t st) {
+  if (nb <= 0 || k <= 0 || ns <= 0 || rows <= 0) return;
+  const int nti = (k + TOEP_JOINT_T - 1) / TOEP_JOINT_T, ntj = (ns + TOEP_JOINT_T - 1) / TOEP_JOINT_T;
+  hipLaunchKernelGGL(toep_inverse_rows_kernel, dim3(nti, ntj, nb), dim3(256), 0, st, p, q, n, idx, k, U, row0,
+                     std::max(0, std::min(rows, n - row0)), rows, toep_joint_nsp(ns), ns, d, V, ld, first ? 1 : 0, last ? 1 : 0, whole ? 1 : 0);
+}
+void launch_toep_gap_scatter(const BatchPtr& g, const double* d, const int* idx, int k, int n, int nb, double* rhs, hipStream_t st) {
+  if (nb <= 0 || k <= 0) return;
+  hipLaunchKernelGGL(toep_gap_scatter_kernel, dim3((k + 255) / 256, nb), dim3(256), 0, st, g, d, idx, k, n, rhs);
 }
 void launch_toep_missing_prep(double* w, int n, const int* idx, int k, const double* w0, int nb, double* d, double* f, hipStream_t st) {
   if (nb <= 0 || k <= 0) return;

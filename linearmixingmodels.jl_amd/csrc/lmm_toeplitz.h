@@ -120,6 +120,16 @@ void launch_toep_cov_finish(const LatentDev* lat, const double* xs, int ns, cons
 // are written whole (i, j < rup(k, TOEP_JOINT_T); zeros from k on); else the lower triangle i >= j, i < k and nothing else.
 void launch_toep_inverse_block(const double* p, const double* q, int n, const int* idx, int k, const BatchPtr& B, int ld, int nb, bool whole,
                                hipStream_t st);
+// Rows of T_l^-1 K* (DESIGN.md 4.22 "Posterior handle for gappy grids"): V_l[i][j] (+)= sum over the rows c of [row0, row0 + rows) of
+// q[idx[i] - c] Uq[c][j] - p[idx[i] - c] Up[c][j], with U as launch_toep_predict_store left it for that chunk of rows and the ns
+// queries; element (i, j) at V.p[l][i ld + j] (the query runs along the memory: one row per query, one column per point, as the rider
+// rows of a triangular solve).  first: the sum starts here (V is not read); it is carried through V from chunk to chunk, so V does not
+// depend on how the rows are chunked.  last: row i is scaled by d[l k + i] (d == nullptr: by 1).  whole: the TOEP_JOINT_T tiles are
+// written whole (i < rup(k, TOEP_JOINT_T), j < rup(ns, TOEP_JOINT_T); zeros from k and from ns on); else i < k, j < ns and nothing else.
+void launch_toep_inverse_rows(const double* p, const double* q, int n, const int* idx, int k, const double* U, int row0, int rows, int ns,
+                              const double* d, const BatchPtr& V, int ld, int nb, bool first, bool last, bool whole, hipStream_t st);
+// rhs[l n + idx[i]] = d[l k + i] g.p[l][i], i < k (the other elements of rhs are not written)
+void launch_toep_gap_scatter(const BatchPtr& g, const double* d, const int* idx, int k, int n, int nb, double* rhs, hipStream_t st);
 // d, f [l k ..] of the points idx from the per-point noise w ([latent][n]; +Inf: no observed output) and the complete-data noise w0[l];
 // w[l n] becomes w0[l], which launch_toep_row then reads
 void launch_toep_missing_prep(double* w, int n, const int* idx, int k, const double* w0, int nb, double* d, double* f, hipStream_t st);

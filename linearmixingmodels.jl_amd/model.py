@@ -1470,7 +1470,8 @@ def toeplitz_logpdf_missing(fx: "FiniteGP", y, blocked: bool = False, *, with_re
     With the k points that have a NaN the covariance is Toeplitz plus a correction on those points, and the k x k block of the
     inverse that the exact value needs comes from the recursion's generators: O(n^2 + k^2 n + k^3) time, O(n + k^2) memory per latent,
     k <= lmm_toeplitz_missing_max_k.  Without NaN the value is bitwise toeplitz_logpdf's.  x and y: NumPy arrays or torch device
-    tensors; blocked: as toeplitz_logpdf's.  Gradients and a posterior handle for such data are not served yet."""
+    tensors; blocked: as toeplitz_logpdf's.  The posterior handle for such data is toeplitz_posterior_missing; gradients are not
+    served yet."""
     y = _toeplitz_args(fx, y, "toeplitz_logpdf_missing")
     f, x = fx.f, fx.x
     L.ensure_init()
@@ -1508,8 +1509,15 @@ class ToeplitzPosterior:
     on the fly, in O(n + ns) memory.  The error of var is relative to the prior variance, not to a small posterior variance.
     Built by toeplitz_posterior; freed by close(), on leaving a `with` block or with the object."""
 
-    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float, m: int = 0):
-        self._ptr, self.n, self.p, self.logpdf, self.m = ptr, n, p, logpdf, m
+    def __init__(self, ptr: C.c_void_p, n: int, p: int, logpdf: float, m: int = 0, k: int = 0):
+        self._ptr, self.n, self.p, self.logpdf, self.m, self.k = ptr, n, p, logpdf, m, k
+
+    def _no_gap(self, what: str) -> None:
+        """k > 0 (toeplitz_posterior_missing on data with NaN): the handle holds alpha-hat and the factored M, which only
+        mean_and_var and its relatives read; the other verbs would answer from alpha-hat as if the data were complete."""
+        if self.k > 0:
+            raise NotImplementedError(f"{what} is not served on a Toeplitz posterior with gap state (k = {self.k} points with a NaN in y): "
+                                      "mean_and_var, mean, var and marginals are")
 
     def close(self) -> None:
         if self._ptr:
@@ -1528,6 +1536,7 @@ class ToeplitzPosterior:
         of an N-sample call is bitwise the one-sample call on the same normals; the samples share the factorisation but are not
         batched beyond it (two small launches per latent and sample).  At the default jitter a C that is not positive definite to
         rounding (queries closer than the data can resolve) is a PosDefException naming the latent: raise jitter."""
+        self._no_gap("ToeplitzPosterior.rand")
         if xs is not None:
             if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)) or horizon != 0:
                 raise ValueError("ToeplitzPosterior.rand: horizon must be 0 when xs is given")
@@ -1591,6 +1600,7 @@ class ToeplitzPosterior:
         ns <= lmm_toeplitz_joint_max_ns(); ys: (ns * p,) by outputs, complete (the library refuses a NaN and names its point);
         sigma2: the noise at the queries, None = the handle's own.  The handle is not changed.  Every refusal below comes before
         any library call that takes the handle (the cap on ns is read from the library)."""
+        self._no_gap("ToeplitzPosterior.predictive_logpdf")
         xs = self._queries(xs)
         ns = self._joint_ns("ToeplitzPosterior.predictive_logpdf", xs)
         if not hasattr(ys, "shape"):
@@ -1671,6 +1681,7 @@ class ToeplitzPosterior:
         on xs, so there is no add_noise argument and no "sigma2" entry.  A query's entry depends on no other query.  Every latent
         kind of the path is served; where a query coincides with a grid point that point contributes 0 (Matern12 and SHO have a
         kink there).  Every refusal below comes before any library call."""
+        self._no_gap("ToeplitzPosterior.mean_and_var_vjp")
         xs = self._queries(xs)
         ns = int(xs.shape[0])
         if dmean is None and dvar is None:
@@ -1711,6 +1722,30 @@ def toeplitz_posterior(fx: "FiniteGP", y, blocked: bool = False) -> ToeplitzPost
     L.check((lib.lmm_oilmm_toeplitz_posterior_create_blocked if blocked else lib.lmm_oilmm_toeplitz_posterior_create)(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2),
                                                          gps, 0, m, C.byref(ptr), C.byref(out)))
     return ToeplitzPosterior(ptr, x.n, p, out.value, m)
+
+
+def toeplitz_posterior_missing(fx: "FiniteGP", y, blocked: bool = False) -> ToeplitzPosterior:
+    """toeplitz_posterior(fx, y) for data with holes: NaN in y means missing, by the rules and refusals of toeplitz_logpdf_missing
+    (DESIGN.md 4.22 "Posterior handle for gappy grids").  post.mean_and_var(xs) (and mean, var, marginals) fill the gap exactly: the
+    mean from a corrected alpha, the variance as that of complete data plus a correction from the rows of T^-1 K* at the k points
+    with a NaN, one more GEMM on the matrix cores and a triangular solve with the stored factor of the k x k matrix M.  post.k is k;
+    post.logpdf is bitwise toeplitz_logpdf_missing(fx, y, blocked).  Without NaN the handle is toeplitz_posterior's (post.k == 0,
+    every result bitwise).  Memory beyond the 3 n doubles per latent: rup(k, 128)^2 doubles per latent for the factored M, 4.3 GB
+    for 32 latents at the cap k = lmm_toeplitz_missing_max_k() = 4096.  rand, predictive_logpdf and mean_and_var_vjp are not served
+    on a handle with k > 0 (NotImplementedError)."""
+    y = _toeplitz_args(fx, y, "toeplitz_posterior_missing")
+    f, x = fx.f, fx.x
+    L.ensure_init()
+    _, gps = _gps_arg(f.f)
+    Ua, Sa, p, m = _H_args(f.H)
+    ptr, out, k = C.c_void_p(), C.c_double(), C.c_int()
+    lib = L.load()
+    L.check(lib.lmm_oilmm_toeplitz_posterior_create_missing(L.Arr(x.x.reshape(-1)).ptr, x.n, L.Arr(y).ptr, p, Ua.ptr, Sa.ptr, m, float(fx.sigma2),
+                                                            gps, 0, m, C.byref(ptr), C.byref(out), int(blocked)))
+    post = ToeplitzPosterior(ptr, x.n, p, out.value, m)
+    L.check(lib.lmm_toeplitz_post_gap_k(ptr, C.byref(k)))
+    post.k = k.value
+    return post
 
 
 def _toeplitz_rand_args(what: str, n: int, N, horizon, jitter):
